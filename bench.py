@@ -6,7 +6,7 @@ GPU, bf16 MFMA with fp32 accumulate -> LR input [4,1,32,32] fp32 in [0,255], out
 One "step" = one forward of that batch through the HIP engine, inputs already resident in HBM.
 Synthetic data; reference-style random init of the full 12-RDG architecture (27.38 M params).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU, every rank runs its own batch (image-parallel, no data-path
@@ -488,10 +488,12 @@ def drn_train_leg(args, torch, dev):
         loss = drn_train_step(m, duals, lrs, hr, opt, dopts)
     torch.cuda.synchronize()
     dt_eager = (time.perf_counter() - t0) / steps
-    # the step as the Trainer runs it on one GPU with '1*L1': one hipGraph per step (train.GraphedDrnTrainStep).  Counter
-    # passes set SRAD_BENCH_NO_STEP_GRAPH: rocprofv3 --pmc segfaulted (host side, deep recursion) instantiating this ~2000-node
-    # graph, and the per-kernel counters are those of the eager launches anyway.
-    graphed = not os.environ.get("SRAD_BENCH_NO_STEP_GRAPH")
+    # the step as the Trainer runs it on one GPU with '1*L1': one hipGraph per step (train.GraphedDrnTrainStep) - opt-in here
+    # (SRAD_BENCH_DRN_STEP_GRAPH=1).  A warm-up replay of this ~2000-node graph segfaulted on the host side, inside the graph
+    # launch, in a bench run as an unprivileged user (the eager steps above had run); the cause is not established, and a
+    # segfault would take the whole bench line with it.  rocprofv3 --pmc had also segfaulted (host side, deep recursion)
+    # instantiating it; counter passes set SRAD_BENCH_NO_STEP_GRAPH, which still wins.
+    graphed = bool(os.environ.get("SRAD_BENCH_DRN_STEP_GRAPH")) and not os.environ.get("SRAD_BENCH_NO_STEP_GRAPH")
     dt = dt_eager
     if graphed:
         gstep = GraphedDrnTrainStep(m, duals, opt, dopts, warmup=1)
@@ -533,7 +535,13 @@ def parse_args(argv=None):
     ap.add_argument("--train-steps", type=int, default=10)
     ap.add_argument("--only", default="", choices=["", "c3", "c4", "c5", "drn_train", "scorer"],
                     help="run ONE secondary leg and print its object (the program of the per-leg counter passes, tools/pmc_passes.sh)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the SR output of the last timed step as DIR/sr.npy (float32; one "
+                         "DIR/sr_rank<r>.npy per rank when N > 1) so that two builds can be compared output for output")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def rank_plan(args, env=None):
@@ -641,6 +649,30 @@ def arm_train_watchdog(result, rank, limit_s, linger_s=5.0):
     return guard
 
 
+DUMP_BUDGET_BYTES = 64 << 20          # --dump-outputs: every file of one run together
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: each tensor of `arrays` as <out_dir>/<name>.npy in float32; returns {name: saved shape}.  A tensor too
+    large for its share of `budget` keeps a fixed, seeded sample of its leading-axis items (batch images) in index order, and
+    the sampled indices go beside it as <name>_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (budget - 4096) // max(1, len(arrays))     # (4 KB: the .npy headers)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        item = a.nbytes // max(1, a.shape[0])
+        if a.nbytes > share:
+            k = max(1, share // (item + 8))
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))
+            a = a[keep]
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), keep.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def run_rank(args):
     import torch
     import torch.distributed as dist
@@ -692,6 +724,9 @@ def run_rank(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs:               # y: what the last timed step returned (a fresh tensor per call, later legs leave it alone)
+        dumped = dump_outputs(args.dump_outputs, {"sr" if world == 1 else f"sr_rank{rank}": y}, DUMP_BUDGET_BYTES // world)
     hr_px = B * H * s * W * s
     value = n_gpus * hr_px * args.steps / elapsed / 1e6
 
@@ -714,6 +749,8 @@ def run_rank(args):
                    "hipgraph": bool(opt.use_graph),
                    "ranks": f"{world} process(es), one per GPU" + (f", backend {dist.get_backend()} (RCCL)" if world > 1 else "")},
     }
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
     if not args.no_train:
         guard = None

@@ -391,6 +391,32 @@ def test_bench_gpus_flag_builds_a_two_rank_launch():
     assert bench.rank_plan(args, env={"WORLD_SIZE": "2", "RANK": "0"}) == []          # already a rank of torch.distributed.run
 
 
+def test_bench_dump_outputs_writes_float32_within_the_budget(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's output as DIR/<name>.npy in float32; an output larger than the
+    budget keeps the same seeded sample of its batch images on every run, with the indices beside it.  --steps 0 is refused."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse_args(["--steps", "7", "--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    y = torch.arange(4 * 128 * 128, dtype=torch.float32).reshape(4, 1, 128, 128)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"sr": y}) == {"sr": [4, 1, 128, 128]}
+    got = np.load(tmp_path / "a" / "sr.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.numpy())
+    big = torch.arange(64 * 1 * 32 * 32, dtype=torch.float64).reshape(64, 1, 32, 32)   # 512 KB against a 128 KB budget
+    for d in ("b", "c"):
+        shapes = bench.dump_outputs(str(tmp_path / d), {"sr": big}, budget=128 << 10)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 128 << 10
+    keep = np.load(tmp_path / "b" / "sr_index.npy")
+    got = np.load(tmp_path / "b" / "sr.npy")
+    assert shapes == {"sr": list(got.shape)} and got.dtype == np.float32 and got.shape[0] == keep.size > 0
+    assert np.all(np.diff(keep) > 0) and np.array_equal(got, big.numpy()[keep.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(keep, np.load(tmp_path / "c" / "sr_index.npy"))
+
+
 def test_checkpoint_writes_what_the_evaluator_parses(tmp_path):
     """Checkpoint (src/checkpoint.py:10-28,53-58): config.txt as 'key: value' lines after a timestamp, log.txt appended
     by write_log; evaluate.infer_from_run_dir (src/evaluate.py:84-118) reads model / class / resolution / scale back."""

@@ -7,7 +7,7 @@
 #          default bench line (which quotes the counter summaries found under profiles/) -> gpurun_out/<round>_bench.json
 set -e -o pipefail
 R=${1:-r03}; WHAT=${2:-pmc}
-ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd "$ROOT"
 if [ "$WHAT" = pmc ]; then
   shift; shift || true

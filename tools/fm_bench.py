@@ -1,5 +1,5 @@
 import ctypes as C, os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from srad_amd import _lib as L
 dev = torch.device("cuda:0")
 for M in (4096, 8192):

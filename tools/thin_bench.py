@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo/tools")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.argv = [sys.argv[0], "bf16", "8192"]
 import gemm_bench as G
 import torch
