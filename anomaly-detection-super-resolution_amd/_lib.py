@@ -109,6 +109,9 @@ _SIG = {
                                     _P, C.c_size_t, _P]),
     "srad_loss_backward": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P,
                                      _P, C.c_float, _P, C.c_int, _P, C.c_size_t, _P]),
+    # reference paths for tests
+    "srad_set_path_override": (C.c_int, [C.c_int, C.c_int]),
+    "srad_get_path_override": (C.c_int, [C.c_int]),
     # event profiler
     "srad_prof_enable": (C.c_int, [C.c_int]),
     "srad_prof_num_classes": (C.c_int, []),

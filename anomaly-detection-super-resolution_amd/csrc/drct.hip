@@ -104,14 +104,13 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
         a.out = w.attn; a.out_h = mlp_fused && !x3 ? attn_h : nullptr; a.ld_out = d;
         a.split = x3; a.w_qkv_lo = h->pt.frag_lo_ptr(sw.qkv.w);
         a.B = B; a.H = H; a.W = W; a.shift = sw.shift; a.d = d; a.heads = sw.heads;
-        a.no_xcd_map = srad_no_xcd_map();
         SRAD_TRY(srad_launch_qkv_attn(a, s));
       } else {
       // norm1 + qkv                                   (drct.py:477, 278)
         // (64 x 64 windows, bf16: the GEMM leaves q | k | v as the bf16 operands the attention's MFMAs take)
         float qscale = 1.f;
         const bool qkv_bf16 = srad_window_attn_bf16_in(prec, c.window_size, sw.shift, d, sw.heads, &qscale);
-        if (qkv_bf16 && h->pt.frag_ptr(sw.qkv.w) && srad_ln_qkv_supported(prec, T, d, sw.heads) && getenv("SRAD_NO_LN_QKV") == nullptr) {
+        if (qkv_bf16 && h->pt.frag_ptr(sw.qkv.w) && srad_ln_qkv_supported(prec, T, d, sw.heads) && !srad_path_override(SRAD_PATH_QKV_VIA_GEMM)) {
           // one launch, 64 rows per workgroup against the whole weight (kernels_fused_attn.hip ln_qkv_kernel)
           LnQkvParams q{};
           q.x = cur; q.ldx = D; q.M = T; q.d = d; q.heads = sw.heads; q.ln_g = h->pt.fptr(sw.n1g); q.ln_b = h->pt.fptr(sw.n1b);
@@ -119,7 +118,7 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
           q.qkv_h = reinterpret_cast<__bf16*>(w.qkv); q.hdp = hdp_of(d, sw.heads); q.qscale = qscale;
           SRAD_TRY(srad_launch_ln_qkv(q, s));
         } else if (x3 && c.window_size == 64 && h->pt.frag_ptr(sw.qkv.w) && h->pt.frag_lo_ptr(sw.qkv.w) && srad_ln_qkv_supported(prec, T, d, sw.heads) &&
-                   getenv("SRAD_NO_LN_QKV") == nullptr) {
+                   !srad_path_override(SRAD_PATH_QKV_VIA_GEMM)) {
           // split-bf16: the same launch with hi + lo planes and packs, fp32 q | k | v out (the split attention kernel scales and splits them)
           LnQkvParams q{};
           q.x = cur; q.ldx = D; q.M = T; q.d = d; q.heads = sw.heads; q.ln_g = h->pt.fptr(sw.n1g); q.ln_b = h->pt.fptr(sw.n1b);
@@ -158,7 +157,6 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
         q.ln_g = h->pt.fptr(sw.n2g); q.ln_b = h->pt.fptr(sw.n2b); q.dbg = 0;
         if (k < 4) { q.act = SRAD_ACT_LRELU; q.slope = 0.2f; q.alpha = 1.f; q.R = nullptr; q.ldr = 0; q.Y = cur; q.ldy = D; q.yoff = d; }
         else { q.act = SRAD_ACT_NONE; q.slope = 0.f; q.alpha = 0.2f; q.R = cur; q.ldr = D; q.Y = nxt; q.ldy = D; q.yoff = 0; }
-        q.no_xcd_map = srad_no_xcd_map();
         SRAD_TRY(srad_launch_mlp_block(q, s));
         continue;
       }
@@ -251,7 +249,7 @@ int srad_drct_create(const srad_drct_config* cfg, srad_drct_t** out) {
   if (!h) return srad_set_error(SRAD_ERR_NOMEM, "drct_create: out of host memory");
   h->cfg = *cfg;
   h->pt.prec = cfg->precision;
-  h->fuse_mlp = getenv("SRAD_NO_FUSE") == nullptr;
+  h->fuse_mlp = !srad_path_override(SRAD_PATH_UNFUSED_BLOCKS);
   const int E = cfg->embed_dim, C = cfg->in_chans, ws = cfg->window_size, F = cfg->num_feat;
   h->conv_first = h->pt.add_layer("conv_first", E, C, 9, true);
   h->pe_g = h->pt.add_raw("patch_embed.norm.weight", E);
@@ -305,8 +303,6 @@ int srad_drct_create(const srad_drct_config* cfg, srad_drct_t** out) {
 void srad_drct_destroy(srad_drct_t* h) {
   if (!h) return;
   h->gc.reset();
-  for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
-  if (h->side) (void)hipStreamDestroy(h->side);
   delete h;
 }
 

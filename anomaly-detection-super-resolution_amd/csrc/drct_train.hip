@@ -103,7 +103,7 @@ void geom(WgradParams& p, int H, int W) { p.Hi = p.Ho = H; p.Wi = p.Wo = W; }
 
 // Which kernels a Swin block's backward takes, and with them the storage form of what the forward saves for it.  The
 // training forward and the backward both ask here (same inputs -> same answer); the forward records what it saved and the
-// backward refuses a mismatch (SRAD_NO_FUSE changing between the two).
+// backward refuses a mismatch (the unfused_blocks path override changing between the two).
 struct BlockPlan {
   bool xh;         // fused forward (qkv_attn + mlp_block): LN1(x), attention output, LN2(.), GELU(.), block output saved as bf16
   bool fuse_mlp;   // mlp_bwd: fc2 / fc1 data gradients + LayerNorm2 backward in one launch
@@ -121,7 +121,7 @@ BlockPlan plan_block(const srad_drct* h, const SwinW& sw, int H, int W, int T, i
   const TrainState& ts = h->ts;
   // (windows other than 8 x 8 - the 32 / 64 / 256 px presets of src/main.py:218-219,286 - take the unfused forward, so they take
   // the unfused backward with it: fp32 saves, the general attention backward kernel)
-  const bool fused_bwd = prec == SRAD_PREC_BF16 && c.window_size == 8 && getenv("SRAD_NO_FUSE") == nullptr;
+  const bool fused_bwd = prec == SRAD_PREC_BF16 && c.window_size == 8 && !srad_path_override(SRAD_PATH_UNFUSED_BLOCKS);
   auto tf = [&](int w) { return !ts.tf_off.empty() && ts.tf_off[w] >= 0; };
   BlockPlan b{};
   b.xh = h->fuse_mlp && srad_qkv_attn_supported(prec, c.window_size, H, W, d, sw.heads) && srad_mlp_block_supported(prec, T, d, sw.hidden, KA);
@@ -130,8 +130,7 @@ BlockPlan plan_block(const srad_drct* h, const SwinW& sw, int H, int W, int T, i
   b.fuse_adj = b.fuse_mlp && tf(sw.adjust.w) && srad_mlp_bwd_supported(prec, T, d, sw.hidden, KA);
   b.fuse_qkv = fused_bwd && tf(sw.qkv.w) && srad_lin_ln_bwd_supported(prec, T, 3 * d, d);
   b.yh_qkv = b.xh && b.fuse_qkv;
-  b.attn_h = b.xh && b.fuse_proj && b.yh_qkv && srad_mlp_bwd_bf16_out(T) && hd <= 128 && c.window_size == 8 &&
-             getenv("SRAD_ATTN_BWD_F32IO") == nullptr;
+  b.attn_h = b.xh && b.fuse_proj && b.yh_qkv && srad_mlp_bwd_bf16_out(T) && hd <= 128 && c.window_size == 8;
   b.yh_dh = b.xh && b.fuse_mlp && srad_mlp_bwd_bf16_out(T);    // (dO: bf16 per head for the all-bf16 attention backward, else fp32)
   b.yh_dx2 = b.yh_dh && b.fuse_adj;
   return b;
@@ -267,7 +266,6 @@ int srad_drct_forward_train(srad_drct_t* h, const float* x, int B, int H, int W,
         h->saved_h[bi] = (char)((bp.attn_h ? 1 : 0) | (bp.yh_dh ? 2 : 0));
         if (bp.attn_h) { a.save_qkv_h = reinterpret_cast<__bf16*>(sv.qkv); a.hp_h = attn_hp(sw); }   // as the MFMA took them
         else a.save_qkv = sv.qkv;
-        a.no_xcd_map = srad_no_xcd_map();
         SRAD_TRY(srad_launch_qkv_attn(a, s));
         MlpBlockParams q{};
         q.attn_h = reinterpret_cast<const __bf16*>(sv.attn); q.ld_attn = d; q.shortcut = cur; q.ld_short = D;
@@ -283,7 +281,6 @@ int srad_drct_forward_train(srad_drct_t* h, const float* x, int B, int H, int W,
         q.save_xn2_h = reinterpret_cast<__bf16*>(sv.xn2); q.save_hact_h = reinterpret_cast<__bf16*>(sv.hact); q.save_x2_h = reinterpret_cast<__bf16*>(sv.x2);
         if (k < 4) { q.act = SRAD_ACT_LRELU; q.slope = 0.2f; q.alpha = 1.f; q.Y = cur; q.ldy = D; q.yoff = d; }
         else { q.act = SRAD_ACT_NONE; q.alpha = 0.2f; q.R = cur; q.ldr = D; q.Y = nxt; q.ldy = D; q.yoff = 0; }
-        q.no_xcd_map = srad_no_xcd_map();
         SRAD_TRY(srad_launch_mlp_block(q, s));
         continue;
       }
@@ -375,42 +372,14 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
   WgradQueue wq = train_wgrad_queue(h->ts);   // split-K partials of the weight gradients, reduced once per Swin block
   // Two streams: the data-gradient chain (each kernel needs the previous one's output) stays on the caller's stream;
   // the weight gradients, which nothing in the backward waits for, run on a side stream and fill the idle CUs.
-  // Set SRAD_BWD_ONE_STREAM=1 to keep everything on the caller's stream.
-  static const bool one_stream = getenv("SRAD_BWD_ONE_STREAM") != nullptr;
-  // (bf16 mode: which fused backward kernels a block takes is plan_block's decision; SRAD_NO_FUSE=1: separate launches)
+  // (bf16 mode: which fused backward kernels a block takes is plan_block's decision)
   // (default priority: a low-priority side stream gained nothing here, and a process that had created one ran later
   //  hipGraph replays of other models at half speed - measured with bench.py's C3 leg)
-  if (!one_stream && !h->side) SRAD_CHECK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-  hipStream_t side = one_stream ? s : h->side;
-  size_t ev_next = 0;
-  auto next_event = [&](hipEvent_t* out) -> int {
-    if (ev_next == h->events.size()) {
-      hipEvent_t ev = nullptr;
-      SRAD_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      h->events.push_back(ev);
-    }
-    *out = h->events[ev_next++];
-    return SRAD_OK;
-  };
-  auto side_waits_main = [&]() -> int {          // everything enqueued on the caller's stream so far is visible to the side stream
-    if (side == s) return SRAD_OK;
-    hipEvent_t ev;
-    SRAD_TRY(next_event(&ev));
-    SRAD_CHECK_HIP(hipEventRecord(ev, s));
-    SRAD_CHECK_HIP(hipStreamWaitEvent(side, ev, 0));
-    return SRAD_OK;
-  };
-  auto main_waits_side = [&]() -> int {
-    if (side == s) return SRAD_OK;
-    hipEvent_t ev;
-    SRAD_TRY(next_event(&ev));
-    SRAD_CHECK_HIP(hipEventRecord(ev, side));
-    SRAD_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
-    return SRAD_OK;
-  };
+  BwdStreams& bs = h->bwd;
+  SRAD_TRY(bs.begin(s));
+  hipStream_t side = bs.side;
   const size_t wq_half = wq.ws_floats / 2;
   float* const wq_base = wq.ws;
-  hipEvent_t side_done[2] = {nullptr, nullptr};    // side stream finished block n - 2 / n - 1 (their temporaries are free)
   int blk_count = 0;
 
   // dLoss/d(outn) = dy / img_range, NCHW -> NHWC (pad channels zero)           (drct.py:897)
@@ -486,11 +455,11 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
         const int saved = bi < (int)h->saved_h.size() ? h->saved_h[bi] : 0;
         if (xh && saved != ((attn_h ? 1 : 0) | (yh_dh ? 2 : 0)))
           return srad_set_error(SRAD_ERR_STATE, "drct_backward: block %d was saved by the forward for other backward kernels than this call "
-                                "takes (q|k|v %s, fc1 pre-activation %s): SRAD_NO_FUSE / SRAD_ATTN_BWD_F32IO must not change between the two",
+                                "takes (q|k|v %s, fc1 pre-activation %s): the unfused_blocks path override must not change between the two",
                                 bi, (saved & 1) ? "bf16" : "fp32", (saved & 2) ? "bf16" : "fp32");
       }
       const int set = blk_count & 1;                       // temporaries + partial workspace of this block
-      if (side != s && side_done[set]) SRAD_CHECK_HIP(hipStreamWaitEvent(s, side_done[set], 0));   // block n - 2 fully consumed
+      SRAD_TRY(bs.main_waits_set(set));                   // block n - 2 fully consumed
       wq.ws = wq_base + (size_t)set * wq_half; wq.ws_floats = wq_half;
       float *dx2 = w.dx2[set], *dx1 = w.dx1[set], *dh = w.dh[set], *dqkv = w.dqkv[set];
       // with the adjust prologue fused the dx2 buffer only holds the bf16 copy (its first half): dx1 * rs1 as bf16 goes behind it
@@ -550,7 +519,6 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
         if (fuse_proj) { mb.w_projt = h->ts.tarena + h->ts.tf_off[sw.proj.w]; mb.rs1 = ks1; mb.rps = HW; mb.dO = w.dO; }
         if (fuse_proj && attn_h) { mb.dO_h = reinterpret_cast<__bf16*>(w.dO); mb.dO_heads = sw.heads; mb.dO_hp = attn_hp(sw); }
         if (yh_dx1) mb.dx1s_h = dx1s_h;
-        mb.no_xcd_map = srad_no_xcd_map();
         SRAD_TRY(srad_launch_mlp_bwd(mb, wq, s));
       } else {
         {
@@ -589,7 +557,6 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
                         sw.shift, d, sw.heads, hdp};
         if (yh_qkv) a.dqkv_h = reinterpret_cast<__bf16*>(dqkv);
         if (attn_h) { a.qkv_h = reinterpret_cast<const __bf16*>(sv.qkv); a.dout_h = reinterpret_cast<const __bf16*>(w.dO); a.hp_h = attn_hp(sw); }
-        a.no_xcd_map = srad_no_xcd_map();
         SRAD_TRY(srad_launch_window_attn_bwd(prec, a, wq, s));
       }
       {
@@ -604,7 +571,6 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
         lb.x = cur; lb.ldx = D; lb.ln_g = h->pt.fptr(sw.n1g); lb.dres = dx1; lb.ld_dres = d;
         lb.out = gc; lb.ld_out = D; lb.accumulate = 1;
         lb.dgamma = G + h->ts.flat_off[sw.n1g]; lb.dbeta = G + h->ts.flat_off[sw.n1b];
-        lb.no_xcd_map = srad_no_xcd_map();
         SRAD_TRY(srad_launch_lin_ln_bwd(lb, wq, s));
       } else {
         {
@@ -622,16 +588,13 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
       }
       // this block's five weight gradients as ONE launch on the side stream (all their operands exist now), then
       // the reduce of their partials and of the LayerNorm / bias-table column sums the caller's stream has written
-      SRAD_TRY(side_waits_main());
+      SRAD_TRY(bs.side_waits_main());
       SRAD_TRY(srad_wgrad_launch_deferred(prec, wq, side));
       SRAD_TRY(srad_wgrad_flush(wq, side));
-      if (side != s) {
-        SRAD_TRY(next_event(&side_done[set]));
-        SRAD_CHECK_HIP(hipEventRecord(side_done[set], side));
-      }
+      SRAD_TRY(bs.set_done(set));
       ++blk_count;
     }
-    SRAD_TRY(main_waits_side());                         // the RDG's gradients are final on the caller's stream
+    SRAD_TRY(bs.main_waits_side());                         // the RDG's gradients are final on the caller's stream
     float* t = gn; gn = gc; gc = t;
     if (on_bucket) on_bucket(user, c.n_rdg - i);
   }

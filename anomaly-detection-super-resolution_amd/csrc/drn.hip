@@ -332,9 +332,8 @@ __global__ __launch_bounds__(256) void ca_scale_add_kernel(const float* __restri
 
 // can the conv's epilogue write the pool's partial rows (GemmParams::pool_part)?  Rows per image then, else 0
 inline int pool_rows_per_image(int prec, const GemmParams& p, int hw) {
-  static const bool off = getenv("SRAD_DRN_NO_POOL_FUSE") != nullptr;
   const int bm = srad_gemm_tile_rows(prec, p);
-  if (off || bm < 64 || hw % bm != 0 || hw / bm > DRN_POOL_MAXCHUNKS) return 0;
+  if (bm < 64 || hw % bm != 0 || hw / bm > DRN_POOL_MAXCHUNKS) return 0;
   return hw / bm;
 }
 
@@ -342,9 +341,7 @@ inline int pool_rows_per_image(int prec, const GemmParams& p, int hw) {
 // kernel, their weight gradients on the nine-tap kernel, the pool sums from the conv's epilogue.  Decided from the shape
 // alone so that the forward and the backward agree; every launch re-checks its kernel's own predicate.
 inline bool drn_level_bf16(int prec, int B, int Hl, int Wl, int ch) {
-  static const bool off = getenv("SRAD_DRN_CHAIN_F32") || getenv("SRAD_NO_CONV80") || getenv("SRAD_NO_WGRAD_CONV9") ||
-                          getenv("SRAD_DRN_NO_POOL_FUSE") || getenv("SRAD_DRN_T_F32");
-  if (off || prec != SRAD_PREC_BF16 || ch != 80 || Hl % 4 || Wl % 32) return false;
+  if (prec != SRAD_PREC_BF16 || ch != 80 || Hl % 4 || Wl % 32) return false;
   const size_t M = (size_t)B * Hl * Wl;
   const int hw = Hl * Wl;
   return M >= 128 * 64 && M * 80 < ((size_t)1 << 31) && hw % 128 == 0 && hw / 128 <= DRN_POOL_MAXCHUNKS;
@@ -353,12 +350,11 @@ inline bool drn_level_bf16(int prec, int B, int Hl, int Wl, int ch) {
 inline int ca_slices(int hw) { return hw >= 128 * 128 ? 128 : (hw >= 1024 ? 64 : (hw >= 64 ? 8 : 1)); }
 
 // ca_scale_add_kernel's instance for the operand storage (r / x / y as bf16) and the slice size: 5 or 10 items per thread wait in
-// registers over the gate chain, larger slices take the loop (SRAD_DRN_CA_NO_PRELOAD: always the loop)
+// registers over the gate chain, larger slices take the loop
 template <class... A>
 inline void launch_ca_scale_add(bool r_h, bool x_h, bool y_h, int slices, int B, int hw, int C, hipStream_t s, A... args) {
-  static const bool no_pre = getenv("SRAD_DRN_CA_NO_PRELOAD") != nullptr;
   const int items = ((hw + slices - 1) / slices) * (C / 4);
-  const int ni = no_pre || items > 2560 ? 0 : (items <= 1280 ? 5 : 10);
+  const int ni = items > 2560 ? 0 : (items <= 1280 ? 5 : 10);
   const dim3 grid(slices, B);
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, args...); };
   auto by_ni = [&](auto RH, auto XH, auto YH) {
@@ -400,8 +396,7 @@ struct srad_drn {
   std::vector<ConvW> tail;                      // phase + 1
   GraphCache gc;
   TrainState ts;                                // training (second half of this file)
-  hipStream_t side = nullptr;                   // weight gradients of the RCAB chain run here, beside the data-gradient chain
-  std::vector<hipEvent_t> events;
+  BwdStreams bwd;                               // the weight gradients of the RCAB chains run on its side stream
 };
 
 namespace {
@@ -533,7 +528,6 @@ int forward_body(srad_drn* h, const float* x, int B, int H, int W, float* const*
     // bf16 along the chain (bf16 mode, both convolutions on conv80, pool sums from the conv's epilogue): relu(conv), the conv
     // result AND the chain tensor between the blocks are bf16 arrays - every pass of the chain is bandwidth-side work, and the
     // MFMA operands are bf16 anyway.  The level's input and its last block's output (the generic GEMMs' operands) stay fp32.
-    static const bool chain_f32 = getenv("SRAD_DRN_CHAIN_F32") != nullptr;
     bool x_h = false;                                          // xin is a bf16 array
     for (int b = 0; b < c.n_blocks; ++b) {
       const RcabW& r = h->rcab[idx][b];
@@ -543,7 +537,7 @@ int forward_body(srad_drn* h, const float* x, int B, int H, int W, float* const*
         if (x_h) p.Xh = reinterpret_cast<const __bf16*>(xin);
         p.act = SRAD_ACT_RELU;
         GemmParams q = conv_params(h, r.c1, w.rt, ch, B, Hl, Wl, 1, w.rr, ch, 0);
-        t_bf16 = srad_conv80_supported(prec, p) && srad_conv80_supported(prec, q) && getenv("SRAD_DRN_T_F32") == nullptr;
+        t_bf16 = srad_conv80_supported(prec, p) && srad_conv80_supported(prec, q);
         SRAD_REQUIRE(t_bf16 || !x_h, "drn_forward: the bf16 chain tensor needs the 80-channel conv kernel");
         if (t_bf16) p.Yh = reinterpret_cast<__bf16*>(w.rt);
         SRAD_TRY(srad_launch_gemm(prec, p, s));
@@ -567,7 +561,7 @@ int forward_body(srad_drn* h, const float* x, int B, int H, int W, float* const*
       }
       const bool r_h = t_bf16 && nchunk_fused;
       SRAD_REQUIRE(r_h || !x_h, "drn_forward: the bf16 chain tensor needs the conv epilogue's pool sums");
-      const bool y_h = r_h && !chain_f32 && b + 1 < c.n_blocks;   // the next block's conv80 reads it (same shape: supported there too)
+      const bool y_h = r_h && b + 1 < c.n_blocks;   // the next block's conv80 reads it (same shape: supported there too)
       {  // the gate, and res = body(x) * gate + x               (drn.py:128-139, 156-157)
         SradProfScope prof(s, SRAD_K_MISC, 2.0 * T * ch, (double)((r_h ? 2 : 4) + (x_h ? 2 : 4) + (y_h ? 2 : 4)) * T * ch);
         launch_ca_scale_add(r_h, x_h, y_h, ca_slices(Hl * Wl), B, Hl * Wl, ch, s, (const float*)w.pool, nchunk, 1.0f / (float)(Hl * Wl), ch, ch / 16,
@@ -676,8 +670,6 @@ int srad_drn_create(const srad_drn_config* cfg, srad_drn_t** out) {
 void srad_drn_destroy(srad_drn_t* h) {
   if (!h) return;
   h->gc.reset();
-  for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
-  if (h->side) (void)hipStreamDestroy(h->side);
   delete h;
 }
 
@@ -1401,31 +1393,11 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
   // Two streams for the RCAB chains (160 of the 170 convolutions): the data-gradient chain stays on the caller's stream, the
   // two weight gradients of a block and their reduce run on a side stream while the next block's chain proceeds (dr / dt
   // and the split-K workspace are double-buffered; a block waits for the side work of the block two before it).
-  // SRAD_BWD_ONE_STREAM=1 keeps everything on the caller's stream.
-  static const bool one_stream = getenv("SRAD_BWD_ONE_STREAM") != nullptr;
-  if (!one_stream && !h->side) SRAD_CHECK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-  hipStream_t side = one_stream ? s : h->side;
-  size_t ev_next = 0;
-  auto next_event = [&](hipEvent_t* out) -> int {
-    if (ev_next == h->events.size()) {
-      hipEvent_t ev = nullptr;
-      SRAD_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      h->events.push_back(ev);
-    }
-    *out = h->events[ev_next++];
-    return SRAD_OK;
-  };
-  auto a_waits_b = [&](hipStream_t a, hipStream_t b) -> int {
-    if (a == b) return SRAD_OK;
-    hipEvent_t ev = nullptr;
-    SRAD_TRY(next_event(&ev));
-    SRAD_CHECK_HIP(hipEventRecord(ev, b));
-    SRAD_CHECK_HIP(hipStreamWaitEvent(a, ev, 0));
-    return SRAD_OK;
-  };
+  BwdStreams& bs = h->bwd;
+  SRAD_TRY(bs.begin(s));
+  hipStream_t side = bs.side;
   float* const wq_base = wq.ws;
   const size_t wq_half = wq.ws_floats / 2;
-  hipEvent_t side_done[2] = {nullptr, nullptr};
   int blk_count = 0;
 
   for (int L = 0; L < P; ++L) SRAD_CHECK_HIP(hipMemsetAsync(w.gcat[L], 0, (T0 >> (2 * L)) * 2 * fw(L) * sizeof(float), s));
@@ -1499,7 +1471,7 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
       const float* xin = b == 0 ? x0 : w.rc[idx][b - 1].xo;
       const int ldin = b == 0 ? ld0 : ch;
       const int set = blk_count & 1;
-      if (side != s && side_done[set]) SRAD_CHECK_HIP(hipStreamWaitEvent(s, side_done[set], 0));   // block n - 2 fully consumed
+      SRAD_TRY(bs.main_waits_set(set));                       // block n - 2 fully consumed
       float* dr = w.dr2[set];
       float* dt = w.dt2[set];
       const bool x_h = lh && b > 0;                            // this block's input is the previous block's bf16 output
@@ -1507,10 +1479,9 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
       if (lh) hipLaunchKernelGGL(pool_dot_kernel<true>, dim3(DRN_POOL_CHUNKS, B), dim3(256), 0, s, ga, sv.r, pp, Hl * Wl, ch, DRN_POOL_CHUNKS);
       else hipLaunchKernelGGL(pool_dot_kernel<false>, dim3(DRN_POOL_CHUNKS, B), dim3(256), 0, s, ga, sv.r, pp, Hl * Wl, ch, DRN_POOL_CHUNKS);
       {
-        static const bool no_pre = getenv("SRAD_DRN_CA_NO_PRELOAD") != nullptr;
         const int slices = ca_slices(Hl * Wl);
         const int items = ((Hl * Wl + slices - 1) / slices) * (ch / 4);
-        const int ni = no_pre || items > 2560 ? 0 : (items <= 1280 ? 5 : 10);
+        const int ni = items > 2560 ? 0 : (items <= 1280 ? 5 : 10);
         const dim3 grid(slices, B);
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, ga, sv.gate, pp, DRN_POOL_CHUNKS, sv.pool, 1.0f / (float)(Hl * Wl), ch, ch / 16,
@@ -1534,7 +1505,7 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       // both weight gradients of the block + their reduce on the side stream (dr and dt exist now)
-      SRAD_TRY(a_waits_b(side, s));
+      SRAD_TRY(bs.side_waits_main());
       wq.ws = wq_base + (size_t)set * wq_half; wq.ws_floats = wq_half;
       // the channel attention's weight / bias gradients (one workgroup, all images): nothing on the data path waits for them
       hipLaunchKernelGGL(ca_bwd_kernel, dim3(1), dim3(256), 0, side, pp, DRN_POOL_CHUNKS, sv.pool, sv.gate, 1.0f / (float)(Hl * Wl), B,
@@ -1552,10 +1523,7 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
         SRAD_TRY(srad_launch_wgrad(prec, g0, wq, side));
         SRAD_TRY(srad_wgrad_flush(wq, side));
       }
-      if (side != s) {
-        SRAD_TRY(next_event(&side_done[set]));
-        SRAD_CHECK_HIP(hipEventRecord(side_done[set], side));
-      }
+      SRAD_TRY(bs.set_done(set));
       {
         GemmParams p = drn_dgrad(h, r.c0, dt, ch, B, Hl, Wl, gb, ch, 0);
         p.R = ga; p.ldr = ch;                                                        // + the skip path
@@ -1565,7 +1533,7 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
       float* t = ga; ga = gb; gb = t;
       ++blk_count;
     }
-    SRAD_TRY(a_waits_b(s, side));                           // the chain's weight gradients are final on the caller's stream
+    SRAD_TRY(bs.main_waits_side());                         // the chain's weight gradients are final on the caller's stream
     wq.ws = wq_base; wq.ws_floats = 2 * wq_half;
     // gradient of the chain's input: deep (idx 0) or the concat buffer of this level
     float* GX = idx == 0 ? w.gdeep : w.gcat[lvl];

@@ -458,40 +458,32 @@ int launch_attn(const AttnParams& p, hipStream_t stream) {
   constexpr int PLANES = PREC == SRAD_PREC_BF16X3 ? 2 : 1;
   size_t base = (size_t)((BQ + 128) * HS) * sizeof(T) * PLANES + (2 * BQ + 6 * 64) * sizeof(int);
   base = srad_align_up(base, 16);
-  const int tbl_in_lds = (base + (size_t)tw * tw * 4) <= 150 * 1024 ? 1 : 0;
-  size_t lds = base + (tbl_in_lds ? (size_t)tw * tw * 4 : 0);
-  const int full = N % 64 == 0 ? 1 : 0;
-  auto kern = tbl_in_lds ? (full ? window_attn_kernel<PREC, NT_O, true, NW, true> : window_attn_kernel<PREC, NT_O, true, NW, false>)
-                         : (full ? window_attn_kernel<PREC, NT_O, false, NW, true> : window_attn_kernel<PREC, NT_O, false, NW, false>);
+  const bool tbl_in_lds = base + (size_t)tw * tw * 4 <= 150 * 1024;
+  const size_t lds = base + (tbl_in_lds ? (size_t)tw * tw * 4 : 0);
+  const bool full = N % 64 == 0;
   // 64 x 64 windows with a shift of 0 or 32 (what DRCT builds: window_size // 2): the one-row-per-chunk path
   const bool row64 = PREC != SRAD_PREC_F32 && NW == 8 && p.ws == 64 && base + (size_t)4 * 128 * 4 <= 158 * 1024 &&
-                     (p.shift == 0 || p.shift == 32) && getenv("SRAD_NO_ROW64") == nullptr;
+                     (p.shift == 0 || p.shift == 32);
   SRAD_REQUIRE(!p.qkv_h || (row64 && (p.d / p.heads) % 4 != 0 && ((uintptr_t)p.qkv_h & 7) == 0),
                "window_attn: bf16 q | k | v are for the 64 x 64-window bf16 path (srad_window_attn_bf16_in)");
-  if constexpr (PREC == SRAD_PREC_BF16 && NW == 8) {
-    if (row64) {
-      kern = p.qkv_h ? window_attn_kernel<PREC, NT_O, true, NW, true, true, true> : window_attn_kernel<PREC, NT_O, true, NW, true, true>;
-      lds = base + (size_t)4 * 128 * 4;            // a four-row ring of the bias table
-    }
-  }
-  if constexpr (PREC == SRAD_PREC_BF16X3 && NW == 8) {
-    if (row64) {
-      kern = window_attn_kernel<PREC, NT_O, true, NW, true, true>;
-      lds = base + (size_t)4 * 128 * 4;
-    }
-  }
-  static size_t configured_dev[16][6] = {};          // per device (hipFuncSetAttribute applies to the current one)
-  size_t (&configured)[6] = configured_dev[srad_device_slot()];
-  const int slot = row64 ? (p.qkv_h ? 5 : 4) : tbl_in_lds * 2 + full;
-  if (lds > configured[slot]) {
-    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured[slot] = lds;
-  }
   const int nW = (p.H / p.ws) * (p.W / p.ws);
-  dim3 grid((N + BQ - 1) / BQ, p.heads, p.B * nW);
+  const dim3 grid((N + BQ - 1) / BQ, p.heads, p.B * nW), block(NW * 64);
   const double Ttok = (double)p.B * p.H * p.W;
   SradProfScope prof(stream, SRAD_K_ATTN, 4.0 * Ttok * N * p.d, 4.0 * Ttok * 4 * p.d);   // q,k,v read + out written
-  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, stream, p);
+  if constexpr (PREC != SRAD_PREC_F32 && NW == 8) {
+    if (row64) {
+      const size_t ring = base + (size_t)4 * 128 * 4;            // a four-row ring of the bias table
+      if constexpr (PREC == SRAD_PREC_BF16)
+        if (p.qkv_h) SRAD_TRY((srad_launch_dyn<window_attn_kernel<PREC, NT_O, true, NW, true, true, true>>(grid, block, ring, stream, p)));
+      if (!p.qkv_h) SRAD_TRY((srad_launch_dyn<window_attn_kernel<PREC, NT_O, true, NW, true, true>>(grid, block, ring, stream, p)));
+      SRAD_CHECK_HIP(hipGetLastError());
+      return SRAD_OK;
+    }
+  }
+  if (tbl_in_lds) SRAD_TRY((full ? srad_launch_dyn<window_attn_kernel<PREC, NT_O, true, NW, true>>(grid, block, lds, stream, p)
+                                : srad_launch_dyn<window_attn_kernel<PREC, NT_O, true, NW, false>>(grid, block, lds, stream, p)));
+  else SRAD_TRY((full ? srad_launch_dyn<window_attn_kernel<PREC, NT_O, false, NW, true>>(grid, block, lds, stream, p)
+                     : srad_launch_dyn<window_attn_kernel<PREC, NT_O, false, NW, false>>(grid, block, lds, stream, p)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
@@ -527,7 +519,7 @@ bool srad_window_attn_bf16_in(int prec, int ws, int shift, int d, int heads, flo
   // the conditions of launch_attn's one-row-per-chunk path (its table ring always fits), plus a spare column for V's ones
   const int hd = heads > 0 ? d / heads : 0;
   const bool ok = prec == SRAD_PREC_BF16 && ws == 64 && (shift == 0 || shift == 32) && hd > 0 && hd <= 128 && hd % 4 != 0 &&
-                  getenv("SRAD_NO_ROW64") == nullptr && getenv("SRAD_ATTN_F32IN") == nullptr;
+                  !srad_path_override(SRAD_PATH_ATTN_F32_IN);
   if (ok && qscale) *qscale = (1.0f / sqrtf((float)hd)) * 1.4426950408889634f;
   return ok;
 }

@@ -903,7 +903,6 @@ int plan_wgrad(const WgradParams& p, WgradQueue& q, hipStream_t s, WgradPlan& pl
   if (target > kmax) target = kmax;
   long ksplit = 1;
   while (ksplit * 2 <= kmax && ksplit * 10 <= target * 7) ksplit *= 2;      // nearest power of two (rounding up from 1.43x)
-  if (const char* e = getenv("SRAD_WGRAD_KSPLIT")) ksplit = atoi(e) > 0 ? atoi(e) : ksplit;   // tools/: timing experiments
   {  // drop empty splits: rows_per is rounded up to whole steps
     const long rows_per = ((p.M + ksplit - 1) / ksplit + 4 * KR - 1) / (4 * KR) * (4 * KR);
     ksplit = (p.M + rows_per - 1) / rows_per;
@@ -968,17 +967,9 @@ int launch_wgrad80(const WgradParams& p, WgradQueue& q, hipStream_t s) {
     q.tiles += square_reduce_tiles(it, 80);
   }
   SradProfScope prof(s, SRAD_K_WGRAD, 2.0 * p.M * 80.0 * 80.0 * p.ntaps, 4.0 * p.M * 160.0 + 8.0 * 6400.0 * p.ntaps);
-  auto launch = [&](auto kern) -> int {
-    static SradOncePerDevice configured;
-    if (configured.need()) {
-      SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)W80_LDS));
-      configured.done();
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.ntaps * ksplit)), dim3(256), W80_LDS, s, p, (int)ksplit, part);
-    return SRAD_OK;
-  };
-  const int rc = p.ntaps == 9 ? launch(wgrad80_kernel<true>) : launch(wgrad80_kernel<false>);
-  if (rc) return rc;
+  const dim3 grid((unsigned)(p.ntaps * ksplit));
+  SRAD_TRY(p.ntaps == 9 ? srad_launch_dyn<wgrad80_kernel<true>>(grid, dim3(256), W80_LDS, s, p, (int)ksplit, part)
+                        : srad_launch_dyn<wgrad80_kernel<false>>(grid, dim3(256), W80_LDS, s, p, (int)ksplit, part));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
@@ -987,7 +978,7 @@ int launch_wgrad80(const WgradParams& p, WgradQueue& q, hipStream_t s) {
 static bool conv9_supported(const WgradParams& p) {
   if (p.ntaps != 9 || p.stride != 1 || p.N != p.Cin || p.n_real != p.N || p.cin_real != p.Cin || p.N > 80 || (p.N & 3) || p.row_scale ||
       ((p.x_bf16 || p.dy_bf16) && !(p.N == 80 && p.dy_bf16)) || p.Hi != p.Ho || p.Wi != p.Wo || (p.Wo % WC9_TW) || (p.ldy & 3) || (p.ldx & 3) || (p.ycol0 & 3) ||
-      (size_t)p.M < 8192 || (size_t)p.M * (size_t)std::max(p.ldy, p.ldx) >= ((size_t)1 << 31) || getenv("SRAD_NO_WGRAD_CONV9") != nullptr)
+      (size_t)p.M < 8192 || (size_t)p.M * (size_t)std::max(p.ldy, p.ldx) >= ((size_t)1 << 31))
     return false;
   return ((reinterpret_cast<uintptr_t>(p.dY) | reinterpret_cast<uintptr_t>(p.X)) & 15) == 0;
 }
@@ -998,10 +989,7 @@ int launch_wgrad_conv9(const WgradParams& p, WgradQueue& q, hipStream_t s) {
   const int nchunks = B * ((p.Ho + WC9_TR - 1) / WC9_TR) * (p.Wo / WC9_TW);
   // workgroups: a 128-pixel tile costs ~2 us, a workgroup ~6 us of ramp plus its partial tiles (9 C^2 floats written and
   // read again): ~4 sqrt(tiles) workgroups balance the two (64 for 256 tiles, 128 for 1024)
-  double kmul = 4.0;
-  if (const char* e = getenv("SRAD_CONV9_KMUL")) kmul = atof(e) > 0 ? atof(e) : kmul;          // tools/: timing experiments
-  int ksplit = (int)(kmul * sqrt((double)nchunks) + 0.5);
-  if (const char* e = getenv("SRAD_WGRAD_KSPLIT")) ksplit = atoi(e) > 0 ? atoi(e) : ksplit;   // tools/: timing experiments
+  int ksplit = (int)(4.0 * sqrt((double)nchunks) + 0.5);
   ksplit = std::max(1, std::min(std::min(ksplit, 256), nchunks));
   const int cpw = (nchunks + ksplit - 1) / ksplit;
   ksplit = (nchunks + cpw - 1) / cpw;
@@ -1019,28 +1007,17 @@ int launch_wgrad_conv9(const WgradParams& p, WgradQueue& q, hipStream_t s) {
   it.ksplit = ksplit; it.tile0 = q.tiles; it.alpha = p.alpha;
   q.tiles += square_reduce_tiles(it, C);
   SradProfScope prof(s, SRAD_K_WGRAD, 2.0 * p.M * C * C * 9.0, (double)p.M * C * ((p.dy_bf16 ? 2 : 4) + (p.x_bf16 ? 2 : 4)) + 8.0 * 9.0 * PART * ksplit);
-  auto launch = [&](auto kern, const size_t lds, SradOncePerDevice& configured) -> int {
-    if (configured.need()) {
-      SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured.done();
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)ksplit), dim3(WC9S_THREADS), lds, s, p, cpw, nchunks, ksplit, part);
-    return SRAD_OK;
-  };
-  static SradOncePerDevice cfg[6], cfg_h[2];
-  int rc = SRAD_OK;
-  if (p.dy_bf16) {                                              // 80 channels only (conv9_supported): DRN's bf16 training chain
-    rc = p.x_bf16 ? launch(wgrad_conv9_kernel<5, true, true>, Wc9<5>::LDS, cfg_h[1]) : launch(wgrad_conv9_kernel<5, true, false>, Wc9<5>::LDS, cfg_h[0]);
-    if (rc) return rc;
-    SRAD_CHECK_HIP(hipGetLastError());
-    return SRAD_OK;
-  }
-  switch (nt) {
-    case 1: rc = launch(wgrad_conv9_kernel<1>, Wc9<1>::LDS, cfg[1]); break;
-    case 2: rc = launch(wgrad_conv9_kernel<2>, Wc9<2>::LDS, cfg[2]); break;
-    case 3: rc = launch(wgrad_conv9_kernel<3>, Wc9<3>::LDS, cfg[3]); break;
-    case 4: rc = launch(wgrad_conv9_kernel<4>, Wc9<4>::LDS, cfg[4]); break;
-    default: rc = launch(wgrad_conv9_kernel<5>, Wc9<5>::LDS, cfg[5]); break;
+  const dim3 grid((unsigned)ksplit), block(WC9S_THREADS);
+  int rc;
+  if (p.dy_bf16)                                                // 80 channels only (conv9_supported): DRN's bf16 training chain
+    rc = p.x_bf16 ? srad_launch_dyn<wgrad_conv9_kernel<5, true, true>>(grid, block, Wc9<5>::LDS, s, p, cpw, nchunks, ksplit, part)
+                  : srad_launch_dyn<wgrad_conv9_kernel<5, true, false>>(grid, block, Wc9<5>::LDS, s, p, cpw, nchunks, ksplit, part);
+  else switch (nt) {
+    case 1: rc = srad_launch_dyn<wgrad_conv9_kernel<1>>(grid, block, Wc9<1>::LDS, s, p, cpw, nchunks, ksplit, part); break;
+    case 2: rc = srad_launch_dyn<wgrad_conv9_kernel<2>>(grid, block, Wc9<2>::LDS, s, p, cpw, nchunks, ksplit, part); break;
+    case 3: rc = srad_launch_dyn<wgrad_conv9_kernel<3>>(grid, block, Wc9<3>::LDS, s, p, cpw, nchunks, ksplit, part); break;
+    case 4: rc = srad_launch_dyn<wgrad_conv9_kernel<4>>(grid, block, Wc9<4>::LDS, s, p, cpw, nchunks, ksplit, part); break;
+    default: rc = srad_launch_dyn<wgrad_conv9_kernel<5>>(grid, block, Wc9<5>::LDS, s, p, cpw, nchunks, ksplit, part); break;
   }
   if (rc) return rc;
   SRAD_CHECK_HIP(hipGetLastError());
@@ -1051,7 +1028,7 @@ template <int PREC>
 int launch_wgrad(const WgradParams& p, WgradQueue& q, hipStream_t s) {
   if (PREC == SRAD_PREC_BF16 && conv9_supported(p)) return launch_wgrad_conv9(p, q, s);
   if (PREC == SRAD_PREC_BF16 && p.N == 80 && p.Cin == 80 && p.n_real == 80 && p.cin_real == 80 && p.stride == 1 && !p.row_scale &&
-      (p.ntaps == 1 || (p.Hi == p.Ho && p.Wi == p.Wo)) && getenv("SRAD_NO_WGRAD80") == nullptr)
+      (p.ntaps == 1 || (p.Hi == p.Ho && p.Wi == p.Wo)))
     return launch_wgrad80(p, q, s);
   const bool conv = p.ntaps == 9 || p.stride != 1;
   WgradPlan pl;
@@ -1059,17 +1036,8 @@ int launch_wgrad(const WgradParams& p, WgradQueue& q, hipStream_t s) {
   dim3 grid((unsigned)(pl.tiles * pl.ksplit));
   const double K = (double)p.ntaps * p.cin_real;
   SradProfScope prof(s, SRAD_K_WGRAD, 2.0 * p.M * p.n_real * K, 4.0 * p.M * ((double)p.N + p.Cin) + 8.0 * p.n_real * K);
-  auto launch = [&](auto kern) -> int {
-    static SradOncePerDevice configured;
-    if (configured.need()) {
-      SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS));
-      configured.done();
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), WG_LDS, s, p, pl.ksplit, pl.tn, pl.tc, pl.part);
-    return SRAD_OK;
-  };
-  const int rc = conv ? launch(wgrad_kernel<PREC, true>) : launch(wgrad_kernel<PREC, false>);
-  if (rc) return rc;
+  SRAD_TRY((conv ? srad_launch_dyn<wgrad_kernel<PREC, true>>(grid, dim3(256), WG_LDS, s, p, pl.ksplit, pl.tn, pl.tc, pl.part)
+                : srad_launch_dyn<wgrad_kernel<PREC, false>>(grid, dim3(256), WG_LDS, s, p, pl.ksplit, pl.tn, pl.tc, pl.part)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
@@ -2212,15 +2180,6 @@ int srad_wgrad_launch_deferred(int prec, WgradQueue& q, hipStream_t stream) {
   const int total = m.blk0[m.count - 1] + m.nblk[m.count - 1];
   {
     SradProfScope prof(stream, SRAD_K_WGRAD, q.multi_flops, q.multi_bytes);
-    auto launch = [&](auto kern) -> int {
-      static SradOncePerDevice configured;
-      if (configured.need()) {
-        SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS));
-        configured.done();
-      }
-      hipLaunchKernelGGL(kern, dim3(total), dim3(256), WG_LDS, stream, m);
-      return SRAD_OK;
-    };
     bool full = prec == SRAD_PREC_BF16;            // every layer: whole 128-row steps, DropPath factor constant per wave step
     for (int i = 0; i < m.count && full; ++i) {
       const long rows_per = ((m.p[i].M + m.ksplit[i] - 1) / m.ksplit[i] + 127) / 128 * 128;
@@ -2231,20 +2190,11 @@ int srad_wgrad_launch_deferred(int prec, WgradQueue& q, hipStream_t stream) {
                    "wgrad: bf16 operand storage needs the bf16 MFMA path, dY only together with X");
     bool all_hh = full;                                // every layer with both operands as bf16: the lean kernel
     for (int i = 0; i < m.count && all_hh; ++i) all_hh = m.p[i].x_bf16 && m.p[i].dy_bf16;
-    static const bool no_hh = getenv("SRAD_WGRAD_NO_HH") != nullptr;
-    if (all_hh && !no_hh) {
-      static SradOncePerDevice configured_hh;
-      if (configured_hh.need()) {
-        SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_multi_hh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS2));
-        configured_hh.done();
-      }
-      hipLaunchKernelGGL(wgrad_multi_hh_kernel, dim3(total), dim3(256), WG_LDS2, stream, m);
-    } else {
-      const int rc = prec != SRAD_PREC_BF16 ? launch(wgrad_multi_kernel<SRAD_PREC_F32, false>)
-                     : full                 ? launch(wgrad_multi_kernel<SRAD_PREC_BF16, true>)
-                                            : launch(wgrad_multi_kernel<SRAD_PREC_BF16, false>);
-      if (rc) return rc;
-    }
+    const dim3 grid(total), block(256);
+    SRAD_TRY((all_hh                    ? srad_launch_dyn<wgrad_multi_hh_kernel>(grid, block, WG_LDS2, stream, m)
+             : prec != SRAD_PREC_BF16 ? srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_F32, false>>(grid, block, WG_LDS, stream, m)
+             : full                   ? srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_BF16, true>>(grid, block, WG_LDS, stream, m)
+                                      : srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_BF16, false>>(grid, block, WG_LDS, stream, m)));
     SRAD_CHECK_HIP(hipGetLastError());
   }
   m.count = 0; q.multi_flops = 0; q.multi_bytes = 0;
@@ -2335,19 +2285,11 @@ static int launch_attn_bwd_gen(const AttnBwdParams& p, WgradQueue& q, hipStream_
   const double T = (double)p.B * p.H * p.W;
   SradProfScope prof(stream, SRAD_K_ATTN_BWD, 10.0 * T * p.ws * p.ws * p.d, 4.0 * T * 8 * p.d);
   const int nb = (p.ws * p.ws + 63) / 64;
-  auto go = [&](auto kern, size_t lds) -> int {
-    static SradOncePerDevice configured;                    // (one per kernel instance)
-    if (configured.need()) {
-      SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured.done();
-    }
-    hipLaunchKernelGGL(kern, dim3(nwin * p.heads), dim3(256), lds, stream, p, tpart);
-    return SRAD_OK;
-  };
-  if (nb == 1) SRAD_TRY(go(window_attn_bwd_gen_kernel<1>, ABG_LDS(1)));
-  else if (nb == 2) SRAD_TRY(go(window_attn_bwd_gen_kernel<2>, ABG_LDS(2)));
-  else if (nb == 3) SRAD_TRY(go(window_attn_bwd_gen_kernel<3>, ABG_LDS(3)));
-  else SRAD_TRY(go(window_attn_bwd_gen_kernel<4>, ABG_LDS(4)));
+  const dim3 grid(nwin * p.heads), block(256);
+  if (nb == 1) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<1>>(grid, block, ABG_LDS(1), stream, p, tpart));
+  else if (nb == 2) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<2>>(grid, block, ABG_LDS(2), stream, p, tpart));
+  else if (nb == 3) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<3>>(grid, block, ABG_LDS(3), stream, p, tpart));
+  else SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<4>>(grid, block, ABG_LDS(4), stream, p, tpart));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
@@ -2359,12 +2301,6 @@ int srad_launch_window_attn_bwd(int prec, const AttnBwdParams& p, WgradQueue& q,
   if (p.ws != 8) return launch_attn_bwd_gen(p, q, stream);
   SRAD_REQUIRE(p.d % p.heads == 0 && p.hdp % 4 == 0 && p.hdp >= p.d / p.heads, "window_attn_bwd: bad head geometry");
   SRAD_REQUIRE(p.shift >= 0 && p.shift < p.ws, "window_attn_bwd: bad shift %d", p.shift);
-  static SradOncePerDevice configured;
-  if (configured.need()) {
-    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_bwd_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)AB_LDS));
-    configured.done();
-  }
   const int nW = (p.H / p.ws) * (p.W / p.ws);
   const double T = (double)p.B * p.H * p.W;
   const int ncols = 225 * p.heads, nwin = p.B * nW;
@@ -2375,35 +2311,21 @@ int srad_launch_window_attn_bwd(int prec, const AttnBwdParams& p, WgradQueue& q,
   q.used += need;
   SRAD_TRY(queue_colsum(q, p.dtable, tpart, ncols, ncols, nwin, 1.f, stream));
   SradProfScope prof(stream, SRAD_K_ATTN_BWD, 10.0 * T * 64 * p.d, 4.0 * T * 8 * p.d);
+  const dim3 grid(p.B * nW * p.heads), block(256);
   if (prec == SRAD_PREC_BF16 && p.qkv_h) {
     const int hd = p.d / p.heads;
     SRAD_REQUIRE(p.dout_h && p.dqkv_h && hd <= 128 && p.hp_h % 8 == 0 && p.hp_h >= hd && p.hp_h <= 128 &&
                      (((uintptr_t)p.qkv_h | (uintptr_t)p.dout_h) & 15) == 0,
                  "window_attn_bwd: the all-bf16 form takes head dims <= 128 in 16-byte aligned slots of hp columns, and writes bf16");
-    auto go = [&](auto kern, size_t lds) -> int {
-      static SradOncePerDevice configured;                  // (one per instantiation of this lambda = per kernel instance)
-      if (configured.need()) {
-        SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured.done();
-      }
-      hipLaunchKernelGGL(kern, dim3(p.B * nW * p.heads), dim3(256), lds, stream, p, tpart);
-      return SRAD_OK;
-    };
     const int nch = (hd + 31) / 32;
-    if (nch == 1) SRAD_TRY(go(window_attn_bwd_h_kernel<1>, ag_lds_bytes<1>()));
-    else if (nch == 2) SRAD_TRY(go(window_attn_bwd_h_kernel<2>, ag_lds_bytes<2>()));
-    else if (nch == 3) SRAD_TRY(go(window_attn_bwd_h_kernel<3>, ag_lds_bytes<3>()));
-    else SRAD_TRY(go(window_attn_bwd_h_kernel<4>, ag_lds_bytes<4>()));
+    if (nch == 1) SRAD_TRY(srad_launch_dyn<window_attn_bwd_h_kernel<1>>(grid, block, ag_lds_bytes<1>(), stream, p, tpart));
+    else if (nch == 2) SRAD_TRY(srad_launch_dyn<window_attn_bwd_h_kernel<2>>(grid, block, ag_lds_bytes<2>(), stream, p, tpart));
+    else if (nch == 3) SRAD_TRY(srad_launch_dyn<window_attn_bwd_h_kernel<3>>(grid, block, ag_lds_bytes<3>(), stream, p, tpart));
+    else SRAD_TRY(srad_launch_dyn<window_attn_bwd_h_kernel<4>>(grid, block, ag_lds_bytes<4>(), stream, p, tpart));
   } else if (prec == SRAD_PREC_BF16) {
-    static SradOncePerDevice configured16;
-    if (configured16.need()) {
-      SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_bwd_bf16_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)AH_LDS));
-      configured16.done();
-    }
-    hipLaunchKernelGGL(window_attn_bwd_bf16_kernel, dim3(p.B * nW * p.heads), dim3(256), AH_LDS, stream, p, tpart);
+    SRAD_TRY(srad_launch_dyn<window_attn_bwd_bf16_kernel>(grid, block, AH_LDS, stream, p, tpart));
   } else {
-    hipLaunchKernelGGL(window_attn_bwd_kernel, dim3(p.B * nW * p.heads), dim3(256), AB_LDS, stream, p, tpart);
+    SRAD_TRY(srad_launch_dyn<window_attn_bwd_kernel>(grid, block, AB_LDS, stream, p, tpart));
   }
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;

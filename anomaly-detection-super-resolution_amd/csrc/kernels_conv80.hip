@@ -41,10 +41,10 @@ constexpr int C80_NT = 512;                         // threads: wave = (tile row
 constexpr int C80_NL = (C80_HCH + C80_NT - 1) / C80_NT;      // per thread
 constexpr size_t C80_LDS = (size_t)(80 * C80_WLD + C80_HH * C80_HW * C80_PLD) * sizeof(__bf16) + 4 * 80 * sizeof(float);
 
-// STAMP: diagnostic build (SRAD_C80_STAMP=1, tools/conv_bench.py): s_memtime of every wave at the phase boundaries
+// STAMP: diagnostic build (srad_op_conv80_h bit 16, tools/c80_stamps.py): s_memtime of every wave at the phase boundaries
 // RM: the residual operand - 0 none, 1 fp32 (p.R), 2 bf16 (p.Rh).  Its tile is requested BEFORE the tile's MFMAs and the bias sits
 // in registers for the kernel's lifetime: as loads inside the epilogue they were a dependent global round trip per tile, and
-// the epilogue took 4 300 of a tile's 12 300 cycles (stamps: SRAD_C80_STAMP=1).
+// the epilogue took 4 300 of a tile's 12 300 cycles (the stamp build).
 template <bool XH, int RM = 0, bool STAMP = false>
 __global__ __launch_bounds__(C80_NT) void conv80_kernel(const GemmParams p, const int ntiles, const int tiles_x, const int tiles_per_img,
                                                         unsigned long long* __restrict__ stamps = nullptr) {
@@ -326,8 +326,7 @@ __global__ __launch_bounds__(C80_NT) void conv80_kernel(const GemmParams p, cons
 }  // namespace
 
 bool srad_conv80_supported(int prec, const GemmParams& p) {
-  static const bool off = getenv("SRAD_NO_CONV80") != nullptr;
-  return !off && prec == SRAD_PREC_BF16 && p.ntaps == 9 && p.stride == 1 && p.Cin == 80 && p.N == 80 && !p.ln_g && p.ps == 0 &&
+  return prec == SRAD_PREC_BF16 && p.ntaps == 9 && p.stride == 1 && p.Cin == 80 && p.N == 80 && !p.ln_g && p.ps == 0 &&
          p.hsplit_hd == 0 && !p.row_scale && !p.Ypre && (p.act == SRAD_ACT_NONE || p.act == SRAD_ACT_RELU || p.act == SRAD_ACT_LRELU) &&   // the epilogue has no GELU: such a call stays on the tiled GEMM
          p.Hi == p.Ho && p.Wi == p.Wo && p.Hi % C80_TH == 0 && p.Wi % C80_TW == 0 &&
          ((!p.R && !p.Rh) || p.rmode == SRAD_RMODE_ADD || p.rmode == SRAD_RMODE_DLRELU) && !(p.R && p.Rh) && (p.ldx & 3) == 0 && (p.ldy & 3) == 0 &&
@@ -337,7 +336,7 @@ bool srad_conv80_supported(int prec, const GemmParams& p) {
          p.M >= 128 * 64;                                        // small launches stay on the tiled GEMM (one tile per workgroup anyway)
 }
 
-int srad_launch_conv80(const GemmParams& p, hipStream_t stream) {
+int srad_launch_conv80(const GemmParams& p, hipStream_t stream, bool stamps) {
   SRAD_REQUIRE(srad_conv80_supported(SRAD_PREC_BF16, p), "conv80: unsupported problem");
   const int tiles_x = p.Wi / C80_TW, tiles_per_img = (p.Hi / C80_TH) * tiles_x;
   const int B = p.M / (p.Hi * p.Wi), ntiles = B * tiles_per_img;
@@ -345,26 +344,18 @@ int srad_launch_conv80(const GemmParams& p, hipStream_t stream) {
   const double K = 9.0 * 80;
   SradProfScope prof(stream, SRAD_K_CONV80, 2.0 * p.M * 80 * K,
                      (double)p.M * 80 * ((p.Xh ? 2 : 4) + (p.Yh ? 2 : 4) + (p.R ? 4 : p.Rh ? 2 : 0)) + 2.0 * 80 * K);
-  static const bool stamp_build = getenv("SRAD_C80_STAMP") != nullptr;
-  auto launch = [&](auto kern, SradOncePerDevice& configured) -> int {
-    if (configured.need()) {
-      SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C80_LDS));
-      configured.done();
-    }
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(C80_NT), C80_LDS, stream, p, ntiles, tiles_x, tiles_per_img, (unsigned long long*)nullptr);
-    return SRAD_OK;
+  auto launch = [&](auto xh, auto rm) {
+    return srad_launch_dyn<conv80_kernel<decltype(xh)::value, decltype(rm)::value>>(dim3(nwg), dim3(C80_NT), C80_LDS, stream, p, ntiles,
+                                                                                   tiles_x, tiles_per_img, (unsigned long long*)nullptr);
   };
-  static SradOncePerDevice cfg[6];
   const int rm = p.R ? 1 : p.Rh ? 2 : 0;
-  if (stamp_build && p.Xh && rm == 0) {                         // diagnostic: phase stamps of every wave, medians to stderr (synchronous)
+  if (stamps) {                                                 // diagnostic: phase stamps of every wave, medians to stderr (synchronous)
+    SRAD_REQUIRE(p.Xh && rm == 0, "conv80: the stamp build takes a bf16 input and no residual");
     static unsigned long long* dbuf = nullptr;
     const size_t n = (size_t)256 * 8 * 32;
-    if (!dbuf) {
-      SRAD_CHECK_HIP(hipMalloc(&dbuf, n * sizeof(unsigned long long)));
-      SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv80_kernel<true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C80_LDS));
-    }
+    if (!dbuf) SRAD_CHECK_HIP(hipMalloc(&dbuf, n * sizeof(unsigned long long)));
     SRAD_CHECK_HIP(hipMemsetAsync(dbuf, 0, n * sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL((conv80_kernel<true, 0, true>), dim3(nwg), dim3(C80_NT), C80_LDS, stream, p, ntiles, tiles_x, tiles_per_img, dbuf);
+    SRAD_TRY((srad_launch_dyn<conv80_kernel<true, 0, true>>(dim3(nwg), dim3(C80_NT), C80_LDS, stream, p, ntiles, tiles_x, tiles_per_img, dbuf)));
     SRAD_CHECK_HIP(hipStreamSynchronize(stream));
     static int printed_small = 0, printed_big = 0;
     int& printed = ntiles <= 256 ? printed_small : printed_big;
@@ -386,10 +377,10 @@ int srad_launch_conv80(const GemmParams& p, hipStream_t stream) {
     }
     return SRAD_OK;
   }
-  int rc;
-  if (p.Xh) rc = rm == 0 ? launch(conv80_kernel<true, 0>, cfg[0]) : rm == 1 ? launch(conv80_kernel<true, 1>, cfg[1]) : launch(conv80_kernel<true, 2>, cfg[2]);
-  else rc = rm == 0 ? launch(conv80_kernel<false, 0>, cfg[3]) : rm == 1 ? launch(conv80_kernel<false, 1>, cfg[4]) : launch(conv80_kernel<false, 2>, cfg[5]);
-  if (rc) return rc;
+  using T = std::true_type; using F = std::false_type;
+  using R0 = std::integral_constant<int, 0>; using R1 = std::integral_constant<int, 1>; using R2 = std::integral_constant<int, 2>;
+  if (p.Xh) SRAD_TRY(rm == 0 ? launch(T{}, R0{}) : rm == 1 ? launch(T{}, R1{}) : launch(T{}, R2{}));
+  else SRAD_TRY(rm == 0 ? launch(F{}, R0{}) : rm == 1 ? launch(F{}, R1{}) : launch(F{}, R2{}));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

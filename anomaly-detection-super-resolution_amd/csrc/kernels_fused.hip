@@ -526,16 +526,10 @@ inline FusedCfg fused_cfg(int d, int m, int no) {
 template <int FM, int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM, bool STAMP = false, bool SPLIT = false>
 int launch_mlp_fm(const MlpBlockParams& p, hipStream_t stream) {
   constexpr size_t lds = (size_t)(FM * F_LDA + FM * F_LDH) * 2 * (SPLIT ? 2 : 1) + (F_NV + FM * 16) * sizeof(float);
-  auto kern = mlp_block_kernel<FM, GD, KGD, GM, KGM, GN, KCD, KCM, STAMP, SPLIT>;
-  static SradOncePerDevice configured;
-  if (configured.need()) {
-    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured.done();
-  }
   const double flops = 2.0 * p.M * ((double)p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
   const double bytes = 4.0 * p.M * (2.0 * p.d + p.no) + 2.0 * ((double)p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
   SradProfScope prof(stream, SRAD_K_MLP_BLOCK, flops, bytes);
-  hipLaunchKernelGGL(kern, dim3(p.M / FM), dim3(512), lds, stream, p);
+  SRAD_TRY((srad_launch_dyn<mlp_block_kernel<FM, GD, KGD, GM, KGM, GN, KCD, KCM, STAMP, SPLIT>>(dim3(p.M / FM), dim3(512), lds, stream, p)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

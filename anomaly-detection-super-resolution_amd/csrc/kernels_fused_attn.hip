@@ -450,18 +450,12 @@ int launch_qa(const QkvAttnParams& p, hipStream_t stream) {
   constexpr size_t lds = (size_t)(SPLIT ? 2 * (XN_E > QP_E ? XN_E : QP_E) : XN_E + QP_E) * 2 +
                          (size_t)(640 + 3 * HDP + 232 + 256 + 64 * QA_LDB) * sizeof(float) + 128 * sizeof(int);
   static_assert(lds <= 160 * 1024, "qkv_attn: LDS budget");
-  auto kern = qkv_attn_kernel<HDT, KC, STAMP, SPLIT>;
-  static SradOncePerDevice configured;
-  if (configured.need()) {
-    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured.done();
-  }
   const double T = (double)p.B * p.H * p.W;
   const double flops = 2.0 * T * 3.0 * p.d * p.d + 4.0 * T * 64.0 * p.d;
   const double bytes = 4.0 * T * p.d * 2 + 2.0 * 3.0 * p.d * p.d;
   SradProfScope prof(stream, SRAD_K_QKV_ATTN, flops, bytes);
   const int nW = (p.H / 8) * (p.W / 8);
-  hipLaunchKernelGGL(kern, dim3(p.B * nW, p.heads), dim3(512), lds, stream, p);
+  SRAD_TRY((srad_launch_dyn<qkv_attn_kernel<HDT, KC, STAMP, SPLIT>>(dim3(p.B * nW, p.heads), dim3(512), lds, stream, p)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
@@ -655,14 +649,8 @@ template <int HDT, int KC, int HEADS, bool SPLIT = false>
 int launch_ln_qkv(const LnQkvParams& p, hipStream_t stream) {
   constexpr size_t lds = (size_t)64 * (KC * 32 + 16) * 2 * (SPLIT ? 2 : 1) + (size_t)(640 + HEADS * 3 * 16 * HDT) * sizeof(float);
   static_assert(lds <= 160 * 1024, "ln_qkv: LDS budget");
-  auto kern = ln_qkv_kernel<HDT, KC, HEADS, SPLIT>;
-  static SradOncePerDevice configured;
-  if (configured.need()) {
-    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured.done();
-  }
   SradProfScope prof(stream, SRAD_K_LN_QKV, 2.0 * p.M * 3.0 * p.d * p.d, 4.0 * p.M * p.d + 2.0 * p.M * 3.0 * p.d + 2.0 * 3.0 * p.d * p.d);
-  hipLaunchKernelGGL(kern, dim3(p.M / 64), dim3(512), lds, stream, p);
+  SRAD_TRY((srad_launch_dyn<ln_qkv_kernel<HDT, KC, HEADS, SPLIT>>(dim3(p.M / 64), dim3(512), lds, stream, p)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

@@ -608,16 +608,11 @@ template <int FM, int GD, int KC>
 int launch_lin_fm(const LinLnBwdParams& p, WgradQueue& q, hipStream_t stream) {
   constexpr int KG = (KC + 7) / 8;
   constexpr size_t lds = (size_t)FM * (KG * 256 + 16) * 2 + (384 + FM * 16) * sizeof(float);
-  auto kern = p.dy_bf16 ? lin_ln_bwd_kernel<FM, GD, KC, true> : lin_ln_bwd_kernel<FM, GD, KC, false>;
-  static SradOncePerDevice configured[2];
-  if (configured[p.dy_bf16 ? 1 : 0].need()) {
-    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured[p.dy_bf16 ? 1 : 0].done();
-  }
   float* part = nullptr;
   SRAD_TRY(srad_wgrad_queue_ln_partials(q, p.dgamma, p.dbeta, p.d, p.M / FM, stream, &part));
   SradProfScope prof(stream, SRAD_K_MLP_BWD, 2.0 * p.M * p.K * p.d, 4.0 * p.M * ((double)p.K + 4.0 * p.d) + 2.0 * p.K * p.d);
-  hipLaunchKernelGGL(kern, dim3(p.M / FM), dim3(512), lds, stream, p, part);
+  SRAD_TRY((p.dy_bf16 ? srad_launch_dyn<lin_ln_bwd_kernel<FM, GD, KC, true>>(dim3(p.M / FM), dim3(512), lds, stream, p, part)
+                     : srad_launch_dyn<lin_ln_bwd_kernel<FM, GD, KC, false>>(dim3(p.M / FM), dim3(512), lds, stream, p, part)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
@@ -637,17 +632,11 @@ template <int FM, int GD, int KCD, int GM, int KCM, int KCA, bool HOUT = false>
 int launch_bwd_fm(const MlpBwdParams& p, WgradQueue& q, hipStream_t stream) {
   constexpr size_t lds = (size_t)(FM * FB_LDA + FM * FB_LDH) * 2 + (384 + FM * 16) * sizeof(float) +
                          (KCA > 0 ? (size_t)FM * (KCA * 32 + 16) * 2 : 0);
-  auto kern = mlp_bwd_kernel<FM, GD, KCD, GM, KCM, KCA, HOUT>;
-  static SradOncePerDevice configured;
-  if (configured.need()) {
-    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured.done();
-  }
   float* part = nullptr;
   SRAD_TRY(srad_wgrad_queue_ln_partials(q, p.dgamma, p.dbeta, p.d, p.M / FM, stream, &part));
   SradProfScope prof(stream, SRAD_K_MLP_BWD, 8.0 * p.M * p.d * p.m + (KCA > 0 ? 2.0 * p.M * p.d * p.KA : 0.0),
                      4.0 * p.M * (3.0 * p.d + 2.0 * p.m) + 4.0 * p.d * p.m);
-  hipLaunchKernelGGL(kern, dim3(p.M / FM), dim3(512), lds, stream, p, part);
+  SRAD_TRY((srad_launch_dyn<mlp_bwd_kernel<FM, GD, KCD, GM, KCM, KCA, HOUT>>(dim3(p.M / FM), dim3(512), lds, stream, p, part)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

@@ -590,12 +590,6 @@ int launch_one(const GemmParams& p, hipStream_t s) {
   constexpr size_t lds = ((size_t)BM * (CPA * 32 + PrecT<PREC>::PAD) + (size_t)BN * (CPS * 32 + PrecT<PREC>::PAD)) * sizeof(T) *
                              (PREC == SRAD_PREC_BF16X3 ? 2 : 1) +
                          (LN ? 2 * (size_t)CPA * 32 * sizeof(float) : 0);
-  auto kern = gemm_kernel<PREC, BM, BN, WMV, WNV, CPS, LN, CONV, SPECIAL>;
-  static SradOncePerDevice configured;
-  if (configured.need()) {
-    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured.done();
-  }
   // pool_part rows are summed per image by callers that size them with srad_gemm_tile_rows(): a tile choice that drifts from that
   // mirror, or an image that is not a whole number of tiles, must fail here instead of averaging the wrong rows
   if (p.pool_part)
@@ -608,8 +602,7 @@ int launch_one(const GemmParams& p, hipStream_t s) {
   const double wbytes = (double)p.N * K * (PREC == SRAD_PREC_BF16 ? 2 : 4);   // (split-bf16: two bf16 planes)
   const double abytes = 4.0 * (p.ntaps == 9 ? (double)p.M * p.stride * p.stride : (double)p.M) * p.Cin;
   SradProfScope prof(s, cls, 2.0 * p.M * p.N * K, abytes + wbytes + 4.0 * p.M * p.N * (p.R ? 2 : 1));
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
-  return SRAD_OK;
+  return srad_launch_dyn<gemm_kernel<PREC, BM, BN, WMV, WNV, CPS, LN, CONV, SPECIAL>>(grid, dim3(256), lds, s, p);
 }
 
 template <int PREC, int BM, int BN, int WMV, int WNV>
@@ -656,7 +649,7 @@ int launch_prec(const GemmParams& p, hipStream_t s) {
   if constexpr (PREC == SRAD_PREC_BF16) {
     // ... and 128 rows per workgroup once that still gives every CU one (C3: 32768 pixels -> 256 workgroups in ONE round; the
     // kernel is a chain of load -> LDS -> MFMA stages per workgroup, so twice the rows per stage cost little more per stage)
-    if (!p.ln_g && p.N > 64 && p.N <= 80 && tiles(128, 80) >= 256 && getenv("SRAD_GEMM_NO_BM128") == nullptr) return launch_cfg<PREC, 128, 80, 4, 1>(p, s);
+    if (!p.ln_g && p.N > 64 && p.N <= 80 && tiles(128, 80) >= 256) return launch_cfg<PREC, 128, 80, 4, 1>(p, s);
   }
   if (!p.ln_g && p.N > 64 && p.N <= 80 && tiles(64, 80) >= 384) return launch_cfg<PREC, 64, 80, 4, 1>(p, s);
   if (tiles(64, 64) >= 384) return launch_cfg<PREC, 64, 64, 2, 2>(p, s);
@@ -674,7 +667,7 @@ int srad_gemm_tile_rows(int prec, const GemmParams& p) {      // keep in step wi
     if (p.N <= 32 && tiles(128, 32) >= 384) return 128;
   }
   if (p.N <= 32) return 32;
-  if (prec == SRAD_PREC_BF16 && !p.ln_g && p.N > 64 && p.N <= 80 && tiles(128, 80) >= 256 && getenv("SRAD_GEMM_NO_BM128") == nullptr) return 128;
+  if (prec == SRAD_PREC_BF16 && !p.ln_g && p.N > 64 && p.N <= 80 && tiles(128, 80) >= 256) return 128;
   if (!p.ln_g && p.N > 64 && p.N <= 80 && tiles(64, 80) >= 384) return 64;
   if (tiles(64, 64) >= 384) return 64;
   return 32;
@@ -695,7 +688,7 @@ int srad_launch_gemm(int prec, const GemmParams& p, hipStream_t stream) {
   if (p.ntaps == 9 || p.stride != 1 || p.ps)
     SRAD_REQUIRE(p.Ho > 0 && p.Wo > 0 && p.M % (p.Ho * p.Wo) == 0, "gemm: M=%d not a multiple of Ho*Wo=%d*%d", p.M, p.Ho, p.Wo);
   if (srad_conv80_supported(prec, p)) return srad_launch_conv80(p, stream);
-  if (prec == SRAD_PREC_BF16 && p.ps == 2 && p.N == 320 && p.Cin == 80 && p.bias && getenv("SRAD_NO_UPCONV_SPLIT") == nullptr) {
+  if (prec == SRAD_PREC_BF16 && p.ps == 2 && p.N == 320 && p.Cin == 80 && p.bias && !srad_path_override(SRAD_PATH_UPCONV_ONE_GEMM)) {
     // DRN's Upsampler conv (80 -> 320 channels + PixelShuffle(2)): four 80 -> 80 convolutions through the weight-resident kernel,
     // one per sub-pixel position (rows 4 c + q of the pack), each writing its quarter of the 2x image - 217 us on this tiled
     // GEMM at 128 px x 8 against 4 x 26

@@ -37,9 +37,16 @@ const char* const kClassNames[SRAD_K_COUNT] = {"gemm_bn64", "gemm_bn32", "gemm_b
                                                "wgrad", "window_attn_bwd", "layernorm_bwd", "optim", "wgrad_reduce", "mlp_bwd", "ln_qkv", "conv80"};
 }  // namespace
 
-bool srad_no_xcd_map() {
-  static const bool off = getenv("SRAD_NO_XCD_MAP") != nullptr;
-  return off;
+// ---------------------------------------------------------------- path overrides (include/srad.h)
+int g_srad_path_override[SRAD_PATH_COUNT] = {};
+extern "C" int srad_set_path_override(int path, int on) {
+  SRAD_REQUIRE(path >= 0 && path < SRAD_PATH_COUNT, "set_path_override: unknown path %d", path);
+  g_srad_path_override[path] = on ? 1 : 0;
+  return SRAD_OK;
+}
+extern "C" int srad_get_path_override(int path) {
+  if (path < 0 || path >= SRAD_PATH_COUNT) return srad_set_error(-1, "get_path_override: unknown path %d", path);
+  return g_srad_path_override[path];
 }
 
 SradProfScope::SradProfScope(hipStream_t stream, int cls, double flops, double bytes) : s(stream), active(0) {

@@ -535,7 +535,7 @@ int chunk_images(int n_img, int H, int W) {
 }
 // widths the LDS-staged sweep takes (ssim_rows_lds_kernel), and the partial sums per (image, window size) either kernel writes
 inline bool lds_sweep_ok(int H, int W) {
-  return W >= 64 && W <= 1024 && (W & (W - 1)) == 0 && (long long)kQ * (H + 1) * (W + 1) * 8 < (1ll << 31) && getenv("SRAD_SCORE_NO_LDS") == nullptr;
+  return W >= 64 && W <= 1024 && (W & (W - 1)) == 0 && (long long)kQ * (H + 1) * (W + 1) * 8 < (1ll << 31);
 }
 inline int partial_slots(int H, int W) { return lds_sweep_ok(H, W) ? H : (H * W + kEvalPix - 1) / kEvalPix; }
 inline int grid1d(size_t total) {
@@ -631,21 +631,16 @@ int srad_score_pairs(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int
       {
         // algorithmic bytes per (pair, window): the two fp32 luminance planes read once
         SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W * g, 8.0 * n * H * W * g);
-        static const bool generic = getenv("SRAD_SCORE_GENERIC") != nullptr;     // A/B: the per-lane kernel for every width
         if (lds_sweep_ok(H, W)) {
           int pmin = wl.ws[0] / 2, pmax = pmin;
           for (int k = 1; k < g; ++k) { pmin = std::min(pmin, wl.ws[k] / 2); pmax = std::max(pmax, wl.ws[k] / 2); }
           const int rb = 1024 / W, t_first = -pmax, nt = H - 1 - pmin - t_first + 1, nt_blocks = (nt + rb - 1) / rb;
           const size_t lds = ((size_t)2 * kQ * rb * (W + 1) + 32) * sizeof(double);
-          static SradOncePerDevice configured;
-          if (configured.need()) {
-            SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ssim_rows_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            configured.done();
-          }
           int lw = 0;
           while ((1 << lw) < W) ++lw;
-          hipLaunchKernelGGL(ssim_rows_lds_kernel, dim3((unsigned)((size_t)nt_blocks * n)), dim3(1024), lds, s, sat, partial, H, lw, wl, g, t_first, nt_blocks);
-        } else if (W % 64 == 0 && !generic)
+          SRAD_TRY(srad_launch_dyn<ssim_rows_lds_kernel>(dim3((unsigned)((size_t)nt_blocks * n)), dim3(1024), lds, s, sat, partial, H, lw, wl, g,
+                                                         t_first, nt_blocks));
+        } else if (W % 64 == 0)
           hipLaunchKernelGGL(ssim_eval_kernel<true>, dim3((unsigned)((size_t)nblk * g * n)), dim3(256), 0, s, sat, partial, H, W, wl, nblk, g, n);
         else
           hipLaunchKernelGGL(ssim_eval_kernel<false>, dim3((unsigned)((size_t)nblk * g * n)), dim3(256), 0, s, sat, partial, H, W, wl, nblk, g, n);

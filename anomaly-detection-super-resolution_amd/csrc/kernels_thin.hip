@@ -267,8 +267,7 @@ __global__ __launch_bounds__(256) void conv_tail40_strip_kernel(const GemmParams
 }  // namespace
 
 bool srad_conv_tail_supported(int prec, const GemmParams& p) {
-  static const bool off = getenv("SRAD_NO_CONV_TAIL") != nullptr;
-  return !off && prec == SRAD_PREC_BF16 && p.ntaps == 9 && p.stride == 1 && p.Hi == p.Ho && p.Wi == p.Wo && !p.ln_g && p.ps == 0 &&
+  return prec == SRAD_PREC_BF16 && p.ntaps == 9 && p.stride == 1 && p.Hi == p.Ho && p.Wi == p.Wo && !p.ln_g && p.ps == 0 &&
          p.hsplit_hd == 0 && !p.row_scale && !p.Ypre && !p.pool_part && !p.Xh && !p.Yh && !p.Rh && p.sp_q < 0 &&
          (p.act == SRAD_ACT_NONE || p.act == SRAD_ACT_RELU || p.act == SRAD_ACT_LRELU) && (!p.R || p.rmode == SRAD_RMODE_ADD) &&
          p.N >= 1 && p.N <= 4 && (p.Cin == 40 || p.Cin == 80) && p.Cp == srad_cp(p.Cin) && (p.Wi & 15) == 0 && (p.ldx & 3) == 0 &&
@@ -283,8 +282,7 @@ int srad_launch_conv_tail(const GemmParams& p, hipStream_t stream) {
   const int cap = tiles >= 16384 ? 512 : 256;
   const int wgs = tiles / 4 < cap ? tiles / 4 : cap;
   SradProfScope prof(stream, SRAD_K_GEMM_BN16, 2.0 * p.M * p.N * 9.0 * p.Cin, 4.0 * p.M * ((double)p.Cin + p.N * (p.R ? 2 : 1)));
-  static const bool no_strip = getenv("SRAD_TAIL_NO_STRIP") != nullptr;
-  if (p.Cin == 40 && p.Hi % CT_RS == 0 && !no_strip) {
+  if (p.Cin == 40 && p.Hi % CT_RS == 0) {
     const int nstrips = tiles / CT_RS;
     const int swgs = std::max(1, std::min(nstrips / 4, 512));
     hipLaunchKernelGGL(conv_tail40_strip_kernel, dim3(swgs), dim3(256), 0, stream, p, nstrips);
@@ -295,9 +293,8 @@ int srad_launch_conv_tail(const GemmParams& p, hipStream_t stream) {
 }
 
 bool srad_conv_thin_supported(int prec, const GemmParams& p) {
-  static const bool off = getenv("SRAD_NO_CONV_THIN") != nullptr;
   const int n4 = (p.N + 3) / 4;
-  return !off && prec == SRAD_PREC_BF16 && p.ntaps == 9 && p.stride == 1 && p.Hi == p.Ho && p.Wi == p.Wo && !p.ln_g && p.ps == 0 &&
+  return prec == SRAD_PREC_BF16 && p.ntaps == 9 && p.stride == 1 && p.Hi == p.Ho && p.Wi == p.Wo && !p.ln_g && p.ps == 0 &&
          p.hsplit_hd == 0 && !p.row_scale && !p.Ypre && !p.pool_part && !p.Xh && !p.Yh && !p.Rh &&
          (p.act == SRAD_ACT_NONE || p.act == SRAD_ACT_RELU || p.act == SRAD_ACT_LRELU) && (!p.R || p.rmode == SRAD_RMODE_ADD) &&
          // few INPUT channels only: with 40 / 80 input channels and 3 outputs (the tails) this kernel is a chain of 90 - 180 dependent

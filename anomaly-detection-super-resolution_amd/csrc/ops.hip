@@ -42,6 +42,7 @@ int srad_op_gemm(int precision, const float* x, int ldx, int B, int Hi, int Wi, 
 // The 80 -> 80 channel 3x3 convolution with bf16 operands as DRN's bf16 chains issue it (conv80_kernel<XH, RM>): x_h [B*H*W][80]
 // bf16; output bf16 (y_h) or fp32 (y); residual operand bf16 (r_h) or fp32 (r) or none, rmode as GemmParams (0 add, 2 the
 // LeakyReLU / ReLU mask of a backward); optional per-tile column sums.  Fails if the shape does not take that kernel.
+// Bit 16 of `rmode`: the phase-stamp build of the kernel (bf16 input, no residual; synchronous, medians to stderr).
 int srad_op_conv80_h(const void* x_h, const float* w, const float* bias, int act, float slope, const void* r_h, const float* r,
                      int rmode, int B, int H, int W, void* y_h, float* y, float* pool_part, void* scratch, size_t scratch_bytes,
                      void* stream) {
@@ -54,9 +55,10 @@ int srad_op_conv80_h(const void* x_h, const float* w, const float* bias, int act
   p.Hi = p.Ho = H; p.Wi = p.Wo = W; p.stride = 1;
   p.Xh = reinterpret_cast<const __bf16*>(x_h); p.ldx = 80; p.M = B * H * W; p.Cin = 80; p.Cp = srad_cp(80); p.ntaps = 9; p.ln_eps = 1e-5f;
   p.Wp = scratch; p.N = 80; p.bias = bias; p.act = act; p.slope = slope; p.alpha = 1.f;
-  p.R = r; p.Rh = reinterpret_cast<const __bf16*>(r_h); p.ldr = 80; p.rmode = rmode;
+  p.R = r; p.Rh = reinterpret_cast<const __bf16*>(r_h); p.ldr = 80; p.rmode = rmode & 0xffff;
   p.Y = y; p.Yh = reinterpret_cast<__bf16*>(y_h); p.ldy = 80; p.pool_part = pool_part;
   SRAD_REQUIRE(srad_conv80_supported(SRAD_PREC_BF16, p), "op_conv80_h: this shape does not take the 80-channel conv kernel");
+  if (rmode & 0x10000) return srad_launch_conv80(p, s, true);
   return srad_launch_gemm(SRAD_PREC_BF16, p, s);
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "../../include/srad.h"
 
 #define SRAD_OK 0
 #define SRAD_ERR_ARG 1
@@ -75,14 +76,6 @@ __device__ __forceinline__ float srad_wave_sum(float v) {
   return v;
 }
 #endif
-// "dynamic LDS limit of this kernel instance is set" - per DEVICE: hipFuncSetAttribute applies to the current device only, so a
-// process that drives two devices (not how this build runs - one rank per process - but legal) configures each once.
-struct SradOncePerDevice {
-  unsigned long long mask = 0, cur = 0;
-  bool need() { int d = 0; (void)hipGetDevice(&d); cur = 1ull << (d & 63); return (mask & cur) == 0; }
-  void done() { mask |= cur; }
-};
-static inline int srad_device_slot() { int d = 0; (void)hipGetDevice(&d); return d & 15; }
 
 #define SRAD_CHECK_HIP(expr)                                                              \
   do {                                                                                    \
@@ -101,6 +94,25 @@ static inline int srad_device_slot() { int d = 0; (void)hipGetDevice(&d); return
     int _rc = (expr);             \
     if (_rc) return _rc;          \
   } while (0)
+
+// Launch of kernel instance K with `lds` bytes of dynamic LDS.  The limit is raised with hipFuncSetAttribute whenever a launch
+// asks for more than this instance was given on the current device (the attribute is per device, the state per instance).
+template <auto K, class... A>
+int srad_launch_dyn(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+  static size_t set[64] = {};
+  int d = 0;
+  (void)hipGetDevice(&d);
+  if (lds > set[d & 63]) {
+    SRAD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    set[d & 63] = lds;
+  }
+  hipLaunchKernelGGL(K, grid, block, lds, s, args...);
+  return SRAD_OK;
+}
+
+// Path overrides of include/srad.h (srad_set_path_override): a process-wide table, all off unless a test sets one
+extern int g_srad_path_override[SRAD_PATH_COUNT];
+static inline bool srad_path_override(int path) { return g_srad_path_override[path] != 0; }
 
 static inline size_t srad_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int srad_round_up(int v, int a) { return (v + a - 1) / a * a; }
@@ -168,7 +180,8 @@ int srad_launch_gemm(int prec, const GemmParams& p, hipStream_t stream);
 int srad_gemm_tile_rows(int prec, const GemmParams& p);     // rows per workgroup tile srad_launch_gemm will pick for p
 // DRN-L's 80 -> 80 channel 3x3 convolutions: weight-resident persistent kernel (kernels_conv80.hip); srad_launch_gemm routes to it
 bool srad_conv80_supported(int prec, const GemmParams& p);
-int srad_launch_conv80(const GemmParams& p, hipStream_t stream);
+// (stamps: the phase-stamp build, bf16 input without a residual; synchronous, medians to stderr - srad_op_conv80_h's bit 16 of rmode)
+int srad_launch_conv80(const GemmParams& p, hipStream_t stream, bool stamps = false);
 // 3x3 convolutions with <= 8 input or <= 4 output channels at large pixel counts (DRN's head / tails and their data gradients):
 // direct fp32 FMAs, one pixel per thread (kernels_thin.hip); routed from srad_launch_gemm in bf16 mode
 bool srad_conv_thin_supported(int prec, const GemmParams& p);
@@ -280,7 +293,6 @@ struct QkvAttnParams {
   // split-bf16 (SRAD_PREC_BF16X3; inference only): lo terms of the per-head pack (srad_launch_pack_qkv_frag_lo); the output is fp32 (`out`)
   int split; const void* w_qkv_lo;
 };
-bool srad_no_xcd_map();     // SRAD_NO_XCD_MAP=1 (read once): plain workgroup order in the Swin-block kernels, for A/B runs
 bool srad_qkv_attn_supported(int prec, int ws, int H, int W, int d, int heads);
 // LayerNorm1 + qkv Linear -> bf16 head-split q | k | v for the 64 x 64-window attention (kernels_fused_attn.hip ln_qkv_kernel)
 struct LnQkvParams {

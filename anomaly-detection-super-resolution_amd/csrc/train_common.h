@@ -18,6 +18,57 @@ struct TrainState {
   bool ready = false;
 };
 
+// The two streams of a backward: the data-gradient chain stays on the caller's stream (`main`), the weight gradients, which
+// nothing on that chain waits for, run on `side` (created on first use, default priority).  Blocks alternate between two
+// sets of temporaries, so block n waits for the side work of block n - 2 (done[n & 1]).  The events come from a pool that
+// every backward walks from its start, so each call records the same events in the same order (and a captured step graph
+// sees the same nodes).
+struct BwdStreams {
+  hipStream_t main = nullptr, side = nullptr;
+  std::vector<hipEvent_t> events;
+  size_t next = 0;
+  hipEvent_t done[2] = {nullptr, nullptr};
+  BwdStreams() = default;
+  BwdStreams(const BwdStreams&) = delete;
+  BwdStreams& operator=(const BwdStreams&) = delete;
+  ~BwdStreams() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    if (side) (void)hipStreamDestroy(side);
+  }
+  int begin(hipStream_t s) {
+    if (!side) SRAD_CHECK_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+    main = s; next = 0; done[0] = done[1] = nullptr;
+    return SRAD_OK;
+  }
+  int event(hipEvent_t* out) {
+    if (next == events.size()) {
+      hipEvent_t e = nullptr;
+      SRAD_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      events.push_back(e);
+    }
+    *out = events[next++];
+    return SRAD_OK;
+  }
+  int wait(hipStream_t waiter, hipStream_t on) {      // everything enqueued on `on` so far is visible to `waiter`
+    hipEvent_t e = nullptr;
+    SRAD_TRY(event(&e));
+    SRAD_CHECK_HIP(hipEventRecord(e, on));
+    SRAD_CHECK_HIP(hipStreamWaitEvent(waiter, e, 0));
+    return SRAD_OK;
+  }
+  int side_waits_main() { return wait(side, main); }
+  int main_waits_side() { return wait(main, side); }
+  int main_waits_set(int set) {                       // the side work of the block that last used this set is finished
+    if (done[set]) SRAD_CHECK_HIP(hipStreamWaitEvent(main, done[set], 0));
+    return SRAD_OK;
+  }
+  int set_done(int set) {                             // ... recorded after a block's side work
+    SRAD_TRY(event(&done[set]));
+    SRAD_CHECK_HIP(hipEventRecord(done[set], side));
+    return SRAD_OK;
+  }
+};
+
 struct SyncDesc {
   long long src_off;    // floats into the flat parameter buffer
   long long dst_off;    // bytes into the forward arena
@@ -264,7 +315,7 @@ inline int train_bind(const ParamTable& pt, TrainState& ts, void* train_arena, s
     if (d.nblk == 0) d.nblk = 1;
     // bf16 Linear layers go tile by tile (sync_linear_tile); the per-head q | k | v pack's padding rows are not rewritten
     // there - they are zero since the arena was packed at creation and nothing else touches them
-    if (e.packed && pt.prec == SRAD_PREC_BF16 && e.ntaps == 1 && e.grp_pad == 0 && e.cin % 4 == 0 && e.cin >= 4 && getenv("SRAD_SYNC_ELEMENTWISE") == nullptr) {
+    if (e.packed && pt.prec == SRAD_PREC_BF16 && e.ntaps == 1 && e.grp_pad == 0 && e.cin % 4 == 0 && e.cin >= 4) {
       const int ext_n = d.Np > d.tKp ? d.Np : d.tKp, ext_c = d.Cp > d.tRp ? d.Cp : d.tRp;
       d.tiled = 1; d.tile_nb = (ext_n + 63) / 64;
       d.nblk = (unsigned)(d.tile_nb * ((ext_c + 63) / 64));

@@ -2,6 +2,7 @@
 tensors on the GPU; weights are given in PyTorch layout and packed by the library."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional, Tuple
 
@@ -14,6 +15,26 @@ def _need_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise RuntimeError("srad_amd ops run on the GPU only (HIP); there is no CPU fallback")
+
+
+# include/srad.h SRAD_PATH_*: the reference paths a test can force instead of the one shape and precision pick
+PATHS = {"unfused_blocks": 0, "qkv_via_gemm": 1, "attn_f32_in": 2, "upconv_one_gemm": 3}
+
+
+@contextlib.contextmanager
+def path_override(**paths: bool):
+    """Force reference paths inside the block, e.g. ``with ops.path_override(unfused_blocks=True):``, and restore the previous
+    settings on exit.  unfused_blocks is read by the DRCT engine when it is created (forward) and at every backward."""
+    lib = L.lib()
+    ids = {name: PATHS[name] for name in paths}
+    before = {name: lib.srad_get_path_override(i) for name, i in ids.items()}
+    try:
+        for name, on in paths.items():
+            L.check(lib.srad_set_path_override(ids[name], 1 if on else 0), "set_path_override")
+        yield
+    finally:
+        for name, was in before.items():
+            L.check(lib.srad_set_path_override(ids[name], was), "set_path_override")
 
 
 def gemm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, B: int = 1, H: int = 0,

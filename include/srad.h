@@ -283,7 +283,8 @@ int srad_op_wgrad(int precision, const float* dy, int ldy, const float* x, int l
  * forward and as the data gradient of the backward: x_h [B*H*W][80] bf16; w [80][80][3][3] fp32; output bf16 (y_h) or fp32 (y);
  * residual operand bf16 (r_h) or fp32 (r) or neither; rmode 0 = add, 2 = multiply by (r > 0 ? 1 : slope) (backward through
  * ReLU / LeakyReLU); pool_part (optional): [B*H*W/128][80] column sums per 128-pixel tile.  H % 4 == 0, W % 32 == 0,
- * B*H*W >= 8192; scratch >= srad_op_gemm_scratch_bytes(SRAD_PRECISION_BF16, 80, 80, 9). */
+ * B*H*W >= 8192; scratch >= srad_op_gemm_scratch_bytes(SRAD_PRECISION_BF16, 80, 80, 9).  Bit 16 of rmode (tools/c80_stamps.py):
+ * the kernel's phase-stamp build, no residual; synchronous, per-phase medians to stderr. */
 int srad_op_conv80_h(const void* x_h, const float* w, const float* bias, int act, float slope, const void* r_h, const float* r,
                      int rmode, int B, int H, int W, void* y_h, float* y, float* pool_part, void* scratch, size_t scratch_bytes,
                      void* stream);
@@ -338,7 +339,20 @@ int srad_op_lin_ln_bwd(int M, int K, int d, const float* dY, const float* w, con
                        size_t scratch_bytes, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------ diagnostics
- * Per-kernel-class device timing with HIP events on the launch stream (bench.py's roofline numbers). */
+ * Reference paths for tests.  The library picks kernel paths from shape and precision alone; these process-wide overrides
+ * (all off at load) force the path a test compares the default one against:
+ *   SRAD_PATH_UNFUSED_BLOCKS    DRCT Swin blocks as separate launches instead of the fused block kernels (the forward reads
+ *                               it at srad_drct_create, the backward at every srad_drct_backward)
+ *   SRAD_PATH_QKV_VIA_GEMM      64 x 64 windows: LayerNorm1 + qkv through the tiled GEMM's epilogue instead of one launch
+ *   SRAD_PATH_ATTN_F32_IN       64 x 64 windows: the attention stages fp32 q | k | v itself
+ *   SRAD_PATH_UPCONV_ONE_GEMM   DRN's Upsampler conv as one tiled GEMM instead of four 80-channel convolutions
+ * srad_set_path_override returns 0, or non-zero for an unknown path; srad_get_path_override returns 0 / 1, or -1 for an
+ * unknown path. */
+enum { SRAD_PATH_UNFUSED_BLOCKS = 0, SRAD_PATH_QKV_VIA_GEMM = 1, SRAD_PATH_ATTN_F32_IN = 2, SRAD_PATH_UPCONV_ONE_GEMM = 3,
+       SRAD_PATH_COUNT = 4 };
+int srad_set_path_override(int path, int on);
+int srad_get_path_override(int path);
+/* Per-kernel-class device timing with HIP events on the launch stream (bench.py's roofline numbers). */
 int srad_prof_enable(int on);
 int srad_prof_num_classes(void);
 const char* srad_prof_class_name(int cls);

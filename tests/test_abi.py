@@ -64,6 +64,33 @@ def test_argument_errors_without_gpu():
     assert lib.srad_roc_auc(y, s, 4, C.byref(auc)) == 0 and abs(auc.value - 0.75) < 1e-15
 
 
+def test_path_overrides_ignore_the_environment():
+    """Kernel paths follow shape and precision, plus the explicit overrides of srad_set_path_override: a fresh process with
+    an old A/B switch in its environment starts with every override off; set / get round-trip; an unknown path is an error."""
+    import subprocess
+    import sys
+    child = r"""
+import ctypes as C
+from srad_amd import _lib as L, ops
+lib = L.lib()
+assert [lib.srad_get_path_override(i) for i in ops.PATHS.values()] == [0, 0, 0, 0]
+for i in ops.PATHS.values():
+    assert lib.srad_set_path_override(i, 1) == 0 and lib.srad_get_path_override(i) == 1
+    assert lib.srad_set_path_override(i, 0) == 0 and lib.srad_get_path_override(i) == 0
+with ops.path_override(unfused_blocks=True, upconv_one_gemm=True):
+    assert [lib.srad_get_path_override(i) for i in ops.PATHS.values()] == [1, 0, 0, 1]
+assert [lib.srad_get_path_override(i) for i in ops.PATHS.values()] == [0, 0, 0, 0]
+SRAD_ERR_ARG = 1
+assert lib.srad_set_path_override(len(ops.PATHS), 1) == SRAD_ERR_ARG and b"unknown path" in lib.srad_last_error()
+assert lib.srad_set_path_override(-1, 1) == SRAD_ERR_ARG
+assert lib.srad_get_path_override(len(ops.PATHS)) == -1
+print("ok")
+"""
+    env = dict(os.environ, SRAD_NO_FUSE="1", SRAD_NO_LN_QKV="1", SRAD_ATTN_F32IN="1", SRAD_NO_UPCONV_SPLIT="1")
+    r = subprocess.run([sys.executable, "-c", child], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+
+
 def test_no_cpu_fallback():
     from srad_amd import metrics, ops
     with pytest.raises(RuntimeError, match="GPU only"):

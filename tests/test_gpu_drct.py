@@ -41,15 +41,14 @@ def test_drct_fp32_matches_reference_golden(sr_golden, name):
 
 @pytest.mark.parametrize("name", DRCT_CASES)
 @pytest.mark.parametrize("fused", [True, False])
-def test_drct_split_bf16_matches_reference_golden(sr_golden, name, fused, monkeypatch):
+def test_drct_split_bf16_matches_reference_golden(sr_golden, name, fused):
     """The split-bf16 mode ("bf16x3": hi + lo operands, three bf16 MFMAs per product) is held to the fp32 mode's bar on every
     reference golden (window sizes 2 / 4 / 8 / 16, RGB, 12 RDG, the dynamic-mask path): window 8 runs the two fused block
-    kernels, the other sizes and SRAD_NO_FUSE the split GEMM + the exact-fp32 attention kernel."""
-    if not fused:
-        monkeypatch.setenv("SRAD_NO_FUSE", "1")
+    kernels, the other sizes and the unfused_blocks override the split GEMM + the exact-fp32 attention kernel."""
+    from srad_amd import ops
     cfg, sd, x, y = drct_case(sr_golden, name)
-    m = build(cfg, sd, "bf16x3")
-    with torch.no_grad():
+    with ops.path_override(unfused_blocks=not fused), torch.no_grad():
+        m = build(cfg, sd, "bf16x3")
         out = m(torch.from_numpy(x).cuda()).cpu().numpy()
     e = rel_err(out, y)
     print(name, "bf16x3", "fused" if fused else "unfused", "rel err", e)
@@ -119,15 +118,14 @@ def test_drct_errors():
         m(torch.zeros(1, 3, 32, 32, device="cuda"))
 
 
-def test_fused_mlp_block_matches_unfused_path(sr_golden, monkeypatch):
+def test_fused_mlp_block_matches_unfused_path(sr_golden):
     """bf16: the fused proj+LN2+MLP+adjust launch (kernels_fused.hip) against the four separate
     launches and against the reference fixture."""
+    from srad_amd import ops
     cfg, sd, x, y = drct_case(sr_golden, "drct_r2_rgb_x4")
     xt = torch.from_numpy(x).cuda()
-    monkeypatch.setenv("SRAD_NO_FUSE", "1")
-    with torch.no_grad():
+    with ops.path_override(unfused_blocks=True), torch.no_grad():
         unfused = build(cfg, sd, "bf16")(xt).cpu().numpy()
-    monkeypatch.delenv("SRAD_NO_FUSE")
     with torch.no_grad():
         fused = build(cfg, sd, "bf16")(xt).cpu().numpy()
     rng = float(y.max() - y.min())
@@ -153,12 +151,13 @@ def test_c5_window64_attention_geometry_matches_oracle():
     assert rel_err(out, ref) < 1e-3, rel_err(out, ref)
 
 
-def test_c5_bf16_qkv_from_the_gemm_matches_fp32_staging(monkeypatch):
+def test_c5_bf16_qkv_from_the_gemm_matches_fp32_staging():
     """64 x 64 windows, bf16: LayerNorm1 + qkv (ln_qkv_kernel, or the tiled GEMM's epilogue) write q | k | v as the bf16
     operands of the attention's MFMAs (q scaled, padding zeroed, V's ones column set) and the attention stages them as they are.  Against the same kernel staging fp32 q | k | v
-    itself (SRAD_ATTN_F32IN=1) only the odd bf16 rounding can differ (the scale is computed on the host in one, on the
+    itself (the attn_f32_in override) only the odd bf16 rounding can differ (the scale is computed on the host in one, on the
     device in the other), and against the CPU oracle it meets the bf16 bar; shifted blocks included (two windows)."""
     from oracle import sr_ref as R
+    from srad_amd import ops
     from srad_amd import spec as S
     cfg = S.DRCTConfig(in_chans=1, img_size=256, window_size=64, upscale=4, n_rdg=1)
     sd = S.synth_state(S.drct_spec(cfg), seed=64, gain=1.0, cfg=cfg)
@@ -167,12 +166,10 @@ def test_c5_bf16_qkv_from_the_gemm_matches_fp32_staging(monkeypatch):
         ref = R.drct_forward(sd, torch.from_numpy(x), cfg).numpy()
         m = build(cfg, sd, "bf16")
         new = m(torch.from_numpy(x).cuda()).cpu().numpy()
-        monkeypatch.setenv("SRAD_NO_LN_QKV", "1")              # the tiled GEMM's bf16 head-split epilogue instead of ln_qkv_kernel
-        via_gemm = m(torch.from_numpy(x).cuda()).cpu().numpy()
-        monkeypatch.delenv("SRAD_NO_LN_QKV")
-        monkeypatch.setenv("SRAD_ATTN_F32IN", "1")
-        old = m(torch.from_numpy(x).cuda()).cpu().numpy()
-        monkeypatch.delenv("SRAD_ATTN_F32IN")
+        with ops.path_override(qkv_via_gemm=True):              # the tiled GEMM's bf16 head-split epilogue instead of ln_qkv_kernel
+            via_gemm = m(torch.from_numpy(x).cuda()).cpu().numpy()
+        with ops.path_override(attn_f32_in=True):
+            old = m(torch.from_numpy(x).cuda()).cpu().numpy()
     rng = float(ref.max() - ref.min())
     print("bf16 q|k|v (ln_qkv) vs fp32 staging: max diff / range", np.abs(new - old).max() / rng, "; via the GEMM epilogue",
           np.abs(via_gemm - old).max() / rng, "; vs oracle", np.abs(new - ref).max() / rng)
@@ -180,12 +177,13 @@ def test_c5_bf16_qkv_from_the_gemm_matches_fp32_staging(monkeypatch):
     assert np.abs(new - ref).max() / rng < 6e-3          # measured 3.1e-3 of the range (1 RDG, bf16 whole model vs the fp32 oracle)
 
 
-def test_c5_split_bf16_matches_oracle_and_fp32_mode(monkeypatch):
+def test_c5_split_bf16_matches_oracle_and_fp32_mode():
     """64 x 64 windows in the split-bf16 (parity-grade) mode, round 3: the split instances of ln_qkv_kernel and of the window
     attention kernel (hi + lo bf16 planes, three MFMAs per product) in front of the split mlp_block.  1-RDG model on a 64 x 128 LR
     image against the CPU oracle at the fp32 bar, with and without the fused LayerNorm1 + qkv launch; then the full C5 shape
     (12 RDG, 65536 tokens) against the engine's fp32 mode: the parity bar of C2 (1e-3 of the range), measured values printed."""
     from oracle import sr_ref as R
+    from srad_amd import ops
     from srad_amd import spec as S
     cfg = S.DRCTConfig(in_chans=1, img_size=256, window_size=64, upscale=4, n_rdg=1)
     sd = S.synth_state(S.drct_spec(cfg), seed=64, gain=1.0, cfg=cfg)
@@ -194,9 +192,8 @@ def test_c5_split_bf16_matches_oracle_and_fp32_mode(monkeypatch):
         ref = R.drct_forward(sd, torch.from_numpy(x), cfg).numpy()
         m = build(cfg, sd, "bf16x3")
         out = m(torch.from_numpy(x).cuda()).cpu().numpy()
-        monkeypatch.setenv("SRAD_NO_LN_QKV", "1")              # LayerNorm1 + qkv through the split tiled GEMM instead
-        out_gemm = m(torch.from_numpy(x).cuda()).cpu().numpy()
-        monkeypatch.delenv("SRAD_NO_LN_QKV")
+        with ops.path_override(qkv_via_gemm=True):              # LayerNorm1 + qkv through the split tiled GEMM instead
+            out_gemm = m(torch.from_numpy(x).cuda()).cpu().numpy()
     print("C5 1-RDG split-bf16 vs oracle:", rel_err(out, ref), "; with the tiled GEMM for qkv:", rel_err(out_gemm, ref))
     assert rel_err(out, ref) < 2e-4 and rel_err(out_gemm, ref) < 2e-4
     cfg = S.DRCTConfig(in_chans=1, img_size=256, window_size=64, upscale=4, n_rdg=12)

@@ -221,12 +221,11 @@ def test_conv_pixel_shuffle(dev, prec):
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 64, 64), (3, 64, 96), (2, 128, 128)])
-def test_upsampler_conv_as_four_subpixel_convolutions(dev, B, H, W):
+def test_upsampler_conv_as_four_subpixel_convolutions_vs_override(dev, B, H, W):
     """DRN's Upsampler convolution (80 -> 320 channels + PixelShuffle(2), src/drn.py:55-81) at sizes the weight-resident kernel takes
     (round 3: four 80 -> 80 launches, one per sub-pixel position - rows 4 c + q of the packed weight and bias, outputs at pixel
     (2 y + q / 2, 2 x + q % 2)): against torch's conv2d + pixel_shuffle on bf16-rounded operands, and against the tiled GEMM's
-    pixel-shuffle epilogue (SRAD_NO_UPCONV_SPLIT is read per call)."""
-    import os
+    pixel-shuffle epilogue (the upconv_one_gemm override is read per call)."""
     from srad_amd import ops
     g = torch.Generator(device="cpu").manual_seed(B + H + W)
     bf = lambda t: t.to(torch.bfloat16).float()
@@ -239,13 +238,12 @@ def test_upsampler_conv_as_four_subpixel_convolutions(dev, B, H, W):
     y = ops.gemm(xn, w, b, B=B, H=H, W=W, pixel_shuffle=True, precision="bf16")
     torch.cuda.synchronize()
     prof = L.prof_collect()
-    os.environ["SRAD_NO_UPCONV_SPLIT"] = "1"
     try:
-        y0 = ops.gemm(xn, w, b, B=B, H=H, W=W, pixel_shuffle=True, precision="bf16")
+        with ops.path_override(upconv_one_gemm=True):
+            y0 = ops.gemm(xn, w, b, B=B, H=H, W=W, pixel_shuffle=True, precision="bf16")
         torch.cuda.synchronize()
         prof0 = L.prof_collect()
     finally:
-        del os.environ["SRAD_NO_UPCONV_SPLIT"]
         L.prof_enable(False)
     assert prof.get("conv80", {}).get("launches") == 4 and "conv80" not in prof0, (prof, prof0)     # the two paths were taken
     ref = F.pixel_shuffle(F.conv2d(x, w, b, padding=1), 2).permute(0, 2, 3, 1).reshape(-1, 80)

@@ -457,10 +457,11 @@ def test_data_parallel_step_two_ranks_equals_one_rank_on_the_full_batch():
     assert np.abs(res[0][2] - p_ref)[big].max() < 2e-5
 
 
-def test_bf16_training_fused_forward_matches_unfused(sr_golden, monkeypatch):
+def test_bf16_training_fused_forward_matches_unfused(sr_golden):
     """bf16 mode: the training forward through the two fused block kernels (with DropPath and the saved activations
-    written from inside them) against the eight-launch path (SRAD_NO_FUSE), same DropPath masks: outputs and
-    gradients agree to bf16 rounding."""
+    written from inside them) against the eight-launch path (the unfused_blocks override), same DropPath masks: outputs
+    and gradients agree to bf16 rounding."""
+    from srad_amd import ops
     name = "drct_r2_rgb_x4"
     cfg, sd, x, y = drct_case(sr_golden, name)
     hr = torch.from_numpy(sr_golden[name + "/hr"]).cuda()
@@ -469,15 +470,12 @@ def test_bf16_training_fused_forward_matches_unfused(sr_golden, monkeypatch):
     keep = (torch.floor(0.8 + torch.rand(2 * cfg.n_rdg * 5, x.shape[0], generator=gen)) / 0.8).cuda()
     outs, grads = {}, {}
     for mode in ("fused", "unfused"):
-        if mode == "unfused":
-            monkeypatch.setenv("SRAD_NO_FUSE", "1")
-        else:
-            monkeypatch.delenv("SRAD_NO_FUSE", raising=False)
-        m = build_train(cfg, sd, "bf16", drop_path_rate=0.1)
-        m.keep_scale_override = keep
-        out = m(xt)
-        F.l1_loss(out, hr).backward()
-        outs[mode], grads[mode] = out.detach().clone(), m.flat_grads.clone()
+        with ops.path_override(unfused_blocks=mode == "unfused"):
+            m = build_train(cfg, sd, "bf16", drop_path_rate=0.1)
+            m.keep_scale_override = keep
+            out = m(xt)
+            F.l1_loss(out, hr).backward()
+            outs[mode], grads[mode] = out.detach().clone(), m.flat_grads.clone()
     rng = float(outs["unfused"].max() - outs["unfused"].min())
     assert float((outs["fused"] - outs["unfused"]).abs().max()) / rng < 1e-2
     a, b = grads["fused"].double(), grads["unfused"].double()
@@ -487,10 +485,11 @@ def test_bf16_training_fused_forward_matches_unfused(sr_golden, monkeypatch):
 
 
 @pytest.mark.parametrize("batch", [2, 8])
-def test_bf16_fused_mlp_backward_matches_unfused(sr_golden, monkeypatch, batch):
+def test_bf16_fused_mlp_backward_matches_unfused(sr_golden, batch):
     """bf16 mode: the fused backward kernels - MLP branch (both data gradients + LayerNorm2 backward) and the qkv data
     gradient + LayerNorm1 backward, 16-row tiles below 8192 tokens, 32-row tiles from there - against the separate
     GEMM / LayerNorm launches, same forward, same DropPath masks."""
+    from srad_amd import ops
     name = "drct_r2_rgb_x4"
     cfg, sd, x, y = drct_case(sr_golden, name)
     reps = batch // x.shape[0]
@@ -501,20 +500,17 @@ def test_bf16_fused_mlp_backward_matches_unfused(sr_golden, monkeypatch, batch):
     keep = (torch.floor(0.8 + torch.rand(2 * cfg.n_rdg * 5, batch, generator=gen)) / 0.8).cuda()
     grads = {}
     for mode in ("fused", "unfused"):
-        monkeypatch.delenv("SRAD_NO_FUSE", raising=False)
         m = build_train(cfg, sd, "bf16", drop_path_rate=0.1)
         m.keep_scale_override = keep
-        if mode == "unfused":
-            # after the engine is built (its forward stays fused), before the forward (which saves q | k | v in the form the
-            # backward will take): only the backward changes
-            monkeypatch.setenv("SRAD_NO_FUSE", "1")
-        out = m(xt)
-        F.l1_loss(out, hr).backward()
-        torch.cuda.synchronize()
+        # on after the engine is built (its forward stays fused), before the forward (which saves q | k | v in the form the
+        # backward will take): only the backward changes
+        with ops.path_override(unfused_blocks=mode == "unfused"):
+            out = m(xt)
+            F.l1_loss(out, hr).backward()
+            torch.cuda.synchronize()
         grads[mode] = m.flat_grads.clone()
         named = {n: p.grad.clone() for n, p in m.named_parameters()}
         grads[mode + "_named"] = named
-    monkeypatch.delenv("SRAD_NO_FUSE", raising=False)
     a, b = grads["fused"].double(), grads["unfused"].double()
     cos = float((a * b).sum() / (a.norm() * b.norm()))
     worst = 0.0

@@ -17,12 +17,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--ksplit", type=int, default=0, help="override the number of row splits (SRAD_WGRAD_KSPLIT)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     B = a.batch
-    if a.ksplit:
-        os.environ["SRAD_WGRAD_KSPLIT"] = str(a.ksplit)
     for (C, px) in [(80, 64), (80, 128), (40, 128), (20, 256)]:
         M = B * px * px
         x = torch.randn(M, C, device=dev)
