@@ -102,6 +102,10 @@ _SIG = {
                                    _P, _P, _P, _P, C.c_size_t, _P]),
     "srad_val_metrics": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "srad_roc_auc": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
+    "srad_anomaly_map_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "srad_anomaly_maps": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "srad_pixel_auc_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "srad_pixel_roc_auc": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
     "srad_l1_workspace_bytes": (C.c_int, [C.POINTER(C.c_size_t)]),
     "srad_l1_loss": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     "srad_loss_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),

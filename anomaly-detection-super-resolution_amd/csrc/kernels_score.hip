@@ -707,3 +707,119 @@ int srad_l1_loss(const float* a, const float* b, int64_t n, double* out, void* w
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Per-pixel anomaly maps: 1 - the SSIM map of ONE window size (the `ssim_map` src/metrics.py:66 averages), from the same float64
+// tables and with the same per-pixel arithmetic as the sweep, but one output value per pixel and no reduction.  One thread per
+// pixel, any width; the reflection pairs of either axis are skipped by wave-uniform branches when no lane of the wave needs them.
+namespace {
+
+__global__ __launch_bounds__(256) void ssim_map_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W, int ws,
+                                                       double dinv, int nblk) {
+  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
+  const int npix = H * W, pad = ws / 2;
+  const int p = pb * 256 + (int)threadIdx.x;
+  const int pix = min(p, npix - 1);                                      // lanes past the end compute a copy of the last pixel
+  const int i = pix / W, j = pix - i * W;
+  const int iper = W + 1;
+  const size_t plane = (size_t)(H + 1) * iper;
+  const double* const S = sat + (size_t)img * kQ * plane;
+  int ri[6], ci[6];
+  axis_pairs(i - pad, i + ws - 1 - pad, H, ri);
+  axis_pairs(j - pad, j + ws - 1 - pad, W, ci);
+  const bool row_lo = __builtin_amdgcn_ballot_w64(i - pad < 0) != 0, row_hi = __builtin_amdgcn_ballot_w64(i + ws - 1 - pad > H - 1) != 0;
+  const bool col_lo = __builtin_amdgcn_ballot_w64(j - pad < 0) != 0, col_hi = __builtin_amdgcn_ballot_w64(j + ws - 1 - pad > W - 1) != 0;
+  double sum[kQ] = {0, 0, 0, 0, 0};
+  auto row_pair = [&](auto RP) __attribute__((always_inline)) {
+    constexpr int rp = decltype(RP)::value;
+    const int oa = ri[2 * rp] * iper, ob = ri[2 * rp + 1] * iper;
+    auto col_pair = [&](auto CP) __attribute__((always_inline)) {
+      constexpr int cp = decltype(CP)::value;
+      double va[kQ], vb[kQ], vc[kQ], vd[kQ];
+#pragma unroll
+      for (int q = 0; q < kQ; ++q) {
+        const double* Sq = S + (size_t)q * plane;
+        va[q] = Sq[oa + ci[2 * cp]]; vb[q] = Sq[oa + ci[2 * cp + 1]];
+        vc[q] = Sq[ob + ci[2 * cp]]; vd[q] = Sq[ob + ci[2 * cp + 1]];
+      }
+#pragma unroll
+      for (int q = 0; q < kQ; ++q) sum[q] += (va[q] - vb[q]) - (vc[q] - vd[q]);
+    };
+    col_pair(std::integral_constant<int, 0>{});
+    if (col_lo) col_pair(std::integral_constant<int, 1>{});
+    if (col_hi) col_pair(std::integral_constant<int, 2>{});
+  };
+  row_pair(std::integral_constant<int, 0>{});
+  if (row_lo) row_pair(std::integral_constant<int, 1>{});
+  if (row_hi) row_pair(std::integral_constant<int, 2>{});
+  const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);
+  const float mu1 = (float)(sum[0] * dinv), mu2 = (float)(sum[1] * dinv);
+  const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+  const float s1 = (float)(sum[2] * dinv) - mu1_sq;
+  const float s2 = (float)(sum[3] * dinv) - mu2_sq;
+  const float s12 = (float)(sum[4] * dinv) - mu12;
+  const float m = ((2.0f * mu12 + C1) * (2.0f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
+  if (p < npix) out[(size_t)img * npix + p] = 1.0f - m;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srad_anomaly_map_workspace_bytes(int n_img, int H, int W, size_t* bytes) {
+  SRAD_REQUIRE(bytes && n_img > 0 && H > 0 && W > 0, "anomaly_map_workspace_bytes: bad argument");
+  const int chunk = chunk_images(n_img, H, W);
+  const int nseg = (H + kSeg - 1) / kSeg;
+  *bytes = srad_align_up((size_t)chunk * (H + 1) * (W + 1) * kQ * sizeof(double), 256) +
+           srad_align_up((size_t)chunk * kQ * nseg * (W + 1) * sizeof(double), 256);
+  return SRAD_OK;
+}
+
+int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  SRAD_REQUIRE(sr && hr && map_out && workspace && n_img > 0 && H > 1 && W > 1, "anomaly_maps: bad argument");
+  SRAD_REQUIRE(C == 1 || C == 3, "anomaly_maps: channels must be 1 or 3 (got %d)", C);
+  SRAD_REQUIRE((long long)(H + 1) * (W + 1) < (1ll << 31), "anomaly_maps: %dx%d images are too large for the 32-bit table offsets", H, W);
+  SRAD_REQUIRE(ws >= 1 && ws / 2 < H && ws / 2 < W && ws - 1 - ws / 2 < H && ws - 1 - ws / 2 < W,
+               "anomaly_maps: window %d needs more than one reflection of a %dx%d image", ws, H, W);
+  size_t need = 0;
+  SRAD_TRY(srad_anomaly_map_workspace_bytes(n_img, H, W, &need));
+  SRAD_REQUIRE(workspace_bytes >= need, "anomaly_maps: workspace %zu bytes, %zu needed", workspace_bytes, need);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int chunk = chunk_images(n_img, H, W);
+  const int nseg = (H + kSeg - 1) / kSeg;
+  const int nblk = (H * W + 255) / 256;
+  double* sat = reinterpret_cast<double*>(workspace);
+  double* segtot = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) +
+                                             srad_align_up((size_t)chunk * (H + 1) * (W + 1) * kQ * sizeof(double), 256));
+  const size_t img_bytes = (size_t)H * W * C;
+  const double dinv = 1.0 / ((double)ws * (double)ws);
+  for (int i0 = 0; i0 < n_img; i0 += chunk) {
+    const int n = std::min(chunk, n_img - i0);
+    const uint8_t* srp = sr + (size_t)i0 * img_bytes;
+    const uint8_t* hrp = hr + (size_t)i0 * img_bytes;
+    {
+      SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W, 2.0 * n * img_bytes + 40.0 * n * (H + 1) * (W + 1));
+      hipLaunchKernelGGL(sat_rows_kernel, dim3((n * (H + 1) + 3) / 4), dim3(256), 0, s, srp, hrp, sat, n, H, W, C);
+    }
+    {
+      const size_t t = (size_t)n * kQ * nseg * (W + 1);
+      SradProfScope prof(s, SRAD_K_SCORE, 1.0 * n * (H + 1) * (W + 1) * kQ, 80.0 * n * (H + 1) * (W + 1));
+      hipLaunchKernelGGL(sat_cols_local_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, sat, segtot, n * kQ, H, W, nseg);
+      if (nseg > 1) {
+        const size_t t2 = (size_t)n * kQ * (nseg - 1) * (W + 1);
+        hipLaunchKernelGGL(sat_cols_carry_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, sat, segtot, n * kQ, H, W, nseg);
+      }
+    }
+    {
+      // algorithmic bytes: the two fp32 luminance planes read once, the fp32 map written once
+      SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W, 12.0 * n * H * W);
+      hipLaunchKernelGGL(ssim_map_kernel, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, sat, map_out + (size_t)i0 * H * W, H, W,
+                         ws, dinv, nblk);
+    }
+  }
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+}  // extern "C"

@@ -15,7 +15,7 @@ from __future__ import annotations
 import os
 import re
 from pathlib import Path
-from typing import Iterable, List, Sequence, Tuple
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -102,6 +102,44 @@ def save_sr_image(sr_u8_hwc: np.ndarray, name: str, split: str, scale_value: int
     img.save(str(out_dir / f"{name}.png"))
 
 
+def load_masks(data_root: str, classe: str, names: Sequence[Tuple[str, str]], hr_shapes: Sequence[Tuple[int, int]]
+               ) -> Tuple[List[Optional[np.ndarray]], List[str]]:
+    """Ground-truth masks of the test split for pixel-level metrics: ``names`` = (split, name) per image, ``hr_shapes`` = the
+    (H, W) of its HR image as ``iter_split`` returns it.  Good images get all-zero masks; a bad image reads
+    ``{root}/{class}/test/bad/GT/<name>.png`` (written by ``prepare_mvtec_data --with-masks``), cropped top-left to the HR size
+    like the HR image.  Returns (masks: uint8 {0, 1} [H, W] arrays, None where a bad image has no usable mask; the names of
+    those bad images)."""
+    from PIL import Image
+    masks: List[Optional[np.ndarray]] = []
+    missing: List[str] = []
+    for (split, name), (h, w) in zip(names, hr_shapes):
+        if split == 'good':
+            masks.append(np.zeros((h, w), dtype=np.uint8))
+            continue
+        f = Path(data_root) / classe / 'test' / 'bad' / 'GT' / f"{name}.png"
+        m = None
+        if f.is_file():
+            with Image.open(f) as im:
+                a = np.array(im.convert('L'))
+            if a.shape[0] >= h and a.shape[1] >= w:
+                m = (a[:h, :w] != 0).astype(np.uint8)
+        if m is None:
+            missing.append(name)
+        masks.append(m)
+    return masks, missing
+
+
+def save_anomaly_maps(maps: torch.Tensor, names: Sequence[str], splits: Sequence[str], output_dir: str) -> None:
+    """``<output_dir>/anomaly_maps/{good,bad}/<name>.png``: 8-bit gray of ``255 * clip(map, 0, 1)``, truncated (the u8 conversion
+    of the evaluator at rgb_range 1)."""
+    from PIL import Image
+    u8 = M.to_u8_hwc(maps[:, None], rgb_range=1.0).cpu().numpy()
+    for k, (name, split) in enumerate(zip(names, splits)):
+        d = Path(output_dir) / 'anomaly_maps' / split
+        d.mkdir(parents=True, exist_ok=True)
+        Image.fromarray(u8[k, :, :, 0]).save(str(d / f"{name}.png"))
+
+
 def shard_indices(n: int, rank: int, world: int) -> List[int]:
     """Images rank ``rank`` of ``world`` scores: r, r + world, ... (image-parallel, no data-path collective)."""
     return list(range(rank, n, world))
@@ -150,10 +188,17 @@ def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndar
 
 
 def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], bad: Sequence[Tuple[np.ndarray, np.ndarray]],
-                     rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False) -> dict:
+                     rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
+                     masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
+                     map_ws: int = 0) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
-    writes the SR images it produced under ``output_dir/{good,bad}/x{scale}`` (src/evaluate.py:190-224)."""
+    writes the SR images it produced under ``output_dir/{good,bad}/x{scale}`` (src/evaluate.py:190-224).
+
+    Pixel level (off by default): the anomaly maps ``1 - SSIM map`` of each rank's own images at window size ``map_ws``
+    (0 = the sweep's best_ws).  ``save_maps``: every rank writes them under ``output_dir/anomaly_maps/{good,bad}``.
+    ``pixel_metrics``: with world 1 and a mask for every image (``masks``, good + bad order, as ``load_masks`` returns them)
+    the exact pixel-level ROC-AUC is added as ``auc_pixel``, with ``map_ws``."""
     model.eval()                                              # H1: deterministic scoring
     y_true = [0] * len(good) + [1] * len(bad)
     pairs = list(good) + list(bad)
@@ -173,6 +218,8 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     rows = torch.cat([ssim, mse[:, None], psnr[:, None]], dim=1)          # [n_mine, n_ws + 2] float64
     full = gather_score_rows(mine, rows.cpu().numpy(), len(pairs), rank, world)
     if full is None:
+        if save_maps or pixel_metrics:
+            _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, None, world)
         return {}
     best_ws, best_auc, best_j = sizes[0], -1.0, 0
     for j, ws in enumerate(sizes):
@@ -182,7 +229,46 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     out = dict(best_ws=best_ws, auc_ssim=M.roc_auc(y_true, 1.0 - full[:, best_j]), auc_mse=M.roc_auc(y_true, full[:, -2]),
                auc_psnr=M.roc_auc(y_true, -full[:, -1]), n_images=len(pairs), window_sizes=sizes)
     print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}")
+    if save_maps or pixel_metrics:
+        out.update(_pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world))
     return out
+
+
+def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world) -> dict:
+    """Anomaly maps of this rank's images; the pixel-level AUC on a single rank.  ``best_ws`` is None off rank 0."""
+    if world > 1 and not save_maps:                           # the same branch on every rank: no collective below
+        if pixel_metrics and best_ws is not None:
+            print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
+        return {}
+    ws = int(map_ws)
+    if ws <= 0:
+        ws = best_ws
+        if world > 1:                                         # only rank 0 has the sweep's result
+            import torch.distributed as dist
+            box = [best_ws]
+            dist.broadcast_object_list(box, src=0)
+            ws = int(box[0])
+    maps = M.anomaly_maps(sr, hr, ws)
+    if save_maps and output_dir:
+        save_anomaly_maps(maps, [names[i] if i < len(names) else f"{i:05d}" for i in mine],
+                          ['good' if y_true[i] == 0 else 'bad' for i in mine], output_dir)
+    if not pixel_metrics or best_ws is None:
+        return {}
+    if world > 1:
+        print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
+        return {}
+    lacking = [i for i in range(len(y_true)) if masks is None or i >= len(masks) or masks[i] is None]
+    if lacking:
+        print(f"Pixel metrics skipped: {len(lacking)} test image(s) have no ground-truth mask")
+        return {}
+    H, W = maps.shape[1:]
+    for i in mine:
+        if tuple(masks[i].shape) != (H, W):
+            raise ValueError(f"mask {i} has shape {tuple(masks[i].shape)}, the images are {H}x{W}")
+    labels = torch.from_numpy(np.stack([np.asarray(masks[i]) for i in mine])).to(maps.device)
+    auc = M.pixel_roc_auc(maps, labels)
+    print(f"Pixel AUC - SSIM map (ws={ws}): {auc:.4f}")
+    return dict(auc_pixel=auc, map_ws=ws)
 
 
 def main(argv=None):
@@ -216,8 +302,16 @@ def _run(args):
     g = list(iter_split(opt.data_root, class_name, 'good', opt.scale, opt.n_colors))
     b = list(iter_split(opt.data_root, class_name, 'bad', opt.scale, opt.n_colors))
     out_dir = args.output_dir or (os.path.join(args.run_dir, 'eval_results') if args.run_dir else './workspace/eval_results')
+    masks = None
+    if args.pixel_metrics and world == 1:
+        masks, missing = load_masks(opt.data_root, class_name, [('good', n) for n, _, _ in g] + [('bad', n) for n, _, _ in b],
+                                    [hr.shape[:2] for _, _, hr in g + b])
+        if missing:
+            print(f"No ground-truth mask for {len(missing)} bad image(s) under test/bad/GT (prepare_mvtec_data --with-masks), "
+                  f"e.g. {missing[0]}")
     evaluate_on_test(opt, model, [(lr, hr) for _, lr, hr in g], [(lr, hr) for _, lr, hr in b], rank, world,
-                     names=[n for n, _, _ in g] + [n for n, _, _ in b], output_dir=out_dir, save_images=args.save_images)
+                     names=[n for n, _, _ in g] + [n for n, _, _ in b], output_dir=out_dir, save_images=args.save_images,
+                     masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

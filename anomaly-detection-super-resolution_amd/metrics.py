@@ -96,6 +96,49 @@ def roc_auc(y_true: Sequence[int], scores: Sequence[float]) -> float:
     return out.value
 
 
+def anomaly_maps(sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws: int) -> torch.Tensor:
+    """Per-pixel anomaly maps ``1 - ssim_map`` of [n,H,W,C] uint8 image stacks (SR, HR) at window size ``ws``: the map
+    ``ssim_numpy(hr/255, sr/255, ws)`` averages (src/metrics.py:26-67).  Returns float32 [n,H,W] on the GPU."""
+    _need_cuda(sr_u8, hr_u8)
+    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
+    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
+    n, H, W, Cc = sr_u8.shape
+    out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
+    nbytes = C.c_size_t()
+    L.check(L.lib().srad_anomaly_map_workspace_bytes(n, H, W, C.byref(nbytes)), "anomaly_map_workspace_bytes")
+    keep, wp, wb = _ws_buffer(nbytes.value, sr_u8.device)
+    L.check(L.lib().srad_anomaly_maps(L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, int(ws), L.dptr(out), wp, wb,
+                                      L.current_stream_ptr()), "anomaly_maps")
+    return out
+
+
+def pixel_roc_auc(scores: torch.Tensor, labels: torch.Tensor) -> float:
+    """Exact pixel-level ROC-AUC (``sklearn.metrics.roc_auc_score`` of the flattened arrays, ties count one half) of GPU
+    tensors: float32 scores, labels nonzero = positive (any integer or bool dtype).  Raises ValueError like ``roc_auc``
+    when one class is absent, and when a score is NaN."""
+    _need_cuda(scores, labels)
+    s = scores.detach().reshape(-1).float().contiguous()
+    y = labels.detach().reshape(-1)
+    y = (y != 0).to(torch.uint8).contiguous() if y.dtype != torch.uint8 else y.contiguous()
+    if s.numel() != y.numel():
+        raise ValueError("scores and labels must have the same number of elements")
+    if s.numel() == 0:
+        raise ValueError("pixel_roc_auc of no elements")
+    counts = torch.empty(4, dtype=torch.int64, device=s.device)          # u64 on the device; the values stay below 2^62
+    auc = torch.empty((), dtype=torch.float64, device=s.device)
+    nbytes = C.c_size_t()
+    L.check(L.lib().srad_pixel_auc_workspace_bytes(C.c_int64(s.numel()), C.byref(nbytes)), "pixel_auc_workspace_bytes")
+    keep, wp, wb = _ws_buffer(nbytes.value, s.device)
+    L.check(L.lib().srad_pixel_roc_auc(L.dptr(s), L.dptr(y), C.c_int64(s.numel()), L.dptr(counts), L.dptr(auc), wp, wb,
+                                       L.current_stream_ptr()), "pixel_roc_auc")
+    n_pos, n_neg, n_nan, _ = counts.tolist()
+    if n_nan:
+        raise ValueError(f"pixel_roc_auc: {n_nan} of {s.numel()} scores are NaN")
+    if n_pos == 0 or n_neg == 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    return float(auc.item())
+
+
 def l1_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """nn.L1Loss(reduction='mean') (src/loss.py:84) -> 0-d float64 tensor on the GPU."""
     _need_cuda(a, b)

@@ -223,6 +223,11 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                    help="bf16x3 = split-bf16 (fp32-grade outputs on the bf16 matrix pipe; the default: AUC parity), fp32 = exact-fp32 MFMA, "
                         "bf16 = fastest, outside the +-0.002 AUC bar")
     p.add_argument('--gpus', type=int, default=1)
+    p.add_argument('--pixel-metrics', action='store_true', default=False,
+                   help="pixel-level ROC-AUC of the anomaly maps against the test/bad/GT masks (needs --gpus 1)")
+    p.add_argument('--save-anomaly-maps', action='store_true', default=False,
+                   help="write the per-pixel anomaly maps (1 - SSIM map) as <output-dir>/anomaly_maps/{good,bad}/<name>.png")
+    p.add_argument('--map-ws', type=int, default=0, help="window size of the anomaly maps; 0 = the image-level sweep's best_ws")
     _with_config(p, pre_args)
     return p.parse_args(argv)
 

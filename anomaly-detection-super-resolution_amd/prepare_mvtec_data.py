@@ -9,6 +9,7 @@ For every class (``carpet``, ``grid``):
     <target>/<class>/{train,val}/good/LR_<s>/<name>.png  the HR image LANCZOS-resized to hr // s, for every s of the scale set
     <target>/<class>/test/good/{HR,LR_<s>}/<name>.png
     <target>/<class>/test/bad/{HR,LR_<s>}/<defect>_<name>.png   every defect class merged into ``bad``, the defect name as prefix
+    <target>/<class>/test/bad/GT/<defect>_<name>.png       (--with-masks only) MVTec's ground-truth mask, NEAREST-resized to hr x hr
 
 The scale set is progressive (what DRN-L's intermediate outputs are trained against): always 2, plus 4 when 8 is asked for.
 The train / val split shuffles the directory listing with ``numpy.random.RandomState(seed)`` and takes the first
@@ -80,8 +81,21 @@ def process_training_data(source_dir, train_target_dir, val_target_dir, scale_fa
     print(f"  Created {len(train)} train pairs and {len(val)} val pairs")
 
 
-def process_test_data(source_dir, target_dir, scale_factors=(4,), target_hr=(128, 128)):
-    """test/<good | defect classes> of one class -> test/good and test/bad (scripts/prepare_mvtec_data.py:95-159)."""
+def _write_mask(src: Path, gt_dir: Path, name: str, target_hr) -> None:
+    """MVTec's ground-truth mask of ``src`` (``<class>/ground_truth/<defect>/<stem>_mask.png``) -> ``gt_dir/<name>``, resized with
+    NEAREST so that it stays binary; a missing mask is reported and nothing is written."""
+    mask = src.parent.parent.parent / "ground_truth" / src.parent.name / f"{src.stem}_mask.png"
+    if not mask.exists():
+        print(f"  WARNING no ground-truth mask for {src.parent.name}/{src.name} (looked for {mask})")
+        return
+    gt_dir.mkdir(parents=True, exist_ok=True)
+    with Image.open(mask) as m:
+        (m if m.mode == 'L' else m.convert('L')).resize(target_hr, Image.NEAREST).save(gt_dir / name)
+
+
+def process_test_data(source_dir, target_dir, scale_factors=(4,), target_hr=(128, 128), with_masks=False):
+    """test/<good | defect classes> of one class -> test/good and test/bad (scripts/prepare_mvtec_data.py:95-159).
+    ``with_masks``: also the ground-truth masks of the defective images under test/bad/GT, named like their HR images."""
     source_dir, target_dir = Path(source_dir), Path(target_dir)
     print(f"Processing test data: {source_dir.name}")
     for label in ("good", "bad"):
@@ -97,12 +111,16 @@ def process_test_data(source_dir, target_dir, scale_factors=(4,), target_hr=(128
         print(f"  Processing {defect.name}: {len(images)} images")
         for f in images:
             _write_pyramid(f, target_dir / "bad", f"{defect.name}_{f.name}", scale_factors, target_hr)   # unique across defect classes
+            if with_masks:
+                _write_mask(f, target_dir / "bad" / "GT", f"{defect.name}_{f.name}", target_hr)
     print(f"  Good test images: {len(list((target_dir / 'good' / 'HR').glob('*.png')))}")
     print(f"  Bad test images: {len(list((target_dir / 'bad' / 'HR').glob('*.png')))}")
 
 
-def prepare_mvtec_dataset(source_base="data/mvtec", target_base="data/mvtec_128", scale_factors=(4,), target_hr=(128, 128), val_ratio=0.1, seed=42):
-    """Both classes, train + val + test; an existing target tree is replaced (scripts/prepare_mvtec_data.py:161-205)."""
+def prepare_mvtec_dataset(source_base="data/mvtec", target_base="data/mvtec_128", scale_factors=(4,), target_hr=(128, 128), val_ratio=0.1, seed=42,
+                          with_masks=False):
+    """Both classes, train + val + test; an existing target tree is replaced (scripts/prepare_mvtec_data.py:161-205).
+    ``with_masks``: also write the test split's ground-truth masks (test/bad/GT) for pixel-level metrics."""
     source_base, target_base = Path(source_base), Path(target_base)
     print(f"Preparing MVTec AD dataset for {target_hr[0]}x{target_hr[1]} training")
     if target_base.exists():
@@ -117,7 +135,7 @@ def prepare_mvtec_dataset(source_base="data/mvtec", target_base="data/mvtec_128"
         else:
             print(f"  ERROR: Training data not found: {train_src}")
         if test_src.exists():
-            process_test_data(test_src, target_base / cls / "test", scale_factors, target_hr=target_hr)
+            process_test_data(test_src, target_base / cls / "test", scale_factors, target_hr=target_hr, with_masks=with_masks)
         else:
             print(f"  ERROR: Test data not found: {test_src}")
     print(f"\nDataset preparation complete!\nOutput directory: {target_base}")
@@ -163,6 +181,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--source", type=str, default="data/mvtec", help="(this build) where the original MVTec AD tree is")
     ap.add_argument("--target", type=str, default="", help="(this build) output tree; default data/mvtec_<hr-size>")
+    ap.add_argument("--with-masks", action="store_true", help="also write the ground-truth masks of test/bad (test/bad/GT)")
     args = ap.parse_args(argv)
     print(f"MVTec AD Dataset Preparation ({args.hr_size}x{args.hr_size})")
     if not Path(args.source).exists():
@@ -174,7 +193,7 @@ def main(argv=None):
         print(f"ERROR: {e if 'supported' in str(e) else 'Invalid --scales. Use comma-separated integers from {4,8}'}")
         return 1
     target = args.target or f"data/mvtec_{args.hr_size}"
-    prepare_mvtec_dataset(args.source, target, scales, (args.hr_size, args.hr_size), args.val_ratio, args.seed)
+    prepare_mvtec_dataset(args.source, target, scales, (args.hr_size, args.hr_size), args.val_ratio, args.seed, with_masks=args.with_masks)
     verify_dataset_structure(target)
     return 0
 

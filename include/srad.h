@@ -192,6 +192,22 @@ int srad_val_metrics(const float* sr, const float* hr, int B, int C, int H, int 
 /* Binary ROC-AUC == sklearn.metrics.roc_auc_score (ties count one half).  labels/scores are HOST
  * arrays (n is the number of test images, a few hundred); returns non-zero if one class is absent. */
 int srad_roc_auc(const int32_t* labels, const double* scores, int n, double* auc);
+/* Per-pixel anomaly maps for `n_img` u8 HWC image pairs (sr, hr, each [n_img,H,W,C]) at ONE window size `ws`:
+ *   map_out[i, y, x] = 1 - ssim_map(hr_i/255, sr_i/255, ws)[y, x]      (src/metrics.py:26-67; the array line 66 averages)
+ * with the arithmetic of srad_score_pairs: luminance, float64 box sums with numpy "reflect" padding, C1 = 1e-4, C2 = 9e-4, the
+ * per-pixel fp32 operations in the order of metrics.py:58-66.  map_out is a DEVICE float32 array [n_img, H, W]; window sizes
+ * srad_score_pairs rejects are rejected; workspace >= srad_anomaly_map_workspace_bytes.  Any width. */
+int srad_anomaly_map_workspace_bytes(int n_img, int H, int W, size_t* bytes);
+int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* Exact ROC-AUC of `n` DEVICE float32 scores against DEVICE u8 labels (labels[i] != 0 = positive), n < 2^31:
+ * sklearn.metrics.roc_auc_score as the Mann-Whitney U with ties counted one half (a device radix sort, no binning).
+ *   counts_out (DEVICE, 4 x u64) = {n_pos, n_neg, n_nan, twice_U};  *auc_out (DEVICE double) = twice_U / (2 n_pos n_neg),
+ *   NaN when a class is absent.  NaN scores are left out of n_pos, n_neg and twice_U and counted in n_nan.
+ * Stream-ordered like the other scorer entry points; workspace >= srad_pixel_auc_workspace_bytes(n) (about 17 bytes per score). */
+int srad_pixel_auc_workspace_bytes(int64_t n, size_t* bytes);
+int srad_pixel_roc_auc(const float* scores, const uint8_t* labels, int64_t n, uint64_t* counts_out, double* auc_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* mean |a-b| (nn.L1Loss, src/loss.py:84) -> *out (device double); workspace >= srad_l1_workspace_bytes */
 int srad_l1_workspace_bytes(size_t* bytes);
