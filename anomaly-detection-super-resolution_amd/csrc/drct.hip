@@ -16,23 +16,8 @@
 
 namespace {
 
-GemmParams base_gemm(const srad_drct* h, const ConvW& c, const float* X, int ldx, int M, float* Y, int ldy) {
-  GemmParams p{};
-  p.X = X; p.ldx = ldx; p.M = M; p.Cin = c.cin; p.Cp = srad_cp(c.cin); p.ntaps = c.ntaps;
-  p.Hi = p.Wi = p.Ho = p.Wo = 0; p.stride = 1;
-  p.ln_g = p.ln_b = nullptr; p.ln_eps = 1e-5f;
-  p.Wp = h->pt.ptr(c.w); p.N = c.n; p.bias = h->pt.fptr(c.b);
-  p.act = SRAD_ACT_NONE; p.slope = 0.f; p.alpha = 1.f;
-  p.R = nullptr; p.ldr = 0;
-  p.Y = Y; p.ldy = ldy; p.yoff = 0; p.ps = 0;
-  return p;
-}
-
-void conv_geom(GemmParams& p, int H, int W) { p.Hi = p.Ho = H; p.Wi = p.Wo = W; p.stride = 1; }
-
-struct DrctWs {
-  float *xin, *feat0, *dense0, *dense1, *qkv, *attn, *x1, *hid, *x2, *body, *c1, *c2, *outn;
-  std::vector<float*> upb;
+struct DrctWs : DrctStemTail {
+  float *dense0, *dense1, *qkv, *attn, *x1, *hid, *x2;
   size_t bytes;
 };
 
@@ -69,20 +54,7 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
   const int prec = c.precision;
   const int T = B * H * W;
   const int E = c.embed_dim, D = E + 4 * c.gc;
-  const float mean3[3] = {c.in_chans == 3 ? 0.4488f : 0.f, c.in_chans == 3 ? 0.4371f : 0.f, c.in_chans == 3 ? 0.4040f : 0.f};
-
-  // (x - mean) * img_range, NCHW -> NHWC            (drct.py:887-888)
-  SRAD_TRY(srad_launch_nchw_to_nhwc(x, w.xin, B, c.in_chans, SRAD_IMG_CPAD, H, W, mean3, c.img_range, s));
-  // conv_first                                       (drct.py:892)
-  {
-    GemmParams p = base_gemm(h, h->conv_first, w.xin, SRAD_IMG_CPAD, T, w.feat0, E);
-    p.Cin = SRAD_IMG_CPAD;                 // padded image channels; the packed weight is zero there
-    conv_geom(p, H, W);
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-  }
-  // patch_embed.norm -> residual stream in dense0[:, :E]   (drct.py:873, 650-654)
-  SRAD_TRY(srad_launch_layernorm(w.feat0, E, w.dense0, D, T, E, h->pt.fptr(h->pe_g), h->pt.fptr(h->pe_b), 1e-5f, s));
-
+  SRAD_TRY(drct_stem(h, x, B, H, W, w, w.dense0, s));
   float* cur = w.dense0;
   float* nxt = w.dense1;
   for (int i = 0; i < c.n_rdg; ++i) {
@@ -98,12 +70,9 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
       if (h->fuse_mlp && srad_qkv_attn_supported(prec, c.window_size, H, W, d, sw.heads)) {
         // norm1 + qkv + shifted-window attention of one (window, head) per workgroup, one launch
         // (drct.py:477-504, 278-299)
-        QkvAttnParams a{};
-        a.x = cur; a.ldx = D; a.ln_g = h->pt.fptr(sw.n1g); a.ln_b = h->pt.fptr(sw.n1b);
-        a.w_qkv = h->pt.frag_ptr(sw.qkv.w); a.b_qkv = h->pt.fptr(sw.qkv.b); a.table = h->pt.fptr(sw.table);
-        a.out = w.attn; a.out_h = mlp_fused && !x3 ? attn_h : nullptr; a.ld_out = d;
+        QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);
+        a.out = w.attn; a.out_h = mlp_fused && !x3 ? attn_h : nullptr;
         a.split = x3; a.w_qkv_lo = h->pt.frag_lo_ptr(sw.qkv.w);
-        a.B = B; a.H = H; a.W = W; a.shift = sw.shift; a.d = d; a.heads = sw.heads;
         SRAD_TRY(srad_launch_qkv_attn(a, s));
       } else {
       // norm1 + qkv                                   (drct.py:477, 278)
@@ -127,7 +96,7 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
           SRAD_TRY(srad_launch_ln_qkv(q, s));
         } else {
           const int hdp = hdp_of(d, sw.heads);
-          GemmParams p = base_gemm(h, sw.qkv, cur, D, T, w.qkv, 3 * sw.heads * hdp);
+          GemmParams p = drct_gemm(h, sw.qkv, cur, D, T, w.qkv, 3 * sw.heads * hdp);
           p.hsplit_hd = d / sw.heads; p.hsplit_hdp = hdp;      // head-padded q|k|v rows for the attention kernel
           p.ln_g = h->pt.fptr(sw.n1g); p.ln_b = h->pt.fptr(sw.n1b);
           if (qkv_bf16) { p.Yh = reinterpret_cast<__bf16*>(w.qkv); p.hsplit_heads = sw.heads; p.hsplit_qscale = qscale; }
@@ -145,66 +114,91 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
       if (mlp_fused) {
         // proj + shortcut -> norm2 -> fc1 -> GELU -> fc2 + residual -> adjust_k, one launch
         // (drct.py:300, 509-510, 184-190, 389-396)
-        MlpBlockParams q{};
-        q.attn_h = attn_h; q.ld_attn = d; q.shortcut = cur; q.ld_short = D;
+        MlpBlockParams q = drct_mlp_block_params(h, sw, k, attn_h, cur, nxt, T);
         q.split = x3; q.attn_f = w.attn;
         q.w_proj_lo = h->pt.frag_lo_ptr(sw.proj.w); q.w_fc1_lo = h->pt.frag_lo_ptr(sw.fc1.w); q.w_fc2_lo = h->pt.frag_lo_ptr(sw.fc2.w);
         q.w_adj_lo = h->pt.frag_lo_ptr(sw.adjust.w);
-        q.M = T; q.d = d; q.m = sw.hidden; q.no = no;
-        q.w_proj = h->pt.frag_ptr(sw.proj.w); q.w_fc1 = h->pt.frag_ptr(sw.fc1.w); q.w_fc2 = h->pt.frag_ptr(sw.fc2.w);
-        q.w_adj = h->pt.frag_ptr(sw.adjust.w);
-        q.b_proj = h->pt.fptr(sw.proj.b); q.b_fc1 = h->pt.fptr(sw.fc1.b); q.b_fc2 = h->pt.fptr(sw.fc2.b); q.b_adj = h->pt.fptr(sw.adjust.b);
-        q.ln_g = h->pt.fptr(sw.n2g); q.ln_b = h->pt.fptr(sw.n2b); q.dbg = 0;
-        if (k < 4) { q.act = SRAD_ACT_LRELU; q.slope = 0.2f; q.alpha = 1.f; q.R = nullptr; q.ldr = 0; q.Y = cur; q.ldy = D; q.yoff = d; }
-        else { q.act = SRAD_ACT_NONE; q.slope = 0.f; q.alpha = 0.2f; q.R = cur; q.ldr = D; q.Y = nxt; q.ldy = D; q.yoff = 0; }
         SRAD_TRY(srad_launch_mlp_block(q, s));
         continue;
       }
       // proj + shortcut                               (drct.py:300, 509)
       {
-        GemmParams p = base_gemm(h, sw.proj, w.attn, d, T, w.x1, d);
+        GemmParams p = drct_gemm(h, sw.proj, w.attn, d, T, w.x1, d);
         p.R = cur; p.ldr = D;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       // norm2 + fc1 + GELU                            (drct.py:510, 185-186)
       {
-        GemmParams p = base_gemm(h, sw.fc1, w.x1, d, T, w.hid, sw.hidden);
+        GemmParams p = drct_gemm(h, sw.fc1, w.x1, d, T, w.hid, sw.hidden);
         p.ln_g = h->pt.fptr(sw.n2g); p.ln_b = h->pt.fptr(sw.n2b);
         p.act = SRAD_ACT_GELU;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       // fc2 + residual                                (drct.py:188, 510)
       {
-        GemmParams p = base_gemm(h, sw.fc2, w.hid, sw.hidden, T, w.x2, d);
+        GemmParams p = drct_gemm(h, sw.fc2, w.hid, sw.hidden, T, w.x2, d);
         p.R = w.x1; p.ldr = d;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       // adjust_k 1x1 conv (+ LeakyReLU 0.2) into the dense buffer; adjust5: *0.2 + x into the next
       if (k < 4) {                                     // (drct.py:389-392)
-        GemmParams p = base_gemm(h, sw.adjust, w.x2, d, T, cur, D);
+        GemmParams p = drct_gemm(h, sw.adjust, w.x2, d, T, cur, D);
         p.yoff = d; p.act = SRAD_ACT_LRELU; p.slope = 0.2f;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       } else {                                         // (drct.py:393, 396)
-        GemmParams p = base_gemm(h, sw.adjust, w.x2, d, T, nxt, D);
+        GemmParams p = drct_gemm(h, sw.adjust, w.x2, d, T, nxt, D);
         p.alpha = 0.2f; p.R = cur; p.ldr = D;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
     }
     float* t = cur; cur = nxt; nxt = t;
   }
+  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s);
+}
+
+}  // namespace
+
+// ---- shared with the training forward (drct_train.hip) ----
+static void drct_mean(const srad_drct_config& c, float m[3]) {   // MeanShift: the RGB mean, none for gray images  (drct.py:887, 897)
+  const float rgb[3] = {0.4488f, 0.4371f, 0.4040f};
+  for (int i = 0; i < 3; ++i) m[i] = c.in_chans == 3 ? rgb[i] : 0.f;
+}
+
+int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s) {
+  const srad_drct_config& c = h->cfg;
+  const int T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc;
+  float mean3[3];
+  drct_mean(c, mean3);
+  // (x - mean) * img_range, NCHW -> NHWC            (drct.py:887-888)
+  SRAD_TRY(srad_launch_nchw_to_nhwc(x, w.xin, B, c.in_chans, SRAD_IMG_CPAD, H, W, mean3, c.img_range, s));
+  // conv_first                                       (drct.py:892)
+  {
+    GemmParams p = drct_gemm(h, h->conv_first, w.xin, SRAD_IMG_CPAD, T, w.feat0, E);
+    p.Cin = SRAD_IMG_CPAD;                 // padded image channels; the packed weight is zero there
+    geom(p, H, W);
+    SRAD_TRY(srad_launch_gemm(c.precision, p, s));
+  }
+  // patch_embed.norm -> residual stream in dense0[:, :E]   (drct.py:873, 650-654)
+  return srad_launch_layernorm(w.feat0, E, dense0, D, T, E, h->pt.fptr(h->pe_g), h->pt.fptr(h->pe_b), 1e-5f, s);
+}
+
+int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
+              hipStream_t s) {
+  const srad_drct_config& c = h->cfg;
+  const int prec = c.precision, T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc, F = c.num_feat;
   // norm                                              (drct.py:881)
-  SRAD_TRY(srad_launch_layernorm(cur, D, w.body, E, T, E, h->pt.fptr(h->norm_g), h->pt.fptr(h->norm_b), 1e-5f, s));
+  SRAD_TRY(srad_launch_layernorm(dense, D, w.body, E, T, E, h->pt.fptr(h->norm_g), h->pt.fptr(h->norm_b), 1e-5f, s));
   // conv_after_body(...) + x                          (drct.py:893)
   {
-    GemmParams p = base_gemm(h, h->conv_after_body, w.body, E, T, w.c1, E);
-    conv_geom(p, H, W);
+    GemmParams p = drct_gemm(h, h->conv_after_body, w.body, E, T, w.c1, E);
+    geom(p, H, W);
     p.R = w.feat0; p.ldr = E;
     SRAD_TRY(srad_launch_gemm(prec, p, s));
   }
   // conv_before_upsample + LeakyReLU(0.01)            (drct.py:844-845, 894)
   {
-    GemmParams p = base_gemm(h, h->conv_before_up, w.c1, E, T, w.c2, c.num_feat);
-    conv_geom(p, H, W);
+    GemmParams p = drct_gemm(h, h->conv_before_up, w.c1, E, T, w.c2, F);
+    geom(p, H, W);
     p.act = SRAD_ACT_LRELU; p.slope = 0.01f;
     SRAD_TRY(srad_launch_gemm(prec, p, s));
   }
@@ -212,8 +206,8 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
   const float* src = w.c2;
   int hh = H, ww = W;
   for (size_t j = 0; j < h->up.size(); ++j) {
-    GemmParams p = base_gemm(h, h->up[j], src, c.num_feat, B * hh * ww, w.upb[j], c.num_feat);
-    conv_geom(p, hh, ww);
+    GemmParams p = drct_gemm(h, h->up[j], src, F, B * hh * ww, w.upb[j], F);
+    geom(p, hh, ww);
     p.ps = 2;
     SRAD_TRY(srad_launch_gemm(prec, p, s));
     src = w.upb[j];
@@ -221,16 +215,39 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
   }
   // conv_last                                         (drct.py:895)
   {
-    GemmParams p = base_gemm(h, h->conv_last, src, c.num_feat, B * hh * ww, w.outn, c.in_chans);
-    conv_geom(p, hh, ww);
+    GemmParams p = drct_gemm(h, h->conv_last, src, F, B * hh * ww, w.outn, ld_outn);
+    geom(p, hh, ww);
     SRAD_TRY(srad_launch_gemm(prec, p, s));
   }
   // x / img_range + mean, NHWC -> NCHW                (drct.py:897)
-  SRAD_TRY(srad_launch_nhwc_to_nchw(w.outn, c.in_chans, y, B, c.in_chans, hh, ww, mean3, 1.0f / c.img_range, s));
-  return SRAD_OK;
+  float mean3[3];
+  drct_mean(c, mean3);
+  return srad_launch_nhwc_to_nchw(w.outn, ld_outn, y, B, c.in_chans, hh, ww, mean3, 1.0f / c.img_range, s);
 }
 
-}  // namespace
+QkvAttnParams drct_qkv_attn_params(const srad_drct* h, const SwinW& sw, const float* cur, int B, int H, int W) {
+  QkvAttnParams a{};
+  a.x = cur; a.ldx = h->cfg.embed_dim + 4 * h->cfg.gc; a.ln_g = h->pt.fptr(sw.n1g); a.ln_b = h->pt.fptr(sw.n1b);
+  a.w_qkv = h->pt.frag_ptr(sw.qkv.w); a.b_qkv = h->pt.fptr(sw.qkv.b); a.table = h->pt.fptr(sw.table);
+  a.ld_out = sw.d;
+  a.B = B; a.H = H; a.W = W; a.shift = sw.shift; a.d = sw.d; a.heads = sw.heads;
+  return a;
+}
+
+MlpBlockParams drct_mlp_block_params(const srad_drct* h, const SwinW& sw, int k, const __bf16* attn_h, float* cur, float* nxt, int T) {
+  const int D = h->cfg.embed_dim + 4 * h->cfg.gc;
+  MlpBlockParams q{};
+  q.attn_h = attn_h; q.ld_attn = sw.d; q.shortcut = cur; q.ld_short = D;
+  q.M = T; q.d = sw.d; q.m = sw.hidden; q.no = k < 4 ? h->cfg.gc : h->cfg.embed_dim;
+  q.w_proj = h->pt.frag_ptr(sw.proj.w); q.w_fc1 = h->pt.frag_ptr(sw.fc1.w); q.w_fc2 = h->pt.frag_ptr(sw.fc2.w);
+  q.w_adj = h->pt.frag_ptr(sw.adjust.w);
+  q.b_proj = h->pt.fptr(sw.proj.b); q.b_fc1 = h->pt.fptr(sw.fc1.b); q.b_fc2 = h->pt.fptr(sw.fc2.b); q.b_adj = h->pt.fptr(sw.adjust.b);
+  q.ln_g = h->pt.fptr(sw.n2g); q.ln_b = h->pt.fptr(sw.n2b);
+  // adjust_k (+ LeakyReLU 0.2) into the dense buffer; adjust5: * 0.2 + x into the next   (drct.py:389-396)
+  if (k < 4) { q.act = SRAD_ACT_LRELU; q.slope = 0.2f; q.alpha = 1.f; q.Y = cur; q.ldy = D; q.yoff = sw.d; }
+  else { q.act = SRAD_ACT_NONE; q.alpha = 0.2f; q.R = cur; q.ldr = D; q.Y = nxt; q.ldy = D; q.yoff = 0; }
+  return q;
+}
 
 extern "C" {
 

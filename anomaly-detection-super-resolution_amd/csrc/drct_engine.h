@@ -1,5 +1,5 @@
 // drct_engine.h - the DRCT handle shared by the inference engine (drct.hip) and the training engine
-// (drct_train.hip).
+// (drct_train.hip), and the pieces of the forward both run: stem, tail, fused-block parameters (defined in drct.hip).
 #pragma once
 #include "train_common.h"
 #include "../../include/srad.h"
@@ -26,3 +26,29 @@ struct srad_drct {
   TrainState ts;                  // training (drct_train.hip)
   BwdStreams bwd;                 // the backward's side stream for the weight gradients, and its events
 };
+
+// GemmParams of a Linear / 1x1 / 3x3 layer of the forward over M token rows (3x3: geom() adds the image geometry)
+static inline GemmParams drct_gemm(const srad_drct* h, const ConvW& c, const float* X, int ldx, int M, float* Y, int ldy) {
+  GemmParams p{};
+  p.X = X; p.ldx = ldx; p.M = M; p.Cin = c.cin; p.Cp = srad_cp(c.cin); p.ntaps = c.ntaps;
+  p.stride = 1; p.ln_eps = 1e-5f;
+  p.Wp = h->pt.ptr(c.w); p.N = c.n; p.bias = h->pt.fptr(c.b);
+  p.alpha = 1.f; p.Y = Y; p.ldy = ldy;
+  return p;
+}
+static inline void geom(GemmParams& p, int H, int W) { p.Hi = p.Ho = H; p.Wi = p.Wo = W; }
+
+// The stem's and the tail's tensors, in the workspace of either forward
+struct DrctStemTail {
+  float *xin, *feat0, *body, *c1, *c2, *outn;
+  std::vector<float*> upb;
+};
+// (x - mean) * img_range -> conv_first -> patch_embed.norm into dense0[:, :embed]            (drct.py:887-892, 873)
+int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s);
+// norm -> conv_after_body + x -> conv_before_upsample -> Upsample -> conv_last (into outn, row stride ld_outn) -> y   (drct.py:881, 893-897)
+int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
+              hipStream_t s);
+// The fields both forwards set for Swin block `sw` of an RDG, block k of its five: weights, biases, LayerNorm, geometry, and
+// (mlp_block) the adjust conv's residual and output in the dense buffers cur / nxt
+QkvAttnParams drct_qkv_attn_params(const srad_drct* h, const SwinW& sw, const float* cur, int B, int H, int W);
+MlpBlockParams drct_mlp_block_params(const srad_drct* h, const SwinW& sw, int k, const __bf16* attn_h, float* cur, float* nxt, int T);

@@ -20,12 +20,9 @@ namespace {
 // ------------------------------------------------------------------------------------------ workspace
 struct BlockSave { float *xn1, *qkv, *attn, *x1, *xn2, *hpre, *hact, *x2; };
 
-struct TrainWs {
-  float *xin, *feat0;
+struct TrainWs : DrctStemTail {
   std::vector<float*> dense;          // n_rdg + 1 buffers [T][D]
   std::vector<BlockSave> blk;
-  float *body, *c1, *c2, *outn;
-  std::vector<float*> upb;
   // backward temporaries
   float *dimg, *dus, *dc2, *dc1, *dbody, *g0, *g1, *dxn, *dO, *dfeat, *dxin;
   float *dx2[2], *dx1[2], *dA[2], *dh[2], *dqkv[2];   // read by the side stream's weight gradients: two sets, alternating per block
@@ -70,14 +67,6 @@ TrainWs plan_train_ws(const srad_drct* h, int B, int H, int W, void* base, size_
   return w;
 }
 
-GemmParams fwd_gemm(const srad_drct* h, const ConvW& c, const float* X, int ldx, int M, float* Y, int ldy) {
-  GemmParams p{};
-  p.X = X; p.ldx = ldx; p.M = M; p.Cin = c.cin; p.Cp = srad_cp(c.cin); p.ntaps = c.ntaps;
-  p.stride = 1; p.ln_eps = 1e-5f;
-  p.Wp = h->pt.ptr(c.w); p.N = c.n; p.bias = h->pt.fptr(c.b);
-  p.alpha = 1.f; p.Y = Y; p.ldy = ldy;
-  return p;
-}
 // dX = dY W : the forward GEMM on the transposed pack (rows = input channels, K = output channels)
 GemmParams dgrad_gemm(const srad_drct* h, const ConvW& c, const float* dY, int ldy, int M, float* dX, int ldx) {
   GemmParams p{};
@@ -98,7 +87,6 @@ WgradParams wgrad_of(const srad_drct* h, const ConvW& c, float* flat_grad, const
   p.db = c.b >= 0 ? flat_grad + h->ts.flat_off[c.b] : nullptr;
   return p;
 }
-void geom(GemmParams& p, int H, int W) { p.Hi = p.Ho = H; p.Wi = p.Wo = W; }
 void geom(WgradParams& p, int H, int W) { p.Hi = p.Ho = H; p.Wi = p.Wo = W; }
 
 // Which kernels a Swin block's backward takes, and with them the storage form of what the forward saves for it.  The
@@ -227,16 +215,8 @@ int srad_drct_forward_train(srad_drct_t* h, const float* x, int B, int H, int W,
   const srad_drct_config& c = h->cfg;
   const int prec = c.precision;
   const int T = B * H * W, HW = H * W;
-  const int E = c.embed_dim, D = E + 4 * c.gc, F = c.num_feat;
-  const float mean3[3] = {c.in_chans == 3 ? 0.4488f : 0.f, c.in_chans == 3 ? 0.4371f : 0.f, c.in_chans == 3 ? 0.4040f : 0.f};
-
-  SRAD_TRY(srad_launch_nchw_to_nhwc(x, w.xin, B, c.in_chans, SRAD_IMG_CPAD, H, W, mean3, c.img_range, s));
-  {
-    GemmParams p = fwd_gemm(h, h->conv_first, w.xin, SRAD_IMG_CPAD, T, w.feat0, E);
-    p.Cin = SRAD_IMG_CPAD; geom(p, H, W);
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-  }
-  SRAD_TRY(srad_launch_layernorm(w.feat0, E, w.dense[0], D, T, E, h->pt.fptr(h->pe_g), h->pt.fptr(h->pe_b), 1e-5f, s));
+  const int E = c.embed_dim, D = E + 4 * c.gc;
+  SRAD_TRY(drct_stem(h, x, B, H, W, w, w.dense[0], s));
   for (int i = 0; i < c.n_rdg; ++i) {
     float* cur = w.dense[i];
     float* nxt = w.dense[i + 1];
@@ -254,11 +234,8 @@ int srad_drct_forward_train(srad_drct_t* h, const float* x, int B, int H, int W,
           srad_mlp_block_supported(prec, T, d, sw.hidden, no)) {
         // bf16: the two fused launches of the inference path, which also leave what the backward needs
         // (LN1(x), q|k|v, x + attn, LN2(.), fc1 pre-activation, GELU(.), block output) and apply DropPath
-        QkvAttnParams a{};
-        a.x = cur; a.ldx = D; a.ln_g = h->pt.fptr(sw.n1g); a.ln_b = h->pt.fptr(sw.n1b);
-        a.w_qkv = h->pt.frag_ptr(sw.qkv.w); a.b_qkv = h->pt.fptr(sw.qkv.b); a.table = h->pt.fptr(sw.table);
-        a.out_h = reinterpret_cast<__bf16*>(sv.attn); a.ld_out = d;      // bf16 hand-off to mlp_block (and to the proj weight gradient)
-        a.B = B; a.H = H; a.W = W; a.shift = sw.shift; a.d = d; a.heads = sw.heads;
+        QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);
+        a.out_h = reinterpret_cast<__bf16*>(sv.attn);                    // bf16 hand-off to mlp_block (and to the proj weight gradient)
         // the tensors only the weight gradients read (LN1(x), LN2(.), GELU(.), the block output) are left as bf16, which is
         // what the MFMA would round them to anyway: half the bytes written here and read (3 - 9 times each) by wgrad
         a.save_xn_h = reinterpret_cast<__bf16*>(sv.xn1); a.hdp = hdp;
@@ -267,26 +244,18 @@ int srad_drct_forward_train(srad_drct_t* h, const float* x, int B, int H, int W,
         if (bp.attn_h) { a.save_qkv_h = reinterpret_cast<__bf16*>(sv.qkv); a.hp_h = attn_hp(sw); }   // as the MFMA took them
         else a.save_qkv = sv.qkv;
         SRAD_TRY(srad_launch_qkv_attn(a, s));
-        MlpBlockParams q{};
-        q.attn_h = reinterpret_cast<const __bf16*>(sv.attn); q.ld_attn = d; q.shortcut = cur; q.ld_short = D;
-        q.M = T; q.d = d; q.m = sw.hidden; q.no = no;
-        q.w_proj = h->pt.frag_ptr(sw.proj.w); q.w_fc1 = h->pt.frag_ptr(sw.fc1.w); q.w_fc2 = h->pt.frag_ptr(sw.fc2.w);
-        q.w_adj = h->pt.frag_ptr(sw.adjust.w);
-        q.b_proj = h->pt.fptr(sw.proj.b); q.b_fc1 = h->pt.fptr(sw.fc1.b); q.b_fc2 = h->pt.fptr(sw.fc2.b); q.b_adj = h->pt.fptr(sw.adjust.b);
-        q.ln_g = h->pt.fptr(sw.n2g); q.ln_b = h->pt.fptr(sw.n2b);
+        MlpBlockParams q = drct_mlp_block_params(h, sw, k, reinterpret_cast<const __bf16*>(sv.attn), cur, nxt, T);
         q.rs1 = ks1; q.rs2 = ks2; q.rps = HW;
         q.save_x1 = sv.x1;
         if (bp.yh_dh) q.save_hpre_h = reinterpret_cast<__bf16*>(sv.hpre);     // GELU' takes it as bf16 in the bf16-output mlp_bwd
         else q.save_hpre = sv.hpre;
         q.save_xn2_h = reinterpret_cast<__bf16*>(sv.xn2); q.save_hact_h = reinterpret_cast<__bf16*>(sv.hact); q.save_x2_h = reinterpret_cast<__bf16*>(sv.x2);
-        if (k < 4) { q.act = SRAD_ACT_LRELU; q.slope = 0.2f; q.alpha = 1.f; q.Y = cur; q.ldy = D; q.yoff = d; }
-        else { q.act = SRAD_ACT_NONE; q.alpha = 0.2f; q.R = cur; q.ldr = D; q.Y = nxt; q.ldy = D; q.yoff = 0; }
         SRAD_TRY(srad_launch_mlp_block(q, s));
         continue;
       }
       SRAD_TRY(srad_launch_layernorm(cur, D, sv.xn1, d, T, d, h->pt.fptr(sw.n1g), h->pt.fptr(sw.n1b), 1e-5f, s));
       {
-        GemmParams p = fwd_gemm(h, sw.qkv, sv.xn1, d, T, sv.qkv, 3 * sw.heads * hdp);
+        GemmParams p = drct_gemm(h, sw.qkv, sv.xn1, d, T, sv.qkv, 3 * sw.heads * hdp);
         p.hsplit_hd = d / sw.heads; p.hsplit_hdp = hdp;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
@@ -295,57 +264,33 @@ int srad_drct_forward_train(srad_drct_t* h, const float* x, int B, int H, int W,
         SRAD_TRY(srad_launch_window_attn(prec, a, s));
       }
       {  // x1 = shortcut + drop_path(proj(attn))          (drct.py:300, 509)
-        GemmParams p = fwd_gemm(h, sw.proj, sv.attn, d, T, sv.x1, d);
+        GemmParams p = drct_gemm(h, sw.proj, sv.attn, d, T, sv.x1, d);
         p.R = cur; p.ldr = D; p.row_scale = ks1; p.rps = HW;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       SRAD_TRY(srad_launch_layernorm(sv.x1, d, sv.xn2, d, T, d, h->pt.fptr(sw.n2g), h->pt.fptr(sw.n2b), 1e-5f, s));
       {  // fc1 + GELU, pre-activation kept            (drct.py:185-186)
-        GemmParams p = fwd_gemm(h, sw.fc1, sv.xn2, d, T, sv.hact, sw.hidden);
+        GemmParams p = drct_gemm(h, sw.fc1, sv.xn2, d, T, sv.hact, sw.hidden);
         p.act = SRAD_ACT_GELU; p.Ypre = sv.hpre;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       {  // x2 = x1 + drop_path(fc2(.))                (drct.py:188, 510)
-        GemmParams p = fwd_gemm(h, sw.fc2, sv.hact, sw.hidden, T, sv.x2, d);
+        GemmParams p = drct_gemm(h, sw.fc2, sv.hact, sw.hidden, T, sv.x2, d);
         p.R = sv.x1; p.ldr = d; p.row_scale = ks2; p.rps = HW;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       if (k < 4) {                                      // (drct.py:389-392)
-        GemmParams p = fwd_gemm(h, sw.adjust, sv.x2, d, T, cur, D);
+        GemmParams p = drct_gemm(h, sw.adjust, sv.x2, d, T, cur, D);
         p.yoff = d; p.act = SRAD_ACT_LRELU; p.slope = 0.2f;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       } else {                                          // (drct.py:393, 396)
-        GemmParams p = fwd_gemm(h, sw.adjust, sv.x2, d, T, nxt, D);
+        GemmParams p = drct_gemm(h, sw.adjust, sv.x2, d, T, nxt, D);
         p.alpha = 0.2f; p.R = cur; p.ldr = D;
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
     }
   }
-  SRAD_TRY(srad_launch_layernorm(w.dense[c.n_rdg], D, w.body, E, T, E, h->pt.fptr(h->norm_g), h->pt.fptr(h->norm_b), 1e-5f, s));
-  {
-    GemmParams p = fwd_gemm(h, h->conv_after_body, w.body, E, T, w.c1, E);
-    geom(p, H, W); p.R = w.feat0; p.ldr = E;
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-  }
-  {
-    GemmParams p = fwd_gemm(h, h->conv_before_up, w.c1, E, T, w.c2, F);
-    geom(p, H, W); p.act = SRAD_ACT_LRELU; p.slope = 0.01f;
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-  }
-  const float* src = w.c2;
-  int hh = H, ww = W;
-  for (size_t j = 0; j < h->up.size(); ++j) {
-    GemmParams p = fwd_gemm(h, h->up[j], src, F, B * hh * ww, w.upb[j], F);
-    geom(p, hh, ww); p.ps = 2;
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-    src = w.upb[j]; hh *= 2; ww *= 2;
-  }
-  {
-    GemmParams p = fwd_gemm(h, h->conv_last, src, F, B * hh * ww, w.outn, SRAD_IMG_CPAD);
-    geom(p, hh, ww);
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-  }
-  return srad_launch_nhwc_to_nchw(w.outn, SRAD_IMG_CPAD, y, B, c.in_chans, hh, ww, mean3, 1.0f / c.img_range, s);
+  return drct_tail(h, w.dense[c.n_rdg], B, H, W, w, SRAD_IMG_CPAD, y, s);
 }
 
 // Backward of srad_drct_forward_train.  dy [B,C,H*s,W*s] is dLoss/dy; parameter gradients are ACCUMULATED

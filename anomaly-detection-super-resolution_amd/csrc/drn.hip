@@ -419,39 +419,52 @@ GemmParams conv_params(const srad_drn* h, const ConvW& c, const float* X, int ld
   return p;
 }
 
-struct DrnWs {
-  float* up0;                       // [T0][4]
-  std::vector<float*> cat;          // level L: [T_L][2 F 2^L]
-  float* deep;                      // [T_P][F 2^P]
-  float* dtmp;                      // down-block intermediate
-  float *ra, *rb, *rt, *rr;         // RCAB ping/pong, relu(conv), conv result
-  float* ups;                       // conv + pixel-shuffle output
-  float* timg;                      // tail conv output [T][C]
-  float* pool;                      // [B][DRN_POOL_CHUNKS][chmax] partial sums of the global average pool
-  float* gate;                      // [B][chmax]
+// One RCAB's tensors: relu(conv), the conv result, the block output, and (training) the gate and the pooled sums
+struct RcabSave { float *t, *r, *xo, *gate, *pool; };
+
+// The forward's tensors, which one walk (forward_walk) runs through in both modes.  Inference aliases them onto a few
+// ping-pong buffers (plan_ws); training gives each its own slot, which the backward reads (plan_train_ws).
+struct DrnFwdWs {
+  float *uraw, *up0;                          // [T0][4] the bicubic image before (training only, else null) and after sub_mean
+  std::vector<float*> cat, dtmp;              // per level L: [T_L][2 F 2^L] concat buffer, its down block's stride-2 output
+  float* deep;                                // [T_P][F 2^P]
+  std::vector<std::vector<RcabSave>> rc;      // [up phase][block]
+  std::vector<float*> ups;                    // per up phase: Upsampler conv + pixel-shuffle output
+  std::vector<float*> timg;                   // tail conv outputs [T][ld_timg], P + 1 of them
+  int ld_timg;
+  float* pool;                                // [B][DRN_POOL_MAXCHUNKS][chmax] partial sums of the global average pool
+  bool train;                                 // which bf16 storage rule the RCAB chains follow (chain_store)
   size_t bytes;
 };
 
-DrnWs plan_ws(const srad_drn* h, int B, int H, int W, void* base, size_t cap) {
+DrnFwdWs plan_ws(const srad_drn* h, int B, int H, int W, void* base, size_t cap) {
   const srad_drn_config& c = h->cfg;
   const int P = h->phase, F = c.n_feats, s = c.scale;
   const size_t T0 = (size_t)B * H * s * W * s;
   Bump bp(base, cap);
-  DrnWs w;
+  DrnFwdWs w;
+  w.train = false;
+  w.uraw = nullptr;
   w.up0 = bp.take(T0 * SRAD_IMG_CPAD);
   const int F0 = srad_round_up(F, 4);                 // level-0 channel count as stored (x8 preset: 10 -> 12)
   for (int L = 0; L < P; ++L) w.cat.push_back(bp.take((T0 >> (2 * L)) * 2 * (L == 0 ? F0 : F << L)));
   const size_t TP = T0 >> (2 * P);
   const int top = F << P;
   w.deep = bp.take(TP * top);
-  w.dtmp = bp.take((T0 >> 2) * F0);                    // largest: level 0 stride-2 output [T0/4][F]
+  w.dtmp.assign(P, bp.take((T0 >> 2) * F0));          // largest: level 0 stride-2 output [T0/4][F]
   // RCAB stacks: idx 0 at level P (top channels), idx >= 1 at level P-idx with 2 F 2^(P-idx) channels
   size_t rmax = TP * top;
   for (int idx = 1; idx < P; ++idx) {
     const size_t e = (T0 >> (2 * (P - idx))) * 2 * F * (1 << (P - idx));
     if (e > rmax) rmax = e;
   }
-  w.ra = bp.take(rmax); w.rb = bp.take(rmax); w.rt = bp.take(rmax); w.rr = bp.take(rmax);
+  float* const ra = bp.take(rmax);
+  float* const rb = bp.take(rmax);
+  float* const rt = bp.take(rmax);
+  float* const rr = bp.take(rmax);
+  w.rc.assign(P, std::vector<RcabSave>(c.n_blocks));
+  for (int idx = 0; idx < P; ++idx)
+    for (int b = 0; b < c.n_blocks; ++b) w.rc[idx][b] = RcabSave{rt, rr, b & 1 ? rb : ra, nullptr, nullptr};
   // Upsampler output (before the 1x1): 4x the pixels of its level, same channels
   size_t umax = 0;
   for (int idx = 0; idx < P; ++idx) {
@@ -460,28 +473,38 @@ DrnWs plan_ws(const srad_drn* h, int B, int H, int W, void* base, size_t cap) {
     const size_t e = (T0 >> (2 * (lvl - 1))) * cin;
     if (e > umax) umax = e;
   }
-  w.ups = bp.take(umax);
-  w.timg = bp.take(T0 * SRAD_IMG_CPAD);
+  w.ups.assign(P, bp.take(umax));
+  w.timg.assign(P + 1, bp.take(T0 * SRAD_IMG_CPAD));
+  w.ld_timg = c.n_colors;
   w.pool = bp.take((size_t)B * DRN_POOL_MAXCHUNKS * top);
-  w.gate = bp.take((size_t)B * top);
+  bp.take((size_t)B * top);                           // [B][chmax], unused: the workspace size is part of the ABI
   w.bytes = bp.used;
   return w;
 }
 
-int tail_out(srad_drn* h, const ConvW& t, const float* X, int ldx, int B, int Hh, int Ww, const DrnWs& w, float* y,
-             hipStream_t s) {
-  const int C = h->cfg.n_colors;
-  GemmParams p = conv_params(h, t, X, ldx, B, Hh, Ww, 1, w.timg, C, 0);
-  SRAD_TRY(srad_launch_gemm(h->cfg.precision, p, s));
-  const size_t tot = (size_t)B * Hh * Ww;
-  SradProfScope prof(s, SRAD_K_LAYOUT, 2.0 * tot * C * C, 8.0 * tot * C);
-  hipLaunchKernelGGL(affine_to_nchw_kernel, dim3(grid1d(tot)), dim3(256), 0, s, w.timg, C, y, B, C, Hh * Ww,
-                     h->pt.fptr(h->add_w), h->pt.fptr(h->add_b));
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
+// Which RCAB tensors of a level are bf16 arrays - every pass of the chain is bandwidth-side work, and the MFMA operands are
+// bf16 anyway.  t: relu(conv), which only the second convolution reads; r: the conv result and the chain tensor between the
+// blocks.  The level's input and its last block's output (the generic GEMMs' operands) stay fp32.
+//  - inference: t when both convolutions take conv80, r too when the conv's epilogue also writes the pool sums;
+//  - training: the whole chain by drn_level_bf16, decided from the shape alone so that the backward agrees.
+struct ChainStore { bool t, r; };
+ChainStore chain_store(const srad_drn* h, const DrnFwdWs& w, int idx, int B, int Hl, int Wl, const float* xin, int ldin) {
+  const int prec = h->cfg.precision, ch = h->rcab[idx][0].ch;
+  if (w.train) {
+    const bool lh = drn_level_bf16(prec, B, Hl, Wl, ch);
+    return {lh, lh};
+  }
+  const RcabW& r = h->rcab[idx][0];
+  const RcabSave& sv = w.rc[idx][0];
+  GemmParams p = conv_params(h, r.c0, xin, ldin, B, Hl, Wl, 1, sv.t, ch, 0);
+  p.act = SRAD_ACT_RELU;
+  const GemmParams q = conv_params(h, r.c1, sv.t, ch, B, Hl, Wl, 1, sv.r, ch, 0);
+  const bool t = srad_conv80_supported(prec, p) && srad_conv80_supported(prec, q);
+  return {t, t && pool_rows_per_image(prec, q, Hl * Wl) > 0};
 }
 
-int forward_body(srad_drn* h, const float* x, int B, int H, int W, float* const* ys, const DrnWs& w, hipStream_t s) {
+// DRN.forward (drn.py:241-270) on the tensors of `w`: the same launches in both modes
+int forward_walk(srad_drn* h, const float* x, int B, int H, int W, float* const* ys, const DrnFwdWs& w, hipStream_t s) {
   const srad_drn_config& c = h->cfg;
   const int prec = c.precision, P = h->phase, F = c.n_feats, sc = c.scale, C = c.n_colors;
   const int H0 = H * sc, W0 = W * sc;
@@ -492,7 +515,7 @@ int forward_body(srad_drn* h, const float* x, int B, int H, int W, float* const*
     const size_t tot = (size_t)B * H0 * W0;
     SradProfScope prof(s, SRAD_K_MISC, 40.0 * tot * C, 4.0 * tot * (4 + C));
     hipLaunchKernelGGL(bicubic_submean_kernel, dim3(grid1d(tot)), dim3(256), 0, s, x, w.up0, B, C, H, W, sc,
-                       h->pt.fptr(h->sub_w), h->pt.fptr(h->sub_b), (float*)nullptr);
+                       h->pt.fptr(h->sub_w), h->pt.fptr(h->sub_b), w.uraw);
     SRAD_CHECK_HIP(hipGetLastError());
   }
   // head -> copies[0], stored in cat[0][:, F:2F]               (drn.py:247, 252)
@@ -504,17 +527,27 @@ int forward_body(srad_drn* h, const float* x, int B, int H, int W, float* const*
   // down phases                                               (drn.py:250-253, 83-119)
   for (int L = 0; L < P; ++L) {
     const int f = L == 0 ? F0 : F << L, Hl = H0 >> L, Wl = W0 >> L;
-    GemmParams p = conv_params(h, h->down_s2[L], w.cat[L] + f, 2 * f, B, Hl, Wl, 2, w.dtmp, f, 0);
+    GemmParams p = conv_params(h, h->down_s2[L], w.cat[L] + f, 2 * f, B, Hl, Wl, 2, w.dtmp[L], f, 0);
     p.act = SRAD_ACT_LRELU; p.slope = c.negval;
     SRAD_TRY(srad_launch_gemm(prec, p, s));
     float* dst = L + 1 < P ? w.cat[L + 1] : w.deep;
     const int f1 = F << (L + 1);
     const int ldd = L + 1 < P ? 2 * f1 : f1, off = L + 1 < P ? f1 : 0;
-    GemmParams q = conv_params(h, h->down_s1[L], w.dtmp, f, B, Hl / 2, Wl / 2, 1, dst, ldd, off);
+    GemmParams q = conv_params(h, h->down_s1[L], w.dtmp[L], f, B, Hl / 2, Wl / 2, 1, dst, ldd, off);
     SRAD_TRY(srad_launch_gemm(prec, q, s));
   }
-  // coarsest output                                           (drn.py:256-258)
-  SRAD_TRY(tail_out(h, h->tail[0], w.deep, top, B, H0 >> P, W0 >> P, w, ys[0], s));
+  // output j: tail conv + add_mean, NHWC -> NCHW              (drn.py:256-258, 265-267)
+  auto tail_out = [&](int j, const float* X, int ldx, int Hh, int Ww) -> int {
+    GemmParams p = conv_params(h, h->tail[j], X, ldx, B, Hh, Ww, 1, w.timg[j], w.ld_timg, 0);
+    SRAD_TRY(srad_launch_gemm(prec, p, s));
+    const size_t tot = (size_t)B * Hh * Ww;
+    SradProfScope prof(s, SRAD_K_LAYOUT, 2.0 * tot * C * C, 8.0 * tot * C);
+    hipLaunchKernelGGL(affine_to_nchw_kernel, dim3(grid1d(tot)), dim3(256), 0, s, w.timg[j], w.ld_timg, ys[j], B, C, Hh * Ww,
+                       h->pt.fptr(h->add_w), h->pt.fptr(h->add_b));
+    SRAD_CHECK_HIP(hipGetLastError());
+    return SRAD_OK;
+  };
+  SRAD_TRY(tail_out(0, w.deep, top, H0 >> P, W0 >> P));
 
   const float* xin = w.deep;
   int ldin = top;
@@ -523,70 +556,62 @@ int forward_body(srad_drn* h, const float* x, int B, int H, int W, float* const*
     const int Hl = H0 >> lvl, Wl = W0 >> lvl;
     const int ch = h->rcab[idx][0].ch;
     const size_t T = (size_t)B * Hl * Wl;
-    float* cur = w.ra;
-    float* nxt = w.rb;
-    // bf16 along the chain (bf16 mode, both convolutions on conv80, pool sums from the conv's epilogue): relu(conv), the conv
-    // result AND the chain tensor between the blocks are bf16 arrays - every pass of the chain is bandwidth-side work, and the
-    // MFMA operands are bf16 anyway.  The level's input and its last block's output (the generic GEMMs' operands) stay fp32.
+    const ChainStore st = chain_store(h, w, idx, B, Hl, Wl, xin, ldin);
     bool x_h = false;                                          // xin is a bf16 array
     for (int b = 0; b < c.n_blocks; ++b) {
       const RcabW& r = h->rcab[idx][b];
-      bool t_bf16 = false;      // the ReLU output between the two convolutions as bf16 (only the second conv reads it) when both take conv80
+      const RcabSave& sv = w.rc[idx][b];
       {  // conv + ReLU                                         (drn.py:147-150)
-        GemmParams p = conv_params(h, r.c0, x_h ? nullptr : xin, ldin, B, Hl, Wl, 1, w.rt, ch, 0);
+        GemmParams p = conv_params(h, r.c0, x_h ? nullptr : xin, ldin, B, Hl, Wl, 1, sv.t, ch, 0);
         if (x_h) p.Xh = reinterpret_cast<const __bf16*>(xin);
         p.act = SRAD_ACT_RELU;
-        GemmParams q = conv_params(h, r.c1, w.rt, ch, B, Hl, Wl, 1, w.rr, ch, 0);
-        t_bf16 = srad_conv80_supported(prec, p) && srad_conv80_supported(prec, q);
-        SRAD_REQUIRE(t_bf16 || !x_h, "drn_forward: the bf16 chain tensor needs the 80-channel conv kernel");
-        if (t_bf16) p.Yh = reinterpret_cast<__bf16*>(w.rt);
+        if (st.t) {
+          p.Yh = reinterpret_cast<__bf16*>(sv.t);
+          SRAD_REQUIRE(srad_conv80_supported(prec, p), "drn forward: bf16 chain without the 80-channel conv kernel");
+        }
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       int nchunk = DRN_POOL_CHUNKS;
-      bool nchunk_fused = false;
       {  // conv; its epilogue also leaves the global average pool's partial sums, one row per row tile  (drn.py:147-150, 127)
-        GemmParams p = conv_params(h, r.c1, w.rt, ch, B, Hl, Wl, 1, w.rr, ch, 0);
-        if (t_bf16) { p.Xh = reinterpret_cast<const __bf16*>(w.rt); p.Yh = reinterpret_cast<__bf16*>(w.rr); }   // r as bf16 too: the pool sums come from the fp32 values in the epilogue
+        GemmParams p = conv_params(h, r.c1, sv.t, ch, B, Hl, Wl, 1, sv.r, ch, 0);
+        if (st.t) p.Xh = reinterpret_cast<const __bf16*>(sv.t);
+        if (st.r) p.Yh = reinterpret_cast<__bf16*>(sv.r);    // the pool sums come from the fp32 values in the epilogue
         nchunk = pool_rows_per_image(prec, p, Hl * Wl);
-        nchunk_fused = nchunk > 0;
         if (nchunk > 0) p.pool_part = w.pool;
-        else p.Yh = nullptr;                                      // the separate pooling pass reads r as fp32
+        SRAD_REQUIRE(!st.r || (nchunk > 0 && srad_conv80_supported(prec, p)), "drn forward: bf16 chain without the conv epilogue's pool sums");
         SRAD_TRY(srad_launch_gemm(prec, p, s));
       }
       if (nchunk == 0) {  // global average pool (partial rows) as a pass of its own                          (drn.py:127-138)
         nchunk = DRN_POOL_CHUNKS;
         SradProfScope prof(s, SRAD_K_MISC, 1.0 * T * ch + 4.0 * B * ch * (ch / 16), 4.0 * T * ch);
-        hipLaunchKernelGGL(pool_dot_kernel<false>, dim3(DRN_POOL_CHUNKS, B), dim3(256), 0, s, (const float*)nullptr, w.rr, w.pool, Hl * Wl, ch,
+        hipLaunchKernelGGL(pool_dot_kernel<false>, dim3(DRN_POOL_CHUNKS, B), dim3(256), 0, s, (const float*)nullptr, sv.r, w.pool, Hl * Wl, ch,
                            DRN_POOL_CHUNKS);
       }
-      const bool r_h = t_bf16 && nchunk_fused;
-      SRAD_REQUIRE(r_h || !x_h, "drn_forward: the bf16 chain tensor needs the conv epilogue's pool sums");
-      const bool y_h = r_h && b + 1 < c.n_blocks;   // the next block's conv80 reads it (same shape: supported there too)
+      const bool y_h = st.r && b + 1 < c.n_blocks;   // the next block's conv80 reads it (same shape: supported there too)
       {  // the gate, and res = body(x) * gate + x               (drn.py:128-139, 156-157)
-        SradProfScope prof(s, SRAD_K_MISC, 2.0 * T * ch, (double)((r_h ? 2 : 4) + (x_h ? 2 : 4) + (y_h ? 2 : 4)) * T * ch);
-        launch_ca_scale_add(r_h, x_h, y_h, ca_slices(Hl * Wl), B, Hl * Wl, ch, s, (const float*)w.pool, nchunk, 1.0f / (float)(Hl * Wl), ch, ch / 16,
+        SradProfScope prof(s, SRAD_K_MISC, 2.0 * T * ch, (double)((st.r ? 2 : 4) + (x_h ? 2 : 4) + (y_h ? 2 : 4)) * T * ch);
+        launch_ca_scale_add(st.r, x_h, y_h, ca_slices(Hl * Wl), B, Hl * Wl, ch, s, (const float*)w.pool, nchunk, 1.0f / (float)(Hl * Wl), ch, ch / 16,
                             (const float*)h->pt.fptr(r.w1), (const float*)h->pt.fptr(r.b1), (const float*)h->pt.fptr(r.w2), (const float*)h->pt.fptr(r.b2),
-                            (float*)nullptr, (float*)nullptr, (const float*)w.rr, (const float*)xin, ldin, (float*)cur, Hl * Wl);
+                            sv.gate, sv.pool, (const float*)sv.r, xin, ldin, sv.xo, Hl * Wl);
       }
       SRAD_CHECK_HIP(hipGetLastError());
-      xin = cur; ldin = ch; x_h = y_h;
-      float* t = cur; cur = nxt; nxt = t;
+      xin = sv.xo; ldin = ch; x_h = y_h;
     }
     // Upsampler: conv ch -> 4 ch + PixelShuffle(2), then the 1x1 reducing conv into cat[lvl-1][:, :cout]
     const int cout = lvl == 1 ? F0 : F << (lvl - 1);
     {
-      GemmParams p = conv_params(h, h->up_conv[idx], xin, ldin, B, Hl, Wl, 1, w.ups, ch, 0);
+      GemmParams p = conv_params(h, h->up_conv[idx], xin, ldin, B, Hl, Wl, 1, w.ups[idx], ch, 0);
       p.ps = 2;
       SRAD_TRY(srad_launch_gemm(prec, p, s));
     }
     {
-      GemmParams p = conv_params(h, h->up_1x1[idx], w.ups, ch, B, 2 * Hl, 2 * Wl, 1, w.cat[lvl - 1], 2 * cout, 0);
+      GemmParams p = conv_params(h, h->up_1x1[idx], w.ups[idx], ch, B, 2 * Hl, 2 * Wl, 1, w.cat[lvl - 1], 2 * cout, 0);
       SRAD_TRY(srad_launch_gemm(prec, p, s));
     }
     // torch.cat((x, copies[..]), 1) is cat[lvl-1] as it stands  (drn.py:263)
     xin = w.cat[lvl - 1];
     ldin = 2 * cout;
-    SRAD_TRY(tail_out(h, h->tail[idx + 1], xin, ldin, B, 2 * Hl, 2 * Wl, w, ys[idx + 1], s));
+    SRAD_TRY(tail_out(idx + 1, xin, ldin, 2 * Hl, 2 * Wl));
   }
   return SRAD_OK;
 }
@@ -718,12 +743,12 @@ int srad_drn_forward(srad_drn_t* h, const float* x, int B, int H, int W, float* 
   if (!h->pt.arena) return srad_set_error(SRAD_ERR_STATE, "drn_forward: no weight arena bound");
   SRAD_TRY(drn_check_shape(h, B, H, W));
   SRAD_REQUIRE(((uintptr_t)workspace & 255) == 0, "drn_forward: workspace must be 256-byte aligned");
-  const DrnWs w = plan_ws(h, B, H, W, workspace, workspace_bytes);
+  const DrnFwdWs w = plan_ws(h, B, H, W, workspace, workspace_bytes);
   SRAD_REQUIRE(w.bytes <= workspace_bytes, "drn_forward: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
   std::vector<float*> outs(ys, ys + n_out);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return srad_run_with_graph(h->gc, h->cfg.use_graph != 0, x, outs.back(), workspace, B, H, W, s,
-                             [&](hipStream_t st) { return forward_body(h, x, B, H, W, outs.data(), w, st); });
+                             [&](hipStream_t st) { return forward_walk(h, x, B, H, W, outs.data(), w, st); });
 }
 
 int srad_drn_flops(const srad_drn_t* h, int B, int H, int W, double* flops) {
@@ -1113,16 +1138,9 @@ __global__ __launch_bounds__(256) void affine_bwd_kernel(const float* __restrict
   }
 }
 
-struct RcabSave { float *t, *r, *xo, *gate, *pool; };
-
-struct DrnTrainWs {
-  float *uraw, *up0, *deep;
-  std::vector<float*> cat, dtmp, ups, timg;
-  std::vector<std::vector<RcabSave>> rc;
-  // backward
-  float *gdeep, *ga, *gb, *dr2[2], *dt2[2], *dups, *dus, *ddtmp, *zup, *dtimg, *dup0, *ppart, *ppart2[2], *dpool2[2];   // dr / dt / pool_dot rows double-buffered (two streams)
+struct DrnTrainWs : DrnFwdWs {   // the forward's tensors, then the backward's
+  float *gdeep, *ga, *gb, *dr2[2], *dt2[2], *dups, *dus, *ddtmp, *zup, *dtimg, *dup0, *ppart2[2], *dpool2[2];   // dr / dt / pool_dot rows double-buffered (two streams)
   std::vector<float*> gcat;
-  size_t bytes;
 };
 
 DrnTrainWs plan_train_ws(const srad_drn* h, int B, int H, int W, void* base, size_t cap) {
@@ -1133,6 +1151,7 @@ DrnTrainWs plan_train_ws(const srad_drn* h, int B, int H, int W, void* base, siz
   const size_t T0 = (size_t)B * H * s * W * s;
   Bump bp(base, cap);
   DrnTrainWs w;
+  w.train = true;
   w.uraw = bp.take(T0 * SRAD_IMG_CPAD);
   w.up0 = bp.take(T0 * SRAD_IMG_CPAD);
   for (int L = 0; L < P; ++L) w.cat.push_back(bp.take((T0 >> (2 * L)) * 2 * fw(L)));
@@ -1156,6 +1175,7 @@ DrnTrainWs plan_train_ws(const srad_drn* h, int B, int H, int W, void* base, siz
     if (4 * T * ch > umax) umax = 4 * T * ch;
   }
   for (int j = 0; j <= P; ++j) w.timg.push_back(bp.take((T0 >> (2 * (P - j))) * SRAD_IMG_CPAD));
+  w.ld_timg = SRAD_IMG_CPAD;
   // backward
   for (int L = 0; L < P; ++L) w.gcat.push_back(bp.take((T0 >> (2 * L)) * 2 * fw(L)));
   w.gdeep = bp.take(TP * top);
@@ -1166,8 +1186,8 @@ DrnTrainWs plan_train_ws(const srad_drn* h, int B, int H, int W, void* base, siz
   w.zup = bp.take(T0 * F0);
   w.dtimg = bp.take(T0 * SRAD_IMG_CPAD);
   w.dup0 = bp.take(T0 * SRAD_IMG_CPAD);
-  w.ppart = bp.take((size_t)B * DRN_POOL_MAXCHUNKS * top);
-  w.ppart2[0] = w.ppart;                                   // the backward's pool_dot rows (DRN_POOL_CHUNKS per image): the forward's are spent
+  w.pool = bp.take((size_t)B * DRN_POOL_MAXCHUNKS * top);
+  w.ppart2[0] = w.pool;                                    // the backward's pool_dot rows (DRN_POOL_CHUNKS per image): the forward's are spent
   w.ppart2[1] = bp.take((size_t)B * DRN_POOL_CHUNKS * top);
   for (int i = 0; i < 2; ++i) w.dpool2[i] = bp.take((size_t)B * top);
   w.bytes = bp.used;
@@ -1271,104 +1291,7 @@ int srad_drn_forward_train(srad_drn_t* h, const float* x, int B, int H, int W, f
   SRAD_REQUIRE(((uintptr_t)workspace & 255) == 0, "drn_forward_train: workspace must be 256-byte aligned");
   const DrnTrainWs w = plan_train_ws(h, B, H, W, workspace, workspace_bytes);
   SRAD_REQUIRE(w.bytes <= workspace_bytes, "drn_forward_train: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const srad_drn_config& c = h->cfg;
-  const int prec = c.precision, P = h->phase, F = c.n_feats, sc = c.scale, C = c.n_colors;
-  const int H0 = H * sc, W0 = W * sc, top = F << P;
-  const int F0 = srad_round_up(F, 4);
-  auto fw = [&](int L) { return L == 0 ? F0 : F << L; };  // stored feature width of level L
-  {
-    const size_t tot = (size_t)B * H0 * W0;
-    hipLaunchKernelGGL(bicubic_submean_kernel, dim3(grid1d(tot)), dim3(256), 0, s, x, w.up0, B, C, H, W, sc,
-                       h->pt.fptr(h->sub_w), h->pt.fptr(h->sub_b), w.uraw);
-    SRAD_CHECK_HIP(hipGetLastError());
-  }
-  {
-    GemmParams p = conv_params(h, h->head, w.up0, SRAD_IMG_CPAD, B, H0, W0, 1, w.cat[0], 2 * F0, F0);
-    p.Cin = SRAD_IMG_CPAD;
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-  }
-  for (int L = 0; L < P; ++L) {
-    const int f = fw(L), Hl = H0 >> L, Wl = W0 >> L;
-    GemmParams p = conv_params(h, h->down_s2[L], w.cat[L] + f, 2 * f, B, Hl, Wl, 2, w.dtmp[L], f, 0);
-    p.act = SRAD_ACT_LRELU; p.slope = c.negval;
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-    float* dst = L + 1 < P ? w.cat[L + 1] : w.deep;
-    const int f1 = F << (L + 1);
-    GemmParams q = conv_params(h, h->down_s1[L], w.dtmp[L], f, B, Hl / 2, Wl / 2, 1, dst, L + 1 < P ? 2 * f1 : f1, L + 1 < P ? f1 : 0);
-    SRAD_TRY(srad_launch_gemm(prec, q, s));
-  }
-  auto tail_out = [&](int j, const float* X, int ldx, int Hh, int Ww) -> int {
-    GemmParams p = conv_params(h, h->tail[j], X, ldx, B, Hh, Ww, 1, w.timg[j], SRAD_IMG_CPAD, 0);
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-    const size_t tot = (size_t)B * Hh * Ww;
-    hipLaunchKernelGGL(affine_to_nchw_kernel, dim3(grid1d(tot)), dim3(256), 0, s, w.timg[j], SRAD_IMG_CPAD, ys[j], B, C, Hh * Ww,
-                       h->pt.fptr(h->add_w), h->pt.fptr(h->add_b));
-    SRAD_CHECK_HIP(hipGetLastError());
-    return SRAD_OK;
-  };
-  SRAD_TRY(tail_out(0, w.deep, top, H0 >> P, W0 >> P));
-  const float* xin = w.deep;
-  int ldin = top;
-  for (int idx = 0; idx < P; ++idx) {
-    const int lvl = P - idx, Hl = H0 >> lvl, Wl = W0 >> lvl;
-    const int ch = h->rcab[idx][0].ch;
-    // bf16 chain (drn_level_bf16): relu(conv), the conv result and the block outputs are saved as bf16 arrays in the same slots
-    // (what the MFMAs of the forward AND of the backward read are these bf16 values either way); the level's input and its last
-    // block's output - operands of the generic GEMMs - stay fp32
-    const bool lh = drn_level_bf16(prec, B, Hl, Wl, ch);
-    bool x_h = false;
-    for (int b = 0; b < c.n_blocks; ++b) {
-      const RcabW& r = h->rcab[idx][b];
-      const RcabSave& sv = w.rc[idx][b];
-      {
-        GemmParams p = conv_params(h, r.c0, x_h ? nullptr : xin, ldin, B, Hl, Wl, 1, sv.t, ch, 0);
-        p.act = SRAD_ACT_RELU;
-        if (lh) {
-          if (x_h) p.Xh = reinterpret_cast<const __bf16*>(xin);
-          p.Yh = reinterpret_cast<__bf16*>(sv.t);
-          SRAD_REQUIRE(srad_conv80_supported(prec, p), "drn_forward_train: bf16 chain without the 80-channel conv kernel");
-        }
-        SRAD_TRY(srad_launch_gemm(prec, p, s));
-      }
-      int nchunk = DRN_POOL_CHUNKS;
-      {
-        GemmParams p = conv_params(h, r.c1, sv.t, ch, B, Hl, Wl, 1, sv.r, ch, 0);
-        if (lh) { p.Xh = reinterpret_cast<const __bf16*>(sv.t); p.Yh = reinterpret_cast<__bf16*>(sv.r); }
-        nchunk = pool_rows_per_image(prec, p, Hl * Wl);      // the pool's partial rows from the conv's epilogue when the tiles allow
-        if (nchunk > 0) p.pool_part = w.ppart;
-        SRAD_REQUIRE(!lh || (nchunk > 0 && srad_conv80_supported(prec, p)), "drn_forward_train: bf16 chain without the conv epilogue's pool sums");
-        SRAD_TRY(srad_launch_gemm(prec, p, s));
-      }
-      if (nchunk == 0) {
-        nchunk = DRN_POOL_CHUNKS;
-        hipLaunchKernelGGL(pool_dot_kernel<false>, dim3(DRN_POOL_CHUNKS, B), dim3(256), 0, s, (const float*)nullptr, sv.r, w.ppart, Hl * Wl, ch,
-                           DRN_POOL_CHUNKS);
-      }
-      const bool y_h = lh && b + 1 < c.n_blocks;
-      {
-        launch_ca_scale_add(lh, x_h, y_h, ca_slices(Hl * Wl), B, Hl * Wl, ch, s, (const float*)w.ppart, nchunk, 1.0f / (float)(Hl * Wl), ch, ch / 16,
-                            (const float*)h->pt.fptr(r.w1), (const float*)h->pt.fptr(r.b1), (const float*)h->pt.fptr(r.w2), (const float*)h->pt.fptr(r.b2),
-                            (float*)sv.gate, (float*)sv.pool, (const float*)sv.r, (const float*)xin, ldin, (float*)sv.xo, Hl * Wl);
-      }
-      SRAD_CHECK_HIP(hipGetLastError());
-      xin = sv.xo; ldin = ch; x_h = y_h;
-    }
-    const int cout = fw(lvl - 1);
-    {
-      GemmParams p = conv_params(h, h->up_conv[idx], xin, ldin, B, Hl, Wl, 1, w.ups[idx], ch, 0);
-      p.ps = 2;
-      SRAD_TRY(srad_launch_gemm(prec, p, s));
-    }
-    {
-      GemmParams p = conv_params(h, h->up_1x1[idx], w.ups[idx], ch, B, 2 * Hl, 2 * Wl, 1, w.cat[lvl - 1], 2 * cout, 0);
-      SRAD_TRY(srad_launch_gemm(prec, p, s));
-    }
-    xin = w.cat[lvl - 1];
-    ldin = 2 * cout;
-    SRAD_TRY(tail_out(idx + 1, xin, ldin, 2 * Hl, 2 * Wl));
-  }
-  return SRAD_OK;
+  return forward_walk(h, x, B, H, W, ys, w, reinterpret_cast<hipStream_t>(stream));
 }
 
 // Backward of srad_drn_forward_train: dys[j] = dLoss/d(output j) (NCHW, null = this output does not enter the loss);
