@@ -106,6 +106,10 @@ _SIG = {
     "srad_anomaly_maps": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "srad_pixel_auc_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
     "srad_pixel_roc_auc": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
+    "srad_mask_regions_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "srad_mask_regions": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "srad_pixel_pro_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "srad_pixel_pro": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, C.c_int64, _P, C.c_size_t, _P]),
     "srad_l1_workspace_bytes": (C.c_int, [C.POINTER(C.c_size_t)]),
     "srad_l1_loss": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     "srad_loss_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),

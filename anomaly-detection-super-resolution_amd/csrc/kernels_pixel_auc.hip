@@ -15,151 +15,16 @@
 // NaN scores sort last and are left out of n_pos, n_neg and twice_U; n_nan counts them, and the host side refuses them.
 #include "engine.h"
 #include "../../include/srad.h"
+#include "pixel_sort.h"
 #include <algorithm>
 #include <math.h>
 
 namespace {
 
-constexpr int kDigitBits = 11, kDigits = 1 << kDigitBits, kPasses = 3;
-constexpr int kSortWaves = 4, kSortRounds = 32, kSortTile = 64 * kSortWaves * kSortRounds;   // 8192 keys per sort tile
-constexpr int kScanItems = 16, kScanTile = 256 * kScanItems;                                 // 4096 values per scan tile
-constexpr uint32_t kNanKey = 0xFFFFFFFFu;
-
-__device__ __forceinline__ uint32_t order_key(float f) {
-  uint32_t b = __float_as_uint(f);
-  if ((b & 0x7FFFFFFFu) > 0x7F800000u) return kNanKey;
-  if (b == 0x80000000u) b = 0u;                                  // -0.0 == +0.0
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// Block-wide scan over 256 threads (Hillis-Steele in LDS): returns the exclusive prefix, `total` = the whole block's.
-template <typename T, typename Op>
-__device__ __forceinline__ T block_scan_excl(T v, T identity, Op op, T* sh, T& total) {
-  const int tid = threadIdx.x;
-  T x = v;
-  sh[tid] = x;
-  __syncthreads();
-#pragma unroll
-  for (int o = 1; o < 256; o <<= 1) {
-    const T y = tid >= o ? sh[tid - o] : identity;
-    __syncthreads();
-    x = op(x, y);
-    sh[tid] = x;
-    __syncthreads();
-  }
-  total = sh[255];
-  const T ex = tid > 0 ? sh[tid - 1] : identity;
-  __syncthreads();                                               // sh may be reused right away
-  return ex;
-}
-struct AddOp { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
-struct MaxOp { template <typename T> __device__ T operator()(T a, T b) const { return a > b ? a : b; } };
-
 __global__ __launch_bounds__(256) void auc_keys_kernel(const float* __restrict__ scores, const uint8_t* __restrict__ labels,
                                                        uint64_t* __restrict__ keys, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     keys[i] = ((uint64_t)order_key(scores[i]) << 1) | (labels[i] != 0 ? 1u : 0u);
-}
-
-// counts[d * n_tiles + tile] = keys of the tile whose digit (at `shift`) is d
-__global__ __launch_bounds__(256) void radix_hist_kernel(const uint64_t* __restrict__ keys, uint32_t* __restrict__ counts, int64_t n,
-                                                         int shift, int n_tiles) {
-  __shared__ uint32_t h[kDigits];
-  for (int d = threadIdx.x; d < kDigits; d += 256) h[d] = 0u;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kSortTile, end = std::min<int64_t>(n, base + kSortTile);
-  for (int64_t i = base + threadIdx.x; i < end; i += 256) atomicAdd(&h[(uint32_t)(keys[i] >> shift) & (kDigits - 1)], 1u);
-  __syncthreads();
-  for (int d = threadIdx.x; d < kDigits; d += 256) counts[(size_t)d * n_tiles + blockIdx.x] = h[d];
-}
-
-// Exclusive scan of a u32 array in place: per-tile sums, one block scanning the tile sums, per-tile scans plus their offset.
-__global__ __launch_bounds__(256) void scan_reduce_kernel(const uint32_t* __restrict__ v, uint32_t* __restrict__ tsum, int64_t m) {
-  __shared__ uint32_t sh[256];
-  const int64_t b = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  uint32_t s = 0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k)
-    if (b + k < m) s += v[b + k];
-  uint32_t total;
-  block_scan_excl<uint32_t>(s, 0u, AddOp{}, sh, total);
-  if (threadIdx.x == 0) tsum[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(256) void scan_top_kernel(uint32_t* __restrict__ tsum, int nt) {
-  __shared__ uint32_t sh[256];
-  uint32_t carry = 0;
-  for (int c0 = 0; c0 < nt; c0 += 256) {
-    const int t = c0 + threadIdx.x;
-    const uint32_t v = t < nt ? tsum[t] : 0u;
-    uint32_t total;
-    const uint32_t ex = block_scan_excl<uint32_t>(v, 0u, AddOp{}, sh, total);
-    if (t < nt) tsum[t] = carry + ex;
-    carry += total;
-  }
-}
-__global__ __launch_bounds__(256) void scan_apply_kernel(uint32_t* __restrict__ v, const uint32_t* __restrict__ tsum, int64_t m) {
-  __shared__ uint32_t sh[256];
-  const int64_t b = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  uint32_t x[kScanItems], s = 0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    x[k] = b + k < m ? v[b + k] : 0u;
-    s += x[k];
-  }
-  uint32_t total;
-  uint32_t run = tsum[blockIdx.x] + block_scan_excl<uint32_t>(s, 0u, AddOp{}, sh, total);
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    if (b + k < m) v[b + k] = run;
-    run += x[k];
-  }
-}
-
-// Stable scatter of one tile: key i of the tile goes to offs[d][tile] + (keys of digit d before it in the tile).  Round r,
-// wave w, lane l holds tile key (r * 4 + w) * 64 + l, so (round, wave, lane) order is input order.
-__global__ __launch_bounds__(256) void radix_scatter_kernel(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst,
-                                                            const uint32_t* __restrict__ offs, int64_t n, int shift, int n_tiles) {
-  __shared__ uint32_t run[kDigits];                              // next free position of each digit
-  __shared__ uint32_t wcnt[kSortWaves][kDigits];                 // keys of each digit in each wave of the current round
-  const int tile = blockIdx.x, lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int d = threadIdx.x; d < kDigits; d += 256) {
-    run[d] = offs[(size_t)d * n_tiles + tile];
-#pragma unroll
-    for (int w = 0; w < kSortWaves; ++w) wcnt[w][d] = 0u;
-  }
-  __syncthreads();
-  const uint64_t lanes_below = (1ull << lane) - 1ull;
-  const int64_t base = (int64_t)tile * kSortTile;
-  for (int r = 0; r < kSortRounds; ++r) {
-    if (base + (int64_t)r * 64 * kSortWaves >= n) break;         // block-uniform
-    const int64_t i = base + (int64_t)(r * kSortWaves + wave) * 64 + lane;
-    const bool valid = i < n;
-    const uint64_t k = valid ? src[i] : 0ull;
-    const uint32_t d = (uint32_t)(k >> shift) & (kDigits - 1);
-    uint64_t same = __builtin_amdgcn_ballot_w64(valid);          // lanes of the wave with the same digit
-#pragma unroll
-    for (int bit = 0; bit < kDigitBits; ++bit) {
-      const bool set = (d >> bit) & 1u;
-      const uint64_t bb = __builtin_amdgcn_ballot_w64(set);
-      same &= set ? bb : ~bb;
-    }
-    const uint32_t rank = (uint32_t)__popcll(same & lanes_below), cnt = (uint32_t)__popcll(same);
-    const bool leader = valid && rank == 0;
-    if (leader) wcnt[wave][d] = cnt;
-    __syncthreads();
-    if (valid) {
-      uint32_t pos = run[d] + rank;
-      for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
-      if (pos < (uint64_t)n) dst[pos] = k;
-    }
-    __syncthreads();
-    if (leader) {
-      atomicAdd(&run[d], cnt);
-      wcnt[wave][d] = 0u;
-    }
-    __syncthreads();
-  }
 }
 
 // ---- the Mann-Whitney scan over the sorted keys, in scan tiles of 4096 (thread t: keys t * 16 .. t * 16 + 15) ----
@@ -349,12 +214,7 @@ int srad_pixel_roc_auc(const float* scores, const uint8_t* labels, int64_t n, ui
   for (int p = 0; p < kPasses; ++p) {
     // key bytes: read twice (histogram, scatter), written once; the count matrix: written, scanned (read + written), read
     SradProfScope prof(s, SRAD_K_SCORE, 0.0, 24.0 * n + 16.0 * L.m);
-    const int shift = p * kDigitBits;
-    hipLaunchKernelGGL(radix_hist_kernel, dim3(L.n_sort_tiles), dim3(256), 0, s, src, offs, n, shift, L.n_sort_tiles);
-    hipLaunchKernelGGL(scan_reduce_kernel, dim3(L.n_count_tiles), dim3(256), 0, s, offs, tsum, L.m);
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(256), 0, s, tsum, L.n_count_tiles);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(L.n_count_tiles), dim3(256), 0, s, offs, tsum, L.m);
-    hipLaunchKernelGGL(radix_scatter_kernel, dim3(L.n_sort_tiles), dim3(256), 0, s, src, dst, offs, n, shift, L.n_sort_tiles);
+    radix_sort_pass(src, dst, offs, tsum, n, p * kDigitBits, L.n_sort_tiles, s);
     std::swap(src, dst);
   }
   {

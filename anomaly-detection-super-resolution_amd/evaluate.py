@@ -190,7 +190,7 @@ def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndar
 def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], bad: Sequence[Tuple[np.ndarray, np.ndarray]],
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
-                     map_ws: int = 0) -> dict:
+                     map_ws: int = 0, aupro: bool = False, pro_fpr_limit: float = 0.3) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
     writes the SR images it produced under ``output_dir/{good,bad}/x{scale}`` (src/evaluate.py:190-224).
@@ -198,7 +198,9 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     Pixel level (off by default): the anomaly maps ``1 - SSIM map`` of each rank's own images at window size ``map_ws``
     (0 = the sweep's best_ws).  ``save_maps``: every rank writes them under ``output_dir/anomaly_maps/{good,bad}``.
     ``pixel_metrics``: with world 1 and a mask for every image (``masks``, good + bad order, as ``load_masks`` returns them)
-    the exact pixel-level ROC-AUC is added as ``auc_pixel``, with ``map_ws``."""
+    the exact pixel-level ROC-AUC is added as ``auc_pixel``, with ``map_ws``.  ``aupro``: under the same conditions the
+    normalised area under the per-region overlap curve up to ``pro_fpr_limit`` is added as ``aupro``, with ``pro_fpr_limit`` and
+    ``map_ws``; the maps are computed once for both."""
     model.eval()                                              # H1: deterministic scoring
     y_true = [0] * len(good) + [1] * len(bad)
     pairs = list(good) + list(bad)
@@ -218,8 +220,9 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     rows = torch.cat([ssim, mse[:, None], psnr[:, None]], dim=1)          # [n_mine, n_ws + 2] float64
     full = gather_score_rows(mine, rows.cpu().numpy(), len(pairs), rank, world)
     if full is None:
-        if save_maps or pixel_metrics:
-            _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, None, world)
+        if save_maps or pixel_metrics or aupro:
+            _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, None, world, aupro,
+                         pro_fpr_limit)
         return {}
     best_ws, best_auc, best_j = sizes[0], -1.0, 0
     for j, ws in enumerate(sizes):
@@ -229,15 +232,18 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     out = dict(best_ws=best_ws, auc_ssim=M.roc_auc(y_true, 1.0 - full[:, best_j]), auc_mse=M.roc_auc(y_true, full[:, -2]),
                auc_psnr=M.roc_auc(y_true, -full[:, -1]), n_images=len(pairs), window_sizes=sizes)
     print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}")
-    if save_maps or pixel_metrics:
-        out.update(_pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world))
+    if save_maps or pixel_metrics or aupro:
+        out.update(_pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
+                                aupro, pro_fpr_limit))
     return out
 
 
-def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world) -> dict:
-    """Anomaly maps of this rank's images; the pixel-level AUC on a single rank.  ``best_ws`` is None off rank 0."""
+def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
+                 aupro=False, pro_fpr_limit=0.3) -> dict:
+    """Anomaly maps of this rank's images; the pixel-level AUC and AU-PRO on a single rank.  ``best_ws`` is None off rank 0."""
+    scored = pixel_metrics or aupro
     if world > 1 and not save_maps:                           # the same branch on every rank: no collective below
-        if pixel_metrics and best_ws is not None:
+        if scored and best_ws is not None:
             print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
         return {}
     ws = int(map_ws)
@@ -252,7 +258,7 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
     if save_maps and output_dir:
         save_anomaly_maps(maps, [names[i] if i < len(names) else f"{i:05d}" for i in mine],
                           ['good' if y_true[i] == 0 else 'bad' for i in mine], output_dir)
-    if not pixel_metrics or best_ws is None:
+    if not scored or best_ws is None:
         return {}
     if world > 1:
         print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
@@ -266,9 +272,14 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
         if tuple(masks[i].shape) != (H, W):
             raise ValueError(f"mask {i} has shape {tuple(masks[i].shape)}, the images are {H}x{W}")
     labels = torch.from_numpy(np.stack([np.asarray(masks[i]) for i in mine])).to(maps.device)
-    auc = M.pixel_roc_auc(maps, labels)
-    print(f"Pixel AUC - SSIM map (ws={ws}): {auc:.4f}")
-    return dict(auc_pixel=auc, map_ws=ws)
+    out = dict(map_ws=ws)
+    if pixel_metrics:
+        out["auc_pixel"] = M.pixel_roc_auc(maps, labels)
+        print(f"Pixel AUC - SSIM map (ws={ws}): {out['auc_pixel']:.4f}")
+    if aupro:
+        out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, pro_fpr_limit), float(pro_fpr_limit)
+        print(f"AU-PRO - SSIM map (ws={ws}, fpr <= {float(pro_fpr_limit):g}): {out['aupro']:.4f}")
+    return out
 
 
 def main(argv=None):
@@ -276,7 +287,7 @@ def main(argv=None):
     from .launch import spawn
     if spawn(_run, getattr(args, "gpus", 1), (args,)):      # --gpus N without a launcher: N fresh ranks (image-parallel)
         return
-    _run(args)
+    return _run(args)                                        # evaluate_on_test's dict ({} off rank 0)
 
 
 def _run(args):
@@ -303,18 +314,20 @@ def _run(args):
     b = list(iter_split(opt.data_root, class_name, 'bad', opt.scale, opt.n_colors))
     out_dir = args.output_dir or (os.path.join(args.run_dir, 'eval_results') if args.run_dir else './workspace/eval_results')
     masks = None
-    if args.pixel_metrics and world == 1:
+    if (args.pixel_metrics or args.aupro) and world == 1:
         masks, missing = load_masks(opt.data_root, class_name, [('good', n) for n, _, _ in g] + [('bad', n) for n, _, _ in b],
                                     [hr.shape[:2] for _, _, hr in g + b])
         if missing:
             print(f"No ground-truth mask for {len(missing)} bad image(s) under test/bad/GT (prepare_mvtec_data --with-masks), "
                   f"e.g. {missing[0]}")
-    evaluate_on_test(opt, model, [(lr, hr) for _, lr, hr in g], [(lr, hr) for _, lr, hr in b], rank, world,
-                     names=[n for n, _, _ in g] + [n for n, _, _ in b], output_dir=out_dir, save_images=args.save_images,
-                     masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws)
+    out = evaluate_on_test(opt, model, [(lr, hr) for _, lr, hr in g], [(lr, hr) for _, lr, hr in b], rank, world,
+                           names=[n for n, _, _ in g] + [n for n, _, _ in b], output_dir=out_dir, save_images=args.save_images,
+                           masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws,
+                           aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

@@ -139,6 +139,84 @@ def pixel_roc_auc(scores: torch.Tensor, labels: torch.Tensor) -> float:
     return float(auc.item())
 
 
+def _mask_stack(masks: torch.Tensor) -> torch.Tensor:
+    """[n,H,W] (or [H,W]) GPU masks of any integer or bool dtype -> contiguous u8 [n,H,W], nonzero = defect."""
+    _need_cuda(masks)
+    m = masks.detach()
+    if m.dim() == 2:
+        m = m[None]
+    if m.dim() != 3 or m.numel() == 0:
+        raise ValueError(f"masks must be a non-empty [n, H, W] tensor, got shape {tuple(masks.shape)}")
+    return (m != 0).to(torch.uint8).contiguous() if m.dtype != torch.uint8 else m.contiguous()
+
+
+def mask_regions(masks: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """Regions of ground-truth masks [n,H,W] (nonzero = defect): the 8-connected components of each image's mask
+    (``scipy.ndimage.label(m_i, structure=np.ones((3, 3)))`` per image).  Returns (int32 [n,H,W] on the GPU: the pixel count of
+    each pixel's region, 0 for ok pixels; the number of regions over all images)."""
+    m = _mask_stack(masks)
+    n, H, W = m.shape
+    size = torch.empty(n, H, W, dtype=torch.int32, device=m.device)     # u32 on the device; sizes stay below 2^31
+    counts = torch.empty(3, dtype=torch.int64, device=m.device)
+    nbytes = C.c_size_t()
+    L.check(L.lib().srad_mask_regions_workspace_bytes(n, H, W, C.byref(nbytes)), "mask_regions_workspace_bytes")
+    keep, wp, wb = _ws_buffer(nbytes.value, m.device)
+    L.check(L.lib().srad_mask_regions(L.dptr(m), n, H, W, L.dptr(size), L.dptr(counts), wp, wb, L.current_stream_ptr()),
+            "mask_regions")
+    return size, int(counts[0].item())
+
+
+def _pixel_pro(scores: torch.Tensor, masks: torch.Tensor, fpr_limit: float, curve: bool):
+    lim = float(fpr_limit)
+    if not 0.0 < lim <= 1.0:
+        raise ValueError(f"fpr_limit = {fpr_limit}, must be in (0, 1]")
+    _need_cuda(scores, masks)
+    m = _mask_stack(masks)
+    s = scores.detach().float()
+    if s.dim() == 2:
+        s = s[None]
+    if tuple(s.shape) != tuple(m.shape):
+        raise ValueError(f"scores {tuple(scores.shape)} and masks {tuple(masks.shape)} must have the same shape")
+    s = s.contiguous()
+    n, H, W = m.shape
+    dev = s.device
+    counts = torch.empty(5, dtype=torch.int64, device=dev)              # u64 on the device; the values stay below 2^62
+    out = torch.empty((), dtype=torch.float64, device=dev)
+    cap = n * H * W + 2 if curve else 0                                  # at most one point per distinct score, plus the two ends
+    fpr = torch.empty(cap, dtype=torch.float64, device=dev) if curve else None
+    pro = torch.empty(cap, dtype=torch.float64, device=dev) if curve else None
+    nbytes = C.c_size_t()
+    L.check(L.lib().srad_pixel_pro_workspace_bytes(n, H, W, C.byref(nbytes)), "pixel_pro_workspace_bytes")
+    keep, wp, wb = _ws_buffer(nbytes.value, dev)
+    L.check(L.lib().srad_pixel_pro(L.dptr(s), L.dptr(m), n, H, W, C.c_double(lim), L.dptr(counts), L.dptr(out),
+                                   L.dptr(fpr), L.dptr(pro), C.c_int64(cap), wp, wb,
+                                   L.current_stream_ptr()), "pixel_pro")
+    n_reg, n_ok, _, n_nan, n_pts = counts.tolist()
+    if n_nan:
+        raise ValueError(f"aupro: {n_nan} of {s.numel()} scores are NaN")
+    if n_reg == 0:
+        raise ValueError("aupro: the masks have no defect region; PRO is not defined")
+    if n_ok == 0:
+        raise ValueError("aupro: the masks have no ok pixel; the false-positive rate is not defined")
+    if curve:
+        return fpr[:n_pts].cpu().numpy(), pro[:n_pts].cpu().numpy()
+    return float(out.item())
+
+
+def pro_curve(scores: torch.Tensor, masks: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
+    """The per-region overlap curve of float32 anomaly maps against ground-truth masks, both [n,H,W] GPU tensors (masks of any
+    integer or bool dtype, nonzero = defect): float64 arrays (fpr, pro) with one point per distinct score from the highest down,
+    led by (0, 0) and closed by (1, 1) (DESIGN.md "AU-PRO").  Raises ValueError for NaN scores, masks without a defect region
+    or without an ok pixel, and a shape mismatch."""
+    return _pixel_pro(scores, masks, 1.0, curve=True)
+
+
+def aupro(scores: torch.Tensor, masks: torch.Tensor, fpr_limit: float = 0.3) -> float:
+    """AU-PRO (Bergmann et al., IJCV 2021): the area under ``pro_curve`` for fpr in [0, fpr_limit], divided by fpr_limit.
+    ValueError as ``pro_curve``, and for a limit outside (0, 1]."""
+    return _pixel_pro(scores, masks, fpr_limit, curve=False)
+
+
 def l1_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """nn.L1Loss(reduction='mean') (src/loss.py:84) -> 0-d float64 tensor on the GPU."""
     _need_cuda(a, b)

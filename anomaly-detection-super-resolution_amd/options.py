@@ -228,6 +228,10 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
     p.add_argument('--save-anomaly-maps', action='store_true', default=False,
                    help="write the per-pixel anomaly maps (1 - SSIM map) as <output-dir>/anomaly_maps/{good,bad}/<name>.png")
     p.add_argument('--map-ws', type=int, default=0, help="window size of the anomaly maps; 0 = the image-level sweep's best_ws")
+    p.add_argument('--aupro', action='store_true', default=False,
+                   help="AU-PRO of the anomaly maps against the test/bad/GT masks: the per-region overlap curve's normalised area "
+                        "up to --pro-fpr-limit (needs --gpus 1)")
+    p.add_argument('--pro-fpr-limit', type=float, default=0.3, help="false-positive-rate limit of --aupro, in (0, 1]")
     _with_config(p, pre_args)
     return p.parse_args(argv)
 

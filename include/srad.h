@@ -208,6 +208,26 @@ int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, in
 int srad_pixel_auc_workspace_bytes(int64_t n, size_t* bytes);
 int srad_pixel_roc_auc(const float* scores, const uint8_t* labels, int64_t n, uint64_t* counts_out, double* auc_out,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* Regions of DEVICE u8 masks [n_img, H, W] (nonzero = defect), n_img x H x W in [1, 2^31): the 8-connected components of each
+ * image's mask (scipy.ndimage.label with a 3 x 3 structure, per image; nothing connects across images).
+ *   region_size_out[i] (DEVICE u32) = |region of pixel i|, 0 where mask == 0;
+ *   counts_out (DEVICE, 3 x u64) = {n_regions, n_ok, n_defect}.
+ * Stream-ordered; workspace >= srad_mask_regions_workspace_bytes (4 bytes per pixel). */
+int srad_mask_regions_workspace_bytes(int n_img, int H, int W, size_t* bytes);
+int srad_mask_regions(const uint8_t* masks, int n_img, int H, int W, uint32_t* region_size_out, uint64_t* counts_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* AU-PRO (Bergmann et al., IJCV 2021) of DEVICE float32 scores [n_img, H, W] against DEVICE u8 masks of the same shape: the area
+ * under the per-region overlap curve up to fpr_limit (in (0, 1]), divided by fpr_limit.  Every distinct score is a threshold
+ * (-0.0 == +0.0); the curve is (0,0), (fpr, pro) at each threshold from the highest down, (1,1) (DESIGN.md "AU-PRO").
+ *   counts_out (DEVICE, 5 x u64) = {n_regions, n_ok, n_defect, n_nan, n_curve_points};
+ *   *aupro_out (DEVICE double) = the normalised AU-PRO, NaN when n_regions == 0 or n_ok == 0;
+ *   curve_fpr / curve_pro (DEVICE double, both or neither may be NULL) receive the first min(curve_cap, n_curve_points) points.
+ * NaN scores are left out of the curve and counted in n_nan.  Stream-ordered, no host sync; workspace >=
+ * srad_pixel_pro_workspace_bytes (about 17 bytes per pixel). */
+int srad_pixel_pro_workspace_bytes(int n_img, int H, int W, size_t* bytes);
+int srad_pixel_pro(const float* scores, const uint8_t* masks, int n_img, int H, int W, double fpr_limit, uint64_t* counts_out,
+                   double* aupro_out, double* curve_fpr, double* curve_pro, int64_t curve_cap, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* mean |a-b| (nn.L1Loss, src/loss.py:84) -> *out (device double); workspace >= srad_l1_workspace_bytes */
 int srad_l1_workspace_bytes(size_t* bytes);
