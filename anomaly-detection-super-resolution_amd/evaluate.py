@@ -190,7 +190,8 @@ def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndar
 def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], bad: Sequence[Tuple[np.ndarray, np.ndarray]],
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
-                     map_ws: int = 0, aupro: bool = False, pro_fpr_limit: float = 0.3) -> dict:
+                     map_ws: int = 0, map_sigma: float = 0.0, map_image_score: bool = False, aupro: bool = False,
+                     pro_fpr_limit: float = 0.3) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
     writes the SR images it produced under ``output_dir/{good,bad}/x{scale}`` (src/evaluate.py:190-224).
@@ -200,7 +201,14 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     ``pixel_metrics``: with world 1 and a mask for every image (``masks``, good + bad order, as ``load_masks`` returns them)
     the exact pixel-level ROC-AUC is added as ``auc_pixel``, with ``map_ws``.  ``aupro``: under the same conditions the
     normalised area under the per-region overlap curve up to ``pro_fpr_limit`` is added as ``aupro``, with ``pro_fpr_limit`` and
-    ``map_ws``; the maps are computed once for both."""
+    ``map_ws``; the maps are computed once for both.  ``map_sigma`` > 0: the maps are smoothed once with that Gaussian sigma
+    (``metrics.smooth_maps``) before they are saved or scored, and ``map_sigma`` is added beside ``map_ws``.
+    ``map_image_score``: the ROC-AUC of each image's map maximum as ``auc_map_max``, with ``map_ws``; no masks needed, and
+    with world > 1 every rank's maxima are gathered to rank 0 like the score rows.  A ``map_sigma`` the maps cannot be smoothed
+    with (negative, or a radius above min(128, H, W)) raises ValueError before any image is super-resolved."""
+    if map_sigma and (good or bad):
+        h, w = (list(good) + list(bad))[0][1].shape[:2]
+        M.smooth_radius(map_sigma, h, w)
     model.eval()                                              # H1: deterministic scoring
     y_true = [0] * len(good) + [1] * len(bad)
     pairs = list(good) + list(bad)
@@ -220,9 +228,9 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     rows = torch.cat([ssim, mse[:, None], psnr[:, None]], dim=1)          # [n_mine, n_ws + 2] float64
     full = gather_score_rows(mine, rows.cpu().numpy(), len(pairs), rank, world)
     if full is None:
-        if save_maps or pixel_metrics or aupro:
+        if save_maps or pixel_metrics or aupro or map_image_score:
             _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, None, world, aupro,
-                         pro_fpr_limit)
+                         pro_fpr_limit, map_sigma, map_image_score, rank)
         return {}
     best_ws, best_auc, best_j = sizes[0], -1.0, 0
     for j, ws in enumerate(sizes):
@@ -232,17 +240,19 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     out = dict(best_ws=best_ws, auc_ssim=M.roc_auc(y_true, 1.0 - full[:, best_j]), auc_mse=M.roc_auc(y_true, full[:, -2]),
                auc_psnr=M.roc_auc(y_true, -full[:, -1]), n_images=len(pairs), window_sizes=sizes)
     print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}")
-    if save_maps or pixel_metrics or aupro:
+    if save_maps or pixel_metrics or aupro or map_image_score:
         out.update(_pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                                aupro, pro_fpr_limit))
+                                aupro, pro_fpr_limit, map_sigma, map_image_score, rank))
     return out
 
 
 def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                 aupro=False, pro_fpr_limit=0.3) -> dict:
-    """Anomaly maps of this rank's images; the pixel-level AUC and AU-PRO on a single rank.  ``best_ws`` is None off rank 0."""
+                 aupro=False, pro_fpr_limit=0.3, map_sigma=0.0, map_image_score=False, rank=0) -> dict:
+    """Anomaly maps of this rank's images, smoothed once when ``map_sigma`` > 0; the map-maximum image AUC on any number of
+    ranks; the pixel-level AUC and AU-PRO on a single rank.  ``best_ws`` is None off rank 0.  Every branch that leads to a
+    collective depends only on the flags and ``world``, which all ranks share, so all ranks make the same collective calls."""
     scored = pixel_metrics or aupro
-    if world > 1 and not save_maps:                           # the same branch on every rank: no collective below
+    if world > 1 and not (save_maps or map_image_score):      # the same branch on every rank: no collective below
         if scored and best_ws is not None:
             print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
         return {}
@@ -255,30 +265,47 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
             dist.broadcast_object_list(box, src=0)
             ws = int(box[0])
     maps = M.anomaly_maps(sr, hr, ws)
+    sigma = float(map_sigma)
+    img_max = None
+    if map_image_score:
+        maps, img_max = M.smooth_maps(maps, sigma, with_max=True)
+    elif sigma > 0:
+        maps = M.smooth_maps(maps, sigma)
     if save_maps and output_dir:
         save_anomaly_maps(maps, [names[i] if i < len(names) else f"{i:05d}" for i in mine],
                           ['good' if y_true[i] == 0 else 'bad' for i in mine], output_dir)
+    out = {}
+    if map_image_score:                                       # every rank: one more gather, one column of maxima
+        full = gather_score_rows(mine, img_max.double().cpu().numpy()[:, None], len(y_true), rank, world)
+        if full is not None:
+            out.update(map_ws=ws, auc_map_max=M.roc_auc(y_true, full[:, 0]))
+            print(f"Image AUC - max of the SSIM map (ws={ws}, sigma={sigma:g}): {out['auc_map_max']:.4f}")
+    if sigma > 0 and out:
+        out["map_sigma"] = sigma
     if not scored or best_ws is None:
-        return {}
+        return out
     if world > 1:
         print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
-        return {}
+        return out
     lacking = [i for i in range(len(y_true)) if masks is None or i >= len(masks) or masks[i] is None]
     if lacking:
         print(f"Pixel metrics skipped: {len(lacking)} test image(s) have no ground-truth mask")
-        return {}
+        return out
     H, W = maps.shape[1:]
     for i in mine:
         if tuple(masks[i].shape) != (H, W):
             raise ValueError(f"mask {i} has shape {tuple(masks[i].shape)}, the images are {H}x{W}")
     labels = torch.from_numpy(np.stack([np.asarray(masks[i]) for i in mine])).to(maps.device)
-    out = dict(map_ws=ws)
+    out["map_ws"] = ws
+    if sigma > 0:
+        out["map_sigma"] = sigma
+    tail = f", sigma={sigma:g}" if sigma > 0 else ""
     if pixel_metrics:
         out["auc_pixel"] = M.pixel_roc_auc(maps, labels)
-        print(f"Pixel AUC - SSIM map (ws={ws}): {out['auc_pixel']:.4f}")
+        print(f"Pixel AUC - SSIM map (ws={ws}{tail}): {out['auc_pixel']:.4f}")
     if aupro:
         out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, pro_fpr_limit), float(pro_fpr_limit)
-        print(f"AU-PRO - SSIM map (ws={ws}, fpr <= {float(pro_fpr_limit):g}): {out['aupro']:.4f}")
+        print(f"AU-PRO - SSIM map (ws={ws}, fpr <= {float(pro_fpr_limit):g}{tail}): {out['aupro']:.4f}")
     return out
 
 
@@ -300,6 +327,11 @@ def _run(args):
         scale = inf.get('scale') or scale
     if args.device == 'cpu':
         raise SystemExit("--device cpu is the reference's own path; this build has no CPU fallback")
+    if args.map_sigma and resolution:                         # before the model and the data are loaded
+        try:
+            M.smooth_radius(args.map_sigma, int(resolution), int(resolution))
+        except ValueError as e:
+            raise SystemExit(f"--map-sigma {args.map_sigma:g}: {e}")
     ckpt = resolve_checkpoint(args)
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     if world > 1:
@@ -323,7 +355,8 @@ def _run(args):
     out = evaluate_on_test(opt, model, [(lr, hr) for _, lr, hr in g], [(lr, hr) for _, lr, hr in b], rank, world,
                            names=[n for n, _, _ in g] + [n for n, _, _ in b], output_dir=out_dir, save_images=args.save_images,
                            masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws,
-                           aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit)
+                           aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit, map_sigma=args.map_sigma,
+                           map_image_score=args.map_image_score)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -217,6 +217,61 @@ def aupro(scores: torch.Tensor, masks: torch.Tensor, fpr_limit: float = 0.3) -> 
     return _pixel_pro(scores, masks, fpr_limit, curve=False)
 
 
+def gaussian_weights(sigma: float, truncate: float = 4.0) -> np.ndarray:
+    """The half ``[r:]`` of ``scipy.ndimage._filters._gaussian_kernel1d(sigma, 0, r)`` with ``r = int(truncate * sigma + 0.5)``:
+    float64 [r + 1], the centre weight first.  Computed here, with numpy's exp, so that the device filter uses scipy's weights
+    to the last bit."""
+    sigma = float(sigma)
+    r = int(float(truncate) * sigma + 0.5)
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[r:])
+
+
+def smooth_radius(sigma: float, H: int, W: int, truncate: float = 4.0) -> int:
+    """The radius ``smooth_maps`` filters [.., H, W] maps with at this sigma: ``int(truncate * sigma + 0.5)``, 0 for
+    sigma <= 1e-15.  ValueError for a negative (or NaN) sigma and for a radius above 128 or above min(H, W) (scipy would reflect
+    more than once).  Needs no GPU, so callers can check their arguments before any work."""
+    sigma = float(sigma)
+    if not sigma >= 0.0:
+        raise ValueError(f"smooth_maps: sigma = {sigma}, must be >= 0")
+    if sigma <= 1e-15:
+        return 0
+    r = int(float(truncate) * sigma + 0.5)
+    if r > min(H, W, 128):
+        raise ValueError(f"smooth_maps: sigma = {sigma:g} (truncate {float(truncate):g}) gives radius {r}; the filter takes radii "
+                         f"up to min(128, H, W) = {min(H, W, 128)} for the {H}x{W} maps (one reflection at the edges)")
+    return r
+
+
+def smooth_maps(maps: torch.Tensor, sigma: float, truncate: float = 4.0, with_max: bool = False):
+    """Gaussian smoothing of float32 anomaly maps [n,H,W] on the GPU:
+    ``scipy.ndimage.gaussian_filter(maps, (0, sigma, sigma), mode='reflect', truncate=truncate)`` bit for bit (DESIGN.md
+    "Map smoothing").  ``sigma == 0`` returns the maps unchanged, as scipy does.  With ``with_max`` returns (smoothed, per-image
+    maximum float32 [n], NaN for an image with a NaN pixel).  ValueError for a negative sigma and for a radius
+    ``int(truncate * sigma + 0.5)`` above 128 or above min(H, W) (scipy would reflect more than once)."""
+    _need_cuda(maps)
+    sigma = float(sigma)
+    m = maps.detach()
+    if m.dim() != 3 or m.numel() == 0 or m.dtype != torch.float32:
+        raise ValueError(f"smooth_maps takes a non-empty float32 [n, H, W] tensor, got {m.dtype} {tuple(m.shape)}")
+    m = m.contiguous()
+    n, H, W = m.shape
+    r = smooth_radius(sigma, H, W, truncate)
+    if sigma <= 1e-15 and not with_max:
+        return m                                              # scipy skips an axis with sigma <= 1e-15
+    w = gaussian_weights(sigma, truncate) if r > 0 else np.ones(1)              # radius 0: the kernel copies
+    out = torch.empty_like(m)
+    img_max = torch.empty(n, dtype=torch.float32, device=m.device) if with_max else None
+    nbytes = C.c_size_t()
+    L.check(L.lib().srad_smooth_maps_workspace_bytes(n, H, W, r, C.byref(nbytes)), "smooth_maps_workspace_bytes")
+    keep, wp, wb = _ws_buffer(nbytes.value, m.device)
+    L.check(L.lib().srad_smooth_maps(L.dptr(m), n, H, W, w.ctypes.data_as(C.POINTER(C.c_double)), r, L.dptr(out),
+                                     L.dptr(img_max), wp, wb, L.current_stream_ptr()), "smooth_maps")
+    return (out, img_max) if with_max else out
+
+
 def l1_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """nn.L1Loss(reduction='mean') (src/loss.py:84) -> 0-d float64 tensor on the GPU."""
     _need_cuda(a, b)

@@ -200,6 +200,13 @@ def parse_train_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     return p.parse_args(argv)
 
 
+def _nonnegative_float(text: str) -> float:
+    v = float(text)
+    if not v >= 0.0:                                          # NaN too
+        raise argparse.ArgumentTypeError(f"{text} is not a number >= 0")
+    return v
+
+
 def parse_eval_args(argv=None) -> argparse.Namespace:
     """src/evaluate.py:20-45 (+ --dtype, --gpus)."""
     pre = argparse.ArgumentParser(add_help=False)
@@ -232,6 +239,11 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                    help="AU-PRO of the anomaly maps against the test/bad/GT masks: the per-region overlap curve's normalised area "
                         "up to --pro-fpr-limit (needs --gpus 1)")
     p.add_argument('--pro-fpr-limit', type=float, default=0.3, help="false-positive-rate limit of --aupro, in (0, 1]")
+    p.add_argument('--map-sigma', type=_nonnegative_float, default=0.0,
+                   help="Gaussian sigma (px) the anomaly maps are smoothed with before they are saved or scored "
+                        "(scipy.ndimage.gaussian_filter, truncate 4); 4 is the MVTec convention, 0 = the raw maps")
+    p.add_argument('--map-image-score', action='store_true', default=False,
+                   help="image-level ROC-AUC of each image's anomaly-map maximum (smoothed with --map-sigma); no masks needed")
     _with_config(p, pre_args)
     return p.parse_args(argv)
 

@@ -228,6 +228,18 @@ int srad_pixel_pro_workspace_bytes(int n_img, int H, int W, size_t* bytes);
 int srad_pixel_pro(const float* scores, const uint8_t* masks, int n_img, int H, int W, double fpr_limit, uint64_t* counts_out,
                    double* aupro_out, double* curve_fpr, double* curve_pro, int64_t curve_cap, void* workspace,
                    size_t workspace_bytes, void* stream);
+/* Gaussian smoothing of DEVICE float32 maps [n_img, H, W] (n_img x H x W < 2^31) with a symmetric separable filter of radius
+ * `radius` in [0, 128], radius <= min(H, W) (one half-sample reflection, d c b a | a b c d, at every edge).  weights_host: HOST
+ * array of radius + 1 doubles, w[0] the centre and w[j] the weight at offsets +-j.  Given scipy's weights the result equals
+ * scipy.ndimage.gaussian_filter(maps, (0, s, s), mode='reflect') bit for bit: the pass along H first, its output rounded to
+ * fp32, then the pass along W; in each, acc = x[i] * w[0], then acc = acc + (x[i-j] + x[i+j]) * w[j] for j = radius down to 1 in
+ * fp64 without fused multiply-adds, cast to fp32.  radius 0 copies the maps.  out (DEVICE float32 [n_img, H, W]) must not
+ * overlap maps.  img_max_out (DEVICE float32 [n_img], may be NULL) receives max(out[i]) per image, NaN if any pixel of image i is
+ * NaN.  Stream-ordered and asynchronous: no host sync, no allocation; workspace >= srad_smooth_maps_workspace_bytes (4 bytes
+ * per image). */
+int srad_smooth_maps_workspace_bytes(int n_img, int H, int W, int radius, size_t* bytes);
+int srad_smooth_maps(const float* maps, int n_img, int H, int W, const double* weights_host, int radius, float* out,
+                     float* img_max_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* mean |a-b| (nn.L1Loss, src/loss.py:84) -> *out (device double); workspace >= srad_l1_workspace_bytes */
 int srad_l1_workspace_bytes(size_t* bytes);
