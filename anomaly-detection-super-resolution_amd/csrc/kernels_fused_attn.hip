@@ -25,17 +25,35 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 constexpr int QA_LDP = 80;     // probability tile row stride (2 mod 4 sixteen-byte units: conflict-free for the lane groups of ds_read_b128, see kernels_conv80.hip)
-constexpr int QA_LDB = 68;     // bias table row stride (floats): the 16 keys a float4 read group touches fall on 16 different bank quads
+
+// LDS bytes of one qkv_attn workgroup (layout: see qkv_attn_kernel)
+template <int HDT, int KC, bool SPLIT>
+constexpr size_t qa_lds_bytes() {
+  constexpr int HDP = 16 * HDT, HS = ((HDP + 31) & ~31) + 16;
+  constexpr int XN_E = 64 * (KC * 32 + 16), QKV_E = 3 * 64 * HS, PS_E = 64 * QA_LDP;
+  constexpr int R0_E = SPLIT ? 2 * (XN_E > QKV_E + PS_E ? XN_E : QKV_E + PS_E) : XN_E + QKV_E;
+  return (size_t)R0_E * 2 + (size_t)(640 + 3 * HDP + 232 + 256) * sizeof(float) + 128 * sizeof(int);
+}
 
 // HDT = ceil(head_dim / 16) (2, 3, 4, 5 or 8), KC = ceil(d / 32) 32-wide k chunks (<= 10)
+// WPC = workgroups per CU the instance is built for: 2 caps it at 128 VGPRs (4 waves per SIMD) and its LDS at 80 KB.
 // SPLIT = the split-bf16 mode (SRAD_PREC_BF16X3, inference): the normalised window, q, k, v and the probabilities each exist as a
 // hi and a lo bf16 plane, the weights stream twice (hi pack, lo pack) and every product is three MFMAs (hi.hi + hi.lo + lo.hi).
 // Two planes of everything do not fit next to each other (head dim 122: 208 KB), so q | k | v and P OVERLAY the normalised
 // window: a wave keeps its q | k | v accumulators of all (<= 3) column stages in registers until every wave is done reading
 // the window (one more barrier), then writes them.  The output is fp32.
-template <int HDT, int KC, bool STAMP = false, bool SPLIT = false>
-__global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
-  constexpr int KG = (KC + 7) / 8;         // 256-wide k groups per weight stage
+// QSPLIT = the query split, for launches with fewer (window, head) pairs than CUs: two workgroups per (window, head), grid
+// (windows, 2 heads), blockIdx.y = 2 head + half.  Both normalise the whole window and project k and v for all 64 tokens; each
+// projects q, and runs the softmax and P.V, for its own 32 queries (row tiles 2 half, 2 half + 1) only.  The products, and
+// the order of every sum, are those of the unsplit kernel.
+template <int HDT, int KC, int WPC, bool STAMP = false, bool SPLIT = false, bool QSPLIT = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) void qkv_attn_kernel(const QkvAttnParams p) {
+  static_assert(!(QSPLIT && (STAMP || SPLIT)), "qkv_attn: the query split is built for the bf16 product path only");
+  static_assert(WPC == 1 || (!SPLIT && qa_lds_bytes<HDT, KC, SPLIT>() <= 80 * 1024), "qkv_attn: two workgroups per CU need <= 80 KB of LDS each");
+  constexpr int KG = (KC + 7) / 8;         // k groups (of <= 8 chunks) per weight stage
+  // chunks per k group: 8, but an instance built for two workgroups per CU balances them (9 chunks: 5 + 4 instead of 8 + 1)
+  // so that its three register sets in flight fit in 128 VGPRs; the chunks still accumulate in order 0 .. KC - 1
+  constexpr int CPG = WPC == 2 ? (KC + KG - 1) / KG : 8;
   constexpr int QA_LDX = KC * 32 + 16;     // LDS row stride of the normalised window tile
   constexpr int HDP = 16 * HDT;            // padded head dim
   constexpr int HDP32 = (HDP + 31) & ~31;  // k extent of the q.k^T MFMA steps
@@ -46,13 +64,14 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
   constexpr int NPART = SPLIT ? 2 : 1;                          // weight streams per stage (hi | hi, lo)
   constexpr int n_vst = n_stages * NPART;
   constexpr int XN_E = 64 * QA_LDX, QKV_E = 3 * 64 * HS, PS_E = 64 * QA_LDP;     // bf16 elements per plane
-  constexpr int R0_E = SPLIT ? (2 * XN_E > 2 * (QKV_E + PS_E) ? 2 * XN_E : 2 * (QKV_E + PS_E)) : XN_E + QKV_E + PS_E;
+  constexpr int R0_E = SPLIT ? (2 * XN_E > 2 * (QKV_E + PS_E) ? 2 * XN_E : 2 * (QKV_E + PS_E)) : XN_E + QKV_E;
+  // bf16: the probabilities overlay the normalised window, which is dead once q | k | v are complete
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* XN = reinterpret_cast<__bf16*>(smem);                 // [64][QA_LDX]
   __bf16* XNL = XN + XN_E;                                      // split-bf16: its lo plane
   __bf16* QKV = SPLIT ? XN : XN + XN_E;                         // [3][64][HS] (split-bf16: over the window tile, see above)
   __bf16* QKVL = QKV + QKV_E;
-  __bf16* Ps = SPLIT ? QKVL + QKV_E : QKV + QKV_E;              // [64][QA_LDP] probabilities
+  __bf16* Ps = SPLIT ? QKVL + QKV_E : XN;                       // [64][QA_LDP] probabilities
   __bf16* PsL = Ps + PS_E;
   float* v_g = reinterpret_cast<float*>(XN + R0_E);             // [320] gamma
   float* v_b = v_g + 320;                                       // [320] beta
@@ -60,13 +79,11 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
   float* tbl = v_bias + 3 * HDP;                                // [225] relative position bias of this head
   float* lsum = tbl + 232;                                      // [2][64] softmax denominators of the two key halves
   float* mxs = lsum + 128;                                      // [2][64] row maxima of the two key halves
-  float* BM = mxs + 128;                                        // [64 keys][QA_LDB] bias + shift mask, query-contiguous
-  int* tok = reinterpret_cast<int*>(BM + 64 * QA_LDB);          // [64] token index
+  int* tok = reinterpret_cast<int*>(mxs + 128);                 // [64] token index
   int* inf = tok + 64;                                          // [64] (region << 16) | (py << 8) | px
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  const int rt = wave & 3, chh = wave >> 2;                     // P.V: row tile, column-tile parity
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   const int d = p.d, heads = p.heads, hd = d / heads;
   // diagnostic build only (tools/stamp_bench.py): shader-clock stamps of every wave at the phase boundaries
@@ -80,12 +97,13 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
     }
   };
   stamp(0);
-  // grid = (windows, heads): linear ids of one window's heads differ by a multiple of 8 when the window
-  // count is, so they share an XCD and the window's x rows are fetched into one L2 only
+  // grid = (windows, heads) (query split: (windows, 2 heads)): linear ids of one window's workgroups differ by a multiple of 8
+  // when the window count is, so they share an XCD and the window's x rows are fetched into one L2 only
   // XCD affinity with the kernels before and after (workgroup L runs on XCD L % 8, each XCD has its own L2): XCD k takes
   // windows [k n/8, (k+1) n/8) - a contiguous strip of the images, the same strip whose token rows mlp_block gives XCD k -
   // so the rows this workgroup gathers were mostly written into ITS L2 by the previous launch
-  const int h = blockIdx.y;
+  const int h = QSPLIT ? blockIdx.y >> 1 : blockIdx.y;
+  const int half = QSPLIT ? blockIdx.y & 1 : 0;                 // query split: this workgroup's 32 queries
   int win = blockIdx.x;
   if ((gridDim.x & 7) == 0 && !p.no_xcd_map) win = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   const int ws = 8, nWx = p.W / ws, nW = (p.H / ws) * nWx;
@@ -126,10 +144,10 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
     constexpr int vs = decltype(S)::value < n_vst - 1 ? decltype(S)::value : n_vst - 1;
     constexpr int sc = vs / NPART;
     constexpr int st = sc / KG, kg = sc - st * KG;
-    constexpr int nch = KC - kg * 8 < 8 ? KC - kg * 8 : 8;
+    constexpr int nch = KC - kg * CPG < CPG ? KC - kg * CPG : CPG;
     const bool live = (st * 8 + wave_s) * 16 < NV;
     const char* const Wp = (vs % NPART) == 1 ? Wl : Wh;
-    const char* base = live ? Wp + ((size_t)(st * 8 + wave) * KC + kg * 8) * 1024 + fr * 64 + fq * 16 : Wp;
+    const char* base = live ? Wp + ((size_t)(st * 8 + wave) * KC + kg * CPG) * 1024 + fr * 64 + fq * 16 : Wp;
     const int step = live ? 1024 : 0;
 #pragma unroll
     for (int cc = 0; cc < nch; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + cc * step);
@@ -191,29 +209,13 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
     stamp(3);                                                     // x rows arrived, statistics done
     __syncthreads();                                              // gamma / beta / table / window geometry staged
     stamp(4);
-    {
-      // relative position bias + 0 / -100 shift mask (drct.py:284-292, 449-470) of this head for every (key, query) pair,
-      // once per workgroup: the softmax then adds one float4 per 4 scores instead of unpacking coordinates per score
-      const int k = tid >> 3, q0 = (tid & 7) * 8;
-      const int ki = inf[k], ky = (ki >> 8) & 0xff, kx = ki & 0xff, kr = ki >> 16;
-      float bm[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int qi = inf[q0 + i], qy = (qi >> 8) & 0xff, qx = qi & 0xff, qr = qi >> 16;
-        float v = tbl[(qy - ky + 7) * 15 + (qx - kx + 7)];
-        if (p.shift > 0 && qr != kr) v += -100.0f;
-        bm[i] = v;
-      }
-      *reinterpret_cast<f32x4*>(BM + k * QA_LDB + q0) = f32x4{bm[0], bm[1], bm[2], bm[3]};
-      *reinterpret_cast<f32x4*>(BM + k * QA_LDB + q0 + 4) = f32x4{bm[4], bm[5], bm[6], bm[7]};
-    }
 #pragma unroll
     for (int j = 0; j < KC; ++j) {
       const int c = j * 32 + col4 * 4;
       const f32x4 g4 = *reinterpret_cast<const f32x4*>(v_g + c);
       const f32x4 b4 = *reinterpret_cast<const f32x4*>(v_b + c);
       const f32x4 v = c < d ? (a_reg[j] - mu) * rstd * g4 + b4 : f32x4{0.f, 0.f, 0.f, 0.f};
-      if (p.save_xn && h == 0 && c < d) *reinterpret_cast<f32x4*>(p.save_xn + (size_t)my_tok * d + c) = v;
+      if (p.save_xn && h == 0 && half == 0 && c < d) *reinterpret_cast<f32x4*>(p.save_xn + (size_t)my_tok * d + c) = v;
       bf16x4 hh;
       if constexpr (SPLIT) {
         bf16x4 ll;
@@ -222,7 +224,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
       } else {
         hh[0] = (__bf16)v[0]; hh[1] = (__bf16)v[1]; hh[2] = (__bf16)v[2]; hh[3] = (__bf16)v[3];
       }
-      if (p.save_xn_h && h == 0 && c < d) *reinterpret_cast<bf16x4*>(p.save_xn_h + (size_t)my_tok * d + c) = hh;
+      if (p.save_xn_h && h == 0 && half == 0 && c < d) *reinterpret_cast<bf16x4*>(p.save_xn_h + (size_t)my_tok * d + c) = hh;
       *reinterpret_cast<bf16x4*>(XN + xrow * QA_LDX + c) = hh;
     }
   }
@@ -233,19 +235,25 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
   stamp(7);
 
   // ---- q|k|v = xn . W^T : 128 virtual columns per stage, transposed result (lane: token fr of row tile t, 4 columns) ----
+  // query split: a stage whose 128 columns are all q (head dim 128) runs on this half's two row tiles only, ac[0..1] = row
+  // tiles 2 half, 2 half + 1; a stage that mixes q with k / v columns computes all four and its q rows of the other half go unused
   f32x4 acc[SPLIT ? NS : 1][4];
-  // bias, the attention's scale on q, zero padding -> the bf16 tile(s) the attention reads (and the training saves)
+  // bias, the attention's scale on q, zero padding -> the bf16 tile(s) the attention reads (and the training saves; query
+  // split: each half saves its own q rows, half 0 the k and v rows)
   auto epi_qkv = [&](auto ST, const f32x4 (&a4)[4]) __attribute__((always_inline)) {
     constexpr int st = decltype(ST)::value;
+    constexpr bool qst = QSPLIT && (st + 1) * 128 <= HDP;
     const bool live = (st * 8 + wave_s) * 16 < NV;
     if (live) {
       const int vc = (st * 8 + wave) * 16 + 4 * fq;               // virtual column of element 0
       const int which = vc / HDP, c = vc - which * HDP;           // HDP % 16 == 0: the wave's 16 columns stay in one slice
       const f32x4 bias = *reinterpret_cast<const f32x4*>(v_bias + which * HDP + c);
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        f32x4 v = a4[t] + bias;
-        if (p.save_qkv && c < p.hdp)
+      for (int tt = 0; tt < (qst ? 2 : 4); ++tt) {
+        const int t = qst ? 2 * half + tt : tt;
+        const bool own = !QSPLIT || (which == 0 ? (t >> 1) == half : half == 0);
+        f32x4 v = a4[tt] + bias;
+        if (p.save_qkv && own && c < p.hdp)
           *reinterpret_cast<f32x4*>(p.save_qkv + (size_t)tok[t * 16 + fr] * (3 * heads * p.hdp) + (which * heads + h) * p.hdp + c) = v;
         if (which == 0) v = v * scale;
 #pragma unroll
@@ -260,7 +268,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
           for (int e = 0; e < 4; ++e) hh[e] = (__bf16)v[e];
         }
         *reinterpret_cast<bf16x4*>(QKV + (which * 64 + t * 16 + fr) * HS + c) = hh;
-        if (p.save_qkv_h && c < p.hp_h)
+        if (p.save_qkv_h && own && c < p.hp_h)
           *reinterpret_cast<bf16x4*>(p.save_qkv_h + (size_t)tok[t * 16 + fr] * (3 * heads * p.hp_h) + (which * heads + h) * p.hp_h + c) = hh;
       }
     }
@@ -271,14 +279,14 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
     constexpr int st = s / KG, kg = s - st * KG;
     u32x4 (&reg)[8] = w_reg[vs % NSETS];
     f32x4 (&ac)[4] = acc[SPLIT ? st : 0];
-    constexpr int nch = KC - kg * 8 < 8 ? KC - kg * 8 : 8;
+    constexpr int nch = KC - kg * CPG < CPG ? KC - kg * CPG : CPG;
     const bool live = (st * 8 + wave_s) * 16 < NV;
     if constexpr (kg == 0 && part == 0) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) ac[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if (live) {
-      const __bf16* ar = XN + fr * QA_LDX + kg * 256 + 8 * fq;
+      const __bf16* ar = XN + fr * QA_LDX + kg * CPG * 32 + 8 * fq;
       if constexpr (SPLIT) {
 #pragma unroll
         for (int cc = 0; cc < nch; ++cc) {                          // one chunk's fragments (both planes with the hi weights) in flight, then its MFMAs
@@ -302,14 +310,17 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
       } else {
         // the window fragments of two chunks are requested together, THEN multiplied (sched_barrier: the scheduler otherwise
         // sinks each LDS read to just above its MFMA and the LDS latency is paid per MFMA; see mlp_block_kernel)
+        constexpr bool qst = QSPLIT && (st + 1) * 128 <= HDP;
+        constexpr int NT = qst ? 2 : 4;
+        const __bf16* arq = ar + (qst ? 32 * half : 0) * QA_LDX;
 #pragma unroll
         for (int cc0 = 0; cc0 < nch; cc0 += 2) {
-          bf16x8 af[2][4];
+          bf16x8 af[2][NT];
 #pragma unroll
           for (int g = 0; g < 2; ++g)
             if (cc0 + g < nch) {
 #pragma unroll
-              for (int t = 0; t < 4; ++t) af[g][t] = *reinterpret_cast<const bf16x8*>(ar + t * 16 * QA_LDX + (cc0 + g) * 32);
+              for (int t = 0; t < NT; ++t) af[g][t] = *reinterpret_cast<const bf16x8*>(arq + t * 16 * QA_LDX + (cc0 + g) * 32);
             }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -317,7 +328,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
             if (cc0 + g < nch) {
               const bf16x8 b0 = __builtin_bit_cast(bf16x8, reg[cc0 + g]);
 #pragma unroll
-              for (int t = 0; t < 4; ++t) ac[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, af[g][t], ac[t], 0, 0, 0);
+              for (int t = 0; t < NT; ++t) ac[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, af[g][t], ac[t], 0, 0, 0);
             }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -331,60 +342,88 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
     zero_qk_pad();
     static_for<0, NS>([&](auto ST) { epi_qkv(ST, acc[decltype(ST)::value]); });
   }
+  // ---- softmax roles: wave = (query row tile srt, key half kh), 16 queries x 32 keys each, on all 8 waves (query split: the
+  //      half's two row tiles on waves 0, 1, 4, 5; the others only meet the barriers).  Relative position bias + 0 / -100
+  //      shift mask (drct.py:284-292, 449-470) of the lane's 8 (key, query) pairs straight from the staged table and window
+  //      geometry, read while the other waves finish their columns (no [64][64] table in LDS, no barrier for one) ----
+  const int kh = wave >> 2;
+  const int srt = QSPLIT ? 2 * half + (wave & 1) : wave & 3;
+  const bool s_act = !QSPLIT || (wave_s & 2) == 0;
+  f32x4 bm[2];
+  {
+    int qi[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) qi[e] = inf[srt * 16 + 4 * fq + e];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int ki = inf[(2 * kh + j) * 16 + fr], ky = (ki >> 8) & 0xff, kx = ki & 0xff, kr = ki >> 16;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int qy = (qi[e] >> 8) & 0xff, qx = qi[e] & 0xff, qr = qi[e] >> 16;
+        float v = tbl[(qy - ky + 7) * 15 + (qx - kx + 7)];
+        if (p.shift > 0 && qr != kr) v += -100.0f;
+        bm[j][e] = v;
+      }
+    }
+  }
   stamp(8);                                                       // this wave's q | k | v columns done
-  __syncthreads();                                                // q, k, v complete
+  __syncthreads();                                                // q, k, v complete (bf16: the window tile is dead, P goes over it)
   stamp(9);
 
   const __bf16* Qs = QKV;
   const __bf16* Ks = QKV + 64 * HS;
   const __bf16* Vs = QKV + 2 * 64 * HS;
 
-  // ---- S = q k^T, bias, mask, softmax on all 8 waves: wave = (query row tile rt, key half kh), 16 queries x 32 keys each;
-  //      the two halves of a row exchange their maxima through LDS, so the probabilities are exp(s - row max) as before ----
+  // ---- S = q k^T, bias, mask, softmax: the two key halves of a row exchange their maxima through LDS, so the probabilities
+  //      are exp(s - row max) as before ----
   {
-    const int kh = chh;
+    const int rt = srt;
     f32x4 sc[2];
+    float mx[4];
+    if (s_act) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) sc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < 2; ++j) sc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int kk = 0; kk < HDP32; kk += 32) {
-      const bf16x8 a = *reinterpret_cast<const bf16x8*>(Qs + (rt * 16 + fr) * HS + kk + 8 * fq);
-      [[maybe_unused]] bf16x8 al;
-      if constexpr (SPLIT) al = *reinterpret_cast<const bf16x8*>(Qs + QKV_E + (rt * 16 + fr) * HS + kk + 8 * fq);
+      for (int kk = 0; kk < HDP32; kk += 32) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Qs + (rt * 16 + fr) * HS + kk + 8 * fq);
+        [[maybe_unused]] bf16x8 al;
+        if constexpr (SPLIT) al = *reinterpret_cast<const bf16x8*>(Qs + QKV_E + (rt * 16 + fr) * HS + kk + 8 * fq);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const bf16x8 bb = *reinterpret_cast<const bf16x8*>(Ks + ((2 * kh + j) * 16 + fr) * HS + kk + 8 * fq);
-        if constexpr (SPLIT) {
-          const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Ks + QKV_E + ((2 * kh + j) * 16 + fr) * HS + kk + 8 * fq);
-          sc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bb, sc[j], 0, 0, 0);
-          sc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bl, sc[j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) {
+          const bf16x8 bb = *reinterpret_cast<const bf16x8*>(Ks + ((2 * kh + j) * 16 + fr) * HS + kk + 8 * fq);
+          if constexpr (SPLIT) {
+            const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Ks + QKV_E + ((2 * kh + j) * 16 + fr) * HS + kk + 8 * fq);
+            sc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bb, sc[j], 0, 0, 0);
+            sc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bl, sc[j], 0, 0, 0);
+          }
+          sc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, sc[j], 0, 0, 0);
         }
-        sc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, sc[j], 0, 0, 0);
+      }
+      // lane: queries rt*16 + 4 fq + e (e = 0..3), keys (2 kh + j) * 16 + fr
+#pragma unroll
+      for (int j = 0; j < 2; ++j) sc[j] += bm[j];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        mx[e] = srad_row16_max(fmaxf(sc[0][e], sc[1][e]));
+        if (fr == 0) mxs[kh * 64 + rt * 16 + fq * 4 + e] = mx[e];
       }
     }
-    // lane: queries rt*16 + 4 fq + e (e = 0..3), keys (2 kh + j) * 16 + fr
-    float mx[4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) sc[j] += *reinterpret_cast<const f32x4*>(BM + ((2 * kh + j) * 16 + fr) * QA_LDB + rt * 16 + 4 * fq);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      mx[e] = srad_row16_max(fmaxf(sc[0][e], sc[1][e]));
-      if (fr == 0) mxs[kh * 64 + rt * 16 + fq * 4 + e] = mx[e];
-    }
     __syncthreads();
+    if (s_act) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int row = rt * 16 + fq * 4 + e;
-      const float m = fmaxf(mx[e], mxs[(kh ^ 1) * 64 + row]);
-      const float p0 = __expf(sc[0][e] - m), p1 = __expf(sc[1][e] - m);
-      const float rs = srad_row16_sum(p0 + p1);
-      if (fr == 0) lsum[kh * 64 + row] = rs;
-      const __bf16 p0h = (__bf16)p0, p1h = (__bf16)p1;
-      Ps[row * QA_LDP + (2 * kh) * 16 + fr] = p0h;
-      Ps[row * QA_LDP + (2 * kh + 1) * 16 + fr] = p1h;
-      if constexpr (SPLIT) {
-        PsL[row * QA_LDP + (2 * kh) * 16 + fr] = (__bf16)(p0 - (float)p0h);
-        PsL[row * QA_LDP + (2 * kh + 1) * 16 + fr] = (__bf16)(p1 - (float)p1h);
+      for (int e = 0; e < 4; ++e) {
+        const int row = rt * 16 + fq * 4 + e;
+        const float m = fmaxf(mx[e], mxs[(kh ^ 1) * 64 + row]);
+        const float p0 = __expf(sc[0][e] - m), p1 = __expf(sc[1][e] - m);
+        const float rs = srad_row16_sum(p0 + p1);
+        if (fr == 0) lsum[kh * 64 + row] = rs;
+        const __bf16 p0h = (__bf16)p0, p1h = (__bf16)p1;
+        Ps[row * QA_LDP + (2 * kh) * 16 + fr] = p0h;
+        Ps[row * QA_LDP + (2 * kh + 1) * 16 + fr] = p1h;
+        if constexpr (SPLIT) {
+          PsL[row * QA_LDP + (2 * kh) * 16 + fr] = (__bf16)(p0 - (float)p0h);
+          PsL[row * QA_LDP + (2 * kh + 1) * 16 + fr] = (__bf16)(p1 - (float)p1h);
+        }
       }
     }
   }
@@ -392,12 +431,16 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
   __syncthreads();
   stamp(11);
 
-  // ---- O = P V (transposed result: lane owns token fr of row tile rt, 4 consecutive output columns) ----
+  // ---- O = P V (transposed result: lane owns token fr of row tile rt, 4 consecutive output columns); the output column
+  //      tiles split over the two wave groups (query split: two row tiles, so four groups of two waves) ----
   {
+    constexpr int JG = QSPLIT ? 4 : 2;
+    const int rt = QSPLIT ? 2 * half + (wave & 1) : wave & 3;
+    const int jg = QSPLIT ? wave >> 1 : wave >> 2;
     const int tq = fr >> 2, tp = fr & 3;
 #pragma unroll
     for (int j = 0; j < HDT; ++j) {
-      if ((j & 1) != chh) continue;                               // output column tiles split over the two wave groups
+      if (j % JG != jg) continue;
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kk = 0; kk < 64; kk += 32) {
@@ -443,19 +486,16 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(const QkvAttnParams p) {
   stamp(15);
 }
 
-template <int HDT, int KC, bool STAMP = false, bool SPLIT = false>
+template <int HDT, int KC, int WPC, bool STAMP = false, bool SPLIT = false, bool QSPLIT = false>
 int launch_qa(const QkvAttnParams& p, hipStream_t stream) {
-  constexpr int HDP = 16 * HDT, HS = ((HDP + 31) & ~31) + 16;
-  constexpr int XN_E = 64 * (KC * 32 + 16), QP_E = 3 * 64 * HS + 64 * QA_LDP;
-  constexpr size_t lds = (size_t)(SPLIT ? 2 * (XN_E > QP_E ? XN_E : QP_E) : XN_E + QP_E) * 2 +
-                         (size_t)(640 + 3 * HDP + 232 + 256 + 64 * QA_LDB) * sizeof(float) + 128 * sizeof(int);
+  constexpr size_t lds = qa_lds_bytes<HDT, KC, SPLIT>();
   static_assert(lds <= 160 * 1024, "qkv_attn: LDS budget");
   const double T = (double)p.B * p.H * p.W;
   const double flops = 2.0 * T * 3.0 * p.d * p.d + 4.0 * T * 64.0 * p.d;
   const double bytes = 4.0 * T * p.d * 2 + 2.0 * 3.0 * p.d * p.d;
   SradProfScope prof(stream, SRAD_K_QKV_ATTN, flops, bytes);
   const int nW = (p.H / 8) * (p.W / 8);
-  SRAD_TRY((srad_launch_dyn<qkv_attn_kernel<HDT, KC, STAMP, SPLIT>>(dim3(p.B * nW, p.heads), dim3(512), lds, stream, p)));
+  SRAD_TRY((srad_launch_dyn<qkv_attn_kernel<HDT, KC, WPC, STAMP, SPLIT, QSPLIT>>(dim3(p.B * nW, p.heads * (QSPLIT ? 2 : 1)), dim3(512), lds, stream, p)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
@@ -655,8 +695,8 @@ int launch_ln_qkv(const LnQkvParams& p, hipStream_t stream) {
   return SRAD_OK;
 }
 
-// (head tiles, k chunks) of DRCT-L's five Swin blocks: d = 180/212/244/276/308, heads 6/4/2/6/4
-#define SRAD_QA_CFGS(X) X(2, 6) X(4, 7) X(8, 8) X(3, 9) X(5, 10)
+// (head tiles, k chunks, bf16 workgroups per CU) of DRCT-L's five Swin blocks: d = 180/212/244/276/308, heads 6/4/2/6/4
+#define SRAD_QA_CFGS(X) X(2, 6, 2) X(4, 7, 2) X(8, 8, 1) X(3, 9, 2) X(5, 10, 1)
 #define SRAD_LQ_CFGS(X) X(2, 6, 6) X(4, 7, 4) X(8, 8, 2) X(3, 9, 6) X(5, 10, 4)
 }  // namespace
 
@@ -690,10 +730,37 @@ int srad_launch_ln_qkv(const LnQkvParams& p, hipStream_t stream) {
 bool srad_qkv_attn_supported(int prec, int ws, int H, int W, int d, int heads) {
   if ((prec != SRAD_PREC_BF16 && prec != SRAD_PREC_BF16X3) || ws != 8 || H % 8 || W % 8 || d % 4 || d > 320 || d < 32 || heads < 1 || d % heads) return false;
   const int hdt = (d / heads + 15) / 16, kc = (d + 31) / 32;
-#define X(a, b) if (hdt == a && kc == b) return true;
+#define X(a, b, c) if (hdt == a && kc == b) return true;
   SRAD_QA_CFGS(X)
 #undef X
   return false;
+}
+
+// CUs of the current device (cached per device)
+static int qa_cu_count() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    cus[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+  }
+  return cus[dev];
+}
+
+// the query split (two workgroups per (window, head)) when the plain grid leaves CUs idle; bf16 product path only
+static bool qa_query_split(const QkvAttnParams& p) {
+  return !p.split && !p.stamps && !p.no_qsplit && p.B * (p.H / 8) * (p.W / 8) * p.heads < qa_cu_count();
+}
+
+int srad_qkv_attn_grid(int precision, int B, int H, int W, int d, int heads, int no_qsplit, int* grid_xy) {
+  SRAD_REQUIRE(grid_xy && B > 0, "qkv_attn_grid: bad argument");
+  SRAD_REQUIRE(srad_qkv_attn_supported(precision, 8, H, W, d, heads), "qkv_attn_grid: unsupported shape d=%d heads=%d %dx%d", d, heads, H, W);
+  QkvAttnParams p{};
+  p.B = B; p.H = H; p.W = W; p.d = d; p.heads = heads; p.no_qsplit = no_qsplit; p.split = precision == SRAD_PREC_BF16X3;
+  grid_xy[0] = B * (H / 8) * (W / 8);
+  grid_xy[1] = heads * (qa_query_split(p) ? 2 : 1);
+  return SRAD_OK;
 }
 
 int srad_launch_qkv_attn(const QkvAttnParams& p, hipStream_t stream) {
@@ -704,16 +771,21 @@ int srad_launch_qkv_attn(const QkvAttnParams& p, hipStream_t stream) {
   if (p.split) {                                                  // split-bf16 (inference)
     SRAD_REQUIRE(p.w_qkv_lo && p.out && !p.out_h, "qkv_attn (split-bf16): needs the lo weight pack and an fp32 output");
     SRAD_REQUIRE(!p.stamps && !p.save_xn && !p.save_xn_h && !p.save_qkv && !p.save_qkv_h, "qkv_attn (split-bf16): inference only");
-#define X(a, b) if (hdt == a && kc == b) return launch_qa<a, b, false, true>(p, stream);
+#define X(a, b, c) if (hdt == a && kc == b) return launch_qa<a, b, 1, false, true>(p, stream);
     SRAD_QA_CFGS(X)
 #undef X
   }
-  if (p.stamps) {                                                 // diagnostic build
-#define X(a, b) if (hdt == a && kc == b) return launch_qa<a, b, true>(p, stream);
+  if (p.stamps) {                                                 // diagnostic build (the unsplit grid; its stamps need registers the 128-VGPR bound lacks)
+#define X(a, b, c) if (hdt == a && kc == b) return launch_qa<a, b, 1, true>(p, stream);
     SRAD_QA_CFGS(X)
 #undef X
   }
-#define X(a, b) if (hdt == a && kc == b) return launch_qa<a, b>(p, stream);
+  if (qa_query_split(p)) {
+#define X(a, b, c) if (hdt == a && kc == b) return launch_qa<a, b, c, false, false, true>(p, stream);
+    SRAD_QA_CFGS(X)
+#undef X
+  }
+#define X(a, b, c) if (hdt == a && kc == b) return launch_qa<a, b, c>(p, stream);
   SRAD_QA_CFGS(X)
 #undef X
   return srad_set_error(SRAD_ERR_ARG, "qkv_attn: no kernel instance for head tiles %d, k chunks %d", hdt, kc);

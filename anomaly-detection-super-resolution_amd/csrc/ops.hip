@@ -218,6 +218,27 @@ int srad_op_qkv_attn(int precision, const float* x, int ldx, int B, int H, int W
   return srad_launch_qkv_attn(a, s);
 }
 
+int srad_op_qkv_attn_train(const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, const float* ln_g,
+                           const float* ln_b, const float* w_qkv, const float* b_qkv, const float* table, void* out_h,
+                           float* save_xn, void* save_xn_h, float* save_qkv, int hdp, void* save_qkv_h, int hp_h, int no_qsplit,
+                           void* scratch, size_t scratch_bytes, void* stream) {
+  SRAD_REQUIRE(x && ln_g && ln_b && w_qkv && b_qkv && table && out_h && scratch, "op_qkv_attn_train: null argument");
+  SRAD_REQUIRE(srad_qkv_attn_supported(SRAD_PREC_BF16, 8, H, W, d, heads), "op_qkv_attn_train: unsupported shape d=%d heads=%d %dx%d", d, heads, H, W);
+  SRAD_REQUIRE(!save_qkv || (hdp >= d / heads && hdp % 4 == 0), "op_qkv_attn_train: hdp %d must be a multiple of 4 >= the head dim", hdp);
+  SRAD_REQUIRE(!save_qkv_h || (hp_h >= d / heads && hp_h % 8 == 0), "op_qkv_attn_train: hp_h %d must be a multiple of 8 >= the head dim", hp_h);
+  SRAD_REQUIRE(scratch_bytes >= srad_align_up(srad_qkv_frag_bytes(d, heads), 256) && ((uintptr_t)scratch & 255) == 0,
+               "op_qkv_attn_train: scratch too small or not 256-byte aligned");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  SRAD_TRY(srad_launch_pack_qkv_frag(w_qkv, scratch, d, heads, s));
+  QkvAttnParams a{};
+  a.x = x; a.ldx = ldx; a.ln_g = ln_g; a.ln_b = ln_b; a.w_qkv = scratch; a.b_qkv = b_qkv; a.table = table;
+  a.out_h = reinterpret_cast<__bf16*>(out_h); a.ld_out = d;
+  a.B = B; a.H = H; a.W = W; a.shift = shift; a.d = d; a.heads = heads; a.no_qsplit = no_qsplit;
+  a.save_xn = save_xn; a.save_xn_h = reinterpret_cast<__bf16*>(save_xn_h);
+  a.save_qkv = save_qkv; a.hdp = hdp; a.save_qkv_h = reinterpret_cast<__bf16*>(save_qkv_h); a.hp_h = hp_h;
+  return srad_launch_qkv_attn(a, s);
+}
+
 // Diagnostic twin of srad_bench_mlp_block for the first half: microseconds per launch, back-to-back launches.
 int srad_bench_qkv_attn(const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, const float* w_fp32,
                         void* out, void* scratch, size_t scratch_bytes, int iters, float* us_out, void* stream) {

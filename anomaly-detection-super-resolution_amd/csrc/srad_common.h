@@ -283,6 +283,7 @@ struct QkvAttnParams {
   float* out; int ld_out;                  // attention output [T][d] ...
   __bf16* out_h;                           // ... or, when set, as bf16 (same ld, in elements): the hand-off to mlp_block
   int no_xcd_map;                          // 1: plain workgroup -> window order (A/B of the XCD-affine mapping)
+  int no_qsplit;                           // 1: the plain (windows, heads) grid even where the query split would be chosen (A/B, tests)
   int B, H, W, shift, d, heads;
   // ---- training (optional): what the backward needs ----
   float* save_xn;                          // [T][d] LayerNorm1(x) (written by the head-0 workgroups)

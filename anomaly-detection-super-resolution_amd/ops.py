@@ -397,6 +397,38 @@ def qkv_attn(x: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w_qkv: tor
     return out
 
 
+def qkv_attn_grid(B: int, H: int, W: int, d: int, heads: int, no_qsplit: bool = False, precision: str = "bf16") -> tuple:
+    """The grid (x, y) ``qkv_attn`` and the engines launch for this shape on the current device (``srad_qkv_attn_grid``):
+    (windows, heads), or (windows, 2 heads) for the query split when that leaves fewer workgroups than CUs."""
+    g = (C.c_int * 2)()
+    L.check(L.lib().srad_qkv_attn_grid(L.PRECISIONS[precision], B, H, W, d, heads, int(no_qsplit), g), "qkv_attn_grid")
+    return g[0], g[1]
+
+
+def qkv_attn_train(x: torch.Tensor, ln_g, ln_b, w_qkv, b_qkv, table, B: int, H: int, W: int, shift: int, heads: int,
+                   hdp: int, hp_h: int, no_qsplit: bool = False, fill: float = 0.0) -> dict:
+    """``qkv_attn`` (bf16 out) with every save the training forward can ask for (``srad_op_qkv_attn_train``): LN1(x) as
+    fp32 and bf16 [T, d], q | k | v as fp32 [T, 3, heads, hdp] (q unscaled) and as bf16 [T, 3, heads, hp_h] (as the
+    attention used them).  The save buffers start as ``fill``; ``no_qsplit`` forces the plain (windows, heads) grid."""
+    _need_cuda(x, ln_g, ln_b, w_qkv, b_qkv, table)
+    d = w_qkv.shape[1]
+    T = B * H * W
+    assert x.dim() == 2 and x.shape[0] == T and x.stride(1) == 1 and x.dtype == torch.float32 and w_qkv.shape[0] == 3 * d
+    f = lambda t: t.detach().float().contiguous()
+    keep = [f(ln_g), f(ln_b), f(w_qkv), f(b_qkv), f(table)]
+    dev = x.device
+    r = {"out_h": torch.full((T, d), fill, dtype=torch.bfloat16, device=dev),
+         "xn": torch.full((T, d), fill, dtype=torch.float32, device=dev),
+         "xn_h": torch.full((T, d), fill, dtype=torch.bfloat16, device=dev),
+         "qkv": torch.full((T, 3, heads, hdp), fill, dtype=torch.float32, device=dev),
+         "qkv_h": torch.full((T, 3, heads, hp_h), fill, dtype=torch.bfloat16, device=dev)}
+    sbuf, sp, sb = _scratch(L.lib().srad_op_swin_scratch_bytes(d, heads, 4, 4), dev)
+    L.check(L.lib().srad_op_qkv_attn_train(L.dptr(x), x.stride(0), B, H, W, shift, d, heads, *[L.dptr(k) for k in keep],
+                                           L.dptr(r["out_h"]), L.dptr(r["xn"]), L.dptr(r["xn_h"]), L.dptr(r["qkv"]), hdp,
+                                           L.dptr(r["qkv_h"]), hp_h, int(no_qsplit), sp, sb, L.current_stream_ptr()), "op_qkv_attn_train")
+    return r
+
+
 def mlp_block(attn: torch.Tensor, shortcut: torch.Tensor, w_proj, b_proj, ln_g, ln_b, w_fc1, b_fc1, w_fc2, b_fc2, w_adj, b_adj, *,
               act: int = L.ACT_LRELU, slope: float = 0.2, alpha: float = 1.0, residual: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None, out_offset: int = 0, fm: int = 0, precision: str = "bf16") -> torch.Tensor:

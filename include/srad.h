@@ -300,6 +300,16 @@ size_t srad_op_swin_scratch_bytes(int d, int heads, int m, int no);
 int srad_op_qkv_attn(int precision, const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, const float* ln_g,
                      const float* ln_b, const float* w_qkv, const float* b_qkv, const float* table, void* out, int out_bf16,
                      void* scratch, size_t scratch_bytes, void* stream);
+/* srad_op_qkv_attn (bf16) with the saves the training backward reads, as the training forward leaves them: out bf16, LN1(x)
+ * as fp32 (save_xn) and / or bf16 (save_xn_h) [B*H*W][d], q | k | v as fp32 [B*H*W][3][heads][hdp] (q unscaled; save_qkv)
+ * or as bf16 [B*H*W][3][heads][hp_h] exactly as the attention used them (save_qkv_h); null saves are skipped.  no_qsplit = 1
+ * launches the plain (windows, heads) grid where the query split would be chosen (A/B of the two paths).
+ * srad_qkv_attn_grid: the grid (x, y) srad_op_qkv_attn / the engines launch for this shape on the current device. */
+int srad_op_qkv_attn_train(const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, const float* ln_g,
+                           const float* ln_b, const float* w_qkv, const float* b_qkv, const float* table, void* out_h,
+                           float* save_xn, void* save_xn_h, float* save_qkv, int hdp, void* save_qkv_h, int hp_h, int no_qsplit,
+                           void* scratch, size_t scratch_bytes, void* stream);
+int srad_qkv_attn_grid(int precision, int B, int H, int W, int d, int heads, int no_qsplit, int* grid_xy);
 int srad_op_mlp_block(int precision, int M, int d, int m, int no, int fm, const void* attn, const float* shortcut, int ld_short,
                       const float* w_proj, const float* b_proj, const float* ln_g, const float* ln_b, const float* w_fc1,
                       const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
