@@ -6,12 +6,17 @@ GPU, bf16 MFMA with fp32 accumulate -> LR input [4,1,32,32] fp32 in [0,255], out
 One "step" = one forward of that batch through the HIP engine, inputs already resident in HBM.
 Synthetic data; reference-style random init of the full 12-RDG architecture (27.38 M params).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU, every rank runs its own batch (image-parallel, no data-path
 collective; SURVEY.md §8(e) eval row) -> weak scaling; barrier + synchronize on both sides of the
 timed region, MAX over ranks.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line.
+--full adds every other leg to the same line after the timed steps (the training step C4, the
+per-kernel table and roofline, the split-bf16 and fp32 modes, the CPU baselines, the anomaly eval,
+the scorer, C5, C3 and DRN training): about 35 s on one MI355X, against under 3 s for a plain run.
 """
 import argparse
 import json
@@ -525,6 +530,10 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "bf16x3"])
     ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run every other leg: C4 training step, per-kernel table and roofline, "
+                         "split-bf16 and fp32 modes, CPU baselines, anomaly eval, scorer, C5, C3 and DRN training; the "
+                         "--no-train / --no-eval / --no-cpu-baseline / --cpu-seconds / --train-* options shape this run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -752,127 +761,130 @@ def run_rank(args):
     if dumped is not None:
         result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
-    if not args.no_train:
-        guard = None
-        if world > 1:
-            guard = arm_train_watchdog(result, rank, float(os.environ.get("SRAD_BENCH_TRAIN_LIMIT_S", "420")))
-        try:
-            torch.manual_seed(1)                           # the replica's weights: same seed on every rank ...
-            result["train"] = train_leg(args, torch, dist, dev, world, rank)
-        except Exception as e:          # the headline line must survive a failure of this extra leg
-            result["train"] = {"error": f"{type(e).__name__}: {e}"}
-        if guard is not None:
-            guard.cancel()
-
     if rank == 0:
         flops = model.flops(B, H, W)
         result["algorithmic_gflop_per_step"] = round(flops / 1e9, 2)
         result["model_tflops"] = round(flops * args.steps / (elapsed) / 1e12, 2)
-        # ---- per-kernel timing with HIP events on the launch stream (eager, same workload) ----
-        model.use_graph = False
-        L.prof_enable(True)
-        reps = 10
-        with torch.no_grad():
-            model(x)
-            torch.cuda.synchronize()
-            L.prof_collect()
-            for _ in range(reps):
-                model(x)
-        torch.cuda.synchronize()
-        prof = L.prof_collect()
-        L.prof_enable(False)
-        model.use_graph = opt.use_graph
-        total_ms = sum(v["ms"] for v in prof.values())
-        dom = max(prof, key=lambda k: prof[k]["ms"])
-        d = prof[dom]
-        achieved = d["flops"] / (d["ms"] * 1e-3)
-        pmc, pmc_file, stale = pmc_profile(dom)
-        roof = {
-            "kernel": dom, "bound": "mfma", "achieved": round(achieved / 1e12, 2), "peak": PEAK[args.dtype] / 1e12,
-            "unit": "TFLOP/s", "frac": round(achieved / PEAK[args.dtype], 4),
-            "traffic": None if (pmc is None or stale) else pmc.get("hbm_bytes_per_launch"),
-            "launches_per_step": d["launches"] // reps,
-            "avg_launch_us": round(d["ms"] * 1e3 / d["launches"], 3),
-            "algorithmic_gflop_per_launch": round(d["flops"] / d["launches"] / 1e9, 4),
-            "algorithmic_mbytes_per_launch": round(d["bytes"] / d["launches"] / 1e6, 3),
-            "share_of_kernel_time": round(d["ms"] / total_ms, 3),
-        }
-        if pmc is not None:
-            # counters come from separate rocprofv3 --pmc passes of this same workload (a PMC pass cannot run inside this
-            # process); they are quoted only while the profile's source hash equals the kernels that just ran
-            roof["pmc_source"] = pmc_file
-            roof["pmc_stale"] = bool(stale)
-            if not stale:
-                for k in ("mfma_busy", "mfma_busy_note", "valu_busy", "wait_frac", "lds_bank_conflict_frac", "dispatch_us"):
-                    if k in pmc:
-                        roof[k] = pmc[k]
-        result["roofline"] = roof
-        result["kernels"] = {k: {"launches_per_step": v["launches"] // reps,
-                                 "avg_us": round(v["ms"] * 1e3 / v["launches"], 3),
-                                 "ms_per_step": round(v["ms"] / reps, 4),
-                                 "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
-                                 "gbytes_per_s": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)}
-                             for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
 
-        y32, yf32 = None, None
-        if n_gpus == 1:
+    if args.full:
+        if not args.no_train:
+            guard = None
+            if world > 1:
+                guard = arm_train_watchdog(result, rank, float(os.environ.get("SRAD_BENCH_TRAIN_LIMIT_S", "420")))
             try:
-                result["parity_mode"], y32, m32 = parity_mode_leg(model, x, y, args, torch, dev, "bf16x3")
-                del m32
-            except Exception as e:
-                result["parity_mode"] = {"error": f"{type(e).__name__}: {e}"}
-            try:
-                result["fp32_mode"], yf32, m32 = parity_mode_leg(model, x, y, args, torch, dev, "fp32")
-                del m32
-            except Exception as e:
-                result["fp32_mode"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline and n_gpus == 1:
-            # the reference's --device cpu path, restated (oracle), same weights, same batch, fp32
-            from oracle import sr_ref as R
-            torch.set_num_threads(usable_cores())
-            sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-            xc = x.cpu()
-            cfg = model.cfg
+                torch.manual_seed(1)                           # the replica's weights: same seed on every rank ...
+                result["train"] = train_leg(args, torch, dist, dev, world, rank)
+            except Exception as e:          # the headline line must survive a failure of this extra leg
+                result["train"] = {"error": f"{type(e).__name__}: {e}"}
+            if guard is not None:
+                guard.cancel()
+        if rank == 0:
+            # ---- per-kernel timing with HIP events on the launch stream (eager, same workload) ----
+            model.use_graph = False
+            L.prof_enable(True)
+            reps = 10
             with torch.no_grad():
-                t0 = time.perf_counter()
-                ref = R.drct_forward(sd, xc, cfg)
-                first = time.perf_counter() - t0
-                n = max(1, min(20, int(args.cpu_seconds / max(first, 1e-3))))
-                t0 = time.perf_counter()
-                for _ in range(n):
-                    R.drct_forward(sd, xc, cfg)
-                cpu_t = (time.perf_counter() - t0) / n
-            err = float((y.cpu() - ref).abs().max() / ref.abs().max())
-            result["cpu_baseline"] = {"value": round(hr_px / cpu_t / 1e6, 4), "unit": "HR Mpixels/s",
-                                      "cores": torch.get_num_threads(), "kind": "port",
-                                      "sample": f"{n} forwards of the same C2 batch (fp32, torch CPU kernels via "
-                                                f"oracle/sr_ref.py), {cpu_t * 1e3:.0f} ms each; {torch.get_num_threads()} threads = "
-                                                f"the cores this job may use, host has {os.cpu_count()} logical cores"}
-            result["speedup_vs_cpu"] = round(value / (hr_px / cpu_t / 1e6), 1)
-            result["max_rel_err_vs_cpu_fp32"] = float(f"{err:.3e}")
-            for key, yy in (("parity_mode", y32), ("fp32_mode", yf32)):
-                if yy is not None and isinstance(result.get(key), dict) and "error" not in result[key]:
-                    e32 = float((yy.cpu() - ref).abs().max() / ref.abs().max())
-                    result[key]["max_rel_err_vs_cpu_fp32"] = float(f"{e32:.3e}")
-                    result[key]["speedup_vs_cpu"] = round(result[key]["hr_mpixels_per_s"] / (hr_px / cpu_t / 1e6), 1)
-        if n_gpus == 1 and not args.no_eval:
-            result["anomaly_eval"] = anomaly_eval_leg(model, args, torch)
-            try:
-                result["scorer"] = scorer_leg(torch, dev)
-            except Exception as e:
-                result["scorer"] = {"error": f"{type(e).__name__}: {e}"}
-            result["eval_1024px_tile"] = c5_leg(args, torch, dev)
-            result["drn_forward"] = c3_leg(args, torch, dev)
-            if not args.no_train:
+                model(x)
+                torch.cuda.synchronize()
+                L.prof_collect()
+                for _ in range(reps):
+                    model(x)
+            torch.cuda.synchronize()
+            prof = L.prof_collect()
+            L.prof_enable(False)
+            model.use_graph = opt.use_graph
+            total_ms = sum(v["ms"] for v in prof.values())
+            dom = max(prof, key=lambda k: prof[k]["ms"])
+            d = prof[dom]
+            achieved = d["flops"] / (d["ms"] * 1e-3)
+            pmc, pmc_file, stale = pmc_profile(dom)
+            roof = {
+                "kernel": dom, "bound": "mfma", "achieved": round(achieved / 1e12, 2), "peak": PEAK[args.dtype] / 1e12,
+                "unit": "TFLOP/s", "frac": round(achieved / PEAK[args.dtype], 4),
+                "traffic": None if (pmc is None or stale) else pmc.get("hbm_bytes_per_launch"),
+                "launches_per_step": d["launches"] // reps,
+                "avg_launch_us": round(d["ms"] * 1e3 / d["launches"], 3),
+                "algorithmic_gflop_per_launch": round(d["flops"] / d["launches"] / 1e9, 4),
+                "algorithmic_mbytes_per_launch": round(d["bytes"] / d["launches"] / 1e6, 3),
+                "share_of_kernel_time": round(d["ms"] / total_ms, 3),
+            }
+            if pmc is not None:
+                # counters come from separate rocprofv3 --pmc passes of this same workload (a PMC pass cannot run inside this
+                # process); they are quoted only while the profile's source hash equals the kernels that just ran
+                roof["pmc_source"] = pmc_file
+                roof["pmc_stale"] = bool(stale)
+                if not stale:
+                    for k in ("mfma_busy", "mfma_busy_note", "valu_busy", "wait_frac", "lds_bank_conflict_frac", "dispatch_us"):
+                        if k in pmc:
+                            roof[k] = pmc[k]
+            result["roofline"] = roof
+            result["kernels"] = {k: {"launches_per_step": v["launches"] // reps,
+                                     "avg_us": round(v["ms"] * 1e3 / v["launches"], 3),
+                                     "ms_per_step": round(v["ms"] / reps, 4),
+                                     "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
+                                     "gbytes_per_s": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)}
+                                 for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
+
+            y32, yf32 = None, None
+            if n_gpus == 1:
                 try:
-                    result["drn_train"] = drn_train_leg(args, torch, dev)
-                except Exception as e:                    # a secondary leg never takes the headline line down
-                    result["drn_train"] = {"error": f"{type(e).__name__}: {e}"}
-            if not args.no_cpu_baseline:
-                try:
-                    c3_cpu_baseline(args, torch, dev, result["drn_forward"])
+                    result["parity_mode"], y32, m32 = parity_mode_leg(model, x, y, args, torch, dev, "bf16x3")
+                    del m32
                 except Exception as e:
-                    result["drn_forward"]["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
+                    result["parity_mode"] = {"error": f"{type(e).__name__}: {e}"}
+                try:
+                    result["fp32_mode"], yf32, m32 = parity_mode_leg(model, x, y, args, torch, dev, "fp32")
+                    del m32
+                except Exception as e:
+                    result["fp32_mode"] = {"error": f"{type(e).__name__}: {e}"}
+            if not args.no_cpu_baseline and n_gpus == 1:
+                # the reference's --device cpu path, restated (oracle), same weights, same batch, fp32
+                from oracle import sr_ref as R
+                torch.set_num_threads(usable_cores())
+                sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+                xc = x.cpu()
+                cfg = model.cfg
+                with torch.no_grad():
+                    t0 = time.perf_counter()
+                    ref = R.drct_forward(sd, xc, cfg)
+                    first = time.perf_counter() - t0
+                    n = max(1, min(20, int(args.cpu_seconds / max(first, 1e-3))))
+                    t0 = time.perf_counter()
+                    for _ in range(n):
+                        R.drct_forward(sd, xc, cfg)
+                    cpu_t = (time.perf_counter() - t0) / n
+                err = float((y.cpu() - ref).abs().max() / ref.abs().max())
+                result["cpu_baseline"] = {"value": round(hr_px / cpu_t / 1e6, 4), "unit": "HR Mpixels/s",
+                                          "cores": torch.get_num_threads(), "kind": "port",
+                                          "sample": f"{n} forwards of the same C2 batch (fp32, torch CPU kernels via "
+                                                    f"oracle/sr_ref.py), {cpu_t * 1e3:.0f} ms each; {torch.get_num_threads()} threads = "
+                                                    f"the cores this job may use, host has {os.cpu_count()} logical cores"}
+                result["speedup_vs_cpu"] = round(value / (hr_px / cpu_t / 1e6), 1)
+                result["max_rel_err_vs_cpu_fp32"] = float(f"{err:.3e}")
+                for key, yy in (("parity_mode", y32), ("fp32_mode", yf32)):
+                    if yy is not None and isinstance(result.get(key), dict) and "error" not in result[key]:
+                        e32 = float((yy.cpu() - ref).abs().max() / ref.abs().max())
+                        result[key]["max_rel_err_vs_cpu_fp32"] = float(f"{e32:.3e}")
+                        result[key]["speedup_vs_cpu"] = round(result[key]["hr_mpixels_per_s"] / (hr_px / cpu_t / 1e6), 1)
+            if n_gpus == 1 and not args.no_eval:
+                result["anomaly_eval"] = anomaly_eval_leg(model, args, torch)
+                try:
+                    result["scorer"] = scorer_leg(torch, dev)
+                except Exception as e:
+                    result["scorer"] = {"error": f"{type(e).__name__}: {e}"}
+                result["eval_1024px_tile"] = c5_leg(args, torch, dev)
+                result["drn_forward"] = c3_leg(args, torch, dev)
+                if not args.no_train:
+                    try:
+                        result["drn_train"] = drn_train_leg(args, torch, dev)
+                    except Exception as e:                    # a secondary leg never takes the headline line down
+                        result["drn_train"] = {"error": f"{type(e).__name__}: {e}"}
+                if not args.no_cpu_baseline:
+                    try:
+                        c3_cpu_baseline(args, torch, dev, result["drn_forward"])
+                    except Exception as e:
+                        result["drn_forward"]["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

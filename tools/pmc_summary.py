@@ -120,8 +120,8 @@ def main():
                 out["grbm_cycles"] = round(avg["GRBM_GUI_ACTIVE"] / 8.0)
         return out
 
-    res = {"source": "rocprofv3 --pmc passes (one counter group per process) of " + os.environ.get("PMC_BENCH", "`bench.py --no-graph --no-train "
-                     "--no-eval --no-cpu-baseline`: the C2 forward") + ", eager launches",
+    res = {"source": "rocprofv3 --pmc passes (one counter group per process) of " + os.environ.get("PMC_BENCH", "`bench.py --no-graph --full "
+                     "--no-train --no-eval --no-cpu-baseline`: the C2 forward") + ", eager launches",
            "corrections": "FETCH_SIZE/WRITE_SIZE KiB -> bytes; FETCH_SIZE x2 (16 B/lane coalesced loads: 128-B requests tallied at 64 B)",
            "kernel_source_sha": kernel_source_sha(), "kernels": {}, "instances": {}}
     for k, ctrs in cls_sum.items():

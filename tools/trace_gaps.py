@@ -2,8 +2,8 @@
 """Timeline summary of one training step from a rocprofv3 --kernel-trace CSV: per-queue busy time, idle gaps on the
 busiest queue (the data-gradient chain) and overlap between the queues.
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace -- python3 bench.py --steps 5 --warmup 2 --train-steps 4 --no-cpu-baseline --no-eval
-    python tools/trace_gaps.py gpurun_out/trace out.json
+    rocprofv3 --kernel-trace --output-format csv -d <trace_dir> -- python3 bench.py --steps 5 --warmup 2 --full --train-steps 4 --no-cpu-baseline --no-eval
+    python tools/trace_gaps.py <trace_dir> out.json
 """
 import collections
 import csv

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the training leg of a bench.py JSON line: python tools/train_summary.py gpurun_out/bench_train.log"""
+"""Print the training leg of a `bench.py --full` JSON line: python tools/train_summary.py <bench log>"""
 import json
 import sys
 
