@@ -138,9 +138,11 @@ __device__ __forceinline__ void axis_pairs(int lo, int hi, int n, int (&idx)[6])
 constexpr int kWsGroup = 16;
 struct WsList { int ws[kWsGroup]; double dinv[kWsGroup]; };    // window sizes of a launch and 1 / ws^2 (a float64 division per pixel otherwise)
 
-// Sum of the 64 SSIM map values of a wave's segment, in every lane.  The values are float32 in [-1, 1]; they are summed as
-// integers of 2^-24 (exact, so the order is irrelevant and DPP lane swizzles can do four of the six steps: a float64 shuffle
-// chain was 12 ds_bpermute round trips + 30 vector instructions per 64 pixels of a kernel that is VALU-bound).
+// Sum of the 64 SSIM map values of a wave's segment, in every lane.  The values are float32 in [-1, 1]; each is first rounded
+// to a multiple of 2^-24 (an error of up to 2^-25 per pixel, so this kernel's mean can differ from the corner kernel's in the
+// last bits), then the integers are summed exactly, so the order is irrelevant and DPP lane swizzles can do four of the six
+// steps (a float64 shuffle chain was 12 ds_bpermute round trips + 30 vector instructions per 64 pixels of a kernel that is
+// VALU-bound).
 __device__ __forceinline__ double wave_sum_map(float m) {
   int v = __float2int_rn(m * 16777216.0f);
   v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
@@ -168,6 +170,7 @@ __global__ __launch_bounds__(256) void ssim_eval_kernel(const double* __restrict
   double local = 0.0;
 #pragma unroll 1
   for (int it = 0; it < kEvalPix / 256; ++it) {
+#pragma clang fp contract(off)     // the fp32 SSIM terms in the reference's rounding: an fma leaves E[x^2] - mu^2 a residue where it is 0
     const int seg0 = pb * kEvalPix + (wave * (kEvalPix / 256) + it) * 64;    // first pixel of this wave's 64 (wave-uniform)
     if (seg0 >= npix) break;
     int i, j;
@@ -329,6 +332,7 @@ __global__ __launch_bounds__(1024) void ssim_rows_lds_kernel(const double* __res
     if (kw + 1 < g) load_b(kw + 1);
     float m_val = 0.f;
     if (row_ok) {
+#pragma clang fp contract(off)     // as in ssim_eval_kernel
       const int lo = c - pad, hi = c + ws - 1 - pad;
       const double* const Dr = Dk + r * iper;
       const int c1 = min(hi, W - 1) + 1, c0 = max(lo, 0);
@@ -538,6 +542,9 @@ inline bool lds_sweep_ok(int H, int W) {
   return W >= 64 && W <= 1024 && (W & (W - 1)) == 0 && (long long)kQ * (H + 1) * (W + 1) * 8 < (1ll << 31);
 }
 inline int partial_slots(int H, int W) { return lds_sweep_ok(H, W) ? H : (H * W + kEvalPix - 1) / kEvalPix; }
+// the evaluation kernel of the sweep (srad_score_plan's numbering): the LDS sweep, the corner kernel with per-row waves, any width
+enum SweepKernel { kSweepLds = 0, kSweepRows = 1, kSweepAny = 2 };
+inline SweepKernel sweep_kernel(int H, int W) { return lds_sweep_ok(H, W) ? kSweepLds : W % 64 == 0 ? kSweepRows : kSweepAny; }
 inline int grid1d(size_t total) {
   size_t b = (total + 255) / 256;
   return (int)std::min<size_t>(std::max<size_t>(b, 1), 4096);
@@ -631,7 +638,8 @@ int srad_score_pairs(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int
       {
         // algorithmic bytes per (pair, window): the two fp32 luminance planes read once
         SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W * g, 8.0 * n * H * W * g);
-        if (lds_sweep_ok(H, W)) {
+        const SweepKernel kern = sweep_kernel(H, W);
+        if (kern == kSweepLds) {
           int pmin = wl.ws[0] / 2, pmax = pmin;
           for (int k = 1; k < g; ++k) { pmin = std::min(pmin, wl.ws[k] / 2); pmax = std::max(pmax, wl.ws[k] / 2); }
           const int rb = 1024 / W, t_first = -pmax, nt = H - 1 - pmin - t_first + 1, nt_blocks = (nt + rb - 1) / rb;
@@ -640,7 +648,7 @@ int srad_score_pairs(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int
           while ((1 << lw) < W) ++lw;
           SRAD_TRY(srad_launch_dyn<ssim_rows_lds_kernel>(dim3((unsigned)((size_t)nt_blocks * n)), dim3(1024), lds, s, sat, partial, H, lw, wl, g,
                                                          t_first, nt_blocks));
-        } else if (W % 64 == 0)
+        } else if (kern == kSweepRows)
           hipLaunchKernelGGL(ssim_eval_kernel<true>, dim3((unsigned)((size_t)nblk * g * n)), dim3(256), 0, s, sat, partial, H, W, wl, nblk, g, n);
         else
           hipLaunchKernelGGL(ssim_eval_kernel<false>, dim3((unsigned)((size_t)nblk * g * n)), dim3(256), 0, s, sat, partial, H, W, wl, nblk, g, n);
@@ -653,11 +661,22 @@ int srad_score_pairs(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int
   return SRAD_OK;
 }
 
+int srad_score_plan(int n_img, int H, int W, int* kernel, int* chunk) {
+  SRAD_REQUIRE(kernel && chunk && n_img > 0 && H > 1 && W > 1, "score_plan: bad argument");
+  *kernel = (int)sweep_kernel(H, W);
+  *chunk = chunk_images(n_img, H, W);
+  return SRAD_OK;
+}
+
 int srad_val_metrics(const float* sr, const float* hr, int B, int C, int H, int W, float rgb_range, double* psnr_out,
                      double* ssim_out, void* workspace, size_t workspace_bytes, void* stream) {
   (void)workspace; (void)workspace_bytes;
   SRAD_REQUIRE(sr && hr && psnr_out && ssim_out && B > 0, "val_metrics: bad argument");
   SRAD_REQUIRE(C == 1 || C == 3, "val_metrics: channels must be 1 or 3 (got %d)", C);
+  SRAD_REQUIRE(H > 0 && W > 0, "val_metrics: bad argument");
+  // the reference shaves 4 rows off each side whenever the WIDTH is above 8: no row is left, its PSNR is NaN and its SSIM raises
+  SRAD_REQUIRE(W <= 8 || H > 8, "val_metrics: a %dx%d image has no rows left after the 4-px shave (applied when the width is above 8)",
+               H, W);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(val_metrics_kernel, dim3(B), dim3(256), 0, s, sr, hr, C, H, W, rgb_range, psnr_out, ssim_out);
   SRAD_CHECK_HIP(hipGetLastError());
@@ -716,6 +735,7 @@ namespace {
 
 __global__ __launch_bounds__(256) void ssim_map_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W, int ws,
                                                        double dinv, int nblk) {
+#pragma clang fp contract(off)     // as in ssim_eval_kernel
   const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
   const int npix = H * W, pad = ws / 2;
   const int p = pb * 256 + (int)threadIdx.x;

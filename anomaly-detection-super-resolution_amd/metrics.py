@@ -67,9 +67,22 @@ def score_pairs(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Sequence
     return ssim, mse, psnr
 
 
+SCORE_KERNELS = ("lds", "rows", "any")     # srad_score_plan's kernel numbers 0, 1, 2
+
+
+def score_plan(n_img: int, H: int, W: int) -> Tuple[int, int]:
+    """The path ``score_pairs`` takes for ``n_img`` H x W pairs (``srad_score_plan``; needs no GPU): (kernel, chunk) with
+    kernel 0 = the LDS sweep (power-of-two widths 64..1024), 1 = the corner kernel (other multiples of 64), 2 = any width
+    (names in ``SCORE_KERNELS``), and chunk = images per summed-area table chunk."""
+    k, c = C.c_int(), C.c_int()
+    L.check(L.lib().srad_score_plan(int(n_img), int(H), int(W), C.byref(k), C.byref(c)), "score_plan")
+    return k.value, c.value
+
+
 def val_metrics(sr: torch.Tensor, hr: torch.Tensor, rgb_range: float) -> Tuple[torch.Tensor, torch.Tensor]:
     """psnr_torch / ssim_torch of Trainer.test (src/metrics.py:70-108) per image, with the
-    reference's quirks kept verbatim: 4-px shave, zero padding, C1/C2 scaled by 255^2."""
+    reference's quirks kept verbatim: 4-px shave, zero padding, C1/C2 scaled by 255^2.  RuntimeError for
+    W > 8 with H <= 8, where the shave leaves no row (the reference's PSNR is NaN there and its SSIM raises)."""
     _need_cuda(sr, hr)
     sr, hr = sr.detach().float().contiguous(), hr.detach().float().contiguous()
     if sr.shape[-2] > hr.shape[-2] or sr.shape[-1] > hr.shape[-1]:

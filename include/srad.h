@@ -182,11 +182,16 @@ int srad_quantize(const float* x, float* y, int64_t n, float rgb_range, void* st
  *   mse_out[i] = mean((sr_i/255 - hr_i/255)^2), psnr_out[i] = psnr_numpy (inf when mse == 0)
  * Outputs are DEVICE double arrays; workspace >= srad_score_workspace_bytes. */
 int srad_score_workspace_bytes(int n_img, int H, int W, size_t* bytes);
+/* The path srad_score_pairs takes for n_img H x W pairs: *kernel = the SSIM sweep's evaluation kernel (0 = the LDS sweep for
+ * power-of-two widths 64..1024, 1 = the corner kernel for other multiples of 64 wide, 2 = the kernel for any width), *chunk =
+ * images per summed-area table chunk (the pairs run in ceil(n_img / chunk) chunks).  Host only, no device needed. */
+int srad_score_plan(int n_img, int H, int W, int* kernel, int* chunk);
 int srad_score_pairs(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host,
                      int n_ws, double* ssim_out, double* mse_out, double* psnr_out, void* workspace,
                      size_t workspace_bytes, void* stream);
 /* Validation metrics of Trainer.test (src/metrics.py:70-108) on fp32 NCHW tensors, one value per
- * image, device double outputs; reproduces the zero padding, 4-px shave and the 255^2 constants. */
+ * image, device double outputs; reproduces the zero padding, 4-px shave and the 255^2 constants.  A shape the shave leaves
+ * no row of (W > 8, H <= 8; the reference's PSNR is NaN there and its SSIM raises) is refused with SRAD_ERR_ARG. */
 int srad_val_metrics(const float* sr, const float* hr, int B, int C, int H, int W, float rgb_range,
                      double* psnr_out, double* ssim_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Binary ROC-AUC == sklearn.metrics.roc_auc_score (ties count one half).  labels/scores are HOST
