@@ -232,6 +232,15 @@ def dptr(t) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def ws_buffer(nbytes: int, device):
+    """A device workspace of ``nbytes`` that starts on a 256-byte boundary: (the tensor to keep alive while the call runs,
+    the aligned pointer, nbytes as size_t)."""
+    import torch
+    t = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    off = (-t.data_ptr()) % 256
+    return t, C.c_void_p(t.data_ptr() + off), C.c_size_t(nbytes)
+
+
 def prof_enable(on: bool) -> None:
     check(lib().srad_prof_enable(1 if on else 0), "prof_enable")
 

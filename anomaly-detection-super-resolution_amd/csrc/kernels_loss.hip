@@ -20,16 +20,6 @@ namespace {
 
 constexpr int LOSS_NB = 1024;     // partial sums per reduction
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // kind 0: |a - b|, kind 1 / 2: (a - b)^2
 template <int SQ>
 __global__ __launch_bounds__(256) void diff_sum_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n,
@@ -40,23 +30,24 @@ __global__ __launch_bounds__(256) void diff_sum_kernel(const float* __restrict__
     const float d = a[i] - b[i];
     local += SQ ? (double)(d * d) : (double)fabsf(d);
   }
-  const double s = block_sum(local, red);
+  const double s = srad_block_sum(local, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-// out[0] = the loss value, out[1] = what the backward needs (the mean squared error for PSNR)
-__global__ void finish_kernel(const double* __restrict__ partial, int nb, double inv_n, int kind, double* __restrict__ out) {
+// *out = the loss value, *aux = what the backward needs (the mean squared error for PSNR); aux may be null except for PSNR
+__global__ void finish_kernel(const double* __restrict__ partial, int nb, double inv_n, int kind, double* __restrict__ out,
+                              double* __restrict__ aux) {
   if (threadIdx.x || blockIdx.x) return;
   double s = 0.0;
   for (int i = 0; i < nb; ++i) s += partial[i];
   if (kind == SRAD_LOSS_PSNR) {
     // nn.MSELoss in fp32, then 10 * log10(255^2 / (mse + 1e-8)) in fp32 (loss.py:67-70)
     const float mse = (float)(s * inv_n);
-    out[1] = (double)mse;
-    out[0] = -(double)(10.0f * log10f((255.0f * 255.0f) / (mse + 1e-8f)));
+    *aux = (double)mse;
+    *out = -(double)(10.0f * log10f((255.0f * 255.0f) / (mse + 1e-8f)));
   } else {
-    out[0] = s * inv_n;
-    out[1] = out[0];
+    *out = s * inv_n;
+    if (aux) *aux = *out;
   }
 }
 
@@ -147,7 +138,7 @@ __global__ __launch_bounds__(256) void ssim_map_kernel(const float* __restrict__
       de12[i] = 2 * A1 / den;
     }
   }
-  const double s = block_sum(local, red);
+  const double s = srad_block_sum(local, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -207,6 +198,24 @@ int ssim_geo(int B, int C, int sH, int sW, int H, int W, float rgb_range, SsimGe
 
 extern "C" {
 
+int srad_l1_workspace_bytes(size_t* bytes) {
+  SRAD_REQUIRE(bytes, "l1_workspace_bytes: null");
+  *bytes = LOSS_NB * sizeof(double);
+  return SRAD_OK;
+}
+
+// mean |a - b| -> *out (device double): the L1 loss forward without its second value.  workspace: >= srad_l1_workspace_bytes().
+int srad_l1_loss(const float* a, const float* b, int64_t n, double* out, void* workspace, void* stream) {
+  SRAD_REQUIRE(a && b && out && workspace && n > 0, "l1_loss: bad argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int nb = grid_for((size_t)n);
+  double* partial = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(diff_sum_kernel<0>, dim3(nb), dim3(256), 0, s, a, b, (size_t)n, partial);
+  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(64), 0, s, partial, nb, 1.0 / (double)n, (int)SRAD_LOSS_L1, out, (double*)nullptr);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
 int srad_loss_workspace_bytes(int kind, int B, int C, int H, int W, size_t* bytes) {
   SRAD_REQUIRE(bytes && B > 0 && C > 0 && H > 0 && W > 0, "loss_workspace_bytes: bad argument");
   size_t n = LOSS_NB * sizeof(double);
@@ -230,7 +239,7 @@ int srad_loss_forward(int kind, const float* sr, const float* hr, int B, int C, 
     const int nb = grid_for(n);
     if (kind == SRAD_LOSS_L1) hipLaunchKernelGGL(diff_sum_kernel<0>, dim3(nb), dim3(256), 0, s, sr, hr, n, partial);
     else hipLaunchKernelGGL(diff_sum_kernel<1>, dim3(nb), dim3(256), 0, s, sr, hr, n, partial);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(64), 0, s, partial, nb, 1.0 / (double)n, kind, out2);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(64), 0, s, partial, nb, 1.0 / (double)n, kind, out2, out2 + 1);
     SRAD_CHECK_HIP(hipGetLastError());
     return SRAD_OK;
   }
@@ -248,7 +257,7 @@ int srad_loss_forward(int kind, const float* sr, const float* hr, int B, int C, 
   const int nb = grid_for(total);
   hipLaunchKernelGGL(ssim_lum_kernel, dim3(nb), dim3(256), 0, s, sr, hr, g, lx, ly);
   hipLaunchKernelGGL(ssim_map_kernel<true>, dim3(nb), dim3(256), 0, s, lx, ly, g, partial, dm1, de11, de12);
-  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(64), 0, s, partial, nb, 1.0 / (double)batch_size, kind, out2);
+  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(64), 0, s, partial, nb, 1.0 / (double)batch_size, kind, out2, out2 + 1);
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

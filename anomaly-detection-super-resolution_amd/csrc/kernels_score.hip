@@ -114,6 +114,19 @@ __global__ void sat_cols_carry_kernel(double* __restrict__ sat, const double* __
   for (int r = r0; r <= r1; ++r) p[(size_t)r * per] += carry;
 }
 
+// The SSIM map value of a pixel from its five window sums and 1 / ws^2, in fp32 in the reference's operation order
+// (metrics.py:58-66), for the three sweep kernels and ssim_map_kernel.
+__device__ __forceinline__ float ssim_of_sums(const double (&sum)[kQ], double dinv) {
+#pragma clang fp contract(off)     // the reference's rounding: an fma leaves E[x^2] - mu^2 a residue where it is 0
+  const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);
+  const float mu1 = (float)(sum[0] * dinv), mu2 = (float)(sum[1] * dinv);
+  const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+  const float s1 = (float)(sum[2] * dinv) - mu1_sq;
+  const float s2 = (float)(sum[3] * dinv) - mu2_sq;
+  const float s12 = (float)(sum[4] * dinv) - mu12;
+  return ((2.0f * mu12 + C1) * (2.0f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
+}
+
 // Reflect-padded window along one axis as table differences.  Padded coordinates lo..hi (each side leaves [0, n-1] by less
 // than n) cover the real indices [max(lo,0), min(hi,n-1)] once, [1, -lo] once more if lo < 0, and [2(n-1)-hi, n-2] once more if
 // hi > n-1 (numpy "reflect": the edge sample is not repeated).  With P the prefix table (P[0] = 0) the covered sum is three
@@ -122,6 +135,45 @@ __device__ __forceinline__ void axis_pairs(int lo, int hi, int n, int (&idx)[6])
   idx[0] = min(hi, n - 1) + 1; idx[1] = max(lo, 0);                       // + P[idx0] - P[idx1]: the part inside the image
   idx[2] = lo < 0 ? -lo + 1 : 1; idx[3] = 1;                              // + P[-lo + 1] - P[1]: reflected over the low edge
   idx[4] = n - 1; idx[5] = hi > n - 1 ? 2 * (n - 1) - hi : n - 1;         // + P[n - 1] - P[2 (n - 1) - hi]: over the high edge
+}
+
+// The SSIM map value of pixel (i, j) for window size ws, from the tables S of its image: the five window sums are the (row
+// pair, column pair) rectangles of axis_pairs.  The reflection pairs of either axis are skipped by wave-uniform branches when no
+// lane of the wave needs them, and all loads of a rectangle are issued before the first add.  (The sums stay in this function:
+// handed out through an array parameter they cost ssim_map_kernel 6 VGPRs.)
+__device__ __forceinline__ float corner_ssim(const double* S, int H, int W, int i, int j, int ws, double dinv) {
+  const int pad = ws / 2, iper = W + 1;
+  const size_t plane = (size_t)(H + 1) * iper;
+  int ri[6], ci[6];
+  axis_pairs(i - pad, i + ws - 1 - pad, H, ri);
+  axis_pairs(j - pad, j + ws - 1 - pad, W, ci);
+  // does any lane of the wave need the reflection pairs?  (a wave-uniform i: the row answers are scalar anyway)
+  const bool row_lo = __builtin_amdgcn_ballot_w64(i - pad < 0) != 0, row_hi = __builtin_amdgcn_ballot_w64(i + ws - 1 - pad > H - 1) != 0;
+  const bool col_lo = __builtin_amdgcn_ballot_w64(j - pad < 0) != 0, col_hi = __builtin_amdgcn_ballot_w64(j + ws - 1 - pad > W - 1) != 0;
+  double sum[kQ] = {0, 0, 0, 0, 0};
+  auto row_pair = [&](auto RP) __attribute__((always_inline)) {               // + row ri[2 rp], - row ri[2 rp + 1]
+    constexpr int rp = decltype(RP)::value;
+    const int oa = ri[2 * rp] * iper, ob = ri[2 * rp + 1] * iper;
+    auto col_pair = [&](auto CP) __attribute__((always_inline)) {
+      constexpr int cp = decltype(CP)::value;
+      double va[kQ], vb[kQ], vc[kQ], vd[kQ];
+#pragma unroll
+      for (int q = 0; q < kQ; ++q) {
+        const double* Sq = S + (size_t)q * plane;
+        va[q] = Sq[oa + ci[2 * cp]]; vb[q] = Sq[oa + ci[2 * cp + 1]];
+        vc[q] = Sq[ob + ci[2 * cp]]; vd[q] = Sq[ob + ci[2 * cp + 1]];
+      }
+#pragma unroll
+      for (int q = 0; q < kQ; ++q) sum[q] += (va[q] - vb[q]) - (vc[q] - vd[q]);
+    };
+    col_pair(std::integral_constant<int, 0>{});
+    if (col_lo) col_pair(std::integral_constant<int, 1>{});
+    if (col_hi) col_pair(std::integral_constant<int, 2>{});
+  };
+  row_pair(std::integral_constant<int, 0>{});
+  if (row_lo) row_pair(std::integral_constant<int, 1>{});
+  if (row_hi) row_pair(std::integral_constant<int, 2>{});
+  return ssim_of_sums(sum, dinv);
 }
 
 // Evaluation: one workgroup = kEvalPix consecutive pixels of one image for ONE window size; up to kWsGroup window sizes share
@@ -159,68 +211,26 @@ __global__ __launch_bounds__(256) void ssim_eval_kernel(const double* __restrict
   const int L = blockIdx.x, per_img = nblk * g;
   const int img = L / per_img, r0 = L - img * per_img;
   const int kw = r0 / nblk, pb = r0 - kw * nblk;
-  const int ws = wl.ws[kw], pad = ws / 2;
+  const int ws = wl.ws[kw];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int iper = W + 1;
-  const size_t plane = (size_t)(H + 1) * iper;
+  const size_t plane = (size_t)(H + 1) * (W + 1);
   const double* const S = sat + (size_t)img * kQ * plane;
   const double dinv = wl.dinv[kw];
-  const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);
   const int npix = H * W;
   double local = 0.0;
 #pragma unroll 1
   for (int it = 0; it < kEvalPix / 256; ++it) {
-#pragma clang fp contract(off)     // the fp32 SSIM terms in the reference's rounding: an fma leaves E[x^2] - mu^2 a residue where it is 0
     const int seg0 = pb * kEvalPix + (wave * (kEvalPix / 256) + it) * 64;    // first pixel of this wave's 64 (wave-uniform)
     if (seg0 >= npix) break;
     int i, j;
     if constexpr (ROWS) { i = seg0 / W; j = seg0 - i * W + lane; }           // i scalar
     else { const int pix = min(seg0 + lane, npix - 1); i = pix / W; j = pix - i * W; }
-    int ri[6], ci[6];
-    axis_pairs(i - pad, i + ws - 1 - pad, H, ri);
-    axis_pairs(j - pad, j + ws - 1 - pad, W, ci);
-    // does any lane of the wave need the reflection pairs?  (ROWS: the row answers are scalar anyway)
-    const bool row_lo = __builtin_amdgcn_ballot_w64(i - pad < 0) != 0, row_hi = __builtin_amdgcn_ballot_w64(i + ws - 1 - pad > H - 1) != 0;
-    const bool col_lo = __builtin_amdgcn_ballot_w64(j - pad < 0) != 0, col_hi = __builtin_amdgcn_ballot_w64(j + ws - 1 - pad > W - 1) != 0;
-    double sum[kQ] = {0, 0, 0, 0, 0};
-    auto row_pair = [&](auto RP) __attribute__((always_inline)) {             // + row ri[2 rp], - row ri[2 rp + 1]
-      constexpr int rp = decltype(RP)::value;
-      const int oa = ri[2 * rp] * iper, ob = ri[2 * rp + 1] * iper;
-      auto col_pair = [&](auto CP) __attribute__((always_inline)) {
-        constexpr int cp = decltype(CP)::value;
-        double va[kQ], vb[kQ], vc[kQ], vd[kQ];
-#pragma unroll
-        for (int q = 0; q < kQ; ++q) {
-          const double* Sq = S + (size_t)q * plane;
-          va[q] = Sq[oa + ci[2 * cp]]; vb[q] = Sq[oa + ci[2 * cp + 1]];
-          vc[q] = Sq[ob + ci[2 * cp]]; vd[q] = Sq[ob + ci[2 * cp + 1]];
-        }
-#pragma unroll
-        for (int q = 0; q < kQ; ++q) sum[q] += (va[q] - vb[q]) - (vc[q] - vd[q]);
-      };
-      col_pair(std::integral_constant<int, 0>{});
-      if (col_lo) col_pair(std::integral_constant<int, 1>{});
-      if (col_hi) col_pair(std::integral_constant<int, 2>{});
-    };
-    row_pair(std::integral_constant<int, 0>{});
-    if (row_lo) row_pair(std::integral_constant<int, 1>{});
-    if (row_hi) row_pair(std::integral_constant<int, 2>{});
-    const float mu1 = (float)(sum[0] * dinv), mu2 = (float)(sum[1] * dinv);
-    const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-    const float s1 = (float)(sum[2] * dinv) - mu1_sq;
-    const float s2 = (float)(sum[3] * dinv) - mu2_sq;
-    const float s12 = (float)(sum[4] * dinv) - mu12;
-    const float m = ((2.0f * mu12 + C1) * (2.0f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
+    const float m = corner_ssim(S, H, W, i, j, ws, dinv);
     if (ROWS || seg0 + lane < npix) local += (double)m;
   }
   __shared__ double red[256];
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[((size_t)img * kWsGroup + kw) * nblk + pb] = red[0];
+  const double s = srad_block_sum(local, red);
+  if (threadIdx.x == 0) partial[((size_t)img * kWsGroup + kw) * nblk + pb] = s;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -281,7 +291,6 @@ __global__ __launch_bounds__(1024) void ssim_rows_lds_kernel(const double* __res
       Tt = ld(tail_off(tta), 0) - (ld(tail_off(ttx), 0) - ld(tail_off(1), 0));
     }
   }
-  const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);
   double b0[kQ], bx[kQ], b0t = 0.0, bxt = 0.0;
   auto load_b = [&](int kw) __attribute__((always_inline)) {
     const int ws = wl.ws[kw], pad = ws / 2;
@@ -332,7 +341,6 @@ __global__ __launch_bounds__(1024) void ssim_rows_lds_kernel(const double* __res
     if (kw + 1 < g) load_b(kw + 1);
     float m_val = 0.f;
     if (row_ok) {
-#pragma clang fp contract(off)     // as in ssim_eval_kernel
       const int lo = c - pad, hi = c + ws - 1 - pad;
       const double* const Dr = Dk + r * iper;
       const int c1 = min(hi, W - 1) + 1, c0 = max(lo, 0);
@@ -349,12 +357,7 @@ __global__ __launch_bounds__(1024) void ssim_rows_lds_kernel(const double* __res
 #pragma unroll
         for (int q = 0; q < kQ; ++q) sum[q] += Dr[q * rowq + W - 1] - Dr[q * rowq + cb];
       }
-      const float mu1 = (float)(sum[0] * dinv), mu2 = (float)(sum[1] * dinv);
-      const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-      const float s1 = (float)(sum[2] * dinv) - mu1_sq;
-      const float s2 = (float)(sum[3] * dinv) - mu2_sq;
-      const float s12 = (float)(sum[4] * dinv) - mu12;
-      m_val = ((2.0f * mu12 + C1) * (2.0f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
+      m_val = ssim_of_sums(sum, dinv);
     }
     const double seg = wave_sum_map(m_val);
     if (lane == 0) wsum[(kw & 1) * 16 + wave] = seg;
@@ -379,13 +382,24 @@ __global__ __launch_bounds__(256) void ssim_finish_kernel(const double* __restri
   double s = 0.0;
   for (int b = threadIdx.x; b < nblk; b += 256) s += p[b];
   __shared__ double red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[(size_t)img * out_stride + out_col0 + kw] = red[0] * inv_count;
+  const double total = srad_block_sum(s, red);
+  if (threadIdx.x == 0) out[(size_t)img * out_stride + out_col0 + kw] = total * inv_count;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Per-pixel anomaly maps: 1 - the SSIM map of ONE window size (the `ssim_map` src/metrics.py:66 averages), from the same float64
+// tables and with the same per-pixel arithmetic as the sweep, but one output value per pixel and no reduction.  One thread per
+// pixel, any width; the reflection pairs of either axis are skipped by wave-uniform branches when no lane of the wave needs them.
+__global__ __launch_bounds__(256) void ssim_map_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W, int ws,
+                                                       double dinv, int nblk) {
+  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
+  const int npix = H * W;
+  const int p = pb * 256 + (int)threadIdx.x;
+  const int pix = min(p, npix - 1);                                      // lanes past the end compute a copy of the last pixel
+  const int i = pix / W, j = pix - i * W;
+  const size_t plane = (size_t)(H + 1) * (W + 1);
+  const float m = corner_ssim(sat + (size_t)img * kQ * plane, H, W, i, j, ws, dinv);
+  if (p < npix) out[(size_t)img * npix + p] = 1.0f - m;
 }
 
 // mean((sr/255 - hr/255)^2) over all H*W*C values of an image: block partial sums (grid = blocks x images) ...
@@ -400,13 +414,8 @@ __global__ __launch_bounds__(256) void mse_partial_kernel(const uint8_t* __restr
     local += (double)(d * d);
   }
   __shared__ double red[256];
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[(size_t)img * nb + blockIdx.x] = red[0];
+  const double s = srad_block_sum(local, red);
+  if (threadIdx.x == 0) partial[(size_t)img * nb + blockIdx.x] = s;
 }
 // ... and one thread per image: the mean as float32 (np.mean of a float32 array), PSNR with data_range 1
 __global__ void mse_finish_kernel(const double* __restrict__ partial, double* __restrict__ mse, double* __restrict__ psnr, int n_img,
@@ -440,28 +449,6 @@ __global__ void quantize_kernel(const float* __restrict__ x, float* __restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n,
-                                                 double* __restrict__ partial) {
-  double local = 0.0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    local += (double)fabsf(a[i] - b[i]);
-  __shared__ double red[256];
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-__global__ void l1_finish_kernel(const double* __restrict__ partial, int nb, double inv_n, double* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < nb; ++i) s += partial[i];
-    *out = s * inv_n;
-  }
-}
-
 // Validation metrics of Trainer.test (metrics.py:70-108): one workgroup per image.
 __global__ __launch_bounds__(256) void val_metrics_kernel(const float* __restrict__ sr, const float* __restrict__ hr, int C,
                                                           int H, int W, float rgb_range, double* __restrict__ psnr,
@@ -484,17 +471,12 @@ __global__ __launch_bounds__(256) void val_metrics_kernel(const float* __restric
       const float d = (s[c * plane + (size_t)yy * W + xx] - h[c * plane + (size_t)yy * W + xx]) / rgb_range;
       local += (double)(d * d);
     }
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  const double sq = srad_block_sum(local, red);
   if (threadIdx.x == 0) {
-    const double m = (double)(float)(red[0] / ((double)C * h2 * w2));
+    const double m = (double)(float)(sq / ((double)C * h2 * w2));
     psnr[img] = m == 0.0 ? INFINITY : 10.0 * log10(1.0 / m);
   }
-  __syncthreads();
+  __syncthreads();                                            // every thread has read red[0] before the second sum writes red
   // ---- SSIM: clamp(x/range, 0, 1), luminance if C > 1, 11x11 box with ZERO padding, C1/C2 * 255^2 ----
   auto lum = [&](const float* t, int yy, int xx) -> float {
     if (yy < y0 || yy >= y1 || xx < x0 || xx >= x1) return 0.0f;           // zero padding of the shaved image
@@ -521,13 +503,8 @@ __global__ __launch_bounds__(256) void val_metrics_kernel(const float* __restric
     const float m = ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s1 + s2 + C2));
     local += (double)m;
   }
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) ssim[img] = red[0] / ((double)h2 * w2);
+  const double ss = srad_block_sum(local, red);
+  if (threadIdx.x == 0) ssim[img] = ss / ((double)h2 * w2);
 }
 
 int chunk_images(int n_img, int H, int W) {
@@ -548,6 +525,56 @@ inline SweepKernel sweep_kernel(int H, int W) { return lds_sweep_ok(H, W) ? kSwe
 inline int grid1d(size_t total) {
   size_t b = (total + 255) / 256;
   return (int)std::min<size_t>(std::max<size_t>(b, 1), 4096);
+}
+
+// Workspace of srad_score_pairs (sweep) and srad_anomaly_maps for n_img H x W pairs, each part 256-byte aligned: the tables of
+// one chunk of images, the sweep's partial sums (sweep only) and the column pass's segment totals.  base == nullptr: sizes only.
+struct ScoreWs {
+  int chunk, nseg, nblk;          // images per chunk, 32-row segments per table column, partial slots per (image, window size)
+  double *sat, *partial, *segtot;
+  size_t bytes;
+};
+ScoreWs plan_score_ws(int n_img, int H, int W, bool sweep, void* base) {
+  ScoreWs w;
+  w.chunk = chunk_images(n_img, H, W);
+  w.nseg = (H + kSeg - 1) / kSeg;
+  w.nblk = partial_slots(H, W);
+  Bump bp(base, 0);
+  auto take = [&](size_t doubles) { return reinterpret_cast<double*>(bp.take(2 * doubles)); };    // Bump counts floats
+  w.sat = take((size_t)w.chunk * (H + 1) * (W + 1) * kQ);
+  w.partial = sweep ? take((size_t)w.chunk * kWsGroup * w.nblk) : nullptr;
+  w.segtot = take((size_t)w.chunk * kQ * w.nseg * (W + 1));
+  w.bytes = bp.used;
+  return w;
+}
+
+// The five tables of n pairs (the chunk that starts at sr / hr): the row pass, then the column pass in 32-row segments.
+void build_tables(const ScoreWs& w, const uint8_t* sr, const uint8_t* hr, int n, int H, int W, int C, hipStream_t s) {
+  const size_t img_bytes = (size_t)H * W * C;
+  {
+    SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W, 2.0 * n * img_bytes + 40.0 * n * (H + 1) * (W + 1));
+    hipLaunchKernelGGL(sat_rows_kernel, dim3((n * (H + 1) + 3) / 4), dim3(256), 0, s, sr, hr, w.sat, n, H, W, C);
+  }
+  const size_t t = (size_t)n * kQ * w.nseg * (W + 1);
+  SradProfScope prof(s, SRAD_K_SCORE, 1.0 * n * (H + 1) * (W + 1) * kQ, 80.0 * n * (H + 1) * (W + 1));
+  hipLaunchKernelGGL(sat_cols_local_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, w.sat, w.segtot, n * kQ, H, W, w.nseg);
+  if (w.nseg > 1) {
+    const size_t t2 = (size_t)n * kQ * (w.nseg - 1) * (W + 1);
+    hipLaunchKernelGGL(sat_cols_carry_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, w.sat, w.segtot, n * kQ, H, W, w.nseg);
+  }
+}
+
+// argument checks shared by srad_score_pairs and srad_anomaly_maps; `what` (the entry point) starts each message
+int check_pairs(const char* what, const uint8_t* sr, const uint8_t* hr, const void* workspace, int n_img, int H, int W, int C) {
+  SRAD_REQUIRE(sr && hr && workspace && n_img > 0 && H > 1 && W > 1, "%s: bad argument", what);
+  SRAD_REQUIRE(C == 1 || C == 3, "%s: channels must be 1 or 3 (got %d)", what, C);
+  SRAD_REQUIRE((long long)(H + 1) * (W + 1) < (1ll << 31), "%s: %dx%d images are too large for the 32-bit table offsets", what, H, W);
+  return SRAD_OK;
+}
+int check_window(const char* what, int ws, int H, int W) {
+  SRAD_REQUIRE(ws >= 1 && ws / 2 < H && ws / 2 < W && ws - 1 - ws / 2 < H && ws - 1 - ws / 2 < W,
+               "%s: window %d needs more than one reflection of a %dx%d image", what, ws, H, W);
+  return SRAD_OK;
 }
 
 }  // namespace
@@ -574,63 +601,33 @@ int srad_quantize(const float* x, float* y, int64_t n, float rgb_range, void* st
 
 int srad_score_workspace_bytes(int n_img, int H, int W, size_t* bytes) {
   SRAD_REQUIRE(bytes && n_img > 0 && H > 0 && W > 0, "score_workspace_bytes: bad argument");
-  const int chunk = chunk_images(n_img, H, W);
-  const int nblk = partial_slots(H, W);
-  const int nseg = (H + kSeg - 1) / kSeg;
-  *bytes = srad_align_up((size_t)chunk * (H + 1) * (W + 1) * kQ * sizeof(double), 256) +
-           srad_align_up((size_t)chunk * kWsGroup * nblk * sizeof(double), 256) +
-           srad_align_up((size_t)chunk * kQ * nseg * (W + 1) * sizeof(double), 256);
+  *bytes = plan_score_ws(n_img, H, W, true, nullptr).bytes;
   return SRAD_OK;
 }
 
 int srad_score_pairs(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host,
                      int n_ws, double* ssim_out, double* mse_out, double* psnr_out, void* workspace,
                      size_t workspace_bytes, void* stream) {
-  SRAD_REQUIRE(sr && hr && workspace && n_img > 0 && H > 1 && W > 1, "score_pairs: bad argument");
-  SRAD_REQUIRE(C == 1 || C == 3, "score_pairs: channels must be 1 or 3 (got %d)", C);
-  SRAD_REQUIRE((long long)(H + 1) * (W + 1) < (1ll << 31), "score_pairs: %dx%d images are too large for the 32-bit table offsets", H, W);
+  SRAD_TRY(check_pairs("score_pairs", sr, hr, workspace, n_img, H, W, C));
   SRAD_REQUIRE(n_ws == 0 || (ws_host && ssim_out), "score_pairs: window list / output missing");
-  size_t need = 0;
-  SRAD_TRY(srad_score_workspace_bytes(n_img, H, W, &need));
-  SRAD_REQUIRE(workspace_bytes >= need, "score_pairs: workspace %zu bytes, %zu needed", workspace_bytes, need);
-  for (int k = 0; k < n_ws; ++k)
-    SRAD_REQUIRE(ws_host[k] >= 1 && ws_host[k] / 2 < H && ws_host[k] / 2 < W && ws_host[k] - 1 - ws_host[k] / 2 < H &&
-                     ws_host[k] - 1 - ws_host[k] / 2 < W,
-                 "score_pairs: window %d needs more than one reflection of a %dx%d image", ws_host[k], H, W);
+  const ScoreWs w = plan_score_ws(n_img, H, W, true, workspace);
+  SRAD_REQUIRE(workspace_bytes >= w.bytes, "score_pairs: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
+  for (int k = 0; k < n_ws; ++k) SRAD_TRY(check_window("score_pairs", ws_host[k], H, W));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int chunk = chunk_images(n_img, H, W);
-  const int nblk = partial_slots(H, W);
-  double* sat = reinterpret_cast<double*>(workspace);
-  double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) +
-                                              srad_align_up((size_t)chunk * (H + 1) * (W + 1) * kQ * sizeof(double), 256));
-  double* segtot = reinterpret_cast<double*>(reinterpret_cast<char*>(partial) + srad_align_up((size_t)chunk * kWsGroup * nblk * sizeof(double), 256));
-  const int nseg = (H + kSeg - 1) / kSeg;
   const size_t img_bytes = (size_t)H * W * C;
   const bool want_mse = mse_out && psnr_out;
-  for (int i0 = 0; i0 < n_img && (n_ws > 0 || want_mse); i0 += chunk) {
-    const int n = std::min(chunk, n_img - i0);
+  for (int i0 = 0; i0 < n_img && (n_ws > 0 || want_mse); i0 += w.chunk) {
+    const int n = std::min(w.chunk, n_img - i0);
     const uint8_t* srp = sr + (size_t)i0 * img_bytes;
     const uint8_t* hrp = hr + (size_t)i0 * img_bytes;
     if (want_mse) {                                   // block partials in the (not yet used) SSIM partial area: nb <= kWsGroup * nblk
-      const int nb = std::min(64, nblk);
+      const int nb = std::min(64, w.nblk);
       SradProfScope prof(s, SRAD_K_SCORE, 3.0 * n * img_bytes, 2.0 * n * img_bytes);
-      hipLaunchKernelGGL(mse_partial_kernel, dim3(nb, n), dim3(256), 0, s, srp, hrp, partial, img_bytes, nb);
-      hipLaunchKernelGGL(mse_finish_kernel, dim3((n + 63) / 64), dim3(64), 0, s, partial, mse_out + i0, psnr_out + i0, n, nb, (double)img_bytes);
+      hipLaunchKernelGGL(mse_partial_kernel, dim3(nb, n), dim3(256), 0, s, srp, hrp, w.partial, img_bytes, nb);
+      hipLaunchKernelGGL(mse_finish_kernel, dim3((n + 63) / 64), dim3(64), 0, s, w.partial, mse_out + i0, psnr_out + i0, n, nb, (double)img_bytes);
     }
     if (n_ws == 0) continue;
-    {
-      SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W, 2.0 * n * img_bytes + 40.0 * n * (H + 1) * (W + 1));
-      hipLaunchKernelGGL(sat_rows_kernel, dim3((n * (H + 1) + 3) / 4), dim3(256), 0, s, srp, hrp, sat, n, H, W, C);
-    }
-    {
-      const size_t t = (size_t)n * kQ * nseg * (W + 1);
-      SradProfScope prof(s, SRAD_K_SCORE, 1.0 * n * (H + 1) * (W + 1) * kQ, 80.0 * n * (H + 1) * (W + 1));
-      hipLaunchKernelGGL(sat_cols_local_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, sat, segtot, n * kQ, H, W, nseg);
-      if (nseg > 1) {
-        const size_t t2 = (size_t)n * kQ * (nseg - 1) * (W + 1);
-        hipLaunchKernelGGL(sat_cols_carry_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, sat, segtot, n * kQ, H, W, nseg);
-      }
-    }
+    build_tables(w, srp, hrp, n, H, W, C, s);
     for (int k0 = 0; k0 < n_ws; k0 += kWsGroup) {      // up to kWsGroup window sizes per launch
       const int g = std::min(kWsGroup, n_ws - k0);
       WsList wl{};
@@ -646,15 +643,17 @@ int srad_score_pairs(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int
           const size_t lds = ((size_t)2 * kQ * rb * (W + 1) + 32) * sizeof(double);
           int lw = 0;
           while ((1 << lw) < W) ++lw;
-          SRAD_TRY(srad_launch_dyn<ssim_rows_lds_kernel>(dim3((unsigned)((size_t)nt_blocks * n)), dim3(1024), lds, s, sat, partial, H, lw, wl, g,
-                                                         t_first, nt_blocks));
+          SRAD_TRY(srad_launch_dyn<ssim_rows_lds_kernel>(dim3((unsigned)((size_t)nt_blocks * n)), dim3(1024), lds, s, w.sat, w.partial, H, lw,
+                                                         wl, g, t_first, nt_blocks));
         } else if (kern == kSweepRows)
-          hipLaunchKernelGGL(ssim_eval_kernel<true>, dim3((unsigned)((size_t)nblk * g * n)), dim3(256), 0, s, sat, partial, H, W, wl, nblk, g, n);
+          hipLaunchKernelGGL(ssim_eval_kernel<true>, dim3((unsigned)((size_t)w.nblk * g * n)), dim3(256), 0, s, w.sat, w.partial, H, W, wl,
+                             w.nblk, g, n);
         else
-          hipLaunchKernelGGL(ssim_eval_kernel<false>, dim3((unsigned)((size_t)nblk * g * n)), dim3(256), 0, s, sat, partial, H, W, wl, nblk, g, n);
+          hipLaunchKernelGGL(ssim_eval_kernel<false>, dim3((unsigned)((size_t)w.nblk * g * n)), dim3(256), 0, s, w.sat, w.partial, H, W, wl,
+                             w.nblk, g, n);
       }
-      hipLaunchKernelGGL(ssim_finish_kernel, dim3(n * g), dim3(256), 0, s, partial, ssim_out + (size_t)i0 * n_ws, n, g,
-                         nblk, n_ws, k0, 1.0 / ((double)H * W));
+      hipLaunchKernelGGL(ssim_finish_kernel, dim3(n * g), dim3(256), 0, s, w.partial, ssim_out + (size_t)i0 * n_ws, n, g,
+                         w.nblk, n_ws, k0, 1.0 / ((double)H * W));
     }
   }
   SRAD_CHECK_HIP(hipGetLastError());
@@ -665,6 +664,35 @@ int srad_score_plan(int n_img, int H, int W, int* kernel, int* chunk) {
   SRAD_REQUIRE(kernel && chunk && n_img > 0 && H > 1 && W > 1, "score_plan: bad argument");
   *kernel = (int)sweep_kernel(H, W);
   *chunk = chunk_images(n_img, H, W);
+  return SRAD_OK;
+}
+
+int srad_anomaly_map_workspace_bytes(int n_img, int H, int W, size_t* bytes) {
+  SRAD_REQUIRE(bytes && n_img > 0 && H > 0 && W > 0, "anomaly_map_workspace_bytes: bad argument");
+  *bytes = plan_score_ws(n_img, H, W, false, nullptr).bytes;
+  return SRAD_OK;
+}
+
+int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  SRAD_REQUIRE(map_out, "anomaly_maps: bad argument");
+  SRAD_TRY(check_pairs("anomaly_maps", sr, hr, workspace, n_img, H, W, C));
+  SRAD_TRY(check_window("anomaly_maps", ws, H, W));
+  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace);
+  SRAD_REQUIRE(workspace_bytes >= w.bytes, "anomaly_maps: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int nblk = (H * W + 255) / 256;
+  const size_t img_bytes = (size_t)H * W * C;
+  const double dinv = 1.0 / ((double)ws * (double)ws);
+  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
+    const int n = std::min(w.chunk, n_img - i0);
+    build_tables(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
+    // algorithmic bytes: the two fp32 luminance planes read once, the fp32 map written once
+    SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W, 12.0 * n * H * W);
+    hipLaunchKernelGGL(ssim_map_kernel, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, w.sat, map_out + (size_t)i0 * H * W, H, W,
+                       ws, dinv, nblk);
+  }
+  SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
 
@@ -704,141 +732,6 @@ int srad_roc_auc(const int32_t* labels, const double* scores, int n, double* auc
     i = j + 1;
   }
   *auc = (rank_sum - npos * (npos + 1) / 2.0) / (npos * nneg);
-  return SRAD_OK;
-}
-
-int srad_l1_workspace_bytes(size_t* bytes) {
-  SRAD_REQUIRE(bytes, "l1_workspace_bytes: null");
-  *bytes = 1024 * sizeof(double);
-  return SRAD_OK;
-}
-
-// mean |a - b| -> *out (device double).  workspace: >= srad_l1_workspace_bytes().
-int srad_l1_loss(const float* a, const float* b, int64_t n, double* out, void* workspace, void* stream) {
-  SRAD_REQUIRE(a && b && out && workspace && n > 0, "l1_loss: bad argument");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nb = (int)std::min<size_t>(1024, ((size_t)n + 255) / 256);
-  double* partial = reinterpret_cast<double*>(workspace);
-  hipLaunchKernelGGL(l1_kernel, dim3(nb), dim3(256), 0, s, a, b, (size_t)n, partial);
-  hipLaunchKernelGGL(l1_finish_kernel, dim3(1), dim3(64), 0, s, partial, nb, 1.0 / (double)n, out);
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------------------------------
-// Per-pixel anomaly maps: 1 - the SSIM map of ONE window size (the `ssim_map` src/metrics.py:66 averages), from the same float64
-// tables and with the same per-pixel arithmetic as the sweep, but one output value per pixel and no reduction.  One thread per
-// pixel, any width; the reflection pairs of either axis are skipped by wave-uniform branches when no lane of the wave needs them.
-namespace {
-
-__global__ __launch_bounds__(256) void ssim_map_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W, int ws,
-                                                       double dinv, int nblk) {
-#pragma clang fp contract(off)     // as in ssim_eval_kernel
-  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
-  const int npix = H * W, pad = ws / 2;
-  const int p = pb * 256 + (int)threadIdx.x;
-  const int pix = min(p, npix - 1);                                      // lanes past the end compute a copy of the last pixel
-  const int i = pix / W, j = pix - i * W;
-  const int iper = W + 1;
-  const size_t plane = (size_t)(H + 1) * iper;
-  const double* const S = sat + (size_t)img * kQ * plane;
-  int ri[6], ci[6];
-  axis_pairs(i - pad, i + ws - 1 - pad, H, ri);
-  axis_pairs(j - pad, j + ws - 1 - pad, W, ci);
-  const bool row_lo = __builtin_amdgcn_ballot_w64(i - pad < 0) != 0, row_hi = __builtin_amdgcn_ballot_w64(i + ws - 1 - pad > H - 1) != 0;
-  const bool col_lo = __builtin_amdgcn_ballot_w64(j - pad < 0) != 0, col_hi = __builtin_amdgcn_ballot_w64(j + ws - 1 - pad > W - 1) != 0;
-  double sum[kQ] = {0, 0, 0, 0, 0};
-  auto row_pair = [&](auto RP) __attribute__((always_inline)) {
-    constexpr int rp = decltype(RP)::value;
-    const int oa = ri[2 * rp] * iper, ob = ri[2 * rp + 1] * iper;
-    auto col_pair = [&](auto CP) __attribute__((always_inline)) {
-      constexpr int cp = decltype(CP)::value;
-      double va[kQ], vb[kQ], vc[kQ], vd[kQ];
-#pragma unroll
-      for (int q = 0; q < kQ; ++q) {
-        const double* Sq = S + (size_t)q * plane;
-        va[q] = Sq[oa + ci[2 * cp]]; vb[q] = Sq[oa + ci[2 * cp + 1]];
-        vc[q] = Sq[ob + ci[2 * cp]]; vd[q] = Sq[ob + ci[2 * cp + 1]];
-      }
-#pragma unroll
-      for (int q = 0; q < kQ; ++q) sum[q] += (va[q] - vb[q]) - (vc[q] - vd[q]);
-    };
-    col_pair(std::integral_constant<int, 0>{});
-    if (col_lo) col_pair(std::integral_constant<int, 1>{});
-    if (col_hi) col_pair(std::integral_constant<int, 2>{});
-  };
-  row_pair(std::integral_constant<int, 0>{});
-  if (row_lo) row_pair(std::integral_constant<int, 1>{});
-  if (row_hi) row_pair(std::integral_constant<int, 2>{});
-  const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);
-  const float mu1 = (float)(sum[0] * dinv), mu2 = (float)(sum[1] * dinv);
-  const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-  const float s1 = (float)(sum[2] * dinv) - mu1_sq;
-  const float s2 = (float)(sum[3] * dinv) - mu2_sq;
-  const float s12 = (float)(sum[4] * dinv) - mu12;
-  const float m = ((2.0f * mu12 + C1) * (2.0f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
-  if (p < npix) out[(size_t)img * npix + p] = 1.0f - m;
-}
-
-}  // namespace
-
-extern "C" {
-
-int srad_anomaly_map_workspace_bytes(int n_img, int H, int W, size_t* bytes) {
-  SRAD_REQUIRE(bytes && n_img > 0 && H > 0 && W > 0, "anomaly_map_workspace_bytes: bad argument");
-  const int chunk = chunk_images(n_img, H, W);
-  const int nseg = (H + kSeg - 1) / kSeg;
-  *bytes = srad_align_up((size_t)chunk * (H + 1) * (W + 1) * kQ * sizeof(double), 256) +
-           srad_align_up((size_t)chunk * kQ * nseg * (W + 1) * sizeof(double), 256);
-  return SRAD_OK;
-}
-
-int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-  SRAD_REQUIRE(sr && hr && map_out && workspace && n_img > 0 && H > 1 && W > 1, "anomaly_maps: bad argument");
-  SRAD_REQUIRE(C == 1 || C == 3, "anomaly_maps: channels must be 1 or 3 (got %d)", C);
-  SRAD_REQUIRE((long long)(H + 1) * (W + 1) < (1ll << 31), "anomaly_maps: %dx%d images are too large for the 32-bit table offsets", H, W);
-  SRAD_REQUIRE(ws >= 1 && ws / 2 < H && ws / 2 < W && ws - 1 - ws / 2 < H && ws - 1 - ws / 2 < W,
-               "anomaly_maps: window %d needs more than one reflection of a %dx%d image", ws, H, W);
-  size_t need = 0;
-  SRAD_TRY(srad_anomaly_map_workspace_bytes(n_img, H, W, &need));
-  SRAD_REQUIRE(workspace_bytes >= need, "anomaly_maps: workspace %zu bytes, %zu needed", workspace_bytes, need);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int chunk = chunk_images(n_img, H, W);
-  const int nseg = (H + kSeg - 1) / kSeg;
-  const int nblk = (H * W + 255) / 256;
-  double* sat = reinterpret_cast<double*>(workspace);
-  double* segtot = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) +
-                                             srad_align_up((size_t)chunk * (H + 1) * (W + 1) * kQ * sizeof(double), 256));
-  const size_t img_bytes = (size_t)H * W * C;
-  const double dinv = 1.0 / ((double)ws * (double)ws);
-  for (int i0 = 0; i0 < n_img; i0 += chunk) {
-    const int n = std::min(chunk, n_img - i0);
-    const uint8_t* srp = sr + (size_t)i0 * img_bytes;
-    const uint8_t* hrp = hr + (size_t)i0 * img_bytes;
-    {
-      SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W, 2.0 * n * img_bytes + 40.0 * n * (H + 1) * (W + 1));
-      hipLaunchKernelGGL(sat_rows_kernel, dim3((n * (H + 1) + 3) / 4), dim3(256), 0, s, srp, hrp, sat, n, H, W, C);
-    }
-    {
-      const size_t t = (size_t)n * kQ * nseg * (W + 1);
-      SradProfScope prof(s, SRAD_K_SCORE, 1.0 * n * (H + 1) * (W + 1) * kQ, 80.0 * n * (H + 1) * (W + 1));
-      hipLaunchKernelGGL(sat_cols_local_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, sat, segtot, n * kQ, H, W, nseg);
-      if (nseg > 1) {
-        const size_t t2 = (size_t)n * kQ * (nseg - 1) * (W + 1);
-        hipLaunchKernelGGL(sat_cols_carry_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, sat, segtot, n * kQ, H, W, nseg);
-      }
-    }
-    {
-      // algorithmic bytes: the two fp32 luminance planes read once, the fp32 map written once
-      SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W, 12.0 * n * H * W);
-      hipLaunchKernelGGL(ssim_map_kernel, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, sat, map_out + (size_t)i0 * H * W, H, W,
-                         ws, dinv, nblk);
-    }
-  }
-  SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
 

@@ -75,6 +75,17 @@ __device__ __forceinline__ float srad_wave_sum(float v) {
   v += __shfl_xor(v, 32);
   return v;
 }
+// Sum over a 256-thread workgroup, in every thread: a fixed-order float64 tree through red[256], so the result is
+// bit-reproducible.  Every thread reads red[0] last: a barrier must come before red is written again.
+__device__ __forceinline__ double srad_block_sum(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return red[0];
+}
 #endif
 
 #define SRAD_CHECK_HIP(expr)                                                              \

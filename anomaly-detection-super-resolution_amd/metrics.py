@@ -11,12 +11,17 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._lib import ws_buffer as _ws_buffer      # the name tests/test_gpu_pro.py calls for its direct C-ABI checks
 
 
-def _ws_buffer(nbytes: int, device) -> Tuple[torch.Tensor, C.c_void_p, C.c_size_t]:
-    t = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    off = (-t.data_ptr()) % 256
-    return t, C.c_void_p(t.data_ptr() + off), C.c_size_t(nbytes)
+def _call_with_ws(query: str, qargs: tuple, fn: str, args: tuple, device, sized: bool = True) -> None:
+    """``srad_<fn>(*args, workspace[, workspace bytes], stream)`` with a fresh workspace of the size ``srad_<query>(*qargs)``
+    reports (``sized=False``: the entry point takes no byte count)."""
+    lib = L.lib()
+    nbytes = C.c_size_t()
+    L.check(getattr(lib, "srad_" + query)(*qargs, C.byref(nbytes)), query)
+    keep, wp, wb = _ws_buffer(nbytes.value, device)
+    L.check(getattr(lib, "srad_" + fn)(*args, wp, *((wb,) if sized else ()), L.current_stream_ptr()), fn)
 
 
 def _need_cuda(*ts):
@@ -59,11 +64,8 @@ def score_pairs(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Sequence
     ssim = torch.empty(n, len(window_sizes), dtype=torch.float64, device=dev)
     mse = torch.empty(n, dtype=torch.float64, device=dev)
     psnr = torch.empty(n, dtype=torch.float64, device=dev)
-    nbytes = C.c_size_t()
-    L.check(L.lib().srad_score_workspace_bytes(n, H, W, C.byref(nbytes)), "score_workspace_bytes")
-    keep, wp, wb = _ws_buffer(nbytes.value, dev)
-    L.check(L.lib().srad_score_pairs(L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, ws, len(window_sizes), L.dptr(ssim),
-                                     L.dptr(mse), L.dptr(psnr), wp, wb, L.current_stream_ptr()), "score_pairs")
+    _call_with_ws("score_workspace_bytes", (n, H, W), "score_pairs",
+                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, ws, len(window_sizes), L.dptr(ssim), L.dptr(mse), L.dptr(psnr)), dev)
     return ssim, mse, psnr
 
 
@@ -117,11 +119,8 @@ def anomaly_maps(sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws: int) -> torch.Ten
     sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
     n, H, W, Cc = sr_u8.shape
     out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
-    nbytes = C.c_size_t()
-    L.check(L.lib().srad_anomaly_map_workspace_bytes(n, H, W, C.byref(nbytes)), "anomaly_map_workspace_bytes")
-    keep, wp, wb = _ws_buffer(nbytes.value, sr_u8.device)
-    L.check(L.lib().srad_anomaly_maps(L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, int(ws), L.dptr(out), wp, wb,
-                                      L.current_stream_ptr()), "anomaly_maps")
+    _call_with_ws("anomaly_map_workspace_bytes", (n, H, W), "anomaly_maps",
+                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, int(ws), L.dptr(out)), sr_u8.device)
     return out
 
 
@@ -139,11 +138,8 @@ def pixel_roc_auc(scores: torch.Tensor, labels: torch.Tensor) -> float:
         raise ValueError("pixel_roc_auc of no elements")
     counts = torch.empty(4, dtype=torch.int64, device=s.device)          # u64 on the device; the values stay below 2^62
     auc = torch.empty((), dtype=torch.float64, device=s.device)
-    nbytes = C.c_size_t()
-    L.check(L.lib().srad_pixel_auc_workspace_bytes(C.c_int64(s.numel()), C.byref(nbytes)), "pixel_auc_workspace_bytes")
-    keep, wp, wb = _ws_buffer(nbytes.value, s.device)
-    L.check(L.lib().srad_pixel_roc_auc(L.dptr(s), L.dptr(y), C.c_int64(s.numel()), L.dptr(counts), L.dptr(auc), wp, wb,
-                                       L.current_stream_ptr()), "pixel_roc_auc")
+    _call_with_ws("pixel_auc_workspace_bytes", (C.c_int64(s.numel()),), "pixel_roc_auc",
+                  (L.dptr(s), L.dptr(y), C.c_int64(s.numel()), L.dptr(counts), L.dptr(auc)), s.device)
     n_pos, n_neg, n_nan, _ = counts.tolist()
     if n_nan:
         raise ValueError(f"pixel_roc_auc: {n_nan} of {s.numel()} scores are NaN")
@@ -171,11 +167,8 @@ def mask_regions(masks: torch.Tensor) -> Tuple[torch.Tensor, int]:
     n, H, W = m.shape
     size = torch.empty(n, H, W, dtype=torch.int32, device=m.device)     # u32 on the device; sizes stay below 2^31
     counts = torch.empty(3, dtype=torch.int64, device=m.device)
-    nbytes = C.c_size_t()
-    L.check(L.lib().srad_mask_regions_workspace_bytes(n, H, W, C.byref(nbytes)), "mask_regions_workspace_bytes")
-    keep, wp, wb = _ws_buffer(nbytes.value, m.device)
-    L.check(L.lib().srad_mask_regions(L.dptr(m), n, H, W, L.dptr(size), L.dptr(counts), wp, wb, L.current_stream_ptr()),
-            "mask_regions")
+    _call_with_ws("mask_regions_workspace_bytes", (n, H, W), "mask_regions", (L.dptr(m), n, H, W, L.dptr(size), L.dptr(counts)),
+                  m.device)
     return size, int(counts[0].item())
 
 
@@ -198,12 +191,9 @@ def _pixel_pro(scores: torch.Tensor, masks: torch.Tensor, fpr_limit: float, curv
     cap = n * H * W + 2 if curve else 0                                  # at most one point per distinct score, plus the two ends
     fpr = torch.empty(cap, dtype=torch.float64, device=dev) if curve else None
     pro = torch.empty(cap, dtype=torch.float64, device=dev) if curve else None
-    nbytes = C.c_size_t()
-    L.check(L.lib().srad_pixel_pro_workspace_bytes(n, H, W, C.byref(nbytes)), "pixel_pro_workspace_bytes")
-    keep, wp, wb = _ws_buffer(nbytes.value, dev)
-    L.check(L.lib().srad_pixel_pro(L.dptr(s), L.dptr(m), n, H, W, C.c_double(lim), L.dptr(counts), L.dptr(out),
-                                   L.dptr(fpr), L.dptr(pro), C.c_int64(cap), wp, wb,
-                                   L.current_stream_ptr()), "pixel_pro")
+    _call_with_ws("pixel_pro_workspace_bytes", (n, H, W), "pixel_pro",
+                  (L.dptr(s), L.dptr(m), n, H, W, C.c_double(lim), L.dptr(counts), L.dptr(out), L.dptr(fpr), L.dptr(pro),
+                   C.c_int64(cap)), dev)
     n_reg, n_ok, _, n_nan, n_pts = counts.tolist()
     if n_nan:
         raise ValueError(f"aupro: {n_nan} of {s.numel()} scores are NaN")
@@ -277,11 +267,8 @@ def smooth_maps(maps: torch.Tensor, sigma: float, truncate: float = 4.0, with_ma
     w = gaussian_weights(sigma, truncate) if r > 0 else np.ones(1)              # radius 0: the kernel copies
     out = torch.empty_like(m)
     img_max = torch.empty(n, dtype=torch.float32, device=m.device) if with_max else None
-    nbytes = C.c_size_t()
-    L.check(L.lib().srad_smooth_maps_workspace_bytes(n, H, W, r, C.byref(nbytes)), "smooth_maps_workspace_bytes")
-    keep, wp, wb = _ws_buffer(nbytes.value, m.device)
-    L.check(L.lib().srad_smooth_maps(L.dptr(m), n, H, W, w.ctypes.data_as(C.POINTER(C.c_double)), r, L.dptr(out),
-                                     L.dptr(img_max), wp, wb, L.current_stream_ptr()), "smooth_maps")
+    _call_with_ws("smooth_maps_workspace_bytes", (n, H, W, r), "smooth_maps",
+                  (L.dptr(m), n, H, W, w.ctypes.data_as(C.POINTER(C.c_double)), r, L.dptr(out), L.dptr(img_max)), m.device)
     return (out, img_max) if with_max else out
 
 
@@ -291,10 +278,8 @@ def l1_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     a, b = a.detach().float().contiguous(), b.detach().float().contiguous()
     assert a.shape == b.shape
     out = torch.empty((), dtype=torch.float64, device=a.device)
-    nbytes = C.c_size_t()
-    L.check(L.lib().srad_l1_workspace_bytes(C.byref(nbytes)), "l1_workspace_bytes")
-    keep, wp, _ = _ws_buffer(nbytes.value, a.device)
-    L.check(L.lib().srad_l1_loss(L.dptr(a), L.dptr(b), C.c_int64(a.numel()), L.dptr(out), wp, L.current_stream_ptr()), "l1_loss")
+    _call_with_ws("l1_workspace_bytes", (), "l1_loss", (L.dptr(a), L.dptr(b), C.c_int64(a.numel()), L.dptr(out)), a.device,
+                  sized=False)
     return out
 
 

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import Optional, Tuple
+from typing import Optional
 
 import torch
 
@@ -273,12 +273,6 @@ def window_attention_bwd_bf16io(qkv: torch.Tensor, dout: torch.Tensor, table: to
     return dqkv_h.float(), dtable
 
 
-def _scratch(nbytes: int, device) -> Tuple[torch.Tensor, C.c_void_p, C.c_size_t]:
-    t = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    off = (-t.data_ptr()) % 256
-    return t, C.c_void_p(t.data_ptr() + off), C.c_size_t(nbytes)
-
-
 def mlp_bwd(dx2: Optional[torch.Tensor], hpre: torch.Tensor, x1: torch.Tensor, gamma: torch.Tensor, w_fc1: torch.Tensor,
             w_fc2: torch.Tensor, rs2: Optional[torch.Tensor] = None, rps: int = 0, adjust=None, proj=None):
     """Fused backward of a Swin block's MLP branch (bf16 MFMA, C ABI ``srad_op_mlp_bwd``; src/drct.py:510, 184-190).
@@ -311,7 +305,7 @@ def mlp_bwd(dx2: Optional[torch.Tensor], hpre: torch.Tensor, x1: torch.Tensor, g
         dO = out["dO"] = torch.empty(M, d, dtype=torch.float32, device=dev)
     keep = [f(hpre), f(x1), f(gamma), f(w_fc1), f(w_fc2), f(rs2)]
     nbytes = L.lib().srad_op_mlp_bwd_scratch_bytes(d, m, KA)
-    sbuf, sp, sb = _scratch(nbytes, dev)
+    sbuf, sp, sb = L.ws_buffer(nbytes, dev)
     L.check(L.lib().srad_op_mlp_bwd(M, d, m, L.dptr(dx2), L.dptr(keep[0]), L.dptr(keep[1]), L.dptr(keep[2]), L.dptr(keep[3]),
                                     L.dptr(keep[4]), L.dptr(keep[5]), int(rps), L.dptr(out["dh"]), L.dptr(out["dx1"]),
                                     L.dptr(out["dgamma"]), L.dptr(out["dbeta"]), KA, L.dptr(dA), KA, L.dptr(y_act), KA,
@@ -336,7 +330,7 @@ def lin_ln_bwd(dy: torch.Tensor, w: torch.Tensor, x: torch.Tensor, gamma: torch.
     keep = [dy.detach().float().contiguous(), w.detach().float().contiguous(), gamma.detach().float().contiguous(),
             None if dres is None else dres.detach().float().contiguous()]
     nbytes = L.lib().srad_op_lin_ln_bwd_scratch_bytes(K, d)
-    sbuf, sp, sb = _scratch(nbytes, dev)
+    sbuf, sp, sb = L.ws_buffer(nbytes, dev)
     L.check(L.lib().srad_op_lin_ln_bwd(M, K, d, L.dptr(keep[0]), L.dptr(keep[1]), L.dptr(x), x.stride(0), L.dptr(keep[2]),
                                        L.dptr(keep[3]), L.dptr(out), out.stride(0), 1 if acc else 0, L.dptr(dg), L.dptr(db),
                                        sp, sb, wgrad_workspace(dev), L.current_stream_ptr()), "op_lin_ln_bwd")
@@ -358,7 +352,7 @@ def ln_qkv(x: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w_qkv: torch
     f = lambda t: t.detach().float().contiguous()
     keep = [f(ln_g), f(ln_b), f(w_qkv), f(b_qkv)]
     out = torch.empty(x.shape[0], 3, heads, hdp, dtype=torch.bfloat16, device=x.device)
-    sbuf, sp, sb = _scratch(L.lib().srad_op_ln_qkv_scratch_bytes(d, heads), x.device)
+    sbuf, sp, sb = L.ws_buffer(L.lib().srad_op_ln_qkv_scratch_bytes(d, heads), x.device)
     L.check(L.lib().srad_op_ln_qkv(L.dptr(x), x.stride(0), x.shape[0], d, heads, L.dptr(keep[0]), L.dptr(keep[1]), L.dptr(keep[2]),
                                    L.dptr(keep[3]), L.dptr(out), hdp, float(qs), sp, sb, L.current_stream_ptr()), "op_ln_qkv")
     return out
@@ -390,7 +384,7 @@ def qkv_attn(x: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w_qkv: tor
     f = lambda t: t.detach().float().contiguous()
     keep = [f(ln_g), f(ln_b), f(w_qkv), f(b_qkv), f(table)]
     out = torch.empty(x.shape[0], d, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
-    sbuf, sp, sb = _scratch(L.lib().srad_op_swin_scratch_bytes(d, heads, 4, 4), x.device)
+    sbuf, sp, sb = L.ws_buffer(L.lib().srad_op_swin_scratch_bytes(d, heads, 4, 4), x.device)
     L.check(L.lib().srad_op_qkv_attn(L.PRECISIONS[precision], L.dptr(x), x.stride(0), B, H, W, shift, d, heads, L.dptr(keep[0]), L.dptr(keep[1]),
                                      L.dptr(keep[2]), L.dptr(keep[3]), L.dptr(keep[4]), L.dptr(out), int(out_bf16), sp, sb,
                                      L.current_stream_ptr()), "op_qkv_attn")
@@ -422,7 +416,7 @@ def qkv_attn_train(x: torch.Tensor, ln_g, ln_b, w_qkv, b_qkv, table, B: int, H: 
          "xn_h": torch.full((T, d), fill, dtype=torch.bfloat16, device=dev),
          "qkv": torch.full((T, 3, heads, hdp), fill, dtype=torch.float32, device=dev),
          "qkv_h": torch.full((T, 3, heads, hp_h), fill, dtype=torch.bfloat16, device=dev)}
-    sbuf, sp, sb = _scratch(L.lib().srad_op_swin_scratch_bytes(d, heads, 4, 4), dev)
+    sbuf, sp, sb = L.ws_buffer(L.lib().srad_op_swin_scratch_bytes(d, heads, 4, 4), dev)
     L.check(L.lib().srad_op_qkv_attn_train(L.dptr(x), x.stride(0), B, H, W, shift, d, heads, *[L.dptr(k) for k in keep],
                                            L.dptr(r["out_h"]), L.dptr(r["xn"]), L.dptr(r["xn_h"]), L.dptr(r["qkv"]), hdp,
                                            L.dptr(r["qkv_h"]), hp_h, int(no_qsplit), sp, sb, L.current_stream_ptr()), "op_qkv_attn_train")
@@ -443,7 +437,7 @@ def mlp_block(attn: torch.Tensor, shortcut: torch.Tensor, w_proj, b_proj, ln_g, 
     attn = attn.detach().to(torch.float32 if L.PRECISIONS[precision] == L.PREC_BF16X3 else torch.bfloat16).contiguous()
     if out is None:
         out = torch.empty(M, no, dtype=torch.float32, device=attn.device)
-    sbuf, sp, sb = _scratch(L.lib().srad_op_swin_scratch_bytes(d, 1, m, no), attn.device)
+    sbuf, sp, sb = L.ws_buffer(L.lib().srad_op_swin_scratch_bytes(d, 1, m, no), attn.device)
     L.check(L.lib().srad_op_mlp_block(L.PRECISIONS[precision], M, d, m, no, int(fm), L.dptr(attn), L.dptr(shortcut), shortcut.stride(0), *[L.dptr(k) for k in keep],
                                       int(act), float(slope), float(alpha), L.dptr(residual), 0 if residual is None else residual.stride(0),
                                       L.dptr(out), out.stride(0), int(out_offset), sp, sb, L.current_stream_ptr()), "op_mlp_block")
