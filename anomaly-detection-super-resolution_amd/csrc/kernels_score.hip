@@ -402,6 +402,44 @@ __global__ __launch_bounds__(256) void ssim_map_kernel(const double* __restrict_
   if (p < npix) out[(size_t)img * npix + p] = 1.0f - m;
 }
 
+// Multi-scale anomaly maps: the maps 1 - ssim_map of the `g` window sizes of `wl` reduced to ONE value per pixel, without a map
+// per size in memory.  A pixel's thread walks the list in order with the arithmetic of ssim_map_kernel (corner_ssim) and keeps
+// one fp32 accumulator:   mean: a_1 = 1 - m_1, a_k = a_(k-1) + (1 - m_k), out = a_K * scale      max: a_k = fmaxf(a_(k-1), 1 - m_k)
+// - single IEEE fp32 operations in list order, so the result is the bits of the K single maps accumulated the same way.  Lists
+// longer than kWsGroup take several launches: `first` = 0 continues from the accumulator the launch before stored in `out`
+// (same thread, same pixel, stream order), and only the last launch of a mean gets scale = (float)(1 / K) (1 otherwise; a
+// multiply by a host-computed factor, not a division).  The loop over the sizes stays a loop: unrolled over the runtime count
+// it would hold several sizes' index sets in registers.
+// ROWS = the width is a multiple of 64: a wave's 64 pixels lie in one row, the row index is scalar (as in ssim_eval_kernel).
+template <bool ROWS>
+__global__ __launch_bounds__(256) void ssim_map_multi_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W,
+                                                             const WsList wl, int g, int reduce_max, int first, float scale, int nblk) {
+#pragma clang fp contract(off)
+  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
+  const int npix = H * W;
+  const int p = pb * 256 + (int)threadIdx.x;
+  int i, j;
+  if constexpr (ROWS) {
+    // npix is a multiple of 64 too; a wave past the end (the last block's) computes a copy of the last 64 pixels
+    const int seg0 = min(__builtin_amdgcn_readfirstlane(pb * 256 + ((int)threadIdx.x & ~63)), npix - 64);
+    i = seg0 / W; j = seg0 - i * W + ((int)threadIdx.x & 63);
+  } else {
+    const int pix = min(p, npix - 1);                                    // lanes past the end compute a copy of the last pixel
+    i = pix / W; j = pix - i * W;
+  }
+  const double* const S = sat + (size_t)img * kQ * ((size_t)(H + 1) * (W + 1));
+  float* const dst = out + (size_t)img * npix + p;
+  float acc = 0.0f;
+  if (!first && p < npix) acc = *dst;
+#pragma unroll 1
+  for (int k = 0; k < g; ++k) {
+    const float v = 1.0f - corner_ssim(S, H, W, i, j, wl.ws[k], wl.dinv[k]);
+    if (first && k == 0) acc = v;
+    else acc = reduce_max ? fmaxf(acc, v) : acc + v;
+  }
+  if (p < npix) *dst = acc * scale;
+}
+
 // mean((sr/255 - hr/255)^2) over all H*W*C values of an image: block partial sums (grid = blocks x images) ...
 __global__ __launch_bounds__(256) void mse_partial_kernel(const uint8_t* __restrict__ sr, const uint8_t* __restrict__ hr,
                                                           double* __restrict__ partial, size_t n, int nb) {
@@ -691,6 +729,43 @@ int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, in
     SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W, 12.0 * n * H * W);
     hipLaunchKernelGGL(ssim_map_kernel, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, w.sat, map_out + (size_t)i0 * H * W, H, W,
                        ws, dinv, nblk);
+  }
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_anomaly_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host, int n_ws,
+                            int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream) {
+  SRAD_REQUIRE(map_out, "anomaly_maps_multi: bad argument");
+  SRAD_REQUIRE(ws_host && n_ws >= 1, "anomaly_maps_multi: the window list is empty");
+  SRAD_REQUIRE(reduce == 0 || reduce == 1, "anomaly_maps_multi: reduce must be 0 (mean) or 1 (max), got %d", reduce);
+  SRAD_TRY(check_pairs("anomaly_maps_multi", sr, hr, workspace, n_img, H, W, C));
+  for (int k = 0; k < n_ws; ++k) SRAD_TRY(check_window("anomaly_maps_multi", ws_host[k], H, W));
+  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace);
+  SRAD_REQUIRE(workspace_bytes >= w.bytes, "anomaly_maps_multi: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int nblk = (H * W + 255) / 256;
+  const size_t img_bytes = (size_t)H * W * C;
+  const float inv_k = (float)(1.0 / (double)n_ws);
+  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
+    const int n = std::min(w.chunk, n_img - i0);
+    build_tables(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
+    float* const out = map_out + (size_t)i0 * H * W;
+    for (int k0 = 0; k0 < n_ws; k0 += kWsGroup) {      // up to kWsGroup window sizes per launch; later launches continue from `out`
+      const int g = std::min(kWsGroup, n_ws - k0);
+      WsList wl{};
+      for (int k = 0; k < g; ++k) { wl.ws[k] = (int)ws_host[k0 + k]; wl.dinv[k] = 1.0 / ((double)wl.ws[k] * (double)wl.ws[k]); }
+      const int first = k0 == 0;
+      const float scale = (reduce == 0 && k0 + g == n_ws) ? inv_k : 1.0f;
+      // algorithmic bytes: the two fp32 luminance planes read once, the fp32 map written once
+      SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W * g, 12.0 * n * H * W);
+      if (W % 64 == 0)
+        hipLaunchKernelGGL(ssim_map_multi_kernel<true>, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce,
+                           first, scale, nblk);
+      else
+        hipLaunchKernelGGL(ssim_map_multi_kernel<false>, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce,
+                           first, scale, nblk);
+    }
   }
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;

@@ -140,6 +140,16 @@ def save_anomaly_maps(maps: torch.Tensor, names: Sequence[str], splits: Sequence
         Image.fromarray(u8[k, :, :, 0]).save(str(d / f"{name}.png"))
 
 
+def resolve_map_scales(map_scales, H: int, W: int) -> List[int]:
+    """The window sizes of ``--map-scales`` for H x W images: 'sweep' = ``metrics.sweep_window_sizes(min(H, W))``, otherwise the
+    list itself; ValueError for a size the map kernels refuse at this image size (``metrics.check_map_scales``)."""
+    if isinstance(map_scales, str):
+        if map_scales != 'sweep':
+            raise ValueError(f"map_scales = {map_scales!r}: a list of window sizes or 'sweep'")
+        map_scales = M.sweep_window_sizes(min(H, W))
+    return M.check_map_scales(map_scales, H, W)
+
+
 def shard_indices(n: int, rank: int, world: int) -> List[int]:
     """Images rank ``rank`` of ``world`` scores: r, r + world, ... (image-parallel, no data-path collective)."""
     return list(range(rank, n, world))
@@ -190,8 +200,8 @@ def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndar
 def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], bad: Sequence[Tuple[np.ndarray, np.ndarray]],
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
-                     map_ws: int = 0, map_sigma: float = 0.0, map_image_score: bool = False, aupro: bool = False,
-                     pro_fpr_limit: float = 0.3) -> dict:
+                     map_ws: int = 0, map_scales=(), map_reduce: str = 'mean', map_sigma: float = 0.0,
+                     map_image_score: bool = False, aupro: bool = False, pro_fpr_limit: float = 0.3) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
     writes the SR images it produced under ``output_dir/{good,bad}/x{scale}`` (src/evaluate.py:190-224).
@@ -205,10 +215,24 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     (``metrics.smooth_maps``) before they are saved or scored, and ``map_sigma`` is added beside ``map_ws``.
     ``map_image_score``: the ROC-AUC of each image's map maximum as ``auc_map_max``, with ``map_ws``; no masks needed, and
     with world > 1 every rank's maxima are gathered to rank 0 like the score rows.  A ``map_sigma`` the maps cannot be smoothed
-    with (negative, or a radius above min(128, H, W)) raises ValueError before any image is super-resolved."""
+    with (negative, or a radius above min(128, H, W)) raises ValueError before any image is super-resolved.
+
+    ``map_scales`` (a list of window sizes, or 'sweep' for every size of the image-level sweep): the maps are the multi-scale
+    maps of ``metrics.anomaly_maps_multi`` with ``map_reduce`` ('mean' or 'max') instead of one window size's; everything after
+    them is unchanged, and the result carries ``map_scales`` (the list used) and ``map_reduce`` in place of ``map_ws``.  The
+    scales do not depend on the sweep's result.  ValueError, before any image is super-resolved, for a size the images are too
+    small for, an unknown ``map_reduce``, and scales together with a non-zero ``map_ws``."""
     if map_sigma and (good or bad):
         h, w = (list(good) + list(bad))[0][1].shape[:2]
         M.smooth_radius(map_sigma, h, w)
+    scales: List[int] = []
+    if (isinstance(map_scales, str) or len(map_scales)) and (good or bad):
+        if int(map_ws):
+            raise ValueError("map_scales and a non-zero map_ws exclude each other")
+        if map_reduce not in M.MAP_REDUCTIONS:
+            raise ValueError(f"map_reduce = {map_reduce!r}, must be one of {M.MAP_REDUCTIONS}")
+        h, w = (list(good) + list(bad))[0][1].shape[:2]
+        scales = resolve_map_scales(map_scales, h, w)
     model.eval()                                              # H1: deterministic scoring
     y_true = [0] * len(good) + [1] * len(bad)
     pairs = list(good) + list(bad)
@@ -230,7 +254,7 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     if full is None:
         if save_maps or pixel_metrics or aupro or map_image_score:
             _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, None, world, aupro,
-                         pro_fpr_limit, map_sigma, map_image_score, rank)
+                         pro_fpr_limit, map_sigma, map_image_score, rank, scales, map_reduce)
         return {}
     best_ws, best_auc, best_j = sizes[0], -1.0, 0
     for j, ws in enumerate(sizes):
@@ -242,29 +266,36 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}")
     if save_maps or pixel_metrics or aupro or map_image_score:
         out.update(_pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                                aupro, pro_fpr_limit, map_sigma, map_image_score, rank))
+                                aupro, pro_fpr_limit, map_sigma, map_image_score, rank, scales, map_reduce))
     return out
 
 
 def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                 aupro=False, pro_fpr_limit=0.3, map_sigma=0.0, map_image_score=False, rank=0) -> dict:
+                 aupro=False, pro_fpr_limit=0.3, map_sigma=0.0, map_image_score=False, rank=0, map_scales=(), map_reduce='mean') -> dict:
     """Anomaly maps of this rank's images, smoothed once when ``map_sigma`` > 0; the map-maximum image AUC on any number of
     ranks; the pixel-level AUC and AU-PRO on a single rank.  ``best_ws`` is None off rank 0.  Every branch that leads to a
-    collective depends only on the flags and ``world``, which all ranks share, so all ranks make the same collective calls."""
+    collective depends only on the flags and ``world``, which all ranks share, so all ranks make the same collective calls.
+    ``map_scales`` (a resolved list) replaces the single window size: every rank knows it, so ``best_ws`` is not broadcast."""
     scored = pixel_metrics or aupro
     if world > 1 and not (save_maps or map_image_score):      # the same branch on every rank: no collective below
         if scored and best_ws is not None:
             print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
         return {}
-    ws = int(map_ws)
-    if ws <= 0:
-        ws = best_ws
-        if world > 1:                                         # only rank 0 has the sweep's result
-            import torch.distributed as dist
-            box = [best_ws]
-            dist.broadcast_object_list(box, src=0)
-            ws = int(box[0])
-    maps = M.anomaly_maps(sr, hr, ws)
+    scales = [int(w) for w in map_scales]
+    if scales:
+        maps = M.anomaly_maps_multi(sr, hr, scales, map_reduce)
+        what, keys = f"scales={scales}, {map_reduce}", dict(map_scales=scales, map_reduce=map_reduce)
+    else:
+        ws = int(map_ws)
+        if ws <= 0:
+            ws = best_ws
+            if world > 1:                                     # only rank 0 has the sweep's result
+                import torch.distributed as dist
+                box = [best_ws]
+                dist.broadcast_object_list(box, src=0)
+                ws = int(box[0])
+        maps = M.anomaly_maps(sr, hr, ws)
+        what, keys = f"ws={ws}", dict(map_ws=ws)
     sigma = float(map_sigma)
     img_max = None
     if map_image_score:
@@ -278,8 +309,8 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
     if map_image_score:                                       # every rank: one more gather, one column of maxima
         full = gather_score_rows(mine, img_max.double().cpu().numpy()[:, None], len(y_true), rank, world)
         if full is not None:
-            out.update(map_ws=ws, auc_map_max=M.roc_auc(y_true, full[:, 0]))
-            print(f"Image AUC - max of the SSIM map (ws={ws}, sigma={sigma:g}): {out['auc_map_max']:.4f}")
+            out.update(keys, auc_map_max=M.roc_auc(y_true, full[:, 0]))
+            print(f"Image AUC - max of the SSIM map ({what}, sigma={sigma:g}): {out['auc_map_max']:.4f}")
     if sigma > 0 and out:
         out["map_sigma"] = sigma
     if not scored or best_ws is None:
@@ -296,16 +327,16 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
         if tuple(masks[i].shape) != (H, W):
             raise ValueError(f"mask {i} has shape {tuple(masks[i].shape)}, the images are {H}x{W}")
     labels = torch.from_numpy(np.stack([np.asarray(masks[i]) for i in mine])).to(maps.device)
-    out["map_ws"] = ws
+    out.update(keys)
     if sigma > 0:
         out["map_sigma"] = sigma
     tail = f", sigma={sigma:g}" if sigma > 0 else ""
     if pixel_metrics:
         out["auc_pixel"] = M.pixel_roc_auc(maps, labels)
-        print(f"Pixel AUC - SSIM map (ws={ws}{tail}): {out['auc_pixel']:.4f}")
+        print(f"Pixel AUC - SSIM map ({what}{tail}): {out['auc_pixel']:.4f}")
     if aupro:
         out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, pro_fpr_limit), float(pro_fpr_limit)
-        print(f"AU-PRO - SSIM map (ws={ws}, fpr <= {float(pro_fpr_limit):g}{tail}): {out['aupro']:.4f}")
+        print(f"AU-PRO - SSIM map ({what}, fpr <= {float(pro_fpr_limit):g}{tail}): {out['aupro']:.4f}")
     return out
 
 
@@ -332,6 +363,11 @@ def _run(args):
             M.smooth_radius(args.map_sigma, int(resolution), int(resolution))
         except ValueError as e:
             raise SystemExit(f"--map-sigma {args.map_sigma:g}: {e}")
+    if args.map_scales and resolution:
+        try:
+            resolve_map_scales(args.map_scales, int(resolution), int(resolution))
+        except ValueError as e:
+            raise SystemExit(f"--map-scales: {e}")
     ckpt = resolve_checkpoint(args)
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     if world > 1:
@@ -356,7 +392,7 @@ def _run(args):
                            names=[n for n, _, _ in g] + [n for n, _, _ in b], output_dir=out_dir, save_images=args.save_images,
                            masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws,
                            aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit, map_sigma=args.map_sigma,
-                           map_image_score=args.map_image_score)
+                           map_image_score=args.map_image_score, map_scales=args.map_scales, map_reduce=args.map_reduce)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -124,6 +124,43 @@ def anomaly_maps(sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws: int) -> torch.Ten
     return out
 
 
+MAP_REDUCTIONS = ("mean", "max")           # srad_anomaly_maps_multi's reduce numbers 0, 1
+
+
+def anomaly_maps_multi(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Sequence[int], reduce: str = "mean") -> torch.Tensor:
+    """Multi-scale anomaly maps: ``anomaly_maps`` at every size of ``window_sizes`` reduced per pixel (``reduce`` = 'mean' or
+    'max') in one kernel pass over tables built once.  The fp32 accumulation is in list order (DESIGN.md "Multi-scale maps"), so
+    the result is bit for bit ``acc = acc + anomaly_maps(.., ws_k)`` then ``acc * float32(1 / K)`` (``torch.maximum`` for 'max');
+    a size listed twice counts twice.  Returns float32 [n,H,W] on the GPU.  ValueError for an empty list or an unknown
+    ``reduce``; RuntimeError for a size ``anomaly_maps`` refuses."""
+    if reduce not in MAP_REDUCTIONS:
+        raise ValueError(f"anomaly_maps_multi: reduce = {reduce!r}, must be one of {MAP_REDUCTIONS}")
+    sizes = [int(w) for w in window_sizes]
+    if not sizes:
+        raise ValueError("anomaly_maps_multi: the window-size list is empty")
+    _need_cuda(sr_u8, hr_u8)
+    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
+    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
+    n, H, W, Cc = sr_u8.shape
+    ws = (C.c_int32 * len(sizes))(*sizes)
+    out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
+    _call_with_ws("anomaly_map_workspace_bytes", (n, H, W), "anomaly_maps_multi",
+                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, ws, len(sizes), MAP_REDUCTIONS.index(reduce), L.dptr(out)), sr_u8.device)
+    return out
+
+
+def check_map_scales(window_sizes: Sequence[int], H: int, W: int) -> List[int]:
+    """The sizes of ``window_sizes`` as a list, once every one passes the window check of the map kernels for H x W images
+    (a window may reflect over an image edge once).  ValueError otherwise.  Needs no GPU, so callers can check their arguments
+    before any work."""
+    sizes = [int(w) for w in window_sizes]
+    for ws in sizes:
+        if not (ws >= 1 and ws // 2 < min(H, W)):
+            raise ValueError(f"map scales: window {ws} needs more than one reflection of a {H}x{W} image "
+                             f"(sizes from 1 to {2 * min(H, W) - 1} fit)")
+    return sizes
+
+
 def pixel_roc_auc(scores: torch.Tensor, labels: torch.Tensor) -> float:
     """Exact pixel-level ROC-AUC (``sklearn.metrics.roc_auc_score`` of the flattened arrays, ties count one half) of GPU
     tensors: float32 scores, labels nonzero = positive (any integer or bool dtype).  Raises ValueError like ``roc_auc``

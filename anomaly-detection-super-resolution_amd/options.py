@@ -207,6 +207,23 @@ def _nonnegative_float(text: str) -> float:
     return v
 
 
+def _map_scales(text: str):
+    """--map-scales: 'sweep', or a comma-separated list of positive integers (the list; '' = none)."""
+    text = text.strip()
+    if text == 'sweep':
+        return 'sweep'
+    sizes = []
+    for part in (text.split(',') if text else []):
+        try:
+            v = int(part.strip())
+        except ValueError:
+            v = 0
+        if v < 1:
+            raise argparse.ArgumentTypeError(f"{part.strip()!r} is not a positive integer (a list like 11,21,31, or 'sweep')")
+        sizes.append(v)
+    return sizes
+
+
 def parse_eval_args(argv=None) -> argparse.Namespace:
     """src/evaluate.py:20-45 (+ --dtype, --gpus)."""
     pre = argparse.ArgumentParser(add_help=False)
@@ -244,8 +261,21 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                         "(scipy.ndimage.gaussian_filter, truncate 4); 4 is the MVTec convention, 0 = the raw maps")
     p.add_argument('--map-image-score', action='store_true', default=False,
                    help="image-level ROC-AUC of each image's anomaly-map maximum (smoothed with --map-sigma); no masks needed")
+    p.add_argument('--map-scales', type=_map_scales, default=[], metavar='LIST|sweep',
+                   help="multi-scale anomaly maps: a comma-separated list of SSIM window sizes (e.g. 11,21,31) or 'sweep' for every "
+                        "size of the image-level sweep, combined per pixel with --map-reduce; replaces --map-ws")
+    p.add_argument('--map-reduce', type=str, default='mean', choices=['mean', 'max'],
+                   help="how --map-scales combines the maps of its window sizes")
     _with_config(p, pre_args)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if isinstance(args.map_scales, (list, tuple)):            # a list from a config file gets the command line's check
+        try:
+            args.map_scales = _map_scales(','.join(str(v) for v in args.map_scales))
+        except argparse.ArgumentTypeError as e:
+            p.error(f"argument --map-scales: {e}")
+    if args.map_scales and args.map_ws:
+        p.error("--map-scales and --map-ws exclude each other (the scales replace the single window size)")
+    return args
 
 
 def build_opt(model_type: str, class_name: str, resolution: int, scale: int, batch_size: int = 1, dtype: str = 'fp32',

@@ -205,6 +205,15 @@ int srad_roc_auc(const int32_t* labels, const double* scores, int n, double* auc
 int srad_anomaly_map_workspace_bytes(int n_img, int H, int W, size_t* bytes);
 int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* Multi-scale anomaly maps: the maps of srad_anomaly_maps at the `n_ws` >= 1 window sizes of the HOST list `ws_host` (any
+ * length; duplicates count twice), reduced per pixel in one pass over the tables - no map per size is stored.  With
+ * d_k = 1 - ssim_map at ws_host[k - 1], every step one IEEE fp32 operation:
+ *   reduce 0 (mean): a_1 = d_1, a_k = a_(k-1) + d_k in LIST ORDER, map_out = a_K * (float)(1.0 / n_ws)
+ *   reduce 1 (max):  a_1 = d_1, a_k = fmaxf(a_(k-1), d_k), map_out = a_K
+ * so map_out is bit for bit the srad_anomaly_maps outputs accumulated that way, and n_ws = 1 gives srad_anomaly_maps itself.
+ * Every size must pass the window check of srad_anomaly_maps; workspace >= srad_anomaly_map_workspace_bytes. */
+int srad_anomaly_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host,
+                            int n_ws, int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Exact ROC-AUC of `n` DEVICE float32 scores against DEVICE u8 labels (labels[i] != 0 = positive), n < 2^31:
  * sklearn.metrics.roc_auc_score as the Mann-Whitney U with ties counted one half (a device radix sort, no binning).
  *   counts_out (DEVICE, 4 x u64) = {n_pos, n_neg, n_nan, twice_U};  *auc_out (DEVICE double) = twice_U / (2 n_pos n_neg),
