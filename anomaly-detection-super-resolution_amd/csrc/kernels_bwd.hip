@@ -1,9 +1,8 @@
 // kernels_bwd.hip - backward kernels of the training step on gfx950 (reference src/trainer.py:152-222:
 // loss.backward() through src/drct.py / src/drn.py; the arithmetic is PyTorch autograd's for Linear,
-// conv2d, LayerNorm, softmax attention, GELU / LeakyReLU and PixelShuffle).
+// conv2d, LayerNorm, GELU / LeakyReLU and PixelShuffle; the attention backward is kernels_attn_bwd.hip).
 //
 //   wgrad_kernel            dW += dY^T A(X)      MFMA straight from global memory, no LDS staging
-//   window_attn_bwd_kernel  dq, dk, dv, dtable   recomputes P per (window, head) from the saved q|k|v
 //   ln_bwd_kernel           dx, dgamma, dbeta    one wave per row, statistics recomputed
 //   small elementwise kernels (activation backward, pixel un-shuffle, column copies, L1 seed, Adam)
 //
@@ -1174,919 +1173,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdParams p, float*
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// Window attention backward for 8x8 windows (N = 64 tokens), one workgroup per (window, head).
-// Pass A walks the head dimension in chunks of 32 columns accumulating S = (q*scale) k^T and
-// dP = dO v^T in MFMA accumulators; the softmax is redone in registers exactly as the forward kernel
-// does (bias table + 0/-100 shift mask), dS = P (dP - rowsum(P dP)); P and dS go to LDS.
-// Pass B walks the chunks again: dq = scale dS k, dk = dS^T (q*scale), dv = P^T dO.
-// All MFMAs are v_mfma_f32_16x16x4_f32 (fp32 in, fp32 out) in both precision modes.
-// ------------------------------------------------------------------------------------------
-constexpr int AB_HC = 32, AB_HS = AB_HC + 4, AB_PS = 64 + 4;
-constexpr size_t AB_LDS = (size_t)(4 * 64 * AB_HS + 2 * 64 * AB_PS + 2 * 256) * sizeof(float) + 2 * 64 * sizeof(int);
-
-__global__ __launch_bounds__(256) void window_attn_bwd_kernel(const AttnBwdParams p, float* __restrict__ tpart) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* Qs = reinterpret_cast<float*>(smem);
-  float* Ks = Qs + 64 * AB_HS;
-  float* Vs = Ks + 64 * AB_HS;
-  float* Gs = Vs + 64 * AB_HS;
-  float* Pm = Gs + 64 * AB_HS;
-  float* Dm = Pm + 64 * AB_PS;
-  float* tbl = Dm + 64 * AB_PS;      // [225] (256 reserved)
-  float* dtb = tbl + 256;
-  int* tok = reinterpret_cast<int*>(dtb + 256);
-  int* inf = tok + 64;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int ws = 8, d = p.d, heads = p.heads, hd = d / heads, hdp = p.hdp;
-  const int ldq = 3 * heads * hdp;
-  const int nWx = p.W / ws, nW = (p.H / ws) * nWx;
-  // workgroups are dealt round-robin over the 8 XCDs: keep all heads of a window on ONE XCD (its L2 then holds the
-  // window's dO / dqkv lines, which the heads share at 4-byte granularity, once)
-  int win, h;
-  {
-    const int L = blockIdx.x, nwin = p.B * nW;
-    if ((nwin & 7) == 0) { const int slot = L >> 3; win = (slot / heads) * 8 + (L & 7); h = slot - (slot / heads) * heads; }
-    else { win = L / heads; h = L - win * heads; }
-  }
-  const int b = win / nW, widx = win - b * nW;
-  const int wy = widx / nWx, wx = widx - wy * nWx;
-  const float scale = rsqrtf((float)hd);
-  const int tw = 2 * ws - 1;
-
-  if (tid < 64) {
-    const int py = tid / ws, px = tid - py * ws;
-    const int r = wy * ws + py, c = wx * ws + px;
-    int orr = r + p.shift; if (orr >= p.H) orr -= p.H;
-    int occ = c + p.shift; if (occ >= p.W) occ -= p.W;
-    tok[tid] = (b * p.H + orr) * p.W + occ;
-    const int rh = r < p.H - ws ? 0 : (r < p.H - p.shift ? 1 : 2);
-    const int rw = c < p.W - ws ? 0 : (c < p.W - p.shift ? 1 : 2);
-    inf[tid] = ((rh * 3 + rw) << 16) | (py << 8) | px;
-  }
-  if (tid < tw * tw) tbl[tid] = p.table[(size_t)tid * heads + h];
-  __syncthreads();
-
-  // chunk staging: q/k/v as float4 (head-padded rows are 16-byte aligned), dO as scalars
-  auto stage = [&](int ch, bool need_v) {
-    const int col0 = ch * AB_HC;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = tid + 256 * i;
-      const int row = idx >> 3, c = col0 + (idx & 7) * 4;
-      const float* base = p.qkv + (size_t)tok[row] * ldq + h * hdp + min(c, hdp - 4);
-      f32x4 q4 = *reinterpret_cast<const f32x4*>(base);
-      f32x4 k4 = *reinterpret_cast<const f32x4*>(base + heads * hdp);
-      f32x4 v4 = need_v ? *reinterpret_cast<const f32x4*>(base + 2 * heads * hdp) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bool ok = c + e < hd;
-        q4[e] = ok ? q4[e] * scale : 0.f;
-        k4[e] = ok ? k4[e] : 0.f;
-        v4[e] = ok ? v4[e] : 0.f;
-      }
-      *reinterpret_cast<f32x4*>(Qs + row * AB_HS + (idx & 7) * 4) = q4;
-      *reinterpret_cast<f32x4*>(Ks + row * AB_HS + (idx & 7) * 4) = k4;
-      if (need_v) *reinterpret_cast<f32x4*>(Vs + row * AB_HS + (idx & 7) * 4) = v4;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = tid + 256 * i;
-      const int row = idx >> 5, cl = idx & 31, c = col0 + cl;
-      const float g = p.dout[(size_t)tok[row] * d + h * hd + min(c, hd - 1)];
-      Gs[row * AB_HS + cl] = c < hd ? g : 0.f;
-    }
-  };
-
-  const int nch = (hd + AB_HC - 1) / AB_HC;
-  f32x4 s[4], dp[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  for (int ch = 0; ch < nch; ++ch) {
-    if (ch > 0) __syncthreads();
-    stage(ch, true);
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < AB_HC; kk += 16) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(Qs + (wave * 16 + fr) * AB_HS + kk + 4 * fq);
-      const f32x4 g = *reinterpret_cast<const f32x4*>(Gs + (wave * 16 + fr) * AB_HS + kk + 4 * fq);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 kb = *reinterpret_cast<const f32x4*>(Ks + (j * 16 + fr) * AB_HS + kk + 4 * fq);
-        const f32x4 vb = *reinterpret_cast<const f32x4*>(Vs + (j * 16 + fr) * AB_HS + kk + 4 * fq);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          s[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], kb[e], s[j], 0, 0, 0);
-          dp[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(g[e], vb[e], dp[j], 0, 0, 0);
-        }
-      }
-    }
-  }
-
-  // ---- softmax (row = 16 wave + 4 fq + e, key = 16 j + fr), dS, bias-table gradient ----
-  {
-    int kinf[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) kinf[j] = inf[j * 16 + fr];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int row = wave * 16 + fq * 4 + e;
-      const int qi = inf[row];
-      const int qy = (qi >> 8) & 0xff, qx = qi & 0xff, qr = qi >> 16;
-      int bi[4];
-      float mx = -1e30f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int kyy = (kinf[j] >> 8) & 0xff, kxx = kinf[j] & 0xff, kr = kinf[j] >> 16;
-        bi[j] = (qy - kyy + ws - 1) * tw + (qx - kxx + ws - 1);
-        float v = s[j][e] + tbl[bi[j]];
-        if (p.shift > 0 && qr != kr) v += -100.0f;
-        s[j][e] = v;
-        mx = fmaxf(mx, v);
-      }
-      mx = srad_row16_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j][e] = expf(s[j][e] - mx); sum += s[j][e]; }
-      sum = srad_row16_sum(sum);
-      const float inv = 1.0f / sum;
-      float dl = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j][e] *= inv; dl += s[j][e] * dp[j][e]; }
-      dl = srad_row16_sum(dl);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float ds = s[j][e] * (dp[j][e] - dl);
-        Pm[row * AB_PS + j * 16 + fr] = s[j][e];
-        Dm[row * AB_PS + j * 16 + fr] = ds;
-      }
-    }
-  }
-  __syncthreads();
-  // bias-table gradient of this (window, head): entry t = (dy + 7) * 15 + (dx + 7) collects dS[q][k] over all query
-  // positions q whose key k = q - (dy, dx) lies in the window (<= 64 terms), read from the dS tile - no atomics.
-  // The row goes to the split-K workspace; wgrad_reduce_kernel sums the windows.
-  if (tid < tw * tw) {
-    const int dy = tid / tw - (ws - 1), dx = tid - (tid / tw) * tw - (ws - 1);
-    float acc = 0.f;
-    for (int qy = max(0, dy); qy < min(ws, ws + dy); ++qy)
-      for (int qx = max(0, dx); qx < min(ws, ws + dx); ++qx)
-        acc += Dm[(qy * ws + qx) * AB_PS + (qy - dy) * ws + (qx - dx)];
-    tpart[(size_t)win * (tw * tw * heads) + (size_t)tid * heads + h] = acc;
-  }
-
-  // ---- pass B: dq, dk, dv per 32-column chunk ----
-  for (int ch = 0; ch < nch; ++ch) {
-    if (ch > 0 || nch > 1) { __syncthreads(); stage(ch, false); __syncthreads(); }
-    f32x4 dq[2], dk[2], dv[2];
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt) { dq[jt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[jt] = dq[jt]; dv[jt] = dq[jt]; }
-#pragma unroll
-    for (int kk = 0; kk < 64; kk += 16) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(Dm + (wave * 16 + fr) * AB_PS + kk + 4 * fq);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int kr = kk + 4 * fq + e;
-        const float at = Dm[kr * AB_PS + wave * 16 + fr];     // dS^T
-        const float pt = Pm[kr * AB_PS + wave * 16 + fr];     // P^T
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt) {
-          const float kb = Ks[kr * AB_HS + jt * 16 + fr];
-          const float qb = Qs[kr * AB_HS + jt * 16 + fr];
-          const float gb = Gs[kr * AB_HS + jt * 16 + fr];
-          dq[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], kb, dq[jt], 0, 0, 0);
-          dk[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(at, qb, dk[jt], 0, 0, 0);
-          dv[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pt, gb, dv[jt], 0, 0, 0);
-        }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float* dst = p.dqkv + (size_t)tok[wave * 16 + fq * 4 + e] * (3 * d) + h * hd;
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        const int c = ch * AB_HC + jt * 16 + fr;
-        if (c < hd) {
-          dst[c] = dq[jt][e] * scale;
-          dst[d + c] = dk[jt][e];
-          dst[2 * d + c] = dv[jt][e];
-        }
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// The same backward for ANY window size up to 16 (N = ws^2 <= 256 tokens; the reference's CLI presets build windows of
-// 2, 4, 8 and 16: window_size = img_size // 4, src/main.py:286 - the 8 x 8 case has its own kernels above).  One workgroup
-// per (window, head); the window's tokens are padded to NB blocks of 64 (padding keys get probability 0, padding queries
-// are never written).  For each block of 64 queries the whole score row block (64 x 64 NB) and dP stay in MFMA
-// accumulators, so the softmax is exact in one pass as above; then key block after key block the P / dS tiles go to LDS
-// and feed dq (accumulated in registers over the key blocks), dk and dv (accumulated over the query blocks by
-// read-add-write of the workgroup's own rows: one owner, fixed order).  The bias-table gradient is collected in LDS over
-// the tiles.  All MFMAs are v_mfma_f32_16x16x4_f32 in every precision mode: these presets are small images, the kernel is
-// for coverage, not for the benchmarked configuration.
-// ------------------------------------------------------------------------------------------
-template <int NB>
-__global__ __launch_bounds__(256) void window_attn_bwd_gen_kernel(const AttnBwdParams p, float* __restrict__ tpart) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* Qs = reinterpret_cast<float*>(smem);
-  float* Ks = Qs + 64 * AB_HS;
-  float* Vs = Ks + 64 * AB_HS;
-  float* Gs = Vs + 64 * AB_HS;
-  float* Pm = Gs + 64 * AB_HS;
-  float* Dm = Pm + 64 * AB_PS;
-  float* tbl = Dm + 64 * AB_PS;      // [(2 ws - 1)^2] <= 961 (1024 reserved)
-  float* dtb = tbl + 1024;           // its gradient
-  int* tok = reinterpret_cast<int*>(dtb + 1024);   // [64 NB]
-  int* inf = tok + 64 * NB;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int ws = p.ws, N = ws * ws, d = p.d, heads = p.heads, hd = d / heads, hdp = p.hdp;
-  const int ldq = 3 * heads * hdp;
-  const int nWx = p.W / ws, nW = (p.H / ws) * nWx;
-  const int win = blockIdx.x / heads, h = blockIdx.x - win * heads;
-  const int b = win / nW, widx = win - b * nW;
-  const int wy = widx / nWx, wx = widx - wy * nWx;
-  const float scale = rsqrtf((float)hd);
-  const int tw = 2 * ws - 1, ntbl = tw * tw;
-
-  for (int t = tid; t < 64 * NB; t += 256) {
-    const int tc = min(t, N - 1);                                 // padding rows point at a real token and are masked
-    const int py = tc / ws, px = tc - py * ws;
-    const int r = wy * ws + py, c = wx * ws + px;
-    int orr = r + p.shift; if (orr >= p.H) orr -= p.H;
-    int occ = c + p.shift; if (occ >= p.W) occ -= p.W;
-    tok[t] = (b * p.H + orr) * p.W + occ;
-    const int rh = r < p.H - ws ? 0 : (r < p.H - p.shift ? 1 : 2);
-    const int rw = c < p.W - ws ? 0 : (c < p.W - p.shift ? 1 : 2);
-    inf[t] = ((rh * 3 + rw) << 16) | (py << 8) | px;
-  }
-  for (int t = tid; t < ntbl; t += 256) { tbl[t] = p.table[(size_t)t * heads + h]; dtb[t] = 0.f; }
-  __syncthreads();
-
-  // stage a 32-column chunk of 64 rows (block `blk` of the window's tokens) of q*scale / k / v / dO into its LDS tile
-  auto stage_rows = [&](float* dst, int blk, int ch, int which /* 0 q, 1 k, 2 v */) {
-    const int col0 = ch * AB_HC;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = tid + 256 * i;
-      const int row = idx >> 3, c = col0 + (idx & 7) * 4;
-      const float* base = p.qkv + (size_t)tok[blk * 64 + row] * ldq + (which * heads + h) * hdp + min(c, hdp - 4);
-      f32x4 v4 = *reinterpret_cast<const f32x4*>(base);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v4[e] = c + e < hd ? (which == 0 ? v4[e] * scale : v4[e]) : 0.f;
-      *reinterpret_cast<f32x4*>(dst + row * AB_HS + (idx & 7) * 4) = v4;
-    }
-  };
-  auto stage_g = [&](int blk, int ch) {
-    const int col0 = ch * AB_HC;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = tid + 256 * i;
-      const int row = idx >> 5, cl = idx & 31, c = col0 + cl;
-      const float g = p.dout[(size_t)tok[blk * 64 + row] * d + h * hd + min(c, hd - 1)];
-      Gs[row * AB_HS + cl] = c < hd ? g : 0.f;
-    }
-  };
-
-  const int nch = (hd + AB_HC - 1) / AB_HC;                        // <= 4 (head dims up to 128)
-  for (int qb = 0; qb < NB; ++qb) {
-    if (qb * 64 >= N) break;
-    // ---- S = (q scale) k^T and dP = dO v^T for this query block against every key block ----
-    f32x4 s[NB][4], dp[NB][4];
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[kb][j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[kb][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    for (int ch = 0; ch < nch; ++ch) {
-      __syncthreads();
-      stage_rows(Qs, qb, ch, 0);
-      stage_g(qb, ch);
-#pragma unroll
-      for (int kb = 0; kb < NB; ++kb) {
-        if (kb > 0) __syncthreads();
-        stage_rows(Ks, kb, ch, 1);
-        stage_rows(Vs, kb, ch, 2);
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < AB_HC; kk += 16) {
-          const f32x4 a = *reinterpret_cast<const f32x4*>(Qs + (wave * 16 + fr) * AB_HS + kk + 4 * fq);
-          const f32x4 g = *reinterpret_cast<const f32x4*>(Gs + (wave * 16 + fr) * AB_HS + kk + 4 * fq);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const f32x4 kbv = *reinterpret_cast<const f32x4*>(Ks + (j * 16 + fr) * AB_HS + kk + 4 * fq);
-            const f32x4 vb = *reinterpret_cast<const f32x4*>(Vs + (j * 16 + fr) * AB_HS + kk + 4 * fq);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              s[kb][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], kbv[e], s[kb][j], 0, 0, 0);
-              dp[kb][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(g[e], vb[e], dp[kb][j], 0, 0, 0);
-            }
-          }
-        }
-      }
-    }
-    // ---- softmax over the window's N keys (row = 64 qb + 16 wave + 4 fq + e, key = 64 kb + 16 j + fr), dS in place of dp ----
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int qi = inf[qb * 64 + wave * 16 + fq * 4 + e];
-      const int qy = (qi >> 8) & 0xff, qx = qi & 0xff, qr = qi >> 16;
-      float mx = -1e30f;
-#pragma unroll
-      for (int kb = 0; kb < NB; ++kb)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int key = kb * 64 + j * 16 + fr;
-          const int ki = inf[key];
-          const int kyy = (ki >> 8) & 0xff, kxx = ki & 0xff, kr = ki >> 16;
-          float v = s[kb][j][e] + tbl[(qy - kyy + ws - 1) * tw + (qx - kxx + ws - 1)];
-          if (p.shift > 0 && qr != kr) v += -100.0f;
-          if (key >= N) v = -1e30f;
-          s[kb][j][e] = v;
-          mx = fmaxf(mx, v);
-        }
-      mx = srad_row16_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NB; ++kb)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float pv = kb * 64 + j * 16 + fr < N ? expf(s[kb][j][e] - mx) : 0.f;
-          s[kb][j][e] = pv;
-          sum += pv;
-        }
-      sum = srad_row16_sum(sum);
-      const float inv = 1.0f / sum;
-      float dl = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NB; ++kb)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { s[kb][j][e] *= inv; dl += s[kb][j][e] * dp[kb][j][e]; }
-      dl = srad_row16_sum(dl);
-      const bool qreal = qb * 64 + wave * 16 + fq * 4 + e < N;      // a padding query contributes nothing to dk / dv / the table
-#pragma unroll
-      for (int kb = 0; kb < NB; ++kb)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          dp[kb][j][e] = qreal ? s[kb][j][e] * (dp[kb][j][e] - dl) : 0.f;
-          if (!qreal) s[kb][j][e] = 0.f;
-        }
-    }
-    // ---- key block after key block: P / dS tiles -> LDS, table gradient, dq (registers), dk / dv (read-add-write) ----
-    f32x4 dq[4][2];
-#pragma unroll
-    for (int ch = 0; ch < 4; ++ch) { dq[ch][0] = f32x4{0.f, 0.f, 0.f, 0.f}; dq[ch][1] = dq[ch][0]; }
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb * 64 >= N) continue;
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          Pm[(wave * 16 + fq * 4 + e) * AB_PS + j * 16 + fr] = s[kb][j][e];
-          Dm[(wave * 16 + fq * 4 + e) * AB_PS + j * 16 + fr] = dp[kb][j][e];
-        }
-      __syncthreads();
-      // table entry t = (dy + ws - 1) (2 ws - 1) + (dx + ws - 1): the dS of every (query, key = query - (dy, dx)) pair of this tile
-      for (int t = tid; t < ntbl; t += 256) {
-        const int dy = t / tw - (ws - 1), dx = t - (t / tw) * tw - (ws - 1);
-        float acc = 0.f;
-        for (int qy = max(0, dy); qy < min(ws, ws + dy); ++qy)
-          for (int qx = max(0, dx); qx < min(ws, ws + dx); ++qx) {
-            const int qn = qy * ws + qx - qb * 64, kn = (qy - dy) * ws + (qx - dx) - kb * 64;
-            if (qn >= 0 && qn < 64 && kn >= 0 && kn < 64) acc += Dm[qn * AB_PS + kn];
-          }
-        dtb[t] += acc;                                              // (one thread per entry: no race)
-      }
-#pragma unroll
-      for (int ch = 0; ch < 4; ++ch) {
-        if (ch >= nch) continue;
-        __syncthreads();
-        stage_rows(Ks, kb, ch, 1);
-        stage_rows(Qs, qb, ch, 0);
-        stage_g(qb, ch);
-        __syncthreads();
-        f32x4 dk[2], dv[2];
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt) { dk[jt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[jt] = dk[jt]; }
-#pragma unroll
-        for (int kk = 0; kk < 64; kk += 16) {
-          const f32x4 a = *reinterpret_cast<const f32x4*>(Dm + (wave * 16 + fr) * AB_PS + kk + 4 * fq);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int kr = kk + 4 * fq + e;
-            const float at = Dm[kr * AB_PS + wave * 16 + fr];     // dS^T
-            const float pt = Pm[kr * AB_PS + wave * 16 + fr];     // P^T
-#pragma unroll
-            for (int jt = 0; jt < 2; ++jt) {
-              const float kbv = Ks[kr * AB_HS + jt * 16 + fr];
-              const float qbv = Qs[kr * AB_HS + jt * 16 + fr];
-              const float gb = Gs[kr * AB_HS + jt * 16 + fr];
-              dq[ch][jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], kbv, dq[ch][jt], 0, 0, 0);
-              dk[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(at, qbv, dk[jt], 0, 0, 0);
-              dv[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pt, gb, dv[jt], 0, 0, 0);
-            }
-          }
-        }
-        // dk / dv rows of key block kb (row = 64 kb + 16 wave + 4 fq + e): first query block writes, later ones add
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int key = kb * 64 + wave * 16 + fq * 4 + e;
-          if (key >= N) continue;
-          float* dst = p.dqkv + (size_t)tok[key] * (3 * d) + h * hd;
-#pragma unroll
-          for (int jt = 0; jt < 2; ++jt) {
-            const int c = ch * AB_HC + jt * 16 + fr;
-            if (c < hd) {
-              if (qb == 0) { dst[d + c] = dk[jt][e]; dst[2 * d + c] = dv[jt][e]; }
-              else { dst[d + c] += dk[jt][e]; dst[2 * d + c] += dv[jt][e]; }
-            }
-          }
-        }
-      }
-    }
-    // dq rows of this query block
-#pragma unroll
-    for (int ch = 0; ch < 4; ++ch) {
-      if (ch >= nch) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int qrow = qb * 64 + wave * 16 + fq * 4 + e;
-        if (qrow >= N) continue;
-        float* dst = p.dqkv + (size_t)tok[qrow] * (3 * d) + h * hd;
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt) {
-          const int c = ch * AB_HC + jt * 16 + fr;
-          if (c < hd) dst[c] = dq[ch][jt][e] * scale;
-        }
-      }
-    }
-    __threadfence_block();
-  }
-  __syncthreads();
-  for (int t = tid; t < ntbl; t += 256) tpart[(size_t)win * (ntbl * heads) + (size_t)t * heads + h] = dtb[t];
-}
-constexpr size_t ABG_LDS(int nb) { return (size_t)(4 * 64 * AB_HS + 2 * 64 * AB_PS + 2 * 1024) * sizeof(float) + 2 * 64 * nb * sizeof(int); }
-
-// ------------------------------------------------------------------------------------------
-// The same backward with bf16 MFMA operands (v_mfma_f32_16x16x32_bf16, fp32 accumulation) for the bf16 precision
-// mode: q, k, v, dO chunks are staged as bf16; P and dS leave the softmax as bf16 tiles - dS in both orientations
-// (row-major for dq = dS k, transposed for dk = dS^T q), P transposed (dv = P^T dO) - and the second operand of
-// those three products (k, q, dO: contraction over tokens, their slow axis in LDS) comes through the transposing
-// LDS read ds_read_b64_tr_b16.  Softmax statistics, dS and the bias-table gradient stay fp32.
-// ------------------------------------------------------------------------------------------
-constexpr int AH_HS = 32 + 8, AH_PS = 64 + 8;
-constexpr size_t AH_LDS = (size_t)(4 * 64 * AH_HS + 3 * 64 * AH_PS) * sizeof(__bf16) + (size_t)(256 + 64 * 68) * sizeof(float) + 2 * 64 * sizeof(int);
-
-__global__ __launch_bounds__(256) void window_attn_bwd_bf16_kernel(const AttnBwdParams p, float* __restrict__ tpart) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* Qs = reinterpret_cast<__bf16*>(smem);          // [64][AH_HS] q * scale chunk
-  __bf16* Ks = Qs + 64 * AH_HS;
-  __bf16* Vs = Ks + 64 * AH_HS;
-  __bf16* Gs = Vs + 64 * AH_HS;                          // dO chunk
-  __bf16* Dm = Gs + 64 * AH_HS;                          // [query][key] dS
-  __bf16* DmT = Dm + 64 * AH_PS;                         // [key][query] dS
-  __bf16* PmT = DmT + 64 * AH_PS;                        // [key][query] P
-  float* tbl = reinterpret_cast<float*>(PmT + 64 * AH_PS);   // [225] (256 reserved)
-  float* Df = tbl + 256;                                 // [64][68] fp32 dS for the bias-table gradient
-  int* tok = reinterpret_cast<int*>(Df + 64 * 68);
-  int* inf = tok + 64;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int ws = 8, d = p.d, heads = p.heads, hd = d / heads, hdp = p.hdp;
-  const int ldq = 3 * heads * hdp;
-  const int nWx = p.W / ws, nW = (p.H / ws) * nWx;
-  // workgroups are dealt round-robin over the 8 XCDs: keep all heads of a window on ONE XCD (its L2 then holds the
-  // window's dO / dqkv lines, which the heads share at 4-byte granularity, once)
-  int win, h;
-  {
-    const int L = blockIdx.x, nwin = p.B * nW;
-    if ((nwin & 7) == 0) { const int slot = L >> 3; win = (slot / heads) * 8 + (L & 7); h = slot - (slot / heads) * heads; }
-    else { win = L / heads; h = L - win * heads; }
-  }
-  const int b = win / nW, widx = win - b * nW;
-  const int wy = widx / nWx, wx = widx - wy * nWx;
-  const float scale = rsqrtf((float)hd);
-  const int tw = 2 * ws - 1;
-
-  if (tid < 64) {
-    const int py = tid / ws, px = tid - py * ws;
-    const int r = wy * ws + py, c = wx * ws + px;
-    int orr = r + p.shift; if (orr >= p.H) orr -= p.H;
-    int occ = c + p.shift; if (occ >= p.W) occ -= p.W;
-    tok[tid] = (b * p.H + orr) * p.W + occ;
-    const int rh = r < p.H - ws ? 0 : (r < p.H - p.shift ? 1 : 2);
-    const int rw = c < p.W - ws ? 0 : (c < p.W - p.shift ? 1 : 2);
-    inf[tid] = ((rh * 3 + rw) << 16) | (py << 8) | px;
-  }
-  if (tid < tw * tw) tbl[tid] = p.table[(size_t)tid * heads + h];
-  __syncthreads();
-
-  auto stage = [&](int ch, bool need_v) {
-    const int col0 = ch * 32;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = tid + 256 * i;
-      const int row = idx >> 3, cl = (idx & 7) * 4, c = col0 + cl;
-      const float* base = p.qkv + (size_t)tok[row] * ldq + h * hdp + min(c, hdp - 4);
-      const f32x4 q4 = *reinterpret_cast<const f32x4*>(base);
-      const f32x4 k4 = *reinterpret_cast<const f32x4*>(base + heads * hdp);
-      const f32x4 v4 = need_v ? *reinterpret_cast<const f32x4*>(base + 2 * heads * hdp) : f32x4{0.f, 0.f, 0.f, 0.f};
-      bf16x4 qh, kh, vh;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bool ok = c + e < hd;
-        qh[e] = (__bf16)(ok ? q4[e] * scale : 0.f);
-        kh[e] = (__bf16)(ok ? k4[e] : 0.f);
-        vh[e] = (__bf16)(ok ? v4[e] : 0.f);
-      }
-      *reinterpret_cast<bf16x4*>(Qs + row * AH_HS + cl) = qh;
-      *reinterpret_cast<bf16x4*>(Ks + row * AH_HS + cl) = kh;
-      if (need_v) *reinterpret_cast<bf16x4*>(Vs + row * AH_HS + cl) = vh;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = tid + 256 * i;
-      const int row = idx >> 5, cl = idx & 31, c = col0 + cl;
-      const float g = p.dout[(size_t)tok[row] * d + h * hd + min(c, hd - 1)];
-      Gs[row * AH_HS + cl] = (__bf16)(c < hd ? g : 0.f);
-    }
-  };
-
-  const int nch = (hd + 31) / 32;
-  f32x4 s[4], dp[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  for (int ch = 0; ch < nch; ++ch) {
-    if (ch > 0) __syncthreads();
-    stage(ch, true);
-    __syncthreads();
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(Qs + (wave * 16 + fr) * AH_HS + 8 * fq);
-    const bf16x8 g = *reinterpret_cast<const bf16x8*>(Gs + (wave * 16 + fr) * AH_HS + 8 * fq);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bf16x8 kb = *reinterpret_cast<const bf16x8*>(Ks + (j * 16 + fr) * AH_HS + 8 * fq);
-      const bf16x8 vb = *reinterpret_cast<const bf16x8*>(Vs + (j * 16 + fr) * AH_HS + 8 * fq);
-      s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, kb, s[j], 0, 0, 0);
-      dp[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(g, vb, dp[j], 0, 0, 0);
-    }
-  }
-
-  // ---- softmax (row = 16 wave + 4 fq + e, key = 16 j + fr), dS ----
-  {
-    int kinf[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) kinf[j] = inf[j * 16 + fr];
-    f32x4 pr[4], dsr[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int row = wave * 16 + fq * 4 + e;
-      const int qi = inf[row];
-      const int qy = (qi >> 8) & 0xff, qx = qi & 0xff, qr = qi >> 16;
-      float mx = -1e30f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int kyy = (kinf[j] >> 8) & 0xff, kxx = kinf[j] & 0xff, kr = kinf[j] >> 16;
-        float v = s[j][e] + tbl[(qy - kyy + ws - 1) * tw + (qx - kxx + ws - 1)];
-        if (p.shift > 0 && qr != kr) v += -100.0f;
-        s[j][e] = v;
-        mx = fmaxf(mx, v);
-      }
-      mx = srad_row16_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j][e] = __expf(s[j][e] - mx); sum += s[j][e]; }
-      sum = srad_row16_sum(sum);
-      const float inv = 1.0f / sum;
-      float dl = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j][e] *= inv; dl += s[j][e] * dp[j][e]; }
-      dl = srad_row16_sum(dl);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float ds = s[j][e] * (dp[j][e] - dl);
-        pr[j][e] = s[j][e]; dsr[j][e] = ds;
-        Dm[row * AH_PS + j * 16 + fr] = (__bf16)ds;
-        Df[row * 68 + j * 16 + fr] = ds;
-      }
-    }
-    // transposed tiles: this lane's four rows 4 fq .. 4 fq + 3 of query slab `wave` are consecutive along k
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      bf16x4 ph, dh;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { ph[e] = (__bf16)pr[j][e]; dh[e] = (__bf16)dsr[j][e]; }
-      *reinterpret_cast<bf16x4*>(PmT + (j * 16 + fr) * AH_PS + wave * 16 + 4 * fq) = ph;
-      *reinterpret_cast<bf16x4*>(DmT + (j * 16 + fr) * AH_PS + wave * 16 + 4 * fq) = dh;
-    }
-  }
-  __syncthreads();
-  if (tid < tw * tw) {                                   // bias-table gradient row of this (window, head), fp32
-    const int dy = tid / tw - (ws - 1), dx = tid - (tid / tw) * tw - (ws - 1);
-    float acc = 0.f;
-    for (int qy = max(0, dy); qy < min(ws, ws + dy); ++qy)
-      for (int qx = max(0, dx); qx < min(ws, ws + dx); ++qx)
-        acc += Df[(qy * ws + qx) * 68 + (qy - dy) * ws + (qx - dx)];
-    tpart[(size_t)win * (tw * tw * heads) + (size_t)tid * heads + h] = acc;
-  }
-
-  // ---- pass B: dq, dk, dv per 32-column chunk ----
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-  const int tq = fr >> 2, tp = fr & 3;
-  for (int ch = 0; ch < nch; ++ch) {
-    if (ch > 0 || nch > 1) { __syncthreads(); stage(ch, false); __syncthreads(); }
-    f32x4 dq[2], dk[2], dv[2];
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt) { dq[jt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[jt] = dq[jt]; dv[jt] = dq[jt]; }
-#pragma unroll
-    for (int kk = 0; kk < 64; kk += 32) {
-      const bf16x8 a_ds = *reinterpret_cast<const bf16x8*>(Dm + (wave * 16 + fr) * AH_PS + kk + 8 * fq);
-      const bf16x8 a_dst = *reinterpret_cast<const bf16x8*>(DmT + (wave * 16 + fr) * AH_PS + kk + 8 * fq);
-      const bf16x8 a_pt = *reinterpret_cast<const bf16x8*>(PmT + (wave * 16 + fr) * AH_PS + kk + 8 * fq);
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        // B[k = token kk + 8 fq + t][j = column 16 jt + fr] of the row-major chunk tiles: two transposing reads each
-        auto tr8 = [&](const __bf16* tile) -> bf16x8 {
-          const __bf16* r0 = tile + (kk + 8 * fq + tq) * AH_HS + jt * 16 + 4 * tp;
-          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0));
-          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0 + 4 * AH_HS));
-          bf16x8 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
-          return o;
-        };
-        dq[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_ds, tr8(Ks), dq[jt], 0, 0, 0);
-        dk[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_dst, tr8(Qs), dk[jt], 0, 0, 0);
-        dv[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_pt, tr8(Gs), dv[jt], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float* dst = p.dqkv + (size_t)tok[wave * 16 + fq * 4 + e] * (3 * d) + h * hd;
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        const int c = ch * 32 + jt * 16 + fr;
-        if (c < hd) {
-          if (p.dqkv_h) {
-            __bf16* dh_ = p.dqkv_h + (size_t)tok[wave * 16 + fq * 4 + e] * (3 * d) + h * hd;
-            dh_[c] = (__bf16)(dq[jt][e] * scale);
-            dh_[d + c] = (__bf16)dk[jt][e];
-            dh_[2 * d + c] = (__bf16)dv[jt][e];
-          } else {
-            dst[c] = dq[jt][e] * scale;
-            dst[d + c] = dk[jt][e];
-            dst[2 * d + c] = dv[jt][e];
-          }
-        }
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// All-bf16 form of the same backward, the training step's case: q (already scaled and rounded, exactly the operand the
-// forward's MFMA took) | k | v and dO arrive as bf16 in per-head slots of hp columns, so a thread stages its share of a
-// 32-column chunk with four 16-byte loads issued before anything else (it derives its row's token itself), and dq | dk | dv
-// leave as bf16.  NCH = 32-column chunks of the head dim (1 .. 4).  With ONE chunk (head dim <= 32, DRCT-L's 30) the second
-// operands of the three pass-B products are fetched (transposing LDS reads) right after pass A and the staging tiles are
-// dead from then on: the fp32 dS copy the bias-table gradient sums is laid over them.  That brings the workgroup to 48.5 KB
-// of LDS - three per CU, which for the 768 (window, head) pairs of the 8-image training batch is ONE resident round on
-// 256 CUs instead of one and a half.  With more chunks pass B stages them again and the dS copy has its own 17 KB.
-// ------------------------------------------------------------------------------------------
-template <int NCH> constexpr size_t ag_lds_bytes() {
-  return (size_t)(4 * 64 * AH_HS + 3 * 64 * AH_PS) * sizeof(__bf16) + 256 * sizeof(float) + 2 * 64 * sizeof(int) +
-         (NCH > 1 ? (size_t)64 * 68 * sizeof(float) : 0);
-}
-static_assert((size_t)64 * 68 * sizeof(float) <= (size_t)4 * 64 * AH_HS * sizeof(__bf16), "the fp32 dS copy must fit in the staging tiles");
-
-template <int NCH>
-__global__ __launch_bounds__(256) void window_attn_bwd_h_kernel(const AttnBwdParams p, float* __restrict__ tpart) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* Qs = reinterpret_cast<__bf16*>(smem);          // [64][AH_HS] q * scale (32-column chunk)
-  __bf16* Ks = Qs + 64 * AH_HS;
-  __bf16* Vs = Ks + 64 * AH_HS;
-  __bf16* Gs = Vs + 64 * AH_HS;                          // dO
-  __bf16* Dm = Gs + 64 * AH_HS;                          // [query][key] dS
-  __bf16* DmT = Dm + 64 * AH_PS;                         // [key][query] dS
-  __bf16* PmT = DmT + 64 * AH_PS;                        // [key][query] P
-  float* tbl = reinterpret_cast<float*>(PmT + 64 * AH_PS);   // [225] (256 reserved)
-  int* tok = reinterpret_cast<int*>(tbl + 256);
-  int* inf = tok + 64;
-  // [64][68] fp32 dS: over Qs .. Gs once pass A is done with them (one chunk), else behind everything
-  float* Df = NCH == 1 ? reinterpret_cast<float*>(smem) : reinterpret_cast<float*>(inf + 64);
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int ws = 8, d = p.d, heads = p.heads, hd = d / heads, hp = p.hp_h;
-  const int nWx = p.W / ws, nW = (p.H / ws) * nWx;
-  int win, h;                                            // all heads of a window on one XCD (see the kernel above)
-  {
-    const int L = blockIdx.x, nwin = p.B * nW;
-    if ((nwin & 7) == 0 && !p.no_xcd_map) { const int slot = L >> 3; win = (L & 7) * (nwin >> 3) + slot / heads; h = slot - (slot / heads) * heads; }   // XCD k: window strip k (affinity with the row-tile kernels)
-    else if ((nwin & 7) == 0) { const int slot = L >> 3; win = (slot / heads) * 8 + (L & 7); h = slot - (slot / heads) * heads; }
-    else { win = L / heads; h = L - win * heads; }
-  }
-  const int b = win / nW, widx = win - b * nW;
-  const int wy = widx / nWx, wx = widx - wy * nWx;
-  const float scale = rsqrtf((float)hd);
-  const int tw = 2 * ws - 1;
-
-  auto geometry = [&](int row, int& token, int& info) {
-    const int py = row >> 3, px = row & 7;
-    const int r = wy * ws + py, c = wx * ws + px;
-    int orr = r + p.shift; if (orr >= p.H) orr -= p.H;
-    int occ = c + p.shift; if (occ >= p.W) occ -= p.W;
-    token = (b * p.H + orr) * p.W + occ;
-    const int rh = r < p.H - ws ? 0 : (r < p.H - p.shift ? 1 : 2);
-    const int rw = c < p.W - ws ? 0 : (c < p.W - p.shift ? 1 : 2);
-    info = ((rh * 3 + rw) << 16) | (py << 8) | px;
-  };
-
-  // ---- staging: thread = (row tid / 4, 8 columns of the chunk), everything in flight before the first LDS store ----
-  const int srow = tid >> 2, scl = (tid & 3) * 8;
-  int stok, sinf;
-  geometry(srow, stok, sinf);
-  const __bf16* const qrow = p.qkv_h + (size_t)stok * (3 * heads * hp) + h * hp;
-  const __bf16* const grow = p.dout_h + (size_t)stok * (heads * hp) + h * hp;
-  u32x4 sq, sk, sv, sg;
-  auto load_chunk = [&](int ch, bool need_v) __attribute__((always_inline)) {
-    const int off = min(ch * 32 + scl, hp - 8);
-    sq = *reinterpret_cast<const u32x4*>(qrow + off);
-    sk = *reinterpret_cast<const u32x4*>(qrow + heads * hp + off);
-    if (need_v) sv = *reinterpret_cast<const u32x4*>(qrow + 2 * heads * hp + off);
-    sg = *reinterpret_cast<const u32x4*>(grow + off);
-  };
-  auto store_chunk = [&](int ch, bool need_v) __attribute__((always_inline)) {
-    auto put = [&](__bf16* tile, const u32x4& raw) {        // columns at or beyond the head dim are zero in LDS
-      bf16x8 v = __builtin_bit_cast(bf16x8, raw);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = ch * 32 + scl + e < hd ? v[e] : (__bf16)0.f;
-      *reinterpret_cast<bf16x8*>(tile + srow * AH_HS + scl) = v;
-    };
-    put(Qs, sq); put(Ks, sk); if (need_v) put(Vs, sv); put(Gs, sg);
-  };
-  load_chunk(0, true);
-  {
-    const float tv = p.table[(size_t)min(tid, tw * tw - 1) * heads + h];
-    if ((tid & 3) == 0) { tok[srow] = stok; inf[srow] = sinf; }
-    tbl[tid] = tv;
-  }
-  store_chunk(0, true);
-  __syncthreads();
-
-  // ---- pass A: S = q k^T, dP = dO v^T (row = 16 wave + 4 fq + e, key = 16 j + fr) ----
-  f32x4 s[4], dp[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-  for (int ch = 0; ch < NCH; ++ch) {
-    if (ch + 1 < NCH) load_chunk(ch + 1, true);             // the next chunk's rows are in flight over this chunk's MFMAs
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(Qs + (wave * 16 + fr) * AH_HS + 8 * fq);
-    const bf16x8 g = *reinterpret_cast<const bf16x8*>(Gs + (wave * 16 + fr) * AH_HS + 8 * fq);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bf16x8 kb = *reinterpret_cast<const bf16x8*>(Ks + (j * 16 + fr) * AH_HS + 8 * fq);
-      const bf16x8 vb = *reinterpret_cast<const bf16x8*>(Vs + (j * 16 + fr) * AH_HS + 8 * fq);
-      s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, kb, s[j], 0, 0, 0);
-      dp[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(g, vb, dp[j], 0, 0, 0);
-    }
-    if (ch + 1 < NCH) { __syncthreads(); store_chunk(ch + 1, true); __syncthreads(); }
-  }
-  // second operands of pass B: B[k = token kk + 8 fq + t][j = column 16 jt + fr] of the row-major tiles
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-  const int tq = fr >> 2, tp = fr & 3;
-  auto tr8 = [&](const __bf16* tile, int kk, int jt) __attribute__((always_inline)) -> bf16x8 {
-    const __bf16* r0 = tile + (kk + 8 * fq + tq) * AH_HS + jt * 16 + 4 * tp;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0 + 4 * AH_HS));
-    bf16x8 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
-    return o;
-  };
-  bf16x8 bK[2][2], bQ[2][2], bG[2][2];
-  if constexpr (NCH == 1) {
-#pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2)
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) { bK[k2][jt] = tr8(Ks, 32 * k2, jt); bQ[k2][jt] = tr8(Qs, 32 * k2, jt); bG[k2][jt] = tr8(Gs, 32 * k2, jt); }
-  } else {
-    load_chunk(0, false);                                   // pass B walks the chunks again (k, q, dO): chunk 0 in flight over the softmax
-  }
-
-  // ---- softmax and dS in registers (their LDS reads are tbl / inf only) ----
-  f32x4 pr[4], dsr[4];
-  {
-    int kinf[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) kinf[j] = inf[j * 16 + fr];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int row = wave * 16 + fq * 4 + e;
-      const int qi = inf[row];
-      const int qy = (qi >> 8) & 0xff, qx = qi & 0xff, qr = qi >> 16;
-      float mx = -1e30f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int kyy = (kinf[j] >> 8) & 0xff, kxx = kinf[j] & 0xff, kr = kinf[j] >> 16;
-        float v = s[j][e] + tbl[(qy - kyy + ws - 1) * tw + (qx - kxx + ws - 1)];
-        if (p.shift > 0 && qr != kr) v += -100.0f;
-        s[j][e] = v;
-        mx = fmaxf(mx, v);
-      }
-      mx = srad_row16_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j][e] = __expf(s[j][e] - mx); sum += s[j][e]; }
-      sum = srad_row16_sum(sum);
-      const float inv = 1.0f / sum;
-      float dl = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j][e] *= inv; dl += s[j][e] * dp[j][e]; }
-      dl = srad_row16_sum(dl);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { pr[j][e] = s[j][e]; dsr[j][e] = s[j][e] * (dp[j][e] - dl); }
-    }
-  }
-  __syncthreads();                                       // every wave has read the staging tiles: Df (one chunk) / chunk 0 may overwrite them
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int row = wave * 16 + fq * 4 + e;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      Dm[row * AH_PS + j * 16 + fr] = (__bf16)dsr[j][e];
-      Df[row * 68 + j * 16 + fr] = dsr[j][e];
-    }
-  }
-  // transposed tiles: this lane's four rows 4 fq .. 4 fq + 3 of query slab `wave` are consecutive along k
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    bf16x4 ph, dh;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { ph[e] = (__bf16)pr[j][e]; dh[e] = (__bf16)dsr[j][e]; }
-    *reinterpret_cast<bf16x4*>(PmT + (j * 16 + fr) * AH_PS + wave * 16 + 4 * fq) = ph;
-    *reinterpret_cast<bf16x4*>(DmT + (j * 16 + fr) * AH_PS + wave * 16 + 4 * fq) = dh;
-  }
-  if constexpr (NCH > 1) store_chunk(0, false);
-  __syncthreads();
-
-  // ---- pass B: dq = dS k, dk = dS^T q, dv = P^T dO, 32 columns at a time ----
-#pragma unroll
-  for (int ch = 0; ch < NCH; ++ch) {
-    if constexpr (NCH > 1) {
-      if (ch + 1 < NCH) load_chunk(ch + 1, false);
-#pragma unroll
-      for (int k2 = 0; k2 < 2; ++k2)
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt) { bK[k2][jt] = tr8(Ks, 32 * k2, jt); bQ[k2][jt] = tr8(Qs, 32 * k2, jt); bG[k2][jt] = tr8(Gs, 32 * k2, jt); }
-    }
-    f32x4 dq[2], dk[2], dv[2];
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt) { dq[jt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[jt] = dq[jt]; dv[jt] = dq[jt]; }
-#pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
-      const bf16x8 a_ds = *reinterpret_cast<const bf16x8*>(Dm + (wave * 16 + fr) * AH_PS + 32 * k2 + 8 * fq);
-      const bf16x8 a_dst = *reinterpret_cast<const bf16x8*>(DmT + (wave * 16 + fr) * AH_PS + 32 * k2 + 8 * fq);
-      const bf16x8 a_pt = *reinterpret_cast<const bf16x8*>(PmT + (wave * 16 + fr) * AH_PS + 32 * k2 + 8 * fq);
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        dq[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_ds, bK[k2][jt], dq[jt], 0, 0, 0);
-        dk[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_dst, bQ[k2][jt], dk[jt], 0, 0, 0);
-        dv[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_pt, bG[k2][jt], dv[jt], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      __bf16* dst = p.dqkv_h + (size_t)tok[wave * 16 + fq * 4 + e] * (3 * d) + h * hd;
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        const int c = ch * 32 + jt * 16 + fr;
-        if (c < hd) {
-          dst[c] = (__bf16)(dq[jt][e] * scale);
-          dst[d + c] = (__bf16)dk[jt][e];
-          dst[2 * d + c] = (__bf16)dv[jt][e];
-        }
-      }
-    }
-    if constexpr (NCH > 1) {
-      if (ch + 1 < NCH) { __syncthreads(); store_chunk(ch + 1, false); __syncthreads(); }
-    }
-  }
-  if (tid < tw * tw) {                                   // bias-table gradient row of this (window, head), fp32
-    const int dy = tid / tw - (ws - 1), dx = tid - (tid / tw) * tw - (ws - 1);
-    float acc = 0.f;
-    for (int qy = max(0, dy); qy < min(ws, ws + dy); ++qy)
-      for (int qx = max(0, dx); qx < min(ws, ws + dx); ++qx)
-        acc += Df[(qy * ws + qx) * 68 + (qy - dy) * ws + (qx - dx)];
-    tpart[(size_t)win * (tw * tw * heads) + (size_t)tid * heads + h] = acc;
-  }
-}
-
 // ------------------------------------------------------------------------------------------ elementwise
 __global__ void dact_kernel(const float* __restrict__ dy, int ld_dy, const float* __restrict__ y, int ld_y,
                             float* __restrict__ out, int ld_out, int rows, int C, float slope) {
@@ -2235,13 +1321,19 @@ static int queue_colsum(WgradQueue& q, float* dst, const float* part, int ncols,
   return SRAD_OK;
 }
 
-int srad_wgrad_queue_ln_partials(WgradQueue& q, float* dgamma, float* dbeta, int C, int nrows, hipStream_t stream, float** part) {
-  const size_t need = (size_t)nrows * 2 * LNB_CP;
-  SRAD_REQUIRE(q.ws && need <= q.ws_floats, "ln_bwd: workspace too small");
-  if (q.batch.count + 2 > SRAD_WGRAD_BATCH || q.used + need > q.ws_floats) SRAD_TRY(srad_wgrad_flush(q, stream));
+int srad_wgrad_reserve_colsum(WgradQueue& q, const char* who, float* dst, int ncols, int row_stride, int nrows, float alpha,
+                              int nitems, hipStream_t stream, float** part) {
+  const size_t need = (size_t)nrows * row_stride;
+  SRAD_REQUIRE(q.ws && need <= q.ws_floats, "%s: workspace too small", who);
+  if (q.batch.count + nitems > SRAD_WGRAD_BATCH || q.used + need > q.ws_floats) SRAD_TRY(srad_wgrad_flush(q, stream));
   *part = q.ws + q.used;
   q.used += need;
-  if (dgamma) SRAD_TRY(queue_colsum(q, dgamma, *part, C, 2 * LNB_CP, nrows, 1.f, stream));
+  if (dst) SRAD_TRY(queue_colsum(q, dst, *part, ncols, row_stride, nrows, alpha, stream));
+  return SRAD_OK;
+}
+
+int srad_wgrad_queue_ln_partials(WgradQueue& q, float* dgamma, float* dbeta, int C, int nrows, hipStream_t stream, float** part) {
+  SRAD_TRY(srad_wgrad_reserve_colsum(q, "ln_bwd", dgamma, C, 2 * LNB_CP, nrows, 1.f, 2, stream, part));
   if (dbeta) SRAD_TRY(queue_colsum(q, dbeta, *part + LNB_CP, C, 2 * LNB_CP, nrows, 1.f, stream));
   return SRAD_OK;
 }
@@ -2265,68 +1357,6 @@ int srad_launch_ln_bwd(const LnBwdParams& p, WgradQueue& q, hipStream_t stream) 
   };
   if (p.C <= 256) go(std::integral_constant<int, 1>{});
   else go(std::integral_constant<int, 2>{});
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
-}
-
-// windows other than 8 x 8 (N = ws^2 <= 256): window_attn_bwd_gen_kernel, fp32 operands and results in every precision mode
-static int launch_attn_bwd_gen(const AttnBwdParams& p, WgradQueue& q, hipStream_t stream) {
-  SRAD_REQUIRE(p.ws >= 1 && p.ws <= 16, "window_attn_bwd: window sizes 1 .. 16 train (got %d)", p.ws);
-  SRAD_REQUIRE(p.qkv && p.dout && p.dqkv && !p.qkv_h && !p.dqkv_h, "window_attn_bwd: window sizes other than 8 take fp32 q | k | v, dO and dqkv");
-  SRAD_REQUIRE(p.d / p.heads <= 128, "window_attn_bwd: head dims up to 128 (got %d)", p.d / p.heads);
-  const int nW = (p.H / p.ws) * (p.W / p.ws), tw = 2 * p.ws - 1;
-  const int ncols = tw * tw * p.heads, nwin = p.B * nW;
-  const size_t need = (size_t)nwin * ncols;
-  SRAD_REQUIRE(q.ws && need <= q.ws_floats, "window_attn_bwd: workspace too small");
-  if (q.used + need > q.ws_floats) SRAD_TRY(srad_wgrad_flush(q, stream));
-  float* tpart = q.ws + q.used;
-  q.used += need;
-  SRAD_TRY(queue_colsum(q, p.dtable, tpart, ncols, ncols, nwin, 1.f, stream));
-  const double T = (double)p.B * p.H * p.W;
-  SradProfScope prof(stream, SRAD_K_ATTN_BWD, 10.0 * T * p.ws * p.ws * p.d, 4.0 * T * 8 * p.d);
-  const int nb = (p.ws * p.ws + 63) / 64;
-  const dim3 grid(nwin * p.heads), block(256);
-  if (nb == 1) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<1>>(grid, block, ABG_LDS(1), stream, p, tpart));
-  else if (nb == 2) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<2>>(grid, block, ABG_LDS(2), stream, p, tpart));
-  else if (nb == 3) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<3>>(grid, block, ABG_LDS(3), stream, p, tpart));
-  else SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<4>>(grid, block, ABG_LDS(4), stream, p, tpart));
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
-}
-
-int srad_launch_window_attn_bwd(int prec, const AttnBwdParams& p, WgradQueue& q, hipStream_t stream) {
-  SRAD_REQUIRE(p.H % p.ws == 0 && p.W % p.ws == 0, "window_attn_bwd: %dx%d not a multiple of the window", p.H, p.W);
-  SRAD_REQUIRE(p.d % p.heads == 0 && p.hdp % 4 == 0 && p.hdp >= p.d / p.heads, "window_attn_bwd: bad head geometry");
-  SRAD_REQUIRE(p.shift >= 0 && p.shift < (p.ws > 0 ? p.ws : 1), "window_attn_bwd: bad shift %d", p.shift);
-  if (p.ws != 8) return launch_attn_bwd_gen(p, q, stream);
-  SRAD_REQUIRE(p.d % p.heads == 0 && p.hdp % 4 == 0 && p.hdp >= p.d / p.heads, "window_attn_bwd: bad head geometry");
-  SRAD_REQUIRE(p.shift >= 0 && p.shift < p.ws, "window_attn_bwd: bad shift %d", p.shift);
-  const int nW = (p.H / p.ws) * (p.W / p.ws);
-  const double T = (double)p.B * p.H * p.W;
-  const int ncols = 225 * p.heads, nwin = p.B * nW;
-  const size_t need = (size_t)nwin * ncols;
-  SRAD_REQUIRE(q.ws && need <= q.ws_floats, "window_attn_bwd: workspace too small");
-  if (q.used + need > q.ws_floats) SRAD_TRY(srad_wgrad_flush(q, stream));
-  float* tpart = q.ws + q.used;
-  q.used += need;
-  SRAD_TRY(queue_colsum(q, p.dtable, tpart, ncols, ncols, nwin, 1.f, stream));
-  SradProfScope prof(stream, SRAD_K_ATTN_BWD, 10.0 * T * 64 * p.d, 4.0 * T * 8 * p.d);
-  const dim3 grid(p.B * nW * p.heads), block(256);
-  if (prec == SRAD_PREC_BF16 && p.qkv_h) {
-    const int hd = p.d / p.heads;
-    SRAD_REQUIRE(p.dout_h && p.dqkv_h && hd <= 128 && p.hp_h % 8 == 0 && p.hp_h >= hd && p.hp_h <= 128 &&
-                     (((uintptr_t)p.qkv_h | (uintptr_t)p.dout_h) & 15) == 0,
-                 "window_attn_bwd: the all-bf16 form takes head dims <= 128 in 16-byte aligned slots of hp columns, and writes bf16");
-    const int nch = (hd + 31) / 32;
-    if (nch == 1) SRAD_TRY(srad_launch_dyn<window_attn_bwd_h_kernel<1>>(grid, block, ag_lds_bytes<1>(), stream, p, tpart));
-    else if (nch == 2) SRAD_TRY(srad_launch_dyn<window_attn_bwd_h_kernel<2>>(grid, block, ag_lds_bytes<2>(), stream, p, tpart));
-    else if (nch == 3) SRAD_TRY(srad_launch_dyn<window_attn_bwd_h_kernel<3>>(grid, block, ag_lds_bytes<3>(), stream, p, tpart));
-    else SRAD_TRY(srad_launch_dyn<window_attn_bwd_h_kernel<4>>(grid, block, ag_lds_bytes<4>(), stream, p, tpart));
-  } else if (prec == SRAD_PREC_BF16) {
-    SRAD_TRY(srad_launch_dyn<window_attn_bwd_bf16_kernel>(grid, block, AH_LDS, stream, p, tpart));
-  } else {
-    SRAD_TRY(srad_launch_dyn<window_attn_bwd_kernel>(grid, block, AB_LDS, stream, p, tpart));
-  }
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

@@ -113,14 +113,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
 
   // token of window position t (cyclic shift + window partition as index arithmetic, drct.py:482-504)
   auto token_of = [&](int t, int& info) {
-    const int py = t >> 3, px = t & 7;
-    const int r = wy * ws + py, c = wx * ws + px;                 // coordinates in the shifted image
-    int orr = r + p.shift; if (orr >= p.H) orr -= p.H;
-    int occ = c + p.shift; if (occ >= p.W) occ -= p.W;
-    const int rh = r < p.H - ws ? 0 : (r < p.H - p.shift ? 1 : 2);
-    const int rw = c < p.W - ws ? 0 : (c < p.W - p.shift ? 1 : 2);
-    info = ((rh * 3 + rw) << 16) | (py << 8) | px;
-    return (b * p.H + orr) * p.W + occ;
+    int token;
+    srad_window_token_info(p.H, p.W, ws, p.shift, b, wy, wx, t >> 3, t & 7, token, info);
+    return token;
   };
   const int xrow = tid >> 3, col4 = tid & 7;
   int my_info;

@@ -86,6 +86,19 @@ __device__ __forceinline__ double srad_block_sum(double v, double* red) {
   }
   return red[0];
 }
+// Shifted-window geometry (cyclic shift + window partition as index arithmetic): position (py, px) of window (wy, wx) of image b
+// -> its token in the unshifted [B][H][W] order, and an info word (shift-mask region << 16) | (py << 8) | px.  The region is
+// one of the 3 x 3 the mask cuts the shifted image into; two tokens of a window attend to each other iff theirs are equal.
+__device__ __forceinline__ void srad_window_token_info(int H, int W, int ws, int shift, int b, int wy, int wx, int py, int px,
+                                                       int& token, int& info) {
+  const int r = wy * ws + py, c = wx * ws + px;                   // coordinates in the shifted image
+  int orr = r + shift; if (orr >= H) orr -= H;
+  int occ = c + shift; if (occ >= W) occ -= W;
+  const int rh = r < H - ws ? 0 : (r < H - shift ? 1 : 2);
+  const int rw = c < W - ws ? 0 : (c < W - shift ? 1 : 2);
+  info = ((rh * 3 + rw) << 16) | (py << 8) | px;
+  token = (b * H + orr) * W + occ;
+}
 #endif
 
 #define SRAD_CHECK_HIP(expr)                                                              \
@@ -384,6 +397,11 @@ int srad_wgrad_launch_deferred(int prec, WgradQueue& q, hipStream_t stream);
 int srad_launch_wgrad(int prec, const WgradParams& p, WgradQueue& q, hipStream_t stream);
 bool srad_wgrad_conv9_supported(const WgradParams& p);   // the nine-tap kernel takes this layer (bf16 mode; the only one with bf16 conv operands)
 int srad_wgrad_flush(WgradQueue& q, hipStream_t stream);
+// Takes `nrows` partial rows of `row_stride` floats from the workspace (*part) for a kernel to fill, and queues alpha times the
+// column sums of their first `ncols` columns into dst (null: none).  `nitems` = column-sum items that will be queued on these
+// rows in all: a flush that the batch or the workspace needs comes before the rows are taken.  `who` names the caller in errors.
+int srad_wgrad_reserve_colsum(WgradQueue& q, const char* who, float* dst, int ncols, int row_stride, int nrows, float alpha,
+                              int nitems, hipStream_t stream, float** part);
 
 #define SRAD_WGRAD_WS_BYTES ((size_t)256 << 20)   /* what the engines give the queue */
 
@@ -472,7 +490,7 @@ struct AttnBwdParams {
   const float* table;  // [(2ws-1)^2][heads]
   float* dtable;       // accumulated (atomicAdd)
   int B, H, W, ws, shift, d, heads, hdp;
-  // all-bf16 form (window_attn_bwd_h_kernel; head dim <= 32): q (scaled) | k | v as the fused forward saved them,
+  // all-bf16 form (window_attn_bwd_h_kernel; head dims up to 128 in one to four 32-column chunks): q (scaled) | k | v as the fused forward saved them,
   // [T][3][heads][hp_h], and dO as [T][heads][hp_h] (padding columns may hold anything); needs dqkv_h
   const __bf16* qkv_h = nullptr; const __bf16* dout_h = nullptr; int hp_h = 0;
   int no_xcd_map = 0;        // 1: windows dealt round-robin over the XCDs (A/B of the strip mapping)

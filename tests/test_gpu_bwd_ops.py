@@ -196,9 +196,14 @@ def test_layernorm_bwd(dev, rows, C):
 def test_window_attention_bwd(dev, d, heads, shift, prec):
     if prec == "bf16io" and d // heads > 128:
         pytest.skip("the all-bf16 kernel takes head dims <= 128")
+    _check_window_attention_bwd_8x8(dev, 2, 16, 24, d, heads, shift, prec)
+
+
+def _check_window_attention_bwd_8x8(dev, B, H, W, d, heads, shift, prec):
+    """One 8 x 8 attention backward (fp32 / bf16 MFMA kernel, or bf16io: the training step's all-bf16 kernel) against autograd."""
     from oracle import sr_ref as R
     from srad_amd import ops
-    B, H, W, ws = 2, 16, 24, 8
+    ws = 8
     g = torch.Generator().manual_seed(d + shift)
     T = B * H * W
     qkv = (torch.randn(T, 3 * d, generator=g) * 0.7).requires_grad_(True)
@@ -237,6 +242,19 @@ def test_window_attention_bwd(dev, d, heads, shift, prec):
     tol = 2e-4 if prec == "fp32" else 2e-2
     assert _rel(dqkv, qkv.grad) < tol
     assert _rel(dtable, table.grad) < tol
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "bf16io"])
+@pytest.mark.parametrize("B,H,W,d,heads,shift", [
+    # 16 windows, a multiple of 8: the round-robin (fp32, bf16) and strip (bf16io) workgroup -> window mappings; head dim 122 = four chunks
+    (2, 16, 32, 180, 6, 0), (2, 16, 32, 180, 6, 4), (2, 16, 32, 244, 2, 0), (2, 16, 32, 244, 2, 4),
+    (1, 16, 32, 32, 2, 4),      # 8 windows exactly: one window per XCD strip
+    (1, 8, 24, 48, 2, 4),       # H = the window size: every row lies in the shift mask's rows 1 - 2, non-square image
+])
+def test_window_attention_bwd_window_mappings_and_mask_corner(dev, B, H, W, d, heads, shift, prec):
+    """The shapes the op-level comparison above never reaches: its 12 windows always take the plain workgroup -> (window, head)
+    mapping.  Here the window count is a multiple of 8 (and 8 exactly), and one image is a single row of windows."""
+    _check_window_attention_bwd_8x8(dev, B, H, W, d, heads, shift, prec)
 
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
