@@ -129,7 +129,8 @@ int train_check(const srad_drct* h, int B, int H, int W) {
   SRAD_REQUIRE(h->ts.ready, "drct training: call srad_drct_train_bind() and srad_drct_sync_params() first");
   SRAD_REQUIRE(B > 0 && H > 0 && W > 0, "drct training: empty input");
   const int ws = h->cfg.window_size;
-  SRAD_REQUIRE(ws >= 1 && ws <= 16, "drct training: window sizes 1 .. 16 (got %d; the reference's presets build 2, 4, 8 and 16)", ws);
+  SRAD_REQUIRE((ws >= 1 && ws <= 16) || ws == 32 || ws == 64,
+               "drct training: window sizes 1 .. 16, 32 and 64 (got %d; the reference's presets build 2, 4, 8, 16, 32 and 64)", ws);
   SRAD_REQUIRE(H % ws == 0 && W % ws == 0, "drct training: input %dx%d is not a multiple of the window size %d", H, W, ws);
   SRAD_REQUIRE((double)B * H * W * h->cfg.upscale * h->cfg.upscale * h->cfg.num_feat * 4.0 < 3.9e9 &&
                (double)B * H * W * 3 * h->dmax * 4.0 < 3.9e9, "drct training: batch too large for 32-bit offsets");

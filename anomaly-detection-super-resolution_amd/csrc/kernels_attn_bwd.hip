@@ -1,9 +1,10 @@
 // kernels_attn_bwd.hip - backward of the shifted-window attention on gfx950: dq, dk, dv and the bias-table gradient,
-// recomputing P per (window, head) from the saved q | k | v.  Four kernels share the scalar code around their MFMA loops
+// recomputing P per (window, head) from the saved q | k | v.  Five kernels share the scalar code around their MFMA loops
 // as far as hipcc gives them the registers they had with their own copies:
 //
 //   window_attn_bwd_kernel         8 x 8 windows, fp32 MFMA
 //   window_attn_bwd_gen_kernel     window sizes 1 .. 16 other than 8, fp32 MFMA
+//   window_attn_bwd_tiled_kernel   32 x 32 and 64 x 64 windows (1024 / 4096 tokens), fp32 MFMA, two passes over 64 x 64 score tiles
 //   window_attn_bwd_bf16_kernel    8 x 8, bf16 MFMA, fp32 in and out
 //   window_attn_bwd_h_kernel       8 x 8, bf16 in and out: the DRCT training step's kernel
 #include "srad_common.h"
@@ -13,7 +14,7 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------
-// What the four kernels share (the token / shift-mask geometry is srad_window_token_info of srad_common.h: the fused
+// What the kernels share (the token / shift-mask geometry is srad_window_token_info of srad_common.h: the fused
 // forward takes the same one).
 // ------------------------------------------------------------------------------------------
 // Workgroup L -> (window, head) of the 8 x 8 kernels.  Workgroups are dealt round-robin over the 8 XCDs; when the window
@@ -477,6 +478,274 @@ __global__ __launch_bounds__(256) void window_attn_bwd_gen_kernel(const AttnBwdP
 constexpr size_t ABG_LDS(int nb) { return (size_t)(4 * 64 * AB_HS + 2 * 64 * AB_PS + 2 * 1024) * sizeof(float) + 2 * 64 * nb * sizeof(int); }
 
 // ------------------------------------------------------------------------------------------
+// The same backward for 32 x 32 and 64 x 64 windows (N = 1024 / 4096 tokens: the 512 and 1024 px presets), where a 64 x N
+// score row block no longer fits in accumulators.  One workgroup per (window, head) owns every output of that pair, and
+// nothing N x N ever exists: the scores are walked as 64 x 64 tiles (query block qb, key block kb), twice per query block.
+//   pass 1, kb = 0 .. N/64 - 1:  S = (q scale) k^T + bias + mask and dP = dO v^T of the tile; the row maximum m, the row sum
+//           l of exp(S - m) and a = sum exp(S - m) dP are carried online (rescaled when m grows).  D = rowsum(P dP) = a / l.
+//   pass 2, kb = 0 .. N/64 - 1:  the tile's S and dP again, P = exp(S - m) / l, dS = P (dP - D); the P / dS tiles go through
+//           LDS as in the general kernel: dq += dS k in registers over kb (written once per query block), dk = dS^T (q scale)
+//           and dv = P^T dO added to the workgroup's own rows in HBM (the thread that wrote an element is the one that adds
+//           to it, query blocks in ascending order), and dS folded into the head's table gradient, which stays in LDS
+//           ((2 ws - 1)^2 floats: 64.5 KB at ws 64) until the end.
+// A block of 64 tokens is 64 / ws window rows (two at ws 32, one at 64), so a tile only meets (4 ws / 64 - 1)(2 ws - 1) <= 189
+// entries of the table: that slice is fetched per tile (the whole table and its gradient do not both fit in LDS), and the
+// fold has one thread per entry of the slice - no atomics, fixed order, bit-identical from run to run.
+// ------------------------------------------------------------------------------------------
+constexpr int ABT_SLICE = 192;      // >= 3 * 63 (ws 32) and >= 127 (ws 64)
+constexpr size_t ABT_LDS(int ws) {
+  return (size_t)(4 * 64 * AB_HS + 2 * 64 * AB_PS + ABT_SLICE + (2 * ws - 1) * (2 * ws - 1) + 3) * sizeof(float) + 4 * 64 * sizeof(int);
+}
+static_assert(ABT_LDS(64) <= 160 * 1024, "window_attn_bwd (tiled): LDS budget");
+
+// attn_bias_mask against a slice of the table that starts at row dy0 + ws - 1 (dy0 = smallest qy - ky of the tile)
+__device__ __forceinline__ float attn_bias_mask_slice(float v, const int qinfo, const int kinfo, const float* tsl, const int dy0,
+                                                      const int ws, const int tw, const int shift) {
+  const int qy = (qinfo >> 8) & 0xff, qx = qinfo & 0xff, qr = qinfo >> 16;
+  const int kyy = (kinfo >> 8) & 0xff, kxx = kinfo & 0xff, kr = kinfo >> 16;
+  v += tsl[(qy - kyy - dy0) * tw + (qx - kxx + ws - 1)];
+  if (shift > 0 && qr != kr) v += -100.0f;
+  return v;
+}
+
+__global__ __launch_bounds__(256) void window_attn_bwd_tiled_kernel(const AttnBwdParams p, float* __restrict__ tpart) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* Qs = reinterpret_cast<float*>(smem);
+  float* Ks = Qs + 64 * AB_HS;
+  float* Vs = Ks + 64 * AB_HS;
+  float* Gs = Vs + 64 * AB_HS;
+  float* Pm = Gs + 64 * AB_HS;
+  float* Dm = Pm + 64 * AB_PS;
+  float* tsl = Dm + 64 * AB_PS;      // the tile's slice of the bias table [2 rpb - 1][2 ws - 1]
+  int* tokq = reinterpret_cast<int*>(tsl + ABT_SLICE);   // [64] each: tokens / info words of the query and the key block
+  int* infq = tokq + 64;
+  int* tokk = infq + 64;
+  int* infk = tokk + 64;
+  float* dtb = reinterpret_cast<float*>(infk + 64);      // [(2 ws - 1)^2] the head's table gradient
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int ws = p.ws, N = ws * ws, d = p.d, heads = p.heads, hd = d / heads, hdp = p.hdp;
+  const int nblk = N / 64, rpb = 64 / ws;                            // window rows per block of 64 tokens
+  const int ldq = 3 * heads * hdp;
+  const int nWx = p.W / ws, nW = (p.H / ws) * nWx;
+  const int win = blockIdx.x / heads, h = blockIdx.x - win * heads;
+  const int b = win / nW, widx = win - b * nW;
+  const int wy = widx / nWx, wx = widx - wy * nWx;
+  const float scale = rsqrtf((float)hd);
+  const int tw = 2 * ws - 1, ntbl = tw * tw, nsl = (2 * rpb - 1) * tw;
+  const int nch = (hd + AB_HC - 1) / AB_HC;                          // <= 4 (head dims up to 128)
+
+  for (int t = tid; t < ntbl; t += 256) dtb[t] = 0.f;
+
+  auto set_block = [&](int* tok, int* inf, int blk) {
+    if (tid < 64) { const int n = blk * 64 + tid; srad_window_token_info(p.H, p.W, ws, p.shift, b, wy, wx, n / ws, n % ws, tok[tid], inf[tid]); }
+  };
+  // table rows (qb - kb) rpb - (rpb - 1) + ws - 1 ... of the tile (qb, kb): every (qy - ky, qx - kx) its 64 x 64 pairs meet
+  auto load_slice = [&](int dy0) {
+    if (tid < nsl) {
+      const int r = dy0 + ws - 1 + tid / tw;
+      tsl[tid] = r >= 0 && r < tw ? p.table[((size_t)r * tw + (tid - (tid / tw) * tw)) * heads + h] : 0.f;
+    }
+  };
+  // stage a 32-column chunk of the 64 rows `tok` of q*scale / k / v / dO into its LDS tile
+  auto stage_rows = [&](float* dst, const int* tok, int ch, int which /* 0 q, 1 k, 2 v */) {
+    const int col0 = ch * AB_HC;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int idx = tid + 256 * i;
+      const int row = idx >> 3, c = col0 + (idx & 7) * 4;
+      const float* base = p.qkv + (size_t)tok[row] * ldq + (which * heads + h) * hdp + min(c, hdp - 4);
+      f32x4 v4 = *reinterpret_cast<const f32x4*>(base);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v4[e] = c + e < hd ? (which == 0 ? v4[e] * scale : v4[e]) : 0.f;
+      *reinterpret_cast<f32x4*>(dst + row * AB_HS + (idx & 7) * 4) = v4;
+    }
+  };
+  auto stage_g = [&](int ch) {
+    const int col0 = ch * AB_HC;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int idx = tid + 256 * i;
+      const int row = idx >> 5, cl = idx & 31, c = col0 + cl;
+      const float g = p.dout[(size_t)tokq[row] * d + h * hd + min(c, hd - 1)];
+      Gs[row * AB_HS + cl] = c < hd ? g : 0.f;
+    }
+  };
+  // S = (q scale) k^T and dP = dO v^T of the current tile (row = 16 wave + 4 fq + e, key = 16 j + fr).  Called after a barrier
+  // behind set_block; with one chunk the query block's q and dO stay in LDS from its first tile on (stage_q false).
+  f32x4 s[4], dp[4];
+  auto tile_scores = [&](bool stage_q) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int ch = 0; ch < nch; ++ch) {
+      if (ch > 0) __syncthreads();
+      if (stage_q || nch > 1) { stage_rows(Qs, tokq, ch, 0); stage_g(ch); }
+      stage_rows(Ks, tokk, ch, 1);
+      stage_rows(Vs, tokk, ch, 2);
+      __syncthreads();
+#pragma unroll
+      for (int kk = 0; kk < AB_HC; kk += 16) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(Qs + (wave * 16 + fr) * AB_HS + kk + 4 * fq);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(Gs + (wave * 16 + fr) * AB_HS + kk + 4 * fq);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const f32x4 kbv = *reinterpret_cast<const f32x4*>(Ks + (j * 16 + fr) * AB_HS + kk + 4 * fq);
+          const f32x4 vb = *reinterpret_cast<const f32x4*>(Vs + (j * 16 + fr) * AB_HS + kk + 4 * fq);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            s[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], kbv[e], s[j], 0, 0, 0);
+            dp[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(g[e], vb[e], dp[j], 0, 0, 0);
+          }
+        }
+      }
+    }
+  };
+
+  for (int qb = 0; qb < nblk; ++qb) {
+    __syncthreads();
+    set_block(tokq, infq, qb);
+    // ---- pass 1: row maximum, row sum and D = rowsum(P dP), online over the key blocks ----
+    float rm[4], rl[4], ra[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { rm[e] = -1e30f; rl[e] = 0.f; ra[e] = 0.f; }
+    for (int kb = 0; kb < nblk; ++kb) {
+      const int dy0 = (qb - kb) * rpb - (rpb - 1);
+      if (kb > 0) __syncthreads();
+      set_block(tokk, infk, kb);
+      load_slice(dy0);
+      __syncthreads();
+      tile_scores(kb == 0);
+      int kinf[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) kinf[j] = infk[j * 16 + fr];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int qi = infq[wave * 16 + fq * 4 + e];
+        float mx = -1e30f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float v = attn_bias_mask_slice(s[j][e], qi, kinf[j], tsl, dy0, ws, tw, p.shift);
+          s[j][e] = v;
+          mx = fmaxf(mx, v);
+        }
+        mx = fmaxf(rm[e], srad_row16_max(mx));
+        float sum = 0.f, da = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const float pv = expf(s[j][e] - mx); sum += pv; da += pv * dp[j][e]; }
+        const float corr = expf(rm[e] - mx);
+        rl[e] = rl[e] * corr + srad_row16_sum(sum);
+        ra[e] = ra[e] * corr + srad_row16_sum(da);
+        rm[e] = mx;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { rl[e] = 1.0f / rl[e]; ra[e] *= rl[e]; }       // 1 / l and D
+    // ---- pass 2: P and dS tile after tile -> table gradient, dq (registers), dk / dv (read-add-write of own rows) ----
+    f32x4 dq[4][2];
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) { dq[ch][0] = f32x4{0.f, 0.f, 0.f, 0.f}; dq[ch][1] = dq[ch][0]; }
+    for (int kb = 0; kb < nblk; ++kb) {
+      const int dy0 = (qb - kb) * rpb - (rpb - 1);
+      __syncthreads();
+      set_block(tokk, infk, kb);
+      load_slice(dy0);
+      __syncthreads();
+      tile_scores(false);
+      {
+        int kinf[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) kinf[j] = infk[j * 16 + fr];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int row = wave * 16 + fq * 4 + e;
+          const int qi = infq[row];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float v = attn_bias_mask_slice(s[j][e], qi, kinf[j], tsl, dy0, ws, tw, p.shift);
+            const float pv = expf(v - rm[e]) * rl[e];
+            Pm[row * AB_PS + j * 16 + fr] = pv;
+            Dm[row * AB_PS + j * 16 + fr] = pv * (dp[j][e] - ra[e]);
+          }
+        }
+      }
+      __syncthreads();
+      // slice entry t = (dyl + rpb - 1) (2 ws - 1) + (dx + ws - 1): the dS of every (query, key = query - (dy, dx)) pair of this tile
+      if (tid < nsl) {
+        const int dyl = tid / tw - (rpb - 1), dxi = tid - (tid / tw) * tw, dx = dxi - (ws - 1);
+        float acc = 0.f;
+        for (int qyl = max(0, dyl); qyl < min(rpb, rpb + dyl); ++qyl)
+          for (int qx = max(0, dx); qx < min(ws, ws + dx); ++qx)
+            acc += Dm[(qyl * ws + qx) * AB_PS + (qyl - dyl) * ws + qx - dx];
+        dtb[((qb - kb) * rpb + dyl + ws - 1) * tw + dxi] += acc;     // (one thread per entry of a tile, tiles behind barriers: no race)
+      }
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) {
+        if (ch >= nch) continue;
+        if (nch > 1) {
+          __syncthreads();
+          stage_rows(Ks, tokk, ch, 1);
+          stage_rows(Qs, tokq, ch, 0);
+          stage_g(ch);
+          __syncthreads();
+        }
+        f32x4 dk[2], dv[2];
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt) { dk[jt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[jt] = dk[jt]; }
+#pragma unroll
+        for (int kk = 0; kk < 64; kk += 16) {
+          const f32x4 a = *reinterpret_cast<const f32x4*>(Dm + (wave * 16 + fr) * AB_PS + kk + 4 * fq);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int kr = kk + 4 * fq + e;
+            const float at = Dm[kr * AB_PS + wave * 16 + fr];     // dS^T
+            const float pt = Pm[kr * AB_PS + wave * 16 + fr];     // P^T
+#pragma unroll
+            for (int jt = 0; jt < 2; ++jt) {
+              const float kbv = Ks[kr * AB_HS + jt * 16 + fr];
+              const float qbv = Qs[kr * AB_HS + jt * 16 + fr];
+              const float gb = Gs[kr * AB_HS + jt * 16 + fr];
+              dq[ch][jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], kbv, dq[ch][jt], 0, 0, 0);
+              dk[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(at, qbv, dk[jt], 0, 0, 0);
+              dv[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pt, gb, dv[jt], 0, 0, 0);
+            }
+          }
+        }
+        // dk / dv rows of key block kb (row = 16 wave + 4 fq + e): the first query block writes, later ones add (same thread)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float* dst = p.dqkv + (size_t)tokk[wave * 16 + fq * 4 + e] * (3 * d) + h * hd;
+#pragma unroll
+          for (int jt = 0; jt < 2; ++jt) {
+            const int c = ch * AB_HC + jt * 16 + fr;
+            if (c < hd) {
+              if (qb == 0) { dst[d + c] = dk[jt][e]; dst[2 * d + c] = dv[jt][e]; }
+              else { dst[d + c] += dk[jt][e]; dst[2 * d + c] += dv[jt][e]; }
+            }
+          }
+        }
+      }
+    }
+    // dq rows of this query block
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+      if (ch >= nch) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float* dst = p.dqkv + (size_t)tokq[wave * 16 + fq * 4 + e] * (3 * d) + h * hd;
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt) {
+          const int c = ch * AB_HC + jt * 16 + fr;
+          if (c < hd) dst[c] = dq[ch][jt][e] * scale;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int t = tid; t < ntbl; t += 256) tpart[(size_t)win * ((size_t)ntbl * heads) + (size_t)t * heads + h] = dtb[t];
+}
+
+// ------------------------------------------------------------------------------------------
 // The same backward with bf16 MFMA operands (v_mfma_f32_16x16x32_bf16, fp32 accumulation) for the bf16 precision
 // mode: q, k, v, dO chunks are staged as bf16; P and dS leave the softmax as bf16 tiles - dS in both orientations
 // (row-major for dq = dS k, transposed for dk = dS^T q), P transposed (dv = P^T dO) - and the second operand of
@@ -888,12 +1157,18 @@ __global__ __launch_bounds__(256) void window_attn_bwd_h_kernel(const AttnBwdPar
 
 }  // namespace
 
-// windows other than 8 x 8 (N = ws^2 <= 256): window_attn_bwd_gen_kernel, fp32 operands and results in every precision mode
+// windows other than 8 x 8: window_attn_bwd_gen_kernel (N = ws^2 <= 256) or window_attn_bwd_tiled_kernel (ws 32 and 64), fp32
+// operands and results in every precision mode
 static int launch_attn_bwd_gen(const AttnBwdParams& p, WgradQueue& q, hipStream_t stream) {
-  SRAD_REQUIRE(p.ws >= 1 && p.ws <= 16, "window_attn_bwd: window sizes 1 .. 16 train (got %d)", p.ws);
+  const bool tiled = p.ws == 32 || p.ws == 64;
+  SRAD_REQUIRE((p.ws >= 1 && p.ws <= 16) || tiled, "window_attn_bwd: window sizes 1 .. 16, 32 and 64 train (got %d)", p.ws);
   SRAD_REQUIRE(p.qkv && p.dout && p.dqkv && !p.qkv_h && !p.dqkv_h, "window_attn_bwd: window sizes other than 8 take fp32 q | k | v, dO and dqkv");
   SRAD_REQUIRE(p.d / p.heads <= 128, "window_attn_bwd: head dims up to 128 (got %d)", p.d / p.heads);
+  // tokens are ints in the kernels (every product with a row length is formed in 64 bits), (window, head) pairs the grid
+  SRAD_REQUIRE((double)p.B * p.H * p.W < 2147483648.0 && (double)p.B * p.H * p.W / (p.ws * p.ws) * p.heads < 2147483648.0,
+               "window_attn_bwd: batch %d of %dx%d tokens is too large for 32-bit token numbers", p.B, p.H, p.W);
   const int nW = (p.H / p.ws) * (p.W / p.ws), tw = 2 * p.ws - 1;
+  SRAD_REQUIRE((double)tw * tw * p.heads < 2147483648.0, "window_attn_bwd: %d heads of a %d x %d table overflow a row of partials", p.heads, tw, tw);
   const int ncols = tw * tw * p.heads, nwin = p.B * nW;
   float* tpart = nullptr;
   SRAD_TRY(srad_wgrad_reserve_colsum(q, "window_attn_bwd", p.dtable, ncols, ncols, nwin, 1.f, 1, stream, &tpart));
@@ -901,7 +1176,8 @@ static int launch_attn_bwd_gen(const AttnBwdParams& p, WgradQueue& q, hipStream_
   SradProfScope prof(stream, SRAD_K_ATTN_BWD, 10.0 * T * p.ws * p.ws * p.d, 4.0 * T * 8 * p.d);
   const int nb = (p.ws * p.ws + 63) / 64;
   const dim3 grid(nwin * p.heads), block(256);
-  if (nb == 1) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<1>>(grid, block, ABG_LDS(1), stream, p, tpart));
+  if (tiled) SRAD_TRY(srad_launch_dyn<window_attn_bwd_tiled_kernel>(grid, block, ABT_LDS(p.ws), stream, p, tpart));
+  else if (nb == 1) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<1>>(grid, block, ABG_LDS(1), stream, p, tpart));
   else if (nb == 2) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<2>>(grid, block, ABG_LDS(2), stream, p, tpart));
   else if (nb == 3) SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<3>>(grid, block, ABG_LDS(3), stream, p, tpart));
   else SRAD_TRY(srad_launch_dyn<window_attn_bwd_gen_kernel<4>>(grid, block, ABG_LDS(4), stream, p, tpart));

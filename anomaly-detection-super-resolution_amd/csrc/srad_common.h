@@ -481,7 +481,7 @@ int srad_launch_lin_ln_bwd(const LinLnBwdParams& p, WgradQueue& q, hipStream_t s
 int srad_launch_mlp_bwd(const MlpBwdParams& p, WgradQueue& q, hipStream_t stream);
 bool srad_mlp_bwd_bf16_out(int M);     // are the bf16-output instances of mlp_bwd built for this row count
 
-// Shifted-window attention backward (window size 8): recomputes P from the saved head-padded q|k|v.
+// Shifted-window attention backward (window sizes 1 .. 16, 32 and 64): recomputes P from the saved head-padded q|k|v.
 struct AttnBwdParams {
   const float* qkv;    // [T][3][heads][hdp] as written by the forward
   const float* dout;   // [T][d] gradient of the attention output (pre-proj)

@@ -381,8 +381,10 @@ int srad_op_dgrad(int precision, const float* dy, int ldy, int B, int H, int W, 
 /* LayerNorm backward: out (+)= dLN(dxn; x, gamma) + dres; dgamma / dbeta accumulated; workspace as for srad_op_wgrad */
 int srad_op_layernorm_bwd(const float* dxn, const float* x, int ldx, const float* gamma, const float* dres, float* out,
                           int accumulate, float* dgamma, float* dbeta, int rows, int C, void* workspace, void* stream);
-/* Window attention backward (window size 8): qkv head-padded as for srad_op_window_attn, dout [T][d],
- * dqkv [T][3d] compact, dtable accumulated; workspace as for srad_op_wgrad */
+/* Window attention backward (window sizes 1 .. 16, 32 and 64; any other is an error): qkv head-padded as for
+ * srad_op_window_attn, dout [T][d], dqkv [T][3d] compact, dtable accumulated; workspace as for srad_op_wgrad.  Windows of 32
+ * and 64 take the tiled kernel (fp32 MFMAs in every precision; one partial row of (2 ws - 1)^2 heads floats per window in
+ * the workspace, so B (H / ws) (W / ws) such rows must fit in it) */
 int srad_op_window_attn_bwd(int precision, const float* qkv, const float* dout, float* dqkv, const float* table,
                             float* dtable, int B, int H, int W, int ws, int shift, int d, int heads, int hdp,
                             void* workspace, void* stream);
