@@ -33,6 +33,14 @@ class DrnConfig(C.Structure):
                 ("precision", C.c_int32), ("use_graph", C.c_int32)]
 
 
+class WqStep(C.Structure):
+    """One step of srad_op_wgrad_queue_script (include/srad.h srad_wq_step)."""
+    _fields_ = [("kind", C.c_int32), ("i", C.c_int32 * 9), ("alpha", C.c_float), ("p", C.c_void_p * 7)]
+
+
+WQ_WGRAD, WQ_WGRAD_DEFERRED, WQ_LAUNCH_DEFERRED, WQ_LN_BWD, WQ_ATTN_BWD, WQ_FLUSH = 1, 2, 3, 4, 5, 6
+WQ_FLUSH_EXPLICIT, WQ_FLUSH_BATCH, WQ_FLUSH_WS = 0, 1, 2
+
 _lock = threading.Lock()
 _lib = None
 
@@ -56,6 +64,8 @@ _SIG = {
     "srad_drct_train_param_offset": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     "srad_drct_train_arena_bytes": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "srad_drct_train_bind": (C.c_int, [_P, _P, C.c_size_t]),
+    "srad_drct_train_set_wgrad_budget": (C.c_int, [_P, C.c_size_t]),
+    "srad_drct_train_wgrad_stats": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "srad_drct_sync_params": (C.c_int, [_P, _P, _P]),
     "srad_drct_train_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "srad_drct_forward_train": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
@@ -164,6 +174,8 @@ _SIG = {
     "srad_op_wgrad": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "srad_op_wgrad_workspace_bytes": (C.c_size_t, []),
+    "srad_op_wgrad_queue_script": (C.c_int, [C.c_int, C.POINTER(WqStep), C.c_int, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int), C.c_int, _P]),
     "srad_op_dgrad": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P,
                                 C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, C.c_int, _P, C.c_size_t, _P]),
     "srad_op_mlp_bwd_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

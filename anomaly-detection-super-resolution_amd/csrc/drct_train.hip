@@ -167,6 +167,21 @@ int srad_drct_train_bind(srad_drct_t* h, void* train_arena, size_t bytes) {
   return train_bind(h->pt, h->ts, train_arena, bytes);
 }
 
+int srad_drct_train_set_wgrad_budget(srad_drct_t* h, size_t bytes) {
+  SRAD_REQUIRE(h, "train_set_wgrad_budget: null argument");
+  SRAD_REQUIRE(bytes > 0 && bytes % 512 == 0 && bytes <= SRAD_WGRAD_WS_BYTES,
+               "train_set_wgrad_budget: %zu bytes: a multiple of 512 up to the %zu bytes the training arena holds", bytes, (size_t)SRAD_WGRAD_WS_BYTES);
+  h->ts.wgrad_budget = bytes;
+  return SRAD_OK;
+}
+
+int srad_drct_train_wgrad_stats(const srad_drct_t* h, int launches[3], size_t* block_peak_floats) {
+  SRAD_REQUIRE(h && launches && block_peak_floats, "train_wgrad_stats: null argument");
+  for (int i = 0; i < 3; ++i) launches[i] = h->ts.wgrad_log.by_why[i];
+  *block_peak_floats = h->ts.wgrad_block_peak;
+  return SRAD_OK;
+}
+
 // Refreshes every packed weight (forward and transposed) and raw parameter from the flat fp32 master buffer:
 // one launch, to be called after each optimizer step (and once after loading a checkpoint).
 int srad_drct_sync_params(srad_drct_t* h, const float* flat_params, void* stream) {
@@ -327,6 +342,10 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
   const size_t wq_half = wq.ws_floats / 2;
   float* const wq_base = wq.ws;
   int blk_count = 0;
+  // a flush that a reservation makes in the middle of a block reduces column sums the caller's stream wrote: it goes there even
+  // when the reservation is a deferred layer's (whose own launch, on the side stream, comes after side_waits_main)
+  wq.own_flush_stream = true; wq.flush_stream = s;
+  h->ts.wgrad_block_peak = 0;
 
   // dLoss/d(outn) = dy / img_range, NCHW -> NHWC (pad channels zero)           (drct.py:897)
   SRAD_TRY(srad_launch_nchw_to_nhwc(dy, w.dimg, B, c.in_chans, SRAD_IMG_CPAD, hh, ww, zero3, 1.0f / c.img_range, s));
@@ -406,7 +425,7 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
       }
       const int set = blk_count & 1;                       // temporaries + partial workspace of this block
       SRAD_TRY(bs.main_waits_set(set));                   // block n - 2 fully consumed
-      wq.ws = wq_base + (size_t)set * wq_half; wq.ws_floats = wq_half;
+      wq.ws = wq_base + (size_t)set * wq_half; wq.ws_floats = wq_half; wq.peak = 0;
       float *dx2 = w.dx2[set], *dx1 = w.dx1[set], *dh = w.dh[set], *dqkv = w.dqkv[set];
       // with the adjust prologue fused the dx2 buffer only holds the bf16 copy (its first half): dx1 * rs1 as bf16 goes behind it
       const bool yh_dx1 = yh_dx2 && fuse_proj;
@@ -537,6 +556,7 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
       SRAD_TRY(bs.side_waits_main());
       SRAD_TRY(srad_wgrad_launch_deferred(prec, wq, side));
       SRAD_TRY(srad_wgrad_flush(wq, side));
+      h->ts.wgrad_block_peak = std::max(h->ts.wgrad_block_peak, wq.peak);
       SRAD_TRY(bs.set_done(set));
       ++blk_count;
     }
@@ -565,6 +585,7 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
     }
   }
   SRAD_TRY(srad_wgrad_flush(wq, s));
+  h->ts.wgrad_log = wq.log;
   if (on_bucket) on_bucket(user, c.n_rdg + 1);
   return SRAD_OK;
 }

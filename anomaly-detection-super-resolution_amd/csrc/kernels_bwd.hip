@@ -886,7 +886,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgradReduceBatc
   }
 }
 
-struct WgradPlan { int tn, tc, ksplit; long tiles; float* part; };
+struct WgradPlan { int tn, tc, ksplit; long tiles; float* part; size_t need; };
 
 // tile / split geometry of one layer, its partial-tile workspace and its entry in the reduce batch
 template <int PREC>
@@ -907,16 +907,10 @@ int plan_wgrad(const WgradParams& p, WgradQueue& q, hipStream_t s, WgradPlan& pl
     ksplit = (p.M + rows_per - 1) / rows_per;
   }
   pl.ksplit = (int)ksplit;
-  pl.part = nullptr;
+  pl.part = nullptr; pl.need = 0;
   if (ksplit > 1) {
-    const size_t need = (size_t)pl.tiles * ksplit * WG_TS;
-    SRAD_REQUIRE(q.ws && need <= q.ws_floats, "wgrad: split-K workspace too small (%zu floats needed, %zu given)", need, q.ws_floats);
-    if (q.batch.count == SRAD_WGRAD_BATCH || q.used + need > q.ws_floats) {
-      SRAD_REQUIRE(q.multi.count == 0, "wgrad: split-K workspace too small for the deferred layers");
-      SRAD_TRY(srad_wgrad_flush(q, s));
-    }
-    pl.part = q.ws + q.used;
-    q.used += need;
+    pl.need = (size_t)pl.tiles * ksplit * WG_TS;
+    SRAD_TRY(srad_wgrad_take(q, "wgrad", pl.need, 1, s, &pl.part));
     WgradReduceItem& it = q.batch.it[q.batch.count++];
     it.dW = p.dW; it.db = p.db; it.part = pl.part; it.n_real = p.n_real; it.cin_real = p.cin_real; it.ntaps = p.ntaps;
     it.grp_real = p.grp_real; it.grp_pad = p.grp_pad;
@@ -953,13 +947,7 @@ int launch_wgrad80(const WgradParams& p, WgradQueue& q, hipStream_t s) {
   float* part = nullptr;
   if (ksplit > 1) {
     const size_t need = (size_t)p.ntaps * ksplit * W80_PART;
-    SRAD_REQUIRE(q.ws && need <= q.ws_floats, "wgrad: split-K workspace too small (%zu floats needed, %zu given)", need, q.ws_floats);
-    if (q.batch.count == SRAD_WGRAD_BATCH || q.used + need > q.ws_floats) {
-      SRAD_REQUIRE(q.multi.count == 0, "wgrad: split-K workspace too small for the deferred layers");
-      SRAD_TRY(srad_wgrad_flush(q, s));
-    }
-    part = q.ws + q.used;
-    q.used += need;
+    SRAD_TRY(srad_wgrad_take(q, "wgrad80", need, 1, s, &part));
     WgradReduceItem& it = q.batch.it[q.batch.count++];
     it.dW = p.dW; it.db = p.db; it.part = part; it.n_real = 80; it.cin_real = 80; it.ntaps = p.ntaps; it.grp_real = it.grp_pad = 0;
     it.ksplit = (int)ksplit; it.tile0 = q.tiles; it.alpha = p.alpha;
@@ -994,13 +982,8 @@ int launch_wgrad_conv9(const WgradParams& p, WgradQueue& q, hipStream_t s) {
   ksplit = (nchunks + cpw - 1) / cpw;
   const size_t PART = (size_t)C * C + C;
   const size_t need = 9 * (size_t)ksplit * PART;
-  SRAD_REQUIRE(q.ws && need <= q.ws_floats, "wgrad: split-K workspace too small (%zu floats needed, %zu given)", need, q.ws_floats);
-  if (q.batch.count == SRAD_WGRAD_BATCH || q.used + need > q.ws_floats) {
-    SRAD_REQUIRE(q.multi.count == 0, "wgrad: split-K workspace too small for the deferred layers");
-    SRAD_TRY(srad_wgrad_flush(q, s));
-  }
-  float* const part = q.ws + q.used;
-  q.used += need;
+  float* part = nullptr;
+  SRAD_TRY(srad_wgrad_take(q, "wgrad_conv9", need, 1, s, &part));
   WgradReduceItem& it = q.batch.it[q.batch.count++];
   it.dW = p.dW; it.db = p.db; it.part = part; it.n_real = C; it.cin_real = C; it.ntaps = 9; it.grp_real = it.grp_pad = 0;
   it.ksplit = ksplit; it.tile0 = q.tiles; it.alpha = p.alpha;
@@ -1050,6 +1033,7 @@ int defer_wgrad(const WgradParams& p, WgradQueue& q, hipStream_t s) {
   WgradMulti& m = q.multi;
   const int i = m.count++;
   m.p[i] = p; m.ksplit[i] = pl.ksplit; m.tn[i] = pl.tn; m.tc[i] = pl.tc; m.part[i] = pl.part;
+  q.multi_need[i] = pl.need;
   m.blk0[i] = i == 0 ? 0 : (m.blk0[i - 1] + m.nblk[i - 1] + 7) / 8 * 8;
   m.nblk[i] = (int)(pl.tiles * pl.ksplit);
   q.multi_flops += 2.0 * p.M * p.n_real * (double)p.cin_real;
@@ -1243,13 +1227,85 @@ __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__
 
 }  // namespace
 
-int srad_wgrad_flush(WgradQueue& q, hipStream_t stream) {
-  if (q.batch.count > 0) {
-    SradProfScope prof(stream, SRAD_K_WGRAD_REDUCE, 0.0, 4.0 * q.used);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(4 * q.tiles), dim3(256), 0, stream, q.batch);
-    SRAD_CHECK_HIP(hipGetLastError());
+static int launch_reduce(WgradQueue& q, const WgradReduceBatch& b, int tiles, int why, hipStream_t stream) {
+  if (b.count == 0) return SRAD_OK;
+  SradProfScope prof(stream, SRAD_K_WGRAD_REDUCE, 0.0, 4.0 * q.used);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(4 * tiles), dim3(256), 0, stream, b);
+  SRAD_CHECK_HIP(hipGetLastError());
+  WgradFlushLog& l = q.log;
+  if (l.count < SRAD_WGRAD_LOG) l.why[l.count] = (unsigned char)why;
+  ++l.count; ++l.by_why[why];
+  return SRAD_OK;
+}
+
+// Reduces every queued item whose partials are written.  No layer pending: the whole batch, and the workspace starts over.
+// Layers pending (queued by srad_launch_wgrad_deferred, not launched yet): their items stay, renumbered, their regions stay
+// live, and what the reduced items held - below, between or above them - can be handed out again (WgradQueue::gap_lo).
+static int flush_written(WgradQueue& q, int why, hipStream_t stream) {
+  const WgradMulti& m = q.multi;
+  if (m.count == 0) {
+    SRAD_TRY(launch_reduce(q, q.batch, q.tiles, why, stream));
+    q.batch.count = 0; q.tiles = 0; q.used = 0; q.gap_lo = q.gap_end = 0;
+    return SRAD_OK;
   }
-  q.batch.count = 0; q.tiles = 0; q.used = 0;
+  WgradReduceBatch now{}, keep{};
+  int now_tiles = 0, keep_tiles = 0;
+  for (int i = 0; i < q.batch.count; ++i) {
+    const WgradReduceItem& it = q.batch.it[i];
+    const int ntiles = (i + 1 < q.batch.count ? q.batch.it[i + 1].tile0 : q.tiles) - it.tile0;
+    bool pending = false;
+    for (int j = 0; j < m.count; ++j) pending = pending || (m.part[j] && it.part == m.part[j]);
+    WgradReduceBatch& to = pending ? keep : now;
+    int& to_tiles = pending ? keep_tiles : now_tiles;
+    to.it[to.count] = it;
+    to.it[to.count++].tile0 = to_tiles;
+    to_tiles += ntiles;
+  }
+  SRAD_TRY(launch_reduce(q, now, now_tiles, why, stream));
+  q.batch = keep; q.tiles = keep_tiles;
+  size_t top = 0;
+  for (int j = 0; j < m.count; ++j)
+    if (m.part[j]) top = std::max(top, (size_t)(m.part[j] - q.ws) + q.multi_need[j]);
+  q.used = top; q.gap_lo = 0; q.gap_end = top;
+  return SRAD_OK;
+}
+
+int srad_wgrad_flush(WgradQueue& q, hipStream_t stream) { return flush_written(q, SRAD_WGRAD_FLUSH_EXPLICIT, stream); }
+
+// a free region of `need` floats: a hole an earlier flush left under the pending layers, else the space above everything
+static bool place(WgradQueue& q, size_t need, size_t* at) {
+  if (q.gap_lo < q.gap_end) {
+    const WgradMulti& m = q.multi;
+    size_t c = q.gap_lo;
+    for (bool moved = true; moved;) {                     // past every pending region [b, e) that [c, c + need) would touch
+      moved = false;
+      for (int j = 0; j < m.count; ++j) {
+        if (!m.part[j]) continue;
+        const size_t b = (size_t)(m.part[j] - q.ws), e = b + q.multi_need[j];
+        if (c < e && c + need > b) { c = e; moved = true; }
+      }
+    }
+    if (c + need <= q.gap_end) { *at = c; q.gap_lo = c + need; return true; }
+  }
+  if (q.used + need > q.ws_floats) return false;
+  *at = q.used; q.used += need;
+  return true;
+}
+
+int srad_wgrad_take(WgradQueue& q, const char* who, size_t need, int nitems, hipStream_t stream, float** part) {
+  SRAD_REQUIRE(q.ws && need <= q.ws_floats, "%s: split-K workspace too small (%zu floats needed, %zu given)", who, need, q.ws_floats);
+  SRAD_REQUIRE(nitems >= 0 && nitems <= SRAD_WGRAD_BATCH - SRAD_WGRAD_MULTI, "%s: %d items in one reservation", who, nitems);
+  const bool batch_ok = q.batch.count + nitems <= SRAD_WGRAD_BATCH;
+  size_t at = 0;
+  if (!batch_ok || !place(q, need, &at)) {
+    const hipStream_t fs = q.multi.count > 0 && q.own_flush_stream ? q.flush_stream : stream;
+    SRAD_TRY(flush_written(q, batch_ok ? SRAD_WGRAD_FLUSH_WS : SRAD_WGRAD_FLUSH_BATCH, fs));
+    SRAD_REQUIRE(q.batch.count + nitems <= SRAD_WGRAD_BATCH && place(q, need, &at),
+                 "%s: split-K workspace too small next to the deferred layers (%zu floats needed, %zu given, %d layers pending)", who, need,
+                 q.ws_floats, q.multi.count);
+  }
+  *part = q.ws + at;
+  q.peak = std::max(q.peak, at + need);
   return SRAD_OK;
 }
 
@@ -1284,6 +1340,7 @@ int srad_wgrad_launch_deferred(int prec, WgradQueue& q, hipStream_t stream) {
     SRAD_CHECK_HIP(hipGetLastError());
   }
   m.count = 0; q.multi_flops = 0; q.multi_bytes = 0;
+  q.gap_lo = q.gap_end;                              // nothing is pending any more: the holes between the layers are not tracked
   return SRAD_OK;
 }
 
@@ -1313,7 +1370,8 @@ int srad_launch_wgrad(int prec, const WgradParams& p, WgradQueue& q, hipStream_t
 
 static int queue_colsum(WgradQueue& q, float* dst, const float* part, int ncols, int row_stride, int rows, float alpha,
                         hipStream_t stream) {
-  if (q.batch.count == SRAD_WGRAD_BATCH) SRAD_TRY(srad_wgrad_flush(q, stream));
+  (void)stream;
+  SRAD_REQUIRE(q.batch.count < SRAD_WGRAD_BATCH, "wgrad: a column sum was queued without room reserved for it");   // the rows are taken: no flush here
   WgradReduceItem& it = q.batch.it[q.batch.count++];
   it.dW = dst; it.db = nullptr; it.part = part; it.n_real = ncols; it.cin_real = row_stride; it.ntaps = 0; it.grp_real = it.grp_pad = 0;   // ntaps 0: column sums
   it.tn = it.tc = 1; it.ksplit = rows; it.tile0 = q.tiles; it.alpha = alpha; it.wc = 0;
@@ -1323,11 +1381,7 @@ static int queue_colsum(WgradQueue& q, float* dst, const float* part, int ncols,
 
 int srad_wgrad_reserve_colsum(WgradQueue& q, const char* who, float* dst, int ncols, int row_stride, int nrows, float alpha,
                               int nitems, hipStream_t stream, float** part) {
-  const size_t need = (size_t)nrows * row_stride;
-  SRAD_REQUIRE(q.ws && need <= q.ws_floats, "%s: workspace too small", who);
-  if (q.batch.count + nitems > SRAD_WGRAD_BATCH || q.used + need > q.ws_floats) SRAD_TRY(srad_wgrad_flush(q, stream));
-  *part = q.ws + q.used;
-  q.used += need;
+  SRAD_TRY(srad_wgrad_take(q, who, (size_t)nrows * row_stride, nitems, stream, part));
   if (dst) SRAD_TRY(queue_colsum(q, dst, *part, ncols, row_stride, nrows, alpha, stream));
   return SRAD_OK;
 }

@@ -376,6 +376,82 @@ int srad_op_wgrad_deferred(int precision, const void* dy, int ldy, int dy_bf16, 
 
 size_t srad_op_wgrad_workspace_bytes(void) { return SRAD_WGRAD_WS_BYTES; }
 
+// A list of queue steps through ONE WgradQueue whose workspace is the first `budget_floats` floats of `workspace`: what a
+// backward pass does to the queue, at sizes where the automatic flushes happen.  Every step kind and pointer is checked before
+// anything is launched; a step that fails returns its error at once (nothing queued behind it is reduced).  Ends with the
+// deferred launch and a flush.  *n_reduce = reduce launches made, why[i] = SRAD_WQ_FLUSH_* of launch i (the first why_cap).
+int srad_op_wgrad_queue_script(int precision, const srad_wq_step* steps, int nsteps, size_t budget_floats, void* workspace,
+                               size_t workspace_bytes, int* n_reduce, int* why, int why_cap, void* stream) {
+  SRAD_REQUIRE(steps && nsteps > 0 && workspace && n_reduce && (why || why_cap == 0) && why_cap >= 0, "op_wgrad_queue_script: null argument");
+  SRAD_REQUIRE(precision == SRAD_PREC_F32 || precision == SRAD_PREC_BF16, "op_wgrad_queue_script: precision must be fp32 or bf16");
+  SRAD_REQUIRE(((uintptr_t)workspace & 255) == 0, "op_wgrad_queue_script: workspace must be 256-byte aligned");
+  SRAD_REQUIRE(budget_floats > 0 && budget_floats <= workspace_bytes / sizeof(float),
+               "op_wgrad_queue_script: a budget of %zu floats does not fit the workspace of %zu bytes", budget_floats, workspace_bytes);
+  for (int i = 0; i < nsteps; ++i) {
+    const srad_wq_step& t = steps[i];
+    const void* const* p = t.p;
+    switch (t.kind) {
+      case SRAD_WQ_WGRAD: case SRAD_WQ_WGRAD_DEFERRED: SRAD_REQUIRE(p[0] && p[1] && p[2], "op_wgrad_queue_script: step %d: null argument", i); break;
+      case SRAD_WQ_LN_BWD: SRAD_REQUIRE(p[0] && p[1] && p[2] && p[4], "op_wgrad_queue_script: step %d: null argument", i); break;
+      case SRAD_WQ_ATTN_BWD: SRAD_REQUIRE(p[0] && p[1] && p[2] && p[3] && p[4], "op_wgrad_queue_script: step %d: null argument", i); break;
+      case SRAD_WQ_LAUNCH_DEFERRED: case SRAD_WQ_FLUSH: break;
+      default: return srad_set_error(SRAD_ERR_ARG, "op_wgrad_queue_script: step %d: unknown step kind %d", i, t.kind);
+    }
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WgradQueue q;
+  q.ws = reinterpret_cast<float*>(workspace);
+  q.ws_floats = budget_floats;
+  auto F = [](const void* v) { return reinterpret_cast<const float*>(v); };
+  auto W = [](const void* v) { return const_cast<float*>(reinterpret_cast<const float*>(v)); };
+  for (int i = 0; i < nsteps; ++i) {
+    const srad_wq_step& t = steps[i];
+    const int32_t* a = t.i;
+    switch (t.kind) {
+      case SRAD_WQ_WGRAD: {          // i: ldy ldx B Hi Wi N Cin ntaps stride;  p: dy x dw db row_scale
+        const int ntaps = a[7], stride = a[8];
+        SRAD_REQUIRE(stride == 1 || stride == 2, "op_wgrad_queue_script: step %d: stride must be 1 or 2", i);
+        WgradParams g{};
+        const int pad = ntaps == 9 ? 1 : 0, k = ntaps == 9 ? 3 : 1;
+        g.Hi = a[3]; g.Wi = a[4]; g.Ho = (g.Hi + 2 * pad - k) / stride + 1; g.Wo = (g.Wi + 2 * pad - k) / stride + 1; g.stride = stride;
+        g.dY = F(t.p[0]); g.ldy = a[0]; g.X = F(t.p[1]); g.ldx = a[1]; g.M = a[2] * g.Ho * g.Wo;
+        g.N = a[5]; g.Cin = a[6]; g.n_real = a[5]; g.cin_real = a[6]; g.ntaps = ntaps;
+        g.row_scale = F(t.p[4]); g.rps = g.Ho * g.Wo; g.alpha = t.alpha; g.dW = W(t.p[2]); g.db = W(t.p[3]);
+        SRAD_TRY(srad_launch_wgrad(precision, g, q, s));
+        break;
+      }
+      case SRAD_WQ_WGRAD_DEFERRED: { // i: ldy dy_bf16 ldx x_bf16 M N Cin rps;  p: dy x dw db row_scale
+        WgradParams g{};
+        g.dY = F(t.p[0]); g.ldy = a[0]; g.dy_bf16 = a[1]; g.X = F(t.p[1]); g.ldx = a[2]; g.x_bf16 = a[3]; g.M = a[4];
+        g.N = a[5]; g.Cin = a[6]; g.n_real = a[5]; g.cin_real = a[6]; g.ntaps = 1; g.stride = 1;
+        g.row_scale = F(t.p[4]); g.rps = a[7]; g.alpha = t.alpha; g.dW = W(t.p[2]); g.db = W(t.p[3]);
+        SRAD_TRY(srad_launch_wgrad_deferred(precision, g, q, s));
+        break;
+      }
+      case SRAD_WQ_LAUNCH_DEFERRED: SRAD_TRY(srad_wgrad_launch_deferred(precision, q, s)); break;
+      case SRAD_WQ_LN_BWD: {         // i: ldx accumulate rows C;  p: dxn x gamma dres out dgamma dbeta
+        LnBwdParams l{};
+        l.dxn = F(t.p[0]); l.ld_dxn = a[3]; l.x = F(t.p[1]); l.ldx = a[0]; l.gamma = F(t.p[2]); l.dres = F(t.p[3]); l.ld_dres = a[3];
+        l.out = W(t.p[4]); l.ld_out = a[3]; l.accumulate = a[1]; l.dgamma = W(t.p[5]); l.dbeta = W(t.p[6]); l.rows = a[2]; l.C = a[3]; l.eps = 1e-5f;
+        SRAD_TRY(srad_launch_ln_bwd(l, q, s));
+        break;
+      }
+      case SRAD_WQ_ATTN_BWD: {       // i: B H W ws shift d heads hdp;  p: qkv dout dqkv table dtable
+        SRAD_REQUIRE(a[6] > 0 && a[3] > 0, "op_wgrad_queue_script: step %d: bad attention geometry", i);
+        AttnBwdParams ab{F(t.p[0]), F(t.p[1]), W(t.p[2]), nullptr, F(t.p[3]), W(t.p[4]), a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]};
+        SRAD_TRY(srad_launch_window_attn_bwd(precision, ab, q, s));
+        break;
+      }
+      default: SRAD_TRY(srad_wgrad_flush(q, s)); break;    // SRAD_WQ_FLUSH
+    }
+  }
+  SRAD_TRY(srad_wgrad_launch_deferred(precision, q, s));
+  SRAD_TRY(srad_wgrad_flush(q, s));
+  *n_reduce = q.log.count;
+  for (int i = 0; i < q.log.count && i < why_cap && i < SRAD_WGRAD_LOG; ++i) why[i] = q.log.why[i];
+  return SRAD_OK;
+}
+
 // tools/wgrad_bench.py: the five weight gradients of one Swin block (qkv, proj, fc1, fc2, adjust) exactly as the training
 // step issues them - deferred into one launch, then the reduce - `iters` times.  storage bit 0: X operands are bf16,
 // bit 1: dY operands are bf16.  All layers read the same two operand buffers (the timing does not care).

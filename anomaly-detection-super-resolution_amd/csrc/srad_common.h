@@ -383,12 +383,26 @@ struct WgradMulti {                            // Linear layers whose weight-gra
   int ksplit[SRAD_WGRAD_MULTI], tn[SRAD_WGRAD_MULTI], tc[SRAD_WGRAD_MULTI], blk0[SRAD_WGRAD_MULTI], nblk[SRAD_WGRAD_MULTI];
   int count;
 };
+// why a reduce launch happened (include/srad.h SRAD_WQ_FLUSH_*): asked for, or made by a reservation that found the batch /
+// the workspace full.  Host bookkeeping only: what a test asserts to know which path it exercised.
+enum { SRAD_WGRAD_FLUSH_EXPLICIT = 0, SRAD_WGRAD_FLUSH_BATCH = 1, SRAD_WGRAD_FLUSH_WS = 2 };
+#define SRAD_WGRAD_LOG 64
+struct WgradFlushLog { int count = 0; int by_why[3] = {0, 0, 0}; unsigned char why[SRAD_WGRAD_LOG] = {}; };   // the first SRAD_WGRAD_LOG reasons in order
 struct WgradQueue {
   float* ws = nullptr; size_t ws_floats = 0;   // caller-owned device workspace, 16-byte aligned
   size_t used = 0; int tiles = 0;
   WgradReduceBatch batch{};
   WgradMulti multi{};
   double multi_flops = 0, multi_bytes = 0;
+  // A deferred layer is PENDING from srad_launch_wgrad_deferred until srad_wgrad_launch_deferred writes its partials: a flush
+  // in between reduces only the other items and keeps the pending layers' items and regions (multi_need: floats at multi.part).
+  size_t multi_need[SRAD_WGRAD_MULTI] = {};
+  size_t gap_lo = 0, gap_end = 0;              // [gap_lo, gap_end) minus the pending regions: free space such a flush left below `used`
+  // Stream that writes the partials of everything but the deferred layers.  Set by a caller that sends the deferred layers to
+  // another stream: a flush a reservation makes while layers are pending then goes here, whichever stream the call names.
+  bool own_flush_stream = false; hipStream_t flush_stream = nullptr;
+  size_t peak = 0;                             // highest end of a region handed out so far (floats)
+  WgradFlushLog log{};
 };
 // queue a Linear layer's weight gradient without launching; srad_wgrad_launch_deferred sends all queued ones as one
 // launch (call it before srad_wgrad_flush, which only sums partials that have been written)
@@ -397,6 +411,10 @@ int srad_wgrad_launch_deferred(int prec, WgradQueue& q, hipStream_t stream);
 int srad_launch_wgrad(int prec, const WgradParams& p, WgradQueue& q, hipStream_t stream);
 bool srad_wgrad_conv9_supported(const WgradParams& p);   // the nine-tap kernel takes this layer (bf16 mode; the only one with bf16 conv operands)
 int srad_wgrad_flush(WgradQueue& q, hipStream_t stream);
+// The one place workspace is handed out: `need` floats (*part) and room for `nitems` more batch entries.  When the batch or the
+// workspace is full the queue flushes itself first - with deferred layers pending only the written items, see WgradQueue - and
+// fails with an error naming `who` if the region still does not fit.  The caller appends its `nitems` items afterwards.
+int srad_wgrad_take(WgradQueue& q, const char* who, size_t need, int nitems, hipStream_t stream, float** part);
 // Takes `nrows` partial rows of `row_stride` floats from the workspace (*part) for a kernel to fill, and queues alpha times the
 // column sums of their first `ncols` columns into dst (null: none).  `nitems` = column-sum items that will be queued on these
 // rows in all: a flush that the batch or the workspace needs comes before the rows are taken.  `who` names the caller in errors.

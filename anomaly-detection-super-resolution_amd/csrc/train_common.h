@@ -16,6 +16,9 @@ struct TrainState {
   int n_sync_blocks = 0;
   char* tarena = nullptr;
   bool ready = false;
+  size_t wgrad_budget = SRAD_WGRAD_WS_BYTES;   // bytes of the split-K workspace the backward uses (<= what the arena holds)
+  WgradFlushLog wgrad_log{};                   // reduce launches of the last backward
+  size_t wgrad_block_peak = 0;                 // ... and the most floats one block had reserved in its half
 };
 
 // The two streams of a backward: the data-gradient chain stays on the caller's stream (`main`), the weight gradients, which
@@ -350,7 +353,7 @@ inline int train_sync_params(const ParamTable& pt, TrainState& ts, const float* 
 inline WgradQueue train_wgrad_queue(const TrainState& ts) {
   WgradQueue q;
   q.ws = reinterpret_cast<float*>(ts.tarena + ts.t_wgrad_off);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  q.ws_floats = ts.wgrad_budget / sizeof(float);
   return q;
 }
 

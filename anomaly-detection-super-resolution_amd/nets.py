@@ -433,6 +433,18 @@ class DRCT(_EngineModule):
             self.grad_buckets.append((a.value, b.value))
         return self
 
+    def set_wgrad_budget(self, nbytes: int) -> None:
+        """Limit the split-K workspace the backward uses (a multiple of 512 bytes, at most what the training arena holds).
+        Gradients do not depend on it; less means more reduce launches (tests of the queue's automatic flushes)."""
+        L.check(L.lib().srad_drct_train_set_wgrad_budget(self._handle, C.c_size_t(nbytes)), "train_set_wgrad_budget")
+
+    def wgrad_stats(self):
+        """(reduce launches of the last backward by reason [explicit, batch full, workspace full], the most floats a Swin block
+        had reserved at once)."""
+        n, peak = (C.c_int * 3)(), C.c_size_t()
+        L.check(L.lib().srad_drct_train_wgrad_stats(self._handle, n, C.byref(peak)), "train_wgrad_stats")
+        return [int(v) for v in n], int(peak.value)
+
     def drop_path_keep_probs(self) -> torch.Tensor:
         """keep_prob of every Swin block: all five blocks of RDG i use dpr[i * depth] of
         linspace(0, rate, sum(depths)) (src/drct.py:819,829,332)."""

@@ -124,6 +124,71 @@ def wgrad_workspace(device) -> C.c_void_p:
     return C.c_void_p(t.data_ptr() + (-t.data_ptr()) % 256)
 
 
+def wq_wgrad(dy, x, dw, db, *, ntaps: int = 1, B: int = 1, H: int = 0, W: int = 0, stride: int = 1, alpha: float = 1.0):
+    """Script step: an immediate weight gradient (Linear, or 3x3 with the image geometry) accumulated into dw [N, Cin, ntaps] / db."""
+    if ntaps == 1 and stride == 1:
+        B, H, W = 1, 1, x.shape[0]
+    return (L.WQ_WGRAD, [dy.stride(0), x.stride(0), B, H, W, dw.shape[0], dw.shape[1], ntaps, stride], alpha, [dy, x, dw, db, None])
+
+
+def wq_wgrad_deferred(dy, x, dw, db, *, row_scale=None, rps: int = 0, alpha: float = 1.0):
+    """Script step: a Linear layer's weight gradient queued for the shared launch (dw [N, Cin])."""
+    return (L.WQ_WGRAD_DEFERRED, [dy.stride(0), int(dy.dtype == torch.bfloat16), x.stride(0), int(x.dtype == torch.bfloat16), dy.shape[0],
+                                  dw.shape[0], dw.shape[1], rps], alpha, [dy, x, dw, db, row_scale])
+
+
+def wq_launch_deferred():
+    return (L.WQ_LAUNCH_DEFERRED, [], 0.0, [])
+
+
+def wq_flush():
+    return (L.WQ_FLUSH, [], 0.0, [])
+
+
+def wq_layernorm_bwd(dxn, x, gamma, out, dgamma, dbeta, *, dres=None, accumulate: bool = False):
+    """Script step: LayerNorm backward over contiguous [rows, C] tensors (x may be a column block of wider rows)."""
+    rows, Cc = dxn.shape
+    return (L.WQ_LN_BWD, [x.stride(0), int(accumulate), rows, Cc], 0.0, [dxn, x, gamma, dres, out, dgamma, dbeta])
+
+
+def wq_window_attention_bwd(qkv_padded, dout, dqkv, table, dtable, *, B: int, H: int, W: int, ws: int, shift: int, heads: int):
+    """Script step: the fp32-operand attention backward; qkv_padded as ``pad_heads`` lays it out."""
+    d = dout.shape[1]
+    return (L.WQ_ATTN_BWD, [B, H, W, ws, shift, d, heads, qkv_padded.shape[1] // (3 * heads)], 0.0, [qkv_padded, dout, dqkv, table, dtable])
+
+
+def pad_heads(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """[T, 3d] q | k | v in the reference's column order -> the head-padded layout the attention kernels read."""
+    hd = qkv.shape[1] // (3 * heads)
+    hdp = (hd + 3) // 4 * 4
+    return torch.nn.functional.pad(qkv.reshape(-1, 3 * heads, hd).float(), (0, hdp - hd)).reshape(-1, 3 * heads * hdp).contiguous()
+
+
+def wgrad_queue_script(steps, *, precision: str = "fp32", budget_floats: Optional[int] = None, device=None):
+    """Runs the steps (``wq_*`` above) through ONE split-K queue limited to ``budget_floats`` of the workspace (default: all of
+    it), then the deferred launch and a flush (C ABI ``srad_op_wgrad_queue_script``).  Returns the reasons of the reduce
+    launches it made, in order (``L.WQ_FLUSH_*``)."""
+    device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    nbytes = L.lib().srad_op_wgrad_workspace_bytes()
+    if budget_floats is None:
+        budget_floats = nbytes // 4
+    arr = (L.WqStep * len(steps))()
+    keep = []
+    for st, (kind, ints, alpha, ptrs) in zip(arr, steps):
+        _need_cuda(*ptrs)
+        st.kind, st.alpha = kind, alpha
+        for j, v in enumerate(ints):
+            st.i[j] = int(v)
+        for j, t in enumerate(ptrs):
+            st.p[j] = None if t is None else t.data_ptr()
+        keep.append(ptrs)
+    n = C.c_int(0)
+    why = (C.c_int * 64)()
+    L.check(L.lib().srad_op_wgrad_queue_script(L.PRECISIONS[precision], arr, len(steps), C.c_size_t(budget_floats), wgrad_workspace(device),
+                                               C.c_size_t(nbytes), C.byref(n), why, 64, L.current_stream_ptr()), "op_wgrad_queue_script")
+    return [int(why[i]) for i in range(min(n.value, 64))] + [-1] * max(0, n.value - 64)
+
+
 def wgrad(dy: torch.Tensor, x: torch.Tensor, N: int, Cin: int, *, ntaps: int = 1, B: int = 1, H: int = 0, W: int = 0,
           stride: int = 1, row_scale: Optional[torch.Tensor] = None, alpha: float = 1.0, bias: bool = True,
           precision: str = "fp32"):

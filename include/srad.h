@@ -79,6 +79,13 @@ int srad_drct_train_param_offset(srad_drct_t* h, int idx, int64_t* off_floats);
 /* second caller-owned arena: transposed weight packs for the data gradients (bind after srad_drct_bind_arena) */
 int srad_drct_train_arena_bytes(srad_drct_t* h, size_t* bytes);
 int srad_drct_train_bind(srad_drct_t* h, void* train_arena, size_t bytes);
+/* Split-K workspace the backward may use out of what the training arena holds (the default: all of it), in bytes, a multiple
+ * of 512; each Swin block works in one half of it.  Less only costs extra reduce launches until a single reservation no longer
+ * fits, which srad_drct_backward reports as an error.  For tests of those launches; outputs do not depend on it. */
+int srad_drct_train_set_wgrad_budget(srad_drct_t* h, size_t bytes);
+/* Reduce launches of the last srad_drct_backward by reason (SRAD_WQ_FLUSH_*, host bookkeeping), and the most floats a Swin
+ * block had reserved in its half at once */
+int srad_drct_train_wgrad_stats(const srad_drct_t* h, int launches[3], size_t* block_peak_floats);
 /* refresh all packed weights from the flat fp32 parameters: call after loading and after every optimizer step */
 int srad_drct_sync_params(srad_drct_t* h, const float* dev_flat_params, void* stream);
 int srad_drct_train_workspace_bytes(const srad_drct_t* h, int B, int H, int W, size_t* bytes);
@@ -373,6 +380,28 @@ int srad_op_wgrad_deferred(int precision, const void* dy, int ldy, int dy_bf16, 
 /* split-K workspace of srad_op_wgrad (256-byte aligned scratch, contents irrelevant, reusable by later calls on the
  * same stream) */
 size_t srad_op_wgrad_workspace_bytes(void);
+/* The split-K queue under a script (tests): `nsteps` steps through ONE queue whose workspace is the first budget_floats floats
+ * of `workspace` (budget_floats * 4 <= workspace_bytes), then the deferred launch and a flush.  A step is one of the calls a
+ * backward pass makes; its integers and pointers, in order:
+ *   SRAD_WQ_WGRAD            i: ldy ldx B Hi Wi N Cin ntaps stride       p: dy x dw db row_scale    (as srad_op_wgrad)
+ *   SRAD_WQ_WGRAD_DEFERRED   i: ldy dy_bf16 ldx x_bf16 M N Cin rps       p: dy x dw db row_scale    (as srad_op_wgrad_deferred, not launched)
+ *   SRAD_WQ_LAUNCH_DEFERRED  the queued Linear layers as one launch
+ *   SRAD_WQ_LN_BWD           i: ldx accumulate rows C                    p: dxn x gamma dres out dgamma dbeta
+ *   SRAD_WQ_ATTN_BWD         i: B H W ws shift d heads hdp               p: qkv dout dqkv table dtable  (as srad_op_window_attn_bwd)
+ *   SRAD_WQ_FLUSH            reduce what is queued
+ * Reports the reduce launches made, counted on the host: *n_reduce, and why[i] (i < why_cap) = the reason of launch i.  The
+ * queue flushes itself when a reservation finds the batch (12 items) or the budget full; a reservation that cannot fit even
+ * then is an error that names the call that made it, returned at once. */
+enum { SRAD_WQ_WGRAD = 1, SRAD_WQ_WGRAD_DEFERRED = 2, SRAD_WQ_LAUNCH_DEFERRED = 3, SRAD_WQ_LN_BWD = 4, SRAD_WQ_ATTN_BWD = 5, SRAD_WQ_FLUSH = 6 };
+enum { SRAD_WQ_FLUSH_EXPLICIT = 0, SRAD_WQ_FLUSH_BATCH = 1, SRAD_WQ_FLUSH_WS = 2 };
+typedef struct {
+  int32_t kind;
+  int32_t i[9];
+  float alpha;
+  const void* p[7];
+} srad_wq_step;
+int srad_op_wgrad_queue_script(int precision, const srad_wq_step* steps, int nsteps, size_t budget_floats, void* workspace,
+                               size_t workspace_bytes, int* n_reduce, int* why, int why_cap, void* stream);
 /* Data gradient dx = (dy . w) * alpha * row_scale (* gelu'(r) if rmode 1, * lrelu'(r) if rmode 2), stride 1:
  * the forward GEMM on the transposed pack of w [N][Cin][taps]; scratch >= srad_op_gemm_scratch_bytes(p, Cin, N, taps) */
 int srad_op_dgrad(int precision, const float* dy, int ldy, int B, int H, int W, int N, const float* w, int Cin,

@@ -64,6 +64,55 @@ def test_argument_errors_without_gpu():
     assert lib.srad_roc_auc(y, s, 4, C.byref(auc)) == 0 and abs(auc.value - 0.75) < 1e-15
 
 
+def test_wgrad_queue_script_argument_errors_without_gpu():
+    """srad_op_wgrad_queue_script checks its budget, every step kind and every step's pointers before it launches anything."""
+    import ctypes as C
+    from srad_amd import _lib as L
+    lib = L.lib()
+    SRAD_ERR_ARG = 1
+    ws, ws_bytes = C.c_void_p(1 << 20), 1 << 16              # never dereferenced: every call below fails in the checks
+    fake = 1 << 12
+    n, why = C.c_int(-1), (C.c_int * 4)()
+
+    def call(steps, budget=1024, workspace=ws, n_out=C.byref(n)):
+        arr = (L.WqStep * max(1, len(steps)))(*steps)
+        return lib.srad_op_wgrad_queue_script(L.PREC_F32, arr if steps else None, len(steps), budget, workspace, ws_bytes, n_out, why, 4, None)
+
+    def step(kind, ptrs=()):
+        st = L.WqStep()
+        st.kind = kind
+        for j, v in enumerate(ptrs):
+            st.p[j] = v
+        return st
+
+    flush = step(L.WQ_FLUSH)
+    assert call([flush], budget=ws_bytes // 4 + 1) == SRAD_ERR_ARG and b"does not fit the workspace" in lib.srad_last_error()
+    assert call([flush], budget=0) == SRAD_ERR_ARG
+    assert call([flush, step(7)]) == SRAD_ERR_ARG and b"step 1: unknown step kind 7" in lib.srad_last_error()
+    assert call([step(0)]) == SRAD_ERR_ARG and b"unknown step kind" in lib.srad_last_error()
+    assert call([]) == SRAD_ERR_ARG and b"null argument" in lib.srad_last_error()
+    assert call([flush], workspace=None) == SRAD_ERR_ARG and b"null argument" in lib.srad_last_error()
+    assert call([flush], n_out=None) == SRAD_ERR_ARG and b"null argument" in lib.srad_last_error()
+    assert call([flush], workspace=C.c_void_p((1 << 20) + 16)) == SRAD_ERR_ARG and b"256-byte aligned" in lib.srad_last_error()
+    for kind, nptr in ((L.WQ_WGRAD, 3), (L.WQ_WGRAD_DEFERRED, 3), (L.WQ_ATTN_BWD, 5)):
+        for missing in range(nptr):                          # each required pointer in turn
+            ptrs = [None if j == missing else fake for j in range(nptr)]
+            assert call([flush, step(kind, ptrs)]) == SRAD_ERR_ARG and b"step 1: null argument" in lib.srad_last_error(), (kind, missing)
+    for missing in (0, 1, 2, 4):                             # LayerNorm: dxn, x, gamma, out (dres, dgamma, dbeta are optional)
+        ptrs = [None if j == missing else fake for j in range(5)]
+        assert call([step(L.WQ_LN_BWD, ptrs)]) == SRAD_ERR_ARG and b"step 0: null argument" in lib.srad_last_error(), missing
+    assert n.value == -1                                     # nothing was reported by a call that failed
+    h = C.c_void_p()
+    ok = L.DrctConfig(1, 32, 8, 4, 180, 12, 6, 32, 64, 2.0, 1.0, 1, 0)
+    assert lib.srad_drct_create(C.byref(ok), C.byref(h)) == 0
+    assert lib.srad_drct_train_set_wgrad_budget(h, 1 << 20) == 0
+    assert lib.srad_drct_train_set_wgrad_budget(h, (1 << 20) + 4) == SRAD_ERR_ARG and b"multiple of 512" in lib.srad_last_error()
+    assert lib.srad_drct_train_set_wgrad_budget(h, lib.srad_op_wgrad_workspace_bytes() + 512) == SRAD_ERR_ARG
+    assert lib.srad_drct_train_set_wgrad_budget(h, 0) == SRAD_ERR_ARG
+    assert lib.srad_drct_train_set_wgrad_budget(None, 512) == SRAD_ERR_ARG
+    lib.srad_drct_destroy(h)
+
+
 def test_path_overrides_ignore_the_environment():
     """Kernel paths follow shape and precision, plus the explicit overrides of srad_set_path_override: a fresh process with
     an old A/B switch in its environment starts with every override off; set / get round-trip; an unknown path is an error."""

@@ -236,6 +236,42 @@ def test_bf16_training_gradients_close_to_fp32(sr_golden):
     assert cos > 0.99 and 0.9 < float(b.norm() / a.norm()) < 1.1
 
 
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_gradients_do_not_depend_on_the_wgrad_budget(prec):
+    """One RDG of 8 x 8 windows on the smallest image of this file (16 x 16), with the split-K workspace cut so that the largest
+    Swin block no longer fits its half: the queue flushes in the middle of that block, while its deferred weight gradients are
+    queued but not launched (and, the whole workspace being smaller than what the layers around the RDG queue, between those
+    too).  Parameter gradients and dx must be bit-identical to the run with the whole workspace: flush positions change, no sum
+    does.  The flush reasons the engine counted say that the pressured path ran."""
+    from srad_amd import spec as S
+    cfg = S.DRCTConfig(in_chans=1, img_size=16, window_size=8, upscale=2, n_rdg=1)
+    sd = S.synth_state(S.drct_spec(cfg), seed=31, gain=1.0, cfg=cfg)
+    B, H, W = 2, 16, 16
+    x = torch.from_numpy(S.synth_image("wq", (B, 1, H, W), seed=3)).cuda()
+    hr = torch.from_numpy(S.synth_image("wq/hr", (B, 1, H * cfg.upscale, W * cfg.upscale), seed=4)).cuda()
+    m = build_train(cfg, sd, prec)
+
+    def step():
+        m.zero_grad()
+        xt = x.clone().requires_grad_(True)
+        F.l1_loss(m(xt), hr).backward()
+        torch.cuda.synchronize()
+        return m.flat_grads.clone(), xt.grad.clone(), m.wgrad_stats()
+
+    g_full, dx_full, (n_full, peak) = step()
+    assert n_full[1] == 0 and n_full[2] == 0 and peak > 4096, (n_full, peak)       # unpressured: explicit flushes only
+    assert float(g_full.abs().max()) > 0
+    # half a budget = the largest block's reservations less 1024 floats: its last reservation (LayerNorm1's partial rows,
+    # 32 x 640 floats) does not fit, and goes where the rows of LayerNorm2, reduced by the flush, were
+    m.set_wgrad_budget(2 * 4 * ((peak - 1024) // 128 * 128))
+    g, dx, (n, peak2) = step()
+    print(f"{prec}: reduce launches [explicit, batch, workspace] {n_full} with the whole workspace, {n} with {peak - 1024} floats per half")
+    assert n[2] >= 1, (n, n_full)
+    assert peak2 <= peak - 1024
+    assert torch.equal(g, g_full)
+    assert torch.equal(dx, dx_full)
+
+
 def test_training_errors_are_reported():
     from srad_amd import spec as S
     from srad_amd.nets import DRCT
