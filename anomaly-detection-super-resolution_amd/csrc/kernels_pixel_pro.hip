@@ -29,6 +29,7 @@
 #include "engine.h"
 #include "../../include/srad.h"
 #include "pixel_sort.h"
+#include "pixel_pro.h"
 #include <algorithm>
 #include <math.h>
 
@@ -226,19 +227,8 @@ __global__ __launch_bounds__(256) void mask_sizes_kernel(const uint8_t* __restri
 }
 
 // ---------------------------------------------------------------- 3. the curve scan, in scan tiles of 4096 (thread t: keys t * 16 ..)
-// Prefix over the walk: the pro numerator as a 128-bit fixed-point number in units of 2^-64, kept as two u64 words with an
-// explicit carry (hi:lo), and the ok-pixel count.  (An unsigned __int128 here lost the high-word update of a conditional copy
-// in the unrolled scan loop on gfx950; two plain words do not depend on i128 lowering.)
-struct alignas(16) Pref {
-  uint64_t lo, hi, ok, pad;      // 32 bytes: LDS copies move as two 16-byte words
-};
+// Pref, PrefAdd and pro_add (the 128-bit fixed-point pro numerator and the ok-pixel count) live in pixel_pro.h.
 __device__ __forceinline__ bool pw_less(const Pref& a, const Pref& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
-struct PrefAdd {
-  __device__ Pref operator()(const Pref& a, const Pref& b) const {
-    const uint64_t lo = a.lo + b.lo;
-    return Pref{lo, a.hi + b.hi + (lo < a.lo ? 1ull : 0ull), a.ok + b.ok, 0};
-  }
-};
 struct PrefMax {      // componentwise: both parts never decrease along the walk, so this is the value at the later position
   __device__ Pref operator()(const Pref& a, const Pref& b) const {
     const bool b_more = pw_less(a, b);
@@ -255,19 +245,6 @@ struct ProTile {
   double area;
 };
 
-// p += floor(2^64 / z) for z >= 1: a 64-bit division, plus one when z divides 2^64 (a power of two); z == 1 adds 2^64 itself
-__device__ __forceinline__ void pro_add(Pref& p, uint64_t key) {
-  const uint32_t z = (uint32_t)key;
-  if (z == 0u) {
-    ++p.ok;
-  } else if (z == 1u) {
-    ++p.hi;
-  } else {
-    const uint64_t q = ~0ull / z + ((z & (z - 1u)) == 0u ? 1ull : 0ull);
-    p.lo += q;
-    p.hi += p.lo < q ? 1ull : 0ull;
-  }
-}
 __device__ __forceinline__ uint32_t hi32(uint64_t k) { return (uint32_t)(k >> 32); }
 __device__ __forceinline__ bool is_head(const uint64_t* keys, int64_t i, uint32_t hi) { return i == 0 || hi32(keys[i - 1]) != hi; }
 __device__ __forceinline__ bool is_end(const uint64_t* keys, int64_t i, int64_t n, uint32_t hi) {
@@ -455,13 +432,6 @@ __global__ __launch_bounds__(256) void pro_finish_kernel(const ProTile* __restri
 }
 
 // ---------------------------------------------------------------- host side
-int check_shape(int n_img, int H, int W, const char* who, int64_t& n) {
-  SRAD_REQUIRE(n_img >= 1 && H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX && (int64_t)H * W * n_img <= INT32_MAX,
-               "%s: n_img x H x W = %d x %d x %d, must be in [1, 2^31)", who, n_img, H, W);
-  n = (int64_t)n_img * H * W;
-  return SRAD_OK;
-}
-
 LabGeom lab_geom(int H, int W) { return LabGeom{H, W, (W + kLabT - 1) / kLabT, (H + kLabT - 1) / kLabT}; }
 
 // Stages 1a - 1d.  parent: n u32 of workspace; size: n u32 (the output, or workspace when `keys` is given).

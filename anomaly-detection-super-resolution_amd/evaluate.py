@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import os
 import re
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -71,9 +72,10 @@ def resolve_checkpoint(args) -> str:
     raise FileNotFoundError('Please provide --checkpoint or a valid --run-dir containing model/*.pt')
 
 
-def iter_split(data_root: str, classe: str, split: str, scale, n_colors: int, rgb_range: float = 255.0
+def iter_split(data_root: str, classe: str, split: str, scale, n_colors: int, rgb_range: float = 255.0, part: str = 'test'
                ) -> Iterable[Tuple[str, np.ndarray, np.ndarray]]:
-    """(name, LR u8 HWC, HR u8 HWC) of ``{root}/{class}/test/{split}`` read the way the reference's evaluator reads it
+    """(name, LR u8 HWC, HR u8 HWC) of ``{root}/{class}/{part}/{split}`` (``part`` = 'test', or 'val' for the held-out
+    defect-free images ``main.py`` validates on) read the way the reference's evaluator reads the test split
     (src/evaluate.py:140-150,204-217): the MVTec test loader (``data.MVTec(train=False)``: LR_{s} / LR_bicubic/X{s} / LR
     next to HR, ``set_channel``, HR cropped to LR * scale) and the TRUNCATING u8 conversion of the HR tensor.  The LR image
     is what the loader feeds the model, kept as u8 when it is integral (PNG input), so the forward sees the same values."""
@@ -83,7 +85,7 @@ def iter_split(data_root: str, classe: str, split: str, scale, n_colors: int, rg
         pass
     o = _O()
     o.scale = list(scale) if isinstance(scale, (list, tuple)) else [scale]
-    o.data_dir = str(Path(data_root) / classe / 'test' / split)
+    o.data_dir = str(Path(data_root) / classe / part / split)
     o.n_colors, o.rgb_range, o.no_augment, o.patch_size, o.batch_size, o.test_every = n_colors, 255, True, 0, 1, 1
     ds = MVTec(o, train=False)
     for i in range(len(ds)):
@@ -138,6 +140,48 @@ def save_anomaly_maps(maps: torch.Tensor, names: Sequence[str], splits: Sequence
         d = Path(output_dir) / 'anomaly_maps' / split
         d.mkdir(parents=True, exist_ok=True)
         Image.fromarray(u8[k, :, :, 0]).save(str(d / f"{name}.png"))
+
+
+def save_masks(pred: torch.Tensor, names: Sequence[str], splits: Sequence[str], output_dir: str) -> None:
+    """``<output_dir>/anomaly_masks/{good,bad}/<name>.png``: the predicted masks (uint8 {0, 1} [n,H,W]) as 8-bit gray, 0 / 255."""
+    from PIL import Image
+    u8 = (pred * 255).cpu().numpy()
+    for k, (name, split) in enumerate(zip(names, splits)):
+        d = Path(output_dir) / 'anomaly_masks' / split
+        d.mkdir(parents=True, exist_ok=True)
+        Image.fromarray(u8[k]).save(str(d / f"{name}.png"))
+
+
+@dataclass
+class OperatingPoint:
+    """What ``evaluate_on_test(operating_point=...)`` takes (a dict with these keys does too): a given ``threshold``, or the
+    rate ``fpr`` in (0, 1) to calibrate one at on the defect-free (LR, HR) u8 pairs ``calib`` - on all pixels of their maps
+    (``level`` 'pixel') or on each map's maximum ('image'); ``min_area``: predicted components below it are removed;
+    ``save_masks``: write the predicted masks under ``output_dir/anomaly_masks``."""
+    threshold: Optional[float] = None
+    fpr: Optional[float] = None
+    level: str = 'pixel'
+    min_area: int = 1
+    save_masks: bool = False
+    calib: Sequence[Tuple[np.ndarray, np.ndarray]] = ()
+
+    def check(self) -> 'OperatingPoint':
+        if (self.threshold is None) == (self.fpr is None):
+            raise ValueError("operating point: give either a threshold or a false-positive rate to calibrate one at")
+        if self.threshold is not None and float(self.threshold) != float(self.threshold):
+            raise ValueError("operating point: the threshold is NaN")
+        if self.fpr is not None:
+            M.rank_for_rate(1, self.fpr)                      # the rate's own check
+        if self.level not in ('pixel', 'image'):
+            raise ValueError(f"operating point: level = {self.level!r}, must be 'pixel' or 'image'")
+        if int(self.min_area) < 1 or int(self.min_area) != self.min_area:
+            raise ValueError(f"operating point: min_area = {self.min_area}, must be an integer >= 1")
+        return self
+
+
+def val_good_dir(data_root: str, classe: str) -> Path:
+    """Where the calibration images of ``--threshold-fpr`` live: the defect-free validation split of the prepared tree."""
+    return Path(data_root) / classe / 'val' / 'good'
 
 
 def resolve_map_scales(map_scales, H: int, W: int) -> List[int]:
@@ -200,7 +244,7 @@ def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndar
 def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], bad: Sequence[Tuple[np.ndarray, np.ndarray]],
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
-                     map_ws: int = 0, map_scales=(), map_reduce: str = 'mean', map_sigma: float = 0.0,
+                     map_ws: int = 0, map_scales=(), map_reduce: str = 'mean', operating_point=None, map_sigma: float = 0.0,
                      map_image_score: bool = False, aupro: bool = False, pro_fpr_limit: float = 0.3) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
@@ -221,7 +265,20 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     maps of ``metrics.anomaly_maps_multi`` with ``map_reduce`` ('mean' or 'max') instead of one window size's; everything after
     them is unchanged, and the result carries ``map_scales`` (the list used) and ``map_reduce`` in place of ``map_ws``.  The
     scales do not depend on the sweep's result.  ValueError, before any image is super-resolved, for a size the images are too
-    small for, an unknown ``map_reduce``, and scales together with a non-zero ``map_ws``."""
+    small for, an unknown ``map_reduce``, and scales together with a non-zero ``map_ws``.
+
+    ``operating_point`` (an ``OperatingPoint`` or a dict of its fields; None = off): with world 1 the maps are thresholded
+    (DESIGN.md "Operating point") at the given threshold, or at the one that the maps of the calibration pairs - made like the
+    test maps: the same forward, u8 conversion, window size or scales, and ``map_sigma`` - give at the asked false-positive
+    rate.  The result gains ``threshold``, ``threshold_source`` ('given' or 'fpr'; then also ``threshold_fpr``,
+    ``threshold_level``, ``calib_images``, ``calib_rate`` = the rate achieved on the calibration values), ``min_region_area``,
+    the image-level counts and rates of ``metrics.operating_point_stats`` and, with a mask for every image, its pixel-level
+    counts, ratios and ``pro_at_threshold``.  ValueError for an inconsistent specification, before any image is super-resolved."""
+    op = None
+    if operating_point is not None:
+        op = (OperatingPoint(**operating_point) if isinstance(operating_point, dict) else operating_point).check()
+        if op.fpr is not None and world == 1 and not len(op.calib):
+            raise ValueError("operating point: a false-positive rate needs calibration pairs (defect-free images)")
     if map_sigma and (good or bad):
         h, w = (list(good) + list(bad))[0][1].shape[:2]
         M.smooth_radius(map_sigma, h, w)
@@ -252,9 +309,9 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     rows = torch.cat([ssim, mse[:, None], psnr[:, None]], dim=1)          # [n_mine, n_ws + 2] float64
     full = gather_score_rows(mine, rows.cpu().numpy(), len(pairs), rank, world)
     if full is None:
-        if save_maps or pixel_metrics or aupro or map_image_score:
+        if save_maps or pixel_metrics or aupro or map_image_score or op is not None:
             _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, None, world, aupro,
-                         pro_fpr_limit, map_sigma, map_image_score, rank, scales, map_reduce)
+                         pro_fpr_limit, map_sigma, map_image_score, rank, op, None, scales, map_reduce)
         return {}
     best_ws, best_auc, best_j = sizes[0], -1.0, 0
     for j, ws in enumerate(sizes):
@@ -264,26 +321,42 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     out = dict(best_ws=best_ws, auc_ssim=M.roc_auc(y_true, 1.0 - full[:, best_j]), auc_mse=M.roc_auc(y_true, full[:, -2]),
                auc_psnr=M.roc_auc(y_true, -full[:, -1]), n_images=len(pairs), window_sizes=sizes)
     print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}")
-    if save_maps or pixel_metrics or aupro or map_image_score:
+    if save_maps or pixel_metrics or aupro or map_image_score or op is not None:
+        calib = None
+        if op is not None and op.fpr is not None and world == 1:      # the calibration images go the test images' way
+            calib = super_resolve_u8(model, [lr for lr, _ in op.calib], [h for _, h in op.calib], float(opt.rgb_range))
         out.update(_pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                                aupro, pro_fpr_limit, map_sigma, map_image_score, rank, scales, map_reduce))
+                                aupro, pro_fpr_limit, map_sigma, map_image_score, rank, op, calib, scales, map_reduce))
     return out
 
 
+def _make_maps(sr, hr, scales, map_reduce, ws, sigma, with_max):
+    """The anomaly maps of (sr, hr) u8 stacks the way the evaluator makes them, for the test images and the calibration images
+    alike: ``scales`` (non-empty) reduced by ``map_reduce``, else the one window size ``ws``; then smoothed when ``sigma`` > 0.
+    Returns (maps, per-image maxima or None without ``with_max``)."""
+    maps = M.anomaly_maps_multi(sr, hr, scales, map_reduce) if scales else M.anomaly_maps(sr, hr, ws)
+    if with_max:
+        return M.smooth_maps(maps, sigma, with_max=True)
+    return (M.smooth_maps(maps, sigma) if sigma > 0 else maps), None
+
+
 def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                 aupro=False, pro_fpr_limit=0.3, map_sigma=0.0, map_image_score=False, rank=0, map_scales=(), map_reduce='mean') -> dict:
+                 aupro=False, pro_fpr_limit=0.3, map_sigma=0.0, map_image_score=False, rank=0, op=None, calib=None,
+                 map_scales=(), map_reduce='mean') -> dict:
     """Anomaly maps of this rank's images, smoothed once when ``map_sigma`` > 0; the map-maximum image AUC on any number of
-    ranks; the pixel-level AUC and AU-PRO on a single rank.  ``best_ws`` is None off rank 0.  Every branch that leads to a
+    ranks; the pixel-level AUC, AU-PRO and the operating point (``op``, a checked ``OperatingPoint``; ``calib`` = the (sr, hr)
+    u8 stacks of its calibration pairs) on a single rank.  ``best_ws`` is None off rank 0.  Every branch that leads to a
     collective depends only on the flags and ``world``, which all ranks share, so all ranks make the same collective calls.
     ``map_scales`` (a resolved list) replaces the single window size: every rank knows it, so ``best_ws`` is not broadcast."""
     scored = pixel_metrics or aupro
+    single = scored or op is not None                         # what runs on one rank only
     if world > 1 and not (save_maps or map_image_score):      # the same branch on every rank: no collective below
-        if scored and best_ws is not None:
+        if single and best_ws is not None:
             print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
         return {}
     scales = [int(w) for w in map_scales]
+    ws = 0
     if scales:
-        maps = M.anomaly_maps_multi(sr, hr, scales, map_reduce)
         what, keys = f"scales={scales}, {map_reduce}", dict(map_scales=scales, map_reduce=map_reduce)
     else:
         ws = int(map_ws)
@@ -294,14 +367,9 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
                 box = [best_ws]
                 dist.broadcast_object_list(box, src=0)
                 ws = int(box[0])
-        maps = M.anomaly_maps(sr, hr, ws)
         what, keys = f"ws={ws}", dict(map_ws=ws)
     sigma = float(map_sigma)
-    img_max = None
-    if map_image_score:
-        maps, img_max = M.smooth_maps(maps, sigma, with_max=True)
-    elif sigma > 0:
-        maps = M.smooth_maps(maps, sigma)
+    maps, img_max = _make_maps(sr, hr, scales, map_reduce, ws, sigma, map_image_score)
     if save_maps and output_dir:
         save_anomaly_maps(maps, [names[i] if i < len(names) else f"{i:05d}" for i in mine],
                           ['good' if y_true[i] == 0 else 'bad' for i in mine], output_dir)
@@ -313,30 +381,59 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
             print(f"Image AUC - max of the SSIM map ({what}, sigma={sigma:g}): {out['auc_map_max']:.4f}")
     if sigma > 0 and out:
         out["map_sigma"] = sigma
-    if not scored or best_ws is None:
+    if not single or best_ws is None:
         return out
     if world > 1:
         print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
         return out
     lacking = [i for i in range(len(y_true)) if masks is None or i >= len(masks) or masks[i] is None]
-    if lacking:
+    if lacking and scored:
         print(f"Pixel metrics skipped: {len(lacking)} test image(s) have no ground-truth mask")
+    if lacking and op is None:
         return out
-    H, W = maps.shape[1:]
-    for i in mine:
-        if tuple(masks[i].shape) != (H, W):
-            raise ValueError(f"mask {i} has shape {tuple(masks[i].shape)}, the images are {H}x{W}")
-    labels = torch.from_numpy(np.stack([np.asarray(masks[i]) for i in mine])).to(maps.device)
+    labels = None
+    if not lacking:
+        H, W = maps.shape[1:]
+        for i in mine:
+            if tuple(masks[i].shape) != (H, W):
+                raise ValueError(f"mask {i} has shape {tuple(masks[i].shape)}, the images are {H}x{W}")
+        labels = torch.from_numpy(np.stack([np.asarray(masks[i]) for i in mine])).to(maps.device)
     out.update(keys)
     if sigma > 0:
         out["map_sigma"] = sigma
     tail = f", sigma={sigma:g}" if sigma > 0 else ""
-    if pixel_metrics:
+    if pixel_metrics and labels is not None:
         out["auc_pixel"] = M.pixel_roc_auc(maps, labels)
         print(f"Pixel AUC - SSIM map ({what}{tail}): {out['auc_pixel']:.4f}")
-    if aupro:
+    if aupro and labels is not None:
         out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, pro_fpr_limit), float(pro_fpr_limit)
         print(f"AU-PRO - SSIM map ({what}, fpr <= {float(pro_fpr_limit):g}{tail}): {out['aupro']:.4f}")
+    if op is not None:
+        if op.fpr is not None:
+            cmaps, cmax = _make_maps(calib[0], calib[1], scales, map_reduce, ws, sigma, op.level == 'image')
+            t, achieved = M.map_threshold(cmax if op.level == 'image' else cmaps, op.fpr)
+            out.update(threshold=t, threshold_source='fpr', threshold_fpr=float(op.fpr), threshold_level=op.level,
+                       calib_images=int(cmaps.shape[0]), calib_rate=achieved)
+            src = f"fpr {float(op.fpr):g} on {op.level}s of {cmaps.shape[0]} defect-free images, achieved {achieved:.6f}"
+        else:
+            t = float(op.threshold)
+            out.update(threshold=t, threshold_source='given')
+            src = "given"
+        out["min_region_area"] = int(op.min_area)
+        pred, img_pred, counts = M.operating_point(maps, t, labels, int(op.min_area))
+        st = M.operating_point_stats(counts if labels is not None else None, img_pred, [y_true[i] for i in mine])
+        out.update(st)
+        line = (f"Operating point - SSIM map ({what}{tail}), threshold={t:.9g} ({src}), min_area={int(op.min_area)}: "
+                f"image tp={st['image_tp']} fp={st['image_fp']} fn={st['image_fn']} tn={st['image_tn']} "
+                f"tpr={st['image_tpr']:.4f} fpr={st['image_fpr']:.4f}")
+        if labels is not None:
+            line += (f"; pixel tp={st['pixel_tp']} fp={st['pixel_fp']} fn={st['pixel_fn']} tn={st['pixel_tn']} "
+                     f"precision={st['precision']:.4f} recall={st['recall']:.4f} f1={st['f1']:.4f} iou={st['iou']:.4f} "
+                     f"fpr={st['fpr']:.6f} pro={st['pro_at_threshold']:.4f}")
+        print(line)
+        if op.save_masks and output_dir:
+            save_masks(pred, [names[i] if i < len(names) else f"{i:05d}" for i in mine],
+                       ['good' if y_true[i] == 0 else 'bad' for i in mine], output_dir)
     return out
 
 
@@ -368,6 +465,15 @@ def _run(args):
             resolve_map_scales(args.map_scales, int(resolution), int(resolution))
         except ValueError as e:
             raise SystemExit(f"--map-scales: {e}")
+    want_op = args.threshold is not None or args.threshold_fpr is not None
+    if args.threshold is not None and args.threshold_fpr is not None:
+        raise SystemExit("--threshold and --threshold-fpr exclude each other")
+    if args.threshold_fpr is not None:                        # before the model is loaded
+        data_root = args.data_root if args.data_root != 'auto' else f"data/mvtec_{resolution}"
+        val_dir = val_good_dir(data_root, class_name)
+        if not any((val_dir / 'HR').glob('*.png')):
+            raise SystemExit(f"--threshold-fpr calibrates on defect-free images, and there is none under {val_dir} "
+                             f"(HR/*.png with LR_<scale> beside it, as prepare_mvtec_data writes the validation split)")
     ckpt = resolve_checkpoint(args)
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     if world > 1:
@@ -382,17 +488,25 @@ def _run(args):
     b = list(iter_split(opt.data_root, class_name, 'bad', opt.scale, opt.n_colors))
     out_dir = args.output_dir or (os.path.join(args.run_dir, 'eval_results') if args.run_dir else './workspace/eval_results')
     masks = None
-    if (args.pixel_metrics or args.aupro) and world == 1:
+    if (args.pixel_metrics or args.aupro or want_op) and world == 1:
         masks, missing = load_masks(opt.data_root, class_name, [('good', n) for n, _, _ in g] + [('bad', n) for n, _, _ in b],
                                     [hr.shape[:2] for _, _, hr in g + b])
         if missing:
             print(f"No ground-truth mask for {len(missing)} bad image(s) under test/bad/GT (prepare_mvtec_data --with-masks), "
                   f"e.g. {missing[0]}")
+    op = None
+    if want_op:
+        calib = []
+        if args.threshold_fpr is not None and world == 1:     # more ranks skip the operating point: nothing to read
+            calib = [(lr, hr) for _, lr, hr in iter_split(opt.data_root, class_name, 'good', opt.scale, opt.n_colors, part='val')]
+        op = OperatingPoint(threshold=args.threshold, fpr=args.threshold_fpr, level=args.threshold_level,
+                            min_area=args.min_region_area, save_masks=args.save_masks, calib=calib)
     out = evaluate_on_test(opt, model, [(lr, hr) for _, lr, hr in g], [(lr, hr) for _, lr, hr in b], rank, world,
                            names=[n for n, _, _ in g] + [n for n, _, _ in b], output_dir=out_dir, save_images=args.save_images,
                            masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws,
                            aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit, map_sigma=args.map_sigma,
-                           map_image_score=args.map_image_score, map_scales=args.map_scales, map_reduce=args.map_reduce)
+                           map_image_score=args.map_image_score, map_scales=args.map_scales, map_reduce=args.map_reduce,
+                           operating_point=op)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

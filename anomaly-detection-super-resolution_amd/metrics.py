@@ -257,6 +257,132 @@ def aupro(scores: torch.Tensor, masks: torch.Tensor, fpr_limit: float = 0.3) -> 
     return _pixel_pro(scores, masks, fpr_limit, curve=False)
 
 
+def rank_for_rate(n: int, rate: float) -> int:
+    """The ascending rank (0-based) whose value is the threshold of ``n`` calibration values at false-positive rate ``rate``
+    (DESIGN.md "Operating point"): ``m = floor(rate * n)`` in Python doubles, clipped to [0, n - 1], and ``k = n - 1 - m``, so at
+    most ``m`` values lie strictly above the value of rank ``k`` whatever the ties.  Host only.  ValueError for n < 1 and for a
+    rate outside (0, 1) (NaN included)."""
+    n, rate = int(n), float(rate)
+    if n < 1:
+        raise ValueError(f"rank_for_rate: n = {n}, must be >= 1")
+    if not 0.0 < rate < 1.0:
+        raise ValueError(f"rank_for_rate: rate = {rate}, must be in (0, 1)")
+    m = min(max(int(np.floor(rate * n)), 0), n - 1)
+    return n - 1 - m
+
+
+def select_kth(values: torch.Tensor, k: int) -> Tuple[float, int, int]:
+    """The value of ascending rank ``k`` (0-based) of a float32 GPU tensor of any shape, exactly (``np.sort(v.ravel())[k]``; a
+    zero comes back as +0.0), by a radix select that neither sorts nor copies the values: (value, values below it, values equal
+    to it).  ValueError for an empty tensor, 2^31 values or more, a rank outside [0, n), and a NaN among the values."""
+    _need_cuda(values)
+    v = values.detach().reshape(-1)
+    if v.dtype != torch.float32:
+        raise ValueError(f"select_kth takes float32 values, got {v.dtype}")
+    v = v.contiguous()
+    n, k = v.numel(), int(k)
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"select_kth of {n} values: 1 to 2^31 - 1 are supported")
+    if not 0 <= k < n:
+        raise ValueError(f"select_kth: rank k = {k}, must be in [0, {n})")
+    value = torch.empty((), dtype=torch.float32, device=v.device)
+    counts = torch.empty(3, dtype=torch.int64, device=v.device)          # u64 on the device; the values stay below 2^31
+    _call_with_ws("select_kth_workspace_bytes", (C.c_int64(n),), "select_kth",
+                  (L.dptr(v), C.c_int64(n), C.c_int64(k), L.dptr(value), L.dptr(counts)), v.device)
+    n_nan, n_below, n_equal = counts.tolist()
+    if n_nan:
+        raise ValueError(f"select_kth: {n_nan} of {n} values are NaN")
+    return float(value.item()), n_below, n_equal
+
+
+def map_threshold(values: torch.Tensor, rate: float) -> Tuple[float, float]:
+    """The threshold that calibration ``values`` (float32 on the GPU: all pixels of defect-free maps, or their per-image maxima)
+    give at false-positive rate ``rate``: the value of rank ``rank_for_rate(n, rate)``, always one of the values, nothing
+    interpolated.  Returns (threshold, achieved rate = the share of the values strictly above it, <= rate).  ValueError as
+    ``rank_for_rate`` and ``select_kth``."""
+    _need_cuda(values)
+    n = values.numel()
+    if n < 1:
+        raise ValueError("map_threshold of no values")
+    t, n_below, n_equal = select_kth(values, rank_for_rate(n, rate))
+    return t, (n - n_below - n_equal) / n
+
+
+OPERATING_POINT_COUNTS = ("tp", "fp", "fn", "tn", "n_nan", "n_regions", "pro_hi", "pro_lo")   # srad_operating_point's counts_out
+
+
+def operating_point(maps: torch.Tensor, threshold: float, masks: Optional[torch.Tensor] = None, min_area: int = 1
+                    ) -> Tuple[torch.Tensor, torch.Tensor, dict]:
+    """The prediction of float32 anomaly maps [n,H,W] on the GPU at ``threshold`` and its counts (DESIGN.md "Operating point"):
+    a pixel is predicted iff ``map > threshold`` (the comparison of the float32 map values with the Python float, exactly); with ``min_area`` > 1 the 8-connected components (per image, as
+    ``mask_regions``) of fewer than ``min_area`` predicted pixels are removed.  ``masks``: ground truth of the same shape (any
+    integer or bool dtype, nonzero = defect), or None = every pixel ok.  Returns (pred: uint8 [n,H,W] in {0, 1}; img_pred:
+    int32 [n], the surviving predicted pixels of each image; counts: Python ints under ``OPERATING_POINT_COUNTS``, with
+    ``pro_hi * 2^64 + pro_lo`` = the sum over predicted defect pixels of ``floor(2^64 / |region|)``).  ValueError for a NaN
+    threshold, ``min_area`` < 1, a shape mismatch and a NaN in the maps."""
+    t, area = float(threshold), int(min_area)
+    if t != t:
+        raise ValueError("operating_point: the threshold is NaN")
+    if area < 1 or area != min_area:
+        raise ValueError(f"operating_point: min_area = {min_area}, must be an integer >= 1")
+    with np.errstate(over="ignore"):
+        tf = np.float32(t)
+    if float(tf) > t:                                         # the largest float32 <= t: for float32 maps, map > tf iff map > t
+        tf = np.nextafter(tf, np.float32(-np.inf))
+    _need_cuda(maps)
+    s = maps.detach()
+    if s.dim() == 2:
+        s = s[None]
+    if s.dim() != 3 or s.numel() == 0 or s.dtype != torch.float32:
+        raise ValueError(f"operating_point takes a non-empty float32 [n, H, W] tensor, got {s.dtype} {tuple(maps.shape)}")
+    s = s.contiguous()
+    m = None
+    if masks is not None:
+        m = _mask_stack(masks)
+        if tuple(m.shape) != tuple(s.shape):
+            raise ValueError(f"maps {tuple(maps.shape)} and masks {tuple(masks.shape)} must have the same shape")
+    n, H, W = s.shape
+    dev = s.device
+    pred = torch.empty(n, H, W, dtype=torch.uint8, device=dev)
+    img_pred = torch.empty(n, dtype=torch.int32, device=dev)            # u32 on the device; at most H x W < 2^31
+    counts = torch.empty(8, dtype=torch.int64, device=dev)              # u64 on the device
+    _call_with_ws("operating_point_workspace_bytes", (n, H, W), "operating_point",
+                  (L.dptr(s), L.dptr(m), n, H, W, C.c_float(float(tf)), min(area, 2 ** 31 - 1), L.dptr(pred), L.dptr(img_pred),
+                   L.dptr(counts)), dev)
+    out = {k: int(v) & (2 ** 64 - 1) for k, v in zip(OPERATING_POINT_COUNTS, counts.tolist())}      # pro_lo uses all 64 bits
+    if out["n_nan"]:
+        raise ValueError(f"operating_point: {out['n_nan']} of {s.numel()} map values are NaN")
+    return pred, img_pred, out
+
+
+def _ratio(a: int, b: int) -> float:
+    return a / b if b else 0.0
+
+
+def operating_point_stats(counts: Optional[dict], img_pred, y_true: Sequence[int]) -> dict:
+    """The report of an operating point (host only).  Image level, from ``img_pred`` (surviving predicted pixels per image; an
+    image is flagged iff it has one) and the labels ``y_true`` (nonzero = defective): ``image_tp/fp/fn/tn``, ``image_tpr``,
+    ``image_fpr``.  Pixel level, when ``counts`` (of ``operating_point`` with masks) is given: ``pixel_tp/fp/fn/tn``,
+    ``precision``, ``recall``, ``f1``, ``iou``, ``fpr`` and ``pro_at_threshold`` = (1/R) sum over predicted defect pixels of
+    1/|region|.  A ratio with a zero denominator is 0.0.  ValueError when the lengths differ."""
+    flagged = [int(v) > 0 for v in (img_pred.tolist() if hasattr(img_pred, "tolist") else img_pred)]
+    y = [int(v) != 0 for v in y_true]
+    if len(flagged) != len(y):
+        raise ValueError(f"operating_point_stats: {len(flagged)} images, {len(y)} labels")
+    tp = sum(f and d for f, d in zip(flagged, y))
+    fp = sum(f and not d for f, d in zip(flagged, y))
+    fn = sum(d and not f for f, d in zip(flagged, y))
+    tn = len(y) - tp - fp - fn
+    out = dict(image_tp=tp, image_fp=fp, image_fn=fn, image_tn=tn, image_tpr=_ratio(tp, tp + fn), image_fpr=_ratio(fp, fp + tn))
+    if counts is not None:
+        tp, fp, fn, tn = (int(counts[k]) for k in ("tp", "fp", "fn", "tn"))
+        num = (int(counts["pro_hi"]) << 64) + int(counts["pro_lo"])
+        out.update(pixel_tp=tp, pixel_fp=fp, pixel_fn=fn, pixel_tn=tn, precision=_ratio(tp, tp + fp), recall=_ratio(tp, tp + fn),
+                   f1=_ratio(2 * tp, 2 * tp + fp + fn), iou=_ratio(tp, tp + fp + fn), fpr=_ratio(fp, fp + tn),
+                   pro_at_threshold=_ratio(num, int(counts["n_regions"]) << 64))
+    return out
+
+
 def gaussian_weights(sigma: float, truncate: float = 4.0) -> np.ndarray:
     """The half ``[r:]`` of ``scipy.ndimage._filters._gaussian_kernel1d(sigma, 0, r)`` with ``r = int(truncate * sigma + 0.5)``:
     float64 [r + 1], the centre weight first.  Computed here, with numpy's exp, so that the device filter uses scipy's weights

@@ -207,6 +207,30 @@ def _nonnegative_float(text: str) -> float:
     return v
 
 
+def _open_unit_float(text: str) -> float:
+    v = float(text)
+    if not 0.0 < v < 1.0:                                     # NaN too
+        raise argparse.ArgumentTypeError(f"{text} is not a rate in (0, 1)")
+    return v
+
+
+def _finite_or_inf_float(text: str) -> float:
+    v = float(text)
+    if v != v:
+        raise argparse.ArgumentTypeError("a threshold cannot be NaN")
+    return v
+
+
+def _positive_int(text: str) -> int:
+    try:
+        v = int(text)
+    except ValueError:
+        v = 0
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"{text!r} is not an integer >= 1")
+    return v
+
+
 def _map_scales(text: str):
     """--map-scales: 'sweep', or a comma-separated list of positive integers (the list; '' = none)."""
     text = text.strip()
@@ -266,8 +290,22 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                         "size of the image-level sweep, combined per pixel with --map-reduce; replaces --map-ws")
     p.add_argument('--map-reduce', type=str, default='mean', choices=['mean', 'max'],
                    help="how --map-scales combines the maps of its window sizes")
+    p.add_argument('--threshold', type=_finite_or_inf_float, default=None, metavar='VALUE',
+                   help="operating point: a pixel is predicted defective iff its anomaly-map value is > VALUE; reports the "
+                        "image-level (and, with test/bad/GT masks, pixel-level) counts at it (needs --gpus 1)")
+    p.add_argument('--threshold-fpr', type=_open_unit_float, default=None, metavar='RATE',
+                   help="operating point at the threshold that the defect-free images of <class>/val/good give at this "
+                        "false-positive rate, in (0, 1); excludes --threshold")
+    p.add_argument('--threshold-level', type=str, default='pixel', choices=['pixel', 'image'],
+                   help="what --threshold-fpr calibrates on: every pixel of the val/good maps, or each map's maximum")
+    p.add_argument('--min-region-area', type=_positive_int, default=1, metavar='A',
+                   help="remove predicted 8-connected components of fewer than A pixels (1 = keep all)")
+    p.add_argument('--save-masks', action='store_true', default=False,
+                   help="write the predicted masks (0 / 255) as <output-dir>/anomaly_masks/{good,bad}/<name>.png")
     _with_config(p, pre_args)
     args = p.parse_args(argv)
+    if args.threshold is not None and args.threshold_fpr is not None:
+        p.error("--threshold and --threshold-fpr exclude each other (a given threshold or a calibrated one)")
     if isinstance(args.map_scales, (list, tuple)):            # a list from a config file gets the command line's check
         try:
             args.map_scales = _map_scales(','.join(str(v) for v in args.map_scales))

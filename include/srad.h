@@ -249,6 +249,36 @@ int srad_pixel_pro_workspace_bytes(int n_img, int H, int W, size_t* bytes);
 int srad_pixel_pro(const float* scores, const uint8_t* masks, int n_img, int H, int W, double fpr_limit, uint64_t* counts_out,
                    double* aupro_out, double* curve_fpr, double* curve_pro, int64_t curve_cap, void* workspace,
                    size_t workspace_bytes, void* stream);
+/* The value of ascending rank k (0-based) of `n` DEVICE float32 scores, 1 <= n < 2^31, 0 <= k < n: an exact radix select over
+ * the order-preserving key of a float (-0.0 == +0.0, and a zero is returned as +0.0; NaN sorts last).  Three histogram passes
+ * over the scores (11 / 11 / 10 key bits, each restricted to the prefix chosen so far); nothing is sorted or moved and the
+ * workspace does not grow with n.  The result is always one of the scores.
+ *   *value_out (DEVICE float) = the score of rank k (NaN when rank k falls among the NaN);
+ *   counts_out (DEVICE, 3 x u64) = {n_nan, n_below, n_equal}: scores below and equal to the value, so that
+ *   n_above = n - n_nan - n_below - n_equal (n_equal = 0 when the value is NaN).
+ * Integer counts only: the same bits on every call.  Stream-ordered, no host sync, no allocation; workspace >=
+ * srad_select_kth_workspace_bytes (about 25 KB whatever n). */
+int srad_select_kth_workspace_bytes(int64_t n, size_t* bytes);
+int srad_select_kth(const float* scores, int64_t n, int64_t k, float* value_out, uint64_t* counts_out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* The operating point of DEVICE float32 scores [n_img, H, W] at `threshold` (DESIGN.md "Operating point"): a pixel is predicted
+ * defective iff score > threshold, strictly (never for a NaN score); with min_area > 1 every 8-connected component of an
+ * image's predicted set (the connectivity of srad_mask_regions) of fewer than min_area pixels is then removed.  masks: DEVICE
+ * u8 of the same shape (nonzero = defect), or NULL = no defect anywhere.
+ *   pred_out (DEVICE u8 [n_img, H, W]) = 1 where a predicted pixel survives, else 0;
+ *   img_pred_out (DEVICE u32 [n_img]) = surviving predicted pixels of each image;
+ *   counts_out (DEVICE, 8 x u64) = {tp, fp, fn, tn, n_nan, n_regions, pro_hi, pro_lo}: the pixel confusion counts (a pixel with
+ *   a NaN score is in n_nan and in no other count), the regions of the masks (0 without masks), and the 128-bit fixed-point
+ *   numerator pro_hi * 2^64 + pro_lo = sum over predicted defect pixels of floor(2^64 / |region of the pixel|), the same sum
+ *   srad_pixel_pro carries: pro = numerator / 2^64 / n_regions.
+ * A NaN threshold and min_area < 1 are refused; +-infinity and min_area > H x W are valid.  Launches: threshold; (min_area > 1)
+ * srad_mask_regions on the prediction, drop small components; (masks) srad_mask_regions on the masks; count per block; final
+ * reduce.  Integer sums only.  Stream-ordered, no host sync, no allocation; workspace >= srad_operating_point_workspace_bytes
+ * (about 8 bytes per pixel). */
+int srad_operating_point_workspace_bytes(int n_img, int H, int W, size_t* bytes);
+int srad_operating_point(const float* scores, const uint8_t* masks, int n_img, int H, int W, float threshold, int min_area,
+                         uint8_t* pred_out, uint32_t* img_pred_out, uint64_t* counts_out, void* workspace, size_t workspace_bytes,
+                         void* stream);
 /* Gaussian smoothing of DEVICE float32 maps [n_img, H, W] (n_img x H x W < 2^31) with a symmetric separable filter of radius
  * `radius` in [0, 128], radius <= min(H, W) (one half-sample reflection, d c b a | a b c d, at every edge).  weights_host: HOST
  * array of radius + 1 doubles, w[0] the centre and w[j] the weight at offsets +-j.  Given scipy's weights the result equals
