@@ -344,7 +344,7 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
   int blk_count = 0;
   // a flush that a reservation makes in the middle of a block reduces column sums the caller's stream wrote: it goes there even
   // when the reservation is a deferred layer's (whose own launch, on the side stream, comes after side_waits_main)
-  wq.own_flush_stream = true; wq.flush_stream = s;
+  wgrad_queue_flush_on(wq, s);
   h->ts.wgrad_block_peak = 0;
 
   // dLoss/d(outn) = dy / img_range, NCHW -> NHWC (pad channels zero)           (drct.py:897)
@@ -425,7 +425,7 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
       }
       const int set = blk_count & 1;                       // temporaries + partial workspace of this block
       SRAD_TRY(bs.main_waits_set(set));                   // block n - 2 fully consumed
-      wq.ws = wq_base + (size_t)set * wq_half; wq.ws_floats = wq_half; wq.peak = 0;
+      SRAD_TRY(srad_wgrad_rebind(wq, "drct_backward", wq_base + (size_t)set * wq_half, wq_half));   // peak restarts: it is per block
       float *dx2 = w.dx2[set], *dx1 = w.dx1[set], *dh = w.dh[set], *dqkv = w.dqkv[set];
       // with the adjust prologue fused the dx2 buffer only holds the bf16 copy (its first half): dx1 * rs1 as bf16 goes behind it
       const bool yh_dx1 = yh_dx2 && fuse_proj;
@@ -564,7 +564,7 @@ int srad_drct_backward(srad_drct_t* h, const float* dy, int B, int H, int W, con
     float* t = gn; gn = gc; gc = t;
     if (on_bucket) on_bucket(user, c.n_rdg - i);
   }
-  wq.ws = wq_base; wq.ws_floats = 2 * wq_half;           // the remaining layers run on the caller's stream only
+  SRAD_TRY(srad_wgrad_rebind(wq, "drct_backward", wq_base, 2 * wq_half));           // the remaining layers run on the caller's stream only
   {  // patch_embed.norm, joined by the long skip of conv_after_body(...) + x      (drct.py:873, 893)
     LnBwdParams l{};
     l.dxn = gn; l.ld_dxn = D; l.x = w.feat0; l.ldx = E; l.gamma = h->pt.fptr(h->pe_g);

@@ -1429,7 +1429,7 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
       }
       // both weight gradients of the block + their reduce on the side stream (dr and dt exist now)
       SRAD_TRY(bs.side_waits_main());
-      wq.ws = wq_base + (size_t)set * wq_half; wq.ws_floats = wq_half;
+      SRAD_TRY(srad_wgrad_rebind(wq, "drn_backward", wq_base + (size_t)set * wq_half, wq_half));
       // the channel attention's weight / bias gradients (one workgroup, all images): nothing on the data path waits for them
       hipLaunchKernelGGL(ca_bwd_kernel, dim3(1), dim3(256), 0, side, pp, DRN_POOL_CHUNKS, sv.pool, sv.gate, 1.0f / (float)(Hl * Wl), B,
                          ch, ch / 16, h->pt.fptr(r.w1), h->pt.fptr(r.b1), h->pt.fptr(r.w2), G + h->ts.flat_off[r.w1],
@@ -1457,7 +1457,7 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
       ++blk_count;
     }
     SRAD_TRY(bs.main_waits_side());                         // the chain's weight gradients are final on the caller's stream
-    wq.ws = wq_base; wq.ws_floats = 2 * wq_half;
+    SRAD_TRY(srad_wgrad_rebind(wq, "drn_backward", wq_base, 2 * wq_half));
     // gradient of the chain's input: deep (idx 0) or the concat buffer of this level
     float* GX = idx == 0 ? w.gdeep : w.gcat[lvl];
     hipLaunchKernelGGL(add_cols_kernel, dim3(grid1d(T * ch / 4)), dim3(256), 0, s, ga, ch, GX, ch, T, ch);
@@ -1541,9 +1541,7 @@ int srad_dual_backward(const float* w0, const float* w1, int C, int n_feats, flo
   void* p0 = bp.take(pk);     // w0 forward   [F][C]
   void* p1t = bp.take(pk);    // w1 transposed (rows F, K = C)
   void* p0t = bp.take(pk);    // w0 transposed (rows C, K = F)
-  WgradQueue wq;
-  wq.ws = bp.take(SRAD_WGRAD_WS_BYTES / 4);
-  wq.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue wq = wgrad_queue_on(bp.take(SRAD_WGRAD_WS_BYTES / 4), SRAD_WGRAD_WS_BYTES / sizeof(float));
   const float zero3[3] = {0.f, 0.f, 0.f};
   SRAD_TRY(srad_launch_nchw_to_nhwc(x, xin, B, C, SRAD_IMG_CPAD, H, W, zero3, 1.0f, s));
   SRAD_TRY(srad_launch_nchw_to_nhwc(dy, dyn, B, C, SRAD_IMG_CPAD, H2, W2, zero3, 1.0f, s));

@@ -329,9 +329,7 @@ int srad_op_wgrad(int precision, const float* dy, int ldy, const float* x, int l
   p.dY = dy; p.ldy = ldy; p.X = x; p.ldx = ldx; p.M = B * p.Ho * p.Wo;
   p.N = N; p.Cin = Cin; p.n_real = N; p.cin_real = Cin; p.ntaps = ntaps;
   p.row_scale = row_scale; p.rps = p.Ho * p.Wo; p.alpha = alpha; p.dW = dw; p.db = db;
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   SRAD_TRY(srad_launch_wgrad(precision, p, q, reinterpret_cast<hipStream_t>(stream)));
   return srad_wgrad_flush(q, reinterpret_cast<hipStream_t>(stream));
 }
@@ -348,9 +346,7 @@ int srad_op_wgrad_conv9_h(const void* dy_h, const void* x, int x_bf16, int B, in
   p.X = reinterpret_cast<const float*>(x); p.ldx = 80; p.x_bf16 = x_bf16 ? 1 : 0;
   p.M = B * H * W; p.N = p.Cin = p.n_real = p.cin_real = 80; p.ntaps = 9; p.alpha = 1.f; p.dW = dw; p.db = db;
   SRAD_REQUIRE(srad_wgrad_conv9_supported(p), "op_wgrad_conv9_h: this shape does not take the nine-tap kernel");
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   SRAD_TRY(srad_launch_wgrad(SRAD_PREC_BF16, p, q, reinterpret_cast<hipStream_t>(stream)));
   return srad_wgrad_flush(q, reinterpret_cast<hipStream_t>(stream));
 }
@@ -365,9 +361,7 @@ int srad_op_wgrad_deferred(int precision, const void* dy, int ldy, int dy_bf16, 
   p.dY = reinterpret_cast<const float*>(dy); p.ldy = ldy; p.X = reinterpret_cast<const float*>(x); p.ldx = ldx; p.M = M;
   p.N = N; p.Cin = Cin; p.n_real = N; p.cin_real = Cin; p.ntaps = 1; p.stride = 1;
   p.row_scale = row_scale; p.rps = rps; p.alpha = alpha; p.dW = dw; p.db = db; p.x_bf16 = x_bf16; p.dy_bf16 = dy_bf16;
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   SRAD_TRY(srad_launch_wgrad_deferred(precision, p, q, s));
   SRAD_TRY(srad_wgrad_launch_deferred(precision, q, s));
@@ -399,9 +393,7 @@ int srad_op_wgrad_queue_script(int precision, const srad_wq_step* steps, int nst
     }
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = budget_floats;
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), budget_floats);
   auto F = [](const void* v) { return reinterpret_cast<const float*>(v); };
   auto W = [](const void* v) { return const_cast<float*>(reinterpret_cast<const float*>(v)); };
   for (int i = 0; i < nsteps; ++i) {
@@ -460,9 +452,7 @@ int srad_bench_wgrad_block(int M, int d, int hidden, int KA, int storage, const 
   SRAD_REQUIRE(xbuf && ybuf && dw && workspace && M > 0 && iters > 0, "bench_wgrad_block: bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int N[5] = {3 * d, d, hidden, d, KA}, C[5] = {d, d, d, hidden, d};
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   for (int it = 0; it < iters; ++it) {
     float* w = dw;
     for (int l = 0; l < 5; ++l) {
@@ -503,9 +493,7 @@ int srad_op_layernorm_bwd(const float* dxn, const float* x, int ldx, const float
   LnBwdParams l{};
   l.dxn = dxn; l.ld_dxn = C; l.x = x; l.ldx = ldx; l.gamma = gamma; l.dres = dres; l.ld_dres = C;
   l.out = out; l.ld_out = C; l.accumulate = accumulate; l.dgamma = dgamma; l.dbeta = dbeta; l.rows = rows; l.C = C; l.eps = 1e-5f;
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   SRAD_TRY(srad_launch_ln_bwd(l, q, reinterpret_cast<hipStream_t>(stream)));
   return srad_wgrad_flush(q, reinterpret_cast<hipStream_t>(stream));
 }
@@ -514,9 +502,7 @@ int srad_op_window_attn_bwd(int precision, const float* qkv, const float* dout, 
                             int B, int H, int W, int ws, int shift, int d, int heads, int hdp, void* workspace, void* stream) {
   SRAD_REQUIRE(qkv && dout && dqkv && table && dtable && workspace, "op_window_attn_bwd: null argument");
   AttnBwdParams a{qkv, dout, dqkv, nullptr, table, dtable, B, H, W, ws, shift, d, heads, hdp};
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   SRAD_TRY(srad_launch_window_attn_bwd(precision, a, q, reinterpret_cast<hipStream_t>(stream)));
   return srad_wgrad_flush(q, reinterpret_cast<hipStream_t>(stream));
 }
@@ -529,9 +515,7 @@ int srad_op_window_attn_bwd_h(const void* qkv_h, const void* dout_h, void* dqkv_
   AttnBwdParams a{nullptr, nullptr, nullptr, reinterpret_cast<__bf16*>(dqkv_h), table, dtable, B, H, W, ws, shift, d, heads,
                   srad_round_up(d / (heads > 0 ? heads : 1), 4)};
   a.qkv_h = reinterpret_cast<const __bf16*>(qkv_h); a.dout_h = reinterpret_cast<const __bf16*>(dout_h); a.hp_h = hp;
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   SRAD_TRY(srad_launch_window_attn_bwd(SRAD_PREC_BF16, a, q, reinterpret_cast<hipStream_t>(stream)));
   return srad_wgrad_flush(q, reinterpret_cast<hipStream_t>(stream));
 }
@@ -570,9 +554,7 @@ int srad_op_mlp_bwd(int M, int d, int m, float* dx2, const float* hpre, const fl
     p.KA = KA; p.dA = dA; p.ld_dA = ld_dA; p.y_act = y_act; p.ld_y = ld_y; p.slope = slope; p.aalpha = aalpha; p.dA_out = dA_out;
     p.w_adjt = sp; SRAD_TRY(srad_launch_pack_weight_frag_t(w_adj, sp, KA, d, s));
   }
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   SRAD_TRY(srad_launch_mlp_bwd(p, q, s));
   return srad_wgrad_flush(q, s);
 }
@@ -589,9 +571,7 @@ int srad_op_lin_ln_bwd(int M, int K, int d, const float* dY, const float* w, con
   LinLnBwdParams p{};
   p.M = M; p.K = K; p.d = d; p.dY = dY; p.ld_dy = K; p.w_t = scratch; p.x = x; p.ldx = ldx; p.ln_g = gamma;
   p.dres = dres; p.ld_dres = d; p.out = out; p.ld_out = ld_out; p.accumulate = accumulate; p.dgamma = dgamma; p.dbeta = dbeta;
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(workspace);
-  q.ws_floats = SRAD_WGRAD_WS_BYTES / sizeof(float);
+  WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   SRAD_TRY(srad_launch_lin_ln_bwd(p, q, s));
   return srad_wgrad_flush(q, s);
 }

@@ -336,11 +336,8 @@ int srad_launch_ln_qkv(const LnQkvParams& p, hipStream_t stream);
 int srad_launch_qkv_attn(const QkvAttnParams& p, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
-// Backward kernels (kernels_bwd.hip) - the training path of reference src/trainer.py:152-222.
+// Backward kernels (kernels_wgrad.hip, kernels_bwd.hip) - the training path of reference src/trainer.py:152-222.
 // ------------------------------------------------------------------------------------------
-// Weight gradient of a Linear / conv layer, accumulated (+=) into the PyTorch-layout fp32 tensor:
-//   dW[n][c][tap] += alpha * sum_m rs(m) * dY[m][ycol0 + n] * A(m, tap, c),   db[n] += alpha * sum_m rs(m) * dY[m][ycol0 + n]
-// with A the forward's row gather (identity for Linear, the 3x3 / strided window for convs).
 // stored input channel c of a layer whose input is `grp_pad`-wide groups with `grp_real` real channels each -> the real
 // channel index, or `none` for a pad column (grp_pad == 0: the identity)
 __host__ __device__ inline int srad_real_channel(int c, int grp_real, int grp_pad, int none) {
@@ -349,61 +346,18 @@ __host__ __device__ inline int srad_real_channel(int c, int grp_real, int grp_pa
   return r < grp_real ? g * grp_real + r : none;
 }
 
-struct WgradParams {
-  const float* dY; int ldy, ycol0;
-  const float* X; int ldx;
-  int M, N, Cin, ntaps;        // N, Cin: padded to multiples of 4 as stored in dY / X
-  int n_real, cin_real;        // extents of dW (columns/rows beyond are padding and never written)
-  int grp_real, grp_pad;       // grp_pad > 0: X's channels are groups of grp_pad holding grp_real real ones each (DRN x8 level 0)
-  int Hi, Wi, Ho, Wo, stride;  // conv geometry (M = B*Ho*Wo); ignored for ntaps == 1 && stride == 1
-  const float* row_scale; int rps;
-  float alpha;
-  float* dW;                   // [n_real][cin_real][ntaps]
-  float* db;                   // [n_real] or null
-  int x_bf16, dy_bf16;         // operand storage: 1 = the pointer is a __bf16 array (ld in elements); Linear layers on the
-                               // mask-free (FULL) bf16 path only.  A bf16 dY is already multiplied by its DropPath factor.
-};
-// Split-K bookkeeping: srad_launch_wgrad() writes partial tiles into `ws` and queues the layer; srad_wgrad_flush()
-// sums the queued layers into their dW / db with one launch (automatic when the batch or `ws` is full).
-// A queue lives on the host for the duration of one backward pass; flush before anyone reads the gradients.
-#define SRAD_WGRAD_BATCH 12
-struct WgradReduceItem {
-  float* dW; float* db; const float* part;
-  int n_real, cin_real, ntaps, tn, tc, ksplit, tile0;
-  int grp_real, grp_pad;         // as WgradParams
-  float alpha;
-  int wc;                        // C > 0: one C x C partial tile per tap (wgrad80_kernel, wgrad_conv9_kernel), row-major + C bias sums;
-                                 // then tn = reduce tiles per tap, tc = float4 per reduce workgroup
-};
-struct WgradReduceBatch { WgradReduceItem it[SRAD_WGRAD_BATCH]; int count; };
-#define SRAD_WGRAD_MULTI 5
-struct WgradMulti {                            // Linear layers whose weight-gradient kernels go out as one launch
-  WgradParams p[SRAD_WGRAD_MULTI];
-  float* part[SRAD_WGRAD_MULTI];
-  int ksplit[SRAD_WGRAD_MULTI], tn[SRAD_WGRAD_MULTI], tc[SRAD_WGRAD_MULTI], blk0[SRAD_WGRAD_MULTI], nblk[SRAD_WGRAD_MULTI];
-  int count;
-};
-// why a reduce launch happened (include/srad.h SRAD_WQ_FLUSH_*): asked for, or made by a reservation that found the batch /
-// the workspace full.  Host bookkeeping only: what a test asserts to know which path it exercised.
-enum { SRAD_WGRAD_FLUSH_EXPLICIT = 0, SRAD_WGRAD_FLUSH_BATCH = 1, SRAD_WGRAD_FLUSH_WS = 2 };
-#define SRAD_WGRAD_LOG 64
-struct WgradFlushLog { int count = 0; int by_why[3] = {0, 0, 0}; unsigned char why[SRAD_WGRAD_LOG] = {}; };   // the first SRAD_WGRAD_LOG reasons in order
-struct WgradQueue {
-  float* ws = nullptr; size_t ws_floats = 0;   // caller-owned device workspace, 16-byte aligned
-  size_t used = 0; int tiles = 0;
-  WgradReduceBatch batch{};
-  WgradMulti multi{};
-  double multi_flops = 0, multi_bytes = 0;
-  // A deferred layer is PENDING from srad_launch_wgrad_deferred until srad_wgrad_launch_deferred writes its partials: a flush
-  // in between reduces only the other items and keeps the pending layers' items and regions (multi_need: floats at multi.part).
-  size_t multi_need[SRAD_WGRAD_MULTI] = {};
-  size_t gap_lo = 0, gap_end = 0;              // [gap_lo, gap_end) minus the pending regions: free space such a flush left below `used`
-  // Stream that writes the partials of everything but the deferred layers.  Set by a caller that sends the deferred layers to
-  // another stream: a flush a reservation makes while layers are pending then goes here, whichever stream the call names.
-  bool own_flush_stream = false; hipStream_t flush_stream = nullptr;
-  size_t peak = 0;                             // highest end of a region handed out so far (floats)
-  WgradFlushLog log{};
-};
+// Split-K bookkeeping (wgrad_queue.h: WgradParams, WgradQueue and every decision the queue makes; kernels_wgrad.hip: the
+// launches): srad_launch_wgrad() writes partial tiles into the queue's workspace and queues the layer; srad_wgrad_flush()
+// sums the queued layers into their dW / db with one launch (automatic when the batch or the workspace is full).
+// A queue is built with wgrad_queue_on(ws, floats) and moved with srad_wgrad_rebind; nobody else writes its fields.
+#include "wgrad_queue.h"
+// moves an empty queue to another workspace; anything queued, pending or reserved is an error naming `who`
+static inline int srad_wgrad_rebind(WgradQueue& q, const char* who, float* ws, size_t floats) {
+  if (wgrad_queue_rebind(q, ws, floats))
+    return srad_set_error(SRAD_ERR_STATE, "%s: the split-K queue cannot move to another workspace with items queued, layers pending or "
+                          "a region reserved (%d items, %d layers, %zu floats)", who, q.batch.count, q.multi.count, q.used);
+  return SRAD_OK;
+}
 // queue a Linear layer's weight gradient without launching; srad_wgrad_launch_deferred sends all queued ones as one
 // launch (call it before srad_wgrad_flush, which only sums partials that have been written)
 int srad_launch_wgrad_deferred(int prec, const WgradParams& p, WgradQueue& q, hipStream_t stream);
@@ -411,9 +365,10 @@ int srad_wgrad_launch_deferred(int prec, WgradQueue& q, hipStream_t stream);
 int srad_launch_wgrad(int prec, const WgradParams& p, WgradQueue& q, hipStream_t stream);
 bool srad_wgrad_conv9_supported(const WgradParams& p);   // the nine-tap kernel takes this layer (bf16 mode; the only one with bf16 conv operands)
 int srad_wgrad_flush(WgradQueue& q, hipStream_t stream);
-// The one place workspace is handed out: `need` floats (*part) and room for `nitems` more batch entries.  When the batch or the
-// workspace is full the queue flushes itself first - with deferred layers pending only the written items, see WgradQueue - and
-// fails with an error naming `who` if the region still does not fit.  The caller appends its `nitems` items afterwards.
+// A region of `need` floats (*part) without an item of its own, through the queue's one reservation (wgrad_queue_reserve): when
+// the batch or the workspace is full the queue flushes itself first - with deferred layers pending only the written items -
+// and fails with an error naming `who` if the region still does not fit.  (Items are queued by kernels_wgrad.hip's launchers
+// and by the two column-sum calls below, which reserve and push in one.)
 int srad_wgrad_take(WgradQueue& q, const char* who, size_t need, int nitems, hipStream_t stream, float** part);
 // Takes `nrows` partial rows of `row_stride` floats from the workspace (*part) for a kernel to fill, and queues alpha times the
 // column sums of their first `ncols` columns into dst (null: none).  `nitems` = column-sum items that will be queued on these
@@ -423,7 +378,8 @@ int srad_wgrad_reserve_colsum(WgradQueue& q, const char* who, float* dst, int nc
 
 #define SRAD_WGRAD_WS_BYTES ((size_t)256 << 20)   /* what the engines give the queue */
 
-// LayerNorm backward over rows: out (+)= dLN(dxn; x, gamma) + dres ; dgamma/dbeta += column sums (atomicAdd)
+// LayerNorm backward over rows: out (+)= dLN(dxn; x, gamma) + dres ; dgamma/dbeta += column sums (partial rows in the split-K
+// queue's workspace, added up by wgrad_reduce_kernel at the next flush)
 struct LnBwdParams {
   const float* dxn; int ld_dxn;
   const float* x; int ldx;
@@ -434,8 +390,6 @@ struct LnBwdParams {
   int rows, C; float eps;
 };
 
-
-// dgamma / dbeta go through the split-K queue too (per-workgroup column sums, added up at the next flush)
 int srad_launch_ln_bwd(const LnBwdParams& p, WgradQueue& q, hipStream_t stream);
 // `nrows` partial rows [dgamma SRAD_LNB_CP | dbeta SRAD_LNB_CP] in the queue's workspace + their two column-sum items
 constexpr int SRAD_LNB_CP = 320;

@@ -351,10 +351,7 @@ inline int train_sync_params(const ParamTable& pt, TrainState& ts, const float* 
 }
 
 inline WgradQueue train_wgrad_queue(const TrainState& ts) {
-  WgradQueue q;
-  q.ws = reinterpret_cast<float*>(ts.tarena + ts.t_wgrad_off);
-  q.ws_floats = ts.wgrad_budget / sizeof(float);
-  return q;
+  return wgrad_queue_on(reinterpret_cast<float*>(ts.tarena + ts.t_wgrad_off), ts.wgrad_budget / sizeof(float));
 }
 
 }  // namespace

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 EXPLICIT, BATCH, WS = 0, 1, 2
-WG_TS = 64 * 64 + 64                 # floats of one partial tile (kernels_bwd.hip)
+WG_TS = 64 * 64 + 64                 # floats of one partial tile (kernels_wgrad.hip)
 
 # operand shapes of the small cases of tests/test_gpu_bwd_ops.py
 LINEAR = {"linA": (77, 308, 180), "linB": (1000, 212, 32), "linC": (4096, 180, 540)}          # M, K, N
