@@ -137,11 +137,12 @@ __device__ __forceinline__ void axis_pairs(int lo, int hi, int n, int (&idx)[6])
   idx[4] = n - 1; idx[5] = hi > n - 1 ? 2 * (n - 1) - hi : n - 1;         // + P[n - 1] - P[2 (n - 1) - hi]: over the high edge
 }
 
-// The SSIM map value of pixel (i, j) for window size ws, from the tables S of its image: the five window sums are the (row
-// pair, column pair) rectangles of axis_pairs.  The reflection pairs of either axis are skipped by wave-uniform branches when no
-// lane of the wave needs them, and all loads of a rectangle are issued before the first add.  (The sums stay in this function:
-// handed out through an array parameter they cost ssim_map_kernel 6 VGPRs.)
-__device__ __forceinline__ float corner_ssim(const double* S, int H, int W, int i, int j, int ws, double dinv) {
+// The window sums of pixel (i, j) for window size ws, from the Q tables S of its image (planes of (H + 1) x (W + 1)), handed to
+// `finish`: the sums are the (row pair, column pair) rectangles of axis_pairs.  The reflection pairs of either axis are skipped by
+// wave-uniform branches when no lane of the wave needs them, and all loads of a rectangle are issued before the first add.  (The
+// sums stay in this function: handed out through an array parameter they cost ssim_map_kernel 6 VGPRs.)
+template <int Q, class Finish>
+__device__ __forceinline__ auto corner_window(const double* S, int H, int W, int i, int j, int ws, Finish finish) {
   const int pad = ws / 2, iper = W + 1;
   const size_t plane = (size_t)(H + 1) * iper;
   int ri[6], ci[6];
@@ -150,21 +151,21 @@ __device__ __forceinline__ float corner_ssim(const double* S, int H, int W, int 
   // does any lane of the wave need the reflection pairs?  (a wave-uniform i: the row answers are scalar anyway)
   const bool row_lo = __builtin_amdgcn_ballot_w64(i - pad < 0) != 0, row_hi = __builtin_amdgcn_ballot_w64(i + ws - 1 - pad > H - 1) != 0;
   const bool col_lo = __builtin_amdgcn_ballot_w64(j - pad < 0) != 0, col_hi = __builtin_amdgcn_ballot_w64(j + ws - 1 - pad > W - 1) != 0;
-  double sum[kQ] = {0, 0, 0, 0, 0};
+  double sum[Q] = {};
   auto row_pair = [&](auto RP) __attribute__((always_inline)) {               // + row ri[2 rp], - row ri[2 rp + 1]
     constexpr int rp = decltype(RP)::value;
     const int oa = ri[2 * rp] * iper, ob = ri[2 * rp + 1] * iper;
     auto col_pair = [&](auto CP) __attribute__((always_inline)) {
       constexpr int cp = decltype(CP)::value;
-      double va[kQ], vb[kQ], vc[kQ], vd[kQ];
+      double va[Q], vb[Q], vc[Q], vd[Q];
 #pragma unroll
-      for (int q = 0; q < kQ; ++q) {
+      for (int q = 0; q < Q; ++q) {
         const double* Sq = S + (size_t)q * plane;
         va[q] = Sq[oa + ci[2 * cp]]; vb[q] = Sq[oa + ci[2 * cp + 1]];
         vc[q] = Sq[ob + ci[2 * cp]]; vd[q] = Sq[ob + ci[2 * cp + 1]];
       }
 #pragma unroll
-      for (int q = 0; q < kQ; ++q) sum[q] += (va[q] - vb[q]) - (vc[q] - vd[q]);
+      for (int q = 0; q < Q; ++q) sum[q] += (va[q] - vb[q]) - (vc[q] - vd[q]);
     };
     col_pair(std::integral_constant<int, 0>{});
     if (col_lo) col_pair(std::integral_constant<int, 1>{});
@@ -173,7 +174,15 @@ __device__ __forceinline__ float corner_ssim(const double* S, int H, int W, int 
   row_pair(std::integral_constant<int, 0>{});
   if (row_lo) row_pair(std::integral_constant<int, 1>{});
   if (row_hi) row_pair(std::integral_constant<int, 2>{});
-  return ssim_of_sums(sum, dinv);
+  return finish(sum);
+}
+// The SSIM map value of pixel (i, j) for window size ws: the five window sums through ssim_of_sums.
+__device__ __forceinline__ float corner_ssim(const double* S, int H, int W, int i, int j, int ws, double dinv) {
+  return corner_window<kQ>(S, H, W, i, j, ws, [&](const double (&sum)[kQ]) __attribute__((always_inline)) { return ssim_of_sums(sum, dinv); });
+}
+// The squared-error window sum of pixel (i, j): one table of integers below 2^53, so every difference and the sum are exact.
+__device__ __forceinline__ double corner_sqerr(const double* S, int H, int W, int i, int j, int ws) {
+  return corner_window<1>(S, H, W, i, j, ws, [](const double (&sum)[1]) __attribute__((always_inline)) { return sum[0]; });
 }
 
 // Evaluation: one workgroup = kEvalPix consecutive pixels of one image for ONE window size; up to kWsGroup window sizes share
@@ -411,14 +420,11 @@ __global__ __launch_bounds__(256) void ssim_map_kernel(const double* __restrict_
 // multiply by a host-computed factor, not a division).  The loop over the sizes stays a loop: unrolled over the runtime count
 // it would hold several sizes' index sets in registers.
 // ROWS = the width is a multiple of 64: a wave's 64 pixels lie in one row, the row index is scalar (as in ssim_eval_kernel).
+// The pixel of a map kernel's thread (blocks of 256 pixels, `pb` = the block within the image): p = its index, which the caller
+// compares with npix before it stores, and (i, j) = the pixel it computes.
 template <bool ROWS>
-__global__ __launch_bounds__(256) void ssim_map_multi_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W,
-                                                             const WsList wl, int g, int reduce_max, int first, float scale, int nblk) {
-#pragma clang fp contract(off)
-  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
-  const int npix = H * W;
-  const int p = pb * 256 + (int)threadIdx.x;
-  int i, j;
+__device__ __forceinline__ void map_pixel(int pb, int npix, int W, int& p, int& i, int& j) {
+  p = pb * 256 + (int)threadIdx.x;
   if constexpr (ROWS) {
     // npix is a multiple of 64 too; a wave past the end (the last block's) computes a copy of the last 64 pixels
     const int seg0 = min(__builtin_amdgcn_readfirstlane(pb * 256 + ((int)threadIdx.x & ~63)), npix - 64);
@@ -427,6 +433,15 @@ __global__ __launch_bounds__(256) void ssim_map_multi_kernel(const double* __res
     const int pix = min(p, npix - 1);                                    // lanes past the end compute a copy of the last pixel
     i = pix / W; j = pix - i * W;
   }
+}
+template <bool ROWS>
+__global__ __launch_bounds__(256) void ssim_map_multi_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W,
+                                                             const WsList wl, int g, int reduce_max, int first, float scale, int nblk) {
+#pragma clang fp contract(off)
+  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
+  const int npix = H * W;
+  int p, i, j;
+  map_pixel<ROWS>(pb, npix, W, p, i, j);
   const double* const S = sat + (size_t)img * kQ * ((size_t)(H + 1) * (W + 1));
   float* const dst = out + (size_t)img * npix + p;
   float acc = 0.0f;
@@ -438,6 +453,127 @@ __global__ __launch_bounds__(256) void ssim_map_multi_kernel(const double* __res
     else acc = reduce_max ? fmaxf(acc, v) : acc + v;
   }
   if (p < npix) *dst = acc * scale;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Squared-error maps (DESIGN.md "Squared-error maps"; the per-pixel form of the MSE score of src/evaluate.py:251-265).  On u8
+// images e[i, j] = sum_c (sr - hr)^2 is an integer, so its sum S over the reflect-padded window of corner_ssim is one too, and
+// the map is (float)((double)S * inv) with inv = 1 / (C ws^2 65025) from the host: defined bit for bit.
+//
+// ONE prefix plane of e per image, float64 in the table layout above (every prefix is below (H + 1)(W + 1) * 3 * 65025 < 2^49, so
+// float64 is exact), built by the row pass below and the column pass of the SSIM tables; the map kernels read it through
+// corner_window<1>.  Per pixel: 8 B of table written by the row pass plus the column pass's 16 to 32 B, 8 B (no reflection) to
+// 72 B (both axes reflect on both sides) of corners per window size, and the 4 B store - the SSIM maps cost 200 B of table and
+// 80 B per size.
+//
+// Row pass: one wave per (image, table row), as sat_rows_kernel; a 64-pixel chunk is scanned in u32 (64 * 3 * 65025 < 2^24).
+__global__ __launch_bounds__(256) void sqerr_rows_kernel(const uint8_t* __restrict__ sr, const uint8_t* __restrict__ hr,
+                                                         double* __restrict__ sat, int n_img, int H, int W, int C) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= n_img * (H + 1)) return;
+  const int img = t / (H + 1), r = t - img * (H + 1);
+  double* const base = sat + ((size_t)img * (H + 1) + r) * (W + 1);
+  if (r == 0) {
+    for (int c = lane; c <= W; c += 64) base[c] = 0.0;
+    return;
+  }
+  if (lane == 0) base[0] = 0.0;
+  const uint8_t* ps = sr + ((size_t)img * H + (r - 1)) * W * C;
+  const uint8_t* ph = hr + ((size_t)img * H + (r - 1)) * W * C;
+  double carry = 0.0;
+  for (int c0 = 0; c0 < W; c0 += 64) {
+    const int c = c0 + lane;
+    unsigned v = 0;
+    if (c < W)
+      for (int ch = 0; ch < C; ++ch) {
+        const int d = (int)ps[(size_t)c * C + ch] - (int)ph[(size_t)c * C + ch];
+        v += (unsigned)(d * d);
+      }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned up = __shfl_up(v, o);
+      if (lane >= o) v += up;
+    }
+    const double s = carry + (double)v;
+    if (c < W) base[c + 1] = s;
+    carry = __shfl(s, 63);
+  }
+}
+
+// The map of ONE window size: one thread per pixel, one multiply and one fp32 store.  ROWS as in ssim_map_multi_kernel.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void sqerr_map_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W, int ws,
+                                                        double inv, int nblk) {
+  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
+  const int npix = H * W;
+  int p, i, j;
+  map_pixel<ROWS>(pb, npix, W, p, i, j);
+  const double S = corner_sqerr(sat + (size_t)img * ((size_t)(H + 1) * (W + 1)), H, W, i, j, ws);
+  if (p < npix) out[(size_t)img * npix + p] = (float)(S * inv);
+}
+
+// Multi-scale: the maps of the `g` sizes of `wl` (dinv = each size's `inv`) reduced per pixel with the accumulation, the `first`
+// / `scale` protocol and the launch splitting of ssim_map_multi_kernel, so the result is the bits of the single maps accumulated
+// in list order.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void sqerr_map_multi_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W,
+                                                              const WsList wl, int g, int reduce_max, int first, float scale, int nblk) {
+#pragma clang fp contract(off)
+  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
+  const int npix = H * W;
+  int p, i, j;
+  map_pixel<ROWS>(pb, npix, W, p, i, j);
+  const double* const S = sat + (size_t)img * ((size_t)(H + 1) * (W + 1));
+  float* const dst = out + (size_t)img * npix + p;
+  float acc = 0.0f;
+  if (!first && p < npix) acc = *dst;
+#pragma unroll 1
+  for (int k = 0; k < g; ++k) {
+    const float v = (float)(corner_sqerr(S, H, W, i, j, wl.ws[k]) * wl.dinv[k]);
+    if (first && k == 0) acc = v;
+    else acc = reduce_max ? fmaxf(acc, v) : acc + v;
+  }
+  if (p < npix) *dst = acc * scale;
+}
+
+// ws = 1 alone needs no table: out = (float)((double)e * inv) straight from the two stacks, 2 C bytes read and 4 B written per
+// pixel.  A thread takes 4 consecutive pixels of the flattened stacks: with `vec` (sr and hr 4-byte aligned, out 16-byte
+// aligned) their 4 C bytes are C dwords per stack and the four values one 16-byte store; the pixels of a last, partial group
+// and unaligned stacks go byte by byte.
+template <int C>
+__global__ __launch_bounds__(256) void sqerr_pixel_kernel(const uint8_t* __restrict__ sr, const uint8_t* __restrict__ hr,
+                                                          float* __restrict__ out, size_t npix, double inv, int vec) {
+  const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x, p0 = q * 4;
+  if (p0 >= npix) return;
+  if (vec && p0 + 4 <= npix) {
+    uint32_t a[C], b[C];
+#pragma unroll
+    for (int w = 0; w < C; ++w) {
+      a[w] = reinterpret_cast<const uint32_t*>(sr)[q * C + w];
+      b[w] = reinterpret_cast<const uint32_t*>(hr)[q * C + w];
+    }
+    unsigned e[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4 * C; ++k) {                                    // byte k of the group belongs to pixel k / C
+      const int d = (int)((a[k / 4] >> (8 * (k % 4))) & 255u) - (int)((b[k / 4] >> (8 * (k % 4))) & 255u);
+      e[k / C] += (unsigned)(d * d);
+    }
+    float4 o;
+    o.x = (float)((double)e[0] * inv); o.y = (float)((double)e[1] * inv);
+    o.z = (float)((double)e[2] * inv); o.w = (float)((double)e[3] * inv);
+    reinterpret_cast<float4*>(out)[q] = o;
+    return;
+  }
+  for (size_t p = p0; p < npix && p < p0 + 4; ++p) {
+    unsigned e = 0;
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) {
+      const int d = (int)sr[p * C + ch] - (int)hr[p * C + ch];
+      e += (unsigned)(d * d);
+    }
+    out[p] = (float)((double)e * inv);
+  }
 }
 
 // mean((sr/255 - hr/255)^2) over all H*W*C values of an image: block partial sums (grid = blocks x images) ...
@@ -566,40 +702,56 @@ inline int grid1d(size_t total) {
 }
 
 // Workspace of srad_score_pairs (sweep) and srad_anomaly_maps for n_img H x W pairs, each part 256-byte aligned: the tables of
-// one chunk of images, the sweep's partial sums (sweep only) and the column pass's segment totals.  base == nullptr: sizes only.
+// one chunk of images (`planes` per image: the five of SSIM, or the one of the squared-error maps), the sweep's partial sums
+// (sweep only) and the column pass's segment totals.  base == nullptr: sizes only.
 struct ScoreWs {
   int chunk, nseg, nblk;          // images per chunk, 32-row segments per table column, partial slots per (image, window size)
   double *sat, *partial, *segtot;
   size_t bytes;
 };
-ScoreWs plan_score_ws(int n_img, int H, int W, bool sweep, void* base) {
+ScoreWs plan_score_ws(int n_img, int H, int W, bool sweep, void* base, int planes = kQ) {
   ScoreWs w;
   w.chunk = chunk_images(n_img, H, W);
   w.nseg = (H + kSeg - 1) / kSeg;
   w.nblk = partial_slots(H, W);
   Bump bp(base, 0);
   auto take = [&](size_t doubles) { return reinterpret_cast<double*>(bp.take(2 * doubles)); };    // Bump counts floats
-  w.sat = take((size_t)w.chunk * (H + 1) * (W + 1) * kQ);
+  w.sat = take((size_t)w.chunk * (H + 1) * (W + 1) * planes);
   w.partial = sweep ? take((size_t)w.chunk * kWsGroup * w.nblk) : nullptr;
-  w.segtot = take((size_t)w.chunk * kQ * w.nseg * (W + 1));
+  w.segtot = take((size_t)w.chunk * planes * w.nseg * (W + 1));
   w.bytes = bp.used;
   return w;
 }
 
-// The five tables of n pairs (the chunk that starts at sr / hr): the row pass, then the column pass in 32-row segments.
+// The column pass over `n_planes` row-summed planes, in 32-row segments.
+void column_pass(const ScoreWs& w, int n_planes, int H, int W, hipStream_t s) {
+  const size_t t = (size_t)n_planes * w.nseg * (W + 1);
+  SradProfScope prof(s, SRAD_K_SCORE, 1.0 * n_planes * (H + 1) * (W + 1), 16.0 * n_planes * (H + 1) * (W + 1));
+  hipLaunchKernelGGL(sat_cols_local_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, w.sat, w.segtot, n_planes, H, W, w.nseg);
+  if (w.nseg > 1) {
+    const size_t t2 = (size_t)n_planes * (w.nseg - 1) * (W + 1);
+    hipLaunchKernelGGL(sat_cols_carry_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, w.sat, w.segtot, n_planes, H, W, w.nseg);
+  }
+}
+
+// The five tables of n pairs (the chunk that starts at sr / hr): the row pass, then the column pass.
 void build_tables(const ScoreWs& w, const uint8_t* sr, const uint8_t* hr, int n, int H, int W, int C, hipStream_t s) {
   const size_t img_bytes = (size_t)H * W * C;
   {
     SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W, 2.0 * n * img_bytes + 40.0 * n * (H + 1) * (W + 1));
     hipLaunchKernelGGL(sat_rows_kernel, dim3((n * (H + 1) + 3) / 4), dim3(256), 0, s, sr, hr, w.sat, n, H, W, C);
   }
-  const size_t t = (size_t)n * kQ * w.nseg * (W + 1);
-  SradProfScope prof(s, SRAD_K_SCORE, 1.0 * n * (H + 1) * (W + 1) * kQ, 80.0 * n * (H + 1) * (W + 1));
-  hipLaunchKernelGGL(sat_cols_local_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, w.sat, w.segtot, n * kQ, H, W, w.nseg);
-  if (w.nseg > 1) {
-    const size_t t2 = (size_t)n * kQ * (w.nseg - 1) * (W + 1);
-    hipLaunchKernelGGL(sat_cols_carry_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, w.sat, w.segtot, n * kQ, H, W, w.nseg);
+  column_pass(w, n * kQ, H, W, s);
+}
+
+// The squared-error table of n pairs: its own row pass, the same column pass.
+void build_sqerr_table(const ScoreWs& w, const uint8_t* sr, const uint8_t* hr, int n, int H, int W, int C, hipStream_t s) {
+  const size_t img_bytes = (size_t)H * W * C;
+  {
+    SradProfScope prof(s, SRAD_K_SCORE, 3.0 * n * img_bytes, 2.0 * n * img_bytes + 8.0 * n * (H + 1) * (W + 1));
+    hipLaunchKernelGGL(sqerr_rows_kernel, dim3((n * (H + 1) + 3) / 4), dim3(256), 0, s, sr, hr, w.sat, n, H, W, C);
   }
+  column_pass(w, n, H, W, s);
 }
 
 // argument checks shared by srad_score_pairs and srad_anomaly_maps; `what` (the entry point) starts each message
@@ -614,6 +766,9 @@ int check_window(const char* what, int ws, int H, int W) {
                "%s: window %d needs more than one reflection of a %dx%d image", what, ws, H, W);
   return SRAD_OK;
 }
+
+// the factor of a squared-error map value: 1 / (C ws^2 255^2), a host double like WsList::dinv
+inline double sqerr_inv(int C, int ws) { return 1.0 / ((double)C * (double)ws * (double)ws * 65025.0); }
 
 }  // namespace
 
@@ -765,6 +920,86 @@ int srad_anomaly_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int
       else
         hipLaunchKernelGGL(ssim_map_multi_kernel<false>, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce,
                            first, scale, nblk);
+    }
+  }
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_error_map_workspace_bytes(int n_img, int H, int W, size_t* bytes) {
+  SRAD_REQUIRE(bytes && n_img > 0 && H > 0 && W > 0, "error_map_workspace_bytes: bad argument");
+  *bytes = plan_score_ws(n_img, H, W, false, nullptr, 1).bytes;
+  return SRAD_OK;
+}
+
+// the per-pixel form of the MSE score of src/evaluate.py:251-265
+int srad_error_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  SRAD_REQUIRE(map_out, "error_maps: bad argument");
+  SRAD_TRY(check_pairs("error_maps", sr, hr, workspace, n_img, H, W, C));
+  SRAD_TRY(check_window("error_maps", ws, H, W));
+  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace, 1);
+  SRAD_REQUIRE(workspace_bytes >= w.bytes, "error_maps: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const size_t img_bytes = (size_t)H * W * C;
+  const double inv = sqerr_inv(C, ws);
+  if (ws == 1) {                                       // no window: no table
+    const size_t npix = (size_t)n_img * H * W, groups = (npix + 3) / 4;
+    SRAD_REQUIRE((groups + 255) / 256 < (1ull << 31), "error_maps: %d %dx%d images are too many pixels for one launch", n_img, H, W);
+    const int vec = (reinterpret_cast<uintptr_t>(sr) | reinterpret_cast<uintptr_t>(hr)) % 4 == 0 && reinterpret_cast<uintptr_t>(map_out) % 16 == 0;
+    SradProfScope prof(s, SRAD_K_SCORE, 3.0 * n_img * img_bytes, 2.0 * n_img * img_bytes + 4.0 * npix);
+    const dim3 grid((unsigned)((groups + 255) / 256));
+    if (C == 1) hipLaunchKernelGGL(sqerr_pixel_kernel<1>, grid, dim3(256), 0, s, sr, hr, map_out, npix, inv, vec);
+    else hipLaunchKernelGGL(sqerr_pixel_kernel<3>, grid, dim3(256), 0, s, sr, hr, map_out, npix, inv, vec);
+    SRAD_CHECK_HIP(hipGetLastError());
+    return SRAD_OK;
+  }
+  const int nblk = (H * W + 255) / 256;
+  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
+    const int n = std::min(w.chunk, n_img - i0);
+    build_sqerr_table(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
+    // algorithmic bytes: the two u8 stacks read once, the fp32 map written once
+    SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W, 2.0 * n * img_bytes + 4.0 * n * H * W);
+    const dim3 grid((unsigned)((size_t)nblk * n));
+    float* const out = map_out + (size_t)i0 * H * W;
+    if (W % 64 == 0) hipLaunchKernelGGL(sqerr_map_kernel<true>, grid, dim3(256), 0, s, w.sat, out, H, W, ws, inv, nblk);
+    else hipLaunchKernelGGL(sqerr_map_kernel<false>, grid, dim3(256), 0, s, w.sat, out, H, W, ws, inv, nblk);
+  }
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+// the multi-scale form of srad_error_maps (the MSE score of src/evaluate.py:251-265 per pixel and window)
+int srad_error_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host, int n_ws,
+                          int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream) {
+  SRAD_REQUIRE(map_out, "error_maps_multi: bad argument");
+  SRAD_REQUIRE(ws_host && n_ws >= 1, "error_maps_multi: the window list is empty");
+  SRAD_REQUIRE(reduce == 0 || reduce == 1, "error_maps_multi: reduce must be 0 (mean) or 1 (max), got %d", reduce);
+  SRAD_TRY(check_pairs("error_maps_multi", sr, hr, workspace, n_img, H, W, C));
+  for (int k = 0; k < n_ws; ++k) SRAD_TRY(check_window("error_maps_multi", ws_host[k], H, W));
+  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace, 1);
+  SRAD_REQUIRE(workspace_bytes >= w.bytes, "error_maps_multi: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
+  if (n_ws == 1) return srad_error_maps(sr, hr, n_img, H, W, C, ws_host[0], map_out, workspace, workspace_bytes, stream);   // K = 1: the single map
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int nblk = (H * W + 255) / 256;
+  const size_t img_bytes = (size_t)H * W * C;
+  const float inv_k = (float)(1.0 / (double)n_ws);
+  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
+    const int n = std::min(w.chunk, n_img - i0);
+    build_sqerr_table(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
+    float* const out = map_out + (size_t)i0 * H * W;
+    for (int k0 = 0; k0 < n_ws; k0 += kWsGroup) {      // up to kWsGroup window sizes per launch; later launches continue from `out`
+      const int g = std::min(kWsGroup, n_ws - k0);
+      WsList wl{};
+      for (int k = 0; k < g; ++k) { wl.ws[k] = (int)ws_host[k0 + k]; wl.dinv[k] = sqerr_inv(C, wl.ws[k]); }
+      const int first = k0 == 0;
+      const float scale = (reduce == 0 && k0 + g == n_ws) ? inv_k : 1.0f;
+      SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W * g, 2.0 * n * img_bytes + 4.0 * n * H * W);
+      const dim3 grid((unsigned)((size_t)nblk * n));
+      if (W % 64 == 0)
+        hipLaunchKernelGGL(sqerr_map_multi_kernel<true>, grid, dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce, first, scale, nblk);
+      else
+        hipLaunchKernelGGL(sqerr_map_multi_kernel<false>, grid, dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce, first, scale, nblk);
     }
   }
   SRAD_CHECK_HIP(hipGetLastError());

@@ -244,7 +244,8 @@ def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndar
 def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], bad: Sequence[Tuple[np.ndarray, np.ndarray]],
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
-                     map_ws: int = 0, map_scales=(), map_reduce: str = 'mean', operating_point=None, map_sigma: float = 0.0,
+                     map_ws: int = 0, map_scales=(), map_reduce: str = 'mean', map_source: str = 'ssim', operating_point=None,
+                     map_sigma: float = 0.0,
                      map_image_score: bool = False, aupro: bool = False, pro_fpr_limit: float = 0.3) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
@@ -267,6 +268,12 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     scales do not depend on the sweep's result.  ValueError, before any image is super-resolved, for a size the images are too
     small for, an unknown ``map_reduce``, and scales together with a non-zero ``map_ws``.
 
+    ``map_source`` 'mse' (default 'ssim'): the maps are the squared-error maps of ``metrics.error_maps`` /
+    ``metrics.error_maps_multi`` (DESIGN.md "Squared-error maps") instead of ``1 - SSIM map``, for the test images and the
+    calibration images alike; everything after them is unchanged, the printed lines say ``MSE map`` and the result carries
+    ``map_source`` beside ``map_ws`` / ``map_scales``.  ``map_ws`` 0 without scales then means window size 1, the raw squared
+    error - not the SSIM sweep's best_ws, so nothing is broadcast for it.  ValueError for an unknown source, before any work.
+
     ``operating_point`` (an ``OperatingPoint`` or a dict of its fields; None = off): with world 1 the maps are thresholded
     (DESIGN.md "Operating point") at the given threshold, or at the one that the maps of the calibration pairs - made like the
     test maps: the same forward, u8 conversion, window size or scales, and ``map_sigma`` - give at the asked false-positive
@@ -274,6 +281,8 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     ``threshold_level``, ``calib_images``, ``calib_rate`` = the rate achieved on the calibration values), ``min_region_area``,
     the image-level counts and rates of ``metrics.operating_point_stats`` and, with a mask for every image, its pixel-level
     counts, ratios and ``pro_at_threshold``.  ValueError for an inconsistent specification, before any image is super-resolved."""
+    if map_source not in M.MAP_SOURCES:
+        raise ValueError(f"map_source = {map_source!r}, must be one of {M.MAP_SOURCES}")
     op = None
     if operating_point is not None:
         op = (OperatingPoint(**operating_point) if isinstance(operating_point, dict) else operating_point).check()
@@ -311,7 +320,7 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     if full is None:
         if save_maps or pixel_metrics or aupro or map_image_score or op is not None:
             _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, None, world, aupro,
-                         pro_fpr_limit, map_sigma, map_image_score, rank, op, None, scales, map_reduce)
+                         pro_fpr_limit, map_sigma, map_image_score, rank, op, None, map_source, scales, map_reduce)
         return {}
     best_ws, best_auc, best_j = sizes[0], -1.0, 0
     for j, ws in enumerate(sizes):
@@ -326,15 +335,19 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
         if op is not None and op.fpr is not None and world == 1:      # the calibration images go the test images' way
             calib = super_resolve_u8(model, [lr for lr, _ in op.calib], [h for _, h in op.calib], float(opt.rgb_range))
         out.update(_pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                                aupro, pro_fpr_limit, map_sigma, map_image_score, rank, op, calib, scales, map_reduce))
+                                aupro, pro_fpr_limit, map_sigma, map_image_score, rank, op, calib, map_source, scales, map_reduce))
     return out
 
 
-def _make_maps(sr, hr, scales, map_reduce, ws, sigma, with_max):
+def _make_maps(sr, hr, scales, map_reduce, ws, sigma, with_max, source='ssim'):
     """The anomaly maps of (sr, hr) u8 stacks the way the evaluator makes them, for the test images and the calibration images
-    alike: ``scales`` (non-empty) reduced by ``map_reduce``, else the one window size ``ws``; then smoothed when ``sigma`` > 0.
+    alike: ``scales`` (non-empty) reduced by ``map_reduce``, else the one window size ``ws``, of the ``1 - SSIM`` maps or
+    (``source`` 'mse') the squared-error maps; then smoothed when ``sigma`` > 0.
     Returns (maps, per-image maxima or None without ``with_max``)."""
-    maps = M.anomaly_maps_multi(sr, hr, scales, map_reduce) if scales else M.anomaly_maps(sr, hr, ws)
+    if source == 'mse':
+        maps = M.error_maps_multi(sr, hr, scales, map_reduce) if scales else M.error_maps(sr, hr, ws)
+    else:
+        maps = M.anomaly_maps_multi(sr, hr, scales, map_reduce) if scales else M.anomaly_maps(sr, hr, ws)
     if with_max:
         return M.smooth_maps(maps, sigma, with_max=True)
     return (M.smooth_maps(maps, sigma) if sigma > 0 else maps), None
@@ -342,12 +355,14 @@ def _make_maps(sr, hr, scales, map_reduce, ws, sigma, with_max):
 
 def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
                  aupro=False, pro_fpr_limit=0.3, map_sigma=0.0, map_image_score=False, rank=0, op=None, calib=None,
-                 map_scales=(), map_reduce='mean') -> dict:
+                 map_source='ssim', map_scales=(), map_reduce='mean') -> dict:
     """Anomaly maps of this rank's images, smoothed once when ``map_sigma`` > 0; the map-maximum image AUC on any number of
     ranks; the pixel-level AUC, AU-PRO and the operating point (``op``, a checked ``OperatingPoint``; ``calib`` = the (sr, hr)
     u8 stacks of its calibration pairs) on a single rank.  ``best_ws`` is None off rank 0.  Every branch that leads to a
     collective depends only on the flags and ``world``, which all ranks share, so all ranks make the same collective calls.
-    ``map_scales`` (a resolved list) replaces the single window size: every rank knows it, so ``best_ws`` is not broadcast."""
+    ``map_scales`` (a resolved list) replaces the single window size: every rank knows it, so ``best_ws`` is not broadcast.
+    ``map_source`` 'mse': squared-error maps; without scales and with ``map_ws`` 0 their window size is 1, which every rank
+    knows too, so this source never broadcasts."""
     scored = pixel_metrics or aupro
     single = scored or op is not None                         # what runs on one rank only
     if world > 1 and not (save_maps or map_image_score):      # the same branch on every rank: no collective below
@@ -355,9 +370,14 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
             print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
         return {}
     scales = [int(w) for w in map_scales]
+    mse = map_source == 'mse'
+    label = "MSE map" if mse else "SSIM map"
     ws = 0
     if scales:
         what, keys = f"scales={scales}, {map_reduce}", dict(map_scales=scales, map_reduce=map_reduce)
+    elif mse:
+        ws = int(map_ws) if int(map_ws) > 0 else 1            # best_ws is a fact about the SSIM score
+        what, keys = f"ws={ws}", dict(map_ws=ws)
     else:
         ws = int(map_ws)
         if ws <= 0:
@@ -368,8 +388,10 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
                 dist.broadcast_object_list(box, src=0)
                 ws = int(box[0])
         what, keys = f"ws={ws}", dict(map_ws=ws)
+    if mse:
+        keys = dict(map_source=map_source, **keys)
     sigma = float(map_sigma)
-    maps, img_max = _make_maps(sr, hr, scales, map_reduce, ws, sigma, map_image_score)
+    maps, img_max = _make_maps(sr, hr, scales, map_reduce, ws, sigma, map_image_score, map_source)
     if save_maps and output_dir:
         save_anomaly_maps(maps, [names[i] if i < len(names) else f"{i:05d}" for i in mine],
                           ['good' if y_true[i] == 0 else 'bad' for i in mine], output_dir)
@@ -378,7 +400,7 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
         full = gather_score_rows(mine, img_max.double().cpu().numpy()[:, None], len(y_true), rank, world)
         if full is not None:
             out.update(keys, auc_map_max=M.roc_auc(y_true, full[:, 0]))
-            print(f"Image AUC - max of the SSIM map ({what}, sigma={sigma:g}): {out['auc_map_max']:.4f}")
+            print(f"Image AUC - max of the {label} ({what}, sigma={sigma:g}): {out['auc_map_max']:.4f}")
     if sigma > 0 and out:
         out["map_sigma"] = sigma
     if not single or best_ws is None:
@@ -404,13 +426,13 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
     tail = f", sigma={sigma:g}" if sigma > 0 else ""
     if pixel_metrics and labels is not None:
         out["auc_pixel"] = M.pixel_roc_auc(maps, labels)
-        print(f"Pixel AUC - SSIM map ({what}{tail}): {out['auc_pixel']:.4f}")
+        print(f"Pixel AUC - {label} ({what}{tail}): {out['auc_pixel']:.4f}")
     if aupro and labels is not None:
         out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, pro_fpr_limit), float(pro_fpr_limit)
-        print(f"AU-PRO - SSIM map ({what}, fpr <= {float(pro_fpr_limit):g}{tail}): {out['aupro']:.4f}")
+        print(f"AU-PRO - {label} ({what}, fpr <= {float(pro_fpr_limit):g}{tail}): {out['aupro']:.4f}")
     if op is not None:
         if op.fpr is not None:
-            cmaps, cmax = _make_maps(calib[0], calib[1], scales, map_reduce, ws, sigma, op.level == 'image')
+            cmaps, cmax = _make_maps(calib[0], calib[1], scales, map_reduce, ws, sigma, op.level == 'image', map_source)
             t, achieved = M.map_threshold(cmax if op.level == 'image' else cmaps, op.fpr)
             out.update(threshold=t, threshold_source='fpr', threshold_fpr=float(op.fpr), threshold_level=op.level,
                        calib_images=int(cmaps.shape[0]), calib_rate=achieved)
@@ -423,7 +445,7 @@ def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, 
         pred, img_pred, counts = M.operating_point(maps, t, labels, int(op.min_area))
         st = M.operating_point_stats(counts if labels is not None else None, img_pred, [y_true[i] for i in mine])
         out.update(st)
-        line = (f"Operating point - SSIM map ({what}{tail}), threshold={t:.9g} ({src}), min_area={int(op.min_area)}: "
+        line = (f"Operating point - {label} ({what}{tail}), threshold={t:.9g} ({src}), min_area={int(op.min_area)}: "
                 f"image tp={st['image_tp']} fp={st['image_fp']} fn={st['image_fn']} tn={st['image_tn']} "
                 f"tpr={st['image_tpr']:.4f} fpr={st['image_fpr']:.4f}")
         if labels is not None:
@@ -506,7 +528,7 @@ def _run(args):
                            masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws,
                            aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit, map_sigma=args.map_sigma,
                            map_image_score=args.map_image_score, map_scales=args.map_scales, map_reduce=args.map_reduce,
-                           operating_point=op)
+                           map_source=args.map_source, operating_point=op)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

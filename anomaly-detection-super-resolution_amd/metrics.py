@@ -149,6 +149,46 @@ def anomaly_maps_multi(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: S
     return out
 
 
+MAP_SOURCES = ("ssim", "mse")              # what the evaluator's pixel-level maps are made of (--map-source)
+
+
+def error_maps(sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws: int = 1) -> torch.Tensor:
+    """Squared-error maps of [n,H,W,C] uint8 image stacks (SR, HR), the per-pixel form of the MSE score (src/evaluate.py:251-265):
+    with the integer ``e = sum_c (sr - hr)^2`` and ``S`` its sum over the reflect-padded ``ws`` x ``ws`` window of
+    ``anomaly_maps``, the map is ``float32(float64(S) * (1.0 / (C * ws * ws * 65025)))`` bit for bit (DESIGN.md "Squared-error
+    maps"); ``ws = 1`` is the raw per-pixel squared error, whose mean is the image's MSE.  Returns float32 [n,H,W] on the GPU,
+    values in [0, 1].  RuntimeError for a window ``anomaly_maps`` refuses."""
+    _need_cuda(sr_u8, hr_u8)
+    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
+    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
+    n, H, W, Cc = sr_u8.shape
+    out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
+    _call_with_ws("error_map_workspace_bytes", (n, H, W), "error_maps",
+                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, int(ws), L.dptr(out)), sr_u8.device)
+    return out
+
+
+def error_maps_multi(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Sequence[int], reduce: str = "mean") -> torch.Tensor:
+    """Multi-scale squared-error maps: ``error_maps`` at every size of ``window_sizes`` reduced per pixel exactly as
+    ``anomaly_maps_multi`` reduces its maps, so the result is bit for bit ``acc = acc + error_maps(.., ws_k)`` in list order then
+    ``acc * float32(1 / K)`` (``torch.maximum`` for 'max'); a size listed twice counts twice.  Returns float32 [n,H,W] on the
+    GPU.  ValueError for an empty list or an unknown ``reduce``; RuntimeError for a size ``error_maps`` refuses."""
+    if reduce not in MAP_REDUCTIONS:
+        raise ValueError(f"error_maps_multi: reduce = {reduce!r}, must be one of {MAP_REDUCTIONS}")
+    sizes = [int(w) for w in window_sizes]
+    if not sizes:
+        raise ValueError("error_maps_multi: the window-size list is empty")
+    _need_cuda(sr_u8, hr_u8)
+    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
+    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
+    n, H, W, Cc = sr_u8.shape
+    ws = (C.c_int32 * len(sizes))(*sizes)
+    out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
+    _call_with_ws("error_map_workspace_bytes", (n, H, W), "error_maps_multi",
+                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, ws, len(sizes), MAP_REDUCTIONS.index(reduce), L.dptr(out)), sr_u8.device)
+    return out
+
+
 def check_map_scales(window_sizes: Sequence[int], H: int, W: int) -> List[int]:
     """The sizes of ``window_sizes`` as a list, once every one passes the window check of the map kernels for H x W images
     (a window may reflect over an image edge once).  ValueError otherwise.  Needs no GPU, so callers can check their arguments

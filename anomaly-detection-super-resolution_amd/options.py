@@ -290,6 +290,9 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                         "size of the image-level sweep, combined per pixel with --map-reduce; replaces --map-ws")
     p.add_argument('--map-reduce', type=str, default='mean', choices=['mean', 'max'],
                    help="how --map-scales combines the maps of its window sizes")
+    p.add_argument('--map-source', type=str, default='ssim', choices=['ssim', 'mse'],
+                   help="what the pixel-level maps are made of: 1 - SSIM map, or (mse) the squared error averaged over the window "
+                        "(--map-ws 0 then means window size 1, the raw per-pixel squared error)")
     p.add_argument('--threshold', type=_finite_or_inf_float, default=None, metavar='VALUE',
                    help="operating point: a pixel is predicted defective iff its anomaly-map value is > VALUE; reports the "
                         "image-level (and, with test/bad/GT masks, pixel-level) counts at it (needs --gpus 1)")
@@ -311,6 +314,8 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
             args.map_scales = _map_scales(','.join(str(v) for v in args.map_scales))
         except argparse.ArgumentTypeError as e:
             p.error(f"argument --map-scales: {e}")
+    if args.map_source not in ('ssim', 'mse'):                # a value from a config file gets the command line's check
+        p.error(f"argument --map-source: invalid choice: {args.map_source!r} (choose from 'ssim', 'mse')")
     if args.map_scales and args.map_ws:
         p.error("--map-scales and --map-ws exclude each other (the scales replace the single window size)")
     return args

@@ -221,6 +221,22 @@ int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, in
  * Every size must pass the window check of srad_anomaly_maps; workspace >= srad_anomaly_map_workspace_bytes. */
 int srad_anomaly_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host,
                             int n_ws, int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Squared-error maps, the per-pixel form of the MSE score (src/evaluate.py:251-265), for `n_img` u8 HWC image pairs at ONE
+ * window size `ws`: with e[y, x] = sum_c (sr - hr)^2 (an integer) and S = the sum of e over the window of srad_anomaly_maps
+ * (numpy "reflect" padding, rows y - ws/2 .. y + ws - 1 - ws/2, columns likewise; an exact integer),
+ *   map_out[i, y, x] = (float)((double)S * inv),   inv = 1.0 / (C * ws * ws * 65025) in double
+ * - one fp64 multiply and one rounding, so the map is defined bit for bit; values lie in [0, 1].  ws = 1 is the raw per-pixel
+ * squared error (its mean is the image's MSE) and needs no table.  map_out is a DEVICE float32 array [n_img, H, W]; the window
+ * check is that of srad_anomaly_maps; workspace >= srad_error_map_workspace_bytes.  Any width. */
+int srad_error_map_workspace_bytes(int n_img, int H, int W, size_t* bytes);
+int srad_error_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* Multi-scale squared-error maps (src/evaluate.py:251-265 per pixel and window): the maps d_k of srad_error_maps at the `n_ws`
+ * >= 1 sizes of the HOST list `ws_host`, reduced per pixel exactly as srad_anomaly_maps_multi reduces its maps (reduce 0: fp32
+ * sum in LIST ORDER times (float)(1.0 / n_ws); reduce 1: fmaxf), so map_out is bit for bit the srad_error_maps outputs
+ * accumulated that way and n_ws = 1 gives srad_error_maps itself.  workspace >= srad_error_map_workspace_bytes. */
+int srad_error_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host,
+                          int n_ws, int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Exact ROC-AUC of `n` DEVICE float32 scores against DEVICE u8 labels (labels[i] != 0 = positive), n < 2^31:
  * sklearn.metrics.roc_auc_score as the Mann-Whitney U with ties counted one half (a device radix sort, no binning).
  *   counts_out (DEVICE, 4 x u64) = {n_pos, n_neg, n_nan, twice_U};  *auc_out (DEVICE double) = twice_U / (2 n_pos n_neg),
