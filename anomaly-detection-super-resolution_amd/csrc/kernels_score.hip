@@ -115,7 +115,7 @@ __global__ void sat_cols_carry_kernel(double* __restrict__ sat, const double* __
 }
 
 // The SSIM map value of a pixel from its five window sums and 1 / ws^2, in fp32 in the reference's operation order
-// (metrics.py:58-66), for the three sweep kernels and ssim_map_kernel.
+// (metrics.py:58-66), for the three sweep kernels and the SSIM maps.
 __device__ __forceinline__ float ssim_of_sums(const double (&sum)[kQ], double dinv) {
 #pragma clang fp contract(off)     // the reference's rounding: an fma leaves E[x^2] - mu^2 a residue where it is 0
   const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);
@@ -140,7 +140,7 @@ __device__ __forceinline__ void axis_pairs(int lo, int hi, int n, int (&idx)[6])
 // The window sums of pixel (i, j) for window size ws, from the Q tables S of its image (planes of (H + 1) x (W + 1)), handed to
 // `finish`: the sums are the (row pair, column pair) rectangles of axis_pairs.  The reflection pairs of either axis are skipped by
 // wave-uniform branches when no lane of the wave needs them, and all loads of a rectangle are issued before the first add.  (The
-// sums stay in this function: handed out through an array parameter they cost ssim_map_kernel 6 VGPRs.)
+// sums stay in this function: handed out through an array parameter they cost the SSIM map kernel 6 VGPRs.)
 template <int Q, class Finish>
 __device__ __forceinline__ auto corner_window(const double* S, int H, int W, int i, int j, int ws, Finish finish) {
   const int pad = ws / 2, iper = W + 1;
@@ -396,32 +396,15 @@ __global__ __launch_bounds__(256) void ssim_finish_kernel(const double* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// Per-pixel anomaly maps: 1 - the SSIM map of ONE window size (the `ssim_map` src/metrics.py:66 averages), from the same float64
-// tables and with the same per-pixel arithmetic as the sweep, but one output value per pixel and no reduction.  One thread per
-// pixel, any width; the reflection pairs of either axis are skipped by wave-uniform branches when no lane of the wave needs them.
-__global__ __launch_bounds__(256) void ssim_map_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W, int ws,
-                                                       double dinv, int nblk) {
-  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
-  const int npix = H * W;
-  const int p = pb * 256 + (int)threadIdx.x;
-  const int pix = min(p, npix - 1);                                      // lanes past the end compute a copy of the last pixel
-  const int i = pix / W, j = pix - i * W;
-  const size_t plane = (size_t)(H + 1) * (W + 1);
-  const float m = corner_ssim(sat + (size_t)img * kQ * plane, H, W, i, j, ws, dinv);
-  if (p < npix) out[(size_t)img * npix + p] = 1.0f - m;
-}
+// Per-pixel maps: one fp32 value per pixel and window size from an image's float64 tables, reduced over the `g` window sizes of
+// `wl` to ONE value per pixel without a map per size in memory.  What a value is made of is the map's source, a trait struct
+// (SsimSrc and SqerrSrc, with their host sides, below): `planes` tables per image, and value(S, H, W, i, j, ws, factor) = the map
+// value of pixel (i, j) at window size ws, with `factor` the size's host-computed double (WsList::dinv).  Either source reads its
+// window through corner_window: the reflection pairs of either axis are skipped by wave-uniform branches when no lane needs them.
 
-// Multi-scale anomaly maps: the maps 1 - ssim_map of the `g` window sizes of `wl` reduced to ONE value per pixel, without a map
-// per size in memory.  A pixel's thread walks the list in order with the arithmetic of ssim_map_kernel (corner_ssim) and keeps
-// one fp32 accumulator:   mean: a_1 = 1 - m_1, a_k = a_(k-1) + (1 - m_k), out = a_K * scale      max: a_k = fmaxf(a_(k-1), 1 - m_k)
-// - single IEEE fp32 operations in list order, so the result is the bits of the K single maps accumulated the same way.  Lists
-// longer than kWsGroup take several launches: `first` = 0 continues from the accumulator the launch before stored in `out`
-// (same thread, same pixel, stream order), and only the last launch of a mean gets scale = (float)(1 / K) (1 otherwise; a
-// multiply by a host-computed factor, not a division).  The loop over the sizes stays a loop: unrolled over the runtime count
-// it would hold several sizes' index sets in registers.
-// ROWS = the width is a multiple of 64: a wave's 64 pixels lie in one row, the row index is scalar (as in ssim_eval_kernel).
 // The pixel of a map kernel's thread (blocks of 256 pixels, `pb` = the block within the image): p = its index, which the caller
 // compares with npix before it stores, and (i, j) = the pixel it computes.
+// ROWS = the width is a multiple of 64: a wave's 64 pixels lie in one row, the row index is scalar (as in ssim_eval_kernel).
 template <bool ROWS>
 __device__ __forceinline__ void map_pixel(int pb, int npix, int W, int& p, int& i, int& j) {
   p = pb * 256 + (int)threadIdx.x;
@@ -434,21 +417,36 @@ __device__ __forceinline__ void map_pixel(int pb, int npix, int W, int& p, int& 
     i = pix / W; j = pix - i * W;
   }
 }
-template <bool ROWS>
-__global__ __launch_bounds__(256) void ssim_map_multi_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W,
-                                                             const WsList wl, int g, int reduce_max, int first, float scale, int nblk) {
+// A pixel's thread walks the list in order and keeps one fp32 accumulator:
+//   mean: a_1 = v_1, a_k = a_(k-1) + v_k, out = a_K * scale      max: a_k = fmaxf(a_(k-1), v_k)
+// - single IEEE fp32 operations in list order, so the result is the bits of the K single maps accumulated the same way.  Lists
+// longer than kWsGroup take several launches: `first` = 0 continues from the accumulator the launch before stored in `out`
+// (same thread, same pixel, stream order), and only the last launch of a mean gets scale = (float)(1 / K) (1 otherwise; a
+// multiply by a host-computed factor, not a division).  The map of ONE size is g = 1, first = 1, scale = 1: v_1 * 1.0f.  The
+// loop over the sizes stays a loop: unrolled over the runtime count it would hold several sizes' index sets in registers.
+// ONE = the list has one size: v_1 is stored as it is, without the loop and the read-back (the same bits).  The squared-error
+// maps take it, their value being so little work that the loop's bookkeeping shows: at 8 x 1024 px and ws 11 a call takes 0.106 ms
+// with it and 0.112 ms without; the SSIM maps of one size are as fast through the loop.
+template <class Src, bool ROWS, bool ONE = false>
+__global__ __launch_bounds__(256) void window_map_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W,
+                                                         const WsList wl, int g, int reduce_max, int first, float scale, int nblk) {
 #pragma clang fp contract(off)
   const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
   const int npix = H * W;
   int p, i, j;
   map_pixel<ROWS>(pb, npix, W, p, i, j);
-  const double* const S = sat + (size_t)img * kQ * ((size_t)(H + 1) * (W + 1));
+  const double* const S = sat + (size_t)img * Src::planes * ((size_t)(H + 1) * (W + 1));
   float* const dst = out + (size_t)img * npix + p;
+  if constexpr (ONE) {
+    const float v = Src::value(S, H, W, i, j, wl.ws[0], wl.dinv[0]);
+    if (p < npix) *dst = v;
+    return;
+  }
   float acc = 0.0f;
   if (!first && p < npix) acc = *dst;
 #pragma unroll 1
   for (int k = 0; k < g; ++k) {
-    const float v = 1.0f - corner_ssim(S, H, W, i, j, wl.ws[k], wl.dinv[k]);
+    const float v = Src::value(S, H, W, i, j, wl.ws[k], wl.dinv[k]);
     if (first && k == 0) acc = v;
     else acc = reduce_max ? fmaxf(acc, v) : acc + v;
   }
@@ -499,42 +497,6 @@ __global__ __launch_bounds__(256) void sqerr_rows_kernel(const uint8_t* __restri
     if (c < W) base[c + 1] = s;
     carry = __shfl(s, 63);
   }
-}
-
-// The map of ONE window size: one thread per pixel, one multiply and one fp32 store.  ROWS as in ssim_map_multi_kernel.
-template <bool ROWS>
-__global__ __launch_bounds__(256) void sqerr_map_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W, int ws,
-                                                        double inv, int nblk) {
-  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
-  const int npix = H * W;
-  int p, i, j;
-  map_pixel<ROWS>(pb, npix, W, p, i, j);
-  const double S = corner_sqerr(sat + (size_t)img * ((size_t)(H + 1) * (W + 1)), H, W, i, j, ws);
-  if (p < npix) out[(size_t)img * npix + p] = (float)(S * inv);
-}
-
-// Multi-scale: the maps of the `g` sizes of `wl` (dinv = each size's `inv`) reduced per pixel with the accumulation, the `first`
-// / `scale` protocol and the launch splitting of ssim_map_multi_kernel, so the result is the bits of the single maps accumulated
-// in list order.
-template <bool ROWS>
-__global__ __launch_bounds__(256) void sqerr_map_multi_kernel(const double* __restrict__ sat, float* __restrict__ out, int H, int W,
-                                                              const WsList wl, int g, int reduce_max, int first, float scale, int nblk) {
-#pragma clang fp contract(off)
-  const int img = blockIdx.x / nblk, pb = blockIdx.x - img * nblk;
-  const int npix = H * W;
-  int p, i, j;
-  map_pixel<ROWS>(pb, npix, W, p, i, j);
-  const double* const S = sat + (size_t)img * ((size_t)(H + 1) * (W + 1));
-  float* const dst = out + (size_t)img * npix + p;
-  float acc = 0.0f;
-  if (!first && p < npix) acc = *dst;
-#pragma unroll 1
-  for (int k = 0; k < g; ++k) {
-    const float v = (float)(corner_sqerr(S, H, W, i, j, wl.ws[k]) * wl.dinv[k]);
-    if (first && k == 0) acc = v;
-    else acc = reduce_max ? fmaxf(acc, v) : acc + v;
-  }
-  if (p < npix) *dst = acc * scale;
 }
 
 // ws = 1 alone needs no table: out = (float)((double)e * inv) straight from the two stacks, 2 C bytes read and 4 B written per
@@ -767,8 +729,104 @@ int check_window(const char* what, int ws, int H, int W) {
   return SRAD_OK;
 }
 
-// the factor of a squared-error map value: 1 / (C ws^2 255^2), a host double like WsList::dinv
-inline double sqerr_inv(int C, int ws) { return 1.0 / ((double)C * (double)ws * (double)ws * 65025.0); }
+// The sources of window_map_kernel.  Device side: `planes` and value().  Host side: one_size_instance = a list of one size takes
+// the kernel's ONE instance, factor(C, ws) = the double value() is handed
+// for a window size, build = the tables of a chunk, and the SradProfScope figures of a map launch per pixel: operations (per
+// window size) and algorithmic bytes.
+//
+// SsimSrc: 1 - the SSIM map of one window size (the `ssim_map` src/metrics.py:66 averages), from the sweep's tables and with its
+// per-pixel arithmetic (corner_ssim); factor = 1 / ws^2.  Bytes: the two fp32 luminance planes read once, the fp32 map written once.
+struct SsimSrc {
+  static constexpr int planes = kQ;
+  static constexpr bool one_size_instance = false;
+  static constexpr auto build = build_tables;
+  static constexpr double ops_px = 40.0;
+  static double bytes_px(int) { return 12.0; }
+  static double factor(int, int ws) { return 1.0 / ((double)ws * (double)ws); }
+  static __device__ __forceinline__ float value(const double* S, int H, int W, int i, int j, int ws, double factor) {
+    return 1.0f - corner_ssim(S, H, W, i, j, ws, factor);
+  }
+};
+// SqerrSrc: the squared-error map (above); factor = 1 / (C ws^2 255^2).  Bytes: the two u8 stacks read once, the fp32 map written once.
+struct SqerrSrc {
+  static constexpr int planes = 1;
+  static constexpr bool one_size_instance = true;
+  static constexpr auto build = build_sqerr_table;
+  static constexpr double ops_px = 10.0;
+  static double bytes_px(int C) { return 2.0 * C + 4.0; }
+  static double factor(int C, int ws) { return 1.0 / ((double)C * (double)ws * (double)ws * 65025.0); }
+  static __device__ __forceinline__ float value(const double* S, int H, int W, int i, int j, int ws, double factor) {
+    return (float)(corner_sqerr(S, H, W, i, j, ws) * factor);
+  }
+};
+
+// The window sizes ws[0 .. g) of one launch (g <= kWsGroup), each with its source's factor.
+template <class Src>
+WsList fill_ws_list(const int32_t* ws, int g, int C) {
+  WsList wl{};
+  for (int k = 0; k < g; ++k) { wl.ws[k] = (int)ws[k]; wl.dinv[k] = Src::factor(C, wl.ws[k]); }
+  return wl;
+}
+
+int map_workspace_bytes(const char* what, int planes, int n_img, int H, int W, size_t* bytes) {
+  SRAD_REQUIRE(bytes && n_img > 0 && H > 0 && W > 0, "%s: bad argument", what);
+  *bytes = plan_score_ws(n_img, H, W, false, nullptr, planes).bytes;
+  return SRAD_OK;
+}
+
+// The squared-error maps of window size 1 straight from the stacks (sqerr_pixel_kernel).
+int sqerr_pixel_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, float* map_out, hipStream_t s) {
+  const size_t img_bytes = (size_t)H * W * C, npix = (size_t)n_img * H * W, groups = (npix + 3) / 4;
+  SRAD_REQUIRE((groups + 255) / 256 < (1ull << 31), "error_maps: %d %dx%d images are too many pixels for one launch", n_img, H, W);
+  const int vec = (reinterpret_cast<uintptr_t>(sr) | reinterpret_cast<uintptr_t>(hr)) % 4 == 0 && reinterpret_cast<uintptr_t>(map_out) % 16 == 0;
+  SradProfScope prof(s, SRAD_K_SCORE, 3.0 * n_img * img_bytes, 2.0 * n_img * img_bytes + 4.0 * npix);
+  const dim3 grid((unsigned)((groups + 255) / 256));
+  const double inv = SqerrSrc::factor(C, 1);
+  if (C == 1) hipLaunchKernelGGL(sqerr_pixel_kernel<1>, grid, dim3(256), 0, s, sr, hr, map_out, npix, inv, vec);
+  else hipLaunchKernelGGL(sqerr_pixel_kernel<3>, grid, dim3(256), 0, s, sr, hr, map_out, npix, inv, vec);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+// The four map entry points: the maps of the sizes ws_host[0 .. n_ws) of source Src reduced per pixel (reduce: 0 mean, 1 max)
+// into map_out; `what` (the entry point) starts each message.  Every size is checked before anything is launched.
+template <class Src>
+int run_maps(const char* what, const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host, int n_ws,
+             int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream) {
+  SRAD_REQUIRE(map_out, "%s: bad argument", what);
+  SRAD_REQUIRE(ws_host && n_ws >= 1, "%s: the window list is empty", what);
+  SRAD_REQUIRE(reduce == 0 || reduce == 1, "%s: reduce must be 0 (mean) or 1 (max), got %d", what, reduce);
+  SRAD_TRY(check_pairs(what, sr, hr, workspace, n_img, H, W, C));
+  for (int k = 0; k < n_ws; ++k) SRAD_TRY(check_window(what, ws_host[k], H, W));
+  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace, Src::planes);
+  SRAD_REQUIRE(workspace_bytes >= w.bytes, "%s: workspace %zu bytes, %zu needed", what, workspace_bytes, w.bytes);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const size_t img_bytes = (size_t)H * W * C;
+  if constexpr (std::is_same<Src, SqerrSrc>::value)
+    if (n_ws == 1 && ws_host[0] == 1) return sqerr_pixel_maps(sr, hr, n_img, H, W, C, map_out, s);      // no window: no table
+  const int nblk = (H * W + 255) / 256;
+  const float inv_k = (float)(1.0 / (double)n_ws);
+  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
+    const int n = std::min(w.chunk, n_img - i0);
+    Src::build(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
+    float* const out = map_out + (size_t)i0 * H * W;
+    const dim3 grid((unsigned)((size_t)nblk * n));
+    for (int k0 = 0; k0 < n_ws; k0 += kWsGroup) {      // up to kWsGroup window sizes per launch; later launches continue from `out`
+      const int g = std::min(kWsGroup, n_ws - k0);
+      const WsList wl = fill_ws_list<Src>(ws_host + k0, g, C);
+      const int first = k0 == 0;
+      const float scale = (reduce == 0 && k0 + g == n_ws) ? inv_k : 1.0f;
+      SradProfScope prof(s, SRAD_K_SCORE, Src::ops_px * n * H * W * g, Src::bytes_px(C) * n * H * W);
+      const bool rows = W % 64 == 0;
+      auto kernel = rows ? window_map_kernel<Src, true> : window_map_kernel<Src, false>;
+      if constexpr (Src::one_size_instance)
+        if (n_ws == 1) kernel = rows ? window_map_kernel<Src, true, true> : window_map_kernel<Src, false, true>;
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce, first, scale, nblk);
+    }
+  }
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
 
 }  // namespace
 
@@ -823,8 +881,7 @@ int srad_score_pairs(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int
     build_tables(w, srp, hrp, n, H, W, C, s);
     for (int k0 = 0; k0 < n_ws; k0 += kWsGroup) {      // up to kWsGroup window sizes per launch
       const int g = std::min(kWsGroup, n_ws - k0);
-      WsList wl{};
-      for (int k = 0; k < g; ++k) { wl.ws[k] = (int)ws_host[k0 + k]; wl.dinv[k] = 1.0 / ((double)wl.ws[k] * (double)wl.ws[k]); }
+      const WsList wl = fill_ws_list<SsimSrc>(ws_host + k0, g, C);
       {
         // algorithmic bytes per (pair, window): the two fp32 luminance planes read once
         SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W * g, 8.0 * n * H * W * g);
@@ -861,149 +918,35 @@ int srad_score_plan(int n_img, int H, int W, int* kernel, int* chunk) {
 }
 
 int srad_anomaly_map_workspace_bytes(int n_img, int H, int W, size_t* bytes) {
-  SRAD_REQUIRE(bytes && n_img > 0 && H > 0 && W > 0, "anomaly_map_workspace_bytes: bad argument");
-  *bytes = plan_score_ws(n_img, H, W, false, nullptr).bytes;
-  return SRAD_OK;
+  return map_workspace_bytes("anomaly_map_workspace_bytes", SsimSrc::planes, n_img, H, W, bytes);
 }
 
 int srad_anomaly_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out,
                       void* workspace, size_t workspace_bytes, void* stream) {
-  SRAD_REQUIRE(map_out, "anomaly_maps: bad argument");
-  SRAD_TRY(check_pairs("anomaly_maps", sr, hr, workspace, n_img, H, W, C));
-  SRAD_TRY(check_window("anomaly_maps", ws, H, W));
-  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace);
-  SRAD_REQUIRE(workspace_bytes >= w.bytes, "anomaly_maps: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nblk = (H * W + 255) / 256;
-  const size_t img_bytes = (size_t)H * W * C;
-  const double dinv = 1.0 / ((double)ws * (double)ws);
-  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
-    const int n = std::min(w.chunk, n_img - i0);
-    build_tables(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
-    // algorithmic bytes: the two fp32 luminance planes read once, the fp32 map written once
-    SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W, 12.0 * n * H * W);
-    hipLaunchKernelGGL(ssim_map_kernel, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, w.sat, map_out + (size_t)i0 * H * W, H, W,
-                       ws, dinv, nblk);
-  }
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
+  const int32_t one = ws;
+  return run_maps<SsimSrc>("anomaly_maps", sr, hr, n_img, H, W, C, &one, 1, 0, map_out, workspace, workspace_bytes, stream);
 }
 
 int srad_anomaly_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host, int n_ws,
                             int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream) {
-  SRAD_REQUIRE(map_out, "anomaly_maps_multi: bad argument");
-  SRAD_REQUIRE(ws_host && n_ws >= 1, "anomaly_maps_multi: the window list is empty");
-  SRAD_REQUIRE(reduce == 0 || reduce == 1, "anomaly_maps_multi: reduce must be 0 (mean) or 1 (max), got %d", reduce);
-  SRAD_TRY(check_pairs("anomaly_maps_multi", sr, hr, workspace, n_img, H, W, C));
-  for (int k = 0; k < n_ws; ++k) SRAD_TRY(check_window("anomaly_maps_multi", ws_host[k], H, W));
-  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace);
-  SRAD_REQUIRE(workspace_bytes >= w.bytes, "anomaly_maps_multi: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nblk = (H * W + 255) / 256;
-  const size_t img_bytes = (size_t)H * W * C;
-  const float inv_k = (float)(1.0 / (double)n_ws);
-  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
-    const int n = std::min(w.chunk, n_img - i0);
-    build_tables(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
-    float* const out = map_out + (size_t)i0 * H * W;
-    for (int k0 = 0; k0 < n_ws; k0 += kWsGroup) {      // up to kWsGroup window sizes per launch; later launches continue from `out`
-      const int g = std::min(kWsGroup, n_ws - k0);
-      WsList wl{};
-      for (int k = 0; k < g; ++k) { wl.ws[k] = (int)ws_host[k0 + k]; wl.dinv[k] = 1.0 / ((double)wl.ws[k] * (double)wl.ws[k]); }
-      const int first = k0 == 0;
-      const float scale = (reduce == 0 && k0 + g == n_ws) ? inv_k : 1.0f;
-      // algorithmic bytes: the two fp32 luminance planes read once, the fp32 map written once
-      SradProfScope prof(s, SRAD_K_SCORE, 40.0 * n * H * W * g, 12.0 * n * H * W);
-      if (W % 64 == 0)
-        hipLaunchKernelGGL(ssim_map_multi_kernel<true>, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce,
-                           first, scale, nblk);
-      else
-        hipLaunchKernelGGL(ssim_map_multi_kernel<false>, dim3((unsigned)((size_t)nblk * n)), dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce,
-                           first, scale, nblk);
-    }
-  }
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
+  return run_maps<SsimSrc>("anomaly_maps_multi", sr, hr, n_img, H, W, C, ws_host, n_ws, reduce, map_out, workspace, workspace_bytes, stream);
 }
 
 int srad_error_map_workspace_bytes(int n_img, int H, int W, size_t* bytes) {
-  SRAD_REQUIRE(bytes && n_img > 0 && H > 0 && W > 0, "error_map_workspace_bytes: bad argument");
-  *bytes = plan_score_ws(n_img, H, W, false, nullptr, 1).bytes;
-  return SRAD_OK;
+  return map_workspace_bytes("error_map_workspace_bytes", SqerrSrc::planes, n_img, H, W, bytes);
 }
 
-// the per-pixel form of the MSE score of src/evaluate.py:251-265
+// the per-pixel form of the MSE score of src/evaluate.py:251-265; ws = 1 takes the table-free sqerr_pixel_kernel
 int srad_error_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int ws, float* map_out, void* workspace,
                     size_t workspace_bytes, void* stream) {
-  SRAD_REQUIRE(map_out, "error_maps: bad argument");
-  SRAD_TRY(check_pairs("error_maps", sr, hr, workspace, n_img, H, W, C));
-  SRAD_TRY(check_window("error_maps", ws, H, W));
-  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace, 1);
-  SRAD_REQUIRE(workspace_bytes >= w.bytes, "error_maps: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t img_bytes = (size_t)H * W * C;
-  const double inv = sqerr_inv(C, ws);
-  if (ws == 1) {                                       // no window: no table
-    const size_t npix = (size_t)n_img * H * W, groups = (npix + 3) / 4;
-    SRAD_REQUIRE((groups + 255) / 256 < (1ull << 31), "error_maps: %d %dx%d images are too many pixels for one launch", n_img, H, W);
-    const int vec = (reinterpret_cast<uintptr_t>(sr) | reinterpret_cast<uintptr_t>(hr)) % 4 == 0 && reinterpret_cast<uintptr_t>(map_out) % 16 == 0;
-    SradProfScope prof(s, SRAD_K_SCORE, 3.0 * n_img * img_bytes, 2.0 * n_img * img_bytes + 4.0 * npix);
-    const dim3 grid((unsigned)((groups + 255) / 256));
-    if (C == 1) hipLaunchKernelGGL(sqerr_pixel_kernel<1>, grid, dim3(256), 0, s, sr, hr, map_out, npix, inv, vec);
-    else hipLaunchKernelGGL(sqerr_pixel_kernel<3>, grid, dim3(256), 0, s, sr, hr, map_out, npix, inv, vec);
-    SRAD_CHECK_HIP(hipGetLastError());
-    return SRAD_OK;
-  }
-  const int nblk = (H * W + 255) / 256;
-  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
-    const int n = std::min(w.chunk, n_img - i0);
-    build_sqerr_table(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
-    // algorithmic bytes: the two u8 stacks read once, the fp32 map written once
-    SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W, 2.0 * n * img_bytes + 4.0 * n * H * W);
-    const dim3 grid((unsigned)((size_t)nblk * n));
-    float* const out = map_out + (size_t)i0 * H * W;
-    if (W % 64 == 0) hipLaunchKernelGGL(sqerr_map_kernel<true>, grid, dim3(256), 0, s, w.sat, out, H, W, ws, inv, nblk);
-    else hipLaunchKernelGGL(sqerr_map_kernel<false>, grid, dim3(256), 0, s, w.sat, out, H, W, ws, inv, nblk);
-  }
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
+  const int32_t one = ws;
+  return run_maps<SqerrSrc>("error_maps", sr, hr, n_img, H, W, C, &one, 1, 0, map_out, workspace, workspace_bytes, stream);
 }
 
-// the multi-scale form of srad_error_maps (the MSE score of src/evaluate.py:251-265 per pixel and window)
+// the multi-scale form of srad_error_maps; a list of one size is that size's srad_error_maps
 int srad_error_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host, int n_ws,
                           int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream) {
-  SRAD_REQUIRE(map_out, "error_maps_multi: bad argument");
-  SRAD_REQUIRE(ws_host && n_ws >= 1, "error_maps_multi: the window list is empty");
-  SRAD_REQUIRE(reduce == 0 || reduce == 1, "error_maps_multi: reduce must be 0 (mean) or 1 (max), got %d", reduce);
-  SRAD_TRY(check_pairs("error_maps_multi", sr, hr, workspace, n_img, H, W, C));
-  for (int k = 0; k < n_ws; ++k) SRAD_TRY(check_window("error_maps_multi", ws_host[k], H, W));
-  const ScoreWs w = plan_score_ws(n_img, H, W, false, workspace, 1);
-  SRAD_REQUIRE(workspace_bytes >= w.bytes, "error_maps_multi: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
-  if (n_ws == 1) return srad_error_maps(sr, hr, n_img, H, W, C, ws_host[0], map_out, workspace, workspace_bytes, stream);   // K = 1: the single map
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nblk = (H * W + 255) / 256;
-  const size_t img_bytes = (size_t)H * W * C;
-  const float inv_k = (float)(1.0 / (double)n_ws);
-  for (int i0 = 0; i0 < n_img; i0 += w.chunk) {
-    const int n = std::min(w.chunk, n_img - i0);
-    build_sqerr_table(w, sr + (size_t)i0 * img_bytes, hr + (size_t)i0 * img_bytes, n, H, W, C, s);
-    float* const out = map_out + (size_t)i0 * H * W;
-    for (int k0 = 0; k0 < n_ws; k0 += kWsGroup) {      // up to kWsGroup window sizes per launch; later launches continue from `out`
-      const int g = std::min(kWsGroup, n_ws - k0);
-      WsList wl{};
-      for (int k = 0; k < g; ++k) { wl.ws[k] = (int)ws_host[k0 + k]; wl.dinv[k] = sqerr_inv(C, wl.ws[k]); }
-      const int first = k0 == 0;
-      const float scale = (reduce == 0 && k0 + g == n_ws) ? inv_k : 1.0f;
-      SradProfScope prof(s, SRAD_K_SCORE, 10.0 * n * H * W * g, 2.0 * n * img_bytes + 4.0 * n * H * W);
-      const dim3 grid((unsigned)((size_t)nblk * n));
-      if (W % 64 == 0)
-        hipLaunchKernelGGL(sqerr_map_multi_kernel<true>, grid, dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce, first, scale, nblk);
-      else
-        hipLaunchKernelGGL(sqerr_map_multi_kernel<false>, grid, dim3(256), 0, s, w.sat, out, H, W, wl, g, reduce, first, scale, nblk);
-    }
-  }
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
+  return run_maps<SqerrSrc>("error_maps_multi", sr, hr, n_img, H, W, C, ws_host, n_ws, reduce, map_out, workspace, workspace_bytes, stream);
 }
 
 int srad_val_metrics(const float* sr, const float* hr, int B, int C, int H, int W, float rgb_range, double* psnr_out,

@@ -50,14 +50,19 @@ def quantize(x: torch.Tensor, rgb_range: float = 255.0) -> torch.Tensor:
     return y
 
 
+def _u8_stacks(sr_u8: torch.Tensor, hr_u8: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The [n,H,W,C] uint8 GPU image stacks (SR, HR) of the scorer's entry points, checked and contiguous."""
+    _need_cuda(sr_u8, hr_u8)
+    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
+    return sr_u8.contiguous(), hr_u8.contiguous()
+
+
 def score_pairs(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Sequence[int]
                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Per-pair scores of [n,H,W,C] uint8 image stacks (SR, HR):
     ssim[n, len(window_sizes)] = ssim_numpy(hr/255, sr/255, ws) (src/metrics.py:26-67), mse[n], psnr[n]
     (float64 tensors on the GPU)."""
-    _need_cuda(sr_u8, hr_u8)
-    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
-    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
+    sr_u8, hr_u8 = _u8_stacks(sr_u8, hr_u8)
     n, H, W, Cc = sr_u8.shape
     ws = (C.c_int32 * max(1, len(window_sizes)))(*[int(w) for w in window_sizes])
     dev = sr_u8.device
@@ -111,20 +116,32 @@ def roc_auc(y_true: Sequence[int], scores: Sequence[float]) -> float:
     return out.value
 
 
-def anomaly_maps(sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws: int) -> torch.Tensor:
-    """Per-pixel anomaly maps ``1 - ssim_map`` of [n,H,W,C] uint8 image stacks (SR, HR) at window size ``ws``: the map
-    ``ssim_numpy(hr/255, sr/255, ws)`` averages (src/metrics.py:26-67).  Returns float32 [n,H,W] on the GPU."""
-    _need_cuda(sr_u8, hr_u8)
-    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
-    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
+MAP_REDUCTIONS = ("mean", "max")           # srad_*_maps_multi's reduce numbers 0, 1
+def _maps(query: str, fn: str, sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws, reduce: Optional[str] = None) -> torch.Tensor:
+    """float32 [n,H,W] maps of the stacks from ``srad_<fn>`` (workspace size from ``srad_<query>``): ``ws`` is one window size,
+    or with ``reduce`` the checked list of ``_map_sizes``."""
+    sr_u8, hr_u8 = _u8_stacks(sr_u8, hr_u8)
     n, H, W, Cc = sr_u8.shape
+    sizes = (int(ws),) if reduce is None else ((C.c_int32 * len(ws))(*ws), len(ws), MAP_REDUCTIONS.index(reduce))
     out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
-    _call_with_ws("anomaly_map_workspace_bytes", (n, H, W), "anomaly_maps",
-                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, int(ws), L.dptr(out)), sr_u8.device)
+    _call_with_ws(query, (n, H, W), fn, (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, *sizes, L.dptr(out)), sr_u8.device)
     return out
 
 
-MAP_REDUCTIONS = ("mean", "max")           # srad_anomaly_maps_multi's reduce numbers 0, 1
+def _map_sizes(fn: str, window_sizes: Sequence[int], reduce: str) -> List[int]:
+    """The window sizes of a multi-scale map call as ints; ValueError (led by ``fn``) for an unknown ``reduce`` or an empty list."""
+    if reduce not in MAP_REDUCTIONS:
+        raise ValueError(f"{fn}: reduce = {reduce!r}, must be one of {MAP_REDUCTIONS}")
+    sizes = [int(w) for w in window_sizes]
+    if not sizes:
+        raise ValueError(f"{fn}: the window-size list is empty")
+    return sizes
+
+
+def anomaly_maps(sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws: int) -> torch.Tensor:
+    """Per-pixel anomaly maps ``1 - ssim_map`` of [n,H,W,C] uint8 image stacks (SR, HR) at window size ``ws``: the map
+    ``ssim_numpy(hr/255, sr/255, ws)`` averages (src/metrics.py:26-67).  Returns float32 [n,H,W] on the GPU."""
+    return _maps("anomaly_map_workspace_bytes", "anomaly_maps", sr_u8, hr_u8, ws)
 
 
 def anomaly_maps_multi(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Sequence[int], reduce: str = "mean") -> torch.Tensor:
@@ -133,20 +150,8 @@ def anomaly_maps_multi(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: S
     the result is bit for bit ``acc = acc + anomaly_maps(.., ws_k)`` then ``acc * float32(1 / K)`` (``torch.maximum`` for 'max');
     a size listed twice counts twice.  Returns float32 [n,H,W] on the GPU.  ValueError for an empty list or an unknown
     ``reduce``; RuntimeError for a size ``anomaly_maps`` refuses."""
-    if reduce not in MAP_REDUCTIONS:
-        raise ValueError(f"anomaly_maps_multi: reduce = {reduce!r}, must be one of {MAP_REDUCTIONS}")
-    sizes = [int(w) for w in window_sizes]
-    if not sizes:
-        raise ValueError("anomaly_maps_multi: the window-size list is empty")
-    _need_cuda(sr_u8, hr_u8)
-    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
-    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
-    n, H, W, Cc = sr_u8.shape
-    ws = (C.c_int32 * len(sizes))(*sizes)
-    out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
-    _call_with_ws("anomaly_map_workspace_bytes", (n, H, W), "anomaly_maps_multi",
-                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, ws, len(sizes), MAP_REDUCTIONS.index(reduce), L.dptr(out)), sr_u8.device)
-    return out
+    sizes = _map_sizes("anomaly_maps_multi", window_sizes, reduce)
+    return _maps("anomaly_map_workspace_bytes", "anomaly_maps_multi", sr_u8, hr_u8, sizes, reduce)
 
 
 MAP_SOURCES = ("ssim", "mse")              # what the evaluator's pixel-level maps are made of (--map-source)
@@ -158,14 +163,7 @@ def error_maps(sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws: int = 1) -> torch.T
     ``anomaly_maps``, the map is ``float32(float64(S) * (1.0 / (C * ws * ws * 65025)))`` bit for bit (DESIGN.md "Squared-error
     maps"); ``ws = 1`` is the raw per-pixel squared error, whose mean is the image's MSE.  Returns float32 [n,H,W] on the GPU,
     values in [0, 1].  RuntimeError for a window ``anomaly_maps`` refuses."""
-    _need_cuda(sr_u8, hr_u8)
-    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
-    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
-    n, H, W, Cc = sr_u8.shape
-    out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
-    _call_with_ws("error_map_workspace_bytes", (n, H, W), "error_maps",
-                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, int(ws), L.dptr(out)), sr_u8.device)
-    return out
+    return _maps("error_map_workspace_bytes", "error_maps", sr_u8, hr_u8, ws)
 
 
 def error_maps_multi(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Sequence[int], reduce: str = "mean") -> torch.Tensor:
@@ -173,20 +171,8 @@ def error_maps_multi(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Seq
     ``anomaly_maps_multi`` reduces its maps, so the result is bit for bit ``acc = acc + error_maps(.., ws_k)`` in list order then
     ``acc * float32(1 / K)`` (``torch.maximum`` for 'max'); a size listed twice counts twice.  Returns float32 [n,H,W] on the
     GPU.  ValueError for an empty list or an unknown ``reduce``; RuntimeError for a size ``error_maps`` refuses."""
-    if reduce not in MAP_REDUCTIONS:
-        raise ValueError(f"error_maps_multi: reduce = {reduce!r}, must be one of {MAP_REDUCTIONS}")
-    sizes = [int(w) for w in window_sizes]
-    if not sizes:
-        raise ValueError("error_maps_multi: the window-size list is empty")
-    _need_cuda(sr_u8, hr_u8)
-    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
-    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
-    n, H, W, Cc = sr_u8.shape
-    ws = (C.c_int32 * len(sizes))(*sizes)
-    out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
-    _call_with_ws("error_map_workspace_bytes", (n, H, W), "error_maps_multi",
-                  (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, ws, len(sizes), MAP_REDUCTIONS.index(reduce), L.dptr(out)), sr_u8.device)
-    return out
+    sizes = _map_sizes("error_maps_multi", window_sizes, reduce)
+    return _maps("error_map_workspace_bytes", "error_maps_multi", sr_u8, hr_u8, sizes, reduce)
 
 
 def check_map_scales(window_sizes: Sequence[int], H: int, W: int) -> List[int]:

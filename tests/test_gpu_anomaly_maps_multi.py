@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(128, 1), (64, 3), (33, 1)]
 TWENTY = list(range(3, 42, 2))                               # 20 sizes: two launches (16 + 4)
+SEVENTEEN = [3] * 16 + [11]                                  # a second launch of exactly one size, continued from the stored accumulator
 
 
 def _dev(a):
@@ -33,7 +34,7 @@ def _compose(sr, hr, sizes, reduce):
 
 def _lists(size):
     from srad_amd import metrics as M
-    return [[11], [3, 11, 21], [21, 3, 11], M.sweep_window_sizes(size), TWENTY]
+    return [[11], [3, 11, 21], [21, 3, 11], M.sweep_window_sizes(size), TWENTY, SEVENTEEN]
 
 
 @pytest.mark.parametrize("reduce", ["mean", "max"])
@@ -57,6 +58,18 @@ def test_bit_identical_to_the_composition(size, ch, reduce):
     # a size listed twice counts twice
     twice = M.anomaly_maps_multi(sr, hr, [11, 11, 3], reduce)
     assert torch.equal(twice, _compose(sr, hr, [11, 11, 3], reduce))
+
+
+@pytest.mark.parametrize("H,W,C", [(33, 45, 1), (64, 64, 3)])
+def test_a_list_of_one_size_is_the_single_map(H, W, C):
+    """The smallest windows and the largest that fits, per-lane instance (33 x 45) and scalar-row instance (64 x 64)."""
+    from srad_amd import metrics as M
+    from tests.test_gpu_error_maps import random_pairs
+    sr, hr = (_dev(a) for a in random_pairs(2, H, W, C, seed=21))
+    for ws in (1, 2, 2 * min(H, W) - 1):
+        single = M.anomaly_maps(sr, hr, ws)
+        for reduce in ("mean", "max"):
+            assert torch.equal(M.anomaly_maps_multi(sr, hr, [ws], reduce), single), (H, W, C, ws, reduce)
 
 
 @pytest.mark.parametrize("reduce", ["mean", "max"])

@@ -140,6 +140,7 @@ def test_wide_sums():
 
 
 TWENTY = list(range(3, 42, 2))                               # 20 sizes: two launches (16 + 4)
+SEVENTEEN = [3] * 16 + [11]                                  # a second launch of exactly one size, continued from the stored accumulator
 
 
 def _compose(sr, hr, sizes, reduce):
@@ -161,13 +162,25 @@ def test_multi_scale_equals_the_composition(H, W, C, reduce):
     assert len(TWENTY) == 20
     sr, hr = random_pairs(2, H, W, C, seed=11)
     dsr, dhr = _dev(sr), _dev(hr)
-    for sizes in ([11], [3, 11, 21], [21, 3, 11], [5, 5], TWENTY, [1], [1, 4]):
+    for sizes in ([11], [3, 11, 21], [21, 3, 11], [5, 5], TWENTY, SEVENTEEN, [1], [1, 4]):
         got = M.error_maps_multi(dsr, dhr, sizes, reduce)
         assert got.dtype == torch.float32 and tuple(got.shape) == (2, H, W)
         assert torch.equal(got, _compose(dsr, dhr, sizes, reduce)), (sizes, reduce)
         assert torch.equal(got.cpu(), torch.from_numpy(multi_ref(sr, hr, sizes, reduce))), (sizes, reduce)
     assert torch.equal(M.error_maps_multi(dsr, dhr, [11], reduce), M.error_maps(dsr, dhr, 11))
     assert torch.equal(M.error_maps_multi(dsr, dhr, (4,)), M.error_maps(dsr, dhr, 4))            # reduce defaults to the mean
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W,C", [(33, 45, 1), (64, 64, 3)])
+def test_a_list_of_one_size_is_the_single_map(H, W, C):
+    """Window size 1 (no table), the smallest table window and the largest that fits, per-lane and scalar-row instance."""
+    from srad_amd import metrics as M
+    dsr, dhr = (_dev(a) for a in random_pairs(2, H, W, C, seed=21))
+    for ws in (1, 2, 2 * min(H, W) - 1):
+        single = M.error_maps(dsr, dhr, ws)
+        for reduce in ("mean", "max"):
+            assert torch.equal(M.error_maps_multi(dsr, dhr, [ws], reduce), single), (H, W, C, ws, reduce)
 
 
 @pytest.mark.gpu
