@@ -17,18 +17,18 @@
 // 2. Keys: (~order_key(score)) << 32 | region size.  An ascending sort of the high words walks the scores from highest down
 //    (a NaN keeps 0xFFFFFFFF, which no number maps to, and sorts last).  Three radix passes at shifts 32 / 43 / 54 (pixel_sort.h);
 //    the sort is stable, so the region size rides along in the low word.
-// 3. One scan of the sorted keys.  An ok pixel adds 1 to the fpr numerator (u64); a pixel of region r adds floor(2^64 / |r|) to
-//    the pro numerator, a 128-bit fixed-point sum.  Integer addition is associative, so the curve does not depend on the order
-//    of the pixels inside a tie group or of the images; the error against the exact rational is below n 2^-64 / R.  The curve's
-//    points are the ends of tie groups.  The predecessor of a group end is the previous group end, i.e. the prefix just before
-//    its own group's head; it is carried across threads and tiles like the AUC's neg_before at the last head (both prefixes
-//    never decrease, so a componentwise running max over heads finds it).  Each segment's trapezoid (and the one interpolated
-//    at L) is computed in float64, and the areas are reduced in a fixed tree order.
+// 3. The tie-group scan of the sorted keys (tie_scan.h), with the pixels of one score as a group.  The prefix: an ok pixel adds
+//    1 to the fpr numerator (u64); a pixel of region r adds floor(2^64 / |r|) to the pro numerator, a 128-bit fixed-point sum.
+//    Integer addition is associative, so the curve does not depend on the order of the pixels inside a tie group or of the
+//    images; the error against the exact rational is below n 2^-64 / R.  The curve's points are the ends of tie groups, and the
+//    predecessor of a group end is the previous group end, i.e. the prefix just before its own group's head, which is what the
+//    scan hands over.  Each segment's trapezoid (and the one interpolated at L) is computed in float64, and the areas are
+//    reduced in a fixed tree order.
 //
 // NaN scores are left out of the curve and counted in n_nan; the host side refuses them.
 #include "engine.h"
 #include "../../include/srad.h"
-#include "pixel_sort.h"
+#include "tie_scan.h"
 #include "pixel_pro.h"
 #include <algorithm>
 #include <math.h>
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void mask_sizes_kernel(const uint8_t* __restri
   }
 }
 
-// ---------------------------------------------------------------- 3. the curve scan, in scan tiles of 4096 (thread t: keys t * 16 ..)
+// ---------------------------------------------------------------- 3. the curve, as a tie_scan.h policy
 // Pref, PrefAdd and pro_add (the 128-bit fixed-point pro numerator and the ok-pixel count) live in pixel_pro.h.
 __device__ __forceinline__ bool pw_less(const Pref& a, const Pref& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
 struct PrefMax {      // componentwise: both parts never decrease along the walk, so this is the value at the later position
@@ -235,21 +235,6 @@ struct PrefMax {      // componentwise: both parts never decrease along the walk
     return Pref{b_more ? b.lo : a.lo, b_more ? b.hi : a.hi, a.ok > b.ok ? a.ok : b.ok, 0};
   }
 };
-
-struct ProTile {
-  Pref sum;          // over the tile's non-NaN keys
-  Pref head;         // prefix (within the tile) just before the tile's last group head; meaningful when has_head
-  Pref off;          // prefix before the tile
-  Pref lt_in;        // prefix just before the last group head before the tile
-  uint32_t nan, ends, has_head, end_off;   // end_off: group ends before the tile
-  double area;
-};
-
-__device__ __forceinline__ uint32_t hi32(uint64_t k) { return (uint32_t)(k >> 32); }
-__device__ __forceinline__ bool is_head(const uint64_t* keys, int64_t i, uint32_t hi) { return i == 0 || hi32(keys[i - 1]) != hi; }
-__device__ __forceinline__ bool is_end(const uint64_t* keys, int64_t i, int64_t n, uint32_t hi) {
-  return i == n - 1 || hi32(keys[i + 1]) != hi;
-}
 
 // (fpr, pro) of a prefix, each clipped at 1
 __device__ __forceinline__ void pro_point(const Pref& p, double n_ok, double n_reg, double& f, double& r) {
@@ -266,128 +251,35 @@ __device__ __forceinline__ double seg_area(double f0, double p0, double f1, doub
   return 0.0;
 }
 
-// A thread's 16 keys: their sum, the prefix (within the thread) just before its last head, its NaN and group-end counts.
-struct ThreadRun {
-  Pref own, head;
-  uint32_t nan, ends, has_head;
+// Each group end: its curve point, the segment from the previous group end, the curve write.
+struct ProScan {
+  using Prefix = Pref;
+  using Add = PrefAdd;
+  using Max = PrefMax;
+  using Acc = double;
+  struct Args {
+    const unsigned long long* counts;      // {regions, ok pixels}, on the device
+    double L;
+    double *curve_fpr, *curve_pro;
+    int64_t cap;
+  };
+  Args a;
+  double n_reg, n_ok;
+  __device__ explicit ProScan(const Args& args) : a(args), n_reg((double)args.counts[0]), n_ok((double)args.counts[1]) {}
+  static __device__ __forceinline__ uint32_t group(uint64_t key) { return (uint32_t)(key >> 32); }
+  static __device__ __forceinline__ void add(Pref& p, uint64_t key) { pro_add(p, key); }
+  __device__ __forceinline__ double at_end(const Pref& before_head, const Pref& through_end, int64_t idx) const {
+    double f0, p0, f1, p1;
+    pro_point(before_head, n_ok, n_reg, f0, p0);
+    pro_point(through_end, n_ok, n_reg, f1, p1);
+    if (a.curve_fpr && idx + 1 < a.cap) {
+      a.curve_fpr[idx + 1] = f1;
+      a.curve_pro[idx + 1] = p1;
+    }
+    return seg_area(f0, p0, f1, p1, a.L);
+  }
 };
-__device__ __forceinline__ ThreadRun thread_run(const uint64_t* keys, int64_t b, int64_t n) {
-  ThreadRun t{};
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    const int64_t i = b + k;
-    if (i >= n) break;
-    const uint64_t key = keys[i];
-    const uint32_t hi = hi32(key);
-    if (hi == kNanKey) {
-      ++t.nan;
-      continue;
-    }
-    if (is_head(keys, i, hi)) {
-      t.head = t.own;
-      t.has_head = 1u;
-    }
-    pro_add(t.own, key);
-    if (is_end(keys, i, n, hi)) ++t.ends;
-  }
-  return t;
-}
-
-__global__ __launch_bounds__(256) void pro_tile_counts_kernel(const uint64_t* __restrict__ keys, ProTile* __restrict__ tiles, int64_t n) {
-  __shared__ Pref shp[256];
-  __shared__ uint32_t sh[256];
-  const ThreadRun t = thread_run(keys, (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems, n);
-  ProTile& o = tiles[blockIdx.x];
-  Pref tsum;
-  const Pref ex = block_scan_excl<Pref>(t.own, Pref{}, PrefAdd{}, shp, tsum);
-  if (threadIdx.x == 0) o.sum = tsum;
-  // the last head's prefix is the block-wide max, i.e. the inclusive max-scan at thread 255 (kept out of a Pref-typed total,
-  // which the compiler sends to scratch)
-  const Pref hv = t.has_head ? PrefAdd{}(ex, t.head) : Pref{};
-  Pref unused;
-  const Pref hex = block_scan_excl<Pref>(hv, Pref{}, PrefMax{}, shp, unused);
-  if (threadIdx.x == 255) o.head = PrefMax{}(hex, hv);
-  uint32_t tnan, tends, thas;
-  block_scan_excl<uint32_t>(t.nan, 0u, AddOp{}, sh, tnan);
-  block_scan_excl<uint32_t>(t.ends, 0u, AddOp{}, sh, tends);
-  block_scan_excl<uint32_t>(t.has_head, 0u, MaxOp{}, sh, thas);
-  if (threadIdx.x == 0) {
-    o.nan = tnan;
-    o.ends = tends;
-    o.has_head = thas;
-  }
-}
-
-// one block: the prefix before each tile, the prefix before the last head before each tile, the group ends before each tile
-__global__ __launch_bounds__(256) void pro_tiles_scan_kernel(ProTile* __restrict__ tiles, int nt) {
-  __shared__ Pref shp[256];
-  __shared__ uint32_t sh[256];
-  Pref carry{}, lt_carry{};
-  uint32_t end_carry = 0;
-  for (int c0 = 0; c0 < nt; c0 += 256) {
-    const int t = c0 + threadIdx.x;
-    ProTile x{};
-    if (t < nt) x = tiles[t];
-    Pref stot, htot;
-    const Pref off = PrefAdd{}(carry, block_scan_excl<Pref>(x.sum, Pref{}, PrefAdd{}, shp, stot));
-    const Pref hv = x.has_head ? PrefAdd{}(off, x.head) : Pref{};
-    const Pref lt = PrefMax{}(lt_carry, block_scan_excl<Pref>(hv, Pref{}, PrefMax{}, shp, htot));
-    uint32_t etot;
-    const uint32_t eoff = end_carry + block_scan_excl<uint32_t>(x.ends, 0u, AddOp{}, sh, etot);
-    if (t < nt) {
-      tiles[t].off = off;
-      tiles[t].lt_in = lt;
-      tiles[t].end_off = eoff;
-    }
-    carry = PrefAdd{}(carry, stot);
-    lt_carry = PrefMax{}(lt_carry, htot);
-    end_carry += etot;
-  }
-}
-
-// Each group end in the tile: its curve point, the segment from the previous group end, the curve write.
-__global__ __launch_bounds__(256) void pro_tile_area_kernel(const uint64_t* __restrict__ keys, ProTile* __restrict__ tiles, int64_t n,
-                                                            const unsigned long long* __restrict__ counts, double L,
-                                                            double* __restrict__ curve_fpr, double* __restrict__ curve_pro, int64_t cap) {
-  __shared__ Pref shp[256];
-  __shared__ uint32_t sh[256];
-  __shared__ double shd[256];
-  const int64_t b = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  const Pref off = tiles[blockIdx.x].off, lt_in = tiles[blockIdx.x].lt_in;
-  const uint32_t end_off = tiles[blockIdx.x].end_off;
-  const double n_reg = (double)counts[0], n_ok = (double)counts[1];
-  const ThreadRun t = thread_run(keys, b, n);
-  Pref tot;
-  Pref cur = PrefAdd{}(off, block_scan_excl<Pref>(t.own, Pref{}, PrefAdd{}, shp, tot));    // prefix before this thread's keys
-  Pref lt = PrefMax{}(lt_in, block_scan_excl<Pref>(t.has_head ? PrefAdd{}(cur, t.head) : Pref{}, Pref{}, PrefMax{}, shp, tot));
-  uint32_t etot;
-  int64_t idx = (int64_t)end_off + block_scan_excl<uint32_t>(t.ends, 0u, AddOp{}, sh, etot);   // curve index - 1 of its next end
-  double area = 0.0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    const int64_t i = b + k;
-    if (i >= n) break;
-    const uint64_t key = keys[i];
-    const uint32_t hi = hi32(key);
-    if (hi == kNanKey) continue;
-    if (is_head(keys, i, hi)) lt = cur;
-    pro_add(cur, key);
-    if (is_end(keys, i, n, hi)) {
-      double f0, p0, f1, p1;
-      pro_point(lt, n_ok, n_reg, f0, p0);
-      pro_point(cur, n_ok, n_reg, f1, p1);
-      area += seg_area(f0, p0, f1, p1, L);
-      if (curve_fpr && idx + 1 < cap) {
-        curve_fpr[idx + 1] = f1;
-        curve_pro[idx + 1] = p1;
-      }
-      ++idx;
-    }
-  }
-  double atot;
-  block_scan_excl<double>(area, 0.0, AddOp{}, shd, atot);
-  if (threadIdx.x == 0) tiles[blockIdx.x].area = atot;
-}
+using ProTile = TieTile<ProScan>;
 
 // one block: the areas in a fixed order, the last segment to (1, 1), the end points of the curve, the counts
 __global__ __launch_bounds__(256) void pro_finish_kernel(const ProTile* __restrict__ tiles, int nt, unsigned long long* __restrict__ counts,
@@ -403,7 +295,7 @@ __global__ __launch_bounds__(256) void pro_finish_kernel(const ProTile* __restri
     sum = PrefAdd{}(sum, tiles[t].sum);
     nan += tiles[t].nan;
     ends += tiles[t].ends;
-    area += tiles[t].area;
+    area += tiles[t].acc;
   }
   Pref tsum;
   uint64_t tnan, tends;
@@ -452,26 +344,6 @@ int launch_regions(const uint8_t* masks, int n_img, int H, int W, int64_t n, uin
   return SRAD_OK;
 }
 
-struct ProLayout {
-  int n_sort_tiles, n_scan_tiles;
-  size_t keys_a, keys_b, offs, tsum, tiles, total;
-};
-ProLayout pro_layout(int64_t n) {
-  ProLayout L{};
-  L.n_sort_tiles = (int)((n + kSortTile - 1) / kSortTile);
-  L.n_scan_tiles = (int)((n + kScanTile - 1) / kScanTile);
-  const int64_t m = (int64_t)kDigits * L.n_sort_tiles;
-  const int64_t n_count_tiles = (m + kScanTile - 1) / kScanTile;
-  size_t o = 0;
-  L.keys_a = o; o += srad_align_up((size_t)n * 8, 256);
-  L.keys_b = o; o += srad_align_up((size_t)n * 8, 256);     // also parent[] and the region sizes before the first radix pass
-  L.offs = o;   o += srad_align_up((size_t)m * 4, 256);
-  L.tsum = o;   o += srad_align_up((size_t)n_count_tiles * 4, 256);
-  L.tiles = o;  o += srad_align_up((size_t)L.n_scan_tiles * sizeof(ProTile), 256);
-  L.total = o;
-  return L;
-}
-
 }  // namespace
 
 extern "C" {
@@ -502,7 +374,7 @@ int srad_pixel_pro_workspace_bytes(int n_img, int H, int W, size_t* bytes) {
   int64_t n;
   SRAD_TRY(check_shape(n_img, H, W, "pixel_pro_workspace_bytes", n));
   SRAD_REQUIRE(bytes, "pixel_pro_workspace_bytes: bytes is NULL");
-  *bytes = pro_layout(n).total;
+  *bytes = sorted_keys_layout(n, sizeof(ProTile)).total;
   return SRAD_OK;
 }
 
@@ -516,32 +388,20 @@ int srad_pixel_pro(const float* scores, const uint8_t* masks, int n_img, int H, 
                "pixel_pro: curve_fpr and curve_pro must both be given or both be NULL, curve_cap >= 0");
   int64_t n;
   SRAD_TRY(check_shape(n_img, H, W, "pixel_pro", n));
-  const ProLayout L = pro_layout(n);
+  const SortedKeysLayout L = sorted_keys_layout(n, sizeof(ProTile));
   SRAD_REQUIRE(workspace_bytes >= L.total, "pixel_pro: workspace %zu bytes, %zu needed", workspace_bytes, L.total);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
-  uint64_t* ka = reinterpret_cast<uint64_t*>(ws + L.keys_a);
-  uint64_t* kb = reinterpret_cast<uint64_t*>(ws + L.keys_b);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(ws + L.offs);
-  uint32_t* tsum = reinterpret_cast<uint32_t*>(ws + L.tsum);
   ProTile* tiles = reinterpret_cast<ProTile*>(ws + L.tiles);
   unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_out);
   if (!curve_fpr) curve_cap = 0;
-  uint32_t* parent = reinterpret_cast<uint32_t*>(kb);          // kb is free until the first radix pass scatters into it
-  SRAD_TRY(launch_regions(masks, n_img, H, W, n, parent, parent + n, counts, scores, ka, s));
-  uint64_t* src = ka;
-  uint64_t* dst = kb;
-  for (int p = 0; p < kPasses; ++p) {
-    SradProfScope prof(s, SRAD_K_SCORE, 0.0, 24.0 * n + 16.0 * kDigits * L.n_sort_tiles);
-    radix_sort_pass(src, dst, offs, tsum, n, 32 + p * kDigitBits, L.n_sort_tiles, s);
-    std::swap(src, dst);
-  }
+  // the second key buffer is free until the first radix pass scatters into it: it holds parent[] and the region sizes
+  uint32_t* parent = reinterpret_cast<uint32_t*>(ws + L.keys_b);
+  SRAD_TRY(launch_regions(masks, n_img, H, W, n, parent, parent + n, counts, scores, reinterpret_cast<uint64_t*>(ws + L.keys_a), s));
+  const uint64_t* sorted = radix_sort_keys(ws, L, n, 32, s);
   {
     SradProfScope prof(s, SRAD_K_SCORE, 0.0, 16.0 * n);
-    hipLaunchKernelGGL(pro_tile_counts_kernel, dim3(L.n_scan_tiles), dim3(256), 0, s, src, tiles, n);
-    hipLaunchKernelGGL(pro_tiles_scan_kernel, dim3(1), dim3(256), 0, s, tiles, L.n_scan_tiles);
-    hipLaunchKernelGGL(pro_tile_area_kernel, dim3(L.n_scan_tiles), dim3(256), 0, s, src, tiles, n, counts, fpr_limit, curve_fpr,
-                       curve_pro, curve_cap);
+    tie_scan_launch<ProScan>(sorted, tiles, n, L.n_scan_tiles, ProScan::Args{counts, fpr_limit, curve_fpr, curve_pro, curve_cap}, s);
     hipLaunchKernelGGL(pro_finish_kernel, dim3(1), dim3(256), 0, s, tiles, L.n_scan_tiles, counts, fpr_limit, aupro_out, curve_fpr,
                        curve_pro, curve_cap);
   }

@@ -1,9 +1,11 @@
-// pixel_sort.h - the device sort shared by the pixel-level metrics (kernels_pixel_auc.hip, kernels_pixel_pro.hip).
+// pixel_sort.h - the device sort of the sort-based pixel metrics (kernels_pixel_auc.hip, kernels_pixel_pro.hip, through
+// tie_scan.h, which holds their workspace layout, the three-pass driver and the scan of the sorted keys).
 //
 // LSD radix sort of u64 keys on 11-bit digits: a pass is a per-tile LDS histogram (tile = 8192 keys), an exclusive scan of the
 // [digit][tile] count matrix, and a stable scatter.  A caller picks the digits with the shifts it passes: the AUC sorts its 33-bit
 // keys at shifts 0 / 11 / 22, AU-PRO sorts the high 32 bits of its keys at 32 / 43 / 54 and lets the low word ride along.  Also
-// here: the order-preserving u32 of a float, and the 256-thread block scan both scans are built from.
+// here, and used by kernels_operating_point.hip and kernels_map_smooth.hip as well: the order-preserving u32 of a float, and the
+// 256-thread block scan every scan is built from.
 #pragma once
 #include "engine.h"
 #include <algorithm>

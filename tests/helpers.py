@@ -31,3 +31,50 @@ def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+# ---- constructed tie groups for the sort-based pixel metrics (scan tile = 4096 keys, 16 per thread, 256 tiles per chunk) ----
+# Group heads at sorted positions 0, 1, 16, 32, 49, 4095, 4096, 4097, 4098 and 8191; the group from 8191 runs past 20480, so scan
+# tiles 2, 3 and 4 hold no head; a few short groups follow, and n = 20807 is no multiple of 16.
+TIE_SMALL = [1, 15, 16, 17, 4046, 1, 1, 1, 4093, 12293, 2, 14, 300, 7]
+TIE_CHUNK_N = 1031 * 1023
+
+
+def tie_chunk_lengths():
+    """n = 1031 * 1023 keys: lengths cycling 1..64 and one filler group up to key 255 * 4096 - 7, a group of 4096 + 32 keys from
+    there (it crosses key 256 * 4096, where the one-block tile scan starts its second chunk, and tile 255 has no head), then
+    groups of 5 and a last shorter one."""
+    start = 255 * 4096 - 7
+    lengths, total, k = [], 0, 0
+    while start - total >= k % 64 + 1:
+        lengths.append(k % 64 + 1)
+        total += lengths[-1]
+        k += 1
+    if start > total:
+        lengths.append(start - total)
+    assert sum(lengths) == start and max(lengths) <= 64
+    lengths.append(4096 + 32)
+    rest = TIE_CHUNK_N - start - (4096 + 32)
+    lengths += [5] * (rest // 5) + ([rest % 5] if rest % 5 else [])
+    assert sum(lengths) == TIE_CHUNK_N
+    return lengths
+
+
+def pad_last_group(lengths, n):
+    """The list with its last group lengthened so that the lengths add up to n."""
+    assert n >= sum(lengths)
+    return list(lengths[:-1]) + [lengths[-1] + n - sum(lengths)]
+
+
+def tie_group_case(lengths, descending, seed):
+    """Scores and labels whose sorted walk meets tie groups of exactly `lengths`, in that order: group j has the score j / 64 for
+    an ascending walk, (G - j) / 64 for a descending one (exact in float32), labels are random at p = 0.37, and the whole is
+    shuffled.  Returns (float32 scores, uint8 labels)."""
+    G = len(lengths)
+    assert G < (1 << 18)
+    rng = np.random.default_rng(seed)
+    j = np.repeat(np.arange(G), lengths)
+    s = ((G - j) if descending else j).astype(np.float32) / np.float32(64)
+    y = (rng.random(len(s)) < 0.37).astype(np.uint8)
+    p = rng.permutation(len(s))
+    return s[p], y[p]

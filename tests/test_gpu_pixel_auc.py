@@ -1,12 +1,16 @@
 """GPU: exact pixel-level ROC-AUC (srad_pixel_roc_auc: device radix sort + Mann-Whitney scan) against scikit-learn's
 roc_auc_score (tests/golden/pixel_auc_golden.npz, written by tests/golden/make_pixel_auc_golden.py) and against a vectorised
-numpy Mann-Whitney U.  Bar: 1e-12, and bit-identical results under permutation of the input and across calls."""
+numpy Mann-Whitney U.  Bar: 1e-12, and bit-identical results under permutation of the input and across calls.  Constructed
+tie groups (tests/helpers.py) on the scan's thread, tile and chunk boundaries are compared as integers."""
+import ctypes as C
 import importlib.util
 import os
 
 import numpy as np
 import pytest
 import torch
+
+from tests.helpers import TIE_SMALL, tie_chunk_lengths, tie_group_case
 
 pytestmark = pytest.mark.gpu
 
@@ -31,14 +35,34 @@ def _auc(s, y):
     return M.pixel_roc_auc(torch.from_numpy(np.ascontiguousarray(s)).cuda(), torch.from_numpy(np.ascontiguousarray(y)).cuda())
 
 
-def mann_whitney_auc(s, y):
-    """sum over tie groups g of pos_g * (2 * negatives below g + neg_g) / (2 * n_pos * n_neg), in int64."""
+def mann_whitney_counts(s, y):
+    """(n_pos, n_neg, twice_U): twice_U = sum over tie groups g of pos_g * (2 * negatives below g + neg_g), in int64."""
     vals, inv = np.unique(s.astype(np.float64), return_inverse=True)
     pos = np.bincount(inv[y != 0], minlength=len(vals)).astype(np.int64)
     neg = np.bincount(inv[y == 0], minlength=len(vals)).astype(np.int64)
     below = np.concatenate([[0], np.cumsum(neg)[:-1]])
-    twice_u = int(np.sum(pos * (2 * below + neg)))
-    return twice_u / (2.0 * int(pos.sum()) * int(neg.sum()))
+    return int(pos.sum()), int(neg.sum()), int(np.sum(pos * (2 * below + neg)))
+
+
+def mann_whitney_auc(s, y):
+    """twice_U / (2 * n_pos * n_neg)."""
+    n_pos, n_neg, twice_u = mann_whitney_counts(s, y)
+    return twice_u / (2.0 * n_pos * n_neg)
+
+
+def _auc_raw(s, y):
+    """srad_pixel_roc_auc's counts {n_pos, n_neg, n_nan, twice_U} and its double, straight from the C entry point."""
+    from srad_amd import _lib as L
+    from srad_amd import metrics as M
+    st, yt = torch.from_numpy(np.ascontiguousarray(s)).cuda(), torch.from_numpy(np.ascontiguousarray(y)).cuda()
+    counts = torch.empty(4, dtype=torch.int64, device="cuda")
+    auc = torch.empty((), dtype=torch.float64, device="cuda")
+    nb = C.c_size_t()
+    L.check(L.lib().srad_pixel_auc_workspace_bytes(C.c_int64(len(s)), C.byref(nb)))
+    keep, wp, wb = M._ws_buffer(nb.value, st.device)
+    L.check(L.lib().srad_pixel_roc_auc(L.dptr(st), L.dptr(yt), C.c_int64(len(s)), L.dptr(counts), L.dptr(auc), wp, wb,
+                                       L.current_stream_ptr()))
+    return counts.tolist(), float(auc.item())
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -96,3 +120,23 @@ def test_one_class_and_nan_raise():
     s[17] = float("nan")
     with pytest.raises(ValueError, match="NaN"):
         M.pixel_roc_auc(s, y)
+
+
+@pytest.mark.parametrize("case", ["small", "chunk"])
+def test_constructed_tie_groups_exact(case):
+    s, y = tie_group_case(TIE_SMALL if case == "small" else tie_chunk_lengths(), descending=False, seed=3)
+    n_pos, n_neg, twice_u = mann_whitney_counts(s, y)
+    assert twice_u < 2 ** 53                                      # so the float division below is exact
+    counts, auc = _auc_raw(s, y)
+    assert counts == [n_pos, n_neg, 0, twice_u]
+    assert auc == twice_u / (2.0 * n_pos * n_neg)
+
+
+def test_constructed_tie_groups_with_nan_exact():
+    s, y = tie_group_case(TIE_SMALL, descending=False, seed=3)
+    bad = np.random.default_rng(5).choice(len(s), 37, replace=False)
+    s[bad] = np.nan
+    keep = ~np.isnan(s)
+    n_pos, n_neg, twice_u = mann_whitney_counts(s[keep], y[keep])
+    counts, _ = _auc_raw(s, y)
+    assert counts == [n_pos, n_neg, 37, twice_u]

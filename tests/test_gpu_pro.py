@@ -1,6 +1,8 @@
 """GPU: region labelling (srad_mask_regions) and AU-PRO (srad_pixel_pro) against tests/golden/pro_golden.npz (scipy.ndimage
 labels and the numpy restatement of the definition, written by tests/golden/make_pro_golden.py), against an in-test pure-Python
-union-find labeller on random masks, and for bit-identical results across calls and image orders.  No scipy or sklearn here."""
+union-find labeller on random masks, and for bit-identical results across calls and image orders; constructed tie groups
+(tests/helpers.py) put group heads and a headless tile on the scan's thread, tile and chunk boundaries.  No scipy or sklearn
+here."""
 import ctypes as C
 import importlib.util
 import os
@@ -8,6 +10,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+from tests.helpers import TIE_CHUNK_N, TIE_SMALL, pad_last_group, tie_chunk_lengths, tie_group_case
 
 pytestmark = pytest.mark.gpu
 
@@ -158,3 +162,40 @@ def test_mask_dtypes_agree():
         got = (size.cpu().numpy().tobytes(), R, M.aupro(s, _cuda(mm)), M.aupro(s, _cuda(mm), 0.1))
         ref = ref or got
         assert got == ref
+
+
+def _rectangles(H, W, step_y, step_x, max_h, max_w):
+    """A mask of non-touching axis-aligned rectangles on a (step_y, step_x) grid, and every pixel's region size; R."""
+    assert max_h < step_y and max_w < step_x
+    m, z, k = np.zeros((1, H, W), np.uint8), np.zeros((1, H, W), np.int64), 0
+    for y0 in range(2, H - max_h, step_y):
+        for x0 in range(3, W - max_w, step_x):
+            h, w = 1 + (k * 37) % max_h, 1 + (k * 53) % max_w
+            m[0, y0:y0 + h, x0:x0 + w] = 1
+            z[0, y0:y0 + h, x0:x0 + w] = h * w
+            k += 1
+    return m, z, k
+
+
+@pytest.mark.parametrize("case", ["small", "chunk"])
+def test_constructed_tie_groups(case):
+    from srad_amd import metrics as M
+    G = _generator()
+    if case == "small":
+        H, W = 131, 159
+        lengths = pad_last_group(TIE_SMALL, H * W)
+        m, z, R = _rectangles(H, W, 23, 29, 17, 19)
+    else:
+        H, W = 1031, 1023
+        lengths = tie_chunk_lengths()
+        assert H * W == TIE_CHUNK_N
+        m, z, R = _rectangles(H, W, 97, 101, 90, 95)
+    s, _ = tie_group_case(lengths, descending=True, seed=3)
+    s = s.reshape(1, H, W)
+    fpr, pro = G.pro_curve_ref(s, z, R)
+    st, mt = _cuda(s), _cuda(m)
+    gf, gp = M.pro_curve(st, mt)
+    assert len(gf) == len(lengths) + 2
+    assert np.max(np.abs(gf - fpr)) <= 1e-9 and np.max(np.abs(gp - pro)) <= 1e-9
+    for L in (0.3, 0.01, 1.0):
+        assert abs(M.aupro(st, mt, L) - G.aupro_ref(fpr, pro, L)) <= 1e-9
