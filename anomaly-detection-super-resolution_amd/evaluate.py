@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import os
 import re
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from pathlib import Path
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -131,26 +131,24 @@ def load_masks(data_root: str, classe: str, names: Sequence[Tuple[str, str]], hr
     return masks, missing
 
 
+def _save_gray(u8: np.ndarray, folder: str, names: Sequence[str], splits: Sequence[str], output_dir: str) -> None:
+    """``<output_dir>/<folder>/{good,bad}/<name>.png`` of the 8-bit gray images ``u8`` [n,H,W]."""
+    from PIL import Image
+    for k, (name, split) in enumerate(zip(names, splits)):
+        d = Path(output_dir) / folder / split
+        d.mkdir(parents=True, exist_ok=True)
+        Image.fromarray(u8[k]).save(str(d / f"{name}.png"))
+
+
 def save_anomaly_maps(maps: torch.Tensor, names: Sequence[str], splits: Sequence[str], output_dir: str) -> None:
     """``<output_dir>/anomaly_maps/{good,bad}/<name>.png``: 8-bit gray of ``255 * clip(map, 0, 1)``, truncated (the u8 conversion
     of the evaluator at rgb_range 1)."""
-    from PIL import Image
-    u8 = M.to_u8_hwc(maps[:, None], rgb_range=1.0).cpu().numpy()
-    for k, (name, split) in enumerate(zip(names, splits)):
-        d = Path(output_dir) / 'anomaly_maps' / split
-        d.mkdir(parents=True, exist_ok=True)
-        Image.fromarray(u8[k, :, :, 0]).save(str(d / f"{name}.png"))
+    _save_gray(M.to_u8_hwc(maps[:, None], rgb_range=1.0).cpu().numpy()[..., 0], 'anomaly_maps', names, splits, output_dir)
 
 
 def save_masks(pred: torch.Tensor, names: Sequence[str], splits: Sequence[str], output_dir: str) -> None:
     """``<output_dir>/anomaly_masks/{good,bad}/<name>.png``: the predicted masks (uint8 {0, 1} [n,H,W]) as 8-bit gray, 0 / 255."""
-    from PIL import Image
-    u8 = (pred * 255).cpu().numpy()
-    for k, (name, split) in enumerate(zip(names, splits)):
-        d = Path(output_dir) / 'anomaly_masks' / split
-        d.mkdir(parents=True, exist_ok=True)
-        Image.fromarray(u8[k]).save(str(d / f"{name}.png"))
-
+    _save_gray((pred * 255).cpu().numpy(), 'anomaly_masks', names, splits, output_dir)
 
 @dataclass
 class OperatingPoint:
@@ -192,6 +190,78 @@ def resolve_map_scales(map_scales, H: int, W: int) -> List[int]:
             raise ValueError(f"map_scales = {map_scales!r}: a list of window sizes or 'sweep'")
         map_scales = M.sweep_window_sizes(min(H, W))
     return M.check_map_scales(map_scales, H, W)
+
+
+@dataclass(frozen=True)
+class MapSpec:
+    """What the pixel-level anomaly maps are made of.  ``source``: 'ssim' = ``1 - SSIM map``, 'mse' = the squared-error maps of
+    ``metrics.error_maps`` (DESIGN.md "Squared-error maps").  One window size ``ws``, or ``scales`` in its place: a list of
+    window sizes, or 'sweep' for every size of the image-level sweep, reduced per pixel by ``reduce`` ('mean' or 'max';
+    ``metrics.anomaly_maps_multi``).  ``sigma`` > 0: the maps are smoothed once with that Gaussian sigma
+    (``metrics.smooth_maps``) before anything is saved or scored.  ``ws`` 0 without scales means the SSIM sweep's best_ws for
+    'ssim' - the one value only rank 0 knows (``needs_best_ws``) - and window size 1, the raw squared error, for 'mse'.
+    The test images and the calibration images get their maps from one spec (``make``), and the spec words what it adds to
+    the result (``entries``) and what the printed lines call the maps (``text``).  An unknown source is a ValueError
+    when the spec is made, before anything else; ``resolve`` checks the rest against the image size."""
+    source: str = 'ssim'
+    ws: int = 0
+    scales: object = ()
+    reduce: str = 'mean'
+    sigma: float = 0.0
+
+    def __post_init__(self):
+        if self.source not in M.MAP_SOURCES:
+            raise ValueError(f"map_source = {self.source!r}, must be one of {M.MAP_SOURCES}")
+
+    def check_sigma(self, H: int, W: int) -> None:
+        """ValueError for a sigma that H x W maps cannot be smoothed with: negative, or a radius above min(128, H, W)."""
+        if self.sigma:
+            M.smooth_radius(self.sigma, H, W)
+
+    def check_scales(self, H: int, W: int) -> List[int]:
+        """The scales as a list of sizes; [] without scales, and ``reduce`` is then not looked at.  ValueError for scales together
+        with a non-zero ``ws``, an unknown ``reduce``, and a size that H x W images are too small for."""
+        if not (isinstance(self.scales, str) or len(self.scales)):
+            return []
+        if int(self.ws):
+            raise ValueError("map_scales and a non-zero map_ws exclude each other")
+        if self.reduce not in M.MAP_REDUCTIONS:
+            raise ValueError(f"map_reduce = {self.reduce!r}, must be one of {M.MAP_REDUCTIONS}")
+        return resolve_map_scales(self.scales, H, W)
+
+    def resolve(self, H: int, W: int) -> 'MapSpec':
+        """The spec for H x W images with its scales a list of sizes, after both checks."""
+        self.check_sigma(H, W)
+        return replace(self, ws=int(self.ws), scales=self.check_scales(H, W), sigma=float(self.sigma))
+
+    @property
+    def needs_best_ws(self) -> bool:
+        """The single case in which rank 0's sweep result has to reach the other ranks."""
+        return self.source == 'ssim' and not self.scales and int(self.ws) <= 0
+
+    def make(self, sr: torch.Tensor, hr: torch.Tensor, with_max: bool):
+        """(maps of the (sr, hr) u8 stacks, their per-image maxima or None without ``with_max``)."""
+        one, multi = (M.error_maps, M.error_maps_multi) if self.source == 'mse' else (M.anomaly_maps, M.anomaly_maps_multi)
+        maps = multi(sr, hr, self.scales, self.reduce) if self.scales else one(sr, hr, self.ws)
+        if with_max:
+            return M.smooth_maps(maps, self.sigma, with_max=True)
+        return (M.smooth_maps(maps, self.sigma) if self.sigma > 0 else maps), None
+
+    def entries(self, found: dict) -> dict:
+        """The result entries of these maps around ``found``: ``map_source`` (for 'mse' only), ``map_ws`` or ``map_scales`` and
+        ``map_reduce``, then ``found``, then ``map_sigma`` when it is above 0."""
+        out = dict(map_source=self.source) if self.source == 'mse' else {}
+        out.update(dict(map_scales=list(self.scales), map_reduce=self.reduce) if self.scales else dict(map_ws=self.ws), **found)
+        if self.sigma > 0:
+            out["map_sigma"] = self.sigma
+        return out
+
+    def text(self, extra: str = '', always_sigma: bool = False) -> str:
+        """What a printed line calls these maps, as in ``SSIM map (ws=11, fpr <= 0.3, sigma=4)``: ``extra`` comes before the
+        sigma, which is left out at 0 unless ``always_sigma``."""
+        what = f"scales={list(self.scales)}, {self.reduce}" if self.scales else f"ws={self.ws}"
+        sigma = f", sigma={self.sigma:g}" if self.sigma > 0 or always_sigma else ""
+        return f"{'MSE' if self.source == 'mse' else 'SSIM'} map ({what}{extra}{sigma})"
 
 
 def shard_indices(n: int, rank: int, world: int) -> List[int]:
@@ -241,6 +311,45 @@ def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndar
     return torch.cat(sr_out), hr
 
 
+@dataclass
+class Shard:
+    """One rank's share of the test split: the (sr, hr) u8 stacks of the images ``mine`` (indices into the whole split) next to
+    what every rank knows of the whole split - the labels ``y_true`` and the ``names``, which may be fewer than the images."""
+    sr: torch.Tensor
+    hr: torch.Tensor
+    mine: Sequence[int]
+    y_true: Sequence[int]
+    names: Sequence[str] = ()
+    rank: int = 0
+    world: int = 1
+    output_dir: str = ''
+
+    def my_names(self) -> List[str]:
+        return [self.names[i] if i < len(self.names) else f"{i:05d}" for i in self.mine]
+
+    def my_splits(self) -> List[str]:
+        return ['good' if self.y_true[i] == 0 else 'bad' for i in self.mine]
+
+
+@dataclass(frozen=True)
+class Request:
+    """What was asked of the pixel stage; ``op`` is a checked ``OperatingPoint`` or None."""
+    save_maps: bool = False
+    map_image_score: bool = False
+    pixel_metrics: bool = False
+    aupro: bool = False
+    pro_fpr_limit: float = 0.3
+    op: Optional[OperatingPoint] = None
+
+    @property
+    def scored(self) -> bool:                                 # what needs a mask for every image
+        return bool(self.pixel_metrics or self.aupro)
+
+    @property
+    def single(self) -> bool:                                 # what runs on one rank only
+        return self.scored or self.op is not None
+
+
 def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], bad: Sequence[Tuple[np.ndarray, np.ndarray]],
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
@@ -251,211 +360,167 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
     writes the SR images it produced under ``output_dir/{good,bad}/x{scale}`` (src/evaluate.py:190-224).
 
-    Pixel level (off by default): the anomaly maps ``1 - SSIM map`` of each rank's own images at window size ``map_ws``
-    (0 = the sweep's best_ws).  ``save_maps``: every rank writes them under ``output_dir/anomaly_maps/{good,bad}``.
-    ``pixel_metrics``: with world 1 and a mask for every image (``masks``, good + bad order, as ``load_masks`` returns them)
-    the exact pixel-level ROC-AUC is added as ``auc_pixel``, with ``map_ws``.  ``aupro``: under the same conditions the
-    normalised area under the per-region overlap curve up to ``pro_fpr_limit`` is added as ``aupro``, with ``pro_fpr_limit`` and
-    ``map_ws``; the maps are computed once for both.  ``map_sigma`` > 0: the maps are smoothed once with that Gaussian sigma
-    (``metrics.smooth_maps``) before they are saved or scored, and ``map_sigma`` is added beside ``map_ws``.
-    ``map_image_score``: the ROC-AUC of each image's map maximum as ``auc_map_max``, with ``map_ws``; no masks needed, and
-    with world > 1 every rank's maxima are gathered to rank 0 like the score rows.  A ``map_sigma`` the maps cannot be smoothed
-    with (negative, or a radius above min(128, H, W)) raises ValueError before any image is super-resolved.
-
-    ``map_scales`` (a list of window sizes, or 'sweep' for every size of the image-level sweep): the maps are the multi-scale
-    maps of ``metrics.anomaly_maps_multi`` with ``map_reduce`` ('mean' or 'max') instead of one window size's; everything after
-    them is unchanged, and the result carries ``map_scales`` (the list used) and ``map_reduce`` in place of ``map_ws``.  The
-    scales do not depend on the sweep's result.  ValueError, before any image is super-resolved, for a size the images are too
-    small for, an unknown ``map_reduce``, and scales together with a non-zero ``map_ws``.
-
-    ``map_source`` 'mse' (default 'ssim'): the maps are the squared-error maps of ``metrics.error_maps`` /
-    ``metrics.error_maps_multi`` (DESIGN.md "Squared-error maps") instead of ``1 - SSIM map``, for the test images and the
-    calibration images alike; everything after them is unchanged, the printed lines say ``MSE map`` and the result carries
-    ``map_source`` beside ``map_ws`` / ``map_scales``.  ``map_ws`` 0 without scales then means window size 1, the raw squared
-    error - not the SSIM sweep's best_ws, so nothing is broadcast for it.  ValueError for an unknown source, before any work.
-
-    ``operating_point`` (an ``OperatingPoint`` or a dict of its fields; None = off): with world 1 the maps are thresholded
-    (DESIGN.md "Operating point") at the given threshold, or at the one that the maps of the calibration pairs - made like the
-    test maps: the same forward, u8 conversion, window size or scales, and ``map_sigma`` - give at the asked false-positive
-    rate.  The result gains ``threshold``, ``threshold_source`` ('given' or 'fpr'; then also ``threshold_fpr``,
-    ``threshold_level``, ``calib_images``, ``calib_rate`` = the rate achieved on the calibration values), ``min_region_area``,
-    the image-level counts and rates of ``metrics.operating_point_stats`` and, with a mask for every image, its pixel-level
-    counts, ratios and ``pro_at_threshold``.  ValueError for an inconsistent specification, before any image is super-resolved."""
-    if map_source not in M.MAP_SOURCES:
-        raise ValueError(f"map_source = {map_source!r}, must be one of {M.MAP_SOURCES}")
+    Pixel level (off by default): the anomaly maps of each rank's own images as ``MapSpec`` describes them (``map_source``,
+    ``map_ws``, ``map_scales``, ``map_reduce``, ``map_sigma``), and on them what ``_pixel_stage`` does with ``save_maps``,
+    ``map_image_score``, ``pixel_metrics``, ``aupro`` (with ``pro_fpr_limit``), ``operating_point`` (an ``OperatingPoint`` or a
+    dict of its fields) and the ``masks`` (good + bad order, as ``load_masks`` returns them).  ValueError for maps that cannot
+    be made of these images and for an inconsistent operating point, before any image is super-resolved."""
+    spec = MapSpec(source=map_source, ws=map_ws, scales=map_scales, reduce=map_reduce, sigma=map_sigma)
     op = None
     if operating_point is not None:
         op = (OperatingPoint(**operating_point) if isinstance(operating_point, dict) else operating_point).check()
         if op.fpr is not None and world == 1 and not len(op.calib):
             raise ValueError("operating point: a false-positive rate needs calibration pairs (defect-free images)")
-    if map_sigma and (good or bad):
-        h, w = (list(good) + list(bad))[0][1].shape[:2]
-        M.smooth_radius(map_sigma, h, w)
-    scales: List[int] = []
-    if (isinstance(map_scales, str) or len(map_scales)) and (good or bad):
-        if int(map_ws):
-            raise ValueError("map_scales and a non-zero map_ws exclude each other")
-        if map_reduce not in M.MAP_REDUCTIONS:
-            raise ValueError(f"map_reduce = {map_reduce!r}, must be one of {M.MAP_REDUCTIONS}")
-        h, w = (list(good) + list(bad))[0][1].shape[:2]
-        scales = resolve_map_scales(map_scales, h, w)
+    want = Request(save_maps=save_maps, map_image_score=map_image_score, pixel_metrics=pixel_metrics, aupro=aupro,
+                   pro_fpr_limit=pro_fpr_limit, op=op)
+    pairs = list(good) + list(bad)
+    if pairs:
+        spec = spec.resolve(*pairs[0][1].shape[:2])
     model.eval()                                              # H1: deterministic scoring
     y_true = [0] * len(good) + [1] * len(bad)
-    pairs = list(good) + list(bad)
     if len(set(y_true)) < 2:
         print('Test set lacks both classes; AUC not available')
         return {}
     mine = shard_indices(len(pairs), rank, world)
     sr, hr = super_resolve_u8(model, [pairs[i][0] for i in mine], [pairs[i][1] for i in mine], float(opt.rgb_range))
+    shard = Shard(sr=sr, hr=hr, mine=mine, y_true=y_true, names=names, rank=rank, world=world, output_dir=output_dir)
     if save_images and output_dir:
         scale_value = opt.scale[-1] if isinstance(opt.scale, list) else int(opt.scale)
         sr_host = sr.cpu().numpy()
-        for k, i in enumerate(mine):
-            save_sr_image(sr_host[k], names[i] if i < len(names) else f"{i:05d}", 'good' if y_true[i] == 0 else 'bad', scale_value, output_dir)
+        for k, (name, split) in enumerate(zip(shard.my_names(), shard.my_splits())):
+            save_sr_image(sr_host[k], name, split, scale_value, output_dir)
     H, W = hr.shape[1:3]
     sizes = M.sweep_window_sizes(min(H, W))
     ssim, mse, psnr = M.score_pairs(sr, hr, sizes)
     rows = torch.cat([ssim, mse[:, None], psnr[:, None]], dim=1)          # [n_mine, n_ws + 2] float64
     full = gather_score_rows(mine, rows.cpu().numpy(), len(pairs), rank, world)
     if full is None:
-        if save_maps or pixel_metrics or aupro or map_image_score or op is not None:
-            _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, None, world, aupro,
-                         pro_fpr_limit, map_sigma, map_image_score, rank, op, None, map_source, scales, map_reduce)
+        _pixel_stage(shard=shard, spec=spec, want=want, masks=masks, best_ws=None)     # its collectives, on every rank
         return {}
-    best_ws, best_auc, best_j = sizes[0], -1.0, 0
-    for j, ws in enumerate(sizes):
-        a = M.roc_auc(y_true, 1.0 - full[:, j])
-        if a > best_auc:
-            best_auc, best_ws, best_j = a, ws, j
-    out = dict(best_ws=best_ws, auc_ssim=M.roc_auc(y_true, 1.0 - full[:, best_j]), auc_mse=M.roc_auc(y_true, full[:, -2]),
+    best_j, sweep = M.best_window(y_true, full, sizes)
+    best_ws = sizes[best_j]
+    out = dict(best_ws=best_ws, auc_ssim=sweep[best_j], auc_mse=M.roc_auc(y_true, full[:, -2]),
                auc_psnr=M.roc_auc(y_true, -full[:, -1]), n_images=len(pairs), window_sizes=sizes)
     print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}")
-    if save_maps or pixel_metrics or aupro or map_image_score or op is not None:
-        calib = None
-        if op is not None and op.fpr is not None and world == 1:      # the calibration images go the test images' way
-            calib = super_resolve_u8(model, [lr for lr, _ in op.calib], [h for _, h in op.calib], float(opt.rgb_range))
-        out.update(_pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                                aupro, pro_fpr_limit, map_sigma, map_image_score, rank, op, calib, map_source, scales, map_reduce))
+    calib = None
+    if op is not None and op.fpr is not None and world == 1:          # the calibration images go the test images' way
+        calib = super_resolve_u8(model, [lr for lr, _ in op.calib], [h for _, h in op.calib], float(opt.rgb_range))
+    out.update(_pixel_stage(shard=shard, spec=spec, want=want, masks=masks, best_ws=best_ws, calib=calib))
     return out
 
 
-def _make_maps(sr, hr, scales, map_reduce, ws, sigma, with_max, source='ssim'):
-    """The anomaly maps of (sr, hr) u8 stacks the way the evaluator makes them, for the test images and the calibration images
-    alike: ``scales`` (non-empty) reduced by ``map_reduce``, else the one window size ``ws``, of the ``1 - SSIM`` maps or
-    (``source`` 'mse') the squared-error maps; then smoothed when ``sigma`` > 0.
-    Returns (maps, per-image maxima or None without ``with_max``)."""
-    if source == 'mse':
-        maps = M.error_maps_multi(sr, hr, scales, map_reduce) if scales else M.error_maps(sr, hr, ws)
-    else:
-        maps = M.anomaly_maps_multi(sr, hr, scales, map_reduce) if scales else M.anomaly_maps(sr, hr, ws)
-    if with_max:
-        return M.smooth_maps(maps, sigma, with_max=True)
-    return (M.smooth_maps(maps, sigma) if sigma > 0 else maps), None
+def _pixel_stage(shard: Shard, spec: MapSpec, want: Request, masks, best_ws, calib=None) -> dict:
+    """The anomaly maps of this rank's images and what was asked for on them: saved maps and the map-maximum image AUC on any
+    number of ranks; the pixel-level AUC, AU-PRO and the operating point (``calib`` = the (sr, hr) u8 stacks of its
+    calibration pairs) on a single rank.  ``spec`` is resolved; ``best_ws`` is None off rank 0.  Every branch that leads to a
+    collective depends only on ``spec``, ``want`` and ``shard.world``, which all ranks share, so all ranks make the same
+    collective calls: at most one broadcast (``_with_window``) and one gather (``_map_max_auc``)."""
+    found, maps = {}, None
+    if want.save_maps or want.map_image_score or (want.single and shard.world == 1):      # what needs the maps here
+        spec = _with_window(spec, best_ws, shard.world)
+        maps, img_max = spec.make(shard.sr, shard.hr, want.map_image_score)
+        if want.save_maps and shard.output_dir:
+            save_anomaly_maps(maps, shard.my_names(), shard.my_splits(), shard.output_dir)
+        if want.map_image_score:
+            found = _map_max_auc(shard, spec, img_max)
+    runs, labels = _single_rank_gate(shard, want, masks, best_ws, maps)
+    if not runs:
+        return spec.entries(found) if found else {}
+    out = spec.entries(found)
+    out.update(_pixel_scores(spec, want, maps, labels))
+    if want.op is not None:
+        out.update(_operating_point(shard, spec, want.op, maps, labels, calib))
+    return out
 
 
-def _pixel_stage(sr, hr, mine, y_true, names, output_dir, masks, pixel_metrics, save_maps, map_ws, best_ws, world,
-                 aupro=False, pro_fpr_limit=0.3, map_sigma=0.0, map_image_score=False, rank=0, op=None, calib=None,
-                 map_source='ssim', map_scales=(), map_reduce='mean') -> dict:
-    """Anomaly maps of this rank's images, smoothed once when ``map_sigma`` > 0; the map-maximum image AUC on any number of
-    ranks; the pixel-level AUC, AU-PRO and the operating point (``op``, a checked ``OperatingPoint``; ``calib`` = the (sr, hr)
-    u8 stacks of its calibration pairs) on a single rank.  ``best_ws`` is None off rank 0.  Every branch that leads to a
-    collective depends only on the flags and ``world``, which all ranks share, so all ranks make the same collective calls.
-    ``map_scales`` (a resolved list) replaces the single window size: every rank knows it, so ``best_ws`` is not broadcast.
-    ``map_source`` 'mse': squared-error maps; without scales and with ``map_ws`` 0 their window size is 1, which every rank
-    knows too, so this source never broadcasts."""
-    scored = pixel_metrics or aupro
-    single = scored or op is not None                         # what runs on one rank only
-    if world > 1 and not (save_maps or map_image_score):      # the same branch on every rank: no collective below
-        if single and best_ws is not None:
-            print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
+def _with_window(spec: MapSpec, best_ws, world: int) -> MapSpec:
+    """The spec with its one window size filled in (scales have none): the sweep's best_ws, which only rank 0 has and
+    broadcasts, where ``spec.needs_best_ws`` - a fact about the SSIM score - and at least 1 otherwise."""
+    if spec.needs_best_ws:
+        if world > 1:
+            import torch.distributed as dist
+            box = [best_ws]
+            dist.broadcast_object_list(box, src=0)
+            best_ws = int(box[0])
+        return replace(spec, ws=best_ws)
+    return spec if spec.scales else replace(spec, ws=max(spec.ws, 1))
+
+
+def _map_max_auc(shard: Shard, spec: MapSpec, img_max: torch.Tensor) -> dict:
+    """``auc_map_max``, the ROC-AUC of each image's map maximum: every rank's maxima are gathered to rank 0 like the score
+    rows (one more gather, one column); {} on the other ranks.  No masks needed."""
+    full = gather_score_rows(shard.mine, img_max.double().cpu().numpy()[:, None], len(shard.y_true), shard.rank, shard.world)
+    if full is None:
         return {}
-    scales = [int(w) for w in map_scales]
-    mse = map_source == 'mse'
-    label = "MSE map" if mse else "SSIM map"
-    ws = 0
-    if scales:
-        what, keys = f"scales={scales}, {map_reduce}", dict(map_scales=scales, map_reduce=map_reduce)
-    elif mse:
-        ws = int(map_ws) if int(map_ws) > 0 else 1            # best_ws is a fact about the SSIM score
-        what, keys = f"ws={ws}", dict(map_ws=ws)
-    else:
-        ws = int(map_ws)
-        if ws <= 0:
-            ws = best_ws
-            if world > 1:                                     # only rank 0 has the sweep's result
-                import torch.distributed as dist
-                box = [best_ws]
-                dist.broadcast_object_list(box, src=0)
-                ws = int(box[0])
-        what, keys = f"ws={ws}", dict(map_ws=ws)
-    if mse:
-        keys = dict(map_source=map_source, **keys)
-    sigma = float(map_sigma)
-    maps, img_max = _make_maps(sr, hr, scales, map_reduce, ws, sigma, map_image_score, map_source)
-    if save_maps and output_dir:
-        save_anomaly_maps(maps, [names[i] if i < len(names) else f"{i:05d}" for i in mine],
-                          ['good' if y_true[i] == 0 else 'bad' for i in mine], output_dir)
-    out = {}
-    if map_image_score:                                       # every rank: one more gather, one column of maxima
-        full = gather_score_rows(mine, img_max.double().cpu().numpy()[:, None], len(y_true), rank, world)
-        if full is not None:
-            out.update(keys, auc_map_max=M.roc_auc(y_true, full[:, 0]))
-            print(f"Image AUC - max of the {label} ({what}, sigma={sigma:g}): {out['auc_map_max']:.4f}")
-    if sigma > 0 and out:
-        out["map_sigma"] = sigma
-    if not single or best_ws is None:
-        return out
-    if world > 1:
+    auc = M.roc_auc(shard.y_true, full[:, 0])
+    print(f"Image AUC - max of the {spec.text(always_sigma=True)}: {auc:.4f}")
+    return dict(auc_map_max=auc)
+
+
+def _single_rank_gate(shard: Shard, want: Request, masks, best_ws, maps):
+    """(whether what runs on one rank only runs here, the ground-truth stack of this rank's images or None).  It runs where
+    it was asked for and the sweep's result is (rank 0), on a single rank - the maps and masks are not gathered - and, but for
+    the operating point, which then reports the image level only, with a mask of the images' size for every image."""
+    if not want.single or best_ws is None:
+        return False, None
+    if shard.world > 1:
         print("Pixel metrics need --gpus 1 (the maps and masks are not gathered across ranks); skipped")
-        return out
-    lacking = [i for i in range(len(y_true)) if masks is None or i >= len(masks) or masks[i] is None]
-    if lacking and scored:
-        print(f"Pixel metrics skipped: {len(lacking)} test image(s) have no ground-truth mask")
-    if lacking and op is None:
-        return out
-    labels = None
-    if not lacking:
-        H, W = maps.shape[1:]
-        for i in mine:
-            if tuple(masks[i].shape) != (H, W):
-                raise ValueError(f"mask {i} has shape {tuple(masks[i].shape)}, the images are {H}x{W}")
-        labels = torch.from_numpy(np.stack([np.asarray(masks[i]) for i in mine])).to(maps.device)
-    out.update(keys)
-    if sigma > 0:
-        out["map_sigma"] = sigma
-    tail = f", sigma={sigma:g}" if sigma > 0 else ""
-    if pixel_metrics and labels is not None:
+        return False, None
+    lacking = [i for i in range(len(shard.y_true)) if masks is None or i >= len(masks) or masks[i] is None]
+    if lacking:
+        if want.scored:
+            print(f"Pixel metrics skipped: {len(lacking)} test image(s) have no ground-truth mask")
+        return want.op is not None, None
+    H, W = maps.shape[1:]
+    for i in shard.mine:
+        if tuple(masks[i].shape) != (H, W):
+            raise ValueError(f"mask {i} has shape {tuple(masks[i].shape)}, the images are {H}x{W}")
+    return True, torch.from_numpy(np.stack([np.asarray(masks[i]) for i in shard.mine])).to(maps.device)
+
+
+def _pixel_scores(spec: MapSpec, want: Request, maps: torch.Tensor, labels) -> dict:
+    """``auc_pixel``, the exact pixel-level ROC-AUC, and ``aupro`` with ``pro_fpr_limit``, the normalised area under the
+    per-region overlap curve up to that limit: each where asked for and ``labels`` are there."""
+    out = {}
+    if want.pixel_metrics and labels is not None:
         out["auc_pixel"] = M.pixel_roc_auc(maps, labels)
-        print(f"Pixel AUC - {label} ({what}{tail}): {out['auc_pixel']:.4f}")
-    if aupro and labels is not None:
-        out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, pro_fpr_limit), float(pro_fpr_limit)
-        print(f"AU-PRO - {label} ({what}, fpr <= {float(pro_fpr_limit):g}{tail}): {out['aupro']:.4f}")
-    if op is not None:
-        if op.fpr is not None:
-            cmaps, cmax = _make_maps(calib[0], calib[1], scales, map_reduce, ws, sigma, op.level == 'image', map_source)
-            t, achieved = M.map_threshold(cmax if op.level == 'image' else cmaps, op.fpr)
-            out.update(threshold=t, threshold_source='fpr', threshold_fpr=float(op.fpr), threshold_level=op.level,
-                       calib_images=int(cmaps.shape[0]), calib_rate=achieved)
-            src = f"fpr {float(op.fpr):g} on {op.level}s of {cmaps.shape[0]} defect-free images, achieved {achieved:.6f}"
-        else:
-            t = float(op.threshold)
-            out.update(threshold=t, threshold_source='given')
-            src = "given"
-        out["min_region_area"] = int(op.min_area)
-        pred, img_pred, counts = M.operating_point(maps, t, labels, int(op.min_area))
-        st = M.operating_point_stats(counts if labels is not None else None, img_pred, [y_true[i] for i in mine])
-        out.update(st)
-        line = (f"Operating point - {label} ({what}{tail}), threshold={t:.9g} ({src}), min_area={int(op.min_area)}: "
-                f"image tp={st['image_tp']} fp={st['image_fp']} fn={st['image_fn']} tn={st['image_tn']} "
-                f"tpr={st['image_tpr']:.4f} fpr={st['image_fpr']:.4f}")
-        if labels is not None:
-            line += (f"; pixel tp={st['pixel_tp']} fp={st['pixel_fp']} fn={st['pixel_fn']} tn={st['pixel_tn']} "
-                     f"precision={st['precision']:.4f} recall={st['recall']:.4f} f1={st['f1']:.4f} iou={st['iou']:.4f} "
-                     f"fpr={st['fpr']:.6f} pro={st['pro_at_threshold']:.4f}")
-        print(line)
-        if op.save_masks and output_dir:
-            save_masks(pred, [names[i] if i < len(names) else f"{i:05d}" for i in mine],
-                       ['good' if y_true[i] == 0 else 'bad' for i in mine], output_dir)
+        print(f"Pixel AUC - {spec.text()}: {out['auc_pixel']:.4f}")
+    if want.aupro and labels is not None:
+        limit = float(want.pro_fpr_limit)
+        out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, want.pro_fpr_limit), limit
+        print(f"AU-PRO - {spec.text(f', fpr <= {limit:g}')}: {out['aupro']:.4f}")
+    return out
+
+
+def _operating_point(shard: Shard, spec: MapSpec, op: OperatingPoint, maps: torch.Tensor, labels, calib) -> dict:
+    """The maps thresholded (DESIGN.md "Operating point") at the given threshold, or at the one that the maps of the
+    calibration stacks - made by the same ``spec`` - give at the asked false-positive rate: ``threshold``,
+    ``threshold_source`` ('given' or 'fpr'; then also ``threshold_fpr``, ``threshold_level``, ``calib_images`` and
+    ``calib_rate``, the rate achieved on the calibration values), ``min_region_area``, the image-level counts and rates of
+    ``metrics.operating_point_stats`` and, with ``labels``, its pixel-level ones; the masks are saved where asked for."""
+    if op.fpr is not None:
+        cmaps, cmax = spec.make(calib[0], calib[1], op.level == 'image')
+        t, achieved = M.map_threshold(cmax if op.level == 'image' else cmaps, op.fpr)
+        out = dict(threshold=t, threshold_source='fpr', threshold_fpr=float(op.fpr), threshold_level=op.level,
+                   calib_images=int(cmaps.shape[0]), calib_rate=achieved)
+        src = f"fpr {float(op.fpr):g} on {op.level}s of {cmaps.shape[0]} defect-free images, achieved {achieved:.6f}"
+    else:
+        t = float(op.threshold)
+        out, src = dict(threshold=t, threshold_source='given'), "given"
+    out["min_region_area"] = int(op.min_area)
+    pred, img_pred, counts = M.operating_point(maps, t, labels, int(op.min_area))
+    st = M.operating_point_stats(counts if labels is not None else None, img_pred, [shard.y_true[i] for i in shard.mine])
+    out.update(st)
+    line = (f"Operating point - {spec.text()}, threshold={t:.9g} ({src}), min_area={int(op.min_area)}: "
+            f"image tp={st['image_tp']} fp={st['image_fp']} fn={st['image_fn']} tn={st['image_tn']} "
+            f"tpr={st['image_tpr']:.4f} fpr={st['image_fpr']:.4f}")
+    if labels is not None:
+        line += (f"; pixel tp={st['pixel_tp']} fp={st['pixel_fp']} fn={st['pixel_fn']} tn={st['pixel_tn']} "
+                 f"precision={st['precision']:.4f} recall={st['recall']:.4f} f1={st['f1']:.4f} iou={st['iou']:.4f} "
+                 f"fpr={st['fpr']:.6f} pro={st['pro_at_threshold']:.4f}")
+    print(line)
+    if op.save_masks and shard.output_dir:
+        save_masks(pred, shard.my_names(), shard.my_splits(), shard.output_dir)
     return out
 
 
@@ -477,19 +542,14 @@ def _run(args):
         scale = inf.get('scale') or scale
     if args.device == 'cpu':
         raise SystemExit("--device cpu is the reference's own path; this build has no CPU fallback")
-    if args.map_sigma and resolution:                         # before the model and the data are loaded
-        try:
-            M.smooth_radius(args.map_sigma, int(resolution), int(resolution))
-        except ValueError as e:
-            raise SystemExit(f"--map-sigma {args.map_sigma:g}: {e}")
-    if args.map_scales and resolution:
-        try:
-            resolve_map_scales(args.map_scales, int(resolution), int(resolution))
-        except ValueError as e:
-            raise SystemExit(f"--map-scales: {e}")
+    spec = MapSpec(source=args.map_source, ws=args.map_ws, scales=args.map_scales, reduce=args.map_reduce, sigma=args.map_sigma)
+    if resolution:                                            # before the model and the data are loaded
+        for flag, check in ((f"--map-sigma {args.map_sigma:g}", spec.check_sigma), ("--map-scales", spec.check_scales)):
+            try:
+                check(int(resolution), int(resolution))
+            except ValueError as e:
+                raise SystemExit(f"{flag}: {e}")
     want_op = args.threshold is not None or args.threshold_fpr is not None
-    if args.threshold is not None and args.threshold_fpr is not None:
-        raise SystemExit("--threshold and --threshold-fpr exclude each other")
     if args.threshold_fpr is not None:                        # before the model is loaded
         data_root = args.data_root if args.data_root != 'auto' else f"data/mvtec_{resolution}"
         val_dir = val_good_dir(data_root, class_name)

@@ -518,6 +518,18 @@ def ssim_torch(sr: torch.Tensor, hr: torch.Tensor, rgb_range: float, win_size: i
     return float(s.mean().item()) if s.numel() > 1 else float(s[0].item())
 
 
+def best_window(y_true: Sequence[int], ssim_cols: np.ndarray, sizes: Sequence[int]) -> Tuple[int, List[float]]:
+    """The window sweep of the evaluator (src/evaluate.py:236-249): column j of ``ssim_cols`` holds the images' SSIM at window
+    size ``sizes[j]`` (further columns are not looked at).  Returns (the index of the size with the highest image-level AUC of
+    ``1 - SSIM``, the AUC of every size).  Strict '>': the first maximum wins (evaluate.py:246)."""
+    best_j, best_auc, sweep = 0, -1.0, []
+    for j in range(len(sizes)):
+        sweep.append(roc_auc(y_true, 1.0 - ssim_cols[:, j]))
+        if sweep[j] > best_auc:
+            best_auc, best_j = sweep[j], j
+    return best_j, sweep
+
+
 def evaluate_pairs(y_true: Sequence[int], sr_u8: torch.Tensor, hr_u8: torch.Tensor) -> dict:
     """Window sweep + final scores + the three AUCs of ``evaluate_on_test`` (src/evaluate.py:226-267)
     for image stacks already on the GPU.  One scorer launch sequence covers every window size."""
@@ -525,12 +537,8 @@ def evaluate_pairs(y_true: Sequence[int], sr_u8: torch.Tensor, hr_u8: torch.Tens
     sizes = sweep_window_sizes(min(H, W))
     ssim, mse, psnr = score_pairs(sr_u8, hr_u8, sizes)
     ssim_h, mse_h, psnr_h = ssim.cpu().numpy(), mse.cpu().numpy(), psnr.cpu().numpy()
-    best_ws, best_auc, sweep, best_j = sizes[0], -1.0, [], 0
-    for j, ws in enumerate(sizes):
-        a = roc_auc(y_true, 1.0 - ssim_h[:, j])
-        sweep.append(a)
-        if a > best_auc:                      # strict '>': the first maximum wins (evaluate.py:246)
-            best_auc, best_ws, best_j = a, ws, j
+    best_j, sweep = best_window(y_true, ssim_h, sizes)
+    best_ws = sizes[best_j]
     s_ssim = (1.0 - ssim_h[:, best_j]).tolist()
     return dict(window_sizes=sizes, sweep_auc=sweep, best_ws=best_ws,
                 scores_ssim=s_ssim, scores_mse=mse_h.tolist(), scores_psnr=psnr_h.tolist(),

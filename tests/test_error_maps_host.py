@@ -6,15 +6,12 @@ them is a broadcast; under map_source='ssim' the calls are those of a run withou
 import ctypes as C
 import inspect
 import itertools
-import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 
-from tests.test_map_scales_host import _cpu_anomaly_maps_multi
-from tests.test_map_smooth_host import N_IMG, _cpu_anomaly_maps, _cpu_smooth_maps, _images
+from tests.helpers import assert_saved_maps_complete, must_not_be_called, run_world2, stage_sweep
 
 SCALES = [3, 5, 9]
 FLAG_SETS = [dict(save_maps=a, map_image_score=b, pixel_metrics=c, aupro=p, map_sigma=d, map_reduce=r)
@@ -30,8 +27,7 @@ def test_map_source_defaults_off():
     from srad_amd import options as Opt
     assert Opt.parse_eval_args([]).map_source == "ssim"
     assert inspect.signature(E.evaluate_on_test).parameters["map_source"].default == "ssim"
-    assert inspect.signature(E._pixel_stage).parameters["map_source"].default == "ssim"
-    assert inspect.signature(E._make_maps).parameters["source"].default == "ssim"
+    assert E.MapSpec().source == "ssim"
     assert inspect.signature(M.error_maps).parameters["ws"].default == 1
     assert inspect.signature(M.error_maps_multi).parameters["reduce"].default == "mean"
     assert M.MAP_SOURCES == ("ssim", "mse")
@@ -149,114 +145,26 @@ def test_error_maps_argument_checks_without_gpu():
 
 
 # ----------------------------------------------------------------------------------- the post-sweep stage under world 2
-def _cpu_error_maps(sr, hr, ws=1):
-    d = sr.float() - hr.float()
-    return ((d * d)[..., 0] / 65025.0 * (1.0 + 0.1 * ws)).contiguous()
-
-
-def _cpu_error_maps_multi(sr, hr, sizes, reduce="mean"):
-    acc = _cpu_error_maps(sr, hr, sizes[0])
-    for ws in sizes[1:]:
-        m = _cpu_error_maps(sr, hr, ws)
-        acc = torch.maximum(acc, m) if reduce == "max" else acc + m
-    return acc * float(np.float32(1.0 / len(sizes))) if reduce == "mean" else acc
-
-
-def _refuse(name):
-    def fn(*a, **k):
-        raise AssertionError(f"{name} called under map_source='mse'")
-    return fn
-
-
-def _stand_ins(E, mode, saved):
-    """CPU stand-ins for the map kernels; under 'mse' the SSIM map functions must not be called at all."""
-    source = mode[0]
-    if source == "mse":
-        E.M.anomaly_maps, E.M.anomaly_maps_multi = _refuse("anomaly_maps"), _refuse("anomaly_maps_multi")
-    else:
-        E.M.anomaly_maps, E.M.anomaly_maps_multi = _cpu_anomaly_maps, _cpu_anomaly_maps_multi
-    E.M.error_maps, E.M.error_maps_multi = _cpu_error_maps, _cpu_error_maps_multi
-    E.M.smooth_maps = _cpu_smooth_maps
-    E.save_anomaly_maps = lambda maps, names, splits, d: saved.append((list(names), maps.clone()))
-
-
-def _stage(E, rank, world, flags, mode, saved):
-    source, scales, map_ws = mode
-    mine = E.shard_indices(N_IMG, rank, world)
-    sr, hr = _images(mine)
-    y_true = [0, 0, 0] + [1] * (N_IMG - 3)
-    names = [f"im{i}" for i in range(N_IMG)]
-    del saved[:]
-    _stand_ins(E, mode, saved)
-    kw = {} if source is None else dict(map_source=source)
-    out = E._pixel_stage(sr, hr, mine, y_true, names, "unused_dir", None, flags["pixel_metrics"], flags["save_maps"], map_ws,
-                         5 if rank == 0 else None, world, flags["aupro"], 0.3, flags["map_sigma"], flags["map_image_score"], rank,
-                         map_scales=scales, map_reduce=flags["map_reduce"], **kw)
-    return out, list(saved)
-
-
-def _count_collectives(calls):
-    import torch.distributed as dist
-    for fn in ("all_gather_object", "broadcast_object_list", "all_reduce", "barrier", "gather_object", "broadcast", "all_gather"):
-        real = getattr(dist, fn)
-
-        def counted(*a, _real=real, _fn=fn, **k):
-            calls.append(_fn)
-            return _real(*a, **k)
-        setattr(dist, fn, counted)
-
-
-def _stage_worker(rank, world, port, q):
-    import torch.distributed as dist
+def _stage_sweeps(rank, world, calls=None):
+    """{(mode, flag set): (result, collective calls, saved maps)}; under 'mse' the SSIM map functions must not be called at all."""
     from srad_amd import evaluate as E
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    calls, saved = [], []
-    _count_collectives(calls)
     res = {}
-    for m, mode in enumerate(MODES):
-        for k, flags in enumerate(FLAG_SETS):
-            del calls[:]
-            out, files = _stage(E, rank, world, flags, mode, saved)
-            res[m, k] = (out, list(calls), [(names, maps.numpy()) for names, maps in files])
-    q.put((rank, res))
-    dist.barrier()
-    dist.destroy_process_group()
+    for m, (source, scales, map_ws) in enumerate(MODES):
+        cases = [dict(f, map_scales=scales, map_ws=map_ws, map_source=source) for f in FLAG_SETS]
+        refuse = {fn: must_not_be_called(fn, "under map_source='mse'") for fn in ("anomaly_maps", "anomaly_maps_multi")}
+        for k, r in enumerate(stage_sweep(E, rank, world, cases, calls, **(refuse if source == "mse" else {}))):
+            res[m, k] = r
+    return res
 
 
 def test_map_source_stage_gloo_world2():
-    import torch.multiprocessing as mp
-    from srad_amd import evaluate as E
     assert len(FLAG_SETS) == 64
-    saved = []
-    keep = (E.M.anomaly_maps, E.M.anomaly_maps_multi, E.M.error_maps, E.M.error_maps_multi, E.M.smooth_maps, E.save_anomaly_maps)
-    try:                                                     # world 1 in this process: the answers rank 0 must reproduce
-        one = {(m, k): _stage(E, 0, 1, f, mode, saved) for m, mode in enumerate(MODES) for k, f in enumerate(FLAG_SETS)}
-    finally:
-        E.M.anomaly_maps, E.M.anomaly_maps_multi, E.M.error_maps, E.M.error_maps_multi, E.M.smooth_maps, E.save_anomaly_maps = keep
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_stage_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = {}
-    try:
-        for _ in procs:
-            r, out = q.get(timeout=240)
-            res[r] = out
-    finally:
-        for p in procs:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    assert [p.exitcode for p in procs] == [0, 0]
+    one = _stage_sweeps(0, 1)                                # world 1 in this process: the answers rank 0 must reproduce
+    res = run_world2(_stage_sweeps)
     for m, (source, scales, map_ws) in enumerate(MODES):
         for k, flags in enumerate(FLAG_SETS):
             (o0, c0, f0), (o1, c1, f1) = res[0][m, k], res[1][m, k]
-            w1, wf = one[m, k]
+            w1, _, wf = one[m, k]
             tag = (source, scales, flags)
             assert c0 == c1, (tag, c0, c1)                                # the same collective sequence on both ranks
             assert o1 == {}, tag
@@ -275,14 +183,7 @@ def test_map_source_stage_gloo_world2():
                 else:
                     assert o0 == {} and "auc_map_max" not in w1
                 assert "auc_pixel" not in o0 and "aupro" not in o0         # pixel metrics stay --gpus 1 only
-            if flags["save_maps"]:                                         # every rank wrote its own images' maps
-                got = {n: mp_[j] for names, mp_ in f0 + f1 for j, n in enumerate(names)}
-                want = {n: mp_[j].numpy() for names, mp_ in wf for j, n in enumerate(names)}
-                assert sorted(got) == sorted(want) == [f"im{i}" for i in range(N_IMG)]
-                for n in want:
-                    assert np.array_equal(got[n], want[n]), (tag, n)
-            else:
-                assert not f0 and not f1 and not wf
+            assert_saved_maps_complete(tag[2], f0, f1, wf)                 # every rank wrote its own images' maps
     # map_source='ssim' is the run without the argument: the same calls, results and saved maps, on both ranks and on one
     for with_arg, without in ((2, 3),):
         assert MODES[with_arg][0] == "ssim" and MODES[without][0] is None and MODES[with_arg][1:] == MODES[without][1:]

@@ -5,14 +5,12 @@ make the same collective calls for every combination of the other flags, and the
 import ctypes as C
 import inspect
 import itertools
-import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 
-from tests.test_map_smooth_host import N_IMG, _cpu_anomaly_maps, _cpu_smooth_maps, _images
+from tests.helpers import assert_saved_maps_complete, must_not_be_called, run_world2, stage_sweep
 
 SCALES = [3, 5, 9]
 FLAG_SETS = [dict(save_maps=a, map_image_score=b, pixel_metrics=c, aupro=p, map_sigma=d, map_reduce=r)
@@ -27,8 +25,7 @@ def test_map_scales_flags_default_off():
     assert a.map_scales == [] and a.map_reduce == "mean" and a.map_ws == 0
     params = inspect.signature(E.evaluate_on_test).parameters
     assert params["map_scales"].default == () and params["map_reduce"].default == "mean"
-    stage = inspect.signature(E._pixel_stage).parameters
-    assert list(stage)[-2:] == ["map_scales", "map_reduce"] and stage["map_scales"].default == ()
+    assert E.MapSpec().scales == () and E.MapSpec().reduce == "mean" and E.MapSpec().ws == 0
 
 
 def test_map_scales_parsing():
@@ -144,96 +141,19 @@ def test_python_argument_errors_come_before_the_library():
 
 
 # ----------------------------------------------------------------------------------- the post-sweep stage under world 2
-def _cpu_anomaly_maps_multi(sr, hr, sizes, reduce="mean"):
-    acc = _cpu_anomaly_maps(sr, hr, sizes[0])
-    for ws in sizes[1:]:
-        m = _cpu_anomaly_maps(sr, hr, ws)
-        acc = torch.maximum(acc, m) if reduce == "max" else acc + m
-    return acc * float(np.float32(1.0 / len(sizes))) if reduce == "mean" else acc
-
-
-def _refuse_single_map(*a, **k):
-    raise AssertionError("anomaly_maps called although map_scales is set")
-
-
-def _stage(E, rank, world, flags, saved):
-    mine = E.shard_indices(N_IMG, rank, world)
-    sr, hr = _images(mine)
-    y_true = [0, 0, 0] + [1] * (N_IMG - 3)
-    names = [f"im{i}" for i in range(N_IMG)]
-    del saved[:]
-    out = E._pixel_stage(sr, hr, mine, y_true, names, "unused_dir", None, flags["pixel_metrics"], flags["save_maps"], 0,
-                         5 if rank == 0 else None, world, flags["aupro"], 0.3, flags["map_sigma"], flags["map_image_score"], rank,
-                         map_scales=SCALES, map_reduce=flags["map_reduce"])
-    return out, list(saved)
-
-
-def _install_stand_ins(E, calls, saved):
-    import torch.distributed as dist
-    E.M.anomaly_maps = _refuse_single_map
-    E.M.anomaly_maps_multi = _cpu_anomaly_maps_multi
-    E.M.smooth_maps = _cpu_smooth_maps
-    E.save_anomaly_maps = lambda maps, names, splits, d: saved.append((list(names), maps.clone()))
-    for fn in ("all_gather_object", "broadcast_object_list", "all_reduce", "barrier", "gather_object", "broadcast", "all_gather"):
-        real = getattr(dist, fn)
-
-        def counted(*a, _real=real, _fn=fn, **k):
-            calls.append(_fn)
-            return _real(*a, **k)
-        setattr(dist, fn, counted)
-
-
-def _stage_worker(rank, world, port, q):
-    import torch.distributed as dist
+def _stage_sweep(rank, world, calls=None):
     from srad_amd import evaluate as E
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    calls, saved = [], []
-    _install_stand_ins(E, calls, saved)
-    res = []
-    for flags in FLAG_SETS:
-        del calls[:]
-        out, files = _stage(E, rank, world, flags, saved)
-        res.append((out, list(calls), [(names, m.numpy()) for names, m in files]))
-    q.put((rank, res))
-    dist.barrier()
-    dist.destroy_process_group()
+    return stage_sweep(E, rank, world, [dict(f, map_scales=SCALES) for f in FLAG_SETS], calls,
+                       anomaly_maps=must_not_be_called("anomaly_maps", "although map_scales is set"))
 
 
 def test_map_scales_stage_gloo_world2():
-    import torch.multiprocessing as mp
-    from srad_amd import evaluate as E
     assert len(FLAG_SETS) == 64
-    saved = []
-    saved_fns = (E.M.anomaly_maps, E.M.anomaly_maps_multi, E.M.smooth_maps, E.save_anomaly_maps)
-    try:                                                     # world 1 in this process: the answers rank 0 must reproduce
-        E.M.anomaly_maps, E.M.anomaly_maps_multi, E.M.smooth_maps = _refuse_single_map, _cpu_anomaly_maps_multi, _cpu_smooth_maps
-        E.save_anomaly_maps = lambda maps, names, splits, d: saved.append((list(names), maps.clone()))
-        one = [_stage(E, 0, 1, f, saved) for f in FLAG_SETS]
-    finally:
-        E.M.anomaly_maps, E.M.anomaly_maps_multi, E.M.smooth_maps, E.save_anomaly_maps = saved_fns
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_stage_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = {}
-    try:
-        for _ in procs:
-            r, out = q.get(timeout=240)
-            res[r] = out
-    finally:
-        for p in procs:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    assert [p.exitcode for p in procs] == [0, 0]
+    one = _stage_sweep(0, 1)                                 # world 1 in this process: the answers rank 0 must reproduce
+    res = run_world2(_stage_sweep)
     for k, flags in enumerate(FLAG_SETS):
         (o0, c0, f0), (o1, c1, f1) = res[0][k], res[1][k]
-        w1, wf = one[k]
+        w1, _, wf = one[k]
         assert c0 == c1, (flags, c0, c1)                                  # the same collective sequence on both ranks
         assert "broadcast_object_list" not in c0 and "broadcast" not in c0, (flags, c0)       # best_ws does not travel
         assert c0 == (["all_gather_object"] if flags["map_image_score"] else []), (flags, c0)
@@ -247,14 +167,7 @@ def test_map_scales_stage_gloo_world2():
         else:
             assert o0 == {} and "auc_map_max" not in w1
         assert "auc_pixel" not in o0 and "aupro" not in o0                 # pixel metrics stay --gpus 1 only
-        if flags["save_maps"]:                                             # every rank wrote its own images' maps
-            got = {n: m[j] for names, m in f0 + f1 for j, n in enumerate(names)}
-            want = {n: m[j].numpy() for names, m in wf for j, n in enumerate(names)}
-            assert sorted(got) == sorted(want) == [f"im{i}" for i in range(N_IMG)]
-            for n in want:
-                assert np.array_equal(got[n], want[n]), (flags, n)
-        else:
-            assert not f0 and not f1 and not wf
+        assert_saved_maps_complete(flags, f0, f1, wf)                      # every rank wrote its own images' maps
     by_reduce = {r: {one[k][0]["auc_map_max"] for k, f in enumerate(FLAG_SETS)
                      if f["map_image_score"] and f["map_sigma"] == 0 and f["map_reduce"] == r} for r in ("mean", "max")}
     assert all(len(v) == 1 for v in by_reduce.values())

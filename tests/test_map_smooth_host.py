@@ -3,24 +3,17 @@ Gaussian weights, the numpy restatement (tests/golden/make_map_smooth_golden.py)
 evaluator flags, and a gloo world-2 run of the evaluator's post-sweep stage with CPU stand-ins for the two map kernels: rank 0
 gets the world-1 ``auc_map_max`` and both ranks make the same collective calls for every combination of flags."""
 import ctypes as C
-import importlib.util
 import inspect
 import itertools
 import os
-import socket
 
 import numpy as np
 import pytest
-import torch
+
+from tests.helpers import BEST_WS, assert_saved_maps_complete, run_world2, stage_sweep
+from tests.helpers import map_smooth_generator as _generator
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _generator():
-    spec = importlib.util.spec_from_file_location("make_map_smooth_golden", os.path.join(GOLDEN_DIR, "make_map_smooth_golden.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_map_smoothing_flags_default_off():
@@ -179,110 +172,23 @@ def test_numpy_restatement_matches_scipy_on_a_large_map():
 
 
 # ----------------------------------------------------------------------------------- the post-sweep stage under world 2
-N_IMG, HW, BEST_WS = 7, 24, 5
 FLAG_SETS = [dict(save_maps=a, map_image_score=b, pixel_metrics=c, aupro=p, map_sigma=d, map_ws=e)
              for a, b, c, p, d, e in itertools.product((False, True), (False, True), (False, True), (False, True), (0.0, 4.0),
                                                        (0, 3))]
 
 
-def _images(idx):
-    """Deterministic u8 (sr, hr) pairs [n, HW, HW, 1] for image indices idx; the bad images (index >= 3) differ more."""
-    sr, hr = [], []
-    for i in idx:
-        y, x = np.mgrid[0:HW, 0:HW]
-        h = ((y * 31 + x * 17 + i * 101) % 256).astype(np.uint8)
-        d = ((y * 7 + x * 13 + i * 29) % (9 + 6 * i)).astype(np.int64)
-        sr.append(np.clip(h.astype(np.int64) + d, 0, 255).astype(np.uint8)[:, :, None])
-        hr.append(h[:, :, None])
-    return torch.from_numpy(np.stack(sr)), torch.from_numpy(np.stack(hr))
-
-
-def _cpu_anomaly_maps(sr, hr, ws):
-    return ((sr.float() - hr.float()).abs()[..., 0] / 255.0 * (1.0 + 0.1 * ws)).contiguous()
-
-
-def _cpu_smooth_maps(maps, sigma, truncate=4.0, with_max=False):
-    out = torch.from_numpy(_generator().smooth_ref(maps.numpy(), float(sigma), truncate))
-    return (out, out.amax((1, 2))) if with_max else out
-
-
-def _stage(E, rank, world, flags, saved):
-    mine = E.shard_indices(N_IMG, rank, world)
-    sr, hr = _images(mine)
-    y_true = [0, 0, 0] + [1] * (N_IMG - 3)
-    names = [f"im{i}" for i in range(N_IMG)]
-    best = BEST_WS if rank == 0 else None
-    del saved[:]
-    out = E._pixel_stage(sr, hr, mine, y_true, names, "unused_dir", None, flags["pixel_metrics"], flags["save_maps"],
-                         flags["map_ws"], best, world, flags["aupro"], 0.3, flags["map_sigma"], flags["map_image_score"], rank)
-    return out, list(saved)
-
-
-def _install_stand_ins(E, calls, saved):
-    import torch.distributed as dist
-    E.M.anomaly_maps = _cpu_anomaly_maps
-    E.M.smooth_maps = _cpu_smooth_maps
-    E.save_anomaly_maps = lambda maps, names, splits, d: saved.append((list(names), maps.clone()))
-    for fn in ("all_gather_object", "broadcast_object_list", "all_reduce", "barrier", "gather_object"):
-        real = getattr(dist, fn)
-
-        def counted(*a, _real=real, _fn=fn, **k):
-            calls.append(_fn)
-            return _real(*a, **k)
-        setattr(dist, fn, counted)
-
-
-def _stage_worker(rank, world, port, q):
-    import torch.distributed as dist
+def _stage_job(rank, world, calls):
     from srad_amd import evaluate as E
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    calls, saved = [], []
-    _install_stand_ins(E, calls, saved)
-    res = []
-    for flags in FLAG_SETS:
-        del calls[:]
-        out, files = _stage(E, rank, world, flags, saved)
-        res.append((out, list(calls), [(names, m.numpy()) for names, m in files]))
-    q.put((rank, res))
-    dist.barrier()
-    dist.destroy_process_group()
+    return stage_sweep(E, rank, world, FLAG_SETS, calls)
 
 
 def test_map_image_score_stage_gloo_world2():
-    import torch.multiprocessing as mp
     from srad_amd import evaluate as E
-    # world 1 in this process: the answers rank 0 must reproduce
-    calls, saved = [], []
-    saved_fns = (E.M.anomaly_maps, E.M.smooth_maps, E.save_anomaly_maps)
-    try:
-        E.M.anomaly_maps, E.M.smooth_maps = _cpu_anomaly_maps, _cpu_smooth_maps
-        E.save_anomaly_maps = lambda maps, names, splits, d: saved.append((list(names), maps.clone()))
-        one = [_stage(E, 0, 1, f, saved) for f in FLAG_SETS]
-    finally:
-        E.M.anomaly_maps, E.M.smooth_maps, E.save_anomaly_maps = saved_fns
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_stage_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = {}
-    try:
-        for _ in procs:
-            r, out = q.get(timeout=240)
-            res[r] = out
-    finally:
-        for p in procs:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    assert [p.exitcode for p in procs] == [0, 0]
+    one = stage_sweep(E, 0, 1, FLAG_SETS)                    # world 1 in this process: the answers rank 0 must reproduce
+    res = run_world2(_stage_job)
     for k, flags in enumerate(FLAG_SETS):
         (o0, c0, f0), (o1, c1, f1) = res[0][k], res[1][k]
-        (w1, wf), = [one[k]]
+        w1, _, wf = one[k]
         assert c0 == c1, (flags, c0, c1)                                  # the same collective sequence on both ranks
         assert o1 == {}, flags
         ws = flags["map_ws"] or BEST_WS
@@ -293,15 +199,7 @@ def test_map_image_score_stage_gloo_world2():
         else:
             assert "auc_map_max" not in o0 and "auc_map_max" not in w1
         assert "auc_pixel" not in o0 and "aupro" not in o0                 # pixel metrics stay --gpus 1 only
-        # every rank wrote its own images' maps: together, the world-1 set
-        if flags["save_maps"]:
-            got = {n: m[j] for names, m in f0 + f1 for j, n in enumerate(names)}
-            want = {n: m[j].numpy() for names, m in wf for j, n in enumerate(names)}
-            assert sorted(got) == sorted(want) == [f"im{i}" for i in range(N_IMG)]
-            for n in want:
-                assert np.array_equal(got[n], want[n]), (flags, n)
-        else:
-            assert not f0 and not f1 and not wf
+        assert_saved_maps_complete(flags, f0, f1, wf)                      # every rank wrote its own images' maps
         if not (flags["save_maps"] or flags["map_image_score"]):
             assert c0 == [] and o0 == {}
     base = [one[k][0] for k, f in enumerate(FLAG_SETS) if f["map_image_score"] and f["map_sigma"] == 0 and f["map_ws"] == 0]

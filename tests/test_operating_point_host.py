@@ -169,8 +169,8 @@ def test_signature_positions():
     ev = list(inspect.signature(E.evaluate_on_test).parameters)
     assert ev[-4:] == ["map_sigma", "map_image_score", "aupro", "pro_fpr_limit"]
     assert "operating_point" in ev[:-4] and inspect.signature(E.evaluate_on_test).parameters["operating_point"].default is None
-    stage = list(inspect.signature(E._pixel_stage).parameters)
-    assert stage[-2:] == ["map_scales", "map_reduce"]
+    maps = E.MapSpec()
+    assert (maps.source, maps.scales, maps.reduce, maps.ws, maps.sigma) == ("ssim", (), "mean", 0, 0.0)
     split = inspect.signature(E.iter_split).parameters
     assert list(split)[:6] == ["data_root", "classe", "split", "scale", "n_colors", "rgb_range"] and split["part"].default == "test"
     spec = E.OperatingPoint()
