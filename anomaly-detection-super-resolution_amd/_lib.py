@@ -113,6 +113,8 @@ _SIG = {
                                    _P, _P, _P, _P, C.c_size_t, _P]),
     "srad_val_metrics": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "srad_roc_auc": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
+    "srad_average_precision": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double)]),
     "srad_anomaly_map_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "srad_anomaly_maps": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "srad_anomaly_maps_multi": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, _P, _P,
@@ -123,6 +125,8 @@ _SIG = {
                                         C.c_size_t, _P]),
     "srad_pixel_auc_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
     "srad_pixel_roc_auc": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
+    "srad_pixel_pr_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "srad_pixel_pr": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_size_t, _P]),
     "srad_mask_regions_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "srad_mask_regions": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "srad_pixel_pro_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),

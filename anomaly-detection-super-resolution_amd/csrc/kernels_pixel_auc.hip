@@ -37,7 +37,7 @@ struct AucScan {
   __device__ explicit AucScan(const Args&) {}
   static __device__ __forceinline__ uint32_t group(uint64_t key) { return (uint32_t)(key >> 1); }
   static __device__ __forceinline__ void add(Prefix& p, uint64_t key) { p += (key & 1u) ? 1ull : 1ull << 32; }
-  __device__ __forceinline__ Acc at_end(Prefix before_head, Prefix through_end, int64_t) const {
+  __device__ __forceinline__ Acc at_end(Prefix before_head, Prefix through_end, int64_t, uint64_t) const {
     return (uint64_t)((uint32_t)through_end - (uint32_t)before_head) * ((before_head >> 32) + (through_end >> 32));
   }
 };

@@ -190,11 +190,6 @@ __global__ __launch_bounds__(256) void mask_flatten_kernel(const uint8_t* __rest
   }
 }
 
-__device__ __forceinline__ uint32_t desc_key(float f) {
-  const uint32_t k = order_key(f);
-  return k == kNanKey ? kNanKey : ~k;
-}
-
 // Every pixel's region size (0 for ok pixels): into `out` (may be `size` itself: only a root's word is read, and a root's thread
 // writes back the value it holds), or with `scores` into the sort keys.  counts (zeroed before) += {regions, ok, defect}.
 __global__ __launch_bounds__(256) void mask_sizes_kernel(const uint8_t* __restrict__ masks, const uint32_t* __restrict__ parent,
@@ -268,7 +263,7 @@ struct ProScan {
   __device__ explicit ProScan(const Args& args) : a(args), n_reg((double)args.counts[0]), n_ok((double)args.counts[1]) {}
   static __device__ __forceinline__ uint32_t group(uint64_t key) { return (uint32_t)(key >> 32); }
   static __device__ __forceinline__ void add(Pref& p, uint64_t key) { pro_add(p, key); }
-  __device__ __forceinline__ double at_end(const Pref& before_head, const Pref& through_end, int64_t idx) const {
+  __device__ __forceinline__ double at_end(const Pref& before_head, const Pref& through_end, int64_t idx, uint64_t) const {
     double f0, p0, f1, p1;
     pro_point(before_head, n_ok, n_reg, f0, p0);
     pro_point(through_end, n_ok, n_reg, f1, p1);

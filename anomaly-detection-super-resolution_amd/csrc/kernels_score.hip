@@ -988,4 +988,42 @@ int srad_roc_auc(const int32_t* labels, const double* scores, int n, double* auc
   return SRAD_OK;
 }
 
+// sklearn.metrics.average_precision_score, sum over distinct scores from the highest down of (R_k - R_k-1) * P_k, and the best
+// F1 = 2 tp / (tp + fp + P) over those thresholds, for the image scores on the host: the definitions of srad_pixel_pr
+// (kernels_pixel_pr.hip), with the same exact integer comparison of two F1 values (the earlier, higher threshold keeps a tie).
+int srad_average_precision(const int32_t* labels, const double* scores, int n, double* ap, double* f1max) {
+  SRAD_REQUIRE(labels && scores && ap && f1max && n > 0, "average_precision: bad argument");
+  int64_t npos = 0;
+  for (int i = 0; i < n; ++i) {
+    if (scores[i] != scores[i]) return srad_set_error(SRAD_ERR_ARG, "average_precision: score %d of %d is NaN", i, n);
+    npos += labels[i] != 0;
+  }
+  if (npos == 0)
+    return srad_set_error(SRAD_ERR_ARG, "No positive class found in y_true. Average precision is not defined in that case.");
+  std::vector<int> idx(n);
+  for (int i = 0; i < n; ++i) idx[i] = i;
+  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return scores[a] > scores[b]; });
+  int64_t tp = 0, fp = 0, best_tp = 0, best_den = 1;             // F1 0 until a point beats it
+  double sum = 0.0;
+  int i = 0;
+  while (i < n) {
+    const int64_t tp0 = tp;
+    int j = i;
+    while (j < n && scores[idx[j]] == scores[idx[i]]) {
+      (labels[idx[j]] ? tp : fp) += 1;
+      ++j;
+    }
+    sum += (double)(tp - tp0) * (double)tp / (double)(tp + fp);
+    const int64_t den = tp + fp + npos;
+    if (tp * best_den > best_tp * den) {
+      best_tp = tp;
+      best_den = den;
+    }
+    i = j;
+  }
+  *ap = sum / (double)npos;
+  *f1max = 2.0 * (double)best_tp / (double)best_den;
+  return SRAD_OK;
+}
+
 }  // extern "C"

@@ -1,11 +1,12 @@
-// pixel_sort.h - the device sort of the sort-based pixel metrics (kernels_pixel_auc.hip, kernels_pixel_pro.hip, through
-// tie_scan.h, which holds their workspace layout, the three-pass driver and the scan of the sorted keys).
+// pixel_sort.h - the device sort of the sort-based pixel metrics (kernels_pixel_auc.hip, kernels_pixel_pro.hip,
+// kernels_pixel_pr.hip, through tie_scan.h, which holds their workspace layout, the three-pass driver and the scan of the sorted
+// keys).
 //
 // LSD radix sort of u64 keys on 11-bit digits: a pass is a per-tile LDS histogram (tile = 8192 keys), an exclusive scan of the
 // [digit][tile] count matrix, and a stable scatter.  A caller picks the digits with the shifts it passes: the AUC sorts its 33-bit
-// keys at shifts 0 / 11 / 22, AU-PRO sorts the high 32 bits of its keys at 32 / 43 / 54 and lets the low word ride along.  Also
-// here, and used by kernels_operating_point.hip and kernels_map_smooth.hip as well: the order-preserving u32 of a float, and the
-// 256-thread block scan every scan is built from.
+// keys at shifts 0 / 11 / 22 (so does precision-recall), AU-PRO sorts the high 32 bits of its keys at 32 / 43 / 54 and lets the
+// low word ride along.  Also here, and used by kernels_operating_point.hip and kernels_map_smooth.hip as well: the
+// order-preserving u32 of a float (and its descending twin), and the 256-thread block scan every scan is built from.
 #pragma once
 #include "engine.h"
 #include <algorithm>
@@ -22,6 +23,11 @@ __device__ __forceinline__ uint32_t order_key(float f) {
   if ((b & 0x7FFFFFFFu) > 0x7F800000u) return kNanKey;
   if (b == 0x80000000u) b = 0u;                                  // -0.0 == +0.0
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// order_key upside down: ascending keys walk the floats from the highest down; a NaN still sorts last.
+__device__ __forceinline__ uint32_t desc_key(float f) {
+  const uint32_t k = order_key(f);
+  return k == kNanKey ? kNanKey : ~k;
 }
 
 // Block-wide scan over 256 threads (Hillis-Steele in LDS): returns the exclusive prefix, `total` = the whole block's.

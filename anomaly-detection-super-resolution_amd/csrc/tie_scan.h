@@ -1,10 +1,11 @@
-// tie_scan.h - what the two sort-based pixel metrics (kernels_pixel_auc.hip, kernels_pixel_pro.hip) share beyond the sort
-// itself: the workspace of a metric over sorted keys, the three-pass sort driver, and the tie-group scan of the sorted keys.
+// tie_scan.h - what the sort-based pixel metrics (kernels_pixel_auc.hip, kernels_pixel_pro.hip, kernels_pixel_pr.hip) share
+// beyond the sort itself: the workspace of a metric over sorted keys, the three-pass sort driver, and the tie-group scan of the
+// sorted keys.
 //
 // The scan.  Walking the sorted keys, a metric keeps a prefix P::Prefix whose every component never decreases (P::add).  Keys
 // with equal P::group(key) form a tie group; group kNanKey (NaN scores, sorted last) is left out and counted.  A key is its
 // group's head if its predecessor's group differs, its end if its successor's does.  At each group end the metric is handed
-//     at_end(prefix just before the head of this group, prefix through this end, number of group ends before this one)
+//     at_end(prefix just before the head of this group, prefix through this end, number of group ends before this one, this key)
 // and the values it returns (P::Acc) are summed: per thread in key order, then by the block's scan tree, then over tiles by
 // the metric's own finish kernel.  "The prefix just before the head of my group" is the prefix before the last head at or
 // before me; because the prefix never decreases, that is a running maximum (P::Max, "the later position") of the prefix before
@@ -14,7 +15,8 @@
 //
 // A policy P provides: Prefix, Add, Max (functors over Prefix; Prefix{} is the identity of both), Acc (summed with +, Acc{} is
 // zero), static uint32_t group(uint64_t key), static void add(Prefix&, uint64_t key), Args (what the host passes to the visiting
-// pass), a device constructor P(const Args&), and Acc at_end(const Prefix& before_head, const Prefix& through_end, int64_t idx).
+// pass), a device constructor P(const Args&), and Acc at_end(const Prefix& before_head, const Prefix& through_end, int64_t idx,
+// uint64_t key of the group end).  Acc may be a struct with its own + and +=.
 //
 // Launches: tie_tile_counts_kernel<P> (per tile), tie_tiles_scan_kernel<P> (one block), tie_visit_kernel<P> (per tile), then
 // the metric's finish kernel over the TieTile<P> records.
@@ -197,7 +199,7 @@ __global__ __launch_bounds__(256) void tie_visit_kernel(const uint64_t* __restri
     if (tie_is_head<P>(keys, i, g)) lt = cur;
     P::add(cur, key);
     if (tie_is_end<P>(keys, i, n, g)) {
-      acc += p.at_end(lt, cur, idx);
+      acc += p.at_end(lt, cur, idx, key);
       ++idx;
     }
   }

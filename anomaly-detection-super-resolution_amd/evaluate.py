@@ -340,10 +340,11 @@ class Request:
     aupro: bool = False
     pro_fpr_limit: float = 0.3
     op: Optional[OperatingPoint] = None
+    pr: bool = False
 
     @property
     def scored(self) -> bool:                                 # what needs a mask for every image
-        return bool(self.pixel_metrics or self.aupro)
+        return bool(self.pixel_metrics or self.aupro or self.pr)
 
     @property
     def single(self) -> bool:                                 # what runs on one rank only
@@ -354,7 +355,7 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
                      map_ws: int = 0, map_scales=(), map_reduce: str = 'mean', map_source: str = 'ssim', operating_point=None,
-                     map_sigma: float = 0.0,
+                     pr_metrics: bool = False, map_sigma: float = 0.0,
                      map_image_score: bool = False, aupro: bool = False, pro_fpr_limit: float = 0.3) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
@@ -364,7 +365,11 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     ``map_ws``, ``map_scales``, ``map_reduce``, ``map_sigma``), and on them what ``_pixel_stage`` does with ``save_maps``,
     ``map_image_score``, ``pixel_metrics``, ``aupro`` (with ``pro_fpr_limit``), ``operating_point`` (an ``OperatingPoint`` or a
     dict of its fields) and the ``masks`` (good + bad order, as ``load_masks`` returns them).  ValueError for maps that cannot
-    be made of these images and for an inconsistent operating point, before any image is super-resolved."""
+    be made of these images and for an inconsistent operating point, before any image is super-resolved.
+
+    ``pr_metrics`` (off by default): average precision and F1-max next to every AUC - of the three image scores (``ap_*``,
+    ``f1max_*``, on rank 0 from the gathered table), of the map maximum with ``map_image_score``, and of the pixels
+    (``_pixel_scores``) where the pixel metrics can run."""
     spec = MapSpec(source=map_source, ws=map_ws, scales=map_scales, reduce=map_reduce, sigma=map_sigma)
     op = None
     if operating_point is not None:
@@ -372,7 +377,7 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
         if op.fpr is not None and world == 1 and not len(op.calib):
             raise ValueError("operating point: a false-positive rate needs calibration pairs (defect-free images)")
     want = Request(save_maps=save_maps, map_image_score=map_image_score, pixel_metrics=pixel_metrics, aupro=aupro,
-                   pro_fpr_limit=pro_fpr_limit, op=op)
+                   pro_fpr_limit=pro_fpr_limit, op=op, pr=pr_metrics)
     pairs = list(good) + list(bad)
     if pairs:
         spec = spec.resolve(*pairs[0][1].shape[:2])
@@ -402,6 +407,12 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     out = dict(best_ws=best_ws, auc_ssim=sweep[best_j], auc_mse=M.roc_auc(y_true, full[:, -2]),
                auc_psnr=M.roc_auc(y_true, -full[:, -1]), n_images=len(pairs), window_sizes=sizes)
     print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}")
+    if want.pr:                                               # the AUCs' score orientation: 1 - SSIM at best_ws, MSE, -PSNR
+        cols = (("ssim", 1.0 - full[:, best_j]), ("mse", full[:, -2]), ("psnr", -full[:, -1]))
+        pr = {k: M.average_precision(y_true, s) for k, s in cols}
+        out.update({f"ap_{k}": v[0] for k, v in pr.items()}, **{f"f1max_{k}": v[1] for k, v in pr.items()})
+        print(f"Test APs - SSIM(best ws={best_ws}): {out['ap_ssim']:.4f}, MSE: {out['ap_mse']:.4f}, PSNR: {out['ap_psnr']:.4f}; "
+              f"F1-max - SSIM: {out['f1max_ssim']:.4f}, MSE: {out['f1max_mse']:.4f}, PSNR: {out['f1max_psnr']:.4f}")
     calib = None
     if op is not None and op.fpr is not None and world == 1:          # the calibration images go the test images' way
         calib = super_resolve_u8(model, [lr for lr, _ in op.calib], [h for _, h in op.calib], float(opt.rgb_range))
@@ -422,7 +433,7 @@ def _pixel_stage(shard: Shard, spec: MapSpec, want: Request, masks, best_ws, cal
         if want.save_maps and shard.output_dir:
             save_anomaly_maps(maps, shard.my_names(), shard.my_splits(), shard.output_dir)
         if want.map_image_score:
-            found = _map_max_auc(shard, spec, img_max)
+            found = _map_max_auc(shard, spec, img_max, want.pr)
     runs, labels = _single_rank_gate(shard, want, masks, best_ws, maps)
     if not runs:
         return spec.entries(found) if found else {}
@@ -446,15 +457,20 @@ def _with_window(spec: MapSpec, best_ws, world: int) -> MapSpec:
     return spec if spec.scales else replace(spec, ws=max(spec.ws, 1))
 
 
-def _map_max_auc(shard: Shard, spec: MapSpec, img_max: torch.Tensor) -> dict:
+def _map_max_auc(shard: Shard, spec: MapSpec, img_max: torch.Tensor, pr: bool = False) -> dict:
     """``auc_map_max``, the ROC-AUC of each image's map maximum: every rank's maxima are gathered to rank 0 like the score
-    rows (one more gather, one column); {} on the other ranks.  No masks needed."""
+    rows (one more gather, one column); {} on the other ranks.  No masks needed.  ``pr``: also ``ap_map_max`` and
+    ``f1max_map_max`` of the same gathered maxima."""
     full = gather_score_rows(shard.mine, img_max.double().cpu().numpy()[:, None], len(shard.y_true), shard.rank, shard.world)
     if full is None:
         return {}
     auc = M.roc_auc(shard.y_true, full[:, 0])
     print(f"Image AUC - max of the {spec.text(always_sigma=True)}: {auc:.4f}")
-    return dict(auc_map_max=auc)
+    if not pr:
+        return dict(auc_map_max=auc)
+    ap, f1 = M.average_precision(shard.y_true, full[:, 0])
+    print(f"Image AP - max of the {spec.text(always_sigma=True)}: {ap:.4f}, F1-max: {f1:.4f}")
+    return dict(auc_map_max=auc, ap_map_max=ap, f1max_map_max=f1)
 
 
 def _single_rank_gate(shard: Shard, want: Request, masks, best_ws, maps):
@@ -479,8 +495,10 @@ def _single_rank_gate(shard: Shard, want: Request, masks, best_ws, maps):
 
 
 def _pixel_scores(spec: MapSpec, want: Request, maps: torch.Tensor, labels) -> dict:
-    """``auc_pixel``, the exact pixel-level ROC-AUC, and ``aupro`` with ``pro_fpr_limit``, the normalised area under the
-    per-region overlap curve up to that limit: each where asked for and ``labels`` are there."""
+    """``auc_pixel``, the exact pixel-level ROC-AUC, ``aupro`` with ``pro_fpr_limit``, the normalised area under the
+    per-region overlap curve up to that limit, and ``ap_pixel`` with the best-F1 point of ``metrics.pixel_pr`` (``f1max_pixel``,
+    its ``f1max_pixel_precision`` and ``f1max_pixel_recall``, and ``f1max_pixel_threshold``, which ``--threshold`` takes: predict
+    iff map > it): each where asked for and ``labels`` are there."""
     out = {}
     if want.pixel_metrics and labels is not None:
         out["auc_pixel"] = M.pixel_roc_auc(maps, labels)
@@ -489,6 +507,12 @@ def _pixel_scores(spec: MapSpec, want: Request, maps: torch.Tensor, labels) -> d
         limit = float(want.pro_fpr_limit)
         out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, want.pro_fpr_limit), limit
         print(f"AU-PRO - {spec.text(f', fpr <= {limit:g}')}: {out['aupro']:.4f}")
+    if want.pr and labels is not None:
+        r = M.pixel_pr(maps, labels)
+        out.update(ap_pixel=r["ap"], f1max_pixel=r["f1max"], f1max_pixel_threshold=r["threshold"],
+                   f1max_pixel_precision=r["precision"], f1max_pixel_recall=r["recall"])
+        print(f"Pixel AP - {spec.text()}: {r['ap']:.4f}, F1-max: {r['f1max']:.4f} (precision={r['precision']:.4f} "
+              f"recall={r['recall']:.4f} at threshold={r['threshold']:.9g})")
     return out
 
 
@@ -570,7 +594,7 @@ def _run(args):
     b = list(iter_split(opt.data_root, class_name, 'bad', opt.scale, opt.n_colors))
     out_dir = args.output_dir or (os.path.join(args.run_dir, 'eval_results') if args.run_dir else './workspace/eval_results')
     masks = None
-    if (args.pixel_metrics or args.aupro or want_op) and world == 1:
+    if (args.pixel_metrics or args.aupro or args.pr_metrics or want_op) and world == 1:
         masks, missing = load_masks(opt.data_root, class_name, [('good', n) for n, _, _ in g] + [('bad', n) for n, _, _ in b],
                                     [hr.shape[:2] for _, _, hr in g + b])
         if missing:
@@ -588,7 +612,7 @@ def _run(args):
                            masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws,
                            aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit, map_sigma=args.map_sigma,
                            map_image_score=args.map_image_score, map_scales=args.map_scales, map_reduce=args.map_reduce,
-                           map_source=args.map_source, operating_point=op)
+                           map_source=args.map_source, operating_point=op, pr_metrics=args.pr_metrics)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -116,6 +116,22 @@ def roc_auc(y_true: Sequence[int], scores: Sequence[float]) -> float:
     return out.value
 
 
+def average_precision(y_true: Sequence[int], scores: Sequence[float]) -> Tuple[float, float]:
+    """(average precision, F1-max) of binary labels: ``sklearn.metrics.average_precision_score``, and the best
+    ``2 tp / (2 tp + fp + fn)`` over the thresholds "predict iff score >= s" at every distinct score s (compared exactly, in
+    integers).  Host only, like ``roc_auc``.  ValueError for a NaN score, no positive label and a shape mismatch."""
+    y = np.ascontiguousarray(np.asarray(y_true), dtype=np.int32)
+    s = np.ascontiguousarray(np.asarray(scores), dtype=np.float64)
+    if y.shape != s.shape or y.ndim != 1:
+        raise ValueError("y_true and scores must be 1-D and of equal length")
+    ap, f1 = C.c_double(), C.c_double()
+    rc = L.lib().srad_average_precision(y.ctypes.data_as(C.POINTER(C.c_int32)), s.ctypes.data_as(C.POINTER(C.c_double)), len(y),
+                                        C.byref(ap), C.byref(f1))
+    if rc:
+        raise ValueError(L.lib().srad_last_error().decode())
+    return ap.value, f1.value
+
+
 MAP_REDUCTIONS = ("mean", "max")           # srad_*_maps_multi's reduce numbers 0, 1
 def _maps(query: str, fn: str, sr_u8: torch.Tensor, hr_u8: torch.Tensor, ws, reduce: Optional[str] = None) -> torch.Tensor:
     """float32 [n,H,W] maps of the stacks from ``srad_<fn>`` (workspace size from ``srad_<query>``): ``ws`` is one window size,
@@ -209,6 +225,61 @@ def pixel_roc_auc(scores: torch.Tensor, labels: torch.Tensor) -> float:
     if n_pos == 0 or n_neg == 0:
         raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
     return float(auc.item())
+
+
+PIXEL_PR_COUNTS = ("n_pos", "n_neg", "n_nan", "n_points", "tp", "fp", "score_bits")     # srad_pixel_pr's counts_out
+
+
+def _pixel_pr(scores: torch.Tensor, labels: torch.Tensor, curve: bool):
+    """``srad_pixel_pr`` on the flattened tensors after the checks of ``pixel_pr``: (counts under ``PIXEL_PR_COUNTS``, ap, the
+    three curve tensors cut to n_points or None)."""
+    _need_cuda(scores, labels)
+    s = scores.detach().reshape(-1).float().contiguous()
+    y = labels.detach().reshape(-1)
+    y = (y != 0).to(torch.uint8).contiguous() if y.dtype != torch.uint8 else y.contiguous()
+    if s.numel() != y.numel():
+        raise ValueError("scores and labels must have the same number of elements")
+    if s.numel() == 0:
+        raise ValueError("pixel_pr of no elements")
+    n, dev = s.numel(), s.device
+    counts = torch.empty(len(PIXEL_PR_COUNTS), dtype=torch.int64, device=dev)       # u64 on the device; the values stay below 2^32
+    ap = torch.empty((), dtype=torch.float64, device=dev)
+    cap = n if curve else 0                                                          # at most one point per score
+    pts = [torch.empty(cap, dtype=t, device=dev) for t in (torch.float64, torch.float64, torch.float32)] if curve else [None] * 3
+    _call_with_ws("pixel_pr_workspace_bytes", (C.c_int64(n),), "pixel_pr",
+                  (L.dptr(s), L.dptr(y), C.c_int64(n), L.dptr(counts), L.dptr(ap), *(L.dptr(p) for p in pts), C.c_int64(cap)), dev)
+    c = dict(zip(PIXEL_PR_COUNTS, counts.tolist()))
+    if c["n_nan"]:
+        raise ValueError(f"pixel_pr: {c['n_nan']} of {n} scores are NaN")
+    if c["n_pos"] == 0:
+        raise ValueError("No positive class found in y_true. Average precision is not defined in that case.")
+    return c, float(ap.item()), ([p[:c["n_points"]] for p in pts] if curve else None)
+
+
+def pixel_pr(scores: torch.Tensor, labels: torch.Tensor) -> dict:
+    """Exact pixel-level precision-recall of GPU tensors (float32 scores; labels nonzero = positive, any integer or bool dtype, as
+    ``pixel_roc_auc``), DESIGN.md "Precision-recall".  Every distinct score s is a threshold "predict iff score >= s".  Returns
+    ``ap`` (``sklearn.metrics.average_precision_score`` of the flattened arrays) and the point of the highest F1, compared
+    exactly in integers, the higher threshold keeping a tie: ``f1max``, ``precision`` and ``recall`` (Python floats from the
+    integer counts ``tp``, ``fp``, ``fn``), ``score`` = its s*, ``threshold`` = the largest float32 below s*, for the
+    ``map > threshold`` convention of ``operating_point`` and ``evaluate --threshold`` (for s* = -inf there is none and -inf is
+    returned, which leaves the -inf scores out), and ``n_pos``, ``n_neg``.  With no negative label AP = 1.  ValueError for a NaN
+    score, no positive label, a size mismatch and an empty input."""
+    c, ap, _ = _pixel_pr(scores, labels, curve=False)
+    tp, fp = c["tp"], c["fp"]
+    fn = c["n_pos"] - tp
+    star = np.array([c["score_bits"]], dtype=np.uint32).view(np.float32)[0]
+    return dict(ap=ap, f1max=2 * tp / (2 * tp + fp + fn), precision=tp / (tp + fp), recall=tp / c["n_pos"], score=float(star),
+                threshold=float(np.nextafter(star, np.float32(-np.inf))), tp=tp, fp=fp, fn=fn, n_pos=c["n_pos"], n_neg=c["n_neg"])
+
+
+def pr_curve(scores: torch.Tensor, labels: torch.Tensor) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The precision-recall curve behind ``pixel_pr``: (precision float64, recall float64, thresholds float32), one point per
+    distinct score from the HIGHEST down, point k being "predict iff score >= thresholds[k]" (a zero threshold is +0.0).
+    These are the points of ``sklearn.metrics.precision_recall_curve`` in reverse order and without the (precision 1, recall 0)
+    end point that sklearn appends.  ValueError as ``pixel_pr``."""
+    _, _, pts = _pixel_pr(scores, labels, curve=True)
+    return tuple(p.cpu().numpy() for p in pts)
 
 
 def _mask_stack(masks: torch.Tensor) -> torch.Tensor:

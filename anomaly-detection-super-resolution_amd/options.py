@@ -280,6 +280,10 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                    help="AU-PRO of the anomaly maps against the test/bad/GT masks: the per-region overlap curve's normalised area "
                         "up to --pro-fpr-limit (needs --gpus 1)")
     p.add_argument('--pro-fpr-limit', type=float, default=0.3, help="false-positive-rate limit of --aupro, in (0, 1]")
+    p.add_argument('--pr-metrics', action='store_true', default=False,
+                   help="average precision and F1-max next to the AUCs: of the image scores, of the map maximum with "
+                        "--map-image-score, and of the anomaly maps against the test/bad/GT masks (the pixel level needs --gpus 1); "
+                        "the F1-max threshold it prints can be passed to --threshold")
     p.add_argument('--map-sigma', type=_nonnegative_float, default=0.0,
                    help="Gaussian sigma (px) the anomaly maps are smoothed with before they are saved or scored "
                         "(scipy.ndimage.gaussian_filter, truncate 4); 4 is the MVTec convention, 0 = the raw maps")

@@ -204,6 +204,10 @@ int srad_val_metrics(const float* sr, const float* hr, int B, int C, int H, int 
 /* Binary ROC-AUC == sklearn.metrics.roc_auc_score (ties count one half).  labels/scores are HOST
  * arrays (n is the number of test images, a few hundred); returns non-zero if one class is absent. */
 int srad_roc_auc(const int32_t* labels, const double* scores, int n, double* auc);
+/* Binary average precision == sklearn.metrics.average_precision_score (the sum over distinct scores from the highest down of
+ * (R_k - R_k-1) * P_k), and the best F1 = 2 tp / (tp + fp + P) over the same thresholds, compared exactly in integers.  HOST
+ * arrays like srad_roc_auc; returns non-zero for a NaN score and when no label is positive. */
+int srad_average_precision(const int32_t* labels, const double* scores, int n, double* ap, double* f1max);
 /* Per-pixel anomaly maps for `n_img` u8 HWC image pairs (sr, hr, each [n_img,H,W,C]) at ONE window size `ws`:
  *   map_out[i, y, x] = 1 - ssim_map(hr_i/255, sr_i/255, ws)[y, x]      (src/metrics.py:26-67; the array line 66 averages)
  * with the arithmetic of srad_score_pairs: luminance, float64 box sums with numpy "reflect" padding, C1 = 1e-4, C2 = 9e-4, the
@@ -245,6 +249,19 @@ int srad_error_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H
 int srad_pixel_auc_workspace_bytes(int64_t n, size_t* bytes);
 int srad_pixel_roc_auc(const float* scores, const uint8_t* labels, int64_t n, uint64_t* counts_out, double* auc_out,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* Exact precision-recall of `n` DEVICE float32 scores against DEVICE u8 labels (labels[i] != 0 = positive), n < 2^31: every
+ * distinct score s (-0.0 == +0.0) is a threshold "predict iff score >= s", from the highest down (DESIGN.md "Precision-recall").
+ *   counts_out (DEVICE, 7 x u64) = {n_pos, n_neg, n_nan, n_points, best_tp, best_fp, best_score_bits}: the point of the highest
+ *   F1 = 2 tp / (tp + fp + n_pos), compared exactly in integers, the higher threshold keeping a tie, and the float32 bits of its
+ *   score;  *ap_out (DEVICE double) = sklearn.metrics.average_precision_score, NaN when n_pos == 0.
+ *   curve_precision / curve_recall (DEVICE double) and curve_score (DEVICE float32), all three or none NULL, receive the first
+ *   min(curve_cap, n_points) points (no (1, 0) end point is appended).
+ * NaN scores are left out of every count but n_nan.  Stream-ordered, no host sync; the same device sort and scan as
+ * srad_pixel_roc_auc; workspace >= srad_pixel_pr_workspace_bytes(n) (about 17 bytes per score). */
+int srad_pixel_pr_workspace_bytes(int64_t n, size_t* bytes);
+int srad_pixel_pr(const float* scores, const uint8_t* labels, int64_t n, uint64_t* counts_out, double* ap_out,
+                  double* curve_precision, double* curve_recall, float* curve_score, int64_t curve_cap, void* workspace,
+                  size_t workspace_bytes, void* stream);
 /* Regions of DEVICE u8 masks [n_img, H, W] (nonzero = defect), n_img x H x W in [1, 2^31): the 8-connected components of each
  * image's mask (scipy.ndimage.label with a 3 x 3 structure, per image; nothing connects across images).
  *   region_size_out[i] (DEVICE u32) = |region of pixel i|, 0 where mask == 0;
