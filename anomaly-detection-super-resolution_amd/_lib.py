@@ -104,6 +104,9 @@ _SIG = {
     "srad_dual_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "srad_dual_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P, _P,
                                     C.c_size_t, C.c_int, _P]),
+    # self-ensemble x8
+    "srad_ensemble_inputs": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "srad_ensemble_mean": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     # scorer
     "srad_to_u8_hwc": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "srad_quantize": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),

@@ -1,6 +1,7 @@
 // kernels_misc.hip - HBM-bound helper kernels: LayerNorm rows, layout changes with the mean
-// shift folded in, bicubic upsampling, channel-attention gate.  All are one pass over their
-// data with coalesced accesses; they are a few percent of the forward's time.
+// shift folded in, bicubic upsampling, channel-attention gate, the self-ensemble's eight members
+// and their mean.  All are one pass over their data with coalesced accesses; they are a few percent
+// of the forward's time.
 #include "srad_common.h"
 #include <stdlib.h>
 #include <stdarg.h>
@@ -34,7 +35,7 @@ struct Prof {
 } g_prof;
 const char* const kClassNames[SRAD_K_COUNT] = {"gemm_bn64", "gemm_bn32", "gemm_bn16", "window_attn", "layernorm",
                                                "layout", "pack_weight", "score", "misc", "mlp_block", "qkv_attn",
-                                               "wgrad", "window_attn_bwd", "layernorm_bwd", "optim", "wgrad_reduce", "mlp_bwd", "ln_qkv", "conv80"};
+                                               "wgrad", "window_attn_bwd", "layernorm_bwd", "optim", "wgrad_reduce", "mlp_bwd", "ln_qkv", "conv80", "ensemble"};
 }  // namespace
 
 // ---------------------------------------------------------------- path overrides (include/srad.h)
@@ -157,7 +158,151 @@ static inline int grid_for(size_t total) {
   return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
 
+// ---------------------------------------------------------------- self-ensemble x8 (DESIGN.md "Self-ensemble")
+// Both kernels: one workgroup of 256 threads per 64 x 64 tile of one [H, W] plane of the UNTRANSFORMED image; thread
+// (tx = tid & 63, ty = tid >> 6) owns column tx of rows ty, ty + 4, ... of the tile.  Members 0..3 keep the row direction,
+// so a wave moves one row segment (256 bytes) forwards or reversed; members 4..7 swap H and W and cross a [64][65] LDS tile:
+// the row-wise access has stride 1 and the column-wise one stride 65 words, both conflict-free on the 64 banks, and both
+// global sides run along their own rows.
+constexpr int kEnsTile = 64, kEnsRows = kEnsTile / 4;
+
+// x [n_planes, H, W] -> a [4, n_planes, H, W] (members 0..3) and b [4, n_planes, W, H] (members 4..7); x is read once.
+__global__ __launch_bounds__(256) void ensemble_inputs_kernel(const float* __restrict__ x, float* __restrict__ a,
+                                                              float* __restrict__ b, int n_planes, int H, int W, int tiles_w,
+                                                              int tiles_h) {
+  __shared__ float tile[kEnsTile][kEnsTile + 1];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int tw = blockIdx.x % tiles_w, th = (blockIdx.x / tiles_w) % tiles_h, plane = blockIdx.x / (tiles_w * tiles_h);
+  const int r0 = th * kEnsTile, c0 = tw * kEnsTile;
+  const int hw = H * W, member = n_planes * hw;      // 8 * member < 2^31 (checked by the caller)
+  const float* xp = x + plane * hw;
+  float* ap = a + plane * hw;
+  float* bp = b + plane * hw;
+  const int c = c0 + tx;
+#pragma unroll
+  for (int k = 0; k < kEnsRows; ++k) {
+    const int rl = ty + 4 * k, r = r0 + rl;
+    if (r < H && c < W) {
+      const float v = xp[r * W + c];
+      tile[rl][tx] = v;
+      ap[r * W + c] = v;                                           // 0: x
+      ap[member + r * W + (W - 1 - c)] = v;                        // 1: v
+      ap[2 * member + (H - 1 - r) * W + c] = v;                    // 2: h
+      ap[3 * member + (H - 1 - r) * W + (W - 1 - c)] = v;          // 3: h v
+    }
+  }
+  __syncthreads();
+  const int r = r0 + tx;                                           // transposed side: the lanes run along H
+#pragma unroll
+  for (int k = 0; k < kEnsRows; ++k) {
+    const int cl = ty + 4 * k, cc = c0 + cl;
+    if (r < H && cc < W) {
+      const float v = tile[tx][cl];                                // x[r][cc]
+      bp[cc * H + r] = v;                                          // 4: T
+      bp[member + (W - 1 - cc) * H + r] = v;                       // 5: T v
+      bp[2 * member + cc * H + (H - 1 - r)] = v;                   // 6: T h
+      bp[3 * member + (W - 1 - cc) * H + (H - 1 - r)] = v;         // 7: T h v
+    }
+  }
+}
+
+// ya [4, n_planes, H, W], yb [4, n_planes, W, H] -> out [n_planes, H, W] = (((z0 + z1) + z2) + ... + z7) * 0.125f with z_t the
+// back-transformed member t: seven fp32 additions in member order (there is no product to contract one with) and one exact
+// scaling.  The sixteen running sums of a thread stay in registers while the one LDS tile takes members 4..7 in turn.
+__global__ __launch_bounds__(256) void ensemble_mean_kernel(const float* __restrict__ ya, const float* __restrict__ yb,
+                                                            float* __restrict__ out, int n_planes, int H, int W, int tiles_w,
+                                                            int tiles_h) {
+  __shared__ float tile[kEnsTile][kEnsTile + 1];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int tw = blockIdx.x % tiles_w, th = (blockIdx.x / tiles_w) % tiles_h, plane = blockIdx.x / (tiles_w * tiles_h);
+  const int r0 = th * kEnsTile, c0 = tw * kEnsTile;
+  const int hw = H * W, member = n_planes * hw;
+  const float* ap = ya + plane * hw;
+  const float* bp = yb + plane * hw;
+  const int c = c0 + tx;
+  float acc[kEnsRows];
+#pragma unroll
+  for (int k = 0; k < kEnsRows; ++k) {
+    const int r = r0 + ty + 4 * k;
+    acc[k] = 0.f;
+    if (r < H && c < W) {
+      float s = ap[r * W + c] + ap[member + r * W + (W - 1 - c)];
+      s = s + ap[2 * member + (H - 1 - r) * W + c];
+      acc[k] = s + ap[3 * member + (H - 1 - r) * W + (W - 1 - c)];
+    }
+  }
+  const int rt = r0 + tx;                                          // transposed side: the lanes run along H
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t) __syncthreads();                                        // the tile's readers of member t - 1 are done
+#pragma unroll
+    for (int k = 0; k < kEnsRows; ++k) {
+      const int cl = ty + 4 * k, cc = c0 + cl;
+      if (rt < H && cc < W)                                        // z[rt][cc] of member 4 + t
+        tile[cl][tx] = bp[t * member + ((t & 1) ? W - 1 - cc : cc) * H + ((t & 2) ? H - 1 - rt : rt)];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kEnsRows; ++k) {
+      const int rl = ty + 4 * k;
+      if (r0 + rl < H && c < W) acc[k] = acc[k] + tile[tx][rl];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kEnsRows; ++k) {
+    const int r = r0 + ty + 4 * k;
+    if (r < H && c < W) out[plane * hw + r * W + c] = acc[k] * 0.125f;
+  }
+}
+
+// What both entry points check before they launch: sizes, the 32-bit offset limit of the kernels, and the tile count.
+int ensemble_check(const char* what, int B, int C, int H, int W, int* tiles_w, int* tiles_h, unsigned* blocks) {
+  SRAD_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "%s: sizes must be positive, got B=%d C=%d H=%d W=%d", what, B, C, H, W);
+  const unsigned long long planes = (unsigned long long)B * C, hw = (unsigned long long)H * W;      // each below 2^62
+  SRAD_REQUIRE(planes < (1ull << 28) && hw < (1ull << 28) && planes * hw < (1ull << 28),
+               "%s: B*C*H*W*8 = %d*%d*%d*%d*8 does not fit 32-bit offsets (limit 2^31 elements over the eight members)", what,
+               B, C, H, W);
+  *tiles_w = (W + kEnsTile - 1) / kEnsTile;
+  *tiles_h = (H + kEnsTile - 1) / kEnsTile;
+  *blocks = (unsigned)((unsigned long long)B * C * *tiles_w * *tiles_h);   // <= total < 2^28
+  return SRAD_OK;
+}
+
+inline bool ranges_overlap(const float* p, size_t np, const float* q, size_t nq) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + nq * sizeof(float) && b < a + np * sizeof(float);
+}
+
 }  // namespace
+
+extern "C" int srad_ensemble_inputs(const float* x, int B, int C, int H, int W, float* out_a, float* out_b, void* stream) {
+  SRAD_REQUIRE(x && out_a && out_b, "ensemble_inputs: null argument");
+  int tiles_w, tiles_h;
+  unsigned blocks;
+  SRAD_TRY(ensemble_check("ensemble_inputs", B, C, H, W, &tiles_w, &tiles_h, &blocks));
+  const size_t n = (size_t)B * C * H * W;
+  SRAD_REQUIRE(!ranges_overlap(x, n, out_a, 4 * n) && !ranges_overlap(x, n, out_b, 4 * n) && !ranges_overlap(out_a, 4 * n, out_b, 4 * n),
+               "ensemble_inputs: the outputs overlap the input or each other");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  SradProfScope prof(s, SRAD_K_ENSEMBLE, 0.0, 36.0 * n);
+  hipLaunchKernelGGL(ensemble_inputs_kernel, dim3(blocks), dim3(256), 0, s, x, out_a, out_b, B * C, H, W, tiles_w, tiles_h);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+extern "C" int srad_ensemble_mean(const float* y_a, const float* y_b, int B, int C, int H, int W, float* out, void* stream) {
+  SRAD_REQUIRE(y_a && y_b && out, "ensemble_mean: null argument");
+  int tiles_w, tiles_h;
+  unsigned blocks;
+  SRAD_TRY(ensemble_check("ensemble_mean", B, C, H, W, &tiles_w, &tiles_h, &blocks));
+  const size_t n = (size_t)B * C * H * W;
+  SRAD_REQUIRE(!ranges_overlap(out, n, y_a, 4 * n) && !ranges_overlap(out, n, y_b, 4 * n), "ensemble_mean: out overlaps an input");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  SradProfScope prof(s, SRAD_K_ENSEMBLE, 7.0 * n, 36.0 * n);
+  hipLaunchKernelGGL(ensemble_mean_kernel, dim3(blocks), dim3(256), 0, s, y_a, y_b, out, B * C, H, W, tiles_w, tiles_h);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
 
 int srad_launch_layernorm(const float* x, int ldx, float* y, int ldy, int rows, int C, const float* g, const float* b,
                           float eps, hipStream_t stream) {

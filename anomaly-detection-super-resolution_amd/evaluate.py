@@ -290,19 +290,24 @@ def gather_score_rows(mine: Sequence[int], rows: np.ndarray, total: int, rank: i
 
 
 @torch.no_grad()
-def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndarray], rgb_range: float, batch: int = 0
-                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndarray], rgb_range: float, batch: int = 0,
+                     self_ensemble: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """collect_pairs (src/evaluate.py:204-224): forward, crop to the HR size, truncate to u8.
     Returns (sr, hr) uint8 stacks [n,H,W,C] on the GPU.  ``batch`` images per forward; 0 = as many as make ~64 k LR pixels
     (64 images at 128 px / x4, one 1024 px tile): the reference forwards one image at a time, the outputs per image are the same
-    and the chip is only filled from a few thousand tokens up (78 pairs at 128 px: 1830 -> 2120 images/s in split-bf16 mode)."""
+    and the chip is only filled from a few thousand tokens up (78 pairs at 128 px: 1830 -> 2120 images/s in split-bf16 mode).
+    ``self_ensemble``: the forwards go through ``model.forward_x8`` (``Model``; DESIGN.md "Self-ensemble"), whose stacked forward
+    holds 8 members per image, so the automatic batch is an eighth; crop and u8 conversion come after the mean."""
     dev = model.device if hasattr(model, 'device') else next(model.parameters()).device
     if batch <= 0 and len(lr_u8):
         batch = max(1, min(64, 65536 // max(1, lr_u8[0].shape[0] * lr_u8[0].shape[1])))
+        if self_ensemble:
+            batch = max(1, batch // 8)
+    forward = model.forward_x8 if self_ensemble else model
     sr_out: List[torch.Tensor] = []
     for i in range(0, len(lr_u8), batch):
         lr = torch.from_numpy(np.stack(lr_u8[i:i + batch])).to(dev).permute(0, 3, 1, 2).float() * (rgb_range / 255.0)   # np2Tensor
-        sr = model(lr)
+        sr = forward(lr)
         if isinstance(sr, list):
             sr = sr[-1]
         h, w = hr_u8[i].shape[:2]
@@ -355,7 +360,7 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
                      map_ws: int = 0, map_scales=(), map_reduce: str = 'mean', map_source: str = 'ssim', operating_point=None,
-                     pr_metrics: bool = False, map_sigma: float = 0.0,
+                     pr_metrics: bool = False, self_ensemble: bool = False, map_sigma: float = 0.0,
                      map_image_score: bool = False, aupro: bool = False, pro_fpr_limit: float = 0.3) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
@@ -369,7 +374,10 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
 
     ``pr_metrics`` (off by default): average precision and F1-max next to every AUC - of the three image scores (``ap_*``,
     ``f1max_*``, on rank 0 from the gathered table), of the map maximum with ``map_image_score``, and of the pixels
-    (``_pixel_scores``) where the pixel metrics can run."""
+    (``_pixel_scores``) where the pixel metrics can run.
+
+    ``self_ensemble`` (off by default): every SR image - test and calibration - is the x8 self-ensemble of the model
+    (``Model.forward_x8``); the result then carries ``self_ensemble: True``."""
     spec = MapSpec(source=map_source, ws=map_ws, scales=map_scales, reduce=map_reduce, sigma=map_sigma)
     op = None
     if operating_point is not None:
@@ -387,7 +395,8 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
         print('Test set lacks both classes; AUC not available')
         return {}
     mine = shard_indices(len(pairs), rank, world)
-    sr, hr = super_resolve_u8(model, [pairs[i][0] for i in mine], [pairs[i][1] for i in mine], float(opt.rgb_range))
+    x8 = dict(self_ensemble=True) if self_ensemble else {}    # off: the call as it always was
+    sr, hr = super_resolve_u8(model, [pairs[i][0] for i in mine], [pairs[i][1] for i in mine], float(opt.rgb_range), **x8)
     shard = Shard(sr=sr, hr=hr, mine=mine, y_true=y_true, names=names, rank=rank, world=world, output_dir=output_dir)
     if save_images and output_dir:
         scale_value = opt.scale[-1] if isinstance(opt.scale, list) else int(opt.scale)
@@ -406,7 +415,10 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     best_ws = sizes[best_j]
     out = dict(best_ws=best_ws, auc_ssim=sweep[best_j], auc_mse=M.roc_auc(y_true, full[:, -2]),
                auc_psnr=M.roc_auc(y_true, -full[:, -1]), n_images=len(pairs), window_sizes=sizes)
-    print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}")
+    if self_ensemble:
+        out["self_ensemble"] = True
+    print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}"
+          + (" (self-ensemble x8)" if self_ensemble else ""))
     if want.pr:                                               # the AUCs' score orientation: 1 - SSIM at best_ws, MSE, -PSNR
         cols = (("ssim", 1.0 - full[:, best_j]), ("mse", full[:, -2]), ("psnr", -full[:, -1]))
         pr = {k: M.average_precision(y_true, s) for k, s in cols}
@@ -415,7 +427,7 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
               f"F1-max - SSIM: {out['f1max_ssim']:.4f}, MSE: {out['f1max_mse']:.4f}, PSNR: {out['f1max_psnr']:.4f}")
     calib = None
     if op is not None and op.fpr is not None and world == 1:          # the calibration images go the test images' way
-        calib = super_resolve_u8(model, [lr for lr, _ in op.calib], [h for _, h in op.calib], float(opt.rgb_range))
+        calib = super_resolve_u8(model, [lr for lr, _ in op.calib], [h for _, h in op.calib], float(opt.rgb_range), **x8)
     out.update(_pixel_stage(shard=shard, spec=spec, want=want, masks=masks, best_ws=best_ws, calib=calib))
     return out
 
@@ -612,7 +624,8 @@ def _run(args):
                            masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws,
                            aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit, map_sigma=args.map_sigma,
                            map_image_score=args.map_image_score, map_scales=args.map_scales, map_reduce=args.map_reduce,
-                           map_source=args.map_source, operating_point=op, pr_metrics=args.pr_metrics)
+                           map_source=args.map_source, operating_point=op, pr_metrics=args.pr_metrics,
+                           self_ensemble=args.self_ensemble)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -106,6 +106,7 @@ def build_train_opt(args):
     opt.test_only = args.test_only
     opt.precision = args.dtype
     opt.data_root = data_root
+    opt.self_ensemble = bool(getattr(args, 'self_ensemble', False))
     return opt
 
 

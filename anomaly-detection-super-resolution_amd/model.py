@@ -65,7 +65,26 @@ class Model(nn.Module):
 
     def forward(self, x, idx_scale=0):
         self.idx_scale = idx_scale
+        if self.self_ensemble and not self.training:
+            return self.forward_x8(x)
         return self.model(x)
+
+    def forward_x8(self, x):
+        """Self-ensemble x8 (DESIGN.md "Self-ensemble"; ``forward_x8`` of the EDSR / DRN code the reference descends from):
+        the network's outputs for the 8 flips and transposes of ``x``, each transform undone, averaged in member order.
+        Square input is one forward of the stacked [8B,C,H,W] batch; other input two forwards, members 0..3 as [4B,C,H,W] and
+        4..7 as [4B,C,W,H].  A list of outputs (DRN-L) is ensembled output by output.  Inference only: the result carries no
+        graph."""
+        from . import ops
+        ys = [self.model(b) for b in ops.ensemble_batches(x)]
+        many = isinstance(ys[0], (list, tuple))
+        outs = []
+        for per_batch in zip(*(y if many else [y] for y in ys)):
+            if len(per_batch) == 1:                           # square: both halves live in the one stacked output
+                n = per_batch[0].shape[0] // 2
+                per_batch = (per_batch[0][:n], per_batch[0][n:])
+            outs.append(ops.ensemble_mean(*per_batch))
+        return outs if many else outs[0]
 
     def get_model(self):
         return self.model

@@ -507,3 +507,50 @@ def mlp_block(attn: torch.Tensor, shortcut: torch.Tensor, w_proj, b_proj, ln_g, 
                                       int(act), float(slope), float(alpha), L.dptr(residual), 0 if residual is None else residual.stride(0),
                                       L.dptr(out), out.stride(0), int(out_offset), sp, sb, L.current_stream_ptr()), "op_mlp_block")
     return out
+
+
+# ----------------------------------------------------------------------------------- self-ensemble x8
+def _ensemble_arg(t: torch.Tensor, what: str) -> torch.Tensor:
+    _need_cuda(t)
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise ValueError(f"{what}: expected a 4-d fp32 tensor, got {tuple(t.shape)} {t.dtype}")
+    return t.detach().contiguous()
+
+
+def ensemble_batches(x: torch.Tensor) -> list:
+    """The forward batches of the self-ensemble of x [B,C,H,W] (DESIGN.md "Self-ensemble"), filled by one launch
+    (``srad_ensemble_inputs``): for square input one stacked [8B,C,H,W] tensor, otherwise members 0..3 as [4B,C,H,W] and
+    members 4..7 as [4B,C,W,H].  Image b of member t is at index t*B + b of the stack (t - 4 in the second tensor)."""
+    x = _ensemble_arg(x, "ensemble_inputs")
+    B, Cc, H, W = x.shape
+    if H == W:
+        batches = [torch.empty(8 * B, Cc, H, W, dtype=torch.float32, device=x.device)]
+        a, b = batches[0][:4 * B], batches[0][4 * B:]
+    else:
+        batches = [torch.empty(4 * B, Cc, H, W, dtype=torch.float32, device=x.device),
+                   torch.empty(4 * B, Cc, W, H, dtype=torch.float32, device=x.device)]
+        a, b = batches
+    L.check(L.lib().srad_ensemble_inputs(L.dptr(x), B, Cc, H, W, L.dptr(a), L.dptr(b), L.current_stream_ptr()), "ensemble_inputs")
+    return batches
+
+
+def ensemble_inputs(x: torch.Tensor) -> tuple:
+    """(a, b): members 0..3 of x [B,C,H,W] as [4B,C,H,W] and members 4..7 as [4B,C,W,H]; for square input both are views of
+    one [8B,C,H,W] allocation (``ensemble_batches``)."""
+    batches = ensemble_batches(x)
+    if len(batches) == 1:
+        n = batches[0].shape[0] // 2
+        return batches[0][:n], batches[0][n:]
+    return batches[0], batches[1]
+
+
+def ensemble_mean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """a [4B,C,H,W] and b [4B,C,W,H], the network's outputs for members 0..3 and 4..7 -> [B,C,H,W]: every member's
+    transform undone, then ``(((z0 + z1) + z2) + ... + z7) * 0.125`` in fp32 (``srad_ensemble_mean``)."""
+    a, b = _ensemble_arg(a, "ensemble_mean"), _ensemble_arg(b, "ensemble_mean")
+    n, Cc, H, W = a.shape
+    if n % 4 or tuple(b.shape) != (n, Cc, W, H):
+        raise ValueError(f"ensemble_mean: {tuple(a.shape)} and {tuple(b.shape)} are not the two halves of an x8 ensemble")
+    out = torch.empty(n // 4, Cc, H, W, dtype=torch.float32, device=a.device)
+    L.check(L.lib().srad_ensemble_mean(L.dptr(a), L.dptr(b), n // 4, Cc, H, W, L.dptr(out), L.current_stream_ptr()), "ensemble_mean")
+    return out

@@ -196,6 +196,9 @@ def parse_train_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'], help="training precision (the evaluation at the end of "
                    "a run uses the evaluator's split-bf16 mode when this is fp32)")
     p.add_argument('--gpus', type=int, default=1)
+    p.add_argument('--self-ensemble', action='store_true', default=False,
+                   help="use self-ensemble method for test: the validation of a run (Trainer.test) and --test-only average the "
+                        "model's outputs for the 8 flips and transposes of each input")
     _with_config(p, pre_args)
     return p.parse_args(argv)
 
@@ -309,6 +312,9 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                    help="remove predicted 8-connected components of fewer than A pixels (1 = keep all)")
     p.add_argument('--save-masks', action='store_true', default=False,
                    help="write the predicted masks (0 / 255) as <output-dir>/anomaly_masks/{good,bad}/<name>.png")
+    p.add_argument('--self-ensemble', action='store_true', default=False,
+                   help="use self-ensemble method for test: every SR image is the mean of the model's outputs for the 8 flips "
+                        "and transposes of its input, each transform undone (8 forwards per image)")
     _with_config(p, pre_args)
     args = p.parse_args(argv)
     if args.threshold is not None and args.threshold_fpr is not None:

@@ -179,6 +179,19 @@ int srad_dual_backward(const float* w0, const float* w1, int C, int n_feats, flo
                        int W, const float* dy, float* dx, float* dw0, float* dw1, void* workspace, size_t workspace_bytes,
                        int precision, void* stream);
 
+/* ------------------------------------------------------------------ self-ensemble x8 (DESIGN.md "Self-ensemble")
+ * Member t in 0..7 of x [B,C,H,W] is T^(t>>2 & 1)( h^(t>>1 & 1)( v^(t & 1)(x) ) ) with v = flip along W, h = flip along H,
+ * T = swap H and W.  srad_ensemble_inputs writes all eight in one launch (x is read once): members 0..3 to out_a
+ * [4,B,C,H,W], members 4..7 to out_b [4,B,C,W,H].  srad_ensemble_mean undoes each member's transform on y_a [4,B,C,H,W] /
+ * y_b [4,B,C,W,H] (H, W are the OUTPUT's) and writes out [B,C,H,W] = (((z0 + z1) + z2) + ... + z7) * 0.125f: seven fp32
+ * additions in member order and one exact scaling, so out is defined bit for bit by its inputs.  The b half may directly
+ * follow the a half (a square stack [8,B,C,H,W]: out_b == out_a + 4*B*C*H*W); out must not overlap an input.  Any H, W >= 1;
+ * B*C*H*W*8 < 2^31.  Stream-ordered: no host synchronisation, no allocation, no atomics. */
+int srad_ensemble_inputs(const float* x, int B, int C, int H, int W, float* out_a /* [4,B,C,H,W] */,
+                         float* out_b /* [4,B,C,W,H] */, void* stream);
+int srad_ensemble_mean(const float* y_a /* [4,B,C,H,W] */, const float* y_b /* [4,B,C,W,H] */, int B, int C, int H, int W,
+                       float* out /* [B,C,H,W] */, void* stream);
+
 /* ------------------------------------------------------------------ scorer (src/evaluate.py:204-265) */
 /* `mul(255/range).clamp(0,255).byte()` TRUNCATING u8 conversion + NCHW->HWC (evaluate.py:214-215). */
 int srad_to_u8_hwc(const float* x, int B, int C, int H, int W, float rgb_range, uint8_t* out, void* stream);
