@@ -613,6 +613,25 @@ int srad_adam_step_dev(float* params, const float* grads, float* exp_avg, float*
                               reinterpret_cast<hipStream_t>(stream));
 }
 
+/* srad_adam_step / srad_adam_step_dev that also keep the weights' exponential moving average (BasicSR's model_ema) in the same
+   launch: after the step ema = fl(fl(ema_decay * ema) + fl((1 - ema_decay) * params)); params, exp_avg, exp_avg_sq get the bits of
+   the plain step */
+int srad_adam_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_decay,
+                       void* stream) {
+  SRAD_REQUIRE(params && grads && exp_avg && exp_avg_sq && n > 0, "adam_ema_step: bad argument");
+  return srad_launch_adam_ema(params, grads, exp_avg, exp_avg_sq, ema, (size_t)n, lr, beta1, beta2, eps, weight_decay, step,
+                              grad_scale, ema_decay, reinterpret_cast<hipStream_t>(stream));
+}
+
+int srad_adam_ema_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                           float beta1, float beta2, float eps, float weight_decay, float ema_decay, const float* dev_hyper,
+                           void* stream) {
+  SRAD_REQUIRE(params && grads && exp_avg && exp_avg_sq && dev_hyper && n > 0, "adam_ema_step_dev: bad argument");
+  return srad_launch_adam_ema_dev(params, grads, exp_avg, exp_avg_sq, ema, (size_t)n, beta1, beta2, eps, weight_decay, ema_decay,
+                                  dev_hyper, reinterpret_cast<hipStream_t>(stream));
+}
+
 /* dst[0..3] = (a, b, c, d) by value through a kernel: how the host hands Adam's per-step scalars to a replayed graph */
 int srad_set4(float* dst, float a, float b, float c, float d, void* stream) {
   SRAD_REQUIRE(dst, "set4: null argument");

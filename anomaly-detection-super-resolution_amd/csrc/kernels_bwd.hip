@@ -7,6 +7,7 @@
 //   dact_kernel, unshuffle_kernel, copy_cols_kernel   activation backward, pixel un-shuffle, column copies
 //   l1_grad_kernel          the L1 loss's gradient seed
 //   adam_kernel, adam_dev_kernel, set4_kernel         torch.optim.Adam on flat buffers, its per-step scalars
+//   adam_ema_kernel, adam_ema_dev_kernel              the same step, also keeping the weights' exponential moving average
 //
 // The weight gradients and the split-K queue's launches are kernels_wgrad.hip.  Data gradients (dX = dY W) are not here
 // either: they are the forward GEMM of kernels_gemm.hip run on the transposed packed weight (srad_launch_pack_weight_transposed).
@@ -185,9 +186,21 @@ __global__ void l1_grad_kernel(const float* __restrict__ a, const float* __restr
 }
 
 // torch.optim.Adam single-tensor arithmetic (torch/optim/adam.py _single_tensor_adam, amsgrad off, maximize off)
+// EMA: the same pass also keeps the exponential moving average of the weights, ema = fl(fl(d * ema) + fl(omd * p')) with p' the
+// parameter just stored - three separately rounded fp32 operations (no contraction into an fma), so the average is defined
+// bit for bit by its previous value and the new parameter (BasicSR's ema.mul_(decay).add_(p, alpha=1 - decay)).
+// HIP's __fmul_rn / __fadd_rn are plain * and + that the compiler may still contract; the pragma is what keeps them apart.
+__device__ __forceinline__ float ema_update(float d, float e, float omd, float pn) {
+#pragma clang fp contract(off)
+  const float a = d * e;
+  const float b = omd * pn;
+  return a + b;
+}
+template <bool EMA>
 __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                           float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps, float wd,
-                                          float bc1, float bc2_sqrt, float gs) {
+                                          float bc1, float bc2_sqrt, float gs, float* __restrict__ ema = nullptr, float d = 0.f,
+                                          float omd = 0.f) {
   const float step_size = lr / bc1;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     float grad = g[i] * gs;
@@ -198,17 +211,28 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
     m[i] = mi; v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     p[i] = w - step_size * (mi / denom);
+    if constexpr (EMA) ema[i] = ema_update(d, ema[i], omd, p[i]);     // p[i]: the value just stored
   }
 }
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gs) {
-  adam_body(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gs);
+  adam_body<false>(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gs);
+}
+__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ ema, size_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
+                                float bc2_sqrt, float gs, float d, float omd) {
+  adam_body<true>(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gs, ema, d, omd);
 }
 // the same step with the per-step scalars [lr, 1 - beta1^t, sqrt(1 - beta2^t), grad_scale] read from device memory, so
 // that a captured hipGraph of a whole training step can be replayed with a new step count / learning rate
 __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                 size_t n, float b1, float b2, float eps, float wd, const float* __restrict__ hyper) {
-  adam_body(p, g, m, v, n, hyper[0], b1, b2, eps, wd, hyper[1], hyper[2], hyper[3]);
+  adam_body<false>(p, g, m, v, n, hyper[0], b1, b2, eps, wd, hyper[1], hyper[2], hyper[3]);
+}
+__global__ void adam_ema_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, float* __restrict__ ema, size_t n, float b1, float b2, float eps,
+                                    float wd, const float* __restrict__ hyper, float d, float omd) {
+  adam_body<true>(p, g, m, v, n, hyper[0], b1, b2, eps, wd, hyper[1], hyper[2], hyper[3], ema, d, omd);
 }
 
 }  // namespace
@@ -284,6 +308,42 @@ int srad_launch_adam_dev(float* p, const float* g, float* m, float* v, size_t n,
                          float weight_decay, const float* hyper, hipStream_t stream) {
   SradProfScope prof(stream, SRAD_K_OPTIM, 12.0 * n, 28.0 * n);
   hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, m, v, n, beta1, beta2, eps, weight_decay, hyper);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+// what both EMA launches refuse before anything is enqueued; *omd = (float)(1 - (double)decay), the weight of the new parameter
+static int adam_ema_check(const char* what, const float* p, const float* g, const float* m, const float* v, const float* ema,
+                          size_t n, float decay, float* omd) {
+  SRAD_REQUIRE(ema, "%s: null ema", what);
+  SRAD_REQUIRE(decay >= 0.f && decay < 1.f, "%s: ema_decay must be in [0, 1) (got %g)", what, (double)decay);     // NaN too
+  SRAD_REQUIRE(!srad_ranges_overlap(ema, n, p, n) && !srad_ranges_overlap(ema, n, g, n) && !srad_ranges_overlap(ema, n, m, n) &&
+                   !srad_ranges_overlap(ema, n, v, n),
+               "%s: ema overlaps another buffer", what);
+  *omd = (float)(1.0 - (double)decay);
+  return SRAD_OK;
+}
+
+int srad_launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int step, float grad_scale, float ema_decay, hipStream_t stream) {
+  SRAD_REQUIRE(step >= 1, "adam_ema_step: step counts from 1 (got %d)", step);
+  float omd;
+  SRAD_TRY(adam_ema_check("adam_ema_step", p, g, m, v, ema, n, ema_decay, &omd));
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  SradProfScope prof(stream, SRAD_K_OPTIM, 15.0 * n, 36.0 * n);
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, m, v, ema, n, lr, beta1, beta2, eps,
+                     weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale, ema_decay, omd);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_launch_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, size_t n, float beta1, float beta2,
+                             float eps, float weight_decay, float ema_decay, const float* hyper, hipStream_t stream) {
+  float omd;
+  SRAD_TRY(adam_ema_check("adam_ema_step_dev", p, g, m, v, ema, n, ema_decay, &omd));
+  SradProfScope prof(stream, SRAD_K_OPTIM, 15.0 * n, 36.0 * n);
+  hipLaunchKernelGGL(adam_ema_dev_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, m, v, ema, n, beta1, beta2, eps,
+                     weight_decay, hyper, ema_decay, omd);
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

@@ -268,11 +268,6 @@ int ensemble_check(const char* what, int B, int C, int H, int W, int* tiles_w, i
   return SRAD_OK;
 }
 
-inline bool ranges_overlap(const float* p, size_t np, const float* q, size_t nq) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + nq * sizeof(float) && b < a + np * sizeof(float);
-}
-
 }  // namespace
 
 extern "C" int srad_ensemble_inputs(const float* x, int B, int C, int H, int W, float* out_a, float* out_b, void* stream) {
@@ -281,7 +276,7 @@ extern "C" int srad_ensemble_inputs(const float* x, int B, int C, int H, int W, 
   unsigned blocks;
   SRAD_TRY(ensemble_check("ensemble_inputs", B, C, H, W, &tiles_w, &tiles_h, &blocks));
   const size_t n = (size_t)B * C * H * W;
-  SRAD_REQUIRE(!ranges_overlap(x, n, out_a, 4 * n) && !ranges_overlap(x, n, out_b, 4 * n) && !ranges_overlap(out_a, 4 * n, out_b, 4 * n),
+  SRAD_REQUIRE(!srad_ranges_overlap(x, n, out_a, 4 * n) && !srad_ranges_overlap(x, n, out_b, 4 * n) && !srad_ranges_overlap(out_a, 4 * n, out_b, 4 * n),
                "ensemble_inputs: the outputs overlap the input or each other");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   SradProfScope prof(s, SRAD_K_ENSEMBLE, 0.0, 36.0 * n);
@@ -296,7 +291,7 @@ extern "C" int srad_ensemble_mean(const float* y_a, const float* y_b, int B, int
   unsigned blocks;
   SRAD_TRY(ensemble_check("ensemble_mean", B, C, H, W, &tiles_w, &tiles_h, &blocks));
   const size_t n = (size_t)B * C * H * W;
-  SRAD_REQUIRE(!ranges_overlap(out, n, y_a, 4 * n) && !ranges_overlap(out, n, y_b, 4 * n), "ensemble_mean: out overlaps an input");
+  SRAD_REQUIRE(!srad_ranges_overlap(out, n, y_a, 4 * n) && !srad_ranges_overlap(out, n, y_b, 4 * n), "ensemble_mean: out overlaps an input");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   SradProfScope prof(s, SRAD_K_ENSEMBLE, 7.0 * n, 36.0 * n);
   hipLaunchKernelGGL(ensemble_mean_kernel, dim3(blocks), dim3(256), 0, s, y_a, y_b, out, B * C, H, W, tiles_w, tiles_h);

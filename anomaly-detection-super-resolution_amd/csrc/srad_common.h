@@ -140,6 +140,11 @@ static inline bool srad_path_override(int path) { return g_srad_path_override[pa
 
 static inline size_t srad_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int srad_round_up(int v, int a) { return (v + a - 1) / a * a; }
+// do p[0..np) and q[0..nq) share a byte?  (the __restrict__ kernels refuse aliased buffers before they launch)
+static inline bool srad_ranges_overlap(const float* p, size_t np, const float* q, size_t nq) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + nq * sizeof(float) && b < a + np * sizeof(float);
+}
 
 // ------------------------------------------------------------------------------------------
 // Row-gather GEMM:  Y[m][n] = epi( sum_{tap,c} A(m,tap,c) * W[n][tap*Cp + c] + bias[n] )
@@ -484,6 +489,12 @@ int srad_launch_adam(float* p, const float* g, float* m, float* v, size_t n, flo
 int srad_launch_set4(float* dst, float a, float b, float c, float d, hipStream_t stream);
 int srad_launch_adam_dev(float* p, const float* g, float* m, float* v, size_t n, float beta1, float beta2, float eps,
                          float weight_decay, const float* hyper, hipStream_t stream);
+// the same two steps, each also updating ema = fl(fl(decay * ema) + fl((1 - decay) * p_new)) in the same pass (36 bytes / element);
+// they refuse a null or overlapping ema and a decay outside [0, 1) before the launch
+int srad_launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int step, float grad_scale, float ema_decay, hipStream_t stream);
+int srad_launch_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, size_t n, float beta1, float beta2,
+                             float eps, float weight_decay, float ema_decay, const float* hyper, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
 // misc kernels

@@ -4,7 +4,7 @@ Images of the test split are independent, so with ``--gpus N`` (one process per 
 ``torch.distributed.run``) rank r scores images r::N and only the per-image score rows are gathered
 (SURVEY.md §8(e)); there is no collective on the data path.
 
-    python -m srad_amd.evaluate --run-dir <run> [--checkpoint f.pt] [--dtype bf16]
+    python -m srad_amd.evaluate --run-dir <run> [--checkpoint f.pt | --ema] [--dtype bf16]
 
 Deliberate, documented departures from the reference (SURVEY.md §8 hazards): the model is put in
 eval mode (H1: the reference leaves DRCT's DropPath active, so its scores are not reproducible); the
@@ -61,7 +61,16 @@ def infer_from_run_dir(run_dir: str) -> dict:
 
 
 def resolve_checkpoint(args) -> str:
-    """src/evaluate.py:125-135"""
+    """src/evaluate.py:125-135.  ``--ema``: the averaged weights of the run directory (model_ema_best.pt, then
+    model_ema_latest.pt) and nothing else - no fall-back to the raw weights."""
+    if getattr(args, 'ema', False):
+        names = ('model_ema_best.pt', 'model_ema_latest.pt')
+        for name in names:
+            cand = os.path.join(args.run_dir, 'model', name)
+            if args.run_dir and os.path.isfile(cand):
+                return cand
+        where = os.path.join(args.run_dir, 'model') if args.run_dir else '<--run-dir>/model'
+        raise FileNotFoundError(f"--ema: neither {names[0]} nor {names[1]} under {where} (a run trained with --ema writes them)")
     if args.checkpoint:
         return args.checkpoint
     if args.run_dir:
@@ -626,6 +635,8 @@ def _run(args):
                            map_image_score=args.map_image_score, map_scales=args.map_scales, map_reduce=args.map_reduce,
                            map_source=args.map_source, operating_point=op, pr_metrics=args.pr_metrics,
                            self_ensemble=args.self_ensemble)
+    if getattr(args, 'ema', False) and out:                   # rank 0's result says which weights it is of
+        out['ema'] = True
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -107,6 +107,11 @@ def build_train_opt(args):
     opt.precision = args.dtype
     opt.data_root = data_root
     opt.self_ensemble = bool(getattr(args, 'self_ensemble', False))
+    if getattr(args, 'ema_decay', None) is not None:
+        opt.ema_decay = float(args.ema_decay)
+    if getattr(args, 'ema', False):                              # only then: a run without it writes today's config.txt
+        opt.ema = True
+        opt.ema_decay = float(getattr(opt, 'ema_decay', 0.999))  # the DRN option set has no such field
     return opt
 
 

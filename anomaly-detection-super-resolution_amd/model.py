@@ -100,12 +100,18 @@ class Model(nn.Module):
 
     def save(self, path, is_best=False):
         """model/model_latest.pt (+ model_best.pt) = raw state_dict; dual models as a LIST of
-        state_dicts in dual_model_{latest,best}.pt (src/model.py:123-147)."""
+        state_dicts in dual_model_{latest,best}.pt (src/model.py:123-147).  A network that keeps a weight average also
+        gets model/model_ema_latest.pt (+ model_ema_best.pt) = ``ema_state_dict()``, loadable like any checkpoint."""
         target = self.get_model()
         os.makedirs(os.path.join(path, 'model'), exist_ok=True)
         torch.save(target.state_dict(), os.path.join(path, 'model', 'model_latest.pt'))
         if is_best:
             torch.save(target.state_dict(), os.path.join(path, 'model', 'model_best.pt'))
+        if getattr(target, 'flat_ema', None) is not None:      # a run with a weight average (--ema): the averaged network too
+            ema = target.ema_state_dict()
+            torch.save(ema, os.path.join(path, 'model', 'model_ema_latest.pt'))
+            if is_best:
+                torch.save(ema, os.path.join(path, 'model', 'model_ema_best.pt'))
         if self.dual_model:
             dual_models = [self.get_dual_model(i).state_dict() for i in range(len(self.dual_models))]
             torch.save(dual_models, os.path.join(path, 'model', 'dual_model_latest.pt'))

@@ -6,6 +6,7 @@ here - owning device memory for parameters under the reference's state-dict name
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Dict, List, Optional
@@ -252,6 +253,8 @@ class _EngineModule(nn.Module):
         L.check(self._fn("train_bind")(h, tp, tb), "train_bind")
         self.flat_params, self.flat_grads, self._grad_views = flat, grad, views
         self._flat_homes = homes
+        if getattr(self, "flat_ema", None) is not None:      # re-homed (the same layout): the average moves along
+            self.flat_ema = self.flat_ema.to(dev)
         self._synced_version = None
         self._train_ws = {}
         self._anchor = torch.zeros(1, device=dev, requires_grad=True)
@@ -263,6 +266,56 @@ class _EngineModule(nn.Module):
         (the fused Adam kernel, a replayed hipGraph)."""
         self._synced_version = None
         self._tags = None
+
+    # -- weight EMA (DESIGN.md "Weight EMA"; kept by the fused Adam kernel, train.FusedAdam(ema_decay=...)) ------------
+    def enable_ema(self):
+        """Allocate ``flat_ema``, the exponential moving average of the flat parameters, as a copy of ``flat_params`` as they
+        are now (BasicSR's ``model_ema(0)``: the average starts as the weights).  Call after ``enable_training()``; a second
+        call keeps the average it finds."""
+        if getattr(self, "flat_params", None) is None:
+            raise RuntimeError(f"{type(self).__name__}: call enable_training() before enable_ema()")
+        if getattr(self, "flat_ema", None) is None:
+            self._flat_state()                               # a parameter whose storage was replaced goes back to its slot first
+            self.flat_ema = self.flat_params.detach().clone()
+            self._ema_active = False
+        return self
+
+    def _refuse_under_ema(self, what: str) -> None:
+        if getattr(self, "_ema_active", False):
+            raise RuntimeError(f"{type(self).__name__}: {what} inside ema_weights() - the engine holds the averaged weights; "
+                               "leave the context first")
+
+    def ema_state_dict(self):
+        """``state_dict()`` with every engine parameter replaced by a clone of its slice of ``flat_ema``; buffers and any other
+        entry unchanged, same keys in the same order.  Loadable like any checkpoint."""
+        if getattr(self, "flat_ema", None) is None:
+            raise RuntimeError(f"{type(self).__name__}: no weight average - call enable_ema() (FusedAdam(ema_decay=...)) first")
+        sd = self.state_dict()
+        off = C.c_int64()
+        for i, (name, numel) in enumerate(self._engine_params):
+            L.check(self._fn("train_param_offset")(self._handle, i, C.byref(off)), "train_param_offset")
+            if name in sd:
+                sd[name] = self.flat_ema[off.value:off.value + numel].view(sd[name].shape).clone()
+        return sd
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context every inference forward - eager or graph replay, ``Model.forward_x8`` included - runs on the
+        averaged weights; after it the training weights are back bit for bit.  Nothing is copied: the engine's one-launch
+        re-pack (``sync_params``) reads ``flat_ema`` instead of ``flat_params`` while the context is active, and a re-pack is
+        forced on entry and on exit.  A training-mode forward, a backward or an optimizer step inside the context is a
+        RuntimeError.  The graphed training steps re-pack from ``flat_params`` at the head of every replay, so they need
+        nothing else after the context has been left."""
+        if getattr(self, "flat_ema", None) is None:
+            raise RuntimeError(f"{type(self).__name__}: no weight average - call enable_ema() (FusedAdam(ema_decay=...)) first")
+        self._refuse_under_ema("a nested ema_weights()")
+        self._ema_active = True
+        self.mark_params_dirty()
+        try:
+            yield self
+        finally:
+            self._ema_active = False
+            self.mark_params_dirty()
 
     def _flat_state(self):
         """Everything that can change the packed weights behind the engine's back.  After ``enable_training`` every
@@ -284,7 +337,8 @@ class _EngineModule(nn.Module):
             raise RuntimeError(f"{type(self).__name__}: call enable_training() before a training-mode forward")
         ver = self._flat_state()
         if self._synced_version != ver:
-            L.check(self._fn("sync_params")(self._handle, L.dptr(self.flat_params), L.current_stream_ptr()), "sync_params")
+            src = self.flat_ema if getattr(self, "_ema_active", False) else self.flat_params     # ema_weights(): pack the average
+            L.check(self._fn("sync_params")(self._handle, L.dptr(src), L.current_stream_ptr()), "sync_params")
             self._synced_version = self._flat_state()      # re-homing above does not repeat
             self._tags = None
 
@@ -456,6 +510,7 @@ class DRCT(_EngineModule):
     def _forward_train(self, x: torch.Tensor) -> torch.Tensor:
         dev = x.device
         B, _, H, W = x.shape
+        self._refuse_under_ema("a training-mode forward")
         self._sync_flat()
         key = (B, H, W)
         wp, wb = self._train_workspace(B, H, W, dev)
@@ -474,6 +529,7 @@ class DRCT(_EngineModule):
         return y
 
     def _backward(self, dy: torch.Tensor, need_dx: bool) -> Optional[torch.Tensor]:
+        self._refuse_under_ema("a backward")
         B, H, W = self._train_shape
         if self._grad_views[0][0].grad is None:          # optimizer.zero_grad(set_to_none=True) dropped the views
             self.zero_grad()
@@ -580,6 +636,7 @@ class DRN(_EngineModule):
     def _forward_train(self, x: torch.Tensor) -> List[torch.Tensor]:
         dev = x.device
         B, Cc, H, W = x.shape
+        self._refuse_under_ema("a training-mode forward")
         self._sync_flat()
         wp, wb = self._train_workspace(B, H, W, dev)
         outs = [torch.empty(B, Cc, H * 2 ** i, W * 2 ** i, dtype=torch.float32, device=dev) for i in range(self.phase + 1)]
@@ -591,6 +648,7 @@ class DRN(_EngineModule):
 
     def _backward(self, dys) -> None:
         """dys: one gradient (or None) per output of the last training forward."""
+        self._refuse_under_ema("a backward")
         B, H, W = self._train_shape
         if self._grad_views[0][0].grad is None:
             self.zero_grad()

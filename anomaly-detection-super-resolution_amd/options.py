@@ -199,8 +199,26 @@ def parse_train_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument('--self-ensemble', action='store_true', default=False,
                    help="use self-ensemble method for test: the validation of a run (Trainer.test) and --test-only average the "
                         "model's outputs for the 8 flips and transposes of each input")
+    p.add_argument('--ema', action='store_true', default=False,
+                   help="keep an exponential moving average of the weights in the fused Adam step (BasicSR's model_ema): the "
+                        "validation runs on it and model/model_ema_{latest,best}.pt are written beside the raw weights")
+    p.add_argument('--ema-decay', type=_ema_decay, default=None, metavar='D',
+                   help="decay of --ema, in [0, 1); default: the option set's ema_decay (0.999)")
     _with_config(p, pre_args)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.ema_decay is not None:                            # a value from a config file gets the command line's check
+        try:
+            args.ema_decay = _ema_decay(str(args.ema_decay))
+        except (argparse.ArgumentTypeError, ValueError) as e:
+            p.error(f"argument --ema-decay: {e}")
+    return args
+
+
+def _ema_decay(text: str) -> float:
+    v = float(text)
+    if not 0.0 <= v < 1.0:                                    # NaN too
+        raise argparse.ArgumentTypeError(f"{text} is not a decay in [0, 1)")
+    return v
 
 
 def _nonnegative_float(text: str) -> float:
@@ -315,8 +333,13 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
     p.add_argument('--self-ensemble', action='store_true', default=False,
                    help="use self-ensemble method for test: every SR image is the mean of the model's outputs for the 8 flips "
                         "and transposes of its input, each transform undone (8 forwards per image)")
+    p.add_argument('--ema', action='store_true', default=False,
+                   help="evaluate the averaged weights of a run trained with --ema: --run-dir's model/model_ema_best.pt, else "
+                        "model_ema_latest.pt (no fall-back to the raw weights; excludes --checkpoint)")
     _with_config(p, pre_args)
     args = p.parse_args(argv)
+    if args.ema and args.checkpoint:
+        p.error("--ema and --checkpoint exclude each other (an explicit file is already a choice)")
     if args.threshold is not None and args.threshold_fpr is not None:
         p.error("--threshold and --threshold-fpr exclude each other (a given threshold or a calibrated one)")
     if isinstance(args.map_scales, (list, tuple)):            # a list from a config file gets the command line's check

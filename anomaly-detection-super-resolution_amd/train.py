@@ -20,12 +20,25 @@ from . import _lib as L
 
 class FusedAdam:
     """torch.optim.Adam arithmetic (src/trainer.py:49-59: betas (0.9, 0.999), eps 1e-8, L2 weight decay)
-    as ONE kernel over the model's flat parameter buffer (C ABI ``srad_adam_step``)."""
+    as ONE kernel over the model's flat parameter buffer (C ABI ``srad_adam_step``).
 
-    def __init__(self, model, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    ``ema_decay`` (a float in [0, 1); default None = no average): the same launch also keeps the exponential moving average of
+    the weights in ``model.flat_ema`` (C ABI ``srad_adam_ema_step``; DESIGN.md "Weight EMA"): after every step
+    ``ema = decay * ema + (1 - decay) * params``, starting from the weights at construction.  The decay is a launch constant, so
+    the captured training graphs need nothing new per replay."""
+
+    def __init__(self, model, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 ema_decay: Optional[float] = None):
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.0 <= ema_decay < 1.0:                 # NaN too
+                raise ValueError(f"ema_decay must be in [0, 1) (got {ema_decay})")
         if getattr(model, "flat_params", None) is None:
             model.enable_training()
         self.model = model
+        self.ema_decay = ema_decay
+        if ema_decay is not None:
+            model.enable_ema()
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
         self.exp_avg = torch.zeros_like(model.flat_params)
         self.exp_avg_sq = torch.zeros_like(model.flat_params)
@@ -37,8 +50,16 @@ class FusedAdam:
 
     def step(self, grad_scale: float = 1.0) -> None:
         m = self.model
+        m._refuse_under_ema("an optimizer step")
         self.step_count += 1
         lr = float(self.param_groups[0]["lr"])
+        if self.ema_decay is not None:
+            L.check(L.lib().srad_adam_ema_step(L.dptr(m.flat_params), L.dptr(m.flat_grads), L.dptr(self.exp_avg),
+                                               L.dptr(self.exp_avg_sq), L.dptr(m.flat_ema), m.flat_params.numel(), lr,
+                                               self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
+                                               grad_scale, self.ema_decay, L.current_stream_ptr()), "adam_ema_step")
+            m.mark_params_dirty()
+            return
         L.check(L.lib().srad_adam_step(L.dptr(m.flat_params), L.dptr(m.flat_grads), L.dptr(self.exp_avg),
                                        L.dptr(self.exp_avg_sq), m.flat_params.numel(), lr, self.betas[0], self.betas[1],
                                        self.eps, self.weight_decay, self.step_count, grad_scale,
@@ -55,6 +76,14 @@ class FusedAdam:
         """``step()`` with the per-step scalars read from ``dev_hyper`` (4 floats on the GPU, see ``hyper()``): the launch
         carries no step-dependent argument, so it can sit inside a captured hipGraph.  The caller bumps ``step_count``."""
         m = self.model
+        m._refuse_under_ema("an optimizer step")
+        if self.ema_decay is not None:
+            L.check(L.lib().srad_adam_ema_step_dev(L.dptr(m.flat_params), L.dptr(m.flat_grads), L.dptr(self.exp_avg),
+                                                   L.dptr(self.exp_avg_sq), L.dptr(m.flat_ema), m.flat_params.numel(),
+                                                   self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_decay,
+                                                   L.dptr(dev_hyper), L.current_stream_ptr()), "adam_ema_step_dev")
+            m.mark_params_dirty()
+            return
         L.check(L.lib().srad_adam_step_dev(L.dptr(m.flat_params), L.dptr(m.flat_grads), L.dptr(self.exp_avg),
                                            L.dptr(self.exp_avg_sq), m.flat_params.numel(), self.betas[0], self.betas[1],
                                            self.eps, self.weight_decay, L.dptr(dev_hyper), L.current_stream_ptr()),
@@ -62,14 +91,20 @@ class FusedAdam:
         m.mark_params_dirty()
 
     def state_dict(self):
-        return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                "lr": self.param_groups[0]["lr"]}
+        sd = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
+              "lr": self.param_groups[0]["lr"]}
+        if self.ema_decay is not None:
+            sd["ema"], sd["ema_decay"] = self.model.flat_ema, self.ema_decay
+        return sd
 
     def load_state_dict(self, sd):
         self.step_count = int(sd["step"])
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.param_groups[0]["lr"] = float(sd["lr"])
+        if self.ema_decay is not None and "ema" in sd:     # a state without the key leaves the average alone
+            self.model.flat_ema.copy_(sd["ema"])
+            self.model.mark_params_dirty()
 
 
 class TensorAdam:

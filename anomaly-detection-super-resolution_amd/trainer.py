@@ -18,6 +18,7 @@ Differences, all deliberate:
     and is read every ``print_every`` batches."""
 from __future__ import annotations
 
+import contextlib
 import time
 from decimal import Decimal
 from typing import List
@@ -59,9 +60,10 @@ def quantize(img, rgb_range):
 
 
 def make_optimizer(opt, my_model) -> FusedAdam:
-    """src/trainer.py:49-59."""
+    """src/trainer.py:49-59.  ``opt.ema``: the same kernel also keeps the weight average (decay ``opt.ema_decay``)."""
+    ema = dict(ema_decay=float(getattr(opt, "ema_decay", 0.999))) if getattr(opt, "ema", False) else {}
     return FusedAdam(my_model.get_model() if hasattr(my_model, "get_model") else my_model, lr=opt.lr,
-                     betas=(opt.beta1, opt.beta2), eps=opt.epsilon, weight_decay=opt.weight_decay)
+                     betas=(opt.beta1, opt.beta2), eps=opt.epsilon, weight_decay=opt.weight_decay, **ema)
 
 
 def make_dual_optimizer(opt, dual_models) -> List[TensorAdam]:
@@ -237,7 +239,9 @@ class Trainer():
         watch = timer()
         n = len(self.loader_test)
         table = self.ckp.log
-        with torch.no_grad():
+        # a run that keeps a weight average validates on it (BasicSR validates net_g_ema) and says so in the result line
+        ema = getattr(self.net, "flat_ema", None) is not None
+        with torch.no_grad(), (self.net.ema_weights() if ema else contextlib.nullcontext()):
             for si, s in enumerate([max(self.scale)]):
                 psnr_sum, ssim_sum = self._validate(s)
                 # the reference stores PSNR at column si and SSIM at column 2 si + 1 and reads PSNR back from column 2 si
@@ -246,7 +250,7 @@ class Trainer():
                 top, at = table.max(0)
                 self._log('[{} x{}]\tPSNR: {:.2f} (Best: {:.2f} @epoch {})\tSSIM: {:.4f} (Best: {:.4f} @epoch {})'.format(
                     self.opt.data_test, s, table[-1, 2 * si], top[2 * si], at[2 * si] + 1,
-                    table[-1, 2 * si + 1], top[2 * si + 1], at[2 * si + 1] + 1))
+                    table[-1, 2 * si + 1], top[2 * si + 1], at[2 * si + 1] + 1) + (' [EMA]' if ema else ''))
         self._log('Total time: {:.2f}s\n'.format(watch.toc()), refresh=True)
         self.model.train()
 

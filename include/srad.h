@@ -114,6 +114,17 @@ int srad_adam_step(float* params, const float* grads, float* exp_avg, float* exp
  * grad_scale] (4 floats), so a hipGraph capturing a whole training step can be replayed for every step */
 int srad_adam_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
                        float beta2, float eps, float weight_decay, const float* dev_hyper, void* stream);
+/* Both steps with the exponential moving average of the weights kept by the same launch (BasicSR's model_ema: no warm-up, no
+ * bias correction).  params, exp_avg and exp_avg_sq end with the bits of the plain step; then, with p' the fp32 parameter
+ * just stored and omd = (float)(1.0 - (double)ema_decay), ema[i] = fl(fl(ema_decay * ema[i]) + fl(omd * p')): three separately
+ * rounded IEEE fp32 operations, no fused multiply-add.  Refused before anything is launched: a null ema, ema_decay outside
+ * [0, 1) or NaN, ema overlapping any of the four other buffers, and what the plain steps refuse. */
+int srad_adam_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_decay,
+                       void* stream);
+int srad_adam_ema_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                           float beta1, float beta2, float eps, float weight_decay, float ema_decay, const float* dev_hyper,
+                           void* stream);
 /* dst[0..3] = (a, b, c, d), passed by value through a kernel launch (no host copy, no synchronisation) */
 int srad_set4(float* dst, float a, float b, float c, float d, void* stream);
 
