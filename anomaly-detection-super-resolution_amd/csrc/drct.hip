@@ -67,7 +67,22 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
       const bool x3 = prec == SRAD_PREC_BF16X3;
       const bool mlp_fused = h->fuse_mlp && srad_mlp_block_supported(prec, T, d, sw.hidden, no);
       __bf16* const attn_h = reinterpret_cast<__bf16*>(w.attn);
-      if (h->fuse_mlp && srad_qkv_attn_supported(prec, c.window_size, H, W, d, sw.heads)) {
+      // the whole block as ONE launch (kernels_fused_block.hip) where the windows' quarters fit the chip in one wave of
+      // workgroups and the block shape measured a win over the pair below; this path has no saves and no DropPath
+      if (mlp_fused && srad_swin_block_supported(prec, c.window_size, B, H, W, d, sw.heads, sw.hidden, no) &&
+          srad_swin_block_wins(d, sw.heads, sw.hidden, no) && !srad_path_override(SRAD_PATH_BLOCK_TWO_LAUNCHES)) {
+        const QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);
+        const MlpBlockParams q = drct_mlp_block_params(h, sw, k, attn_h, cur, nxt, T);
+        SwinBlockParams b{};
+        b.x = a.x; b.ldx = a.ldx; b.B = B; b.H = H; b.W = W; b.shift = a.shift; b.d = d; b.heads = sw.heads; b.m = q.m; b.no = q.no;
+        b.ln1_g = a.ln_g; b.ln1_b = a.ln_b; b.w_qkv = a.w_qkv; b.b_qkv = a.b_qkv; b.table = a.table;
+        b.w_proj = q.w_proj; b.w_fc1 = q.w_fc1; b.w_fc2 = q.w_fc2; b.w_adj = q.w_adj;
+        b.b_proj = q.b_proj; b.b_fc1 = q.b_fc1; b.b_fc2 = q.b_fc2; b.b_adj = q.b_adj; b.ln2_g = q.ln_g; b.ln2_b = q.ln_b;
+        b.act = q.act; b.slope = q.slope; b.alpha = q.alpha; b.R = q.R; b.ldr = q.ldr; b.Y = q.Y; b.ldy = q.ldy; b.yoff = q.yoff;
+        SRAD_TRY(srad_launch_swin_block(b, s));
+        continue;
+      }
+      if (h->fuse_mlp &&srad_qkv_attn_supported(prec, c.window_size, H, W, d, sw.heads)) {
         // norm1 + qkv + shifted-window attention of one (window, head) per workgroup, one launch
         // (drct.py:477-504, 278-299)
         QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);

@@ -1,0 +1,625 @@
+// kernels_fused_block.hip - a whole DRCT Swin block + the RDG's adjust conv as ONE bf16 launch (window 8, inference):
+//
+//   xn   = LayerNorm1(x[window tokens]);  q|k|v = xn . Wqkv^T + b              (src/drct.py:477, 278)
+//   a    = softmax(q*scale k^T + rel-pos bias + shift mask) v                   (src/drct.py:281-299)
+//   x1   = x + proj(a) + b_proj;  x2 = x1 + fc2(GELU(fc1(LayerNorm2(x1))))      (src/drct.py:300, 509-510, 184-190)
+//   out  = act(adjust(x2) + b_adj) * alpha (+ R)                                (src/drct.py:389-396)
+//
+// i.e. qkv_attn_kernel followed by mlp_block_kernel<16> without the launch boundary and without the attention output's trip
+// through HBM.  A workgroup owns a QUARTER of a window: its 16 query tokens (window rows 2q, 2q + 1) are the 16-row tile of
+// the MLP half, so 64 windows x 4 quarters fill 256 CUs.  Each workgroup gathers and normalises all 64 rows of its window and
+// projects k and v of every head for them (redundantly with its three siblings - on a matrix pipe the two-kernel form leaves
+// 80-95 % idle); q is projected for its own row tile only.  A wave then owns one head: scores, bias + mask, softmax and P.V of
+// 16 queries x 64 keys stay inside the wave (no barrier between them), and the result lands as the bf16 A tile of the proj
+// GEMM in LDS.  The weights of all five matrices stream through ONE sequence of register-set stages (three ahead, as in the
+// two kernels), so the first MLP stages are in flight under the attention.  Head dims whose k | v of all heads do not fit
+// next to the window tile (d = 276, 308) run the heads in two groups.
+//
+// Write hazard: adjust_k (k < 4) writes columns [d, d + no) of its 16 rows into the same dense buffer whose columns [0, d)
+// other workgroups of this launch still read.  d % 4 == 0, every access is a float4 on a 4-column boundary, so no access
+// straddles the two ranges.  adjust5 writes the other dense buffer.
+//
+// Same rules as kernels_fused.hip / kernels_fused_attn.hip: unconditional loads on clamped addresses, activations ahead of
+// weights, padding zeroed by selects, stage geometry in template parameters (no runtime-indexed register arrays: no scratch),
+// LDS row strides of 2 mod 4 sixteen-byte units.
+#include "srad_common.h"
+#include <type_traits>
+
+namespace {
+
+template <int B, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (B < N) {
+    f(std::integral_constant<int, B>{});
+    static_for<B + 1, N>(f);
+  }
+}
+
+constexpr int B_LDA = 400;         // LDS row stride of the <=384-wide bf16 activation tile (as F_LDA in kernels_fused.hip)
+constexpr int B_LDH = 528;         // ... of the <=512-wide hidden tile
+constexpr int B_SC = 128;          // output columns per weight stage
+constexpr int B_NV = 2560;         // floats of the MLP half's staged vectors
+constexpr int B_LDP = 80;          // probability tile row stride
+
+// erf by Abramowitz-Stegun 7.1.26, as in mlp_block_kernel
+__device__ __forceinline__ float blk_gelu(float x) {
+  const float z = fabsf(x) * 0.70710678118654752440f;
+  const float t = 1.0f / (1.0f + 0.3275911f * z);
+  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+  const float erfa = 1.0f - poly * __expf(-z * z);
+  return 0.5f * x * (1.0f + (x < 0.f ? -erfa : erfa));
+}
+
+// Stage counts and the LDS layout of one instance.  HDT = ceil(head_dim / 16), KC = ceil(d / 32), NG = head groups.
+template <int HDT, int KC, int HEADS, int NG>
+struct BlkGeo {
+  static_assert(HEADS % NG == 0, "head groups must divide the heads");
+  static constexpr int HG = HEADS / NG;                   // heads per group = waves that run an attention
+  static constexpr int HDP = 16 * HDT, HDP32 = (HDP + 31) & ~31, HS = HDP32 + 16, LDX = KC * 32 + 16;
+  static constexpr int NKVT = HG * 2 * HDT, NQT = HG * HDT;        // 16-column tiles of k | v (x 4 row tiles) and of q (x 1)
+  static constexpr int NKVS = (NKVT + 7) / 8, NQS = (NQT + 7) / 8; // column stages: one tile per wave
+  static constexpr int SPG = NKVS + NQS;                           // weight stages per head group: a stage spans all KC k chunks
+  static constexpr int QS = NG * SPG;                              // ... of the attention half
+  // bytes
+  static constexpr int XN_B = 64 * LDX * 2, KV_B = 2 * HG * 64 * HS * 2, Q_B = HG * 16 * HS * 2, PS_B = HG * 16 * B_LDP * 2;
+  static constexpr int A1_B = 16 * B_LDA * 2, HS_B = 16 * B_LDH * 2;
+  // one group: the normalised window is dead once q | k | v exist, so the probabilities (and the attention tile, if both fit)
+  // overlay it; two groups: the window is read again by the second group
+  static constexpr bool OVER = NG == 1, A1_OVER = OVER && PS_B + A1_B <= XN_B;
+  static constexpr int OFF_KV = XN_B, OFF_Q = OFF_KV + KV_B;
+  static constexpr int OFF_A1 = A1_OVER ? PS_B : OFF_Q + Q_B;
+  static constexpr int OFF_PS = OVER ? 0 : OFF_A1 + A1_B;
+  static constexpr int OFF_VEC = (A1_OVER ? OFF_Q + Q_B : (OVER ? OFF_A1 + A1_B : OFF_PS + PS_B));
+  static constexpr int NBIAS = HEADS * 3 * HDP, NTBL = 225 * HEADS, NTBLP = (NTBL + 3) & ~3;
+  // floats: MLP vectors | gamma1 320 | beta1 320 | qkv bias | table | LayerNorm2 partial sums [16][8][2] | softmax sums [HG][16]
+  static constexpr int NFLT = B_NV + 640 + NBIAS + NTBLP + 256 + 128;
+  static constexpr int LDS = OFF_VEC + NFLT * 4 + 64 * 4;          // + window geometry words [64]
+  static_assert(KV_B >= HS_B, "the hidden tile overlays k | v");
+  static_assert(LDS <= 160 * 1024, "swin_block: LDS budget");
+};
+
+// GD .. KCM: the stage geometry of the MLP half, as mlp_block_kernel's (KCD == KC)
+template <int HDT, int KC, int HEADS, int NG, int GD, int KGD, int GM, int KGM, int GN, int KCM>
+__global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p) {
+  using G = BlkGeo<HDT, KC, HEADS, NG>;
+  constexpr int KCD = KC;
+  static_assert(KGD == (KCD + 7) / 8 && KGM == (KCM + 7) / 8, "k groups are 8 chunks wide");
+  constexpr int HG = G::HG, HDP = G::HDP, HDP32 = G::HDP32, HS = G::HS, LDX = G::LDX;
+  constexpr int RC = KC > 8 ? KC : 8;                                    // fragment registers per weight set: a W_qkv stage holds all
+                                                                         // KC (<= 10) chunks of its tile, an MLP stage up to 8
+  constexpr int NKVS = G::NKVS, SPG = G::SPG, QS = G::QS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* XN = reinterpret_cast<__bf16*>(smem);                          // [64][LDX] LayerNorm1(window)
+  __bf16* KV = reinterpret_cast<__bf16*>(smem + G::OFF_KV);              // [k | v][HG][64][HS]
+  __bf16* Qb = reinterpret_cast<__bf16*>(smem + G::OFF_Q);               // [HG][16][HS] (scaled)
+  __bf16* A1 = reinterpret_cast<__bf16*>(smem + G::OFF_A1);              // [16][B_LDA] attention output -> LN2(x1) -> x2
+  __bf16* Ps = reinterpret_cast<__bf16*>(smem + G::OFF_PS);              // [HG][16][B_LDP] probabilities
+  __bf16* Hs = KV;                                                       // [16][B_LDH] GELU(fc1): k | v are dead by then
+  float* vec = reinterpret_cast<float*>(smem + G::OFF_VEC);
+  float* v_g1 = vec + B_NV;                                              // [320] gamma1
+  float* v_b1n = v_g1 + 320;                                             // [320] beta1
+  float* v_bias = v_b1n + 320;                                           // [HEADS][3][HDP] q|k|v bias (0 in padding)
+  float* tbl = v_bias + G::NBIAS;                                        // [225][HEADS] relative position bias
+  float* red = tbl + G::NTBLP;                                           // [16][8][2] LayerNorm2 partial sums
+  float* lsum = red + 256;                                               // [HG][16] softmax denominators
+  int* inf = reinterpret_cast<int*>(lsum + 128);                         // [64] (region << 16) | (py << 8) | px
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+  const int d = p.d, m = p.m, no = p.no, hd = d / HEADS;
+  const float scale = rsqrtf((float)hd);
+  // grid = (windows, 4 quarters): a window's four workgroups have linear ids that differ by the window count, a multiple of 8
+  // where the XCD-affine mapping applies, so they share an XCD (and its L2 copy of the window's rows and of the weights)
+  const int quarter = blockIdx.y;
+  int win = blockIdx.x;
+  if ((gridDim.x & 7) == 0 && !p.no_xcd_map) win = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const int ws = 8, nWx = p.W / ws, nW = (p.H / ws) * nWx;
+  const int b = win / nW, widx = win - b * nW;
+  const int wy = widx / nWx, wx = widx - wy * nWx;
+  auto token_of = [&](int t, int& info) {
+    int token;
+    srad_window_token_info(p.H, p.W, ws, p.shift, b, wy, wx, t >> 3, t & 7, token, info);
+    return token;
+  };
+  const int xrow = tid >> 3, col4 = tid & 7;
+  int info;
+  const int my_tok = token_of(xrow, info);                        // the window row this thread gathers
+  const int row_tok = token_of(16 * quarter + fr, info);          // the tile row this lane owns in the MLP half
+  if (tid < 64) {
+    token_of(tid, info);
+    inf[tid] = info;
+  }
+
+  constexpr int n_proj = GD * KGD, n_fc1 = GM * KGD, n_fc2 = GD * KGM, n_adj = GN * KGD;
+  constexpr int n_mlp = n_proj + n_fc1 + n_fc2 + n_adj;
+  constexpr int n_all = QS + n_mlp;
+  float* const v_bp = vec; float* const v_bf1 = vec + 384; float* const v_bf2 = vec + 896; float* const v_ba = vec + 1280;
+  float* const v_g2 = vec + 1664; float* const v_b2n = vec + 2048;
+
+  struct StageGeo { int ph, g, kg, nch, kc; };
+  auto geo = [](int s) constexpr -> StageGeo {
+    if (s > n_mlp - 1) s = n_mlp - 1;
+    int ph = 0, kgs = 1, kc = 1;
+    if (s < n_proj) { ph = 0; kgs = KGD; kc = KCD; }
+    else if ((s -= n_proj) < n_fc1) { ph = 1; kgs = KGD; kc = KCD; }
+    else if ((s -= n_fc1) < n_fc2) { ph = 2; kgs = KGM; kc = KCM; }
+    else { s -= n_fc2; ph = 3; kgs = KGD; kc = KCD; }
+    const int g = s / kgs, kg = s - g * kgs;
+    const int nch = kc - kg * 8 < 8 ? kc - kg * 8 : 8;
+    return StageGeo{ph, g, kg, nch, kc};
+  };
+  // the 16-column tile of q | k | v this wave owns in column stage cs of head group gr: head (within the group), slice
+  // (0 q, 1 k, 2 v), column tile of the slice, liveness
+  struct QTile { int hl, which, ct; bool live; };
+  auto qtile = [&](int cs) -> QTile {
+    if (cs < NKVS) {
+      const int j = cs * 8 + wave_s, hl = j / (2 * HDT), r = j - hl * 2 * HDT;
+      return QTile{hl, 1 + r / HDT, r % HDT, j < G::NKVT};
+    }
+    const int j = (cs - NKVS) * 8 + wave_s, hl = j / HDT;
+    return QTile{hl, 0, j - hl * HDT, j < G::NQT};
+  };
+  // ---- ONE weight stream for the whole block: stages [0, QS) are the per-head fragment tiles of W_qkv (a wave owns 16 virtual
+  //      columns of a stage and nobody else reads their weights), stages [QS, n_all) those of proj | fc1 | fc2 | adjust exactly
+  //      as in mlp_block_kernel.  Straight from global memory into MFMA operand registers, three stages ahead. ----
+  constexpr int NSETS = 3;
+  u32x4 w_reg[NSETS][RC];
+  auto load_w = [&](auto S, u32x4 (&reg)[RC]) __attribute__((always_inline)) {
+    constexpr int u = decltype(S)::value < n_all - 1 ? decltype(S)::value : n_all - 1;
+    if constexpr (u < QS) {
+      constexpr int gr = u / SPG, cs = u - gr * SPG;
+      const QTile t = qtile(cs);
+      const char* const Wq = reinterpret_cast<const char*>(p.w_qkv);
+      const int gt = ((gr * HG + t.hl) * 3 + t.which) * HDT + t.ct;           // tile row of the pack: [head][q | k | v][HDT]
+      const char* base = t.live ? Wq + (size_t)gt * KC * 1024 + fr * 64 + fq * 16 : Wq;
+      const int step = t.live ? 1024 : 0;
+#pragma unroll
+      for (int cc = 0; cc < KC; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + cc * step);
+    } else {
+      constexpr StageGeo sg = geo(u - QS);
+      const char* w = (const char*)(sg.ph == 0 ? p.w_proj : (sg.ph == 1 ? p.w_fc1 : (sg.ph == 2 ? p.w_fc2 : p.w_adj)));
+      const int nreal = sg.ph == 0 ? d : (sg.ph == 1 ? m : (sg.ph == 2 ? d : no));
+      const bool live = (sg.g * 8 + wave_s) * 16 < nreal;
+      const char* base = live ? w + ((size_t)(sg.g * 8 + wave) * sg.kc + sg.kg * 8) * 1024 + fr * 64 + fq * 16 : w;
+      const int step = live ? 1024 : 0;
+#pragma unroll
+      for (int cc = 0; cc < sg.nch; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + cc * step);
+    }
+  };
+
+  // ---- loads in the order their data is needed: the window's rows, the tile's shortcut quads, the vectors, the first stage ----
+  f32x4 a_reg[KC];
+  {
+    const char* src = reinterpret_cast<const char*>(p.x) + (size_t)my_tok * p.ldx * 4;
+#pragma unroll
+    for (int j = 0; j < KC; ++j) a_reg[j] = *reinterpret_cast<const f32x4*>(src + (unsigned)min(j * 32 + col4 * 4, d - 4) * 4u);
+  }
+  // accumulator layout of this lane in the MLP half: token row fr of the tile, columns 128 g + 16 wave + 4 fq + (0..3)
+  f32x4 x1[GD];
+#pragma unroll
+  for (int g = 0; g < GD; ++g)
+    x1[g] = *reinterpret_cast<const f32x4*>(p.x + (size_t)row_tok * p.ldx + min(B_SC * g + 16 * wave + 4 * fq, d - 4));
+  typedef const float __attribute__((address_space(1)))* gfloat_p;
+  float g1q, b1q, biasq[2], tblq[3];
+  {
+    const int e = min(tid, d - 1);
+    g1q = ((gfloat_p)p.ln1_g)[e]; b1q = ((gfloat_p)p.ln1_b)[e];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int idx = min(tid + 512 * q, G::NBIAS - 1);
+      const int slice = idx / HDP, c = idx - slice * HDP, hh = slice / 3, which = slice - 3 * hh;
+      biasq[q] = ((gfloat_p)p.b_qkv)[which * d + hh * hd + min(c, hd - 1)];
+      if (c >= hd) biasq[q] = 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) tblq[q] = ((gfloat_p)p.table)[min(tid + 512 * q, G::NTBL - 1)];
+  }
+  // MLP vectors: [0,384) b_proj, [384,896) b_fc1, [896,1280) b_fc2, [1280,1664) b_adj, [1664,2048) gamma2, [2048,2432) beta2
+  f32x4 vq[2];
+  int v_off = 0, v_len = 0;
+  {
+    const float* src = p.b_proj; int n = d;
+    if (wave_s == 1) { src = p.b_fc1; n = m; v_off = 384; }
+    else if (wave_s == 2) { src = p.b_fc2; n = d; v_off = 896; }
+    else if (wave_s == 3) { src = p.b_adj; n = no; v_off = 1280; }
+    else if (wave_s == 4) { src = p.ln2_g; n = d; v_off = 1664; }
+    else if (wave_s == 5) { src = p.ln2_b; n = d; v_off = 2048; }
+    v_len = wave_s == 1 ? 512 : 384;
+    vq[0] = *reinterpret_cast<const f32x4*>(src + min(4 * lane, n - 4));
+    vq[1] = *reinterpret_cast<const f32x4*>(src + min(256 + 4 * lane, n - 4));
+  }
+  load_w(std::integral_constant<int, 0>{}, w_reg[0]);
+  if (tid < 320) { v_g1[tid] = tid < d ? g1q : 0.f; v_b1n[tid] = tid < d ? b1q : 0.f; }
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    if (tid + 512 * q < G::NBIAS) v_bias[tid + 512 * q] = biasq[q];
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+    if (tid + 512 * q < G::NTBL) tbl[tid + 512 * q] = tblq[q];
+  if (wave_s < 6) {
+    *reinterpret_cast<f32x4*>(vec + v_off + 4 * lane) = vq[0];
+    if (256 + 4 * lane < v_len) *reinterpret_cast<f32x4*>(vec + v_off + 256 + 4 * lane) = vq[1];
+  }
+  if constexpr (HDP32 != HDP) {
+    // head dims padded to 48 / 80: the last 32-wide k step of q.k^T also covers 16 columns no epilogue writes (k: all 64 rows
+    // of every head of a group; q: this tile's 16)
+    for (int i = tid; i < HG * 64 * 4; i += 512) {
+      const int row = i >> 2, part = i & 3;
+      *reinterpret_cast<bf16x4*>(KV + row * HS + HDP + 4 * part) = bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+    }
+    for (int i = tid; i < HG * 16 * 4; i += 512) {
+      const int row = i >> 2, part = i & 3;
+      *reinterpret_cast<bf16x4*>(Qb + row * HS + HDP + 4 * part) = bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+    }
+  }
+  // ---- LayerNorm1 from the registers (the 8 lanes of a row hold all its columns) -> bf16 -> XN ----
+  {
+    float s = 0.f, ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+      const bool in = j * 32 + col4 * 4 < d;
+      const f32x4 v = in ? a_reg[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+      s += (v[0] + v[1]) + (v[2] + v[3]);
+      ss += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+    }
+    { s = srad_row8_sum(s); ss = srad_row8_sum(ss); }
+    const float mu = s / (float)d;
+    const float rstd = rsqrtf(fmaxf(ss / (float)d - mu * mu, 0.f) + 1e-5f);
+    __syncthreads();                                              // vectors / table / window geometry staged
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+      const int c = j * 32 + col4 * 4;
+      const f32x4 g4 = *reinterpret_cast<const f32x4*>(v_g1 + c);
+      const f32x4 b4 = *reinterpret_cast<const f32x4*>(v_b1n + c);
+      const f32x4 v = c < d ? (a_reg[j] - mu) * rstd * g4 + b4 : f32x4{0.f, 0.f, 0.f, 0.f};
+      bf16x4 hh;
+      hh[0] = (__bf16)v[0]; hh[1] = (__bf16)v[1]; hh[2] = (__bf16)v[2]; hh[3] = (__bf16)v[3];
+      *reinterpret_cast<bf16x4*>(XN + xrow * LDX + c) = hh;
+    }
+  }
+  static_for<1, NSETS>([&](auto Q) { load_w(Q, w_reg[decltype(Q)::value]); });   // the rest of the weight look-ahead
+  __syncthreads();                                                // the normalised window is in LDS
+
+  // ======================================= attention half, head group after head group =======================================
+  static_for<0, NG>([&](auto GR) {
+    constexpr int gr = decltype(GR)::value;
+    // ---- q|k|v = xn . W^T : one 16-column tile per wave and stage, transposed result (lane: token fr of row tile t, 4 columns);
+    //      k | v tiles for all four row tiles, q tiles for this workgroup's row tile only ----
+    f32x4 ac[4];
+    static_for<0, SPG>([&](auto LS) {
+      constexpr int cs = decltype(LS)::value, S = gr * SPG + cs;
+      constexpr bool isq = cs >= NKVS;
+      constexpr int NT = isq ? 1 : 4;
+      constexpr int nch = KC;
+      u32x4 (&reg)[RC] = w_reg[S % NSETS];
+      const QTile t = qtile(cs);
+#pragma unroll
+      for (int tt = 0; tt < 4; ++tt) ac[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (t.live) {
+        const __bf16* ar = XN + ((isq ? 16 * quarter : 0) + fr) * LDX + 8 * fq;
+        // the window fragments of two chunks (q: of all chunks) are requested together, THEN multiplied (see qkv_attn_kernel)
+        constexpr int CG = isq ? KC : 2;
+#pragma unroll
+        for (int cc0 = 0; cc0 < nch; cc0 += CG) {
+          bf16x8 af[CG][NT];
+#pragma unroll
+          for (int g = 0; g < CG; ++g)
+            if (cc0 + g < nch) {
+#pragma unroll
+              for (int tt = 0; tt < NT; ++tt) af[g][tt] = *reinterpret_cast<const bf16x8*>(ar + tt * 16 * LDX + (cc0 + g) * 32);
+            }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int g = 0; g < CG; ++g)
+            if (cc0 + g < nch) {
+              const bf16x8 b0 = __builtin_bit_cast(bf16x8, reg[cc0 + g]);
+#pragma unroll
+              for (int tt = 0; tt < NT; ++tt) ac[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, af[g][tt], ac[tt], 0, 0, 0);
+            }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      load_w(std::integral_constant<int, S + NSETS>{}, reg);
+      {
+        // the previous group's attention still reads q | k | v: its waves arrive here when they are done
+        if constexpr (gr > 0 && cs == 0) __syncthreads();
+        // bias, the attention's scale on q, zero padding -> the bf16 tiles the attention reads
+        if (t.live) {
+          const int c = t.ct * 16 + 4 * fq;
+          const f32x4 bias = *reinterpret_cast<const f32x4*>(v_bias + ((gr * HG + t.hl) * 3 + t.which) * HDP + c);
+          __bf16* dst = isq ? Qb + (t.hl * 16 + fr) * HS + c : KV + (((t.which - 1) * HG + t.hl) * 64 + fr) * HS + c;
+#pragma unroll
+          for (int tt = 0; tt < NT; ++tt) {
+            f32x4 v = ac[tt] + bias;
+            if constexpr (isq) v = v * scale;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = c + e < hd ? v[e] : 0.f;
+            bf16x4 hh;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hh[e] = (__bf16)v[e];
+            *reinterpret_cast<bf16x4*>(dst + tt * 16 * HS) = hh;
+          }
+        }
+      }
+    });
+    __syncthreads();                                              // q, k, v of the group complete (one group: the window tile is dead)
+    if constexpr (gr == 0) {
+      // columns [d, 32 KC) of the attention tile: the proj GEMM's k padding
+      const int row = tid >> 5, c = d + (tid & 31);
+      if (c < KC * 32) A1[row * B_LDA + c] = (__bf16)0.f;
+    }
+    // ---- one head per wave: S = q k^T + bias + mask, softmax, O = P V for this tile's 16 queries against the window's 64 keys ----
+    if (wave_s < HG) {
+      const int hl = wave_s, h = gr * HG + hl;
+      const __bf16* Qs = Qb + hl * 16 * HS;
+      const __bf16* Ks = KV + hl * 64 * HS;
+      const __bf16* Vs = KV + (HG + hl) * 64 * HS;
+      __bf16* Pw = Ps + hl * 16 * B_LDP;
+      f32x4 sc[4];
+      // relative position bias + 0 / -100 shift mask (drct.py:284-292, 449-470) of the lane's 16 (key, query) pairs
+      {
+        int qi[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) qi[e] = inf[16 * quarter + 4 * fq + e];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int ki = inf[j * 16 + fr], ky = (ki >> 8) & 0xff, kx = ki & 0xff, kr = ki >> 16;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int qy = (qi[e] >> 8) & 0xff, qx = qi[e] & 0xff, qr = qi[e] >> 16;
+            float v = tbl[((qy - ky + 7) * 15 + (qx - kx + 7)) * HEADS + h];
+            if (p.shift > 0 && qr != kr) v += -100.0f;
+            sc[j][e] = v;
+          }
+        }
+      }
+      f32x4 s4[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < HDP32; kk += 32) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Qs + fr * HS + kk + 8 * fq);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bf16x8 bb = *reinterpret_cast<const bf16x8*>(Ks + (j * 16 + fr) * HS + kk + 8 * fq);
+          s4[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, s4[j], 0, 0, 0);
+        }
+      }
+      // lane: queries 4 fq + e (e = 0..3) of the tile, keys 16 j + fr
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s4[j] += sc[j];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float mx = srad_row16_max(fmaxf(fmaxf(s4[0][e], s4[1][e]), fmaxf(s4[2][e], s4[3][e])));
+        float pr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pr[j] = __expf(s4[j][e] - mx);
+        const float rs = srad_row16_sum(pr[0] + pr[1]) + srad_row16_sum(pr[2] + pr[3]);   // the two key halves, as qkv_attn_kernel sums them
+        if (fr == 0) lsum[hl * 16 + 4 * fq + e] = rs;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Pw[(4 * fq + e) * B_LDP + j * 16 + fr] = (__bf16)pr[j];
+      }
+      __builtin_amdgcn_wave_barrier();                            // P and the sums are this wave's own: LDS keeps a wave's accesses in order
+      const float inv = 1.0f / lsum[hl * 16 + fr];
+      const int tq = fr >> 2, tp = fr & 3;
+#pragma unroll
+      for (int j = 0; j < HDT; ++j) {
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 64; kk += 32) {
+          const bf16x8 pa = *reinterpret_cast<const bf16x8*>(Pw + fr * B_LDP + kk + 8 * fq);
+          typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+          const __bf16* r0 = Vs + (kk + 8 * fq + tq) * HS + j * 16 + 4 * tp;
+          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0));
+          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0 + 4 * HS));
+          bf16x8 vb;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { vb[e] = lo[e]; vb[4 + e] = hi[e]; }
+          o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb, pa, o, 0, 0, 0);
+        }
+        // transposed result: token fr of the tile, columns 16 j + 4 fq + e of the head -> the proj GEMM's A tile
+        __bf16* dst = A1 + fr * B_LDA + h * hd;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = j * 16 + 4 * fq + e;
+          if (c < hd) dst[c] = (__bf16)(o[e] * inv);
+        }
+      }
+    }
+  });
+
+  // ============================ MLP half: mlp_block_kernel<16> on the tile's 16 token rows ============================
+  auto col4_of = [&](int g) { return B_SC * g + 16 * wave + 4 * fq; };
+  auto store_bf4 = [&](__bf16* base, int ld, int c4, f32x4 v) __attribute__((always_inline)) {
+    bf16x4 h;
+    h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
+    *reinterpret_cast<bf16x4*>(base + fr * ld + c4) = h;
+  };
+  // c += (A[16 rows][k0 .. k0 + nch*32) . W[16 columns of this wave][..]^T)^T
+  auto mma_stage = [&](const __bf16* A, int lda, int k0, int nch, const u32x4 (&reg)[RC], f32x4& c) __attribute__((always_inline)) {
+    const __bf16* ar = A + fr * lda + k0 + 8 * fq;
+    bf16x8 af[8];
+#pragma unroll
+    for (int g = 0; g < 8; ++g)
+      if (g < nch) af[g] = *reinterpret_cast<const bf16x8*>(ar + g * 32);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int g = 0; g < 8; ++g)
+      if (g < nch) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, reg[g]), af[g], c, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto epi_proj = [&](auto GI, const f32x4& c) __attribute__((always_inline)) {
+    constexpr int g = decltype(GI)::value;
+    x1[g] += c + *reinterpret_cast<const f32x4*>(v_bp + min(col4_of(g), 380));
+    if constexpr (g != GD - 1) return;
+    // LayerNorm2 over the d real columns of x1 -> bf16 -> A1 (all proj reads of A1 are behind a barrier)
+    float sm = 0.f, sq = 0.f;
+#pragma unroll
+    for (int gg = 0; gg < GD; ++gg) {
+      const f32x4 v = col4_of(gg) < d ? x1[gg] : f32x4{0.f, 0.f, 0.f, 0.f};
+      sm += (v[0] + v[1]) + (v[2] + v[3]);
+      sq += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+    }
+    sm += __shfl_xor(sm, 16); sq += __shfl_xor(sq, 16);
+    sm += __shfl_xor(sm, 32); sq += __shfl_xor(sq, 32);
+    if (fq == 0) { red[(fr * 8 + wave) * 2 + 0] = sm; red[(fr * 8 + wave) * 2 + 1] = sq; }
+    __syncthreads();
+    float su = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) { su += red[fr * 16 + 2 * w]; s2 += red[fr * 16 + 2 * w + 1]; }
+    const float mu = su / (float)d;
+    const float rstd = rsqrtf(fmaxf(s2 / (float)d - mu * mu, 0.f) + 1e-5f);
+#pragma unroll
+    for (int gg = 0; gg < GD; ++gg) {
+      const int c4 = col4_of(gg);
+      const f32x4 gam = *reinterpret_cast<const f32x4*>(v_g2 + min(c4, 380));
+      const f32x4 bet = *reinterpret_cast<const f32x4*>(v_b2n + min(c4, 380));
+      store_bf4(A1, B_LDA, c4, c4 < d ? (x1[gg] - mu) * rstd * gam + bet : f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+  };
+  auto epi_fc1 = [&](int g, const f32x4& c) __attribute__((always_inline)) {
+    const int c4 = col4_of(g);
+    f32x4 v = c + *reinterpret_cast<const f32x4*>(v_bf1 + min(c4, 508));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = blk_gelu(v[e]);
+    store_bf4(Hs, B_LDH, c4, c4 < m ? v : f32x4{0.f, 0.f, 0.f, 0.f});      // m % 4 == 0
+  };
+  auto epi_fc2 = [&](auto GI, const f32x4& c) __attribute__((always_inline)) {
+    constexpr int g = decltype(GI)::value;
+    x1[g] += c + *reinterpret_cast<const f32x4*>(v_bf2 + min(col4_of(g), 380));
+    if constexpr (g != GD - 1) return;
+    // x2 -> bf16 -> A1 (its last readers, the fc1 stages, finished long ago)
+#pragma unroll
+    for (int gg = 0; gg < GD; ++gg) {
+      const int c4 = col4_of(gg);
+      store_bf4(A1, B_LDA, c4, c4 < d ? x1[gg] : f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+  };
+  auto epi_adj = [&](int g, const f32x4& c) __attribute__((always_inline)) {
+    const int c4 = col4_of(g);
+    const int cc = min(c4, no - 4);                                 // no % 4 == 0
+    const f32x4 ba = *reinterpret_cast<const f32x4*>(v_ba + min(c4, 380));
+    f32x4 rv = {0.f, 0.f, 0.f, 0.f};
+    if (p.R) rv = *reinterpret_cast<const f32x4*>(p.R + (size_t)row_tok * p.ldr + cc);
+    f32x4 v = c + ba;
+    if (p.act == SRAD_ACT_LRELU) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.slope;
+    }
+    v = v * p.alpha + rv;
+    if (c4 < no) *reinterpret_cast<f32x4*>(p.Y + (size_t)row_tok * p.ldy + p.yoff + c4) = v;
+  };
+
+  f32x4 c;
+  static_for<0, n_mlp>([&](auto SI) {
+    constexpr int s = decltype(SI)::value;
+    constexpr int ph = s < n_proj ? 0 : (s < n_proj + n_fc1 ? 1 : (s < n_proj + n_fc1 + n_fc2 ? 2 : 3));
+    constexpr int ls = s - (ph == 0 ? 0 : (ph == 1 ? n_proj : (ph == 2 ? n_proj + n_fc1 : n_proj + n_fc1 + n_fc2)));
+    constexpr int kgs = ph == 2 ? KGM : KGD;
+    constexpr int g = ls / kgs, kg = ls - g * kgs;
+    u32x4 (&reg)[RC] = w_reg[(QS + s) % NSETS];
+    constexpr int kch = ph == 2 ? KCM : KCD;
+    constexpr int nch = kch - kg * 8 < 8 ? kch - kg * 8 : 8;
+    if constexpr (ls == 0) __syncthreads();            // first stage of a phase: the activation tile (A1 / Hs) is complete
+    if constexpr (kg == 0) c = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bool live = (g * 8 + wave_s) * 16 < (ph == 0 ? d : (ph == 1 ? m : (ph == 2 ? d : no)));
+    if (live) mma_stage(ph == 2 ? Hs : A1, ph == 2 ? B_LDH : B_LDA, kg * 256, nch, reg, c);
+    // refill this set, NSETS stages ahead; behind an epilogue that other waves wait for (see mlp_block_kernel)
+    constexpr bool epi_first = kg == kgs - 1;
+    if constexpr (!epi_first) load_w(std::integral_constant<int, QS + s + NSETS>{}, reg);
+    if constexpr (epi_first) {
+      if constexpr (ph == 0) epi_proj(std::integral_constant<int, g>{}, c);
+      else if constexpr (ph == 1) epi_fc1(g, c);
+      else if constexpr (ph == 2) epi_fc2(std::integral_constant<int, g>{}, c);
+      else epi_adj(g, c);
+      load_w(std::integral_constant<int, QS + s + NSETS>{}, reg);
+    }
+  });
+}
+
+template <int HDT, int KC, int HEADS, int NG, int GD, int KGD, int GM, int KGM, int GN, int KCM>
+int launch_blk(const SwinBlockParams& p, hipStream_t stream) {
+  constexpr size_t lds = BlkGeo<HDT, KC, HEADS, NG>::LDS;
+  const double T = (double)p.B * p.H * p.W;
+  const double flops = 2.0 * T * (4.0 * p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d) + 4.0 * T * 64.0 * p.d;
+  const double bytes = 4.0 * T * (2.0 * p.d + p.no) + 2.0 * (4.0 * p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
+  SradProfScope prof(stream, SRAD_K_SWIN_BLOCK, flops, bytes);
+  const int nW = (p.H / 8) * (p.W / 8);
+  SRAD_TRY((srad_launch_dyn<swin_block_kernel<HDT, KC, HEADS, NG, GD, KGD, GM, KGM, GN, KCM>>(dim3(p.B * nW, 4), dim3(512), lds, stream, p)));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+// DRCT-L's five Swin blocks (d = 180 / 212 / 244 / 276 / 308): (head tiles, k chunks of d, heads, head groups) of the attention
+// half, then mlp_block's stage geometry (column groups of d, k groups of d, column groups of m, k groups of m, column groups
+// of the adjust output, k chunks of m)
+#define SRAD_BLK_CFGS(X) X(2, 6, 6, 1, 2, 1, 3, 2, 1, 12) X(4, 7, 4, 1, 2, 1, 4, 2, 1, 14) X(8, 8, 2, 1, 2, 1, 4, 2, 1, 16) \
+  X(3, 9, 6, 2, 3, 2, 3, 2, 1, 9) X(5, 10, 4, 2, 3, 2, 3, 2, 2, 10)
+
+struct BlkKey { int hdt, kc, heads, gd, kgd, gm, kgm, gn, kcm; };
+inline BlkKey blk_key(int d, int heads, int m, int no) {
+  const int Kd = srad_cp(d), Km = srad_cp(m);
+  return BlkKey{(d / heads + 15) / 16, Kd / 32, heads, (d + B_SC - 1) / B_SC, (Kd + 255) / 256, (m + B_SC - 1) / B_SC, (Km + 255) / 256,
+                (no + B_SC - 1) / B_SC, Km / 32};
+}
+#define SRAD_BLK_MATCH(K_, A_, B_, H_, NG_, GD_, KGD_, GM_, KGM_, GN_, KCM_) \
+  (K_.hdt == A_ && K_.kc == B_ && K_.heads == H_ && K_.gd == GD_ && K_.kgd == KGD_ && K_.gm == GM_ && K_.kgm == KGM_ && K_.gn == GN_ && K_.kcm == KCM_)
+
+// CUs of the current device (cached per device)
+int blk_cu_count() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    cus[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+  }
+  return cus[dev];
+}
+}  // namespace
+
+extern "C" int srad_swin_block_supported(int prec, int ws, int B, int H, int W, int d, int heads, int hidden, int no) {
+  if (prec != SRAD_PREC_BF16 || ws != 8 || B < 1 || H < 8 || W < 8 || H % 8 || W % 8 || d % 4 || hidden % 4 || no % 4 || d < 32 || d > 320 ||
+      hidden < 32 || hidden > 512 || no < 4 || no > 384 || heads < 1 || d % heads)
+    return false;
+  if ((long long)B * (H / 8) * (W / 8) * 4 > blk_cu_count()) return false;   // one workgroup per CU, all resident: a quarter window each
+  const BlkKey k = blk_key(d, heads, hidden, no);
+#define X(...) if (SRAD_BLK_MATCH(k, __VA_ARGS__)) return true;
+  SRAD_BLK_CFGS(X)
+#undef X
+  return false;
+}
+
+// Block shapes (d, heads, hidden, adjust outputs) for which tools/swin_block_bench.py measured the single launch faster than
+// qkv_attn + mlp_block + one launch boundary at B = 4, 32 x 32 AND the step measured faster with them (d = 276
+// wins 1.1 us on the bench and nothing measurable in the step, d = 308 loses).  The engine takes the new kernel for these only.
+bool srad_swin_block_wins(int d, int heads, int hidden, int no) {
+  struct Shape { int d, heads, hidden, no; };
+  static const Shape wins[] = {{180, 6, 360, 32}, {212, 4, 424, 32}, {244, 2, 488, 32}};
+  for (const Shape& s : wins)
+    if (s.d == d && s.heads == heads && s.hidden == hidden && s.no == no) return true;
+  return false;
+}
+
+int srad_launch_swin_block(const SwinBlockParams& p, hipStream_t stream) {
+  SRAD_REQUIRE(srad_swin_block_supported(SRAD_PREC_BF16, 8, p.B, p.H, p.W, p.d, p.heads, p.m, p.no),
+               "swin_block: unsupported shape %dx%dx%d d=%d heads=%d m=%d no=%d (bf16, window 8, windows x 4 <= CUs)", p.B, p.H, p.W, p.d, p.heads, p.m, p.no);
+  SRAD_REQUIRE(p.x && p.ln1_g && p.ln1_b && p.w_qkv && p.b_qkv && p.table && p.w_proj && p.w_fc1 && p.w_fc2 && p.w_adj && p.b_proj && p.b_fc1 &&
+                   p.b_fc2 && p.b_adj && p.ln2_g && p.ln2_b && p.Y, "swin_block: null argument");
+  SRAD_REQUIRE(p.shift >= 0 && p.shift < 8, "swin_block: shift %d must be in [0, 8)", p.shift);
+  SRAD_REQUIRE((p.ldx & 3) == 0 && ((uintptr_t)p.x & 15) == 0 && (p.ldy & 3) == 0 && (p.yoff & 3) == 0 && ((uintptr_t)p.Y & 15) == 0 &&
+                   (!p.R || ((p.ldr & 3) == 0 && ((uintptr_t)p.R & 15) == 0)),
+               "swin_block: input / output / residual rows must be float4-addressable");
+  SRAD_REQUIRE((((uintptr_t)p.b_proj | (uintptr_t)p.b_fc1 | (uintptr_t)p.b_fc2 | (uintptr_t)p.b_adj | (uintptr_t)p.ln2_g | (uintptr_t)p.ln2_b) & 15) == 0,
+               "swin_block: bias / LayerNorm2 vectors must be 16-byte aligned");
+  // the output may share x's buffer only as the columns behind the block's own (adjust_k); anything else would race with the
+  // other workgroups' reads of columns [0, d)
+  SRAD_REQUIRE(p.Y != p.x || (p.ldy == p.ldx && p.yoff >= p.d), "swin_block: an in-place output must lie behind the block's %d input columns", p.d);
+  const BlkKey k = blk_key(p.d, p.heads, p.m, p.no);
+#define X(a, b, h, ng, gd, kgd, gm, kgm, gn, kcm) \
+  if (SRAD_BLK_MATCH(k, a, b, h, ng, gd, kgd, gm, kgm, gn, kcm)) return launch_blk<a, b, h, ng, gd, kgd, gm, kgm, gn, kcm>(p, stream);
+  SRAD_BLK_CFGS(X)
+#undef X
+  return srad_set_error(SRAD_ERR_ARG, "swin_block: no kernel instance for this geometry");
+}

@@ -35,18 +35,18 @@ struct Prof {
 } g_prof;
 const char* const kClassNames[SRAD_K_COUNT] = {"gemm_bn64", "gemm_bn32", "gemm_bn16", "window_attn", "layernorm",
                                                "layout", "pack_weight", "score", "misc", "mlp_block", "qkv_attn",
-                                               "wgrad", "window_attn_bwd", "layernorm_bwd", "optim", "wgrad_reduce", "mlp_bwd", "ln_qkv", "conv80", "ensemble"};
+                                               "wgrad", "window_attn_bwd", "layernorm_bwd", "optim", "wgrad_reduce", "mlp_bwd", "ln_qkv", "conv80", "ensemble", "swin_block"};
 }  // namespace
 
 // ---------------------------------------------------------------- path overrides (include/srad.h)
-int g_srad_path_override[SRAD_PATH_COUNT] = {};
+int g_srad_path_override[SRAD_PATH_END] = {};
 extern "C" int srad_set_path_override(int path, int on) {
-  SRAD_REQUIRE(path >= 0 && path < SRAD_PATH_COUNT, "set_path_override: unknown path %d", path);
+  SRAD_REQUIRE(srad_path_known(path), "set_path_override: unknown path %d", path);
   g_srad_path_override[path] = on ? 1 : 0;
   return SRAD_OK;
 }
 extern "C" int srad_get_path_override(int path) {
-  if (path < 0 || path >= SRAD_PATH_COUNT) return srad_set_error(-1, "get_path_override: unknown path %d", path);
+  if (!srad_path_known(path)) return srad_set_error(-1, "get_path_override: unknown path %d", path);
   return g_srad_path_override[path];
 }
 

@@ -317,6 +317,76 @@ int srad_op_mlp_block(int precision, int M, int d, int m, int no, int fm, const 
   return srad_launch_mlp_block(q, s);
 }
 
+// A whole Swin block + the adjust conv in one launch (kernels_fused_block.hip): the two ops above back to back, x being the shortcut.
+int srad_op_swin_block(int precision, const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, int m, int no,
+                       const float* ln1_g, const float* ln1_b, const float* w_qkv, const float* b_qkv, const float* table,
+                       const float* w_proj, const float* b_proj, const float* ln2_g, const float* ln2_b, const float* w_fc1,
+                       const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
+                       float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+  SRAD_REQUIRE(x && ln1_g && ln1_b && w_qkv && b_qkv && table && w_proj && b_proj && ln2_g && ln2_b && w_fc1 && b_fc1 && w_fc2 && b_fc2 && w_adj &&
+                   b_adj && y && scratch, "op_swin_block: null argument");
+  SRAD_REQUIRE(srad_swin_block_supported(precision, 8, B, H, W, d, heads, m, no),
+               "op_swin_block: unsupported: precision %d, %dx%dx%d, d=%d heads=%d m=%d no=%d (bf16, 8 x 8 windows, windows x 4 <= CUs)", precision, B, H, W,
+               d, heads, m, no);
+  size_t off[10];
+  swin_scratch_parts(d, heads, m, no, off);                        // off[5]: where the lo packs would start = the size of the hi packs
+  SRAD_REQUIRE(scratch_bytes >= off[5] && ((uintptr_t)scratch & 255) == 0,
+               "op_swin_block: scratch %zu bytes, %zu needed (256-byte aligned)", scratch_bytes, off[5]);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* sc = reinterpret_cast<char*>(scratch);
+  SRAD_TRY(srad_launch_pack_qkv_frag(w_qkv, sc + off[0], d, heads, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_proj, sc + off[1], d, d, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fc1, sc + off[2], m, d, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fc2, sc + off[3], d, m, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_adj, sc + off[4], no, d, s));
+  SwinBlockParams q{};
+  q.x = x; q.ldx = ldx; q.B = B; q.H = H; q.W = W; q.shift = shift; q.d = d; q.heads = heads; q.m = m; q.no = no;
+  q.ln1_g = ln1_g; q.ln1_b = ln1_b; q.w_qkv = sc + off[0]; q.b_qkv = b_qkv; q.table = table;
+  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = sc + off[3]; q.w_adj = sc + off[4];
+  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.b_adj = b_adj; q.ln2_g = ln2_g; q.ln2_b = ln2_b;
+  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff;
+  return srad_launch_swin_block(q, s);
+}
+
+// Diagnostic twin of srad_bench_qkv_attn + srad_bench_mlp_block for the one-launch block: microseconds per launch, back-to-back
+// launches.  x, y: [B*H*W][320] fp32; the output goes to columns [d, d + no) of y (adjust_k's epilogue), or [0, no) where those do not fit.
+int srad_bench_swin_block(const float* x, int B, int H, int W, int shift, int d, int heads, int m, int no, const float* w_fp32,
+                          float* y, void* scratch, size_t scratch_bytes, int iters, float* us_out, void* stream) {
+  SRAD_REQUIRE(x && w_fp32 && y && scratch && us_out && iters > 0, "bench_swin_block: bad argument");
+  SRAD_REQUIRE(srad_swin_block_supported(SRAD_PREC_BF16, 8, B, H, W, d, heads, m, no) && no <= 320, "bench_swin_block: unsupported shape");
+  size_t off[10];
+  swin_scratch_parts(d, heads, m, no, off);
+  SRAD_REQUIRE(scratch_bytes >= off[5] && ((uintptr_t)scratch & 255) == 0, "bench_swin_block: scratch too small or not 256-byte aligned");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* sc = reinterpret_cast<char*>(scratch);
+  SRAD_TRY(srad_launch_pack_qkv_frag(w_fp32, sc + off[0], d, heads, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fp32, sc + off[1], d, d, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fp32, sc + off[2], m, d, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fp32, sc + off[3], d, m, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fp32, sc + off[4], no, d, s));
+  SwinBlockParams q{};
+  q.x = x; q.ldx = 320; q.B = B; q.H = H; q.W = W; q.shift = shift; q.d = d; q.heads = heads; q.m = m; q.no = no;
+  q.ln1_g = q.ln1_b = q.b_qkv = q.table = w_fp32; q.w_qkv = sc + off[0];
+  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = sc + off[3]; q.w_adj = sc + off[4];
+  q.b_proj = q.b_fc1 = q.b_fc2 = q.b_adj = q.ln2_g = q.ln2_b = w_fp32;
+  q.act = SRAD_ACT_LRELU; q.slope = 0.2f; q.alpha = 1.f; q.Y = y; q.ldy = 320; q.yoff = d + no <= 320 ? d : 0;
+  for (int i = 0; i < 3; ++i) SRAD_TRY(srad_launch_swin_block(q, s));
+  hipEvent_t e0, e1;
+  SRAD_CHECK_HIP(hipEventCreate(&e0));
+  SRAD_CHECK_HIP(hipEventCreate(&e1));
+  SRAD_CHECK_HIP(hipEventRecord(e0, s));
+  for (int i = 0; i < iters; ++i) SRAD_TRY(srad_launch_swin_block(q, s));
+  SRAD_CHECK_HIP(hipEventRecord(e1, s));
+  SRAD_CHECK_HIP(hipEventSynchronize(e1));
+  float ms = 0.f;
+  SRAD_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  *us_out = ms * 1e3f / iters;
+  return SRAD_OK;
+}
+
 int srad_op_wgrad(int precision, const float* dy, int ldy, const float* x, int ldx, int B, int Hi, int Wi, int N,
                   int Cin, int ntaps, int stride, const float* row_scale, float alpha, float* dw, float* db,
                   void* workspace, void* stream) {

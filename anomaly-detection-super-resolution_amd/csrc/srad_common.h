@@ -135,7 +135,8 @@ int srad_launch_dyn(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&..
 }
 
 // Path overrides of include/srad.h (srad_set_path_override): a process-wide table, all off unless a test sets one
-extern int g_srad_path_override[SRAD_PATH_COUNT];
+extern int g_srad_path_override[SRAD_PATH_END];
+static inline bool srad_path_known(int path) { return (path >= 0 && path < SRAD_PATH_COUNT) || (path >= SRAD_PATH_PLAN_FIRST && path < SRAD_PATH_END); }
 static inline bool srad_path_override(int path) { return g_srad_path_override[path] != 0; }
 
 static inline size_t srad_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -341,6 +342,29 @@ int srad_launch_ln_qkv(const LnQkvParams& p, hipStream_t stream);
 int srad_launch_qkv_attn(const QkvAttnParams& p, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
+// A whole Swin block + the adjust conv as one launch (kernels_fused_block.hip): qkv_attn followed by mlp_block on 16-row
+// tiles, a quarter window per workgroup; bf16, window 8, inference, windows x 4 <= CUs.  The fields are those of
+// QkvAttnParams and MlpBlockParams; the shortcut is x itself.
+// ------------------------------------------------------------------------------------------
+struct SwinBlockParams {
+  const float* x; int ldx;                 // block input rows [T][ldx] (columns [0, d) are read): LayerNorm1's input and the shortcut
+  int B, H, W, shift, d, heads, m, no;     // image geometry, block dim, heads, MLP hidden, adjust output channels
+  const float *ln1_g, *ln1_b;
+  const void* w_qkv; const float* b_qkv;   // per-head fragment pack (srad_launch_pack_qkv_frag), bias [3d]
+  const float* table;                      // [225][heads]
+  const void *w_proj, *w_fc1, *w_fc2, *w_adj;   // fragment-major packs (srad_launch_pack_weight_frag)
+  const float *b_proj, *b_fc1, *b_fc2, *b_adj, *ln2_g, *ln2_b;
+  int act; float slope, alpha;             // adjust epilogue
+  const float* R; int ldr;
+  float* Y; int ldy, yoff;
+  int no_xcd_map;                          // 1: plain workgroup -> window order
+};
+// (srad_swin_block_supported(prec, ws, B, H, W, d, heads, hidden, no) is part of the C ABI: include/srad.h)
+// is this block shape in the table of shapes for which the single launch measured faster than the pair?
+bool srad_swin_block_wins(int d, int heads, int hidden, int no);
+int srad_launch_swin_block(const SwinBlockParams& p, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------
 // Backward kernels (kernels_wgrad.hip, kernels_bwd.hip) - the training path of reference src/trainer.py:152-222.
 // ------------------------------------------------------------------------------------------
 // stored input channel c of a layer whose input is `grp_pad`-wide groups with `grp_real` real channels each -> the real
@@ -515,7 +539,7 @@ int srad_launch_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int C, in
 enum {
   SRAD_K_GEMM_BN64 = 0, SRAD_K_GEMM_BN32, SRAD_K_GEMM_BN16, SRAD_K_ATTN, SRAD_K_LAYERNORM,
   SRAD_K_LAYOUT, SRAD_K_PACK, SRAD_K_SCORE, SRAD_K_MISC, SRAD_K_MLP_BLOCK, SRAD_K_QKV_ATTN,
-  SRAD_K_WGRAD, SRAD_K_ATTN_BWD, SRAD_K_LN_BWD, SRAD_K_OPTIM, SRAD_K_WGRAD_REDUCE, SRAD_K_MLP_BWD, SRAD_K_LN_QKV, SRAD_K_CONV80, SRAD_K_ENSEMBLE, SRAD_K_COUNT
+  SRAD_K_WGRAD, SRAD_K_ATTN_BWD, SRAD_K_LN_BWD, SRAD_K_OPTIM, SRAD_K_WGRAD_REDUCE, SRAD_K_MLP_BWD, SRAD_K_LN_QKV, SRAD_K_CONV80, SRAD_K_ENSEMBLE, SRAD_K_SWIN_BLOCK, SRAD_K_COUNT
 };
 struct SradProfScope {
   hipStream_t s; int active;

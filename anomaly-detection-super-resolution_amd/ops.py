@@ -19,14 +19,18 @@ def _need_cuda(*ts):
 
 # include/srad.h SRAD_PATH_*: the reference paths a test can force instead of the one shape and precision pick
 PATHS = {"unfused_blocks": 0, "qkv_via_gemm": 1, "attn_f32_in": 2, "upconv_one_gemm": 3}
+# ... and its launch-plan overrides (ids from SRAD_PATH_PLAN_FIRST): the launches a default path is compared against
+PLAN_PATHS = {"block_two_launches": 16}
 
 
 @contextlib.contextmanager
 def path_override(**paths: bool):
     """Force reference paths inside the block, e.g. ``with ops.path_override(unfused_blocks=True):``, and restore the previous
-    settings on exit.  unfused_blocks is read by the DRCT engine when it is created (forward) and at every backward."""
+    settings on exit.  unfused_blocks is read by the DRCT engine when it is created (forward) and at every backward;
+    block_two_launches (a Swin block as qkv_attn + mlp_block where the one-launch kernel would run) whenever a forward
+    records its launches, i.e. before the first forward of a shape."""
     lib = L.lib()
-    ids = {name: PATHS[name] for name in paths}
+    ids = {name: PATHS[name] if name in PATHS else PLAN_PATHS[name] for name in paths}
     before = {name: lib.srad_get_path_override(i) for name, i in ids.items()}
     try:
         for name, on in paths.items():
@@ -506,6 +510,34 @@ def mlp_block(attn: torch.Tensor, shortcut: torch.Tensor, w_proj, b_proj, ln_g, 
     L.check(L.lib().srad_op_mlp_block(L.PRECISIONS[precision], M, d, m, no, int(fm), L.dptr(attn), L.dptr(shortcut), shortcut.stride(0), *[L.dptr(k) for k in keep],
                                       int(act), float(slope), float(alpha), L.dptr(residual), 0 if residual is None else residual.stride(0),
                                       L.dptr(out), out.stride(0), int(out_offset), sp, sb, L.current_stream_ptr()), "op_mlp_block")
+    return out
+
+
+def swin_block_supported(B: int, H: int, W: int, d: int, heads: int, hidden: int, no: int, ws: int = 8, precision: str = "bf16") -> bool:
+    """Does the one-launch Swin block kernel take this shape on the current device (``srad_swin_block_supported``)?"""
+    return bool(L.lib().srad_swin_block_supported(L.PRECISIONS[precision], ws, B, H, W, d, heads, hidden, no))
+
+
+def swin_block(x: torch.Tensor, ln1_g, ln1_b, w_qkv, b_qkv, table, w_proj, b_proj, ln2_g, ln2_b, w_fc1, b_fc1, w_fc2, b_fc2, w_adj, b_adj,
+               B: int, H: int, W: int, shift: int, heads: int, *, act: int = L.ACT_LRELU, slope: float = 0.2, alpha: float = 1.0,
+               residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_offset: int = 0,
+               precision: str = "bf16") -> torch.Tensor:
+    """A whole Swin block + the RDG's 1x1 adjust conv in ONE launch (``srad_op_swin_block``): ``qkv_attn`` followed by
+    ``mlp_block`` with x [B*H*W, >=d] as the shortcut.  bf16, 8 x 8 windows, B * H/8 * W/8 * 4 <= the device's CUs; anything
+    else raises.  Returns / fills out[:, out_offset:out_offset+no]; ``out`` may be x itself with out_offset >= d."""
+    _need_cuda(x, w_qkv, w_proj, w_fc1, w_fc2, w_adj)
+    d = w_qkv.shape[1]
+    m, no = w_fc1.shape[0], w_adj.shape[0]
+    assert x.dim() == 2 and x.shape[0] == B * H * W and x.stride(1) == 1 and x.dtype == torch.float32 and w_qkv.shape[0] == 3 * d
+    f = lambda t: t.detach().float().contiguous()
+    keep = [f(ln1_g), f(ln1_b), f(w_qkv), f(b_qkv), f(table), f(w_proj), f(b_proj), f(ln2_g), f(ln2_b), f(w_fc1), f(b_fc1), f(w_fc2), f(b_fc2),
+            f(w_adj.reshape(no, d)), f(b_adj)]
+    if out is None:
+        out = torch.empty(x.shape[0], no, dtype=torch.float32, device=x.device)
+    sbuf, sp, sb = L.ws_buffer(L.lib().srad_op_swin_scratch_bytes(d, heads, m, no), x.device)
+    L.check(L.lib().srad_op_swin_block(L.PRECISIONS[precision], L.dptr(x), x.stride(0), B, H, W, shift, d, heads, m, no, *[L.dptr(k) for k in keep],
+                                       int(act), float(slope), float(alpha), L.dptr(residual), 0 if residual is None else residual.stride(0),
+                                       L.dptr(out), out.stride(0), int(out_offset), sp, sb, L.current_stream_ptr()), "op_swin_block")
     return out
 
 

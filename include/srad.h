@@ -423,6 +423,17 @@ int srad_op_mlp_block(int precision, int M, int d, int m, int no, int fm, const 
                       const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
                       float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
                       size_t scratch_bytes, void* stream);
+/* A whole Swin block + the adjust conv as ONE launch (kernels_fused_block.hip): srad_op_qkv_attn followed by srad_op_mlp_block
+ * on 16-row tiles, a quarter window per workgroup, the attention output never leaving the CU.  bf16, 8 x 8 windows, inference,
+ * B * (H / 8) * (W / 8) * 4 <= the device's CU count; anything else is an error (srad_swin_block_supported tells).  x is
+ * LayerNorm1's input and the shortcut; scratch as for the pair (srad_op_swin_scratch_bytes(d, heads, m, no)). */
+int srad_swin_block_supported(int precision, int ws, int B, int H, int W, int d, int heads, int m, int no);
+int srad_op_swin_block(int precision, const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, int m, int no,
+                       const float* ln1_g, const float* ln1_b, const float* w_qkv, const float* b_qkv, const float* table,
+                       const float* w_proj, const float* b_proj, const float* ln2_g, const float* ln2_b, const float* w_fc1,
+                       const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
+                       float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
+                       size_t scratch_bytes, void* stream);
 
 /* The two kernels of BASELINE config C5's attention (bf16, 64 x 64 windows = 4096-token windows; src/main.py:286), each on its own:
  *   srad_op_ln_qkv              norm1 + attn.qkv (src/drct.py:477, 278) -> qkv_h [M][3][heads][hdp] bf16, the attention's MFMA
@@ -540,6 +551,10 @@ int srad_op_lin_ln_bwd(int M, int K, int d, const float* dY, const float* w, con
  * unknown path. */
 enum { SRAD_PATH_UNFUSED_BLOCKS = 0, SRAD_PATH_QKV_VIA_GEMM = 1, SRAD_PATH_ATTN_F32_IN = 2, SRAD_PATH_UPCONV_ONE_GEMM = 3,
        SRAD_PATH_COUNT = 4 };
+/* Launch-plan overrides: the same two calls, ids from SRAD_PATH_PLAN_FIRST (the ids between SRAD_PATH_COUNT and it stay unknown).
+ *   SRAD_PATH_BLOCK_TWO_LAUNCHES  DRCT forward: a Swin block as the qkv_attn + mlp_block pair where the one-launch
+ *                                 swin_block kernel would be chosen (read at every forward that records launches) */
+enum { SRAD_PATH_PLAN_FIRST = 16, SRAD_PATH_BLOCK_TWO_LAUNCHES = 16, SRAD_PATH_END = 17 };
 int srad_set_path_override(int path, int on);
 int srad_get_path_override(int path);
 /* Per-kernel-class device timing with HIP events on the launch stream (bench.py's roofline numbers). */
@@ -560,6 +575,10 @@ int srad_bench_window_attn(int precision, const float* qkv, float* out, const fl
 int srad_bench_qkv_attn(const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, const float* w_fp32,
                         void* out /* written as bf16 [B*H*W][d] */, void* scratch, size_t scratch_bytes, int iters, float* us_out,
                         void* stream);
+/* tools/swin_block_bench.py: the one-launch Swin block on synthetic operands (x, y: [B*H*W][320] fp32; y also takes the
+ * output: columns [d, d + no), or [0, no) where those do not fit), microseconds per launch, back-to-back launches. */
+int srad_bench_swin_block(const float* x, int B, int H, int W, int shift, int d, int heads, int m, int no, const float* w_fp32,
+                          float* y, void* scratch, size_t scratch_bytes, int iters, float* us_out, void* stream);
 /* tools/wgrad_bench.py: one Swin block's five weight gradients as the training step issues them (one deferred launch +
  * the reduce), `iters` times; storage bit 0 / 1: the X / dY operands are bf16. */
 int srad_bench_wgrad_block(int M, int d, int hidden, int KA, int storage, const void* xbuf, const void* ybuf, float* dw,
