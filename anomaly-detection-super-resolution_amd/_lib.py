@@ -218,6 +218,20 @@ _SIG = {
     "srad_bench_wgrad_block": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "srad_op_window_attn_bwd_h": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_int, _P, _P]),
+    # DRN's own kernels, one by one (csrc/drn.hip)
+    "srad_drn_ca_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "srad_op_drn_bicubic": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "srad_op_drn_affine_to_nchw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "srad_op_drn_pool_dot": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "srad_op_drn_ca_scale_add": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int,
+                                           _P, C.c_int, _P, _P, _P]),
+    "srad_op_drn_ca_apply_bwd": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
+    "srad_op_drn_ca_bwd": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "srad_op_drn_affine_bwd": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "srad_op_drn_zero_upsample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "srad_op_drn_add_cols": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, C.c_int, _P]),
+    "srad_op_conv_pool": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_int), _P,
+                                    C.c_size_t, _P]),
 }
 
 BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int)

@@ -349,12 +349,17 @@ inline bool drn_level_bf16(int prec, int B, int Hl, int Wl, int ch) {
 
 inline int ca_slices(int hw) { return hw >= 128 * 128 ? 128 : (hw >= 1024 ? 64 : (hw >= 64 ? 8 : 1)); }
 
-// ca_scale_add_kernel's instance for the operand storage (r / x / y as bf16) and the slice size: 5 or 10 items per thread wait in
-// registers over the gate chain, larger slices take the loop
+// float4 items per thread that wait in registers over the gate chain (the NI of ca_scale_add_kernel / ca_apply_bwd_kernel): 5 or
+// 10 by the slice size, 0 = larger slices take the loop
+inline int ca_ni(int hw, int slices, int C) {
+  const int items = ((hw + slices - 1) / slices) * (C / 4);
+  return items > 2560 ? 0 : (items <= 1280 ? 5 : 10);
+}
+
+// ca_scale_add_kernel's instance for the operand storage (r / x / y as bf16) and the slice size
 template <class... A>
 inline void launch_ca_scale_add(bool r_h, bool x_h, bool y_h, int slices, int B, int hw, int C, hipStream_t s, A... args) {
-  const int items = ((hw + slices - 1) / slices) * (C / 4);
-  const int ni = items > 2560 ? 0 : (items <= 1280 ? 5 : 10);
+  const int ni = ca_ni(hw, slices, C);
   const dim3 grid(slices, B);
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, args...); };
   auto by_ni = [&](auto RH, auto XH, auto YH) {
@@ -374,6 +379,22 @@ inline void launch_ca_scale_add(bool r_h, bool x_h, bool y_h, int slices, int B,
 inline int grid1d(size_t total) {
   size_t b = (total + 255) / 256;
   return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+}
+
+// the launches of this file's own kernels, shared by the engines and the srad_op_drn_* entries (tests)
+inline void launch_bicubic_submean(const float* x, float* y, int B, int C, int H, int W, int scale, const float* mw, const float* mb,
+                                   float* raw, hipStream_t s) {
+  const size_t tot = (size_t)B * H * scale * W * scale;
+  hipLaunchKernelGGL(bicubic_submean_kernel, dim3(grid1d(tot)), dim3(256), 0, s, x, y, B, C, H, W, scale, mw, mb, raw);
+}
+
+inline void launch_affine_to_nchw(const float* x, int ldx, float* y, int B, int C, int HW, const float* mw, const float* mb, hipStream_t s) {
+  hipLaunchKernelGGL(affine_to_nchw_kernel, dim3(grid1d((size_t)B * HW)), dim3(256), 0, s, x, ldx, y, B, C, HW, mw, mb);
+}
+
+inline void launch_pool_dot(bool r_h, const float* g, const float* r, float* part, int B, int hw, int C, int nchunk, hipStream_t s) {
+  if (r_h) hipLaunchKernelGGL(pool_dot_kernel<true>, dim3(nchunk, B), dim3(256), 0, s, g, r, part, hw, C, nchunk);
+  else hipLaunchKernelGGL(pool_dot_kernel<false>, dim3(nchunk, B), dim3(256), 0, s, g, r, part, hw, C, nchunk);
 }
 
 struct RcabW {
@@ -401,8 +422,9 @@ struct srad_drn {
 
 namespace {
 
-GemmParams conv_params(const srad_drn* h, const ConvW& c, const float* X, int ldx, int B, int Hi, int Wi, int stride,
-                       float* Y, int ldy, int yoff) {
+// a layer of c.n x c.cin x c.ntaps on the packed weight Wp (srad_op_conv_pool brings its own pack)
+GemmParams conv_params_on(const void* Wp, const float* bias, const ConvW& c, const float* X, int ldx, int B, int Hi, int Wi, int stride,
+                          float* Y, int ldy, int yoff) {
   GemmParams p{};
   const int pad = c.ntaps == 9 ? 1 : 0, k = c.ntaps == 9 ? 3 : 1;
   p.Hi = Hi; p.Wi = Wi;
@@ -411,12 +433,17 @@ GemmParams conv_params(const srad_drn* h, const ConvW& c, const float* X, int ld
   p.stride = stride;
   p.X = X; p.ldx = ldx; p.M = B * p.Ho * p.Wo; p.Cin = c.cin; p.Cp = srad_cp(c.cin); p.ntaps = c.ntaps;
   p.ln_g = p.ln_b = nullptr; p.ln_eps = 1e-5f;
-  p.Wp = h->pt.ptr(c.w); p.N = c.n; p.bias = h->pt.fptr(c.b);
+  p.Wp = Wp; p.N = c.n; p.bias = bias;
   p.act = SRAD_ACT_NONE; p.slope = 0.f; p.alpha = 1.f;
   p.R = nullptr; p.ldr = 0;
   p.Y = Y; p.ldy = ldy; p.yoff = yoff; p.ps = 0;
   p.hsplit_hd = 0; p.hsplit_hdp = 0;
   return p;
+}
+
+GemmParams conv_params(const srad_drn* h, const ConvW& c, const float* X, int ldx, int B, int Hi, int Wi, int stride,
+                       float* Y, int ldy, int yoff) {
+  return conv_params_on(h->pt.ptr(c.w), h->pt.fptr(c.b), c, X, ldx, B, Hi, Wi, stride, Y, ldy, yoff);
 }
 
 // One RCAB's tensors: relu(conv), the conv result, the block output, and (training) the gate and the pooled sums
@@ -514,8 +541,7 @@ int forward_walk(srad_drn* h, const float* x, int B, int H, int W, float* const*
   {
     const size_t tot = (size_t)B * H0 * W0;
     SradProfScope prof(s, SRAD_K_MISC, 40.0 * tot * C, 4.0 * tot * (4 + C));
-    hipLaunchKernelGGL(bicubic_submean_kernel, dim3(grid1d(tot)), dim3(256), 0, s, x, w.up0, B, C, H, W, sc,
-                       h->pt.fptr(h->sub_w), h->pt.fptr(h->sub_b), w.uraw);
+    launch_bicubic_submean(x, w.up0, B, C, H, W, sc, h->pt.fptr(h->sub_w), h->pt.fptr(h->sub_b), w.uraw, s);
     SRAD_CHECK_HIP(hipGetLastError());
   }
   // head -> copies[0], stored in cat[0][:, F:2F]               (drn.py:247, 252)
@@ -542,8 +568,7 @@ int forward_walk(srad_drn* h, const float* x, int B, int H, int W, float* const*
     SRAD_TRY(srad_launch_gemm(prec, p, s));
     const size_t tot = (size_t)B * Hh * Ww;
     SradProfScope prof(s, SRAD_K_LAYOUT, 2.0 * tot * C * C, 8.0 * tot * C);
-    hipLaunchKernelGGL(affine_to_nchw_kernel, dim3(grid1d(tot)), dim3(256), 0, s, w.timg[j], w.ld_timg, ys[j], B, C, Hh * Ww,
-                       h->pt.fptr(h->add_w), h->pt.fptr(h->add_b));
+    launch_affine_to_nchw(w.timg[j], w.ld_timg, ys[j], B, C, Hh * Ww, h->pt.fptr(h->add_w), h->pt.fptr(h->add_b), s);
     SRAD_CHECK_HIP(hipGetLastError());
     return SRAD_OK;
   };
@@ -584,8 +609,7 @@ int forward_walk(srad_drn* h, const float* x, int B, int H, int W, float* const*
       if (nchunk == 0) {  // global average pool (partial rows) as a pass of its own                          (drn.py:127-138)
         nchunk = DRN_POOL_CHUNKS;
         SradProfScope prof(s, SRAD_K_MISC, 1.0 * T * ch + 4.0 * B * ch * (ch / 16), 4.0 * T * ch);
-        hipLaunchKernelGGL(pool_dot_kernel<false>, dim3(DRN_POOL_CHUNKS, B), dim3(256), 0, s, (const float*)nullptr, sv.r, w.pool, Hl * Wl, ch,
-                           DRN_POOL_CHUNKS);
+        launch_pool_dot(false, nullptr, sv.r, w.pool, B, Hl * Wl, ch, DRN_POOL_CHUNKS, s);
       }
       const bool y_h = st.r && b + 1 < c.n_blocks;   // the next block's conv80 reads it (same shape: supported there too)
       {  // the gate, and res = body(x) * gate + x               (drn.py:128-139, 156-157)
@@ -1138,6 +1162,37 @@ __global__ __launch_bounds__(256) void affine_bwd_kernel(const float* __restrict
   }
 }
 
+// ca_apply_bwd_kernel's instance for dr's storage and the slice size (as launch_ca_scale_add)
+template <class... A>
+inline void launch_ca_apply_bwd(bool dr_h, int slices, int B, int hw, int C, hipStream_t s, A... args) {
+  const int ni = ca_ni(hw, slices, C);
+  const dim3 grid(slices, B);
+  auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, args...); };
+  if (dr_h) { if (ni == 5) launch(ca_apply_bwd_kernel<true, 5>); else if (ni == 10) launch(ca_apply_bwd_kernel<true, 10>); else launch(ca_apply_bwd_kernel<true, 0>); }
+  else { if (ni == 5) launch(ca_apply_bwd_kernel<false, 5>); else if (ni == 10) launch(ca_apply_bwd_kernel<false, 10>); else launch(ca_apply_bwd_kernel<false, 0>); }
+}
+
+inline void launch_ca_bwd(const float* part, int nchunk, const float* pool, const float* gate, float inv_hw, int B, int C, int Cr,
+                          const float* w1, const float* b1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dpool,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(ca_bwd_kernel, dim3(1), dim3(256), 0, s, part, nchunk, pool, gate, inv_hw, B, C, Cr, w1, b1, w2, dw1, db1, dw2, db2, dpool);
+}
+
+inline void launch_affine_bwd(const float* dy_nchw, const float* dy_rows, const float* t, int ldt, float* dt, int B, int C, int HW,
+                              const float* w, float* dw, float* db, hipStream_t s) {
+  const int g = grid1d((size_t)B * HW);
+  hipLaunchKernelGGL(affine_bwd_kernel, dim3(g > 256 ? 256 : g), dim3(256), 0, s, dy_nchw, dy_rows, t, ldt, dt, B, C, HW, w, dw, db);
+}
+
+inline void launch_zero_upsample(const float* dy, float* z, int B, int Ho, int Wo, int C, hipStream_t s) {
+  const size_t tot = (size_t)B * 2 * Ho * 2 * Wo * (C / 4);
+  hipLaunchKernelGGL(zero_upsample_kernel, dim3(grid1d(tot)), dim3(256), 0, s, dy, z, B, Ho, Wo, C);
+}
+
+inline void launch_add_cols(const float* src, int ld_src, float* dst, int ld_dst, size_t rows, int C, hipStream_t s) {
+  hipLaunchKernelGGL(add_cols_kernel, dim3(grid1d(rows * C / 4)), dim3(256), 0, s, src, ld_src, dst, ld_dst, rows, C);
+}
+
 struct DrnTrainWs : DrnFwdWs {   // the forward's tensors, then the backward's
   float *gdeep, *ga, *gb, *dr2[2], *dt2[2], *dups, *dus, *ddtmp, *zup, *dtimg, *dup0, *ppart2[2], *dpool2[2];   // dr / dt / pool_dot rows double-buffered (two streams)
   std::vector<float*> gcat;
@@ -1334,10 +1389,8 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
     const float* X = j == 0 ? w.deep : w.cat[lvl_in];
     float* GX = j == 0 ? w.gdeep : w.gcat[lvl_in];
     const int ld = j == 0 ? top : 2 * fw(lvl_in);
-    const size_t tot = (size_t)B * Hh * Ww;
-    hipLaunchKernelGGL(affine_bwd_kernel, dim3(grid1d(tot) > 256 ? 256 : grid1d(tot)), dim3(256), 0, s, dys[j], (const float*)nullptr,
-                       w.timg[j], SRAD_IMG_CPAD, w.dtimg, B, C, Hh * Ww, h->pt.fptr(h->add_w), G + h->ts.flat_off[h->add_w],
-                       G + h->ts.flat_off[h->add_b]);
+    launch_affine_bwd(dys[j], nullptr, w.timg[j], SRAD_IMG_CPAD, w.dtimg, B, C, Hh * Ww, h->pt.fptr(h->add_w), G + h->ts.flat_off[h->add_w],
+                      G + h->ts.flat_off[h->add_b], s);
     SRAD_CHECK_HIP(hipGetLastError());
     WgradParams g = drn_wgrad(h, h->tail[j], G, w.dtimg, SRAD_IMG_CPAD, 0, X, ld, B, Hh, Ww, 1);
     SRAD_TRY(srad_launch_wgrad(prec, g, wq, s));
@@ -1399,20 +1452,10 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
       float* dt = w.dt2[set];
       const bool x_h = lh && b > 0;                            // this block's input is the previous block's bf16 output
       float* const pp = w.ppart2[set];
-      if (lh) hipLaunchKernelGGL(pool_dot_kernel<true>, dim3(DRN_POOL_CHUNKS, B), dim3(256), 0, s, ga, sv.r, pp, Hl * Wl, ch, DRN_POOL_CHUNKS);
-      else hipLaunchKernelGGL(pool_dot_kernel<false>, dim3(DRN_POOL_CHUNKS, B), dim3(256), 0, s, ga, sv.r, pp, Hl * Wl, ch, DRN_POOL_CHUNKS);
-      {
-        const int slices = ca_slices(Hl * Wl);
-        const int items = ((Hl * Wl + slices - 1) / slices) * (ch / 4);
-        const int ni = items > 2560 ? 0 : (items <= 1280 ? 5 : 10);
-        const dim3 grid(slices, B);
-        auto launch = [&](auto kern) {
-          hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, ga, sv.gate, pp, DRN_POOL_CHUNKS, sv.pool, 1.0f / (float)(Hl * Wl), ch, ch / 16,
-                             h->pt.fptr(r.w1), h->pt.fptr(r.b1), h->pt.fptr(r.w2), dr, Hl * Wl);
-        };
-        if (lh) { if (ni == 5) launch(ca_apply_bwd_kernel<true, 5>); else if (ni == 10) launch(ca_apply_bwd_kernel<true, 10>); else launch(ca_apply_bwd_kernel<true, 0>); }
-        else { if (ni == 5) launch(ca_apply_bwd_kernel<false, 5>); else if (ni == 10) launch(ca_apply_bwd_kernel<false, 10>); else launch(ca_apply_bwd_kernel<false, 0>); }
-      }
+      launch_pool_dot(lh, ga, sv.r, pp, B, Hl * Wl, ch, DRN_POOL_CHUNKS, s);
+      launch_ca_apply_bwd(lh, ca_slices(Hl * Wl), B, Hl * Wl, ch, s, (const float*)ga, (const float*)sv.gate, (const float*)pp, DRN_POOL_CHUNKS,
+                          (const float*)sv.pool, 1.0f / (float)(Hl * Wl), ch, ch / 16, (const float*)h->pt.fptr(r.w1), (const float*)h->pt.fptr(r.b1),
+                          (const float*)h->pt.fptr(r.w2), dr, Hl * Wl);
       SRAD_CHECK_HIP(hipGetLastError());
       {
         GemmParams p = drn_dgrad(h, r.c1, dr, ch, B, Hl, Wl, dt, ch, 0);
@@ -1431,9 +1474,9 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
       SRAD_TRY(bs.side_waits_main());
       SRAD_TRY(srad_wgrad_rebind(wq, "drn_backward", wq_base + (size_t)set * wq_half, wq_half));
       // the channel attention's weight / bias gradients (one workgroup, all images): nothing on the data path waits for them
-      hipLaunchKernelGGL(ca_bwd_kernel, dim3(1), dim3(256), 0, side, pp, DRN_POOL_CHUNKS, sv.pool, sv.gate, 1.0f / (float)(Hl * Wl), B,
-                         ch, ch / 16, h->pt.fptr(r.w1), h->pt.fptr(r.b1), h->pt.fptr(r.w2), G + h->ts.flat_off[r.w1],
-                         G + h->ts.flat_off[r.b1], G + h->ts.flat_off[r.w2], G + h->ts.flat_off[r.b2], w.dpool2[set]);
+      launch_ca_bwd(pp, DRN_POOL_CHUNKS, sv.pool, sv.gate, 1.0f / (float)(Hl * Wl), B, ch, ch / 16, h->pt.fptr(r.w1), h->pt.fptr(r.b1),
+                    h->pt.fptr(r.w2), G + h->ts.flat_off[r.w1], G + h->ts.flat_off[r.b1], G + h->ts.flat_off[r.w2], G + h->ts.flat_off[r.b2],
+                    w.dpool2[set], side);
       SRAD_CHECK_HIP(hipGetLastError());
       {
         WgradParams g = drn_wgrad(h, r.c1, G, dr, ch, 0, sv.t, ch, B, Hl, Wl, 1);
@@ -1460,7 +1503,7 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
     SRAD_TRY(srad_wgrad_rebind(wq, "drn_backward", wq_base, 2 * wq_half));
     // gradient of the chain's input: deep (idx 0) or the concat buffer of this level
     float* GX = idx == 0 ? w.gdeep : w.gcat[lvl];
-    hipLaunchKernelGGL(add_cols_kernel, dim3(grid1d(T * ch / 4)), dim3(256), 0, s, ga, ch, GX, ch, T, ch);
+    launch_add_cols(ga, ch, GX, ch, T, ch, s);
     SRAD_CHECK_HIP(hipGetLastError());
     if (on_bucket) on_bucket(user, P - idx);
   }
@@ -1480,8 +1523,7 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
     {
       WgradParams g = drn_wgrad(h, h->down_s2[L], G, w.ddtmp, f, 0, w.cat[L] + f, 2 * f, B, Hl, Wl, 2);
       SRAD_TRY(srad_launch_wgrad(prec, g, wq, s));
-      const size_t tot = (size_t)B * Hl * Wl * f / 4;
-      hipLaunchKernelGGL(zero_upsample_kernel, dim3(grid1d(tot)), dim3(256), 0, s, w.ddtmp, w.zup, B, Hl / 2, Wl / 2, f);
+      launch_zero_upsample(w.ddtmp, w.zup, B, Hl / 2, Wl / 2, f, s);
       SRAD_CHECK_HIP(hipGetLastError());
       GemmParams p = drn_dgrad(h, h->down_s2[L], w.zup, f, B, Hl, Wl, w.gcat[L], 2 * f, f);
       accumulate_into(p);
@@ -1495,10 +1537,8 @@ int srad_drn_backward(srad_drn_t* h, const float* const* dys, int n_out, int B, 
     SRAD_TRY(srad_launch_wgrad(prec, g, wq, s));
     GemmParams p = drn_dgrad(h, h->head, w.gcat[0] + F0, 2 * F0, B, H0, W0, w.dup0, SRAD_IMG_CPAD, 0);
     SRAD_TRY(srad_launch_gemm(prec, p, s));
-    const size_t tot = (size_t)B * H0 * W0;
-    hipLaunchKernelGGL(affine_bwd_kernel, dim3(grid1d(tot) > 256 ? 256 : grid1d(tot)), dim3(256), 0, s, (const float*)nullptr, w.dup0,
-                       w.uraw, SRAD_IMG_CPAD, (float*)nullptr, B, C, H0 * W0, h->pt.fptr(h->sub_w), G + h->ts.flat_off[h->sub_w],
-                       G + h->ts.flat_off[h->sub_b]);
+    launch_affine_bwd(nullptr, w.dup0, w.uraw, SRAD_IMG_CPAD, nullptr, B, C, H0 * W0, h->pt.fptr(h->sub_w), G + h->ts.flat_off[h->sub_w],
+                      G + h->ts.flat_off[h->sub_b], s);
     SRAD_CHECK_HIP(hipGetLastError());
   }
   SRAD_TRY(srad_wgrad_flush(wq, s));
@@ -1572,8 +1612,7 @@ int srad_dual_backward(const float* w0, const float* w1, int C, int n_feats, flo
     g.n_real = n_feats; g.cin_real = C; g.Hi = H; g.Wi = W; g.Ho = H2; g.Wo = W2; g.stride = 2; g.alpha = 1.f; g.dW = dw0;
     SRAD_TRY(srad_launch_wgrad(precision, g, wq, s));
     if (dx) {
-      const size_t tot = T * Fh / 4;
-      hipLaunchKernelGGL(zero_upsample_kernel, dim3(grid1d(tot)), dim3(256), 0, s, dmid, zup, B, H2, W2, Fh);
+      launch_zero_upsample(dmid, zup, B, H2, W2, Fh, s);
       SRAD_CHECK_HIP(hipGetLastError());
       GemmParams p{};
       p.Hi = p.Ho = H; p.Wi = p.Wo = W; p.stride = 1; p.X = zup; p.ldx = Fh; p.M = (int)T; p.Cin = Fh; p.Cp = srad_cp(Fh);
@@ -1583,6 +1622,158 @@ int srad_dual_backward(const float* w0, const float* w1, int C, int n_feats, flo
     }
   }
   return srad_wgrad_flush(wq, s);
+}
+
+}  // extern "C"
+
+// =====================================================================================================
+// Operator-level entries (include/srad.h, srad_op_drn_*): each kernel of this file on its own, through the launcher the
+// engines call, so that a test sees the engines' own grid, slice count, NI and storage instance.
+// =====================================================================================================
+namespace {
+
+int drn_op_ca_shape(const char* what, int B, int hw, int C, int nchunk) {
+  SRAD_REQUIRE(B > 0 && B <= 65535 && hw > 0, "%s: bad batch %d or image size %d", what, B, hw);
+  SRAD_REQUIRE(C % 4 == 0 && C >= 16 && C <= 512, "%s: C must be a multiple of 4 in 16 .. 512 (got %d)", what, C);
+  SRAD_REQUIRE(nchunk >= 1 && nchunk <= DRN_POOL_MAXCHUNKS, "%s: nchunk must be in 1 .. %d (got %d)", what, DRN_POOL_MAXCHUNKS, nchunk);
+  SRAD_REQUIRE((double)hw * (C / 4) < 2147483648.0, "%s: an image of %d pixels x %d channels is beyond the 32-bit item index", what, hw, C);
+  return SRAD_OK;
+}
+inline bool al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int srad_drn_ca_plan(int hw, int C, int* slices, int* ni) {
+  SRAD_REQUIRE(slices && ni, "drn_ca_plan: null argument");
+  SRAD_TRY(drn_op_ca_shape("drn_ca_plan", 1, hw, C, 1));
+  *slices = ca_slices(hw);
+  *ni = ca_ni(hw, *slices, C);
+  return SRAD_OK;
+}
+
+int srad_op_drn_bicubic(const float* x, int B, int C, int H, int W, int scale, const float* mw, const float* mb, float* y, float* raw,
+                        void* stream) {
+  SRAD_REQUIRE(x && mw && mb && y, "op_drn_bicubic: null argument");
+  SRAD_REQUIRE((C == 1 || C == 3) && B > 0 && H > 0 && W > 0 && scale >= 1, "op_drn_bicubic: needs 1 or 3 channels and a non-empty image");
+  SRAD_REQUIRE((double)B * H * scale * W * scale < 2147483648.0, "op_drn_bicubic: output too large");
+  SRAD_REQUIRE(al(y, 16) && al(raw, 16), "op_drn_bicubic: outputs must be 16-byte aligned");
+  launch_bicubic_submean(x, y, B, C, H, W, scale, mw, mb, raw, reinterpret_cast<hipStream_t>(stream));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_op_drn_affine_to_nchw(const float* x, int ldx, int B, int C, int HW, const float* mw, const float* mb, float* y, void* stream) {
+  SRAD_REQUIRE(x && mw && mb && y, "op_drn_affine_to_nchw: null argument");
+  SRAD_REQUIRE((C == 1 || C == 3) && B > 0 && HW > 0 && ldx >= C, "op_drn_affine_to_nchw: needs 1 or 3 channels, ldx >= C and a non-empty image");
+  launch_affine_to_nchw(x, ldx, y, B, C, HW, mw, mb, reinterpret_cast<hipStream_t>(stream));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_op_drn_pool_dot(const float* g, const void* r, int r_bf16, int B, int hw, int C, int nchunk, float* part, void* stream) {
+  SRAD_REQUIRE(r && part, "op_drn_pool_dot: null argument");
+  SRAD_TRY(drn_op_ca_shape("op_drn_pool_dot", B, hw, C, nchunk));
+  SRAD_REQUIRE(al(g, 16) && al(r, r_bf16 ? 8 : 16) && al(part, 16), "op_drn_pool_dot: misaligned argument");
+  launch_pool_dot(r_bf16 != 0, g, reinterpret_cast<const float*>(r), part, B, hw, C, nchunk, reinterpret_cast<hipStream_t>(stream));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_op_drn_ca_scale_add(const float* part, int nchunk, int B, int hw, int C, const float* w1, const float* b1, const float* w2,
+                             const float* b2, const void* r, int r_bf16, const void* x, int x_bf16, int ldx, void* y, int y_bf16,
+                             float* gate_out, float* pool_out, void* stream) {
+  SRAD_REQUIRE(part && w1 && b1 && w2 && b2 && r && x && y, "op_drn_ca_scale_add: null argument");
+  SRAD_TRY(drn_op_ca_shape("op_drn_ca_scale_add", B, hw, C, nchunk));
+  SRAD_REQUIRE(r_bf16 || (!x_bf16 && !y_bf16), "op_drn_ca_scale_add: bf16 x or y storage exists only with a bf16 r");
+  SRAD_REQUIRE(ldx >= C && ldx % 4 == 0, "op_drn_ca_scale_add: ldx must be a multiple of 4 and >= C (got %d)", ldx);
+  SRAD_REQUIRE(al(part, 16) && al(r, r_bf16 ? 8 : 16) && al(x, x_bf16 ? 8 : 16) && al(y, y_bf16 ? 8 : 16), "op_drn_ca_scale_add: misaligned argument");
+  launch_ca_scale_add(r_bf16 != 0, x_bf16 != 0, y_bf16 != 0, ca_slices(hw), B, hw, C, reinterpret_cast<hipStream_t>(stream), part, nchunk,
+                      1.0f / (float)hw, C, C / 16, w1, b1, w2, b2, gate_out, pool_out, reinterpret_cast<const float*>(r),
+                      reinterpret_cast<const float*>(x), ldx, reinterpret_cast<float*>(y), hw);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_op_drn_ca_apply_bwd(const float* g, const float* gate, const float* part, int nchunk, const float* pool, int B, int hw, int C,
+                             const float* w1, const float* b1, const float* w2, void* dr, int dr_bf16, void* stream) {
+  SRAD_REQUIRE(g && gate && part && pool && w1 && b1 && w2 && dr, "op_drn_ca_apply_bwd: null argument");
+  SRAD_TRY(drn_op_ca_shape("op_drn_ca_apply_bwd", B, hw, C, nchunk));
+  SRAD_REQUIRE(al(g, 16) && al(part, 16) && al(dr, dr_bf16 ? 8 : 16), "op_drn_ca_apply_bwd: misaligned argument");
+  launch_ca_apply_bwd(dr_bf16 != 0, ca_slices(hw), B, hw, C, reinterpret_cast<hipStream_t>(stream), g, gate, part, nchunk, pool,
+                      1.0f / (float)hw, C, C / 16, w1, b1, w2, reinterpret_cast<float*>(dr), hw);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_op_drn_ca_bwd(const float* part, int nchunk, const float* pool, const float* gate, int B, int hw, int C, const float* w1,
+                       const float* b1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dpool, void* stream) {
+  SRAD_REQUIRE(part && pool && gate && w1 && b1 && w2 && dw1 && db1 && dw2 && db2 && dpool, "op_drn_ca_bwd: null argument");
+  SRAD_TRY(drn_op_ca_shape("op_drn_ca_bwd", B, hw, C, nchunk));
+  SRAD_REQUIRE(C * (C / 16) <= 4096, "op_drn_ca_bwd: C * C/16 = %d weights do not fit the kernel's staging (4096)", C * (C / 16));
+  SRAD_REQUIRE(al(part, 16) && al(pool, 16) && al(gate, 16), "op_drn_ca_bwd: misaligned argument");
+  launch_ca_bwd(part, nchunk, pool, gate, 1.0f / (float)hw, B, C, C / 16, w1, b1, w2, dw1, db1, dw2, db2, dpool,
+                reinterpret_cast<hipStream_t>(stream));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_op_drn_affine_bwd(const float* dy_nchw, const float* dy_rows, const float* t, int ldt, float* dt, int B, int C, int HW,
+                           const float* w, float* dw, float* db, void* stream) {
+  SRAD_REQUIRE((dy_nchw != nullptr) != (dy_rows != nullptr) && t && w && dw && db, "op_drn_affine_bwd: null argument (dy in exactly one layout)");
+  SRAD_REQUIRE((C == 1 || C == 3) && B > 0 && HW > 0 && ldt >= C, "op_drn_affine_bwd: needs 1 or 3 channels, ldt >= C and a non-empty image");
+  SRAD_REQUIRE(al(dt, 16), "op_drn_affine_bwd: dt must be 16-byte aligned");
+  launch_affine_bwd(dy_nchw, dy_rows, t, ldt, dt, B, C, HW, w, dw, db, reinterpret_cast<hipStream_t>(stream));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_op_drn_zero_upsample(const float* dy, float* z, int B, int Ho, int Wo, int C, void* stream) {
+  SRAD_REQUIRE(dy && z, "op_drn_zero_upsample: null argument");
+  SRAD_REQUIRE(B > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 4 == 0, "op_drn_zero_upsample: needs a non-empty image and C %% 4 == 0 (got %d)", C);
+  SRAD_REQUIRE(al(dy, 16) && al(z, 16), "op_drn_zero_upsample: misaligned argument");
+  launch_zero_upsample(dy, z, B, Ho, Wo, C, reinterpret_cast<hipStream_t>(stream));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_op_drn_add_cols(const float* src, int ld_src, float* dst, int ld_dst, int64_t rows, int C, void* stream) {
+  SRAD_REQUIRE(src && dst, "op_drn_add_cols: null argument");
+  SRAD_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && ld_src % 4 == 0 && ld_dst % 4 == 0 && ld_src >= C && ld_dst >= C,
+               "op_drn_add_cols: C and the row strides must be multiples of 4, strides >= C");
+  SRAD_REQUIRE(al(src, 16) && al(dst, 16), "op_drn_add_cols: misaligned argument");
+  launch_add_cols(src, ld_src, dst, ld_dst, (size_t)rows, C, reinterpret_cast<hipStream_t>(stream));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+// One C -> C 3x3 convolution with bias, set up as forward_walk sets up an RCAB's second conv: fp32 rows in and out, and the global
+// average pool's partial rows from the conv's epilogue where pool_rows_per_image allows them.  *rows = partial rows per image
+// (pool_part [B][rows][C] is then written), or 0 (pool_part untouched: the engine runs pool_dot_kernel there).  Without x, w and y
+// it only answers *rows for the shape.
+int srad_op_conv_pool(int precision, const float* x, const float* w, const float* bias, int B, int H, int W, int C, float* y,
+                      float* pool_part, int* rows, void* scratch, size_t scratch_bytes, void* stream) {
+  SRAD_REQUIRE(rows, "op_conv_pool: null argument");
+  SRAD_REQUIRE(precision == SRAD_PREC_F32 || precision == SRAD_PREC_BF16 || precision == SRAD_PREC_BF16X3, "op_conv_pool: bad precision %d", precision);
+  SRAD_REQUIRE(B > 0 && H > 0 && W > 0 && C % 4 == 0 && C >= 16 && C <= 512, "op_conv_pool: needs a non-empty image and C a multiple of 4 in 16 .. 512");
+  SRAD_REQUIRE((double)B * H * W * C * 4.0 < 3.9e9, "op_conv_pool: problem too large for the 32-bit offsets of the conv kernel");
+  ConvW c;
+  c.n = C; c.cin = C; c.ntaps = 9;
+  const bool query = !x && !w && !y;
+  if (!query) {
+    SRAD_REQUIRE(x && w && bias && y && pool_part && scratch, "op_conv_pool: null argument");
+    const size_t need = srad_packed_bytes(precision, C, C, 9);
+    SRAD_REQUIRE(scratch_bytes >= need && al(scratch, 256), "op_conv_pool: scratch %zu bytes, %zu needed (256-byte aligned)", scratch_bytes, need);
+  }
+  GemmParams p = conv_params_on(query ? nullptr : scratch, bias, c, x, C, B, H, W, 1, y, C, 0);
+  const int n = pool_rows_per_image(precision, p, H * W);
+  *rows = n;
+  if (query) return SRAD_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  SRAD_TRY(srad_launch_pack_weight(precision, w, scratch, C, C, 9, s));
+  if (n > 0) p.pool_part = pool_part;
+  return srad_launch_gemm(precision, p, s);
 }
 
 }  // extern "C"

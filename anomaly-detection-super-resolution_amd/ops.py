@@ -586,3 +586,193 @@ def ensemble_mean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     out = torch.empty(n // 4, Cc, H, W, dtype=torch.float32, device=a.device)
     L.check(L.lib().srad_ensemble_mean(L.dptr(a), L.dptr(b), n // 4, Cc, H, W, L.dptr(out), L.current_stream_ptr()), "ensemble_mean")
     return out
+
+
+# ----------------------------------------------------------------------------------- DRN's own kernels, one by one
+# (C ABI ``srad_op_drn_*``, csrc/drn.hip).  Every call goes through the launcher the engines use, so grid, slices per image,
+# NI and storage instance are the engines' own.  ``out=`` tensors let a test place an output inside a guarded allocation.
+def _out(out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.is_contiguous() and out.is_cuda, (out.shape, shape, out.dtype)
+    return out
+
+
+def _rows(t: torch.Tensor, what: str) -> torch.Tensor:
+    assert t.dim() == 2 and t.is_contiguous() and t.dtype in (torch.float32, torch.bfloat16), what
+    return t
+
+
+def drn_ca_plan(hw: int, C_: int) -> tuple:
+    """(slices per image, NI) the streaming channel-attention kernels get for an image of ``hw`` pixels and ``C_`` channels
+    (``srad_drn_ca_plan``; host only)."""
+    sl, ni = C.c_int(), C.c_int()
+    L.check(L.lib().srad_drn_ca_plan(hw, C_, C.byref(sl), C.byref(ni)), "drn_ca_plan")
+    return sl.value, ni.value
+
+
+def drn_bicubic(x: torch.Tensor, scale: int, mw: torch.Tensor, mb: torch.Tensor, *, raw: bool = False,
+                out: Optional[torch.Tensor] = None, raw_out: Optional[torch.Tensor] = None):
+    """x [B, C, H, W] (C = 1 | 3) -> bicubic x ``scale`` + sub_mean as NHWC[4] rows [B*Hs*Ws, 4]; with ``raw`` also the
+    upsampled image before sub_mean, same layout."""
+    _need_cuda(x, mw, mb)
+    assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
+    B, Cc, H, W = x.shape
+    T = B * H * scale * W * scale
+    y = _out(out, (T, 4), torch.float32, x.device)
+    r = _out(raw_out, (T, 4), torch.float32, x.device) if raw or raw_out is not None else None
+    L.check(L.lib().srad_op_drn_bicubic(L.dptr(x), B, Cc, H, W, scale, L.dptr(mw.contiguous()), L.dptr(mb.contiguous()), L.dptr(y),
+                                        L.dptr(r), L.current_stream_ptr()), "op_drn_bicubic")
+    return (y, r) if r is not None else y
+
+
+def drn_affine_to_nchw(x: torch.Tensor, B: int, Cc: int, mw: torch.Tensor, mb: torch.Tensor, *,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """add_mean + NHWC -> NCHW: x [B*HW, ld] rows (columns [0, Cc)) -> [B, Cc, HW]."""
+    _need_cuda(x, mw, mb)
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and x.shape[0] % B == 0
+    HW = x.shape[0] // B
+    y = _out(out, (B, Cc, HW), torch.float32, x.device)
+    L.check(L.lib().srad_op_drn_affine_to_nchw(L.dptr(x), x.stride(0), B, Cc, HW, L.dptr(mw.contiguous()), L.dptr(mb.contiguous()),
+                                               L.dptr(y), L.current_stream_ptr()), "op_drn_affine_to_nchw")
+    return y
+
+
+def drn_pool_dot(r: torch.Tensor, B: int, *, g: Optional[torch.Tensor] = None, nchunk: int = 32,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """part [B, nchunk, C]: per-chunk column sums of r [B*hw, C] (fp32 or bf16), times g (fp32) when given."""
+    _need_cuda(r, g)
+    _rows(r, "r")
+    hw, Cc = r.shape[0] // B, r.shape[1]
+    assert r.shape[0] == B * hw and (g is None or (g.shape == r.shape and g.dtype == torch.float32 and g.is_contiguous()))
+    part = _out(out, (B, nchunk, Cc), torch.float32, r.device)
+    L.check(L.lib().srad_op_drn_pool_dot(L.dptr(g), L.dptr(r), int(r.dtype == torch.bfloat16), B, hw, Cc, nchunk, L.dptr(part),
+                                         L.current_stream_ptr()), "op_drn_pool_dot")
+    return part
+
+
+def drn_ca_scale_add(part: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, r: torch.Tensor,
+                     x: torch.Tensor, *, y_bf16: bool = False, keep: bool = True, out: Optional[torch.Tensor] = None,
+                     gate_out: Optional[torch.Tensor] = None, pool_out: Optional[torch.Tensor] = None):
+    """The RCAB tail: y = r * gate + x with gate = sigmoid(w2 relu(w1 mean + b1) + b2), mean = part.sum(1) / hw.  part
+    [B, nchunk, C] fp32; r [B*hw, C] and x [B*hw, >= C] (row stride x.stride(0)) fp32 or bf16 - the storage combination picks
+    the kernel instance; ``keep``: also return the gate and the pooled sums [B, C] (training keeps them).
+    Returns y, or (y, gate, pool)."""
+    _need_cuda(part, w1, b1, w2, b2, r, x)
+    _rows(r, "r")
+    B, nchunk, Cc = part.shape
+    hw = r.shape[0] // B
+    assert part.is_contiguous() and part.dtype == torch.float32 and r.shape == (B * hw, Cc)
+    assert x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == B * hw and x.shape[1] >= Cc and x.dtype in (torch.float32, torch.bfloat16)
+    y = _out(out, (B * hw, Cc), torch.bfloat16 if y_bf16 else torch.float32, r.device)
+    gate = _out(gate_out, (B, Cc), torch.float32, r.device) if keep else None
+    pool = _out(pool_out, (B, Cc), torch.float32, r.device) if keep else None
+    L.check(L.lib().srad_op_drn_ca_scale_add(L.dptr(part), nchunk, B, hw, Cc, L.dptr(w1.contiguous()), L.dptr(b1.contiguous()),
+                                             L.dptr(w2.contiguous()), L.dptr(b2.contiguous()), L.dptr(r), int(r.dtype == torch.bfloat16),
+                                             L.dptr(x), int(x.dtype == torch.bfloat16), x.stride(0), L.dptr(y), int(y_bf16),
+                                             L.dptr(gate), L.dptr(pool), L.current_stream_ptr()), "op_drn_ca_scale_add")
+    return (y, gate, pool) if keep else y
+
+
+def drn_ca_apply_bwd(g: torch.Tensor, gate: torch.Tensor, part: torch.Tensor, pool: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+                     w2: torch.Tensor, *, dr_bf16: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d/dr of r * gate(mean r) + x under the upstream gradient g [B*hw, C]: part = drn_pool_dot(r, B, g=g), gate and pool as
+    drn_ca_scale_add kept them.  Returns dr [B*hw, C] fp32 or bf16."""
+    _need_cuda(g, gate, part, pool, w1, b1, w2)
+    B, nchunk, Cc = part.shape
+    hw = g.shape[0] // B
+    assert g.shape == (B * hw, Cc) and g.is_contiguous() and g.dtype == torch.float32 and part.is_contiguous()
+    assert gate.shape == pool.shape == (B, Cc) and gate.is_contiguous() and pool.is_contiguous()
+    dr = _out(out, (B * hw, Cc), torch.bfloat16 if dr_bf16 else torch.float32, g.device)
+    L.check(L.lib().srad_op_drn_ca_apply_bwd(L.dptr(g), L.dptr(gate), L.dptr(part), nchunk, L.dptr(pool), B, hw, Cc,
+                                             L.dptr(w1.contiguous()), L.dptr(b1.contiguous()), L.dptr(w2.contiguous()), L.dptr(dr),
+                                             int(dr_bf16), L.current_stream_ptr()), "op_drn_ca_apply_bwd")
+    return dr
+
+
+def drn_ca_bwd(part: torch.Tensor, pool: torch.Tensor, gate: torch.Tensor, hw: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+               dw1: torch.Tensor, db1: torch.Tensor, dw2: torch.Tensor, db2: torch.Tensor, *,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The channel attention's weight / bias gradients summed over the batch, ACCUMULATED into dw1 [Cr, C], db1 [Cr],
+    dw2 [C, Cr], db2 [C]; returns dpool [B, C] (the gradient of the pooled sums)."""
+    _need_cuda(part, pool, gate, w1, b1, w2, dw1, db1, dw2, db2)
+    B, nchunk, Cc = part.shape
+    for t in (part, pool, gate, dw1, db1, dw2, db2):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    assert dw1.shape == (Cc // 16, Cc) and dw2.shape == (Cc, Cc // 16) and db1.shape == (Cc // 16,) and db2.shape == (Cc,)
+    dpool = _out(out, (B, Cc), torch.float32, part.device)
+    L.check(L.lib().srad_op_drn_ca_bwd(L.dptr(part), nchunk, L.dptr(pool), L.dptr(gate), B, hw, Cc, L.dptr(w1.contiguous()),
+                                       L.dptr(b1.contiguous()), L.dptr(w2.contiguous()), L.dptr(dw1), L.dptr(db1), L.dptr(dw2),
+                                       L.dptr(db2), L.dptr(dpool), L.current_stream_ptr()), "op_drn_ca_bwd")
+    return dpool
+
+
+def drn_affine_bwd(dy: torch.Tensor, t: torch.Tensor, w: torch.Tensor, dw: torch.Tensor, db: torch.Tensor, *, want_dt: bool = True,
+                   out: Optional[torch.Tensor] = None):
+    """MeanShift backward.  dy [B, C, HW] (NCHW) or [T, 4] rows; t [T, ld] rows (columns [0, C)), w [C, C]; dw [C, C] and db [C]
+    are ACCUMULATED into; returns dt [T, 4] (= w^T dy, column C.. zero) or None."""
+    _need_cuda(dy, t, w, dw, db)
+    Cc = w.shape[0]
+    assert dy.is_contiguous() and dy.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and dw.is_contiguous() and db.is_contiguous()
+    nchw = dy.dim() == 3
+    if nchw:
+        B, HW = dy.shape[0], dy.shape[2]
+        assert dy.shape[1] == Cc
+    else:
+        B, HW = 1, dy.shape[0]
+        assert dy.shape[1] == 4
+    assert t.shape[0] == B * HW
+    dt = _out(out, (B * HW, 4), torch.float32, dy.device) if want_dt else None
+    L.check(L.lib().srad_op_drn_affine_bwd(L.dptr(dy) if nchw else None, None if nchw else L.dptr(dy), L.dptr(t), t.stride(0), L.dptr(dt),
+                                           B, Cc, HW, L.dptr(w.contiguous()), L.dptr(dw), L.dptr(db), L.current_stream_ptr()),
+            "op_drn_affine_bwd")
+    return dt
+
+
+def drn_zero_upsample(dy: torch.Tensor, B: int, Ho: int, Wo: int, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dy [B*Ho*Wo, C] -> [B*2Ho*2Wo, C]: dy at the even pixels, zero elsewhere (the stride-2 convolution's backward)."""
+    _need_cuda(dy)
+    assert dy.dim() == 2 and dy.is_contiguous() and dy.dtype == torch.float32 and dy.shape[0] == B * Ho * Wo
+    z = _out(out, (4 * B * Ho * Wo, dy.shape[1]), torch.float32, dy.device)
+    L.check(L.lib().srad_op_drn_zero_upsample(L.dptr(dy), L.dptr(z), B, Ho, Wo, dy.shape[1], L.current_stream_ptr()), "op_drn_zero_upsample")
+    return z
+
+
+def drn_add_cols(src: torch.Tensor, dst: torch.Tensor, Cc: int) -> torch.Tensor:
+    """dst[:, :Cc] += src[:, :Cc] in place (row strides may exceed Cc); returns dst."""
+    _need_cuda(src, dst)
+    assert src.dim() == dst.dim() == 2 and src.stride(1) == dst.stride(1) == 1 and src.shape[0] == dst.shape[0]
+    assert src.dtype == dst.dtype == torch.float32 and src.shape[1] >= Cc and dst.shape[1] >= Cc
+    L.check(L.lib().srad_op_drn_add_cols(L.dptr(src), src.stride(0), L.dptr(dst), dst.stride(0), src.shape[0], Cc, L.current_stream_ptr()),
+            "op_drn_add_cols")
+    return dst
+
+
+def conv_pool_rows(B: int, H: int, W: int, Cc: int, precision: str = "fp32") -> int:
+    """Partial rows per image the conv epilogue writes for an RCAB's second conv of this shape, 0 when it is not eligible (the
+    query form of ``srad_op_conv_pool``; host only)."""
+    rows = C.c_int(-1)
+    L.check(L.lib().srad_op_conv_pool(L.PRECISIONS[precision], None, None, None, B, H, W, Cc, None, None, C.byref(rows), None, 0, None),
+            "op_conv_pool")
+    return rows.value
+
+
+def conv_pool(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, B: int, H: int, W: int, precision: str = "fp32",
+              out: Optional[torch.Tensor] = None, part_out: Optional[torch.Tensor] = None):
+    """One C -> C 3x3 convolution with bias as DRN's forward runs an RCAB's second conv: x [B*H*W, C] fp32 rows, weight
+    [C, C, 3, 3].  Returns (y [B*H*W, C], part, rows): rows partial rows per image from the conv's epilogue in part[:, :rows]
+    (part is [B, 256, C] unless ``part_out`` is given, which must be [B, conv_pool_rows(...), C]); rows = 0: not eligible."""
+    _need_cuda(x, weight, bias)
+    Cc = weight.shape[0]
+    assert x.shape == (B * H * W, Cc) and x.is_contiguous() and x.dtype == torch.float32 and weight.shape[1] == Cc
+    w = weight.detach().reshape(Cc, Cc, 9).float().contiguous()
+    y = _out(out, (B * H * W, Cc), torch.float32, x.device)
+    want = conv_pool_rows(B, H, W, Cc, precision)
+    part = _out(part_out, (B, want if part_out is not None else 256, Cc), torch.float32, x.device)
+    prec = L.PRECISIONS[precision]
+    keep, sp, nb = L.ws_buffer(L.lib().srad_op_gemm_scratch_bytes(prec, Cc, Cc, 9), x.device)
+    rows = C.c_int(-1)
+    L.check(L.lib().srad_op_conv_pool(prec, L.dptr(x), L.dptr(w), L.dptr(bias.contiguous()), B, H, W, Cc, L.dptr(y), L.dptr(part),
+                                      C.byref(rows), sp, nb, L.current_stream_ptr()), "op_conv_pool")
+    assert rows.value == want, (rows.value, want)
+    return y, part, rows.value

@@ -539,6 +539,49 @@ int srad_op_lin_ln_bwd(int M, int K, int d, const float* dY, const float* w, con
                        const float* dres, float* out, int ld_out, int accumulate, float* dgamma, float* dbeta, void* scratch,
                        size_t scratch_bytes, void* workspace, void* stream);
 
+/* DRN's own kernels (csrc/drn.hip), one entry each, launched through the function the engines call: grid, slices per image,
+ * items held in registers (NI) and storage instance are the engines' own.  NHWC fp32 rows unless a *_bf16 flag says the array
+ * holds bf16.  The channel-attention entries take C % 4 == 0 in 16 .. 512 (Cr = C / 16 hidden units, w1 [Cr][C], w2 [C][Cr])
+ * and nchunk in 1 .. 256 partial rows per image; anything else is an error before any launch.
+ *   srad_drn_ca_plan          host only: the slices per image and NI (0 = loop, 5, 10) the two streaming CA kernels get for (hw, C)
+ *   srad_op_drn_bicubic       x [B][C][H][W] -> bicubic x scale (align_corners = False, A = -0.75) -> raw [T][4] (optional),
+ *                             then sub_mean (mw [C][C], mb [C]) -> y [T][4]; C = 1 | 3, column 3 is 0    (src/drn.py:243-246)
+ *   srad_op_drn_affine_to_nchw add_mean: x [B*HW][ldx] -> y [B][C][HW] = mw x + mb                      (src/drn.py:257,266)
+ *   srad_op_drn_pool_dot      part[b][k][c] = sum over chunk k's pixels of r (* g if given); r [B*hw][C] fp32 | bf16
+ *   srad_op_drn_ca_scale_add  y = r * sigmoid(w2 relu(w1 mean + b1) + b2) + x, mean = (sum of part's rows) / hw; storage r / x / y:
+ *                             all fp32, or r bf16 with x and y each fp32 | bf16; x rows ldx elements apart; gate_out, pool_out
+ *                             [B][C] optional                                                            (src/drn.py:123-158)
+ *   srad_op_drn_ca_apply_bwd  dr = g * gate + d(mean path): part = pool_dot(g, r) rows, pool / gate as the forward left them;
+ *                             dr fp32 | bf16
+ *   srad_op_drn_ca_bwd        the CA weight / bias gradients ACCUMULATED into dw1, db1, dw2, db2, and dpool [B][C];
+ *                             C * C/16 <= 4096
+ *   srad_op_drn_affine_bwd    MeanShift backward: dy as NCHW or as [T][4] rows (exactly one), t [T][ldt]; dt [T][4] optional;
+ *                             dw [C][C], db [C] ACCUMULATED
+ *   srad_op_drn_zero_upsample z [B][2 Ho][2 Wo][C] = dy at the even pixels, 0 elsewhere
+ *   srad_op_drn_add_cols      dst[m][0..C) += src[m][0..C)
+ *   srad_op_conv_pool         one C -> C 3x3 conv + bias as the forward's second RCAB conv, x, y [B*H*W][C] fp32, w [C][C][3][3];
+ *                             *rows = partial rows per image the conv's epilogue wrote to pool_part [B][*rows][C], or 0 when the
+ *                             shape does not take that epilogue (pool_part untouched).  x = w = y = NULL: only *rows is answered.
+ *                             scratch >= srad_op_gemm_scratch_bytes(precision, C, C, 9), 256-byte aligned */
+int srad_drn_ca_plan(int hw, int C, int* slices, int* ni);
+int srad_op_drn_bicubic(const float* x, int B, int C, int H, int W, int scale, const float* mw, const float* mb, float* y, float* raw,
+                        void* stream);
+int srad_op_drn_affine_to_nchw(const float* x, int ldx, int B, int C, int HW, const float* mw, const float* mb, float* y, void* stream);
+int srad_op_drn_pool_dot(const float* g, const void* r, int r_bf16, int B, int hw, int C, int nchunk, float* part, void* stream);
+int srad_op_drn_ca_scale_add(const float* part, int nchunk, int B, int hw, int C, const float* w1, const float* b1, const float* w2,
+                             const float* b2, const void* r, int r_bf16, const void* x, int x_bf16, int ldx, void* y, int y_bf16,
+                             float* gate_out, float* pool_out, void* stream);
+int srad_op_drn_ca_apply_bwd(const float* g, const float* gate, const float* part, int nchunk, const float* pool, int B, int hw, int C,
+                             const float* w1, const float* b1, const float* w2, void* dr, int dr_bf16, void* stream);
+int srad_op_drn_ca_bwd(const float* part, int nchunk, const float* pool, const float* gate, int B, int hw, int C, const float* w1,
+                       const float* b1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dpool, void* stream);
+int srad_op_drn_affine_bwd(const float* dy_nchw, const float* dy_rows, const float* t, int ldt, float* dt, int B, int C, int HW,
+                           const float* w, float* dw, float* db, void* stream);
+int srad_op_drn_zero_upsample(const float* dy, float* z, int B, int Ho, int Wo, int C, void* stream);
+int srad_op_drn_add_cols(const float* src, int ld_src, float* dst, int ld_dst, int64_t rows, int C, void* stream);
+int srad_op_conv_pool(int precision, const float* x, const float* w, const float* bias, int B, int H, int W, int C, float* y,
+                      float* pool_part, int* rows, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics
  * Reference paths for tests.  The library picks kernel paths from shape and precision alone; these process-wide overrides
  * (all off at load) force the path a test compares the default one against:

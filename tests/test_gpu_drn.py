@@ -104,3 +104,25 @@ def test_drn_oracle_c1_shape():
     assert [tuple(o.shape) for o in out] == [(2, 1, 32, 32), (2, 1, 64, 64)]
     for o, r in zip(out, ref):
         assert rel_err(o.cpu().numpy(), r.numpy()) < 2e-4
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16x3"])
+def test_drn_forward_with_conv_epilogue_pool_matches_oracle(prec):
+    """x4, 20 features, batch 6, 32x32 LR: the 64x64 level's 80-channel RCAB convolutions have 24576 output rows, enough for the
+    tiled GEMM's 64-row tiles, so the global average pool comes from the conv's epilogue (64 partial rows per image) and not
+    from pool_dot_kernel - which every other case of this file takes."""
+    import dataclasses
+    from oracle import sr_ref as R
+    from srad_amd import ops
+    from srad_amd import spec as S
+    cfg = dataclasses.replace(S.DRNConfig.for_scale(4, 1), n_feats=20, n_blocks=2)
+    assert ops.conv_pool_rows(6, 64, 64, 80, prec) > 0
+    sd = S.synth_state(S.drn_spec(cfg), seed=7, gain=0.5, cfg=cfg)
+    x = S.synth_image("pool_epilogue", (6, 1, 32, 32), seed=2)
+    with torch.no_grad():
+        ref = R.drn_forward(sd, torch.from_numpy(x), cfg)
+        out = build(cfg, sd, prec)(torch.from_numpy(x).cuda())
+    errs = [rel_err(o.cpu().numpy(), r.numpy()) for o, r in zip(out, ref)]
+    print("DRN with the conv-epilogue pool,", prec, "rel err per output", errs)
+    assert [tuple(o.shape) for o in out] == [(6, 1, 32, 32), (6, 1, 64, 64), (6, 1, 128, 128)]
+    assert max(errs) < 2e-4

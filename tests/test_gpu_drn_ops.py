@@ -1,0 +1,394 @@
+"""GPU: every kernel of csrc/drn.hip on its own (srad_op_drn_*, through the launchers the engines call) against plain torch in
+fp64 on the CPU, at every launch path the production shapes take: 1 / 8 / 64 / 128 slices per image, NI = 5 / 10 / the loop,
+the small and the wide gate, 1 .. 256 partial rows, the five bf16 storage instances, and the conv epilogue's pool sums.
+tests/test_drn_ops_host.py shows on the CPU that the case table reaches those paths and that the references are right.
+
+The kernel's fp32 / bf16 inputs are taken as exact.  Bars (none of them measured):
+  sums of stored fp32 values (pool_dot, conv_pool, pool_out)   |got - ref| <= n * 2^-24 * sum|v| per element, n terms
+  fp32 outputs of the chains                                   1e-5 of the reference tensor's max (test_gpu_ops.test_layernorm);
+                                                               the fp32 restatements sit at 1.8e-7 or lower (host test)
+  bf16 outputs                                                 |got - ref| <= 2^-8 |ref| + 1e-5 max|ref| per element
+Every output sits in the middle of a NaN-filled allocation whose guard elements must still be NaN afterwards."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import drn_ops_ref as R
+
+pytestmark = pytest.mark.gpu
+
+BAR = R.BAR32
+NAN = float("nan")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch.device("cuda:0")
+
+
+class Guarded:
+    """A contiguous output of `shape` between two runs of `pad` NaN elements."""
+
+    def __init__(self, shape, dtype=torch.float32, pad=256, fill=NAN):
+        self.n = int(math.prod(shape))
+        self.pad = pad
+        self.buf = torch.full((2 * pad + self.n,), NAN, dtype=dtype, device="cuda")
+        self.t = self.buf[pad:pad + self.n].view(shape)
+        if fill == fill:
+            self.t.fill_(fill)
+
+    def check(self):
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(self.buf[:self.pad]).all()) and bool(torch.isnan(self.buf[self.pad + self.n:]).all()), "guard overwritten"
+        assert not bool(torch.isnan(self.t).any()), "output not fully written"
+        return self.t.cpu()
+
+
+def rel(got, ref):
+    return float((got.double() - ref).abs().max() / ref.abs().max().clamp_min(1e-300))
+
+
+def sum_excess(got, ref, n, sabs):
+    """max over elements of |got - ref| / (n * 2^-24 * sum|v|); <= 1 passes.  Where the bound is 0 the sum must be exact."""
+    bound = n * R.U32 * sabs
+    err = (got.double() - ref).abs()
+    assert bool((err[bound == 0] == 0).all())
+    return float((err / bound.clamp_min(1e-300))[bound > 0].max()) if bool((bound > 0).any()) else 0.0
+
+
+def bf16_excess(got, ref):
+    return float(((got.double() - ref).abs() / (2.0 ** -8 * ref.abs() + BAR * ref.abs().max())).max())
+
+
+def h(t):       # an input "built by rounding"
+    return t.to(torch.bfloat16)
+
+
+def run_tail(d, B, hw, storage=(False, False, False), keep=True, ldx=None):
+    """ops.drn_ca_scale_add on the inputs d with r / x / y stored as `storage` says; outputs guarded.
+    Returns (y, gate, pool) on the CPU and the inputs as the kernel saw them (bf16 ones widened)."""
+    from srad_amd import ops
+    rh, xh, yh = storage
+    C = d["r"].shape[1]
+    r = h(d["r"]) if rh else d["r"]
+    x = h(d["x"]) if xh else d["x"]
+    xd = x.cuda()
+    if ldx is not None:                                      # x in the first C columns of wider rows, NaN beside it
+        wide = torch.full((B * hw, ldx), NAN, dtype=x.dtype, device="cuda")
+        wide[:, :C] = xd
+        xd = wide[:, :C]
+    y = Guarded((B * hw, C), torch.bfloat16 if yh else torch.float32)
+    gate, pool = Guarded((B, C)), Guarded((B, C))
+    c = lambda k: d[k].cuda()
+    ops.drn_ca_scale_add(c("part"), c("w1"), c("b1"), c("w2"), c("b2"), r.cuda(), xd, y_bf16=yh, keep=keep, out=y.t,
+                         gate_out=gate.t if keep else None, pool_out=pool.t if keep else None)
+    return y.check(), gate.check() if keep else None, pool.check() if keep else None, r.float(), x.float()
+
+
+def check_tail(case, nchunk=32, storage=(False, False, False), ldx=None, seed=0):
+    B, hw, C = case
+    d = R.ca_inputs(B, hw, C, nchunk=nchunk, seed=seed)
+    worst = {}
+    for keep in (True, False):                                # gate_out / pool_out given, and both null
+        y, gate, pool, r_in, x_in = run_tail(d, B, hw, storage, keep, ldx)
+        ry, rgate, rpool, pre = R.ca_tail64(d["part"], hw, d["w1"], d["b1"], d["w2"], d["b2"], r_in, x_in)
+        assert float(pre.abs().min()) > 1e-3                  # the ReLU mask is stable
+        if storage[2]:
+            worst["y(bf16) / bound"] = max(worst.get("y(bf16) / bound", 0.0), bf16_excess(y, ry))
+        else:
+            worst["y"] = max(worst.get("y", 0.0), rel(y, ry))
+        if keep:
+            worst["gate"] = rel(gate, rgate)
+            worst["pool / bound"] = sum_excess(pool, rpool, nchunk, d["part"].double().abs().sum(1))
+    print(f"ca_scale_add {case} nchunk {nchunk} storage {storage} ldx {ldx}: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    for k, v in worst.items():
+        assert v <= (1.0 if "bound" in k else BAR), (k, v)
+
+
+# ------------------------------------------------------------------------------------------ forward RCAB tail
+@pytest.mark.parametrize("case", list(R.CA_CASES))
+def test_ca_scale_add_matches_fp64(dev, case):
+    check_tail(case)
+
+
+@pytest.mark.parametrize("nchunk", R.NCHUNKS)
+@pytest.mark.parametrize("case", R.NCHUNK_CASES)
+def test_ca_scale_add_partial_row_counts(dev, case, nchunk):
+    """1, 143, 144, 145 and 256 partial rows: the 12 x nparts trips of the clamped-and-masked sum end before, at and after a
+    trip boundary at C = 80 (nparts = 12), and 256 is the most the conv epilogue leaves."""
+    check_tail(case, nchunk=nchunk)
+
+
+@pytest.mark.parametrize("storage", R.STORAGES)
+@pytest.mark.parametrize("case", R.STORAGE_CASES)
+def test_ca_scale_add_storage_instances(dev, case, storage):
+    """The five r / x / y storage combinations launch_ca_scale_add dispatches, at NI = 10, the loop, NI = 10 on 128 slices, and
+    NI = 5 with slices past the image's end: all fifteen instances of the kernel."""
+    check_tail(case, storage=storage)
+
+
+@pytest.mark.parametrize("storage", [(False, False, False), (True, True, True)])
+def test_ca_scale_add_wide_x_rows(dev, storage):
+    """x rows 2 C elements apart (a concat buffer), NaN in the columns beside it."""
+    check_tail((2, 1025, 80), storage=storage, ldx=160)
+
+
+def test_ca_scale_add_check_is_sensitive_to_a_dropped_row_and_one_gate_channel(dev):
+    """A dropped partial row (one of 32) and a wrong gate for ONE channel must each move y by more than 20x the bar."""
+    B, hw, C = case = (2, 1025, 80)
+    d = R.ca_inputs(B, hw, C)
+    ref = R.ca_tail64(d["part"], hw, d["w1"], d["b1"], d["w2"], d["b2"], d["r"], d["x"])[0]
+    assert rel(run_tail(d, B, hw)[0], ref) < BAR
+    drop = dict(d, part=d["part"].clone())
+    drop["part"][1, 17] = 0
+    onec = dict(d, b2=d["b2"].clone())
+    onec["b2"][37] += 0.05
+    e_drop, e_gate = rel(run_tail(drop, B, hw)[0], ref), rel(run_tail(onec, B, hw)[0], ref)
+    print(f"{case}: one partial row dropped {e_drop:.2e}, one channel's gate bias off by 0.05 {e_gate:.2e} (> {20 * BAR:.0e})")
+    assert e_drop > 20 * BAR and e_gate > 20 * BAR
+
+
+# ------------------------------------------------------------------------------------------ pool_dot
+@pytest.mark.parametrize("hw", [16, 63, 4096, 12289])
+@pytest.mark.parametrize("C", [40, 80, 160, 512])
+def test_pool_dot_partial_rows(dev, C, hw):
+    """Every partial row against the fp64 sum over that chunk's pixels; 16 pixels leave 16 of the 32 chunks empty (exact 0)."""
+    from srad_amd import ops
+    B, nchunk = 2, 32
+    gen = torch.Generator().manual_seed(C + hw)
+    r = torch.randn(B * hw, C, generator=gen) + (torch.rand(C, generator=gen) * 2 - 1)
+    g = torch.randn(B * hw, C, generator=gen)
+    per = -(-hw // nchunk)
+    n = torch.tensor([max(0, min(hw, (k + 1) * per) - k * per) for k in range(nchunk)], dtype=torch.float64)[None, :, None]
+
+    def chunks(v):                                            # [B*hw, C] fp64 -> per-chunk sums [B, nchunk, C]
+        p = torch.zeros(B, nchunk * per, C, dtype=torch.float64)
+        p[:, :hw] = v.reshape(B, hw, C)
+        return p.reshape(B, nchunk, per, C).sum(2)
+    worst = 0.0
+    for r_in in (r, h(r)):
+        for g_in in (None, g):
+            out = Guarded((B, nchunk, C))
+            ops.drn_pool_dot(r_in.cuda(), B, g=None if g_in is None else g_in.cuda(), nchunk=nchunk, out=out.t)
+            v = r_in.double() if g_in is None else r_in.double() * g_in.double()
+            e = sum_excess(out.check(), chunks(v), n, chunks(v.abs()))
+            worst = max(worst, e)
+            assert e <= 1.0, (str(r_in.dtype), g_in is not None, e)
+    print(f"pool_dot C {C} hw {hw}: worst |err| / (n 2^-24 sum|v|) {worst:.3f}")
+
+
+# ------------------------------------------------------------------------------------------ backward
+@pytest.mark.parametrize("case", list(R.CA_CASES))
+def test_ca_apply_bwd_chain_matches_autograd(dev, case):
+    """drn_pool_dot(g, r) -> drn_ca_apply_bwd against autograd's d/dr of r * gate(mean r) + x under the upstream g; dr as fp32
+    and as bf16.  gate and pool are the fp64 forward's, rounded: what the training forward leaves."""
+    from srad_amd import ops
+    B, hw, C = case
+    d = R.ca_inputs(B, hw, C, from_r=True)
+    g = torch.randn(B * hw, C, generator=torch.Generator().manual_seed(hw + C)) + 0.25
+    ref = R.ca_backward64(d["r"], d["x"], g, B, hw, d["w1"], d["b1"], d["w2"], d["b2"])
+    assert float(ref["pre"].abs().min()) > 1e-3
+    gd, rd = g.cuda(), d["r"].cuda()
+    part = ops.drn_pool_dot(rd, B, g=gd)
+    errs = []
+    for dr_h in (False, True):
+        dr = Guarded((B * hw, C), torch.bfloat16 if dr_h else torch.float32)
+        ops.drn_ca_apply_bwd(gd, ref["gate"].float().cuda(), part, ref["pool"].float().cuda(), d["w1"].cuda(), d["b1"].cuda(),
+                             d["w2"].cuda(), dr_bf16=dr_h, out=dr.t)
+        errs.append(bf16_excess(dr.check(), ref["dr"]) if dr_h else rel(dr.check(), ref["dr"]))
+    print(f"ca_apply_bwd {case}: dr {errs[0]:.2e}, bf16 dr / bound {errs[1]:.3f}")
+    assert errs[0] < BAR and errs[1] <= 1.0
+
+
+@pytest.mark.parametrize("B", [1, 8, 9, 17])
+@pytest.mark.parametrize("C", [40, 80, 128, 256])
+def test_ca_bwd_weight_gradients(dev, B, C):
+    """ca_bwd_kernel: one pass of up to 8 images, two passes, three; dw1 / db1 / dw2 / db2 accumulated onto non-zero buffers and
+    dpool, against autograd of sum(dgate * gate(pool / hw)) summed over the batch."""
+    from srad_amd import ops
+    hw, nchunk, Cr = 1000, 32, C // 16
+    for seed in range(50):
+        gen = torch.Generator().manual_seed(977 * seed + 31 * B + C)
+        pool = ((torch.rand(C, generator=gen) * 2 - 1) + 0.3 * torch.randn(B, C, generator=gen)) * hw
+        w1, b1, w2, b2 = R.ca_weights(C, 977 * seed + C)
+        part = (0.5 + torch.randn(B, nchunk, C, generator=gen)) / nchunk
+        ref = R.gate_backward64(part.double().sum(1), pool, hw, w1, b1, w2, b2)
+        if float(ref["pre"].abs().min()) > 2e-3:
+            break
+    assert float(ref["pre"].abs().min()) > 1e-3
+    base = {k: torch.randn(s, generator=gen) * float(ref[k].abs().max()) for k, s in
+            (("dw1", (Cr, C)), ("db1", (Cr,)), ("dw2", (C, Cr)), ("db2", (C,)))}
+    acc = {k: Guarded(v.shape) for k, v in base.items()}
+    for k in acc:
+        acc[k].t.copy_(base[k])
+    dpool = Guarded((B, C))
+    ops.drn_ca_bwd(part.cuda(), pool.cuda(), ref["gate"].float().cuda(), hw, w1.cuda(), b1.cuda(), w2.cuda(), acc["dw1"].t, acc["db1"].t,
+                   acc["dw2"].t, acc["db2"].t, out=dpool.t)
+    errs = {k: rel(acc[k].check(), base[k].double() + ref[k]) for k in acc}
+    errs["dpool"] = rel(dpool.check(), ref["dpool"])
+    print(f"ca_bwd B {B} C {C}: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    for k, v in errs.items():
+        assert v < BAR, (k, v)
+
+
+@pytest.mark.parametrize("want_dt", [True, False])
+@pytest.mark.parametrize("layout", ["nchw", "rows"])
+@pytest.mark.parametrize("C", [1, 3])
+def test_affine_bwd(dev, C, layout, want_dt):
+    """MeanShift backward over T = 70000 pixels (above the 65536 threads of its capped grid: the stride loop runs), dy as NCHW
+    or as [T][4] rows, dt given or null, dw / db accumulated onto non-zero values; autograd of y = w t + b.  t is image-like and
+    dy has a per-channel offset, so the sums are not cancellations and 1e-5 of the tensor's max is a meaningful bar."""
+    from srad_amd import ops
+    B, HW = 2, 35000
+    T = B * HW
+    gen = torch.Generator().manual_seed(10 * C + len(layout))
+    t = torch.rand(T, 4, generator=gen)
+    w = torch.eye(C) + 0.2 * torch.randn(C, C, generator=gen)
+    dy = torch.randn(T, C, generator=gen) * 0.3 + (torch.arange(C) + 1.0) * 0.5
+    td = t[:, :C].double().clone().requires_grad_(True)
+    wd, bd = w.double().clone().requires_grad_(True), torch.zeros(C, dtype=torch.float64, requires_grad=True)
+    ((td @ wd.t() + bd) * dy.double()).sum().backward()
+    if layout == "nchw":
+        dy_in = dy.reshape(B, HW, C).permute(0, 2, 1).contiguous()
+    else:
+        dy_in = torch.full((T, 4), NAN)                      # the columns beyond C are never read
+        dy_in[:, :C] = dy
+    base_w, base_b = torch.randn(C, C, generator=gen) * float(wd.grad.abs().max()), torch.randn(C, generator=gen) * float(bd.grad.abs().max())
+    dw, db, dt = Guarded((C, C)), Guarded((C,)), Guarded((T, 4))
+    dw.t.copy_(base_w)
+    db.t.copy_(base_b)
+    ops.drn_affine_bwd(dy_in.cuda(), t.cuda(), w.cuda(), dw.t, db.t, want_dt=want_dt, out=dt.t if want_dt else None)
+    e_w, e_b = rel(dw.check(), base_w.double() + wd.grad), rel(db.check(), base_b.double() + bd.grad)
+    e_t = 0.0
+    if want_dt:
+        got = dt.check()
+        assert bool((got[:, C:] == 0).all())
+        e_t = rel(got[:, :C], td.grad)
+    else:
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(dt.buf).all())
+    print(f"affine_bwd C {C} {layout} dt {want_dt}: dw {e_w:.2e} db {e_b:.2e} dt {e_t:.2e}")
+    assert e_w < BAR and e_b < BAR and e_t < BAR
+
+
+@pytest.mark.parametrize("C", [12, 80])
+def test_zero_upsample_and_add_cols_exact(dev, C):
+    from srad_amd import ops
+    B, Ho, Wo = 2, 5, 7
+    gen = torch.Generator().manual_seed(C)
+    dy = torch.randn(B * Ho * Wo, C, generator=gen)
+    z = Guarded((4 * B * Ho * Wo, C))
+    ops.drn_zero_upsample(dy.cuda(), B, Ho, Wo, out=z.t)
+    ref = torch.zeros(B, 2 * Ho, 2 * Wo, C)
+    ref[:, ::2, ::2] = dy.reshape(B, Ho, Wo, C)
+    assert torch.equal(z.check(), ref.reshape(-1, C))
+    # add_cols: rows of both operands wider than C, the columns beside it NaN; more rows than one pass of the grid at C = 80
+    rows = 60001 if C == 80 else 77
+    src = torch.full((rows, C + 8), NAN)
+    dst = torch.full((rows, C + 4), NAN)
+    src[:, :C] = torch.randn(rows, C, generator=gen)
+    dst[:, :C] = torch.randn(rows, C, generator=gen)
+    out = Guarded((rows, C + 4))
+    out.t.copy_(dst)
+    ops.drn_add_cols(src.cuda(), out.t, C)
+    torch.cuda.synchronize()
+    got = out.t.cpu()
+    assert bool(torch.isnan(out.buf[:out.pad]).all()) and bool(torch.isnan(out.buf[out.pad + out.n:]).all()) and bool(torch.isnan(got[:, C:]).all())
+    assert torch.equal(got[:, :C], dst[:, :C] + src[:, :C])
+    print(f"zero_upsample / add_cols C {C}: exact")
+
+
+# ------------------------------------------------------------------------------------------ image ends
+@pytest.mark.parametrize("raw", [True, False])
+@pytest.mark.parametrize("B,C,H,W,scale", [(2, 3, 5, 7, 4), (1, 1, 1, 9, 2), (1, 3, 4, 4, 8), (3, 1, 6, 1, 8), (2, 3, 96, 96, 8)])
+def test_bicubic_submean(dev, B, C, H, W, scale, raw):
+    """Against F.interpolate(bicubic, align_corners=False) in fp64, then the C x C sub_mean; (2, 3, 96, 96, 8) has 1.18 M output
+    pixels, above the 4096 x 256 grid cap: the stride loop runs.  The fourth float of every pixel is exactly 0."""
+    from srad_amd import ops
+    gen = torch.Generator().manual_seed(H * W + scale)
+    x = torch.rand(B, C, H, W, generator=gen) * 255
+    mw = torch.eye(C) + 0.1 * torch.randn(C, C, generator=gen)
+    mb = -torch.rand(C, generator=gen) * 255
+    T = B * H * scale * W * scale
+    up = F.interpolate(x.double(), scale_factor=scale, mode="bicubic", align_corners=False)
+    ref = F.conv2d(up, mw.double()[:, :, None, None], mb.double()).permute(0, 2, 3, 1).reshape(T, C)
+    y, rw = Guarded((T, 4)), Guarded((T, 4))
+    ops.drn_bicubic(x.cuda(), scale, mw.cuda(), mb.cuda(), out=y.t, raw_out=rw.t if raw else None)
+    got = y.check()
+    assert bool((got[:, C:] == 0).all())
+    e_y, e_r = rel(got[:, :C], ref), 0.0
+    if raw:
+        gr = rw.check()
+        assert bool((gr[:, C:] == 0).all())
+        e_r = rel(gr[:, :C], up.permute(0, 2, 3, 1).reshape(T, C))
+    else:
+        assert bool(torch.isnan(rw.buf).all())
+    print(f"bicubic {(B, C, H, W, scale)} raw {raw}: y {e_y:.2e} raw {e_r:.2e}")
+    assert e_y < BAR and e_r < BAR
+
+
+@pytest.mark.parametrize("B,C,HW,ldx", [(2, 3, 35, 4), (2, 3, 35, 3), (3, 1, 50, 1), (1, 1, 1048576 + 77, 4)])
+def test_affine_to_nchw(dev, B, C, HW, ldx):
+    """add_mean + NHWC -> NCHW; the last case has more pixels than the 4096 x 256 threads of the capped grid."""
+    from srad_amd import ops
+    gen = torch.Generator().manual_seed(HW)
+    x = torch.full((B * HW, ldx), NAN)
+    x[:, :C] = torch.rand(B * HW, C, generator=gen) * 255
+    mw = torch.eye(C) + 0.1 * torch.randn(C, C, generator=gen)
+    mb = torch.rand(C, generator=gen) * 255
+    ref = (x[:, :C].double() @ mw.double().t() + mb.double()).reshape(B, HW, C).permute(0, 2, 1)
+    y = Guarded((B, C, HW))
+    ops.drn_affine_to_nchw(x.cuda()[:, :C], B, C, mw.cuda(), mb.cuda(), out=y.t)
+    e = rel(y.check(), ref)
+    print(f"affine_to_nchw {(B, C, HW, ldx)}: {e:.2e}")
+    assert e < BAR
+
+
+# ------------------------------------------------------------------------------------------ conv epilogue pool sums
+_CONV_TOL = 1e-4      # tests/test_gpu_ops.py TOL["fp32"]
+
+
+@pytest.mark.parametrize("B,H,W,C,prec", [(6, 64, 64, 80, "fp32"), (6, 64, 64, 80, "bf16x3"), (3, 64, 64, 80, "fp32"), (2, 64, 64, 160, "fp32"),
+                                          (11, 64, 48, 80, "bf16"), (8, 64, 48, 80, "bf16"), (6, 64, 64, 40, "fp32")])
+def test_conv_pool_epilogue_sums(dev, B, H, W, C, prec):
+    """The tiled GEMM's pool_part epilogue at the smallest shapes that take it: 64 x 80 tiles (B = 6), 64 x 64 tiles with a
+    second, mostly empty column tile (B = 3), three column tiles with the last half full (C = 160), bf16 with W % 32 != 0 (the
+    80-channel kernel does not take it) on 128- and 64-row tiles, and C = 40.  part[b][k][c] against the fp64 sum of the op's OWN
+    y over that tile's rows - independent of the conv's precision; y itself against conv2d on the C = 80 fp32 case."""
+    from srad_amd import ops
+    gen = torch.Generator().manual_seed(B + H + W + C)
+    x = torch.randn(B * H * W, C, generator=gen)
+    w = torch.randn(C, C, 3, 3, generator=gen) / math.sqrt(9 * C)
+    b = torch.randn(C, generator=gen)                        # the bias keeps the column sums away from 0
+    rows = ops.conv_pool_rows(B, H, W, C, prec)
+    assert rows > 0, "this shape does not run the epilogue: the case checks nothing"
+    y, part = Guarded((B * H * W, C)), Guarded((B, rows, C))
+    _, _, got_rows = ops.conv_pool(x.cuda(), w.cuda(), b.cuda(), B=B, H=H, W=W, precision=prec, out=y.t, part_out=part.t)
+    assert got_rows == rows and (H * W) % rows == 0
+    yc = y.check().double()
+    bm = H * W // rows
+    tiles = yc.reshape(B, rows, bm, C)
+    e = sum_excess(part.check(), tiles.sum(2), bm, tiles.abs().sum(2))
+    print(f"conv_pool {(B, H, W, C, prec)}: {rows} rows of {bm} pixels per image, worst |err| / (n 2^-24 sum|v|) {e:.3f}")
+    assert e <= 1.0
+    if (B, C, prec) == (6, 80, "fp32"):
+        ref = F.conv2d(x.double().reshape(B, H, W, C).permute(0, 3, 1, 2), w.double(), b.double(), padding=1).permute(0, 2, 3, 1).reshape(-1, C)
+        e_y = rel(yc, ref)
+        print(f"  y against conv2d: {e_y:.2e}")
+        assert e_y < _CONV_TOL
+
+
+def test_conv_pool_small_shape_is_not_eligible(dev):
+    from srad_amd import ops
+    B, H, W, C = 1, 8, 8, 80
+    assert ops.conv_pool_rows(B, H, W, C) == 0
+    gen = torch.Generator().manual_seed(1)
+    x, w, b = torch.randn(B * H * W, C, generator=gen), torch.randn(C, C, 3, 3, generator=gen) / math.sqrt(720), torch.randn(C, generator=gen)
+    y = Guarded((B * H * W, C))
+    _, part, rows = ops.conv_pool(x.cuda(), w.cuda(), b.cuda(), B=B, H=H, W=W, out=y.t)
+    assert rows == 0
+    ref = F.conv2d(x.double().reshape(B, H, W, C).permute(0, 3, 1, 2), w.double(), b.double(), padding=1).permute(0, 2, 3, 1).reshape(-1, C)
+    assert rel(y.check(), ref) < _CONV_TOL

@@ -34,11 +34,16 @@ def _setup(scale, n_colors, n_blocks, n_feats, B, H, W, seed=31, prec="fp32"):
 
 
 @pytest.mark.parametrize("scale,n_colors,n_feats,B,H,W", [(4, 1, 20, 2, 8, 12), (2, 3, 8, 1, 16, 16), (4, 3, 20, 1, 8, 8),
-                                                             (8, 1, 10, 2, 4, 6), (8, 3, 10, 1, 4, 4), (2, 1, 10, 1, 8, 8)])
+                                                             (8, 1, 10, 2, 4, 6), (8, 3, 10, 1, 4, 4), (2, 1, 10, 1, 8, 8),
+                                                             (4, 1, 32, 1, 4, 4),        # 128 channels at the top, Cr = 8: the wide gate, forward and backward
+                                                             (2, 1, 20, 6, 64, 64)])     # 64 x 64 level, M = 24576: the conv epilogue's pool sums (fp32)
 def test_drn_gradients_match_oracle_autograd(scale, n_colors, n_feats, B, H, W):
     from oracle import sr_ref as R
     from srad_amd.train import drn_loss
     cfg, sd, duals, lrs, hr, m, dms = _setup(scale, n_colors, 2, n_feats, B, H, W)
+    if (B, H) == (6, 64):
+        from srad_amd import ops
+        assert ops.conv_pool_rows(B, 64, 64, 2 * n_feats) > 0      # this case is here for the epilogue: it must be eligible
     # oracle: torch CPU autograd over the same state
     sdt = {k: torch.from_numpy(np.asarray(v)).clone().requires_grad_(True) for k, v in sd.items()}
     dts = [{k: torch.from_numpy(np.asarray(v)).clone().requires_grad_(True) for k, v in d.items()} for d in duals]
