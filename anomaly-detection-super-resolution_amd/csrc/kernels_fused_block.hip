@@ -12,8 +12,9 @@
 // 80-95 % idle); q is projected for its own row tile only.  A wave then owns one head: scores, bias + mask, softmax and P.V of
 // 16 queries x 64 keys stay inside the wave (no barrier between them), and the result lands as the bf16 A tile of the proj
 // GEMM in LDS.  The weights of all five matrices stream through ONE sequence of register-set stages (three ahead, as in the
-// two kernels), so the first MLP stages are in flight under the attention.  Head dims whose k | v of all heads do not fit
-// next to the window tile (d = 276, 308) run the heads in two groups.
+// two kernels), so the first MLP stages are in flight under the attention.  Head rows are stored at the smallest stride that
+// keeps the bank rule (48 / 80 elements for the 46- / 77-wide heads of d = 276 / 308), so k | v of all heads fit next to the
+// window tile at every d.
 //
 // Write hazard: adjust_k (k < 4) writes columns [d, d + no) of its 16 rows into the same dense buffer whose columns [0, d)
 // other workgroups of this launch still read.  d % 4 == 0, every access is a float4 on a 4-column boundary, so no access
@@ -50,28 +51,28 @@ __device__ __forceinline__ float blk_gelu(float x) {
   return 0.5f * x * (1.0f + (x < 0.f ? -erfa : erfa));
 }
 
-// Stage counts and the LDS layout of one instance.  HDT = ceil(head_dim / 16), KC = ceil(d / 32), NG = head groups.
-template <int HDT, int KC, int HEADS, int NG>
+// Stage counts and the LDS layout of one instance.  HDT = ceil(head_dim / 16), KC = ceil(d / 32).
+template <int HDT, int KC, int HEADS>
 struct BlkGeo {
-  static_assert(HEADS % NG == 0, "head groups must divide the heads");
-  static constexpr int HG = HEADS / NG;                   // heads per group = waves that run an attention
-  static constexpr int HDP = 16 * HDT, HDP32 = (HDP + 31) & ~31, HS = HDP32 + 16, LDX = KC * 32 + 16;
-  static constexpr int NKVT = HG * 2 * HDT, NQT = HG * HDT;        // 16-column tiles of k | v (x 4 row tiles) and of q (x 1)
+  static constexpr int HDP = 16 * HDT, LDX = KC * 32 + 16;
+  // head row stride: the smallest multiple of 8 elements >= HDP whose count of 16-byte units is 2 mod 4 (32 -> 48, 48 -> 48,
+  // 64 -> 80, 80 -> 80, 128 -> 144)
+  static constexpr int HS = (HDP / 8 + (6 - HDP / 8 % 4) % 4) * 8;
+  static_assert(HS >= HDP && HS % 8 == 0 && HS / 8 % 4 == 2, "head rows keep the bank rule");
+  static constexpr int NKVT = HEADS * 2 * HDT, NQT = HEADS * HDT;  // 16-column tiles of k | v (x 4 row tiles) and of q (x 1)
   static constexpr int NKVS = (NKVT + 7) / 8, NQS = (NQT + 7) / 8; // column stages: one tile per wave
-  static constexpr int SPG = NKVS + NQS;                           // weight stages per head group: a stage spans all KC k chunks
-  static constexpr int QS = NG * SPG;                              // ... of the attention half
+  static constexpr int QS = NKVS + NQS;                            // weight stages of the attention half: a stage spans all KC k chunks
   // bytes
-  static constexpr int XN_B = 64 * LDX * 2, KV_B = 2 * HG * 64 * HS * 2, Q_B = HG * 16 * HS * 2, PS_B = HG * 16 * B_LDP * 2;
+  static constexpr int XN_B = 64 * LDX * 2, KV_B = 2 * HEADS * 64 * HS * 2, Q_B = HEADS * 16 * HS * 2, PS_B = HEADS * 16 * B_LDP * 2;
   static constexpr int A1_B = 16 * B_LDA * 2, HS_B = 16 * B_LDH * 2;
-  // one group: the normalised window is dead once q | k | v exist, so the probabilities (and the attention tile, if both fit)
-  // overlay it; two groups: the window is read again by the second group
-  static constexpr bool OVER = NG == 1, A1_OVER = OVER && PS_B + A1_B <= XN_B;
+  // the normalised window is dead once q | k | v exist, so the probabilities (and the attention tile, if both fit) overlay it
+  static constexpr bool A1_OVER = PS_B + A1_B <= XN_B;
   static constexpr int OFF_KV = XN_B, OFF_Q = OFF_KV + KV_B;
   static constexpr int OFF_A1 = A1_OVER ? PS_B : OFF_Q + Q_B;
-  static constexpr int OFF_PS = OVER ? 0 : OFF_A1 + A1_B;
-  static constexpr int OFF_VEC = (A1_OVER ? OFF_Q + Q_B : (OVER ? OFF_A1 + A1_B : OFF_PS + PS_B));
+  static constexpr int OFF_PS = 0;
+  static constexpr int OFF_VEC = A1_OVER ? OFF_Q + Q_B : OFF_A1 + A1_B;
   static constexpr int NBIAS = HEADS * 3 * HDP, NTBL = 225 * HEADS, NTBLP = (NTBL + 3) & ~3;
-  // floats: MLP vectors | gamma1 320 | beta1 320 | qkv bias | table | LayerNorm2 partial sums [16][8][2] | softmax sums [HG][16]
+  // floats: MLP vectors | gamma1 320 | beta1 320 | qkv bias | table | LayerNorm2 partial sums [16][8][2] | softmax sums [HEADS][16]
   static constexpr int NFLT = B_NV + 640 + NBIAS + NTBLP + 256 + 128;
   static constexpr int LDS = OFF_VEC + NFLT * 4 + 64 * 4;          // + window geometry words [64]
   static_assert(KV_B >= HS_B, "the hidden tile overlays k | v");
@@ -79,21 +80,21 @@ struct BlkGeo {
 };
 
 // GD .. KCM: the stage geometry of the MLP half, as mlp_block_kernel's (KCD == KC)
-template <int HDT, int KC, int HEADS, int NG, int GD, int KGD, int GM, int KGM, int GN, int KCM>
+template <int HDT, int KC, int HEADS, int GD, int KGD, int GM, int KGM, int GN, int KCM>
 __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p) {
-  using G = BlkGeo<HDT, KC, HEADS, NG>;
+  using G = BlkGeo<HDT, KC, HEADS>;
   constexpr int KCD = KC;
   static_assert(KGD == (KCD + 7) / 8 && KGM == (KCM + 7) / 8, "k groups are 8 chunks wide");
-  constexpr int HG = G::HG, HDP = G::HDP, HDP32 = G::HDP32, HS = G::HS, LDX = G::LDX;
+  constexpr int HDP = G::HDP, HS = G::HS, LDX = G::LDX;
   constexpr int RC = KC > 8 ? KC : 8;                                    // fragment registers per weight set: a W_qkv stage holds all
                                                                          // KC (<= 10) chunks of its tile, an MLP stage up to 8
-  constexpr int NKVS = G::NKVS, SPG = G::SPG, QS = G::QS;
+  constexpr int NKVS = G::NKVS, QS = G::QS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* XN = reinterpret_cast<__bf16*>(smem);                          // [64][LDX] LayerNorm1(window)
-  __bf16* KV = reinterpret_cast<__bf16*>(smem + G::OFF_KV);              // [k | v][HG][64][HS]
-  __bf16* Qb = reinterpret_cast<__bf16*>(smem + G::OFF_Q);               // [HG][16][HS] (scaled)
+  __bf16* KV = reinterpret_cast<__bf16*>(smem + G::OFF_KV);              // [k | v][HEADS][64][HS]
+  __bf16* Qb = reinterpret_cast<__bf16*>(smem + G::OFF_Q);               // [HEADS][16][HS] (scaled)
   __bf16* A1 = reinterpret_cast<__bf16*>(smem + G::OFF_A1);              // [16][B_LDA] attention output -> LN2(x1) -> x2
-  __bf16* Ps = reinterpret_cast<__bf16*>(smem + G::OFF_PS);              // [HG][16][B_LDP] probabilities
+  __bf16* Ps = reinterpret_cast<__bf16*>(smem + G::OFF_PS);              // [HEADS][16][B_LDP] probabilities
   __bf16* Hs = KV;                                                       // [16][B_LDH] GELU(fc1): k | v are dead by then
   float* vec = reinterpret_cast<float*>(smem + G::OFF_VEC);
   float* v_g1 = vec + B_NV;                                              // [320] gamma1
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   float* v_bias = v_b1n + 320;                                           // [HEADS][3][HDP] q|k|v bias (0 in padding)
   float* tbl = v_bias + G::NBIAS;                                        // [225][HEADS] relative position bias
   float* red = tbl + G::NTBLP;                                           // [16][8][2] LayerNorm2 partial sums
-  float* lsum = red + 256;                                               // [HG][16] softmax denominators
+  float* lsum = red + 256;                                               // [HEADS][16] softmax denominators
   int* inf = reinterpret_cast<int*>(lsum + 128);                         // [64] (region << 16) | (py << 8) | px
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -149,8 +150,8 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     const int nch = kc - kg * 8 < 8 ? kc - kg * 8 : 8;
     return StageGeo{ph, g, kg, nch, kc};
   };
-  // the 16-column tile of q | k | v this wave owns in column stage cs of head group gr: head (within the group), slice
-  // (0 q, 1 k, 2 v), column tile of the slice, liveness
+  // the 16-column tile of q | k | v this wave owns in column stage cs: head, slice (0 q, 1 k, 2 v), column tile of the
+  // slice, liveness
   struct QTile { int hl, which, ct; bool live; };
   auto qtile = [&](int cs) -> QTile {
     if (cs < NKVS) {
@@ -168,10 +169,9 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   auto load_w = [&](auto S, u32x4 (&reg)[RC]) __attribute__((always_inline)) {
     constexpr int u = decltype(S)::value < n_all - 1 ? decltype(S)::value : n_all - 1;
     if constexpr (u < QS) {
-      constexpr int gr = u / SPG, cs = u - gr * SPG;
-      const QTile t = qtile(cs);
+      const QTile t = qtile(u);
       const char* const Wq = reinterpret_cast<const char*>(p.w_qkv);
-      const int gt = ((gr * HG + t.hl) * 3 + t.which) * HDT + t.ct;           // tile row of the pack: [head][q | k | v][HDT]
+      const int gt = (t.hl * 3 + t.which) * HDT + t.ct;                       // tile row of the pack: [head][q | k | v][HDT]
       const char* base = t.live ? Wq + (size_t)gt * KC * 1024 + fr * 64 + fq * 16 : Wq;
       const int step = t.live ? 1024 : 0;
 #pragma unroll
@@ -241,18 +241,6 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     *reinterpret_cast<f32x4*>(vec + v_off + 4 * lane) = vq[0];
     if (256 + 4 * lane < v_len) *reinterpret_cast<f32x4*>(vec + v_off + 256 + 4 * lane) = vq[1];
   }
-  if constexpr (HDP32 != HDP) {
-    // head dims padded to 48 / 80: the last 32-wide k step of q.k^T also covers 16 columns no epilogue writes (k: all 64 rows
-    // of every head of a group; q: this tile's 16)
-    for (int i = tid; i < HG * 64 * 4; i += 512) {
-      const int row = i >> 2, part = i & 3;
-      *reinterpret_cast<bf16x4*>(KV + row * HS + HDP + 4 * part) = bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-    }
-    for (int i = tid; i < HG * 16 * 4; i += 512) {
-      const int row = i >> 2, part = i & 3;
-      *reinterpret_cast<bf16x4*>(Qb + row * HS + HDP + 4 * part) = bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-    }
-  }
   // ---- LayerNorm1 from the registers (the 8 lanes of a row hold all its columns) -> bf16 -> XN ----
   {
     float s = 0.f, ss = 0.f;
@@ -281,14 +269,15 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   static_for<1, NSETS>([&](auto Q) { load_w(Q, w_reg[decltype(Q)::value]); });   // the rest of the weight look-ahead
   __syncthreads();                                                // the normalised window is in LDS
 
-  // ======================================= attention half, head group after head group =======================================
-  static_for<0, NG>([&](auto GR) {
-    constexpr int gr = decltype(GR)::value;
-    // ---- q|k|v = xn . W^T : one 16-column tile per wave and stage, transposed result (lane: token fr of row tile t, 4 columns);
-    //      k | v tiles for all four row tiles, q tiles for this workgroup's row tile only ----
+  // ================================================== attention half ==================================================
+  // ---- q|k|v = xn . W^T : one 16-column tile per wave and stage, transposed result (lane: token fr of row tile t, 4 columns);
+  //      k | v tiles for all four row tiles, q tiles for this workgroup's row tile only ----
+  // (a lambda of its own, as the head-group loop was: with its temporaries scoped like this the d = 180 / 212 / 244 instances
+  // compile to the instruction streams they had)
+  [&]() __attribute__((always_inline)) {
     f32x4 ac[4];
-    static_for<0, SPG>([&](auto LS) {
-      constexpr int cs = decltype(LS)::value, S = gr * SPG + cs;
+    static_for<0, QS>([&](auto LS) {
+      constexpr int cs = decltype(LS)::value, S = cs;
       constexpr bool isq = cs >= NKVS;
       constexpr int NT = isq ? 1 : 4;
       constexpr int nch = KC;
@@ -321,41 +310,37 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
         }
       }
       load_w(std::integral_constant<int, S + NSETS>{}, reg);
-      {
-        // the previous group's attention still reads q | k | v: its waves arrive here when they are done
-        if constexpr (gr > 0 && cs == 0) __syncthreads();
-        // bias, the attention's scale on q, zero padding -> the bf16 tiles the attention reads
-        if (t.live) {
-          const int c = t.ct * 16 + 4 * fq;
-          const f32x4 bias = *reinterpret_cast<const f32x4*>(v_bias + ((gr * HG + t.hl) * 3 + t.which) * HDP + c);
-          __bf16* dst = isq ? Qb + (t.hl * 16 + fr) * HS + c : KV + (((t.which - 1) * HG + t.hl) * 64 + fr) * HS + c;
+      // bias, the attention's scale on q, zero padding -> the bf16 tiles the attention reads
+      if (t.live) {
+        const int c = t.ct * 16 + 4 * fq;
+        const f32x4 bias = *reinterpret_cast<const f32x4*>(v_bias + (t.hl * 3 + t.which) * HDP + c);
+        __bf16* dst = isq ? Qb + (t.hl * 16 + fr) * HS + c : KV + (((t.which - 1) * HEADS + t.hl) * 64 + fr) * HS + c;
 #pragma unroll
-          for (int tt = 0; tt < NT; ++tt) {
-            f32x4 v = ac[tt] + bias;
-            if constexpr (isq) v = v * scale;
+        for (int tt = 0; tt < NT; ++tt) {
+          f32x4 v = ac[tt] + bias;
+          if constexpr (isq) v = v * scale;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = c + e < hd ? v[e] : 0.f;
-            bf16x4 hh;
+          for (int e = 0; e < 4; ++e) v[e] = c + e < hd ? v[e] : 0.f;
+          bf16x4 hh;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) hh[e] = (__bf16)v[e];
-            *reinterpret_cast<bf16x4*>(dst + tt * 16 * HS) = hh;
-          }
+          for (int e = 0; e < 4; ++e) hh[e] = (__bf16)v[e];
+          *reinterpret_cast<bf16x4*>(dst + tt * 16 * HS) = hh;
         }
       }
     });
-    __syncthreads();                                              // q, k, v of the group complete (one group: the window tile is dead)
-    if constexpr (gr == 0) {
+    __syncthreads();                                              // q, k, v complete: the window tile is dead
+    {
       // columns [d, 32 KC) of the attention tile: the proj GEMM's k padding
       const int row = tid >> 5, c = d + (tid & 31);
       if (c < KC * 32) A1[row * B_LDA + c] = (__bf16)0.f;
     }
     // ---- one head per wave: S = q k^T + bias + mask, softmax, O = P V for this tile's 16 queries against the window's 64 keys ----
-    if (wave_s < HG) {
-      const int hl = wave_s, h = gr * HG + hl;
-      const __bf16* Qs = Qb + hl * 16 * HS;
-      const __bf16* Ks = KV + hl * 64 * HS;
-      const __bf16* Vs = KV + (HG + hl) * 64 * HS;
-      __bf16* Pw = Ps + hl * 16 * B_LDP;
+    if (wave_s < HEADS) {
+      const int h = wave_s;
+      const __bf16* Qs = Qb + h * 16 * HS;
+      const __bf16* Ks = KV + h * 64 * HS;
+      const __bf16* Vs = KV + (HEADS + h) * 64 * HS;
+      __bf16* Pw = Ps + h * 16 * B_LDP;
       f32x4 sc[4];
       // relative position bias + 0 / -100 shift mask (drct.py:284-292, 449-470) of the lane's 16 (key, query) pairs
       {
@@ -378,11 +363,18 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
 #pragma unroll
       for (int j = 0; j < 4; ++j) s4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kk = 0; kk < HDP32; kk += 32) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Qs + fr * HS + kk + 8 * fq);
+      for (int kk = 0; kk < HDP; kk += 32) {
+        // head dims padded to 48 / 80: the last 32-wide step has 16 real columns and the row ends there.  The lanes of the upper
+        // half (fq >= 2) load a clamped column of the same row and get zeros in both operands.
+        const bool half = kk + 32 > HDP, cut = half && fq >= 2;
+        const int col = kk + 8 * (half ? fq & 1 : fq);
+        const bf16x8 zero = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+        bf16x8 a = *reinterpret_cast<const bf16x8*>(Qs + fr * HS + col);
+        a = cut ? zero : a;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const bf16x8 bb = *reinterpret_cast<const bf16x8*>(Ks + (j * 16 + fr) * HS + kk + 8 * fq);
+          bf16x8 bb = *reinterpret_cast<const bf16x8*>(Ks + (j * 16 + fr) * HS + col);
+          bb = cut ? zero : bb;
           s4[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, s4[j], 0, 0, 0);
         }
       }
@@ -396,12 +388,12 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
 #pragma unroll
         for (int j = 0; j < 4; ++j) pr[j] = __expf(s4[j][e] - mx);
         const float rs = srad_row16_sum(pr[0] + pr[1]) + srad_row16_sum(pr[2] + pr[3]);   // the two key halves, as qkv_attn_kernel sums them
-        if (fr == 0) lsum[hl * 16 + 4 * fq + e] = rs;
+        if (fr == 0) lsum[h * 16 + 4 * fq + e] = rs;
 #pragma unroll
         for (int j = 0; j < 4; ++j) Pw[(4 * fq + e) * B_LDP + j * 16 + fr] = (__bf16)pr[j];
       }
       __builtin_amdgcn_wave_barrier();                            // P and the sums are this wave's own: LDS keeps a wave's accesses in order
-      const float inv = 1.0f / lsum[hl * 16 + fr];
+      const float inv = 1.0f / lsum[h * 16 + fr];
       const int tq = fr >> 2, tp = fr & 3;
 #pragma unroll
       for (int j = 0; j < HDT; ++j) {
@@ -427,7 +419,7 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
         }
       }
     }
-  });
+  }();
 
   // ============================ MLP half: mlp_block_kernel<16> on the tile's 16 token rows ============================
   auto col4_of = [&](int g) { return B_SC * g + 16 * wave + 4 * fq; };
@@ -538,24 +530,24 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   });
 }
 
-template <int HDT, int KC, int HEADS, int NG, int GD, int KGD, int GM, int KGM, int GN, int KCM>
+template <int HDT, int KC, int HEADS, int GD, int KGD, int GM, int KGM, int GN, int KCM>
 int launch_blk(const SwinBlockParams& p, hipStream_t stream) {
-  constexpr size_t lds = BlkGeo<HDT, KC, HEADS, NG>::LDS;
+  constexpr size_t lds = BlkGeo<HDT, KC, HEADS>::LDS;
   const double T = (double)p.B * p.H * p.W;
   const double flops = 2.0 * T * (4.0 * p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d) + 4.0 * T * 64.0 * p.d;
   const double bytes = 4.0 * T * (2.0 * p.d + p.no) + 2.0 * (4.0 * p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
   SradProfScope prof(stream, SRAD_K_SWIN_BLOCK, flops, bytes);
   const int nW = (p.H / 8) * (p.W / 8);
-  SRAD_TRY((srad_launch_dyn<swin_block_kernel<HDT, KC, HEADS, NG, GD, KGD, GM, KGM, GN, KCM>>(dim3(p.B * nW, 4), dim3(512), lds, stream, p)));
+  SRAD_TRY((srad_launch_dyn<swin_block_kernel<HDT, KC, HEADS, GD, KGD, GM, KGM, GN, KCM>>(dim3(p.B * nW, 4), dim3(512), lds, stream, p)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
 
-// DRCT-L's five Swin blocks (d = 180 / 212 / 244 / 276 / 308): (head tiles, k chunks of d, heads, head groups) of the attention
+// DRCT-L's five Swin blocks (d = 180 / 212 / 244 / 276 / 308): (head tiles, k chunks of d, heads) of the attention
 // half, then mlp_block's stage geometry (column groups of d, k groups of d, column groups of m, k groups of m, column groups
 // of the adjust output, k chunks of m)
-#define SRAD_BLK_CFGS(X) X(2, 6, 6, 1, 2, 1, 3, 2, 1, 12) X(4, 7, 4, 1, 2, 1, 4, 2, 1, 14) X(8, 8, 2, 1, 2, 1, 4, 2, 1, 16) \
-  X(3, 9, 6, 2, 3, 2, 3, 2, 1, 9) X(5, 10, 4, 2, 3, 2, 3, 2, 2, 10)
+#define SRAD_BLK_CFGS(X) X(2, 6, 6, 2, 1, 3, 2, 1, 12) X(4, 7, 4, 2, 1, 4, 2, 1, 14) X(8, 8, 2, 2, 1, 4, 2, 1, 16) \
+  X(3, 9, 6, 3, 2, 3, 2, 1, 9) X(5, 10, 4, 3, 2, 3, 2, 2, 10)
 
 struct BlkKey { int hdt, kc, heads, gd, kgd, gm, kgm, gn, kcm; };
 inline BlkKey blk_key(int d, int heads, int m, int no) {
@@ -563,7 +555,7 @@ inline BlkKey blk_key(int d, int heads, int m, int no) {
   return BlkKey{(d / heads + 15) / 16, Kd / 32, heads, (d + B_SC - 1) / B_SC, (Kd + 255) / 256, (m + B_SC - 1) / B_SC, (Km + 255) / 256,
                 (no + B_SC - 1) / B_SC, Km / 32};
 }
-#define SRAD_BLK_MATCH(K_, A_, B_, H_, NG_, GD_, KGD_, GM_, KGM_, GN_, KCM_) \
+#define SRAD_BLK_MATCH(K_, A_, B_, H_, GD_, KGD_, GM_, KGM_, GN_, KCM_) \
   (K_.hdt == A_ && K_.kc == B_ && K_.heads == H_ && K_.gd == GD_ && K_.kgd == KGD_ && K_.gm == GM_ && K_.kgm == KGM_ && K_.gn == GN_ && K_.kcm == KCM_)
 
 // CUs of the current device (cached per device)
@@ -592,11 +584,12 @@ extern "C" int srad_swin_block_supported(int prec, int ws, int B, int H, int W, 
 }
 
 // Block shapes (d, heads, hidden, adjust outputs) for which tools/swin_block_bench.py measured the single launch faster than
-// qkv_attn + mlp_block + one launch boundary at B = 4, 32 x 32 AND the step measured faster with them (d = 276
-// wins 1.1 us on the bench and nothing measurable in the step, d = 308 loses).  The engine takes the new kernel for these only.
+// qkv_attn + mlp_block + one launch boundary at B = 4, 32 x 32 AND the step measured faster with them (with
+// compact head rows and one head group d = 276 wins 3.1 us on the bench and 0.03 ms in the step; d = 308 wins 0.4 - 1.0 us on
+// the bench and nothing measurable in the step, so it keeps the pair).  The engine takes the new kernel for these only.
 bool srad_swin_block_wins(int d, int heads, int hidden, int no) {
   struct Shape { int d, heads, hidden, no; };
-  static const Shape wins[] = {{180, 6, 360, 32}, {212, 4, 424, 32}, {244, 2, 488, 32}};
+  static const Shape wins[] = {{180, 6, 360, 32}, {212, 4, 424, 32}, {244, 2, 488, 32}, {276, 6, 276, 32}};
   for (const Shape& s : wins)
     if (s.d == d && s.heads == heads && s.hidden == hidden && s.no == no) return true;
   return false;
@@ -617,8 +610,8 @@ int srad_launch_swin_block(const SwinBlockParams& p, hipStream_t stream) {
   // other workgroups' reads of columns [0, d)
   SRAD_REQUIRE(p.Y != p.x || (p.ldy == p.ldx && p.yoff >= p.d), "swin_block: an in-place output must lie behind the block's %d input columns", p.d);
   const BlkKey k = blk_key(p.d, p.heads, p.m, p.no);
-#define X(a, b, h, ng, gd, kgd, gm, kgm, gn, kcm) \
-  if (SRAD_BLK_MATCH(k, a, b, h, ng, gd, kgd, gm, kgm, gn, kcm)) return launch_blk<a, b, h, ng, gd, kgd, gm, kgm, gn, kcm>(p, stream);
+#define X(a, b, h, gd, kgd, gm, kgm, gn, kcm) \
+  if (SRAD_BLK_MATCH(k, a, b, h, gd, kgd, gm, kgm, gn, kcm)) return launch_blk<a, b, h, gd, kgd, gm, kgm, gn, kcm>(p, stream);
   SRAD_BLK_CFGS(X)
 #undef X
   return srad_set_error(SRAD_ERR_ARG, "swin_block: no kernel instance for this geometry");
