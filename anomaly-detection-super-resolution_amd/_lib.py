@@ -80,6 +80,12 @@ _SIG = {
                                      C.c_int, C.c_float, C.c_float, _P]),
     "srad_adam_ema_step_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                          _P, _P]),
+    "srad_grad_guard_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "srad_grad_guard_partials": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, C.c_int, _P]),
+    "srad_grad_guard_finalize": (C.c_int, [_P, C.c_size_t, C.c_int, _P, C.c_float, C.c_float, C.c_double, _P]),
+    "srad_adam_guarded_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
+    "srad_adam_ema_guarded_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                             _P, _P]),
     "srad_set4": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     # DRN
     "srad_drn_create": (C.c_int, [C.POINTER(DrnConfig), C.POINTER(_P)]),

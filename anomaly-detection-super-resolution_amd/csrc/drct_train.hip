@@ -632,6 +632,44 @@ int srad_adam_ema_step_dev(float* params, const float* grads, float* exp_avg, fl
                                   dev_hyper, reinterpret_cast<hipStream_t>(stream));
 }
 
+/* Guarded step (include/srad.h): the workspace size, the two guard launches and the two Adam steps that obey the record */
+int srad_grad_guard_workspace(int64_t n, int* slots, size_t* bytes) {
+  SRAD_REQUIRE(n > 0 && (slots || bytes), "grad_guard_workspace: bad argument");
+  const int s = srad_guard_slots_for((size_t)n);
+  if (slots) *slots = s;
+  if (bytes) *bytes = SRAD_GUARD_HEADER_BYTES + (size_t)s * sizeof(double);
+  return SRAD_OK;
+}
+
+int srad_grad_guard_partials(const float* grads, int64_t n, void* workspace, size_t workspace_bytes, int first_slot,
+                             void* stream) {
+  SRAD_REQUIRE(grads && workspace && n > 0, "grad_guard_partials: bad argument");
+  return srad_launch_grad_guard_partials(grads, (size_t)n, workspace, workspace_bytes, first_slot,
+                                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int srad_grad_guard_finalize(void* workspace, size_t workspace_bytes, int n_slots, const float* dev_hyper, float beta1,
+                             float beta2, double max_norm, void* stream) {
+  SRAD_REQUIRE(workspace && dev_hyper, "grad_guard_finalize: bad argument");
+  return srad_launch_grad_guard_finalize(workspace, workspace_bytes, n_slots, dev_hyper, beta1, beta2, max_norm,
+                                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int srad_adam_guarded_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
+                           float beta2, float eps, float weight_decay, const void* workspace, void* stream) {
+  SRAD_REQUIRE(params && grads && exp_avg && exp_avg_sq && workspace && n > 0, "adam_guarded_step: bad argument");
+  return srad_launch_adam_guarded(params, grads, exp_avg, exp_avg_sq, (size_t)n, beta1, beta2, eps, weight_decay, workspace,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+int srad_adam_ema_guarded_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                               float beta1, float beta2, float eps, float weight_decay, float ema_decay, const void* workspace,
+                               void* stream) {
+  SRAD_REQUIRE(params && grads && exp_avg && exp_avg_sq && workspace && n > 0, "adam_ema_guarded_step: bad argument");
+  return srad_launch_adam_ema_guarded(params, grads, exp_avg, exp_avg_sq, ema, (size_t)n, beta1, beta2, eps, weight_decay,
+                                      ema_decay, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
 /* dst[0..3] = (a, b, c, d) by value through a kernel: how the host hands Adam's per-step scalars to a replayed graph */
 int srad_set4(float* dst, float a, float b, float c, float d, void* stream) {
   SRAD_REQUIRE(dst, "set4: null argument");

@@ -8,6 +8,8 @@
 //   l1_grad_kernel          the L1 loss's gradient seed
 //   adam_kernel, adam_dev_kernel, set4_kernel         torch.optim.Adam on flat buffers, its per-step scalars
 //   adam_ema_kernel, adam_ema_dev_kernel              the same step, also keeping the weights' exponential moving average
+//   sumsq_partials_kernel, grad_guard_finalize_kernel the gradient's global L2 norm in fp64 and the apply / clip / skip decision
+//   adam_guarded_kernel, adam_ema_guarded_kernel      the two device-scalar steps behind that decision
 //
 // The weight gradients and the split-K queue's launches are kernels_wgrad.hip.  Data gradients (dX = dY W) are not here
 // either: they are the forward GEMM of kernels_gemm.hip run on the transposed packed weight (srad_launch_pack_weight_transposed).
@@ -235,6 +237,109 @@ __global__ void adam_ema_dev_kernel(float* __restrict__ p, const float* __restri
   adam_body<true>(p, g, m, v, n, hyper[0], b1, b2, eps, wd, hyper[1], hyper[2], hyper[3], ema, d, omd);
 }
 
+// ------------------------------------------------------------------------------------------
+// Guarded step (DESIGN.md "Guarded step"): the gradient's global L2 norm, one device-side decision (apply, scale or skip),
+// and the Adam step that obeys it.  Three launches, no atomics, no host read: the whole thing replays inside a hipGraph.
+// ------------------------------------------------------------------------------------------
+
+// all 64 lanes' values summed in a fixed tree; lane 0 holds the result
+__device__ __forceinline__ double wave_sum_f64(double s) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  return s;
+}
+// the workgroup's four wave sums added in wave order; thread 0 holds the result
+__device__ __forceinline__ double block_sum_f64(double s, double* red) {
+  s = wave_sum_f64(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ double sq4_f64(const f32x4 x, double a) {
+  a = fma((double)x[0], (double)x[0], a);      // the fp64 square of an fp32 value is exact: no overflow, one rounding per add
+  a = fma((double)x[1], (double)x[1], a);
+  a = fma((double)x[2], (double)x[2], a);
+  return fma((double)x[3], (double)x[3], a);
+}
+
+// part[blockIdx.x] = this workgroup's share of sum g[i]^2, squares and sums in fp64.  g needs only float alignment: the up
+// to three floats in front of the first 16-byte boundary and the up to three behind the last whole float4 are read one by
+// one, everything between as 16-byte loads, four in flight per thread.  Which thread adds which element in which order
+// depends on n, the grid (a function of n) and g's offset from a 16-byte boundary alone, so the sum's bits repeat.
+__global__ __launch_bounds__(256) void sumsq_partials_kernel(const float* __restrict__ g, size_t n, double* __restrict__ part) {
+  __shared__ double red[4];
+  const size_t tid = blockIdx.x * (size_t)256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  size_t head = ((16 - ((uintptr_t)g & 15)) & 15) >> 2;
+  if (head > n) head = n;
+  const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g + head);
+  const size_t nvec = (n - head) >> 2, tail0 = head + 4 * nvec;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  size_t i = tid;
+  for (; i + 3 * stride < nvec; i += 4 * stride) {
+    const f32x4 x0 = g4[i], x1 = g4[i + stride], x2 = g4[i + 2 * stride], x3 = g4[i + 3 * stride];
+    a0 = sq4_f64(x0, a0); a1 = sq4_f64(x1, a1); a2 = sq4_f64(x2, a2); a3 = sq4_f64(x3, a3);
+  }
+  for (; i < nvec; i += stride) a0 = sq4_f64(g4[i], a0);
+  if (tid < head) { const double x = (double)g[tid]; a1 = fma(x, x, a1); }
+  if (tid < n - tail0) { const double x = (double)g[tail0 + tid]; a2 = fma(x, x, a2); }
+  const double s = block_sum_f64((a0 + a1) + (a2 + a3), red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__device__ __forceinline__ double ipow_f64(double b, long long e) {      // b^e by squaring, e >= 0
+  double r = 1.0;
+  for (; e; e >>= 1, b *= b)
+    if (e & 1) r *= b;
+  return r;
+}
+
+// One workgroup: thread t adds the slots [t c, (t + 1) c), c = ceil(n_slots / 256), in index order, the 256 sums go through
+// the same fixed tree as above; thread 0 then decides and writes the state and the record Adam reads.
+__global__ __launch_bounds__(256) void grad_guard_finalize_kernel(const double* __restrict__ part, int n_slots,
+                                                                  SradGuardState* __restrict__ st, SradGuardRecord* __restrict__ rec,
+                                                                  const float* __restrict__ hyper_in, float b1, float b2,
+                                                                  double max_norm) {
+  __shared__ double red[4];
+  const int c = (n_slots + 255) / 256, lo = min((int)threadIdx.x * c, n_slots), hi = min(lo + c, n_slots);
+  double s = 0.0;
+  for (int j = lo; j < hi; ++j) s += part[j];
+  s = block_sum_f64(s, red);
+  if (threadIdx.x != 0) return;
+  const float lr = hyper_in[0];
+  const double gs = (double)hyper_in[3];
+  const double norm = gs * sqrt(s);                       // non-finite exactly when some gradient element is
+  st->last_norm = norm;
+  if (!isfinite(norm)) {
+    st->skipped += 1;
+    rec->hyper[0] = lr; rec->hyper[1] = 1.f; rec->hyper[2] = 1.f; rec->hyper[3] = 0.f;
+    rec->apply = 0;
+    return;
+  }
+  const double coef = fmin(1.0, max_norm / (norm + 1e-6));     // clip_grad_norm_; max_norm = +inf gives exactly 1
+  if (coef < 1.0) st->clipped += 1;
+  const long long t = st->applied + 1;                    // bias correction counts the steps that were applied
+  st->applied = t;
+  rec->hyper[0] = lr;
+  rec->hyper[1] = (float)(1.0 - ipow_f64((double)b1, t));
+  rec->hyper[2] = (float)sqrt(1.0 - ipow_f64((double)b2, t));
+  rec->hyper[3] = (float)(gs * coef);
+  rec->apply = 1;
+}
+
+// adam_dev_kernel / adam_ema_dev_kernel behind the guard's record: a skipped step returns before any access to the five
+// buffers; an applied one is the same adam_body on the record's four scalars
+__global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                    size_t n, float b1, float b2, float eps, float wd, const SradGuardRecord* __restrict__ rec) {
+  if (rec->apply == 0) return;
+  adam_body<false>(p, g, m, v, n, rec->hyper[0], b1, b2, eps, wd, rec->hyper[1], rec->hyper[2], rec->hyper[3]);
+}
+__global__ void adam_ema_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                        float* __restrict__ v, float* __restrict__ ema, size_t n, float b1, float b2, float eps,
+                                        float wd, const SradGuardRecord* __restrict__ rec, float d, float omd) {
+  if (rec->apply == 0) return;
+  adam_body<true>(p, g, m, v, n, rec->hyper[0], b1, b2, eps, wd, rec->hyper[1], rec->hyper[2], rec->hyper[3], ema, d, omd);
+}
+
 }  // namespace
 
 
@@ -344,6 +449,82 @@ int srad_launch_adam_ema_dev(float* p, const float* g, float* m, float* v, float
   SradProfScope prof(stream, SRAD_K_OPTIM, 15.0 * n, 36.0 * n);
   hipLaunchKernelGGL(adam_ema_dev_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, m, v, ema, n, beta1, beta2, eps,
                      weight_decay, hyper, ema_decay, omd);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Guarded step: workspace = [SradGuardState | SradGuardRecord | fp64 partial slots]
+// ------------------------------------------------------------------------------------------
+int srad_guard_slots_for(size_t n) { return grid_for(n); }
+
+static inline double* guard_partials(void* ws) { return reinterpret_cast<double*>((char*)ws + SRAD_GUARD_HEADER_BYTES); }
+static inline SradGuardRecord* guard_record(const void* ws) {
+  return reinterpret_cast<SradGuardRecord*>((char*)const_cast<void*>(ws) + sizeof(SradGuardState));
+}
+// does the byte range [ws, ws + bytes) touch q[0..nq)?
+static inline bool guard_overlaps(const void* ws, size_t bytes, const float* q, size_t nq) {
+  const uintptr_t a = (uintptr_t)ws, b = (uintptr_t)q;
+  return a < b + nq * sizeof(float) && b < a + bytes;
+}
+
+int srad_launch_grad_guard_partials(const float* g, size_t n, void* ws, size_t ws_bytes, int first_slot, hipStream_t stream) {
+  SRAD_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)g & 3) == 0, "grad_guard_partials: the workspace must be 16-byte aligned, the gradients float aligned");
+  SRAD_REQUIRE(first_slot >= 0, "grad_guard_partials: first_slot %d is negative", first_slot);
+  const int slots = grid_for(n);
+  const size_t need = SRAD_GUARD_HEADER_BYTES + ((size_t)first_slot + slots) * sizeof(double);
+  SRAD_REQUIRE(ws_bytes >= need, "grad_guard_partials: workspace too small (%zu bytes, slots %d..%d need %zu)", ws_bytes, first_slot,
+               first_slot + slots - 1, need);
+  SRAD_REQUIRE(!guard_overlaps(ws, ws_bytes, g, n), "grad_guard_partials: the workspace overlaps the gradients");
+  SradProfScope prof(stream, SRAD_K_OPTIM, 2.0 * n, 4.0 * n);
+  hipLaunchKernelGGL(sumsq_partials_kernel, dim3(slots), dim3(256), 0, stream, g, n, guard_partials(ws) + first_slot);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_launch_grad_guard_finalize(void* ws, size_t ws_bytes, int n_slots, const float* hyper, float beta1, float beta2,
+                                    double max_norm, hipStream_t stream) {
+  SRAD_REQUIRE(((uintptr_t)ws & 15) == 0, "grad_guard_finalize: the workspace must be 16-byte aligned");
+  SRAD_REQUIRE(n_slots >= 1, "grad_guard_finalize: n_slots must be positive (got %d)", n_slots);
+  SRAD_REQUIRE(max_norm > 0.0, "grad_guard_finalize: max_norm must be > 0 (got %g; +inf = no clipping)", max_norm);     // NaN too
+  const size_t need = SRAD_GUARD_HEADER_BYTES + (size_t)n_slots * sizeof(double);
+  SRAD_REQUIRE(ws_bytes >= need, "grad_guard_finalize: workspace too small (%zu bytes, %d slots need %zu)", ws_bytes, n_slots, need);
+  SRAD_REQUIRE(!guard_overlaps(ws, ws_bytes, hyper, 4), "grad_guard_finalize: the workspace overlaps dev_hyper");
+  hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(256), 0, stream, guard_partials(ws), n_slots,
+                     reinterpret_cast<SradGuardState*>(ws), guard_record(ws), hyper, beta1, beta2, max_norm);
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+// the guard's state and record may not share a byte with a buffer the step reads or writes
+static int adam_guarded_check(const char* what, const float* p, const float* g, const float* m, const float* v, const float* ema,
+                              size_t n, const void* ws) {
+  SRAD_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: the workspace must be 16-byte aligned", what);
+  const size_t hb = SRAD_GUARD_HEADER_BYTES;
+  SRAD_REQUIRE(!guard_overlaps(ws, hb, p, n) && !guard_overlaps(ws, hb, g, n) && !guard_overlaps(ws, hb, m, n) &&
+                   !guard_overlaps(ws, hb, v, n) && !(ema && guard_overlaps(ws, hb, ema, n)),
+               "%s: the guard state overlaps another buffer", what);
+  return SRAD_OK;
+}
+
+int srad_launch_adam_guarded(float* p, const float* g, float* m, float* v, size_t n, float beta1, float beta2, float eps,
+                             float weight_decay, const void* ws, hipStream_t stream) {
+  SRAD_TRY(adam_guarded_check("adam_guarded_step", p, g, m, v, nullptr, n, ws));
+  SradProfScope prof(stream, SRAD_K_OPTIM, 12.0 * n, 28.0 * n);
+  hipLaunchKernelGGL(adam_guarded_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, m, v, n, beta1, beta2, eps, weight_decay,
+                     guard_record(ws));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int srad_launch_adam_ema_guarded(float* p, const float* g, float* m, float* v, float* ema, size_t n, float beta1, float beta2,
+                                 float eps, float weight_decay, float ema_decay, const void* ws, hipStream_t stream) {
+  float omd;
+  SRAD_TRY(adam_ema_check("adam_ema_guarded_step", p, g, m, v, ema, n, ema_decay, &omd));
+  SRAD_TRY(adam_guarded_check("adam_ema_guarded_step", p, g, m, v, ema, n, ws));
+  SradProfScope prof(stream, SRAD_K_OPTIM, 15.0 * n, 36.0 * n);
+  hipLaunchKernelGGL(adam_ema_guarded_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, m, v, ema, n, beta1, beta2, eps,
+                     weight_decay, guard_record(ws), ema_decay, omd);
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

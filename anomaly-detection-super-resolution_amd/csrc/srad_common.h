@@ -519,6 +519,22 @@ int srad_launch_adam_ema(float* p, const float* g, float* m, float* v, float* em
                          float eps, float weight_decay, int step, float grad_scale, float ema_decay, hipStream_t stream);
 int srad_launch_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, size_t n, float beta1, float beta2,
                              float eps, float weight_decay, float ema_decay, const float* hyper, hipStream_t stream);
+// Guarded step (DESIGN.md "Guarded step").  One device workspace: [SradGuardState | SradGuardRecord | fp64 partial slots].
+struct SradGuardState { long long applied, skipped, clipped; double last_norm; };     // survives from step to step
+struct SradGuardRecord { float hyper[4]; int apply; int pad[3]; };                      // [lr, 1 - b1^t, sqrt(1 - b2^t), grad_scale * coef], rewritten by every finalize
+#define SRAD_GUARD_HEADER_BYTES (sizeof(SradGuardState) + sizeof(SradGuardRecord))
+static_assert(sizeof(SradGuardState) == 32 && sizeof(SradGuardRecord) == 32, "the guard workspace layout is part of the C ABI");
+int srad_guard_slots_for(size_t n);                 // partial slots (= workgroups) of the sum-of-squares pass over n floats
+// sum g[i]^2 in fp64 into the slots first_slot .. first_slot + srad_guard_slots_for(n) - 1, one per workgroup, no atomics
+int srad_launch_grad_guard_partials(const float* g, size_t n, void* ws, size_t ws_bytes, int first_slot, hipStream_t stream);
+// slots 0 .. n_slots - 1 -> norm, coef, apply; updates the state, writes the record (hyper: [lr, -, -, grad_scale] on the device)
+int srad_launch_grad_guard_finalize(void* ws, size_t ws_bytes, int n_slots, const float* hyper, float beta1, float beta2,
+                                    double max_norm, hipStream_t stream);
+// srad_launch_adam_dev / srad_launch_adam_ema_dev on the record's scalars; nothing is touched when the record says skip
+int srad_launch_adam_guarded(float* p, const float* g, float* m, float* v, size_t n, float beta1, float beta2, float eps,
+                             float weight_decay, const void* ws, hipStream_t stream);
+int srad_launch_adam_ema_guarded(float* p, const float* g, float* m, float* v, float* ema, size_t n, float beta1, float beta2,
+                                 float eps, float weight_decay, float ema_decay, const void* ws, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
 // misc kernels

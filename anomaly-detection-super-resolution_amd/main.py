@@ -112,6 +112,10 @@ def build_train_opt(args):
     if getattr(args, 'ema', False):                              # only then: a run without it writes today's config.txt
         opt.ema = True
         opt.ema_decay = float(getattr(opt, 'ema_decay', 0.999))  # the DRN option set has no such field
+    if getattr(args, 'grad_clip', None) is not None:             # the guarded step: each field only with its flag
+        opt.grad_clip = float(args.grad_clip)
+    if getattr(args, 'skip_nonfinite', False):
+        opt.skip_nonfinite = True
     return opt
 
 

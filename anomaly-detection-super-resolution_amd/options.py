@@ -204,6 +204,12 @@ def parse_train_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "validation runs on it and model/model_ema_{latest,best}.pt are written beside the raw weights")
     p.add_argument('--ema-decay', type=_ema_decay, default=None, metavar='D',
                    help="decay of --ema, in [0, 1); default: the option set's ema_decay (0.999)")
+    p.add_argument('--grad-clip', type=_grad_clip, default=None, metavar='MAX_NORM',
+                   help="clip the gradients' global L2 norm to MAX_NORM (> 0) before every Adam step, on the device "
+                        "(torch.nn.utils.clip_grad_norm_; BasicSR's use_grad_clip); a guarded step also skips non-finite gradients")
+    p.add_argument('--skip-nonfinite', action='store_true', default=False,
+                   help="drop every optimizer step whose gradients hold an inf or a NaN (what the reference's GradScaler.step did): "
+                        "weights, moments and the weight average keep their bits and the bias correction counts applied steps")
     _with_config(p, pre_args)
     args = p.parse_args(argv)
     if args.ema_decay is not None:                            # a value from a config file gets the command line's check
@@ -211,7 +217,19 @@ def parse_train_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             args.ema_decay = _ema_decay(str(args.ema_decay))
         except (argparse.ArgumentTypeError, ValueError) as e:
             p.error(f"argument --ema-decay: {e}")
+    if args.grad_clip is not None:                            # the same for --grad-clip
+        try:
+            args.grad_clip = _grad_clip(str(args.grad_clip))
+        except (argparse.ArgumentTypeError, ValueError) as e:
+            p.error(f"argument --grad-clip: {e}")
     return args
+
+
+def _grad_clip(text: str) -> float:
+    v = float(text)
+    if not v > 0.0:                                           # zero, negatives and NaN
+        raise argparse.ArgumentTypeError(f"{text} is not a norm > 0")
+    return v
 
 
 def _ema_decay(text: str) -> float:

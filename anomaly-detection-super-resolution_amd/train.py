@@ -9,6 +9,7 @@ of the earlier layers is still running.  With the ``nccl`` backend that is RCCL 
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import struct
 from typing import List, Optional
@@ -18,9 +19,90 @@ import torch
 from . import _lib as L
 
 
+def guard_reference(grads, grad_scale: float = 1.0, max_norm: float = math.inf):
+    """The guard's decision in numpy fp64 (DESIGN.md "Guarded step"), for tests and for reading a log: ``grads`` is one array
+    or a list of arrays under one norm.  Returns ``(norm, coef, apply)``; ``coef`` is None for a skipped step."""
+    import numpy as np
+    parts = grads if isinstance(grads, (list, tuple)) else [grads]
+    with np.errstate(over="ignore", invalid="ignore"):
+        sumsq = sum(float(np.sum(np.square(np.asarray(g).astype(np.float64).ravel()))) for g in parts)
+        norm = float(grad_scale) * math.sqrt(sumsq) if not math.isnan(sumsq) else math.nan
+    if not math.isfinite(norm):
+        return norm, None, False
+    return norm, min(1.0, float(max_norm) / (norm + 1e-6)), True
+
+
+def guard_reference_run(norms, max_norm: float = math.inf):
+    """``(applied, skipped, clipped)`` after a sequence of steps with the given norms."""
+    applied = sum(1 for x in norms if math.isfinite(x))
+    clipped = sum(1 for x in norms if math.isfinite(x) and float(max_norm) / (x + 1e-6) < 1.0)
+    return applied, len(norms) - applied, clipped
+
+
+class GradGuard:
+    """The device side of a guarded optimizer step (C ABI ``srad_grad_guard_*``; DESIGN.md "Guarded step"): one workspace
+    holding the state ``applied / skipped / clipped / last_norm``, the record the guarded Adam kernels read, and the fp64
+    partial sums.  ``run(grads, dev_hyper)`` enqueues the sum-of-squares pass over every tensor and the finalize; nothing here
+    reads the device except ``stats()``."""
+
+    def __init__(self, sizes, device, betas, max_grad_norm: Optional[float]):
+        max_norm = math.inf if max_grad_norm is None else float(max_grad_norm)
+        if not max_norm > 0.0:                             # NaN too
+            raise ValueError(f"max_grad_norm must be > 0 (got {max_grad_norm})")
+        self.max_norm, self.betas = max_norm, tuple(betas)
+        self.sizes = [int(n) for n in sizes]
+        self.slots = []
+        for n in self.sizes:
+            s = C.c_int()
+            L.check(L.lib().srad_grad_guard_workspace(n, C.byref(s), None), "grad_guard_workspace")
+            self.slots.append(s.value)
+        self.nbytes = 64 + 8 * sum(self.slots)
+        self.ws = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)      # the caching allocator aligns to 512 bytes
+        self.hyper = torch.zeros(4, dtype=torch.float32, device=device)           # [lr, -, -, grad_scale] of an eager step
+
+    def run(self, grads, dev_hyper: torch.Tensor) -> None:
+        lib, stream, first = L.lib(), L.current_stream_ptr(), 0
+        if [g.numel() for g in grads] != self.sizes:
+            raise RuntimeError(f"the guard was sized for tensors of {self.sizes} elements, got {[g.numel() for g in grads]}")
+        for g, s in zip(grads, self.slots):
+            L.check(lib.srad_grad_guard_partials(L.dptr(g), g.numel(), L.dptr(self.ws), self.nbytes, first, stream),
+                    "grad_guard_partials")
+            first += s
+        L.check(lib.srad_grad_guard_finalize(L.dptr(self.ws), self.nbytes, first, L.dptr(dev_hyper), self.betas[0], self.betas[1],
+                                             self.max_norm, stream), "grad_guard_finalize")
+
+    def set_hyper(self, lr: float, grad_scale: float) -> torch.Tensor:
+        L.check(L.lib().srad_set4(L.dptr(self.hyper), float(lr), 0.0, 0.0, float(grad_scale), L.current_stream_ptr()), "set4")
+        return self.hyper
+
+    @property
+    def state(self) -> torch.Tensor:
+        return self.ws[:32]
+
+    @property
+    def record(self) -> torch.Tensor:
+        """The four Adam scalars of the last finalize, as a float32 view of the workspace."""
+        return self.ws[32:48].view(torch.float32)
+
+    @property
+    def apply_flag(self) -> torch.Tensor:
+        return self.ws[48:52].view(torch.int32)
+
+    def stats(self) -> dict:
+        host = self.state.cpu()                            # the one synchronising read
+        a, s, c = (int(x) for x in host[:24].view(torch.int64))
+        return {"applied": a, "skipped": s, "clipped": c, "last_norm": float(host[24:32].view(torch.float64)[0])}
+
+
 class FusedAdam:
     """torch.optim.Adam arithmetic (src/trainer.py:49-59: betas (0.9, 0.999), eps 1e-8, L2 weight decay)
     as ONE kernel over the model's flat parameter buffer (C ABI ``srad_adam_step``).
+
+    ``max_grad_norm`` (a float > 0) and ``skip_nonfinite`` switch the guard on (DESIGN.md "Guarded step"): every step first
+    takes the gradient's global L2 norm on the device, scales the gradient by ``min(1, max_grad_norm / (norm + 1e-6))`` and
+    drops the whole step, bit for bit, when the norm is not finite.  ``skip_nonfinite`` alone clips nothing.  ``step()`` and
+    ``step_dev()`` then run the same three launches, the bias correction counts the applied steps on the device, and
+    ``guard_stats()`` is the only call that reads anything back.
 
     ``ema_decay`` (a float in [0, 1); default None = no average): the same launch also keeps the exponential moving average of
     the weights in ``model.flat_ema`` (C ABI ``srad_adam_ema_step``; DESIGN.md "Weight EMA"): after every step
@@ -28,7 +110,9 @@ class FusedAdam:
     the captured training graphs need nothing new per replay."""
 
     def __init__(self, model, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 ema_decay: Optional[float] = None):
+                 ema_decay: Optional[float] = None, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:     # NaN too
+            raise ValueError(f"max_grad_norm must be > 0 (got {max_grad_norm})")
         if ema_decay is not None:
             ema_decay = float(ema_decay)
             if not 0.0 <= ema_decay < 1.0:                 # NaN too
@@ -44,6 +128,9 @@ class FusedAdam:
         self.exp_avg_sq = torch.zeros_like(model.flat_params)
         self.step_count = 0
         self.param_groups = [{"lr": self.lr}]          # what lr schedulers read / write
+        self.guard = None
+        if max_grad_norm is not None or skip_nonfinite:
+            self.guard = GradGuard([model.flat_params.numel()], model.flat_params.device, self.betas, max_grad_norm)
 
     def zero_grad(self, set_to_none: bool = False) -> None:
         self.model.zero_grad()
@@ -53,6 +140,9 @@ class FusedAdam:
         m._refuse_under_ema("an optimizer step")
         self.step_count += 1
         lr = float(self.param_groups[0]["lr"])
+        if self.guard is not None:                         # the device route: set4, the guard, guarded Adam (as a graphed step)
+            self._guarded(self.guard.set_hyper(lr, grad_scale))
+            return
         if self.ema_decay is not None:
             L.check(L.lib().srad_adam_ema_step(L.dptr(m.flat_params), L.dptr(m.flat_grads), L.dptr(self.exp_avg),
                                                L.dptr(self.exp_avg_sq), L.dptr(m.flat_ema), m.flat_params.numel(), lr,
@@ -77,6 +167,9 @@ class FusedAdam:
         carries no step-dependent argument, so it can sit inside a captured hipGraph.  The caller bumps ``step_count``."""
         m = self.model
         m._refuse_under_ema("an optimizer step")
+        if self.guard is not None:                         # reads dev_hyper[0] (lr) and [3] (grad_scale); counts t itself
+            self._guarded(dev_hyper)
+            return
         if self.ema_decay is not None:
             L.check(L.lib().srad_adam_ema_step_dev(L.dptr(m.flat_params), L.dptr(m.flat_grads), L.dptr(self.exp_avg),
                                                    L.dptr(self.exp_avg_sq), L.dptr(m.flat_ema), m.flat_params.numel(),
@@ -90,11 +183,34 @@ class FusedAdam:
                 "adam_step_dev")
         m.mark_params_dirty()
 
+    def _guarded(self, dev_hyper: torch.Tensor) -> None:
+        m, gd = self.model, self.guard
+        gd.run([m.flat_grads], dev_hyper)
+        if self.ema_decay is not None:
+            L.check(L.lib().srad_adam_ema_guarded_step(L.dptr(m.flat_params), L.dptr(m.flat_grads), L.dptr(self.exp_avg),
+                                                       L.dptr(self.exp_avg_sq), L.dptr(m.flat_ema), m.flat_params.numel(),
+                                                       self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_decay,
+                                                       L.dptr(gd.ws), L.current_stream_ptr()), "adam_ema_guarded_step")
+        else:
+            L.check(L.lib().srad_adam_guarded_step(L.dptr(m.flat_params), L.dptr(m.flat_grads), L.dptr(self.exp_avg),
+                                                   L.dptr(self.exp_avg_sq), m.flat_params.numel(), self.betas[0], self.betas[1],
+                                                   self.eps, self.weight_decay, L.dptr(gd.ws), L.current_stream_ptr()),
+                    "adam_guarded_step")
+        m.mark_params_dirty()
+
+    def guard_stats(self) -> dict:
+        """``applied``, ``skipped``, ``clipped`` step counts and ``last_norm`` of the guard; synchronises."""
+        if self.guard is None:
+            raise RuntimeError("guard_stats() needs max_grad_norm or skip_nonfinite")
+        return self.guard.stats()
+
     def state_dict(self):
         sd = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
               "lr": self.param_groups[0]["lr"]}
         if self.ema_decay is not None:
             sd["ema"], sd["ema_decay"] = self.model.flat_ema, self.ema_decay
+        if self.guard is not None:
+            sd["guard_state"] = self.guard.state.clone()   # 32 bytes, copied on the device: no read-back
         return sd
 
     def load_state_dict(self, sd):
@@ -105,18 +221,27 @@ class FusedAdam:
         if self.ema_decay is not None and "ema" in sd:     # a state without the key leaves the average alone
             self.model.flat_ema.copy_(sd["ema"])
             self.model.mark_params_dirty()
+        if self.guard is not None and "guard_state" in sd:
+            self.guard.state.copy_(sd["guard_state"])
 
 
 class TensorAdam:
     """The same Adam kernel applied tensor by tensor: the optimizer of a dual regression model (two small convolution
     weights; src/trainer.py:62-73).  ``step(grad_scale)`` divides the (all-reduced) gradients by the world size."""
 
-    def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:     # NaN too
+            raise ValueError(f"max_grad_norm must be > 0 (got {max_grad_norm})")
         self.params = [p for p in params]
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
         self.state = [(torch.zeros_like(p.data), torch.zeros_like(p.data)) for p in self.params]
         self.step_count = 0
         self.param_groups = [{"lr": self.lr}]
+        # the guard (as FusedAdam's): ONE norm over all the tensors, so every tensor needs a gradient at every step
+        self.guard = None
+        if max_grad_norm is not None or skip_nonfinite:
+            self.guard = GradGuard([p.numel() for p in self.params], self.params[0].device, self.betas, max_grad_norm)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         for p in self.params:
@@ -125,6 +250,9 @@ class TensorAdam:
     def step(self, grad_scale: float = 1.0) -> None:
         self.step_count += 1
         lr = float(self.param_groups[0]["lr"])
+        if self.guard is not None:
+            self._guarded(self.guard.set_hyper(lr, grad_scale))
+            return
         for p, (m, v) in zip(self.params, self.state):
             if p.grad is None:
                 continue
@@ -143,6 +271,9 @@ class TensorAdam:
 
     def step_dev(self, dev_hyper: torch.Tensor) -> None:
         """``step()`` with the per-step scalars on the GPU (inside a captured hipGraph); the caller bumps ``step_count``."""
+        if self.guard is not None:
+            self._guarded(dev_hyper)
+            return
         for p, (m, v) in zip(self.params, self.state):
             if p.grad is None:
                 continue
@@ -153,9 +284,32 @@ class TensorAdam:
                                                self.betas[1], self.eps, self.weight_decay, L.dptr(dev_hyper),
                                                L.current_stream_ptr()), "adam_step_dev")
 
+    def _guarded(self, dev_hyper: torch.Tensor) -> None:
+        grads = []
+        for p in self.params:
+            if p.grad is None:
+                raise RuntimeError("a guarded TensorAdam takes one norm over all its tensors: every one needs a gradient")
+            if not p.data.is_contiguous():
+                raise RuntimeError("TensorAdam needs contiguous parameters")
+            grads.append(p.grad.detach().float().contiguous())
+        self.guard.run(grads, dev_hyper)
+        for p, g, (m, v) in zip(self.params, grads, self.state):
+            L.check(L.lib().srad_adam_guarded_step(L.dptr(p.data), L.dptr(g), L.dptr(m), L.dptr(v), p.numel(), self.betas[0],
+                                                   self.betas[1], self.eps, self.weight_decay, L.dptr(self.guard.ws),
+                                                   L.current_stream_ptr()), "adam_guarded_step")
+
+    def guard_stats(self) -> dict:
+        """As ``FusedAdam.guard_stats``."""
+        if self.guard is None:
+            raise RuntimeError("guard_stats() needs max_grad_norm or skip_nonfinite")
+        return self.guard.stats()
+
     def state_dict(self):
-        return {"step": self.step_count, "lr": self.param_groups[0]["lr"],
-                "exp_avg": [m for m, _ in self.state], "exp_avg_sq": [v for _, v in self.state]}
+        sd = {"step": self.step_count, "lr": self.param_groups[0]["lr"],
+              "exp_avg": [m for m, _ in self.state], "exp_avg_sq": [v for _, v in self.state]}
+        if self.guard is not None:
+            sd["guard_state"] = self.guard.state.clone()
+        return sd
 
     def load_state_dict(self, sd):
         self.step_count = int(sd["step"])
@@ -163,6 +317,8 @@ class TensorAdam:
         for (m, v), a, b in zip(self.state, sd["exp_avg"], sd["exp_avg_sq"]):
             m.copy_(a)
             v.copy_(b)
+        if self.guard is not None and "guard_state" in sd:
+            self.guard.state.copy_(sd["guard_state"])
 
 
 def cosine_lr(base_lr: float, epoch: int, t_max: float, eta_min: float) -> float:

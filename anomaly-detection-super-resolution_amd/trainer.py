@@ -59,16 +59,28 @@ def quantize(img, rgb_range):
     return M.quantize(img, rgb_range)
 
 
+def _guard_args(opt) -> dict:
+    """``opt.grad_clip`` / ``opt.skip_nonfinite`` as optimizer keywords; empty (today's optimizer) when neither is set."""
+    kw = {}
+    if getattr(opt, "grad_clip", None) is not None:
+        kw["max_grad_norm"] = float(opt.grad_clip)
+    if getattr(opt, "skip_nonfinite", False):
+        kw["skip_nonfinite"] = True
+    return kw
+
+
 def make_optimizer(opt, my_model) -> FusedAdam:
-    """src/trainer.py:49-59.  ``opt.ema``: the same kernel also keeps the weight average (decay ``opt.ema_decay``)."""
+    """src/trainer.py:49-59.  ``opt.ema``: the same kernel also keeps the weight average (decay ``opt.ema_decay``);
+    ``opt.grad_clip`` / ``opt.skip_nonfinite``: the step is guarded (DESIGN.md "Guarded step")."""
     ema = dict(ema_decay=float(getattr(opt, "ema_decay", 0.999))) if getattr(opt, "ema", False) else {}
     return FusedAdam(my_model.get_model() if hasattr(my_model, "get_model") else my_model, lr=opt.lr,
-                     betas=(opt.beta1, opt.beta2), eps=opt.epsilon, weight_decay=opt.weight_decay, **ema)
+                     betas=(opt.beta1, opt.beta2), eps=opt.epsilon, weight_decay=opt.weight_decay, **ema, **_guard_args(opt))
 
 
 def make_dual_optimizer(opt, dual_models) -> List[TensorAdam]:
-    """src/trainer.py:62-73: one Adam per dual model."""
-    return [TensorAdam(dm.parameters(), lr=opt.lr, betas=(opt.beta1, opt.beta2), eps=opt.epsilon, weight_decay=opt.weight_decay)
+    """src/trainer.py:62-73: one Adam per dual model, each with a guard of its own when the run has one."""
+    return [TensorAdam(dm.parameters(), lr=opt.lr, betas=(opt.beta1, opt.beta2), eps=opt.epsilon, weight_decay=opt.weight_decay,
+                       **_guard_args(opt))
             for dm in dual_models]
 
 
@@ -181,6 +193,9 @@ class Trainer():
             self.loader_train.set_epoch(epoch)
         timer_data, timer_model = timer(), timer()
         n_batches = 0
+        guarded = [o for o in [self.optimizer] + (self.dual_optimizers if self.dual_model else [])
+                   if getattr(o, "guard", None) is not None]
+        before = [o.guard_stats() for o in guarded]
         for batch, (lr, hr, _) in enumerate(self.loader_train):
             lr, hr = self.prepare(lr, hr)
             timer_data.hold()
@@ -203,12 +218,19 @@ class Trainer():
             n_batches = batch + 1
             if (batch + 1) % self.opt.print_every == 0:
                 shown = self.loss.display_loss(batch) if self.loss is not None else ''
+                if guarded:                                # read where display_loss has just synchronised
+                    shown += '[grad norm: {:.4e}]'.format(guarded[0].guard_stats()["last_norm"])
                 self._log('[{}/{}]\t{}\t{:.1f}+{:.1f}s'.format((batch + 1) * self.opt.batch_size, len(self.loader_train.dataset),
                                                                 shown, timer_model.release(), timer_data.release()))
             timer_data.tic()
         if self.loss is not None:
             self.loss.end_log(max(n_batches, 1))
             self.error_last = self.loss.log[-1, -1]
+        if guarded:
+            now = [o.guard_stats() for o in guarded]
+            self._log('Guarded steps: {} clipped, {} skipped (non-finite gradients) of {}'.format(
+                sum(b["clipped"] - a["clipped"] for a, b in zip(before, now)),
+                sum(b["skipped"] - a["skipped"] for a, b in zip(before, now)), len(guarded) * n_batches))
         self.step()
 
     def _validate(self, s: int):

@@ -125,6 +125,36 @@ int srad_adam_ema_step(float* params, const float* grads, float* exp_avg, float*
 int srad_adam_ema_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
                            float beta1, float beta2, float eps, float weight_decay, float ema_decay, const float* dev_hyper,
                            void* stream);
+/* Guarded step: global-norm gradient clipping and a skip of every step whose gradients hold an inf or a NaN, decided on
+ * the device so that the step stays free of host reads and replays inside a hipGraph.  One device workspace per optimizer,
+ * 16-byte aligned, laid out as
+ *     bytes  0..31  state : int64 applied, int64 skipped, int64 clipped, double last_norm   (zero it once; it lives on)
+ *     bytes 32..63  record: float[4] = [lr, 1 - beta1^t, sqrt(1 - beta2^t), grad_scale * coef], int32 apply, 12 bytes unused
+ *     bytes 64..    one fp64 partial sum per slot
+ * srad_grad_guard_workspace: *slots = the slots the pass over n floats writes (a function of n alone), *bytes = 64 + 8 *slots
+ * (either may be NULL; several tensors under one norm need 64 + 8 * the sum of their slots).
+ * srad_grad_guard_partials: slot first_slot + k = workgroup k's share of sum grads[i]^2, every square and sum in fp64 (exact
+ * squares, no overflow), fixed order, no atomics, no pre-zeroed buffer; grads needs float alignment only.
+ * srad_grad_guard_finalize: sums the slots 0 .. n_slots - 1 in a fixed order; norm = grad_scale * sqrt(sum), non-finite
+ * exactly when some element is; coef = min(1, max_norm / (norm + 1e-6)) in fp64 (max_norm = +inf: exactly 1).  lr and
+ * grad_scale are dev_hyper[0] and dev_hyper[3] (device memory, srad_set4).  A finite norm sets apply = 1, t = ++applied,
+ * counts clipped when coef < 1 and writes the record with both bias corrections formed in fp64 from the fp32 betas; a
+ * non-finite one sets apply = 0 and counts skipped.  last_norm = norm either way.
+ * srad_adam_guarded_step / srad_adam_ema_guarded_step: srad_adam_step_dev / srad_adam_ema_step_dev on the record's four
+ * scalars, the same bits; with apply = 0 no buffer is read or written.
+ * Refused before anything is launched: null pointers, n <= 0, first_slot < 0, n_slots < 1, max_norm <= 0 or NaN, a
+ * workspace that is misaligned or smaller than the slots named, a workspace overlapping grads or dev_hyper, the state and
+ * record overlapping any Adam buffer, and what the unguarded steps refuse. */
+int srad_grad_guard_workspace(int64_t n, int* slots, size_t* bytes);
+int srad_grad_guard_partials(const float* grads, int64_t n, void* workspace, size_t workspace_bytes, int first_slot,
+                             void* stream);
+int srad_grad_guard_finalize(void* workspace, size_t workspace_bytes, int n_slots, const float* dev_hyper, float beta1,
+                             float beta2, double max_norm, void* stream);
+int srad_adam_guarded_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
+                           float beta2, float eps, float weight_decay, const void* workspace, void* stream);
+int srad_adam_ema_guarded_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                               float beta1, float beta2, float eps, float weight_decay, float ema_decay, const void* workspace,
+                               void* stream);
 /* dst[0..3] = (a, b, c, d), passed by value through a kernel launch (no host copy, no synchronisation) */
 int srad_set4(float* dst, float a, float b, float c, float d, void* stream);
 
