@@ -38,6 +38,14 @@ class WqStep(C.Structure):
     _fields_ = [("kind", C.c_int32), ("i", C.c_int32 * 9), ("alpha", C.c_float), ("p", C.c_void_p * 7)]
 
 
+class ResampleTable(C.Structure):
+    """One axis of srad_resize_u8 (include/srad.h srad_resample_table): the bounds on the host and the device copies."""
+    _fields_ = [("in_size", C.c_int32), ("out_size", C.c_int32), ("ksize", C.c_int32), ("bounds", C.c_void_p),
+                ("dev_bounds", C.c_void_p), ("dev_coeffs", C.c_void_p)]
+
+
+RESAMPLE_FILTERS = {"lanczos": 0, "bicubic": 1}
+
 WQ_WGRAD, WQ_WGRAD_DEFERRED, WQ_LAUNCH_DEFERRED, WQ_LN_BWD, WQ_ATTN_BWD, WQ_FLUSH = 1, 2, 3, 4, 5, 6
 WQ_FLUSH_EXPLICIT, WQ_FLUSH_BATCH, WQ_FLUSH_WS = 0, 1, 2
 
@@ -117,6 +125,11 @@ _SIG = {
     # self-ensemble x8
     "srad_ensemble_inputs": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "srad_ensemble_mean": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    # 8-bit resize (PIL-exact)
+    "srad_resample_ksize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "srad_resample_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),
+    "srad_resize_u8": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.POINTER(ResampleTable),
+                                 C.POINTER(ResampleTable), _P, _P]),
     # scorer
     "srad_to_u8_hwc": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "srad_quantize": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),

@@ -309,20 +309,40 @@ def super_resolve_u8(model, lr_u8: Sequence[np.ndarray], hr_u8: Sequence[np.ndar
     holds 8 members per image, so the automatic batch is an eighth; crop and u8 conversion come after the mean."""
     dev = model.device if hasattr(model, 'device') else next(model.parameters()).device
     if batch <= 0 and len(lr_u8):
-        batch = max(1, min(64, 65536 // max(1, lr_u8[0].shape[0] * lr_u8[0].shape[1])))
-        if self_ensemble:
-            batch = max(1, batch // 8)
+        batch = _auto_batch(lr_u8[0].shape[0], lr_u8[0].shape[1], self_ensemble)
     forward = model.forward_x8 if self_ensemble else model
     sr_out: List[torch.Tensor] = []
     for i in range(0, len(lr_u8), batch):
         lr = torch.from_numpy(np.stack(lr_u8[i:i + batch])).to(dev).permute(0, 3, 1, 2).float() * (rgb_range / 255.0)   # np2Tensor
-        sr = forward(lr)
-        if isinstance(sr, list):
-            sr = sr[-1]
-        h, w = hr_u8[i].shape[:2]
-        sr_out.append(M.to_u8_hwc(sr[..., :h, :w].contiguous(), rgb_range))
+        sr_out.append(_forward_u8(forward, lr, hr_u8[i].shape[:2], rgb_range))
     hr = torch.from_numpy(np.stack(hr_u8)).to(dev)
     return torch.cat(sr_out), hr
+
+
+def _auto_batch(lr_h: int, lr_w: int, self_ensemble: bool) -> int:
+    """Images per forward when none is asked for: as many as make ~64 k LR pixels, an eighth of that under the self-ensemble."""
+    batch = max(1, min(64, 65536 // max(1, lr_h * lr_w)))
+    return max(1, batch // 8) if self_ensemble else batch
+
+
+def _forward_u8(forward, lr: torch.Tensor, hr_hw, rgb_range: float) -> torch.Tensor:
+    """One forward of ``lr`` [b,C,h,w] (already in [0, rgb_range]): the last output, cropped to the HR size, truncated to u8 HWC."""
+    sr = forward(lr)
+    if isinstance(sr, list):
+        sr = sr[-1]
+    return M.to_u8_hwc(sr[..., :hr_hw[0], :hr_hw[1]].contiguous(), rgb_range)
+
+
+@torch.no_grad()
+def super_resolve_dev(model, lr: torch.Tensor, hr_hw, rgb_range: float, batch: int = 0, self_ensemble: bool = False) -> torch.Tensor:
+    """``super_resolve_u8`` for LR images that are on the GPU already: ``lr`` float32 [n,C,h,w] with values in [0, 255] (what
+    ``np.stack(lr_u8)`` holds there, channels first), ``hr_hw`` the HR size to crop to.  The same batching, the same scaling by
+    ``rgb_range / 255`` and the same forward and u8 conversion, so the SR stack uint8 [n,H,W,C] has ``super_resolve_u8``'s bits."""
+    if batch <= 0 and len(lr):
+        batch = _auto_batch(lr.shape[2], lr.shape[3], self_ensemble)
+    forward = model.forward_x8 if self_ensemble else model
+    return torch.cat([_forward_u8(forward, lr[i:i + batch].float() * (rgb_range / 255.0), hr_hw, rgb_range)
+                      for i in range(0, len(lr), batch)])
 
 
 @dataclass

@@ -588,6 +588,63 @@ def ensemble_mean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------- 8-bit resize, equal to PIL.Image.resize
+def resample_coeffs(in_size: int, out_size: int, filter: str = "lanczos"):
+    """(ksize, bounds int32 [out, 2], coeffs int32 [out, ksize]) of one axis as numpy arrays (``srad_resample_coeffs``; host
+    only, needs no GPU): Pillow's own fixed-point taps.  ValueError for an unknown filter, RuntimeError for refused sizes."""
+    import numpy as np
+    if filter not in L.RESAMPLE_FILTERS:
+        raise ValueError(f"resample filter {filter!r}: one of {sorted(L.RESAMPLE_FILTERS)}")
+    f, k = L.RESAMPLE_FILTERS[filter], C.c_int()
+    L.check(L.lib().srad_resample_ksize(int(in_size), int(out_size), f, C.byref(k)), "resample_ksize")
+    bounds = np.empty((int(out_size), 2), dtype=np.int32)
+    coeffs = np.empty((int(out_size), k.value), dtype=np.int32)
+    L.check(L.lib().srad_resample_coeffs(int(in_size), int(out_size), f, bounds.ctypes.data, coeffs.ctypes.data), "resample_coeffs")
+    return k.value, bounds, coeffs
+
+
+_RESAMPLE_TABLES: dict = {}
+
+
+def resample_table(in_size: int, out_size: int, filter: str, device) -> tuple:
+    """The ``_lib.ResampleTable`` of one axis on ``device`` and what keeps its arrays alive, cached per (in, out, filter,
+    device): the tables are built and uploaded once."""
+    key = (int(in_size), int(out_size), filter, str(device))
+    hit = _RESAMPLE_TABLES.get(key)
+    if hit is None:
+        ksize, bounds, coeffs = resample_coeffs(in_size, out_size, filter)
+        dev_bounds, dev_coeffs = torch.from_numpy(bounds).to(device), torch.from_numpy(coeffs).to(device)
+        table = L.ResampleTable(int(in_size), int(out_size), ksize, bounds.ctypes.data, dev_bounds.data_ptr(), dev_coeffs.data_ptr())
+        hit = _RESAMPLE_TABLES[key] = (table, (bounds, dev_bounds, dev_coeffs))
+    return hit
+
+
+def resize_u8(x: torch.Tensor, size, filter: str = "lanczos", *, out: Optional[torch.Tensor] = None,
+              tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x uint8 [n,H,W,C] (C = 1..4) on the GPU -> uint8 [n,h,w,C] with ``size = (h, w)``: every byte equals
+    ``PIL.Image.resize((w, h), LANCZOS | BICUBIC)`` of the image (``srad_resize_u8``).  ``out`` / ``tmp`` ([n,H,w,C]): buffers to
+    use instead of fresh ones."""
+    _need_cuda(x)
+    if x.dim() != 4 or x.dtype != torch.uint8:
+        raise ValueError(f"resize_u8: expected a uint8 [n,H,W,C] tensor, got {tuple(x.shape)} {x.dtype}")
+    x = x.contiguous()
+    n, H, W, Cc = x.shape
+    h, w = int(size[0]), int(size[1])
+    if h < 1 or w < 1 or n < 1:
+        raise ValueError(f"resize_u8: {n} images to {h}x{w}: every size must be >= 1")
+    for t, shape, what in ((out, (n, h, w, Cc), "out"), (tmp, (n, H, w, Cc), "tmp")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"resize_u8: {what} must be a contiguous uint8 GPU tensor of shape {shape}")
+    if out is None:
+        out = torch.empty(n, h, w, Cc, dtype=torch.uint8, device=x.device)
+    xt =resample_table(W, w, filter, x.device)[0] if W != w else None
+    yt = resample_table(H, h, filter, x.device)[0] if H != h else None
+    if tmp is None and xt is not None and yt is not None:
+        tmp = torch.empty(n, H, w, Cc, dtype=torch.uint8, device=x.device)
+    L.check(L.lib().srad_resize_u8(L.dptr(x), n, H, W, Cc, L.dptr(out), h, w, xt, yt, L.dptr(tmp), L.current_stream_ptr()), "resize_u8")
+    return out
+
+
 # ----------------------------------------------------------------------------------- DRN's own kernels, one by one
 # (C ABI ``srad_op_drn_*``, csrc/drn.hip).  Every call goes through the launcher the engines use, so grid, slices per image,
 # NI and storage instance are the engines' own.  ``out=`` tensors let a test place an output inside a guarded allocation.

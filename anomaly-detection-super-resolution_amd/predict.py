@@ -1,0 +1,376 @@
+"""Predict on raw images: "defective or not, and where" for new, unlabelled, unprepared images.
+
+    python -m srad_amd.predict --run-dir <run> --calibrate <dir of defect-free images> --threshold-fpr 0.01 [--map-ws 11 ...]
+    python -m srad_amd.predict --run-dir <run> --input <files or directories> [--threshold T] [--save-masks ...]
+
+``Detector`` chains what the evaluator already has - SR forward, anomaly maps (``evaluate.MapSpec``), operating point
+(``metrics.operating_point``) - behind one step the evaluator leaves to ``prepare_mvtec_data``: turning a raw image into the
+(LR, HR) pair the model was trained on.  That is two ``PIL.Image.resize(..., LANCZOS)`` calls, source -> hr x hr -> hr // scale,
+and here both run on the GPU (``ops.resize_u8``, equal to PIL byte for byte; DESIGN.md "Resize on the device"), so the pair is
+exactly what ``prepare_mvtec_data._write_pyramid`` followed by ``evaluate.iter_split`` gives and the maps and thresholds mean
+what they mean in the evaluator.  Calibration writes ``<run-dir>/operating_point.json``; prediction reads it back.  One GPU;
+image decoding stays on the host."""
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import os
+from dataclasses import asdict
+from pathlib import Path
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import metrics as M
+from . import ops
+from .data import rgb2y, set_channel
+from .evaluate import MapSpec, _with_window, infer_from_run_dir, resolve_checkpoint, save_anomaly_maps, save_masks, save_sr_image, super_resolve_dev
+from .options import _finite_or_inf_float, _map_scales, _nonnegative_float, _open_unit_float, _positive_int, build_opt
+
+OPERATING_POINT_FILE = 'operating_point.json'
+OPERATING_POINT_VERSION = 1
+IMAGE_SUFFIXES = ('.png', '.jpg', '.jpeg', '.bmp', '.tif', '.tiff')
+MAP_WS_DEFAULT = 11                                           # skimage's default SSIM window: no labelled sweep picks one here
+
+
+def luma_table() -> np.ndarray:
+    """float32 [256]: what the loader makes of a gray value v once ``prepare_mvtec_data`` has written it as RGB (v, v, v) -
+    ``data.rgb2y`` (float64) cast to float32 by ``np2Tensor``.  The float32 value does not depend on the shape of the array
+    ``rgb2y`` is given (its float64 one does, in the last bits), so one table serves every image."""
+    v = np.arange(256, dtype=np.uint8)
+    return rgb2y(np.stack([v, v, v], axis=1)[:, None, :])[:, 0].astype(np.float32)
+
+
+def as_source(image) -> np.ndarray:
+    """A raw image as the uint8 array the resize starts from: [H,W] for gray (mode L, one channel, or r = g = b everywhere),
+    [H,W,3] otherwise.  ``image``: a uint8 array [H,W], [H,W,1] or [H,W,3], or a path, read as ``prepare_mvtec_data.resize_image``
+    reads it (anything but L and RGB goes through ``convert('RGB')``)."""
+    if isinstance(image, (str, os.PathLike)):
+        from PIL import Image
+        with Image.open(image) as im:
+            a = np.asarray(im if im.mode in ('L', 'RGB') else im.convert('RGB'))
+    else:
+        a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)) or a.size == 0:
+        raise ValueError(f"predict takes uint8 images [H,W], [H,W,1] or [H,W,3], got {a.dtype} {a.shape}")
+    if a.ndim == 3 and (a.shape[2] == 1 or (np.array_equal(a[..., 0], a[..., 1]) and np.array_equal(a[..., 0], a[..., 2]))):
+        a = a[..., 0]
+    return np.ascontiguousarray(a)
+
+
+def check_spec(spec: MapSpec) -> MapSpec:
+    """A predict-time spec names its window: ``ws`` >= 1 or scales.  'ssim' with ``ws`` 0 means the labelled sweep's best_ws in
+    the evaluator, and there are no labels here."""
+    if spec.needs_best_ws:
+        raise ValueError("predict: an SSIM map spec needs its window size (--map-ws >= 1) or --map-scales; "
+                         "window 0 is the labelled sweep's best_ws, and prediction has no labels")
+    return spec
+
+
+class Detector:
+    """A model, a map spec and (once calibrated or given) a threshold.  ``hr_size``: the side the model's HR images have
+    (default ``opt.patch_size``); scale, ``n_colors`` and ``rgb_range`` come from ``opt``."""
+
+    def __init__(self, opt, model, spec: MapSpec, threshold: Optional[float] = None, min_area: int = 1, self_ensemble: bool = False,
+                 hr_size: Optional[int] = None):
+        self.opt, self.model, self.self_ensemble = opt, model, bool(self_ensemble)
+        self.hr_size = int(hr_size or opt.patch_size)
+        self.scale = int(opt.scale[-1] if isinstance(opt.scale, (list, tuple)) else opt.scale)
+        self.n_colors, self.rgb_range = int(opt.n_colors), float(opt.rgb_range)
+        if self.hr_size // self.scale < 1:
+            raise ValueError(f"predict: HR size {self.hr_size} is below the scale {self.scale}")
+        lr = self.hr_size // self.scale
+        self.spec = _with_window(check_spec(spec).resolve(lr * self.scale, lr * self.scale), None, 1)      # mse: window 0 means 1
+        if int(min_area) < 1 or int(min_area) != min_area:
+            raise ValueError(f"predict: min_area = {min_area}, must be an integer >= 1")
+        self.threshold, self.min_area = (None if threshold is None else float(threshold)), int(min_area)
+        self.device = model.device
+        self._luma = None
+        model.eval()                                          # H1 of the evaluator: deterministic scoring
+
+    # ---------------------------------------------------------------------------------------------------------- the pair
+    def _pyramid(self, stack: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
+        """uint8 [n,H,W,C] sources of one shape -> (LR uint8 [n,h,w,C], HR uint8 [n,hr,hr,C]) on the GPU: two LANCZOS resizes."""
+        hr = ops.resize_u8(torch.from_numpy(stack).to(self.device), (self.hr_size, self.hr_size), 'lanczos')
+        lr = self.hr_size // self.scale
+        return ops.resize_u8(hr, (lr, lr), 'lanczos'), hr
+
+    def prepare(self, images: Sequence) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Raw images (``as_source``), of any and mixed sizes -> (lr float32 [n,C,h,w] with values in [0, 255], hr uint8
+        [n,H,W,C]) on the GPU, equal to ``iter_split`` of the tree ``prepare_mvtec_data`` writes from them: source to RGB,
+        LANCZOS to hr x hr, that to hr // scale, ``set_channel``, HR cropped to LR * scale and truncated to u8.  One resize
+        launch pair per source shape.  Gray sources resize one channel; with ``n_colors`` 1 their luma is the 256-entry float32
+        table of ``luma_table`` (LR) and its truncation (HR); true colour with ``n_colors`` 1 takes ``data.set_channel`` on the
+        host; ``n_colors`` 3 replicates gray."""
+        sources = [as_source(im) for im in images]
+        if not sources:
+            raise ValueError("predict: no images")
+        C_ = self.n_colors
+        lr_side = self.hr_size // self.scale
+        crop = lr_side * self.scale
+        lr_out = torch.empty(len(sources), C_, lr_side, lr_side, dtype=torch.float32, device=self.device)
+        hr_out = torch.empty(len(sources), crop, crop, C_, dtype=torch.uint8, device=self.device)
+        groups: dict = {}
+        for i, a in enumerate(sources):
+            groups.setdefault(a.shape, []).append(i)
+        for shape, idx in groups.items():
+            stack = np.stack([sources[i] for i in idx])
+            gray = len(shape) == 2
+            lr, hr = self._pyramid(stack[..., None] if gray else stack)
+            if gray and C_ == 1:
+                if self._luma is None:
+                    table = luma_table()
+                    self._luma = (torch.from_numpy(table).to(self.device), torch.from_numpy(table.astype(np.uint8)).to(self.device))
+                lr_f, hr_u = self._luma[0][lr.long()], self._luma[1][hr.long()]
+            elif gray:
+                lr_f, hr_u = lr.expand(-1, -1, -1, C_).float(), hr.expand(-1, -1, -1, C_)
+            elif C_ == 1:                                     # true colour to luma: the loader's own float64 arithmetic, on the host
+                lr_h, hr_h = lr.cpu().numpy(), hr.cpu().numpy()
+                ys = [set_channel([l], h, n_channels=1) for l, h in zip(lr_h, hr_h)]
+                lr_f = torch.from_numpy(np.stack([y[0][0] for y in ys])).float().to(self.device)
+                hr_u = torch.from_numpy(np.stack([y[1] for y in ys])).float().clamp(0, 255).to(torch.uint8).to(self.device)
+            else:
+                lr_f, hr_u = lr.float(), hr
+            where = torch.tensor(idx, device=self.device)
+            lr_out[where] = lr_f.permute(0, 3, 1, 2)
+            hr_out[where] = hr_u[:, :crop, :crop]             # the loader crops after set_channel
+        return lr_out, hr_out
+
+    # ---------------------------------------------------------------------------------------------------------- the maps
+    def _maps(self, images: Sequence, with_max: bool):
+        lr, hr = self.prepare(images)
+        sr = super_resolve_dev(self.model, lr, hr.shape[1:3], self.rgb_range, self_ensemble=self.self_ensemble)
+        maps, img_max = self.spec.make(sr, hr, with_max)
+        return sr, hr, maps, img_max
+
+    def calibrate(self, images: Sequence, fpr: float, level: str = 'pixel') -> Tuple[float, float]:
+        """The threshold that the maps of the defect-free ``images`` give at false-positive rate ``fpr`` - on all their pixels
+        (``level`` 'pixel') or on each map's maximum ('image') - as the evaluator's ``--threshold-fpr`` calibrates it
+        (``metrics.map_threshold``).  Sets and returns it, with the rate achieved."""
+        if level not in ('pixel', 'image'):
+            raise ValueError(f"predict: level = {level!r}, must be 'pixel' or 'image'")
+        M.rank_for_rate(1, fpr)                               # the rate's own check, before any work
+        _, _, maps, img_max = self._maps(images, level == 'image')
+        self.threshold, achieved = M.map_threshold(img_max if level == 'image' else maps, fpr)
+        return self.threshold, achieved
+
+    def predict(self, images: Sequence) -> dict:
+        """Per image (lists, in input order): ``ssim``, ``mse``, ``psnr`` of SR against HR (``metrics.score_pairs``; the SSIM at
+        the spec's window, the mean over its scales where it has scales), ``map_max``, ``defect_pixels`` (pixels above the
+        threshold that survive the area filter) and ``defective`` (any such pixel); ``maps`` float32 [n,H,W] and ``masks``
+        uint8 {0, 1} [n,H,W] stay on the GPU, as do ``sr`` and ``hr`` (uint8 [n,H,W,C]).  ValueError without a threshold."""
+        if self.threshold is None:
+            raise ValueError("predict: no threshold (calibrate on defect-free images first, or give one)")
+        sr, hr, maps, img_max = self._maps(images, True)
+        sizes = list(self.spec.scales) or [self.spec.ws]
+        ssim, mse, psnr = M.score_pairs(sr, hr, sizes)
+        masks, img_pred, _ = M.operating_point(maps, self.threshold, None, self.min_area)
+        pixels = [int(v) for v in img_pred.tolist()]
+        return dict(ssim=ssim.mean(1).tolist() if len(sizes) > 1 else ssim[:, 0].tolist(), mse=mse.tolist(), psnr=psnr.tolist(),
+                    map_max=[float(v) for v in img_max.tolist()], defective=[v > 0 for v in pixels], defect_pixels=pixels,
+                    threshold=self.threshold, maps=maps, masks=masks, sr=sr, hr=hr)
+
+
+# -------------------------------------------------------------------------------------------------------------------- files
+def list_images(paths: Sequence[str]) -> List[Path]:
+    """The image files of ``paths``: a file is taken as it is, a directory gives its image files (by suffix), sorted by name."""
+    out: List[Path] = []
+    for p in paths:
+        p = Path(p)
+        if p.is_dir():
+            out.extend(sorted(f for f in p.iterdir() if f.is_file() and f.suffix.lower() in IMAGE_SUFFIXES))
+        elif p.is_file():
+            out.append(p)
+        else:
+            raise FileNotFoundError(f"no such image file or directory: {p}")
+    return out
+
+
+def unique_names(files: Sequence[Path]) -> List[str]:
+    """A name per file for the outputs: the stem, with ``_2``, ``_3``, .. where a stem comes again."""
+    seen: dict = {}
+    names = []
+    for f in files:
+        k = seen[f.stem] = seen.get(f.stem, 0) + 1
+        names.append(f.stem if k == 1 else f"{f.stem}_{k}")
+    return names
+
+
+def write_operating_point(path, threshold: float, fpr: float, level: str, achieved: float, n_images: int, min_area: int, spec: MapSpec,
+                          self_ensemble: bool, checkpoint: str) -> dict:
+    """``operating_point.json``: everything a threshold depends on next to it.  Python's JSON writes a float's shortest
+    round-trip form, so the threshold reads back bit for bit."""
+    doc = dict(version=OPERATING_POINT_VERSION, threshold=float(threshold), threshold_source='fpr', threshold_fpr=float(fpr),
+               threshold_level=level, calib_rate=float(achieved), calib_images=int(n_images), min_region_area=int(min_area),
+               map_spec=dict(asdict(spec), scales=list(spec.scales)), self_ensemble=bool(self_ensemble),
+               checkpoint=os.path.basename(checkpoint))
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    Path(path).write_text(json.dumps(doc, indent=2) + "\n")
+    return doc
+
+
+def read_operating_point(path) -> dict:
+    """The document ``write_operating_point`` wrote, its ``map_spec`` as a ``MapSpec``.  ValueError for another version or a
+    missing entry."""
+    doc = json.loads(Path(path).read_text())
+    if doc.get('version') != OPERATING_POINT_VERSION:
+        raise ValueError(f"{path}: version {doc.get('version')!r}, this build reads version {OPERATING_POINT_VERSION}")
+    try:
+        m = doc['map_spec']
+        doc['map_spec'] = MapSpec(source=m['source'], ws=int(m['ws']), scales=list(m['scales']) or (), reduce=m['reduce'], sigma=float(m['sigma']))
+        doc['threshold'], doc['min_region_area'], doc['self_ensemble'] = float(doc['threshold']), int(doc['min_region_area']), bool(doc['self_ensemble'])
+    except KeyError as e:
+        raise ValueError(f"{path}: entry {e} is missing")
+    return doc
+
+
+MAP_FLAGS = (('map_source', '--map-source', 'source'), ('map_ws', '--map-ws', 'ws'), ('map_scales', '--map-scales', 'scales'),
+             ('map_reduce', '--map-reduce', 'reduce'), ('map_sigma', '--map-sigma', 'sigma'))
+
+
+def spec_from_args(args, stored: Optional[MapSpec] = None, side: int = 0) -> MapSpec:
+    """The map spec of the command line.  Without ``stored``: the flags, ``--map-ws`` defaulting to 11 where neither it nor
+    scales are given.  With ``stored`` (the spec a threshold was calibrated on): that spec, and a ``--map-*`` flag that says
+    otherwise is a ValueError - a threshold belongs to the maps it was calibrated on (``side``: the HR side, which says what
+    ``--map-scales sweep`` stands for)."""
+    if stored is not None:
+        for attr, flag, field in MAP_FLAGS:
+            given, kept = getattr(args, attr), getattr(stored, field)
+            if field == 'scales' and given == 'sweep' and side:
+                given = M.sweep_window_sizes(side)
+            if field == 'ws' and given == 0 and (args.map_source or stored.source) == 'mse' and not stored.scales:
+                given = 1                                     # the squared-error maps' window 0 is stored as what it means, 1
+            if given is not None and (list(given) != list(kept) if field == 'scales' else given != kept):
+                raise ValueError(f"{flag} {given} contradicts the calibrated operating point ({field} = {kept}): "
+                                 f"calibrate again with it, or give --threshold")
+        return stored
+    scales = args.map_scales or ()
+    if scales and args.map_ws:
+        raise ValueError("--map-scales and --map-ws exclude each other (the scales replace the single window size)")
+    ws = args.map_ws if args.map_ws is not None else (0 if scales else MAP_WS_DEFAULT)
+    return MapSpec(source=args.map_source or 'ssim', ws=ws, scales=scales, reduce=args.map_reduce or 'mean', sigma=args.map_sigma or 0.0)
+
+
+def parse_predict_args(argv=None) -> argparse.Namespace:
+    p = argparse.ArgumentParser(description='Predict on raw images: calibrate a threshold on defect-free images, then flag and '
+                                            'localise defects in new ones')
+    p.add_argument('--model-type', type=str, default='drct', choices=['drct', 'drn-l'])
+    p.add_argument('--classe', type=str, default='grid')
+    p.add_argument('--scale', type=int, default=4)
+    p.add_argument('--resolution', type=int, default=128)
+    p.add_argument('--run-dir', type=str, default='')
+    p.add_argument('--checkpoint', type=str, default='')
+    p.add_argument('--ema', action='store_true', default=False, help="the averaged weights of a run trained with --ema (as evaluate.py)")
+    p.add_argument('--dtype', type=str, default='bf16x3', choices=['fp32', 'bf16', 'bf16x3'])
+    p.add_argument('--input', type=str, nargs='+', default=[], metavar='PATH', help="image files, or directories of images, to predict on")
+    p.add_argument('--calibrate', type=str, default='', metavar='DIR',
+                   help="calibrate the threshold on the defect-free images of DIR at --threshold-fpr and write "
+                        f"<run-dir>/{OPERATING_POINT_FILE} (or <output-dir>/ without a run directory)")
+    p.add_argument('--threshold-fpr', type=_open_unit_float, default=None, metavar='RATE', help="false-positive rate of --calibrate, in (0, 1)")
+    p.add_argument('--threshold-level', type=str, default='pixel', choices=['pixel', 'image'],
+                   help="what --calibrate calibrates on: every pixel of the maps, or each map's maximum")
+    p.add_argument('--min-region-area', type=_positive_int, default=None, metavar='A',
+                   help="remove predicted 8-connected components of fewer than A pixels (default: the calibrated file's, else 1)")
+    p.add_argument('--threshold', type=_finite_or_inf_float, default=None, metavar='VALUE',
+                   help=f"predict with this threshold instead of the one in {OPERATING_POINT_FILE}")
+    p.add_argument('--map-source', type=str, default=None, choices=['ssim', 'mse'])
+    p.add_argument('--map-ws', type=int, default=None, help=f"window size of the anomaly maps (default {MAP_WS_DEFAULT}; there is no labelled sweep here)")
+    p.add_argument('--map-scales', type=_map_scales, default=None, metavar='LIST|sweep')
+    p.add_argument('--map-reduce', type=str, default=None, choices=['mean', 'max'])
+    p.add_argument('--map-sigma', type=_nonnegative_float, default=None)
+    p.add_argument('--self-ensemble', action='store_true', default=False)
+    p.add_argument('--save-anomaly-maps', action='store_true', default=False)
+    p.add_argument('--save-masks', action='store_true', default=False)
+    p.add_argument('--save-images', action='store_true', default=False, help="write the SR images too")
+    p.add_argument('--output-dir', type=str, default='')
+    args = p.parse_args(argv)
+    if args.ema and args.checkpoint:
+        p.error("--ema and --checkpoint exclude each other (an explicit file is already a choice)")
+    if not args.calibrate and not args.input:
+        p.error("nothing to do: give --calibrate DIR, --input PATH..., or both")
+    if bool(args.calibrate) != (args.threshold_fpr is not None):
+        p.error("--calibrate DIR and --threshold-fpr RATE go together")
+    if args.calibrate and args.threshold is not None:
+        p.error("--calibrate and --threshold exclude each other (a calibrated threshold or a given one)")
+    return args
+
+
+def main(argv=None):
+    return _run(parse_predict_args(argv))
+
+
+def _run(args) -> dict:
+    model_type, class_name, resolution, scale = args.model_type, args.classe, args.resolution, args.scale
+    if args.run_dir:
+        inf = infer_from_run_dir(args.run_dir)
+        model_type = inf.get('model_type') or model_type
+        class_name = inf.get('classe') or class_name
+        resolution = inf.get('resolution') or resolution
+        scale = inf.get('scale') or scale
+    out_dir = args.output_dir or (os.path.join(args.run_dir, 'predictions') if args.run_dir else './workspace/predictions')
+    op_file = Path(args.run_dir or out_dir) / OPERATING_POINT_FILE
+    stored = None
+    if not args.calibrate and args.threshold is None:         # before the model is loaded
+        if not op_file.is_file():
+            raise SystemExit(f"no threshold: give --threshold, or calibrate first (--calibrate DIR --threshold-fpr RATE writes {op_file})")
+        stored = read_operating_point(op_file)
+        if args.self_ensemble and not stored['self_ensemble']:
+            raise SystemExit(f"--self-ensemble contradicts the calibrated operating point ({op_file} was calibrated without it)")
+    try:
+        spec = check_spec(spec_from_args(args, stored['map_spec'] if stored else None, int(resolution) // int(scale) * int(scale)))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    self_ensemble = stored['self_ensemble'] if stored else args.self_ensemble
+    min_area = args.min_region_area if args.min_region_area is not None else (stored['min_region_area'] if stored else 1)
+    calib_files = list_images([args.calibrate]) if args.calibrate else []
+    files = list_images(args.input)
+    if args.calibrate and not calib_files:
+        raise SystemExit(f"--calibrate: no image under {args.calibrate}")
+    ckpt = resolve_checkpoint(args)
+    if stored and stored.get('checkpoint') != os.path.basename(ckpt):
+        print(f"Note: {op_file.name} was calibrated with {stored.get('checkpoint')}, these weights are {os.path.basename(ckpt)}")
+    opt = build_opt(model_type, class_name, resolution, scale, 1, args.dtype, pre_train=ckpt)
+    opt.test_only = True
+    from .model import Model
+    model = Model(opt, None, dual_model=(model_type == 'drn-l'))
+    try:
+        det = Detector(opt, model, spec, threshold=stored['threshold'] if stored else args.threshold, min_area=min_area,
+                       self_ensemble=self_ensemble, hr_size=int(resolution))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    out: dict = {}
+    if args.calibrate:
+        t, achieved = det.calibrate(calib_files, args.threshold_fpr, args.threshold_level)
+        out['operating_point'] = write_operating_point(op_file, t, args.threshold_fpr, args.threshold_level, achieved, len(calib_files), min_area,
+                                                       det.spec, self_ensemble, ckpt)
+        print(f"Calibrated - {det.spec.text()}, threshold={t:.9g} (fpr {args.threshold_fpr:g} on {args.threshold_level}s of "
+              f"{len(calib_files)} defect-free images, achieved {achieved:.6f}), min_area={min_area}: {op_file}")
+    if files:
+        names = unique_names(files)
+        res = det.predict(files)
+        out.update(res, names=names, files=[str(f) for f in files])
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, 'predictions.csv'), 'w', newline='') as fh:
+            w = csv.writer(fh)
+            w.writerow(['name', 'file', 'defective', 'defect_pixels', 'map_max', 'ssim', 'mse', 'psnr', 'threshold'])
+            for k, name in enumerate(names):
+                w.writerow([name, str(files[k]), int(res['defective'][k]), res['defect_pixels'][k], repr(res['map_max'][k]), repr(res['ssim'][k]),
+                            repr(res['mse'][k]), repr(res['psnr'][k]), repr(det.threshold)])
+        kinds = ['bad' if d else 'good' for d in res['defective']]        # the evaluator's folder names, by prediction
+        if args.save_anomaly_maps:
+            save_anomaly_maps(res['maps'], names, kinds, out_dir)
+        if args.save_masks:
+            save_masks(res['masks'], names, kinds, out_dir)
+        if args.save_images:
+            sr_host = res['sr'].cpu().numpy()
+            for k, name in enumerate(names):
+                save_sr_image(sr_host[k], name, kinds[k], det.scale, out_dir)
+        print(f"Predicted - {det.spec.text()}, threshold={det.threshold:.9g}, min_area={min_area}: {sum(res['defective'])} of {len(files)} "
+              f"images defective; {os.path.join(out_dir, 'predictions.csv')}" + (" (self-ensemble x8)" if self_ensemble else ""))
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -233,6 +233,30 @@ int srad_ensemble_inputs(const float* x, int B, int C, int H, int W, float* out_
 int srad_ensemble_mean(const float* y_a /* [4,B,C,H,W] */, const float* y_b /* [4,B,C,W,H] */, int B, int C, int H, int W,
                        float* out /* [B,C,H,W] */, void* stream);
 
+/* ------------------------------------------------------------------ 8-bit resize, equal to PIL.Image.resize (DESIGN.md "Resize
+ * on the device"; scripts/prepare_mvtec_data.py:22-33 calls it with LANCZOS).  A table holds one axis: for every output index the
+ * first source index and tap count (bounds [out_size][2]) and the taps as int32 with 22 fractional bits (coeffs
+ * [out_size][ksize]), computed on the HOST by srad_resample_coeffs in Pillow's own arithmetic; neither function needs a GPU.
+ * srad_resize_u8 resizes u8 images src [n,H,W,C] (C = 1..4) to dst [n,h,w,C]: the horizontal pass first, rounded to u8 in tmp
+ * [n,H,w,C], then the vertical pass; a pass whose sizes agree is skipped (its table may be NULL, and tmp when only one pass
+ * runs), both skipped is a copy.  Every table carries its bounds twice: `bounds` on the host, which the call checks against the
+ * source before it launches, and `dev_bounds` / `dev_coeffs`, the device copies the kernels read.  dst and tmp must overlap
+ * neither src nor each other.  Integer arithmetic only (int32 accumulators, as Pillow), 64-bit offsets, stream-ordered, no
+ * allocation. */
+#define SRAD_RESAMPLE_LANCZOS 0
+#define SRAD_RESAMPLE_BICUBIC 1
+typedef struct {
+  int32_t in_size, out_size, ksize;
+  const int32_t* bounds;     /* host   [out_size][2] */
+  const int32_t* dev_bounds; /* device [out_size][2] */
+  const int32_t* dev_coeffs; /* device [out_size][ksize] */
+} srad_resample_table;
+int srad_resample_ksize(int in_size, int out_size, int filter, int* ksize);
+int srad_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds /* [out_size][2] */,
+                         int32_t* coeffs /* [out_size][ksize] */);
+int srad_resize_u8(const uint8_t* src, int n, int H, int W, int C, uint8_t* dst, int h, int w, const srad_resample_table* x_table,
+                   const srad_resample_table* y_table, uint8_t* tmp, void* stream);
+
 /* ------------------------------------------------------------------ scorer (src/evaluate.py:204-265) */
 /* `mul(255/range).clamp(0,255).byte()` TRUNCATING u8 conversion + NCHW->HWC (evaluate.py:214-215). */
 int srad_to_u8_hwc(const float* x, int B, int C, int H, int W, float rgb_range, uint8_t* out, void* stream);
