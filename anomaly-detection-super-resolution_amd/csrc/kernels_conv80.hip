@@ -13,18 +13,9 @@
 // Same arithmetic as the GEMM path (bf16 operands, fp32 accumulation); the summation order over k differs.
 #include "srad_common.h"
 #include <algorithm>
-#include <type_traits>
 #include <vector>
 
 namespace {
-
-template <int B, int N, class F>
-__device__ __forceinline__ void c80_static_for(F&& f) {
-  if constexpr (B < N) {
-    f(std::integral_constant<int, B>{});
-    c80_static_for<B + 1, N>(f);
-  }
-}
 
 constexpr int C80_K = 736;                // 9 taps x 80 channels = 720, padded to 23 chunks of 32 (the weight rows are zero there)
 // LDS strides.  ds_read_b128 is served in four groups of 16 lanes that are NOT lane-contiguous ({0-3, 12-15, 20-27}, {4-11, 16-19,
@@ -216,8 +207,8 @@ __global__ __launch_bounds__(C80_NT) void conv80_kernel(const GemmParams p, cons
         for (int nt = 0; nt < NTW; ++nt) fw[st][nt] = *reinterpret_cast<const bf16x8*>(wrow + nt * 16 * C80_WLD + 32 * kc);
       }
     };
-    c80_static_for<0, DEPTH>([&](auto K) { fetch(K); });
-    c80_static_for<0, NCH>([&](auto K) {
+    static_for<0, DEPTH>([&](auto K) { fetch(K); });
+    static_for<0, NCH>([&](auto K) {
       constexpr int kc = decltype(K)::value, st = kc % (DEPTH + 1);
       fetch(std::integral_constant<int, kc + DEPTH>{});
 #pragma unroll

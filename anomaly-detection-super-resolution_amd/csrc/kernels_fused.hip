@@ -20,20 +20,13 @@
 //     template parameter and the stage sequence is unrolled with static_for.
 // Rules carried over from kernels_gemm.hip: unconditional loads on clamped addresses, padding zeroed by
 // selects when values are written to LDS (never "x * 0": the clamped reads may be NaN bit patterns).
-#include "srad_common.h"
+// The tile strides, the staged-vector layout, the stage decode (MlpChain) and the chunk-grouped bf16 MFMA loop are
+// swin_tiles.h's, shared with swin_block_kernel.  The epilogues, the vector staging and the weight-stage load are written out
+// here and again in swin_block_kernel: shared, mlp_block<16> at d = 276 ran 1.3 % slower in every form tried.
+#include "swin_tiles.h"
 #include <cstdlib>
-#include <type_traits>
 
 namespace {
-
-// compile-time loop: f(std::integral_constant<int, I>{}) for I = B .. N-1
-template <int B, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < N) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, N>(f);
-  }
-}
 
 #ifndef SRAD_MLP_NSETS16
 #define SRAD_MLP_NSETS16 3
@@ -43,21 +36,6 @@ __device__ __forceinline__ void static_for(F&& f) {
 #ifndef SRAD_X3_FULLSTAGE
 #define SRAD_X3_FULLSTAGE 1
 #endif
-constexpr int F_LDA = 400;         // LDS row stride of the <=384-wide bf16 activation tile (2 mod 4 sixteen-byte units: conflict-free for the lane groups of ds_read_b128, see kernels_conv80.hip)
-constexpr int F_LDH = 528;         // LDS row stride of the <=512-wide hidden tile
-constexpr int F_SC = 128;          // output columns per weight stage
-constexpr int F_NV = 2560;         // floats of bias / gamma / beta staged in LDS (10 per thread)
-
-// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7): enough below bf16 resolution, ~4x fewer
-// instructions than erff
-__device__ __forceinline__ float gelu_fast(float x) {
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = 1.0f / (1.0f + 0.3275911f * z);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float erfa = 1.0f - poly * __expf(-z * z);
-  return 0.5f * x * (1.0f + (x < 0.f ? -erfa : erfa));
-}
-
 // GD/GM/GN = 128-column groups of the block dim / hidden / adjust output, KGD/KGM = 256-wide k groups
 // of the block dim / hidden.
 // FM = token rows per workgroup (16, or 64 for large token counts: every workgroup streams all four weight
@@ -69,23 +47,21 @@ __device__ __forceinline__ float gelu_fast(float x) {
 // W_hi.A_hi + W_hi.A_lo + W_lo.A_hi; the attention output comes in as fp32.  Nothing else changes - same stages, same epilogues.
 template <int FM, int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM, bool STAMP = false, bool SPLIT = false>
 __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) {
-  static_assert(KGD == (KCD + 7) / 8 && KGM == (KCM + 7) / 8, "k groups are 8 chunks wide");
+  using Chain = MlpChain<GD, KGD, GM, KGM, GN, KCD, KCM>;
   static_assert(!SPLIT || (FM <= 32 && !STAMP), "split-bf16: 16 / 32-row tiles (two planes of each tile in LDS)");
   constexpr int NRT = FM / 16;       // 16-row MFMA tiles per workgroup
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* A1 = reinterpret_cast<__bf16*>(smem);                  // [FM][F_LDA] attn tile -> LN2(x1) -> x2
-  __bf16* Hs = A1 + FM * F_LDA;                                  // [FM][F_LDH] GELU(fc1)
-  __bf16* A1L = Hs + FM * F_LDH;                                 // split-bf16: the lo planes of the two tiles
-  __bf16* HsL = A1L + FM * F_LDA;
-  float* vec = reinterpret_cast<float*>(SPLIT ? HsL + FM * F_LDH : Hs + FM * F_LDH);   // b_proj | b_fc1 | b_fc2 | b_adj | gamma | beta
-  float* red = vec + F_NV;                                       // [FM][8 waves][2] LayerNorm partial sums
+  __bf16* A1 = reinterpret_cast<__bf16*>(smem);                  // [FM][SW_LDA] attn tile -> LN2(x1) -> x2
+  __bf16* Hs = A1 + FM * SW_LDA;                                  // [FM][SW_LDH] GELU(fc1)
+  __bf16* A1L = Hs + FM * SW_LDH;                                 // split-bf16: the lo planes of the two tiles
+  __bf16* HsL = A1L + FM * SW_LDA;
+  float* vec = reinterpret_cast<float*>(SPLIT ? HsL + FM * SW_LDH : Hs + FM * SW_LDH);   // b_proj | b_fc1 | b_fc2 | b_adj | gamma | beta
+  float* red = vec + SW_NV;                                       // [FM][8 waves][2] LayerNorm partial sums
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   // XCD affinity (see qkv_attn_kernel): XCD k takes the row tiles of strip k of the token range
-  int tile_i = blockIdx.x;
-  if ((gridDim.x & 7) == 0 && !p.no_xcd_map) tile_i = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int m0 = tile_i * FM;
+  const int m0 = sw_xcd_tile(!p.no_xcd_map) * FM;
   const int d = p.d, m = p.m, no = p.no;
   const int dbg = STAMP ? p.dbg : 0;                               // the switch-off experiments exist in the diagnostic build only
   // diagnostic build only (tools/stamp_bench.py): shader-clock stamps of every wave at the phase boundaries
@@ -99,34 +75,19 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
     }
   };
   stamp(0);
-  constexpr int Kd = KCD * 32, Km = KCM * 32;                    // packed K of the weights
-  constexpr int n_proj = GD * KGD, n_fc1 = GM * KGD, n_fc2 = GD * KGM, n_adj = GN * KGD;
-  constexpr int n_stages = n_proj + n_fc1 + n_fc2 + n_adj;
+  constexpr int n_stages = Chain::n_stages;
   constexpr bool FULLST = SPLIT && SRAD_X3_FULLSTAGE;
   constexpr int NPART = (SPLIT && !FULLST) ? 2 : 1;              // weight streams per stage (hi | hi, lo)
   constexpr int RPS = FULLST ? 16 : 8;                           // registers (32-wide k chunks) per set
   constexpr int n_vst = n_stages * NPART;                        // (stage, part) pairs in stream order
   // offsets of the staged vectors
-  float* const v_bp = vec; float* const v_b1 = vec + 384; float* const v_b2 = vec + 896; float* const v_ba = vec + 1280;
-  float* const v_g = vec + 1664; float* const v_b = vec + 2048;
+  float* const v_bp = vec; float* const v_b1 = vec + SW_V_B1; float* const v_b2 = vec + SW_V_B2; float* const v_ba = vec + SW_V_BA;
+  float* const v_g = vec + SW_V_G; float* const v_b = vec + SW_V_B;
 
   // A wave whose 16 output columns all lie beyond the matrix (column groups are 128 wide: d = 276 fills 17.25 of its
   // 24 sixteen-column tiles, the 32-channel adjust conv 2 of 8) would stream zero rows of the padded pack and multiply
   // them: it skips both (wave-uniform scalar branch; its accumulators stay zero, which is what the epilogues expect).
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-  // stage s: phase (0 proj, 1 fc1, 2 fc2, 3 adjust), 128-column group g, 256-wide k group kg - all compile-time
-  struct StageGeo { int ph, g, kg, nch, kc; };
-  auto geo = [](int s) constexpr -> StageGeo {
-    if (s > n_stages - 1) s = n_stages - 1;
-    int ph = 0, kgs = 1, kc = 1;
-    if (s < n_proj) { ph = 0; kgs = KGD; kc = KCD; }
-    else if ((s -= n_proj) < n_fc1) { ph = 1; kgs = KGD; kc = KCD; }
-    else if ((s -= n_fc1) < n_fc2) { ph = 2; kgs = KGM; kc = KCM; }
-    else { s -= n_fc2; ph = 3; kgs = KGD; kc = KCD; }
-    const int g = s / kgs, kg = s - g * kgs;
-    const int nch = kc - kg * 8 < 8 ? kc - kg * 8 : 8;
-    return StageGeo{ph, g, kg, nch, kc};
-  };
   // 8 waves (two per SIMD), each owns 16 output columns of a 128-column stage, i.e. 16 rows of the packed weight that
   // NOBODY else reads: the weights go straight from global memory into MFMA fragment registers, three stages ahead (no
   // LDS stage, no barrier per stage), from the fragment-major pack (one contiguous kilobyte per wave load).
@@ -134,7 +95,7 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
   u32x4 w_reg[NSETS][RPS];
   auto load_w = [&](auto S, u32x4 (&reg)[RPS]) __attribute__((always_inline)) {
     constexpr int vs = decltype(S)::value < n_vst - 1 ? decltype(S)::value : n_vst - 1;
-    constexpr StageGeo sg = geo(vs / NPART);
+    constexpr MlpStage sg = Chain::stage(vs / NPART);
     constexpr bool lo = (vs % NPART) == 1;
     const char* w = lo ? (const char*)(sg.ph == 0 ? p.w_proj_lo : (sg.ph == 1 ? p.w_fc1_lo : (sg.ph == 2 ? p.w_fc2_lo : p.w_adj_lo)))
                        : (const char*)(sg.ph == 0 ? p.w_proj : (sg.ph == 1 ? p.w_fc1 : (sg.ph == 2 ? p.w_fc2 : p.w_adj)));
@@ -220,31 +181,7 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if constexpr (!SPLIT) {
-      // bf16: the activation fragments of G chunks are requested together, THEN multiplied (sched_barrier: left alone the
-      // scheduler sinks every LDS read to just above its MFMA - s_waitcnt lgkmcnt(0 / 1) in front of each of a stage's eight
-      // dependent MFMAs, i.e. the LDS latency exposed four to eight times per stage and ten to sixteen stages per launch)
-      constexpr int G = NRT == 1 ? 8 : (NRT == 2 ? 4 : 2);
-#pragma unroll
-      for (int cc0 = 0; cc0 < 8; cc0 += G) {
-        bf16x8 af[G][NRT];
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-          if (cc0 + g < nch) {
-#pragma unroll
-            for (int rt = 0; rt < NRT; ++rt) af[g][rt] = *reinterpret_cast<const bf16x8*>(ar + rt * 16 * lda + (cc0 + g) * 32);
-          }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-          if (cc0 + g < nch) {
-            const bf16x8 b0 = __builtin_bit_cast(bf16x8, reg[cc0 + g]);
-#pragma unroll
-            for (int rt = 0; rt < NRT; ++rt) c[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, af[g][rt], c[rt], 0, 0, 0);
-          }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+    if constexpr (!SPLIT) sw_mma_chunks<NRT == 1 ? 8 : (NRT == 2 ? 4 : 2), NRT>(ar, lda, nch, 8, reg, c);
   };
 
   // ---- issue the independent loads, in the order their data is needed: the attn tile and the shortcut rows (first GEMM /
@@ -270,25 +207,25 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
   f32x4 x1[GD][NRT];
 #pragma unroll
   for (int g = 0; g < GD; ++g) {
-    const int c4 = min(F_SC * g + 16 * wave + 4 * fq, d - 4);
+    const int c4 = min(SW_SC * g + 16 * wave + 4 * fq, d - 4);
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
       x1[g][rt] = (dbg & 32) ? f32x4{0.f, 0.f, 0.f, 0.f}
                                : *reinterpret_cast<const f32x4*>(p.shortcut + (size_t)(m0 + rt * 16 + fr) * p.ld_short + c4);
   }
-  // staged vectors: [0,384) b_proj, [384,896) b_fc1, [896,1280) b_fc2, [1280,1664) b_adj, [1664,2048) gamma, [2048,2432) beta.
+  // staged vectors, in their slots SW_V_* (b_proj | b_fc1 | b_fc2 | b_adj | gamma | beta).
   // Wave w < 6 stages vector w: a wave-uniform base pointer (scalar select, no per-lane pointer table in memory) and two
   // clamped float4 per lane; entries past a vector's length are never used.
   f32x4 vq[2];
   int v_off = 0, v_len = 0;
   {
     const float* src = p.b_proj; int n = d;
-    if (wave_s == 1) { src = p.b_fc1; n = m; v_off = 384; }
-    else if (wave_s == 2) { src = p.b_fc2; n = d; v_off = 896; }
-    else if (wave_s == 3) { src = p.b_adj; n = no; v_off = 1280; }
-    else if (wave_s == 4) { src = p.ln_g; n = d; v_off = 1664; }
-    else if (wave_s == 5) { src = p.ln_b; n = d; v_off = 2048; }
-    v_len = wave_s == 1 ? 512 : 384;
+    if (wave_s == 1) { src = p.b_fc1; n = m; v_off = SW_V_B1; }
+    else if (wave_s == 2) { src = p.b_fc2; n = d; v_off = SW_V_B2; }
+    else if (wave_s == 3) { src = p.b_adj; n = no; v_off = SW_V_BA; }
+    else if (wave_s == 4) { src = p.ln_g; n = d; v_off = SW_V_G; }
+    else if (wave_s == 5) { src = p.ln_b; n = d; v_off = SW_V_B; }
+    v_len = wave_s == 1 ? SW_VM : SW_VD;
     vq[0] = *reinterpret_cast<const f32x4*>(src + min(4 * lane, n - 4));
     vq[1] = *reinterpret_cast<const f32x4*>(src + min(256 + 4 * lane, n - 4));
   }
@@ -319,17 +256,17 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
       if constexpr (SPLIT) {
         bf16x4 hh, ll;
         srad_split4(c < d ? a_regf[j] : f32x4{0.f, 0.f, 0.f, 0.f}, hh, ll);
-        *reinterpret_cast<bf16x4*>(A1 + row * F_LDA + c) = hh;
-        *reinterpret_cast<bf16x4*>(A1L + row * F_LDA + c) = ll;
+        *reinterpret_cast<bf16x4*>(A1 + row * SW_LDA + c) = hh;
+        *reinterpret_cast<bf16x4*>(A1L + row * SW_LDA + c) = ll;
       } else {
-        *reinterpret_cast<u32x2*>(A1 + row * F_LDA + c) = c < d ? a_reg[j] : u32x2{0u, 0u};
+        *reinterpret_cast<u32x2*>(A1 + row * SW_LDA + c) = c < d ? a_reg[j] : u32x2{0u, 0u};
       }
     }
   }
   static_for<1, NSETS>([&](auto Q) { load_w(Q, w_reg[decltype(Q)::value]); });   // the rest of the look-ahead, behind the tile
 
   // ---- phase epilogues (run when the last k-group of a 128-column group is done) ----
-  auto col4_of = [&](int g) { return F_SC * g + 16 * wave + 4 * fq; };
+  auto col4_of = [&](int g) { return SW_SC * g + 16 * wave + 4 * fq; };
   // bf16 quad into the LDS tile and, when `gsave` is set and the quad holds real columns, into the global bf16 copy the
   // weight gradient reads ([M][gld])
   auto store_bf4 = [&](__bf16* base, int ld, int rt, int c4, f32x4 v, __bf16* gsave = nullptr, int gld = 0, bool real = false) __attribute__((always_inline)) {
@@ -347,7 +284,7 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
   auto epi_proj = [&](auto G, const f32x4 (&c)[NRT]) __attribute__((always_inline)) {
     constexpr int g = decltype(G)::value;
     {
-      const f32x4 bp = *reinterpret_cast<const f32x4*>(v_bp + min(col4_of(g), 380));
+      const f32x4 bp = *reinterpret_cast<const f32x4*>(v_bp + min(col4_of(g), SW_VD - 4));
 #pragma unroll
       for (int rt = 0; rt < NRT; ++rt) x1[g][rt] += (c[rt] + bp) * rs1v[rt];
     }
@@ -399,19 +336,19 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
     for (int gg = 0; gg < GD; ++gg) {
       const int c4 = col4_of(gg);
       const bool in = c4 < d;
-      const f32x4 gam = *reinterpret_cast<const f32x4*>(v_g + min(c4, 380));
-      const f32x4 bet = *reinterpret_cast<const f32x4*>(v_b + min(c4, 380));
+      const f32x4 gam = *reinterpret_cast<const f32x4*>(v_g + min(c4, SW_VD - 4));
+      const f32x4 bet = *reinterpret_cast<const f32x4*>(v_b + min(c4, SW_VD - 4));
 #pragma unroll
       for (int rt = 0; rt < NRT; ++rt) {
         const f32x4 v = in ? (x1[gg][rt] - mu[rt]) * rstd[rt] * gam + bet : f32x4{0.f, 0.f, 0.f, 0.f};
         if (p.save_xn2 && in) *reinterpret_cast<f32x4*>(p.save_xn2 + (size_t)(m0 + rt * 16 + fr) * d + c4) = v;
-        store_bf4(A1, F_LDA, rt, c4, v, p.save_xn2_h, d, in);
+        store_bf4(A1, SW_LDA, rt, c4, v, p.save_xn2_h, d, in);
       }
     }
   };
   auto epi_fc1 = [&](int g, const f32x4 (&c)[NRT]) __attribute__((always_inline)) {
     const int c4 = col4_of(g);
-    const f32x4 b1 = *reinterpret_cast<const f32x4*>(v_b1 + min(c4, 508));
+    const f32x4 b1 = *reinterpret_cast<const f32x4*>(v_b1 + min(c4, SW_VM - 4));
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt) {
       f32x4 v = c[rt] + b1;
@@ -426,13 +363,13 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
         for (int e = 0; e < 4; ++e) v[e] = gelu_fast(v[e]);
       }
       if (p.save_hact && c4 < m) *reinterpret_cast<f32x4*>(p.save_hact + (size_t)(m0 + rt * 16 + fr) * m + c4) = v;
-      store_bf4(Hs, F_LDH, rt, c4, c4 < m ? v : f32x4{0.f, 0.f, 0.f, 0.f}, p.save_hact_h, m, c4 < m);      // m % 4 == 0
+      store_bf4(Hs, SW_LDH, rt, c4, c4 < m ? v : f32x4{0.f, 0.f, 0.f, 0.f}, p.save_hact_h, m, c4 < m);      // m % 4 == 0
     }
   };
   auto epi_fc2 = [&](auto G, const f32x4 (&c)[NRT]) __attribute__((always_inline)) {
     constexpr int g = decltype(G)::value;
     {
-      const f32x4 b2 = *reinterpret_cast<const f32x4*>(v_b2 + min(col4_of(g), 380));
+      const f32x4 b2 = *reinterpret_cast<const f32x4*>(v_b2 + min(col4_of(g), SW_VD - 4));
 #pragma unroll
       for (int rt = 0; rt < NRT; ++rt) x1[g][rt] += (c[rt] + b2) * rs2v[rt];
     }
@@ -451,13 +388,13 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
     for (int gg = 0; gg < GD; ++gg) {
       const int c4 = col4_of(gg);
 #pragma unroll
-      for (int rt = 0; rt < NRT; ++rt) store_bf4(A1, F_LDA, rt, c4, c4 < d ? x1[gg][rt] : f32x4{0.f, 0.f, 0.f, 0.f}, p.save_x2_h, d, c4 < d);
+      for (int rt = 0; rt < NRT; ++rt) store_bf4(A1, SW_LDA, rt, c4, c4 < d ? x1[gg][rt] : f32x4{0.f, 0.f, 0.f, 0.f}, p.save_x2_h, d, c4 < d);
     }
   };
   auto epi_adj = [&](int g, const f32x4 (&c)[NRT]) __attribute__((always_inline)) {
     const int c4 = col4_of(g);
     const int cc = min(c4, no - 4);                                 // no % 4 == 0
-    const f32x4 ba = *reinterpret_cast<const f32x4*>(v_ba + min(c4, 380));
+    const f32x4 ba = *reinterpret_cast<const f32x4*>(v_ba + min(c4, SW_VD - 4));
     f32x4 rv[NRT];
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt) rv[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -482,14 +419,10 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
   static_for<0, n_vst>([&](auto S) {
     constexpr int vs = decltype(S)::value;
     constexpr int s = vs / NPART, part = vs % NPART;               // split-bf16: part 0 = hi weights, 1 = lo weights
-    constexpr int ph = s < n_proj ? 0 : (s < n_proj + n_fc1 ? 1 : (s < n_proj + n_fc1 + n_fc2 ? 2 : 3));
-    constexpr int ls = s - (ph == 0 ? 0 : (ph == 1 ? n_proj : (ph == 2 ? n_proj + n_fc1 : n_proj + n_fc1 + n_fc2)));
-    constexpr int kgs = ph == 2 ? KGM : KGD;
-    constexpr int g = ls / kgs, kg = ls - g * kgs;
+    constexpr MlpStage sg = Chain::stage(s);
+    constexpr int ph = sg.ph, g = sg.g, kg = sg.kg, nch = sg.nch;
     u32x4 (&reg)[RPS] = w_reg[vs % NSETS];
-    constexpr int Kp = ph == 2 ? Km : Kd;
-    constexpr int nch = (Kp >> 5) - kg * 8 < 8 ? (Kp >> 5) - kg * 8 : 8;
-    if constexpr (ls == 0 && part == 0) {
+    if constexpr (sg.first && part == 0) {
       stamp(3 + 3 * ph);                               // this wave's previous phase (its epilogue included) is done
       __syncthreads();                                 // first stage of a phase: the activation tile (A1 / Hs) and,
                                                        // at s == 0, the staged vectors written before are visible
@@ -501,10 +434,10 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
     }
     const bool live = (g * 8 + wave_s) * 16 < (ph == 0 ? d : (ph == 1 ? m : (ph == 2 ? d : no)));
     if (!(dbg & 2) && live)
-      mma_stage(ph == 2 ? Hs : A1, (SPLIT && part == 0) ? (ph == 2 ? HsL : A1L) : nullptr, ph == 2 ? F_LDH : F_LDA, kg * 256, nch, reg, c);   // (part == 0 always when a set holds both packs)
+      mma_stage(ph == 2 ? Hs : A1, (SPLIT && part == 0) ? (ph == 2 ? HsL : A1L) : nullptr, ph == 2 ? SW_LDH : SW_LDA, kg * 256, nch, reg, c);   // (part == 0 always when a set holds both packs)
     // refill this set, NSETS stages ahead.  Issuing a load can block (the queue is full while the weights stream), so where
     // an epilogue follows that other waves wait for (LayerNorm2, the tile hand-overs) the refill goes behind it
-    constexpr bool epi_first = kg == kgs - 1 && part == NPART - 1;
+    constexpr bool epi_first = sg.last && part == NPART - 1;
     if constexpr (!epi_first) { if (!(dbg & 1)) load_w(std::integral_constant<int, vs + NSETS>{}, reg); }
     if constexpr (epi_first && g == (ph == 0 ? GD : (ph == 1 ? GM : (ph == 2 ? GD : GN))) - 1) stamp(5 + 3 * ph);   // last MFMAs of the phase issued
     if (!(dbg & 16)) if constexpr (epi_first) {
@@ -518,14 +451,9 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
   stamp(15);
 }
 
-struct FusedCfg { int gd, kgd, gm, kgm, gn, kcd, kcm; };
-inline FusedCfg fused_cfg(int d, int m, int no) {
-  const int Kd = srad_cp(d), Km = srad_cp(m);
-  return FusedCfg{(d + F_SC - 1) / F_SC, (Kd + 255) / 256, (m + F_SC - 1) / F_SC, (Km + 255) / 256, (no + F_SC - 1) / F_SC, Kd / 32, Km / 32};
-}
 template <int FM, int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM, bool STAMP = false, bool SPLIT = false>
 int launch_mlp_fm(const MlpBlockParams& p, hipStream_t stream) {
-  constexpr size_t lds = (size_t)(FM * F_LDA + FM * F_LDH) * 2 * (SPLIT ? 2 : 1) + (F_NV + FM * 16) * sizeof(float);
+  constexpr size_t lds = (size_t)(FM * SW_LDA + FM * SW_LDH) * 2 * (SPLIT ? 2 : 1) + (SW_NV + FM * 16) * sizeof(float);
   const double flops = 2.0 * p.M * ((double)p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
   const double bytes = 4.0 * p.M * (2.0 * p.d + p.no) + 2.0 * ((double)p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
   SradProfScope prof(stream, SRAD_K_MLP_BLOCK, flops, bytes);
@@ -548,18 +476,15 @@ int launch_mlp(const MlpBlockParams& p, hipStream_t stream) {
   if (p.M >= 8192 && p.M % 32 == 0) return launch_mlp_fm<32, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
   return launch_mlp_fm<16, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
 }
-// stage geometries of DRCT-L's five Swin blocks (embed 180 + k*32; mlp ratio 2,2,2,1,1; adjust to 32 / 180 channels):
-// (column groups of d, k groups of d, column groups of m, k groups of m, column groups of the adjust output, k chunks of d, of m)
-#define SRAD_FUSED_CFGS(X) X(2, 1, 3, 2, 1, 6, 12) X(2, 1, 4, 2, 1, 7, 14) X(2, 1, 4, 2, 1, 8, 16) X(3, 2, 3, 2, 1, 9, 9) X(3, 2, 3, 2, 2, 10, 10)
 }  // namespace
 
 bool srad_mlp_block_supported(int prec, int M, int d, int m, int no) {
   if (!((prec == SRAD_PREC_BF16 || prec == SRAD_PREC_BF16X3) && M % 16 == 0 && d % 4 == 0 && m % 4 == 0 && no % 4 == 0 && d >= 32 && d <= 384 && m >= 32 &&
         m <= 512 && no >= 4 && no <= 384))
     return false;
-  const FusedCfg c = fused_cfg(d, m, no);
-#define X(a, b, cc, dd, e, f, g) if (c.gd == a && c.kgd == b && c.gm == cc && c.kgm == dd && c.gn == e && c.kcd == f && c.kcm == g) return true;
-  SRAD_FUSED_CFGS(X)
+  const SwinKey c = swin_key(d, 1, m, no);
+#define X(d_, h_, m_, no_, wpc_) if (swin_key_mlp_eq(c, swin_key(d_, h_, m_, no_))) return true;
+  SRAD_SWIN_SHAPES(X)
 #undef X
   return false;
 }
@@ -579,9 +504,10 @@ int srad_launch_mlp_block(const MlpBlockParams& p, hipStream_t stream) {
                "mlp_block: shortcut / output / residual rows must be float4-addressable");
   SRAD_REQUIRE((((uintptr_t)p.b_proj | (uintptr_t)p.b_fc1 | (uintptr_t)p.b_fc2 | (uintptr_t)p.b_adj | (uintptr_t)p.ln_g | (uintptr_t)p.ln_b) & 15) == 0,
                "mlp_block: bias / LayerNorm vectors must be 16-byte aligned");
-  const FusedCfg c = fused_cfg(p.d, p.m, p.no);
-#define X(a, b, cc, dd, e, f, g) if (c.gd == a && c.kgd == b && c.gm == cc && c.kgm == dd && c.gn == e && c.kcd == f && c.kcm == g) return launch_mlp<a, b, cc, dd, e, f, g>(p, stream);
-  SRAD_FUSED_CFGS(X)
+  const SwinKey c = swin_key(p.d, 1, p.m, p.no);
+#define X(d_, h_, m_, no_, wpc_) \
+  if (constexpr SwinKey k = swin_key(d_, h_, m_, no_); swin_key_mlp_eq(c, k)) return launch_mlp<k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kc, k.kcm>(p, stream);
+  SRAD_SWIN_SHAPES(X)
 #undef X
   return srad_set_error(SRAD_ERR_ARG, "mlp_block: no kernel instance for this geometry");
 }

@@ -9,28 +9,19 @@
 // the A operand; the head's three weight slices stream from a per-head fragment pack straight into MFMA
 // registers (no LDS weight stage: 33.8 KB less LDS, two workgroups per CU for the 6-head blocks); q, k, v
 // never exist in HBM.  This replaces the LN1+QKV GEMM launch, its [T][3d] round trip and the attention
-// launch.  Same rules as kernels_gemm.hip / kernels_fused.hip (unconditional clamped loads, selects for
-// padding, template-unrolled stages, transposed MFMA results so a lane owns 4 consecutive columns).
-#include "srad_common.h"
-#include <type_traits>
+// launch.  Same rules as kernels_gemm.hip (unconditional clamped loads, selects for padding, template-unrolled stages,
+// transposed MFMA results so a lane owns 4 consecutive columns).  The window mapping, the fragment-tile load, the
+// chunk-grouped MFMA loop, the bias + mask lookup and the transposed V read are swin_tiles.h's, shared with
+// swin_block_kernel; LayerNorm1 is written out in each kernel.
+#include "swin_tiles.h"
 
 namespace {
-
-template <int B, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < N) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, N>(f);
-  }
-}
-
-constexpr int QA_LDP = 80;     // probability tile row stride (2 mod 4 sixteen-byte units: conflict-free for the lane groups of ds_read_b128, see kernels_conv80.hip)
 
 // LDS bytes of one qkv_attn workgroup (layout: see qkv_attn_kernel)
 template <int HDT, int KC, bool SPLIT>
 constexpr size_t qa_lds_bytes() {
   constexpr int HDP = 16 * HDT, HS = ((HDP + 31) & ~31) + 16;
-  constexpr int XN_E = 64 * (KC * 32 + 16), QKV_E = 3 * 64 * HS, PS_E = 64 * QA_LDP;
+  constexpr int XN_E = 64 * (KC * 32 + 16), QKV_E = 3 * 64 * HS, PS_E = 64 * SW_LDP;
   constexpr int R0_E = SPLIT ? 2 * (XN_E > QKV_E + PS_E ? XN_E : QKV_E + PS_E) : XN_E + QKV_E;
   return (size_t)R0_E * 2 + (size_t)(640 + 3 * HDP + 232 + 256) * sizeof(float) + 128 * sizeof(int);
 }
@@ -63,7 +54,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
   constexpr int n_stages = NS * KG;
   constexpr int NPART = SPLIT ? 2 : 1;                          // weight streams per stage (hi | hi, lo)
   constexpr int n_vst = n_stages * NPART;
-  constexpr int XN_E = 64 * QA_LDX, QKV_E = 3 * 64 * HS, PS_E = 64 * QA_LDP;     // bf16 elements per plane
+  constexpr int XN_E = 64 * QA_LDX, QKV_E = 3 * 64 * HS, PS_E = 64 * SW_LDP;     // bf16 elements per plane
   constexpr int R0_E = SPLIT ? (2 * XN_E > 2 * (QKV_E + PS_E) ? 2 * XN_E : 2 * (QKV_E + PS_E)) : XN_E + QKV_E;
   // bf16: the probabilities overlay the normalised window, which is dead once q | k | v are complete
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
   __bf16* XNL = XN + XN_E;                                      // split-bf16: its lo plane
   __bf16* QKV = SPLIT ? XN : XN + XN_E;                         // [3][64][HS] (split-bf16: over the window tile, see above)
   __bf16* QKVL = QKV + QKV_E;
-  __bf16* Ps = SPLIT ? QKVL + QKV_E : XN;                       // [64][QA_LDP] probabilities
+  __bf16* Ps = SPLIT ? QKVL + QKV_E : XN;                       // [64][SW_LDP] probabilities
   __bf16* PsL = Ps + PS_E;
   float* v_g = reinterpret_cast<float*>(XN + R0_E);             // [320] gamma
   float* v_b = v_g + 320;                                       // [320] beta
@@ -104,25 +95,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
   // so the rows this workgroup gathers were mostly written into ITS L2 by the previous launch
   const int h = QSPLIT ? blockIdx.y >> 1 : blockIdx.y;
   const int half = QSPLIT ? blockIdx.y & 1 : 0;                 // query split: this workgroup's 32 queries
-  int win = blockIdx.x;
-  if ((gridDim.x & 7) == 0 && !p.no_xcd_map) win = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int ws = 8, nWx = p.W / ws, nW = (p.H / ws) * nWx;
-  const int b = win / nW, widx = win - b * nW;
-  const int wy = widx / nWx, wx = widx - wy * nWx;
+  const SwinWindow wnd = sw_window(p.H, p.W, p.shift, !p.no_xcd_map);
   const float scale = rsqrtf((float)hd);
 
-  // token of window position t (cyclic shift + window partition as index arithmetic, drct.py:482-504)
-  auto token_of = [&](int t, int& info) {
-    int token;
-    srad_window_token_info(p.H, p.W, ws, p.shift, b, wy, wx, t >> 3, t & 7, token, info);
-    return token;
-  };
   const int xrow = tid >> 3, col4 = tid & 7;
   int my_info;
-  const int my_tok = token_of(xrow, my_info);                     // every thread knows its own row: no barrier before the loads
+  const int my_tok = wnd.token(xrow, my_info);                    // every thread knows its own row: no barrier before the loads
   if (tid < 64) {
     int info;
-    tok[tid] = token_of(tid, info);
+    tok[tid] = wnd.token(tid, info);
     inf[tid] = info;
   }
 
@@ -142,10 +123,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
     constexpr int nch = KC - kg * CPG < CPG ? KC - kg * CPG : CPG;
     const bool live = (st * 8 + wave_s) * 16 < NV;
     const char* const Wp = (vs % NPART) == 1 ? Wl : Wh;
-    const char* base = live ? Wp + ((size_t)(st * 8 + wave) * KC + kg * CPG) * 1024 + fr * 64 + fq * 16 : Wp;
-    const int step = live ? 1024 : 0;
-#pragma unroll
-    for (int cc = 0; cc < nch; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + cc * step);
+    sw_load_tiles<nch>(reg, Wp, live, (size_t)(st * 8 + wave) * KC + kg * CPG, fr, fq);
   };
 
   // ---- issue the loads in the order their data is needed (vmcnt retires in issue order): the window's rows of x
@@ -189,6 +167,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
 
   stamp(2);                                                       // vectors staged
   // ---- LayerNorm1 from the registers (the 8 lanes of a row hold all its columns) -> bf16 -> XN ----
+  // (written out in each of its three kernels: with the statistics in a swin_tiles.h helper <5, 10, 1> goes from 152 to 156 - 158
+  // VGPRs and <3, 9, 2> from 114 to 116)
   {
     float s = 0.f, ss = 0.f;
 #pragma unroll
@@ -308,25 +288,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
         constexpr bool qst = QSPLIT && (st + 1) * 128 <= HDP;
         constexpr int NT = qst ? 2 : 4;
         const __bf16* arq = ar + (qst ? 32 * half : 0) * QA_LDX;
-#pragma unroll
-        for (int cc0 = 0; cc0 < nch; cc0 += 2) {
-          bf16x8 af[2][NT];
-#pragma unroll
-          for (int g = 0; g < 2; ++g)
-            if (cc0 + g < nch) {
-#pragma unroll
-              for (int t = 0; t < NT; ++t) af[g][t] = *reinterpret_cast<const bf16x8*>(arq + t * 16 * QA_LDX + (cc0 + g) * 32);
-            }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int g = 0; g < 2; ++g)
-            if (cc0 + g < nch) {
-              const bf16x8 b0 = __builtin_bit_cast(bf16x8, reg[cc0 + g]);
-#pragma unroll
-              for (int t = 0; t < NT; ++t) ac[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, af[g][t], ac[t], 0, 0, 0);
-            }
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        sw_mma_chunks<2, NT>(arq, QA_LDX, nch, nch, reg, ac);
       }
     }
     load_w(std::integral_constant<int, vs + NSETS>{}, reg);
@@ -351,14 +313,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
     for (int e = 0; e < 4; ++e) qi[e] = inf[srt * 16 + 4 * fq + e];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int ki = inf[(2 * kh + j) * 16 + fr], ky = (ki >> 8) & 0xff, kx = ki & 0xff, kr = ki >> 16;
+      const int ki = inf[(2 * kh + j) * 16 + fr];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int qy = (qi[e] >> 8) & 0xff, qx = qi[e] & 0xff, qr = qi[e] >> 16;
-        float v = tbl[(qy - ky + 7) * 15 + (qx - kx + 7)];
-        if (p.shift > 0 && qr != kr) v += -100.0f;
-        bm[j][e] = v;
-      }
+      for (int e = 0; e < 4; ++e) bm[j][e] = sw_bias_mask(tbl, 1, 0, qi[e], ki, p.shift);
     }
   }
   stamp(8);                                                       // this wave's q | k | v columns done
@@ -413,11 +370,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
         const float rs = srad_row16_sum(p0 + p1);
         if (fr == 0) lsum[kh * 64 + row] = rs;
         const __bf16 p0h = (__bf16)p0, p1h = (__bf16)p1;
-        Ps[row * QA_LDP + (2 * kh) * 16 + fr] = p0h;
-        Ps[row * QA_LDP + (2 * kh + 1) * 16 + fr] = p1h;
+        Ps[row * SW_LDP + (2 * kh) * 16 + fr] = p0h;
+        Ps[row * SW_LDP + (2 * kh + 1) * 16 + fr] = p1h;
         if constexpr (SPLIT) {
-          PsL[row * QA_LDP + (2 * kh) * 16 + fr] = (__bf16)(p0 - (float)p0h);
-          PsL[row * QA_LDP + (2 * kh + 1) * 16 + fr] = (__bf16)(p1 - (float)p1h);
+          PsL[row * SW_LDP + (2 * kh) * 16 + fr] = (__bf16)(p0 - (float)p0h);
+          PsL[row * SW_LDP + (2 * kh + 1) * 16 + fr] = (__bf16)(p1 - (float)p1h);
         }
       }
     }
@@ -439,21 +396,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2 * WPC))) 
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kk = 0; kk < 64; kk += 32) {
-        const bf16x8 pa = *reinterpret_cast<const bf16x8*>(Ps + (rt * 16 + fr) * QA_LDP + kk + 8 * fq);
-        typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+        const bf16x8 pa = *reinterpret_cast<const bf16x8*>(Ps + (rt * 16 + fr) * SW_LDP + kk + 8 * fq);
         const __bf16* r0 = Vs + (kk + 8 * fq + tq) * HS + j * 16 + 4 * tp;
-        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0));
-        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0 + 4 * HS));
-        bf16x8 vb;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { vb[e] = lo[e]; vb[4 + e] = hi[e]; }
+        const bf16x8 vb = sw_read_v_tr(r0, HS);
         if constexpr (SPLIT) {                                      // v_lo . p_hi and v_hi . p_lo first (the small terms)
-          const bf16x4 llo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0 + QKV_E));
-          const bf16x4 lhi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0 + QKV_E + 4 * HS));
-          bf16x8 vl;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { vl[e] = llo[e]; vl[4 + e] = lhi[e]; }
-          const bf16x8 pl = *reinterpret_cast<const bf16x8*>(PsL + (rt * 16 + fr) * QA_LDP + kk + 8 * fq);
+          const bf16x8 vl = sw_read_v_tr(r0 + QKV_E, HS);
+          const bf16x8 pl = *reinterpret_cast<const bf16x8*>(PsL + (rt * 16 + fr) * SW_LDP + kk + 8 * fq);
           o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vl, pa, o, 0, 0, 0);
           o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb, pl, o, 0, 0, 0);
         }
@@ -527,9 +475,7 @@ __global__ __launch_bounds__(512) void ln_qkv_kernel(const LnQkvParams p) {
   const int fr = lane & 15, fq = lane >> 4;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   const int d = p.d, hd = d / HEADS, hdp = p.hdp;
-  int tile_i = blockIdx.x;                                      // XCD affinity with mlp_block's row tiles (see qkv_attn_kernel)
-  if ((gridDim.x & 7) == 0) tile_i = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int m0 = tile_i * 64;
+  const int m0 = sw_xcd_tile(true) * 64;                        // XCD affinity with mlp_block's row tiles
   const int xrow = tid >> 3, col4 = tid & 7;
 
   constexpr int NSETS = 3;
@@ -542,10 +488,7 @@ __global__ __launch_bounds__(512) void ln_qkv_kernel(const LnQkvParams p) {
     constexpr int nch = KC - kg * 8 < 8 ? KC - kg * 8 : 8;
     const char* const Wh = reinterpret_cast<const char*>((va % NPART) == 1 ? p.w_qkv_lo : p.w_qkv) + (size_t)hh * (NV / 16) * KC * 1024;
     const bool live = (st * 8 + wave_s) * 16 < NV;
-    const char* base = live ? Wh + ((size_t)(st * 8 + wave) * KC + kg * 8) * 1024 + fr * 64 + fq * 16 : Wh;
-    const int step = live ? 1024 : 0;
-#pragma unroll
-    for (int cc = 0; cc < nch; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + cc * step);
+    sw_load_tiles<nch>(reg, Wh, live, (size_t)(st * 8 + wave) * KC + kg * 8, fr, fq);
   };
 
   // loads in the order their data is needed: the rows, the vectors, the first weight stage
@@ -576,6 +519,7 @@ __global__ __launch_bounds__(512) void ln_qkv_kernel(const LnQkvParams p) {
     if (tid + 512 * q < NBIAS) v_bias[tid + 512 * q] = biasq[q];
 
   // LayerNorm1 from the registers (the 8 lanes of a row hold all its columns) -> bf16 -> XN
+  // (written out: with the statistics in a swin_tiles.h helper <5, 10, 4> goes from 140 to 158 VGPRs)
   {
     float s = 0.f, ss = 0.f;
 #pragma unroll
@@ -626,32 +570,32 @@ __global__ __launch_bounds__(512) void ln_qkv_kernel(const LnQkvParams p) {
     }
     if (live) {
       const __bf16* ar = XN + fr * LDX + kg * 256 + 8 * fq;
+      if constexpr (!(SPLIT && part == 0)) sw_mma_chunks<2, 4>(ar, LDX, nch, nch, reg, acc);   // two chunks' fragments in flight, then their MFMAs
+      else {                                                        // the hi weights against both planes
 #pragma unroll
-      for (int cc0 = 0; cc0 < nch; cc0 += 2) {                     // two chunks' fragments in flight, then their MFMAs (see qkv_attn_kernel)
-        bf16x8 af[2][4];
-        [[maybe_unused]] bf16x8 afl[2][4];
+        for (int cc0 = 0; cc0 < nch; cc0 += 2) {
+          bf16x8 af[2][4], afl[2][4];
 #pragma unroll
-        for (int g = 0; g < 2; ++g)
-          if (cc0 + g < nch) {
+          for (int g = 0; g < 2; ++g)
+            if (cc0 + g < nch) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              af[g][t] = *reinterpret_cast<const bf16x8*>(ar + t * 16 * LDX + (cc0 + g) * 32);
-              if constexpr (SPLIT && part == 0) afl[g][t] = *reinterpret_cast<const bf16x8*>(ar + 64 * LDX + t * 16 * LDX + (cc0 + g) * 32);
+              for (int t = 0; t < 4; ++t) {
+                af[g][t] = *reinterpret_cast<const bf16x8*>(ar + t * 16 * LDX + (cc0 + g) * 32);
+                afl[g][t] = *reinterpret_cast<const bf16x8*>(ar + 64 * LDX + t * 16 * LDX + (cc0 + g) * 32);
+              }
             }
-          }
-        __builtin_amdgcn_sched_barrier(0);
+          __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int g = 0; g < 2; ++g)
-          if (cc0 + g < nch) {
-            const bf16x8 b0 = __builtin_bit_cast(bf16x8, reg[cc0 + g]);
-            if constexpr (SPLIT && part == 0) {
+          for (int g = 0; g < 2; ++g)
+            if (cc0 + g < nch) {
+              const bf16x8 b0 = __builtin_bit_cast(bf16x8, reg[cc0 + g]);
 #pragma unroll
               for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, afl[g][t], acc[t], 0, 0, 0);
-            }
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, af[g][t], acc[t], 0, 0, 0);
-          }
-        __builtin_amdgcn_sched_barrier(0);
+              for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, af[g][t], acc[t], 0, 0, 0);
+            }
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
     }
     load_w(std::integral_constant<int, va + NSETS>{}, reg);
@@ -690,16 +634,20 @@ int launch_ln_qkv(const LnQkvParams& p, hipStream_t stream) {
   return SRAD_OK;
 }
 
-// (head tiles, k chunks, bf16 workgroups per CU) of DRCT-L's five Swin blocks: d = 180/212/244/276/308, heads 6/4/2/6/4
-#define SRAD_QA_CFGS(X) X(2, 6, 2) X(4, 7, 2) X(8, 8, 1) X(3, 9, 2) X(5, 10, 1)
-#define SRAD_LQ_CFGS(X) X(2, 6, 6) X(4, 7, 4) X(8, 8, 2) X(3, 9, 6) X(5, 10, 4)
+// The instances are those of swin_tiles.h's table of block shapes.  Each list applies the macro named X at its place of use:
+// SRAD_QA_CFGS as X(head tiles, k chunks, bf16 workgroups per CU) for qkv_attn, which runs any head count; SRAD_LQ_CFGS as
+// X(head tiles, k chunks, heads) for ln_qkv
+#define SRAD_QA_SHAPE(d_, h_, m_, no_, wpc_) X(swin_key(d_, h_, m_, no_).hdt, swin_key(d_, h_, m_, no_).kc, wpc_)
+#define SRAD_LQ_SHAPE(d_, h_, m_, no_, wpc_) X(swin_key(d_, h_, m_, no_).hdt, swin_key(d_, h_, m_, no_).kc, h_)
+#define SRAD_QA_CFGS SRAD_SWIN_SHAPES(SRAD_QA_SHAPE)
+#define SRAD_LQ_CFGS SRAD_SWIN_SHAPES(SRAD_LQ_SHAPE)
 }  // namespace
 
 bool srad_ln_qkv_supported(int prec, int M, int d, int heads) {
   if ((prec != SRAD_PREC_BF16 && prec != SRAD_PREC_BF16X3) || M <= 0 || M % 64 || d % 4 || d > 320 || d < 32 || heads < 1 || d % heads) return false;
-  const int hdt = (d / heads + 15) / 16, kc = (d + 31) / 32;
+  const int hdt = swin_key(d, heads).hdt, kc = swin_key(d, heads).kc;
 #define X(a, b, c) if (hdt == a && kc == b && heads == c) return true;
-  SRAD_LQ_CFGS(X)
+  SRAD_LQ_CFGS
 #undef X
   return false;
 }
@@ -710,42 +658,30 @@ int srad_launch_ln_qkv(const LnQkvParams& p, hipStream_t stream) {
   SRAD_REQUIRE((p.ldx & 3) == 0 && ((uintptr_t)p.x & 15) == 0 && ((uintptr_t)p.qkv_h & 7) == 0 && ((uintptr_t)p.qkv_f & 15) == 0 && p.hdp % 4 == 0 && p.hdp >= p.d / p.heads &&
                    p.hdp <= 16 * ((p.d / p.heads + 15) / 16),
                "ln_qkv: x rows must be float4-addressable, the head slots 4-column multiples within the head's 16-column tiles");
-  const int hdt = (p.d / p.heads + 15) / 16, kc = (p.d + 31) / 32;
+  const int hdt = swin_key(p.d, p.heads).hdt, kc = swin_key(p.d, p.heads).kc;
   if (p.qkv_f) {                                                  // split-bf16
 #define X(a, b, c) if (hdt == a && kc == b && p.heads == c) return launch_ln_qkv<a, b, c, true>(p, stream);
-    SRAD_LQ_CFGS(X)
+    SRAD_LQ_CFGS
 #undef X
   }
 #define X(a, b, c) if (hdt == a && kc == b && p.heads == c) return launch_ln_qkv<a, b, c>(p, stream);
-  SRAD_LQ_CFGS(X)
+  SRAD_LQ_CFGS
 #undef X
   return srad_set_error(SRAD_ERR_ARG, "ln_qkv: no kernel instance for d=%d heads=%d", p.d, p.heads);
 }
 
 bool srad_qkv_attn_supported(int prec, int ws, int H, int W, int d, int heads) {
   if ((prec != SRAD_PREC_BF16 && prec != SRAD_PREC_BF16X3) || ws != 8 || H % 8 || W % 8 || d % 4 || d > 320 || d < 32 || heads < 1 || d % heads) return false;
-  const int hdt = (d / heads + 15) / 16, kc = (d + 31) / 32;
+  const int hdt = swin_key(d, heads).hdt, kc = swin_key(d, heads).kc;
 #define X(a, b, c) if (hdt == a && kc == b) return true;
-  SRAD_QA_CFGS(X)
+  SRAD_QA_CFGS
 #undef X
   return false;
 }
 
-// CUs of the current device (cached per device)
-static int qa_cu_count() {
-  static int cus[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int n = 0;
-    cus[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-  }
-  return cus[dev];
-}
-
 // the query split (two workgroups per (window, head)) when the plain grid leaves CUs idle; bf16 product path only
 static bool qa_query_split(const QkvAttnParams& p) {
-  return !p.split && !p.stamps && !p.no_qsplit && p.B * (p.H / 8) * (p.W / 8) * p.heads < qa_cu_count();
+  return !p.split && !p.stamps && !p.no_qsplit && p.B * (p.H / 8) * (p.W / 8) * p.heads < srad_cu_count();
 }
 
 int srad_qkv_attn_grid(int precision, int B, int H, int W, int d, int heads, int no_qsplit, int* grid_xy) {
@@ -762,26 +698,26 @@ int srad_launch_qkv_attn(const QkvAttnParams& p, hipStream_t stream) {
   SRAD_REQUIRE(srad_qkv_attn_supported(SRAD_PREC_BF16, 8, p.H, p.W, p.d, p.heads), "qkv_attn: unsupported shape d=%d heads=%d %dx%d", p.d, p.heads, p.H, p.W);
   SRAD_REQUIRE((p.ldx & 3) == 0 && ((uintptr_t)p.x & 15) == 0, "qkv_attn: x rows must be float4-addressable");
   SRAD_REQUIRE(p.shift >= 0 && p.shift < 8, "qkv_attn: shift %d must be in [0, 8)", p.shift);
-  const int hdt = (p.d / p.heads + 15) / 16, kc = (p.d + 31) / 32;
+  const int hdt = swin_key(p.d, p.heads).hdt, kc = swin_key(p.d, p.heads).kc;
   if (p.split) {                                                  // split-bf16 (inference)
     SRAD_REQUIRE(p.w_qkv_lo && p.out && !p.out_h, "qkv_attn (split-bf16): needs the lo weight pack and an fp32 output");
     SRAD_REQUIRE(!p.stamps && !p.save_xn && !p.save_xn_h && !p.save_qkv && !p.save_qkv_h, "qkv_attn (split-bf16): inference only");
 #define X(a, b, c) if (hdt == a && kc == b) return launch_qa<a, b, 1, false, true>(p, stream);
-    SRAD_QA_CFGS(X)
+    SRAD_QA_CFGS
 #undef X
   }
   if (p.stamps) {                                                 // diagnostic build (the unsplit grid; its stamps need registers the 128-VGPR bound lacks)
 #define X(a, b, c) if (hdt == a && kc == b) return launch_qa<a, b, 1, true>(p, stream);
-    SRAD_QA_CFGS(X)
+    SRAD_QA_CFGS
 #undef X
   }
   if (qa_query_split(p)) {
 #define X(a, b, c) if (hdt == a && kc == b) return launch_qa<a, b, c, false, false, true>(p, stream);
-    SRAD_QA_CFGS(X)
+    SRAD_QA_CFGS
 #undef X
   }
 #define X(a, b, c) if (hdt == a && kc == b) return launch_qa<a, b, c>(p, stream);
-  SRAD_QA_CFGS(X)
+  SRAD_QA_CFGS
 #undef X
   return srad_set_error(SRAD_ERR_ARG, "qkv_attn: no kernel instance for head tiles %d, k chunks %d", hdt, kc);
 }

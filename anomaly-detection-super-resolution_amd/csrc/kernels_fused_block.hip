@@ -20,36 +20,14 @@
 // other workgroups of this launch still read.  d % 4 == 0, every access is a float4 on a 4-column boundary, so no access
 // straddles the two ranges.  adjust5 writes the other dense buffer.
 //
-// Same rules as kernels_fused.hip / kernels_fused_attn.hip: unconditional loads on clamped addresses, activations ahead of
-// weights, padding zeroed by selects, stage geometry in template parameters (no runtime-indexed register arrays: no scratch),
-// LDS row strides of 2 mod 4 sixteen-byte units.
-#include "srad_common.h"
-#include <type_traits>
+// The tile geometry, the MLP stage decode, the transposed V read and the chunk-grouped MFMA loop are swin_tiles.h's, shared
+// with the two kernels.  What else the kernels have in common is written out here, each with a note why (through
+// the shared form this kernel or mlp_block_kernel ran slower).  Same rules as there: unconditional loads on clamped addresses,
+// activations ahead of weights, padding zeroed by selects, stage geometry in template parameters (no runtime-indexed register
+// arrays: no scratch), LDS row strides of 2 mod 4 sixteen-byte units.
+#include "swin_tiles.h"
 
 namespace {
-
-template <int B, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < N) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, N>(f);
-  }
-}
-
-constexpr int B_LDA = 400;         // LDS row stride of the <=384-wide bf16 activation tile (as F_LDA in kernels_fused.hip)
-constexpr int B_LDH = 528;         // ... of the <=512-wide hidden tile
-constexpr int B_SC = 128;          // output columns per weight stage
-constexpr int B_NV = 2560;         // floats of the MLP half's staged vectors
-constexpr int B_LDP = 80;          // probability tile row stride
-
-// erf by Abramowitz-Stegun 7.1.26, as in mlp_block_kernel
-__device__ __forceinline__ float blk_gelu(float x) {
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = 1.0f / (1.0f + 0.3275911f * z);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float erfa = 1.0f - poly * __expf(-z * z);
-  return 0.5f * x * (1.0f + (x < 0.f ? -erfa : erfa));
-}
 
 // Stage counts and the LDS layout of one instance.  HDT = ceil(head_dim / 16), KC = ceil(d / 32).
 template <int HDT, int KC, int HEADS>
@@ -63,8 +41,8 @@ struct BlkGeo {
   static constexpr int NKVS = (NKVT + 7) / 8, NQS = (NQT + 7) / 8; // column stages: one tile per wave
   static constexpr int QS = NKVS + NQS;                            // weight stages of the attention half: a stage spans all KC k chunks
   // bytes
-  static constexpr int XN_B = 64 * LDX * 2, KV_B = 2 * HEADS * 64 * HS * 2, Q_B = HEADS * 16 * HS * 2, PS_B = HEADS * 16 * B_LDP * 2;
-  static constexpr int A1_B = 16 * B_LDA * 2, HS_B = 16 * B_LDH * 2;
+  static constexpr int XN_B = 64 * LDX * 2, KV_B = 2 * HEADS * 64 * HS * 2, Q_B = HEADS * 16 * HS * 2, PS_B = HEADS * 16 * SW_LDP * 2;
+  static constexpr int A1_B = 16 * SW_LDA * 2, HS_B = 16 * SW_LDH * 2;
   // the normalised window is dead once q | k | v exist, so the probabilities (and the attention tile, if both fit) overlay it
   static constexpr bool A1_OVER = PS_B + A1_B <= XN_B;
   static constexpr int OFF_KV = XN_B, OFF_Q = OFF_KV + KV_B;
@@ -73,7 +51,7 @@ struct BlkGeo {
   static constexpr int OFF_VEC = A1_OVER ? OFF_Q + Q_B : OFF_A1 + A1_B;
   static constexpr int NBIAS = HEADS * 3 * HDP, NTBL = 225 * HEADS, NTBLP = (NTBL + 3) & ~3;
   // floats: MLP vectors | gamma1 320 | beta1 320 | qkv bias | table | LayerNorm2 partial sums [16][8][2] | softmax sums [HEADS][16]
-  static constexpr int NFLT = B_NV + 640 + NBIAS + NTBLP + 256 + 128;
+  static constexpr int NFLT = SW_NV + 640 + NBIAS + NTBLP + 256 + 128;
   static constexpr int LDS = OFF_VEC + NFLT * 4 + 64 * 4;          // + window geometry words [64]
   static_assert(KV_B >= HS_B, "the hidden tile overlays k | v");
   static_assert(LDS <= 160 * 1024, "swin_block: LDS budget");
@@ -84,7 +62,6 @@ template <int HDT, int KC, int HEADS, int GD, int KGD, int GM, int KGM, int GN, 
 __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p) {
   using G = BlkGeo<HDT, KC, HEADS>;
   constexpr int KCD = KC;
-  static_assert(KGD == (KCD + 7) / 8 && KGM == (KCM + 7) / 8, "k groups are 8 chunks wide");
   constexpr int HDP = G::HDP, HS = G::HS, LDX = G::LDX;
   constexpr int RC = KC > 8 ? KC : 8;                                    // fragment registers per weight set: a W_qkv stage holds all
                                                                          // KC (<= 10) chunks of its tile, an MLP stage up to 8
@@ -93,11 +70,11 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   __bf16* XN = reinterpret_cast<__bf16*>(smem);                          // [64][LDX] LayerNorm1(window)
   __bf16* KV = reinterpret_cast<__bf16*>(smem + G::OFF_KV);              // [k | v][HEADS][64][HS]
   __bf16* Qb = reinterpret_cast<__bf16*>(smem + G::OFF_Q);               // [HEADS][16][HS] (scaled)
-  __bf16* A1 = reinterpret_cast<__bf16*>(smem + G::OFF_A1);              // [16][B_LDA] attention output -> LN2(x1) -> x2
-  __bf16* Ps = reinterpret_cast<__bf16*>(smem + G::OFF_PS);              // [HEADS][16][B_LDP] probabilities
-  __bf16* Hs = KV;                                                       // [16][B_LDH] GELU(fc1): k | v are dead by then
+  __bf16* A1 = reinterpret_cast<__bf16*>(smem + G::OFF_A1);              // [16][SW_LDA] attention output -> LN2(x1) -> x2
+  __bf16* Ps = reinterpret_cast<__bf16*>(smem + G::OFF_PS);              // [HEADS][16][SW_LDP] probabilities
+  __bf16* Hs = KV;                                                       // [16][SW_LDH] GELU(fc1): k | v are dead by then
   float* vec = reinterpret_cast<float*>(smem + G::OFF_VEC);
-  float* v_g1 = vec + B_NV;                                              // [320] gamma1
+  float* v_g1 = vec + SW_NV;                                              // [320] gamma1
   float* v_b1n = v_g1 + 320;                                             // [320] beta1
   float* v_bias = v_b1n + 320;                                           // [HEADS][3][HDP] q|k|v bias (0 in padding)
   float* tbl = v_bias + G::NBIAS;                                        // [225][HEADS] relative position bias
@@ -113,6 +90,7 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   // grid = (windows, 4 quarters): a window's four workgroups have linear ids that differ by the window count, a multiple of 8
   // where the XCD-affine mapping applies, so they share an XCD (and its L2 copy of the window's rows and of the weights)
   const int quarter = blockIdx.y;
+  // (qkv_attn_kernel's sw_window, written out: through the helper d = 180 / 212 ran 0.02 - 0.08 us slower)
   int win = blockIdx.x;
   if ((gridDim.x & 7) == 0 && !p.no_xcd_map) win = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   const int ws = 8, nWx = p.W / ws, nW = (p.H / ws) * nWx;
@@ -132,24 +110,12 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     inf[tid] = info;
   }
 
-  constexpr int n_proj = GD * KGD, n_fc1 = GM * KGD, n_fc2 = GD * KGM, n_adj = GN * KGD;
-  constexpr int n_mlp = n_proj + n_fc1 + n_fc2 + n_adj;
+  using Chain = MlpChain<GD, KGD, GM, KGM, GN, KCD, KCM>;
+  constexpr int n_mlp = Chain::n_stages;
   constexpr int n_all = QS + n_mlp;
-  float* const v_bp = vec; float* const v_bf1 = vec + 384; float* const v_bf2 = vec + 896; float* const v_ba = vec + 1280;
-  float* const v_g2 = vec + 1664; float* const v_b2n = vec + 2048;
+  float* const v_bp = vec; float* const v_bf1 = vec + SW_V_B1; float* const v_bf2 = vec + SW_V_B2; float* const v_ba = vec + SW_V_BA;
+  float* const v_g2 = vec + SW_V_G; float* const v_b2n = vec + SW_V_B;
 
-  struct StageGeo { int ph, g, kg, nch, kc; };
-  auto geo = [](int s) constexpr -> StageGeo {
-    if (s > n_mlp - 1) s = n_mlp - 1;
-    int ph = 0, kgs = 1, kc = 1;
-    if (s < n_proj) { ph = 0; kgs = KGD; kc = KCD; }
-    else if ((s -= n_proj) < n_fc1) { ph = 1; kgs = KGD; kc = KCD; }
-    else if ((s -= n_fc1) < n_fc2) { ph = 2; kgs = KGM; kc = KCM; }
-    else { s -= n_fc2; ph = 3; kgs = KGD; kc = KCD; }
-    const int g = s / kgs, kg = s - g * kgs;
-    const int nch = kc - kg * 8 < 8 ? kc - kg * 8 : 8;
-    return StageGeo{ph, g, kg, nch, kc};
-  };
   // the 16-column tile of q | k | v this wave owns in column stage cs: head, slice (0 q, 1 k, 2 v), column tile of the
   // slice, liveness
   struct QTile { int hl, which, ct; bool live; };
@@ -172,12 +138,13 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
       const QTile t = qtile(u);
       const char* const Wq = reinterpret_cast<const char*>(p.w_qkv);
       const int gt = (t.hl * 3 + t.which) * HDT + t.ct;                       // tile row of the pack: [head][q | k | v][HDT]
+      // (sw_load_tiles written out: through the helper all five instances compile differently)
       const char* base = t.live ? Wq + (size_t)gt * KC * 1024 + fr * 64 + fq * 16 : Wq;
       const int step = t.live ? 1024 : 0;
 #pragma unroll
       for (int cc = 0; cc < KC; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + cc * step);
     } else {
-      constexpr StageGeo sg = geo(u - QS);
+      constexpr MlpStage sg = Chain::stage(u - QS);
       const char* w = (const char*)(sg.ph == 0 ? p.w_proj : (sg.ph == 1 ? p.w_fc1 : (sg.ph == 2 ? p.w_fc2 : p.w_adj)));
       const int nreal = sg.ph == 0 ? d : (sg.ph == 1 ? m : (sg.ph == 2 ? d : no));
       const bool live = (sg.g * 8 + wave_s) * 16 < nreal;
@@ -199,12 +166,13 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   f32x4 x1[GD];
 #pragma unroll
   for (int g = 0; g < GD; ++g)
-    x1[g] = *reinterpret_cast<const f32x4*>(p.x + (size_t)row_tok * p.ldx + min(B_SC * g + 16 * wave + 4 * fq, d - 4));
+    x1[g] = *reinterpret_cast<const f32x4*>(p.x + (size_t)row_tok * p.ldx + min(SW_SC * g + 16 * wave + 4 * fq, d - 4));
   typedef const float __attribute__((address_space(1)))* gfloat_p;
   float g1q, b1q, biasq[2], tblq[3];
   {
     const int e = min(tid, d - 1);
     g1q = ((gfloat_p)p.ln1_g)[e]; b1q = ((gfloat_p)p.ln1_b)[e];
+    // (the qkv-bias staging is ln_qkv_kernel's, written out in both: as a helper it changes all ten ln_qkv instances)
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int idx = min(tid + 512 * q, G::NBIAS - 1);
@@ -215,17 +183,17 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
 #pragma unroll
     for (int q = 0; q < 3; ++q) tblq[q] = ((gfloat_p)p.table)[min(tid + 512 * q, G::NTBL - 1)];
   }
-  // MLP vectors: [0,384) b_proj, [384,896) b_fc1, [896,1280) b_fc2, [1280,1664) b_adj, [1664,2048) gamma2, [2048,2432) beta2
+  // the MLP vectors into their slots (SW_V_*)
   f32x4 vq[2];
   int v_off = 0, v_len = 0;
   {
     const float* src = p.b_proj; int n = d;
-    if (wave_s == 1) { src = p.b_fc1; n = m; v_off = 384; }
-    else if (wave_s == 2) { src = p.b_fc2; n = d; v_off = 896; }
-    else if (wave_s == 3) { src = p.b_adj; n = no; v_off = 1280; }
-    else if (wave_s == 4) { src = p.ln2_g; n = d; v_off = 1664; }
-    else if (wave_s == 5) { src = p.ln2_b; n = d; v_off = 2048; }
-    v_len = wave_s == 1 ? 512 : 384;
+    if (wave_s == 1) { src = p.b_fc1; n = m; v_off = SW_V_B1; }
+    else if (wave_s == 2) { src = p.b_fc2; n = d; v_off = SW_V_B2; }
+    else if (wave_s == 3) { src = p.b_adj; n = no; v_off = SW_V_BA; }
+    else if (wave_s == 4) { src = p.ln2_g; n = d; v_off = SW_V_G; }
+    else if (wave_s == 5) { src = p.ln2_b; n = d; v_off = SW_V_B; }
+    v_len = wave_s == 1 ? SW_VM : SW_VD;
     vq[0] = *reinterpret_cast<const f32x4*>(src + min(4 * lane, n - 4));
     vq[1] = *reinterpret_cast<const f32x4*>(src + min(256 + 4 * lane, n - 4));
   }
@@ -242,6 +210,8 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     if (256 + 4 * lane < v_len) *reinterpret_cast<f32x4*>(vec + v_off + 256 + 4 * lane) = vq[1];
   }
   // ---- LayerNorm1 from the registers (the 8 lanes of a row hold all its columns) -> bf16 -> XN ----
+  // (written out in each of its three kernels: with the statistics in a swin_tiles.h helper the d = 276 / 308 instances go from
+  // 178 / 190 to 188 / 204 VGPRs)
   {
     float s = 0.f, ss = 0.f;
 #pragma unroll
@@ -288,26 +258,7 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
       if (t.live) {
         const __bf16* ar = XN + ((isq ? 16 * quarter : 0) + fr) * LDX + 8 * fq;
         // the window fragments of two chunks (q: of all chunks) are requested together, THEN multiplied (see qkv_attn_kernel)
-        constexpr int CG = isq ? KC : 2;
-#pragma unroll
-        for (int cc0 = 0; cc0 < nch; cc0 += CG) {
-          bf16x8 af[CG][NT];
-#pragma unroll
-          for (int g = 0; g < CG; ++g)
-            if (cc0 + g < nch) {
-#pragma unroll
-              for (int tt = 0; tt < NT; ++tt) af[g][tt] = *reinterpret_cast<const bf16x8*>(ar + tt * 16 * LDX + (cc0 + g) * 32);
-            }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int g = 0; g < CG; ++g)
-            if (cc0 + g < nch) {
-              const bf16x8 b0 = __builtin_bit_cast(bf16x8, reg[cc0 + g]);
-#pragma unroll
-              for (int tt = 0; tt < NT; ++tt) ac[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0, af[g][tt], ac[tt], 0, 0, 0);
-            }
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        sw_mma_chunks<isq ? KC : 2, NT>(ar, LDX, nch, nch, reg, ac);
       }
       load_w(std::integral_constant<int, S + NSETS>{}, reg);
       // bias, the attention's scale on q, zero padding -> the bf16 tiles the attention reads
@@ -332,7 +283,7 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     {
       // columns [d, 32 KC) of the attention tile: the proj GEMM's k padding
       const int row = tid >> 5, c = d + (tid & 31);
-      if (c < KC * 32) A1[row * B_LDA + c] = (__bf16)0.f;
+      if (c < KC * 32) A1[row * SW_LDA + c] = (__bf16)0.f;
     }
     // ---- one head per wave: S = q k^T + bias + mask, softmax, O = P V for this tile's 16 queries against the window's 64 keys ----
     if (wave_s < HEADS) {
@@ -340,9 +291,10 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
       const __bf16* Qs = Qb + h * 16 * HS;
       const __bf16* Ks = KV + h * 64 * HS;
       const __bf16* Vs = KV + (HEADS + h) * 64 * HS;
-      __bf16* Pw = Ps + h * 16 * B_LDP;
+      __bf16* Pw = Ps + h * 16 * SW_LDP;
       f32x4 sc[4];
       // relative position bias + 0 / -100 shift mask (drct.py:284-292, 449-470) of the lane's 16 (key, query) pairs
+      // (qkv_attn_kernel's sw_bias_mask, written out: with it and sw_window the step ran 0.1 - 0.2 % slower)
       {
         int qi[4];
 #pragma unroll
@@ -390,7 +342,7 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
         const float rs = srad_row16_sum(pr[0] + pr[1]) + srad_row16_sum(pr[2] + pr[3]);   // the two key halves, as qkv_attn_kernel sums them
         if (fr == 0) lsum[h * 16 + 4 * fq + e] = rs;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) Pw[(4 * fq + e) * B_LDP + j * 16 + fr] = (__bf16)pr[j];
+        for (int j = 0; j < 4; ++j) Pw[(4 * fq + e) * SW_LDP + j * 16 + fr] = (__bf16)pr[j];
       }
       __builtin_amdgcn_wave_barrier();                            // P and the sums are this wave's own: LDS keeps a wave's accesses in order
       const float inv = 1.0f / lsum[h * 16 + fr];
@@ -400,18 +352,12 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
         f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 64; kk += 32) {
-          const bf16x8 pa = *reinterpret_cast<const bf16x8*>(Pw + fr * B_LDP + kk + 8 * fq);
-          typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-          const __bf16* r0 = Vs + (kk + 8 * fq + tq) * HS + j * 16 + 4 * tp;
-          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0));
-          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(r0 + 4 * HS));
-          bf16x8 vb;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { vb[e] = lo[e]; vb[4 + e] = hi[e]; }
+          const bf16x8 pa = *reinterpret_cast<const bf16x8*>(Pw + fr * SW_LDP + kk + 8 * fq);
+          const bf16x8 vb = sw_read_v_tr(Vs + (kk + 8 * fq + tq) * HS + j * 16 + 4 * tp, HS);
           o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb, pa, o, 0, 0, 0);
         }
         // transposed result: token fr of the tile, columns 16 j + 4 fq + e of the head -> the proj GEMM's A tile
-        __bf16* dst = A1 + fr * B_LDA + h * hd;
+        __bf16* dst = A1 + fr * SW_LDA + h * hd;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int c = j * 16 + 4 * fq + e;
@@ -422,28 +368,19 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   }();
 
   // ============================ MLP half: mlp_block_kernel<16> on the tile's 16 token rows ============================
-  auto col4_of = [&](int g) { return B_SC * g + 16 * wave + 4 * fq; };
+  auto col4_of = [&](int g) { return SW_SC * g + 16 * wave + 4 * fq; };
   auto store_bf4 = [&](__bf16* base, int ld, int c4, f32x4 v) __attribute__((always_inline)) {
     bf16x4 h;
     h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
     *reinterpret_cast<bf16x4*>(base + fr * ld + c4) = h;
   };
   // c += (A[16 rows][k0 .. k0 + nch*32) . W[16 columns of this wave][..]^T)^T
-  auto mma_stage = [&](const __bf16* A, int lda, int k0, int nch, const u32x4 (&reg)[RC], f32x4& c) __attribute__((always_inline)) {
-    const __bf16* ar = A + fr * lda + k0 + 8 * fq;
-    bf16x8 af[8];
-#pragma unroll
-    for (int g = 0; g < 8; ++g)
-      if (g < nch) af[g] = *reinterpret_cast<const bf16x8*>(ar + g * 32);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int g = 0; g < 8; ++g)
-      if (g < nch) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, reg[g]), af[g], c, 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
+  auto mma_stage = [&](const __bf16* A, int lda, int k0, int nch, const u32x4 (&reg)[RC], f32x4 (&c)[1]) __attribute__((always_inline)) {
+    sw_mma_chunks<8, 1>(A + fr * lda + k0 + 8 * fq, lda, nch, 8, reg, c);
   };
   auto epi_proj = [&](auto GI, const f32x4& c) __attribute__((always_inline)) {
     constexpr int g = decltype(GI)::value;
-    x1[g] += c + *reinterpret_cast<const f32x4*>(v_bp + min(col4_of(g), 380));
+    x1[g] += c + *reinterpret_cast<const f32x4*>(v_bp + min(col4_of(g), SW_VD - 4));
     if constexpr (g != GD - 1) return;
     // LayerNorm2 over the d real columns of x1 -> bf16 -> A1 (all proj reads of A1 are behind a barrier)
     float sm = 0.f, sq = 0.f;
@@ -465,33 +402,33 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
 #pragma unroll
     for (int gg = 0; gg < GD; ++gg) {
       const int c4 = col4_of(gg);
-      const f32x4 gam = *reinterpret_cast<const f32x4*>(v_g2 + min(c4, 380));
-      const f32x4 bet = *reinterpret_cast<const f32x4*>(v_b2n + min(c4, 380));
-      store_bf4(A1, B_LDA, c4, c4 < d ? (x1[gg] - mu) * rstd * gam + bet : f32x4{0.f, 0.f, 0.f, 0.f});
+      const f32x4 gam = *reinterpret_cast<const f32x4*>(v_g2 + min(c4, SW_VD - 4));
+      const f32x4 bet = *reinterpret_cast<const f32x4*>(v_b2n + min(c4, SW_VD - 4));
+      store_bf4(A1, SW_LDA, c4, c4 < d ? (x1[gg] - mu) * rstd * gam + bet : f32x4{0.f, 0.f, 0.f, 0.f});
     }
   };
   auto epi_fc1 = [&](int g, const f32x4& c) __attribute__((always_inline)) {
     const int c4 = col4_of(g);
-    f32x4 v = c + *reinterpret_cast<const f32x4*>(v_bf1 + min(c4, 508));
+    f32x4 v = c + *reinterpret_cast<const f32x4*>(v_bf1 + min(c4, SW_VM - 4));
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = blk_gelu(v[e]);
-    store_bf4(Hs, B_LDH, c4, c4 < m ? v : f32x4{0.f, 0.f, 0.f, 0.f});      // m % 4 == 0
+    for (int e = 0; e < 4; ++e) v[e] = gelu_fast(v[e]);
+    store_bf4(Hs, SW_LDH, c4, c4 < m ? v : f32x4{0.f, 0.f, 0.f, 0.f});      // m % 4 == 0
   };
   auto epi_fc2 = [&](auto GI, const f32x4& c) __attribute__((always_inline)) {
     constexpr int g = decltype(GI)::value;
-    x1[g] += c + *reinterpret_cast<const f32x4*>(v_bf2 + min(col4_of(g), 380));
+    x1[g] += c + *reinterpret_cast<const f32x4*>(v_bf2 + min(col4_of(g), SW_VD - 4));
     if constexpr (g != GD - 1) return;
     // x2 -> bf16 -> A1 (its last readers, the fc1 stages, finished long ago)
 #pragma unroll
     for (int gg = 0; gg < GD; ++gg) {
       const int c4 = col4_of(gg);
-      store_bf4(A1, B_LDA, c4, c4 < d ? x1[gg] : f32x4{0.f, 0.f, 0.f, 0.f});
+      store_bf4(A1, SW_LDA, c4, c4 < d ? x1[gg] : f32x4{0.f, 0.f, 0.f, 0.f});
     }
   };
   auto epi_adj = [&](int g, const f32x4& c) __attribute__((always_inline)) {
     const int c4 = col4_of(g);
     const int cc = min(c4, no - 4);                                 // no % 4 == 0
-    const f32x4 ba = *reinterpret_cast<const f32x4*>(v_ba + min(c4, 380));
+    const f32x4 ba = *reinterpret_cast<const f32x4*>(v_ba + min(c4, SW_VD - 4));
     f32x4 rv = {0.f, 0.f, 0.f, 0.f};
     if (p.R) rv = *reinterpret_cast<const f32x4*>(p.R + (size_t)row_tok * p.ldr + cc);
     f32x4 v = c + ba;
@@ -503,28 +440,24 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     if (c4 < no) *reinterpret_cast<f32x4*>(p.Y + (size_t)row_tok * p.ldy + p.yoff + c4) = v;
   };
 
-  f32x4 c;
+  f32x4 c[1];
   static_for<0, n_mlp>([&](auto SI) {
     constexpr int s = decltype(SI)::value;
-    constexpr int ph = s < n_proj ? 0 : (s < n_proj + n_fc1 ? 1 : (s < n_proj + n_fc1 + n_fc2 ? 2 : 3));
-    constexpr int ls = s - (ph == 0 ? 0 : (ph == 1 ? n_proj : (ph == 2 ? n_proj + n_fc1 : n_proj + n_fc1 + n_fc2)));
-    constexpr int kgs = ph == 2 ? KGM : KGD;
-    constexpr int g = ls / kgs, kg = ls - g * kgs;
+    constexpr MlpStage sg = Chain::stage(s);
+    constexpr int ph = sg.ph, g = sg.g, kg = sg.kg, nch = sg.nch;
     u32x4 (&reg)[RC] = w_reg[(QS + s) % NSETS];
-    constexpr int kch = ph == 2 ? KCM : KCD;
-    constexpr int nch = kch - kg * 8 < 8 ? kch - kg * 8 : 8;
-    if constexpr (ls == 0) __syncthreads();            // first stage of a phase: the activation tile (A1 / Hs) is complete
-    if constexpr (kg == 0) c = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (sg.first) __syncthreads();            // first stage of a phase: the activation tile (A1 / Hs) is complete
+    if constexpr (kg == 0) c[0] = f32x4{0.f, 0.f, 0.f, 0.f};
     const bool live = (g * 8 + wave_s) * 16 < (ph == 0 ? d : (ph == 1 ? m : (ph == 2 ? d : no)));
-    if (live) mma_stage(ph == 2 ? Hs : A1, ph == 2 ? B_LDH : B_LDA, kg * 256, nch, reg, c);
+    if (live) mma_stage(ph == 2 ? Hs : A1, ph == 2 ? SW_LDH : SW_LDA, kg * 256, nch, reg, c);
     // refill this set, NSETS stages ahead; behind an epilogue that other waves wait for (see mlp_block_kernel)
-    constexpr bool epi_first = kg == kgs - 1;
+    constexpr bool epi_first = sg.last;
     if constexpr (!epi_first) load_w(std::integral_constant<int, QS + s + NSETS>{}, reg);
     if constexpr (epi_first) {
-      if constexpr (ph == 0) epi_proj(std::integral_constant<int, g>{}, c);
-      else if constexpr (ph == 1) epi_fc1(g, c);
-      else if constexpr (ph == 2) epi_fc2(std::integral_constant<int, g>{}, c);
-      else epi_adj(g, c);
+      if constexpr (ph == 0) epi_proj(std::integral_constant<int, g>{}, c[0]);
+      else if constexpr (ph == 1) epi_fc1(g, c[0]);
+      else if constexpr (ph == 2) epi_fc2(std::integral_constant<int, g>{}, c[0]);
+      else epi_adj(g, c[0]);
       load_w(std::integral_constant<int, QS + s + NSETS>{}, reg);
     }
   });
@@ -543,42 +476,18 @@ int launch_blk(const SwinBlockParams& p, hipStream_t stream) {
   return SRAD_OK;
 }
 
-// DRCT-L's five Swin blocks (d = 180 / 212 / 244 / 276 / 308): (head tiles, k chunks of d, heads) of the attention
-// half, then mlp_block's stage geometry (column groups of d, k groups of d, column groups of m, k groups of m, column groups
-// of the adjust output, k chunks of m)
-#define SRAD_BLK_CFGS(X) X(2, 6, 6, 2, 1, 3, 2, 1, 12) X(4, 7, 4, 2, 1, 4, 2, 1, 14) X(8, 8, 2, 2, 1, 4, 2, 1, 16) \
-  X(3, 9, 6, 3, 2, 3, 2, 1, 9) X(5, 10, 4, 3, 2, 3, 2, 2, 10)
-
-struct BlkKey { int hdt, kc, heads, gd, kgd, gm, kgm, gn, kcm; };
-inline BlkKey blk_key(int d, int heads, int m, int no) {
-  const int Kd = srad_cp(d), Km = srad_cp(m);
-  return BlkKey{(d / heads + 15) / 16, Kd / 32, heads, (d + B_SC - 1) / B_SC, (Kd + 255) / 256, (m + B_SC - 1) / B_SC, (Km + 255) / 256,
-                (no + B_SC - 1) / B_SC, Km / 32};
-}
-#define SRAD_BLK_MATCH(K_, A_, B_, H_, GD_, KGD_, GM_, KGM_, GN_, KCM_) \
-  (K_.hdt == A_ && K_.kc == B_ && K_.heads == H_ && K_.gd == GD_ && K_.kgd == KGD_ && K_.gm == GM_ && K_.kgm == KGM_ && K_.gn == GN_ && K_.kcm == KCM_)
-
-// CUs of the current device (cached per device)
-int blk_cu_count() {
-  static int cus[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int n = 0;
-    cus[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-  }
-  return cus[dev];
-}
+// the whole geometry key: head tiles, heads and the MLP chain's stages (instances: swin_tiles.h's table of block shapes)
+constexpr bool blk_key_eq(const SwinKey& a, const SwinKey& b) { return a.hdt == b.hdt && a.heads == b.heads && swin_key_mlp_eq(a, b); }
 }  // namespace
 
 extern "C" int srad_swin_block_supported(int prec, int ws, int B, int H, int W, int d, int heads, int hidden, int no) {
   if (prec != SRAD_PREC_BF16 || ws != 8 || B < 1 || H < 8 || W < 8 || H % 8 || W % 8 || d % 4 || hidden % 4 || no % 4 || d < 32 || d > 320 ||
       hidden < 32 || hidden > 512 || no < 4 || no > 384 || heads < 1 || d % heads)
     return false;
-  if ((long long)B * (H / 8) * (W / 8) * 4 > blk_cu_count()) return false;   // one workgroup per CU, all resident: a quarter window each
-  const BlkKey k = blk_key(d, heads, hidden, no);
-#define X(...) if (SRAD_BLK_MATCH(k, __VA_ARGS__)) return true;
-  SRAD_BLK_CFGS(X)
+  if ((long long)B * (H / 8) * (W / 8) * 4 > srad_cu_count()) return false;   // one workgroup per CU, all resident: a quarter window each
+  const SwinKey c = swin_key(d, heads, hidden, no);
+#define X(d_, h_, m_, no_, wpc_) if (blk_key_eq(c, swin_key(d_, h_, m_, no_))) return true;
+  SRAD_SWIN_SHAPES(X)
 #undef X
   return false;
 }
@@ -609,10 +518,10 @@ int srad_launch_swin_block(const SwinBlockParams& p, hipStream_t stream) {
   // the output may share x's buffer only as the columns behind the block's own (adjust_k); anything else would race with the
   // other workgroups' reads of columns [0, d)
   SRAD_REQUIRE(p.Y != p.x || (p.ldy == p.ldx && p.yoff >= p.d), "swin_block: an in-place output must lie behind the block's %d input columns", p.d);
-  const BlkKey k = blk_key(p.d, p.heads, p.m, p.no);
-#define X(a, b, h, gd, kgd, gm, kgm, gn, kcm) \
-  if (SRAD_BLK_MATCH(k, a, b, h, gd, kgd, gm, kgm, gn, kcm)) return launch_blk<a, b, h, gd, kgd, gm, kgm, gn, kcm>(p, stream);
-  SRAD_BLK_CFGS(X)
+  const SwinKey c = swin_key(p.d, p.heads, p.m, p.no);
+#define X(d_, h_, m_, no_, wpc_) \
+  if (constexpr SwinKey k = swin_key(d_, h_, m_, no_); blk_key_eq(c, k)) return launch_blk<k.hdt, k.kc, k.heads, k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kcm>(p, stream);
+  SRAD_SWIN_SHAPES(X)
 #undef X
   return srad_set_error(SRAD_ERR_ARG, "swin_block: no kernel instance for this geometry");
 }

@@ -11,31 +11,17 @@
 // into MFMA registers three stages ahead, results are transposed so a lane owns 4 consecutive columns of a token row.
 // It replaces two data-gradient GEMM launches and the LayerNorm backward launch of the unfused chain and the
 // [M][m] + [M][d] round trips between them.
-#include "srad_common.h"
+#include "swin_tiles.h"
 bool srad_mlp_bwd_bf16_out(int M);
-#include <type_traits>
 
 namespace {
 
-template <int B, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < N) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, N>(f);
-  }
-}
+// tile strides and stage width: swin_tiles.h's SW_LDA / SW_LDH / SW_SC, as the forward kernel's
 
-constexpr int FB_LDA = 400;        // LDS row stride of the <=384-wide bf16 dx2 tile
-constexpr int FB_LDH = 528;        // LDS row stride of the <=512-wide bf16 dh tile
-constexpr int FB_SC = 128;         // output columns per weight stage
-
-// d/dx of the exact-erf GELU, Phi(x) + x phi(x), with erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7)
+// d/dx of the exact-erf GELU, Phi(x) + x phi(x)
 __device__ __forceinline__ float dgelu_fast(float x) {
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = 1.0f / (1.0f + 0.3275911f * z);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float ex = __expf(-z * z);                   // exp(-x^2 / 2)
-  const float erfa = 1.0f - poly * ex;
+  float ex;
+  const float erfa = srad_erf_abs(x, ex);
   return 0.5f * (1.0f + (x < 0.f ? -erfa : erfa)) + x * 0.39894228040143267794f * ex;
 }
 
@@ -49,7 +35,7 @@ __device__ __forceinline__ void ln_bwd_tail(f32x4 (&dxn)[GD][NRT], f32x4 (&xv)[G
                                             int ld_out, float* prow, __bf16* a_out = nullptr, int lda_out = 0,
                                             __bf16* h_out0 = nullptr, const float* h_scale = nullptr) {
   const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto col4_of = [&](int g) { return FB_SC * g + 16 * wave + 4 * fq; };
+  auto col4_of = [&](int g) { return SW_SC * g + 16 * wave + 4 * fq; };
   const float invC = 1.0f / (float)d;
   auto row_reduce2 = [&](float (&a)[NRT], float (&b)[NRT]) {     // sums over the whole row: 4 fq groups x 8 waves
 #pragma unroll
@@ -170,9 +156,9 @@ __global__ __launch_bounds__(512) void mlp_bwd_kernel(const MlpBwdParams p, floa
   constexpr int NRT = FM / 16;
   constexpr int LDAA = KCA * 32 + 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* A1 = reinterpret_cast<__bf16*>(smem);                  // [FM][FB_LDA] dx2
-  __bf16* Hs = A1 + FM * FB_LDA;                                 // [FM][FB_LDH] dh
-  float* v_g = reinterpret_cast<float*>(Hs + FM * FB_LDH);       // [384] gamma
+  __bf16* A1 = reinterpret_cast<__bf16*>(smem);                  // [FM][SW_LDA] dx2
+  __bf16* Hs = A1 + FM * SW_LDA;                                 // [FM][SW_LDH] dh
+  float* v_g = reinterpret_cast<float*>(Hs + FM * SW_LDH);       // [384] gamma
   float* red = v_g + 384;                                        // [FM][8 waves][2] row partial sums
   [[maybe_unused]] __bf16* Aa = reinterpret_cast<__bf16*>(red + FM * 16);   // [FM][LDAA] gradient of the adjust conv's output
 
@@ -236,7 +222,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_kernel(const MlpBwdParams p, floa
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  auto col4_of = [&](int g) { return FB_SC * g + 16 * wave + 4 * fq; };
+  auto col4_of = [&](int g) { return SW_SC * g + 16 * wave + 4 * fq; };
   auto store_bf4 = [&](__bf16* base, int ld, int rt, int c4, f32x4 v) {
     bf16x4 h;
     h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
@@ -315,7 +301,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_kernel(const MlpBwdParams p, floa
       } else {
         const f32x4 v = c < d ? a_reg[j] : z4;
         h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
-        *reinterpret_cast<bf16x4*>(A1 + row * FB_LDA + c) = h;
+        *reinterpret_cast<bf16x4*>(A1 + row * SW_LDA + c) = h;
       }
     }
   }
@@ -338,7 +324,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_kernel(const MlpBwdParams p, floa
       for (int rt = 0; rt < NRT; ++rt) c[rt] = z4;
     }
     if ((g * 8 + wave_s) * 16 < (ph == 0 ? m : d))
-      mma_stage(ph == -1 ? Aa : (ph == 0 ? A1 : Hs), ph == -1 ? LDAA : (ph == 0 ? FB_LDA : FB_LDH), kg * 256, nch, reg, c);
+      mma_stage(ph == -1 ? Aa : (ph == 0 ? A1 : Hs), ph == -1 ? LDAA : (ph == 0 ? SW_LDA : SW_LDH), kg * 256, nch, reg, c);
     load_w(std::integral_constant<int, s + NSETS>{}, reg);
     if constexpr (kg == kgs - 1) {
       if constexpr (ph == -1) {                        // dx2 = alpha * dA . Wadj: residual registers, global copy, bf16 A tile
@@ -357,7 +343,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_kernel(const MlpBwdParams p, floa
           } else if (c4 < d) {
             *reinterpret_cast<f32x4*>(p.dx2 + (size_t)(m0 + rt * 16 + fr) * d + c4) = v;
           }
-          store_bf4(A1, FB_LDA, rt, c4, v);
+          store_bf4(A1, SW_LDA, rt, c4, v);
         }
       } else if constexpr (ph == 0) {
         const int c4 = col4_of(g);
@@ -382,7 +368,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_kernel(const MlpBwdParams p, floa
           } else if (c4 < m) {
             *reinterpret_cast<f32x4*>(p.dh + (size_t)(m0 + rt * 16 + fr) * m + c4) = v;
           }
-          store_bf4(Hs, FB_LDH, rt, c4, v);
+          store_bf4(Hs, SW_LDH, rt, c4, v);
         }
       } else {
 #pragma unroll
@@ -415,7 +401,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_kernel(const MlpBwdParams p, floa
     }
   }
   ln_bwd_tail<NRT, GD>(dxn, xv, r2, v_g, red, d, wave, fr, fq, p.dx1 + (size_t)m0 * d, d, part + (size_t)tile_i * (2 * SRAD_LNB_CP),
-                       p.w_projt ? A1 : nullptr, FB_LDA, (HOUT && p.w_projt && p.dx1s_h) ? p.dx1s_h + (size_t)m0 * d : nullptr, rs1v);
+                       p.w_projt ? A1 : nullptr, SW_LDA, (HOUT && p.w_projt && p.dx1s_h) ? p.dx1s_h + (size_t)m0 * d : nullptr, rs1v);
   if (p.w_projt) {
     __syncthreads();                                             // the dx1 tile is complete
     static_for<0, n_proj>([&](auto S) {
@@ -427,7 +413,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_kernel(const MlpBwdParams p, floa
 #pragma unroll
         for (int rt = 0; rt < NRT; ++rt) c[rt] = z4;
       }
-      if ((g * 8 + wave_s) * 16 < d) mma_stage(A1, FB_LDA, kg * 256, nch, reg, c);
+      if ((g * 8 + wave_s) * 16 < d) mma_stage(A1, SW_LDA, kg * 256, nch, reg, c);
       load_wp(std::integral_constant<int, s + NSETS>{}, reg);
       if constexpr (kg == KGD - 1) {
         const int c4 = col4_of(g);
@@ -507,7 +493,7 @@ __global__ __launch_bounds__(512) void lin_ln_bwd_kernel(const LinLnBwdParams p,
 #pragma unroll
     for (int cc = 0; cc < nch; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + cc * step);
   };
-  auto col4_of = [&](int g) { return FB_SC * g + 16 * wave + 4 * fq; };
+  auto col4_of = [&](int g) { return SW_SC * g + 16 * wave + 4 * fq; };
   // loads in the order their data is needed, all unconditional (see mlp_block_kernel): residual / input rows, gamma, the dY
   // tile, then the weight stages
   const float gq = p.ln_g[min(tid, d - 1)];
@@ -626,11 +612,11 @@ int launch_lin(const LinLnBwdParams& p, WgradQueue& q, hipStream_t stream) {
 
 struct BwdCfg { int gd, kcd, gm, kcm, kca; };
 inline BwdCfg bwd_cfg(int d, int m, int KA) {
-  return BwdCfg{(d + FB_SC - 1) / FB_SC, srad_cp(d) / 32, (m + FB_SC - 1) / FB_SC, srad_cp(m) / 32, (KA + 31) / 32};
+  return BwdCfg{(d + SW_SC - 1) / SW_SC, srad_cp(d) / 32, (m + SW_SC - 1) / SW_SC, srad_cp(m) / 32, (KA + 31) / 32};
 }
 template <int FM, int GD, int KCD, int GM, int KCM, int KCA, bool HOUT = false>
 int launch_bwd_fm(const MlpBwdParams& p, WgradQueue& q, hipStream_t stream) {
-  constexpr size_t lds = (size_t)(FM * FB_LDA + FM * FB_LDH) * 2 + (384 + FM * 16) * sizeof(float) +
+  constexpr size_t lds = (size_t)(FM * SW_LDA + FM * SW_LDH) * 2 + (384 + FM * 16) * sizeof(float) +
                          (KCA > 0 ? (size_t)FM * (KCA * 32 + 16) * 2 : 0);
   float* part = nullptr;
   SRAD_TRY(srad_wgrad_queue_ln_partials(q, p.dgamma, p.dbeta, p.d, p.M / FM, stream, &part));
@@ -694,7 +680,7 @@ int srad_launch_mlp_bwd(const MlpBwdParams& p, WgradQueue& q, hipStream_t stream
 
 bool srad_lin_ln_bwd_supported(int prec, int M, int K, int d) {
   if (!(prec == SRAD_PREC_BF16 && M % 16 == 0 && d % 4 == 0 && K % 4 == 0 && d >= 32 && d <= SRAD_LNB_CP && K >= 32 && K <= 1024)) return false;
-  const int gd = (d + FB_SC - 1) / FB_SC, kc = srad_cp(K) / 32;
+  const int gd = (d + SW_SC - 1) / SW_SC, kc = srad_cp(K) / 32;
 #define X(a, b) if (gd == a && kc == b) return true;
   SRAD_LIN_CFGS(X)
 #undef X
@@ -707,7 +693,7 @@ int srad_launch_lin_ln_bwd(const LinLnBwdParams& p, WgradQueue& q, hipStream_t s
   SRAD_REQUIRE(((p.ld_dy | p.ldx | p.ld_out | (p.dres ? p.ld_dres : 0)) & 3) == 0 &&
                    (((uintptr_t)p.dY | (uintptr_t)p.x | (uintptr_t)p.out | (uintptr_t)p.dres) & 15) == 0,
                "lin_ln_bwd: rows must be 16-byte aligned (strides multiples of 4 floats)");
-  const int gd = (p.d + FB_SC - 1) / FB_SC, kc = srad_cp(p.K) / 32;
+  const int gd = (p.d + SW_SC - 1) / SW_SC, kc = srad_cp(p.K) / 32;
 #define X(a, b) if (gd == a && kc == b) return launch_lin<a, b>(p, q, stream);
   SRAD_LIN_CFGS(X)
 #undef X

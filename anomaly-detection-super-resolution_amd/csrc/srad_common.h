@@ -27,8 +27,29 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 int srad_set_error(int code, const char* fmt, ...);
+// CUs of the current device (cached per device; 256 where it cannot be asked)
+inline int srad_cu_count() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    cus[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+  }
+  return cus[dev];
+}
 
 #if defined(__HIPCC__)
+#include <type_traits>
+// compile-time loop: f(std::integral_constant<int, I>{}) for I = B .. N-1 (stage geometry as template parameters: a run-time
+// index into a register array sends it to scratch)
+template <int B, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (B < N) {
+    f(std::integral_constant<int, B>{});
+    static_for<B + 1, N>(f);
+  }
+}
 // Sum over the 64 lanes of a wave, result in every lane.  The first four butterfly steps are DPP lane swizzles
 // (VALU speed: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror); only the last two cross a 16-lane
 // row and go through ds_bpermute.  A plain __shfl_xor chain is six dependent LDS round trips.
@@ -85,6 +106,15 @@ __device__ __forceinline__ double srad_block_sum(double v, double* red) {
     __syncthreads();
   }
   return red[0];
+}
+// erf(|x| / sqrt 2) by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7: enough below bf16 resolution, ~4x fewer instructions than
+// erff); ex = exp(-x^2 / 2), which the GELU's derivative needs too
+__device__ __forceinline__ float srad_erf_abs(float x, float& ex) {
+  const float z = fabsf(x) * 0.70710678118654752440f;
+  const float t = 1.0f / (1.0f + 0.3275911f * z);
+  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+  ex = __expf(-z * z);
+  return 1.0f - poly * ex;
 }
 // Shifted-window geometry (cyclic shift + window partition as index arithmetic): position (py, px) of window (wy, wx) of image b
 // -> its token in the unshifted [B][H][W] order, and an info word (shift-mask region << 16) | (py << 8) | px.  The region is
