@@ -44,7 +44,13 @@ class ResampleTable(C.Structure):
                 ("dev_bounds", C.c_void_p), ("dev_coeffs", C.c_void_p)]
 
 
+class ResampleTableF(C.Structure):
+    """One axis of srad_resize_f32 (include/srad.h srad_resample_table_f): as ResampleTable, the device taps are double."""
+    _fields_ = ResampleTable._fields_
+
+
 RESAMPLE_FILTERS = {"lanczos": 0, "bicubic": 1}
+RESAMPLE_FILTERS_F = dict(RESAMPLE_FILTERS, bilinear=2)      # the float32 resize takes BILINEAR too
 
 WQ_WGRAD, WQ_WGRAD_DEFERRED, WQ_LAUNCH_DEFERRED, WQ_LN_BWD, WQ_ATTN_BWD, WQ_FLUSH = 1, 2, 3, 4, 5, 6
 WQ_FLUSH_EXPLICIT, WQ_FLUSH_BATCH, WQ_FLUSH_WS = 0, 1, 2
@@ -130,6 +136,13 @@ _SIG = {
     "srad_resample_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),
     "srad_resize_u8": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.POINTER(ResampleTable),
                                  C.POINTER(ResampleTable), _P, _P]),
+    # float32 resize (PIL mode F exact) and the overlay
+    "srad_resample_ksize_f64": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "srad_resample_coeffs_f64": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),
+    "srad_resize_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.POINTER(ResampleTableF),
+                                  C.POINTER(ResampleTableF), _P, _P]),
+    "srad_overlay_rgb": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   _P, _P]),
     # scorer
     "srad_to_u8_hwc": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "srad_quantize": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),

@@ -645,6 +645,92 @@ def resize_u8(x: torch.Tensor, size, filter: str = "lanczos", *, out: Optional[t
     return out
 
 
+# ----------------------------------------------------------------------------------- float32 resize, equal to PIL's mode-F resize
+def resample_coeffs_f64(in_size: int, out_size: int, filter: str = "bilinear"):
+    """(ksize, bounds int32 [out, 2], coeffs float64 [out, ksize]) of one axis as numpy arrays (``srad_resample_coeffs_f64``;
+    host only, needs no GPU): the taps Pillow resamples mode-F images with, divided by their sum and left in double.
+    ValueError for an unknown filter, RuntimeError for refused sizes."""
+    import numpy as np
+    if filter not in L.RESAMPLE_FILTERS_F:
+        raise ValueError(f"resample filter {filter!r}: one of {sorted(L.RESAMPLE_FILTERS_F)}")
+    f, k = L.RESAMPLE_FILTERS_F[filter], C.c_int()
+    L.check(L.lib().srad_resample_ksize_f64(int(in_size), int(out_size), f, C.byref(k)), "resample_ksize_f64")
+    bounds = np.empty((int(out_size), 2), dtype=np.int32)
+    coeffs = np.empty((int(out_size), k.value), dtype=np.float64)
+    L.check(L.lib().srad_resample_coeffs_f64(int(in_size), int(out_size), f, bounds.ctypes.data, coeffs.ctypes.data), "resample_coeffs_f64")
+    return k.value, bounds, coeffs
+
+
+_RESAMPLE_TABLES_F: dict = {}
+
+
+def resample_table_f(in_size: int, out_size: int, filter: str, device) -> tuple:
+    """``resample_table`` for the float32 resize: the ``_lib.ResampleTableF`` of one axis on ``device`` and what keeps its arrays
+    alive, cached per (in, out, filter, device)."""
+    key = (int(in_size), int(out_size), filter, str(device))
+    hit = _RESAMPLE_TABLES_F.get(key)
+    if hit is None:
+        ksize, bounds, coeffs = resample_coeffs_f64(in_size, out_size, filter)
+        dev_bounds, dev_coeffs = torch.from_numpy(bounds).to(device), torch.from_numpy(coeffs).to(device)
+        table = L.ResampleTableF(int(in_size), int(out_size), ksize, bounds.ctypes.data, dev_bounds.data_ptr(), dev_coeffs.data_ptr())
+        hit = _RESAMPLE_TABLES_F[key] = (table, (bounds, dev_bounds, dev_coeffs))
+    return hit
+
+
+def resize_f32(x: torch.Tensor, size, filter: str = "bilinear", *, out: Optional[torch.Tensor] = None,
+               tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x float32 [n,H,W], contiguous, on the GPU -> float32 [n,h,w] with ``size = (h, w)``: every value equals, bit for bit,
+    ``Image.fromarray(a, mode='F').resize((w, h), BILINEAR | BICUBIC | LANCZOS)`` of the map (``srad_resize_f32``).  ``out`` /
+    ``tmp`` ([n,H,w]): buffers to use instead of fresh ones."""
+    _need_cuda(x)
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"resize_f32: expected a contiguous float32 [n,H,W] tensor, got {tuple(x.shape)} {x.dtype}"
+                         f"{'' if x.is_contiguous() else ', not contiguous'}")
+    if filter not in L.RESAMPLE_FILTERS_F:
+        raise ValueError(f"resample filter {filter!r}: one of {sorted(L.RESAMPLE_FILTERS_F)}")
+    n, H, W = x.shape
+    h, w = int(size[0]), int(size[1])
+    if h < 1 or w < 1 or n < 1 or H < 1 or W < 1:
+        raise ValueError(f"resize_f32: {n} maps of {H}x{W} to {h}x{w}: every size must be >= 1")
+    for t, shape, what in ((out, (n, h, w), "out"), (tmp, (n, H, w), "tmp")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"resize_f32: {what} must be a contiguous float32 GPU tensor of shape {shape}")
+    if out is None:
+        out = torch.empty(n, h, w, dtype=torch.float32, device=x.device)
+    xt = resample_table_f(W, w, filter, x.device)[0] if W != w else None
+    yt = resample_table_f(H, h, filter, x.device)[0] if H != h else None
+    if tmp is None and xt is not None and yt is not None:
+        tmp = torch.empty(n, H, w, dtype=torch.float32, device=x.device)
+    L.check(L.lib().srad_resize_f32(L.dptr(x), n, H, W, L.dptr(out), h, w, xt, yt, L.dptr(tmp), L.current_stream_ptr()), "resize_f32")
+    return out
+
+
+# ----------------------------------------------------------------------------------- overlay: heat map and mask outline on the image
+def overlay_rgb(src: torch.Tensor, maps: torch.Tensor, masks: torch.Tensor, lut: torch.Tensor, scale: float, contour_radius: int = 1,
+                contour_rgb=(255, 255, 255), *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src uint8 [n,H,W,Cs] (Cs 1 or 3; gray is replicated), maps float32 [n,H,W], masks uint8 [n,H,W], lut uint8 [256,4]
+    (r, g, b, alpha per level), all contiguous on the GPU -> uint8 [n,H,W,3] (``srad_overlay_rgb``): level = ``maps * scale``
+    truncated into 0..255 (NaN: 0), ``out_c = (src_c * (255 - a) + lut_c * a + 127) // 255``, and a mask pixel with a 0 or the
+    image's border within Chebyshev distance ``contour_radius`` (0..4; 0 draws none) takes ``contour_rgb``."""
+    _need_cuda(src, maps, masks, lut, out)
+    if src.dim() != 4 or src.dtype != torch.uint8 or src.shape[3] not in (1, 3) or not src.is_contiguous():
+        raise ValueError(f"overlay_rgb: expected a contiguous uint8 [n,H,W,1|3] source, got {tuple(src.shape)} {src.dtype}")
+    n, H, W, Cs = src.shape
+    for t, dtype, shape, what in ((maps, torch.float32, (n, H, W), "maps"), (masks, torch.uint8, (n, H, W), "masks"),
+                                  (lut, torch.uint8, (256, 4), "lut"), (out, torch.uint8, (n, H, W, 3), "out")):
+        if t is not None and not (t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"overlay_rgb: {what} must be a contiguous {dtype} GPU tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+    r = int(contour_radius)
+    colour = [int(v) for v in contour_rgb]
+    if r != contour_radius or len(colour) != 3:
+        raise ValueError(f"overlay_rgb: contour radius {contour_radius!r} / colour {contour_rgb!r}: an integer and three integers")
+    if out is None:
+        out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=src.device)
+    L.check(L.lib().srad_overlay_rgb(L.dptr(src), n, H, W, Cs, L.dptr(maps), L.dptr(masks), L.dptr(lut), float(scale), r, *colour,
+                                     L.dptr(out), L.current_stream_ptr()), "overlay_rgb")
+    return out
+
+
 # ----------------------------------------------------------------------------------- DRN's own kernels, one by one
 # (C ABI ``srad_op_drn_*``, csrc/drn.hip).  Every call goes through the launcher the engines use, so grid, slices per image,
 # NI and storage instance are the engines' own.  ``out=`` tensors let a test place an output inside a guarded allocation.

@@ -2,6 +2,7 @@
 
     python -m srad_amd.predict --run-dir <run> --calibrate <dir of defect-free images> --threshold-fpr 0.01 [--map-ws 11 ...]
     python -m srad_amd.predict --run-dir <run> --input <files or directories> [--threshold T] [--save-masks ...]
+    python -m srad_amd.predict --run-dir <run> --input <files or directories> --source-frame --save-overlays
 
 ``Detector`` chains what the evaluator already has - SR forward, anomaly maps (``evaluate.MapSpec``), operating point
 (``metrics.operating_point``) - behind one step the evaluator leaves to ``prepare_mvtec_data``: turning a raw image into the
@@ -9,7 +10,12 @@
 and here both run on the GPU (``ops.resize_u8``, equal to PIL byte for byte; DESIGN.md "Resize on the device"), so the pair is
 exactly what ``prepare_mvtec_data._write_pyramid`` followed by ``evaluate.iter_split`` gives and the maps and thresholds mean
 what they mean in the evaluator.  Calibration writes ``<run-dir>/operating_point.json``; prediction reads it back.  One GPU;
-image decoding stays on the host."""
+image decoding stays on the host.
+
+Every decision is taken in the model's frame (hr x hr).  ``--source-frame`` / ``--save-overlays`` add renderings of those
+decisions at each source image's own size: the map and the filtered mask resized bilinearly on the GPU (``ops.resize_f32``,
+equal to Pillow's mode-F resize bit for bit) and the heat map with the mask's outline drawn on the source
+(``ops.overlay_rgb``; DESIGN.md "Maps and masks at source size")."""
 from __future__ import annotations
 
 import argparse
@@ -60,6 +66,39 @@ def as_source(image) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+OVERLAY_ALPHA_DEFAULT = 0.6                                   # --overlay-alpha: the opacity of the hottest level
+OVERLAY_CONTOUR_DEFAULT = 1                                   # --overlay-contour: the outline's Chebyshev radius, 0 draws none
+OVERLAY_CONTOUR_RGB = (255, 255, 255)
+
+
+def heat_lut(alpha_max: int) -> np.ndarray:
+    """uint8 [256, 4]: (r, g, b, alpha) of every map level for ``ops.overlay_rgb``, from integer formulas alone.  Alpha is
+    ``(alpha_max * level + 127) // 255``: 0 at level 0, never decreasing, ``alpha_max`` (0..255) at level 255.  The colours are
+    a piecewise-linear ramp over four segments of 64 levels, ``t = 4 * (level % 64)``: blue (0, t, 255) -> cyan (0, 255, 255 - t)
+    -> green (t, 255, 0) -> yellow (255, 255 - t, 0), ending near red.  With ``overlay_scale`` the threshold sits at level 127,
+    the cyan -> green / green -> yellow boundary: what is below the threshold is blue to green and faint, what is above it
+    yellow to red."""
+    if not float(alpha_max).is_integer() or not 0 <= alpha_max <= 255:         # NaN and infinities are no integers
+        raise ValueError(f"heat_lut: alpha_max = {alpha_max!r}, must be an integer in 0..255")
+    level = np.arange(256, dtype=np.int64)
+    seg, t = level // 64, 4 * (level % 64)
+    zero, full = np.zeros_like(t), np.full_like(t, 255)
+    r = np.choose(seg, [zero, zero, t, full])
+    g = np.choose(seg, [t, full, full, 255 - t])
+    b = np.choose(seg, [full, 255 - t, zero, zero])
+    a = (int(alpha_max) * level + 127) // 255
+    return np.stack([r, g, b, a], axis=1).astype(np.uint8)
+
+
+def overlay_scale(threshold) -> np.float32:
+    """The factor that takes a map value to its level: ``float32(127.5 / threshold)``, so the threshold sits at the middle of
+    the ramp.  A threshold that is not finite or is <= 0 gives 255.0 (the maps lie in [0, 1]: the whole ramp)."""
+    t = float(threshold)
+    if not np.isfinite(t) or t <= 0.0:
+        return np.float32(255.0)
+    return np.float32(min(127.5 / t, float(np.finfo(np.float32).max)))      # finite for every threshold > 0
+
+
 def check_spec(spec: MapSpec) -> MapSpec:
     """A predict-time spec names its window: ``ws`` >= 1 or scales.  'ssim' with ``ws`` 0 means the labelled sweep's best_ws in
     the evaluator, and there are no labels here."""
@@ -71,11 +110,17 @@ def check_spec(spec: MapSpec) -> MapSpec:
 
 class Detector:
     """A model, a map spec and (once calibrated or given) a threshold.  ``hr_size``: the side the model's HR images have
-    (default ``opt.patch_size``); scale, ``n_colors`` and ``rgb_range`` come from ``opt``."""
+    (default ``opt.patch_size``); scale, ``n_colors`` and ``rgb_range`` come from ``opt``.  ``overlay_alpha`` (0..255, the
+    ``alpha_max`` of ``heat_lut``) and ``overlay_contour`` (0..4) shape the overlays ``predict(..., overlays=True)`` draws."""
 
     def __init__(self, opt, model, spec: MapSpec, threshold: Optional[float] = None, min_area: int = 1, self_ensemble: bool = False,
-                 hr_size: Optional[int] = None):
+                 hr_size: Optional[int] = None, overlay_alpha: int = int(OVERLAY_ALPHA_DEFAULT * 255 + 0.5),
+                 overlay_contour: int = OVERLAY_CONTOUR_DEFAULT):
         self.opt, self.model, self.self_ensemble = opt, model, bool(self_ensemble)
+        self._lut_host = heat_lut(overlay_alpha)
+        if not float(overlay_contour).is_integer() or not 0 <= overlay_contour <= 4:
+            raise ValueError(f"predict: overlay_contour = {overlay_contour!r}, must be an integer in 0..4")
+        self.overlay_contour, self._lut = int(overlay_contour), None
         self.hr_size = int(hr_size or opt.patch_size)
         self.scale = int(opt.scale[-1] if isinstance(opt.scale, (list, tuple)) else opt.scale)
         self.n_colors, self.rgb_range = int(opt.n_colors), float(opt.rgb_range)
@@ -91,9 +136,9 @@ class Detector:
         model.eval()                                          # H1 of the evaluator: deterministic scoring
 
     # ---------------------------------------------------------------------------------------------------------- the pair
-    def _pyramid(self, stack: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
-        """uint8 [n,H,W,C] sources of one shape -> (LR uint8 [n,h,w,C], HR uint8 [n,hr,hr,C]) on the GPU: two LANCZOS resizes."""
-        hr = ops.resize_u8(torch.from_numpy(stack).to(self.device), (self.hr_size, self.hr_size), 'lanczos')
+    def _pyramid(self, stack: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """uint8 [n,H,W,C] sources of one shape, on the GPU -> (LR uint8 [n,h,w,C], HR uint8 [n,hr,hr,C]): two LANCZOS resizes."""
+        hr = ops.resize_u8(stack, (self.hr_size, self.hr_size), 'lanczos')
         lr = self.hr_size // self.scale
         return ops.resize_u8(hr, (lr, lr), 'lanczos'), hr
 
@@ -104,6 +149,11 @@ class Detector:
         launch pair per source shape.  Gray sources resize one channel; with ``n_colors`` 1 their luma is the 256-entry float32
         table of ``luma_table`` (LR) and its truncation (HR); true colour with ``n_colors`` 1 takes ``data.set_channel`` on the
         host; ``n_colors`` 3 replicates gray."""
+        return self._prepare(images, False)[:2]
+
+    def _prepare(self, images: Sequence, keep_sources: bool):
+        """``prepare``, and with ``keep_sources`` the groups it worked in: [(indices into ``images``, their sources as one
+        uint8 [n,H,W,C] tensor on the GPU)], one entry per source shape - the upload the resize needed, kept."""
         sources = [as_source(im) for im in images]
         if not sources:
             raise ValueError("predict: no images")
@@ -115,10 +165,14 @@ class Detector:
         groups: dict = {}
         for i, a in enumerate(sources):
             groups.setdefault(a.shape, []).append(i)
+        kept = []
         for shape, idx in groups.items():
             stack = np.stack([sources[i] for i in idx])
             gray = len(shape) == 2
-            lr, hr = self._pyramid(stack[..., None] if gray else stack)
+            stack = torch.from_numpy(stack[..., None] if gray else stack).to(self.device)
+            if keep_sources:
+                kept.append((idx, stack))
+            lr, hr = self._pyramid(stack)
             if gray and C_ == 1:
                 if self._luma is None:
                     table = luma_table()
@@ -136,14 +190,14 @@ class Detector:
             where = torch.tensor(idx, device=self.device)
             lr_out[where] = lr_f.permute(0, 3, 1, 2)
             hr_out[where] = hr_u[:, :crop, :crop]             # the loader crops after set_channel
-        return lr_out, hr_out
+        return lr_out, hr_out, kept
 
     # ---------------------------------------------------------------------------------------------------------- the maps
-    def _maps(self, images: Sequence, with_max: bool):
-        lr, hr = self.prepare(images)
+    def _maps(self, images: Sequence, with_max: bool, keep_sources: bool = False):
+        lr, hr, kept = self._prepare(images, keep_sources)
         sr = super_resolve_dev(self.model, lr, hr.shape[1:3], self.rgb_range, self_ensemble=self.self_ensemble)
         maps, img_max = self.spec.make(sr, hr, with_max)
-        return sr, hr, maps, img_max
+        return sr, hr, maps, img_max, kept
 
     def calibrate(self, images: Sequence, fpr: float, level: str = 'pixel') -> Tuple[float, float]:
         """The threshold that the maps of the defect-free ``images`` give at false-positive rate ``fpr`` - on all their pixels
@@ -152,25 +206,59 @@ class Detector:
         if level not in ('pixel', 'image'):
             raise ValueError(f"predict: level = {level!r}, must be 'pixel' or 'image'")
         M.rank_for_rate(1, fpr)                               # the rate's own check, before any work
-        _, _, maps, img_max = self._maps(images, level == 'image')
+        _, _, maps, img_max, _ = self._maps(images, level == 'image')
         self.threshold, achieved = M.map_threshold(img_max if level == 'image' else maps, fpr)
         return self.threshold, achieved
 
-    def predict(self, images: Sequence) -> dict:
+    def predict(self, images: Sequence, source_frame: bool = False, overlays: bool = False) -> dict:
         """Per image (lists, in input order): ``ssim``, ``mse``, ``psnr`` of SR against HR (``metrics.score_pairs``; the SSIM at
         the spec's window, the mean over its scales where it has scales), ``map_max``, ``defect_pixels`` (pixels above the
         threshold that survive the area filter) and ``defective`` (any such pixel); ``maps`` float32 [n,H,W] and ``masks``
-        uint8 {0, 1} [n,H,W] stay on the GPU, as do ``sr`` and ``hr`` (uint8 [n,H,W,C]).  ValueError without a threshold."""
+        uint8 {0, 1} [n,H,W] stay on the GPU, as do ``sr`` and ``hr`` (uint8 [n,H,W,C]).  ValueError without a threshold.
+
+        All of that is in the model's frame and does not depend on the two flags.  ``source_frame`` adds renderings of it at
+        each image's own size, as lists in input order (the sizes differ), on the GPU: ``maps_src[i]`` float32 [H_i,W_i],
+        ``ops.resize_f32`` of ``maps[i]`` (bilinear, equal to Pillow's mode-F resize), and ``masks_src[i]`` uint8 {0, 1},
+        the same resize of the float mask at >= 0.5 - a component the area filter removed stays removed.  ``overlays`` implies
+        ``source_frame`` and adds ``overlays[i]`` uint8 [H_i,W_i,3]: ``ops.overlay_rgb`` of the raw source (``as_source``; true
+        colour stays colour) under ``maps_src[i]`` through ``heat_lut`` at ``overlay_scale(threshold)``, ``masks_src[i]``
+        outlined."""
         if self.threshold is None:
             raise ValueError("predict: no threshold (calibrate on defect-free images first, or give one)")
-        sr, hr, maps, img_max = self._maps(images, True)
+        source_frame = bool(source_frame or overlays)
+        sr, hr, maps, img_max, kept = self._maps(images, True, source_frame)
         sizes = list(self.spec.scales) or [self.spec.ws]
         ssim, mse, psnr = M.score_pairs(sr, hr, sizes)
         masks, img_pred, _ = M.operating_point(maps, self.threshold, None, self.min_area)
         pixels = [int(v) for v in img_pred.tolist()]
-        return dict(ssim=ssim.mean(1).tolist() if len(sizes) > 1 else ssim[:, 0].tolist(), mse=mse.tolist(), psnr=psnr.tolist(),
-                    map_max=[float(v) for v in img_max.tolist()], defective=[v > 0 for v in pixels], defect_pixels=pixels,
-                    threshold=self.threshold, maps=maps, masks=masks, sr=sr, hr=hr)
+        res = dict(ssim=ssim.mean(1).tolist() if len(sizes) > 1 else ssim[:, 0].tolist(), mse=mse.tolist(), psnr=psnr.tolist(),
+                   map_max=[float(v) for v in img_max.tolist()], defective=[v > 0 for v in pixels], defect_pixels=pixels,
+                   threshold=self.threshold, maps=maps, masks=masks, sr=sr, hr=hr)
+        if source_frame:
+            res.update(self._source_frame(kept, maps, masks, bool(overlays)))
+        return res
+
+    def _source_frame(self, kept, maps: torch.Tensor, masks: torch.Tensor, overlays: bool) -> dict:
+        """The model-frame ``maps`` and ``masks`` at the size of their sources, one resize (and one overlay) call per source
+        shape: ``kept`` is ``_prepare``'s [(indices, sources uint8 [n,H,W,C] on the GPU)]."""
+        n = maps.shape[0]
+        out = dict(maps_src=[None] * n, masks_src=[None] * n)
+        if overlays:
+            out['overlays'] = [None] * n
+            if self._lut is None:
+                self._lut = torch.from_numpy(self._lut_host).to(self.device)
+            scale = overlay_scale(self.threshold)
+        for idx, src in kept:
+            size = tuple(src.shape[1:3])
+            where = torch.tensor(idx, device=self.device)
+            m = ops.resize_f32(maps[where], size, 'bilinear')
+            k = (ops.resize_f32(masks[where].float(), size, 'bilinear') >= 0.5).to(torch.uint8)
+            o = ops.overlay_rgb(src, m, k, self._lut, scale, self.overlay_contour, OVERLAY_CONTOUR_RGB) if overlays else None
+            for j, i in enumerate(idx):
+                out['maps_src'][i], out['masks_src'][i] = m[j], k[j]
+                if overlays:
+                    out['overlays'][i] = o[j]
+        return out
 
 
 # -------------------------------------------------------------------------------------------------------------------- files
@@ -253,6 +341,29 @@ def spec_from_args(args, stored: Optional[MapSpec] = None, side: int = 0) -> Map
     return MapSpec(source=args.map_source or 'ssim', ws=ws, scales=scales, reduce=args.map_reduce or 'mean', sigma=args.map_sigma or 0.0)
 
 
+def _unit_float(text: str) -> float:
+    v = float(text)
+    if not 0.0 <= v <= 1.0:                                   # NaN too
+        raise argparse.ArgumentTypeError(f"{text} is not an opacity in [0, 1]")
+    return v
+
+
+def save_source_frame(res: dict, names: Sequence[str], kinds: Sequence[str], output_dir: str) -> None:
+    """What ``Detector.predict(..., source_frame=True)`` added, as PNGs at source size under ``output_dir``:
+    ``source_maps/{good,bad}/<name>.png`` (8-bit gray, the conversion of ``save_anomaly_maps``), ``source_masks/`` (0 / 255)
+    and, where there are overlays, ``overlays/`` (RGB)."""
+    from PIL import Image
+    folders = [('source_maps', [M.to_u8_hwc(m[None, None], rgb_range=1.0)[0, :, :, 0] for m in res['maps_src']]),
+               ('source_masks', [k * 255 for k in res['masks_src']])]
+    if 'overlays' in res:
+        folders.append(('overlays', res['overlays']))
+    for folder, images in folders:
+        for image, name, kind in zip(images, names, kinds):
+            d = Path(output_dir) / folder / kind
+            d.mkdir(parents=True, exist_ok=True)
+            Image.fromarray(image.cpu().numpy()).save(str(d / f"{name}.png"))
+
+
 def parse_predict_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description='Predict on raw images: calibrate a threshold on defect-free images, then flag and '
                                             'localise defects in new ones')
@@ -284,8 +395,22 @@ def parse_predict_args(argv=None) -> argparse.Namespace:
     p.add_argument('--save-anomaly-maps', action='store_true', default=False)
     p.add_argument('--save-masks', action='store_true', default=False)
     p.add_argument('--save-images', action='store_true', default=False, help="write the SR images too")
+    p.add_argument('--source-frame', action='store_true', default=False,
+                   help="write every map and mask at its source image's own size too: source_maps/ and source_masks/ "
+                        "(bilinear on the GPU; the decisions stay in the model's frame)")
+    p.add_argument('--save-overlays', action='store_true', default=False,
+                   help="write overlays/: the heat map and the mask's outline on every source image (implies --source-frame)")
+    p.add_argument('--overlay-alpha', type=_unit_float, default=None, metavar='A',
+                   help=f"opacity of the hottest level of the overlay, in [0, 1] (default {OVERLAY_ALPHA_DEFAULT})")
+    p.add_argument('--overlay-contour', type=int, default=None, choices=range(5), metavar='R',
+                   help=f"radius of the mask outline in pixels, 0..4, 0 draws none (default {OVERLAY_CONTOUR_DEFAULT})")
     p.add_argument('--output-dir', type=str, default='')
     args = p.parse_args(argv)
+    if (args.overlay_alpha is not None or args.overlay_contour is not None) and not args.save_overlays:
+        p.error("--overlay-alpha and --overlay-contour shape what --save-overlays writes: give it too")
+    args.source_frame = args.source_frame or args.save_overlays
+    args.overlay_alpha = OVERLAY_ALPHA_DEFAULT if args.overlay_alpha is None else args.overlay_alpha
+    args.overlay_contour = OVERLAY_CONTOUR_DEFAULT if args.overlay_contour is None else args.overlay_contour
     if args.ema and args.checkpoint:
         p.error("--ema and --checkpoint exclude each other (an explicit file is already a choice)")
     if not args.calibrate and not args.input:
@@ -337,7 +462,8 @@ def _run(args) -> dict:
     model = Model(opt, None, dual_model=(model_type == 'drn-l'))
     try:
         det = Detector(opt, model, spec, threshold=stored['threshold'] if stored else args.threshold, min_area=min_area,
-                       self_ensemble=self_ensemble, hr_size=int(resolution))
+                       self_ensemble=self_ensemble, hr_size=int(resolution), overlay_alpha=int(args.overlay_alpha * 255 + 0.5),
+                       overlay_contour=args.overlay_contour)
     except ValueError as e:
         raise SystemExit(str(e))
     out: dict = {}
@@ -349,7 +475,7 @@ def _run(args) -> dict:
               f"{len(calib_files)} defect-free images, achieved {achieved:.6f}), min_area={min_area}: {op_file}")
     if files:
         names = unique_names(files)
-        res = det.predict(files)
+        res = det.predict(files, source_frame=args.source_frame, overlays=args.save_overlays)
         out.update(res, names=names, files=[str(f) for f in files])
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, 'predictions.csv'), 'w', newline='') as fh:
@@ -363,6 +489,8 @@ def _run(args) -> dict:
             save_anomaly_maps(res['maps'], names, kinds, out_dir)
         if args.save_masks:
             save_masks(res['masks'], names, kinds, out_dir)
+        if args.source_frame:
+            save_source_frame(res, names, kinds, out_dir)
         if args.save_images:
             sr_host = res['sr'].cpu().numpy()
             for k, name in enumerate(names):

@@ -257,6 +257,41 @@ int srad_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds 
 int srad_resize_u8(const uint8_t* src, int n, int H, int W, int C, uint8_t* dst, int h, int w, const srad_resample_table* x_table,
                    const srad_resample_table* y_table, uint8_t* tmp, void* stream);
 
+/* ------------------------------------------------------------------ float32 resize, equal to PIL's mode-F Image.resize (DESIGN.md
+ * "Maps and masks at source size").  Pillow resamples float32 images with the taps in double, divided by their sum and not
+ * brought to fixed point; a pass is `ss = 0.0; for x < xmax: ss += (double)src[xmin + x] * k[x]; out = (float)ss` - sequential
+ * fp64 products and sums, no fused multiply-add - horizontal first, its result rounded to float32.  A table holds one axis:
+ * bounds [out_size][2] as above and the taps as double (coeffs [out_size][ksize], zero from xmax on), computed on the HOST by
+ * srad_resample_coeffs_f64; neither table function needs a GPU.  These functions take BILINEAR as well (the 8-bit ones refuse
+ * it).  srad_resize_f32 resizes maps src [n,H,W] to dst [n,h,w] through tmp [n,H,w]: a pass whose sizes agree is skipped (its
+ * table may be NULL, and tmp when only one pass runs), both skipped is a copy.  A table carries `bounds` on the host, which the
+ * call checks against the source before it launches, and the device copies the kernels read.  dst and tmp must overlap
+ * neither src nor each other.  One thread per output value, 64-bit offsets, stream-ordered, no allocation, no host
+ * synchronisation; one launch per pass, which takes n * H < 2^26 (horizontal), n * h < 2^24 (vertical) and w < 2^22.  NaN and
+ * infinities travel as in Pillow: through every output whose taps reach them. */
+#define SRAD_RESAMPLE_BILINEAR 2
+typedef struct {
+  int32_t in_size, out_size, ksize;
+  const int32_t* bounds;     /* host   [out_size][2] */
+  const int32_t* dev_bounds; /* device [out_size][2] */
+  const double* dev_coeffs;  /* device [out_size][ksize] */
+} srad_resample_table_f;
+int srad_resample_ksize_f64(int in_size, int out_size, int filter, int* ksize);
+int srad_resample_coeffs_f64(int in_size, int out_size, int filter, int32_t* bounds /* [out_size][2] */,
+                             double* coeffs /* [out_size][ksize] */);
+int srad_resize_f32(const float* src, int n, int H, int W, float* dst, int h, int w, const srad_resample_table_f* x_table,
+                    const srad_resample_table_f* y_table, float* tmp, void* stream);
+
+/* ------------------------------------------------------------------ overlay (DESIGN.md "Maps and masks at source size")
+ * out u8 [n,H,W,3] = the images src u8 [n,H,W,Cs] (Cs = 1: gray, replicated; Cs = 3) under a heat map and a mask outline.  Per
+ * pixel: q = maps * scale (one fp32 multiply), level = q >= 255 ? 255 : q > 0 ? (int)q : 0 (a NaN map value gives level 0),
+ * (r, g, b, a) = lut[level] (lut: DEVICE u8 [256][4]) and out_c = (src_c * (255 - a) + lut_c * a + 127) / 255 in integers.  A
+ * pixel whose mask (u8 [n,H,W]) is nonzero and which has, within Chebyshev distance contour_radius (0 .. 4), a pixel with mask 0
+ * or one outside the image takes the contour colour (each 0 .. 255) instead; radius 0 draws no contour.  out must overlap no
+ * input.  One thread per pixel, 64-bit offsets, stream-ordered, no atomics, no workspace. */
+int srad_overlay_rgb(const uint8_t* src, int n, int H, int W, int Cs, const float* maps, const uint8_t* masks, const uint8_t* lut,
+                     float scale, int contour_radius, int contour_r, int contour_g, int contour_b, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ scorer (src/evaluate.py:204-265) */
 /* `mul(255/range).clamp(0,255).byte()` TRUNCATING u8 conversion + NCHW->HWC (evaluate.py:214-215). */
 int srad_to_u8_hwc(const float* x, int B, int C, int H, int W, float rgb_range, uint8_t* out, void* stream);
