@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.grad_ref import leaf_state
 from tests.helpers import DRN_GAIN, rel_err
 from tests.test_gpu_drn import Opt
 
@@ -45,8 +46,7 @@ def test_drn_gradients_match_oracle_autograd(scale, n_colors, n_feats, B, H, W):
         from srad_amd import ops
         assert ops.conv_pool_rows(B, 64, 64, 2 * n_feats) > 0      # this case is here for the epilogue: it must be eligible
     # oracle: torch CPU autograd over the same state
-    sdt = {k: torch.from_numpy(np.asarray(v)).clone().requires_grad_(True) for k, v in sd.items()}
-    dts = [{k: torch.from_numpy(np.asarray(v)).clone().requires_grad_(True) for k, v in d.items()} for d in duals]
+    sdt, dts = leaf_state(sd), [leaf_state(d) for d in duals]
     sr_ref = R.drn_forward(sdt, torch.from_numpy(lrs[0]), cfg)
     sr2lr_ref = [R.dual_forward(dts[i], sr_ref[i - len(dts)], cfg) for i in range(len(dts))]
     loss_ref = R.drn_total_loss(sr_ref, [torch.from_numpy(a) for a in lrs], torch.from_numpy(hr), sr2lr_ref)

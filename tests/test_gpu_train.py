@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.grad_ref import leaf_state
 from tests.helpers import drct_case, rel_err
 from tests.test_gpu_drct import Opt
 
@@ -98,7 +99,7 @@ def test_training_forward_backward_with_droppath_matches_oracle(gray):
     gen = torch.Generator().manual_seed(1)
     keep = torch.floor(0.7 + torch.rand(2 * cfg.n_rdg * 5, B, generator=gen)) / 0.7        # independent per branch
     # oracle (torch CPU autograd)
-    sdt = {k: torch.from_numpy(np.asarray(v)).clone().requires_grad_(np.asarray(v).dtype == np.float32) for k, v in sd.items()}
+    sdt = leaf_state(sd)
     keeps = [[(keep[2 * (i * 5 + k)], keep[2 * (i * 5 + k) + 1]) for k in range(5)] for i in range(cfg.n_rdg)]
     xr = torch.from_numpy(x).requires_grad_(True)
     ref = R.drct_forward(sdt, xr, cfg, keeps=keeps)
@@ -141,7 +142,7 @@ def test_training_other_window_sizes_matches_oracle_autograd(ws, img, up, B, H, 
     hr = S.synth_image("trws/hr", (B, 1, H * up, W * up), seed=6)
     gen = torch.Generator().manual_seed(2)
     keep = torch.floor(0.8 + torch.rand(2 * cfg.n_rdg * 5, B, generator=gen)) / 0.8
-    sdt = {k: torch.from_numpy(np.asarray(v)).clone().requires_grad_(np.asarray(v).dtype == np.float32) for k, v in sd.items()}
+    sdt = leaf_state(sd)
     keeps = [[(keep[2 * (i * 5 + k)], keep[2 * (i * 5 + k) + 1]) for k in range(5)] for i in range(cfg.n_rdg)]
     xr = torch.from_numpy(x).requires_grad_(True)
     ref = R.drct_forward(sdt, xr, cfg, keeps=keeps)

@@ -6,11 +6,11 @@ tiled attention backward.
  * every other window size above 16 is still refused."""
 import types
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.grad_ref import leaf_state
 from tests.helpers import rel_err
 from tests.test_gpu_drct import Opt
 from tests.test_gpu_train import build_train
@@ -45,7 +45,7 @@ def _case(ws):
         keep = torch.floor(0.8 + torch.rand(2 * cfg.n_rdg * 5, B, generator=gen)) / 0.8
         if float(keep.min()) > 0:
             keep[3, 0] = 0.0                                     # B = 1: make sure one branch IS dropped
-        sdt = {k: torch.from_numpy(np.asarray(v)).clone().requires_grad_(np.asarray(v).dtype == np.float32) for k, v in sd.items()}
+        sdt = leaf_state(sd)
         keeps = [[(keep[2 * (i * 5 + k)], keep[2 * (i * 5 + k) + 1]) for k in range(5)] for i in range(cfg.n_rdg)]
         xr = torch.from_numpy(x).requires_grad_(True)
         ref = R.drct_forward(sdt, xr, cfg, keeps=keeps)
