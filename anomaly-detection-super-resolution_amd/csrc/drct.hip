@@ -168,7 +168,26 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
     }
     float* t = cur; cur = nxt; nxt = t;
   }
-  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s);
+  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s, h->fold_in_graph);
+}
+
+// Does this forward end in the folded launch?  Inference handles only: one bound for training gets its weights through
+// srad_drct_sync_params, which does not pass the fold's sources on.
+bool drct_fold_active(const srad_drct* h, int H, int W) {
+  return h->fold_ok && !h->ts.tarena && !h->ts.ready && H >= 2 && W >= 2 && !srad_path_override(SRAD_PATH_TAIL_CHAIN);
+}
+
+// the fold's sources among the parameters: byte offset in the fold's region, or -1
+long long drct_fold_source(const srad_drct* h, const char* name) {
+  const TailFoldLayout& l = h->fold;
+  const std::string n(name);
+  if (n == "upsample.0.weight") return (long long)l.w_up0;
+  if (n == "upsample.0.bias") return (long long)l.b_up0;
+  if (n == "upsample.2.weight" && l.scale == 4) return (long long)l.w_up1;
+  if (n == "upsample.2.bias" && l.scale == 4) return (long long)l.b_up1;
+  if (n == "conv_last.weight") return (long long)l.w_last;
+  if (n == "conv_last.bias") return (long long)l.b_last;
+  return -1;
 }
 
 }  // namespace
@@ -198,7 +217,7 @@ int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const Drc
 }
 
 int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
-              hipStream_t s) {
+              hipStream_t s, bool fold) {
   const srad_drct_config& c = h->cfg;
   const int prec = c.precision, T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc, F = c.num_feat;
   // norm                                              (drct.py:881)
@@ -217,6 +236,10 @@ int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const
     p.act = SRAD_ACT_LRELU; p.slope = 0.01f;
     SRAD_TRY(srad_launch_gemm(prec, p, s));
   }
+  float mean3[3];
+  drct_mean(c, mean3);
+  // Upsample, conv_last and x / img_range + mean as one 5 x 5 convolution of c2 (kernels_tail_fold.hip; drct.py:694-713, 895-897)
+  if (fold) return srad_launch_tail_fold(h->fold, h->pt.arena + h->fold_off, w.c2, B, H, W, y, 1.0f / c.img_range, mean3, s);
   // Upsample: conv 64->256 + PixelShuffle(2) per stage (drct.py:694-713)
   const float* src = w.c2;
   int hh = H, ww = W;
@@ -235,8 +258,6 @@ int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const
     SRAD_TRY(srad_launch_gemm(prec, p, s));
   }
   // x / img_range + mean, NHWC -> NCHW                (drct.py:897)
-  float mean3[3];
-  drct_mean(c, mean3);
   return srad_launch_nhwc_to_nchw(w.outn, ld_outn, y, B, c.in_chans, hh, ww, mean3, 1.0f / c.img_range, s);
 }
 
@@ -328,6 +349,11 @@ int srad_drct_create(const srad_drct_config* cfg, srad_drct_t** out) {
   for (int s = cfg->upscale; s > 1; s >>= 1) ++stages;
   for (int j = 0; j < stages; ++j) h->up.push_back(h->pt.add_layer("upsample." + std::to_string(2 * j), 4 * F, F, 9, true));
   h->conv_last = h->pt.add_layer("conv_last", C, F, 9, true);
+  h->fold_ok = srad_tail_fold_supported(cfg->precision, F, C, cfg->upscale);
+  if (h->fold_ok) {
+    h->fold = tf_layout(F, C, cfg->upscale);
+    h->fold_off = srad_align_up(h->pt.bytes, 256);
+  }
   *out = h;
   return SRAD_OK;
 }
@@ -338,18 +364,22 @@ void srad_drct_destroy(srad_drct_t* h) {
   delete h;
 }
 
+// the parameter table's packs, then the folded output end's region (sources, fold, pack, bias table) where the model has one
+static size_t drct_arena_need(const srad_drct_t* h) { return h->fold_ok ? h->fold_off + h->fold.bytes : h->pt.bytes; }
+
 int srad_drct_arena_bytes(const srad_drct_t* h, size_t* bytes) {
   SRAD_REQUIRE(h && bytes, "drct_arena_bytes: null argument");
-  *bytes = h->pt.bytes;
+  *bytes = drct_arena_need(h);
   return SRAD_OK;
 }
 
 int srad_drct_bind_arena(srad_drct_t* h, void* arena, size_t bytes) {
   SRAD_REQUIRE(h && arena, "drct_bind_arena: null argument");
-  SRAD_REQUIRE(bytes >= h->pt.bytes, "drct_bind_arena: %zu bytes given, %zu needed", bytes, h->pt.bytes);
+  SRAD_REQUIRE(bytes >= drct_arena_need(h), "drct_bind_arena: %zu bytes given, %zu needed", bytes, drct_arena_need(h));
   SRAD_REQUIRE(((uintptr_t)arena & 255) == 0, "drct_bind_arena: arena must be 256-byte aligned");
   h->pt.arena = reinterpret_cast<char*>(arena);
   h->pt.arena_bytes = bytes;
+  h->fold_stale = true;
   h->gc.reset();
   return SRAD_OK;
 }
@@ -365,7 +395,14 @@ int srad_drct_param_info(const srad_drct_t* h, int idx, const char** name, int64
 
 int srad_drct_set_param(srad_drct_t* h, const char* name, const float* dev_src, int64_t numel, void* stream) {
   SRAD_REQUIRE(h && name && dev_src, "drct_set_param: null argument");
-  return h->pt.set(name, dev_src, numel, reinterpret_cast<hipStream_t>(stream));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  SRAD_TRY(h->pt.set(name, dev_src, numel, s));
+  const long long off = h->fold_ok ? drct_fold_source(h, name) : -1;
+  if (off >= 0) {      // a source of the folded output end: keep its fp32 copy, rebuild before the next forward
+    SRAD_CHECK_HIP(hipMemcpyAsync(h->pt.arena + h->fold_off + off, dev_src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
+    h->fold_stale = true;
+  }
+  return SRAD_OK;
 }
 
 static int drct_check_shape(const srad_drct_t* h, int B, int H, int W) {
@@ -392,6 +429,18 @@ int srad_drct_forward(srad_drct_t* h, const float* x, int B, int H, int W, float
   const DrctWs w = plan_ws(h, B, H, W, workspace, workspace_bytes);
   SRAD_REQUIRE(w.bytes <= workspace_bytes, "drct_forward: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // the folded output end: decided per call (a recorded graph holds one of the two ends), rebuilt here - on the stream, ahead
+  // of the forward, never inside a capture and never as a node of the replayed graph - when one of its sources has changed
+  const bool fold = drct_fold_active(h, H, W);
+  if (fold != h->fold_in_graph) { h->gc.reset(); h->fold_in_graph = fold; }
+  if (fold && h->fold_stale) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (s) SRAD_CHECK_HIP(hipStreamIsCapturing(s, &st));
+    if (st != hipStreamCaptureStatusNone)
+      return srad_set_error(SRAD_ERR_STATE, "drct_forward: the folded output end is stale and the stream is capturing: run one forward outside the capture first");
+    SRAD_TRY(srad_launch_tail_fold_build(h->fold, h->pt.arena + h->fold_off, s));
+    h->fold_stale = false;
+  }
   return srad_run_with_graph(h->gc, h->cfg.use_graph != 0, x, y, workspace, B, H, W, s,
                              [&](hipStream_t st) { return forward_body(h, x, B, H, W, y, w, st); });
 }

@@ -2,6 +2,7 @@
 // (drct_train.hip), and the pieces of the forward both run: stem, tail, fused-block parameters (defined in drct.hip).
 #pragma once
 #include "train_common.h"
+#include "tail_fold.h"
 #include "../../include/srad.h"
 
 struct SwinW {
@@ -22,6 +23,12 @@ struct srad_drct {
   int dmax, hmax, qkvmax;         // widest block dim / hidden / head-padded qkv row
   std::vector<char> saved_h;      // per Swin block, what the last training forward saved as bf16: 1 q | k | v, 2 the fc1 pre-activation (plan_block)
   bool fuse_mlp = true;           // bf16: second half of each Swin block as one launch (kernels_fused.hip)
+  // The folded output end (kernels_tail_fold.hip): its region follows the parameter table's in the weight arena and is no
+  // entry of the table.  srad_drct_set_param copies the fp32 sources in and marks the fold stale; srad_drct_forward rebuilds a
+  // stale fold before it runs or replays anything.  A handle bound for training keeps the chain of launches.
+  bool fold_ok = false, fold_stale = true, fold_in_graph = false;
+  TailFoldLayout fold{};
+  size_t fold_off = 0;
   GraphCache gc;
   TrainState ts;                  // training (drct_train.hip)
   BwdStreams bwd;                 // the backward's side stream for the weight gradients, and its events
@@ -46,8 +53,9 @@ struct DrctStemTail {
 // (x - mean) * img_range -> conv_first -> patch_embed.norm into dense0[:, :embed]            (drct.py:887-892, 873)
 int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s);
 // norm -> conv_after_body + x -> conv_before_upsample -> Upsample -> conv_last (into outn, row stride ld_outn) -> y   (drct.py:881, 893-897)
+// fold: everything after conv_before_upsample as the one folded launch (the caller has checked drct_fold_active and freshness)
 int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
-              hipStream_t s);
+              hipStream_t s, bool fold = false);
 // The fields both forwards set for Swin block `sw` of an RDG, block k of its five: weights, biases, LayerNorm, geometry, and
 // (mlp_block) the adjust conv's residual and output in the dense buffers cur / nxt
 QkvAttnParams drct_qkv_attn_params(const srad_drct* h, const SwinW& sw, const float* cur, int B, int H, int W);

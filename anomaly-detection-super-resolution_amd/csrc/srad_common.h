@@ -254,6 +254,15 @@ int srad_launch_conv_thin(const GemmParams& p, hipStream_t stream);
 // DRN's tail convolutions (40 / 80 -> <= 4 channels): MFMA with both operands from registers, no LDS (kernels_thin.hip)
 bool srad_conv_tail_supported(int prec, const GemmParams& p);
 int srad_launch_conv_tail(const GemmParams& p, hipStream_t stream);
+// DRCT's output end folded into one 5 x 5 convolution at LR resolution (kernels_tail_fold.hip; tail_fold.h has the algebra and the
+// layout of a fold's region).  bf16, 64 features, scale 2 | 4, gray | RGB.  build: from the fp32 sources already in the region
+// (four launches; once per weight load, never inside a capture).  The kernel reads c2 [B*H*W][64] and writes y [B][C][sH][sW]
+// = fold(c2) * inv_range + mean; H, W >= 2.
+struct TailFoldLayout;
+bool srad_tail_fold_supported(int prec, int F, int C, int scale);
+int srad_launch_tail_fold_build(const TailFoldLayout& l, char* base, hipStream_t stream);
+int srad_launch_tail_fold(const TailFoldLayout& l, const char* base, const float* X, int B, int H, int W, float* Y, float inv_range,
+                          const float mean3[3], hipStream_t stream);
 
 // Packed weight geometry shared by the packer and the GEMM
 static inline int srad_cp(int cin) { return srad_round_up(cin, 32); }
@@ -590,7 +599,7 @@ int srad_launch_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int C, in
 enum {
   SRAD_K_GEMM_BN64 = 0, SRAD_K_GEMM_BN32, SRAD_K_GEMM_BN16, SRAD_K_ATTN, SRAD_K_LAYERNORM,
   SRAD_K_LAYOUT, SRAD_K_PACK, SRAD_K_SCORE, SRAD_K_MISC, SRAD_K_MLP_BLOCK, SRAD_K_QKV_ATTN,
-  SRAD_K_WGRAD, SRAD_K_ATTN_BWD, SRAD_K_LN_BWD, SRAD_K_OPTIM, SRAD_K_WGRAD_REDUCE, SRAD_K_MLP_BWD, SRAD_K_LN_QKV, SRAD_K_CONV80, SRAD_K_ENSEMBLE, SRAD_K_SWIN_BLOCK, SRAD_K_RESIZE, SRAD_K_OVERLAY, SRAD_K_COUNT
+  SRAD_K_WGRAD, SRAD_K_ATTN_BWD, SRAD_K_LN_BWD, SRAD_K_OPTIM, SRAD_K_WGRAD_REDUCE, SRAD_K_MLP_BWD, SRAD_K_LN_QKV, SRAD_K_CONV80, SRAD_K_ENSEMBLE, SRAD_K_SWIN_BLOCK, SRAD_K_RESIZE, SRAD_K_OVERLAY, SRAD_K_TAIL_FOLD, SRAD_K_COUNT
 };
 struct SradProfScope {
   hipStream_t s; int active;

@@ -20,7 +20,7 @@ def _need_cuda(*ts):
 # include/srad.h SRAD_PATH_*: the reference paths a test can force instead of the one shape and precision pick
 PATHS = {"unfused_blocks": 0, "qkv_via_gemm": 1, "attn_f32_in": 2, "upconv_one_gemm": 3}
 # ... and its launch-plan overrides (ids from SRAD_PATH_PLAN_FIRST): the launches a default path is compared against
-PLAN_PATHS = {"block_two_launches": 16}
+PLAN_PATHS = {"block_two_launches": 16, "tail_chain": 17}
 
 
 @contextlib.contextmanager
@@ -28,7 +28,8 @@ def path_override(**paths: bool):
     """Force reference paths inside the block, e.g. ``with ops.path_override(unfused_blocks=True):``, and restore the previous
     settings on exit.  unfused_blocks is read by the DRCT engine when it is created (forward) and at every backward;
     block_two_launches (a Swin block as qkv_attn + mlp_block where the one-launch kernel would run) whenever a forward
-    records its launches, i.e. before the first forward of a shape."""
+    records its launches, i.e. before the first forward of a shape; tail_chain (the Upsample convolutions, conv_last and the
+    layout change as their own launches where the folded output end would run) at every forward."""
     lib = L.lib()
     ids = {name: PATHS[name] if name in PATHS else PLAN_PATHS[name] for name in paths}
     before = {name: lib.srad_get_path_override(i) for name, i in ids.items()}
@@ -111,6 +112,48 @@ def layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor) -> torch.Tensor
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     L.check(L.lib().srad_op_layernorm(L.dptr(x), x.stride(0), L.dptr(y), y.stride(0), x.shape[0], x.shape[1],
                                       L.dptr(g), L.dptr(b), L.current_stream_ptr()), "op_layernorm")
+    return y
+
+
+def tail_fold_build(up_weights, up_biases, last_w: torch.Tensor, last_b: torch.Tensor) -> dict:
+    """The folded DRCT output end built on the device (C ABI ``srad_op_tail_fold_build``) from the Upsample convolutions
+    (one for x2, two for x4: ``[4F, F, 3, 3]`` / ``[4F]``) and conv_last (``[C, F, 3, 3]`` / ``[C]``).  Returns the region and
+    views into it: ``wf`` fp32 [9, N, 25, F], ``pack`` bf16 [9, NT, 25, F // 32, 64, 8], ``bias`` fp32 [9, 16 NT]."""
+    _need_cuda(last_w, last_b, *up_weights, *up_biases)
+    scale, Cc, F = 2 ** len(up_weights), last_w.shape[0], last_w.shape[1]
+    offs = [C.c_size_t() for _ in range(4)]
+    L.check(L.lib().srad_op_tail_fold_layout(F, Cc, scale, *[C.byref(o) for o in offs]), "op_tail_fold_layout")
+    wf_off, pack_off, bias_off, nbytes = [o.value for o in offs]
+    keep, ptr, _ = L.ws_buffer(nbytes, last_w.device)
+    srcs = [t.detach().float().contiguous() for t in (up_weights[0], up_biases[0])]
+    srcs += [t.detach().float().contiguous() for t in (up_weights[1], up_biases[1])] if scale == 4 else [None, None]
+    srcs += [last_w.detach().float().contiguous(), last_b.detach().float().contiguous()]
+    L.check(L.lib().srad_op_tail_fold_build(F, Cc, scale, *[L.dptr(t) for t in srcs], ptr, C.c_size_t(nbytes), L.current_stream_ptr()),
+            "op_tail_fold_build")
+    base = ptr.value - keep.data_ptr()
+    N, NT = scale * scale * Cc, (scale * scale * Cc + 15) // 16
+
+    def view(off, count, dtype, shape):
+        return keep[base + off: base + off + count * dtype.itemsize].view(dtype).view(shape)
+    return dict(region=keep, ptr=ptr, scale=scale, C=Cc, F=F,
+                wf=view(wf_off, 9 * N * 25 * F, torch.float32, (9, N, 25, F)),
+                pack=view(pack_off, 9 * NT * 25 * F * 16, torch.bfloat16, (9, NT, 25, F // 32, 64, 8)),
+                bias=view(bias_off, 9 * NT * 16, torch.float32, (9, NT * 16)))
+
+
+def tail_fold(c2: torch.Tensor, up_weights, up_biases, last_w: torch.Tensor, last_b: torch.Tensor, B: int, H: int, W: int,
+              img_range: float = 1.0, mean=(0.0, 0.0, 0.0), fold: Optional[dict] = None) -> torch.Tensor:
+    """DRCT's output end as one launch: c2 [B*H*W, 64] (conv_before_upsample's output, NHWC rows) -> y [B, C, sH, sW] =
+    conv_last(PixelShuffle(up(...))) / img_range + mean (C ABI ``srad_op_tail_fold``).  Builds the fold unless one is given."""
+    _need_cuda(c2)
+    assert c2.dim() == 2 and c2.shape == (B * H * W, 64) and c2.is_contiguous() and c2.dtype == torch.float32
+    if fold is None:
+        fold = tail_fold_build(up_weights, up_biases, last_w, last_b)
+    s, Cc = fold["scale"], fold["C"]
+    mean = list(mean) + [0.0] * (3 - len(mean))
+    y = torch.empty(B, Cc, s * H, s * W, dtype=torch.float32, device=c2.device)
+    L.check(L.lib().srad_op_tail_fold(L.dptr(c2), B, H, W, Cc, s, fold["ptr"], img_range, mean[0], mean[1], mean[2], L.dptr(y),
+                                      L.current_stream_ptr()), "op_tail_fold")
     return y
 
 

@@ -524,6 +524,23 @@ int srad_op_swin_block(int precision, const float* x, int ldx, int B, int H, int
                        float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
                        size_t scratch_bytes, void* stream);
 
+/* DRCT's output end folded into one launch.  Everything after conv_before_upsample's LeakyReLU - the Upsample
+ * convolutions with their PixelShuffles, conv_last, then / img_range + mean (src/drct.py:694-713, 842-847, 894-897) - is linear:
+ * the s x s HR pixels of an LR pixel are one 5 x 5 convolution of c2, whose weights and bias depend on whether the pixel lies in
+ * the first, an interior or the last row / column (nine classes; the inner convolutions pad their own, finer inputs).
+ *   srad_op_tail_fold_layout: byte offsets, in a fold's region, of the fp32 fold wf [9][N][25][F] (N = s s C, output
+ *       (c s + py) s + px, tap (dy + 2) 5 + dx + 2), of its bf16 pack [9][NT][25][F / 32][64][8] (NT = ceil(N / 16); lane 16 fq + fr
+ *       holds row 16 nt + fr, channels 32 j + 8 fq .. + 7; rows >= N zero) and of the fp32 bias table [9][16 NT], and the region's size
+ *   srad_op_tail_fold_build : builds a fold in `scratch` (256-byte aligned, >= that size) from upsample.0 (w_up0 [4F][F][3][3],
+ *       b_up0), upsample.2 (w_up1, b_up1; scale 4 only, else NULL) and conv_last (w_last [C][F][3][3], b_last), device fp32
+ *   srad_op_tail_fold       : y [B][C][sH][sW] = fold(c2) / img_range + mean_c from c2 [B*H*W][64] fp32 (rounded to bf16 once, fp32
+ *       accumulation); F = 64, scale 2 | 4, C 1 | 3, H, W >= 2 */
+int srad_op_tail_fold_layout(int F, int C, int scale, size_t* wf_off, size_t* pack_off, size_t* bias_off, size_t* bytes);
+int srad_op_tail_fold_build(int F, int C, int scale, const float* w_up0, const float* b_up0, const float* w_up1, const float* b_up1,
+                            const float* w_last, const float* b_last, void* scratch, size_t scratch_bytes, void* stream);
+int srad_op_tail_fold(const float* c2, int B, int H, int W, int C, int scale, const void* fold, float img_range, float mean0, float mean1,
+                      float mean2, float* y, void* stream);
+
 /* The two kernels of BASELINE config C5's attention (bf16, 64 x 64 windows = 4096-token windows; src/main.py:286), each on its own:
  *   srad_op_ln_qkv              norm1 + attn.qkv (src/drct.py:477, 278) -> qkv_h [M][3][heads][hdp] bf16, the attention's MFMA
  *                               operands: q times qscale (= head_dim^-0.5 log2 e, srad_op_window_attn_qscale), padding columns 0,
@@ -685,8 +702,10 @@ enum { SRAD_PATH_UNFUSED_BLOCKS = 0, SRAD_PATH_QKV_VIA_GEMM = 1, SRAD_PATH_ATTN_
        SRAD_PATH_COUNT = 4 };
 /* Launch-plan overrides: the same two calls, ids from SRAD_PATH_PLAN_FIRST (the ids between SRAD_PATH_COUNT and it stay unknown).
  *   SRAD_PATH_BLOCK_TWO_LAUNCHES  DRCT forward: a Swin block as the qkv_attn + mlp_block pair where the one-launch
- *                                 swin_block kernel would be chosen (read at every forward that records launches) */
-enum { SRAD_PATH_PLAN_FIRST = 16, SRAD_PATH_BLOCK_TWO_LAUNCHES = 16, SRAD_PATH_END = 17 };
+ *                                 swin_block kernel would be chosen (read at every forward that records launches)
+ *   SRAD_PATH_TAIL_CHAIN          DRCT bf16 forward: the Upsample convolutions, conv_last and the layout change as their own
+ *                                 launches where the folded output end (srad_op_tail_fold) would run (read at every forward) */
+enum { SRAD_PATH_PLAN_FIRST = 16, SRAD_PATH_BLOCK_TWO_LAUNCHES = 16, SRAD_PATH_TAIL_CHAIN = 17, SRAD_PATH_END = 18 };
 int srad_set_path_override(int path, int on);
 int srad_get_path_override(int path);
 /* Per-kernel-class device timing with HIP events on the launch stream (bench.py's roofline numbers). */
