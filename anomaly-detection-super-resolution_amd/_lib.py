@@ -174,6 +174,8 @@ _SIG = {
     "srad_select_kth": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
     "srad_operating_point_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "srad_operating_point": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "srad_region_table_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "srad_region_table": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "srad_smooth_maps_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "srad_smooth_maps": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "srad_l1_workspace_bytes": (C.c_int, [C.POINTER(C.c_size_t)]),

@@ -93,11 +93,6 @@ __global__ __launch_bounds__(256) void select_hist_kernel(const float* __restric
   if (nan) atomicAdd(&st->n_nan, nan);
 }
 
-__device__ __forceinline__ float key_to_float(uint32_t key) {
-  if (key == kNanKey) return NAN;
-  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
-
 // One block: the digit whose bin holds the rank.  Thread t sums bins t * per .. t * per + per - 1 (per = 8 or 4).
 __global__ __launch_bounds__(256) void select_pick_kernel(const uint32_t* __restrict__ hist, SelState* __restrict__ st, int pass,
                                                           uint32_t k, float* __restrict__ value_out,

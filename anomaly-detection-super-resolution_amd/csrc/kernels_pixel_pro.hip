@@ -36,23 +36,7 @@
 namespace {
 
 // ---------------------------------------------------------------- 1. regions
-constexpr int kLabT = 32, kLabPx = kLabT * kLabT, kLabPer = kLabPx / 256;   // 32 x 32 tile, 4 pixels per thread
-constexpr uint32_t kNoParent = 0xFFFFFFFFu;                                  // ok pixel; no index reaches it (n < 2^31)
-
-struct LabGeom {
-  int H, W, tiles_x, tiles_y;
-};
-
-// block -> (first pixel of its image, tile origin)
-__device__ __forceinline__ void lab_tile(const LabGeom& g, int64_t& base, int& y0, int& x0) {
-  int b = blockIdx.x;
-  const int tx = b % g.tiles_x;
-  b /= g.tiles_x;
-  const int ty = b % g.tiles_y;
-  base = (int64_t)(b / g.tiles_y) * g.H * g.W;
-  y0 = ty * kLabT;
-  x0 = tx * kLabT;
-}
+constexpr int kLabPer = kLabPx / 256;                                       // 4 pixels per thread (kLabT, LabGeom: pixel_pro.h)
 
 __device__ __forceinline__ int lds_find(int* lab, int x) {
   int p = __hip_atomic_load(&lab[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -319,27 +303,35 @@ __global__ __launch_bounds__(256) void pro_finish_kernel(const ProTile* __restri
 }
 
 // ---------------------------------------------------------------- host side
-LabGeom lab_geom(int H, int W) { return LabGeom{H, W, (W + kLabT - 1) / kLabT, (H + kLabT - 1) / kLabT}; }
-
 // Stages 1a - 1d.  parent: n u32 of workspace; size: n u32 (the output, or workspace when `keys` is given).
 int launch_regions(const uint8_t* masks, int n_img, int H, int W, int64_t n, uint32_t* parent, uint32_t* size,
                    unsigned long long* counts, const float* scores, uint64_t* keys, hipStream_t s) {
-  const LabGeom g = lab_geom(H, W);
-  const unsigned n_tiles = (unsigned)((int64_t)n_img * g.tiles_x * g.tiles_y);
   const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
   // masks read 4 times (local, merge borders, flatten, sizes); parent written, read twice, rewritten in part; sizes written,
   // read, written (or the 8-byte keys written, and the scores read)
   SradProfScope prof(s, SRAD_K_SCORE, 0.0, 4.0 * n + 16.0 * n + (keys ? 16.0 * n : 8.0 * n));
   SRAD_CHECK_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), s));
-  hipLaunchKernelGGL(mask_local_kernel, dim3(n_tiles), dim3(256), 0, s, masks, g, parent, size);
-  hipLaunchKernelGGL(mask_merge_kernel, dim3(n_tiles), dim3(64), 0, s, masks, g, parent);
-  hipLaunchKernelGGL(mask_flatten_kernel, dim3(grid), dim3(256), 0, s, masks, parent, size, n);
+  SRAD_TRY(srad_label_roots(masks, n_img, H, W, parent, size, nullptr, s));
   hipLaunchKernelGGL(mask_sizes_kernel, dim3(std::min(grid, 1024u)), dim3(256), 0, s, masks, parent, size, n, size, scores, keys,
                      counts);
   return SRAD_OK;
 }
 
 }  // namespace
+
+// Stages 1a - 1c (declared in pixel_pro.h).
+int srad_label_roots(const uint8_t* masks, int n_img, int H, int W, uint32_t* parent, uint32_t* size, uint32_t* tile_root,
+                     hipStream_t s) {
+  const int64_t n = (int64_t)n_img * H * W;
+  const LabGeom g = lab_geom(H, W);
+  const unsigned n_tiles = (unsigned)((int64_t)n_img * g.tiles_x * g.tiles_y);
+  const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(mask_local_kernel, dim3(n_tiles), dim3(256), 0, s, masks, g, parent, size);
+  if (tile_root) SRAD_CHECK_HIP(hipMemcpyAsync(tile_root, parent, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(mask_merge_kernel, dim3(n_tiles), dim3(64), 0, s, masks, g, parent);
+  hipLaunchKernelGGL(mask_flatten_kernel, dim3(grid), dim3(256), 0, s, masks, parent, size, n);
+  return SRAD_OK;
+}
 
 extern "C" {
 

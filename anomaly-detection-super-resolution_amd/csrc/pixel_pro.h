@@ -1,5 +1,6 @@
-// pixel_pro.h - the fixed-point per-region overlap sum shared by AU-PRO (kernels_pixel_pro.hip) and the operating point
-// (kernels_operating_point.hip): a pixel of a region of z pixels adds floor(2^64 / z) to a 128-bit numerator.
+// pixel_pro.h - what the region code shares.  The fixed-point per-region overlap sum of AU-PRO (kernels_pixel_pro.hip) and the
+// operating point (kernels_operating_point.hip): a pixel of a region of z pixels adds floor(2^64 / z) to a 128-bit numerator.
+// The labelling's tile geometry and its entry for other files (kernels_region_table.hip): srad_label_roots.
 #pragma once
 #include "engine.h"
 #include <stdint.h>
@@ -33,6 +34,26 @@ __device__ __forceinline__ void pro_add(Pref& p, uint64_t key) {
   }
 }
 
+// The labelling's geometry: one 32 x 32 tile per block.
+constexpr int kLabT = 32, kLabPx = kLabT * kLabT;
+constexpr uint32_t kNoParent = 0xFFFFFFFFu;                                  // ok pixel; no index reaches it (n < 2^31)
+
+struct LabGeom {
+  int H, W, tiles_x, tiles_y;
+};
+inline LabGeom lab_geom(int H, int W) { return LabGeom{H, W, (W + kLabT - 1) / kLabT, (H + kLabT - 1) / kLabT}; }
+
+// block -> (first pixel of its image, tile origin)
+__device__ __forceinline__ void lab_tile(const LabGeom& g, int64_t& base, int& y0, int& x0) {
+  int b = blockIdx.x;
+  const int tx = b % g.tiles_x;
+  b /= g.tiles_x;
+  const int ty = b % g.tiles_y;
+  base = (int64_t)(b / g.tiles_y) * g.H * g.W;
+  y0 = ty * kLabT;
+  x0 = tx * kLabT;
+}
+
 // n = n_img x H x W of an [n_img, H, W] stack, refused outside [1, 2^31) (a pixel index is a u32 with 0xFFFFFFFF to spare)
 inline int check_shape(int n_img, int H, int W, const char* who, int64_t& n) {
   SRAD_REQUIRE(n_img >= 1 && H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX && (int64_t)H * W * n_img <= INT32_MAX,
@@ -42,3 +63,11 @@ inline int check_shape(int n_img, int H, int W, const char* who, int64_t& n) {
 }
 
 }  // namespace
+
+// The labelling of kernels_pixel_pro.hip, stages 1a - 1c, on stream s: parent[i] = the root (its component's smallest linear
+// index over the whole stack) of every pixel with masks[i] != 0, kNoParent elsewhere.  parent, size: n u32 each; size is
+// scratch afterwards except at a root, where it holds the component's pixel count.  tile_root (n u32, or NULL): a copy of parent
+// as stage 1a left it - each pixel's root within its own 32 x 32 tile (lab_tile), a pixel of that tile.  The shape is the
+// caller's to check (check_shape).
+int srad_label_roots(const uint8_t* masks, int n_img, int H, int W, uint32_t* parent, uint32_t* size, uint32_t* tile_root,
+                     hipStream_t s);

@@ -30,6 +30,12 @@ __device__ __forceinline__ uint32_t desc_key(float f) {
   return k == kNanKey ? kNanKey : ~k;
 }
 
+// order_key back to its float (of the two zeros, +0.0)
+__device__ __forceinline__ float key_to_float(uint32_t key) {
+  if (key == kNanKey) return __uint_as_float(0x7FC00000u);
+  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
 // Block-wide scan over 256 threads (Hillis-Steele in LDS): returns the exclusive prefix, `total` = the whole block's.
 template <typename T, typename Op>
 __device__ __forceinline__ T block_scan_excl(T v, T identity, Op op, T* sh, T& total) {

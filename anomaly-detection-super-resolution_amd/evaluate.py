@@ -164,13 +164,18 @@ class OperatingPoint:
     """What ``evaluate_on_test(operating_point=...)`` takes (a dict with these keys does too): a given ``threshold``, or the
     rate ``fpr`` in (0, 1) to calibrate one at on the defect-free (LR, HR) u8 pairs ``calib`` - on all pixels of their maps
     (``level`` 'pixel') or on each map's maximum ('image'); ``min_area``: predicted components below it are removed;
-    ``save_masks``: write the predicted masks under ``output_dir/anomaly_masks``."""
+    ``save_masks``: write the predicted masks under ``output_dir/anomaly_masks``.  ``region_metrics``: add the region-level
+    counts of ``metrics.region_stats`` (DESIGN.md "Defect regions"), a ground-truth region counting as found at
+    ``region_min_overlap`` of its pixels; ``save_regions``: then also write ``output_dir/regions.csv``."""
     threshold: Optional[float] = None
     fpr: Optional[float] = None
     level: str = 'pixel'
     min_area: int = 1
     save_masks: bool = False
     calib: Sequence[Tuple[np.ndarray, np.ndarray]] = ()
+    region_metrics: bool = False
+    region_min_overlap: float = 0.0
+    save_regions: bool = False
 
     def check(self) -> 'OperatingPoint':
         if (self.threshold is None) == (self.fpr is None):
@@ -183,6 +188,10 @@ class OperatingPoint:
             raise ValueError(f"operating point: level = {self.level!r}, must be 'pixel' or 'image'")
         if int(self.min_area) < 1 or int(self.min_area) != self.min_area:
             raise ValueError(f"operating point: min_area = {self.min_area}, must be an integer >= 1")
+        if not 0.0 <= float(self.region_min_overlap) <= 1.0:
+            raise ValueError(f"operating point: region_min_overlap = {self.region_min_overlap}, must be in [0, 1]")
+        if self.save_regions and not self.region_metrics:
+            raise ValueError("operating point: save_regions belongs to region_metrics")
         return self
 
 
@@ -562,7 +571,10 @@ def _operating_point(shard: Shard, spec: MapSpec, op: OperatingPoint, maps: torc
     calibration stacks - made by the same ``spec`` - give at the asked false-positive rate: ``threshold``,
     ``threshold_source`` ('given' or 'fpr'; then also ``threshold_fpr``, ``threshold_level``, ``calib_images`` and
     ``calib_rate``, the rate achieved on the calibration values), ``min_region_area``, the image-level counts and rates of
-    ``metrics.operating_point_stats`` and, with ``labels``, its pixel-level ones; the masks are saved where asked for."""
+    ``metrics.operating_point_stats`` and, with ``labels``, its pixel-level ones; the masks are saved where asked for.  With
+    ``op.region_metrics`` also the entries of ``metrics.region_stats`` and ``region_min_overlap``, from the table of the
+    predicted regions against ``labels`` and the table of the ground-truth regions against the prediction (without ``labels``
+    every image counts as all-ok: no ground-truth region, every predicted region a false alarm)."""
     if op.fpr is not None:
         cmaps, cmax = spec.make(calib[0], calib[1], op.level == 'image')
         t, achieved = M.map_threshold(cmax if op.level == 'image' else cmaps, op.fpr)
@@ -586,6 +598,28 @@ def _operating_point(shard: Shard, spec: MapSpec, op: OperatingPoint, maps: torc
     print(line)
     if op.save_masks and shard.output_dir:
         save_masks(pred, shard.my_names(), shard.my_splits(), shard.output_dir)
+    if op.region_metrics:
+        out.update(_region_metrics(shard, op, maps, pred, labels))
+    return out
+
+
+def _region_metrics(shard: Shard, op: OperatingPoint, maps: torch.Tensor, pred: torch.Tensor, labels) -> dict:
+    """``metrics.region_stats`` of the surviving prediction ``pred`` against ``labels`` (None: no defect anywhere), the
+    ``Regions - ...`` line, and ``regions.csv`` where asked for."""
+    ptab = M.region_table(pred, maps, labels)
+    gtab = M.region_table(labels if labels is not None else torch.zeros_like(pred), None, pred)
+    y = [shard.y_true[i] for i in shard.mine]
+    st = M.region_stats(ptab, gtab, len(y), y, float(op.region_min_overlap))
+    out = dict(st, region_min_overlap=float(op.region_min_overlap))
+    print(f"Regions - predicted={st['region_pred']} hit={st['region_hit']} precision={st['region_precision']:.4f} "
+          f"false_alarms={st['region_false_alarms']} per_image={st['false_alarms_per_image']:.4f} "
+          f"on_good={st['false_alarms_on_good']}; ground truth={st['region_gt']} found={st['region_found']} "
+          f"recall={st['region_recall']:.4f} (min_overlap={float(op.region_min_overlap):g})")
+    if op.save_regions and shard.output_dir:
+        from .predict import write_regions_csv
+        if labels is not None:
+            ptab = dict(ptab, gt_overlap=ptab['overlap'])
+        write_regions_csv(os.path.join(shard.output_dir, 'regions.csv'), ptab, shard.my_names(), shard.my_splits())
     return out
 
 
@@ -647,7 +681,9 @@ def _run(args):
         if args.threshold_fpr is not None and world == 1:     # more ranks skip the operating point: nothing to read
             calib = [(lr, hr) for _, lr, hr in iter_split(opt.data_root, class_name, 'good', opt.scale, opt.n_colors, part='val')]
         op = OperatingPoint(threshold=args.threshold, fpr=args.threshold_fpr, level=args.threshold_level,
-                            min_area=args.min_region_area, save_masks=args.save_masks, calib=calib)
+                            min_area=args.min_region_area, save_masks=args.save_masks, calib=calib,
+                            region_metrics=args.region_metrics, region_min_overlap=args.region_min_overlap,
+                            save_regions=args.save_regions)
     out = evaluate_on_test(opt, model, [(lr, hr) for _, lr, hr in g], [(lr, hr) for _, lr, hr in b], rank, world,
                            names=[n for n, _, _ in g] + [n for n, _, _ in b], output_dir=out_dir, save_images=args.save_images,
                            masks=masks, pixel_metrics=args.pixel_metrics, save_maps=args.save_anomaly_maps, map_ws=args.map_ws,

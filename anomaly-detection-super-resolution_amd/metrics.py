@@ -480,6 +480,100 @@ def operating_point_stats(counts: Optional[dict], img_pred, y_true: Sequence[int
     return out
 
 
+REGION_FIELDS = ("image", "area", "box", "sum_y", "sum_x", "overlap")      # of every region table; with scores also REGION_PEAK
+REGION_PEAK = ("peak", "peak_y", "peak_x")
+_REGION_CAP = 4096                                                          # records of region_table's first call
+
+
+def _region_call(m, s, o, cap: int):
+    """One ``srad_region_table``: (records as int32 [cap, 14], R, NaN scores inside regions)."""
+    n, H, W = m.shape
+    rec = torch.empty(cap, 14, dtype=torch.int32, device=m.device)       # srad_region_record: 56 bytes
+    counts = torch.empty(3, dtype=torch.int64, device=m.device)          # u64 on the device; the values stay below 2^31
+    _call_with_ws("region_table_workspace_bytes", (n, H, W), "region_table",
+                  (L.dptr(m), L.dptr(s), L.dptr(o), n, H, W, L.dptr(rec) if cap else None, C.c_int64(cap), L.dptr(counts)), m.device)
+    n_reg, n_nan, _ = counts.tolist()
+    return rec, n_reg, n_nan
+
+
+def region_table(masks: torch.Tensor, scores: Optional[torch.Tensor] = None, other: Optional[torch.Tensor] = None,
+                 cap: Optional[int] = None) -> dict:
+    """The table of regions of GPU masks [n,H,W] (any integer or bool dtype, nonzero = member): one row per 8-connected
+    component of each image's mask (the components of ``mask_regions``), ordered by image and, within an image, by the region's
+    first pixel in raster order - the order of ``scipy.ndimage.label(m_i, np.ones((3, 3)))`` (DESIGN.md "Defect regions").
+    Returns GPU tensors of length R under ``REGION_FIELDS``: ``image`` int32, ``area`` int32, ``box`` int32 [R, 4] = (y0, x0, y1,
+    x1), inclusive, ``sum_y`` / ``sum_x`` int64 (centroid = sum / area), ``overlap`` int32 = member pixels where ``other`` (a
+    second mask of the same shape) is nonzero, 0 without it; with ``scores`` (float32, same shape) also ``peak`` float32, the
+    region's largest score, and ``peak_y`` / ``peak_x`` int32, of equal maxima (-0.0 == +0.0) the first in raster order; and
+    ``n_regions`` = R, a Python int.  ``cap``: the records of the first call (default 4096); when R exceeds it the call is
+    repeated once at R.  R = 0 gives empty tensors.  ValueError for a shape mismatch, scores that are not float32, an empty
+    tensor, a negative ``cap`` and a NaN score inside a region (a NaN outside every region is not looked at)."""
+    m = _mask_stack(masks)
+    s = o = None
+    if scores is not None:
+        _need_cuda(scores)
+        s = scores.detach()
+        if s.dim() == 2:
+            s = s[None]
+        if s.dtype != torch.float32:
+            raise ValueError(f"region_table takes float32 scores, got {s.dtype}")
+        if tuple(s.shape) != tuple(m.shape):
+            raise ValueError(f"scores {tuple(scores.shape)} and masks {tuple(masks.shape)} must have the same shape")
+        s = s.contiguous()
+    if other is not None:
+        o = _mask_stack(other)
+        if tuple(o.shape) != tuple(m.shape):
+            raise ValueError(f"other {tuple(other.shape)} and masks {tuple(masks.shape)} must have the same shape")
+    first = _REGION_CAP if cap is None else int(cap)
+    if first < 0:
+        raise ValueError(f"region_table: cap = {cap}, must be >= 0")
+    rec, n_reg, n_nan = _region_call(m, s, o, first)
+    if n_nan:
+        raise ValueError(f"region_table: {n_nan} scores inside the regions are NaN")
+    if n_reg > first:
+        rec, n_reg, _ = _region_call(m, s, o, n_reg)
+    rec = rec[:n_reg]
+    out = dict(image=rec[:, 0].contiguous(), area=rec[:, 1].contiguous(), box=rec[:, 2:6].contiguous(),
+               sum_y=rec[:, 6:8].contiguous().view(torch.int64).reshape(-1),       # u64 on the device; below 2^62
+               sum_x=rec[:, 8:10].contiguous().view(torch.int64).reshape(-1), overlap=rec[:, 10].contiguous())
+    if s is not None:
+        out.update(peak=rec[:, 11].contiguous().view(torch.float32), peak_y=rec[:, 12].contiguous(), peak_x=rec[:, 13].contiguous())
+    out["n_regions"] = n_reg
+    return out
+
+
+def _column(table: dict, key: str) -> np.ndarray:
+    v = table[key]
+    return np.asarray(v.cpu() if hasattr(v, "cpu") else v)
+
+
+def region_stats(pred_table: dict, gt_table: dict, n_images: int, y_true: Sequence[int], min_overlap: float = 0.0) -> dict:
+    """Detection counts at the level of regions (host only), from two tables of ``region_table``: ``pred_table`` of the predicted
+    masks with ``other`` = the ground truth, ``gt_table`` of the ground-truth masks with ``other`` = the prediction.
+    ``region_pred``; ``region_hit`` = predicted regions that touch the ground truth (``overlap`` >= 1); ``region_precision`` =
+    hit / pred; ``region_false_alarms`` = pred - hit; ``false_alarms_per_image`` (over ``n_images``); ``false_alarms_on_good`` =
+    the false alarms in images with ``y_true`` 0; ``region_gt``; ``region_found`` = ground-truth regions with ``overlap`` >=
+    max(1, ceil(min_overlap * area)); ``region_recall`` = found / gt.  A ratio with a zero denominator is 0.0.  ValueError for
+    ``min_overlap`` outside [0, 1] and for ``y_true`` of another length than ``n_images``."""
+    f = float(min_overlap)
+    if not 0.0 <= f <= 1.0:
+        raise ValueError(f"region_stats: min_overlap = {min_overlap}, must be in [0, 1]")
+    n_images = int(n_images)
+    good = np.asarray([int(v) == 0 for v in y_true], dtype=bool)
+    if len(good) != n_images:
+        raise ValueError(f"region_stats: {n_images} images, {len(good)} labels")
+    p_img, p_ov = _column(pred_table, "image").astype(np.int64), _column(pred_table, "overlap").astype(np.int64)
+    g_area, g_ov = _column(gt_table, "area").astype(np.int64), _column(gt_table, "overlap").astype(np.int64)
+    miss = p_ov < 1
+    pred, hit = int(p_ov.size), int(p_ov.size - miss.sum())
+    need = np.maximum(1, np.ceil(f * g_area.astype(np.float64)).astype(np.int64))
+    gt, found = int(g_area.size), int((g_ov >= need).sum())
+    return dict(region_pred=pred, region_hit=hit, region_precision=_ratio(hit, pred), region_false_alarms=pred - hit,
+                false_alarms_per_image=_ratio(pred - hit, n_images),
+                false_alarms_on_good=int(good[p_img[miss]].sum()) if pred else 0, region_gt=gt, region_found=found,
+                region_recall=_ratio(found, gt))
+
+
 def gaussian_weights(sigma: float, truncate: float = 4.0) -> np.ndarray:
     """The half ``[r:]`` of ``scipy.ndimage._filters._gaussian_kernel1d(sigma, 0, r)`` with ``r = int(truncate * sigma + 0.5)``:
     float64 [r + 1], the centre weight first.  Computed here, with numpy's exp, so that the device filter uses scipy's weights

@@ -253,6 +253,13 @@ def _open_unit_float(text: str) -> float:
     return v
 
 
+def _closed_unit_float(text: str) -> float:
+    v = float(text)
+    if not 0.0 <= v <= 1.0:                                   # NaN too
+        raise argparse.ArgumentTypeError(f"{text} is not a share in [0, 1]")
+    return v
+
+
 def _finite_or_inf_float(text: str) -> float:
     v = float(text)
     if v != v:
@@ -354,10 +361,25 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
     p.add_argument('--ema', action='store_true', default=False,
                    help="evaluate the averaged weights of a run trained with --ema: --run-dir's model/model_ema_best.pt, else "
                         "model_ema_latest.pt (no fall-back to the raw weights; excludes --checkpoint)")
+    p.add_argument('--region-metrics', action='store_true', default=False,
+                   help="detection counts at the level of defect regions at the operating point: predicted regions that touch the "
+                        "ground truth, false alarms (per image, on good images), ground-truth regions found; needs --threshold or "
+                        "--threshold-fpr, the test/bad/GT masks and --gpus 1")
+    p.add_argument('--region-min-overlap', type=_closed_unit_float, default=None, metavar='F',
+                   help="a ground-truth region counts as found when at least this share of its pixels is predicted (and at least "
+                        "one pixel), in [0, 1]; default 0 (with --region-metrics)")
+    p.add_argument('--save-regions', action='store_true', default=False,
+                   help="write <output-dir>/regions.csv: one row per predicted region (with --region-metrics)")
     _with_config(p, pre_args)
     args = p.parse_args(argv)
     if args.ema and args.checkpoint:
         p.error("--ema and --checkpoint exclude each other (an explicit file is already a choice)")
+    if args.region_metrics and args.threshold is None and args.threshold_fpr is None:
+        p.error("--region-metrics counts the regions of an operating point against the ground-truth masks: give --threshold or "
+                "--threshold-fpr (and prepare the data with masks, test/bad/GT)")
+    if (args.region_min_overlap is not None or args.save_regions) and not args.region_metrics:
+        p.error("--region-min-overlap and --save-regions belong to --region-metrics: give it too")
+    args.region_min_overlap = 0.0 if args.region_min_overlap is None else args.region_min_overlap
     if args.threshold is not None and args.threshold_fpr is not None:
         p.error("--threshold and --threshold-fpr exclude each other (a given threshold or a calibrated one)")
     if isinstance(args.map_scales, (list, tuple)):            # a list from a config file gets the command line's check

@@ -15,7 +15,8 @@ image decoding stays on the host.
 Every decision is taken in the model's frame (hr x hr).  ``--source-frame`` / ``--save-overlays`` add renderings of those
 decisions at each source image's own size: the map and the filtered mask resized bilinearly on the GPU (``ops.resize_f32``,
 equal to Pillow's mode-F resize bit for bit) and the heat map with the mask's outline drawn on the source
-(``ops.overlay_rgb``; DESIGN.md "Maps and masks at source size")."""
+(``ops.overlay_rgb``; DESIGN.md "Maps and masks at source size").  ``--save-regions`` lists the defects: ``regions.csv`` has one row
+per 8-connected component of the filtered masks (``metrics.region_table``; DESIGN.md "Defect regions")."""
 from __future__ import annotations
 
 import argparse
@@ -210,7 +211,7 @@ class Detector:
         self.threshold, achieved = M.map_threshold(img_max if level == 'image' else maps, fpr)
         return self.threshold, achieved
 
-    def predict(self, images: Sequence, source_frame: bool = False, overlays: bool = False) -> dict:
+    def predict(self, images: Sequence, source_frame: bool = False, overlays: bool = False, regions: bool = False) -> dict:
         """Per image (lists, in input order): ``ssim``, ``mse``, ``psnr`` of SR against HR (``metrics.score_pairs``; the SSIM at
         the spec's window, the mean over its scales where it has scales), ``map_max``, ``defect_pixels`` (pixels above the
         threshold that survive the area filter) and ``defective`` (any such pixel); ``maps`` float32 [n,H,W] and ``masks``
@@ -222,7 +223,12 @@ class Detector:
         the same resize of the float mask at >= 0.5 - a component the area filter removed stays removed.  ``overlays`` implies
         ``source_frame`` and adds ``overlays[i]`` uint8 [H_i,W_i,3]: ``ops.overlay_rgb`` of the raw source (``as_source``; true
         colour stays colour) under ``maps_src[i]`` through ``heat_lut`` at ``overlay_scale(threshold)``, ``masks_src[i]``
-        outlined."""
+        outlined.
+
+        ``regions`` adds the list of defects: ``regions``, ``metrics.region_table`` of ``masks`` against ``maps`` (one row per
+        8-connected component that survived the area filter, so every area is >= ``min_area``; tensors on the GPU), and
+        ``region_count``, the rows of each image; with the source frame also ``src_box``, int [R, 4] on the host, each region's
+        box in its source image (``source_box``)."""
         if self.threshold is None:
             raise ValueError("predict: no threshold (calibrate on defect-free images first, or give one)")
         source_frame = bool(source_frame or overlays)
@@ -236,6 +242,13 @@ class Detector:
                    threshold=self.threshold, maps=maps, masks=masks, sr=sr, hr=hr)
         if source_frame:
             res.update(self._source_frame(kept, maps, masks, bool(overlays)))
+        if regions:
+            table = M.region_table(masks, maps)
+            res.update(regions=table, region_count=np.bincount(table['image'].cpu().numpy(), minlength=len(pixels)).tolist())
+            if source_frame:
+                sizes_src = [tuple(m.shape) for m in res['maps_src']]
+                res['src_box'] = np.array([source_box(b, tuple(maps.shape[1:]), sizes_src[i])
+                                           for i, b in zip(table['image'].tolist(), table['box'].tolist())], dtype=np.int64).reshape(-1, 4)
         return res
 
     def _source_frame(self, kept, maps: torch.Tensor, masks: torch.Tensor, overlays: bool) -> dict:
@@ -284,6 +297,49 @@ def unique_names(files: Sequence[Path]) -> List[str]:
         k = seen[f.stem] = seen.get(f.stem, 0) + 1
         names.append(f.stem if k == 1 else f"{f.stem}_{k}")
     return names
+
+
+def source_box(box, model_hw, source_hw) -> Tuple[int, int, int, int]:
+    """A model-frame box (y0, x0, y1, x1), inclusive, in a source image of ``source_hw`` = (H, W), when the model's frame is
+    ``model_hw``: the source pixels that the box's pixels cover when pixel c of M spans [c * S / M, (c + 1) * S / M) - per axis
+    ``src0 = (c0 * S) // M`` and ``src1 = ceil((c1 + 1) * S / M) - 1``, in integers, clipped to the image.  ``src1 >= src0``
+    always; M == S is the identity."""
+    out = []
+    for (c0, c1), m, s in zip(((box[0], box[2]), (box[1], box[3])), model_hw, source_hw):
+        c0, c1, m, s = int(c0), int(c1), int(m), int(s)
+        if m < 1 or s < 1 or not 0 <= c0 <= c1 < m:
+            raise ValueError(f"source_box: box {tuple(box)} in a {tuple(model_hw)} frame, source {tuple(source_hw)}")
+        lo, hi = (c0 * s) // m, -((-(c1 + 1) * s) // m) - 1
+        out.append((min(max(lo, 0), s - 1), min(max(hi, 0), s - 1)))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+REGION_COLUMNS = ('area', 'y0', 'x0', 'y1', 'x1', 'centroid_y', 'centroid_x', 'peak', 'peak_y', 'peak_x')
+
+
+def write_regions_csv(path, table: dict, names: Sequence[str], kinds: Sequence[str], src_box=None) -> int:
+    """``regions.csv``: one row per region of ``table`` (``metrics.region_table`` with scores; tensors or arrays) - name, kind
+    (the image's split or predicted kind), region (its index within the image), ``REGION_COLUMNS``, ``gt_overlap`` where the
+    table has ``gt_overlap`` (a table made against ground-truth masks), ``src_y0 .. src_x1`` where ``src_box`` is given.  The
+    centroid is ``sum / area`` in doubles; floats are written with ``repr``.  Returns the number of rows."""
+    col = {k: np.asarray(v.cpu() if hasattr(v, 'cpu') else v) for k, v in table.items() if k != 'n_regions'}
+    header = ['name', 'kind', 'region'] + list(REGION_COLUMNS) + (['gt_overlap'] if 'gt_overlap' in col else [])
+    header += ['src_y0', 'src_x0', 'src_y1', 'src_x1'] if src_box is not None else []
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    with open(path, 'w', newline='') as fh:
+        w = csv.writer(fh)
+        w.writerow(header)
+        seen: dict = {}
+        for r in range(len(col['image'])):
+            i, area = int(col['image'][r]), int(col['area'][r])
+            k = seen[i] = seen.get(i, -1) + 1
+            row = [names[i], kinds[i], k, area] + [int(v) for v in col['box'][r]]
+            row += [repr(int(col['sum_y'][r]) / area), repr(int(col['sum_x'][r]) / area), repr(float(col['peak'][r])),
+                    int(col['peak_y'][r]), int(col['peak_x'][r])]
+            row += [int(col['gt_overlap'][r])] if 'gt_overlap' in col else []
+            row += [int(v) for v in src_box[r]] if src_box is not None else []
+            w.writerow(row)
+    return len(col['image'])
 
 
 def write_operating_point(path, threshold: float, fpr: float, level: str, achieved: float, n_images: int, min_area: int, spec: MapSpec,
@@ -404,8 +460,13 @@ def parse_predict_args(argv=None) -> argparse.Namespace:
                    help=f"opacity of the hottest level of the overlay, in [0, 1] (default {OVERLAY_ALPHA_DEFAULT})")
     p.add_argument('--overlay-contour', type=int, default=None, choices=range(5), metavar='R',
                    help=f"radius of the mask outline in pixels, 0..4, 0 draws none (default {OVERLAY_CONTOUR_DEFAULT})")
+    p.add_argument('--save-regions', action='store_true', default=False,
+                   help="write regions.csv: one row per predicted defect region (area, box, centroid, peak; with --source-frame "
+                        "its box in the source image too)")
     p.add_argument('--output-dir', type=str, default='')
     args = p.parse_args(argv)
+    if args.save_regions and not args.input:
+        p.error("--save-regions lists the regions of --input images: give --input too")
     if (args.overlay_alpha is not None or args.overlay_contour is not None) and not args.save_overlays:
         p.error("--overlay-alpha and --overlay-contour shape what --save-overlays writes: give it too")
     args.source_frame = args.source_frame or args.save_overlays
@@ -475,7 +536,7 @@ def _run(args) -> dict:
               f"{len(calib_files)} defect-free images, achieved {achieved:.6f}), min_area={min_area}: {op_file}")
     if files:
         names = unique_names(files)
-        res = det.predict(files, source_frame=args.source_frame, overlays=args.save_overlays)
+        res = det.predict(files, source_frame=args.source_frame, overlays=args.save_overlays, regions=args.save_regions)
         out.update(res, names=names, files=[str(f) for f in files])
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, 'predictions.csv'), 'w', newline='') as fh:
@@ -491,6 +552,8 @@ def _run(args) -> dict:
             save_masks(res['masks'], names, kinds, out_dir)
         if args.source_frame:
             save_source_frame(res, names, kinds, out_dir)
+        if args.save_regions:
+            write_regions_csv(os.path.join(out_dir, 'regions.csv'), res['regions'], names, kinds, res.get('src_box'))
         if args.save_images:
             sr_host = res['sr'].cpu().numpy()
             for k, name in enumerate(names):

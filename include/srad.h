@@ -425,6 +425,32 @@ int srad_operating_point_workspace_bytes(int n_img, int H, int W, size_t* bytes)
 int srad_operating_point(const float* scores, const uint8_t* masks, int n_img, int H, int W, float threshold, int min_area,
                          uint8_t* pred_out, uint32_t* img_pred_out, uint64_t* counts_out, void* workspace, size_t workspace_bytes,
                          void* stream);
+/* One record of srad_region_table (56 bytes). */
+typedef struct {
+  int32_t image;              /* index into the stack */
+  int32_t area;               /* pixels of the region */
+  int32_t y0, x0, y1, x1;     /* bounding box, inclusive */
+  uint64_t sum_y, sum_x;      /* sums of the member pixels' coordinates: centroid = sum / area */
+  int32_t overlap;            /* member pixels with other != 0 (0 without `other`) */
+  float peak;                 /* with scores: the region's largest score (-0.0 as +0.0); NaN without scores */
+  int32_t peak_y, peak_x;     /* where: of equal maxima the first in raster order; -1 without scores */
+} srad_region_record;
+/* The table of regions of DEVICE u8 masks [n_img, H, W] (nonzero = member), n_img x H x W in [1, 2^31): one record per
+ * 8-connected component of each image's mask, with the labelling of srad_mask_regions itself (DESIGN.md "Defect regions").
+ * Records are ordered by image and, within an image, by the region's first pixel in raster order - the order of
+ * scipy.ndimage.label(mask, ones((3, 3))).  scores: DEVICE float32 of the same shape, or NULL; other: DEVICE u8 of the same
+ * shape, or NULL.
+ *   records_out (DEVICE, cap x srad_region_record; may be NULL when cap == 0) receives the first min(R, cap) records;
+ *   counts_out (DEVICE, 3 x u64) = {R = regions over all images (exact whatever cap), NaN scores inside regions, records
+ *   written = min(R, cap)}.
+ * A NaN score inside a region is counted and never the peak (a region of NaN scores only has peak NaN at (-1, -1)); outside the
+ * regions the scores are not read.  cap < 0 is refused.  Launches: the labelling (3), a copy, the rank of the roots (3), one
+ * accumulation pass, the peak decode.  Integer sums, minima and maxima only: the same bits on every call.  Stream-ordered, no
+ * host sync, no allocation; workspace >= srad_region_table_workspace_bytes (about 12 bytes per pixel). */
+int srad_region_table_workspace_bytes(int n_img, int H, int W, size_t* bytes);
+int srad_region_table(const uint8_t* masks, const float* scores, const uint8_t* other, int n_img, int H, int W,
+                      srad_region_record* records_out, int64_t cap, uint64_t* counts_out, void* workspace, size_t workspace_bytes,
+                      void* stream);
 /* Gaussian smoothing of DEVICE float32 maps [n_img, H, W] (n_img x H x W < 2^31) with a symmetric separable filter of radius
  * `radius` in [0, 128], radius <= min(H, W) (one half-sample reflection, d c b a | a b c d, at every edge).  weights_host: HOST
  * array of radius + 1 doubles, w[0] the centre and w[j] the weight at offsets +-j.  Given scipy's weights the result equals
