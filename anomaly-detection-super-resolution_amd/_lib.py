@@ -38,6 +38,14 @@ class WqStep(C.Structure):
     _fields_ = [("kind", C.c_int32), ("i", C.c_int32 * 9), ("alpha", C.c_float), ("p", C.c_void_p * 7)]
 
 
+class GemmPlan(C.Structure):
+    """What srad_op_gemm runs for a set of arguments (include/srad.h srad_gemm_plan)."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "BM", "BN", "CPS", "LN", "CONV", "SPECIAL", "grid_x", "grid_y", "launches")]
+
+
+GEMM_FAMILIES = ("tiled", "conv80", "conv80x4", "thin", "tail")      # SRAD_GEMM_*
+
+
 class ResampleTable(C.Structure):
     """One axis of srad_resize_u8 (include/srad.h srad_resample_table): the bounds on the host and the device copies."""
     _fields_ = [("in_size", C.c_int32), ("out_size", C.c_int32), ("ksize", C.c_int32), ("bounds", C.c_void_p),
@@ -203,6 +211,9 @@ _SIG = {
     "srad_op_gemm": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                _P, C.c_size_t, _P]),
+    "srad_op_gemm_plan": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                    _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                    _P, C.c_size_t, _P, C.POINTER(GemmPlan)]),
     "srad_bench_gemm": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                   _P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t,
                                   C.c_int, C.POINTER(C.c_float), _P]),

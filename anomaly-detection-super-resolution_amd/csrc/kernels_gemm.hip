@@ -582,20 +582,32 @@ __global__ void pack_qkv_frag_kernel(const float* __restrict__ src, __bf16* __re
   }
 }
 
-template <int PREC, int BM, int BN, int WMV, int WNV, bool LN, bool CONV, bool SPECIAL, int CPS_ = 0>
-int launch_one(const GemmParams& p, hipStream_t s) {
-  constexpr int CPS = CPS_ ? CPS_ : (PREC == SRAD_PREC_BF16 ? 8 : 4);
+// K-stage depth (32-wide chunks per stage) of the instance that serves a tile: the one rule behind both the plan and the
+// template arguments below.  bf16 stages 8 chunks, except 4 ("128-wide K stages": half the LDS, four workgroups per CU, deeper
+// load / MFMA overlap) at 64x64 (4 % on the training step) and, for the conv gather, at 64x80 and 128x80 too (DRN's 80-channel
+// 3x3 convs 185 -> 225 TFLOP/s); LayerNorm keeps the whole K resident and stays at 8.  fp32 and split-bf16 stage 4.
+constexpr int gemm_cps(int prec, int bm, int bn, bool ln, bool conv) {
+  if (prec != SRAD_PREC_BF16) return 4;
+  if (ln) return 8;
+  if (conv) return ((bm == 64 && (bn == 64 || bn == 80)) || (bm == 128 && bn == 80)) ? 4 : 8;
+  return (bm == 64 && bn == 64) ? 4 : 8;
+}
+
+template <int PREC, int BM, int BN, int WMV, int WNV, bool LN, bool CONV, bool SPECIAL>
+int launch_one(const GemmPlan& pl, const GemmParams& p, hipStream_t s) {
+  constexpr int CPS = gemm_cps(PREC, BM, BN, LN, CONV);
   constexpr int CPA = LN ? CPS + (PREC == SRAD_PREC_BF16 ? 2 : 6) : CPS;
   using T = typename PrecT<PREC>::type;
   constexpr size_t lds = ((size_t)BM * (CPA * 32 + PrecT<PREC>::PAD) + (size_t)BN * (CPS * 32 + PrecT<PREC>::PAD)) * sizeof(T) *
                              (PREC == SRAD_PREC_BF16X3 ? 2 : 1) +
                          (LN ? 2 * (size_t)CPA * 32 * sizeof(float) : 0);
-  // pool_part rows are summed per image by callers that size them with srad_gemm_tile_rows(): a tile choice that drifts from that
-  // mirror, or an image that is not a whole number of tiles, must fail here instead of averaging the wrong rows
+  SRAD_REQUIRE(pl.BM == BM && pl.BN == BN && pl.CPS == CPS && pl.LN == (int)LN && pl.CONV == (int)CONV && pl.SPECIAL == (int)SPECIAL,
+               "gemm: the plan (%dx%d, %d chunks per stage) does not name the instance it was dispatched to", pl.BM, pl.BN, pl.CPS);
+  // pool_part rows are summed per image by callers that size them with srad_gemm_tile_rows(): an image that is not a whole
+  // number of tiles must fail here instead of averaging the wrong rows
   if (p.pool_part)
-    SRAD_REQUIRE(BM == srad_gemm_tile_rows(PREC, p) && p.Ho > 0 && (p.Ho * p.Wo) % BM == 0,
-                 "gemm: pool_part with %d-row tiles, but srad_gemm_tile_rows says %d and an image has %d rows", BM, srad_gemm_tile_rows(PREC, p), p.Ho * p.Wo);
-  dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM);
+    SRAD_REQUIRE(p.Ho > 0 && (p.Ho * p.Wo) % BM == 0, "gemm: pool_part with %d-row tiles, but an image has %d rows", BM, p.Ho * p.Wo);
+  dim3 grid(pl.grid_x, pl.grid_y);
   const int cls = BN >= 64 ? SRAD_K_GEMM_BN64 : (BN == 32 ? SRAD_K_GEMM_BN32 : SRAD_K_GEMM_BN16);
   // algorithmic work: 2*M*N*K flops; bytes = A rows once + packed W once + Y once (+ residual)
   const double K = (double)p.ntaps * p.Cin;
@@ -605,75 +617,71 @@ int launch_one(const GemmParams& p, hipStream_t s) {
   return srad_launch_dyn<gemm_kernel<PREC, BM, BN, WMV, WNV, CPS, LN, CONV, SPECIAL>>(grid, dim3(256), lds, s, p);
 }
 
+// the template variant of a tile that the plan names (mode switches are template parameters of the kernel)
 template <int PREC, int BM, int BN, int WMV, int WNV>
-int launch_cfg(const GemmParams& p, hipStream_t s) {
-  const bool conv = p.ntaps == 9 || p.stride != 1;
-  const bool special = p.ps == 2 || p.hsplit_hd > 0;
-  if (conv) {
-    if constexpr (PREC == SRAD_PREC_BF16 && ((BM == 64 && (BN == 64 || BN == 80)) || (BM == 128 && BN == 80))) {
-      // 128-wide K stages here too: DRN's 80-channel 3x3 convs 185 -> 225 TFLOP/s
-      return special ? launch_one<PREC, BM, BN, WMV, WNV, false, true, true, 4>(p, s)
-                     : launch_one<PREC, BM, BN, WMV, WNV, false, true, false, 4>(p, s);
-    }
-    return special ? launch_one<PREC, BM, BN, WMV, WNV, false, true, true>(p, s)
-                   : launch_one<PREC, BM, BN, WMV, WNV, false, true, false>(p, s);
+int launch_cfg(const GemmPlan& pl, const GemmParams& p, hipStream_t s) {
+  if (pl.CONV) {
+    return pl.SPECIAL ? launch_one<PREC, BM, BN, WMV, WNV, false, true, true>(pl, p, s)
+                      : launch_one<PREC, BM, BN, WMV, WNV, false, true, false>(pl, p, s);
   }
-  if (p.ln_g) {
+  if (pl.LN) {
     if constexpr (BM <= 64) {
-      return special ? launch_one<PREC, BM, BN, WMV, WNV, true, false, true>(p, s)
-                     : launch_one<PREC, BM, BN, WMV, WNV, true, false, false>(p, s);
+      return pl.SPECIAL ? launch_one<PREC, BM, BN, WMV, WNV, true, false, true>(pl, p, s)
+                        : launch_one<PREC, BM, BN, WMV, WNV, true, false, false>(pl, p, s);
     } else {
       return srad_set_error(SRAD_ERR_ARG, "gemm: LayerNorm fusion needs N > 32");
     }
   }
-  if constexpr (PREC == SRAD_PREC_BF16 && BM == 64 && BN == 64) {
-    // 128-wide K stages (half the LDS, four workgroups per CU, deeper load / MFMA overlap): 4 % on the training step
-    return special ? launch_one<PREC, BM, BN, WMV, WNV, false, false, true, 4>(p, s)
-                   : launch_one<PREC, BM, BN, WMV, WNV, false, false, false, 4>(p, s);
-  }
-  return special ? launch_one<PREC, BM, BN, WMV, WNV, false, false, true>(p, s)
-                 : launch_one<PREC, BM, BN, WMV, WNV, false, false, false>(p, s);
+  return pl.SPECIAL ? launch_one<PREC, BM, BN, WMV, WNV, false, false, true>(pl, p, s)
+                    : launch_one<PREC, BM, BN, WMV, WNV, false, false, false>(pl, p, s);
 }
 
-// Tile choice: the problems are small (M = B*H*W rows, a few thousand), so prefer the largest tile
-// that still yields >= ~1.5 workgroups per CU.
+// the tile the plan names -> its instance (wave layout: 2 x 2 on the square-ish tiles, 4 x 1 on the tall ones)
 template <int PREC>
-int launch_prec(const GemmParams& p, hipStream_t s) {
-  auto tiles = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  if (!p.ln_g) {
-    if (p.N <= 16 && tiles(128, 16) >= 384) return launch_cfg<PREC, 128, 16, 4, 1>(p, s);
-    if (p.N <= 32 && tiles(128, 32) >= 384) return launch_cfg<PREC, 128, 32, 4, 1>(p, s);
-  }
-  if (p.N <= 32) return launch_cfg<PREC, 32, 32, 2, 2>(p, s);
-  // N = 65..80 (DRN's 80-channel RCAB convolutions): one 80-wide tile instead of a full and a mostly empty 64-wide one
+int launch_prec(const GemmPlan& pl, const GemmParams& p, hipStream_t s) {
+  const int tile = pl.BM * 1000 + pl.BN;
+  if (tile == 128016) return launch_cfg<PREC, 128, 16, 4, 1>(pl, p, s);
+  if (tile == 128032) return launch_cfg<PREC, 128, 32, 4, 1>(pl, p, s);
+  if (tile == 32032) return launch_cfg<PREC, 32, 32, 2, 2>(pl, p, s);
   if constexpr (PREC == SRAD_PREC_BF16) {
-    // ... and 128 rows per workgroup once that still gives every CU one (C3: 32768 pixels -> 256 workgroups in ONE round; the
-    // kernel is a chain of load -> LDS -> MFMA stages per workgroup, so twice the rows per stage cost little more per stage)
-    if (!p.ln_g && p.N > 64 && p.N <= 80 && tiles(128, 80) >= 256) return launch_cfg<PREC, 128, 80, 4, 1>(p, s);
+    if (tile == 128080) return launch_cfg<PREC, 128, 80, 4, 1>(pl, p, s);
   }
-  if (!p.ln_g && p.N > 64 && p.N <= 80 && tiles(64, 80) >= 384) return launch_cfg<PREC, 64, 80, 4, 1>(p, s);
-  if (tiles(64, 64) >= 384) return launch_cfg<PREC, 64, 64, 2, 2>(p, s);
-  if (tiles(32, 64) >= 384) return launch_cfg<PREC, 32, 64, 2, 2>(p, s);
-  return launch_cfg<PREC, 32, 32, 2, 2>(p, s);
+  if (tile == 64080) return launch_cfg<PREC, 64, 80, 4, 1>(pl, p, s);
+  if (tile == 64064) return launch_cfg<PREC, 64, 64, 2, 2>(pl, p, s);
+  if (tile == 32064) return launch_cfg<PREC, 32, 64, 2, 2>(pl, p, s);
+  return srad_set_error(SRAD_ERR_ARG, "gemm: no instance for a %dx%d tile in precision %d", pl.BM, pl.BN, PREC);
 }
 
-}  // namespace
-
-int srad_gemm_tile_rows(int prec, const GemmParams& p) {      // keep in step with launch_prec
-  if (srad_conv80_supported(prec, p)) return 128;              // 4 x 32-pixel tiles of conv80_kernel
+// THE tile rule of the tiled kernel.  The problems are small (M = B*H*W rows, a few thousand), so prefer the largest tile
+// that still yields >= ~1.5 workgroups per CU.
+GemmPlan tiled_plan(int prec, const GemmParams& p) {
   auto tiles = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  if (!p.ln_g) {
-    if (p.N <= 16 && tiles(128, 16) >= 384) return 128;
-    if (p.N <= 32 && tiles(128, 32) >= 384) return 128;
-  }
-  if (p.N <= 32) return 32;
-  if (prec == SRAD_PREC_BF16 && !p.ln_g && p.N > 64 && p.N <= 80 && tiles(128, 80) >= 256) return 128;
-  if (!p.ln_g && p.N > 64 && p.N <= 80 && tiles(64, 80) >= 384) return 64;
-  if (tiles(64, 64) >= 384) return 64;
-  return 32;
+  int bm = 32, bn = 32;
+  if (!p.ln_g && p.N <= 16 && tiles(128, 16) >= 384) { bm = 128; bn = 16; }
+  else if (!p.ln_g && p.N <= 32 && tiles(128, 32) >= 384) { bm = 128; bn = 32; }
+  else if (p.N <= 32) { bm = 32; bn = 32; }
+  // N = 65..80 (DRN's 80-channel RCAB convolutions): one 80-wide tile instead of a full and a mostly empty 64-wide one ...
+  // ... and, in bf16, 128 rows per workgroup once that still gives every CU one (C3: 32768 pixels -> 256 workgroups in ONE round;
+  // the kernel is a chain of load -> LDS -> MFMA stages per workgroup, so twice the rows per stage cost little more per stage)
+  else if (prec == SRAD_PREC_BF16 && !p.ln_g && p.N > 64 && p.N <= 80 && tiles(128, 80) >= 256) { bm = 128; bn = 80; }
+  else if (!p.ln_g && p.N > 64 && p.N <= 80 && tiles(64, 80) >= 384) { bm = 64; bn = 80; }
+  else if (tiles(64, 64) >= 384) { bm = 64; bn = 64; }
+  else if (tiles(32, 64) >= 384) { bm = 32; bn = 64; }
+  GemmPlan pl{};
+  pl.family = SRAD_GEMM_TILED;
+  pl.BM = bm; pl.BN = bn;
+  pl.CONV = p.ntaps == 9 || p.stride != 1;
+  pl.LN = !pl.CONV && p.ln_g != nullptr;
+  pl.SPECIAL = p.ps == 2 || p.hsplit_hd > 0;
+  pl.CPS = gemm_cps(prec, bm, bn, pl.LN, pl.CONV);
+  pl.grid_x = (p.N + bn - 1) / bn;
+  pl.grid_y = (p.M + bm - 1) / bm;
+  pl.launches = 1;
+  return pl;
 }
 
-int srad_launch_gemm(int prec, const GemmParams& p, hipStream_t stream) {
+// what srad_launch_gemm refuses before it picks a kernel
+int gemm_check(const GemmParams& p) {
   SRAD_REQUIRE(p.M > 0 && p.N > 0 && p.Cin > 0, "gemm: empty problem M=%d N=%d Cin=%d", p.M, p.N, p.Cin);
   SRAD_REQUIRE(p.Cp == srad_cp(p.Cin), "gemm: Cp %d does not match Cin %d", p.Cp, p.Cin);
   SRAD_REQUIRE(p.ntaps == 1 || p.ntaps == 9, "gemm: ntaps must be 1 or 9 (got %d)", p.ntaps);
@@ -687,23 +695,64 @@ int srad_launch_gemm(int prec, const GemmParams& p, hipStream_t stream) {
                "gemm: activations need a channel count and row stride that are multiples of 4 floats (Cin=%d ldx=%d)", p.Cin, p.ldx);
   if (p.ntaps == 9 || p.stride != 1 || p.ps)
     SRAD_REQUIRE(p.Ho > 0 && p.Wo > 0 && p.M % (p.Ho * p.Wo) == 0, "gemm: M=%d not a multiple of Ho*Wo=%d*%d", p.M, p.Ho, p.Wo);
-  if (srad_conv80_supported(prec, p)) return srad_launch_conv80(p, stream);
-  if (prec == SRAD_PREC_BF16 && p.ps == 2 && p.N == 320 && p.Cin == 80 && p.bias && !srad_path_override(SRAD_PATH_UPCONV_ONE_GEMM)) {
-    // DRN's Upsampler conv (80 -> 320 channels + PixelShuffle(2)): four 80 -> 80 convolutions through the weight-resident kernel,
-    // one per sub-pixel position (rows 4 c + q of the pack), each writing its quarter of the 2x image - 217 us on this tiled
-    // GEMM at 128 px x 8 against 4 x 26
-    GemmParams q = p;
-    q.ps = 0; q.N = 80; q.sp_q = 0;
-    if (srad_conv80_supported(prec, q)) {
-      for (int k = 0; k < 4; ++k) { q.sp_q = k; SRAD_TRY(srad_launch_conv80(q, stream)); }
-      return SRAD_OK;
-    }
+  return SRAD_OK;
+}
+
+// one of the four 80 -> 80 convolutions DRN's Upsampler conv (80 -> 320 channels + PixelShuffle(2)) splits into: rows 4 c + q of
+// the pack through the weight-resident kernel, each writing its quarter of the 2x image - 217 us on the tiled GEMM at 128 px x 8
+// against 4 x 26
+GemmParams upconv_quarter(const GemmParams& p, int q) {
+  GemmParams r = p;
+  r.ps = 0; r.N = 80; r.sp_q = q;
+  return r;
+}
+
+// kernel family by shape and precision; the tiled kernel's plan where it falls through to that
+GemmPlan plan_of(int prec, const GemmParams& p) {
+  GemmPlan pl{};
+  pl.launches = 1;
+  if (srad_conv80_supported(prec, p)) { pl.family = SRAD_GEMM_CONV80; pl.BM = 128; pl.BN = 80; pl.CONV = 1; return pl; }   // 4 x 32-pixel tiles of conv80_kernel
+  if (prec == SRAD_PREC_BF16 && p.ps == 2 && p.N == 320 && p.Cin == 80 && p.bias && !srad_path_override(SRAD_PATH_UPCONV_ONE_GEMM) &&
+      srad_conv80_supported(prec, upconv_quarter(p, 0))) {
+    pl.family = SRAD_GEMM_CONV80X4; pl.BM = 128; pl.BN = 80; pl.CONV = 1; pl.launches = 4;
+    return pl;
   }
-  if (srad_conv_thin_supported(prec, p)) return srad_launch_conv_thin(p, stream);
-  if (srad_conv_tail_supported(prec, p)) return srad_launch_conv_tail(p, stream);
+  if (srad_conv_thin_supported(prec, p)) { pl.family = SRAD_GEMM_THIN; pl.CONV = 1; return pl; }
+  if (srad_conv_tail_supported(prec, p)) { pl.family = SRAD_GEMM_TAIL; pl.CONV = 1; return pl; }
+  return tiled_plan(prec, p);
+}
+
+}  // namespace
+
+int srad_plan_gemm(int prec, const GemmParams& p, GemmPlan* plan) {
+  SRAD_REQUIRE(plan, "gemm_plan: null argument");
+  SRAD_REQUIRE(prec == SRAD_PREC_F32 || prec == SRAD_PREC_BF16 || prec == SRAD_PREC_BF16X3, "gemm: unknown precision %d", prec);
+  SRAD_TRY(gemm_check(p));
+  *plan = plan_of(prec, p);
+  return SRAD_OK;
+}
+
+// The kernel that writes GemmParams::pool_part for p: the 80-channel conv kernel, else the tiled one (thin, tail and the
+// four-way upconv write no pool sums, and a call with pool_part set never takes them).
+int srad_gemm_tile_rows(int prec, const GemmParams& p) {
+  GemmPlan pl = plan_of(prec, p);
+  if (pl.family != SRAD_GEMM_CONV80 && pl.family != SRAD_GEMM_TILED) pl = tiled_plan(prec, p);
+  return pl.BM;
+}
+
+int srad_launch_gemm(int prec, const GemmParams& p, hipStream_t stream) {
+  SRAD_TRY(gemm_check(p));
+  const GemmPlan pl = plan_of(prec, p);
+  if (pl.family == SRAD_GEMM_CONV80) return srad_launch_conv80(p, stream);
+  if (pl.family == SRAD_GEMM_CONV80X4) {
+    for (int k = 0; k < 4; ++k) SRAD_TRY(srad_launch_conv80(upconv_quarter(p, k), stream));
+    return SRAD_OK;
+  }
+  if (pl.family == SRAD_GEMM_THIN) return srad_launch_conv_thin(p, stream);
+  if (pl.family == SRAD_GEMM_TAIL) return srad_launch_conv_tail(p, stream);
   SRAD_REQUIRE(!p.Xh && !p.Rh && (!p.Yh || p.hsplit_hd > 0), "gemm: bf16 activations in / out are the 80-channel conv kernel's (srad_conv80_supported)");
-  int rc = prec == SRAD_PREC_BF16 ? launch_prec<SRAD_PREC_BF16>(p, stream)
-           : prec == SRAD_PREC_BF16X3 ? launch_prec<SRAD_PREC_BF16X3>(p, stream) : launch_prec<SRAD_PREC_F32>(p, stream);
+  int rc = prec == SRAD_PREC_BF16 ? launch_prec<SRAD_PREC_BF16>(pl, p, stream)
+           : prec == SRAD_PREC_BF16X3 ? launch_prec<SRAD_PREC_BF16X3>(pl, p, stream) : launch_prec<SRAD_PREC_F32>(pl, p, stream);
   if (rc) return rc;
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;

@@ -13,17 +13,15 @@ extern "C" {
 //   ln_g/b : optional LayerNorm over the Cin channels of each row (eps 1e-5), ntaps = 1 only
 //   epilogue: + bias -> act (0 none, 1 GELU-erf, 2 LeakyReLU(slope), 3 ReLU) -> * alpha -> + r
 //   ps     : 0 plain rows [M][ldy] at column yoff; 2 = PixelShuffle(2) scatter
-int srad_op_gemm(int precision, const float* x, int ldx, int B, int Hi, int Wi, int Cin, const float* w, int N,
-                 int ntaps, int stride, const float* bias, const float* ln_g, const float* ln_b, int act, float slope,
-                 float alpha, const float* r, int ldr, float* y, int ldy, int yoff, int ps, void* scratch,
-                 size_t scratch_bytes, void* stream) {
+static int op_gemm_params(int precision, const float* x, int ldx, int B, int Hi, int Wi, int Cin, const float* w, int N, int ntaps,
+                          int stride, const float* bias, const float* ln_g, const float* ln_b, int act, float slope, float alpha,
+                          const float* r, int ldr, float* y, int ldy, int yoff, int ps, void* scratch, size_t scratch_bytes,
+                          GemmParams* out) {
   SRAD_REQUIRE(x && w && y && scratch, "op_gemm: null argument");
   SRAD_REQUIRE(ntaps == 1 || ntaps == 9, "op_gemm: ntaps must be 1 or 9");
   SRAD_REQUIRE(stride == 1 || stride == 2, "op_gemm: stride must be 1 or 2");
   const size_t need = srad_packed_bytes(precision, N, Cin, ntaps);
   SRAD_REQUIRE(scratch_bytes >= need, "op_gemm: scratch %zu bytes, %zu needed", scratch_bytes, need);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  SRAD_TRY(srad_launch_pack_weight(precision, w, scratch, N, Cin, ntaps, s));
   GemmParams p{};
   const int pad = ntaps == 9 ? 1 : 0, k = ntaps == 9 ? 3 : 1;
   p.Hi = Hi; p.Wi = Wi;
@@ -36,7 +34,32 @@ int srad_op_gemm(int precision, const float* x, int ldx, int B, int Hi, int Wi, 
   p.act = act; p.slope = slope; p.alpha = alpha;
   p.R = r; p.ldr = ldr; p.Y = y; p.ldy = ldy; p.yoff = yoff; p.ps = ps;
   p.hsplit_hd = 0; p.hsplit_hdp = 0;
+  *out = p;
+  return SRAD_OK;
+}
+
+int srad_op_gemm(int precision, const float* x, int ldx, int B, int Hi, int Wi, int Cin, const float* w, int N,
+                 int ntaps, int stride, const float* bias, const float* ln_g, const float* ln_b, int act, float slope,
+                 float alpha, const float* r, int ldr, float* y, int ldy, int yoff, int ps, void* scratch,
+                 size_t scratch_bytes, void* stream) {
+  GemmParams p;
+  SRAD_TRY(op_gemm_params(precision, x, ldx, B, Hi, Wi, Cin, w, N, ntaps, stride, bias, ln_g, ln_b, act, slope, alpha, r, ldr, y, ldy,
+                          yoff, ps, scratch, scratch_bytes, &p));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  SRAD_TRY(srad_launch_pack_weight(precision, w, scratch, N, Cin, ntaps, s));
   return srad_launch_gemm(precision, p, s);
+}
+
+// The plan of that call (include/srad.h): same arguments, same checks, no launch.
+int srad_op_gemm_plan(int precision, const float* x, int ldx, int B, int Hi, int Wi, int Cin, const float* w, int N,
+                      int ntaps, int stride, const float* bias, const float* ln_g, const float* ln_b, int act, float slope,
+                      float alpha, const float* r, int ldr, float* y, int ldy, int yoff, int ps, void* scratch,
+                      size_t scratch_bytes, void* stream, srad_gemm_plan* plan) {
+  (void)stream;
+  GemmParams p;
+  SRAD_TRY(op_gemm_params(precision, x, ldx, B, Hi, Wi, Cin, w, N, ntaps, stride, bias, ln_g, ln_b, act, slope, alpha, r, ldr, y, ldy,
+                          yoff, ps, scratch, scratch_bytes, &p));
+  return srad_plan_gemm(precision, p, plan);
 }
 
 // The 80 -> 80 channel 3x3 convolution with bf16 operands as DRN's bf16 chains issue it (conv80_kernel<XH, RM>): x_h [B*H*W][80]

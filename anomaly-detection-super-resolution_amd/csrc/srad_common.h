@@ -242,7 +242,11 @@ struct GemmParams {
 enum { SRAD_RMODE_ADD = 0, SRAD_RMODE_DGELU = 1, SRAD_RMODE_DLRELU = 2 };
 
 int srad_launch_gemm(int prec, const GemmParams& p, hipStream_t stream);
-int srad_gemm_tile_rows(int prec, const GemmParams& p);     // rows per workgroup tile srad_launch_gemm will pick for p
+// Kernel family, tile, K-stage depth, template variant and grid srad_launch_gemm takes for p (include/srad.h srad_gemm_plan): the
+// one place where that is decided.  srad_launch_gemm dispatches on it; srad_plan_gemm also runs the launch's argument checks.
+typedef srad_gemm_plan GemmPlan;
+int srad_plan_gemm(int prec, const GemmParams& p, GemmPlan* plan);
+int srad_gemm_tile_rows(int prec, const GemmParams& p);     // rows per workgroup tile of the kernel that writes p's pool_part
 // DRN-L's 80 -> 80 channel 3x3 convolutions: weight-resident persistent kernel (kernels_conv80.hip); srad_launch_gemm routes to it
 bool srad_conv80_supported(int prec, const GemmParams& p);
 // (stamps: the phase-stamp build, bf16 input without a residual; synchronous, medians to stderr - srad_op_conv80_h's bit 16 of rmode)

@@ -2,6 +2,7 @@
 tensors on the GPU; weights are given in PyTorch layout and packed by the library."""
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 from typing import Optional
@@ -42,13 +43,8 @@ def path_override(**paths: bool):
             L.check(lib.srad_set_path_override(ids[name], was), "set_path_override")
 
 
-def gemm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, B: int = 1, H: int = 0,
-         W: int = 0, stride: int = 1, ln: Optional[tuple] = None, act: int = L.ACT_NONE, slope: float = 0.0,
-         alpha: float = 1.0, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-         out_offset: int = 0, pixel_shuffle: bool = False, precision: str = "fp32") -> torch.Tensor:
-    """x: [rows, Cin] (row stride = x.stride(0)); weight: [N, Cin] or [N, Cin, 3, 3].
-    For a 3x3 / strided conv pass the image geometry (B, H, W) of the NHWC input rows."""
-    _need_cuda(x, weight)
+def _gemm_geometry(x, weight, B, H, W, stride, ln):
+    """The (x, w, ldx, Cin, N, ntaps, B, H, W, M) a gemm call hands to the library: channels padded to a multiple of 4."""
     assert x.dim() == 2 and (x.stride(1) == 1 or x.shape[1] == 1) and x.dtype == torch.float32
     ldx = x.stride(0) if x.shape[0] > 1 else x.shape[1]
     ntaps = 9 if weight.dim() == 4 and weight.shape[-1] == 3 else 1
@@ -68,7 +64,18 @@ def gemm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = N
         B, H, W = 1, 1, x.shape[0]
     pad, k = (1, 3) if ntaps == 9 else (0, 1)
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    M = B * Ho * Wo
+    return x, w, ldx, Cin, N, ntaps, B, H, W, B * Ho * Wo
+
+
+def gemm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, B: int = 1, H: int = 0,
+         W: int = 0, stride: int = 1, ln: Optional[tuple] = None, act: int = L.ACT_NONE, slope: float = 0.0,
+         alpha: float = 1.0, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+         out_offset: int = 0, pixel_shuffle: bool = False, precision: str = "fp32", plan_only: bool = False):
+    """x: [rows, Cin] (row stride = x.stride(0)); weight: [N, Cin] or [N, Cin, 3, 3].
+    For a 3x3 / strided conv pass the image geometry (B, H, W) of the NHWC input rows.
+    plan_only: launch nothing and return the GemmPlan of this very call (gemm_plan)."""
+    _need_cuda(x, weight)
+    x, w, ldx, Cin, N, ntaps, B, H, W, M = _gemm_geometry(x, weight, B, H, W, stride, ln)
     if out is None:
         if pixel_shuffle:
             out = torch.empty(M * 4, N // 4, dtype=torch.float32, device=x.device)
@@ -79,12 +86,49 @@ def gemm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = N
     scratch = torch.empty(nbytes + 256, dtype=torch.uint8, device=x.device)
     off = (-scratch.data_ptr()) % 256
     g, b_ = (ln if ln is not None else (None, None))
-    L.check(L.lib().srad_op_gemm(prec, L.dptr(x), ldx, B, H, W, Cin, L.dptr(w), N, ntaps, stride,
-                                 L.dptr(bias), L.dptr(g), L.dptr(b_), act, slope, alpha, L.dptr(residual),
-                                 0 if residual is None else residual.stride(0), L.dptr(out), out.stride(0),
-                                 out_offset, 2 if pixel_shuffle else 0, C.c_void_p(scratch.data_ptr() + off),
-                                 C.c_size_t(nbytes), L.current_stream_ptr()), "op_gemm")
+    args = (prec, L.dptr(x), ldx, B, H, W, Cin, L.dptr(w), N, ntaps, stride,
+            L.dptr(bias), L.dptr(g), L.dptr(b_), act, slope, alpha, L.dptr(residual),
+            0 if residual is None else residual.stride(0), L.dptr(out), out.stride(0),
+            out_offset, 2 if pixel_shuffle else 0, C.c_void_p(scratch.data_ptr() + off),
+            C.c_size_t(nbytes), L.current_stream_ptr())
+    if plan_only:
+        plan = L.GemmPlan()
+        L.check(L.lib().srad_op_gemm_plan(*args, C.byref(plan)), "op_gemm_plan")
+        return _plan_tuple(plan)
+    L.check(L.lib().srad_op_gemm(*args), "op_gemm")
     return out
+
+
+GemmPlan = collections.namedtuple("GemmPlan", "family BM BN CPS LN CONV SPECIAL grid launches")
+
+
+def _plan_tuple(p: "L.GemmPlan") -> GemmPlan:
+    return GemmPlan(L.GEMM_FAMILIES[p.family], p.BM, p.BN, p.CPS, bool(p.LN), bool(p.CONV), bool(p.SPECIAL), (p.grid_x, p.grid_y),
+                    p.launches)
+
+
+def gemm_plan(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, **kw) -> GemmPlan:
+    """The kernel family, tile, K-stage depth, template variant and grid that gemm() with the same arguments runs
+    (srad_op_gemm_plan): decided on the host, nothing is launched."""
+    return gemm(x, weight, bias, plan_only=True, **kw)
+
+
+def gemm_plan_shape(precision: str, M: int, N: int, Cin: int, *, ntaps: int = 1, stride: int = 1, B: int = 1, H: int = 0, W: int = 0,
+                    ln: bool = False, bias: bool = True, act: int = L.ACT_NONE, residual: bool = False,
+                    pixel_shuffle: bool = False) -> GemmPlan:
+    """gemm_plan from a shape alone, with aligned stand-in pointers that are never dereferenced: needs no GPU.  A row-identity
+    problem is M rows; a conv (ntaps = 9 or stride 2) is (B, H, W) input pixels and M is ignored."""
+    fake = C.c_void_p(1 << 20)
+    if ntaps == 1 and stride == 1:
+        B, H, W = 1, 1, M
+    prec = L.PRECISIONS[precision]
+    plan = L.GemmPlan()
+    L.check(L.lib().srad_op_gemm_plan(prec, fake, Cin, B, H, W, Cin, fake, N, ntaps, stride, fake if bias else None,
+                                      fake if ln else None, fake if ln else None, act, 0.0, 1.0, fake if residual else None,
+                                      N if residual else 0, fake, N // 4 if pixel_shuffle else N, 0, 2 if pixel_shuffle else 0, fake,
+                                      C.c_size_t(L.lib().srad_op_gemm_scratch_bytes(prec, N, Cin, ntaps)), None, C.byref(plan)),
+            "op_gemm_plan")
+    return _plan_tuple(plan)
 
 
 def window_attention(qkv: torch.Tensor, table: torch.Tensor, B: int, H: int, W: int, ws: int, shift: int,

@@ -499,6 +499,32 @@ int srad_op_gemm(int precision, const float* x, int ldx, int B, int Hi, int Wi, 
                  int ntaps, int stride, const float* bias, const float* ln_g, const float* ln_b, int act, float slope,
                  float alpha, const float* r, int ldr, float* y, int ldy, int yoff, int ps, void* scratch,
                  size_t scratch_bytes, void* stream);
+/* Which kernel srad_op_gemm runs for these arguments, decided on the host from shape, precision and pointers alone; launches
+ * nothing and needs no GPU (the pointers are compared with NULL and tested for alignment, never dereferenced).  Fails, with the
+ * launch's own status and message, for a problem srad_op_gemm refuses.
+ *   family : SRAD_GEMM_TILED the row-gather MFMA GEMM; SRAD_GEMM_CONV80 the weight-resident 80 -> 80 channel 3x3 kernel;
+ *            SRAD_GEMM_CONV80X4 an 80 -> 320 conv + PixelShuffle(2) as four launches of it; SRAD_GEMM_THIN / SRAD_GEMM_TAIL the
+ *            direct kernels for very few input / output channels
+ *   TILED  : BM x BN output tile per workgroup, CPS 32-wide K chunks per stage, the LayerNorm / conv-gather / special-epilogue
+ *            (PixelShuffle) template variant, and the launch grid (grid_x column tiles x grid_y row tiles)
+ *   CONV80 / CONV80X4 : BM x BN = 128 x 80 (four 32-pixel tiles x all channels per step); THIN / TAIL leave the tile fields 0.
+ *            Those kernels size their own grids: grid_x = grid_y = 0. */
+#define SRAD_GEMM_TILED 0
+#define SRAD_GEMM_CONV80 1
+#define SRAD_GEMM_CONV80X4 2
+#define SRAD_GEMM_THIN 3
+#define SRAD_GEMM_TAIL 4
+typedef struct {
+  int32_t family;            /* SRAD_GEMM_* */
+  int32_t BM, BN, CPS;
+  int32_t LN, CONV, SPECIAL; /* 0 | 1 */
+  int32_t grid_x, grid_y;
+  int32_t launches;          /* kernel launches behind the call (the weight pack not counted) */
+} srad_gemm_plan;
+int srad_op_gemm_plan(int precision, const float* x, int ldx, int B, int Hi, int Wi, int Cin, const float* w, int N,
+                      int ntaps, int stride, const float* bias, const float* ln_g, const float* ln_b, int act, float slope,
+                      float alpha, const float* r, int ldr, float* y, int ldy, int yoff, int ps, void* scratch,
+                      size_t scratch_bytes, void* stream, srad_gemm_plan* plan);
 /* WindowAttention core + cyclic shift + window partition/reverse (src/drct.py:271-302,472-506):
  * qkv [B*H*W][3][heads][hdp] (each head slice padded to hdp floats, hdp % 4 == 0) -> out [B*H*W][d] */
 int srad_op_window_attn(int precision, const float* qkv, float* out, const float* table, int B, int H, int W, int ws,

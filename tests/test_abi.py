@@ -58,6 +58,15 @@ def test_argument_errors_without_gpu():
     assert lib.srad_drn_flops(h, 1, 64, 64, C.byref(f)) == 0
     assert abs(f.value / 1e9 - 199.51) < 1.5                                     # 199.51 GFLOP / 256^2 RGB image
     lib.srad_drn_destroy(h)
+    # srad_op_gemm_plan is host code: the launcher's decision for srad_op_gemm's arguments, pointers never dereferenced
+    plan, fake = L.GemmPlan(), C.c_void_p(1 << 20)
+    args = [L.PREC_BF16, fake, 180, 1, 1, 12293, 180, fake, 100, 1, 1, fake, None, None, 0, 0.0, 1.0, None, 0, fake, 100, 0, 0, fake,
+            C.c_size_t(lib.srad_op_gemm_scratch_bytes(L.PREC_BF16, 100, 180, 1)), None]
+    assert lib.srad_op_gemm_plan(*args, C.byref(plan)) == 0
+    assert (L.GEMM_FAMILIES[plan.family], plan.BM, plan.BN, plan.CPS, plan.grid_x, plan.grid_y) == ("tiled", 64, 64, 4, 2, 193)
+    assert lib.srad_op_gemm_plan(*args, None) != 0 and b"null argument" in lib.srad_last_error()
+    args[1] = None
+    assert lib.srad_op_gemm_plan(*args, C.byref(plan)) != 0 and b"null argument" in lib.srad_last_error()
     auc = C.c_double()
     y = (C.c_int32 * 4)(0, 0, 1, 1)
     s = (C.c_double * 4)(0.1, 0.4, 0.35, 0.8)
