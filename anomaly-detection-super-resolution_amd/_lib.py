@@ -45,6 +45,19 @@ class GemmPlan(C.Structure):
 
 GEMM_FAMILIES = ("tiled", "conv80", "conv80x4", "thin", "tail")      # SRAD_GEMM_*
 
+WGRAD_PLAN_LAYERS = 6                                                # SRAD_WGRAD_PLAN_LAYERS
+
+
+class WgradPlan(C.Structure):
+    """What a weight-gradient call runs (include/srad.h srad_wgrad_plan): per launch, per layer."""
+    _fields_ = ([(n, C.c_int32) for n in ("count", "launches", "reduce_tiles", "precision")] +
+                [(n, C.c_int32 * 2) for n in ("family", "FULL", "grid")] +
+                [(n, C.c_int32) for n in ("CONV", "NT", "cpw", "nchunks")] +
+                [(n, C.c_int32 * WGRAD_PLAN_LAYERS) for n in ("launch", "ksplit", "rows_per", "tn", "tc", "XH", "YH", "blk0", "nblk")])
+
+
+WGRAD_FAMILIES = ("tile64", "w80", "conv9", "multi", "multi_hh")     # SRAD_WGRAD_FAM_*
+
 
 class ResampleTable(C.Structure):
     """One axis of srad_resize_u8 (include/srad.h srad_resample_table): the bounds on the host and the device copies."""
@@ -246,6 +259,10 @@ _SIG = {
     # backward operators
     "srad_op_wgrad": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, _P, C.c_float, _P, _P, _P, _P]),
+    "srad_op_wgrad_ex": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, _P, C.c_int] + [C.c_int] * 11 + [_P, C.c_float, _P, _P, _P, _P]),
+    "srad_op_wgrad_plan": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int] + [C.c_int] * 11 +
+                           [_P, C.POINTER(WgradPlan)]),
+    "srad_op_wgrad_deferred_plan": (C.c_int, [C.c_int, C.POINTER(WqStep), C.c_int, C.POINTER(WgradPlan)]),
     "srad_op_wgrad_workspace_bytes": (C.c_size_t, []),
     "srad_op_wgrad_queue_script": (C.c_int, [C.c_int, C.POINTER(WqStep), C.c_int, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), C.c_int, _P]),

@@ -8,7 +8,9 @@
 //   wgrad80_kernel          80 -> 80 channels, one 80 x 80 tile per tap
 //   wgrad_conv9_kernel      3x3 stride-1 C -> C convolutions (C <= 80), all nine taps per workgroup
 //   wgrad_reduce_kernel     sums a batch of queued items' partials into dW / db / column-sum destinations, fixed order
-//   plan_wgrad, launch_wgrad80, launch_wgrad_conv9, launch_wgrad, defer_wgrad, check_wgrad: split geometry, reservation, launch
+//   decide_tile64, decide_wgrad80, decide_wgrad_conv9, decide_wgrad, decide_multi: which kernel, split geometry, grid (host only)
+//   queue_partials, launch_wgrad80, launch_wgrad_conv9, launch_wgrad, defer_wgrad, check_wgrad: reservation and launch of a decision
+//   srad_plan_wgrad, srad_plan_wgrad_deferred: a decision reported instead of launched (include/srad.h srad_wgrad_plan)
 //   srad_launch_wgrad*, srad_wgrad_*: the entry points (srad_common.h), among them the column-sum reservations the LayerNorm
 //   and attention backward kernels use (srad_wgrad_reserve_colsum, srad_wgrad_queue_ln_partials)
 #include "srad_common.h"
@@ -909,63 +911,75 @@ int take(WgradQueue& q, const char* who, size_t need, int nitems, hipStream_t st
   }
 }
 
-struct WgradPlan { int tn, tc, ksplit; long tiles; float* part; };
-
-// tile / split geometry of one layer, its partial-tile workspace and its entry in the reduce batch (pending: a deferred layer's)
-template <int PREC>
-int plan_wgrad(const WgradParams& p, WgradQueue& q, hipStream_t s, WgradPlan& pl, const long wg_target = 512, const bool pending = false) {
-  pl.tn = (p.N + 63) / 64; pl.tc = (p.Cin + 63) / 64;
-  pl.tiles = (long)pl.tn * pl.tc * p.ntaps;
-  constexpr int KR = PREC == SRAD_PREC_BF16 ? 32 : 4;
-  // about two workgroups per CU for a launch of its own (wg_target 512; layers that share a launch ask for fewer,
-  // longer workgroups: less ramp, fewer partial tiles)
-  pl.ksplit = srad_wgrad_split_count<4 * KR>(p.M, pl.tiles, wg_target);
-  pl.part = nullptr;
-  if (pl.ksplit > 1) {
-    WgradRegion r;
-    SRAD_TRY(take(q, "wgrad", (size_t)pl.tiles * pl.ksplit * WG_TS, 1, s, &r));
-    pl.part = q.ws + r.off;
-    WgradReduceItem it{};
-    it.dW = p.dW; it.db = p.db; it.part = pl.part; it.n_real = p.n_real; it.cin_real = p.cin_real; it.ntaps = p.ntaps;
-    it.grp_real = p.grp_real; it.grp_pad = p.grp_pad;
-    it.tn = pl.tn; it.tc = pl.tc; it.ksplit = pl.ksplit; it.alpha = p.alpha; it.wc = 0;
-    wgrad_queue_push(q, it, (int)pl.tiles, r, pending);
-  }
-  return SRAD_OK;
-}
-
 constexpr size_t WG_LDS = (size_t)(4 * 64 * 68 + 4 * 64) * sizeof(float);
 constexpr size_t WG_LDS2 = (size_t)(2 * 64 * 68 + 4 * 64) * sizeof(float);   // wgrad_body<.., LDS2 = true>
 
-// reduce geometry of a layer whose partials are one C x C tile per tap (see wgrad_reduce_kernel): reduce tiles to add to the queue
-static int square_reduce_tiles(WgradReduceItem& it, const int C) {
+// ------------------------------------------------------------------------------------------
+// Decide first, launch second.  Which kernel a layer takes, its tiles, row splits, grid, partial-tile workspace and reduce
+// tiles are fixed here from the parameters alone, on the host; the launchers below carry a decision out and srad_plan_wgrad*
+// report it (include/srad.h srad_wgrad_plan) - the same functions, so a plan cannot drift from the launch.
+// ------------------------------------------------------------------------------------------
+struct WgradDecision {
+  int family = SRAD_WGRAD_FAM_TILE64;   // SRAD_WGRAD_FAM_TILE64 | W80 | CONV9 (a shared launch's family is decided per launch: decide_multi)
+  bool conv = false;                // tile64 / w80: the row-gather variant of the kernel
+  int tn = 1, tc = 1;               // tile64: 64-wide tiles along N / Cin
+  long tiles = 0;                   // output tiles: tn tc ntaps (tile64), ntaps (w80), 9 (conv9)
+  int ksplit = 1, rows_per = 0;     // row splits and rows of one (conv9: workgroups; its ranges are cpw chunks, not rows)
+  int grid = 0;                     // workgroups of the layer
+  int nt = 0, cpw = 0, nchunks = 0; // conv9: 16-channel sub-tiles, 4 x 32 pixel chunks per workgroup, chunks in all
+  size_t need = 0;                  // floats of partial tiles in the queue's workspace; 0: the kernel adds into dW / db itself
+  int wc = 0, rtn = 0, rtc = 0;     // the reduce item's geometry (WgradReduceItem wc, tn, tc)
+  int reduce_tiles = 0;             // reduce tiles the layer adds to the queue
+};
+
+// 64 x 64 tiles: about two workgroups per CU for a launch of its own (wg_target 512; layers that share a launch ask for fewer,
+// longer workgroups: less ramp, fewer partial tiles)
+template <int PREC>
+WgradDecision decide_tile64(const WgradParams& p, const long wg_target) {
+  constexpr int KR = PREC == SRAD_PREC_BF16 ? 32 : 4;
+  WgradDecision d;
+  d.family = SRAD_WGRAD_FAM_TILE64;
+  d.conv = p.ntaps == 9 || p.stride != 1;
+  d.tn = (p.N + 63) / 64; d.tc = (p.Cin + 63) / 64;
+  d.tiles = (long)d.tn * d.tc * p.ntaps;
+  d.ksplit = srad_wgrad_split_count<4 * KR>(p.M, d.tiles, wg_target);
+  d.rows_per = srad_wgrad_rows_per<4 * KR>(p.M, d.ksplit);
+  d.grid = (int)(d.tiles * d.ksplit);
+  if (d.ksplit > 1) {
+    d.need = (size_t)d.tiles * d.ksplit * WG_TS;
+    d.rtn = d.tn; d.rtc = d.tc; d.reduce_tiles = (int)d.tiles;
+  }
+  return d;
+}
+
+// reduce geometry of a layer whose partials are one C x C tile per tap (see wgrad_reduce_kernel)
+static void square_reduce_tiles(WgradDecision& d, const int C, const int ntaps) {
   const int cc4 = C * C / 4;
-  it.wc = C;
-  it.tn = (cc4 + 199) / 200;                      // x 4 workgroups per tap, <= 50 float4 each
-  it.tc = (cc4 + 4 * it.tn - 1) / (4 * it.tn);
-  return it.ntaps * it.tn;
+  d.wc = C;
+  d.rtn = (cc4 + 199) / 200;                      // x 4 workgroups per tap, <= 50 float4 each
+  d.rtc = (cc4 + 4 * d.rtn - 1) / (4 * d.rtn);
+  d.reduce_tiles = ntaps * d.rtn;
 }
 
 // 80 -> 80 channels, stride 1, bf16: one 80 x 80 tile per tap
-int launch_wgrad80(const WgradParams& p, WgradQueue& q, hipStream_t s) {
-  const int ksplit = srad_wgrad_split_count<128>(p.M, p.ntaps, 512);       // about two workgroups per CU
-  float* part = nullptr;
-  if (ksplit > 1) {
-    WgradRegion r;
-    SRAD_TRY(take(q, "wgrad80", (size_t)p.ntaps * ksplit * W80_PART, 1, s, &r));
-    part = q.ws + r.off;
-    WgradReduceItem it{};
-    it.dW = p.dW; it.db = p.db; it.part = part; it.n_real = 80; it.cin_real = 80; it.ntaps = p.ntaps; it.grp_real = it.grp_pad = 0;
-    it.ksplit = ksplit; it.alpha = p.alpha;
-    const int ntiles = square_reduce_tiles(it, 80);
-    wgrad_queue_push(q, it, ntiles, r);
+static bool wgrad80_supported(const WgradParams& p) {
+  return p.N == 80 && p.Cin == 80 && p.n_real == 80 && p.cin_real == 80 && p.stride == 1 && !p.row_scale &&
+         (p.ntaps == 1 || (p.Hi == p.Ho && p.Wi == p.Wo));
+}
+
+WgradDecision decide_wgrad80(const WgradParams& p) {
+  WgradDecision d;
+  d.family = SRAD_WGRAD_FAM_W80;
+  d.conv = p.ntaps == 9;
+  d.tn = d.tc = 1; d.tiles = p.ntaps;
+  d.ksplit = srad_wgrad_split_count<128>(p.M, p.ntaps, 512);       // about two workgroups per CU
+  d.rows_per = srad_wgrad_rows_per<128>(p.M, d.ksplit);
+  d.grid = p.ntaps * d.ksplit;
+  if (d.ksplit > 1) {
+    d.need = (size_t)p.ntaps * d.ksplit * W80_PART;
+    square_reduce_tiles(d, 80, p.ntaps);
   }
-  SradProfScope prof(s, SRAD_K_WGRAD, 2.0 * p.M * 80.0 * 80.0 * p.ntaps, 4.0 * p.M * 160.0 + 8.0 * 6400.0 * p.ntaps);
-  const dim3 grid((unsigned)(p.ntaps * ksplit));
-  SRAD_TRY(p.ntaps == 9 ? srad_launch_dyn<wgrad80_kernel<true>>(grid, dim3(256), W80_LDS, s, p, ksplit, part)
-                        : srad_launch_dyn<wgrad80_kernel<false>>(grid, dim3(256), W80_LDS, s, p, ksplit, part));
-  SRAD_CHECK_HIP(hipGetLastError());
-  return SRAD_OK;
+  return d;
 }
 
 // 3x3 stride-1 C -> C convolution, all nine taps per workgroup (wgrad_conv9_kernel); false: not this layer's kernel
@@ -977,33 +991,75 @@ static bool conv9_supported(const WgradParams& p) {
   return ((reinterpret_cast<uintptr_t>(p.dY) | reinterpret_cast<uintptr_t>(p.X)) & 15) == 0;
 }
 
-int launch_wgrad_conv9(const WgradParams& p, WgradQueue& q, hipStream_t s) {
-  const int C = p.N, nt = (C + 15) / 16;
+WgradDecision decide_wgrad_conv9(const WgradParams& p) {
+  WgradDecision d;
+  d.family = SRAD_WGRAD_FAM_CONV9;
+  d.conv = true;
+  const int C = p.N;
+  d.nt = p.dy_bf16 ? 5 : std::min(5, (C + 15) / 16);          // bf16 operands: 80 channels only (conv9_supported)
+  d.tn = d.tc = 1; d.tiles = 9;
   const int B = p.M / (p.Ho * p.Wo);
-  const int nchunks = B * ((p.Ho + WC9_TR - 1) / WC9_TR) * (p.Wo / WC9_TW);
+  d.nchunks = B * ((p.Ho + WC9_TR - 1) / WC9_TR) * (p.Wo / WC9_TW);
   // workgroups: a 128-pixel tile costs ~2 us, a workgroup ~6 us of ramp plus its partial tiles (9 C^2 floats written and
   // read again): ~4 sqrt(tiles) workgroups balance the two (64 for 256 tiles, 128 for 1024)
-  int ksplit = (int)(4.0 * sqrt((double)nchunks) + 0.5);
-  ksplit = std::max(1, std::min(std::min(ksplit, 256), nchunks));
-  const int cpw = (nchunks + ksplit - 1) / ksplit;
-  ksplit = (nchunks + cpw - 1) / cpw;
-  const size_t PART = (size_t)C * C + C;
-  const size_t need = 9 * (size_t)ksplit * PART;
+  int ksplit = (int)(4.0 * sqrt((double)d.nchunks) + 0.5);
+  ksplit = std::max(1, std::min(std::min(ksplit, 256), d.nchunks));
+  d.cpw = (d.nchunks + ksplit - 1) / ksplit;
+  d.ksplit = (d.nchunks + d.cpw - 1) / d.cpw;
+  d.rows_per = d.cpw * WC9_PT;
+  d.grid = d.ksplit;
+  d.need = 9 * (size_t)d.ksplit * ((size_t)C * C + C);         // always through the reduce kernel
+  square_reduce_tiles(d, C, 9);
+  return d;
+}
+
+// the kernel family of an immediate layer
+template <int PREC>
+WgradDecision decide_wgrad(const WgradParams& p) {
+  if (PREC == SRAD_PREC_BF16 && conv9_supported(p)) return decide_wgrad_conv9(p);
+  if (PREC == SRAD_PREC_BF16 && wgrad80_supported(p)) return decide_wgrad80(p);
+  return decide_tile64<PREC>(p, 512);
+}
+
+// the decision's partial-tile workspace (*part; null: none) and its entry in the reduce batch (pending: a deferred layer's)
+int queue_partials(const WgradParams& p, const WgradDecision& d, const char* who, WgradQueue& q, hipStream_t s, const bool pending,
+                   float** part) {
+  *part = nullptr;
+  if (d.need == 0) return SRAD_OK;
   WgradRegion r;
-  SRAD_TRY(take(q, "wgrad_conv9", need, 1, s, &r));
-  float* const part = q.ws + r.off;
+  SRAD_TRY(take(q, who, d.need, 1, s, &r));
+  *part = q.ws + r.off;
   WgradReduceItem it{};
-  it.dW = p.dW; it.db = p.db; it.part = part; it.n_real = C; it.cin_real = C; it.ntaps = 9; it.grp_real = it.grp_pad = 0;
-  it.ksplit = ksplit; it.alpha = p.alpha;
-  const int ntiles = square_reduce_tiles(it, C);
-  wgrad_queue_push(q, it, ntiles, r);
-  SradProfScope prof(s, SRAD_K_WGRAD, 2.0 * p.M * C * C * 9.0, (double)p.M * C * ((p.dy_bf16 ? 2 : 4) + (p.x_bf16 ? 2 : 4)) + 8.0 * 9.0 * PART * ksplit);
-  const dim3 grid((unsigned)ksplit), block(WC9S_THREADS);
+  it.dW = p.dW; it.db = p.db; it.part = *part; it.n_real = p.n_real; it.cin_real = p.cin_real; it.ntaps = p.ntaps;
+  it.grp_real = d.wc ? 0 : p.grp_real; it.grp_pad = d.wc ? 0 : p.grp_pad;
+  it.tn = d.rtn; it.tc = d.rtc; it.ksplit = d.ksplit; it.alpha = p.alpha; it.wc = d.wc;
+  wgrad_queue_push(q, it, d.reduce_tiles, r, pending);
+  return SRAD_OK;
+}
+
+int launch_wgrad80(const WgradParams& p, const WgradDecision& d, WgradQueue& q, hipStream_t s) {
+  float* part;
+  SRAD_TRY(queue_partials(p, d, "wgrad80", q, s, false, &part));
+  SradProfScope prof(s, SRAD_K_WGRAD, 2.0 * p.M * 80.0 * 80.0 * p.ntaps, 4.0 * p.M * 160.0 + 8.0 * 6400.0 * p.ntaps);
+  const dim3 grid((unsigned)d.grid);
+  SRAD_TRY(d.conv ? srad_launch_dyn<wgrad80_kernel<true>>(grid, dim3(256), W80_LDS, s, p, d.ksplit, part)
+                  : srad_launch_dyn<wgrad80_kernel<false>>(grid, dim3(256), W80_LDS, s, p, d.ksplit, part));
+  SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+int launch_wgrad_conv9(const WgradParams& p, const WgradDecision& d, WgradQueue& q, hipStream_t s) {
+  const int C = p.N, cpw = d.cpw, nchunks = d.nchunks, ksplit = d.ksplit;
+  float* part;
+  SRAD_TRY(queue_partials(p, d, "wgrad_conv9", q, s, false, &part));
+  SradProfScope prof(s, SRAD_K_WGRAD, 2.0 * p.M * C * C * 9.0,
+                     (double)p.M * C * ((p.dy_bf16 ? 2 : 4) + (p.x_bf16 ? 2 : 4)) + 8.0 * 9.0 * ((double)C * C + C) * ksplit);
+  const dim3 grid((unsigned)d.grid), block(WC9S_THREADS);
   int rc;
   if (p.dy_bf16)                                                // 80 channels only (conv9_supported): DRN's bf16 training chain
     rc = p.x_bf16 ? srad_launch_dyn<wgrad_conv9_kernel<5, true, true>>(grid, block, Wc9<5>::LDS, s, p, cpw, nchunks, ksplit, part)
                   : srad_launch_dyn<wgrad_conv9_kernel<5, true, false>>(grid, block, Wc9<5>::LDS, s, p, cpw, nchunks, ksplit, part);
-  else switch (nt) {
+  else switch (d.nt) {
     case 1: rc = srad_launch_dyn<wgrad_conv9_kernel<1>>(grid, block, Wc9<1>::LDS, s, p, cpw, nchunks, ksplit, part); break;
     case 2: rc = srad_launch_dyn<wgrad_conv9_kernel<2>>(grid, block, Wc9<2>::LDS, s, p, cpw, nchunks, ksplit, part); break;
     case 3: rc = srad_launch_dyn<wgrad_conv9_kernel<3>>(grid, block, Wc9<3>::LDS, s, p, cpw, nchunks, ksplit, part); break;
@@ -1017,19 +1073,48 @@ int launch_wgrad_conv9(const WgradParams& p, WgradQueue& q, hipStream_t s) {
 
 template <int PREC>
 int launch_wgrad(const WgradParams& p, WgradQueue& q, hipStream_t s) {
-  if (PREC == SRAD_PREC_BF16 && conv9_supported(p)) return launch_wgrad_conv9(p, q, s);
-  if (PREC == SRAD_PREC_BF16 && p.N == 80 && p.Cin == 80 && p.n_real == 80 && p.cin_real == 80 && p.stride == 1 && !p.row_scale &&
-      (p.ntaps == 1 || (p.Hi == p.Ho && p.Wi == p.Wo)))
-    return launch_wgrad80(p, q, s);
-  const bool conv = p.ntaps == 9 || p.stride != 1;
-  WgradPlan pl;
-  SRAD_TRY(plan_wgrad<PREC>(p, q, s, pl));
-  dim3 grid((unsigned)(pl.tiles * pl.ksplit));
+  const WgradDecision d = decide_wgrad<PREC>(p);
+  if (d.family == SRAD_WGRAD_FAM_CONV9) return launch_wgrad_conv9(p, d, q, s);
+  if (d.family == SRAD_WGRAD_FAM_W80) return launch_wgrad80(p, d, q, s);
+  float* part;
+  SRAD_TRY(queue_partials(p, d, "wgrad", q, s, false, &part));
+  const dim3 grid((unsigned)d.grid);
   const double K = (double)p.ntaps * p.cin_real;
   SradProfScope prof(s, SRAD_K_WGRAD, 2.0 * p.M * p.n_real * K, 4.0 * p.M * ((double)p.N + p.Cin) + 8.0 * p.n_real * K);
-  SRAD_TRY((conv ? srad_launch_dyn<wgrad_kernel<PREC, true>>(grid, dim3(256), WG_LDS, s, p, pl.ksplit, pl.tn, pl.tc, pl.part)
-                : srad_launch_dyn<wgrad_kernel<PREC, false>>(grid, dim3(256), WG_LDS, s, p, pl.ksplit, pl.tn, pl.tc, pl.part)));
+  SRAD_TRY((d.conv ? srad_launch_dyn<wgrad_kernel<PREC, true>>(grid, dim3(256), WG_LDS, s, p, d.ksplit, d.tn, d.tc, part)
+                  : srad_launch_dyn<wgrad_kernel<PREC, false>>(grid, dim3(256), WG_LDS, s, p, d.ksplit, d.tn, d.tc, part)));
   SRAD_CHECK_HIP(hipGetLastError());
+  return SRAD_OK;
+}
+
+// ---- the shared launch of up to SRAD_WGRAD_MULTI Linear layers ----
+// a deferred layer's tiles and splits: the launch is shared, so each layer asks for fewer, longer workgroups
+template <int PREC>
+WgradDecision decide_deferred(const WgradParams& p) { return decide_tile64<PREC>(p, 144); }
+
+// slot i of the shared launch: the layer's block range starts at a multiple of 8 (the XCD mapping of wgrad_body)
+void multi_put(WgradMulti& m, const int i, const WgradParams& p, const WgradDecision& d, float* part) {
+  m.p[i] = p; m.ksplit[i] = d.ksplit; m.tn[i] = d.tn; m.tc[i] = d.tc; m.part[i] = part;
+  m.blk0[i] = i == 0 ? 0 : (m.blk0[i - 1] + m.nblk[i - 1] + 7) / 8 * 8;
+  m.nblk[i] = d.grid;
+}
+
+// which kernel sends the layers of m, and with how many workgroups
+struct MultiDecision { int family; bool full; int grid; };
+int decide_multi(const int prec, const WgradMulti& m, MultiDecision& md) {
+  bool full = prec == SRAD_PREC_BF16;            // every layer: whole 128-row steps, DropPath factor constant per wave step
+  for (int i = 0; i < m.count && full; ++i) {
+    const long rows_per = srad_wgrad_rows_per<128>(m.p[i].M, m.ksplit[i]);
+    full = rows_per * m.ksplit[i] == m.p[i].M && (!m.p[i].row_scale || m.p[i].rps % 32 == 0);
+  }
+  for (int i = 0; i < m.count; ++i)
+    SRAD_REQUIRE(!(m.p[i].x_bf16 || m.p[i].dy_bf16) || (prec == SRAD_PREC_BF16 && (!m.p[i].dy_bf16 || m.p[i].x_bf16)),
+                 "wgrad: bf16 operand storage needs the bf16 MFMA path, dY only together with X");
+  bool all_hh = full;                                // every layer with both operands as bf16: the lean kernel
+  for (int i = 0; i < m.count && all_hh; ++i) all_hh = m.p[i].x_bf16 && m.p[i].dy_bf16;
+  md.family = all_hh ? SRAD_WGRAD_FAM_MULTI_HH : SRAD_WGRAD_FAM_MULTI;
+  md.full = full;
+  md.grid = m.blk0[m.count - 1] + m.nblk[m.count - 1];
   return SRAD_OK;
 }
 
@@ -1037,16 +1122,21 @@ template <int PREC>
 int defer_wgrad(const WgradParams& p, WgradQueue& q, hipStream_t s) {
   SRAD_REQUIRE(p.ntaps == 1 && p.stride == 1, "wgrad: only Linear layers can be deferred");
   if (q.multi.count == SRAD_WGRAD_MULTI) SRAD_TRY(srad_wgrad_launch_deferred(PREC, q, s));
-  WgradPlan pl;
-  SRAD_TRY(plan_wgrad<PREC>(p, q, s, pl, 144, true));      // the launch is shared by up to SRAD_WGRAD_MULTI layers; the item is pending until it goes out
-  WgradMulti& m = q.multi;
-  const int i = wgrad_queue_defer_slot(q);
-  m.p[i] = p; m.ksplit[i] = pl.ksplit; m.tn[i] = pl.tn; m.tc[i] = pl.tc; m.part[i] = pl.part;
-  m.blk0[i] = i == 0 ? 0 : (m.blk0[i - 1] + m.nblk[i - 1] + 7) / 8 * 8;
-  m.nblk[i] = (int)(pl.tiles * pl.ksplit);
+  const WgradDecision d = decide_deferred<PREC>(p);
+  float* part;
+  SRAD_TRY(queue_partials(p, d, "wgrad", q, s, true, &part));      // the item is pending until the shared launch goes out
+  multi_put(q.multi, wgrad_queue_defer_slot(q), p, d, part);
   q.multi_flops += 2.0 * p.M * p.n_real * (double)p.cin_real;
   q.multi_bytes += 4.0 * p.M * ((double)p.N + p.Cin) + 8.0 * p.n_real * (double)p.cin_real;
   return SRAD_OK;
+}
+
+// one layer's entries of a plan
+void plan_layer(srad_wgrad_plan& pl, const int i, const int launch, const WgradParams& p, const WgradDecision& d) {
+  pl.launch[i] = launch; pl.ksplit[i] = d.ksplit; pl.rows_per[i] = d.rows_per; pl.tn[i] = d.tn; pl.tc[i] = d.tc;
+  pl.XH[i] = p.x_bf16 ? 1 : 0; pl.YH[i] = p.dy_bf16 ? 1 : 0;
+  pl.nblk[i] = d.grid;
+  pl.reduce_tiles += d.reduce_tiles;
 }
 
 }  // namespace
@@ -1063,6 +1153,7 @@ int srad_wgrad_take(WgradQueue& q, const char* who, size_t need, int nitems, hip
 }
 
 static int check_wgrad(const WgradParams& p);
+static int check_wgrad_storage(int prec, const WgradParams& p);
 
 int srad_launch_wgrad_deferred(int prec, const WgradParams& p, WgradQueue& q, hipStream_t stream) {
   SRAD_TRY(check_wgrad(p));
@@ -1072,24 +1163,15 @@ int srad_launch_wgrad_deferred(int prec, const WgradParams& p, WgradQueue& q, hi
 int srad_wgrad_launch_deferred(int prec, WgradQueue& q, hipStream_t stream) {
   WgradMulti& m = q.multi;
   if (m.count == 0) return SRAD_OK;
-  const int total = m.blk0[m.count - 1] + m.nblk[m.count - 1];
+  MultiDecision md;
+  SRAD_TRY(decide_multi(prec, m, md));
   {
     SradProfScope prof(stream, SRAD_K_WGRAD, q.multi_flops, q.multi_bytes);
-    bool full = prec == SRAD_PREC_BF16;            // every layer: whole 128-row steps, DropPath factor constant per wave step
-    for (int i = 0; i < m.count && full; ++i) {
-      const long rows_per = srad_wgrad_rows_per<128>(m.p[i].M, m.ksplit[i]);
-      full = rows_per * m.ksplit[i] == m.p[i].M && (!m.p[i].row_scale || m.p[i].rps % 32 == 0);
-    }
-    for (int i = 0; i < m.count; ++i)
-      SRAD_REQUIRE(!(m.p[i].x_bf16 || m.p[i].dy_bf16) || (prec == SRAD_PREC_BF16 && (!m.p[i].dy_bf16 || m.p[i].x_bf16)),
-                   "wgrad: bf16 operand storage needs the bf16 MFMA path, dY only together with X");
-    bool all_hh = full;                                // every layer with both operands as bf16: the lean kernel
-    for (int i = 0; i < m.count && all_hh; ++i) all_hh = m.p[i].x_bf16 && m.p[i].dy_bf16;
-    const dim3 grid(total), block(256);
-    SRAD_TRY((all_hh                    ? srad_launch_dyn<wgrad_multi_hh_kernel>(grid, block, WG_LDS2, stream, m)
-             : prec != SRAD_PREC_BF16 ? srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_F32, false>>(grid, block, WG_LDS, stream, m)
-             : full                   ? srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_BF16, true>>(grid, block, WG_LDS, stream, m)
-                                      : srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_BF16, false>>(grid, block, WG_LDS, stream, m)));
+    const dim3 grid(md.grid), block(256);
+    SRAD_TRY((md.family == SRAD_WGRAD_FAM_MULTI_HH ? srad_launch_dyn<wgrad_multi_hh_kernel>(grid, block, WG_LDS2, stream, m)
+             : prec != SRAD_PREC_BF16         ? srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_F32, false>>(grid, block, WG_LDS, stream, m)
+             : md.full                        ? srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_BF16, true>>(grid, block, WG_LDS, stream, m)
+                                              : srad_launch_dyn<wgrad_multi_kernel<SRAD_PREC_BF16, false>>(grid, block, WG_LDS, stream, m)));
     SRAD_CHECK_HIP(hipGetLastError());
   }
   wgrad_queue_deferred_launched(q);
@@ -1115,9 +1197,63 @@ bool srad_wgrad_conv9_supported(const WgradParams& p) { return conv9_supported(p
 
 int srad_launch_wgrad(int prec, const WgradParams& p, WgradQueue& q, hipStream_t stream) {
   SRAD_TRY(check_wgrad(p));
+  SRAD_TRY(check_wgrad_storage(prec, p));
+  return prec == SRAD_PREC_BF16 ? launch_wgrad<SRAD_PREC_BF16>(p, q, stream) : launch_wgrad<SRAD_PREC_F32>(p, q, stream);
+}
+
+static int check_wgrad_storage(int prec, const WgradParams& p) {
   SRAD_REQUIRE((!p.x_bf16 && !p.dy_bf16) || (prec == SRAD_PREC_BF16 && conv9_supported(p)),
                "wgrad: bf16 operand storage is for deferred Linear layers and the nine-tap 80-channel convolution kernel only");
-  return prec == SRAD_PREC_BF16 ? launch_wgrad<SRAD_PREC_BF16>(p, q, stream) : launch_wgrad<SRAD_PREC_F32>(p, q, stream);
+  return SRAD_OK;
+}
+
+// What srad_launch_wgrad would launch for p: its own checks and its own decision, nothing launched or reserved.
+int srad_plan_wgrad(int prec, const WgradParams& p, srad_wgrad_plan* plan) {
+  SRAD_REQUIRE(plan, "wgrad plan: null argument");
+  SRAD_TRY(check_wgrad(p));
+  SRAD_TRY(check_wgrad_storage(prec, p));
+  const WgradDecision d = prec == SRAD_PREC_BF16 ? decide_wgrad<SRAD_PREC_BF16>(p) : decide_wgrad<SRAD_PREC_F32>(p);
+  srad_wgrad_plan pl{};
+  pl.count = 1; pl.launches = 1;
+  pl.precision = prec == SRAD_PREC_BF16 ? SRAD_PREC_BF16 : SRAD_PREC_F32;
+  pl.family[0] = d.family; pl.grid[0] = d.grid; pl.CONV = d.conv ? 1 : 0;
+  pl.NT = d.nt; pl.cpw = d.cpw; pl.nchunks = d.nchunks;
+  plan_layer(pl, 0, 0, p, d);
+  *plan = pl;
+  return SRAD_OK;
+}
+
+// The same for `count` layers given to srad_launch_wgrad_deferred one after the other and then sent (srad_wgrad_launch_deferred):
+// a layer that finds SRAD_WGRAD_MULTI waiting sends them first, so up to SRAD_WGRAD_MULTI + 1 layers make two launches.
+int srad_plan_wgrad_deferred(int prec, const WgradParams* layers, int count, srad_wgrad_plan* plan) {
+  SRAD_REQUIRE(plan && layers, "wgrad plan: null argument");
+  SRAD_REQUIRE(count > 0 && count <= SRAD_WGRAD_PLAN_LAYERS, "wgrad plan: 1 to %d deferred layers, not %d", SRAD_WGRAD_PLAN_LAYERS, count);
+  srad_wgrad_plan pl{};
+  pl.count = count;
+  pl.precision = prec == SRAD_PREC_BF16 ? SRAD_PREC_BF16 : SRAD_PREC_F32;
+  WgradMulti m{};
+  auto send = [&]() -> int {
+    MultiDecision md;
+    SRAD_TRY(decide_multi(prec, m, md));
+    pl.family[pl.launches] = md.family; pl.FULL[pl.launches] = md.full ? 1 : 0; pl.grid[pl.launches] = md.grid;
+    ++pl.launches;
+    m.count = 0;
+    return SRAD_OK;
+  };
+  for (int i = 0; i < count; ++i) {
+    const WgradParams& p = layers[i];
+    SRAD_TRY(check_wgrad(p));
+    SRAD_REQUIRE(p.ntaps == 1 && p.stride == 1, "wgrad: only Linear layers can be deferred");
+    if (m.count == SRAD_WGRAD_MULTI) SRAD_TRY(send());
+    const WgradDecision d = prec == SRAD_PREC_BF16 ? decide_deferred<SRAD_PREC_BF16>(p) : decide_deferred<SRAD_PREC_F32>(p);
+    const int slot = m.count++;
+    multi_put(m, slot, p, d, nullptr);
+    plan_layer(pl, i, pl.launches, p, d);
+    pl.blk0[i] = m.blk0[slot];
+  }
+  SRAD_TRY(send());
+  *plan = pl;
+  return SRAD_OK;
 }
 
 // queues alpha times the column sums of `rows` partial rows at `part` (inside r, whose reservation made room for the item)

@@ -410,21 +410,59 @@ int srad_bench_swin_block(const float* x, int B, int H, int W, int shift, int d,
   return SRAD_OK;
 }
 
-int srad_op_wgrad(int precision, const float* dy, int ldy, const float* x, int ldx, int B, int Hi, int Wi, int N,
-                  int Cin, int ntaps, int stride, const float* row_scale, float alpha, float* dw, float* db,
-                  void* workspace, void* stream) {
-  SRAD_REQUIRE(dy && x && dw && workspace, "op_wgrad: null argument");
-  SRAD_REQUIRE(((uintptr_t)workspace & 255) == 0, "op_wgrad: workspace must be 256-byte aligned");
-  SRAD_REQUIRE(stride == 1 || stride == 2, "op_wgrad: stride must be 1 or 2");
+// WgradParams of an op-level call, filled as the engines fill theirs (drn_wgrad, csrc/drn.hip): stored extents N / Cin, the
+// real ones of dW, the channel groups and dY's first column
+static int op_wgrad_params(const char* who, const void* dy, int ldy, int ycol0, int dy_bf16, const void* x, int ldx, int x_bf16, int B,
+                           int Hi, int Wi, int N, int Cin, int n_real, int cin_real, int grp_real, int grp_pad, int ntaps, int stride,
+                           const float* row_scale, float alpha, float* dw, float* db, WgradParams* out) {
+  SRAD_REQUIRE(dy && x && dw, "%s: null argument", who);
+  SRAD_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2", who);
   WgradParams p{};
   const int pad = ntaps == 9 ? 1 : 0, k = ntaps == 9 ? 3 : 1;
   p.Hi = Hi; p.Wi = Wi; p.Ho = (Hi + 2 * pad - k) / stride + 1; p.Wo = (Wi + 2 * pad - k) / stride + 1; p.stride = stride;
-  p.dY = dy; p.ldy = ldy; p.X = x; p.ldx = ldx; p.M = B * p.Ho * p.Wo;
-  p.N = N; p.Cin = Cin; p.n_real = N; p.cin_real = Cin; p.ntaps = ntaps;
+  p.dY = reinterpret_cast<const float*>(dy); p.ldy = ldy; p.ycol0 = ycol0; p.dy_bf16 = dy_bf16 ? 1 : 0;
+  p.X = reinterpret_cast<const float*>(x); p.ldx = ldx; p.x_bf16 = x_bf16 ? 1 : 0;
+  p.M = B * p.Ho * p.Wo;
+  p.N = N; p.Cin = Cin; p.n_real = n_real; p.cin_real = cin_real; p.grp_real = grp_real; p.grp_pad = grp_pad; p.ntaps = ntaps;
   p.row_scale = row_scale; p.rps = p.Ho * p.Wo; p.alpha = alpha; p.dW = dw; p.db = db;
+  *out = p;
+  return SRAD_OK;
+}
+
+static int op_wgrad_run(int precision, const WgradParams& p, void* workspace, void* stream) {
+  SRAD_REQUIRE(workspace, "op_wgrad: null argument");
+  SRAD_REQUIRE(((uintptr_t)workspace & 255) == 0, "op_wgrad: workspace must be 256-byte aligned");
   WgradQueue q = wgrad_queue_on(reinterpret_cast<float*>(workspace), SRAD_WGRAD_WS_BYTES / sizeof(float));
   SRAD_TRY(srad_launch_wgrad(precision, p, q, reinterpret_cast<hipStream_t>(stream)));
   return srad_wgrad_flush(q, reinterpret_cast<hipStream_t>(stream));
+}
+
+int srad_op_wgrad(int precision, const float* dy, int ldy, const float* x, int ldx, int B, int Hi, int Wi, int N,
+                  int Cin, int ntaps, int stride, const float* row_scale, float alpha, float* dw, float* db,
+                  void* workspace, void* stream) {
+  WgradParams p;
+  SRAD_TRY(op_wgrad_params("op_wgrad", dy, ldy, 0, 0, x, ldx, 0, B, Hi, Wi, N, Cin, N, Cin, 0, 0, ntaps, stride, row_scale, alpha, dw, db, &p));
+  return op_wgrad_run(precision, p, workspace, stream);
+}
+
+int srad_op_wgrad_ex(int precision, const float* dy, int ldy, int ycol0, const float* x, int ldx, int B, int Hi, int Wi, int N,
+                     int Cin, int n_real, int cin_real, int grp_real, int grp_pad, int ntaps, int stride, const float* row_scale,
+                     float alpha, float* dw, float* db, void* workspace, void* stream) {
+  WgradParams p;
+  SRAD_TRY(op_wgrad_params("op_wgrad", dy, ldy, ycol0, 0, x, ldx, 0, B, Hi, Wi, N, Cin, n_real, cin_real, grp_real, grp_pad, ntaps, stride,
+                           row_scale, alpha, dw, db, &p));
+  return op_wgrad_run(precision, p, workspace, stream);
+}
+
+// The plan of that call (include/srad.h): same parameters, same checks, no launch.  dW is not part of any decision.
+int srad_op_wgrad_plan(int precision, const void* dy, int ldy, int ycol0, int dy_bf16, const void* x, int ldx, int x_bf16, int B,
+                       int Hi, int Wi, int N, int Cin, int n_real, int cin_real, int grp_real, int grp_pad, int ntaps, int stride,
+                       const float* row_scale, srad_wgrad_plan* plan) {
+  WgradParams p;
+  float* const no_dw = reinterpret_cast<float*>(uintptr_t(256));
+  SRAD_TRY(op_wgrad_params("op_wgrad_plan", dy, ldy, ycol0, dy_bf16, x, ldx, x_bf16, B, Hi, Wi, N, Cin, n_real, cin_real, grp_real, grp_pad,
+                           ntaps, stride, row_scale, 1.f, no_dw, nullptr, &p));
+  return srad_plan_wgrad(precision, p, plan);
 }
 
 // Weight / bias gradient of the 80 -> 80 channel 3x3 convolution from bf16 operands (wgrad_conv9_kernel<5, YH, XH>, DRN's bf16
@@ -462,6 +500,32 @@ int srad_op_wgrad_deferred(int precision, const void* dy, int ldy, int dy_bf16, 
 }
 
 size_t srad_op_wgrad_workspace_bytes(void) { return SRAD_WGRAD_WS_BYTES; }
+
+// WgradParams of a SRAD_WQ_WGRAD_DEFERRED step (i: ldy dy_bf16 ldx x_bf16 M N Cin rps;  p: dy x dw db row_scale)
+static WgradParams wq_deferred_params(const srad_wq_step& t) {
+  auto F = [](const void* v) { return reinterpret_cast<const float*>(v); };
+  auto W = [](const void* v) { return const_cast<float*>(reinterpret_cast<const float*>(v)); };
+  const int32_t* a = t.i;
+  WgradParams g{};
+  g.dY = F(t.p[0]); g.ldy = a[0]; g.dy_bf16 = a[1]; g.X = F(t.p[1]); g.ldx = a[2]; g.x_bf16 = a[3]; g.M = a[4];
+  g.N = a[5]; g.Cin = a[6]; g.n_real = a[5]; g.cin_real = a[6]; g.ntaps = 1; g.stride = 1;
+  g.row_scale = F(t.p[4]); g.rps = a[7]; g.alpha = t.alpha; g.dW = W(t.p[2]); g.db = W(t.p[3]);
+  return g;
+}
+
+// The plan of a script's deferred layers (include/srad.h): the steps' own parameters, the launch's own decisions, no launch.
+int srad_op_wgrad_deferred_plan(int precision, const srad_wq_step* steps, int nsteps, srad_wgrad_plan* plan) {
+  SRAD_REQUIRE(steps && plan, "op_wgrad_deferred_plan: null argument");
+  SRAD_REQUIRE(precision == SRAD_PREC_F32 || precision == SRAD_PREC_BF16, "op_wgrad_deferred_plan: precision must be fp32 or bf16");
+  SRAD_REQUIRE(nsteps > 0 && nsteps <= SRAD_WGRAD_PLAN_LAYERS, "op_wgrad_deferred_plan: 1 to %d layers, not %d", SRAD_WGRAD_PLAN_LAYERS, nsteps);
+  WgradParams layers[SRAD_WGRAD_PLAN_LAYERS];
+  for (int i = 0; i < nsteps; ++i) {
+    SRAD_REQUIRE(steps[i].kind == SRAD_WQ_WGRAD_DEFERRED, "op_wgrad_deferred_plan: step %d is not a deferred weight gradient", i);
+    SRAD_REQUIRE(steps[i].p[0] && steps[i].p[1] && steps[i].p[2], "op_wgrad_deferred_plan: step %d: null argument", i);
+    layers[i] = wq_deferred_params(steps[i]);
+  }
+  return srad_plan_wgrad_deferred(precision, layers, nsteps, plan);
+}
 
 // A list of queue steps through ONE WgradQueue whose workspace is the first `budget_floats` floats of `workspace`: what a
 // backward pass does to the queue, at sizes where the automatic flushes happen.  Every step kind and pointer is checked before
@@ -506,11 +570,7 @@ int srad_op_wgrad_queue_script(int precision, const srad_wq_step* steps, int nst
         break;
       }
       case SRAD_WQ_WGRAD_DEFERRED: { // i: ldy dy_bf16 ldx x_bf16 M N Cin rps;  p: dy x dw db row_scale
-        WgradParams g{};
-        g.dY = F(t.p[0]); g.ldy = a[0]; g.dy_bf16 = a[1]; g.X = F(t.p[1]); g.ldx = a[2]; g.x_bf16 = a[3]; g.M = a[4];
-        g.N = a[5]; g.Cin = a[6]; g.n_real = a[5]; g.cin_real = a[6]; g.ntaps = 1; g.stride = 1;
-        g.row_scale = F(t.p[4]); g.rps = a[7]; g.alpha = t.alpha; g.dW = W(t.p[2]); g.db = W(t.p[3]);
-        SRAD_TRY(srad_launch_wgrad_deferred(precision, g, q, s));
+        SRAD_TRY(srad_launch_wgrad_deferred(precision, wq_deferred_params(t), q, s));
         break;
       }
       case SRAD_WQ_LAUNCH_DEFERRED: SRAD_TRY(srad_wgrad_launch_deferred(precision, q, s)); break;

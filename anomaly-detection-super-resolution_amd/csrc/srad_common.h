@@ -442,6 +442,10 @@ int srad_wgrad_launch_deferred(int prec, WgradQueue& q, hipStream_t stream);
 int srad_launch_wgrad(int prec, const WgradParams& p, WgradQueue& q, hipStream_t stream);
 bool srad_wgrad_conv9_supported(const WgradParams& p);   // the nine-tap kernel takes this layer (bf16 mode; the only one with bf16 conv operands)
 int srad_wgrad_flush(WgradQueue& q, hipStream_t stream);
+// what srad_launch_wgrad, resp. srad_launch_wgrad_deferred for each of `count` layers and then srad_wgrad_launch_deferred, would
+// launch (include/srad.h srad_wgrad_plan): the launchers' own checks and decisions, nothing launched, no queue touched
+int srad_plan_wgrad(int prec, const WgradParams& p, srad_wgrad_plan* plan);
+int srad_plan_wgrad_deferred(int prec, const WgradParams* layers, int count, srad_wgrad_plan* plan);
 // A region of `need` floats (*part) without an item of its own, through the queue's one reservation (wgrad_queue_reserve): when
 // the batch or the workspace is full the queue flushes itself first - with deferred layers pending only the written items -
 // and fails with an error naming `who` if the region still does not fit.  (Items are queued by kernels_wgrad.hip's launchers

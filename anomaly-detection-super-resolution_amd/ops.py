@@ -280,21 +280,109 @@ def wgrad_queue_script(steps, *, precision: str = "fp32", budget_floats: Optiona
     return [int(why[i]) for i in range(min(n.value, 64))] + [-1] * max(0, n.value - 64)
 
 
+WgradPlan = collections.namedtuple("WgradPlan", "families full grids precision conv launches reduce_tiles NT cpw nchunks layers")
+WgradLayerPlan = collections.namedtuple("WgradLayerPlan", "launch ksplit rows_per tn tc XH YH blk0 nblk")
+
+
+def _wgrad_plan_tuple(p: "L.WgradPlan") -> WgradPlan:
+    """families / full / grids: one entry per launch; layers: one WgradLayerPlan per layer, in the order given."""
+    layers = tuple(WgradLayerPlan(p.launch[i], p.ksplit[i], p.rows_per[i], p.tn[i], p.tc[i], bool(p.XH[i]), bool(p.YH[i]), p.blk0[i], p.nblk[i])
+                   for i in range(p.count))
+    n = p.launches
+    return WgradPlan(tuple(L.WGRAD_FAMILIES[p.family[j]] for j in range(n)), tuple(bool(p.FULL[j]) for j in range(n)),
+                     tuple(p.grid[j] for j in range(n)), ("fp32", "bf16")[p.precision], bool(p.CONV), n, p.reduce_tiles, p.NT, p.cpw,
+                     p.nchunks, layers)
+
+
+def _wgrad_geometry(rows: int, ntaps: int, stride: int, B: int, H: int, W: int):
+    """A Linear layer is `rows` rows, or B samples of H * W rows when the caller gives them (row_scale is per sample)."""
+    if ntaps == 1 and stride == 1 and H == 0:
+        return 1, 1, rows
+    return B, H, W
+
+
 def wgrad(dy: torch.Tensor, x: torch.Tensor, N: int, Cin: int, *, ntaps: int = 1, B: int = 1, H: int = 0, W: int = 0,
           stride: int = 1, row_scale: Optional[torch.Tensor] = None, alpha: float = 1.0, bias: bool = True,
-          precision: str = "fp32"):
-    """Weight / bias gradient of Linear (ntaps 1) or a 3x3 conv: dy [B*Ho*Wo, >=N], x [B*H*W, >=Cin] NHWC rows.
-    Returns (dW [N, Cin, ntaps], db [N] or None), freshly zeroed and accumulated into by the kernel."""
+          precision: str = "fp32", n_real: Optional[int] = None, cin_real: Optional[int] = None, grp_real: int = 0,
+          grp_pad: int = 0, ycol0: int = 0, dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None,
+          plan_only: bool = False):
+    """Weight / bias gradient of Linear (ntaps 1) or a 3x3 conv: dy [B*Ho*Wo, >= ycol0 + N], x [B*H*W, >= Cin] NHWC rows.
+    Returns (dW [n_real, cin_real, ntaps], db [n_real] or None), freshly zeroed and accumulated into by the kernel - or the
+    caller's ``dw`` / ``db`` (contiguous fp32 of that many elements, e.g. views into larger buffers), accumulated into.
+    N, Cin: the stored channel counts (multiples of 4); n_real / cin_real: the extents of dW; grp_pad > 0: x holds groups of
+    grp_pad channels with grp_real real ones each (C ABI ``srad_op_wgrad_ex``).  plan_only: launch nothing, return the WgradPlan."""
     _need_cuda(dy, x)
     assert dy.stride(1) == 1 and x.stride(1) == 1 and N % 4 == 0 and Cin % 4 == 0
-    if ntaps == 1 and stride == 1:
-        B, H, W = 1, 1, x.shape[0]
-    dw = torch.zeros(N, Cin, ntaps, dtype=torch.float32, device=x.device)
-    db = torch.zeros(N, dtype=torch.float32, device=x.device) if bias else None
-    L.check(L.lib().srad_op_wgrad(L.PRECISIONS[precision], L.dptr(dy), dy.stride(0), L.dptr(x), x.stride(0), B, H, W, N,
-                                  Cin, ntaps, stride, L.dptr(row_scale), alpha, L.dptr(dw), L.dptr(db),
-                                  wgrad_workspace(x.device), L.current_stream_ptr()), "op_wgrad")
+    B, H, W = _wgrad_geometry(x.shape[0], ntaps, stride, B, H, W)
+    n_real = N if n_real is None else n_real
+    cin_real = Cin if cin_real is None else cin_real
+    if plan_only:
+        plan = L.WgradPlan()
+        L.check(L.lib().srad_op_wgrad_plan(L.PRECISIONS[precision], L.dptr(dy), dy.stride(0), ycol0, int(dy.dtype == torch.bfloat16), L.dptr(x),
+                                           x.stride(0), int(x.dtype == torch.bfloat16), B, H, W, N, Cin, n_real, cin_real, grp_real, grp_pad,
+                                           ntaps, stride, L.dptr(row_scale), C.byref(plan)), "op_wgrad_plan")
+        return _wgrad_plan_tuple(plan)
+    if dw is None:
+        dw = torch.zeros(n_real, cin_real, ntaps, dtype=torch.float32, device=x.device)
+    if db is None and bias:
+        db = torch.zeros(n_real, dtype=torch.float32, device=x.device)
+    assert dw.is_contiguous() and dw.dtype == torch.float32 and dw.numel() == n_real * cin_real * ntaps
+    assert db is None or (db.is_contiguous() and db.dtype == torch.float32 and db.numel() == n_real)
+    L.check(L.lib().srad_op_wgrad_ex(L.PRECISIONS[precision], L.dptr(dy), dy.stride(0), ycol0, L.dptr(x), x.stride(0), B, H, W, N,
+                                     Cin, n_real, cin_real, grp_real, grp_pad, ntaps, stride, L.dptr(row_scale), alpha, L.dptr(dw),
+                                     L.dptr(db), wgrad_workspace(x.device), L.current_stream_ptr()), "op_wgrad")
     return dw, db
+
+
+def wgrad_plan(dy: torch.Tensor, x: torch.Tensor, N: int, Cin: int, **kw) -> WgradPlan:
+    """The kernel family, variant, row splits, tiles and grid that wgrad() with the same arguments runs (C ABI
+    ``srad_op_wgrad_plan``): decided on the host by the launch's own functions, nothing is launched.  bf16 ``dy`` / ``x`` plan
+    the bf16-storage kernels (wgrad_conv9_bf16)."""
+    return wgrad(dy, x, N, Cin, plan_only=True, **kw)
+
+
+def wgrad_plan_shape(precision: str, N: int, Cin: int, *, M: int = 0, ntaps: int = 1, stride: int = 1, B: int = 1, H: int = 0, W: int = 0,
+                     ldy: Optional[int] = None, ldx: Optional[int] = None, ycol0: int = 0, n_real: Optional[int] = None,
+                     cin_real: Optional[int] = None, grp_real: int = 0, grp_pad: int = 0, row_scale: bool = False, dy_bf16: bool = False,
+                     x_bf16: bool = False) -> WgradPlan:
+    """wgrad_plan from a shape alone, with aligned stand-in pointers that are never dereferenced: needs no GPU.  A Linear layer
+    is M rows (or B samples of H * W rows); a conv is (B, H, W) input pixels."""
+    fake = C.c_void_p(1 << 20)
+    B, H, W = _wgrad_geometry(M, ntaps, stride, B, H, W)
+    plan = L.WgradPlan()
+    L.check(L.lib().srad_op_wgrad_plan(L.PRECISIONS[precision], fake, ycol0 + N if ldy is None else ldy, ycol0, int(dy_bf16), fake,
+                                       Cin if ldx is None else ldx, int(x_bf16), B, H, W, N, Cin, N if n_real is None else n_real,
+                                       Cin if cin_real is None else cin_real, grp_real, grp_pad, ntaps, stride,
+                                       fake if row_scale else None, C.byref(plan)), "op_wgrad_plan")
+    return _wgrad_plan_tuple(plan)
+
+
+WGRAD_STORAGES = {"f32": (False, False), "xh": (True, False), "xh+yh": (True, True)}      # (X stored as bf16, dY stored as bf16)
+
+
+def wgrad_deferred_plan(layers, precision: str = "bf16") -> WgradPlan:
+    """The plan of 1 to 6 Linear layers queued for the shared launch one after the other and then sent (C ABI
+    ``srad_op_wgrad_deferred_plan``).  A layer is a ``wq_wgrad_deferred`` step, or a shape ``(M, N, Cin, storage, rps)`` with
+    storage one of WGRAD_STORAGES and rps the rows per row_scale entry (0: no row_scale) - that form needs no GPU."""
+    fake = 1 << 20
+    arr = (L.WqStep * len(layers))()
+    for st, layer in zip(arr, layers):
+        if len(layer) == 5:
+            M, N, Cin, storage, rps = layer
+            xh, yh = WGRAD_STORAGES[storage]
+            ints, ptrs = [N, int(yh), Cin, int(xh), M, N, Cin, rps], [fake, fake, fake, fake, fake if rps else None]
+        else:
+            kind, ints, _, tensors = layer
+            assert kind == L.WQ_WGRAD_DEFERRED
+            ptrs = [None if t is None else t.data_ptr() for t in tensors]
+        st.kind, st.alpha = L.WQ_WGRAD_DEFERRED, 1.0
+        for j, v in enumerate(ints):
+            st.i[j] = int(v)
+        for j, v in enumerate(ptrs):
+            st.p[j] = v
+    plan = L.WgradPlan()
+    L.check(L.lib().srad_op_wgrad_deferred_plan(L.PRECISIONS[precision], arr, len(layers), C.byref(plan)), "op_wgrad_deferred_plan")
+    return _wgrad_plan_tuple(plan)
 
 
 def conv80_bf16(x_h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, B: int, H: int, W: int, act: int = 0,

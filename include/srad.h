@@ -614,6 +614,42 @@ int srad_op_window_attn_bf16_in(const void* qkv_h, float* out, const float* tabl
 int srad_op_wgrad(int precision, const float* dy, int ldy, const float* x, int ldx, int B, int Hi, int Wi, int N,
                   int Cin, int ntaps, int stride, const float* row_scale, float alpha, float* dw, float* db,
                   void* workspace, void* stream);
+/* srad_op_wgrad with the extents and layout the engines give their layers: dY's columns start at ycol0 of its rows; dw is
+ * [n_real][cin_real][taps] and db [n_real] with n_real <= N, cin_real <= Cin (the stored channel counts, multiples of 4, pad
+ * columns never written); grp_pad > 0: x's channels are cin_real / grp_real groups of grp_pad stored channels holding grp_real
+ * real ones each.  row_scale [B] is per Ho*Wo output rows; a Linear layer (ntaps 1, stride 1) is B samples of Hi*Wi rows. */
+int srad_op_wgrad_ex(int precision, const float* dy, int ldy, int ycol0, const float* x, int ldx, int B, int Hi, int Wi, int N,
+                     int Cin, int n_real, int cin_real, int grp_real, int grp_pad, int ntaps, int stride, const float* row_scale,
+                     float alpha, float* dw, float* db, void* workspace, void* stream);
+/* Which weight-gradient kernel a call runs, decided on the host by the functions the launch itself uses; launches nothing and
+ * needs no GPU (pointers are compared with NULL and tested for alignment, never dereferenced).  Fails with the launch's own
+ * status and message for a problem the launch refuses.
+ *   per launch (launches <= 2): family SRAD_WGRAD_FAM_*, FULL (the mask-free body of a shared bf16 launch), grid (workgroups)
+ *   per layer (count <= SRAD_WGRAD_PLAN_LAYERS): launch (which one it rides in), ksplit row splits of rows_per rows, tn x tc
+ *       64-wide tiles (1 x 1 for the square-tile families), XH / YH operand storage, nblk workgroups from block blk0 of its launch
+ *   CONV: the row-gather variant (3x3 or strided);  conv9: NT 16-channel sub-tiles, nchunks 4 x 32 pixel chunks, cpw per
+ *       workgroup (ksplit = workgroups, rows_per = cpw * 128);  reduce_tiles: reduce tiles the call queues (0: direct stores)
+ *   srad_op_wgrad_plan          : srad_op_wgrad_ex's arguments; dy_bf16 / x_bf16 as srad_op_wgrad_conv9_h stores its operands
+ *   srad_op_wgrad_deferred_plan : the SRAD_WQ_WGRAD_DEFERRED steps of a script (below), sent by one srad_wgrad_launch_deferred at
+ *       the end - a layer that finds five waiting sends them first, so six layers are two launches */
+#define SRAD_WGRAD_FAM_TILE64 0
+#define SRAD_WGRAD_FAM_W80 1
+#define SRAD_WGRAD_FAM_CONV9 2
+#define SRAD_WGRAD_FAM_MULTI 3
+#define SRAD_WGRAD_FAM_MULTI_HH 4
+#define SRAD_WGRAD_PLAN_LAYERS 6
+typedef struct {
+  int32_t count, launches, reduce_tiles;
+  int32_t precision;         /* 0 fp32 MFMA, 1 bf16 MFMA */
+  int32_t family[2], FULL[2], grid[2];
+  int32_t CONV, NT, cpw, nchunks;
+  int32_t launch[SRAD_WGRAD_PLAN_LAYERS], ksplit[SRAD_WGRAD_PLAN_LAYERS], rows_per[SRAD_WGRAD_PLAN_LAYERS];
+  int32_t tn[SRAD_WGRAD_PLAN_LAYERS], tc[SRAD_WGRAD_PLAN_LAYERS], XH[SRAD_WGRAD_PLAN_LAYERS], YH[SRAD_WGRAD_PLAN_LAYERS];
+  int32_t blk0[SRAD_WGRAD_PLAN_LAYERS], nblk[SRAD_WGRAD_PLAN_LAYERS];
+} srad_wgrad_plan;
+int srad_op_wgrad_plan(int precision, const void* dy, int ldy, int ycol0, int dy_bf16, const void* x, int ldx, int x_bf16, int B,
+                       int Hi, int Wi, int N, int Cin, int n_real, int cin_real, int grp_real, int grp_pad, int ntaps, int stride,
+                       const float* row_scale, srad_wgrad_plan* plan);
 /* The 80 -> 80 channel 3x3 convolution (src/drn.py:143-158, RCAB) with bf16 operands, as DRN's bf16 chains issue it in the
  * forward and as the data gradient of the backward: x_h [B*H*W][80] bf16; w [80][80][3][3] fp32; output bf16 (y_h) or fp32 (y);
  * residual operand bf16 (r_h) or fp32 (r) or neither; rmode 0 = add, 2 = multiply by (r > 0 ? 1 : slope) (backward through
@@ -658,6 +694,8 @@ typedef struct {
 } srad_wq_step;
 int srad_op_wgrad_queue_script(int precision, const srad_wq_step* steps, int nsteps, size_t budget_floats, void* workspace,
                                size_t workspace_bytes, int* n_reduce, int* why, int why_cap, void* stream);
+/* srad_wgrad_plan (above) of a script of 1 to SRAD_WGRAD_PLAN_LAYERS SRAD_WQ_WGRAD_DEFERRED steps */
+int srad_op_wgrad_deferred_plan(int precision, const srad_wq_step* steps, int nsteps, srad_wgrad_plan* plan);
 /* Data gradient dx = (dy . w) * alpha * row_scale (* gelu'(r) if rmode 1, * lrelu'(r) if rmode 2), stride 1:
  * the forward GEMM on the transposed pack of w [N][Cin][taps]; scratch >= srad_op_gemm_scratch_bytes(p, Cin, N, taps) */
 int srad_op_dgrad(int precision, const float* dy, int ldy, int B, int H, int W, int N, const float* w, int Cin,

@@ -67,6 +67,30 @@ def test_argument_errors_without_gpu():
     assert lib.srad_op_gemm_plan(*args, None) != 0 and b"null argument" in lib.srad_last_error()
     args[1] = None
     assert lib.srad_op_gemm_plan(*args, C.byref(plan)) != 0 and b"null argument" in lib.srad_last_error()
+    # srad_op_wgrad_plan / srad_op_wgrad_deferred_plan: the weight-gradient launchers' decisions, host code as well
+    wp = L.WgradPlan()
+    wargs = [L.PREC_BF16, fake, 84, 0, 0, fake, 84, 0, 1, 17, 23, 80, 80, 80, 80, 0, 0, 9, 1, None]
+    assert lib.srad_op_wgrad_plan(*wargs, C.byref(wp)) == 0
+    assert (L.WGRAD_FAMILIES[wp.family[0]], wp.CONV, wp.launches, wp.ksplit[0], wp.rows_per[0], wp.grid[0]) == ("w80", 1, 1, 2, 256, 18)
+    wargs[0] = L.PREC_F32
+    assert lib.srad_op_wgrad_plan(*wargs, C.byref(wp)) == 0 and L.WGRAD_FAMILIES[wp.family[0]] == "tile64" and (wp.tn[0], wp.tc[0]) == (2, 2)
+    assert lib.srad_op_wgrad_plan(*wargs, None) != 0 and b"null argument" in lib.srad_last_error()
+    wargs[1] = None
+    assert lib.srad_op_wgrad_plan(*wargs, C.byref(wp)) != 0 and b"null argument" in lib.srad_last_error()
+    st = L.WqStep()
+    st.kind = L.WQ_WGRAD_DEFERRED
+    for j, v in enumerate([180, 0, 180, 1, 1000, 180, 180, 0]):
+        st.i[j] = v
+    for j in range(3):
+        st.p[j] = 1 << 20
+    assert lib.srad_op_wgrad_deferred_plan(L.PREC_BF16, C.byref(st), 1, C.byref(wp)) == 0
+    assert (L.WGRAD_FAMILIES[wp.family[0]], wp.FULL[0], wp.XH[0], wp.YH[0], wp.ksplit[0], wp.nblk[0]) == ("multi", 0, 1, 0, 4, 36)
+    st.kind = L.WQ_WGRAD
+    assert lib.srad_op_wgrad_deferred_plan(L.PREC_BF16, C.byref(st), 1, C.byref(wp)) != 0 and b"not a deferred" in lib.srad_last_error()
+    assert lib.srad_op_wgrad_deferred_plan(L.PREC_BF16, None, 1, C.byref(wp)) != 0
+    # srad_op_wgrad_ex checks before it launches: real extents beyond the stored ones are refused without a device
+    assert lib.srad_op_wgrad_ex(L.PREC_F32, fake, 8, 0, fake, 8, 1, 1, 16, 4, 4, 5, 4, 0, 0, 1, 1, None, 1.0, fake, None, fake, None) != 0
+    assert b"bad real extents" in lib.srad_last_error()
     auc = C.c_double()
     y = (C.c_int32 * 4)(0, 0, 1, 1)
     s = (C.c_double * 4)(0.1, 0.4, 0.35, 0.8)

@@ -53,7 +53,10 @@ def test_wgrad_linear(dev, prec, M, K, N):
 @pytest.mark.parametrize("M,N,K", [(2048, 540, 180), (1024, 180, 360), (2048, 32, 180), (1024, 360, 244), (3072, 128, 64), (1536, 180, 180)])
 def test_wgrad_linear_deferred(dev, storage, M, N, K):
     """The training step's route (queue -> one deferred launch -> reduce), with the operands as fp32, X as bf16, or both as
-    bf16 with dY pre-multiplied by its per-sample factor; whole 128-row steps (mask-free path) and not (M = 1536 ... )."""
+    bf16 with dY pre-multiplied by its per-sample factor.  By the launcher's plan (ops.wgrad_deferred_plan, asserted in
+    tests/test_wgrad_ref_host.py) all six shapes are whole 128-row steps - M = 1536 is four splits of 384 rows - with rps = 256:
+    the mask-free body every time, on the lean all-bf16 kernel for xh_yh.  The masked bodies are tested in
+    tests/test_gpu_wgrad_paths.py."""
     from srad_amd import ops
     g = torch.Generator().manual_seed(M + N + K)
     dy = torch.randn(M, N, generator=g).to(dev)
