@@ -70,6 +70,13 @@ class ResampleTableF(C.Structure):
     _fields_ = ResampleTable._fields_
 
 
+class TileGeom(C.Structure):
+    """The cover of an LR image with tiles (include/srad.h srad_tile_geom)."""
+    _fields_ = [(n, C.c_int32) for n in ("h", "w", "tile", "overlap", "granule", "scale", "ph", "pw", "ty", "tx", "stride", "ny", "nx")]
+
+
+TILE_BLENDS = {"mean": 0, "feather": 1}                              # SRAD_TILE_BLEND_*
+
 RESAMPLE_FILTERS = {"lanczos": 0, "bicubic": 1}
 RESAMPLE_FILTERS_F = dict(RESAMPLE_FILTERS, bilinear=2)      # the float32 resize takes BILINEAR too
 
@@ -152,6 +159,11 @@ _SIG = {
     # self-ensemble x8
     "srad_ensemble_inputs": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "srad_ensemble_mean": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    # tiled inference
+    "srad_tile_plan": (C.c_int, [C.c_int] * 6 + [C.POINTER(TileGeom)]),
+    "srad_tile_origins": (C.c_int, [C.POINTER(TileGeom), _P, _P]),
+    "srad_tile_gather": (C.c_int, [_P] + [C.c_int] * 7 + [_P, _P]),
+    "srad_tile_blend": (C.c_int, [_P] + [C.c_int] * 9 + [_P, _P]),
     # 8-bit resize (PIL-exact)
     "srad_resample_ksize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "srad_resample_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -23,7 +23,7 @@ import torch
 
 from . import metrics as M
 from .model import Model
-from .options import build_opt, parse_eval_args
+from .options import build_opt, parse_eval_args, set_tile_opt, tile_suffix
 
 
 def infer_from_run_dir(run_dir: str) -> dict:
@@ -455,8 +455,10 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
                auc_psnr=M.roc_auc(y_true, -full[:, -1]), n_images=len(pairs), window_sizes=sizes)
     if self_ensemble:
         out["self_ensemble"] = True
+    if getattr(model, 'tile', 0):                             # tiled inference is the model's own setting (Model.forward_tiled)
+        out["tile"] = [int(model.tile), int(model.tile_overlap), str(model.tile_blend)]
     print(f"Test AUCs - SSIM(best ws={best_ws}): {out['auc_ssim']:.4f}, MSE: {out['auc_mse']:.4f}, PSNR: {out['auc_psnr']:.4f}"
-          + (" (self-ensemble x8)" if self_ensemble else ""))
+          + (" (self-ensemble x8)" if self_ensemble else "") + tile_suffix(model))
     if want.pr:                                               # the AUCs' score orientation: 1 - SSIM at best_ws, MSE, -PSNR
         cols = (("ssim", 1.0 - full[:, best_j]), ("mse", full[:, -2]), ("psnr", -full[:, -1]))
         pr = {k: M.average_precision(y_true, s) for k, s in cols}
@@ -664,7 +666,13 @@ def _run(args):
     opt = build_opt(model_type, class_name, resolution, scale, args.batch_size, args.dtype, pre_train=ckpt,
                     data_root=args.data_root)
     opt.test_only = True
-    model = Model(opt, None, dual_model=(model_type == 'drn-l'))
+    set_tile_opt(opt, args)
+    try:
+        model = Model(opt, None, dual_model=(model_type == 'drn-l'))
+    except ValueError as e:                                   # a tile setting the network cannot take (not a multiple of its window)
+        if not getattr(args, 'tile', 0):
+            raise
+        raise SystemExit(f"--tile {args.tile} --tile-overlap {args.tile_overlap}: {e}")
     g = list(iter_split(opt.data_root, class_name, 'good', opt.scale, opt.n_colors))
     b = list(iter_split(opt.data_root, class_name, 'bad', opt.scale, opt.n_colors))
     out_dir = args.output_dir or (os.path.join(args.run_dir, 'eval_results') if args.run_dir else './workspace/eval_results')

@@ -16,7 +16,7 @@ import random
 import sys
 import time
 
-from .options import DRCT, DRN, parse_train_args, setup_opt_drct, setup_opt_drn
+from .options import DRCT, DRN, parse_train_args, set_tile_opt, setup_opt_drct, setup_opt_drn
 
 
 def set_seed(seed: int) -> None:
@@ -107,6 +107,7 @@ def build_train_opt(args):
     opt.precision = args.dtype
     opt.data_root = data_root
     opt.self_ensemble = bool(getattr(args, 'self_ensemble', False))
+    set_tile_opt(opt, args)                                      # only with --tile: a run without it writes today's config.txt
     if getattr(args, 'ema_decay', None) is not None:
         opt.ema_decay = float(args.ema_decay)
     if getattr(args, 'ema', False):                              # only then: a run without it writes today's config.txt

@@ -40,6 +40,11 @@ class Model(nn.Module):
         self.scale = opt.scale
         self.idx_scale = 0
         self.self_ensemble = getattr(opt, 'self_ensemble', False)
+        # tiled inference (DESIGN.md "Tiled inference"): off at tile 0; tile_batch = tiles per network call, 0 = by the tile's size
+        self.tile = int(getattr(opt, 'tile', 0) or 0)
+        self.tile_overlap = int(getattr(opt, 'tile_overlap', 0) or 0)
+        self.tile_blend = getattr(opt, 'tile_blend', 'mean') or 'mean'
+        self.tile_batch = 0
         self.cpu = getattr(opt, 'cpu', False)
         if self.cpu:
             raise RuntimeError("--device cpu: this build runs the SR path on the HIP engine only; the CPU path is "
@@ -55,6 +60,14 @@ class Model(nn.Module):
             self.dual_models = []
             for _ in self.opt.scale:
                 self.dual_models.append(DownBlock(opt, 2).to(self.device))
+        if self.tile:                                         # refused before anything runs: a ValueError names the setting
+            from . import ops
+            if self.tile_blend not in ('mean', 'feather'):
+                raise ValueError(f"tile_blend {self.tile_blend!r}: one of 'mean', 'feather'")
+            scales = opt.scale if isinstance(opt.scale, (list, tuple)) else [opt.scale]
+            ops.tile_plan(1, 1, self.tile, self.tile_overlap, self.model.granule, max(int(s) for s in scales))
+        elif self.tile_overlap or self.tile_blend != 'mean':
+            raise ValueError("tile_overlap / tile_blend are settings of tiled inference: set tile > 0")
         self.load(getattr(opt, 'pre_train', '.'), getattr(opt, 'pre_train_dual', '.'), cpu=False)
         if not getattr(opt, 'test_only', False) and getattr(ckp, 'log_file', None) is not None:
             print(self.model, file=ckp.log_file)
@@ -67,7 +80,30 @@ class Model(nn.Module):
         self.idx_scale = idx_scale
         if self.self_ensemble and not self.training:
             return self.forward_x8(x)
+        if self.tile > 0 and not self.training:
+            return self.forward_tiled(x)
         return self.model(x)
+
+    def forward_tiled(self, x):
+        """The network over overlapping tiles of ``x`` [B,C,h,w] (DESIGN.md "Tiled inference"; ``--tile`` / ``--tile_overlap`` of
+        the public DRCT and SwinIR test scripts): the cover of ``ops.tile_plan`` for (h, w), ``tile``, ``tile_overlap`` and the
+        network's granule, the tiles cut by one launch, the network on ``tile_batch`` tiles at a time (the last chunk may be
+        smaller), one blend launch per output.  A list of outputs (DRN-L) is blended output by output, each at its own scale
+        ``out.shape[2] // tile height``.  Any h, w >= 1.  Inference only: the result carries no graph."""
+        from . import ops
+        from .evaluate import _auto_batch
+        g = self.model.granule
+        h, w = x.shape[-2:]
+        tiles = ops.tile_gather(x, self.tile, self.tile_overlap, g)
+        ty, tx = tiles.shape[-2:]
+        step = self.tile_batch if self.tile_batch > 0 else _auto_batch(ty, tx, False)
+        ys = [self.model(tiles[i:i + step]) for i in range(0, tiles.shape[0], step)]
+        many = isinstance(ys[0], (list, tuple))
+        outs = []
+        for per_out in zip(*(y if many else [y] for y in ys)):
+            y = per_out[0] if len(per_out) == 1 else torch.cat(per_out)
+            outs.append(ops.tile_blend(y, h, w, self.tile, self.tile_overlap, g, y.shape[2] // ty, self.tile_blend))
+        return outs if many else outs[0]
 
     def forward_x8(self, x):
         """Self-ensemble x8 (DESIGN.md "Self-ensemble"; ``forward_x8`` of the EDSR / DRN code the reference descends from):
@@ -76,7 +112,8 @@ class Model(nn.Module):
         4..7 as [4B,C,W,H].  A list of outputs (DRN-L) is ensembled output by output.  Inference only: the result carries no
         graph."""
         from . import ops
-        ys = [self.model(b) for b in ops.ensemble_batches(x)]
+        net = self.forward_tiled if self.tile > 0 and not self.training else self.model      # each member tiled with its own plan
+        ys = [net(b) for b in ops.ensemble_batches(x)]
         many = isinstance(ys[0], (list, tuple))
         outs = []
         for per_batch in zip(*(y if many else [y] for y in ys)):

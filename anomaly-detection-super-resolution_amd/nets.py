@@ -452,6 +452,7 @@ class DRCT(_EngineModule):
             raise ValueError("only resi_connection='1conv' is supported")
         self.cfg = cfg
         self.window_size = cfg.window_size
+        self.granule = cfg.window_size          # what the input's H and W must be multiples of (tiled inference pads to it)
         self.upscale = cfg.upscale
         self.img_range = cfg.img_range
         self.drop_path_rate = float(getattr(opt, "drop_path_rate", 0.1))      # src/drct.py:736
@@ -607,6 +608,7 @@ class DRN(_EngineModule):
         self.cfg = cfg
         self.scale = list(scales)
         self.phase = cfg.phase
+        self.granule = 1                        # any input size
         prec = precision or getattr(opt, "precision", "fp32")
         graph = getattr(opt, "use_graph", True) if use_graph is None else use_graph
         self._init_engine(S.drn_spec(cfg), cfg, prec, graph)

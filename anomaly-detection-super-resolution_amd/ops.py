@@ -763,6 +763,67 @@ def ensemble_mean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------- tiled inference
+TilePlan = collections.namedtuple("TilePlan", "h w tile overlap granule scale ph pw ty tx stride ny nx oy ox")
+TilePlan.__doc__ = """The cover of an LR image [h, w] with tiles (include/srad.h ``srad_tile_geom`` + the origins): padded extents
+ph x pw, tile extents ty x tx, ny x nx tiles at the origins oy / ox, numbered row-major."""
+
+
+def tile_plan(h: int, w: int, tile: int, overlap: int = 0, granule: int = 1, scale: int = 1) -> TilePlan:
+    """The tile cover both kernels use (``srad_tile_plan``; host only, needs no GPU).  ValueError for what the library refuses:
+    tile < 1, overlap outside [0, tile), tile % granule != 0, overlap * scale > 4094."""
+    g = L.TileGeom()
+    if L.lib().srad_tile_plan(int(h), int(w), int(tile), int(overlap), int(granule), int(scale), C.byref(g)):
+        raise ValueError(L.lib().srad_last_error().decode())
+    oy, ox = (C.c_int32 * g.ny)(), (C.c_int32 * g.nx)()
+    L.check(L.lib().srad_tile_origins(C.byref(g), oy, ox), "tile_origins")
+    return TilePlan(*[getattr(g, n) for n, _ in L.TileGeom._fields_], tuple(oy), tuple(ox))
+
+
+def _tile_arg(t: torch.Tensor, what: str) -> torch.Tensor:
+    _need_cuda(t)
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise ValueError(f"{what}: expected a 4-d fp32 tensor, got {tuple(t.shape)} {t.dtype}")
+    return t.detach()
+
+
+def tile_gather(x: torch.Tensor, tile: int, overlap: int = 0, granule: int = 1) -> torch.Tensor:
+    """x [B,C,h,w] -> its tiles [B*ny*nx, C, ty, tx] under ``tile_plan(h, w, tile, overlap, granule)``, the symmetric padding
+    included (``srad_tile_gather``): a pure copy."""
+    x = _tile_arg(x, "tile_gather")
+    B, Cc, h, w = x.shape
+    plan = tile_plan(h, w, tile, overlap, granule)            # its refusals come before any GPU work
+    x = x.contiguous()
+    tiles = torch.empty(B * plan.ny * plan.nx, Cc, plan.ty, plan.tx, dtype=torch.float32, device=x.device)
+    L.check(L.lib().srad_tile_gather(L.dptr(x), B, Cc, h, w, int(tile), int(overlap), int(granule), L.dptr(tiles), L.current_stream_ptr()),
+            "tile_gather")
+    return tiles
+
+
+def tile_blend(y: torch.Tensor, h: int, w: int, tile: int, overlap: int = 0, granule: int = 1, scale: int = 1, mode: str = "mean",
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [B*ny*nx, C, ty*scale, tx*scale], the network's outputs for the tiles of an [B,C,h,w] batch -> [B,C,h*scale,w*scale]
+    (``srad_tile_blend``): every pixel the mean ('mean') or the feathered mean ('feather') of the tiles that cover it, summed
+    in tile order in fp32."""
+    if mode not in L.TILE_BLENDS:
+        raise ValueError(f"tile_blend: mode {mode!r}: one of {sorted(L.TILE_BLENDS)}")
+    plan = tile_plan(h, w, tile, overlap, granule, scale)
+    y = _tile_arg(y, "tile_blend").contiguous()
+    n, Cc = y.shape[:2]
+    per = plan.ny * plan.nx
+    if n % per or tuple(y.shape[2:]) != (plan.ty * scale, plan.tx * scale):
+        raise ValueError(f"tile_blend: {tuple(y.shape)} is not a batch of {plan.ny} x {plan.nx} tiles of "
+                         f"{plan.ty * scale} x {plan.tx * scale} per image")
+    B = n // per
+    if out is None:
+        out = torch.empty(B, Cc, h * scale, w * scale, dtype=torch.float32, device=y.device)
+    elif tuple(out.shape) != (B, Cc, h * scale, w * scale) or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"tile_blend: out must be a contiguous fp32 GPU tensor of shape {(B, Cc, h * scale, w * scale)}")
+    L.check(L.lib().srad_tile_blend(L.dptr(y), B, Cc, int(h), int(w), int(tile), int(overlap), int(granule), int(scale),
+                                    L.TILE_BLENDS[mode], L.dptr(out), L.current_stream_ptr()), "tile_blend")
+    return out
+
+
 # ----------------------------------------------------------------------------------- 8-bit resize, equal to PIL.Image.resize
 def resample_coeffs(in_size: int, out_size: int, filter: str = "lanczos"):
     """(ksize, bounds int32 [out, 2], coeffs int32 [out, ksize]) of one axis as numpy arrays (``srad_resample_coeffs``; host

@@ -210,8 +210,10 @@ def parse_train_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument('--skip-nonfinite', action='store_true', default=False,
                    help="drop every optimizer step whose gradients hold an inf or a NaN (what the reference's GradScaler.step did): "
                         "weights, moments and the weight average keep their bits and the bias correction counts applied steps")
+    add_tile_args(p)                                          # test time only, like --self-ensemble
     _with_config(p, pre_args)
     args = p.parse_args(argv)
+    check_tile_args(p, args)
     if args.ema_decay is not None:                            # a value from a config file gets the command line's check
         try:
             args.ema_decay = _ema_decay(str(args.ema_decay))
@@ -223,6 +225,63 @@ def parse_train_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         except (argparse.ArgumentTypeError, ValueError) as e:
             p.error(f"argument --grad-clip: {e}")
     return args
+
+
+def _nonnegative_int(text: str) -> int:
+    try:
+        v = int(text)
+    except ValueError:
+        v = -1
+    if v < 0:
+        raise argparse.ArgumentTypeError(f"{text!r} is not an integer >= 0")
+    return v
+
+
+TILE_BLENDS = ('mean', 'feather')
+
+
+def add_tile_args(p: argparse.ArgumentParser) -> None:
+    """--tile / --tile-overlap / --tile-blend (DESIGN.md "Tiled inference"), the same three in every parser; all off by default."""
+    p.add_argument('--tile', type=_nonnegative_int, default=0, metavar='T',
+                   help="tiled inference (--tile of the public DRCT / SwinIR test scripts): cover every LR image with overlapping "
+                        "T x T tiles, super-resolve the tiles and blend the overlaps; any image size, bounded memory; 0 = whole "
+                        "images (for DRCT, T must be a multiple of the window size)")
+    p.add_argument('--tile-overlap', type=_nonnegative_int, default=None, metavar='O',
+                   help="LR pixels neighbouring tiles share, in [0, T); default 0 (with --tile)")
+    p.add_argument('--tile-blend', type=str, default=None, choices=list(TILE_BLENDS),
+                   help="how overlaps are combined: the plain mean of the covering tiles (the public scripts' rule, the default) "
+                        "or a feathered mean whose weights fall off towards each tile's edge (with --tile)")
+
+
+def check_tile_args(p: argparse.ArgumentParser, args: argparse.Namespace) -> None:
+    """The checks of the three flags, for values from a config file too; fills the defaults of the two that belong to --tile."""
+    try:
+        args.tile = _nonnegative_int(str(args.tile))
+        if args.tile_overlap is not None:
+            args.tile_overlap = _nonnegative_int(str(args.tile_overlap))
+    except argparse.ArgumentTypeError as e:
+        p.error(f"argument --tile / --tile-overlap: {e}")
+    if args.tile_blend is not None and args.tile_blend not in TILE_BLENDS:
+        p.error(f"argument --tile-blend: invalid choice: {args.tile_blend!r} (choose from 'mean', 'feather')")
+    if not args.tile and (args.tile_overlap is not None or args.tile_blend is not None):
+        p.error("--tile-overlap and --tile-blend belong to --tile: give it too")
+    args.tile_overlap = 0 if args.tile_overlap is None else args.tile_overlap
+    args.tile_blend = 'mean' if args.tile_blend is None else args.tile_blend
+    if args.tile and args.tile_overlap >= args.tile:
+        p.error(f"argument --tile-overlap: {args.tile_overlap} is not below the tile size {args.tile}")
+
+
+def set_tile_opt(opt, args) -> None:
+    """Carries the parsed tile setting to the option object the Model reads - only when it is on, so a run without the flags
+    builds (and writes, config.txt) the option object it always did."""
+    if getattr(args, 'tile', 0):
+        opt.tile, opt.tile_overlap, opt.tile_blend = int(args.tile), int(args.tile_overlap), str(args.tile_blend)
+
+
+def tile_suffix(model) -> str:
+    """' (tiles T/O blend)' for a model that tiles, '' otherwise: what the summary lines append."""
+    t = int(getattr(model, 'tile', 0) or 0)
+    return f" (tiles {t}/{int(model.tile_overlap)} {model.tile_blend})" if t else ""
 
 
 def _grad_clip(text: str) -> float:
@@ -370,8 +429,10 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                         "one pixel), in [0, 1]; default 0 (with --region-metrics)")
     p.add_argument('--save-regions', action='store_true', default=False,
                    help="write <output-dir>/regions.csv: one row per predicted region (with --region-metrics)")
+    add_tile_args(p)
     _with_config(p, pre_args)
     args = p.parse_args(argv)
+    check_tile_args(p, args)
     if args.ema and args.checkpoint:
         p.error("--ema and --checkpoint exclude each other (an explicit file is already a choice)")
     if args.region_metrics and args.threshold is None and args.threshold_fpr is None:

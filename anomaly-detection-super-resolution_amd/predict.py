@@ -34,7 +34,8 @@ from . import metrics as M
 from . import ops
 from .data import rgb2y, set_channel
 from .evaluate import MapSpec, _with_window, infer_from_run_dir, resolve_checkpoint, save_anomaly_maps, save_masks, save_sr_image, super_resolve_dev
-from .options import _finite_or_inf_float, _map_scales, _nonnegative_float, _open_unit_float, _positive_int, build_opt
+from .options import (_finite_or_inf_float, _map_scales, _nonnegative_float, _open_unit_float, _positive_int, add_tile_args, build_opt,
+                      check_tile_args, tile_suffix)
 
 OPERATING_POINT_FILE = 'operating_point.json'
 OPERATING_POINT_VERSION = 1
@@ -111,7 +112,9 @@ def check_spec(spec: MapSpec) -> MapSpec:
 
 class Detector:
     """A model, a map spec and (once calibrated or given) a threshold.  ``hr_size``: the side the model's HR images have
-    (default ``opt.patch_size``); scale, ``n_colors`` and ``rgb_range`` come from ``opt``.  ``overlay_alpha`` (0..255, the
+    (default ``opt.patch_size``), or ``(H, W)`` for a rectangular frame - every source is resized to it, the LR images are
+    ``(H // scale, W // scale)``, and a model that tiles (``Model.tile``) takes any such frame; scale, ``n_colors`` and
+    ``rgb_range`` come from ``opt``.  ``overlay_alpha`` (0..255, the
     ``alpha_max`` of ``heat_lut``) and ``overlay_contour`` (0..4) shape the overlays ``predict(..., overlays=True)`` draws."""
 
     def __init__(self, opt, model, spec: MapSpec, threshold: Optional[float] = None, min_area: int = 1, self_ensemble: bool = False,
@@ -122,13 +125,19 @@ class Detector:
         if not float(overlay_contour).is_integer() or not 0 <= overlay_contour <= 4:
             raise ValueError(f"predict: overlay_contour = {overlay_contour!r}, must be an integer in 0..4")
         self.overlay_contour, self._lut = int(overlay_contour), None
-        self.hr_size = int(hr_size or opt.patch_size)
+        if isinstance(hr_size, (tuple, list)):                # a rectangular frame (H, W)
+            if len(hr_size) != 2:
+                raise ValueError(f"predict: hr_size = {hr_size!r}, must be a side or (H, W)")
+            self.frame = (int(hr_size[0]), int(hr_size[1]))
+        else:
+            self.frame = (int(hr_size or opt.patch_size),) * 2
+        self.hr_size = self.frame[0] if self.frame[0] == self.frame[1] else self.frame
         self.scale = int(opt.scale[-1] if isinstance(opt.scale, (list, tuple)) else opt.scale)
         self.n_colors, self.rgb_range = int(opt.n_colors), float(opt.rgb_range)
-        if self.hr_size // self.scale < 1:
+        if min(self.frame) // self.scale < 1:
             raise ValueError(f"predict: HR size {self.hr_size} is below the scale {self.scale}")
-        lr = self.hr_size // self.scale
-        self.spec = _with_window(check_spec(spec).resolve(lr * self.scale, lr * self.scale), None, 1)      # mse: window 0 means 1
+        self.lr_frame = (self.frame[0] // self.scale, self.frame[1] // self.scale)
+        self.spec = _with_window(check_spec(spec).resolve(self.lr_frame[0] * self.scale, self.lr_frame[1] * self.scale), None, 1)      # mse: window 0 means 1
         if int(min_area) < 1 or int(min_area) != min_area:
             raise ValueError(f"predict: min_area = {min_area}, must be an integer >= 1")
         self.threshold, self.min_area = (None if threshold is None else float(threshold)), int(min_area)
@@ -139,9 +148,8 @@ class Detector:
     # ---------------------------------------------------------------------------------------------------------- the pair
     def _pyramid(self, stack: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """uint8 [n,H,W,C] sources of one shape, on the GPU -> (LR uint8 [n,h,w,C], HR uint8 [n,hr,hr,C]): two LANCZOS resizes."""
-        hr = ops.resize_u8(stack, (self.hr_size, self.hr_size), 'lanczos')
-        lr = self.hr_size // self.scale
-        return ops.resize_u8(hr, (lr, lr), 'lanczos'), hr
+        hr = ops.resize_u8(stack, self.frame, 'lanczos')
+        return ops.resize_u8(hr, self.lr_frame, 'lanczos'), hr
 
     def prepare(self, images: Sequence) -> Tuple[torch.Tensor, torch.Tensor]:
         """Raw images (``as_source``), of any and mixed sizes -> (lr float32 [n,C,h,w] with values in [0, 255], hr uint8
@@ -159,10 +167,9 @@ class Detector:
         if not sources:
             raise ValueError("predict: no images")
         C_ = self.n_colors
-        lr_side = self.hr_size // self.scale
-        crop = lr_side * self.scale
-        lr_out = torch.empty(len(sources), C_, lr_side, lr_side, dtype=torch.float32, device=self.device)
-        hr_out = torch.empty(len(sources), crop, crop, C_, dtype=torch.uint8, device=self.device)
+        (lr_h, lr_w), crop_h, crop_w = self.lr_frame, self.lr_frame[0] * self.scale, self.lr_frame[1] * self.scale
+        lr_out = torch.empty(len(sources), C_, lr_h, lr_w, dtype=torch.float32, device=self.device)
+        hr_out = torch.empty(len(sources), crop_h, crop_w, C_, dtype=torch.uint8, device=self.device)
         groups: dict = {}
         for i, a in enumerate(sources):
             groups.setdefault(a.shape, []).append(i)
@@ -190,7 +197,7 @@ class Detector:
                 lr_f, hr_u = lr.float(), hr
             where = torch.tensor(idx, device=self.device)
             lr_out[where] = lr_f.permute(0, 3, 1, 2)
-            hr_out[where] = hr_u[:, :crop, :crop]             # the loader crops after set_channel
+            hr_out[where] = hr_u[:, :crop_h, :crop_w]         # the loader crops after set_channel
         return lr_out, hr_out, kept
 
     # ---------------------------------------------------------------------------------------------------------- the maps
@@ -343,13 +350,18 @@ def write_regions_csv(path, table: dict, names: Sequence[str], kinds: Sequence[s
 
 
 def write_operating_point(path, threshold: float, fpr: float, level: str, achieved: float, n_images: int, min_area: int, spec: MapSpec,
-                          self_ensemble: bool, checkpoint: str) -> dict:
+                          self_ensemble: bool, checkpoint: str, tile=None, frame=None) -> dict:
     """``operating_point.json``: everything a threshold depends on next to it.  Python's JSON writes a float's shortest
-    round-trip form, so the threshold reads back bit for bit."""
+    round-trip form, so the threshold reads back bit for bit.  ``tile`` (tile, overlap, blend) and ``frame`` (H, W) are written
+    only when they are set: a file without them says whole images in the square frame of the run's resolution."""
     doc = dict(version=OPERATING_POINT_VERSION, threshold=float(threshold), threshold_source='fpr', threshold_fpr=float(fpr),
                threshold_level=level, calib_rate=float(achieved), calib_images=int(n_images), min_region_area=int(min_area),
                map_spec=dict(asdict(spec), scales=list(spec.scales)), self_ensemble=bool(self_ensemble),
                checkpoint=os.path.basename(checkpoint))
+    if tile:
+        doc['tile'] = [int(tile[0]), int(tile[1]), str(tile[2])]
+    if frame:
+        doc['frame'] = [int(frame[0]), int(frame[1])]
     Path(path).parent.mkdir(parents=True, exist_ok=True)
     Path(path).write_text(json.dumps(doc, indent=2) + "\n")
     return doc
@@ -365,9 +377,32 @@ def read_operating_point(path) -> dict:
         m = doc['map_spec']
         doc['map_spec'] = MapSpec(source=m['source'], ws=int(m['ws']), scales=list(m['scales']) or (), reduce=m['reduce'], sigma=float(m['sigma']))
         doc['threshold'], doc['min_region_area'], doc['self_ensemble'] = float(doc['threshold']), int(doc['min_region_area']), bool(doc['self_ensemble'])
+        tile, frame = doc.get('tile'), doc.get('frame')       # absent in files written before tiling, and whenever it is off
+        doc['tile'] = (int(tile[0]), int(tile[1]), str(tile[2])) if tile else None
+        doc['frame'] = (int(frame[0]), int(frame[1])) if frame else None
     except KeyError as e:
         raise ValueError(f"{path}: entry {e} is missing")
     return doc
+
+
+def tile_from_args(args, stored: Optional[dict] = None):
+    """((tile, overlap, blend) or None, (H, W) or None) of the command line.  With ``stored`` (the operating point a threshold
+    was calibrated at): what it holds, and a ``--tile*`` or ``--frame`` flag that says otherwise is a ValueError - the
+    threshold belongs to the SR images it was calibrated on."""
+    tile = (int(args.tile), int(args.tile_overlap), str(args.tile_blend)) if getattr(args, 'tile', 0) else None
+    frame = tuple(int(v) for v in args.frame) if getattr(args, 'frame', None) else None
+    if stored is None:
+        return tile, frame
+    kept_tile, kept_frame = stored.get('tile'), stored.get('frame')
+    if tile is not None and tile != kept_tile:
+        was = "without tiling" if kept_tile is None else f"with --tile {kept_tile[0]} --tile-overlap {kept_tile[1]} --tile-blend {kept_tile[2]}"
+        raise ValueError(f"--tile {tile[0]} --tile-overlap {tile[1]} --tile-blend {tile[2]} contradicts the calibrated operating point "
+                         f"(calibrated {was}): calibrate again with it, or give --threshold")
+    if frame is not None and frame != kept_frame:
+        was = "in the square frame of the resolution" if kept_frame is None else f"with --frame {kept_frame[0]} {kept_frame[1]}"
+        raise ValueError(f"--frame {frame[0]} {frame[1]} contradicts the calibrated operating point (calibrated {was}): "
+                         f"calibrate again with it, or give --threshold")
+    return kept_tile, kept_frame
 
 
 MAP_FLAGS = (('map_source', '--map-source', 'source'), ('map_ws', '--map-ws', 'ws'), ('map_scales', '--map-scales', 'scales'),
@@ -464,7 +499,12 @@ def parse_predict_args(argv=None) -> argparse.Namespace:
                    help="write regions.csv: one row per predicted defect region (area, box, centroid, peak; with --source-frame "
                         "its box in the source image too)")
     p.add_argument('--output-dir', type=str, default='')
+    add_tile_args(p)
+    p.add_argument('--frame', type=_positive_int, nargs=2, default=None, metavar=('H', 'W'),
+                   help="the model's frame: every source is resized to H x W (default: the square of --resolution); with --tile any "
+                        "rectangle at least the scale on a side, without it what the network takes whole")
     args = p.parse_args(argv)
+    check_tile_args(p, args)
     if args.save_regions and not args.input:
         p.error("--save-regions lists the regions of --input images: give --input too")
     if (args.overlay_alpha is not None or args.overlay_contour is not None) and not args.save_overlays:
@@ -505,7 +545,9 @@ def _run(args) -> dict:
         if args.self_ensemble and not stored['self_ensemble']:
             raise SystemExit(f"--self-ensemble contradicts the calibrated operating point ({op_file} was calibrated without it)")
     try:
-        spec = check_spec(spec_from_args(args, stored['map_spec'] if stored else None, int(resolution) // int(scale) * int(scale)))
+        tile, frame = tile_from_args(args, stored)
+        side = min(frame) if frame else int(resolution)       # what --map-scales sweep stands for
+        spec = check_spec(spec_from_args(args, stored['map_spec'] if stored else None, side // int(scale) * int(scale)))
     except ValueError as e:
         raise SystemExit(str(e))
     self_ensemble = stored['self_ensemble'] if stored else args.self_ensemble
@@ -519,11 +561,13 @@ def _run(args) -> dict:
         print(f"Note: {op_file.name} was calibrated with {stored.get('checkpoint')}, these weights are {os.path.basename(ckpt)}")
     opt = build_opt(model_type, class_name, resolution, scale, 1, args.dtype, pre_train=ckpt)
     opt.test_only = True
+    if tile:
+        opt.tile, opt.tile_overlap, opt.tile_blend = tile
     from .model import Model
-    model = Model(opt, None, dual_model=(model_type == 'drn-l'))
     try:
+        model = Model(opt, None, dual_model=(model_type == 'drn-l'))
         det = Detector(opt, model, spec, threshold=stored['threshold'] if stored else args.threshold, min_area=min_area,
-                       self_ensemble=self_ensemble, hr_size=int(resolution), overlay_alpha=int(args.overlay_alpha * 255 + 0.5),
+                       self_ensemble=self_ensemble, hr_size=frame or int(resolution), overlay_alpha=int(args.overlay_alpha * 255 + 0.5),
                        overlay_contour=args.overlay_contour)
     except ValueError as e:
         raise SystemExit(str(e))
@@ -531,7 +575,7 @@ def _run(args) -> dict:
     if args.calibrate:
         t, achieved = det.calibrate(calib_files, args.threshold_fpr, args.threshold_level)
         out['operating_point'] = write_operating_point(op_file, t, args.threshold_fpr, args.threshold_level, achieved, len(calib_files), min_area,
-                                                       det.spec, self_ensemble, ckpt)
+                                                       det.spec, self_ensemble, ckpt, tile=tile, frame=frame)
         print(f"Calibrated - {det.spec.text()}, threshold={t:.9g} (fpr {args.threshold_fpr:g} on {args.threshold_level}s of "
               f"{len(calib_files)} defect-free images, achieved {achieved:.6f}), min_area={min_area}: {op_file}")
     if files:
@@ -559,7 +603,8 @@ def _run(args) -> dict:
             for k, name in enumerate(names):
                 save_sr_image(sr_host[k], name, kinds[k], det.scale, out_dir)
         print(f"Predicted - {det.spec.text()}, threshold={det.threshold:.9g}, min_area={min_area}: {sum(res['defective'])} of {len(files)} "
-              f"images defective; {os.path.join(out_dir, 'predictions.csv')}" + (" (self-ensemble x8)" if self_ensemble else ""))
+              f"images defective; {os.path.join(out_dir, 'predictions.csv')}" + (" (self-ensemble x8)" if self_ensemble else "")
+              + tile_suffix(model))
     return out
 
 

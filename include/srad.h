@@ -233,6 +233,42 @@ int srad_ensemble_inputs(const float* x, int B, int C, int H, int W, float* out_
 int srad_ensemble_mean(const float* y_a /* [4,B,C,H,W] */, const float* y_b /* [4,B,C,W,H] */, int B, int C, int H, int W,
                        float* out /* [B,C,H,W] */, void* stream);
 
+/* ------------------------------------------------------------------ tiled inference (DESIGN.md "Tiled inference")
+ * An LR image [h, w] is covered with overlapping tiles, the network runs on the tiles, and the tile outputs are blended into the
+ * image's output.  srad_tile_plan is the one place where the cover is decided (host only, needs no GPU); the two kernels'
+ * launchers call it themselves, so a caller passes the same six numbers everywhere.  Per axis, for an extent n:
+ *   padded extent p = ceil(n / granule) * granule; tile extent t = min(tile, p); stride S = tile - overlap;
+ *   origins = 0, S, 2S, ... below p - t, then p - t (the last tile snapped to the edge, no origin twice): origin k = min(kS, p - t);
+ *   padded coordinate i reads source coordinate r(i): j = i mod 2n, r = j < n ? j : 2n - 1 - j (symmetric reflection with the
+ *   edge sample repeated, periodic, so defined for any n >= 1).
+ * Tiles are numbered row-major (y outer, x inner), image-major across a batch.  Refused: tile < 1, overlap outside [0, tile),
+ * granule < 1 or tile % granule != 0, scale < 1, overlap * scale > 4094 (every blend weight a <= 4095 and every product a_y * a_x
+ * stays an exact fp32 integer), and extents that do not fit 32 bits.  The two kernels also refuse 2^31 tiles or more in a batch;
+ * their element offsets are 64-bit. */
+typedef struct {
+  int32_t h, w, tile, overlap, granule, scale; /* as asked */
+  int32_t ph, pw;                              /* padded extents */
+  int32_t ty, tx;                              /* tile extents (LR) */
+  int32_t stride;                              /* tile - overlap */
+  int32_t ny, nx;                              /* tiles per axis */
+} srad_tile_geom;
+#define SRAD_TILE_BLEND_MEAN 0
+#define SRAD_TILE_BLEND_FEATHER 1
+int srad_tile_plan(int h, int w, int tile, int overlap, int granule, int scale, srad_tile_geom* geom);
+int srad_tile_origins(const srad_tile_geom* geom, int32_t* oy /* [ny] */, int32_t* ox /* [nx] */);
+/* x [B,C,h,w] -> tiles [B*ny*nx, C, ty, tx]: a copy through r(), the padding included; no arithmetic.  tiles must not overlap x. */
+int srad_tile_gather(const float* x, int B, int C, int h, int w, int tile, int overlap, int granule, float* tiles, void* stream);
+/* y [B*ny*nx, C, ty*scale, tx*scale] (the network's outputs for the tiles of srad_tile_gather) -> out [B,C,h*scale,w*scale], the
+ * padding cropped away.  Gather form: every output pixel sums the tiles that cover it, in tile order, without atomics, so out is
+ * defined bit for bit by its inputs.  With v_k the covering tiles' values at the pixel, every product and sum rounded to fp32:
+ *   SRAD_TILE_BLEND_MEAN:    acc = v_0; acc = acc + v_k; out = acc / (float)count
+ *   SRAD_TILE_BLEND_FEATHER: w_k = a_y * a_x with a(U) = min(U + 1, E - U, overlap * scale + 1) at local HR coordinate U of a tile
+ *                            of HR extent E; acc = (float)w_0 * v_0; acc = acc + (float)w_k * v_k; out = acc / (float)(sum of w_k)
+ * (the divisions correctly rounded).  A pixel that one tile covers is that tile's value; overlap 0 makes both modes a copy.
+ * out must not overlap y.  Stream-ordered: no host synchronisation, no allocation. */
+int srad_tile_blend(const float* y, int B, int C, int h, int w, int tile, int overlap, int granule, int scale, int mode, float* out,
+                    void* stream);
+
 /* ------------------------------------------------------------------ 8-bit resize, equal to PIL.Image.resize (DESIGN.md "Resize
  * on the device"; scripts/prepare_mvtec_data.py:22-33 calls it with LANCZOS).  A table holds one axis: for every output index the
  * first source index and tap count (bounds [out_size][2]) and the taps as int32 with 22 fractional bits (coeffs
