@@ -211,6 +211,10 @@ _SIG = {
     "srad_region_table": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "srad_smooth_maps_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "srad_smooth_maps": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "srad_map_stats_accumulate": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "srad_map_normalize_workspace_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "srad_map_normalize": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "srad_map_normalize_loo": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_double, _P, _P, _P, C.c_size_t, _P]),
     "srad_l1_workspace_bytes": (C.c_int, [C.POINTER(C.c_size_t)]),
     "srad_l1_loss": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     "srad_loss_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),

@@ -16,10 +16,10 @@
 //      four rows' fp64 chains in flight and slides their inputs through registers), its fp32 result kept in LDS;
 //   2. the W pass from LDS, the stores, and the tile's maximum: a wave reduction of order_key (pixel_sort.h; NaN is the largest
 //      key) and one atomicMax per workgroup into a u32 per image.  A max does not depend on the order, so the result is
-//      deterministic.  A last tiny kernel turns the keys back into floats.
+//      deterministic.  A last tiny kernel turns the keys back into floats (map_max.h, shared with kernels_map_baseline.hip).
 #include "engine.h"
 #include "../../include/srad.h"
-#include "pixel_sort.h"
+#include "map_max.h"
 #include <algorithm>
 #include <math.h>
 
@@ -36,12 +36,6 @@ struct SmoothWeights {
 };
 
 __device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = std::max(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
 
 __global__ __launch_bounds__(256) void smooth_maps_kernel(const float* __restrict__ maps, float* __restrict__ out,
                                                           uint32_t* __restrict__ max_key, int H, int W, int r, int tiles_x,
@@ -133,14 +127,6 @@ __global__ __launch_bounds__(256) void smooth_maps_kernel(const float* __restric
   }
 }
 
-// order_key back to the float: kNanKey -> NaN, keys with the top bit set were non-negative floats, the others negative ones
-__global__ __launch_bounds__(256) void smooth_max_finish_kernel(const uint32_t* __restrict__ keys, float* __restrict__ img_max, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t k = keys[i];
-  img_max[i] = k == kNanKey ? __uint_as_float(0x7FC00000u) : __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
 int smooth_check_shape(const char* who, int n_img, int H, int W, int radius) {
   SRAD_REQUIRE(n_img >= 1 && H >= 1 && W >= 1 && (int64_t)n_img * H * W < ((int64_t)1 << 31),
                "%s: n_img x H x W = %d x %d x %d, each must be >= 1 and the product below 2^31", who, n_img, H, W);
@@ -156,7 +142,7 @@ extern "C" {
 int srad_smooth_maps_workspace_bytes(int n_img, int H, int W, int radius, size_t* bytes) {
   SRAD_REQUIRE(bytes, "smooth_maps_workspace_bytes: bytes is NULL");
   SRAD_TRY(smooth_check_shape("smooth_maps_workspace_bytes", n_img, H, W, radius));
-  *bytes = srad_align_up((size_t)n_img * sizeof(uint32_t), 256);
+  *bytes = map_max_workspace_bytes(n_img);
   return SRAD_OK;
 }
 
@@ -175,7 +161,7 @@ int srad_smooth_maps(const float* maps, int n_img, int H, int W, const double* w
   if (radius == 0) wt.w[0] = 1.0;                        // radius 0 copies: x * 1.0 == x for every float, NaN included
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   uint32_t* keys = img_max_out ? reinterpret_cast<uint32_t*>(workspace) : nullptr;
-  if (keys) SRAD_CHECK_HIP(hipMemsetAsync(keys, 0, (size_t)n_img * sizeof(uint32_t), s));
+  if (keys) SRAD_CHECK_HIP(map_max_begin(keys, n_img, s));
   const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
   {
     // fp64 operations: 3 per tap and one for the centre, in the H pass for the halo columns too; bytes: read once, written once
@@ -184,8 +170,7 @@ int srad_smooth_maps(const float* maps, int n_img, int H, int W, const double* w
     hipLaunchKernelGGL(smooth_maps_kernel, dim3((unsigned)((size_t)n_img * tiles_y * tiles_x)), dim3(256), 0, s, maps, out, keys,
                        H, W, radius, tiles_x, tiles_y, wt);
   }
-  if (keys)
-    hipLaunchKernelGGL(smooth_max_finish_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, s, keys, img_max_out, n_img);
+  if (keys) map_max_finish(keys, img_max_out, n_img, s);
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }

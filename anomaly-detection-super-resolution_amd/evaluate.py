@@ -21,6 +21,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import baseline as B
 from . import metrics as M
 from .model import Model
 from .options import build_opt, parse_eval_args, set_tile_opt, tile_suffix
@@ -149,9 +150,12 @@ def _save_gray(u8: np.ndarray, folder: str, names: Sequence[str], splits: Sequen
         Image.fromarray(u8[k]).save(str(d / f"{name}.png"))
 
 
-def save_anomaly_maps(maps: torch.Tensor, names: Sequence[str], splits: Sequence[str], output_dir: str) -> None:
+def save_anomaly_maps(maps: torch.Tensor, names: Sequence[str], splits: Sequence[str], output_dir: str, sigmas: bool = False) -> None:
     """``<output_dir>/anomaly_maps/{good,bad}/<name>.png``: 8-bit gray of ``255 * clip(map, 0, 1)``, truncated (the u8 conversion
-    of the evaluator at rgb_range 1)."""
+    of the evaluator at rgb_range 1).  ``sigmas``: the maps are z-scores of a baseline and ``z / baseline.SAVED_MAP_SIGMAS`` is
+    what is converted, so negative values become 0 and 16 sigmas saturate."""
+    if sigmas:
+        maps = maps * (1.0 / B.SAVED_MAP_SIGMAS)
     _save_gray(M.to_u8_hwc(maps[:, None], rgb_range=1.0).cpu().numpy()[..., 0], 'anomaly_maps', names, splits, output_dir)
 
 
@@ -398,7 +402,7 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
                      rank: int = 0, world: int = 1, names: Sequence[str] = (), output_dir: str = '', save_images: bool = False,
                      masks: Optional[Sequence[Optional[np.ndarray]]] = None, pixel_metrics: bool = False, save_maps: bool = False,
                      map_ws: int = 0, map_scales=(), map_reduce: str = 'mean', map_source: str = 'ssim', operating_point=None,
-                     pr_metrics: bool = False, self_ensemble: bool = False, map_sigma: float = 0.0,
+                     pr_metrics: bool = False, self_ensemble: bool = False, map_baseline=None, map_sigma: float = 0.0,
                      map_image_score: bool = False, aupro: bool = False, pro_fpr_limit: float = 0.3) -> dict:
     """src/evaluate.py:138-267 for in-memory (LR, HR) u8 pairs.  With world > 1 every rank scores its
     share r::world; rank 0 gathers the score rows and returns the AUCs (others return {}).  ``save_images``: every rank
@@ -415,15 +419,26 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     (``_pixel_scores``) where the pixel metrics can run.
 
     ``self_ensemble`` (off by default): every SR image - test and calibration - is the x8 self-ensemble of the model
-    (``Model.forward_x8``); the result then carries ``self_ensemble: True``."""
+    (``Model.forward_x8``); the result then carries ``self_ensemble: True``.
+
+    ``map_baseline`` (off by default; DESIGN.md "Baseline"): ``dict(calib=defect-free (LR, HR) u8 pairs, floor_rel=F)``.  A
+    ``baseline.MapBaseline`` is fitted on the maps of the calibration pairs - at least 3, made by the resolved spec - and the
+    test maps are put in sigmas of it before anything is saved or scored; per-image maxima are taken after that.  An
+    operating point calibrated at a rate is then calibrated on these same pairs (its own ``calib`` may be left empty; one
+    super-resolve pass serves both) and on their leave-one-out maps.  One rank only: ValueError with ``world`` > 1, before
+    any image is super-resolved.  The result gains ``map_baseline`` and the printed map lines `` [baseline: ...]``."""
     spec = MapSpec(source=map_source, ws=map_ws, scales=map_scales, reduce=map_reduce, sigma=map_sigma)
     op = None
     if operating_point is not None:
         op = (OperatingPoint(**operating_point) if isinstance(operating_point, dict) else operating_point).check()
+        if map_baseline is not None and op.fpr is not None:
+            op = _calib_of_baseline(op, map_baseline)
         if op.fpr is not None and world == 1 and not len(op.calib):
             raise ValueError("operating point: a false-positive rate needs calibration pairs (defect-free images)")
     want = Request(save_maps=save_maps, map_image_score=map_image_score, pixel_metrics=pixel_metrics, aupro=aupro,
                    pro_fpr_limit=pro_fpr_limit, op=op, pr=pr_metrics)
+    if map_baseline is not None:
+        floor_rel = _check_baseline_request(map_baseline, world)
     pairs = list(good) + list(bad)
     if pairs:
         spec = spec.resolve(*pairs[0][1].shape[:2])
@@ -468,31 +483,73 @@ def evaluate_on_test(opt, model, good: Sequence[Tuple[np.ndarray, np.ndarray]], 
     calib = None
     if op is not None and op.fpr is not None and world == 1:          # the calibration images go the test images' way
         calib = super_resolve_u8(model, [lr for lr, _ in op.calib], [h for _, h in op.calib], float(opt.rgb_range), **x8)
-    out.update(_pixel_stage(shard=shard, spec=spec, want=want, masks=masks, best_ws=best_ws, calib=calib))
+    if map_baseline is None:
+        out.update(_pixel_stage(shard=shard, spec=spec, want=want, masks=masks, best_ws=best_ws, calib=calib))
+        return out
+    if calib is None:                                         # with a calibrated operating point its pass serves both
+        pairs_c = map_baseline['calib']
+        calib = super_resolve_u8(model, [lr for lr, _ in pairs_c], [h for _, h in pairs_c], float(opt.rgb_range), **x8)
+    out.update(_pixel_stage(shard=shard, spec=spec, want=want, masks=masks, best_ws=best_ws, calib=calib, floor_rel=floor_rel))
     return out
 
 
-def _pixel_stage(shard: Shard, spec: MapSpec, want: Request, masks, best_ws, calib=None) -> dict:
+def _check_baseline_request(map_baseline, world: int) -> float:
+    """The checks of ``evaluate_on_test(map_baseline=...)`` that need no GPU; returns its floor_rel."""
+    if not isinstance(map_baseline, dict) or set(map_baseline) - {'calib', 'floor_rel'} or 'calib' not in map_baseline:
+        raise ValueError("map_baseline: a dict(calib=defect-free (LR, HR) pairs, floor_rel=F)")
+    if world > 1:
+        raise ValueError("map_baseline needs one rank (the baseline is fitted and applied where the maps are, like the operating point)")
+    floor_rel = map_baseline.get('floor_rel')
+    floor_rel = B.check_floor_rel(B.FLOOR_REL_DEFAULT if floor_rel is None else floor_rel)
+    B.check_count(len(map_baseline['calib']))
+    return floor_rel
+
+
+def _calib_of_baseline(op: OperatingPoint, map_baseline) -> OperatingPoint:
+    """With a baseline, a rate is calibrated on the baseline's own calibration pairs (leave-one-out): the operating point's
+    ``calib`` is filled from them where it is empty, and must be them where it is not."""
+    pairs_c = map_baseline.get('calib', ()) if isinstance(map_baseline, dict) else ()
+    if len(op.calib):
+        same = len(op.calib) == len(pairs_c) and all(a is c or (np.array_equal(a[0], c[0]) and np.array_equal(a[1], c[1]))
+                                                      for a, c in zip(op.calib, pairs_c))
+        if not same:
+            raise ValueError("operating point: with map_baseline the rate is calibrated on the baseline's calibration pairs "
+                             "(leave-one-out); its own calib must be those pairs, or empty")
+        return op
+    return replace(op, calib=pairs_c)
+
+
+def _pixel_stage(shard: Shard, spec: MapSpec, want: Request, masks, best_ws, calib=None, floor_rel=None) -> dict:
     """The anomaly maps of this rank's images and what was asked for on them: saved maps and the map-maximum image AUC on any
     number of ranks; the pixel-level AUC, AU-PRO and the operating point (``calib`` = the (sr, hr) u8 stacks of its
     calibration pairs) on a single rank.  ``spec`` is resolved; ``best_ws`` is None off rank 0.  Every branch that leads to a
     collective depends only on ``spec``, ``want`` and ``shard.world``, which all ranks share, so all ranks make the same
-    collective calls: at most one broadcast (``_with_window``) and one gather (``_map_max_auc``)."""
-    found, maps = {}, None
+    collective calls: at most one broadcast (``_with_window``) and one gather (``_map_max_auc``).
+
+    ``floor_rel`` (a single rank only, with ``calib``): a ``baseline.MapBaseline`` is fitted on the maps of ``calib`` - made by
+    the spec after ``_with_window`` - and the test maps and their maxima are the normalised ones from here on."""
+    found, maps, bl, cmaps, note = {}, None, None, None, ''
     if want.save_maps or want.map_image_score or (want.single and shard.world == 1):      # what needs the maps here
         spec = _with_window(spec, best_ws, shard.world)
-        maps, img_max = spec.make(shard.sr, shard.hr, want.map_image_score)
+        if floor_rel is None:
+            maps, img_max = spec.make(shard.sr, shard.hr, want.map_image_score)
+        else:
+            cmaps, _ = spec.make(calib[0], calib[1], False)
+            bl = B.MapBaseline.fit(cmaps, floor_rel)
+            maps, _ = spec.make(shard.sr, shard.hr, False)
+            maps, img_max = bl.apply(maps, with_max=True, out=maps)
+            found, note = bl.entries(), bl.note()
         if want.save_maps and shard.output_dir:
-            save_anomaly_maps(maps, shard.my_names(), shard.my_splits(), shard.output_dir)
+            save_anomaly_maps(maps, shard.my_names(), shard.my_splits(), shard.output_dir, **(dict(sigmas=True) if bl else {}))
         if want.map_image_score:
-            found = _map_max_auc(shard, spec, img_max, want.pr)
+            found = dict(found, **_map_max_auc(shard, spec, img_max, want.pr, note))
     runs, labels = _single_rank_gate(shard, want, masks, best_ws, maps)
     if not runs:
         return spec.entries(found) if found else {}
     out = spec.entries(found)
-    out.update(_pixel_scores(spec, want, maps, labels))
+    out.update(_pixel_scores(spec, want, maps, labels, note))
     if want.op is not None:
-        out.update(_operating_point(shard, spec, want.op, maps, labels, calib))
+        out.update(_operating_point(shard, spec, want.op, maps, labels, calib, note, bl, cmaps))
     return out
 
 
@@ -509,7 +566,7 @@ def _with_window(spec: MapSpec, best_ws, world: int) -> MapSpec:
     return spec if spec.scales else replace(spec, ws=max(spec.ws, 1))
 
 
-def _map_max_auc(shard: Shard, spec: MapSpec, img_max: torch.Tensor, pr: bool = False) -> dict:
+def _map_max_auc(shard: Shard, spec: MapSpec, img_max: torch.Tensor, pr: bool = False, note: str = '') -> dict:
     """``auc_map_max``, the ROC-AUC of each image's map maximum: every rank's maxima are gathered to rank 0 like the score
     rows (one more gather, one column); {} on the other ranks.  No masks needed.  ``pr``: also ``ap_map_max`` and
     ``f1max_map_max`` of the same gathered maxima."""
@@ -517,11 +574,11 @@ def _map_max_auc(shard: Shard, spec: MapSpec, img_max: torch.Tensor, pr: bool = 
     if full is None:
         return {}
     auc = M.roc_auc(shard.y_true, full[:, 0])
-    print(f"Image AUC - max of the {spec.text(always_sigma=True)}: {auc:.4f}")
+    print(f"Image AUC - max of the {spec.text(always_sigma=True)}{note}: {auc:.4f}")
     if not pr:
         return dict(auc_map_max=auc)
     ap, f1 = M.average_precision(shard.y_true, full[:, 0])
-    print(f"Image AP - max of the {spec.text(always_sigma=True)}: {ap:.4f}, F1-max: {f1:.4f}")
+    print(f"Image AP - max of the {spec.text(always_sigma=True)}{note}: {ap:.4f}, F1-max: {f1:.4f}")
     return dict(auc_map_max=auc, ap_map_max=ap, f1max_map_max=f1)
 
 
@@ -546,7 +603,7 @@ def _single_rank_gate(shard: Shard, want: Request, masks, best_ws, maps):
     return True, torch.from_numpy(np.stack([np.asarray(masks[i]) for i in shard.mine])).to(maps.device)
 
 
-def _pixel_scores(spec: MapSpec, want: Request, maps: torch.Tensor, labels) -> dict:
+def _pixel_scores(spec: MapSpec, want: Request, maps: torch.Tensor, labels, note: str = '') -> dict:
     """``auc_pixel``, the exact pixel-level ROC-AUC, ``aupro`` with ``pro_fpr_limit``, the normalised area under the
     per-region overlap curve up to that limit, and ``ap_pixel`` with the best-F1 point of ``metrics.pixel_pr`` (``f1max_pixel``,
     its ``f1max_pixel_precision`` and ``f1max_pixel_recall``, and ``f1max_pixel_threshold``, which ``--threshold`` takes: predict
@@ -554,21 +611,22 @@ def _pixel_scores(spec: MapSpec, want: Request, maps: torch.Tensor, labels) -> d
     out = {}
     if want.pixel_metrics and labels is not None:
         out["auc_pixel"] = M.pixel_roc_auc(maps, labels)
-        print(f"Pixel AUC - {spec.text()}: {out['auc_pixel']:.4f}")
+        print(f"Pixel AUC - {spec.text()}{note}: {out['auc_pixel']:.4f}")
     if want.aupro and labels is not None:
         limit = float(want.pro_fpr_limit)
         out["aupro"], out["pro_fpr_limit"] = M.aupro(maps, labels, want.pro_fpr_limit), limit
-        print(f"AU-PRO - {spec.text(f', fpr <= {limit:g}')}: {out['aupro']:.4f}")
+        print(f"AU-PRO - {spec.text(f', fpr <= {limit:g}')}{note}: {out['aupro']:.4f}")
     if want.pr and labels is not None:
         r = M.pixel_pr(maps, labels)
         out.update(ap_pixel=r["ap"], f1max_pixel=r["f1max"], f1max_pixel_threshold=r["threshold"],
                    f1max_pixel_precision=r["precision"], f1max_pixel_recall=r["recall"])
-        print(f"Pixel AP - {spec.text()}: {r['ap']:.4f}, F1-max: {r['f1max']:.4f} (precision={r['precision']:.4f} "
+        print(f"Pixel AP - {spec.text()}{note}: {r['ap']:.4f}, F1-max: {r['f1max']:.4f} (precision={r['precision']:.4f} "
               f"recall={r['recall']:.4f} at threshold={r['threshold']:.9g})")
     return out
 
 
-def _operating_point(shard: Shard, spec: MapSpec, op: OperatingPoint, maps: torch.Tensor, labels, calib) -> dict:
+def _operating_point(shard: Shard, spec: MapSpec, op: OperatingPoint, maps: torch.Tensor, labels, calib, note: str = '',
+                     baseline=None, calib_maps=None) -> dict:
     """The maps thresholded (DESIGN.md "Operating point") at the given threshold, or at the one that the maps of the
     calibration stacks - made by the same ``spec`` - give at the asked false-positive rate: ``threshold``,
     ``threshold_source`` ('given' or 'fpr'; then also ``threshold_fpr``, ``threshold_level``, ``calib_images`` and
@@ -576,9 +634,13 @@ def _operating_point(shard: Shard, spec: MapSpec, op: OperatingPoint, maps: torc
     ``metrics.operating_point_stats`` and, with ``labels``, its pixel-level ones; the masks are saved where asked for.  With
     ``op.region_metrics`` also the entries of ``metrics.region_stats`` and ``region_min_overlap``, from the table of the
     predicted regions against ``labels`` and the table of the ground-truth regions against the prediction (without ``labels``
-    every image counts as all-ok: no ground-truth region, every predicted region a false alarm)."""
-    if op.fpr is not None:
+    every image counts as all-ok: no ground-truth region, every predicted region a false alarm).  With a ``baseline`` (fitted
+    on ``calib_maps``, the maps of ``calib``; ``maps`` are in its sigmas) a rate is calibrated on the leave-one-out maps."""
+    if op.fpr is not None and baseline is not None:
+        cmaps, cmax = baseline.apply_loo(calib_maps, with_max=True)
+    elif op.fpr is not None:
         cmaps, cmax = spec.make(calib[0], calib[1], op.level == 'image')
+    if op.fpr is not None:
         t, achieved = M.map_threshold(cmax if op.level == 'image' else cmaps, op.fpr)
         out = dict(threshold=t, threshold_source='fpr', threshold_fpr=float(op.fpr), threshold_level=op.level,
                    calib_images=int(cmaps.shape[0]), calib_rate=achieved)
@@ -590,7 +652,7 @@ def _operating_point(shard: Shard, spec: MapSpec, op: OperatingPoint, maps: torc
     pred, img_pred, counts = M.operating_point(maps, t, labels, int(op.min_area))
     st = M.operating_point_stats(counts if labels is not None else None, img_pred, [shard.y_true[i] for i in shard.mine])
     out.update(st)
-    line = (f"Operating point - {spec.text()}, threshold={t:.9g} ({src}), min_area={int(op.min_area)}: "
+    line = (f"Operating point - {spec.text()}{note}, threshold={t:.9g} ({src}), min_area={int(op.min_area)}: "
             f"image tp={st['image_tp']} fp={st['image_fp']} fn={st['image_fn']} tn={st['image_tn']} "
             f"tpr={st['image_tpr']:.4f} fpr={st['image_fpr']:.4f}")
     if labels is not None:
@@ -651,11 +713,18 @@ def _run(args):
             except ValueError as e:
                 raise SystemExit(f"{flag}: {e}")
     want_op = args.threshold is not None or args.threshold_fpr is not None
-    if args.threshold_fpr is not None:                        # before the model is loaded
+    want_baseline = bool(getattr(args, 'map_baseline', False))
+    if want_baseline and int(os.environ.get('WORLD_SIZE', '1')) > 1:      # before the model is loaded
+        raise SystemExit("--map-baseline needs --gpus 1 (the baseline is fitted and applied on one rank, like the operating point)")
+    if args.threshold_fpr is not None or want_baseline:       # before the model is loaded
         data_root = args.data_root if args.data_root != 'auto' else f"data/mvtec_{resolution}"
         val_dir = val_good_dir(data_root, class_name)
-        if not any((val_dir / 'HR').glob('*.png')):
+        n_val = len(list((val_dir / 'HR').glob('*.png')))
+        if not n_val and args.threshold_fpr is not None:
             raise SystemExit(f"--threshold-fpr calibrates on defect-free images, and there is none under {val_dir} "
+                             f"(HR/*.png with LR_<scale> beside it, as prepare_mvtec_data writes the validation split)")
+        if want_baseline and n_val < B.MIN_IMAGES:
+            raise SystemExit(f"--map-baseline fits on defect-free images, and there are {n_val} under {val_dir}, fewer than {B.MIN_IMAGES} "
                              f"(HR/*.png with LR_<scale> beside it, as prepare_mvtec_data writes the validation split)")
     ckpt = resolve_checkpoint(args)
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -684,10 +753,11 @@ def _run(args):
             print(f"No ground-truth mask for {len(missing)} bad image(s) under test/bad/GT (prepare_mvtec_data --with-masks), "
                   f"e.g. {missing[0]}")
     op = None
+    calib = []
+    if (args.threshold_fpr is not None or want_baseline) and world == 1:      # more ranks skip the operating point: nothing to read
+        calib = [(lr, hr) for _, lr, hr in iter_split(opt.data_root, class_name, 'good', opt.scale, opt.n_colors, part='val')]
+    baseline = dict(map_baseline=dict(calib=calib, floor_rel=getattr(args, 'baseline_floor', None))) if want_baseline else {}
     if want_op:
-        calib = []
-        if args.threshold_fpr is not None and world == 1:     # more ranks skip the operating point: nothing to read
-            calib = [(lr, hr) for _, lr, hr in iter_split(opt.data_root, class_name, 'good', opt.scale, opt.n_colors, part='val')]
         op = OperatingPoint(threshold=args.threshold, fpr=args.threshold_fpr, level=args.threshold_level,
                             min_area=args.min_region_area, save_masks=args.save_masks, calib=calib,
                             region_metrics=args.region_metrics, region_min_overlap=args.region_min_overlap,
@@ -698,7 +768,7 @@ def _run(args):
                            aupro=args.aupro, pro_fpr_limit=args.pro_fpr_limit, map_sigma=args.map_sigma,
                            map_image_score=args.map_image_score, map_scales=args.map_scales, map_reduce=args.map_reduce,
                            map_source=args.map_source, operating_point=op, pr_metrics=args.pr_metrics,
-                           self_ensemble=args.self_ensemble)
+                           self_ensemble=args.self_ensemble, **baseline)
     if getattr(args, 'ema', False) and out:                   # rank 0's result says which weights it is of
         out['ema'] = True
     if world > 1:

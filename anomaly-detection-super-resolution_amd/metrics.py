@@ -626,6 +626,92 @@ def smooth_maps(maps: torch.Tensor, sigma: float, truncate: float = 4.0, with_ma
     return (out, img_max) if with_max else out
 
 
+def _map_stack(who: str, maps: torch.Tensor) -> torch.Tensor:
+    """``maps`` as the float32 [n, H, W] tensor on the GPU the baseline kernels take; a contiguous one is passed as it is."""
+    _need_cuda(maps)
+    m = maps.detach()
+    if m.dim() != 3 or m.numel() == 0 or m.dtype != torch.float32:
+        raise ValueError(f"{who} takes a non-empty float32 [n, H, W] tensor, got {m.dtype} {tuple(m.shape)}")
+    return m.contiguous()
+
+
+def _map_plane(who: str, name: str, p: torch.Tensor, like: torch.Tensor, dtype) -> torch.Tensor:
+    """A [H, W] plane of the baseline, checked against the maps ``like``: same device, ``dtype``, the maps' H x W, contiguous."""
+    _need_cuda(p)
+    if p.dtype != dtype or tuple(p.shape) != tuple(like.shape[1:]) or p.device != like.device or not p.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} {tuple(like.shape[1:])} tensor on {like.device}, "
+                         f"got {p.dtype} {tuple(p.shape)} on {p.device}")
+    return p
+
+
+def map_stats_accumulate(maps: torch.Tensor, s1: Optional[torch.Tensor] = None, s2: Optional[torch.Tensor] = None
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The per-pixel sums of float32 maps [n,H,W] on the GPU, in float64 [H,W]: ``s1 += sum_i m_i`` and ``s2 += sum_i m_i * m_i``,
+    added sequentially in image order with one rounding per add (DESIGN.md "Baseline"), so a stack split over consecutive
+    calls gives the bits of one call.  Without ``s1`` and ``s2`` the sums start at +0.0; with them they are updated in place and
+    returned.  A NaN pixel makes that pixel's sums NaN."""
+    m = _map_stack("map_stats_accumulate", maps)
+    if (s1 is None) != (s2 is None):
+        raise ValueError("map_stats_accumulate: give both s1 and s2, or neither")
+    n, H, W = m.shape
+    if s1 is None:
+        s1 = torch.zeros(H, W, dtype=torch.float64, device=m.device)
+        s2 = torch.zeros(H, W, dtype=torch.float64, device=m.device)
+    else:
+        s1 = _map_plane("map_stats_accumulate", "s1", s1, m, torch.float64)
+        s2 = _map_plane("map_stats_accumulate", "s2", s2, m, torch.float64)
+    L.check(L.lib().srad_map_stats_accumulate(L.dptr(m), n, H, W, L.dptr(s1), L.dptr(s2), L.current_stream_ptr()), "map_stats_accumulate")
+    return s1, s2
+
+
+def _normalize_out(who: str, m: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    if out is None:
+        return torch.empty_like(m)
+    _need_cuda(out)
+    if out.dtype != torch.float32 or out.shape != m.shape or out.device != m.device or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous float32 {tuple(m.shape)} tensor on {m.device}, "
+                         f"got {out.dtype} {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def normalize_maps(maps: torch.Tensor, mu: torch.Tensor, inv_sd: torch.Tensor, with_max: bool = False,
+                   out: Optional[torch.Tensor] = None):
+    """Per-pixel z-scores of float32 maps [n,H,W] on the GPU against the float32 planes ``mu`` and ``inv_sd`` [H,W]:
+    ``z = fl32(fl32(m - mu) * inv_sd)``, signed, NaN propagating (DESIGN.md "Baseline").  ``out``: where to write them, which
+    may be ``maps`` itself (in place).  With ``with_max`` returns (z, per-image maximum float32 [n], NaN for an image with a
+    NaN pixel)."""
+    m = _map_stack("normalize_maps", maps)
+    mu = _map_plane("normalize_maps", "mu", mu, m, torch.float32)
+    inv_sd = _map_plane("normalize_maps", "inv_sd", inv_sd, m, torch.float32)
+    out = _normalize_out("normalize_maps", m, out)
+    n, H, W = m.shape
+    img_max = torch.empty(n, dtype=torch.float32, device=m.device) if with_max else None
+    _call_with_ws("map_normalize_workspace_bytes", (n,), "map_normalize",
+                  (L.dptr(m), n, H, W, L.dptr(mu), L.dptr(inv_sd), L.dptr(out), L.dptr(img_max)), m.device)
+    return (out, img_max) if with_max else out
+
+
+def normalize_maps_loo(maps: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, n: int, floor: float, with_max: bool = False):
+    """Leave-one-out z-scores of float32 maps [k,H,W] that are part of the float64 sums ``s1``, ``s2`` [H,W] over ``n`` >= 3
+    maps (``map_stats_accumulate``): each map against the mean and spread of the other ``n - 1``, in float64 with the fitted
+    ``floor`` > 0 under the spread, rounded to float32 once (DESIGN.md "Baseline").  With ``with_max`` returns (z, per-image
+    maximum)."""
+    m = _map_stack("normalize_maps_loo", maps)
+    s1 = _map_plane("normalize_maps_loo", "s1", s1, m, torch.float64)
+    s2 = _map_plane("normalize_maps_loo", "s2", s2, m, torch.float64)
+    if int(n) != n or int(n) < 3:
+        raise ValueError(f"normalize_maps_loo: n = {n}, leave-one-out needs sums over at least 3 maps")
+    floor = float(floor)
+    if not (floor > 0.0 and np.isfinite(floor)):
+        raise ValueError(f"normalize_maps_loo: floor = {floor}, must be finite and > 0")
+    out = torch.empty_like(m)
+    k, H, W = m.shape
+    img_max = torch.empty(k, dtype=torch.float32, device=m.device) if with_max else None
+    _call_with_ws("map_normalize_workspace_bytes", (k,), "map_normalize_loo",
+                  (L.dptr(m), k, H, W, L.dptr(s1), L.dptr(s2), int(n), C.c_double(floor), L.dptr(out), L.dptr(img_max)), m.device)
+    return (out, img_max) if with_max else out
+
+
 def l1_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """nn.L1Loss(reduction='mean') (src/loss.py:84) -> 0-d float64 tensor on the GPU."""
     _need_cuda(a, b)

@@ -284,6 +284,35 @@ def tile_suffix(model) -> str:
     return f" (tiles {t}/{int(model.tile_overlap)} {model.tile_blend})" if t else ""
 
 
+def _positive_finite_float(text: str) -> float:
+    v = float(text)
+    if not 0.0 < v < float('inf'):                            # zero, negatives, infinities and NaN
+        raise argparse.ArgumentTypeError(f"{text} is not a finite number > 0")
+    return v
+
+
+def add_baseline_args(p: argparse.ArgumentParser, flag: str, where: str) -> None:
+    """``flag`` (--map-baseline in the evaluator, --baseline in predict) and --baseline-floor (DESIGN.md "Baseline"); off by default."""
+    p.add_argument(flag, action='store_true', default=False,
+                   help=f"per-pixel baseline: fit the mean and spread of the anomaly maps on the defect-free images {where} and "
+                        "score, threshold and save the maps in sigmas of it (needs at least 3 such images)")
+    p.add_argument('--baseline-floor', type=_positive_finite_float, default=None, metavar='F',
+                   help=f"the least per-pixel spread of the baseline, as a share of the pooled spread; finite and > 0, default 0.1 (with {flag})")
+
+
+def check_baseline_args(p: argparse.ArgumentParser, args: argparse.Namespace, attr: str, flag: str) -> None:
+    """The checks of the two flags, for values from a config file too; --baseline-floor stays None where it was not given."""
+    if not isinstance(getattr(args, attr), bool):
+        p.error(f"argument {flag}: {getattr(args, attr)!r} is not a boolean")
+    if args.baseline_floor is not None:
+        try:
+            args.baseline_floor = _positive_finite_float(str(args.baseline_floor))
+        except (argparse.ArgumentTypeError, ValueError) as e:
+            p.error(f"argument --baseline-floor: {e}")
+        if not getattr(args, attr):
+            p.error(f"--baseline-floor belongs to {flag}: give it too")
+
+
 def _grad_clip(text: str) -> float:
     v = float(text)
     if not v > 0.0:                                           # zero, negatives and NaN
@@ -430,9 +459,17 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
     p.add_argument('--save-regions', action='store_true', default=False,
                    help="write <output-dir>/regions.csv: one row per predicted region (with --region-metrics)")
     add_tile_args(p)
+    add_baseline_args(p, '--map-baseline', "of <class>/val/good (the images of --threshold-fpr)")
     _with_config(p, pre_args)
     args = p.parse_args(argv)
     check_tile_args(p, args)
+    check_baseline_args(p, args, 'map_baseline', '--map-baseline')
+    if args.map_baseline and int(args.gpus) > 1:
+        p.error("--map-baseline needs --gpus 1 (the baseline is fitted and applied on one rank, like the operating point)")
+    if args.map_baseline and not (args.pixel_metrics or args.aupro or args.pr_metrics or args.save_anomaly_maps or args.map_image_score
+                                  or args.threshold is not None or args.threshold_fpr is not None):
+        p.error("--map-baseline normalises the anomaly maps: give a flag that makes them too (--pixel-metrics, --aupro, "
+                "--pr-metrics, --map-image-score, --save-anomaly-maps, --threshold or --threshold-fpr)")
     if args.ema and args.checkpoint:
         p.error("--ema and --checkpoint exclude each other (an explicit file is already a choice)")
     if args.region_metrics and args.threshold is None and args.threshold_fpr is None:

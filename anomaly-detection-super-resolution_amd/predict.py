@@ -30,12 +30,13 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import baseline as B
 from . import metrics as M
 from . import ops
 from .data import rgb2y, set_channel
 from .evaluate import MapSpec, _with_window, infer_from_run_dir, resolve_checkpoint, save_anomaly_maps, save_masks, save_sr_image, super_resolve_dev
-from .options import (_finite_or_inf_float, _map_scales, _nonnegative_float, _open_unit_float, _positive_int, add_tile_args, build_opt,
-                      check_tile_args, tile_suffix)
+from .options import (_finite_or_inf_float, _map_scales, _nonnegative_float, _open_unit_float, _positive_int, add_baseline_args,
+                      add_tile_args, build_opt, check_baseline_args, check_tile_args, tile_suffix)
 
 OPERATING_POINT_FILE = 'operating_point.json'
 OPERATING_POINT_VERSION = 1
@@ -119,8 +120,9 @@ class Detector:
 
     def __init__(self, opt, model, spec: MapSpec, threshold: Optional[float] = None, min_area: int = 1, self_ensemble: bool = False,
                  hr_size: Optional[int] = None, overlay_alpha: int = int(OVERLAY_ALPHA_DEFAULT * 255 + 0.5),
-                 overlay_contour: int = OVERLAY_CONTOUR_DEFAULT):
+                 overlay_contour: int = OVERLAY_CONTOUR_DEFAULT, baseline: Optional[B.MapBaseline] = None):
         self.opt, self.model, self.self_ensemble = opt, model, bool(self_ensemble)
+        self.baseline, self._fitted_on = None, None
         self._lut_host = heat_lut(overlay_alpha)
         if not float(overlay_contour).is_integer() or not 0 <= overlay_contour <= 4:
             raise ValueError(f"predict: overlay_contour = {overlay_contour!r}, must be an integer in 0..4")
@@ -144,6 +146,19 @@ class Detector:
         self.device = model.device
         self._luma = None
         model.eval()                                          # H1 of the evaluator: deterministic scoring
+        if baseline is not None:
+            self.set_baseline(baseline)
+
+    @property
+    def map_shape(self) -> Tuple[int, int]:
+        """(H, W) of the maps: the HR frame cropped to LR * scale."""
+        return self.lr_frame[0] * self.scale, self.lr_frame[1] * self.scale
+
+    def set_baseline(self, baseline: Optional[B.MapBaseline]) -> None:
+        """Maps are in sigmas of ``baseline`` from here on (None: the raw maps again).  ValueError for one of another frame."""
+        if baseline is not None and baseline.shape != self.map_shape:
+            raise ValueError(f"predict: the baseline is {baseline.shape}, the maps of this frame are {self.map_shape}")
+        self.baseline, self._fitted_on = baseline, None
 
     # ---------------------------------------------------------------------------------------------------------- the pair
     def _pyramid(self, stack: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -201,20 +216,48 @@ class Detector:
         return lr_out, hr_out, kept
 
     # ---------------------------------------------------------------------------------------------------------- the maps
-    def _maps(self, images: Sequence, with_max: bool, keep_sources: bool = False):
+    def _maps(self, images: Sequence, with_max: bool, keep_sources: bool = False, raw: bool = False):
+        """``raw``: the spec's maps even with a baseline (what a baseline is fitted on and leaves one out of)."""
         lr, hr, kept = self._prepare(images, keep_sources)
         sr = super_resolve_dev(self.model, lr, hr.shape[1:3], self.rgb_range, self_ensemble=self.self_ensemble)
-        maps, img_max = self.spec.make(sr, hr, with_max)
+        if self.baseline is None or raw:
+            maps, img_max = self.spec.make(sr, hr, with_max and not raw)
+        else:                                                 # the maximum is taken after the normalisation
+            maps, _ = self.spec.make(sr, hr, False)
+            maps, img_max = self.baseline.apply(maps, with_max=True, out=maps)
         return sr, hr, maps, img_max, kept
+
+    @staticmethod
+    def _image_keys(images: Sequence) -> list:
+        return [os.fspath(im) if isinstance(im, (str, os.PathLike)) else id(im) for im in images]
+
+    def fit_baseline(self, images: Sequence, floor_rel: float = B.FLOOR_REL_DEFAULT) -> B.MapBaseline:
+        """Fits a per-pixel baseline (``baseline.MapBaseline``; DESIGN.md "Baseline") on the maps of the defect-free
+        ``images`` - at least 3 - and makes it this detector's: ``predict`` then gives maps in sigmas of it, and a ``calibrate``
+        on these same images takes their leave-one-out maps.  The fitted maps are kept until that calibration."""
+        floor_rel = B.check_floor_rel(floor_rel)
+        B.check_count(len(images))
+        _, _, maps, _, _ = self._maps(images, False, raw=True)
+        self.baseline = B.MapBaseline.fit(maps, floor_rel)
+        self._fitted_on = (self._image_keys(images), maps)
+        return self.baseline
 
     def calibrate(self, images: Sequence, fpr: float, level: str = 'pixel') -> Tuple[float, float]:
         """The threshold that the maps of the defect-free ``images`` give at false-positive rate ``fpr`` - on all their pixels
         (``level`` 'pixel') or on each map's maximum ('image') - as the evaluator's ``--threshold-fpr`` calibrates it
-        (``metrics.map_threshold``).  Sets and returns it, with the rate achieved."""
+        (``metrics.map_threshold``).  Sets and returns it, with the rate achieved.  With a baseline the ``images`` must be
+        the ones it was fitted on (``fit_baseline``), and the threshold comes from their leave-one-out maps."""
         if level not in ('pixel', 'image'):
             raise ValueError(f"predict: level = {level!r}, must be 'pixel' or 'image'")
         M.rank_for_rate(1, fpr)                               # the rate's own check, before any work
-        _, _, maps, img_max, _ = self._maps(images, level == 'image')
+        if self.baseline is None:
+            _, _, maps, img_max, _ = self._maps(images, level == 'image')
+        else:
+            if self._fitted_on is None or self._fitted_on[0] != self._image_keys(images):
+                raise ValueError("predict: with a baseline the threshold is calibrated on the images the baseline was fitted on "
+                                 "(fit_baseline on them first): in-sample z-scores of other maps are not leave-one-out")
+            maps, img_max = self.baseline.apply_loo(self._fitted_on[1], with_max=True)
+            self._fitted_on = None
         self.threshold, achieved = M.map_threshold(img_max if level == 'image' else maps, fpr)
         return self.threshold, achieved
 
@@ -350,10 +393,12 @@ def write_regions_csv(path, table: dict, names: Sequence[str], kinds: Sequence[s
 
 
 def write_operating_point(path, threshold: float, fpr: float, level: str, achieved: float, n_images: int, min_area: int, spec: MapSpec,
-                          self_ensemble: bool, checkpoint: str, tile=None, frame=None) -> dict:
+                          self_ensemble: bool, checkpoint: str, tile=None, frame=None, baseline=None) -> dict:
     """``operating_point.json``: everything a threshold depends on next to it.  Python's JSON writes a float's shortest
     round-trip form, so the threshold reads back bit for bit.  ``tile`` (tile, overlap, blend) and ``frame`` (H, W) are written
-    only when they are set: a file without them says whole images in the square frame of the run's resolution."""
+    only when they are set: a file without them says whole images in the square frame of the run's resolution.  So is
+    ``baseline`` (``baseline_entry``: the file of the per-pixel baseline beside this one and its hash): a file without it says
+    the threshold is in the maps' own units."""
     doc = dict(version=OPERATING_POINT_VERSION, threshold=float(threshold), threshold_source='fpr', threshold_fpr=float(fpr),
                threshold_level=level, calib_rate=float(achieved), calib_images=int(n_images), min_region_area=int(min_area),
                map_spec=dict(asdict(spec), scales=list(spec.scales)), self_ensemble=bool(self_ensemble),
@@ -362,9 +407,59 @@ def write_operating_point(path, threshold: float, fpr: float, level: str, achiev
         doc['tile'] = [int(tile[0]), int(tile[1]), str(tile[2])]
     if frame:
         doc['frame'] = [int(frame[0]), int(frame[1])]
+    if baseline:
+        doc['baseline'] = _baseline_entry(baseline)
     Path(path).parent.mkdir(parents=True, exist_ok=True)
     Path(path).write_text(json.dumps(doc, indent=2) + "\n")
     return doc
+
+
+def _baseline_entry(e: dict) -> dict:
+    """The ``baseline`` entry of ``operating_point.json`` with its five keys and their types (KeyError for a missing one)."""
+    return dict(file=str(e['file']), n_images=int(e['n_images']), floor_rel=float(e['floor_rel']), floor=float(e['floor']),
+                sha256=str(e['sha256']))
+
+
+def baseline_entry(baseline: B.MapBaseline, path, sha256: str) -> dict:
+    """What ``write_operating_point(baseline=...)`` takes for ``baseline`` saved at ``path`` (``MapBaseline.save`` returns the hash)."""
+    return dict(file=os.path.basename(path), n_images=baseline.n, floor_rel=baseline.floor_rel, floor=baseline.floor, sha256=sha256)
+
+
+def baseline_from_args(args, stored: Optional[dict], folder) -> Optional[dict]:
+    """Which saved baseline a prediction runs with: None, or dict(path, sha256 or None).  With ``stored`` (the operating point
+    a threshold was calibrated at): what it holds, its file beside it in ``folder`` - and ``--baseline`` or a
+    ``--baseline-floor`` that says otherwise is a ValueError, as the threshold is in sigmas of that baseline or in none.  With
+    a given ``--threshold`` and ``--baseline``: ``folder``'s ``map_baseline.npz``, which must be there."""
+    want, floor = bool(getattr(args, 'baseline', False)), getattr(args, 'baseline_floor', None)
+    if stored is None:
+        if not want or getattr(args, 'calibrate', ''):
+            return None
+        path = Path(folder) / B.BASELINE_FILE
+        if not path.is_file():
+            raise ValueError(f"--baseline: no {path} (--calibrate DIR --threshold-fpr RATE --baseline writes it)")
+        return dict(path=path, sha256=None, floor_rel=floor)
+    kept = stored.get('baseline')
+    if want and kept is None:
+        raise ValueError("--baseline contradicts the calibrated operating point (calibrated without a baseline): "
+                         "calibrate again with it, or give --threshold")
+    if kept is not None and floor is not None and floor != kept['floor_rel']:
+        raise ValueError(f"--baseline-floor {floor:g} contradicts the calibrated operating point (floor_rel = {kept['floor_rel']:g}): "
+                         f"calibrate again with it, or give --threshold")
+    return None if kept is None else dict(path=Path(folder) / kept['file'], sha256=kept['sha256'], floor_rel=None)
+
+
+def load_baseline(which: dict, det: 'Detector') -> B.MapBaseline:
+    """The saved baseline ``baseline_from_args`` named, for ``det``: the file's hash (where the operating point recorded one),
+    its frame and its map spec are checked against the detector's.  ValueError for a mismatch or an unreadable file."""
+    path = which['path']
+    if not Path(path).is_file():
+        raise ValueError(f"{path}: the baseline of the calibrated operating point is missing")
+    if which.get('sha256') is not None and B.file_sha256(path) != which['sha256']:
+        raise ValueError(f"{path}: the file's sha256 is not the one the operating point was calibrated with")
+    b = B.load(path, device=det.device, shape=det.map_shape, spec=det.spec)
+    if which.get('floor_rel') is not None and which['floor_rel'] != b.floor_rel:
+        raise ValueError(f"--baseline-floor {which['floor_rel']:g} contradicts {path} (floor_rel = {b.floor_rel:g})")
+    return b
 
 
 def read_operating_point(path) -> dict:
@@ -380,6 +475,7 @@ def read_operating_point(path) -> dict:
         tile, frame = doc.get('tile'), doc.get('frame')       # absent in files written before tiling, and whenever it is off
         doc['tile'] = (int(tile[0]), int(tile[1]), str(tile[2])) if tile else None
         doc['frame'] = (int(frame[0]), int(frame[1])) if frame else None
+        doc['baseline'] = _baseline_entry(doc['baseline']) if doc.get('baseline') else None      # absent whenever it is off
     except KeyError as e:
         raise ValueError(f"{path}: entry {e} is missing")
     return doc
@@ -439,12 +535,13 @@ def _unit_float(text: str) -> float:
     return v
 
 
-def save_source_frame(res: dict, names: Sequence[str], kinds: Sequence[str], output_dir: str) -> None:
+def save_source_frame(res: dict, names: Sequence[str], kinds: Sequence[str], output_dir: str, sigmas: bool = False) -> None:
     """What ``Detector.predict(..., source_frame=True)`` added, as PNGs at source size under ``output_dir``:
-    ``source_maps/{good,bad}/<name>.png`` (8-bit gray, the conversion of ``save_anomaly_maps``), ``source_masks/`` (0 / 255)
-    and, where there are overlays, ``overlays/`` (RGB)."""
+    ``source_maps/{good,bad}/<name>.png`` (8-bit gray, the conversion of ``save_anomaly_maps``, its ``sigmas`` included),
+    ``source_masks/`` (0 / 255) and, where there are overlays, ``overlays/`` (RGB)."""
     from PIL import Image
-    folders = [('source_maps', [M.to_u8_hwc(m[None, None], rgb_range=1.0)[0, :, :, 0] for m in res['maps_src']]),
+    k = 1.0 / B.SAVED_MAP_SIGMAS if sigmas else 1.0
+    folders = [('source_maps', [M.to_u8_hwc((m * k if sigmas else m)[None, None], rgb_range=1.0)[0, :, :, 0] for m in res['maps_src']]),
                ('source_masks', [k * 255 for k in res['masks_src']])]
     if 'overlays' in res:
         folders.append(('overlays', res['overlays']))
@@ -503,8 +600,11 @@ def parse_predict_args(argv=None) -> argparse.Namespace:
     p.add_argument('--frame', type=_positive_int, nargs=2, default=None, metavar=('H', 'W'),
                    help="the model's frame: every source is resized to H x W (default: the square of --resolution); with --tile any "
                         "rectangle at least the scale on a side, without it what the network takes whole")
+    add_baseline_args(p, '--baseline', "of --calibrate DIR; written as map_baseline.npz beside the operating point, which then "
+                      "says so, and read back from there when predicting")
     args = p.parse_args(argv)
     check_tile_args(p, args)
+    check_baseline_args(p, args, 'baseline', '--baseline')
     if args.save_regions and not args.input:
         p.error("--save-regions lists the regions of --input images: give --input too")
     if (args.overlay_alpha is not None or args.overlay_contour is not None) and not args.save_overlays:
@@ -527,6 +627,11 @@ def main(argv=None):
     return _run(parse_predict_args(argv))
 
 
+def _note(det: Detector) -> str:
+    """What the summary lines append with a baseline, '' without."""
+    return det.baseline.note() if det.baseline is not None else ""
+
+
 def _run(args) -> dict:
     model_type, class_name, resolution, scale = args.model_type, args.classe, args.resolution, args.scale
     if args.run_dir:
@@ -546,6 +651,7 @@ def _run(args) -> dict:
             raise SystemExit(f"--self-ensemble contradicts the calibrated operating point ({op_file} was calibrated without it)")
     try:
         tile, frame = tile_from_args(args, stored)
+        which_baseline = baseline_from_args(args, stored, op_file.parent)
         side = min(frame) if frame else int(resolution)       # what --map-scales sweep stands for
         spec = check_spec(spec_from_args(args, stored['map_spec'] if stored else None, side // int(scale) * int(scale)))
     except ValueError as e:
@@ -569,14 +675,24 @@ def _run(args) -> dict:
         det = Detector(opt, model, spec, threshold=stored['threshold'] if stored else args.threshold, min_area=min_area,
                        self_ensemble=self_ensemble, hr_size=frame or int(resolution), overlay_alpha=int(args.overlay_alpha * 255 + 0.5),
                        overlay_contour=args.overlay_contour)
+        if which_baseline:
+            det.set_baseline(load_baseline(which_baseline, det))
     except ValueError as e:
         raise SystemExit(str(e))
     out: dict = {}
     if args.calibrate:
+        wrote = {}
+        if args.baseline:                                     # fitted on DIR; the threshold then comes from DIR's leave-one-out maps
+            try:
+                fitted = det.fit_baseline(calib_files, B.FLOOR_REL_DEFAULT if args.baseline_floor is None else args.baseline_floor)
+            except ValueError as e:
+                raise SystemExit(f"--baseline: {e}")
+            b_file = op_file.parent / B.BASELINE_FILE
+            wrote = dict(baseline=baseline_entry(fitted, b_file, fitted.save(b_file, det.spec)))
         t, achieved = det.calibrate(calib_files, args.threshold_fpr, args.threshold_level)
         out['operating_point'] = write_operating_point(op_file, t, args.threshold_fpr, args.threshold_level, achieved, len(calib_files), min_area,
-                                                       det.spec, self_ensemble, ckpt, tile=tile, frame=frame)
-        print(f"Calibrated - {det.spec.text()}, threshold={t:.9g} (fpr {args.threshold_fpr:g} on {args.threshold_level}s of "
+                                                       det.spec, self_ensemble, ckpt, tile=tile, frame=frame, **wrote)
+        print(f"Calibrated - {det.spec.text()}{_note(det)}, threshold={t:.9g} (fpr {args.threshold_fpr:g} on {args.threshold_level}s of "
               f"{len(calib_files)} defect-free images, achieved {achieved:.6f}), min_area={min_area}: {op_file}")
     if files:
         names = unique_names(files)
@@ -590,19 +706,20 @@ def _run(args) -> dict:
                 w.writerow([name, str(files[k]), int(res['defective'][k]), res['defect_pixels'][k], repr(res['map_max'][k]), repr(res['ssim'][k]),
                             repr(res['mse'][k]), repr(res['psnr'][k]), repr(det.threshold)])
         kinds = ['bad' if d else 'good' for d in res['defective']]        # the evaluator's folder names, by prediction
+        sigmas = dict(sigmas=True) if det.baseline is not None else {}     # 8-bit maps of z-scores: z / 16 (baseline.SAVED_MAP_SIGMAS)
         if args.save_anomaly_maps:
-            save_anomaly_maps(res['maps'], names, kinds, out_dir)
+            save_anomaly_maps(res['maps'], names, kinds, out_dir, **sigmas)
         if args.save_masks:
             save_masks(res['masks'], names, kinds, out_dir)
         if args.source_frame:
-            save_source_frame(res, names, kinds, out_dir)
+            save_source_frame(res, names, kinds, out_dir, **sigmas)
         if args.save_regions:
             write_regions_csv(os.path.join(out_dir, 'regions.csv'), res['regions'], names, kinds, res.get('src_box'))
         if args.save_images:
             sr_host = res['sr'].cpu().numpy()
             for k, name in enumerate(names):
                 save_sr_image(sr_host[k], name, kinds[k], det.scale, out_dir)
-        print(f"Predicted - {det.spec.text()}, threshold={det.threshold:.9g}, min_area={min_area}: {sum(res['defective'])} of {len(files)} "
+        print(f"Predicted - {det.spec.text()}{_note(det)}, threshold={det.threshold:.9g}, min_area={min_area}: {sum(res['defective'])} of {len(files)} "
               f"images defective; {os.path.join(out_dir, 'predictions.csv')}" + (" (self-ensemble x8)" if self_ensemble else "")
               + tile_suffix(model))
     return out

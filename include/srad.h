@@ -499,6 +499,26 @@ int srad_region_table(const uint8_t* masks, const float* scores, const uint8_t* 
 int srad_smooth_maps_workspace_bytes(int n_img, int H, int W, int radius, size_t* bytes);
 int srad_smooth_maps(const float* maps, int n_img, int H, int W, const double* weights_host, int radius, float* out,
                      float* img_max_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The per-pixel baseline of anomaly maps (DESIGN.md "Baseline").  maps: DEVICE float32 [n_img, H, W], n_img x H x W in
+ * [1, 2^31).  Every operation named below is one IEEE operation, no fused multiply-adds.
+ *   srad_map_stats_accumulate: per pixel s1 = s1 + (double)m_i and s2 = s2 + (double)m_i * (double)m_i for i = 0 .. n_img - 1 in
+ *     that order, on DEVICE double planes [H, W] the caller has set (zeros for a new fit): a stack split over consecutive calls
+ *     gives the bits of one call.  A NaN pixel makes that pixel's sums NaN.  maps, s1 and s2 must not overlap.
+ *   srad_map_normalize: out = fl32(fl32(m - mu) * inv_sd) with DEVICE float32 planes mu, inv_sd [H, W]; signed, NaN propagates.
+ *   srad_map_normalize_loo: the z-score of a map that is part of sums over n_total >= 3 maps against the other n_total - 1,
+ *     in double: x = m, a = s1 - x, q = s2 - x * x, mean = a / (n_total - 1), var = max(q - a * a / (n_total - 1), 0) /
+ *     (n_total - 2), sd = max(sqrt(var), floor) with a finite floor > 0 (both maxima keep a NaN), out = (float)((x - mean) / sd).
+ * out (DEVICE float32 [n_img, H, W]) may be maps itself (in place); any other overlap is refused.  img_max_out (DEVICE float32
+ * [n_img], may be NULL) receives max(out[i]) per image, NaN if any pixel of image i is NaN; it needs workspace >=
+ * srad_map_normalize_workspace_bytes (1 KiB per image), which may be NULL otherwise.  Four pixels per thread with 16-byte
+ * accesses where H x W is a multiple of 4 and every pointer sits on 16 bytes, one pixel per thread otherwise: the same bits.
+ * Stream-ordered and asynchronous: no host sync, no allocation. */
+int srad_map_stats_accumulate(const float* maps, int n_img, int H, int W, double* s1, double* s2, void* stream);
+int srad_map_normalize_workspace_bytes(int n_img, size_t* bytes);
+int srad_map_normalize(const float* maps, int n_img, int H, int W, const float* mu, const float* inv_sd, float* out,
+                       float* img_max_out, void* workspace, size_t workspace_bytes, void* stream);
+int srad_map_normalize_loo(const float* maps, int n_img, int H, int W, const double* s1, const double* s2, int n_total,
+                           double floor, float* out, float* img_max_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* mean |a-b| (nn.L1Loss, src/loss.py:84) -> *out (device double); workspace >= srad_l1_workspace_bytes */
 int srad_l1_workspace_bytes(size_t* bytes);
