@@ -236,6 +236,12 @@ _SIG = {
                                            C.POINTER(C.c_size_t)]),
     "srad_op_tail_fold_build": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "srad_op_tail_fold": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
+    # the DRCT body end as one launch
+    "srad_drct_ends_supported": (C.c_int, [C.c_int] * 7),
+    "srad_drct_ends_supported_cus": (C.c_int, [C.c_int] * 8),
+    "srad_op_drct_ends_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "srad_op_drct_body_end": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                        _P]),
     # single operators
     "srad_op_gemm": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,

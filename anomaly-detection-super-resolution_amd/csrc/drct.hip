@@ -168,7 +168,15 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
     }
     float* t = cur; cur = nxt; nxt = t;
   }
-  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s, h->fold_in_graph);
+  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s, h->fold_in_graph, h->ends_in_graph);
+}
+
+// Does this forward run the body end as one launch?  Inference handles only, as the fold: srad_drct_sync_params does not
+// refresh its packs.
+bool drct_ends_active(const srad_drct* h, int B, int H, int W) {
+  const srad_drct_config& c = h->cfg;
+  return h->ends_ok && !h->ts.tarena && !h->ts.ready && srad_drct_ends_supported(c.precision, c.embed_dim, c.num_feat, c.in_chans, B, H, W) &&
+         !srad_path_override(SRAD_PATH_ENDS_CHAIN);
 }
 
 // Does this forward end in the folded launch?  Inference handles only: one bound for training gets its weights through
@@ -217,24 +225,30 @@ int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const Drc
 }
 
 int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
-              hipStream_t s, bool fold) {
+              hipStream_t s, bool fold, bool ends) {
   const srad_drct_config& c = h->cfg;
   const int prec = c.precision, T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc, F = c.num_feat;
-  // norm                                              (drct.py:881)
-  SRAD_TRY(srad_launch_layernorm(dense, D, w.body, E, T, E, h->pt.fptr(h->norm_g), h->pt.fptr(h->norm_b), 1e-5f, s));
-  // conv_after_body(...) + x                          (drct.py:893)
-  {
-    GemmParams p = drct_gemm(h, h->conv_after_body, w.body, E, T, w.c1, E);
-    geom(p, H, W);
-    p.R = w.feat0; p.ldr = E;
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
-  }
-  // conv_before_upsample + LeakyReLU(0.01)            (drct.py:844-845, 894)
-  {
-    GemmParams p = drct_gemm(h, h->conv_before_up, w.c1, E, T, w.c2, F);
-    geom(p, H, W);
-    p.act = SRAD_ACT_LRELU; p.slope = 0.01f;
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
+  if (ends) {
+    // norm, conv_after_body + x and conv_before_upsample + LeakyReLU(0.01) as one launch into c2 (kernels_drct_ends.hip)
+    DrctBodyEndParams p{};
+    p.X = dense; p.ldx = D; p.ln_g = h->pt.fptr(h->norm_g); p.ln_b = h->pt.fptr(h->norm_b);
+    p.w1 = h->pt.ends_ptr(h->conv_after_body.w); p.b1 = h->pt.fptr(h->conv_after_body.b);
+    p.w2 = h->pt.ends_ptr(h->conv_before_up.w); p.b2 = h->pt.fptr(h->conv_before_up.b);
+    p.feat0 = w.feat0; p.Y = w.c2; p.B = B; p.H = H; p.W = W; p.E = E;
+    SRAD_TRY(srad_launch_drct_body_end(p, s));
+  } else {
+    // norm                                              (drct.py:881)
+    SRAD_TRY(srad_launch_layernorm(dense, D, w.body, E, T, E, h->pt.fptr(h->norm_g), h->pt.fptr(h->norm_b), 1e-5f, s));
+    // conv_after_body(...) + x                          (drct.py:893)
+    GemmParams p1 = drct_gemm(h, h->conv_after_body, w.body, E, T, w.c1, E);
+    geom(p1, H, W);
+    p1.R = w.feat0; p1.ldr = E;
+    SRAD_TRY(srad_launch_gemm(prec, p1, s));
+    // conv_before_upsample + LeakyReLU(0.01)            (drct.py:844-845, 894)
+    GemmParams p2 = drct_gemm(h, h->conv_before_up, w.c1, E, T, w.c2, F);
+    geom(p2, H, W);
+    p2.act = SRAD_ACT_LRELU; p2.slope = 0.01f;
+    SRAD_TRY(srad_launch_gemm(prec, p2, s));
   }
   float mean3[3];
   drct_mean(c, mean3);
@@ -349,6 +363,12 @@ int srad_drct_create(const srad_drct_config* cfg, srad_drct_t** out) {
   for (int s = cfg->upscale; s > 1; s >>= 1) ++stages;
   for (int j = 0; j < stages; ++j) h->up.push_back(h->pt.add_layer("upsample." + std::to_string(2 * j), 4 * F, F, 9, true));
   h->conv_last = h->pt.add_layer("conv_last", C, F, 9, true);
+  // the body end's two fragment packs (kernels_drct_ends.hip), refreshed by set_param like every other pack
+  h->ends_ok = srad_drct_ends_supported_cus(cfg->precision, E, F, C, 1, 1, 1, 1) != 0;
+  if (h->ends_ok) {
+    h->pt.add_ends_pack(h->conv_after_body);
+    h->pt.add_ends_pack(h->conv_before_up);
+  }
   h->fold_ok = srad_tail_fold_supported(cfg->precision, F, C, cfg->upscale);
   if (h->fold_ok) {
     h->fold = tf_layout(F, C, cfg->upscale);
@@ -433,6 +453,8 @@ int srad_drct_forward(srad_drct_t* h, const float* x, int B, int H, int W, float
   // of the forward, never inside a capture and never as a node of the replayed graph - when one of its sources has changed
   const bool fold = drct_fold_active(h, H, W);
   if (fold != h->fold_in_graph) { h->gc.reset(); h->fold_in_graph = fold; }
+  const bool ends = drct_ends_active(h, B, H, W);                  // likewise per call: the rule depends on the shape
+  if (ends != h->ends_in_graph) { h->gc.reset(); h->ends_in_graph = ends; }
   if (fold && h->fold_stale) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (s) SRAD_CHECK_HIP(hipStreamIsCapturing(s, &st));

@@ -29,6 +29,9 @@ struct srad_drct {
   bool fold_ok = false, fold_stale = true, fold_in_graph = false;
   TailFoldLayout fold{};
   size_t fold_off = 0;
+  // The body-end launch (kernels_drct_ends.hip): ends_ok = the model's shape has it (its packs are entries' ends packs in the
+  // table); which forwards take it is decided per call, and a recorded graph holds one of the two forms.
+  bool ends_ok = false, ends_in_graph = false;
   GraphCache gc;
   TrainState ts;                  // training (drct_train.hip)
   BwdStreams bwd;                 // the backward's side stream for the weight gradients, and its events
@@ -54,8 +57,9 @@ struct DrctStemTail {
 int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s);
 // norm -> conv_after_body + x -> conv_before_upsample -> Upsample -> conv_last (into outn, row stride ld_outn) -> y   (drct.py:881, 893-897)
 // fold: everything after conv_before_upsample as the one folded launch (the caller has checked drct_fold_active and freshness)
+// ends: norm, conv_after_body and conv_before_upsample as the one body-end launch (the caller has checked drct_ends_active)
 int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
-              hipStream_t s, bool fold = false);
+              hipStream_t s, bool fold = false, bool ends = false);
 // The fields both forwards set for Swin block `sw` of an RDG, block k of its five: weights, biases, LayerNorm, geometry, and
 // (mlp_block) the adjust conv's residual and output in the dense buffers cur / nxt
 QkvAttnParams drct_qkv_attn_params(const srad_drct* h, const SwinW& sw, const float* cur, int B, int H, int W);

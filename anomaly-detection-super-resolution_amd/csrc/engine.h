@@ -17,6 +17,7 @@ struct ParamEntry {
   bool tfrag = false;                         // training: keep W^T as bf16 MFMA fragments too (fused backward kernels)
   int qkv_heads = 0;                          // > 0: frag_off holds the per-head [q | k | v] fragment pack (srad_launch_pack_qkv_frag)
   long long frag_lo_off = -1;                 // >= 0 (split-bf16): the lo terms of the fragment pack at frag_off, same geometry
+  long long ends_off = -1;                    // >= 0: 3 x 3 conv also kept as bf16 fragments for DRCT's body-end launch (srad_launch_pack_conv_frag)
 };
 
 struct ConvW {       // one Linear / conv layer
@@ -97,6 +98,12 @@ struct ParamTable {
       bytes += srad_align_up(srad_qkv_frag_bytes(d, heads), 256);
     }
   }
+  // 3 x 3 conv that DRCT's body-end launch also reads, in that kernel's fragment order
+  void add_ends_pack(const ConvW& c) {
+    entries[c.w].ends_off = (long long)bytes;
+    bytes += srad_align_up(srad_drct_conv_frag_bytes(c.n, c.cin), 256);
+  }
+  const void* ends_ptr(int idx) const { return idx < 0 || entries[idx].ends_off < 0 ? nullptr : arena + entries[idx].ends_off; }
   const void* ptr(int idx) const { return idx < 0 ? nullptr : arena + entries[idx].off; }
   const void* frag_ptr(int idx) const { return idx < 0 || entries[idx].frag_off < 0 ? nullptr : arena + entries[idx].frag_off; }
   const void* frag_lo_ptr(int idx) const { return idx < 0 || entries[idx].frag_lo_off < 0 ? nullptr : arena + entries[idx].frag_lo_off; }
@@ -115,6 +122,7 @@ struct ParamTable {
       else if (e.frag_off >= 0) SRAD_TRY(srad_launch_pack_weight_frag(src, arena + e.frag_off, e.n, e.cin, s));
       if (e.frag_lo_off >= 0 && e.qkv_heads > 0) SRAD_TRY(srad_launch_pack_qkv_frag_lo(src, arena + e.frag_lo_off, e.cin, e.qkv_heads, s));
       else if (e.frag_lo_off >= 0) SRAD_TRY(srad_launch_pack_weight_frag_lo(src, arena + e.frag_lo_off, e.n, e.cin, s));
+      if (e.ends_off >= 0) SRAD_TRY(srad_launch_pack_conv_frag(src, arena + e.ends_off, e.n, e.cin, s));
       return srad_launch_pack_weight_padded(prec, src, arena + e.off, e.n, e.cin, e.ntaps, e.n_pad > 0 ? e.n_pad : e.n, e.grp_real, e.grp_pad, s);
     }
     if (e.n_pad > numel) SRAD_CHECK_HIP(hipMemsetAsync(arena + e.off, 0, (size_t)e.n_pad * 4, s));

@@ -35,11 +35,11 @@ struct Prof {
 } g_prof;
 const char* const kClassNames[SRAD_K_COUNT] = {"gemm_bn64", "gemm_bn32", "gemm_bn16", "window_attn", "layernorm",
                                                "layout", "pack_weight", "score", "misc", "mlp_block", "qkv_attn",
-                                               "wgrad", "window_attn_bwd", "layernorm_bwd", "optim", "wgrad_reduce", "mlp_bwd", "ln_qkv", "conv80", "ensemble", "swin_block", "resize", "overlay", "tail_fold"};
+                                               "wgrad", "window_attn_bwd", "layernorm_bwd", "optim", "wgrad_reduce", "mlp_bwd", "ln_qkv", "conv80", "ensemble", "swin_block", "resize", "overlay", "tail_fold", "body_end"};
 }  // namespace
 
 // ---------------------------------------------------------------- path overrides (include/srad.h)
-int g_srad_path_override[SRAD_PATH_END] = {};
+int g_srad_path_override[SRAD_PATH_PLAN2_END] = {};
 extern "C" int srad_set_path_override(int path, int on) {
   SRAD_REQUIRE(srad_path_known(path), "set_path_override: unknown path %d", path);
   g_srad_path_override[path] = on ? 1 : 0;

@@ -165,8 +165,10 @@ int srad_launch_dyn(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&..
 }
 
 // Path overrides of include/srad.h (srad_set_path_override): a process-wide table, all off unless a test sets one
-extern int g_srad_path_override[SRAD_PATH_END];
-static inline bool srad_path_known(int path) { return (path >= 0 && path < SRAD_PATH_COUNT) || (path >= SRAD_PATH_PLAN_FIRST && path < SRAD_PATH_END); }
+extern int g_srad_path_override[SRAD_PATH_PLAN2_END];
+static inline bool srad_path_known(int path) { return (path >= 0 && path < SRAD_PATH_COUNT) || (path >= SRAD_PATH_PLAN_FIRST && path < SRAD_PATH_END) ||
+         (path >= SRAD_PATH_PLAN2_FIRST && path < SRAD_PATH_PLAN2_END);
+}
 static inline bool srad_path_override(int path) { return g_srad_path_override[path] != 0; }
 
 static inline size_t srad_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -267,6 +269,24 @@ bool srad_tail_fold_supported(int prec, int F, int C, int scale);
 int srad_launch_tail_fold_build(const TailFoldLayout& l, char* base, hipStream_t stream);
 int srad_launch_tail_fold(const TailFoldLayout& l, const char* base, const float* X, int B, int H, int W, float* Y, float inv_range,
                           const float mean3[3], hipStream_t stream);
+
+// The end of the DRCT bf16 inference forward's body as one launch (kernels_drct_ends.hip).  One workgroup per
+// 16 pixels of an LR row; E % 4 == 0, E <= 192, 64 features.  Which forwards take it is srad_drct_ends_supported
+// (include/srad.h): one round of tiles on the chip.
+struct DrctBodyEndParams {
+  const float* X; int ldx;           // the last dense buffer [B*H*W][ldx]: columns [0, E) are the body's output
+  const float *ln_g, *ln_b;          // norm
+  const void *w1, *w2;               // conv_after_body / conv_before_upsample as srad_launch_pack_conv_frag packs
+  const float *b1, *b2;
+  const float* feat0;                // [B*H*W][E] conv_first's output, added to conv_after_body's
+  float* Y;                          // c2 [B*H*W][64] = LeakyReLU_0.01(conv_before_upsample(conv_after_body(norm(X)) + feat0))
+  int B, H, W, E, tpr;               // tpr (16-pixel tiles per row) is the launcher's
+};
+// conv [n][cin][3][3] as bf16 MFMA fragments [ceil(n / 16)][9][ceil(cin / 32)][16 x 32] (1 KB tiles: one row tile's taps and
+// chunks are contiguous)
+size_t srad_drct_conv_frag_bytes(int n, int cin);
+int srad_launch_pack_conv_frag(const float* src, void* dst, int n, int cin, hipStream_t stream);
+int srad_launch_drct_body_end(const DrctBodyEndParams& p, hipStream_t stream);
 
 // Packed weight geometry shared by the packer and the GEMM
 static inline int srad_cp(int cin) { return srad_round_up(cin, 32); }
@@ -651,7 +671,7 @@ int srad_launch_add_cols(const float* src, int ld_src, float* dst, int ld_dst, s
 enum {
   SRAD_K_GEMM_BN64 = 0, SRAD_K_GEMM_BN32, SRAD_K_GEMM_BN16, SRAD_K_ATTN, SRAD_K_LAYERNORM,
   SRAD_K_LAYOUT, SRAD_K_PACK, SRAD_K_SCORE, SRAD_K_MISC, SRAD_K_MLP_BLOCK, SRAD_K_QKV_ATTN,
-  SRAD_K_WGRAD, SRAD_K_ATTN_BWD, SRAD_K_LN_BWD, SRAD_K_OPTIM, SRAD_K_WGRAD_REDUCE, SRAD_K_MLP_BWD, SRAD_K_LN_QKV, SRAD_K_CONV80, SRAD_K_ENSEMBLE, SRAD_K_SWIN_BLOCK, SRAD_K_RESIZE, SRAD_K_OVERLAY, SRAD_K_TAIL_FOLD, SRAD_K_COUNT
+  SRAD_K_WGRAD, SRAD_K_ATTN_BWD, SRAD_K_LN_BWD, SRAD_K_OPTIM, SRAD_K_WGRAD_REDUCE, SRAD_K_MLP_BWD, SRAD_K_LN_QKV, SRAD_K_CONV80, SRAD_K_ENSEMBLE, SRAD_K_SWIN_BLOCK, SRAD_K_RESIZE, SRAD_K_OVERLAY, SRAD_K_TAIL_FOLD, SRAD_K_BODY_END, SRAD_K_COUNT
 };
 struct SradProfScope {
   hipStream_t s; int active;

@@ -20,8 +20,8 @@ def _need_cuda(*ts):
 
 # include/srad.h SRAD_PATH_*: the reference paths a test can force instead of the one shape and precision pick
 PATHS = {"unfused_blocks": 0, "qkv_via_gemm": 1, "attn_f32_in": 2, "upconv_one_gemm": 3}
-# ... and its launch-plan overrides (ids from SRAD_PATH_PLAN_FIRST): the launches a default path is compared against
-PLAN_PATHS = {"block_two_launches": 16, "tail_chain": 17}
+# ... and its launch-plan overrides (ids from SRAD_PATH_PLAN_FIRST, then from SRAD_PATH_PLAN2_FIRST): the launches a default path is compared against
+PLAN_PATHS = {"block_two_launches": 16, "tail_chain": 17, "ends_chain": 32}
 
 
 @contextlib.contextmanager
@@ -30,7 +30,9 @@ def path_override(**paths: bool):
     settings on exit.  unfused_blocks is read by the DRCT engine when it is created (forward) and at every backward;
     block_two_launches (a Swin block as qkv_attn + mlp_block where the one-launch kernel would run) whenever a forward
     records its launches, i.e. before the first forward of a shape; tail_chain (the Upsample convolutions, conv_last and the
-    layout change as their own launches where the folded output end would run) at every forward."""
+    layout change as their own launches where the folded output end would run) and ends_chain (the final LayerNorm,
+    conv_after_body and conv_before_upsample as their own launches where the body-end launch would run) at every forward; a
+    model whose choice changes drops its recorded graph."""
     lib = L.lib()
     ids = {name: PATHS[name] if name in PATHS else PLAN_PATHS[name] for name in paths}
     before = {name: lib.srad_get_path_override(i) for name, i in ids.items()}
@@ -199,6 +201,33 @@ def tail_fold(c2: torch.Tensor, up_weights, up_biases, last_w: torch.Tensor, las
     L.check(L.lib().srad_op_tail_fold(L.dptr(c2), B, H, W, Cc, s, fold["ptr"], img_range, mean[0], mean[1], mean[2], L.dptr(y),
                                       L.current_stream_ptr()), "op_tail_fold")
     return y
+
+
+def drct_ends_supported(precision: str, E: int, F: int, C_: int, B: int, H: int, W: int, cus: Optional[int] = None) -> bool:
+    """Does a DRCT inference forward of this shape run its body end as one launch (C ABI
+    ``srad_drct_ends_supported``): bf16, E % 4 == 0, E <= 192, F = 64, gray or RGB, and one round of 16-pixel tiles on the
+    device's CUs (``cus``: on that many instead; host code, needs no GPU)."""
+    prec = L.PRECISIONS[precision]
+    if cus is None:
+        return bool(L.lib().srad_drct_ends_supported(prec, E, F, C_, B, H, W))
+    return bool(L.lib().srad_drct_ends_supported_cus(prec, E, F, C_, B, H, W, cus))
+
+
+def drct_body_end(x: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, feat0: torch.Tensor,
+                  w2: torch.Tensor, b2: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+    """DRCT's body end as one launch (C ABI ``srad_op_drct_body_end``): x [B*H*W, >= E] (row stride = x.stride(0)) ->
+    c2 [B*H*W, 64] = LeakyReLU_0.01(conv_before_upsample(conv_after_body(LayerNorm(x[:, :E])) + feat0))."""
+    _need_cuda(x, ln_g, ln_b, w1, b1, feat0, w2, b2)
+    E, F = w1.shape[0], w2.shape[0]
+    assert x.dim() == 2 and x.shape[0] == B * H * W and x.stride(1) == 1 and x.dtype == torch.float32
+    assert feat0.shape == (B * H * W, E) and feat0.is_contiguous()
+    c2 = torch.empty(B * H * W, F, dtype=torch.float32, device=x.device)
+    keep, ptr, nbytes = L.ws_buffer(L.lib().srad_op_drct_ends_scratch_bytes(E, F), x.device)
+    vec = [t.detach().float().contiguous() for t in (ln_g, ln_b, w1, b1)]
+    w2c, b2c = w2.detach().float().contiguous(), b2.detach().float().contiguous()
+    L.check(L.lib().srad_op_drct_body_end(L.dptr(x), x.stride(0), B, H, W, E, F, *[L.dptr(t) for t in vec], L.dptr(feat0), L.dptr(w2c),
+                                          L.dptr(b2c), L.dptr(c2), ptr, nbytes, L.current_stream_ptr()), "op_drct_body_end")
+    return c2
 
 
 # ----------------------------------------------------------------------------------- backward operators

@@ -649,6 +649,21 @@ int srad_op_tail_fold_build(int F, int C, int scale, const float* w_up0, const f
 int srad_op_tail_fold(const float* c2, int B, int H, int W, int C, int scale, const void* fold, float img_range, float mean0, float mean1,
                       float mean2, float* y, void* stream);
 
+/* The end of the DRCT bf16 inference forward's body as one launch, 16 pixels of an LR row per workgroup.
+ * E % 4 == 0, E <= 192, F = 64; rows and vectors 16-byte aligned, scratch 256-byte aligned.
+ *   srad_drct_ends_supported     does a bf16 inference forward of this shape take it: the limits above, C 1 | 3 and
+ *                                B * H * ceil(W / 16) <= the device's CU count (one round of tiles); _cus: the same on a given count
+ *   srad_op_drct_ends_scratch_bytes  scratch the op needs (the two fragment packs it builds from the fp32 weights)
+ *   srad_op_drct_body_end        c2 [B*H*W][F] = LeakyReLU_0.01(conv_before_upsample(conv_after_body(LayerNorm(x[:, :E])) + feat0))
+ *                                (drct.py:881, 893-894) from x [B*H*W][ldx], w1 [E][E][3][3], w2 [F][E][3][3]; bf16 MFMA operands at
+ *                                the chain's rounding points (LayerNorm output, c1), fp32 accumulation */
+int srad_drct_ends_supported(int precision, int E, int F, int C, int B, int H, int W);
+int srad_drct_ends_supported_cus(int precision, int E, int F, int C, int B, int H, int W, int cus);
+size_t srad_op_drct_ends_scratch_bytes(int E, int F);
+int srad_op_drct_body_end(const float* x, int ldx, int B, int H, int W, int E, int F, const float* ln_g, const float* ln_b, const float* w1,
+                          const float* b1, const float* feat0, const float* w2, const float* b2, float* c2, void* scratch,
+                          size_t scratch_bytes, void* stream);
+
 /* The two kernels of BASELINE config C5's attention (bf16, 64 x 64 windows = 4096-token windows; src/main.py:286), each on its own:
  *   srad_op_ln_qkv              norm1 + attn.qkv (src/drct.py:477, 278) -> qkv_h [M][3][heads][hdp] bf16, the attention's MFMA
  *                               operands: q times qscale (= head_dim^-0.5 log2 e, srad_op_window_attn_qscale), padding columns 0,
@@ -852,6 +867,11 @@ enum { SRAD_PATH_UNFUSED_BLOCKS = 0, SRAD_PATH_QKV_VIA_GEMM = 1, SRAD_PATH_ATTN_
  *   SRAD_PATH_TAIL_CHAIN          DRCT bf16 forward: the Upsample convolutions, conv_last and the layout change as their own
  *                                 launches where the folded output end (srad_op_tail_fold) would run (read at every forward) */
 enum { SRAD_PATH_PLAN_FIRST = 16, SRAD_PATH_BLOCK_TWO_LAUNCHES = 16, SRAD_PATH_TAIL_CHAIN = 17, SRAD_PATH_END = 18 };
+/* ... continued in a second range, so that the ids above and their end stay what callers know (18 .. 31 stay unknown):
+ *   SRAD_PATH_ENDS_CHAIN          DRCT bf16 forward: the final LayerNorm, conv_after_body and conv_before_upsample as their
+ *                                 own launches where the body-end launch (srad_op_drct_body_end) would run (read at every
+ *                                 forward) */
+enum { SRAD_PATH_PLAN2_FIRST = 32, SRAD_PATH_ENDS_CHAIN = 32, SRAD_PATH_PLAN2_END = 33 };
 int srad_set_path_override(int path, int on);
 int srad_get_path_override(int path);
 /* Per-kernel-class device timing with HIP events on the launch stream (bench.py's roofline numbers). */
