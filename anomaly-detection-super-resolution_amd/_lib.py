@@ -269,6 +269,13 @@ _SIG = {
     "srad_swin_block_supported": (C.c_int, [C.c_int] * 9),
     "srad_op_swin_block": (C.c_int, [C.c_int, _P, C.c_int] + [C.c_int] * 8 + [_P] * 15 + [C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_int,
                                      C.c_int, _P, C.c_size_t, _P]),
+    "srad_op_mlp_fold_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "srad_op_mlp_fold_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "srad_op_mlp_fold_compose": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_int), _P]),
+    "srad_swin_block_fold_supported": (C.c_int, [C.c_int] * 9),
+    "srad_op_swin_block_folded": (C.c_int, [C.c_int, _P, C.c_int] + [C.c_int] * 8 + [_P] * 15 + [C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_int,
+                                            C.c_int, _P, C.c_size_t, _P]),
     "srad_bench_swin_block": (C.c_int, [_P] + [C.c_int] * 8 + [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float), _P]),
     "srad_op_gemm_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "srad_op_window_attn": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

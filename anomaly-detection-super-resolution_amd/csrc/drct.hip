@@ -71,6 +71,8 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
       // workgroups and the block shape measured a win over the pair below; this path has no saves and no DropPath
       if (mlp_fused && srad_swin_block_supported(prec, c.window_size, B, H, W, d, sw.heads, sw.hidden, no) &&
           srad_swin_block_wins(d, sw.heads, sw.hidden, no) && !srad_path_override(SRAD_PATH_BLOCK_TWO_LAUNCHES)) {
+        // ... with fc2 folded into the adjust conv (mlp_fold.h) where this forward runs the folded form and the shape has it
+        const bool folded = h->mfold_in_graph && srad_swin_block_fold_supported(prec, c.window_size, B, H, W, d, sw.heads, sw.hidden, no);
         const QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);
         const MlpBlockParams q = drct_mlp_block_params(h, sw, k, attn_h, cur, nxt, T);
         SwinBlockParams b{};
@@ -79,6 +81,12 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
         b.w_proj = q.w_proj; b.w_fc1 = q.w_fc1; b.w_fc2 = q.w_fc2; b.w_adj = q.w_adj;
         b.b_proj = q.b_proj; b.b_fc1 = q.b_fc1; b.b_fc2 = q.b_fc2; b.b_adj = q.b_adj; b.ln2_g = q.ln_g; b.ln2_b = q.ln_b;
         b.act = q.act; b.slope = q.slope; b.alpha = q.alpha; b.R = q.R; b.ldr = q.ldr; b.Y = q.Y; b.ldy = q.ldy; b.yoff = q.yoff;
+        if (folded) {
+          const char* const reg = h->pt.arena + h->mfold_off[i * 5 + k];
+          b.w_adj = reg + h->mfold[i * 5 + k].pack; b.b_adj = reinterpret_cast<const float*>(reg + h->mfold[i * 5 + k].bias);
+          SRAD_TRY(srad_launch_swin_block_folded(b, s));
+          continue;
+        }
         SRAD_TRY(srad_launch_swin_block(b, s));
         continue;
       }
@@ -184,6 +192,10 @@ bool drct_ends_active(const srad_drct* h, int B, int H, int W) {
 bool drct_fold_active(const srad_drct* h, int H, int W) {
   return h->fold_ok && !h->ts.tarena && !h->ts.ready && H >= 2 && W >= 2 && !srad_path_override(SRAD_PATH_TAIL_CHAIN);
 }
+
+// Do this forward's Swin blocks run the folded second half (where a block's launch has one: forward_body)?  Inference handles
+// only, for the same reason; bf16 and the fused blocks are settled at create (mfold_ok).
+bool drct_mfold_active(const srad_drct* h) { return h->mfold_ok && !h->ts.tarena && !h->ts.ready && !srad_path_override(SRAD_PATH_FC2_CHAIN); }
 
 // the fold's sources among the parameters: byte offset in the fold's region, or -1
 long long drct_fold_source(const srad_drct* h, const char* name) {
@@ -374,6 +386,24 @@ int srad_drct_create(const srad_drct_config* cfg, srad_drct_t** out) {
     h->fold = tf_layout(F, C, cfg->upscale);
     h->fold_off = srad_align_up(h->pt.bytes, 256);
   }
+  // the blocks' folded second halves: a region each behind the table's packs and the folded output end
+  h->mfold_ok = cfg->precision == SRAD_PREC_BF16 && ws == 8 && h->fuse_mlp;
+  if (h->mfold_ok) {
+    size_t off = srad_align_up(h->fold_ok ? h->fold_off + h->fold.bytes : h->pt.bytes, 256);
+    for (int i = 0; i < cfg->n_rdg; ++i)
+      for (int k = 0; k < 5; ++k) {
+        const SwinW& sw = h->blocks[i * 5 + k];
+        const MlpFoldLayout l = mf_layout(sw.d, sw.hidden, k < 4 ? cfg->gc : E);
+        const std::string li = "layers." + std::to_string(i), sk = std::to_string(k + 1);
+        h->mfold_src[li + ".swin" + sk + ".mlp.fc2.weight"] = {i * 5 + k, l.w2};
+        h->mfold_src[li + ".swin" + sk + ".mlp.fc2.bias"] = {i * 5 + k, l.b2};
+        h->mfold_src[li + ".adjust" + sk + ".weight"] = {i * 5 + k, l.a};
+        h->mfold_src[li + ".adjust" + sk + ".bias"] = {i * 5 + k, l.ba};
+        h->mfold.push_back(l); h->mfold_off.push_back(off); h->mfold_dirty.push_back(1);
+        off += l.bytes;
+      }
+    h->mfold_end = off;
+  }
   *out = h;
   return SRAD_OK;
 }
@@ -385,7 +415,8 @@ void srad_drct_destroy(srad_drct_t* h) {
 }
 
 // the parameter table's packs, then the folded output end's region (sources, fold, pack, bias table) where the model has one
-static size_t drct_arena_need(const srad_drct_t* h) { return h->fold_ok ? h->fold_off + h->fold.bytes : h->pt.bytes; }
+// and the regions of the blocks' folded second halves
+static size_t drct_arena_need(const srad_drct_t* h) { return h->mfold_ok ? h->mfold_end : (h->fold_ok ? h->fold_off + h->fold.bytes : h->pt.bytes); }
 
 int srad_drct_arena_bytes(const srad_drct_t* h, size_t* bytes) {
   SRAD_REQUIRE(h && bytes, "drct_arena_bytes: null argument");
@@ -400,6 +431,8 @@ int srad_drct_bind_arena(srad_drct_t* h, void* arena, size_t bytes) {
   h->pt.arena = reinterpret_cast<char*>(arena);
   h->pt.arena_bytes = bytes;
   h->fold_stale = true;
+  h->mfold_stale = true;
+  for (char& dirty : h->mfold_dirty) dirty = 1;
   h->gc.reset();
   return SRAD_OK;
 }
@@ -421,6 +454,15 @@ int srad_drct_set_param(srad_drct_t* h, const char* name, const float* dev_src, 
   if (off >= 0) {      // a source of the folded output end: keep its fp32 copy, rebuild before the next forward
     SRAD_CHECK_HIP(hipMemcpyAsync(h->pt.arena + h->fold_off + off, dev_src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
     h->fold_stale = true;
+  }
+  if (h->mfold_ok) {   // likewise a source of a block's folded second half
+    const auto it = h->mfold_src.find(name);
+    if (it != h->mfold_src.end()) {
+      const int blk = it->second.first;
+      SRAD_CHECK_HIP(hipMemcpyAsync(h->pt.arena + h->mfold_off[blk] + it->second.second, dev_src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
+      h->mfold_dirty[blk] = 1;
+      h->mfold_stale = true;
+    }
   }
   return SRAD_OK;
 }
@@ -462,6 +504,20 @@ int srad_drct_forward(srad_drct_t* h, const float* x, int B, int H, int W, float
       return srad_set_error(SRAD_ERR_STATE, "drct_forward: the folded output end is stale and the stream is capturing: run one forward outside the capture first");
     SRAD_TRY(srad_launch_tail_fold_build(h->fold, h->pt.arena + h->fold_off, s));
     h->fold_stale = false;
+  }
+  const bool mfold = drct_mfold_active(h);                         // likewise: a recorded graph holds one of the two second halves
+  if (mfold != h->mfold_in_graph) { h->gc.reset(); h->mfold_in_graph = mfold; }
+  if (mfold && h->mfold_stale) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (s) SRAD_CHECK_HIP(hipStreamIsCapturing(s, &st));
+    if (st != hipStreamCaptureStatusNone)
+      return srad_set_error(SRAD_ERR_STATE, "drct_forward: a folded block weight is stale and the stream is capturing: run one forward outside the capture first");
+    for (size_t blk = 0; blk < h->mfold.size(); ++blk)
+      if (h->mfold_dirty[blk]) {
+        SRAD_TRY(srad_launch_mlp_fold_build(h->mfold[blk], h->pt.arena + h->mfold_off[blk], s));
+        h->mfold_dirty[blk] = 0;
+      }
+    h->mfold_stale = false;
   }
   return srad_run_with_graph(h->gc, h->cfg.use_graph != 0, x, y, workspace, B, H, W, s,
                              [&](hipStream_t st) { return forward_body(h, x, B, H, W, y, w, st); });

@@ -3,7 +3,11 @@
 #pragma once
 #include "train_common.h"
 #include "tail_fold.h"
+#include "mlp_fold.h"
 #include "../../include/srad.h"
+#include <string>
+#include <unordered_map>
+#include <utility>
 
 struct SwinW {
   int d, heads, hidden, shift;
@@ -32,6 +36,15 @@ struct srad_drct {
   // The body-end launch (kernels_drct_ends.hip): ends_ok = the model's shape has it (its packs are entries' ends packs in the
   // table); which forwards take it is decided per call, and a recorded graph holds one of the two forms.
   bool ends_ok = false, ends_in_graph = false;
+  // The folded second halves of the Swin blocks (mlp_fold.h): one region per block behind the folded output
+  // end's, same rules - set_param copies a block's four fp32 sources in and marks it stale, srad_drct_forward rebuilds stale
+  // blocks before it runs or replays anything, a handle bound for training keeps the chain.  The handle keeps both packs.
+  bool mfold_ok = false, mfold_stale = true, mfold_in_graph = false;
+  std::vector<MlpFoldLayout> mfold;           // per block
+  std::vector<size_t> mfold_off;              // per block: byte offset of its region in the arena
+  std::vector<char> mfold_dirty;              // per block: a source changed since its last build
+  std::unordered_map<std::string, std::pair<int, size_t>> mfold_src;   // parameter name -> (block, byte offset in its region)
+  size_t mfold_end = 0;                       // end of the last region
   GraphCache gc;
   TrainState ts;                  // training (drct_train.hip)
   BwdStreams bwd;                 // the backward's side stream for the weight gradients, and its events

@@ -16,6 +16,10 @@
 // keeps the bank rule (48 / 80 elements for the 46- / 77-wide heads of d = 276 / 308), so k | v of all heads fit next to the
 // window tile at every d.
 //
+// FOLD form (inference; mlp_fold.h): x2 is read by the adjust conv alone and nothing non-linear sits between, so
+//   out  = act([A | A W2] . [x1 | h] + (A b2 + b_a)) * alpha (+ R),   h = GELU(fc1(LayerNorm2(x1)))
+// replaces the last two lines: no fc2 phase, no x2, one barrier less, and x1 leaves the registers after the proj epilogue.
+//
 // Write hazard: adjust_k (k < 4) writes columns [d, d + no) of its 16 rows into the same dense buffer whose columns [0, d)
 // other workgroups of this launch still read.  d % 4 == 0, every access is a float4 on a 4-column boundary, so no access
 // straddles the two ranges.  adjust5 writes the other dense buffer.
@@ -58,7 +62,9 @@ struct BlkGeo {
 };
 
 // GD .. KCM: the stage geometry of the MLP half, as mlp_block_kernel's (KCD == KC)
-template <int HDT, int KC, int HEADS, int GD, int KGD, int GM, int KGM, int GN, int KCM>
+// FOLD: the folded second half (mlp_fold.h) - p.w_adj is the pack of [A | A W2], p.b_adj is A b2 + b_a, and
+// p.w_fc2 is not read: proj | fc1 | adjF, no fc2 phase and no x2
+template <int HDT, int KC, int HEADS, int GD, int KGD, int GM, int KGM, int GN, int KCM, bool FOLD>
 __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p) {
   using G = BlkGeo<HDT, KC, HEADS>;
   constexpr int KCD = KC;
@@ -73,6 +79,12 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   __bf16* A1 = reinterpret_cast<__bf16*>(smem + G::OFF_A1);              // [16][SW_LDA] attention output -> LN2(x1) -> x2
   __bf16* Ps = reinterpret_cast<__bf16*>(smem + G::OFF_PS);              // [HEADS][16][SW_LDP] probabilities
   __bf16* Hs = KV;                                                       // [16][SW_LDH] GELU(fc1): k | v are dead by then
+  // FOLD: adjF's A tile instead, [16][LDF] = bf16(x1) in k chunks [0, KC) | GELU(fc1) in chunks [KC, KC + KCM), one k range
+  constexpr int KF = KC + KCM, LDF = KF * 32 + 16;                       // (row stride: 2 mod 4 sixteen-byte units)
+  constexpr bool SPLITK = FOLD && GN == 1;                               // adjust outputs <= 32: k split over the eight waves
+  static_assert(!FOLD || 16 * LDF * 2 <= G::KV_B, "the folded A tile overlays k | v");
+  static_assert(!SPLITK || 4 * 2 * 16 * 16 * 4 <= G::A1_B, "the k parts' partial sums overlay the LayerNorm2 tile");
+  [[maybe_unused]] __bf16* Ft = KV;
   float* vec = reinterpret_cast<float*>(smem + G::OFF_VEC);
   float* v_g1 = vec + SW_NV;                                              // [320] gamma1
   float* v_b1n = v_g1 + 320;                                             // [320] beta1
@@ -110,7 +122,7 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     inf[tid] = info;
   }
 
-  using Chain = MlpChain<GD, KGD, GM, KGM, GN, KCD, KCM>;
+  using Chain = std::conditional_t<FOLD, MlpFoldChain<GD, KGD, GM, GN, KCD, KCM, SPLITK>, MlpChain<GD, KGD, GM, KGM, GN, KCD, KCM>>;
   constexpr int n_mlp = Chain::n_stages;
   constexpr int n_all = QS + n_mlp;
   float* const v_bp = vec; float* const v_bf1 = vec + SW_V_B1; float* const v_bf2 = vec + SW_V_B2; float* const v_ba = vec + SW_V_BA;
@@ -143,6 +155,14 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
       const int step = t.live ? 1024 : 0;
 #pragma unroll
       for (int cc = 0; cc < KC; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + cc * step);
+    } else if constexpr (SPLITK && Chain::stage(u - QS).ph == 3) {
+      // adjF's one stage: column tile wave & 1 (the pack's rows are padded to 128: both tiles exist), k part wave >> 1; a
+      // part that ends past the last chunk reloads that chunk (the MFMA loop zeroes its operand)
+      constexpr MlpStage sg = Chain::stage(u - QS);
+      const char* base = (const char*)p.w_adj + (size_t)(wave_s & 1) * sg.kc * 1024 + fr * 64 + fq * 16;
+      const int p0 = (wave_s >> 1) * sg.nch;
+#pragma unroll
+      for (int cc = 0; cc < sg.nch; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + (size_t)min(p0 + cc, sg.kc - 1) * 1024);
     } else {
       constexpr MlpStage sg = Chain::stage(u - QS);
       const char* w = (const char*)(sg.ph == 0 ? p.w_proj : (sg.ph == 1 ? p.w_fc1 : (sg.ph == 2 ? p.w_fc2 : p.w_adj)));
@@ -405,6 +425,10 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
       const f32x4 gam = *reinterpret_cast<const f32x4*>(v_g2 + min(c4, SW_VD - 4));
       const f32x4 bet = *reinterpret_cast<const f32x4*>(v_b2n + min(c4, SW_VD - 4));
       store_bf4(A1, SW_LDA, c4, c4 < d ? (x1[gg] - mu) * rstd * gam + bet : f32x4{0.f, 0.f, 0.f, 0.f});
+      // FOLD: x1 itself is adjF's first k range (k | v are dead: every wave is past the attention); x1[] dies here
+      if constexpr (FOLD) {
+        if (c4 < 32 * KC) store_bf4(Ft, LDF, c4, c4 < d ? x1[gg] : f32x4{0.f, 0.f, 0.f, 0.f});
+      }
     }
   };
   auto epi_fc1 = [&](int g, const f32x4& c) __attribute__((always_inline)) {
@@ -412,6 +436,9 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     f32x4 v = c + *reinterpret_cast<const f32x4*>(v_bf1 + min(c4, SW_VM - 4));
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = gelu_fast(v[e]);
+    if constexpr (FOLD) {
+      if (c4 < 32 * KCM) store_bf4(Ft + 32 * KC, LDF, c4, c4 < m ? v : f32x4{0.f, 0.f, 0.f, 0.f});
+    } else
     store_bf4(Hs, SW_LDH, c4, c4 < m ? v : f32x4{0.f, 0.f, 0.f, 0.f});      // m % 4 == 0
   };
   auto epi_fc2 = [&](auto GI, const f32x4& c) __attribute__((always_inline)) {
@@ -449,9 +476,38 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
     if constexpr (sg.first) __syncthreads();            // first stage of a phase: the activation tile (A1 / Hs) is complete
     if constexpr (kg == 0) c[0] = f32x4{0.f, 0.f, 0.f, 0.f};
     const bool live = (g * 8 + wave_s) * 16 < (ph == 0 ? d : (ph == 1 ? m : (ph == 2 ? d : no)));
+    if constexpr (SPLITK && ph == 3) {
+      // ---- adjF, k split: this wave's part of [bf16(x1) | h] against its part of [A | A W2]; the four partial tiles of a
+      //      column tile meet in LDS (the LayerNorm2 tile is dead: every wave is past fc1) and waves 0 / 1 add them in part
+      //      order - a fixed order, whatever the waves' timing ----
+      const int ct = wave_s & 1, pt = wave_s >> 1, p0 = pt * nch;
+      const __bf16* ar = Ft + fr * LDF + 8 * fq;
+      bf16x8 af[nch];
+#pragma unroll
+      for (int gq = 0; gq < nch; ++gq) af[gq] = *reinterpret_cast<const bf16x8*>(ar + min(p0 + gq, KF - 1) * 32);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int gq = 0; gq < nch; ++gq) {
+        const u32x4 wz = p0 + gq < KF ? reg[gq] : u32x4{0u, 0u, 0u, 0u};
+        c[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wz), af[gq], c[0], 0, 0, 0);
+      }
+      float* const part = reinterpret_cast<float*>(A1);            // [4 parts][2 column tiles][16 rows][16]
+      *reinterpret_cast<f32x4*>(part + ((pt * 2 + ct) * 16 + fr) * 16 + 4 * fq) = c[0];
+      __syncthreads();
+      if (wave_s < 2) {
+        const float* src = part + (wave_s * 16 + fr) * 16 + 4 * fq;
+        f32x4 sum = *reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+        for (int q = 1; q < 4; ++q) sum += *reinterpret_cast<const f32x4*>(src + q * 512);
+        epi_adj(0, sum);
+      }
+    } else if constexpr (FOLD && ph == 3) {
+      if (live) mma_stage(Ft, LDF, kg * 256, nch, reg, c);
+    } else
     if (live) mma_stage(ph == 2 ? Hs : A1, ph == 2 ? SW_LDH : SW_LDA, kg * 256, nch, reg, c);
     // refill this set, NSETS stages ahead; behind an epilogue that other waves wait for (see mlp_block_kernel)
-    constexpr bool epi_first = sg.last;
+    constexpr bool epi_first = sg.last && !(SPLITK && ph == 3);     // (the split stage is the last and has stored already)
+    if constexpr (SPLITK && ph == 3) return;
     if constexpr (!epi_first) load_w(std::integral_constant<int, QS + s + NSETS>{}, reg);
     if constexpr (epi_first) {
       if constexpr (ph == 0) epi_proj(std::integral_constant<int, g>{}, c[0]);
@@ -463,15 +519,17 @@ __global__ __launch_bounds__(512) void swin_block_kernel(const SwinBlockParams p
   });
 }
 
-template <int HDT, int KC, int HEADS, int GD, int KGD, int GM, int KGM, int GN, int KCM>
+template <int HDT, int KC, int HEADS, int GD, int KGD, int GM, int KGM, int GN, int KCM, bool FOLD>
 int launch_blk(const SwinBlockParams& p, hipStream_t stream) {
   constexpr size_t lds = BlkGeo<HDT, KC, HEADS>::LDS;
   const double T = (double)p.B * p.H * p.W;
-  const double flops = 2.0 * T * (4.0 * p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d) + 4.0 * T * 64.0 * p.d;
-  const double bytes = 4.0 * T * (2.0 * p.d + p.no) + 2.0 * (4.0 * p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
+  // (FOLD: fc2 d x m and adjust no x d are one no x (d + m) GEMM)
+  const double mlp2 = FOLD ? (double)p.no * (p.d + p.m) : (double)p.d * p.m + (double)p.no * p.d;
+  const double flops = 2.0 * T * (4.0 * p.d * p.d + (double)p.d * p.m + mlp2) + 4.0 * T * 64.0 * p.d;
+  const double bytes = 4.0 * T * (2.0 * p.d + p.no) + 2.0 * (4.0 * p.d * p.d + (double)p.d * p.m + mlp2);
   SradProfScope prof(stream, SRAD_K_SWIN_BLOCK, flops, bytes);
   const int nW = (p.H / 8) * (p.W / 8);
-  SRAD_TRY((srad_launch_dyn<swin_block_kernel<HDT, KC, HEADS, GD, KGD, GM, KGM, GN, KCM>>(dim3(p.B * nW, 4), dim3(512), lds, stream, p)));
+  SRAD_TRY((srad_launch_dyn<swin_block_kernel<HDT, KC, HEADS, GD, KGD, GM, KGM, GN, KCM, FOLD>>(dim3(p.B * nW, 4), dim3(512), lds, stream, p)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
 }
@@ -504,7 +562,15 @@ bool srad_swin_block_wins(int d, int heads, int hidden, int no) {
   return false;
 }
 
-int srad_launch_swin_block(const SwinBlockParams& p, hipStream_t stream) {
+// the folded second half (mlp_fold.h): the block shapes with an instance, and of those the ones whose adjF stage form fits -
+// one 128-column group takes the k-split stage, which has two column tiles
+extern "C" int srad_swin_block_fold_supported(int prec, int ws, int B, int H, int W, int d, int heads, int hidden, int no) {
+  return srad_swin_block_supported(prec, ws, B, H, W, d, heads, hidden, no) && (no > SW_SC || no <= 32);
+}
+
+static int launch_swin_block(const SwinBlockParams& p, bool fold, hipStream_t stream) {
+  SRAD_REQUIRE(!fold || srad_swin_block_fold_supported(SRAD_PREC_BF16, 8, p.B, p.H, p.W, p.d, p.heads, p.m, p.no),
+               "swin_block: no folded form for d=%d heads=%d m=%d no=%d", p.d, p.heads, p.m, p.no);
   SRAD_REQUIRE(srad_swin_block_supported(SRAD_PREC_BF16, 8, p.B, p.H, p.W, p.d, p.heads, p.m, p.no),
                "swin_block: unsupported shape %dx%dx%d d=%d heads=%d m=%d no=%d (bf16, window 8, windows x 4 <= CUs)", p.B, p.H, p.W, p.d, p.heads, p.m, p.no);
   SRAD_REQUIRE(p.x && p.ln1_g && p.ln1_b && p.w_qkv && p.b_qkv && p.table && p.w_proj && p.w_fc1 && p.w_fc2 && p.w_adj && p.b_proj && p.b_fc1 &&
@@ -520,8 +586,15 @@ int srad_launch_swin_block(const SwinBlockParams& p, hipStream_t stream) {
   SRAD_REQUIRE(p.Y != p.x || (p.ldy == p.ldx && p.yoff >= p.d), "swin_block: an in-place output must lie behind the block's %d input columns", p.d);
   const SwinKey c = swin_key(p.d, p.heads, p.m, p.no);
 #define X(d_, h_, m_, no_, wpc_) \
-  if (constexpr SwinKey k = swin_key(d_, h_, m_, no_); blk_key_eq(c, k)) return launch_blk<k.hdt, k.kc, k.heads, k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kcm>(p, stream);
+  if (constexpr SwinKey k = swin_key(d_, h_, m_, no_); blk_key_eq(c, k)) { \
+    if (fold) return launch_blk<k.hdt, k.kc, k.heads, k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kcm, true>(p, stream); \
+    return launch_blk<k.hdt, k.kc, k.heads, k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kcm, false>(p, stream); \
+  }
   SRAD_SWIN_SHAPES(X)
 #undef X
   return srad_set_error(SRAD_ERR_ARG, "swin_block: no kernel instance for this geometry");
 }
+
+int srad_launch_swin_block(const SwinBlockParams& p, hipStream_t stream) { return launch_swin_block(p, false, stream); }
+// p.w_adj = the fragment pack of [A | A W2], p.b_adj = A b2 + b_a (mlp_fold.h); p.w_fc2 is not read (any non-null pointer)
+int srad_launch_swin_block_folded(const SwinBlockParams& p, hipStream_t stream) { return launch_swin_block(p, true, stream); }

@@ -39,7 +39,7 @@ const char* const kClassNames[SRAD_K_COUNT] = {"gemm_bn64", "gemm_bn32", "gemm_b
 }  // namespace
 
 // ---------------------------------------------------------------- path overrides (include/srad.h)
-int g_srad_path_override[SRAD_PATH_PLAN2_END] = {};
+int g_srad_path_override[SRAD_PATH_PLAN3_END] = {};
 extern "C" int srad_set_path_override(int path, int on) {
   SRAD_REQUIRE(srad_path_known(path), "set_path_override: unknown path %d", path);
   g_srad_path_override[path] = on ? 1 : 0;

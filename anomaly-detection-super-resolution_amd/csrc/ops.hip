@@ -1,6 +1,7 @@
 // ops.hip - operator-level C ABI: the single kernels behind the engines, exposed so that each
 // row of SURVEY.md §8(a) (A4-A7, A9, B3-B6) can be parity-tested on its own against the oracle.
 #include "engine.h"
+#include "mlp_fold.h"
 #include "../../include/srad.h"
 
 extern "C" {
@@ -372,12 +373,49 @@ int srad_op_swin_block(int precision, const float* x, int ldx, int B, int H, int
   return srad_launch_swin_block(q, s);
 }
 
+// The same block with the folded second half (mlp_fold.h): the four packs the kernel still reads, then [A | A W2] and
+// A b2 + b_a composed behind them in scratch
+int srad_op_swin_block_folded(int precision, const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, int m, int no,
+                              const float* ln1_g, const float* ln1_b, const float* w_qkv, const float* b_qkv, const float* table,
+                              const float* w_proj, const float* b_proj, const float* ln2_g, const float* ln2_b, const float* w_fc1,
+                              const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj,
+                              int act, float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
+                              size_t scratch_bytes, void* stream) {
+  SRAD_REQUIRE(x && ln1_g && ln1_b && w_qkv && b_qkv && table && w_proj && b_proj && ln2_g && ln2_b && w_fc1 && b_fc1 && w_fc2 && b_fc2 && w_adj &&
+                   b_adj && y && scratch, "op_swin_block_folded: null argument");
+  SRAD_REQUIRE(srad_swin_block_fold_supported(precision, 8, B, H, W, d, heads, m, no),
+               "op_swin_block_folded: unsupported: precision %d, %dx%dx%d, d=%d heads=%d m=%d no=%d (bf16, 8 x 8 windows, windows x 4 <= CUs, no <= 32 or > 128)",
+               precision, B, H, W, d, heads, m, no);
+  size_t off[10];
+  swin_scratch_parts(d, heads, m, no, off);
+  const MlpFoldLayout l = mf_layout(d, m, no);
+  SRAD_REQUIRE(scratch_bytes >= off[5] + l.bytes && ((uintptr_t)scratch & 255) == 0,
+               "op_swin_block_folded: scratch %zu bytes, %zu needed (256-byte aligned)", scratch_bytes, off[5] + l.bytes);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* sc = reinterpret_cast<char*>(scratch);
+  SRAD_TRY(srad_launch_pack_qkv_frag(w_qkv, sc + off[0], d, heads, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_proj, sc + off[1], d, d, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fc1, sc + off[2], m, d, s));
+  char* const fold = sc + off[5];
+  SRAD_TRY(srad_mlp_fold_from_sources(l, fold, w_fc2, b_fc2, w_adj, b_adj, s));
+  SwinBlockParams q{};
+  q.x = x; q.ldx = ldx; q.B = B; q.H = H; q.W = W; q.shift = shift; q.d = d; q.heads = heads; q.m = m; q.no = no;
+  q.ln1_g = ln1_g; q.ln1_b = ln1_b; q.w_qkv = sc + off[0]; q.b_qkv = b_qkv; q.table = table;
+  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = fold + l.pack; q.w_adj = fold + l.pack;
+  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.b_adj = reinterpret_cast<const float*>(fold + l.bias); q.ln2_g = ln2_g; q.ln2_b = ln2_b;
+  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff;
+  return srad_launch_swin_block_folded(q, s);
+}
+
 // Diagnostic twin of srad_bench_qkv_attn + srad_bench_mlp_block for the one-launch block: microseconds per launch, back-to-back
 // launches.  x, y: [B*H*W][320] fp32; the output goes to columns [d, d + no) of y (adjust_k's epilogue), or [0, no) where those do not fit.
 int srad_bench_swin_block(const float* x, int B, int H, int W, int shift, int d, int heads, int m, int no, const float* w_fp32,
                           float* y, void* scratch, size_t scratch_bytes, int iters, float* us_out, void* stream) {
   SRAD_REQUIRE(x && w_fp32 && y && scratch && us_out && iters > 0, "bench_swin_block: bad argument");
+  const bool folded = (shift & 0x20000) != 0;       // bit 17 of `shift`: the folded second half, [A | A W2] cut from w_fp32 like every weight
+  shift &= 0xffff;
   SRAD_REQUIRE(srad_swin_block_supported(SRAD_PREC_BF16, 8, B, H, W, d, heads, m, no) && no <= 320, "bench_swin_block: unsupported shape");
+  SRAD_REQUIRE(!folded || srad_swin_block_fold_supported(SRAD_PREC_BF16, 8, B, H, W, d, heads, m, no), "bench_swin_block: no folded form for this shape");
   size_t off[10];
   swin_scratch_parts(d, heads, m, no, off);
   SRAD_REQUIRE(scratch_bytes >= off[5] && ((uintptr_t)scratch & 255) == 0, "bench_swin_block: scratch too small or not 256-byte aligned");
@@ -394,12 +432,19 @@ int srad_bench_swin_block(const float* x, int B, int H, int W, int shift, int d,
   q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = sc + off[3]; q.w_adj = sc + off[4];
   q.b_proj = q.b_fc1 = q.b_fc2 = q.b_adj = q.ln2_g = q.ln2_b = w_fp32;
   q.act = SRAD_ACT_LRELU; q.slope = 0.2f; q.alpha = 1.f; q.Y = y; q.ldy = 320; q.yoff = d + no <= 320 ? d : 0;
-  for (int i = 0; i < 3; ++i) SRAD_TRY(srad_launch_swin_block(q, s));
+  if (folded) {                                     // the pack of a [no][32 (KC + KCM)] matrix over the fc2 and adjust packs' space
+    const MlpFoldLayout l = mf_layout(d, m, no);
+    SRAD_REQUIRE(off[5] - off[3] >= (size_t)srad_np(no) * l.kf * 2, "bench_swin_block: the folded pack does not fit the scratch layout");
+    SRAD_TRY(srad_launch_pack_weight_frag(w_fp32, sc + off[3], no, l.kf, s));
+    q.w_adj = sc + off[3];
+  }
+  const auto launch = folded ? srad_launch_swin_block_folded : srad_launch_swin_block;
+  for (int i = 0; i < 3; ++i) SRAD_TRY(launch(q, s));
   hipEvent_t e0, e1;
   SRAD_CHECK_HIP(hipEventCreate(&e0));
   SRAD_CHECK_HIP(hipEventCreate(&e1));
   SRAD_CHECK_HIP(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) SRAD_TRY(srad_launch_swin_block(q, s));
+  for (int i = 0; i < iters; ++i) SRAD_TRY(launch(q, s));
   SRAD_CHECK_HIP(hipEventRecord(e1, s));
   SRAD_CHECK_HIP(hipEventSynchronize(e1));
   float ms = 0.f;

@@ -165,9 +165,9 @@ int srad_launch_dyn(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&..
 }
 
 // Path overrides of include/srad.h (srad_set_path_override): a process-wide table, all off unless a test sets one
-extern int g_srad_path_override[SRAD_PATH_PLAN2_END];
+extern int g_srad_path_override[SRAD_PATH_PLAN3_END];
 static inline bool srad_path_known(int path) { return (path >= 0 && path < SRAD_PATH_COUNT) || (path >= SRAD_PATH_PLAN_FIRST && path < SRAD_PATH_END) ||
-         (path >= SRAD_PATH_PLAN2_FIRST && path < SRAD_PATH_PLAN2_END);
+         (path >= SRAD_PATH_PLAN2_FIRST && path < SRAD_PATH_PLAN2_END) || (path >= SRAD_PATH_PLAN3_FIRST && path < SRAD_PATH_PLAN3_END);
 }
 static inline bool srad_path_override(int path) { return g_srad_path_override[path] != 0; }
 
@@ -431,6 +431,15 @@ struct SwinBlockParams {
 // is this block shape in the table of shapes for which the single launch measured faster than the pair?
 bool srad_swin_block_wins(int d, int heads, int hidden, int no);
 int srad_launch_swin_block(const SwinBlockParams& p, hipStream_t stream);
+// The same launch with the folded second half (mlp_fold.h): proj | fc1 | adjF.  w_adj = the fragment pack of
+// [A | A W2], b_adj = A b2 + b_a, w_fc2 is not read.  (srad_swin_block_fold_supported is part of the C ABI: include/srad.h)
+int srad_launch_swin_block_folded(const SwinBlockParams& p, hipStream_t stream);
+// A block's folded weight from the fp32 sources already in its region (three launches, profiler class pack_weight; once per
+// weight load, never inside a capture); from_sources copies the four tensors in first
+struct MlpFoldLayout;
+int srad_launch_mlp_fold_build(const MlpFoldLayout& l, char* base, hipStream_t stream);
+int srad_mlp_fold_from_sources(const MlpFoldLayout& l, char* base, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj,
+                               hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
 // Backward kernels (kernels_wgrad.hip, kernels_bwd.hip) - the training path of reference src/trainer.py:152-222.

@@ -41,6 +41,30 @@ struct MlpChain {
   }
 };
 
+// ---- the folded chain (mlp_fold.h): proj | fc1 | adjF, adjF = [bf16(x1) | h] . [A | A W2]^T over KCD + KCM
+//      k chunks.  SPLITK (adjust outputs <= 32: two column tiles): ONE stage - wave w owns column tile w & 1 and k part w >> 1
+//      of four, each PS = ceil((KCD + KCM) / 4) <= 8 chunks; else 128-column groups x 8-chunk k groups like the other phases ----
+template <int GD, int KGD, int GM, int GN, int KCD, int KCM, bool SPLITK>
+struct MlpFoldChain {
+  static_assert(KGD == (KCD + 7) / 8, "k groups are 8 chunks wide");
+  static constexpr int KF = KCD + KCM, KGF = (KF + 7) / 8, PS = (KF + 3) / 4;
+  static_assert(!SPLITK || PS <= 8, "a k part fits one register set");
+  static constexpr int n_proj = GD * KGD, n_fc1 = GM * KGD, n_adj = SPLITK ? 1 : GN * KGF;
+  static constexpr int n_stages = n_proj + n_fc1 + n_adj;
+  static constexpr MlpStage stage(int s) {                        // (stages past the end: the last one, for the look-ahead)
+    if (s > n_stages - 1) s = n_stages - 1;
+    int ph = 0, kgs = KGD, kc = KCD;
+    if (s < n_proj) ph = 0;
+    else if ((s -= n_proj) < n_fc1) ph = 1;
+    else {
+      s -= n_fc1; ph = 3; kgs = KGF; kc = KF;
+      if (SPLITK) return MlpStage{3, 0, 0, KF, PS, true, true};
+    }
+    const int g = s / kgs, kg = s - g * kgs;
+    return MlpStage{ph, g, kg, kc, kc - kg * 8 < 8 ? kc - kg * 8 : 8, s == 0, kg == kgs - 1};
+  }
+};
+
 // ---- DRCT-L's five Swin block shapes, the one table behind every instance of the four kernels:
 //      (d, heads, MLP hidden, adjust outputs, qkv_attn workgroups per CU).  The last column is tuning that cannot be derived.
 //      Dispatch matches the geometry key, not d: another shape with the same key (d = 184 ...) runs the same instance. ----

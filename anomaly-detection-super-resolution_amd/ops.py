@@ -21,7 +21,7 @@ def _need_cuda(*ts):
 # include/srad.h SRAD_PATH_*: the reference paths a test can force instead of the one shape and precision pick
 PATHS = {"unfused_blocks": 0, "qkv_via_gemm": 1, "attn_f32_in": 2, "upconv_one_gemm": 3}
 # ... and its launch-plan overrides (ids from SRAD_PATH_PLAN_FIRST, then from SRAD_PATH_PLAN2_FIRST): the launches a default path is compared against
-PLAN_PATHS = {"block_two_launches": 16, "tail_chain": 17, "ends_chain": 32}
+PLAN_PATHS = {"block_two_launches": 16, "tail_chain": 17, "ends_chain": 32, "fc2_chain": 48}
 
 
 @contextlib.contextmanager
@@ -31,7 +31,8 @@ def path_override(**paths: bool):
     block_two_launches (a Swin block as qkv_attn + mlp_block where the one-launch kernel would run) whenever a forward
     records its launches, i.e. before the first forward of a shape; tail_chain (the Upsample convolutions, conv_last and the
     layout change as their own launches where the folded output end would run) and ends_chain (the final LayerNorm,
-    conv_after_body and conv_before_upsample as their own launches where the body-end launch would run) at every forward; a
+    conv_after_body and conv_before_upsample as their own launches where the body-end launch would run) and fc2_chain (a
+    Swin block's fc2 and adjust conv as the chain's two GEMMs where the folded second half would run) at every forward; a
     model whose choice changes drops its recorded graph."""
     lib = L.lib()
     ids = {name: PATHS[name] if name in PATHS else PLAN_PATHS[name] for name in paths}
@@ -742,6 +743,59 @@ def swin_block(x: torch.Tensor, ln1_g, ln1_b, w_qkv, b_qkv, table, w_proj, b_pro
     L.check(L.lib().srad_op_swin_block(L.PRECISIONS[precision], L.dptr(x), x.stride(0), B, H, W, shift, d, heads, m, no, *[L.dptr(k) for k in keep],
                                        int(act), float(slope), float(alpha), L.dptr(residual), 0 if residual is None else residual.stride(0),
                                        L.dptr(out), out.stride(0), int(out_offset), sp, sb, L.current_stream_ptr()), "op_swin_block")
+    return out
+
+
+def mlp_fold_compose(w_fc2: torch.Tensor, b_fc2: torch.Tensor, w_adj: torch.Tensor, b_adj: torch.Tensor) -> dict:
+    """The folded second-half weight of a Swin block built on the device (``srad_op_mlp_fold_compose``): ``wf`` fp32
+    [no, 32 (ceil(d / 32) + ceil(m / 32))] = [A | A W2] with both parts zero-padded to whole 32-wide chunks, ``bias`` fp32 [no] =
+    A b2 + b_a, ``pack`` (the bf16 fragment pack, raw bytes), ``kc32`` (the column where the A W2 part starts)."""
+    _need_cuda(w_fc2, b_fc2, w_adj, b_adj)
+    d, m = w_fc2.shape
+    no = w_adj.shape[0]
+    f = lambda t: t.detach().float().contiguous()
+    keep = [f(w_fc2), f(b_fc2), f(w_adj.reshape(no, d)), f(b_adj)]
+    lib = L.lib()
+    sbuf, sp, sb = L.ws_buffer(lib.srad_op_mlp_fold_scratch_bytes(d, m, no), w_fc2.device)
+    offs = [C.c_size_t() for _ in range(3)]
+    kf = C.c_int()
+    L.check(lib.srad_op_mlp_fold_compose(d, m, no, *[L.dptr(t) for t in keep], sp, sb, *[C.byref(o) for o in offs], C.byref(kf),
+                                         L.current_stream_ptr()), "op_mlp_fold_compose")
+    base = sp.value - sbuf.data_ptr()
+
+    def view(off, nbytes, dtype):
+        return sbuf[base + off:base + off + nbytes].view(dtype)
+    wf = view(offs[0].value, no * kf.value * 4, torch.float32).reshape(no, kf.value)
+    pack_bytes = (no + 127) // 128 * 128 * kf.value * 2
+    return {"wf": wf, "bias": view(offs[2].value, no * 4, torch.float32), "pack": view(offs[1].value, pack_bytes, torch.uint8),
+            "kc32": 32 * ((d + 31) // 32), "buf": sbuf}
+
+
+def swin_block_fold_supported(B: int, H: int, W: int, d: int, heads: int, hidden: int, no: int, ws: int = 8, precision: str = "bf16") -> bool:
+    """Does the one-launch Swin block kernel have a folded form for this shape (``srad_swin_block_fold_supported``)?"""
+    return bool(L.lib().srad_swin_block_fold_supported(L.PRECISIONS[precision], ws, B, H, W, d, heads, hidden, no))
+
+
+def swin_block_folded(x: torch.Tensor, ln1_g, ln1_b, w_qkv, b_qkv, table, w_proj, b_proj, ln2_g, ln2_b, w_fc1, b_fc1, w_fc2, b_fc2, w_adj, b_adj,
+                      B: int, H: int, W: int, shift: int, heads: int, *, act: int = L.ACT_LRELU, slope: float = 0.2, alpha: float = 1.0,
+                      residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_offset: int = 0,
+                      precision: str = "bf16") -> torch.Tensor:
+    """``swin_block`` with fc2 folded into the adjust conv (``srad_op_swin_block_folded``; inference): the same arguments and
+    the same result up to rounding - adjust(x1 + fc2(h) + b2) as one GEMM [A | A W2] [x1 | h] + (A b2 + b_a)."""
+    _need_cuda(x, w_qkv, w_proj, w_fc1, w_fc2, w_adj)
+    d = w_qkv.shape[1]
+    m, no = w_fc1.shape[0], w_adj.shape[0]
+    assert x.dim() == 2 and x.shape[0] == B * H * W and x.stride(1) == 1 and x.dtype == torch.float32 and w_qkv.shape[0] == 3 * d
+    f = lambda t: t.detach().float().contiguous()
+    keep = [f(ln1_g), f(ln1_b), f(w_qkv), f(b_qkv), f(table), f(w_proj), f(b_proj), f(ln2_g), f(ln2_b), f(w_fc1), f(b_fc1), f(w_fc2), f(b_fc2),
+            f(w_adj.reshape(no, d)), f(b_adj)]
+    if out is None:
+        out = torch.empty(x.shape[0], no, dtype=torch.float32, device=x.device)
+    lib = L.lib()
+    sbuf, sp, sb = L.ws_buffer(lib.srad_op_swin_scratch_bytes(d, heads, m, no) + lib.srad_op_mlp_fold_scratch_bytes(d, m, no), x.device)
+    L.check(lib.srad_op_swin_block_folded(L.PRECISIONS[precision], L.dptr(x), x.stride(0), B, H, W, shift, d, heads, m, no, *[L.dptr(k) for k in keep],
+                                          int(act), float(slope), float(alpha), L.dptr(residual), 0 if residual is None else residual.stride(0),
+                                          L.dptr(out), out.stride(0), int(out_offset), sp, sb, L.current_stream_ptr()), "op_swin_block_folded")
     return out
 
 

@@ -631,6 +631,29 @@ int srad_op_swin_block(int precision, const float* x, int ldx, int B, int H, int
                        const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
                        float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
                        size_t scratch_bytes, void* stream);
+/* The folded second half of a Swin block (inference).  Nothing non-linear sits between mlp.fc2 and the RDG's
+ * adjust conv, so adjust(x1 + fc2(h) + b2) = [A | A W2] [x1 | h] + (A b2 + b_a): one GEMM with `no` output columns.
+ * srad_op_mlp_fold_compose builds, in caller scratch (>= srad_op_mlp_fold_scratch_bytes(d, m, no), 256-byte aligned) and from
+ * the fp32 tensors in PyTorch layout, Wf = [A zero-padded to 32 ceil(d / 32) columns | A W2 zero-padded to 32 ceil(m / 32)]
+ * as fp32 [no][*kf], its bf16 fragment pack and bf = A b2 + b_a [no]; products accumulate in fp64 and are rounded to fp32 once.
+ * The three results lie at the byte offsets it reports.  srad_op_swin_block_folded is srad_op_swin_block with that second
+ * half (proj | fc1 | adjF, no fc2 phase); its scratch holds srad_op_swin_scratch_bytes(d, heads, m, no) followed by
+ * srad_op_mlp_fold_scratch_bytes(d, m, no).  srad_swin_block_fold_supported: the shapes of srad_swin_block_supported whose
+ * adjust width the folded stage takes (no <= 32 or no > 128). */
+size_t srad_op_mlp_fold_scratch_bytes(int d, int m, int no);
+/* the scratch region's layout, no device needed: off[8] = byte offsets of the copies of w_fc2, b_fc2, w_adj, b_adj, of Wf, the
+ * pack and bf, and the region's size */
+int srad_op_mlp_fold_layout(int d, int m, int no, size_t* off, int* kf);
+int srad_op_mlp_fold_compose(int d, int m, int no, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj,
+                             void* scratch, size_t scratch_bytes, size_t* wf_off, size_t* pack_off, size_t* bias_off, int* kf,
+                             void* stream);
+int srad_swin_block_fold_supported(int precision, int ws, int B, int H, int W, int d, int heads, int m, int no);
+int srad_op_swin_block_folded(int precision, const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, int m, int no,
+                              const float* ln1_g, const float* ln1_b, const float* w_qkv, const float* b_qkv, const float* table,
+                              const float* w_proj, const float* b_proj, const float* ln2_g, const float* ln2_b, const float* w_fc1,
+                              const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj,
+                              int act, float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
+                              size_t scratch_bytes, void* stream);
 
 /* DRCT's output end folded into one launch.  Everything after conv_before_upsample's LeakyReLU - the Upsample
  * convolutions with their PixelShuffles, conv_last, then / img_range + mean (src/drct.py:694-713, 842-847, 894-897) - is linear:
@@ -872,6 +895,11 @@ enum { SRAD_PATH_PLAN_FIRST = 16, SRAD_PATH_BLOCK_TWO_LAUNCHES = 16, SRAD_PATH_T
  *                                 own launches where the body-end launch (srad_op_drct_body_end) would run (read at every
  *                                 forward) */
 enum { SRAD_PATH_PLAN2_FIRST = 32, SRAD_PATH_ENDS_CHAIN = 32, SRAD_PATH_PLAN2_END = 33 };
+/* ... and in a third range (33 .. 47 stay unknown):
+ *   SRAD_PATH_FC2_CHAIN           DRCT bf16 inference forward: a Swin block's fc2 and the adjust conv as the two GEMMs of the
+ *                                 chain where the folded second half (srad_op_swin_block_folded) would run (read at every
+ *                                 forward) */
+enum { SRAD_PATH_PLAN3_FIRST = 48, SRAD_PATH_FC2_CHAIN = 48, SRAD_PATH_PLAN3_END = 49 };
 int srad_set_path_override(int path, int on);
 int srad_get_path_override(int path);
 /* Per-kernel-class device timing with HIP events on the launch stream (bench.py's roofline numbers). */
@@ -893,7 +921,8 @@ int srad_bench_qkv_attn(const float* x, int ldx, int B, int H, int W, int shift,
                         void* out /* written as bf16 [B*H*W][d] */, void* scratch, size_t scratch_bytes, int iters, float* us_out,
                         void* stream);
 /* tools/swin_block_bench.py: the one-launch Swin block on synthetic operands (x, y: [B*H*W][320] fp32; y also takes the
- * output: columns [d, d + no), or [0, no) where those do not fit), microseconds per launch, back-to-back launches. */
+ * output: columns [d, d + no), or [0, no) where those do not fit), microseconds per launch, back-to-back launches.  Bit 17 of
+ * `shift` selects the folded second half. */
 int srad_bench_swin_block(const float* x, int B, int H, int W, int shift, int d, int heads, int m, int no, const float* w_fp32,
                           float* y, void* scratch, size_t scratch_bytes, int iters, float* us_out, void* stream);
 /* tools/wgrad_bench.py: one Swin block's five weight gradients as the training step issues them (one deferred launch +

@@ -1,6 +1,7 @@
 """The one-launch Swin block (swin_block_kernel) against the pair it replaces (qkv_attn + mlp_block<16>), per block shape of
 DRCT-L at the benched geometry (B = 4, 32 x 32), shift 0 and 4: back-to-back launches, microseconds per launch, median of 3.
-A shape goes into the engine's table (srad_swin_block_wins) only if  block < qkv_attn + mlp_block + BOUNDARY."""
+A shape goes into the engine's table (srad_swin_block_wins) only if  block < qkv_attn + mlp_block + BOUNDARY.
+Each line ends with the folded second half against the unfolded block, three alternating runs of each."""
 import ctypes as C, os, statistics, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from srad_amd import _lib as L
@@ -35,7 +36,19 @@ with torch.cuda.stream(s):
                                                          L.current_stream_ptr()))
             sbk = med(lambda us: lib.srad_bench_swin_block(L.dptr(x), B, H, W, shift, d, heads, m, no, L.dptr(w), L.dptr(y), sp, sb, iters, C.byref(us),
                                                           L.current_stream_ptr()))
+            # the folded second half (bit 17 of the shift argument): the three runs of each form alternate, and the
+            # folded form counts as faster when its median is below the unfolded minimum
+            runs = {False: [], True: []}
+            for _ in range(3):
+                for folded in (False, True):
+                    us = C.c_float()
+                    L.check(lib.srad_bench_swin_block(L.dptr(x), B, H, W, shift | (0x20000 if folded else 0), d, heads, m, no, L.dptr(w), L.dptr(y),
+                                                      sp, sb, iters, C.byref(us), L.current_stream_ptr()), "bench")
+                    runs[folded].append(us.value)
+            fmed, umin = statistics.median(runs[True]), min(runs[False])
             pair = qa + mb + BOUNDARY
             print(f"d={d} heads={heads} m={m} no={no} shift={shift}: qkv_attn {qa:6.2f} + mlp_block {mb:6.2f} + {BOUNDARY} = {pair:6.2f} us | "
-                  f"swin_block {sbk:6.2f} us | {'WIN' if sbk < pair else 'loss'} ({pair - sbk:+.2f})", flush=True)
+                  f"swin_block {sbk:6.2f} us | {'WIN' if sbk < pair else 'loss'} ({pair - sbk:+.2f}) | folded "
+                  f"{' '.join(f'{v:6.2f}' for v in runs[True])} vs unfolded {' '.join(f'{v:6.2f}' for v in runs[False])} us: "
+                  f"{'FASTER' if fmed < umin else 'not faster'} ({umin - fmed:+.2f})", flush=True)
 torch.cuda.synchronize()

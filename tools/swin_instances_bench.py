@@ -52,6 +52,9 @@ with torch.cuda.stream(s):
             if on("swin_block"):
                 us = med(lambda u: lib.srad_bench_swin_block(L.dptr(x), 4, 32, 32, shift, d, heads, m, no, L.dptr(w), L.dptr(y), sp, sb, ITERS, C.byref(u), st))
                 print(f"swin_block d={d} B=4 shift={shift} {us:.3f}", flush=True)
+                # the folded second half: bit 17 of the shift argument
+                us = med(lambda u: lib.srad_bench_swin_block(L.dptr(x), 4, 32, 32, shift | 0x20000, d, heads, m, no, L.dptr(w), L.dptr(y), sp, sb, ITERS, C.byref(u), st))
+                print(f"swin_block d={d} folded B=4 shift={shift} {us:.3f}", flush=True)
         if not on("mlp_block"):
             continue
         for fm, M in ((16, 4096), (32, 8192), (64, 32768)):
