@@ -195,6 +195,8 @@ _SIG = {
     "srad_error_maps": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "srad_error_maps_multi": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, _P, _P,
                                         C.c_size_t, _P]),
+    "srad_gms_map_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "srad_gms_maps": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "srad_pixel_auc_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
     "srad_pixel_roc_auc": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
     "srad_pixel_pr_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),

@@ -2,7 +2,8 @@
 // their gradients: L1 (nn.L1Loss), MSE (nn.MSELoss), PSNR (PSNRLoss, loss.py:63-70) and SSIM (calc_ssim, loss.py:9-52).
 // Every CLI path of the reference hard-codes '1*L1' (main.py:453, evaluate.py:317); the other three exist for
 // completeness of the `Loss(opt, ckp)` surface.  All are HBM-bound elementwise / small-stencil work: coalesced float
-// loads, double partial sums per workgroup, a fixed-order finish (results are bit-reproducible).
+// loads, double partial sums per workgroup, a fixed-order finish (results are bit-reproducible).  The kinds GMS and MSGMS
+// (not in the reference) enter through the same three entry points; their kernels are in kernels_gms.hip (gms_loss.h).
 //
 // SSIM loss, as written in the reference (quirks kept verbatim):
 //   s = clamp(x / rgb_range, 0, 1); shave = scale + 6 with scale hard-wired to 4 (loss.py:61) -> crop 10 px when the
@@ -14,6 +15,7 @@
 // then the luminance weights, the clamp's indicator and 1 / rgb_range.
 #include "../../include/srad.h"
 #include "srad_common.h"
+#include "gms_loss.h"
 #include <algorithm>
 
 namespace {
@@ -218,6 +220,7 @@ int srad_l1_loss(const float* a, const float* b, int64_t n, double* out, void* w
 
 int srad_loss_workspace_bytes(int kind, int B, int C, int H, int W, size_t* bytes) {
   SRAD_REQUIRE(bytes && B > 0 && C > 0 && H > 0 && W > 0, "loss_workspace_bytes: bad argument");
+  if (kind == SRAD_LOSS_GMS || kind == SRAD_LOSS_MSGMS) return srad_gms_loss_workspace_bytes("loss_workspace_bytes", kind, B, C, H, W, bytes);
   size_t n = LOSS_NB * sizeof(double);
   if (kind == SRAD_LOSS_SSIM) n += 5 * srad_align_up((size_t)B * H * W * sizeof(float), 256);   // lx, ly, dm1, de11, de12
   *bytes = n;
@@ -227,12 +230,16 @@ int srad_loss_workspace_bytes(int kind, int B, int C, int H, int W, size_t* byte
 int srad_loss_forward(int kind, const float* sr, const float* hr, int B, int C, int sH, int sW, int H, int W, float rgb_range,
                       int batch_size, double* out2, void* workspace, size_t workspace_bytes, void* stream) {
   SRAD_REQUIRE(sr && hr && out2 && workspace, "loss_forward: null argument");
-  SRAD_REQUIRE(kind >= SRAD_LOSS_L1 && kind <= SRAD_LOSS_SSIM, "loss_forward: unknown loss kind %d", kind);
+  SRAD_REQUIRE(kind >= SRAD_LOSS_L1 && kind <= SRAD_LOSS_MSGMS, "loss_forward: unknown loss kind %d", kind);
   size_t need = 0;
   SRAD_TRY(srad_loss_workspace_bytes(kind, B, C, H, W, &need));
   SRAD_REQUIRE(workspace_bytes >= need, "loss_forward: workspace %zu bytes, %zu needed", workspace_bytes, need);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   double* partial = reinterpret_cast<double*>(workspace);
+  if (kind == SRAD_LOSS_GMS || kind == SRAD_LOSS_MSGMS) {
+    SRAD_REQUIRE(sH == H && sW == W, "loss_forward: sr and hr must have the same size");
+    return srad_gms_loss_forward(kind, sr, hr, B, C, H, W, rgb_range, out2, workspace, stream);
+  }
   if (kind != SRAD_LOSS_SSIM) {
     SRAD_REQUIRE(sH == H && sW == W, "loss_forward: sr and hr must have the same size");
     const size_t n = (size_t)B * C * H * W;
@@ -266,8 +273,15 @@ int srad_loss_backward(int kind, const float* sr, const float* hr, int B, int C,
                        int batch_size, const double* fwd_out2, const float* gscale_dev, float weight, float* dsr, int accumulate,
                        void* workspace, size_t workspace_bytes, void* stream) {
   SRAD_REQUIRE(sr && hr && dsr && fwd_out2 && workspace, "loss_backward: null argument");
-  SRAD_REQUIRE(kind >= SRAD_LOSS_L1 && kind <= SRAD_LOSS_SSIM, "loss_backward: unknown loss kind %d", kind);
+  SRAD_REQUIRE(kind >= SRAD_LOSS_L1 && kind <= SRAD_LOSS_MSGMS, "loss_backward: unknown loss kind %d", kind);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (kind == SRAD_LOSS_GMS || kind == SRAD_LOSS_MSGMS) {
+    SRAD_REQUIRE(sH == H && sW == W, "loss_backward: sr and hr must have the same size");
+    size_t need = 0;
+    SRAD_TRY(srad_loss_workspace_bytes(kind, B, C, H, W, &need));
+    SRAD_REQUIRE(workspace_bytes >= need, "loss_backward: workspace %zu bytes, %zu needed (the one srad_loss_forward filled)", workspace_bytes, need);
+    return srad_gms_loss_backward(kind, sr, B, C, H, W, rgb_range, gscale_dev, weight, dsr, accumulate, workspace, stream);
+  }
   if (kind != SRAD_LOSS_SSIM) {
     SRAD_REQUIRE(sH == H && sW == W, "loss_backward: sr and hr must have the same size");
     const size_t n = (size_t)B * C * H * W;

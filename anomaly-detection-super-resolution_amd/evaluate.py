@@ -217,7 +217,9 @@ def resolve_map_scales(map_scales, H: int, W: int) -> List[int]:
 @dataclass(frozen=True)
 class MapSpec:
     """What the pixel-level anomaly maps are made of.  ``source``: 'ssim' = ``1 - SSIM map``, 'mse' = the squared-error maps of
-    ``metrics.error_maps`` (DESIGN.md "Squared-error maps").  One window size ``ws``, or ``scales`` in its place: a list of
+    ``metrics.error_maps`` (DESIGN.md "Squared-error maps"), 'gms' / 'msgms' = the gradient-magnitude similarity maps of
+    ``metrics.gms_maps`` at 1 / 4 levels, which have no window (``ws`` 0, no scales; ``levels``).
+    One window size ``ws``, or ``scales`` in its place: a list of
     window sizes, or 'sweep' for every size of the image-level sweep, reduced per pixel by ``reduce`` ('mean' or 'max';
     ``metrics.anomaly_maps_multi``).  ``sigma`` > 0: the maps are smoothed once with that Gaussian sigma
     (``metrics.smooth_maps``) before anything is saved or scored.  ``ws`` 0 without scales means the SSIM sweep's best_ws for
@@ -232,8 +234,15 @@ class MapSpec:
     sigma: float = 0.0
 
     def __post_init__(self):
-        if self.source not in M.MAP_SOURCES:
-            raise ValueError(f"map_source = {self.source!r}, must be one of {M.MAP_SOURCES}")
+        if self.source not in M.MAP_SOURCES and self.source not in M.GMS_MAP_SOURCES:
+            raise ValueError(f"map_source = {self.source!r}, must be one of {M.MAP_SOURCES + tuple(M.GMS_MAP_SOURCES)}")
+        if self.levels and (int(self.ws) or isinstance(self.scales, str) or len(self.scales)):
+            raise ValueError("the GMS maps have no window; smooth with map_sigma")
+
+    @property
+    def levels(self) -> int:
+        """Pyramid levels of a GMS source ('gms' 1, 'msgms' 4); 0 for the windowed sources."""
+        return M.GMS_MAP_SOURCES.get(self.source, 0)
 
     def check_sigma(self, H: int, W: int) -> None:
         """ValueError for a sigma that H x W maps cannot be smoothed with: negative, or a radius above min(128, H, W)."""
@@ -254,6 +263,8 @@ class MapSpec:
     def resolve(self, H: int, W: int) -> 'MapSpec':
         """The spec for H x W images with its scales a list of sizes, after both checks."""
         self.check_sigma(H, W)
+        if self.levels:
+            M.check_gms_levels(self.levels, H, W)
         return replace(self, ws=int(self.ws), scales=self.check_scales(H, W), sigma=float(self.sigma))
 
     @property
@@ -263,8 +274,11 @@ class MapSpec:
 
     def make(self, sr: torch.Tensor, hr: torch.Tensor, with_max: bool):
         """(maps of the (sr, hr) u8 stacks, their per-image maxima or None without ``with_max``)."""
-        one, multi = (M.error_maps, M.error_maps_multi) if self.source == 'mse' else (M.anomaly_maps, M.anomaly_maps_multi)
-        maps = multi(sr, hr, self.scales, self.reduce) if self.scales else one(sr, hr, self.ws)
+        if self.levels:
+            maps = M.gms_maps(sr, hr, self.levels)
+        else:
+            one, multi = (M.error_maps, M.error_maps_multi) if self.source == 'mse' else (M.anomaly_maps, M.anomaly_maps_multi)
+            maps = multi(sr, hr, self.scales, self.reduce) if self.scales else one(sr, hr, self.ws)
         if with_max:
             return M.smooth_maps(maps, self.sigma, with_max=True)
         return (M.smooth_maps(maps, self.sigma) if self.sigma > 0 else maps), None
@@ -272,8 +286,11 @@ class MapSpec:
     def entries(self, found: dict) -> dict:
         """The result entries of these maps around ``found``: ``map_source`` (for 'mse' only), ``map_ws`` or ``map_scales`` and
         ``map_reduce``, then ``found``, then ``map_sigma`` when it is above 0."""
-        out = dict(map_source=self.source) if self.source == 'mse' else {}
-        out.update(dict(map_scales=list(self.scales), map_reduce=self.reduce) if self.scales else dict(map_ws=self.ws), **found)
+        if self.levels:
+            out = dict(map_source=self.source, map_levels=self.levels, **found)
+        else:
+            out = dict(map_source=self.source) if self.source == 'mse' else {}
+            out.update(dict(map_scales=list(self.scales), map_reduce=self.reduce) if self.scales else dict(map_ws=self.ws), **found)
         if self.sigma > 0:
             out["map_sigma"] = self.sigma
         return out
@@ -281,9 +298,9 @@ class MapSpec:
     def text(self, extra: str = '', always_sigma: bool = False) -> str:
         """What a printed line calls these maps, as in ``SSIM map (ws=11, fpr <= 0.3, sigma=4)``: ``extra`` comes before the
         sigma, which is left out at 0 unless ``always_sigma``."""
-        what = f"scales={list(self.scales)}, {self.reduce}" if self.scales else f"ws={self.ws}"
+        what = f"levels={self.levels}" if self.levels else (f"scales={list(self.scales)}, {self.reduce}" if self.scales else f"ws={self.ws}")
         sigma = f", sigma={self.sigma:g}" if self.sigma > 0 or always_sigma else ""
-        return f"{'MSE' if self.source == 'mse' else 'SSIM'} map ({what}{extra}{sigma})"
+        return f"{'GMS' if self.levels else 'MSE' if self.source == 'mse' else 'SSIM'} map ({what}{extra}{sigma})"
 
 
 def shard_indices(n: int, rank: int, world: int) -> List[int]:
@@ -563,7 +580,7 @@ def _with_window(spec: MapSpec, best_ws, world: int) -> MapSpec:
             dist.broadcast_object_list(box, src=0)
             best_ws = int(box[0])
         return replace(spec, ws=best_ws)
-    return spec if spec.scales else replace(spec, ws=max(spec.ws, 1))
+    return spec if spec.scales or spec.levels else replace(spec, ws=max(spec.ws, 1))      # the GMS maps have no window
 
 
 def _map_max_auc(shard: Shard, spec: MapSpec, img_max: torch.Tensor, pr: bool = False, note: str = '') -> dict:
@@ -707,7 +724,9 @@ def _run(args):
         raise SystemExit("--device cpu is the reference's own path; this build has no CPU fallback")
     spec = MapSpec(source=args.map_source, ws=args.map_ws, scales=args.map_scales, reduce=args.map_reduce, sigma=args.map_sigma)
     if resolution:                                            # before the model and the data are loaded
-        for flag, check in ((f"--map-sigma {args.map_sigma:g}", spec.check_sigma), ("--map-scales", spec.check_scales)):
+        levels = (lambda H, W: M.check_gms_levels(spec.levels, H, W)) if spec.levels else (lambda H, W: None)
+        for flag, check in ((f"--map-sigma {args.map_sigma:g}", spec.check_sigma), ("--map-scales", spec.check_scales),
+                            (f"--map-source {args.map_source}", levels)):
             try:
                 check(int(resolution), int(resolution))
             except ValueError as e:

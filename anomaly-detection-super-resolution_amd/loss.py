@@ -1,6 +1,6 @@
 """Loss factory - host-side mirror of reference ``src/loss.py`` (``Loss(opt, ckp)``, 72-152): the ``'w*TYPE+w*TYPE'``
 string, the per-epoch loss log (``start_log`` / ``end_log`` / ``display_loss`` / ``save`` -> ``loss_log.pt``) and the four
-loss types L1 / MSE / PSNR / SSIM.  Values and gradients come from the engine's reductions (C ABI ``srad_loss_forward`` /
+loss types L1 / MSE / PSNR / SSIM, plus GMS / MSGMS (the gradient-magnitude similarity, not in the reference).  Values and gradients come from the engine's reductions (C ABI ``srad_loss_forward`` /
 ``srad_loss_backward``, csrc/kernels_loss.hip); no torch arithmetic touches the images.
 
 Two ways in:
@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import _lib as L
 
-KINDS = {"L1": 0, "MSE": 1, "PSNR": 2, "SSIM": 3}
+KINDS = {"L1": 0, "MSE": 1, "PSNR": 2, "SSIM": 3, "GMS": 4, "MSGMS": 5}
 
 
 def _workspace(kind: int, shape, device):
@@ -33,6 +33,14 @@ def _workspace(kind: int, shape, device):
     return t, C.c_void_p(t.data_ptr() + off), C.c_size_t(nbytes.value)
 
 
+def check_gms_size(kind: int, H: int, W: int) -> None:
+    """ValueError for an image size the level geometry of a GMS kind cannot serve (any other kind passes); needs no GPU."""
+    if kind == KINDS["MSGMS"] and (H % 8 or W % 8 or H < 16 or W < 16):
+        raise ValueError(f"MSGMS loss: the four levels need H and W to be multiples of 8 and at least 16 (got {H}x{W})")
+    if kind == KINDS["GMS"] and (H < 2 or W < 2):
+        raise ValueError(f"GMS loss: H and W must be at least 2 (got {H}x{W})")
+
+
 def _prep(sr: torch.Tensor, hr: torch.Tensor, kind: int):
     if not (sr.is_cuda and hr.is_cuda):
         raise RuntimeError("srad_amd losses run on the GPU only (HIP reductions); there is no CPU fallback")
@@ -40,6 +48,7 @@ def _prep(sr: torch.Tensor, hr: torch.Tensor, kind: int):
         raise ValueError(f"expected [B, C, H, W] tensors with equal batch and channels, got {tuple(sr.shape)} and {tuple(hr.shape)}")
     if kind != KINDS["SSIM"] and sr.shape != hr.shape:
         raise ValueError(f"sr {tuple(sr.shape)} and hr {tuple(hr.shape)} differ")
+    check_gms_size(kind, *hr.shape[2:])
     return sr.detach().float().contiguous(), hr.detach().float().contiguous()
 
 
@@ -118,6 +127,21 @@ class SSIMLoss(_Term):
         super().__init__("SSIM", args.rgb_range, args.batch_size)
 
 
+class GMSLoss(_Term):
+    """Gradient-magnitude similarity at one level: mean of (ga - gb)^2 / (ga^2 + gb^2 + 0.0026) over the Prewitt gradient
+    magnitudes of the clamped channel means (DESIGN.md "Gradient-magnitude maps and loss")."""
+
+    def __init__(self, args):
+        super().__init__("GMS", args.rgb_range)
+
+
+class MSGMSLoss(_Term):
+    """The mean of GMSLoss over four levels of 2x2 averages (RIAD's MSGMS); H and W multiples of 8, at least 16."""
+
+    def __init__(self, args):
+        super().__init__("MSGMS", args.rgb_range)
+
+
 class Loss(nn.modules.loss._Loss):
     def __init__(self, args, ckp=None):
         super().__init__()
@@ -133,6 +157,10 @@ class Loss(nn.modules.loss._Loss):
                 fn = PSNRLoss()
             elif loss_type == 'SSIM':
                 fn = SSIMLoss(args)
+            elif loss_type == 'GMS':
+                fn = GMSLoss(args)
+            elif loss_type == 'MSGMS':
+                fn = MSGMSLoss(args)
             else:
                 assert False, f"Unsupported loss type: {loss_type:s}"
             self.loss.append({'type': loss_type, 'weight': float(weight), 'function': fn})

@@ -81,6 +81,19 @@ def train_drct(opt_drct: DRCT) -> None:
     _train(opt_drct, dual_model=False)
 
 
+def check_loss_geometry(loss: str, resolution: int, down_to: int = 1) -> None:
+    """ValueError, before anything is built, for a loss whose level geometry the training images cannot serve: MSGMS needs
+    sizes that are multiples of 8 and at least 16.  DRN evaluates the loss on its intermediate outputs too, down to
+    ``resolution / down_to`` (the LR size)."""
+    if any(term.split('*')[-1] == 'MSGMS' for term in loss.split('+')):
+        size = resolution
+        while size >= max(1, resolution // down_to):
+            if size % 8 or size < 16:
+                raise ValueError(f"--loss {loss}: the four levels of MSGMS need image sizes that are multiples of 8 and at least 16; "
+                                 f"this run evaluates the loss at {size} px")
+            size //= 2
+
+
 def build_train_opt(args):
     """src/main.py:398-471: paths, virtual dataset length (256 samples per epoch), the option object."""
     n_colors = 3 if (args.dataset == 'mvtec' and args.classe == 'carpet') else 1
@@ -91,17 +104,19 @@ def build_train_opt(args):
     save = f"{args.save_dir}/{args.model_type}/mvtec_{args.classe}_{res}_X{scale}{date_string}/"
     data_range = '1-210/211-264' if args.classe == 'grid' else '1-224/225-280'
     test_every = 256 // args.batch_size
+    loss = getattr(args, 'loss', '1*L1')
+    check_loss_geometry(loss, res, scale if args.model_type == 'drn-l' else 1)
     if args.model_type == 'drn-l':
         pre, pre_dual = ((f'workspace/pretrained_model_weights/DRNL{scale}x.pt',
                           f'workspace/pretrained_model_weights/DRNL{scale}x_dual_model.pt') if args.pretrain else ('.', '.'))
         opt = setup_opt_drn(DRN(), 0.0, 11, args.dataset, args.classe, False, scale, args.no_augment, n_colors, args.epochs,
                             args.batch_size, res, data_dir, save, data_range, test_every, test_every, 1, 0.005, 4, pre, pre_dual,
-                            '1*L1')
+                            loss)
     else:
         pre = 'workspace/pretrained_model_weights/net_g_latest.pth' if args.pretrain else '.'
         opt = setup_opt_drct(DRCT(), 0.0, 11, args.dataset, args.classe, False, scale, args.no_augment, n_colors, args.epochs,
                              args.batch_size, res, res // scale, data_dir, save, data_range, test_every, test_every, 1, 0.005, 4,
-                             pre, '1*L1')
+                             pre, loss)
     opt.model_name = args.model_type
     opt.test_only = args.test_only
     opt.precision = args.dtype

@@ -191,6 +191,40 @@ def error_maps_multi(sr_u8: torch.Tensor, hr_u8: torch.Tensor, window_sizes: Seq
     return _maps("error_map_workspace_bytes", "error_maps_multi", sr_u8, hr_u8, sizes, reduce)
 
 
+GMS_MAP_SOURCES = {"gms": 1, "msgms": 4}    # the window-free map sources and their pyramid levels (DESIGN.md "Gradient-magnitude maps and loss")
+
+
+def check_gms_levels(levels: int, H: int, W: int) -> int:
+    """``levels`` as an int once H x W images can carry that many pyramid levels: 1..4, H and W multiples of ``2^(levels-1)``
+    and at least twice that.  ValueError otherwise.  Needs no GPU."""
+    levels = int(levels)
+    if not 1 <= levels <= 4:
+        raise ValueError(f"gms_maps: levels = {levels}, must be 1..4")
+    f = 1 << (levels - 1)
+    if H % f or W % f or H < 2 * f or W < 2 * f:
+        raise ValueError(f"gms_maps: {levels} levels need H and W to be multiples of {f} and at least {2 * f} (got {H}x{W})")
+    return levels
+
+
+def gms_maps(sr_u8: torch.Tensor, hr_u8: torch.Tensor, levels: int = 1) -> torch.Tensor:
+    """Gradient-magnitude similarity maps of [n,H,W,C] uint8 image stacks (SR, HR): per pyramid level the Prewitt gradient
+    magnitudes of the channel sums (reflect padding) compared as ``(ga - gb)^2 / (ga^2 + gb^2 + c)``, the coarser levels
+    upsampled bilinearly, the mean over ``levels`` (1 = GMS, 4 = MSGMS) rounded to float32 once - ``srad_gms_maps`` in
+    include/srad.h states every operation.  Exactly 0 where the images agree, in [0, 1), symmetric in (SR, HR).  Returns float32
+    [n,H,W] on the GPU.  ValueError for levels the image size cannot carry; the stacks may be views that start at any byte."""
+    _need_cuda(sr_u8, hr_u8)
+    assert sr_u8.dtype == torch.uint8 and hr_u8.dtype == torch.uint8 and sr_u8.shape == hr_u8.shape and sr_u8.dim() == 4
+    n, H, W, Cc = sr_u8.shape
+    levels = check_gms_levels(levels, H, W)
+    if Cc not in (1, 3):
+        raise ValueError(f"gms_maps: channels must be 1 or 3 (got {Cc})")
+    sr_u8, hr_u8 = sr_u8.contiguous(), hr_u8.contiguous()
+    out = torch.empty(n, H, W, dtype=torch.float32, device=sr_u8.device)
+    _call_with_ws("gms_map_workspace_bytes", (n, H, W, levels), "gms_maps", (L.dptr(sr_u8), L.dptr(hr_u8), n, H, W, Cc, levels, L.dptr(out)),
+                  sr_u8.device)
+    return out
+
+
 def check_map_scales(window_sizes: Sequence[int], H: int, W: int) -> List[int]:
     """The sizes of ``window_sizes`` as a list, once every one passes the window check of the map kernels for H x W images
     (a window may reflect over an image edge once).  ValueError otherwise.  Needs no GPU, so callers can check their arguments

@@ -210,10 +210,17 @@ def parse_train_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument('--skip-nonfinite', action='store_true', default=False,
                    help="drop every optimizer step whose gradients hold an inf or a NaN (what the reference's GradScaler.step did): "
                         "weights, moments and the weight average keep their bits and the bias correction counts applied steps")
+    p.add_argument('--loss', type=_loss_spec, default='1*L1', metavar='SPEC',
+                   help="the training loss as w*TYPE(+w*TYPE)*, e.g. 0.8*L1+0.2*MSGMS; types " + ', '.join(LOSS_TYPES) +
+                        "; the default 1*L1 runs the graphed step, any other string the eager one")
     add_tile_args(p)                                          # test time only, like --self-ensemble
     _with_config(p, pre_args)
     args = p.parse_args(argv)
     check_tile_args(p, args)
+    try:                                                      # a value from a config file gets the command line's check
+        args.loss = _loss_spec(str(args.loss))
+    except argparse.ArgumentTypeError as e:
+        p.error(f"argument --loss: {e}")
     if args.ema_decay is not None:                            # a value from a config file gets the command line's check
         try:
             args.ema_decay = _ema_decay(str(args.ema_decay))
@@ -313,6 +320,22 @@ def check_baseline_args(p: argparse.ArgumentParser, args: argparse.Namespace, at
             p.error(f"--baseline-floor belongs to {flag}: give it too")
 
 
+LOSS_TYPES = ('L1', 'MSE', 'PSNR', 'SSIM', 'GMS', 'MSGMS')     # loss.KINDS, kept here so that parsing needs no torch
+
+
+def _loss_spec(text: str) -> str:
+    """--loss: ``w*TYPE(+w*TYPE)*`` with finite weights and types of ``LOSS_TYPES`` (the string itself)."""
+    for term in text.split('+'):
+        parts = term.split('*')
+        try:
+            weight = float(parts[0]) if len(parts) == 2 else float('nan')
+        except ValueError:
+            weight = float('nan')
+        if len(parts) != 2 or weight != weight or weight in (float('inf'), float('-inf')) or parts[1] not in LOSS_TYPES:
+            raise argparse.ArgumentTypeError(f"{text!r} is not w*TYPE(+w*TYPE)* with finite weights and types of {LOSS_TYPES}")
+    return text
+
+
 def _grad_clip(text: str) -> float:
     v = float(text)
     if not v > 0.0:                                           # zero, negatives and NaN
@@ -363,6 +386,10 @@ def _positive_int(text: str) -> int:
     if v < 1:
         raise argparse.ArgumentTypeError(f"{text!r} is not an integer >= 1")
     return v
+
+
+GMS_MAP_SOURCES = ('gms', 'msgms')                            # metrics.GMS_MAP_SOURCES, kept here so that parsing needs no torch
+ALL_MAP_SOURCES = ('ssim', 'mse') + GMS_MAP_SOURCES
 
 
 def _map_scales(text: str):
@@ -428,9 +455,10 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
                         "size of the image-level sweep, combined per pixel with --map-reduce; replaces --map-ws")
     p.add_argument('--map-reduce', type=str, default='mean', choices=['mean', 'max'],
                    help="how --map-scales combines the maps of its window sizes")
-    p.add_argument('--map-source', type=str, default='ssim', choices=['ssim', 'mse'],
-                   help="what the pixel-level maps are made of: 1 - SSIM map, or (mse) the squared error averaged over the window "
-                        "(--map-ws 0 then means window size 1, the raw per-pixel squared error)")
+    p.add_argument('--map-source', type=str, default='ssim', choices=list(ALL_MAP_SOURCES),
+                   help="what the pixel-level maps are made of: 1 - SSIM map, (mse) the squared error averaged over the window "
+                        "(--map-ws 0 then means window size 1, the raw per-pixel squared error), or the gradient-magnitude "
+                        "similarity at one level (gms) or four (msgms), which has no window: smooth with --map-sigma")
     p.add_argument('--threshold', type=_finite_or_inf_float, default=None, metavar='VALUE',
                    help="operating point: a pixel is predicted defective iff its anomaly-map value is > VALUE; reports the "
                         "image-level (and, with test/bad/GT masks, pixel-level) counts at it (needs --gpus 1)")
@@ -485,8 +513,10 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
             args.map_scales = _map_scales(','.join(str(v) for v in args.map_scales))
         except argparse.ArgumentTypeError as e:
             p.error(f"argument --map-scales: {e}")
-    if args.map_source not in ('ssim', 'mse'):                # a value from a config file gets the command line's check
-        p.error(f"argument --map-source: invalid choice: {args.map_source!r} (choose from 'ssim', 'mse')")
+    if args.map_source not in ALL_MAP_SOURCES:                # a value from a config file gets the command line's check
+        p.error(f"argument --map-source: invalid choice: {args.map_source!r} (choose from {', '.join(repr(m) for m in ALL_MAP_SOURCES)})")
+    if args.map_source in GMS_MAP_SOURCES and (args.map_ws or args.map_scales):
+        p.error(f"--map-source {args.map_source}: the GMS maps have no window (no --map-ws, no --map-scales); smooth with --map-sigma")
     if args.map_scales and args.map_ws:
         p.error("--map-scales and --map-ws exclude each other (the scales replace the single window size)")
     return args
@@ -494,7 +524,7 @@ def parse_eval_args(argv=None) -> argparse.Namespace:
 
 def build_opt(model_type: str, class_name: str, resolution: int, scale: int, batch_size: int = 1, dtype: str = 'fp32',
               pre_train: str = '.', pre_train_dual: str = '.', data_root: str = 'auto', save: str = './workspace/eval',
-              epochs: int = 1, no_augment: bool = True):
+              epochs: int = 1, no_augment: bool = True, loss: str = '1*L1'):
     """The option object main.py / evaluate.py build before calling Model (src/main.py:398-471,
     src/evaluate.py:293-334)."""
     n_colors = 3 if class_name == 'carpet' else 1
@@ -504,10 +534,10 @@ def build_opt(model_type: str, class_name: str, resolution: int, scale: int, bat
     data_dir = f"{data_root}/{class_name}/train/good"
     if model_type == 'drn-l':
         opt = setup_opt_drn(DRN(), 0.0, 11, 'mvtec', class_name, False, scale, no_augment, n_colors, epochs, batch_size,
-                            resolution, data_dir, save, '', 1, 1, 1, 0.0, 4, pre_train, pre_train_dual, '1*L1')
+                            resolution, data_dir, save, '', 1, 1, 1, 0.0, 4, pre_train, pre_train_dual, loss)
     else:
         opt = setup_opt_drct(DRCT(), 0.0, 11, 'mvtec', class_name, False, scale, no_augment, n_colors, epochs, batch_size,
-                             resolution, img_size, data_dir, save, '', 1, 1, 1, 0.0, 4, pre_train, '1*L1')
+                             resolution, img_size, data_dir, save, '', 1, 1, 1, 0.0, 4, pre_train, loss)
     opt.model_name = model_type
     opt.data_root = data_root
     opt.precision = dtype

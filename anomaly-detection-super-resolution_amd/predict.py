@@ -35,8 +35,8 @@ from . import metrics as M
 from . import ops
 from .data import rgb2y, set_channel
 from .evaluate import MapSpec, _with_window, infer_from_run_dir, resolve_checkpoint, save_anomaly_maps, save_masks, save_sr_image, super_resolve_dev
-from .options import (_finite_or_inf_float, _map_scales, _nonnegative_float, _open_unit_float, _positive_int, add_baseline_args,
-                      add_tile_args, build_opt, check_baseline_args, check_tile_args, tile_suffix)
+from .options import (ALL_MAP_SOURCES, GMS_MAP_SOURCES, _finite_or_inf_float, _map_scales, _nonnegative_float, _open_unit_float,
+                      _positive_int, add_baseline_args, add_tile_args, build_opt, check_baseline_args, check_tile_args, tile_suffix)
 
 OPERATING_POINT_FILE = 'operating_point.json'
 OPERATING_POINT_VERSION = 1
@@ -283,7 +283,7 @@ class Detector:
             raise ValueError("predict: no threshold (calibrate on defect-free images first, or give one)")
         source_frame = bool(source_frame or overlays)
         sr, hr, maps, img_max, kept = self._maps(images, True, source_frame)
-        sizes = list(self.spec.scales) or [self.spec.ws]
+        sizes = list(self.spec.scales) or [self.spec.ws or MAP_WS_DEFAULT]      # the GMS maps have no window: the SSIM score's default
         ssim, mse, psnr = M.score_pairs(sr, hr, sizes)
         masks, img_pred, _ = M.operating_point(maps, self.threshold, None, self.min_area)
         pixels = [int(v) for v in img_pred.tolist()]
@@ -524,7 +524,7 @@ def spec_from_args(args, stored: Optional[MapSpec] = None, side: int = 0) -> Map
     scales = args.map_scales or ()
     if scales and args.map_ws:
         raise ValueError("--map-scales and --map-ws exclude each other (the scales replace the single window size)")
-    ws = args.map_ws if args.map_ws is not None else (0 if scales else MAP_WS_DEFAULT)
+    ws = args.map_ws if args.map_ws is not None else (0 if scales or args.map_source in GMS_MAP_SOURCES else MAP_WS_DEFAULT)
     return MapSpec(source=args.map_source or 'ssim', ws=ws, scales=scales, reduce=args.map_reduce or 'mean', sigma=args.map_sigma or 0.0)
 
 
@@ -574,7 +574,7 @@ def parse_predict_args(argv=None) -> argparse.Namespace:
                    help="remove predicted 8-connected components of fewer than A pixels (default: the calibrated file's, else 1)")
     p.add_argument('--threshold', type=_finite_or_inf_float, default=None, metavar='VALUE',
                    help=f"predict with this threshold instead of the one in {OPERATING_POINT_FILE}")
-    p.add_argument('--map-source', type=str, default=None, choices=['ssim', 'mse'])
+    p.add_argument('--map-source', type=str, default=None, choices=list(ALL_MAP_SOURCES))
     p.add_argument('--map-ws', type=int, default=None, help=f"window size of the anomaly maps (default {MAP_WS_DEFAULT}; there is no labelled sweep here)")
     p.add_argument('--map-scales', type=_map_scales, default=None, metavar='LIST|sweep')
     p.add_argument('--map-reduce', type=str, default=None, choices=['mean', 'max'])
@@ -605,6 +605,8 @@ def parse_predict_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     check_tile_args(p, args)
     check_baseline_args(p, args, 'baseline', '--baseline')
+    if args.map_source in GMS_MAP_SOURCES and (args.map_ws or args.map_scales):
+        p.error(f"--map-source {args.map_source}: the GMS maps have no window (no --map-ws, no --map-scales); smooth with --map-sigma")
     if args.save_regions and not args.input:
         p.error("--save-regions lists the regions of --input images: give --input too")
     if (args.overlay_alpha is not None or args.overlay_contour is not None) and not args.save_overlays:

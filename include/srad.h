@@ -390,6 +390,27 @@ int srad_error_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int 
  * accumulated that way and n_ws = 1 gives srad_error_maps itself.  workspace >= srad_error_map_workspace_bytes. */
 int srad_error_maps_multi(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, const int32_t* ws_host,
                           int n_ws, int reduce, float* map_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Gradient-magnitude similarity maps (GMSD, Xue et al. 2014; multi-scale as RIAD's MSGMS, Zavrtanik et al. 2021) of `n_img` u8
+ * HWC image pairs over `levels` = L in 1..4 pyramid levels; H and W multiples of 2^(L-1), H >> (L-1) and W >> (L-1) >= 2.
+ * Every step is one IEEE operation in the stated precision (no contraction), so the map is defined up to the device's sqrt
+ * and division, both correctly rounded:
+ *   s_0[y, x] = sum_c u8 (an integer <= 765); s_l = the 2x2 block sums of s_(l-1) (exact integers <= 765 * 4^l)
+ *   per level and stack, numpy "reflect" padding by one pixel, the Prewitt sums as tap-pair differences
+ *     Gx = (p[y-1,x+1] - p[y-1,x-1]) + (p[y,x+1] - p[y,x-1]) + (p[y+1,x+1] - p[y+1,x-1]), Gy likewise along the other axis,
+ *     M = Gx * Gx + Gy * Gy in int64 (past 2^32 at level 3)
+ *   with Ma of sr, Mb of hr, K_l = 3 * C * 255 * 4^l and cK2_l = 0.0026 * K_l * K_l (a host double), in float64
+ *     r = sqrt((double)Ma) - sqrt((double)Mb);   d_l = (r * r) / ((double)(Ma + Mb) + cK2_l)
+ *   which is 1 - (2 ga gb + c) / (ga^2 + gb^2 + c) for magnitudes in [0, 1] units without the cancellation: exactly 0 for
+ *   identical inputs, never negative, below 1, bit-symmetric in (sr, hr)
+ *   levels l >= 1 are upsampled bilinearly (align_corners = False) with f = 2^l: o = (y + 0.5) / f - 0.5, i0 = floor(o),
+ *     t = o - i0 (dyadic, exact), both neighbour indices clamped to [0, h_l - 1],
+ *     u_l = (d[i0,j0] * (1 - tx) + d[i0,j1] * tx) * (1 - ty) + (d[i1,j0] * (1 - tx) + d[i1,j1] * tx) * ty   in float64, this order
+ *   map_out = (float)((d_0 + u_1 + ... + u_(L-1)) * (1.0 / L)), summed in level order: one rounding to fp32.
+ * map_out is a DEVICE float32 array [n_img, H, W]; any width, the stacks may start at any byte.  The workspace is linear in
+ * n_img (no chunks): workspace >= srad_gms_map_workspace_bytes.  All argument checks come before any launch. */
+int srad_gms_map_workspace_bytes(int n_img, int H, int W, int levels, size_t* bytes);
+int srad_gms_maps(const uint8_t* sr, const uint8_t* hr, int n_img, int H, int W, int C, int levels,
+                  float* map_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Exact ROC-AUC of `n` DEVICE float32 scores against DEVICE u8 labels (labels[i] != 0 = positive), n < 2^31:
  * sklearn.metrics.roc_auc_score as the Mann-Whitney U with ties counted one half (a device radix sort, no binning).
  *   counts_out (DEVICE, 4 x u64) = {n_pos, n_neg, n_nan, twice_U};  *auc_out (DEVICE double) = twice_U / (2 n_pos n_neg),
@@ -530,6 +551,14 @@ int srad_l1_loss(const float* a, const float* b, int64_t n, double* out, void* w
  *   SRAD_LOSS_PSNR PSNRLoss: -10 log10(255^2 / (mse + 1e-8))       (src/loss.py:63-70)
  *   SRAD_LOSS_SSIM SSIMLoss / calc_ssim: sum(1 - ssim_map) / batch_size with the 10-px shave, zero-padded 11x11 mean
  *                  filter and the 255^2-scaled constants           (src/loss.py:9-61)
+ *   SRAD_LOSS_GMS / SRAD_LOSS_MSGMS (not in the reference) the gradient-magnitude similarity over L = 1 / 4 levels, in fp32:
+ *                  x = clamp(t / rgb_range, 0, 1) averaged over the channels, levels by 2x2 averages, reflect padding by
+ *                  one pixel, Prewitt tap-pair differences summed then divided by 3, M = gx^2 + gy^2,
+ *                  d = (sqrt(Ma) - sqrt(Mb))^2 / (Ma + Mb + 0.0026), loss = (1 / L) sum_l mean_{B, h_l, w_l} d_l (a plain
+ *                  mean; batch_size is ignored).  d sqrt(M) / d gx is 0 where M == 0.  sr and hr of one size; MSGMS needs
+ *                  H and W multiples of 8 and at least 16 (srad_loss_workspace_bytes refuses other sizes).  On u8-valued
+ *                  inputs the loss is the mean of srad_gms_maps.  The backward reads the workspace the forward filled
+ *                  and gathers (no atomics): gradients are bit-reproducible.
  * sr [B,C,sH,sW] and hr [B,C,H,W] fp32 NCHW (sH, sW may exceed H, W only for SSIM, which crops sr like the reference).
  * forward: out2[0] = loss, out2[1] = state for the backward (device doubles).  backward: dsr (+)= weight * gscale_dev[0]
  * * dLoss/dsr (gscale_dev may be NULL = 1); SSIM's backward reads the workspace its forward filled. */
@@ -537,6 +566,8 @@ int srad_l1_loss(const float* a, const float* b, int64_t n, double* out, void* w
 #define SRAD_LOSS_MSE 1
 #define SRAD_LOSS_PSNR 2
 #define SRAD_LOSS_SSIM 3
+#define SRAD_LOSS_GMS 4
+#define SRAD_LOSS_MSGMS 5
 int srad_loss_workspace_bytes(int kind, int B, int C, int H, int W, size_t* bytes);
 int srad_loss_forward(int kind, const float* sr, const float* hr, int B, int C, int sH, int sW, int H, int W, float rgb_range,
                       int batch_size, double* out2, void* workspace, size_t workspace_bytes, void* stream);
