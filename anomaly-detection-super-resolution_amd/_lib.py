@@ -278,6 +278,10 @@ _SIG = {
     "srad_swin_block_fold_supported": (C.c_int, [C.c_int] * 9),
     "srad_op_swin_block_folded": (C.c_int, [C.c_int, _P, C.c_int] + [C.c_int] * 8 + [_P] * 15 + [C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_int,
                                             C.c_int, _P, C.c_size_t, _P]),
+    "srad_mlp_block_fold_supported": (C.c_int, [C.c_int] * 5),
+    "srad_mlp_block_stage_counts": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "srad_op_mlp_block_folded": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "srad_bench_swin_block": (C.c_int, [_P] + [C.c_int] * 8 + [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float), _P]),
     "srad_op_gemm_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "srad_op_window_attn": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -138,6 +138,16 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
         // proj + shortcut -> norm2 -> fc1 -> GELU -> fc2 + residual -> adjust_k, one launch
         // (drct.py:300, 509-510, 184-190, 389-396)
         MlpBlockParams q = drct_mlp_block_params(h, sw, k, attn_h, cur, nxt, T);
+        // ... with fc2 folded into the adjust conv where this forward runs the folded form and the launch has it:
+        // the block's region is the one the one-launch block reads.  16-row tiles only - the form the one-launch block's
+        // second half has: a forward on 32- or 64-row tiles keeps the chain (tests/test_gpu_mlp_fold.py holds such a batch to
+        // the chain's bits; the wider folded instances exist at the op level and are measured there)
+        if (h->mfold_in_graph && srad_mlp_block_rows(T) == 16 && srad_mlp_block_fold_supported(prec, T, d, sw.hidden, no)) {
+          const char* const reg = h->pt.arena + h->mfold_off[i * 5 + k];
+          q.w_adj = reg + h->mfold[i * 5 + k].pack; q.b_adj = reinterpret_cast<const float*>(reg + h->mfold[i * 5 + k].bias);
+          SRAD_TRY(srad_launch_mlp_block_folded(q, s));
+          continue;
+        }
         q.split = x3; q.attn_f = w.attn;
         q.w_proj_lo = h->pt.frag_lo_ptr(sw.proj.w); q.w_fc1_lo = h->pt.frag_lo_ptr(sw.fc1.w); q.w_fc2_lo = h->pt.frag_lo_ptr(sw.fc2.w);
         q.w_adj_lo = h->pt.frag_lo_ptr(sw.adjust.w);
@@ -386,8 +396,9 @@ int srad_drct_create(const srad_drct_config* cfg, srad_drct_t** out) {
     h->fold = tf_layout(F, C, cfg->upscale);
     h->fold_off = srad_align_up(h->pt.bytes, 256);
   }
-  // the blocks' folded second halves: a region each behind the table's packs and the folded output end
-  h->mfold_ok = cfg->precision == SRAD_PREC_BF16 && ws == 8 && h->fuse_mlp;
+  // the blocks' folded second halves: a region each behind the table's packs and the folded output end (any window size: the
+  // composition does not depend on it; the one-launch block keeps its own check in srad_swin_block_fold_supported)
+  h->mfold_ok = cfg->precision == SRAD_PREC_BF16 && h->fuse_mlp;
   if (h->mfold_ok) {
     size_t off = srad_align_up(h->fold_ok ? h->fold_off + h->fold.bytes : h->pt.bytes, 256);
     for (int i = 0; i < cfg->n_rdg; ++i)

@@ -45,17 +45,26 @@ namespace {
 // SPLIT = the split-bf16 mode (SRAD_PREC_BF16X3, inference): both activation tiles exist as a hi and a lo bf16 plane, every
 // weight stage streams twice (hi pack, then lo pack: "half stages" through the same register sets) and a product is
 // W_hi.A_hi + W_hi.A_lo + W_lo.A_hi; the attention output comes in as fp32.  Nothing else changes - same stages, same epilogues.
-template <int FM, int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM, bool STAMP = false, bool SPLIT = false>
+// FOLD = the folded second half (bf16 inference; mlp_fold.h): p.w_adj is the pack of [A | A W2], p.b_adj is
+// A b2 + b_a and p.w_fc2 is not read - proj | fc1 | adjF (MlpFoldChain), no fc2 phase, no x2, one barrier less, and x1[] dies
+// after the proj epilogue.  The folded A tile [FM][LDF] = bf16(x1) in k chunks [0, KCD) | GELU(fc1) in [KCD, KCD + KCM) takes
+// the hidden tile's place.  No saves, no DropPath, no split-bf16, no stamps.
+template <int FM, int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM, bool STAMP = false, bool SPLIT = false, bool FOLD = false>
 __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) {
-  using Chain = MlpChain<GD, KGD, GM, KGM, GN, KCD, KCM>;
+  constexpr bool SPLITK = FOLD && GN == 1;                        // adjust outputs <= 32: adjF's k split over the eight waves
+  using Chain = std::conditional_t<FOLD, MlpFoldChain<GD, KGD, GM, GN, KCD, KCM, SPLITK>, MlpChain<GD, KGD, GM, KGM, GN, KCD, KCM>>;
   static_assert(!SPLIT || (FM <= 32 && !STAMP), "split-bf16: 16 / 32-row tiles (two planes of each tile in LDS)");
+  static_assert(!FOLD || (!SPLIT && !STAMP), "the folded form: plain bf16 inference");
+  constexpr int KF = KCD + KCM, LDF = mlp_fold_ldf(KCD, KCM);    // the folded tile's k chunks and row stride (2 mod 4 sixteen-byte units)
+  static_assert(!SPLITK || 4 * 2 * FM * 16 * 4 <= FM * SW_LDA * 2, "the k parts' partial sums overlay the LayerNorm2 tile");
   constexpr int NRT = FM / 16;       // 16-row MFMA tiles per workgroup
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* A1 = reinterpret_cast<__bf16*>(smem);                  // [FM][SW_LDA] attn tile -> LN2(x1) -> x2
   __bf16* Hs = A1 + FM * SW_LDA;                                  // [FM][SW_LDH] GELU(fc1)
   __bf16* A1L = Hs + FM * SW_LDH;                                 // split-bf16: the lo planes of the two tiles
   __bf16* HsL = A1L + FM * SW_LDA;
-  float* vec = reinterpret_cast<float*>(SPLIT ? HsL + FM * SW_LDH : Hs + FM * SW_LDH);   // b_proj | b_fc1 | b_fc2 | b_adj | gamma | beta
+  [[maybe_unused]] __bf16* Ft = Hs;                               // FOLD: [FM][LDF] the folded A tile instead
+  float* vec = reinterpret_cast<float*>(SPLIT ? HsL + FM * SW_LDH : Hs + FM * (FOLD ? LDF : SW_LDH));   // b_proj | b_fc1 | b_fc2 | b_adj | gamma | beta
   float* red = vec + SW_NV;                                       // [FM][8 waves][2] LayerNorm partial sums
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -97,6 +106,15 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
     constexpr int vs = decltype(S)::value < n_vst - 1 ? decltype(S)::value : n_vst - 1;
     constexpr MlpStage sg = Chain::stage(vs / NPART);
     constexpr bool lo = (vs % NPART) == 1;
+    if constexpr (SPLITK && sg.ph == 3) {
+      // adjF's one stage: column tile wave & 1 (the pack's rows are padded to 128: both tiles exist), k part wave >> 1; a
+      // part that ends past the last chunk reloads that chunk (the MFMA loop zeroes its operand)
+      const char* base = (const char*)p.w_adj + (size_t)(wave_s & 1) * sg.kc * 1024 + fr * 64 + fq * 16;
+      const int p0 = (wave_s >> 1) * sg.nch;
+#pragma unroll
+      for (int cc = 0; cc < sg.nch; ++cc) reg[cc] = *reinterpret_cast<const u32x4*>(base + (size_t)min(p0 + cc, sg.kc - 1) * 1024);
+      return;
+    }
     const char* w = lo ? (const char*)(sg.ph == 0 ? p.w_proj_lo : (sg.ph == 1 ? p.w_fc1_lo : (sg.ph == 2 ? p.w_fc2_lo : p.w_adj_lo)))
                        : (const char*)(sg.ph == 0 ? p.w_proj : (sg.ph == 1 ? p.w_fc1 : (sg.ph == 2 ? p.w_fc2 : p.w_adj)));
     const int nreal = sg.ph == 0 ? d : (sg.ph == 1 ? m : (sg.ph == 2 ? d : no));
@@ -233,6 +251,7 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
   float rs1v[NRT], rs2v[NRT];
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt) {
+    if constexpr (FOLD) { rs1v[rt] = 1.f; rs2v[rt] = 1.f; continue; }
     const int smp = p.rps > 0 ? (m0 + rt * 16 + fr) / p.rps : 0;
     // unconditional loads from a global pointer either way (see load_w; a pointer to a __device__ constant would make
     // these flat loads, which count out of order: hipcc then waits vmcnt(0) for everything)
@@ -289,7 +308,7 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
       for (int rt = 0; rt < NRT; ++rt) x1[g][rt] += (c[rt] + bp) * rs1v[rt];
     }
     if constexpr (g != GD - 1) return;
-    if (p.save_x1) {
+    if (!FOLD && p.save_x1) {
 #pragma unroll
       for (int gg = 0; gg < GD; ++gg) {
         const int c4 = col4_of(gg);
@@ -341,8 +360,12 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
 #pragma unroll
       for (int rt = 0; rt < NRT; ++rt) {
         const f32x4 v = in ? (x1[gg][rt] - mu[rt]) * rstd[rt] * gam + bet : f32x4{0.f, 0.f, 0.f, 0.f};
-        if (p.save_xn2 && in) *reinterpret_cast<f32x4*>(p.save_xn2 + (size_t)(m0 + rt * 16 + fr) * d + c4) = v;
-        store_bf4(A1, SW_LDA, rt, c4, v, p.save_xn2_h, d, in);
+        if (!FOLD && p.save_xn2 && in) *reinterpret_cast<f32x4*>(p.save_xn2 + (size_t)(m0 + rt * 16 + fr) * d + c4) = v;
+        store_bf4(A1, SW_LDA, rt, c4, v, FOLD ? nullptr : p.save_xn2_h, d, in);
+        // FOLD: x1 itself is adjF's first k range (nobody reads the tile before the fc1 epilogues fill the rest); x1[] dies here
+        if constexpr (FOLD) {
+          if (c4 < 32 * KCD) store_bf4(Ft, LDF, rt, c4, in ? x1[gg][rt] : f32x4{0.f, 0.f, 0.f, 0.f});
+        }
       }
     }
   };
@@ -352,6 +375,12 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt) {
       f32x4 v = c[rt] + b1;
+      if constexpr (FOLD) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = gelu_fast(v[e]);
+        if (c4 < 32 * KCM) store_bf4(Ft + 32 * KCD, LDF, rt, c4, c4 < m ? v : f32x4{0.f, 0.f, 0.f, 0.f});
+        continue;
+      }
       if (p.save_hpre && c4 < m) *reinterpret_cast<f32x4*>(p.save_hpre + (size_t)(m0 + rt * 16 + fr) * m + c4) = v;
       if (p.save_hpre_h && c4 < m) {
         bf16x4 hq;
@@ -433,6 +462,51 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
       for (int rt = 0; rt < NRT; ++rt) c[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const bool live = (g * 8 + wave_s) * 16 < (ph == 0 ? d : (ph == 1 ? m : (ph == 2 ? d : no)));
+    if constexpr (SPLITK && ph == 3) {
+      // ---- adjF, k split: this wave's part of [bf16(x1) | h] against its part of [A | A W2]; the four partial tiles of a
+      //      column tile meet in LDS (the LayerNorm2 tile is dead: every wave is past fc1) and waves 0 / 1 add them in part
+      //      order - a fixed order, whatever the waves' timing - and run the adjust epilogue ----
+      const int ct = wave_s & 1, pt = wave_s >> 1, p0 = pt * nch;
+      const __bf16* ar = Ft + fr * LDF + 8 * fq;
+      constexpr int CG = NRT == 1 ? 8 : (NRT == 2 ? 4 : 2);         // chunks whose fragments are requested together (sw_mma_chunks)
+#pragma unroll
+      for (int g0 = 0; g0 < nch; g0 += CG) {
+        bf16x8 af[CG][NRT];
+#pragma unroll
+        for (int gq = 0; gq < CG; ++gq)
+          if (g0 + gq < nch) {
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) af[gq][rt] = *reinterpret_cast<const bf16x8*>(ar + rt * 16 * LDF + min(p0 + g0 + gq, KF - 1) * 32);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int gq = 0; gq < CG; ++gq)
+          if (g0 + gq < nch) {
+            const u32x4 wz = p0 + g0 + gq < KF ? reg[g0 + gq] : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) c[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wz), af[gq][rt], c[rt], 0, 0, 0);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      float* const part = reinterpret_cast<float*>(A1);            // [4 parts][2 column tiles][FM rows][16]
+#pragma unroll
+      for (int rt = 0; rt < NRT; ++rt) *reinterpret_cast<f32x4*>(part + ((pt * 2 + ct) * FM + rt * 16 + fr) * 16 + 4 * fq) = c[rt];
+      __syncthreads();
+      if (wave_s < 2) {
+        f32x4 sum[NRT];
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) {
+          const float* src = part + (wave_s * FM + rt * 16 + fr) * 16 + 4 * fq;
+          sum[rt] = *reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+          for (int q = 1; q < 4; ++q) sum[rt] += *reinterpret_cast<const f32x4*>(src + q * 2 * FM * 16);
+        }
+        epi_adj(0, sum);
+      }
+      return;                                                       // (the split stage is the chain's last and has stored already)
+    } else if constexpr (FOLD && ph == 3) {
+      if (live) mma_stage(Ft, nullptr, LDF, kg * 256, nch, reg, c);
+    } else
     if (!(dbg & 2) && live)
       mma_stage(ph == 2 ? Hs : A1, (SPLIT && part == 0) ? (ph == 2 ? HsL : A1L) : nullptr, ph == 2 ? SW_LDH : SW_LDA, kg * 256, nch, reg, c);   // (part == 0 always when a set holds both packs)
     // refill this set, NSETS stages ahead.  Issuing a load can block (the queue is full while the weights stream), so where
@@ -451,15 +525,27 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(const MlpBlockParams p) 
   stamp(15);
 }
 
-template <int FM, int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM, bool STAMP = false, bool SPLIT = false>
+template <int FM, int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM, bool STAMP = false, bool SPLIT = false, bool FOLD = false>
 int launch_mlp_fm(const MlpBlockParams& p, hipStream_t stream) {
-  constexpr size_t lds = (size_t)(FM * SW_LDA + FM * SW_LDH) * 2 * (SPLIT ? 2 : 1) + (SW_NV + FM * 16) * sizeof(float);
-  const double flops = 2.0 * p.M * ((double)p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
-  const double bytes = 4.0 * p.M * (2.0 * p.d + p.no) + 2.0 * ((double)p.d * p.d + 2.0 * p.d * p.m + (double)p.no * p.d);
+  constexpr size_t lds = FOLD ? mlp_fold_lds(FM, KCD, KCM) : (size_t)(FM * SW_LDA + FM * SW_LDH) * 2 * (SPLIT ? 2 : 1) + (SW_NV + FM * 16) * sizeof(float);
+  // (FOLD: fc2 d x m and adjust no x d are one no x (d + m) GEMM)
+  const double mlp2 = FOLD ? (double)p.no * (p.d + p.m) : (double)p.d * p.m + (double)p.no * p.d;
+  const double flops = 2.0 * p.M * ((double)p.d * p.d + (double)p.d * p.m + mlp2);
+  const double bytes = 4.0 * p.M * (2.0 * p.d + p.no) + 2.0 * ((double)p.d * p.d + (double)p.d * p.m + mlp2);
   SradProfScope prof(stream, SRAD_K_MLP_BLOCK, flops, bytes);
-  SRAD_TRY((srad_launch_dyn<mlp_block_kernel<FM, GD, KGD, GM, KGM, GN, KCD, KCM, STAMP, SPLIT>>(dim3(p.M / FM), dim3(512), lds, stream, p)));
+  SRAD_TRY((srad_launch_dyn<mlp_block_kernel<FM, GD, KGD, GM, KGM, GN, KCD, KCM, STAMP, SPLIT, FOLD>>(dim3(p.M / FM), dim3(512), lds, stream, p)));
   SRAD_CHECK_HIP(hipGetLastError());
   return SRAD_OK;
+}
+// token rows per workgroup of a bf16 launch: the caller's choice where it divides M, else 16-row tiles until there are enough
+// tokens to fill the chip several times with wider ones
+int mlp_rows(int M, int fm) {
+  if (fm == 64 && M % 64 == 0) return 64;
+  if (fm == 32 && M % 32 == 0) return 32;
+  if (fm == 16) return 16;
+  if (M >= 32768 && M % 64 == 0) return 64;
+  if (M >= 8192 && M % 32 == 0) return 32;
+  return 16;
 }
 template <int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM>
 int launch_mlp(const MlpBlockParams& p, hipStream_t stream) {
@@ -467,14 +553,26 @@ int launch_mlp(const MlpBlockParams& p, hipStream_t stream) {
     if ((p.fm == 32 || (p.fm == 0 && p.M >= 8192)) && p.M % 32 == 0) return launch_mlp_fm<32, GD, KGD, GM, KGM, GN, KCD, KCM, false, true>(p, stream);
     return launch_mlp_fm<16, GD, KGD, GM, KGM, GN, KCD, KCM, false, true>(p, stream);
   }
-  // 16-row tiles until there are enough tokens to fill the chip several times with 64-row tiles
-  if (p.fm == 64 && p.M % 64 == 0) return launch_mlp_fm<64, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
-  if (p.fm == 32 && p.M % 32 == 0) return launch_mlp_fm<32, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
-  if (p.stamps && p.M % 16 == 0) return launch_mlp_fm<16, GD, KGD, GM, KGM, GN, KCD, KCM, true>(p, stream);   // diagnostic build
-  if (p.fm == 16) return launch_mlp_fm<16, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
-  if (p.M >= 32768 && p.M % 64 == 0) return launch_mlp_fm<64, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
-  if (p.M >= 8192 && p.M % 32 == 0) return launch_mlp_fm<32, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
+  const bool asked = (p.fm == 64 && p.M % 64 == 0) || (p.fm == 32 && p.M % 32 == 0);
+  if (p.stamps && !asked && p.M % 16 == 0) return launch_mlp_fm<16, GD, KGD, GM, KGM, GN, KCD, KCM, true>(p, stream);   // diagnostic build
+  const int fm = mlp_rows(p.M, p.fm);
+  if (fm == 64) return launch_mlp_fm<64, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
+  if (fm == 32) return launch_mlp_fm<32, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
   return launch_mlp_fm<16, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
+}
+// the folded form at the tile height the chain would take; a height whose folded tile does not fit the LDS has no instance
+// (srad_mlp_block_fold_supported says so first)
+template <int FM, int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM>
+int launch_mlp_fold_fm(const MlpBlockParams& p, hipStream_t stream) {
+  if constexpr (mlp_fold_fits(FM, KCD, KCM)) return launch_mlp_fm<FM, GD, KGD, GM, KGM, GN, KCD, KCM, false, false, true>(p, stream);
+  else return srad_set_error(SRAD_ERR_ARG, "mlp_block (folded): no instance at this tile height");
+}
+template <int GD, int KGD, int GM, int KGM, int GN, int KCD, int KCM>
+int launch_mlp_fold(const MlpBlockParams& p, hipStream_t stream) {
+  const int fm = mlp_rows(p.M, p.fm);
+  if (fm == 64) return launch_mlp_fold_fm<64, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
+  if (fm == 32) return launch_mlp_fold_fm<32, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
+  return launch_mlp_fold_fm<16, GD, KGD, GM, KGM, GN, KCD, KCM>(p, stream);
 }
 }  // namespace
 
@@ -489,8 +587,39 @@ bool srad_mlp_block_supported(int prec, int M, int d, int m, int no) {
   return false;
 }
 
-int srad_launch_mlp_block(const MlpBlockParams& p, hipStream_t stream) {
+// the folded second half (mlp_fold.h): bf16 only, the adjust widths the folded stage takes (one 128-column group takes the
+// k-split stage, which has two column tiles) and a tile height - the one the chain would take for M rows and `fm` - whose
+// folded A tile fits the LDS
+bool srad_mlp_block_fold_has(int M, int fm, int d, int m, int no) {
+  if (!srad_mlp_block_supported(SRAD_PREC_BF16, M, d, m, no) || !(no > SW_SC || no <= 32)) return false;
+  const SwinKey c = swin_key(d, 1, m, no);
+  return mlp_fold_fits(mlp_rows(M, fm), c.kc, c.kcm);
+}
+int srad_mlp_block_rows(int M) { return mlp_rows(M, 0); }
+extern "C" int srad_mlp_block_fold_supported(int prec, int T, int d, int m, int no) { return prec == SRAD_PREC_BF16 && srad_mlp_block_fold_has(T, 0, d, m, no); }
+
+// weight stages of the second half's chain and of its folded form (0 where the shape has none) for a block shape of the table
+extern "C" int srad_mlp_block_stage_counts(int d, int m, int no, int* chain, int* folded) {
+  SRAD_REQUIRE(chain && folded, "mlp_block_stage_counts: null argument");
+  const SwinKey c = swin_key(d, 1, m, no);
+#define X(d_, h_, m_, no_, wpc_) \
+  if (constexpr SwinKey k = swin_key(d_, h_, m_, no_); swin_key_mlp_eq(c, k)) { \
+    *chain = MlpChain<k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kc, k.kcm>::n_stages; \
+    *folded = (no > SW_SC || no <= 32) ? MlpFoldChain<k.gd, k.kgd, k.gm, k.gn, k.kc, k.kcm, k.gn == 1>::n_stages : 0; \
+    return SRAD_OK; \
+  }
+  SRAD_SWIN_SHAPES(X)
+#undef X
+  return srad_set_error(SRAD_ERR_ARG, "mlp_block_stage_counts: no kernel instance for this geometry");
+}
+
+static int launch_mlp_block(const MlpBlockParams& p, bool fold, hipStream_t stream) {
   SRAD_REQUIRE(srad_mlp_block_supported(SRAD_PREC_BF16, p.M, p.d, p.m, p.no), "mlp_block: unsupported shape M=%d d=%d m=%d no=%d", p.M, p.d, p.m, p.no);
+  if (fold) {
+    SRAD_REQUIRE(srad_mlp_block_fold_has(p.M, p.fm, p.d, p.m, p.no), "mlp_block: no folded form for M=%d fm=%d d=%d m=%d no=%d", p.M, p.fm, p.d, p.m, p.no);
+    SRAD_REQUIRE(!p.split && !p.stamps && !p.dbg && !p.rs1 && !p.rs2 && !p.save_x1 && !p.save_xn2 && !p.save_hpre && !p.save_hact && !p.save_x2 &&
+                     !p.save_hpre_h && !p.save_xn2_h && !p.save_hact_h && !p.save_x2_h, "mlp_block (folded): plain bf16 inference only");
+  }
   if (p.split) {
     SRAD_REQUIRE(p.attn_f && (p.ld_attn & 3) == 0 && ((uintptr_t)p.attn_f & 15) == 0, "mlp_block (split-bf16): the fp32 attn rows must be float4-addressable");
     SRAD_REQUIRE(p.w_proj_lo && p.w_fc1_lo && p.w_fc2_lo && p.w_adj_lo, "mlp_block (split-bf16): the lo weight packs are missing");
@@ -506,8 +635,15 @@ int srad_launch_mlp_block(const MlpBlockParams& p, hipStream_t stream) {
                "mlp_block: bias / LayerNorm vectors must be 16-byte aligned");
   const SwinKey c = swin_key(p.d, 1, p.m, p.no);
 #define X(d_, h_, m_, no_, wpc_) \
-  if (constexpr SwinKey k = swin_key(d_, h_, m_, no_); swin_key_mlp_eq(c, k)) return launch_mlp<k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kc, k.kcm>(p, stream);
+  if (constexpr SwinKey k = swin_key(d_, h_, m_, no_); swin_key_mlp_eq(c, k)) { \
+    if (fold) return launch_mlp_fold<k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kc, k.kcm>(p, stream); \
+    return launch_mlp<k.gd, k.kgd, k.gm, k.kgm, k.gn, k.kc, k.kcm>(p, stream); \
+  }
   SRAD_SWIN_SHAPES(X)
 #undef X
   return srad_set_error(SRAD_ERR_ARG, "mlp_block: no kernel instance for this geometry");
 }
+
+int srad_launch_mlp_block(const MlpBlockParams& p, hipStream_t stream) { return launch_mlp_block(p, false, stream); }
+// p.w_adj = the fragment pack of [A | A W2], p.b_adj = A b2 + b_a (mlp_fold.h); p.w_fc2 is not read (any non-null pointer)
+int srad_launch_mlp_block_folded(const MlpBlockParams& p, hipStream_t stream) { return launch_mlp_block(p, true, stream); }

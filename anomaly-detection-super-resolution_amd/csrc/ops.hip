@@ -178,16 +178,24 @@ int srad_bench_mlp_block(int M, int d, int m, int no, const void* attn /* bf16 [
     q.w_proj_lo = lo; q.w_fc1_lo = lo + b1; q.w_fc2_lo = lo + b1 + b2; q.w_adj_lo = lo + b1 + b2 + b3;
     q.dbg = 0;
   } else
+  if (dbg & 0x40000) {                              // bit 18: the folded second half, [A | A W2] cut from w_fp32 like every weight:
+    const MlpFoldLayout l = mf_layout(d, m, no);    // the pack of a [no][32 (KC + KCM)] matrix over the fc2 and adjust packs' space
+    SRAD_REQUIRE(srad_mlp_block_fold_has(M, q.fm, d, m, no), "bench_mlp_block: no folded form for this shape");
+    SRAD_REQUIRE(b3 + b4 >= (size_t)srad_np(no) * l.kf * 2, "bench_mlp_block: the folded pack does not fit the scratch layout");
+    SRAD_TRY(srad_launch_pack_weight_frag(w_fp32, sc + b1 + b2, no, l.kf, s));
+    q.w_adj = sc + b1 + b2; q.dbg = 0;
+  } else
   if (dbg & 0x100ff) {                              // bit 16 or any switch-off bit: the diagnostic build; its stamps go behind the packed weights
     SRAD_REQUIRE(scratch_bytes >= b1 + b2 + b3 + b4 + (size_t)(M / 16) * 8 * 16 * 8, "bench_mlp_block: scratch too small for the stamps");
     q.stamps = reinterpret_cast<unsigned long long*>(sc + b1 + b2 + b3 + b4);
   }
-  for (int i = 0; i < 3; ++i) SRAD_TRY(srad_launch_mlp_block(q, s));
+  const auto launch = (dbg & 0x40000) ? srad_launch_mlp_block_folded : srad_launch_mlp_block;
+  for (int i = 0; i < 3; ++i) SRAD_TRY(launch(q, s));
   hipEvent_t a, b;
   SRAD_CHECK_HIP(hipEventCreate(&a));
   SRAD_CHECK_HIP(hipEventCreate(&b));
   SRAD_CHECK_HIP(hipEventRecord(a, s));
-  for (int i = 0; i < iters; ++i) SRAD_TRY(srad_launch_mlp_block(q, s));
+  for (int i = 0; i < iters; ++i) SRAD_TRY(launch(q, s));
   SRAD_CHECK_HIP(hipEventRecord(b, s));
   SRAD_CHECK_HIP(hipEventSynchronize(b));
   float ms = 0.f;
@@ -339,6 +347,38 @@ int srad_op_mlp_block(int precision, int M, int d, int m, int no, int fm, const 
   q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.b_adj = b_adj; q.ln_g = ln_g; q.ln_b = ln_b;
   q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff; q.fm = fm;
   return srad_launch_mlp_block(q, s);
+}
+
+// The same second half with fc2 folded into the adjust conv (mlp_fold.h; bf16): the two packs the kernel still reads, then
+// [A | A W2] and A b2 + b_a composed behind the pair's layout in scratch
+int srad_op_mlp_block_folded(int precision, int M, int d, int m, int no, int fm, const void* attn /* bf16 [M][d] */, const float* shortcut, int ld_short,
+                             const float* w_proj, const float* b_proj, const float* ln_g, const float* ln_b, const float* w_fc1,
+                             const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
+                             float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
+                             size_t scratch_bytes, void* stream) {
+  SRAD_REQUIRE(attn && shortcut && w_proj && b_proj && ln_g && ln_b && w_fc1 && b_fc1 && w_fc2 && b_fc2 && w_adj && b_adj && y && scratch,
+               "op_mlp_block_folded: null argument");
+  SRAD_REQUIRE(fm == 0 || ((fm == 16 || fm == 32 || fm == 64) && M % fm == 0), "op_mlp_block_folded: fm must be 0, 16, 32 or 64 and divide M");
+  SRAD_REQUIRE(precision == SRAD_PREC_BF16 && srad_mlp_block_fold_has(M, fm, d, m, no),
+               "op_mlp_block_folded: unsupported: precision %d, M=%d fm=%d d=%d m=%d no=%d (bf16, no <= 32 or > 128, a tile height whose folded tile fits the LDS)",
+               precision, M, fm, d, m, no);
+  size_t off[10];
+  swin_scratch_parts(d, 1, m, no, off);
+  const MlpFoldLayout l = mf_layout(d, m, no);
+  SRAD_REQUIRE(scratch_bytes >= off[5] + l.bytes && ((uintptr_t)scratch & 255) == 0,
+               "op_mlp_block_folded: scratch %zu bytes, %zu needed (256-byte aligned)", scratch_bytes, off[5] + l.bytes);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* sc = reinterpret_cast<char*>(scratch);
+  SRAD_TRY(srad_launch_pack_weight_frag(w_proj, sc + off[1], d, d, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fc1, sc + off[2], m, d, s));
+  char* const fold = sc + off[5];
+  SRAD_TRY(srad_mlp_fold_from_sources(l, fold, w_fc2, b_fc2, w_adj, b_adj, s));
+  MlpBlockParams q{};
+  q.attn_h = reinterpret_cast<const __bf16*>(attn); q.ld_attn = d; q.shortcut = shortcut; q.ld_short = ld_short; q.M = M; q.d = d; q.m = m; q.no = no;
+  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = fold + l.pack; q.w_adj = fold + l.pack;
+  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.b_adj = reinterpret_cast<const float*>(fold + l.bias); q.ln_g = ln_g; q.ln_b = ln_b;
+  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff; q.fm = fm;
+  return srad_launch_mlp_block_folded(q, s);
 }
 
 // A whole Swin block + the adjust conv in one launch (kernels_fused_block.hip): the two ops above back to back, x being the shortcut.

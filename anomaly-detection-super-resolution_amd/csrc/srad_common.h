@@ -368,6 +368,14 @@ struct MlpBlockParams {
 };
 bool srad_mlp_block_supported(int prec, int M, int d, int m, int no);
 int srad_launch_mlp_block(const MlpBlockParams& p, hipStream_t stream);
+// The same launch with the folded second half (mlp_fold.h): proj | fc1 | adjF.  w_adj = the fragment pack
+// of [A | A W2], b_adj = A b2 + b_a, w_fc2 is not read; plain bf16 inference (no split, saves, DropPath or stamps).
+// fold_has: is there a folded instance for these rows at the tile height `fm` selects (0 = chosen from M)?
+// (srad_mlp_block_fold_supported(prec, T, d, m, no), the same question at fm = 0, is part of the C ABI: include/srad.h)
+bool srad_mlp_block_fold_has(int M, int fm, int d, int m, int no);
+// token rows per workgroup a bf16 launch of M rows picks on its own (16 below 8192 rows, 32 from there, 64 from 32768)
+int srad_mlp_block_rows(int M);
+int srad_launch_mlp_block_folded(const MlpBlockParams& p, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
 // Fused first half of a Swin block (kernels_fused_attn.hip): LayerNorm1 -> q|k|v of one head ->

@@ -64,6 +64,14 @@ struct MlpFoldChain {
     return MlpStage{ph, g, kg, kc, kc - kg * 8 < 8 ? kc - kg * 8 : 8, s == 0, kg == kgs - 1};
   }
 };
+// mlp_block_kernel's folded form: row stride of the folded A tile [rows][32 (KCD + KCM) + 16] (2 mod 4
+// sixteen-byte units), and the launch's LDS bytes with that tile in the hidden tile's place; a tile height whose bytes exceed
+// the 160 KB of a CU has no folded instance
+constexpr int mlp_fold_ldf(int kcd, int kcm) { return 32 * (kcd + kcm) + 16; }
+constexpr size_t mlp_fold_lds(int fm, int kcd, int kcm) {
+  return (size_t)(fm * SW_LDA + fm * mlp_fold_ldf(kcd, kcm)) * 2 + (size_t)(SW_NV + fm * 16) * sizeof(float);
+}
+constexpr bool mlp_fold_fits(int fm, int kcd, int kcm) { return mlp_fold_lds(fm, kcd, kcm) <= 160 * 1024; }
 
 // ---- DRCT-L's five Swin block shapes, the one table behind every instance of the four kernels:
 //      (d, heads, MLP hidden, adjust outputs, qkv_attn workgroups per CU).  The last column is tuning that cannot be derived.

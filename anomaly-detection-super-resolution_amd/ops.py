@@ -799,6 +799,33 @@ def swin_block_folded(x: torch.Tensor, ln1_g, ln1_b, w_qkv, b_qkv, table, w_proj
     return out
 
 
+def mlp_block_fold_supported(T: int, d: int, hidden: int, no: int, precision: str = "bf16") -> bool:
+    """Does a ``mlp_block`` launch of T rows have a folded form at the tile height it picks (``srad_mlp_block_fold_supported``)?"""
+    return bool(L.lib().srad_mlp_block_fold_supported(L.PRECISIONS[precision], T, d, hidden, no))
+
+
+def mlp_block_folded(attn: torch.Tensor, shortcut: torch.Tensor, w_proj, b_proj, ln_g, ln_b, w_fc1, b_fc1, w_fc2, b_fc2, w_adj, b_adj, *,
+                     act: int = L.ACT_LRELU, slope: float = 0.2, alpha: float = 1.0, residual: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, out_offset: int = 0, fm: int = 0, precision: str = "bf16") -> torch.Tensor:
+    """``mlp_block`` with fc2 folded into the adjust conv (``srad_op_mlp_block_folded``; bf16 inference): the same arguments and
+    the same result up to rounding - adjust(x1 + fc2(h) + b2) as one GEMM [A | A W2] [x1 | h] + (A b2 + b_a)."""
+    _need_cuda(attn, shortcut, w_proj, w_fc1, w_fc2, w_adj)
+    M, d = attn.shape
+    m, no = w_fc1.shape[0], w_adj.shape[0]
+    f = lambda t: t.detach().float().contiguous()
+    keep = [f(w_proj), f(b_proj), f(ln_g), f(ln_b), f(w_fc1), f(b_fc1), f(w_fc2), f(b_fc2), f(w_adj.reshape(no, d)), f(b_adj)]
+    attn = attn.detach().to(torch.bfloat16).contiguous()
+    if out is None:
+        out = torch.empty(M, no, dtype=torch.float32, device=attn.device)
+    lib = L.lib()
+    sbuf, sp, sb = L.ws_buffer(lib.srad_op_swin_scratch_bytes(d, 1, m, no) + lib.srad_op_mlp_fold_scratch_bytes(d, m, no), attn.device)
+    L.check(lib.srad_op_mlp_block_folded(L.PRECISIONS[precision], M, d, m, no, int(fm), L.dptr(attn), L.dptr(shortcut), shortcut.stride(0),
+                                         *[L.dptr(k) for k in keep], int(act), float(slope), float(alpha), L.dptr(residual),
+                                         0 if residual is None else residual.stride(0), L.dptr(out), out.stride(0), int(out_offset), sp, sb,
+                                         L.current_stream_ptr()), "op_mlp_block_folded")
+    return out
+
+
 # ----------------------------------------------------------------------------------- self-ensemble x8
 def _ensemble_arg(t: torch.Tensor, what: str) -> torch.Tensor:
     _need_cuda(t)

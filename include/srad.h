@@ -685,6 +685,19 @@ int srad_op_swin_block_folded(int precision, const float* x, int ldx, int B, int
                               const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj,
                               int act, float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
                               size_t scratch_bytes, void* stream);
+/* The same fold in the two-launch form: srad_op_mlp_block_folded is srad_op_mlp_block (bf16) with the second
+ * half proj | fc1 | adjF; its scratch holds srad_op_swin_scratch_bytes(d, 1, m, no) followed by
+ * srad_op_mlp_fold_scratch_bytes(d, m, no).  srad_mlp_block_fold_supported: bf16, a shape of the fused second half, an adjust
+ * width the folded stage takes (no <= 32 or no > 128) and, at the tile height the launch picks for T rows, a folded tile
+ * that fits the LDS (64-row tiles at d = 244 do not).  The DRCT engine folds the launches on 16-row tiles (T < 8192). */
+int srad_mlp_block_fold_supported(int precision, int T, int d, int m, int no);
+/* weight stages of the second half's chain and of its folded form (0: the adjust width has none) at a block shape of the table */
+int srad_mlp_block_stage_counts(int d, int m, int no, int* chain, int* folded);
+int srad_op_mlp_block_folded(int precision, int M, int d, int m, int no, int fm, const void* attn, const float* shortcut, int ld_short,
+                             const float* w_proj, const float* b_proj, const float* ln_g, const float* ln_b, const float* w_fc1,
+                             const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
+                             float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
+                             size_t scratch_bytes, void* stream);
 
 /* DRCT's output end folded into one launch.  Everything after conv_before_upsample's LeakyReLU - the Upsample
  * convolutions with their PixelShuffles, conv_last, then / img_range + mean (src/drct.py:694-713, 842-847, 894-897) - is linear:
@@ -928,8 +941,8 @@ enum { SRAD_PATH_PLAN_FIRST = 16, SRAD_PATH_BLOCK_TWO_LAUNCHES = 16, SRAD_PATH_T
 enum { SRAD_PATH_PLAN2_FIRST = 32, SRAD_PATH_ENDS_CHAIN = 32, SRAD_PATH_PLAN2_END = 33 };
 /* ... and in a third range (33 .. 47 stay unknown):
  *   SRAD_PATH_FC2_CHAIN           DRCT bf16 inference forward: a Swin block's fc2 and the adjust conv as the two GEMMs of the
- *                                 chain where the folded second half (srad_op_swin_block_folded) would run (read at every
- *                                 forward) */
+ *                                 chain where the folded second half (srad_op_swin_block_folded, srad_op_mlp_block_folded)
+ *                                 would run (read at every forward) */
 enum { SRAD_PATH_PLAN3_FIRST = 48, SRAD_PATH_FC2_CHAIN = 48, SRAD_PATH_PLAN3_END = 49 };
 int srad_set_path_override(int path, int on);
 int srad_get_path_override(int path);
