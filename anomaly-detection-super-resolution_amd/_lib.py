@@ -100,6 +100,7 @@ _SIG = {
     "srad_drct_set_param": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),
     "srad_drct_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "srad_drct_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "srad_drct_graph_captures": (C.c_int, [_P]),
     "srad_drct_flops": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     # DRCT training
     "srad_drct_train_param_floats": (C.c_int, [_P, C.POINTER(C.c_int64)]),

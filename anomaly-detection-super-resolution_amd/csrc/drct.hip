@@ -49,14 +49,18 @@ DrctWs plan_ws(const srad_drct* h, int B, int H, int W, void* base, size_t cap) 
   return w;
 }
 
-int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, const DrctWs& w, hipStream_t s) {
+// parts (drct_engine.h): the whole forward, or its entry / interior / exit alone; x is read by the entry only and y written by
+// the exit only
+int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, const DrctWs& w, hipStream_t s, int parts = DRCT_ALL) {
   const srad_drct_config& c = h->cfg;
   const int prec = c.precision;
   const int T = B * H * W;
   const int E = c.embed_dim, D = E + 4 * c.gc;
-  SRAD_TRY(drct_stem(h, x, B, H, W, w, w.dense0, s));
+  SRAD_TRY(drct_stem(h, x, B, H, W, w, w.dense0, s, parts));
   float* cur = w.dense0;
   float* nxt = w.dense1;
+  // an odd number of RDGs leaves the last residual stream in dense1
+  if (!(parts & DRCT_INTERIOR)) return drct_tail(h, c.n_rdg % 2 ? nxt : cur, B, H, W, w, c.in_chans, y, s, h->fold_in_graph, h->ends_in_graph, parts);
   for (int i = 0; i < c.n_rdg; ++i) {
     for (int k = 0; k < 5; ++k) {
       const SwinW& sw = h->blocks[i * 5 + k];
@@ -186,7 +190,7 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
     }
     float* t = cur; cur = nxt; nxt = t;
   }
-  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s, h->fold_in_graph, h->ends_in_graph);
+  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s, h->fold_in_graph, h->ends_in_graph, parts);
 }
 
 // Does this forward run the body end as one launch?  Inference handles only, as the fold: srad_drct_sync_params does not
@@ -228,13 +232,15 @@ static void drct_mean(const srad_drct_config& c, float m[3]) {   // MeanShift: t
   for (int i = 0; i < 3; ++i) m[i] = c.in_chans == 3 ? rgb[i] : 0.f;
 }
 
-int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s) {
+int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s,
+              int parts) {
   const srad_drct_config& c = h->cfg;
   const int T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc;
   float mean3[3];
   drct_mean(c, mean3);
   // (x - mean) * img_range, NCHW -> NHWC            (drct.py:887-888)
-  SRAD_TRY(srad_launch_nchw_to_nhwc(x, w.xin, B, c.in_chans, SRAD_IMG_CPAD, H, W, mean3, c.img_range, s));
+  if (parts & DRCT_ENTRY) SRAD_TRY(srad_launch_nchw_to_nhwc(x, w.xin, B, c.in_chans, SRAD_IMG_CPAD, H, W, mean3, c.img_range, s));
+  if (!(parts & DRCT_INTERIOR)) return SRAD_OK;
   // conv_first                                       (drct.py:892)
   {
     GemmParams p = drct_gemm(h, h->conv_first, w.xin, SRAD_IMG_CPAD, T, w.feat0, E);
@@ -247,10 +253,13 @@ int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const Drc
 }
 
 int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
-              hipStream_t s, bool fold, bool ends) {
+              hipStream_t s, bool fold, bool ends, int parts) {
   const srad_drct_config& c = h->cfg;
   const int prec = c.precision, T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc, F = c.num_feat;
-  if (ends) {
+  const bool interior = (parts & DRCT_INTERIOR) != 0, last = (parts & DRCT_EXIT) != 0;
+  if (!interior) {
+    // the launches ahead of the last one belong to another call
+  } else if (ends) {
     // norm, conv_after_body + x and conv_before_upsample + LeakyReLU(0.01) as one launch into c2 (kernels_drct_ends.hip)
     DrctBodyEndParams p{};
     p.X = dense; p.ldx = D; p.ln_g = h->pt.fptr(h->norm_g); p.ln_b = h->pt.fptr(h->norm_b);
@@ -275,26 +284,28 @@ int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const
   float mean3[3];
   drct_mean(c, mean3);
   // Upsample, conv_last and x / img_range + mean as one 5 x 5 convolution of c2 (kernels_tail_fold.hip; drct.py:694-713, 895-897)
-  if (fold) return srad_launch_tail_fold(h->fold, h->pt.arena + h->fold_off, w.c2, B, H, W, y, 1.0f / c.img_range, mean3, s);
+  if (fold) return last ? srad_launch_tail_fold(h->fold, h->pt.arena + h->fold_off, w.c2, B, H, W, y, 1.0f / c.img_range, mean3, s) : SRAD_OK;
   // Upsample: conv 64->256 + PixelShuffle(2) per stage (drct.py:694-713)
   const float* src = w.c2;
   int hh = H, ww = W;
   for (size_t j = 0; j < h->up.size(); ++j) {
-    GemmParams p = drct_gemm(h, h->up[j], src, F, B * hh * ww, w.upb[j], F);
-    geom(p, hh, ww);
-    p.ps = 2;
-    SRAD_TRY(srad_launch_gemm(prec, p, s));
+    if (interior) {
+      GemmParams p = drct_gemm(h, h->up[j], src, F, B * hh * ww, w.upb[j], F);
+      geom(p, hh, ww);
+      p.ps = 2;
+      SRAD_TRY(srad_launch_gemm(prec, p, s));
+    }
     src = w.upb[j];
     hh *= 2; ww *= 2;
   }
   // conv_last                                         (drct.py:895)
-  {
+  if (interior) {
     GemmParams p = drct_gemm(h, h->conv_last, src, F, B * hh * ww, w.outn, ld_outn);
     geom(p, hh, ww);
     SRAD_TRY(srad_launch_gemm(prec, p, s));
   }
   // x / img_range + mean, NHWC -> NCHW                (drct.py:897)
-  return srad_launch_nhwc_to_nchw(w.outn, ld_outn, y, B, c.in_chans, hh, ww, mean3, 1.0f / c.img_range, s);
+  return last ? srad_launch_nhwc_to_nchw(w.outn, ld_outn, y, B, c.in_chans, hh, ww, mean3, 1.0f / c.img_range, s) : SRAD_OK;
 }
 
 QkvAttnParams drct_qkv_attn_params(const srad_drct* h, const SwinW& sw, const float* cur, int B, int H, int W) {
@@ -530,9 +541,17 @@ int srad_drct_forward(srad_drct_t* h, const float* x, int B, int H, int W, float
       }
     h->mfold_stale = false;
   }
-  return srad_run_with_graph(h->gc, h->cfg.use_graph != 0, x, y, workspace, B, H, W, s,
-                             [&](hipStream_t st) { return forward_body(h, x, B, H, W, y, w, st); });
+  // Graph replay: only the interior is recorded, keyed on the workspace and the shape; the entry and the exit launch on the
+  // stream either side of it, so a new x or y neither recaptures nor costs a copy.  (The legacy default stream cannot be
+  // captured: there, and with the graph off, the forward is one eager sequence.)
+  if (!h->cfg.use_graph || s == nullptr) return forward_body(h, x, B, H, W, y, w, s);
+  SRAD_TRY(forward_body(h, x, B, H, W, y, w, s, DRCT_ENTRY));
+  SRAD_TRY(srad_run_with_graph(h->gc, true, workspace, B, H, W, s,
+                               [&](hipStream_t st) { return forward_body(h, nullptr, B, H, W, nullptr, w, st, DRCT_INTERIOR); }));
+  return forward_body(h, x, B, H, W, y, w, s, DRCT_EXIT);
 }
+
+int srad_drct_graph_captures(const srad_drct_t* h) { return h ? h->gc.captures : 0; }
 
 int srad_drct_flops(const srad_drct_t* h, int B, int H, int W, double* flops) {
   SRAD_REQUIRE(h && flops, "drct_flops: null argument");

@@ -66,13 +66,20 @@ struct DrctStemTail {
   float *xin, *feat0, *body, *c1, *c2, *outn;
   std::vector<float*> upb;
 };
+// The forward's launches in three parts: the entry is the one launch that reads x, the exit the one launch that writes y,
+// the interior everything between them, which touches the workspace and the weight arena only.  The inference forward
+// records just the interior into its graph (drct.hip), so the graph does not depend on the call's x and y.
+enum : int { DRCT_ENTRY = 1, DRCT_INTERIOR = 2, DRCT_EXIT = 4, DRCT_ALL = 7 };
 // (x - mean) * img_range -> conv_first -> patch_embed.norm into dense0[:, :embed]            (drct.py:887-892, 873)
-int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s);
+// parts: DRCT_ENTRY the layout launch off x, DRCT_INTERIOR the rest
+int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s,
+              int parts = DRCT_ALL);
 // norm -> conv_after_body + x -> conv_before_upsample -> Upsample -> conv_last (into outn, row stride ld_outn) -> y   (drct.py:881, 893-897)
 // fold: everything after conv_before_upsample as the one folded launch (the caller has checked drct_fold_active and freshness)
 // ends: norm, conv_after_body and conv_before_upsample as the one body-end launch (the caller has checked drct_ends_active)
+// parts: DRCT_EXIT the last launch (the folded launch, or the chain's layout launch into y), DRCT_INTERIOR all before it
 int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
-              hipStream_t s, bool fold = false, bool ends = false);
+              hipStream_t s, bool fold = false, bool ends = false, int parts = DRCT_ALL);
 // The fields both forwards set for Swin block `sw` of an RDG, block k of its five: weights, biases, LayerNorm, geometry, and
 // (mlp_block) the adjust conv's residual and output in the dense buffers cur / nxt
 QkvAttnParams drct_qkv_attn_params(const srad_drct* h, const SwinW& sw, const float* cur, int B, int H, int W);

@@ -149,6 +149,7 @@ struct GraphCache {
   const void* key[3] = {nullptr, nullptr, nullptr};
   int shape[3] = {0, 0, 0};
   int seen = 0;   // eager runs with the current key (the first call runs eagerly, the second captures)
+  int captures = 0;   // graphs instantiated over the handle's life (reset() keeps the count)
   bool matches(const void* a, const void* b, const void* c, int B, int H, int W) const {
     return key[0] == a && key[1] == b && key[2] == c && shape[0] == B && shape[1] == H && shape[2] == W;
   }
@@ -186,6 +187,14 @@ int srad_run_with_graph(GraphCache& gc, bool enable, const void* a, const void* 
   if (e != hipSuccess) return srad_set_error(SRAD_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
   gc.graph = g;
   SRAD_CHECK_HIP(hipGraphInstantiate(&gc.exec, g, nullptr, nullptr, 0));
+  ++gc.captures;
   SRAD_CHECK_HIP(hipGraphLaunch(gc.exec, stream));
   return SRAD_OK;
+}
+
+// The same for a launch sequence that touches the workspace (and the weight arena) only: keyed on the workspace and the shape,
+// whatever the call's input and output pointers are.
+template <class F>
+int srad_run_with_graph(GraphCache& gc, bool enable, const void* workspace, int B, int H, int W, hipStream_t stream, F&& body) {
+  return srad_run_with_graph(gc, enable, nullptr, nullptr, workspace, B, H, W, stream, static_cast<F&&>(body));
 }

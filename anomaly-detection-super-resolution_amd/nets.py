@@ -573,24 +573,20 @@ class DRCT(_EngineModule):
         self._sync_weights(dev)
         ws = self._workspace(B, H, W, dev)
         s = self.upscale
-        if self.use_graph:
-            key = (B, H, W)
-            if key not in self._static_io:
-                self._static_io = {key: (torch.empty_like(x), torch.empty(B, self.cfg.in_chans, H * s, W * s,
-                                                                          dtype=torch.float32, device=dev))}
-            xin, yout = self._static_io[key]
-        else:
-            xin = x
-            yout = torch.empty(B, self.cfg.in_chans, H * s, W * s, dtype=torch.float32, device=dev)
+        # graph replay records only the launches between the one that reads x and the one that writes y (csrc/drct.hip): the
+        # caller's input and a fresh output go straight in, with the graph on or off
+        yout = torch.empty(B, self.cfg.in_chans, H * s, W * s, dtype=torch.float32, device=dev)
         wp, wb = self._aligned(ws)
 
         def launch():
-            if self.use_graph:
-                xin.copy_(x)
-            L.check(L.lib().srad_drct_forward(self._handle, L.dptr(xin), B, H, W, L.dptr(yout), wp, wb,
+            L.check(L.lib().srad_drct_forward(self._handle, L.dptr(x), B, H, W, L.dptr(yout), wp, wb,
                                               L.current_stream_ptr()), "drct_forward")
-            return yout.clone() if self.use_graph else yout
+            return yout
         return self._run(launch)
+
+    def graph_captures(self) -> int:
+        """hipGraphs the engine has instantiated so far (0 before the first forward)."""
+        return 0 if self._handle is None else int(L.lib().srad_drct_graph_captures(self._handle))
 
 
 # ------------------------------------------------------------------ DRN

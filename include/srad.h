@@ -67,6 +67,8 @@ int srad_drct_workspace_bytes(const srad_drct_t* h, int B, int H, int W, size_t*
 /* DRCT.forward (src/drct.py:886-898): x [B,C,H,W] -> y [B,C,H*s,W*s]; H, W multiples of the window */
 int srad_drct_forward(srad_drct_t* h, const float* x, int B, int H, int W, float* y, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* read-only: hipGraphs this handle has instantiated so far (use_graph: one per workspace and shape, whatever x and y are) */
+int srad_drct_graph_captures(const srad_drct_t* h);
 /* FLOPs (2 per MAC) of one forward at this shape, for roofline accounting */
 int srad_drct_flops(const srad_drct_t* h, int B, int H, int W, double* flops);
 
