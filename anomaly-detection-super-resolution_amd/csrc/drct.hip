@@ -49,106 +49,115 @@ DrctWs plan_ws(const srad_drct* h, int B, int H, int W, void* base, size_t cap) 
   return w;
 }
 
-// parts (drct_engine.h): the whole forward, or its entry / interior / exit alone; x is read by the entry only and y written by
-// the exit only
-int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, const DrctWs& w, hipStream_t s, int parts = DRCT_ALL) {
+// How one Swin block of an inference forward runs: decided in drct_block_path, launched in forward_body.  First half (LayerNorm1,
+// qkv, attention): in the one-launch block | qkv_attn | ln_qkv (bf16 q | k | v out; split-bf16: fp32 out) or the tiled GEMM, then
+// the attention.  qkv_bf16 (64 x 64 windows, bf16): q | k | v are written as the attention's bf16 MFMA operands, scaled by qscale.
+enum DrctFirstHalf { DRCT_H1_IN_BLOCK, DRCT_H1_QKV_ATTN, DRCT_H1_LN_QKV, DRCT_H1_LN_QKV_SPLIT, DRCT_H1_GEMM };
+// Second half (proj .. adjust_k): in the block or as mlp_block, fc2 as it is or folded into the adjust conv | the four-GEMM chain
+enum DrctSecondHalf { DRCT_H2_IN_BLOCK, DRCT_H2_IN_BLOCK_FOLDED, DRCT_H2_MLP_BLOCK, DRCT_H2_MLP_BLOCK_FOLDED, DRCT_H2_CHAIN };
+struct DrctBlockPath { DrctFirstHalf first; DrctSecondHalf second; bool qkv_bf16; float qscale; };
+// (no allocation and no string: this runs for every block of every eager forward)
+DrctBlockPath drct_block_path(const srad_drct* h, const SwinW& sw, int k, int B, int H, int W, const DrctPaths& paths) {
   const srad_drct_config& c = h->cfg;
-  const int prec = c.precision;
-  const int T = B * H * W;
-  const int E = c.embed_dim, D = E + 4 * c.gc;
+  const int prec = c.precision, ws = c.window_size, T = B * H * W, d = sw.d, no = k < 4 ? c.gc : c.embed_dim;
+  DrctBlockPath p{DRCT_H1_GEMM, DRCT_H2_CHAIN, false, 1.f};
+  const bool mlp_fused = h->fuse_mlp && srad_mlp_block_supported(prec, T, d, sw.hidden, no);
+  // the whole block as ONE launch (kernels_fused_block.hip) where the windows' quarters fit the chip in one wave of workgroups
+  // and the block shape measured a win over the pair below; this path has no saves and no DropPath
+  if (mlp_fused && srad_swin_block_supported(prec, ws, B, H, W, d, sw.heads, sw.hidden, no) && srad_swin_block_wins(d, sw.heads, sw.hidden, no) &&
+      !srad_path_override(SRAD_PATH_BLOCK_TWO_LAUNCHES)) {
+    const bool folded = paths.mfold && srad_swin_block_fold_supported(prec, ws, B, H, W, d, sw.heads, sw.hidden, no);
+    return DrctBlockPath{DRCT_H1_IN_BLOCK, folded ? DRCT_H2_IN_BLOCK_FOLDED : DRCT_H2_IN_BLOCK, false, 1.f};
+  }
+  if (h->fuse_mlp && srad_qkv_attn_supported(prec, ws, H, W, d, sw.heads)) p.first = DRCT_H1_QKV_ATTN;
+  else {
+    p.qkv_bf16 = srad_window_attn_bf16_in(prec, ws, sw.shift, d, sw.heads, &p.qscale);
+    const auto ln_qkv = [&] { return srad_ln_qkv_supported(prec, T, d, sw.heads) && !srad_path_override(SRAD_PATH_QKV_VIA_GEMM); };
+    if (p.qkv_bf16 && h->pt.frag_ptr(sw.qkv.w) && ln_qkv()) p.first = DRCT_H1_LN_QKV;
+    else if (prec == SRAD_PREC_BF16X3 && ws == 64 && h->pt.frag_ptr(sw.qkv.w) && h->pt.frag_lo_ptr(sw.qkv.w) && ln_qkv()) p.first = DRCT_H1_LN_QKV_SPLIT;
+  }
+  // mlp_block folded on 16-row tiles only - the form the one-launch block's second half has: a forward on 32- or
+  // 64-row tiles keeps the chain (tests/test_gpu_mlp_fold.py; the wider folded instances exist at the op level)
+  if (mlp_fused)
+    p.second = paths.mfold && srad_mlp_block_rows(T) == 16 && srad_mlp_block_fold_supported(prec, T, d, sw.hidden, no) ? DRCT_H2_MLP_BLOCK_FOLDED : DRCT_H2_MLP_BLOCK;
+  return p;
+}
+
+// w_adj / b_adj of a folded launch: the pack [A | A W2] and the bias A b2 + b_a in block blk's region
+template <class Params> void drct_fold_adjust(const srad_drct* h, int blk, Params& p) {
+  const char* const reg = h->pt.arena + h->derived.region(DRCT_BLOCK_FOLD, blk).off;
+  p.w_adj = reg + h->mfold[blk].pack; p.b_adj = reinterpret_cast<const float*>(reg + h->mfold[blk].bias);
+}
+
+// parts (drct_engine.h): the whole forward, or its entry / interior / exit alone; only the entry reads x, only the exit writes y
+int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, const DrctWs& w, hipStream_t s, const DrctPaths& paths,
+                 int parts = DRCT_ALL) {
+  const srad_drct_config& c = h->cfg;
+  const int prec = c.precision, T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc;
   SRAD_TRY(drct_stem(h, x, B, H, W, w, w.dense0, s, parts));
-  float* cur = w.dense0;
-  float* nxt = w.dense1;
+  float *cur = w.dense0, *nxt = w.dense1;
   // an odd number of RDGs leaves the last residual stream in dense1
-  if (!(parts & DRCT_INTERIOR)) return drct_tail(h, c.n_rdg % 2 ? nxt : cur, B, H, W, w, c.in_chans, y, s, h->fold_in_graph, h->ends_in_graph, parts);
+  if (!(parts & DRCT_INTERIOR)) return drct_tail(h, c.n_rdg % 2 ? nxt : cur, B, H, W, w, c.in_chans, y, s, paths, parts);
   for (int i = 0; i < c.n_rdg; ++i) {
     for (int k = 0; k < 5; ++k) {
       const SwinW& sw = h->blocks[i * 5 + k];
-      const int d = sw.d;
-      const int no = k < 4 ? c.gc : E;
+      const int d = sw.d, hdp = hdp_of(d, sw.heads);
+      const DrctBlockPath bp = drct_block_path(h, sw, k, B, H, W, paths);
       // the attention output is handed to the fused second half as bf16 (what its MFMA rounds it to anyway: half the bytes);
       // split-bf16: as fp32, both fused kernels with their lo weight packs
       const bool x3 = prec == SRAD_PREC_BF16X3;
-      const bool mlp_fused = h->fuse_mlp && srad_mlp_block_supported(prec, T, d, sw.hidden, no);
       __bf16* const attn_h = reinterpret_cast<__bf16*>(w.attn);
-      // the whole block as ONE launch (kernels_fused_block.hip) where the windows' quarters fit the chip in one wave of
-      // workgroups and the block shape measured a win over the pair below; this path has no saves and no DropPath
-      if (mlp_fused && srad_swin_block_supported(prec, c.window_size, B, H, W, d, sw.heads, sw.hidden, no) &&
-          srad_swin_block_wins(d, sw.heads, sw.hidden, no) && !srad_path_override(SRAD_PATH_BLOCK_TWO_LAUNCHES)) {
-        // ... with fc2 folded into the adjust conv (mlp_fold.h) where this forward runs the folded form and the shape has it
-        const bool folded = h->mfold_in_graph && srad_swin_block_fold_supported(prec, c.window_size, B, H, W, d, sw.heads, sw.hidden, no);
-        const QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);
-        const MlpBlockParams q = drct_mlp_block_params(h, sw, k, attn_h, cur, nxt, T);
-        SwinBlockParams b{};
-        b.x = a.x; b.ldx = a.ldx; b.B = B; b.H = H; b.W = W; b.shift = a.shift; b.d = d; b.heads = sw.heads; b.m = q.m; b.no = q.no;
-        b.ln1_g = a.ln_g; b.ln1_b = a.ln_b; b.w_qkv = a.w_qkv; b.b_qkv = a.b_qkv; b.table = a.table;
-        b.w_proj = q.w_proj; b.w_fc1 = q.w_fc1; b.w_fc2 = q.w_fc2; b.w_adj = q.w_adj;
-        b.b_proj = q.b_proj; b.b_fc1 = q.b_fc1; b.b_fc2 = q.b_fc2; b.b_adj = q.b_adj; b.ln2_g = q.ln_g; b.ln2_b = q.ln_b;
-        b.act = q.act; b.slope = q.slope; b.alpha = q.alpha; b.R = q.R; b.ldr = q.ldr; b.Y = q.Y; b.ldy = q.ldy; b.yoff = q.yoff;
-        if (folded) {
-          const char* const reg = h->pt.arena + h->mfold_off[i * 5 + k];
-          b.w_adj = reg + h->mfold[i * 5 + k].pack; b.b_adj = reinterpret_cast<const float*>(reg + h->mfold[i * 5 + k].bias);
-          SRAD_TRY(srad_launch_swin_block_folded(b, s));
+      const bool hand_h = bp.second != DRCT_H2_CHAIN && !x3;
+      switch (bp.first) {
+        case DRCT_H1_IN_BLOCK: {
+          SwinBlockParams b = drct_swin_block_params(drct_qkv_attn_params(h, sw, cur, B, H, W), drct_mlp_block_params(h, sw, k, attn_h, cur, nxt, T));
+          if (bp.second == DRCT_H2_IN_BLOCK_FOLDED) drct_fold_adjust(h, i * 5 + k, b);
+          SRAD_TRY(bp.second == DRCT_H2_IN_BLOCK_FOLDED ? srad_launch_swin_block_folded(b, s) : srad_launch_swin_block(b, s));
           continue;
         }
-        SRAD_TRY(srad_launch_swin_block(b, s));
-        continue;
-      }
-      if (h->fuse_mlp &&srad_qkv_attn_supported(prec, c.window_size, H, W, d, sw.heads)) {
-        // norm1 + qkv + shifted-window attention of one (window, head) per workgroup, one launch
-        // (drct.py:477-504, 278-299)
-        QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);
-        a.out = w.attn; a.out_h = mlp_fused && !x3 ? attn_h : nullptr;
-        a.split = x3; a.w_qkv_lo = h->pt.frag_lo_ptr(sw.qkv.w);
-        SRAD_TRY(srad_launch_qkv_attn(a, s));
-      } else {
-      // norm1 + qkv                                   (drct.py:477, 278)
-        // (64 x 64 windows, bf16: the GEMM leaves q | k | v as the bf16 operands the attention's MFMAs take)
-        float qscale = 1.f;
-        const bool qkv_bf16 = srad_window_attn_bf16_in(prec, c.window_size, sw.shift, d, sw.heads, &qscale);
-        if (qkv_bf16 && h->pt.frag_ptr(sw.qkv.w) && srad_ln_qkv_supported(prec, T, d, sw.heads) && !srad_path_override(SRAD_PATH_QKV_VIA_GEMM)) {
-          // one launch, 64 rows per workgroup against the whole weight (kernels_fused_attn.hip ln_qkv_kernel)
+        case DRCT_H1_QKV_ATTN: {
+          // norm1 + qkv + shifted-window attention of one (window, head) per workgroup, one launch (drct.py:477-504, 278-299)
+          QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);
+          a.out = w.attn; a.out_h = hand_h ? attn_h : nullptr;
+          a.split = x3; a.w_qkv_lo = h->pt.frag_lo_ptr(sw.qkv.w);
+          SRAD_TRY(srad_launch_qkv_attn(a, s));
+          break;
+        }
+        // norm1 + qkv                                   (drct.py:477, 278)
+        case DRCT_H1_LN_QKV:
+        case DRCT_H1_LN_QKV_SPLIT: {
+          // one launch, 64 rows per workgroup against the whole weight (kernels_fused_attn.hip ln_qkv_kernel); split-bf16: hi + lo
+          // planes and packs, fp32 q | k | v out (the split attention kernel scales and splits them)
+          const bool split = bp.first == DRCT_H1_LN_QKV_SPLIT;
           LnQkvParams q{};
           q.x = cur; q.ldx = D; q.M = T; q.d = d; q.heads = sw.heads; q.ln_g = h->pt.fptr(sw.n1g); q.ln_b = h->pt.fptr(sw.n1b);
-          q.w_qkv = h->pt.frag_ptr(sw.qkv.w); q.b_qkv = h->pt.fptr(sw.qkv.b);
-          q.qkv_h = reinterpret_cast<__bf16*>(w.qkv); q.hdp = hdp_of(d, sw.heads); q.qscale = qscale;
+          q.w_qkv = h->pt.frag_ptr(sw.qkv.w); q.w_qkv_lo = split ? h->pt.frag_lo_ptr(sw.qkv.w) : nullptr; q.b_qkv = h->pt.fptr(sw.qkv.b);
+          if (split) q.qkv_f = w.qkv; else q.qkv_h = reinterpret_cast<__bf16*>(w.qkv);
+          q.hdp = hdp; q.qscale = split ? 1.f : bp.qscale;
           SRAD_TRY(srad_launch_ln_qkv(q, s));
-        } else if (x3 && c.window_size == 64 && h->pt.frag_ptr(sw.qkv.w) && h->pt.frag_lo_ptr(sw.qkv.w) && srad_ln_qkv_supported(prec, T, d, sw.heads) &&
-                   !srad_path_override(SRAD_PATH_QKV_VIA_GEMM)) {
-          // split-bf16: the same launch with hi + lo planes and packs, fp32 q | k | v out (the split attention kernel scales and splits them)
-          LnQkvParams q{};
-          q.x = cur; q.ldx = D; q.M = T; q.d = d; q.heads = sw.heads; q.ln_g = h->pt.fptr(sw.n1g); q.ln_b = h->pt.fptr(sw.n1b);
-          q.w_qkv = h->pt.frag_ptr(sw.qkv.w); q.w_qkv_lo = h->pt.frag_lo_ptr(sw.qkv.w); q.b_qkv = h->pt.fptr(sw.qkv.b);
-          q.qkv_f = w.qkv; q.hdp = hdp_of(d, sw.heads); q.qscale = 1.f;
-          SRAD_TRY(srad_launch_ln_qkv(q, s));
-        } else {
-          const int hdp = hdp_of(d, sw.heads);
+          break;
+        }
+        case DRCT_H1_GEMM: {
           GemmParams p = drct_gemm(h, sw.qkv, cur, D, T, w.qkv, 3 * sw.heads * hdp);
           p.hsplit_hd = d / sw.heads; p.hsplit_hdp = hdp;      // head-padded q|k|v rows for the attention kernel
           p.ln_g = h->pt.fptr(sw.n1g); p.ln_b = h->pt.fptr(sw.n1b);
-          if (qkv_bf16) { p.Yh = reinterpret_cast<__bf16*>(w.qkv); p.hsplit_heads = sw.heads; p.hsplit_qscale = qscale; }
+          if (bp.qkv_bf16) { p.Yh = reinterpret_cast<__bf16*>(w.qkv); p.hsplit_heads = sw.heads; p.hsplit_qscale = bp.qscale; }
           SRAD_TRY(srad_launch_gemm(prec, p, s));
-        }
-        // shifted-window attention                      (drct.py:481-504, 281-299)
-        {
-          AttnParams a{w.qkv, w.attn, h->pt.fptr(sw.table), B, H, W, c.window_size, sw.shift, d, sw.heads,
-                       hdp_of(d, sw.heads)};
-          if (mlp_fused && !x3) a.out_h = attn_h;
-          if (qkv_bf16) a.qkv_h = reinterpret_cast<const __bf16*>(w.qkv);
-          SRAD_TRY(srad_launch_window_attn(prec, a, s));
+          break;
         }
       }
-      if (mlp_fused) {
-        // proj + shortcut -> norm2 -> fc1 -> GELU -> fc2 + residual -> adjust_k, one launch
-        // (drct.py:300, 509-510, 184-190, 389-396)
+      // shifted-window attention                      (drct.py:481-504, 281-299)
+      if (bp.first != DRCT_H1_QKV_ATTN) {
+        AttnParams a{w.qkv, w.attn, h->pt.fptr(sw.table), B, H, W, c.window_size, sw.shift, d, sw.heads, hdp};
+        if (hand_h) a.out_h = attn_h;
+        if (bp.qkv_bf16) a.qkv_h = reinterpret_cast<const __bf16*>(w.qkv);
+        SRAD_TRY(srad_launch_window_attn(prec, a, s));
+      }
+      if (bp.second != DRCT_H2_CHAIN) {
+        // proj + shortcut -> norm2 -> fc1 -> GELU -> fc2 + residual -> adjust_k, one launch (drct.py:300, 509-510, 184-190, 389-396)
         MlpBlockParams q = drct_mlp_block_params(h, sw, k, attn_h, cur, nxt, T);
-        // ... with fc2 folded into the adjust conv where this forward runs the folded form and the launch has it:
-        // the block's region is the one the one-launch block reads.  16-row tiles only - the form the one-launch block's
-        // second half has: a forward on 32- or 64-row tiles keeps the chain (tests/test_gpu_mlp_fold.py holds such a batch to
-        // the chain's bits; the wider folded instances exist at the op level and are measured there)
-        if (h->mfold_in_graph && srad_mlp_block_rows(T) == 16 && srad_mlp_block_fold_supported(prec, T, d, sw.hidden, no)) {
-          const char* const reg = h->pt.arena + h->mfold_off[i * 5 + k];
-          q.w_adj = reg + h->mfold[i * 5 + k].pack; q.b_adj = reinterpret_cast<const float*>(reg + h->mfold[i * 5 + k].bias);
+        if (bp.second == DRCT_H2_MLP_BLOCK_FOLDED) {
+          drct_fold_adjust(h, i * 5 + k, q);
           SRAD_TRY(srad_launch_mlp_block_folded(q, s));
           continue;
         }
@@ -159,69 +168,38 @@ int forward_body(srad_drct* h, const float* x, int B, int H, int W, float* y, co
         continue;
       }
       // proj + shortcut                               (drct.py:300, 509)
-      {
-        GemmParams p = drct_gemm(h, sw.proj, w.attn, d, T, w.x1, d);
-        p.R = cur; p.ldr = D;
-        SRAD_TRY(srad_launch_gemm(prec, p, s));
-      }
+      GemmParams p1 = drct_gemm(h, sw.proj, w.attn, d, T, w.x1, d);
+      p1.R = cur; p1.ldr = D;
+      SRAD_TRY(srad_launch_gemm(prec, p1, s));
       // norm2 + fc1 + GELU                            (drct.py:510, 185-186)
-      {
-        GemmParams p = drct_gemm(h, sw.fc1, w.x1, d, T, w.hid, sw.hidden);
-        p.ln_g = h->pt.fptr(sw.n2g); p.ln_b = h->pt.fptr(sw.n2b);
-        p.act = SRAD_ACT_GELU;
-        SRAD_TRY(srad_launch_gemm(prec, p, s));
-      }
+      GemmParams p2 = drct_gemm(h, sw.fc1, w.x1, d, T, w.hid, sw.hidden);
+      p2.ln_g = h->pt.fptr(sw.n2g); p2.ln_b = h->pt.fptr(sw.n2b); p2.act = SRAD_ACT_GELU;
+      SRAD_TRY(srad_launch_gemm(prec, p2, s));
       // fc2 + residual                                (drct.py:188, 510)
-      {
-        GemmParams p = drct_gemm(h, sw.fc2, w.hid, sw.hidden, T, w.x2, d);
-        p.R = w.x1; p.ldr = d;
-        SRAD_TRY(srad_launch_gemm(prec, p, s));
-      }
-      // adjust_k 1x1 conv (+ LeakyReLU 0.2) into the dense buffer; adjust5: *0.2 + x into the next
-      if (k < 4) {                                     // (drct.py:389-392)
-        GemmParams p = drct_gemm(h, sw.adjust, w.x2, d, T, cur, D);
-        p.yoff = d; p.act = SRAD_ACT_LRELU; p.slope = 0.2f;
-        SRAD_TRY(srad_launch_gemm(prec, p, s));
-      } else {                                         // (drct.py:393, 396)
-        GemmParams p = drct_gemm(h, sw.adjust, w.x2, d, T, nxt, D);
-        p.alpha = 0.2f; p.R = cur; p.ldr = D;
-        SRAD_TRY(srad_launch_gemm(prec, p, s));
-      }
+      GemmParams p3 = drct_gemm(h, sw.fc2, w.hid, sw.hidden, T, w.x2, d);
+      p3.R = w.x1; p3.ldr = d;
+      SRAD_TRY(srad_launch_gemm(prec, p3, s));
+      // adjust_k 1x1 conv (+ LeakyReLU 0.2) into the dense buffer (drct.py:389-392); adjust5: *0.2 + x into the next (drct.py:393, 396)
+      GemmParams p4 = drct_gemm(h, sw.adjust, w.x2, d, T, k < 4 ? cur : nxt, D);
+      if (k < 4) { p4.yoff = d; p4.act = SRAD_ACT_LRELU; p4.slope = 0.2f; }
+      else { p4.alpha = 0.2f; p4.R = cur; p4.ldr = D; }
+      SRAD_TRY(srad_launch_gemm(prec, p4, s));
     }
     float* t = cur; cur = nxt; nxt = t;
   }
-  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s, h->fold_in_graph, h->ends_in_graph, parts);
+  return drct_tail(h, cur, B, H, W, w, c.in_chans, y, s, paths, parts);
 }
 
-// Does this forward run the body end as one launch?  Inference handles only, as the fold: srad_drct_sync_params does not
-// refresh its packs.
-bool drct_ends_active(const srad_drct* h, int B, int H, int W) {
+// Which inference-only forms this forward runs.  Inference handles only: one bound for training gets its weights through
+// srad_drct_sync_params, which neither passes the folds' sources on nor refreshes the ends packs.  Overrides are read per call.
+DrctPaths drct_paths(const srad_drct* h, int B, int H, int W) {
   const srad_drct_config& c = h->cfg;
-  return h->ends_ok && !h->ts.tarena && !h->ts.ready && srad_drct_ends_supported(c.precision, c.embed_dim, c.num_feat, c.in_chans, B, H, W) &&
-         !srad_path_override(SRAD_PATH_ENDS_CHAIN);
-}
-
-// Does this forward end in the folded launch?  Inference handles only: one bound for training gets its weights through
-// srad_drct_sync_params, which does not pass the fold's sources on.
-bool drct_fold_active(const srad_drct* h, int H, int W) {
-  return h->fold_ok && !h->ts.tarena && !h->ts.ready && H >= 2 && W >= 2 && !srad_path_override(SRAD_PATH_TAIL_CHAIN);
-}
-
-// Do this forward's Swin blocks run the folded second half (where a block's launch has one: forward_body)?  Inference handles
-// only, for the same reason; bf16 and the fused blocks are settled at create (mfold_ok).
-bool drct_mfold_active(const srad_drct* h) { return h->mfold_ok && !h->ts.tarena && !h->ts.ready && !srad_path_override(SRAD_PATH_FC2_CHAIN); }
-
-// the fold's sources among the parameters: byte offset in the fold's region, or -1
-long long drct_fold_source(const srad_drct* h, const char* name) {
-  const TailFoldLayout& l = h->fold;
-  const std::string n(name);
-  if (n == "upsample.0.weight") return (long long)l.w_up0;
-  if (n == "upsample.0.bias") return (long long)l.b_up0;
-  if (n == "upsample.2.weight" && l.scale == 4) return (long long)l.w_up1;
-  if (n == "upsample.2.bias" && l.scale == 4) return (long long)l.b_up1;
-  if (n == "conv_last.weight") return (long long)l.w_last;
-  if (n == "conv_last.bias") return (long long)l.b_last;
-  return -1;
+  DrctPaths p;
+  if (h->ts.tarena || h->ts.ready) return p;
+  p.fold = h->derived.has(DRCT_TAIL_FOLD) && H >= 2 && W >= 2 && !srad_path_override(SRAD_PATH_TAIL_CHAIN);
+  p.ends = h->ends_ok && srad_drct_ends_supported(c.precision, c.embed_dim, c.num_feat, c.in_chans, B, H, W) && !srad_path_override(SRAD_PATH_ENDS_CHAIN);
+  p.mfold = h->derived.has(DRCT_BLOCK_FOLD) && !srad_path_override(SRAD_PATH_FC2_CHAIN);
+  return p;
 }
 
 }  // namespace
@@ -236,30 +214,25 @@ int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const Drc
               int parts) {
   const srad_drct_config& c = h->cfg;
   const int T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc;
-  float mean3[3];
-  drct_mean(c, mean3);
+  float mean3[3]; drct_mean(c, mean3);
   // (x - mean) * img_range, NCHW -> NHWC            (drct.py:887-888)
   if (parts & DRCT_ENTRY) SRAD_TRY(srad_launch_nchw_to_nhwc(x, w.xin, B, c.in_chans, SRAD_IMG_CPAD, H, W, mean3, c.img_range, s));
   if (!(parts & DRCT_INTERIOR)) return SRAD_OK;
   // conv_first                                       (drct.py:892)
-  {
-    GemmParams p = drct_gemm(h, h->conv_first, w.xin, SRAD_IMG_CPAD, T, w.feat0, E);
-    p.Cin = SRAD_IMG_CPAD;                 // padded image channels; the packed weight is zero there
-    geom(p, H, W);
-    SRAD_TRY(srad_launch_gemm(c.precision, p, s));
-  }
+  GemmParams p = drct_gemm(h, h->conv_first, w.xin, SRAD_IMG_CPAD, T, w.feat0, E);
+  p.Cin = SRAD_IMG_CPAD;                 // padded image channels; the packed weight is zero there
+  geom(p, H, W);
+  SRAD_TRY(srad_launch_gemm(c.precision, p, s));
   // patch_embed.norm -> residual stream in dense0[:, :E]   (drct.py:873, 650-654)
   return srad_launch_layernorm(w.feat0, E, dense0, D, T, E, h->pt.fptr(h->pe_g), h->pt.fptr(h->pe_b), 1e-5f, s);
 }
 
 int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
-              hipStream_t s, bool fold, bool ends, int parts) {
+              hipStream_t s, const DrctPaths& paths, int parts) {
   const srad_drct_config& c = h->cfg;
   const int prec = c.precision, T = B * H * W, E = c.embed_dim, D = E + 4 * c.gc, F = c.num_feat;
   const bool interior = (parts & DRCT_INTERIOR) != 0, last = (parts & DRCT_EXIT) != 0;
-  if (!interior) {
-    // the launches ahead of the last one belong to another call
-  } else if (ends) {
+  if (interior && paths.ends) {      // (not interior: the launches ahead of the last one belong to another call)
     // norm, conv_after_body + x and conv_before_upsample + LeakyReLU(0.01) as one launch into c2 (kernels_drct_ends.hip)
     DrctBodyEndParams p{};
     p.X = dense; p.ldx = D; p.ln_g = h->pt.fptr(h->norm_g); p.ln_b = h->pt.fptr(h->norm_b);
@@ -267,32 +240,29 @@ int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const
     p.w2 = h->pt.ends_ptr(h->conv_before_up.w); p.b2 = h->pt.fptr(h->conv_before_up.b);
     p.feat0 = w.feat0; p.Y = w.c2; p.B = B; p.H = H; p.W = W; p.E = E;
     SRAD_TRY(srad_launch_drct_body_end(p, s));
-  } else {
+  } else if (interior) {
     // norm                                              (drct.py:881)
     SRAD_TRY(srad_launch_layernorm(dense, D, w.body, E, T, E, h->pt.fptr(h->norm_g), h->pt.fptr(h->norm_b), 1e-5f, s));
     // conv_after_body(...) + x                          (drct.py:893)
     GemmParams p1 = drct_gemm(h, h->conv_after_body, w.body, E, T, w.c1, E);
-    geom(p1, H, W);
-    p1.R = w.feat0; p1.ldr = E;
+    geom(p1, H, W); p1.R = w.feat0; p1.ldr = E;
     SRAD_TRY(srad_launch_gemm(prec, p1, s));
     // conv_before_upsample + LeakyReLU(0.01)            (drct.py:844-845, 894)
     GemmParams p2 = drct_gemm(h, h->conv_before_up, w.c1, E, T, w.c2, F);
-    geom(p2, H, W);
-    p2.act = SRAD_ACT_LRELU; p2.slope = 0.01f;
+    geom(p2, H, W); p2.act = SRAD_ACT_LRELU; p2.slope = 0.01f;
     SRAD_TRY(srad_launch_gemm(prec, p2, s));
   }
-  float mean3[3];
-  drct_mean(c, mean3);
+  float mean3[3]; drct_mean(c, mean3);
   // Upsample, conv_last and x / img_range + mean as one 5 x 5 convolution of c2 (kernels_tail_fold.hip; drct.py:694-713, 895-897)
-  if (fold) return last ? srad_launch_tail_fold(h->fold, h->pt.arena + h->fold_off, w.c2, B, H, W, y, 1.0f / c.img_range, mean3, s) : SRAD_OK;
+  if (paths.fold)
+    return last ? srad_launch_tail_fold(h->fold, h->pt.arena + h->derived.region(DRCT_TAIL_FOLD, 0).off, w.c2, B, H, W, y, 1.0f / c.img_range, mean3, s) : SRAD_OK;
   // Upsample: conv 64->256 + PixelShuffle(2) per stage (drct.py:694-713)
   const float* src = w.c2;
   int hh = H, ww = W;
   for (size_t j = 0; j < h->up.size(); ++j) {
     if (interior) {
       GemmParams p = drct_gemm(h, h->up[j], src, F, B * hh * ww, w.upb[j], F);
-      geom(p, hh, ww);
-      p.ps = 2;
+      geom(p, hh, ww); p.ps = 2;
       SRAD_TRY(srad_launch_gemm(prec, p, s));
     }
     src = w.upb[j];
@@ -312,8 +282,7 @@ QkvAttnParams drct_qkv_attn_params(const srad_drct* h, const SwinW& sw, const fl
   QkvAttnParams a{};
   a.x = cur; a.ldx = h->cfg.embed_dim + 4 * h->cfg.gc; a.ln_g = h->pt.fptr(sw.n1g); a.ln_b = h->pt.fptr(sw.n1b);
   a.w_qkv = h->pt.frag_ptr(sw.qkv.w); a.b_qkv = h->pt.fptr(sw.qkv.b); a.table = h->pt.fptr(sw.table);
-  a.ld_out = sw.d;
-  a.B = B; a.H = H; a.W = W; a.shift = sw.shift; a.d = sw.d; a.heads = sw.heads;
+  a.ld_out = sw.d; a.B = B; a.H = H; a.W = W; a.shift = sw.shift; a.d = sw.d; a.heads = sw.heads;
   return a;
 }
 
@@ -330,6 +299,16 @@ MlpBlockParams drct_mlp_block_params(const srad_drct* h, const SwinW& sw, int k,
   if (k < 4) { q.act = SRAD_ACT_LRELU; q.slope = 0.2f; q.alpha = 1.f; q.Y = cur; q.ldy = D; q.yoff = sw.d; }
   else { q.act = SRAD_ACT_NONE; q.alpha = 0.2f; q.R = cur; q.ldr = D; q.Y = nxt; q.ldy = D; q.yoff = 0; }
   return q;
+}
+
+SwinBlockParams drct_swin_block_params(const QkvAttnParams& a, const MlpBlockParams& q) {
+  SwinBlockParams b{};
+  b.x = a.x; b.ldx = a.ldx; b.B = a.B; b.H = a.H; b.W = a.W; b.shift = a.shift; b.d = a.d; b.heads = a.heads; b.m = q.m; b.no = q.no;
+  b.ln1_g = a.ln_g; b.ln1_b = a.ln_b; b.w_qkv = a.w_qkv; b.b_qkv = a.b_qkv; b.table = a.table;
+  b.w_proj = q.w_proj; b.w_fc1 = q.w_fc1; b.w_fc2 = q.w_fc2; b.w_adj = q.w_adj;
+  b.b_proj = q.b_proj; b.b_fc1 = q.b_fc1; b.b_fc2 = q.b_fc2; b.b_adj = q.b_adj; b.ln2_g = q.ln_g; b.ln2_b = q.ln_b;
+  b.act = q.act; b.slope = q.slope; b.alpha = q.alpha; b.R = q.R; b.ldr = q.ldr; b.Y = q.Y; b.ldy = q.ldy; b.yoff = q.yoff;
+  return b;
 }
 
 extern "C" {
@@ -402,30 +381,20 @@ int srad_drct_create(const srad_drct_config* cfg, srad_drct_t** out) {
     h->pt.add_ends_pack(h->conv_after_body);
     h->pt.add_ends_pack(h->conv_before_up);
   }
-  h->fold_ok = srad_tail_fold_supported(cfg->precision, F, C, cfg->upscale);
-  if (h->fold_ok) {
+  // the composed weights behind the table's packs (drct_derived.h): the folded output end where the model has one ...
+  h->derived.end = h->pt.bytes;
+  if (srad_tail_fold_supported(cfg->precision, F, C, cfg->upscale)) {
     h->fold = tf_layout(F, C, cfg->upscale);
-    h->fold_off = srad_align_up(h->pt.bytes, 256);
+    drct_derived_add_tail(h->derived, h->fold);
   }
-  // the blocks' folded second halves: a region each behind the table's packs and the folded output end (any window size: the
-  // composition does not depend on it; the one-launch block keeps its own check in srad_swin_block_fold_supported)
-  h->mfold_ok = cfg->precision == SRAD_PREC_BF16 && h->fuse_mlp;
-  if (h->mfold_ok) {
-    size_t off = srad_align_up(h->fold_ok ? h->fold_off + h->fold.bytes : h->pt.bytes, 256);
+  // ... then the blocks' folded second halves (any window size: the one-launch block keeps its own check, srad_swin_block_fold_supported)
+  if (cfg->precision == SRAD_PREC_BF16 && h->fuse_mlp)
     for (int i = 0; i < cfg->n_rdg; ++i)
       for (int k = 0; k < 5; ++k) {
         const SwinW& sw = h->blocks[i * 5 + k];
-        const MlpFoldLayout l = mf_layout(sw.d, sw.hidden, k < 4 ? cfg->gc : E);
-        const std::string li = "layers." + std::to_string(i), sk = std::to_string(k + 1);
-        h->mfold_src[li + ".swin" + sk + ".mlp.fc2.weight"] = {i * 5 + k, l.w2};
-        h->mfold_src[li + ".swin" + sk + ".mlp.fc2.bias"] = {i * 5 + k, l.b2};
-        h->mfold_src[li + ".adjust" + sk + ".weight"] = {i * 5 + k, l.a};
-        h->mfold_src[li + ".adjust" + sk + ".bias"] = {i * 5 + k, l.ba};
-        h->mfold.push_back(l); h->mfold_off.push_back(off); h->mfold_dirty.push_back(1);
-        off += l.bytes;
+        h->mfold.push_back(mf_layout(sw.d, sw.hidden, k < 4 ? cfg->gc : E));
+        drct_derived_add_block(h->derived, i, k, h->mfold.back());
       }
-    h->mfold_end = off;
-  }
   *out = h;
   return SRAD_OK;
 }
@@ -436,25 +405,19 @@ void srad_drct_destroy(srad_drct_t* h) {
   delete h;
 }
 
-// the parameter table's packs, then the folded output end's region (sources, fold, pack, bias table) where the model has one
-// and the regions of the blocks' folded second halves
-static size_t drct_arena_need(const srad_drct_t* h) { return h->mfold_ok ? h->mfold_end : (h->fold_ok ? h->fold_off + h->fold.bytes : h->pt.bytes); }
-
 int srad_drct_arena_bytes(const srad_drct_t* h, size_t* bytes) {
   SRAD_REQUIRE(h && bytes, "drct_arena_bytes: null argument");
-  *bytes = drct_arena_need(h);
+  *bytes = h->derived.end;      // the parameter table's packs, then the regions of the composed weights
   return SRAD_OK;
 }
 
 int srad_drct_bind_arena(srad_drct_t* h, void* arena, size_t bytes) {
   SRAD_REQUIRE(h && arena, "drct_bind_arena: null argument");
-  SRAD_REQUIRE(bytes >= drct_arena_need(h), "drct_bind_arena: %zu bytes given, %zu needed", bytes, drct_arena_need(h));
+  SRAD_REQUIRE(bytes >= h->derived.end, "drct_bind_arena: %zu bytes given, %zu needed", bytes, h->derived.end);
   SRAD_REQUIRE(((uintptr_t)arena & 255) == 0, "drct_bind_arena: arena must be 256-byte aligned");
   h->pt.arena = reinterpret_cast<char*>(arena);
   h->pt.arena_bytes = bytes;
-  h->fold_stale = true;
-  h->mfold_stale = true;
-  for (char& dirty : h->mfold_dirty) dirty = 1;
+  h->derived.mark_all();
   h->gc.reset();
   return SRAD_OK;
 }
@@ -472,19 +435,9 @@ int srad_drct_set_param(srad_drct_t* h, const char* name, const float* dev_src, 
   SRAD_REQUIRE(h && name && dev_src, "drct_set_param: null argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   SRAD_TRY(h->pt.set(name, dev_src, numel, s));
-  const long long off = h->fold_ok ? drct_fold_source(h, name) : -1;
-  if (off >= 0) {      // a source of the folded output end: keep its fp32 copy, rebuild before the next forward
-    SRAD_CHECK_HIP(hipMemcpyAsync(h->pt.arena + h->fold_off + off, dev_src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
-    h->fold_stale = true;
-  }
-  if (h->mfold_ok) {   // likewise a source of a block's folded second half
-    const auto it = h->mfold_src.find(name);
-    if (it != h->mfold_src.end()) {
-      const int blk = it->second.first;
-      SRAD_CHECK_HIP(hipMemcpyAsync(h->pt.arena + h->mfold_off[blk] + it->second.second, dev_src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
-      h->mfold_dirty[blk] = 1;
-      h->mfold_stale = true;
-    }
+  if (const DrctDerivedSource* src = h->derived.find(name)) {      // a source of a composed weight: keep its fp32 copy, rebuild before the next forward
+    SRAD_CHECK_HIP(hipMemcpyAsync(h->pt.arena + h->derived.regions[src->region].off + src->off, dev_src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
+    h->derived.mark(src->region);
   }
   return SRAD_OK;
 }
@@ -513,42 +466,28 @@ int srad_drct_forward(srad_drct_t* h, const float* x, int B, int H, int W, float
   const DrctWs w = plan_ws(h, B, H, W, workspace, workspace_bytes);
   SRAD_REQUIRE(w.bytes <= workspace_bytes, "drct_forward: workspace %zu bytes, %zu needed", workspace_bytes, w.bytes);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // the folded output end: decided per call (a recorded graph holds one of the two ends), rebuilt here - on the stream, ahead
-  // of the forward, never inside a capture and never as a node of the replayed graph - when one of its sources has changed
-  const bool fold = drct_fold_active(h, H, W);
-  if (fold != h->fold_in_graph) { h->gc.reset(); h->fold_in_graph = fold; }
-  const bool ends = drct_ends_active(h, B, H, W);                  // likewise per call: the rule depends on the shape
-  if (ends != h->ends_in_graph) { h->gc.reset(); h->ends_in_graph = ends; }
-  if (fold && h->fold_stale) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (s) SRAD_CHECK_HIP(hipStreamIsCapturing(s, &st));
-    if (st != hipStreamCaptureStatusNone)
-      return srad_set_error(SRAD_ERR_STATE, "drct_forward: the folded output end is stale and the stream is capturing: run one forward outside the capture first");
-    SRAD_TRY(srad_launch_tail_fold_build(h->fold, h->pt.arena + h->fold_off, s));
-    h->fold_stale = false;
-  }
-  const bool mfold = drct_mfold_active(h);                         // likewise: a recorded graph holds one of the two second halves
-  if (mfold != h->mfold_in_graph) { h->gc.reset(); h->mfold_in_graph = mfold; }
-  if (mfold && h->mfold_stale) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (s) SRAD_CHECK_HIP(hipStreamIsCapturing(s, &st));
-    if (st != hipStreamCaptureStatusNone)
-      return srad_set_error(SRAD_ERR_STATE, "drct_forward: a folded block weight is stale and the stream is capturing: run one forward outside the capture first");
-    for (size_t blk = 0; blk < h->mfold.size(); ++blk)
-      if (h->mfold_dirty[blk]) {
-        SRAD_TRY(srad_launch_mlp_fold_build(h->mfold[blk], h->pt.arena + h->mfold_off[blk], s));
-        h->mfold_dirty[blk] = 0;
-      }
-    h->mfold_stale = false;
-  }
-  // Graph replay: only the interior is recorded, keyed on the workspace and the shape; the entry and the exit launch on the
-  // stream either side of it, so a new x or y neither recaptures nor costs a copy.  (The legacy default stream cannot be
-  // captured: there, and with the graph off, the forward is one eager sequence.)
-  if (!h->cfg.use_graph || s == nullptr) return forward_body(h, x, B, H, W, y, w, s);
-  SRAD_TRY(forward_body(h, x, B, H, W, y, w, s, DRCT_ENTRY));
+  // the forms this call runs: decided per call; a recorded graph holds one form of each
+  const DrctPaths paths = drct_paths(h, B, H, W);
+  if (paths != h->graph_paths) { h->gc.reset(); h->graph_paths = paths; }
+  // their stale folds are rebuilt here - on the stream, ahead of the forward, never inside a capture or as a node of the graph
+  const unsigned kinds = (paths.fold ? 1u << DRCT_TAIL_FOLD : 0) | (paths.mfold ? 1u << DRCT_BLOCK_FOLD : 0);
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (s && h->derived.stale(kinds)) SRAD_CHECK_HIP(hipStreamIsCapturing(s, &st));
+  const int built = h->derived.refresh(kinds, st != hipStreamCaptureStatusNone, [&](const DrctDerivedRegion& r) {
+    return r.kind == DRCT_TAIL_FOLD ? srad_launch_tail_fold_build(h->fold, h->pt.arena + r.off, s)
+                                    : srad_launch_mlp_fold_build(h->mfold[r.index], h->pt.arena + r.off, s);
+  });
+  if (built == DRCT_DERIVED_CAPTURING)
+    return srad_set_error(SRAD_ERR_STATE, "drct_forward: %s is stale and the stream is capturing: run one forward outside the capture first",
+                          h->derived.stale(paths.fold ? 1u << DRCT_TAIL_FOLD : 0) ? "the folded output end" : "a folded block weight");
+  SRAD_TRY(built);
+  // Graph replay: only the interior is recorded, keyed on the workspace and the shape; the entry and the exit launch on the stream
+  // either side of it.  (The legacy default stream cannot be captured: there, and with the graph off, it is one eager sequence.)
+  if (!h->cfg.use_graph || s == nullptr) return forward_body(h, x, B, H, W, y, w, s, paths);
+  SRAD_TRY(forward_body(h, x, B, H, W, y, w, s, paths, DRCT_ENTRY));
   SRAD_TRY(srad_run_with_graph(h->gc, true, workspace, B, H, W, s,
-                               [&](hipStream_t st) { return forward_body(h, nullptr, B, H, W, nullptr, w, st, DRCT_INTERIOR); }));
-  return forward_body(h, x, B, H, W, y, w, s, DRCT_EXIT);
+                               [&](hipStream_t cs) { return forward_body(h, nullptr, B, H, W, nullptr, w, cs, paths, DRCT_INTERIOR); }));
+  return forward_body(h, x, B, H, W, y, w, s, paths, DRCT_EXIT);
 }
 
 int srad_drct_graph_captures(const srad_drct_t* h) { return h ? h->gc.captures : 0; }

@@ -2,12 +2,9 @@
 // (drct_train.hip), and the pieces of the forward both run: stem, tail, fused-block parameters (defined in drct.hip).
 #pragma once
 #include "train_common.h"
-#include "tail_fold.h"
-#include "mlp_fold.h"
+#include "drct_derived.h"
 #include "../../include/srad.h"
 #include <string>
-#include <unordered_map>
-#include <utility>
 
 struct SwinW {
   int d, heads, hidden, shift;
@@ -16,6 +13,14 @@ struct SwinW {
 };
 
 static inline int hdp_of(int d, int heads) { return srad_round_up(d / heads, 4); }
+
+// Which of the inference-only forms one forward runs: fold = all after conv_before_upsample as the one folded launch, ends = norm,
+// conv_after_body and conv_before_upsample as the one body-end launch, mfold = fc2 folded into the adjust conv in the blocks whose
+// launch has that form.  Decided per call (drct_paths) and passed as an argument, never read back out of the handle.
+struct DrctPaths {
+  bool fold = false, ends = false, mfold = false;
+  bool operator!=(const DrctPaths& o) const { return fold != o.fold || ends != o.ends || mfold != o.mfold; }
+};
 
 struct srad_drct {
   srad_drct_config cfg;
@@ -27,25 +32,15 @@ struct srad_drct {
   int dmax, hmax, qkvmax;         // widest block dim / hidden / head-padded qkv row
   std::vector<char> saved_h;      // per Swin block, what the last training forward saved as bf16: 1 q | k | v, 2 the fc1 pre-activation (plan_block)
   bool fuse_mlp = true;           // bf16: second half of each Swin block as one launch (kernels_fused.hip)
-  // The folded output end (kernels_tail_fold.hip): its region follows the parameter table's in the weight arena and is no
-  // entry of the table.  srad_drct_set_param copies the fp32 sources in and marks the fold stale; srad_drct_forward rebuilds a
-  // stale fold before it runs or replays anything.  A handle bound for training keeps the chain of launches.
-  bool fold_ok = false, fold_stale = true, fold_in_graph = false;
+  // The composed weights (drct_derived.h): the folded output end (kernels_tail_fold.hip) and the Swin blocks' folded second halves
+  // (mlp_fold.h), where the model has them.  srad_drct_set_param copies a changed fp32 source in and marks its region;
+  // srad_drct_forward rebuilds the stale regions of the forms the call runs before it runs or replays anything.
+  DrctDerived derived;
   TailFoldLayout fold{};
-  size_t fold_off = 0;
-  // The body-end launch (kernels_drct_ends.hip): ends_ok = the model's shape has it (its packs are entries' ends packs in the
-  // table); which forwards take it is decided per call, and a recorded graph holds one of the two forms.
-  bool ends_ok = false, ends_in_graph = false;
-  // The folded second halves of the Swin blocks (mlp_fold.h): one region per block behind the folded output
-  // end's, same rules - set_param copies a block's four fp32 sources in and marks it stale, srad_drct_forward rebuilds stale
-  // blocks before it runs or replays anything, a handle bound for training keeps the chain.  The handle keeps both packs.
-  bool mfold_ok = false, mfold_stale = true, mfold_in_graph = false;
-  std::vector<MlpFoldLayout> mfold;           // per block
-  std::vector<size_t> mfold_off;              // per block: byte offset of its region in the arena
-  std::vector<char> mfold_dirty;              // per block: a source changed since its last build
-  std::unordered_map<std::string, std::pair<int, size_t>> mfold_src;   // parameter name -> (block, byte offset in its region)
-  size_t mfold_end = 0;                       // end of the last region
+  std::vector<MlpFoldLayout> mfold;           // per block: where in its region the launches find the pack and the bias
+  bool ends_ok = false;           // the model's shape has the body-end launch (kernels_drct_ends.hip; its packs are table entries' ends packs)
   GraphCache gc;
+  DrctPaths graph_paths;          // what gc's graph was recorded with: a recorded graph holds one form of each
   TrainState ts;                  // training (drct_train.hip)
   BwdStreams bwd;                 // the backward's side stream for the weight gradients, and its events
 };
@@ -75,12 +70,11 @@ enum : int { DRCT_ENTRY = 1, DRCT_INTERIOR = 2, DRCT_EXIT = 4, DRCT_ALL = 7 };
 int drct_stem(const srad_drct* h, const float* x, int B, int H, int W, const DrctStemTail& w, float* dense0, hipStream_t s,
               int parts = DRCT_ALL);
 // norm -> conv_after_body + x -> conv_before_upsample -> Upsample -> conv_last (into outn, row stride ld_outn) -> y   (drct.py:881, 893-897)
-// fold: everything after conv_before_upsample as the one folded launch (the caller has checked drct_fold_active and freshness)
-// ends: norm, conv_after_body and conv_before_upsample as the one body-end launch (the caller has checked drct_ends_active)
-// parts: DRCT_EXIT the last launch (the folded launch, or the chain's layout launch into y), DRCT_INTERIOR all before it
+// paths: fold and ends as decided for this call (the fold is fresh); parts: DRCT_EXIT the last launch, DRCT_INTERIOR all before it
 int drct_tail(const srad_drct* h, const float* dense, int B, int H, int W, const DrctStemTail& w, int ld_outn, float* y,
-              hipStream_t s, bool fold = false, bool ends = false, int parts = DRCT_ALL);
+              hipStream_t s, const DrctPaths& paths = DrctPaths(), int parts = DRCT_ALL);
 // The fields both forwards set for Swin block `sw` of an RDG, block k of its five: weights, biases, LayerNorm, geometry, and
-// (mlp_block) the adjust conv's residual and output in the dense buffers cur / nxt
+// (mlp_block) the adjust conv's residual and output in the dense buffers cur / nxt; the one-launch block takes the two together
 QkvAttnParams drct_qkv_attn_params(const srad_drct* h, const SwinW& sw, const float* cur, int B, int H, int W);
 MlpBlockParams drct_mlp_block_params(const srad_drct* h, const SwinW& sw, int k, const __bf16* attn_h, float* cur, float* nxt, int T);
+SwinBlockParams drct_swin_block_params(const QkvAttnParams& a, const MlpBlockParams& q);

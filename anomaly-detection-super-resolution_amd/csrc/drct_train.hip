@@ -246,8 +246,8 @@ int srad_drct_forward_train(srad_drct_t* h, const float* x, int B, int H, int W,
       const int no = k < 4 ? c.gc : E;
       if (h->saved_h.size() != h->blocks.size()) h->saved_h.assign(h->blocks.size(), 0);
       h->saved_h[bi] = 0;
-      if (h->fuse_mlp && srad_qkv_attn_supported(prec, c.window_size, H, W, d, sw.heads) &&
-          srad_mlp_block_supported(prec, T, d, sw.hidden, no)) {
+      const BlockPlan bp = plan_block(h, sw, H, W, T, no);
+      if (bp.xh) {
         // bf16: the two fused launches of the inference path, which also leave what the backward needs
         // (LN1(x), q|k|v, x + attn, LN2(.), fc1 pre-activation, GELU(.), block output) and apply DropPath
         QkvAttnParams a = drct_qkv_attn_params(h, sw, cur, B, H, W);
@@ -255,7 +255,6 @@ int srad_drct_forward_train(srad_drct_t* h, const float* x, int B, int H, int W,
         // the tensors only the weight gradients read (LN1(x), LN2(.), GELU(.), the block output) are left as bf16, which is
         // what the MFMA would round them to anyway: half the bytes written here and read (3 - 9 times each) by wgrad
         a.save_xn_h = reinterpret_cast<__bf16*>(sv.xn1); a.hdp = hdp;
-        const BlockPlan bp = plan_block(h, sw, H, W, T, no);
         h->saved_h[bi] = (char)((bp.attn_h ? 1 : 0) | (bp.yh_dh ? 2 : 0));
         if (bp.attn_h) { a.save_qkv_h = reinterpret_cast<__bf16*>(sv.qkv); a.hp_h = attn_hp(sw); }   // as the MFMA took them
         else a.save_qkv = sv.qkv;

@@ -314,28 +314,49 @@ int srad_bench_qkv_attn(const float* x, int ldx, int B, int H, int W, int shift,
 // Second half of a Swin block + the RDG's adjust conv (src/drct.py:300, 509-510, 184-190, 389-396):
 //   x1 = shortcut + proj(attn); x2 = x1 + fc2(GELU(fc1(LN2(x1)))); Y[:, yoff:yoff+no] = act(adjust(x2)) * alpha (+ R)
 //   fm: token rows per workgroup (16 / 32 / 64; 0 = the engine's choice for M)
-int srad_op_mlp_block(int precision, int M, int d, int m, int no, int fm, const void* attn /* bf16 [M][d]; split-bf16: fp32 */, const float* shortcut, int ld_short,
-                      const float* w_proj, const float* b_proj, const float* ln_g, const float* ln_b, const float* w_fc1,
-                      const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
-                      float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
-                      size_t scratch_bytes, void* stream) {
+// folded: the same second half with fc2 folded into the adjust conv (mlp_fold.h; bf16): the two packs the kernel still reads, then
+// [A | A W2] and A b2 + b_a composed behind the pair's layout in scratch (from off[5], where the lo packs would start)
+static int op_mlp_block(bool folded, int precision, int M, int d, int m, int no, int fm, const void* attn, const float* shortcut, int ld_short,
+                        const float* w_proj, const float* b_proj, const float* ln_g, const float* ln_b, const float* w_fc1,
+                        const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
+                        float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch, size_t scratch_bytes, void* stream) {
+  const char* const who = folded ? "op_mlp_block_folded" : "op_mlp_block";
   SRAD_REQUIRE(attn && shortcut && w_proj && b_proj && ln_g && ln_b && w_fc1 && b_fc1 && w_fc2 && b_fc2 && w_adj && b_adj && y && scratch,
-               "op_mlp_block: null argument");
-  SRAD_REQUIRE(precision == SRAD_PREC_BF16 || precision == SRAD_PREC_BF16X3, "op_mlp_block: precision must be bf16 or split-bf16 (fp32 runs the unfused kernels)");
-  SRAD_REQUIRE(srad_mlp_block_supported(precision, M, d, m, no), "op_mlp_block: unsupported shape M=%d d=%d m=%d no=%d", M, d, m, no);
-  SRAD_REQUIRE(fm == 0 || ((fm == 16 || fm == 32 || fm == 64) && M % fm == 0), "op_mlp_block: fm must be 0, 16, 32 or 64 and divide M");
+               "%s: null argument", who);
+  const bool fm_ok = fm == 0 || ((fm == 16 || fm == 32 || fm == 64) && M % fm == 0);
+  if (folded) {
+    SRAD_REQUIRE(fm_ok, "op_mlp_block_folded: fm must be 0, 16, 32 or 64 and divide M");
+    SRAD_REQUIRE(precision == SRAD_PREC_BF16 && srad_mlp_block_fold_has(M, fm, d, m, no),
+                 "op_mlp_block_folded: unsupported: precision %d, M=%d fm=%d d=%d m=%d no=%d (bf16, no <= 32 or > 128, a tile height whose folded tile fits the LDS)",
+                 precision, M, fm, d, m, no);
+  } else {
+    SRAD_REQUIRE(precision == SRAD_PREC_BF16 || precision == SRAD_PREC_BF16X3, "op_mlp_block: precision must be bf16 or split-bf16 (fp32 runs the unfused kernels)");
+    SRAD_REQUIRE(srad_mlp_block_supported(precision, M, d, m, no), "op_mlp_block: unsupported shape M=%d d=%d m=%d no=%d", M, d, m, no);
+    SRAD_REQUIRE(fm_ok, "op_mlp_block: fm must be 0, 16, 32 or 64 and divide M");
+  }
   size_t off[10];
-  const size_t need = swin_scratch_parts(d, 1, m, no, off);
-  SRAD_REQUIRE(scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0, "op_mlp_block: scratch %zu bytes, %zu needed (256-byte aligned)", scratch_bytes, need);
+  const size_t packs = swin_scratch_parts(d, 1, m, no, off);
+  const MlpFoldLayout l = folded ? mf_layout(d, m, no) : MlpFoldLayout{};
+  const size_t need = folded ? off[5] + l.bytes : packs;
+  SRAD_REQUIRE(scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0, "%s: scratch %zu bytes, %zu needed (256-byte aligned)", who, scratch_bytes, need);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   char* sc = reinterpret_cast<char*>(scratch);
   SRAD_TRY(srad_launch_pack_weight_frag(w_proj, sc + off[1], d, d, s));
   SRAD_TRY(srad_launch_pack_weight_frag(w_fc1, sc + off[2], m, d, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_fc2, sc + off[3], d, m, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_adj, sc + off[4], no, d, s));
   MlpBlockParams q{};
   q.attn_h = reinterpret_cast<const __bf16*>(attn); q.ld_attn = d; q.shortcut = shortcut; q.ld_short = ld_short; q.M = M; q.d = d; q.m = m; q.no = no;
-  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = sc + off[3]; q.w_adj = sc + off[4];
+  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2];
+  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.ln_g = ln_g; q.ln_b = ln_b;
+  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff; q.fm = fm;
+  if (folded) {
+    char* const fold = sc + off[5];
+    SRAD_TRY(srad_mlp_fold_from_sources(l, fold, w_fc2, b_fc2, w_adj, b_adj, s));
+    q.w_fc2 = fold + l.pack; q.w_adj = fold + l.pack; q.b_adj = reinterpret_cast<const float*>(fold + l.bias);
+    return srad_launch_mlp_block_folded(q, s);
+  }
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fc2, sc + off[3], d, m, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_adj, sc + off[4], no, d, s));
+  q.w_fc2 = sc + off[3]; q.w_adj = sc + off[4]; q.b_adj = b_adj;
   if (precision == SRAD_PREC_BF16X3) {
     SRAD_TRY(srad_launch_pack_weight_frag_lo(w_proj, sc + off[6], d, d, s));
     SRAD_TRY(srad_launch_pack_weight_frag_lo(w_fc1, sc + off[7], m, d, s));
@@ -344,107 +365,84 @@ int srad_op_mlp_block(int precision, int M, int d, int m, int no, int fm, const 
     q.split = 1; q.attn_f = reinterpret_cast<const float*>(attn);
     q.w_proj_lo = sc + off[6]; q.w_fc1_lo = sc + off[7]; q.w_fc2_lo = sc + off[8]; q.w_adj_lo = sc + off[9];
   }
-  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.b_adj = b_adj; q.ln_g = ln_g; q.ln_b = ln_b;
-  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff; q.fm = fm;
   return srad_launch_mlp_block(q, s);
 }
-
-// The same second half with fc2 folded into the adjust conv (mlp_fold.h; bf16): the two packs the kernel still reads, then
-// [A | A W2] and A b2 + b_a composed behind the pair's layout in scratch
+int srad_op_mlp_block(int precision, int M, int d, int m, int no, int fm, const void* attn /* bf16 [M][d]; split-bf16: fp32 */, const float* shortcut, int ld_short,
+                      const float* w_proj, const float* b_proj, const float* ln_g, const float* ln_b, const float* w_fc1,
+                      const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
+                      float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch, size_t scratch_bytes, void* stream) {
+  return op_mlp_block(false, precision, M, d, m, no, fm, attn, shortcut, ld_short, w_proj, b_proj, ln_g, ln_b, w_fc1, b_fc1, w_fc2, b_fc2, w_adj, b_adj,
+                      act, slope, alpha, r, ldr, y, ldy, yoff, scratch, scratch_bytes, stream);
+}
 int srad_op_mlp_block_folded(int precision, int M, int d, int m, int no, int fm, const void* attn /* bf16 [M][d] */, const float* shortcut, int ld_short,
                              const float* w_proj, const float* b_proj, const float* ln_g, const float* ln_b, const float* w_fc1,
                              const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
-                             float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
-                             size_t scratch_bytes, void* stream) {
-  SRAD_REQUIRE(attn && shortcut && w_proj && b_proj && ln_g && ln_b && w_fc1 && b_fc1 && w_fc2 && b_fc2 && w_adj && b_adj && y && scratch,
-               "op_mlp_block_folded: null argument");
-  SRAD_REQUIRE(fm == 0 || ((fm == 16 || fm == 32 || fm == 64) && M % fm == 0), "op_mlp_block_folded: fm must be 0, 16, 32 or 64 and divide M");
-  SRAD_REQUIRE(precision == SRAD_PREC_BF16 && srad_mlp_block_fold_has(M, fm, d, m, no),
-               "op_mlp_block_folded: unsupported: precision %d, M=%d fm=%d d=%d m=%d no=%d (bf16, no <= 32 or > 128, a tile height whose folded tile fits the LDS)",
-               precision, M, fm, d, m, no);
-  size_t off[10];
-  swin_scratch_parts(d, 1, m, no, off);
-  const MlpFoldLayout l = mf_layout(d, m, no);
-  SRAD_REQUIRE(scratch_bytes >= off[5] + l.bytes && ((uintptr_t)scratch & 255) == 0,
-               "op_mlp_block_folded: scratch %zu bytes, %zu needed (256-byte aligned)", scratch_bytes, off[5] + l.bytes);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* sc = reinterpret_cast<char*>(scratch);
-  SRAD_TRY(srad_launch_pack_weight_frag(w_proj, sc + off[1], d, d, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_fc1, sc + off[2], m, d, s));
-  char* const fold = sc + off[5];
-  SRAD_TRY(srad_mlp_fold_from_sources(l, fold, w_fc2, b_fc2, w_adj, b_adj, s));
-  MlpBlockParams q{};
-  q.attn_h = reinterpret_cast<const __bf16*>(attn); q.ld_attn = d; q.shortcut = shortcut; q.ld_short = ld_short; q.M = M; q.d = d; q.m = m; q.no = no;
-  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = fold + l.pack; q.w_adj = fold + l.pack;
-  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.b_adj = reinterpret_cast<const float*>(fold + l.bias); q.ln_g = ln_g; q.ln_b = ln_b;
-  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff; q.fm = fm;
-  return srad_launch_mlp_block_folded(q, s);
+                             float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch, size_t scratch_bytes, void* stream) {
+  return op_mlp_block(true, precision, M, d, m, no, fm, attn, shortcut, ld_short, w_proj, b_proj, ln_g, ln_b, w_fc1, b_fc1, w_fc2, b_fc2, w_adj, b_adj,
+                      act, slope, alpha, r, ldr, y, ldy, yoff, scratch, scratch_bytes, stream);
 }
 
 // A whole Swin block + the adjust conv in one launch (kernels_fused_block.hip): the two ops above back to back, x being the shortcut.
+// folded: the same block with the folded second half (mlp_fold.h): the three packs the kernel still reads, then [A | A W2] and
+// A b2 + b_a composed behind the hi packs' layout in scratch
+static int op_swin_block(bool folded, int precision, const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, int m, int no,
+                         const float* ln1_g, const float* ln1_b, const float* w_qkv, const float* b_qkv, const float* table,
+                         const float* w_proj, const float* b_proj, const float* ln2_g, const float* ln2_b, const float* w_fc1,
+                         const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
+                         float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch, size_t scratch_bytes, void* stream) {
+  const char* const who = folded ? "op_swin_block_folded" : "op_swin_block";
+  SRAD_REQUIRE(x && ln1_g && ln1_b && w_qkv && b_qkv && table && w_proj && b_proj && ln2_g && ln2_b && w_fc1 && b_fc1 && w_fc2 && b_fc2 && w_adj &&
+                   b_adj && y && scratch, "%s: null argument", who);
+  if (folded)
+    SRAD_REQUIRE(srad_swin_block_fold_supported(precision, 8, B, H, W, d, heads, m, no),
+                 "op_swin_block_folded: unsupported: precision %d, %dx%dx%d, d=%d heads=%d m=%d no=%d (bf16, 8 x 8 windows, windows x 4 <= CUs, no <= 32 or > 128)",
+                 precision, B, H, W, d, heads, m, no);
+  else
+    SRAD_REQUIRE(srad_swin_block_supported(precision, 8, B, H, W, d, heads, m, no),
+                 "op_swin_block: unsupported: precision %d, %dx%dx%d, d=%d heads=%d m=%d no=%d (bf16, 8 x 8 windows, windows x 4 <= CUs)", precision, B, H, W,
+                 d, heads, m, no);
+  size_t off[10];
+  swin_scratch_parts(d, heads, m, no, off);                        // off[5]: where the lo packs would start = the size of the hi packs
+  const MlpFoldLayout l = folded ? mf_layout(d, m, no) : MlpFoldLayout{};
+  const size_t need = off[5] + (folded ? l.bytes : 0);
+  SRAD_REQUIRE(scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0, "%s: scratch %zu bytes, %zu needed (256-byte aligned)", who, scratch_bytes, need);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* sc = reinterpret_cast<char*>(scratch);
+  SRAD_TRY(srad_launch_pack_qkv_frag(w_qkv, sc + off[0], d, heads, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_proj, sc + off[1], d, d, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fc1, sc + off[2], m, d, s));
+  SwinBlockParams q{};
+  q.x = x; q.ldx = ldx; q.B = B; q.H = H; q.W = W; q.shift = shift; q.d = d; q.heads = heads; q.m = m; q.no = no;
+  q.ln1_g = ln1_g; q.ln1_b = ln1_b; q.w_qkv = sc + off[0]; q.b_qkv = b_qkv; q.table = table;
+  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2];
+  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.ln2_g = ln2_g; q.ln2_b = ln2_b;
+  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff;
+  if (folded) {
+    char* const fold = sc + off[5];
+    SRAD_TRY(srad_mlp_fold_from_sources(l, fold, w_fc2, b_fc2, w_adj, b_adj, s));
+    q.w_fc2 = fold + l.pack; q.w_adj = fold + l.pack; q.b_adj = reinterpret_cast<const float*>(fold + l.bias);
+    return srad_launch_swin_block_folded(q, s);
+  }
+  SRAD_TRY(srad_launch_pack_weight_frag(w_fc2, sc + off[3], d, m, s));
+  SRAD_TRY(srad_launch_pack_weight_frag(w_adj, sc + off[4], no, d, s));
+  q.w_fc2 = sc + off[3]; q.w_adj = sc + off[4]; q.b_adj = b_adj;
+  return srad_launch_swin_block(q, s);
+}
 int srad_op_swin_block(int precision, const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, int m, int no,
                        const float* ln1_g, const float* ln1_b, const float* w_qkv, const float* b_qkv, const float* table,
                        const float* w_proj, const float* b_proj, const float* ln2_g, const float* ln2_b, const float* w_fc1,
                        const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj, int act,
-                       float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
-                       size_t scratch_bytes, void* stream) {
-  SRAD_REQUIRE(x && ln1_g && ln1_b && w_qkv && b_qkv && table && w_proj && b_proj && ln2_g && ln2_b && w_fc1 && b_fc1 && w_fc2 && b_fc2 && w_adj &&
-                   b_adj && y && scratch, "op_swin_block: null argument");
-  SRAD_REQUIRE(srad_swin_block_supported(precision, 8, B, H, W, d, heads, m, no),
-               "op_swin_block: unsupported: precision %d, %dx%dx%d, d=%d heads=%d m=%d no=%d (bf16, 8 x 8 windows, windows x 4 <= CUs)", precision, B, H, W,
-               d, heads, m, no);
-  size_t off[10];
-  swin_scratch_parts(d, heads, m, no, off);                        // off[5]: where the lo packs would start = the size of the hi packs
-  SRAD_REQUIRE(scratch_bytes >= off[5] && ((uintptr_t)scratch & 255) == 0,
-               "op_swin_block: scratch %zu bytes, %zu needed (256-byte aligned)", scratch_bytes, off[5]);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* sc = reinterpret_cast<char*>(scratch);
-  SRAD_TRY(srad_launch_pack_qkv_frag(w_qkv, sc + off[0], d, heads, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_proj, sc + off[1], d, d, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_fc1, sc + off[2], m, d, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_fc2, sc + off[3], d, m, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_adj, sc + off[4], no, d, s));
-  SwinBlockParams q{};
-  q.x = x; q.ldx = ldx; q.B = B; q.H = H; q.W = W; q.shift = shift; q.d = d; q.heads = heads; q.m = m; q.no = no;
-  q.ln1_g = ln1_g; q.ln1_b = ln1_b; q.w_qkv = sc + off[0]; q.b_qkv = b_qkv; q.table = table;
-  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = sc + off[3]; q.w_adj = sc + off[4];
-  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.b_adj = b_adj; q.ln2_g = ln2_g; q.ln2_b = ln2_b;
-  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff;
-  return srad_launch_swin_block(q, s);
+                       float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch, size_t scratch_bytes, void* stream) {
+  return op_swin_block(false, precision, x, ldx, B, H, W, shift, d, heads, m, no, ln1_g, ln1_b, w_qkv, b_qkv, table, w_proj, b_proj, ln2_g, ln2_b,
+                       w_fc1, b_fc1, w_fc2, b_fc2, w_adj, b_adj, act, slope, alpha, r, ldr, y, ldy, yoff, scratch, scratch_bytes, stream);
 }
-
-// The same block with the folded second half (mlp_fold.h): the four packs the kernel still reads, then [A | A W2] and
-// A b2 + b_a composed behind them in scratch
 int srad_op_swin_block_folded(int precision, const float* x, int ldx, int B, int H, int W, int shift, int d, int heads, int m, int no,
                               const float* ln1_g, const float* ln1_b, const float* w_qkv, const float* b_qkv, const float* table,
                               const float* w_proj, const float* b_proj, const float* ln2_g, const float* ln2_b, const float* w_fc1,
                               const float* b_fc1, const float* w_fc2, const float* b_fc2, const float* w_adj, const float* b_adj,
-                              int act, float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch,
-                              size_t scratch_bytes, void* stream) {
-  SRAD_REQUIRE(x && ln1_g && ln1_b && w_qkv && b_qkv && table && w_proj && b_proj && ln2_g && ln2_b && w_fc1 && b_fc1 && w_fc2 && b_fc2 && w_adj &&
-                   b_adj && y && scratch, "op_swin_block_folded: null argument");
-  SRAD_REQUIRE(srad_swin_block_fold_supported(precision, 8, B, H, W, d, heads, m, no),
-               "op_swin_block_folded: unsupported: precision %d, %dx%dx%d, d=%d heads=%d m=%d no=%d (bf16, 8 x 8 windows, windows x 4 <= CUs, no <= 32 or > 128)",
-               precision, B, H, W, d, heads, m, no);
-  size_t off[10];
-  swin_scratch_parts(d, heads, m, no, off);
-  const MlpFoldLayout l = mf_layout(d, m, no);
-  SRAD_REQUIRE(scratch_bytes >= off[5] + l.bytes && ((uintptr_t)scratch & 255) == 0,
-               "op_swin_block_folded: scratch %zu bytes, %zu needed (256-byte aligned)", scratch_bytes, off[5] + l.bytes);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* sc = reinterpret_cast<char*>(scratch);
-  SRAD_TRY(srad_launch_pack_qkv_frag(w_qkv, sc + off[0], d, heads, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_proj, sc + off[1], d, d, s));
-  SRAD_TRY(srad_launch_pack_weight_frag(w_fc1, sc + off[2], m, d, s));
-  char* const fold = sc + off[5];
-  SRAD_TRY(srad_mlp_fold_from_sources(l, fold, w_fc2, b_fc2, w_adj, b_adj, s));
-  SwinBlockParams q{};
-  q.x = x; q.ldx = ldx; q.B = B; q.H = H; q.W = W; q.shift = shift; q.d = d; q.heads = heads; q.m = m; q.no = no;
-  q.ln1_g = ln1_g; q.ln1_b = ln1_b; q.w_qkv = sc + off[0]; q.b_qkv = b_qkv; q.table = table;
-  q.w_proj = sc + off[1]; q.w_fc1 = sc + off[2]; q.w_fc2 = fold + l.pack; q.w_adj = fold + l.pack;
-  q.b_proj = b_proj; q.b_fc1 = b_fc1; q.b_fc2 = b_fc2; q.b_adj = reinterpret_cast<const float*>(fold + l.bias); q.ln2_g = ln2_g; q.ln2_b = ln2_b;
-  q.act = act; q.slope = slope; q.alpha = alpha; q.R = r; q.ldr = ldr; q.Y = y; q.ldy = ldy; q.yoff = yoff;
-  return srad_launch_swin_block_folded(q, s);
+                              int act, float slope, float alpha, const float* r, int ldr, float* y, int ldy, int yoff, void* scratch, size_t scratch_bytes, void* stream) {
+  return op_swin_block(true, precision, x, ldx, B, H, W, shift, d, heads, m, no, ln1_g, ln1_b, w_qkv, b_qkv, table, w_proj, b_proj, ln2_g, ln2_b,
+                       w_fc1, b_fc1, w_fc2, b_fc2, w_adj, b_adj, act, slope, alpha, r, ldr, y, ldy, yoff, scratch, scratch_bytes, stream);
 }
 
 // Diagnostic twin of srad_bench_qkv_attn + srad_bench_mlp_block for the one-launch block: microseconds per launch, back-to-back
