@@ -558,6 +558,29 @@ def test_bf16_fused_mlp_backward_matches_unfused(sr_golden, batch):
     assert cos > 0.9999 and worst < 2e-2
 
 
+def test_backward_refuses_saves_made_for_other_backward_kernels():
+    """bf16 at 8192 tokens: the plain forward leaves q | k | v and the fc1 pre-activation as bf16, for the all-bf16 backward
+    kernels.  A backward under the unfused_blocks override would take the separate launches, which read them as fp32: it is
+    refused before it touches the block.  The next plain step, on a fresh model, succeeds."""
+    from srad_amd import ops
+    from srad_amd import spec as S
+    cfg = S.DRCTConfig(in_chans=1, img_size=64, window_size=8, upscale=2, n_rdg=1)
+    sd = S.synth_state(S.drct_spec(cfg), seed=31, gain=1.0, cfg=cfg)
+    x = torch.from_numpy(S.synth_image("sf", (2, 1, 64, 64), seed=3)).cuda()
+    hr = torch.from_numpy(S.synth_image("sf/hr", (2, 1, 128, 128), seed=4)).cuda()
+    m = build_train(cfg, sd, "bf16")
+    loss = F.l1_loss(m(x), hr)
+    with ops.path_override(unfused_blocks=True):
+        with pytest.raises(RuntimeError, match="must not change between the two"):
+            loss.backward()
+    torch.cuda.synchronize()
+    m = build_train(cfg, sd, "bf16")
+    F.l1_loss(m(x), hr).backward()
+    torch.cuda.synchronize()
+    g = m.flat_grads
+    assert bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0
+
+
 @pytest.mark.parametrize("prec", ["bf16", "fp32"])
 def test_graphed_train_step_matches_eager(sr_golden, prec):
     """The whole training step as one replayed hipGraph (two eager warm-up steps, then capture + replays) walks the
